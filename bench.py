@@ -12,6 +12,11 @@ is the same graph without it -- identical single-GPU numbers, 7/8 of all neighbo
                                                            its N rank processes itself, as children)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
+A plain run does only what the headline figure needs: set-up, W warm-up steps, EXACTLY K timed steps, the line.
+`--full` adds everything else this script measures or checks (timed windows, live kernel profiling and rooflines, whole
+epochs, the model-step legs, the CPU baseline, the exchange parity check); `--dump-outputs DIR` writes what the last
+timed step delivered.
+
 A "step" is one batch through the hot path.  N == 1: single-GPU iterator (FastSampler +
 DevicePrefetcher), all features in HBM.  N > 1: one process per GPU, replicated topology, features
 range-partitioned N ways with a VIP cache of remote rows (analytic model, 10 % of N/P), cache-miss
@@ -73,7 +78,14 @@ def parse():
     ap.add_argument("--windows", type=int, default=0,
                     help="timed windows of --steps steps run back to back, pipeline kept full in between; the "
                          "reported ms_per_step / value are the plain mean over the windows "
-                         "(0 = max(6, 2 * ceil(128 / steps)))")
+                         "(0 = one window, i.e. exactly --steps timed steps; with --full: max(6, 2 * ceil(128 / steps)))")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: several timed windows, live delivery / chain profiling and the "
+                         "roofline entries, the exchange parity check (N>1), whole epochs, the model-step legs, the CPU baseline "
+                         "and the opt-in --p2p-leg; without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one delivered (the PreparedBatch: x, y, every hop's CSR "
+                         "and sizes, the seed range) as DIR/<name>.npy in float32 / float64, at most 64 MB in all")
     ap.add_argument("--fanouts", default="",
                     help="comma-separated fan-outs instead of the workload's own (e.g. 20,20,20: the reference's batchwise "
                          "inference; a hop < 0 or > 32 takes the generic sampling path: one batch per launch, a host sync per hop)")
@@ -546,6 +558,36 @@ def cpu_baseline(wl_host, sizes, batch_size, seconds, threads):
             "batches_per_s": nb / dt}
 
 
+def dump_outputs(out_dir, batch, budget=60 << 20):           # (60 MiB of data: under 64 MB with the .npy headers)
+    """--dump-outputs: what a caller of the timed path received in the last timed step -- the PreparedBatch's features x,
+    labels y, every hop's CSR (rowptr, col) and size (S, T), its seed range -- as out_dir/<name>.npy: float32 for floating
+    point data up to 32 bits, float64 for the rest (node ids < 2**53 are exact).  Smallest first, every array gets an equal
+    share of the budget still left; one above its share is written as a fixed, seeded sample of its rows, the rows taken in
+    out_dir/<name>_rows.npy."""
+    import numpy as np
+    arrays = {"x": batch.x, "y": batch.y}
+    for i, adj in enumerate(batch.adjs):
+        rowptr, col, _ = adj.adj_t.csr()
+        arrays[f"adj{i}_rowptr"], arrays[f"adj{i}_col"] = rowptr, col
+        arrays[f"adj{i}_size"] = torch.tensor([int(v) for v in adj.size])
+    arrays["idx_range"] = torch.tensor([batch.idx_range.start, batch.idx_range.stop])
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    os.makedirs(out_dir, exist_ok=True)
+    left = budget
+    for k, name in enumerate(sorted(arrays, key=lambda k_: arrays[k_].numel())):
+        t = arrays[name]
+        share = left // (len(arrays) - k)
+        dtype = torch.float32 if t.dtype in (torch.float16, torch.bfloat16, torch.float32) else torch.float64
+        n = t.size(0) if t.dim() > 0 else 1
+        row_bytes = max(1, t[0].numel() if t.dim() > 1 and n > 0 else 1) * (4 if dtype == torch.float32 else 8)
+        left -= min(n * row_bytes, share)
+        if n * row_bytes > share:
+            rows = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:max(1, share // (row_bytes + 8))].sort().values
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.numpy().astype(np.float64))
+            t = t[rows.to(t.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.to(dtype).cpu().numpy())
+
+
 def _trace(msg):
     """progress markers on stderr (SPP_BENCH_TRACE=1): where a multi-rank run stops making progress"""
     if os.environ.get("SPP_BENCH_TRACE") == "1":
@@ -710,7 +752,7 @@ def main():
         if world > 1 and native and rccl_world != world:
             raise SystemExit(f"bench.py --gpus {a.gpus}: the native exchange communicator spans {rccl_world} ranks, "
                              f"the process group {world}")
-        if native and not a.no_verify:
+        if native and a.full and not a.no_verify:
             import dataclasses
             n_check = min(8, max(1, n_local // bs))
             vcfg = dataclasses.replace(cfg, idx=get_idx()[:n_check * bs].contiguous(), exact_num_batches=n_check)
@@ -758,14 +800,15 @@ def main():
     torch.cuda.synchronize()
     # live HIP-event timing of the delivery launches: every launch with group delivery (one per sampling group), every 8th
     # with per-batch delivery (the two timing events around EVERY ~100 us launch cost the delivery queue ~7 us each time)
+    # (--full only: a plain run does not pay for them)
     prof_every = 1 if os.environ.get("SPP_GROUP_DELIVERY", "0") != "0" else 8
-    L.spp_profile_enable(0 if os.environ.get("SPP_BENCH_NO_PROF") == "1" else prof_every)
+    L.spp_profile_enable(prof_every if a.full and os.environ.get("SPP_BENCH_NO_PROF") != "1" else 0)
     # R windows of EXACTLY K steps each, every one bracketed by barrier + synchronize on both sides (the
     # closing bracket of a window is the opening bracket of the next, so the sampler's slots stay full
     # in between).  A single 20-step window is ~3 ms: its closing synchronize also waits for the refill
     # chains the sampler has in flight, which makes one short window noisy.  Reported: the mean over the windows (see
-    # below for the one guard); every window is in the line.
-    R = a.windows if a.windows > 0 else max(6, 2 * -(-128 // max(1, a.steps)))
+    # below for the one guard); every window is in the line.  A plain run times one window: exactly K steps.
+    R = a.windows if a.windows > 0 else (max(6, 2 * -(-128 // max(1, a.steps))) if a.full else 1)
     xb0 = feeder.exchange_bytes()
     dev_allocs0 = int(torch.cuda.memory_stats(dev).get("num_device_alloc", 0))
     if os.environ.get("SPP_BENCH_STALL_DUMP"):        # diagnostic: Python stacks of all threads every N seconds of the timed region
@@ -819,9 +862,10 @@ def main():
         groups_per_window.append(fs.groups_opened() - g0)
         # (outside the window's clock) the delivery launches timed so far: per-window in-situ duration of the dominant kernel,
         # which tells a slow window of the GPU (longer launches) from one of the host or the queue (same launches, more gaps)
-        _ms, _n, _u = C.c_double(0), C.c_int64(0), C.c_int64(0)
-        nat.check(L.spp_profile_read(1 if (distributed and not native) else 0, C.byref(_ms), C.byref(_n), C.byref(_u)))
-        prof_cum.append((_ms.value, _n.value))
+        if a.full:
+            _ms, _n, _u = C.c_double(0), C.c_int64(0), C.c_int64(0)
+            nat.check(L.spp_profile_read(1 if (distributed and not native) else 0, C.byref(_ms), C.byref(_n), C.byref(_u)))
+            prof_cum.append((_ms.value, _n.value))
     xb1 = feeder.exchange_bytes()
     dev_allocs_timed = int(torch.cuda.memory_stats(dev).get("num_device_alloc", 0)) - dev_allocs0
     if os.environ.get("SPP_BENCH_STALL_DUMP"):
@@ -836,6 +880,8 @@ def main():
     ch_ms, ch_n, ch_batches = C.c_double(0), C.c_int64(0), C.c_int64(0)
     nat.check(L.spp_profile_read(2, C.byref(ch_ms), C.byref(ch_n), C.byref(ch_batches)))
     L.spp_profile_enable(0)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, b)       # the last timed step's batch
 
     stats = torch.tensor(win, dtype=torch.float64, device=dev)      # [R, 3]
     if distributed:
@@ -877,95 +923,98 @@ def main():
         if a.workload in LOCALITY:
             locality_note = f" (planted {LOCALITY[a.workload][0]}-block locality, {LOCALITY[a.workload][1]:.0%} intra-block edges)"
         if rank == 0:
-            # dominant HBM kernel: the feature-row gather (x rows dominate: y rows are 8 B each)
-            row_bytes = F * 2
-            # read row + write row + the index (int64 at the boundary); the assembly of the partitioned path
-            # reads an 8-byte {bucket, row} record and the row's own address instead: + 12
-            alg_bytes_per_row = 2 * row_bytes + (12 if distributed else 8)
-            # One profiled launch per batch.  N == 1: the fused delivery kernel (x-row gather + the small
-            # label gather and int64 widening of the MFG, which are charged to the gather's time but not
-            # to its bytes: conservative).  N > 1: the fused assembly kernel.
-            x_rows = rows.value
-            x_ms = ms.value
-            launches_x = n_launch.value
-            achieved = (x_rows * alg_bytes_per_row) / (x_ms * 1e-3) / 1e9 if x_ms > 0 else 0.0
-            roof = {"bound": "hbm", "kernel": "k_assemble" if prof_kind == 1 else
-                    ("k_deliver (assemble from local/received/cache rows)" if distributed else "k_deliver (gather_rows_body)"),
-                    "achieved": achieved, "peak": HBM_PEAK_GBS,
-                    "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": None,
-                    "avg_launch_ms": x_ms / max(1, launches_x), "launches": launches_x,
-                    "algorithmic_bytes_per_row": alg_bytes_per_row, "rows_per_launch": x_rows / max(1, launches_x)}
-            # HBM traffic of the same kernel from the PMC passes kept under profiles/ (FETCH_SIZE and
-            # WRITE_SIZE in separate rocprofv3 runs, corrected on a known-bytes launch of this access width)
-            # (the partitioned path's delivery -- assembly from {local, received, cache} rows -- has a pass of its own)
-            import glob
-            prof_dir = os.path.join(ROOT, "profiles")
+            # the rooflines: live kernel timings of the timed windows (--full only) against the algorithmic bytes
+            roof = roof_s = roof_p = None
+            if a.full:
+                # dominant HBM kernel: the feature-row gather (x rows dominate: y rows are 8 B each)
+                row_bytes = F * 2
+                # read row + write row + the index (int64 at the boundary); the assembly of the partitioned path
+                # reads an 8-byte {bucket, row} record and the row's own address instead: + 12
+                alg_bytes_per_row = 2 * row_bytes + (12 if distributed else 8)
+                # One profiled launch per batch.  N == 1: the fused delivery kernel (x-row gather + the small
+                # label gather and int64 widening of the MFG, which are charged to the gather's time but not
+                # to its bytes: conservative).  N > 1: the fused assembly kernel.
+                x_rows = rows.value
+                x_ms = ms.value
+                launches_x = n_launch.value
+                achieved = (x_rows * alg_bytes_per_row) / (x_ms * 1e-3) / 1e9 if x_ms > 0 else 0.0
+                roof = {"bound": "hbm", "kernel": "k_assemble" if prof_kind == 1 else
+                        ("k_deliver (assemble from local/received/cache rows)" if distributed else "k_deliver (gather_rows_body)"),
+                        "achieved": achieved, "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": None,
+                        "avg_launch_ms": x_ms / max(1, launches_x), "launches": launches_x,
+                        "algorithmic_bytes_per_row": alg_bytes_per_row, "rows_per_launch": x_rows / max(1, launches_x)}
+                # HBM traffic of the same kernel from the PMC passes kept under profiles/ (FETCH_SIZE and
+                # WRITE_SIZE in separate rocprofv3 runs, corrected on a known-bytes launch of this access width)
+                # (the partitioned path's delivery -- assembly from {local, received, cache} rows -- has a pass of its own)
+                import glob
+                prof_dir = os.path.join(ROOT, "profiles")
 
-            def newest_first(pattern):
-                return tuple(os.path.basename(f) for f in sorted(glob.glob(os.path.join(prof_dir, pattern)), reverse=True))
-            pmc_files = newest_first("r0?_deliver_partitioned_pmc.json") if distributed else \
-                newest_first("r0?_deliver_pmc_*.json") + newest_first("r0?_gather_pmc_papers.json") + newest_first("r0?_gather_pmc.json")
-            for pmc_name in pmc_files:
-                pmc_path = os.path.join(ROOT, "profiles", pmc_name)
-                if (distributed and not native) or not os.path.exists(pmc_path):
-                    continue
-                pmc = json.load(open(pmc_path))
-                if pmc["shape"]["row_bytes"] == row_bytes:
-                    roof["traffic"] = pmc["traffic_bytes_per_row"] * roof["rows_per_launch"]
-                    roof["traffic_source"] = (f"profiles/{pmc_name}: PMC bytes/row of this kernel from an earlier rocprofv3 "
-                                              f"--pmc pass (NOT measured in this run) x this run's rows/launch")
-                    roof["algorithmic_bytes_per_launch"] = alg_bytes_per_row * roof["rows_per_launch"]
-                    break
-            # The sampler (roofline per kernel family).  Algorithmic bytes of the batches this rank consumed in the
-            # timed region / their number = per batch; time = the in-situ span of a chain (all hops of a group of batches, first
-            # launch to last on its sampling stream, beside the delivery kernel and the chain of the other sampling stream)
-            # / the batches of the group.  traffic: per batch, from the last committed PMC passes over this command.
-            roof_s = None
-            if ch_n.value > 0 and ch_ms.value > 0:
-                alg_pb = chain_alg_bytes / max(1, a.steps * R)
-                span_pb = ch_ms.value / max(1, ch_batches.value)                 # ms of chain span per batch
-                ach = alg_pb / (span_pb * 1e-3) / 1e9
-                roof_s = {"bound": "hbm", "kernel": "sampling chain (k_seed_init, k_hop_count/pick, k_bucket_*, k_hop_flag/rows; all hops)",
-                          "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": None,
-                          "algorithmic_bytes_per_batch": alg_pb, "chain_span_ms_per_batch": span_pb,
-                          "avg_chain_span_ms": ch_ms.value / ch_n.value, "batches_per_chain": ch_batches.value / ch_n.value,
-                          "chains_timed": ch_n.value,
-                          "note": "in-situ span on the chain's own stream: the chains of two slot-sets run concurrently on two sampling "
-                                  "streams beside the delivery kernel, so spans overlap (the per-batch cost in the step is smaller than the span)"}
-                pmc_txt = sorted(glob.glob(os.path.join(ROOT, "profiles", "r0?_partitioned_pmc_traffic_per_kernel.txt" if distributed
-                                                        else "r0?_pipeline_pmc_traffic_per_kernel.txt")))
-                # (the committed passes are of S-papers with its own fan-outs: any other workload keeps "traffic": null)
-                if pmc_txt and a.workload == "S-papers" and not a.fanouts:
-                    mb = 0.0
-                    for ln in open(pmc_txt[-1]):
-                        f_ = ln.split()
-                        if ln.startswith("spp::") and "k_deliver" not in ln and len(f_) >= 4:
-                            mb += float(f_[-3]) + float(f_[-2])
-                    if mb > 0:
-                        roof_s["traffic"] = mb * 1e6
-                        roof_s["traffic_source"] = (f"profiles/{os.path.basename(pmc_txt[-1])}: fetch + write MB per batch of the chain's kernels from "
-                                                    f"earlier rocprofv3 --pmc passes over this command (NOT measured in this run)")
-            if roof_s is not None and not distributed:
-                # context for the in-situ span: the chain ALONE on the GPU (two sampling streams, no deliveries), from the
-                # committed sampling-only run of this workload's default configuration -- not measured in this run
-                lone = sorted(glob.glob(os.path.join(ROOT, "profiles", "r0?_chain_only_trace_report.txt")))
-                if lone and a.workload == "S-papers" and not a.fanouts:
-                    import re
-                    m_ = re.search(r"chain only: .*?([0-9.]+) us/batch", open(lone[-1]).read())
-                    if m_:
-                        us = float(m_.group(1))
-                        roof_s["lone_chain"] = {"us_per_batch": us, "achieved_GBps_algorithmic": roof_s["algorithmic_bytes_per_batch"] / us / 1e3,
-                                                "achieved_GBps_traffic": (roof_s["traffic"] / us / 1e3) if roof_s["traffic"] else None,
-                                                "source": f"profiles/{os.path.basename(lone[-1])} (tools/microbench.py chain; NOT measured in this run)"}
-            # the step as a whole against the memory system: the HBM traffic of one batch (delivery + chain, from the committed PMC
-            # passes over this command) over the measured step
-            roof_p = None
-            if roof.get("traffic") and roof_s is not None and roof_s.get("traffic") and not distributed:
-                tot = roof["traffic"] + roof_s["traffic"]
-                ach = tot / (dt / a.steps) / 1e9
-                roof_p = {"bound": "hbm", "what": "the whole step: counter traffic of one batch's delivery + sampling chain over ms_per_step",
-                          "traffic_bytes_per_batch": tot, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                          "traffic_source": "profiles/ PMC passes (NOT measured in this run) x this run's step"}
+                def newest_first(pattern):
+                    return tuple(os.path.basename(f) for f in sorted(glob.glob(os.path.join(prof_dir, pattern)), reverse=True))
+                pmc_files = newest_first("r0?_deliver_partitioned_pmc.json") if distributed else \
+                    newest_first("r0?_deliver_pmc_*.json") + newest_first("r0?_gather_pmc_papers.json") + newest_first("r0?_gather_pmc.json")
+                for pmc_name in pmc_files:
+                    pmc_path = os.path.join(ROOT, "profiles", pmc_name)
+                    if (distributed and not native) or not os.path.exists(pmc_path):
+                        continue
+                    pmc = json.load(open(pmc_path))
+                    if pmc["shape"]["row_bytes"] == row_bytes:
+                        roof["traffic"] = pmc["traffic_bytes_per_row"] * roof["rows_per_launch"]
+                        roof["traffic_source"] = (f"profiles/{pmc_name}: PMC bytes/row of this kernel from an earlier rocprofv3 "
+                                                  f"--pmc pass (NOT measured in this run) x this run's rows/launch")
+                        roof["algorithmic_bytes_per_launch"] = alg_bytes_per_row * roof["rows_per_launch"]
+                        break
+                # The sampler (roofline per kernel family).  Algorithmic bytes of the batches this rank consumed in the
+                # timed region / their number = per batch; time = the in-situ span of a chain (all hops of a group of batches, first
+                # launch to last on its sampling stream, beside the delivery kernel and the chain of the other sampling stream)
+                # / the batches of the group.  traffic: per batch, from the last committed PMC passes over this command.
+                roof_s = None
+                if ch_n.value > 0 and ch_ms.value > 0:
+                    alg_pb = chain_alg_bytes / max(1, a.steps * R)
+                    span_pb = ch_ms.value / max(1, ch_batches.value)                 # ms of chain span per batch
+                    ach = alg_pb / (span_pb * 1e-3) / 1e9
+                    roof_s = {"bound": "hbm", "kernel": "sampling chain (k_seed_init, k_hop_count/pick, k_bucket_*, k_hop_flag/rows; all hops)",
+                              "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": None,
+                              "algorithmic_bytes_per_batch": alg_pb, "chain_span_ms_per_batch": span_pb,
+                              "avg_chain_span_ms": ch_ms.value / ch_n.value, "batches_per_chain": ch_batches.value / ch_n.value,
+                              "chains_timed": ch_n.value,
+                              "note": "in-situ span on the chain's own stream: the chains of two slot-sets run concurrently on two sampling "
+                                      "streams beside the delivery kernel, so spans overlap (the per-batch cost in the step is smaller than the span)"}
+                    pmc_txt = sorted(glob.glob(os.path.join(ROOT, "profiles", "r0?_partitioned_pmc_traffic_per_kernel.txt" if distributed
+                                                            else "r0?_pipeline_pmc_traffic_per_kernel.txt")))
+                    # (the committed passes are of S-papers with its own fan-outs: any other workload keeps "traffic": null)
+                    if pmc_txt and a.workload == "S-papers" and not a.fanouts:
+                        mb = 0.0
+                        for ln in open(pmc_txt[-1]):
+                            f_ = ln.split()
+                            if ln.startswith("spp::") and "k_deliver" not in ln and len(f_) >= 4:
+                                mb += float(f_[-3]) + float(f_[-2])
+                        if mb > 0:
+                            roof_s["traffic"] = mb * 1e6
+                            roof_s["traffic_source"] = (f"profiles/{os.path.basename(pmc_txt[-1])}: fetch + write MB per batch of the chain's kernels from "
+                                                        f"earlier rocprofv3 --pmc passes over this command (NOT measured in this run)")
+                if roof_s is not None and not distributed:
+                    # context for the in-situ span: the chain ALONE on the GPU (two sampling streams, no deliveries), from the
+                    # committed sampling-only run of this workload's default configuration -- not measured in this run
+                    lone = sorted(glob.glob(os.path.join(ROOT, "profiles", "r0?_chain_only_trace_report.txt")))
+                    if lone and a.workload == "S-papers" and not a.fanouts:
+                        import re
+                        m_ = re.search(r"chain only: .*?([0-9.]+) us/batch", open(lone[-1]).read())
+                        if m_:
+                            us = float(m_.group(1))
+                            roof_s["lone_chain"] = {"us_per_batch": us, "achieved_GBps_algorithmic": roof_s["algorithmic_bytes_per_batch"] / us / 1e3,
+                                                    "achieved_GBps_traffic": (roof_s["traffic"] / us / 1e3) if roof_s["traffic"] else None,
+                                                    "source": f"profiles/{os.path.basename(lone[-1])} (tools/microbench.py chain; NOT measured in this run)"}
+                # the step as a whole against the memory system: the HBM traffic of one batch (delivery + chain, from the committed PMC
+                # passes over this command) over the measured step
+                roof_p = None
+                if roof.get("traffic") and roof_s is not None and roof_s.get("traffic") and not distributed:
+                    tot = roof["traffic"] + roof_s["traffic"]
+                    ach = tot / (dt / a.steps) / 1e9
+                    roof_p = {"bound": "hbm", "what": "the whole step: counter traffic of one batch's delivery + sampling chain over ms_per_step",
+                              "traffic_bytes_per_batch": tot, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+                              "traffic_source": "profiles/ PMC passes (NOT measured in this run) x this run's step"}
             out = {
                 "metric": "sampled_edges_per_sec", "value": edges / dt, "unit": "sampled-edges/s",
                 "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3,
@@ -991,8 +1040,9 @@ def main():
                             "opens_two_groups": [k for k, n_ in enumerate(groups_per_window) if n_ >= 2],
                             # in-situ duration of the timed delivery launches of each window (rank 0; live HIP events)
                             "deliver_us_all": [round(1e3 * (b[0] - a_[0]) / max(1, b[1] - a_[1]), 1)
-                                               for a_, b in zip([(0.0, 0)] + prof_cum[:-1], prof_cum)]},
+                                               for a_, b in zip([(0.0, 0)] + prof_cum[:-1], prof_cum)] if a.full else None},
                 "timed_region_s": timed_total_s,          # all R windows (also under "windows")
+                "full": a.full,                           # --full: the legs and figures below that are null without it
             "optional_legs_timed_out": legs_state["partial"],   # N > 1 only: the watchdog printed this line
                 "host": {"cpu_cores_flag": a.cpu_cores, "affinity_cores": len(os.sched_getaffinity(0)), "cpu_share": host_cpu_share()},
                 "hbm": None if legs_state["partial"] else
@@ -1040,7 +1090,7 @@ def main():
                 out["exchange_p2p"] = p2p_out
             if model_out is not None:
                 out.update(model_out)
-            if not a.no_cpu_baseline and not distributed:
+            if a.full and not a.no_cpu_baseline and not distributed:
                 threads = host_cpu_share()
                 host = (wl.rowptr.cpu(), wl.col.cpu(), wl.x.cpu(), wl.y.cpu(), shuffler.get_idx().cpu())
                 out["cpu_baseline"] = cpu_baseline(host, sizes, bs, a.cpu_seconds, threads)
@@ -1050,11 +1100,11 @@ def main():
             sys.stdout.flush()
             os.write(line_fd, (json.dumps(out) + "\n").encode())
 
-    # N > 1: the legs below are optional extras behind the measured windows, and every one of them is a sequence of
+    # N > 1: the legs below (--full) are optional extras behind the measured windows, and every one of them is a sequence of
     # collectives -- a rank that falls out of step would hang the others, and the line (printed last) with it.  A watchdog
     # prints the line with what has been measured so far (`optional_legs_timed_out`) and ends the process.
     watchdog = None
-    if distributed:
+    if distributed and a.full:
         import threading
 
         def _deadline():
@@ -1085,14 +1135,14 @@ def main():
     sess0 = getattr(getattr(feeder.devit, "it", None), "session", None)
     sinfo = sess0.sampler_info() if sess0 is not None else {}
     del sess0        # (a live reference would keep the Session, and with it the pooled sampler, away from the next one)
-    if a.epochs > 0:
+    if a.full and a.epochs > 0:
         if distributed:
             feeder.quiesce()
         feeder.devit = None                      # the windows' Session ends; its pooled sampler serves the epochs' Sessions
         gc.collect()
         _trace("measuring whole epochs (data path alone)")
         epoch_measured = {"data_path_only": run_epochs(make_iter)}
-    if not a.no_model_step:
+    if a.full and not a.no_model_step:
         try:
             if distributed:
                 feeder.quiesce()
@@ -1198,7 +1248,7 @@ def main():
             model_out = {"model_step": {"error": repr(e)}}
     # ---- opt-in second leg: the same partitioned workload over the P2P transport ----
     p2p_out = None
-    if distributed and a.p2p_leg:
+    if distributed and a.full and a.p2p_leg:
         feeder.quiesce()
         feeder.devit = None
         gc.collect()

@@ -3,7 +3,8 @@
 The single-GPU path and the partitioned path (RCCL communicator at world size 1, bucketing, native exchange, assembly, the
 model-step leg under DistributedDataParallel with consumer-issued exchanges) run as the driver runs them -- a child process,
 one JSON line on stdout -- on the small S-arxiv workload with a handful of steps (two windows of 24: three sampling
-groups, so that the sampler's roofline entry has chains to time)."""
+groups, so that the sampler's roofline entry has chains to time), all of it with --full; and the plain line, which times
+exactly the steps asked for, with the outputs it dumps."""
 import json
 import os
 import subprocess
@@ -16,17 +17,21 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
 
-def _run(extra, more_env=None):
+def _bench(args, more_env=None):
     env = dict(os.environ)
     env.update(more_env or {})
     env.setdefault("MASTER_PORT", "29741")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "S-arxiv", "--steps", "24", "--warmup", "2",
-                        "--windows", "2", "--prime", "8", "--cpu-seconds", "1"] + extra, env=env, capture_output=True, text=True,
-                       timeout=600, cwd=ROOT)
+                        "--prime", "8"] + args, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-2000:]          # ONE JSON line
     return json.loads(lines[0])
+
+
+def _run(extra, more_env=None):
+    """--full: the windows, rooflines, legs and CPU baseline checked below live behind it"""
+    return _bench(["--full", "--windows", "2", "--cpu-seconds", "1"] + extra, more_env)
 
 
 def _check_common(d, n_gpus):
@@ -134,3 +139,31 @@ def test_partitioned_line_survives_an_optional_leg_that_never_returns():
     d = _run(["--gpus", "1", "--force-distributed", "--no-cpu-baseline"], {"SPP_BENCH_LEG_TIMEOUT_S": "0.2"})
     assert d["optional_legs_timed_out"] is True and d["value"] > 0 and d["ms_per_step"] > 0 and d["roofline"]["frac"] > 0
     assert "range-partitioned" in d["config"]["parallelism"]
+
+
+def test_plain_line_times_exactly_the_steps_asked_for_and_dumps_the_last_batch(tmp_path):
+    """without --full: one window of exactly --steps steps, none of the legs; --dump-outputs writes the last timed batch
+    (float32 / float64, within 64 MB), the same from run to run"""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        d = _bench(["--dump-outputs", str(out)])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in d, key
+        assert d["full"] is False and d["steps"] == 24 and d["warmup"] == 2 and d["windows"]["n"] == 1
+        assert abs(d["ms_per_step"] * 1e-3 * 24 - d["timed_region_s"]) <= 1e-6 + 1e-3 * d["timed_region_s"]
+        assert d["value"] > 0 and d["roofline"] is None and d["epoch_measured"] is None
+        assert "model_step" not in d and "cpu_baseline" not in d
+        files = {f.name: np.load(f) for f in sorted(out.iterdir())}
+        assert sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20
+        for name in ("x.npy", "y.npy", "idx_range.npy", "adj0_rowptr.npy", "adj0_col.npy", "adj0_size.npy"):
+            assert name in files, name
+        assert all(v.dtype in (np.float32, np.float64) for v in files.values())
+        assert files["x.npy"].dtype == np.float32 and files["x.npy"].shape[1] == 128
+        lo, hi = files["idx_range.npy"]
+        assert files["y.npy"].shape == (hi - lo,)
+        dumps.append(files)
+    assert dumps[0].keys() == dumps[1].keys()
+    for name in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][name], dumps[1][name], err_msg=name)

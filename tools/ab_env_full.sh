@@ -10,7 +10,7 @@ for v in $A $B; do
   env $VAR=$v WL=S-papers CHAIN_CFG=64,16 timeout -k 10 200 python tools/microbench.py chain 2>&1 | grep "chain only"
   env $VAR=$v SPP_WORK_STREAMS=1 WL=S-papers CHAIN_CFG=64,16 timeout -k 10 200 python tools/microbench.py chain 2>&1 | grep "chain only" | sed 's/^/  one stream: /'
   for K in 192 20; do
-    env $VAR=$v timeout -k 10 300 python bench.py --steps $K --warmup 5 --no-cpu-baseline --no-model-step > $OUT/bench_${v}_k${K}_$rep.json 2> $OUT/bench_${v}_k${K}_$rep.err || { tail -5 $OUT/bench_${v}_k${K}_$rep.err; exit 1; }
+    env $VAR=$v timeout -k 10 300 python bench.py --full --steps $K --warmup 5 --no-cpu-baseline --no-model-step > $OUT/bench_${v}_k${K}_$rep.json 2> $OUT/bench_${v}_k${K}_$rep.err || { tail -5 $OUT/bench_${v}_k${K}_$rep.err; exit 1; }
     python - $OUT/bench_${v}_k${K}_$rep.json $K <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

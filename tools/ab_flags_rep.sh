@@ -12,7 +12,7 @@ for r in $(seq 1 $reps); do
     f="$fl"; [ "$fl" = "-" ] && f=""
     SPP_EXTRA_FLAGS="$f" python3 -m salient_plusplus_amd.build > /dev/null 2>&1 || { echo "build with '$fl' failed" >> "$out"; continue; }
     ( for kv in $envs; do export "$kv"; done
-      SPP_EXTRA_FLAGS="$f" timeout -k 10 300 python3 bench.py $args --no-cpu-baseline --no-model-step 2>/dev/null | python3 -c "
+      SPP_EXTRA_FLAGS="$f" timeout -k 10 300 python3 bench.py --full $args --no-cpu-baseline --no-model-step 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('cfg$k rep$r [$spec]', 'ms_per_step', round(d['ms_per_step'],4), 'deliver_us', round(d['roofline']['avg_launch_ms']*1e3,1))" ) >> "$out" 2>&1

@@ -13,7 +13,7 @@ for r in $(seq 1 $reps); do
   for v in "$@"; do
     k=$((k+1))
     cp "$v" "$lib" || continue
-    ( timeout -k 10 300 python3 bench.py $args --no-cpu-baseline --no-model-step 2>/dev/null | python3 -c "
+    ( timeout -k 10 300 python3 bench.py --full $args --no-cpu-baseline --no-model-step 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('cfg$k rep$r [$(basename $v)]', 'ms_per_step', round(d['ms_per_step'],4), 'deliver_us', round(d['roofline']['avg_launch_ms']*1e3,1))"

@@ -9,7 +9,7 @@ for r in $(seq 1 $reps); do
   for envs in "$@"; do
     k=$((k+1))
     ( for kv in $envs; do export "$kv"; done
-      timeout -k 10 400 python3 bench.py $args $BENCH_EXTRA --no-cpu-baseline 2>/dev/null | python3 -c "
+      timeout -k 10 400 python3 bench.py --full $args $BENCH_EXTRA --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 m=d['model_step']

@@ -10,7 +10,7 @@ for r in $(seq 1 $reps); do
   for envs in "$@"; do
     k=$((k+1))
     ( for kv in $envs; do export "$kv"; done
-      timeout -k 10 300 python3 bench.py $args --no-cpu-baseline --no-model-step 2>/dev/null | python3 -c "
+      timeout -k 10 300 python3 bench.py --full $args --no-cpu-baseline --no-model-step 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 w=d['windows']['ms_per_step_all']

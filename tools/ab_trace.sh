@@ -6,7 +6,7 @@ out=$1; tag=$2; shift 2
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p "$out"
 for kv in "$@"; do export "$kv"; done
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$out" -o "$tag" -- python3 bench.py --no-cpu-baseline --no-model-step > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err" || exit 1
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$out" -o "$tag" -- python3 bench.py --full --no-cpu-baseline --no-model-step > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err" || exit 1
 f=$(find "$out" -name "${tag}_kernel_trace.csv" | head -1)
 python3 tools/trace_report.py "$f" 128 > "$out/${tag}_trace_report.txt"
 rm -f "$f" "$out/${tag}_agent_info.csv" "$out/${tag}_domain_stats.csv"

@@ -14,7 +14,7 @@ for r in $(seq 1 $rounds); do
     cp "$keep"/* salient_plusplus_amd/csrc/
     [ -d ".abt/$v" ] && cp .abt/$v/* salient_plusplus_amd/csrc/
     python3 -m salient_plusplus_amd.build > /dev/null 2>&1 || { echo "build of $v failed" >> "$out"; continue; }
-    timeout -k 10 400 python3 bench.py $args --no-cpu-baseline 2>/dev/null | python3 -c "
+    timeout -k 10 400 python3 bench.py --full $args --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); m=d.get('model_step') or {}
 print('round $r variant $v:', 'ms_per_step', round(d['ms_per_step'],4), 'deliver_us', round(d['roofline']['avg_launch_ms']*1e3,1), 'model only', m.get('ms_per_step_model_only_resident_batch'), 'with data path', m.get('ms_per_step_with_data_path'))" >> "$out"

@@ -3,8 +3,8 @@
 # the partitioned path with the DDP model-step leg, confined to 2 / 4 cores and unconfined; then the single-GPU path
 OUT=${1:-gpurun_out/r5h}; mkdir -p $OUT
 for cores in 0 2 4; do
-  python bench.py --gpus 1 --force-distributed --steps 20 --warmup 5 --no-cpu-baseline --cpu-cores $cores > $OUT/host_budget_dist_cores$cores.json 2> $OUT/host_budget_dist_cores$cores.err || tail -5 $OUT/host_budget_dist_cores$cores.err
-  python bench.py --steps 20 --warmup 5 --no-cpu-baseline --cpu-cores $cores > $OUT/host_budget_single_cores$cores.json 2> $OUT/host_budget_single_cores$cores.err || tail -5 $OUT/host_budget_single_cores$cores.err
+  python bench.py --full --gpus 1 --force-distributed --steps 20 --warmup 5 --no-cpu-baseline --cpu-cores $cores > $OUT/host_budget_dist_cores$cores.json 2> $OUT/host_budget_dist_cores$cores.err || tail -5 $OUT/host_budget_dist_cores$cores.err
+  python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --cpu-cores $cores > $OUT/host_budget_single_cores$cores.json 2> $OUT/host_budget_single_cores$cores.err || tail -5 $OUT/host_budget_single_cores$cores.err
   python - $OUT/host_budget_dist_cores$cores.json $OUT/host_budget_single_cores$cores.json $cores <<'PY'
 import json,sys
 for f in sys.argv[1:3]:

@@ -7,8 +7,8 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p "$out"
 for kv in "$@"; do export "$kv"; done
 ARGS="--steps 48 --warmup 8 --prime 8 --no-cpu-baseline --no-model-step $EXTRA_ARGS"   # EXTRA_ARGS="--gpus 1 --force-distributed": the partitioned path
-timeout -k 10 500 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out" -o "${tag}_fetch" -- python3 bench.py $ARGS > /dev/null 2> "$out/${tag}_fetch.err" || exit 1
-timeout -k 10 500 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$out" -o "${tag}_write" -- python3 bench.py $ARGS > /dev/null 2> "$out/${tag}_write.err" || exit 1
+timeout -k 10 500 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out" -o "${tag}_fetch" -- python3 bench.py --full $ARGS > /dev/null 2> "$out/${tag}_fetch.err" || exit 1
+timeout -k 10 500 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$out" -o "${tag}_write" -- python3 bench.py --full $ARGS > /dev/null 2> "$out/${tag}_write.err" || exit 1
 f=$(find "$out" -name "${tag}_fetch_counter_collection.csv" | head -1)
 w=$(find "$out" -name "${tag}_write_counter_collection.csv" | head -1)
 # batches delivered = k_deliver launches (+ G per group launch); batches sampled = k_seed_init launches x G (G = batches per sampling launch)

@@ -13,13 +13,13 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p "$out"
 set -x
 if want 1; then
-timeout -k 10 400 python3 bench.py > "$out/${tag}_bench_papers.json" 2> "$out/bench.err" || exit 1
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-model-step --no-cpu-baseline > "$out/${tag}_bench_papers_steps20.json" 2>> "$out/bench.err" || exit 1
-timeout -k 10 300 python3 bench.py --workload S-products --no-cpu-baseline --no-model-step > "$out/${tag}_bench_products.json" 2>> "$out/bench.err" || exit 1
-timeout -k 10 300 python3 bench.py --gpus 1 --force-distributed --no-cpu-baseline --no-model-step > "$out/${tag}_bench_papers_force_distributed.json" 2>> "$out/bench.err" || exit 1
+timeout -k 10 400 python3 bench.py --full > "$out/${tag}_bench_papers.json" 2> "$out/bench.err" || exit 1
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-model-step --no-cpu-baseline > "$out/${tag}_bench_papers_steps20.json" 2>> "$out/bench.err" || exit 1
+timeout -k 10 300 python3 bench.py --full --workload S-products --no-cpu-baseline --no-model-step > "$out/${tag}_bench_products.json" 2>> "$out/bench.err" || exit 1
+timeout -k 10 300 python3 bench.py --full --gpus 1 --force-distributed --no-cpu-baseline --no-model-step > "$out/${tag}_bench_papers_force_distributed.json" 2>> "$out/bench.err" || exit 1
 # kernel statistics + timeline of the default command (model step, CPU leg and the whole-epoch legs off: the statistics
 # then cover priming + warm-up + the timed windows, the launches the line's live HIP-event timing samples)
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$out" -o "${tag}_bench_papers" -- python3 bench.py --no-cpu-baseline --no-model-step --epochs 0 > "$out/prof_bench.json" 2>> "$out/bench.err" || exit 1
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$out" -o "${tag}_bench_papers" -- python3 bench.py --full --no-cpu-baseline --no-model-step --epochs 0 > "$out/prof_bench.json" 2>> "$out/bench.err" || exit 1
 f=$(find "$out" -name "${tag}_bench_papers_kernel_trace.csv" | head -1)
 python3 tools/trace_report.py "$f" 192 > "$out/${tag}_pipeline_trace_report.txt"
 rm -f "$f" "$out"/${tag}_bench_papers_agent_info.csv "$out"/${tag}_bench_papers_domain_stats.csv
@@ -53,13 +53,13 @@ ls -la "$out"
 if want 4; then
 # the other workloads and legs DESIGN.md quotes (one line each)
 set -x
-timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$out/${tag}_bench_papers_driver_command.json" 2>> "$out/bench.err" || exit 1
-timeout -k 10 300 python3 bench.py --workload S-arxiv --no-cpu-baseline --no-model-step > "$out/${tag}_bench_arxiv.json" 2>> "$out/bench.err" || exit 1
-timeout -k 10 300 python3 bench.py --workload S-mag --no-cpu-baseline --no-model-step > "$out/${tag}_bench_mag.json" 2>> "$out/bench.err" || exit 1
-timeout -k 10 400 python3 bench.py --model gat --no-cpu-baseline > "$out/${tag}_bench_papers_gat.json" 2>> "$out/bench.err" || exit 1
-timeout -k 10 400 python3 bench.py --gpus 1 --force-distributed --steps 20 --warmup 5 --no-cpu-baseline > "$out/${tag}_bench_papers_force_distributed_ddp.json" 2>> "$out/bench.err" || exit 1
-SPP_GROUP_DELIVERY=1 timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-model-step > "$out/${tag}_bench_papers_group_delivery.json" 2>> "$out/bench.err" || exit 1
-SPP_GROUP_DELIVERY=1 timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-model-step > "$out/${tag}_bench_papers_steps20_group_delivery.json" 2>> "$out/bench.err" || exit 1
+timeout -k 10 400 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > "$out/${tag}_bench_papers_driver_command.json" 2>> "$out/bench.err" || exit 1
+timeout -k 10 300 python3 bench.py --full --workload S-arxiv --no-cpu-baseline --no-model-step > "$out/${tag}_bench_arxiv.json" 2>> "$out/bench.err" || exit 1
+timeout -k 10 300 python3 bench.py --full --workload S-mag --no-cpu-baseline --no-model-step > "$out/${tag}_bench_mag.json" 2>> "$out/bench.err" || exit 1
+timeout -k 10 400 python3 bench.py --full --model gat --no-cpu-baseline > "$out/${tag}_bench_papers_gat.json" 2>> "$out/bench.err" || exit 1
+timeout -k 10 400 python3 bench.py --full --gpus 1 --force-distributed --steps 20 --warmup 5 --no-cpu-baseline > "$out/${tag}_bench_papers_force_distributed_ddp.json" 2>> "$out/bench.err" || exit 1
+SPP_GROUP_DELIVERY=1 timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-model-step > "$out/${tag}_bench_papers_group_delivery.json" 2>> "$out/bench.err" || exit 1
+SPP_GROUP_DELIVERY=1 timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-model-step > "$out/${tag}_bench_papers_steps20_group_delivery.json" 2>> "$out/bench.err" || exit 1
 fi
 set +x
 ls -la "$out"

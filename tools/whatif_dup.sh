@@ -5,7 +5,7 @@ K=${K:-192}
 for rep in 1 2; do
 for dup in none count pick flag rows "count,pick,flag,rows"; do
   tag=$(echo $dup | tr ',' '_')
-  SPP_WHATIF_DUP=$dup python bench.py --steps $K --warmup 5 --no-cpu-baseline --no-model-step > $OUT/dup_${tag}_$rep.json 2> $OUT/dup_${tag}_$rep.err
+  SPP_WHATIF_DUP=$dup python bench.py --full --steps $K --warmup 5 --no-cpu-baseline --no-model-step > $OUT/dup_${tag}_$rep.json 2> $OUT/dup_${tag}_$rep.err
   python - $OUT/dup_${tag}_$rep.json $dup <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
