@@ -687,6 +687,44 @@ spp_status spp_gat_aggregate_backward_gather(const int64_t* rowptr_dev, const in
                                              float* grad_x_dev, float* grad_a_src_dev, float* grad_a_dst_dev,
                                              void* workspace_dev, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * f3  Sum aggregation of GINConv over one MFG hop (driver/models.py:234-283: GINConv(nn) with PyG's
+ *     defaults eps = 0, train_eps = False, aggr='add', on ((x, x_target), adj_t)); fp32 accumulate and output.
+ *       forward : out[t,:] = s * x[t,:] + sum_{e in row t} x[col[e],:],  s = 1 + eps passed in; every entry of
+ *                 the row counts (duplicates, self edges), an empty row gives s * x[t,:].  The targets are the
+ *                 first T rows of x (the MFG contract, `x_target = x[:size[1]]`).  With s == 0 the target's own
+ *                 row is not read.  x fp32 or fp16, rows x_stride_elems apart; out rows out_stride_elems apart
+ *                 (0 = dense).
+ *       backward: grad_x[j,:] = (j < T ? s * grad_out[j,:] : 0) + sum_{e: col[e] = j} grad_out[row e,:]; grad_x
+ *                 [S, F] fp32 dense, written completely (fp32 atomics for the scatter: order not fixed).
+ * ------------------------------------------------------------------------- */
+spp_status spp_csr_sum_forward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                               const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t F,
+                               float self_scale, float* out_dev, int64_t out_stride_elems, void* stream);
+/* The same sum straight from the RESIDENT feature table (the TableRows input of a table_features Session, as
+ * spp_sage_operand_forward_table): row j of the batch is table[n_id[j]] (fast_sampler.cpp:1004-1016), same rows and
+ * summation order as spp_csr_sum_forward over the materialised x.  An id outside [0, table_rows) reads row 0. */
+spp_status spp_csr_sum_forward_table(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                                     const void* table_dev, int32_t table_is_half, int64_t table_stride_elems,
+                                     int64_t table_rows, const int64_t* n_id_dev, int64_t F, float self_scale,
+                                     float* out_dev, int64_t out_stride_elems, void* stream);
+/* The same sum from ROW REFERENCES (spp_mfg_out.row_addr, as spp_sage_operand_forward_rows; replaces the assembly
+ * x = cat(...)[perm] of transferers.py:472-486): row j of the batch is the F elements at row_addr_dev[j]; any F
+ * (8-byte aligned fp16 / 16-byte aligned fp32 rows when F % 4 == 0). */
+spp_status spp_csr_sum_forward_rows(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                                    const int64_t* row_addr_dev, int32_t rows_are_half, int64_t F, float self_scale,
+                                    float* out_dev, int64_t out_stride_elems, void* stream);
+spp_status spp_csr_sum_backward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                                int64_t num_sources, const float* grad_out_dev, int64_t grad_out_stride_elems,
+                                int64_t F, float self_scale, float* grad_x_dev, void* stream);
+/* The same gradient by GATHER over the transposed hop (no fp32 atomics), built as for
+ * spp_sage_operand_backward_gather: workspace_dev holds spp_sage_operand_backward_workspace_bytes(T, S, E) bytes,
+ * 16-byte aligned. */
+spp_status spp_csr_sum_backward_gather(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                                       int64_t num_sources, int64_t num_edges, const float* grad_out_dev,
+                                       int64_t grad_out_stride_elems, int64_t F, float self_scale, float* grad_x_dev,
+                                       void* workspace_dev, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

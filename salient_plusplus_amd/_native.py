@@ -160,6 +160,11 @@ SIGNATURES = {
     "spp_ipc_export": (C.c_int, [p, p, C.POINTER(i64)]),
     "spp_ipc_open": (C.c_int, [p, i32, C.POINTER(p)]),
     "spp_ipc_close": (C.c_int, [p]),
+    "spp_csr_sum_forward": (C.c_int, [p, p, i64, p, i32, i64, i64, C.c_float, p, i64, p]),
+    "spp_csr_sum_forward_table": (C.c_int, [p, p, i64, p, i32, i64, i64, p, i64, C.c_float, p, i64, p]),
+    "spp_csr_sum_forward_rows": (C.c_int, [p, p, i64, p, i32, i64, C.c_float, p, i64, p]),
+    "spp_csr_sum_backward": (C.c_int, [p, p, i64, i64, p, i64, i64, C.c_float, p, p]),
+    "spp_csr_sum_backward_gather": (C.c_int, [p, p, i64, i64, i64, p, i64, i64, C.c_float, p, p, i64, p]),
     "spp_session_try_next": (C.c_int, [p, C.POINTER(BatchDesc)]),
     "spp_session_quiesce": (C.c_int, [p]),
     "spp_session_exchange_stats": (C.c_int, [p, C.POINTER(i64), C.POINTER(i64)]),

@@ -483,24 +483,12 @@ extern "C" int64_t spp_sage_operand_backward_workspace_bytes(int64_t num_targets
   return up(4 * (num_sources + 1)) * 2 + up(4 * num_edges) + up(4 * num_targets) + up((int64_t)scan_tmp) + 64;
 }
 
-static spp_status operand_backward_gather(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
-                                          int64_t num_sources, int64_t num_edges, const float* grad_out_dev,
-                                          int64_t grad_out_stride_elems, int64_t F, float* grad_x_dev,
-                                          void* workspace_dev, int64_t workspace_bytes, const float* z_pre_dev,
-                                          ActArgs act, void* stream) {
-  SPP_REQUIRE(num_targets >= 0 && num_sources >= num_targets && F >= 0 && num_edges >= 0,
-              "spp_sage_operand_backward_gather: bad sizes");
-  if (num_sources == 0 || F == 0) return SPP_OK;
-  SPP_REQUIRE(num_sources < (1ll << 31) && num_edges < (1ll << 31), "spp_sage_operand_backward_gather: 32-bit indices");
-  SPP_REQUIRE(grad_x_dev && workspace_dev && (grad_out_dev || num_targets == 0),
-              "spp_sage_operand_backward_gather: NULL buffer");
-  SPP_REQUIRE(F % 4 == 0 && grad_out_stride_elems >= 2 * F && grad_out_stride_elems % 4 == 0 &&
-                  reinterpret_cast<uintptr_t>(grad_out_dev) % 16 == 0 && reinterpret_cast<uintptr_t>(grad_x_dev) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(workspace_dev) % 16 == 0,
-              "spp_sage_operand_backward_gather: needs F %% 4 == 0 and 16-byte aligned buffers");
-  SPP_REQUIRE(workspace_bytes >= spp_sage_operand_backward_workspace_bytes(num_targets, num_sources, num_edges),
-              "spp_sage_operand_backward_gather: workspace too small");
-  hipStream_t st = as_stream(stream);
+// The transposed hop (sources -> targets) in a spp_sage_operand_backward_workspace_bytes workspace: source s's targets
+// are tcol[start[s] .. start[s+1]), inv[t] = 1 / max(deg t, 1).  Count, scan, fill; the callers have checked the sizes.
+static spp_status transpose_hop(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                                int64_t num_sources, int64_t num_edges, void* workspace_dev, int64_t workspace_bytes,
+                                hipStream_t st, const int32_t** start_out, const int32_t** tcol_out,
+                                const float** inv_out) {
   auto up = [](int64_t v) { return (v + 15) & ~(int64_t)15; };
   char* w = static_cast<char*>(workspace_dev);
   int32_t* cnt = reinterpret_cast<int32_t*>(w);
@@ -520,6 +508,34 @@ static spp_status operand_backward_gather(const int64_t* rowptr_dev, const int64
   SPP_HIP_TRY(hipMemsetAsync(cnt, 0, 4 * (size_t)(num_sources + 1), st));
   if (num_targets > 0)
     hipLaunchKernelGGL(k_tr_fill, dim3(gt), dim3(kAggNT), 0, st, rowptr_dev, col_dev, num_targets, start, cnt, tcol);
+  *start_out = start;
+  *tcol_out = tcol;
+  *inv_out = inv;
+  return SPP_OK;
+}
+
+static spp_status operand_backward_gather(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                                          int64_t num_sources, int64_t num_edges, const float* grad_out_dev,
+                                          int64_t grad_out_stride_elems, int64_t F, float* grad_x_dev,
+                                          void* workspace_dev, int64_t workspace_bytes, const float* z_pre_dev,
+                                          ActArgs act, void* stream) {
+  SPP_REQUIRE(num_targets >= 0 && num_sources >= num_targets && F >= 0 && num_edges >= 0,
+              "spp_sage_operand_backward_gather: bad sizes");
+  if (num_sources == 0 || F == 0) return SPP_OK;
+  SPP_REQUIRE(num_sources < (1ll << 31) && num_edges < (1ll << 31), "spp_sage_operand_backward_gather: 32-bit indices");
+  SPP_REQUIRE(grad_x_dev && workspace_dev && (grad_out_dev || num_targets == 0),
+              "spp_sage_operand_backward_gather: NULL buffer");
+  SPP_REQUIRE(F % 4 == 0 && grad_out_stride_elems >= 2 * F && grad_out_stride_elems % 4 == 0 &&
+                  reinterpret_cast<uintptr_t>(grad_out_dev) % 16 == 0 && reinterpret_cast<uintptr_t>(grad_x_dev) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(workspace_dev) % 16 == 0,
+              "spp_sage_operand_backward_gather: needs F %% 4 == 0 and 16-byte aligned buffers");
+  SPP_REQUIRE(workspace_bytes >= spp_sage_operand_backward_workspace_bytes(num_targets, num_sources, num_edges),
+              "spp_sage_operand_backward_gather: workspace too small");
+  hipStream_t st = as_stream(stream);
+  const int32_t *start, *tcol;
+  const float* inv;
+  SPP_TRY(transpose_hop(rowptr_dev, col_dev, num_targets, num_sources, num_edges, workspace_dev, workspace_bytes, st,
+                        &start, &tcol, &inv));
   const int lpr_log2 = lanes_log2(F / 4);
   const unsigned grid = (unsigned)ceil_div(num_sources << lpr_log2, kAggNT);
   if (z_pre_dev)
@@ -1252,6 +1268,259 @@ extern "C" spp_status spp_gat_backward(const int64_t* rowptr_dev, const int64_t*
   hipLaunchKernelGGL(k_gat_bwd, dim3(grid), dim3(kAggNT), 0, as_stream(stream), rowptr_dev, col_dev, num_targets, h_dev,
                      F, a_src_dev, a_dst_dev, negative_slope, out_dev, row_max_dev, row_sum_dev, grad_out_dev,
                      grad_h_dev, grad_a_src_dev, grad_a_dst_dev);
+  SPP_HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
+
+// ================================================================================================
+// GINConv sum aggregation over an MFG hop (reference: driver/models.py:234-283 uses
+// torch_geometric.nn.GINConv(nn, eps=0, train_eps=False), aggr='add', on ((x, x_target), adj_t)):
+//     out[t,:]    = s * x[t,:] + sum_{e in row t} x[col[e],:]                    s = 1 + eps   forward
+//     grad_x[j,:] = (j < T ? s * grad_out[j,:] : 0) + sum_{e: col[e] = j} grad_out[row e,:]    backward
+// Every entry of the row counts (duplicates and self edges included); targets are the first T rows of x.
+// Same lane layout as k_csr_mean_fwd, and the same three first-layer inputs (x, table + n_id, row
+// addresses).  The gather backward walks the transposed hop the mean's backward builds (transpose_hop).
+// ================================================================================================
+namespace spp {
+
+// s == 0: the target's own row is not read (a foreign x_target is added by the caller)
+template <typename Tin, bool VEC4, bool kTable = false, bool kRefs = false>
+__global__ __launch_bounds__(kAggNT) void k_csr_sum_fwd(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,
+                                                        int64_t T, const Tin* __restrict__ x, int64_t x_stride, int64_t F,
+                                                        int lpr_log2, float s, float* __restrict__ out, int64_t out_stride,
+                                                        const int64_t* __restrict__ nid, int64_t x_rows) {
+  const int lpr = 1 << lpr_log2;
+  const int lane = threadIdx.x & (lpr - 1);
+  const int64_t t = ((int64_t)blockIdx.x * kAggNT + threadIdx.x) >> lpr_log2;
+  if (t >= T) return;
+  const int64_t b = rowptr[t], e = rowptr[t + 1];
+  auto row = [&](int64_t j) -> const Tin* {  // where row j of the batch starts
+    if constexpr (kRefs) return reinterpret_cast<const Tin*>((uintptr_t)nid[j]);
+    if constexpr (kTable) {
+      const int64_t g = nid[j];
+      j = (uint64_t)g < (uint64_t)x_rows ? g : 0;
+    }
+    return x + j * x_stride;
+  };
+  const Tin* own = s != 0.f ? row(t) : nullptr;
+  if (VEC4) {
+    for (int64_t c = (int64_t)lane * 4; c < F; c += (int64_t)lpr * 4) {
+      f4 acc = {0.f, 0.f, 0.f, 0.f};
+      int64_t k = b;
+      for (; k + 1 < e; k += 2) {  // two independent rows in flight
+        const f4 v0 = load4(row(col[k]) + c), v1 = load4(row(col[k + 1]) + c);
+        acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
+        acc.x += v1.x; acc.y += v1.y; acc.z += v1.z; acc.w += v1.w;
+      }
+      if (k < e) {
+        const f4 v0 = load4(row(col[k]) + c);
+        acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
+      }
+      if (own) {
+        const f4 o = load4(own + c);
+        acc.x = fmaf(s, o.x, acc.x); acc.y = fmaf(s, o.y, acc.y); acc.z = fmaf(s, o.z, acc.z); acc.w = fmaf(s, o.w, acc.w);
+      }
+      *reinterpret_cast<float4*>(out + t * out_stride + c) = make_float4(acc.x, acc.y, acc.z, acc.w);
+    }
+  } else {
+    for (int64_t c = lane; c < F; c += lpr) {
+      float acc = 0.f;
+      for (int64_t k = b; k < e; ++k) acc += load1(row(col[k]) + c);
+      if (own) acc = fmaf(s, load1(own + c), acc);
+      out[t * out_stride + c] = acc;
+    }
+  }
+}
+
+// grad_x rows < T start from s * grad_out (the self term), the others from zero; any F
+__global__ __launch_bounds__(kAggNT) void k_sum_grad_init(const float* __restrict__ g, int64_t go_stride, int64_t T,
+                                                          int64_t S, int64_t F, float s, float* __restrict__ grad_x) {
+  const int64_t n = S * F;
+  for (int64_t i = (int64_t)blockIdx.x * kAggNT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kAggNT) {
+    const int64_t r = i / F, c = i - r * F;
+    grad_x[i] = r < T ? s * g[r * go_stride + c] : 0.f;
+  }
+}
+
+// the scatter: grad_x[col[e],:] += grad_out[t,:] (hardware fp32 atomics, summation order not fixed)
+__global__ __launch_bounds__(kAggNT) void k_csr_sum_bwd(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,
+                                                        int64_t T, const float* __restrict__ g, int64_t go_stride, int64_t F,
+                                                        int lpr_log2, float* __restrict__ grad_x) {
+  const int lpr = 1 << lpr_log2;
+  const int lane = threadIdx.x & (lpr - 1);
+  const int64_t t = ((int64_t)blockIdx.x * kAggNT + threadIdx.x) >> lpr_log2;
+  if (t >= T) return;
+  const int64_t b = rowptr[t], e = rowptr[t + 1];
+  for (int64_t c = lane; c < F; c += lpr) {
+    const float v = g[t * go_stride + c];
+    for (int64_t k = b; k < e; ++k) unsafeAtomicAdd(grad_x + col[k] * F + c, v);
+  }
+}
+
+// the same gradient by gather over the transposed hop: source j's targets are tcol[start[j] .. start[j+1])
+template <bool VEC4>
+__global__ __launch_bounds__(kAggNT) void k_sum_bwd_gather(const int32_t* __restrict__ start,
+                                                           const int32_t* __restrict__ tcol, int64_t T, int64_t S,
+                                                           const float* __restrict__ g, int64_t go_stride, int64_t F,
+                                                           int lpr_log2, float s, float* __restrict__ grad_x) {
+  const int lpr = 1 << lpr_log2;
+  const int lane = threadIdx.x & (lpr - 1);
+  const int64_t j = ((int64_t)blockIdx.x * kAggNT + threadIdx.x) >> lpr_log2;
+  if (j >= S) return;
+  const int32_t b = start[j], e = start[j + 1];
+  if (VEC4) {
+    for (int64_t c = (int64_t)lane * 4; c < F; c += (int64_t)lpr * 4) {
+      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+      int32_t k = b;
+      for (; k + 1 < e; k += 2) {  // two independent rows in flight
+        const float4 v0 = *reinterpret_cast<const float4*>(g + (int64_t)tcol[k] * go_stride + c);
+        const float4 v1 = *reinterpret_cast<const float4*>(g + (int64_t)tcol[k + 1] * go_stride + c);
+        acc.x += v0.x + v1.x; acc.y += v0.y + v1.y; acc.z += v0.z + v1.z; acc.w += v0.w + v1.w;
+      }
+      if (k < e) {
+        const float4 v0 = *reinterpret_cast<const float4*>(g + (int64_t)tcol[k] * go_stride + c);
+        acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
+      }
+      if (j < T) {
+        const float4 o = *reinterpret_cast<const float4*>(g + j * go_stride + c);
+        acc.x = fmaf(s, o.x, acc.x); acc.y = fmaf(s, o.y, acc.y); acc.z = fmaf(s, o.z, acc.z); acc.w = fmaf(s, o.w, acc.w);
+      }
+      *reinterpret_cast<float4*>(grad_x + j * F + c) = acc;
+    }
+  } else {
+    for (int64_t c = lane; c < F; c += lpr) {
+      float acc = 0.f;
+      for (int32_t k = b; k < e; ++k) acc += g[(int64_t)tcol[k] * go_stride + c];
+      if (j < T) acc = fmaf(s, g[j * go_stride + c], acc);
+      grad_x[j * F + c] = acc;
+    }
+  }
+}
+
+}  // namespace spp
+
+// x: a dense batch matrix (n_id == NULL), the resident table (n_id != NULL) or -- refs -- nothing (n_id = row addresses)
+static spp_status sum_forward(const char* who, const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                              const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t F, float self_scale,
+                              float* out_dev, int64_t out_stride_elems, void* stream, const int64_t* n_id_dev,
+                              int64_t table_rows, bool refs) {
+  SPP_REQUIRE(num_targets >= 0 && F >= 0, "%s: negative size", who);
+  if (num_targets == 0 || F == 0) return SPP_OK;
+  SPP_REQUIRE(rowptr_dev && out_dev && (refs || x_dev) && ((!refs && table_rows == 0) || n_id_dev),
+              "%s: NULL buffer", who);
+  SPP_REQUIRE(refs || x_stride_elems >= F, "%s: row stride smaller than the row", who);
+  if (out_stride_elems <= 0) out_stride_elems = F;
+  SPP_REQUIRE(out_stride_elems >= F, "%s: output stride smaller than the row", who);
+  hipStream_t st = as_stream(stream);
+  const int64_t esz = x_is_half ? 2 : 4;
+  // row references: 8-byte aligned fp16 / 16-byte aligned fp32 rows when F % 4 == 0 (spp_mfg_out.row_addr)
+  const bool vec = (F % 4 == 0) && (reinterpret_cast<uintptr_t>(out_dev) % 16 == 0) && (out_stride_elems % 4 == 0) &&
+                   (refs || (((x_stride_elems * esz) % (4 * esz) == 0) &&
+                             (reinterpret_cast<uintptr_t>(x_dev) % (4 * esz) == 0)));
+  const int lpr_log2 = lanes_log2(vec ? F / 4 : F);
+  const unsigned grid = (unsigned)ceil_div(num_targets << lpr_log2, kAggNT);
+#define SPP_SUM(TIN, V)                                                                                                \
+  do {                                                                                                                 \
+    const TIN* x_ = static_cast<const TIN*>(x_dev);                                                                    \
+    if (refs)                                                                                                          \
+      hipLaunchKernelGGL((k_csr_sum_fwd<TIN, V, false, true>), dim3(grid), dim3(kAggNT), 0, st, rowptr_dev, col_dev,   \
+                         num_targets, x_, (int64_t)0, F, lpr_log2, self_scale, out_dev, out_stride_elems, n_id_dev,    \
+                         (int64_t)0);                                                                                  \
+    else if (n_id_dev)                                                                                                 \
+      hipLaunchKernelGGL((k_csr_sum_fwd<TIN, V, true>), dim3(grid), dim3(kAggNT), 0, st, rowptr_dev, col_dev,          \
+                         num_targets, x_, x_stride_elems, F, lpr_log2, self_scale, out_dev, out_stride_elems, n_id_dev, \
+                         table_rows);                                                                                  \
+    else                                                                                                               \
+      hipLaunchKernelGGL((k_csr_sum_fwd<TIN, V>), dim3(grid), dim3(kAggNT), 0, st, rowptr_dev, col_dev, num_targets,   \
+                         x_, x_stride_elems, F, lpr_log2, self_scale, out_dev, out_stride_elems, nullptr, (int64_t)0); \
+  } while (0)
+  if (x_is_half) {
+    if (vec) SPP_SUM(__half, true); else SPP_SUM(__half, false);
+  } else {
+    if (vec) SPP_SUM(float, true); else SPP_SUM(float, false);
+  }
+#undef SPP_SUM
+  SPP_HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
+
+extern "C" spp_status spp_csr_sum_forward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                                          const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t F,
+                                          float self_scale, float* out_dev, int64_t out_stride_elems, void* stream) {
+  return sum_forward("spp_csr_sum_forward", rowptr_dev, col_dev, num_targets, x_dev, x_is_half, x_stride_elems, F,
+                     self_scale, out_dev, out_stride_elems, stream, nullptr, 0, false);
+}
+
+extern "C" spp_status spp_csr_sum_forward_table(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                                                const void* table_dev, int32_t table_is_half, int64_t table_stride_elems,
+                                                int64_t table_rows, const int64_t* n_id_dev, int64_t F, float self_scale,
+                                                float* out_dev, int64_t out_stride_elems, void* stream) {
+  SPP_REQUIRE(num_targets == 0 || (n_id_dev && table_dev && table_rows > 0),
+              "spp_csr_sum_forward_table: needs the feature table and the batch's node ids");
+  return sum_forward("spp_csr_sum_forward_table", rowptr_dev, col_dev, num_targets, table_dev, table_is_half,
+                     table_stride_elems, F, self_scale, out_dev, out_stride_elems, stream, n_id_dev, table_rows, false);
+}
+
+extern "C" spp_status spp_csr_sum_forward_rows(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                                               const int64_t* row_addr_dev, int32_t rows_are_half, int64_t F,
+                                               float self_scale, float* out_dev, int64_t out_stride_elems, void* stream) {
+  return sum_forward("spp_csr_sum_forward_rows", rowptr_dev, col_dev, num_targets, nullptr, rows_are_half, 0, F,
+                     self_scale, out_dev, out_stride_elems, stream, row_addr_dev, 0, true);
+}
+
+extern "C" spp_status spp_csr_sum_backward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                                           int64_t num_sources, const float* grad_out_dev, int64_t grad_out_stride_elems,
+                                           int64_t F, float self_scale, float* grad_x_dev, void* stream) {
+  SPP_REQUIRE(num_targets >= 0 && num_sources >= num_targets && F >= 0, "spp_csr_sum_backward: bad sizes");
+  if (num_sources == 0 || F == 0) return SPP_OK;
+  SPP_REQUIRE(grad_x_dev && ((grad_out_dev && rowptr_dev) || num_targets == 0), "spp_csr_sum_backward: NULL buffer");
+  if (grad_out_stride_elems <= 0) grad_out_stride_elems = F;
+  SPP_REQUIRE(grad_out_stride_elems >= F, "spp_csr_sum_backward: gradient stride smaller than the row");
+  hipStream_t st = as_stream(stream);
+  const unsigned g0 = (unsigned)std::min<int64_t>(ceil_div(num_sources * F, kAggNT), 256 * 32);
+  hipLaunchKernelGGL(k_sum_grad_init, dim3(g0), dim3(kAggNT), 0, st, grad_out_dev, grad_out_stride_elems, num_targets,
+                     num_sources, F, self_scale, grad_x_dev);
+  SPP_HIP_TRY(hipGetLastError());
+  if (num_targets == 0) return SPP_OK;
+  const int lpr_log2 = lanes_log2(F);
+  const unsigned grid = (unsigned)ceil_div(num_targets << lpr_log2, kAggNT);
+  hipLaunchKernelGGL(k_csr_sum_bwd, dim3(grid), dim3(kAggNT), 0, st, rowptr_dev, col_dev, num_targets, grad_out_dev,
+                     grad_out_stride_elems, F, lpr_log2, grad_x_dev);
+  SPP_HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
+
+extern "C" spp_status spp_csr_sum_backward_gather(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                                                  int64_t num_sources, int64_t num_edges, const float* grad_out_dev,
+                                                  int64_t grad_out_stride_elems, int64_t F, float self_scale,
+                                                  float* grad_x_dev, void* workspace_dev, int64_t workspace_bytes,
+                                                  void* stream) {
+  SPP_REQUIRE(num_targets >= 0 && num_sources >= num_targets && F >= 0 && num_edges >= 0,
+              "spp_csr_sum_backward_gather: bad sizes");
+  if (num_sources == 0 || F == 0) return SPP_OK;
+  SPP_REQUIRE(num_sources < (1ll << 31) && num_edges < (1ll << 31), "spp_csr_sum_backward_gather: 32-bit indices");
+  SPP_REQUIRE(grad_x_dev && workspace_dev && ((grad_out_dev && rowptr_dev) || num_targets == 0),
+              "spp_csr_sum_backward_gather: NULL buffer");
+  if (grad_out_stride_elems <= 0) grad_out_stride_elems = F;
+  SPP_REQUIRE(grad_out_stride_elems >= F && reinterpret_cast<uintptr_t>(workspace_dev) % 16 == 0,
+              "spp_csr_sum_backward_gather: gradient stride smaller than the row or unaligned workspace");
+  SPP_REQUIRE(workspace_bytes >= spp_sage_operand_backward_workspace_bytes(num_targets, num_sources, num_edges),
+              "spp_csr_sum_backward_gather: workspace too small");
+  hipStream_t st = as_stream(stream);
+  const int32_t *start, *tcol;
+  const float* inv;
+  SPP_TRY(transpose_hop(rowptr_dev, col_dev, num_targets, num_sources, num_edges, workspace_dev, workspace_bytes, st,
+                        &start, &tcol, &inv));
+  const bool vec = F % 4 == 0 && grad_out_stride_elems % 4 == 0 &&
+                   (reinterpret_cast<uintptr_t>(grad_out_dev) | reinterpret_cast<uintptr_t>(grad_x_dev)) % 16 == 0;
+  const int lpr_log2 = lanes_log2(vec ? F / 4 : F);
+  const unsigned grid = (unsigned)ceil_div(num_sources << lpr_log2, kAggNT);
+  if (vec)
+    hipLaunchKernelGGL(k_sum_bwd_gather<true>, dim3(grid), dim3(kAggNT), 0, st, start, tcol, num_targets, num_sources,
+                       grad_out_dev, grad_out_stride_elems, F, lpr_log2, self_scale, grad_x_dev);
+  else
+    hipLaunchKernelGGL(k_sum_bwd_gather<false>, dim3(grid), dim3(kAggNT), 0, st, start, tcol, num_targets, num_sources,
+                       grad_out_dev, grad_out_stride_elems, F, lpr_log2, self_scale, grad_x_dev);
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
 }

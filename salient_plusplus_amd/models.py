@@ -1,7 +1,8 @@
 """Model-step fallback for boxes without PyG / torch_sparse: the reference's flagship
 ``SAGE`` (driver/models.py:19-56: ``num_layers`` x SAGEConv(bias=False, mean aggregation), ReLU +
 dropout 0.5 between layers, log_softmax) on the MFG's CSR, with the message passing on HIP kernels
-(csrc/aggregate.hip) and the linear layers on the library GEMMs torch dispatches to.
+(csrc/aggregate.hip) and the linear layers on the library GEMMs torch dispatches to.  The reference's other working
+models follow: GAT, GIN (sum aggregation) and SAGEResInception; ``get_model_type`` maps their names (driver/main.py:74-95).
 
 The constructor, ``reset_parameters`` and ``forward(x, adjs)`` follow the reference; ``adjs`` is
 what the data path delivers: ``[(adj_t, e_id, (S, T)), ...]``, outermost hop first."""
@@ -557,3 +558,275 @@ class GAT(torch.nn.Module):
             if i != self.num_layers - 1:
                 x = relu_dropout(x, 0.5, self.training)
         return torch.log_softmax(x, dim=-1)
+
+
+# --------------------------------------------------------------------------------------------
+# GIN  (driver/models.py:234-283: GINConv(Sequential(Linear, BatchNorm1d, ReLU, Linear, ReLU)), eps = 0)
+# --------------------------------------------------------------------------------------------
+_SUM_GATHER_MIN_WORK = 1 << 22      # E x F from which the input gradient is gathered, as in the mean's backward
+
+
+class _SumAggregate(torch.autograd.Function):
+    """out[t] = s * x[t] + sum_{e in row t} x[col[e]]  (fp32 [T, F]; targets are the first T rows of x).
+
+    ``x`` is a feature matrix (fp16 / fp32, any row stride), a TableRows or a RowRefs: the latter two are read in
+    place (spp_csr_sum_forward_table / _rows) and get no gradient.  With s == 0 the targets' rows are not read."""
+
+    @staticmethod
+    def forward(ctx, x, rowptr, col, num_targets, scale):
+        L = nat.load()
+        nat.require_device()
+        st = _stream()
+        S, Fdim = x.size(0), x.size(1)
+        assert x.is_cuda and rowptr.is_cuda and col.is_cuda and _readable(x), "fp16 / fp32 rows on the GPU"
+        assert num_targets <= S or scale == 0.0, "the targets are the first rows of the sources"
+        out = torch.empty((num_targets, Fdim), dtype=torch.float32, device=x.device)
+        half = int(x.dtype == torch.float16)
+        if isinstance(x, TableRows):
+            tb = x.table
+            nat.check(L.spp_csr_sum_forward_table(_p(rowptr), _p(col), num_targets, _p(tb), half,
+                                                  tb.stride(0) if tb.size(0) > 1 else Fdim, tb.size(0), _p(x.n_id), Fdim,
+                                                  float(scale), _p(out), Fdim, st))
+        elif isinstance(x, RowRefs):
+            nat.check(L.spp_csr_sum_forward_rows(_p(rowptr), _p(col), num_targets, _p(x.addr), half, Fdim, float(scale),
+                                                 _p(out), Fdim, st))
+        else:
+            nat.check(L.spp_csr_sum_forward(_p(rowptr), _p(col), num_targets, _p(x), half,
+                                            x.stride(0) if S > 1 else Fdim, Fdim, float(scale), _p(out), Fdim, st))
+        ctx.save_for_backward(rowptr, col)
+        ctx.shape = (S, Fdim, num_targets)
+        ctx.scale = float(scale)
+        ctx.in_dtype = x.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:            # the first layer: the batch's features are no leaves
+            return None, None, None, None, None
+        rowptr, col = ctx.saved_tensors
+        S, Fdim, T = ctx.shape
+        L = nat.load()
+        g = grad_out if (grad_out.stride(1) == 1 and grad_out.dtype == torch.float32) else \
+            grad_out.contiguous().to(torch.float32)
+        go_stride = g.stride(0) if T > 1 else Fdim
+        grad_x = torch.empty((S, Fdim), dtype=torch.float32, device=g.device)
+        E = col.numel()
+        if E * Fdim >= _SUM_GATHER_MIN_WORK:
+            # gather over the transposed hop (the mean's transposition and workspace) instead of E x F fp32 atomics
+            nbytes = int(L.spp_sage_operand_backward_workspace_bytes(T, S, E))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=g.device)
+            nat.check(L.spp_csr_sum_backward_gather(_p(rowptr), _p(col), T, S, E, _p(g), go_stride, Fdim, ctx.scale,
+                                                    _p(grad_x), _p(ws), nbytes, _stream()))
+        else:
+            nat.check(L.spp_csr_sum_backward(_p(rowptr), _p(col), T, S, _p(g), go_stride, Fdim, ctx.scale, _p(grad_x),
+                                             _stream()))
+        return grad_x.to(ctx.in_dtype), None, None, None, None
+
+
+def sum_aggregate(x, rowptr, col, num_targets, scale=1.0):
+    """scale * x[:T] + the sum of each target's neighbour rows (GINConv's aggregation with scale = 1 + eps)"""
+    return _SumAggregate.apply(x, rowptr, col, num_targets, scale)
+
+
+def _readable(x):
+    """a feature matrix, TableRows or RowRefs the sum kernels read as they are (fp16 / fp32 rows)"""
+    if isinstance(x, TableRows):
+        return x.table.is_cuda and x.table.dtype in (torch.float16, torch.float32) and x.table.stride(1) == 1
+    if isinstance(x, RowRefs):
+        return x.dtype in (torch.float16, torch.float32)
+    return x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and x.dtype in (torch.float16, torch.float32)
+
+
+class GINConv(torch.nn.Module):
+    """torch_geometric.nn.GINConv(nn, eps=0., train_eps=False) on a bipartite ((x, x_target), adj_t):
+    nn((1 + eps) * x_target + sum_j x_j), the sum over every entry of the target's row.  ``eps`` is a buffer.
+
+    ``forward(x, adj_t, size)`` with a single ``x`` (a matrix, TableRows or RowRefs) takes the first size[1] rows
+    as the targets (the MFG contract)."""
+
+    def __init__(self, nn, eps=0., train_eps=False):
+        super().__init__()
+        if train_eps:
+            raise NotImplementedError("the reference models use GINConv with a fixed eps (train_eps=False)")
+        self.nn = nn
+        self.initial_eps = eps
+        self.register_buffer("eps", torch.empty(1))
+        self._scale_key = self._scale_val = None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for m in self.nn.children():                     # PyG's reset(nn)
+            if hasattr(m, "reset_parameters"):
+                m.reset_parameters()
+        with torch.no_grad():
+            self.eps.fill_(self.initial_eps)
+
+    def _scale(self):
+        # 1 + eps as a host float for the kernel, read back only when the buffer has changed (a device read syncs)
+        key = (self.eps.data_ptr(), self.eps._version)
+        if key != self._scale_key:
+            self._scale_val, self._scale_key = 1.0 + float(self.eps), key
+        return self._scale_val
+
+    def forward(self, x, adj_t, size=None):
+        rowptr, col, _ = adj_t.csr()
+        if isinstance(x, tuple):
+            x, x_target = x
+            T = x_target.size(0)
+        else:
+            x_target = None
+            T = int(size[1]) if size is not None else x.size(0)
+        if not _readable(x):
+            x = (x.materialize() if isinstance(x, (TableRows, RowRefs)) else x).to(torch.float32).contiguous()
+            if x_target is not None:
+                x_target = x[:T]
+        prefix = x_target is None or (isinstance(x, torch.Tensor) and x_target.data_ptr() == x.data_ptr() and
+                                      x_target.stride() == x.stride() and x_target.size(1) == x.size(1))
+        if prefix:                                                          # x_target = x[:T] (the MFG contract)
+            h = _SumAggregate.apply(x, rowptr, col, T, self._scale())
+        else:                                                               # a foreign target matrix
+            h = _SumAggregate.apply(x, rowptr, col, T, 0.0) + (1 + self.eps) * x_target.to(torch.float32)
+        return self.nn(h)
+
+
+def _gin_mlp(d_in, d_hidden):
+    return torch.nn.Sequential(torch.nn.Linear(d_in, d_hidden), torch.nn.BatchNorm1d(d_hidden), torch.nn.ReLU(),
+                               torch.nn.Linear(d_hidden, d_hidden), torch.nn.ReLU())
+
+
+class GIN(torch.nn.Module):
+    """``num_layers`` GINConv (in -> hidden, then hidden -> hidden, the last one included), then lin1, ReLU, dropout,
+    lin2, log_softmax.  The first layer reads a TableRows / RowRefs input in place."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, dropout=0.5):
+        super().__init__()
+        self.num_layers = num_layers
+        self.hidden_channels = hidden_channels
+        self.dropout = dropout
+        self.convs = torch.nn.ModuleList()
+        self.convs.append(GINConv(_gin_mlp(in_channels, hidden_channels)))
+        for _ in range(num_layers - 1):
+            self.convs.append(GINConv(_gin_mlp(hidden_channels, hidden_channels)))
+        self.lin1 = torch.nn.Linear(hidden_channels, hidden_channels)
+        self.lin2 = torch.nn.Linear(hidden_channels, out_channels)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for conv in self.convs:
+            conv.reset_parameters()
+            conv.apply(init_weights)
+        self.lin1.reset_parameters()
+        self.lin2.reset_parameters()
+
+    def forward(self, x, adjs):
+        # the reference converts the features to fp32 first (models.py:272); the sum reads fp16 rows directly (exact)
+        for i, (adj_t, _e_id, size) in enumerate(adjs):
+            if isinstance(x, (TableRows, RowRefs)):
+                x = self.convs[i](x, adj_t, size)
+            else:
+                x = self.convs[i]((x, x[:size[1]]), adj_t)
+        x = F.relu(self.lin1(x))
+        x = F.dropout(x, p=self.dropout, training=self.training)
+        return torch.log_softmax(self.lin2(x), dim=-1)
+
+
+# --------------------------------------------------------------------------------------------
+# SAGEResInception  (driver/models.py:95-192)
+# --------------------------------------------------------------------------------------------
+class MLP(torch.nn.Module):
+    """driver/models.py:95-125: ``num_layers`` Linears (input -> hidden -> ... -> embed), each followed by
+    [BatchNorm1d] + activation unless ``end_up_with_fc``, which skips both for EVERY layer (the reference's
+    ``continue``): SAGEResInception's MLP is two bare Linears."""
+
+    def __init__(self, input_dim, hidden_dim, embed_dim, num_layers, act="ReLU", bn=False, end_up_with_fc=False,
+                 bias=True):
+        super().__init__()
+        layers = []
+        for i in range(num_layers):
+            d_in = input_dim if i == 0 else hidden_dim
+            d_out = embed_dim if i == num_layers - 1 else hidden_dim
+            layers.append(torch.nn.Linear(d_in, d_out, bias=bias))
+            if not end_up_with_fc:
+                if bn:
+                    layers.append(torch.nn.BatchNorm1d(d_out))
+                layers.append(getattr(torch.nn, act)(True))
+        self.module_list = torch.nn.Sequential(*layers)
+
+    def reset_parameters(self):
+        for m in self.module_list:
+            if hasattr(m, "reset_parameters"):
+                m.reset_parameters()
+
+    def forward(self, x):
+        return self.module_list(x)
+
+
+def _dropout(x, p, training):
+    return F.dropout(x, p=p, training=True) if (training and p > 0) else x
+
+
+class SAGEResInception(torch.nn.Module):
+    """SAGEConv layers (in -> hidden, then hidden -> hidden: the last one outputs hidden too), each followed by
+    BatchNorm1d, leaky_relu and dropout, with a residual (Linear for the first layer, identity after); the input
+    and every layer's rows of the final targets are concatenated into a two-Linear MLP head."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, dropout=0.1):
+        super().__init__()
+        self.num_layers = num_layers
+        self.hidden_channels = hidden_channels
+        self.dropout = dropout
+        self.convs = torch.nn.ModuleList()
+        self.bns = torch.nn.ModuleList()
+        self.res_linears = torch.nn.ModuleList()
+        for i in range(num_layers):
+            d_in = in_channels if i == 0 else hidden_channels
+            self.convs.append(SAGEConv(d_in, hidden_channels, bias=False))
+            self.bns.append(torch.nn.BatchNorm1d(hidden_channels))
+            self.res_linears.append(torch.nn.Linear(in_channels, hidden_channels) if i == 0 else torch.nn.Identity())
+        self.mlp = MLP(in_channels + hidden_channels * num_layers, 2 * out_channels, out_channels, num_layers=2, bn=True,
+                       end_up_with_fc=True, act="LeakyReLU")
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for conv in self.convs:
+            conv.reset_parameters()
+            conv.apply(init_weights)
+        for m in self.res_linears:
+            if isinstance(m, torch.nn.Linear):
+                m.reset_parameters()
+        for bn in self.bns:
+            bn.reset_parameters()
+        self.mlp.reset_parameters()
+
+    def forward(self, x, adjs):
+        if isinstance(x, (TableRows, RowRefs)):          # every layer-0 row is dropped out first: nothing to fuse
+            x = x.materialize()
+        p, tr = self.dropout, self.training
+        x = _dropout(x.to(torch.float32), p, tr)
+        end_size = adjs[-1][-1][1]
+        collect = [x[:end_size]]
+        for i, (adj_t, _e_id, size) in enumerate(adjs):
+            x_target = x[:size[1]]
+            h = self.convs[i]((_dropout(x, p, tr), _dropout(x_target, p, tr)), adj_t)
+            h = _dropout(F.leaky_relu(self.bns[i](h)), p, tr)
+            # the reference stores the view h[:end_size] and then adds the residual to h IN PLACE, which writes through
+            # the view: what is concatenated are the rows after the residual add
+            x = h + self.res_linears[i](x_target)
+            collect.append(x[:end_size])
+        return torch.log_softmax(self.mlp(torch.cat(collect, -1)), dim=-1)
+
+
+_UNSUPPORTED_MODELS = {"sageclassic": "not used in the paper", "jknet": "not used in the paper",
+                       "gcn": "not used in the paper", "arma": "broken in the reference"}
+
+
+def get_model_type(model_name):
+    """driver/main.py:74-95 for the four models the reference marks as working (names case-insensitive)"""
+    name = model_name.lower()
+    models = {"sage": SAGE, "gat": GAT, "gin": GIN, "sageresinception": SAGEResInception}
+    if name in models:
+        return models[name]
+    if name in _UNSUPPORTED_MODELS:
+        raise NotImplementedError(f"model {model_name!r} is not implemented here ({_UNSUPPORTED_MODELS[name]} per the "
+                                  "reference); the working models are SAGE, GAT, GIN and SAGEResInception")
+    raise ValueError(f"unknown model {model_name!r}")

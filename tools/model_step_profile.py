@@ -1,6 +1,7 @@
-"""One resident batch of the bench workload, N optimisation steps of models.SAGE / models.GAT on it
-(fwd + bwd + Adam), timed; run under `rocprofv3 --kernel-trace --stats` for the per-kernel table.
-usage: model_step_profile.py [sage|gat] [steps=30] [workload=S-papers]"""
+"""One resident batch of the bench workload, N optimisation steps of one of the models (models.get_model_type: SAGE, GAT,
+GIN, SAGEResInception) on it (fwd + bwd + Adam), timed; run under `rocprofv3 --kernel-trace --stats` for the per-kernel
+table.
+usage: model_step_profile.py [sage|gat|gin|sageresinception] [steps=30] [workload=S-papers]"""
 import os
 import sys
 import time
@@ -11,7 +12,7 @@ import torch  # noqa: E402
 from salient_plusplus_amd import fast_sampler as fs  # noqa: E402
 from salient_plusplus_amd.fast_trainer.samplers import FastSampler, FastSamplerConfig  # noqa: E402
 from salient_plusplus_amd.fast_trainer.transferers import DevicePrefetcher  # noqa: E402
-from salient_plusplus_amd.models import GAT, SAGE  # noqa: E402
+from salient_plusplus_amd.models import get_model_type  # noqa: E402
 from salient_plusplus_amd.synthetic import make_workload  # noqa: E402
 
 arch = sys.argv[1] if len(sys.argv) > 1 else "sage"
@@ -26,7 +27,7 @@ cfg = FastSamplerConfig(
 it = DevicePrefetcher([dev], iter(FastSampler(2, 8, cfg)))
 batch = next(it)[0]
 torch.cuda.synchronize()
-model = (GAT if arch == "gat" else SAGE)(wl.x.size(1), 256, 47, 3).to(dev)
+model = get_model_type(arch)(wl.x.size(1), 256, 47, 3).to(dev)
 opt = torch.optim.Adam(model.parameters(), lr=1e-3, fused=True)    # one multi-tensor launch per step
 
 
@@ -47,4 +48,4 @@ for _ in range(steps):
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / steps
 print(f"MODEL_STEP {arch} {dt * 1e3:.3f} ms/step on a resident batch: {batch.x.size(0)} nodes, "
-      f"{[int(a.adj_t.nnz()) for a in batch.adjs]} edges, loss {float(loss):.4f}", flush=True)
+      f"{[int(a.adj_t.nnz()) for a in batch.adjs]} edges, (S, T) {[tuple(int(v) for v in a.size) for a in batch.adjs]}, loss {float(loss):.4f}", flush=True)
