@@ -12,6 +12,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <type_traits>
 
 namespace spp {
 
@@ -61,44 +62,78 @@ __device__ __forceinline__ f4 relu_dropout4(f4 v, int64_t i4, const ActArgs& a) 
   return o;
 }
 
-// VEC4: F % 4 == 0 and rows 16-B (fp32) / 8-B (fp16) aligned
-// kAct (fp32, VEC4, dense rows: x_stride == F): x is a PRE-activation; relu + dropout are applied to every row
-// as it is loaded -- the same values a k_relu_dropout_fwd pass over x would have produced (same generator,
-// same element indices), without the pass.
-// kTable (first layer, opt-in): x is the RESIDENT feature table and row j of the batch is x[nid[j]] (nid = the batch's
-// n_id, int64) -- the batch's feature matrix is never written and re-read (242 MB each way at papers scale); the sum
-// runs over the same rows in the same order as over a materialised x[n_id], so the operand is bit-identical.  An id
-// outside [0, x_rows) reads row 0 (no fault).
-// kRefs (first layer, opt-in, partitioned path): row j of the batch is the F elements at ADDRESS nid[j] (row references,
-// spp_mfg_out.row_addr: local partition / VIP cache / received rows / a peer's partition); x and x_stride are unused.
-template <typename Tin, bool VEC4, bool kAct = false, bool kTable = false, bool kRefs = false>
-__global__ __launch_bounds__(kAggNT) void k_csr_mean_fwd(const int64_t* __restrict__ rowptr,
-                                                         const int64_t* __restrict__ col, int64_t T,
-                                                         const Tin* __restrict__ x, int64_t x_stride, int64_t F,
-                                                         int lpr_log2, float* __restrict__ out, int64_t out_stride,
-                                                         int concat_target, ActArgs act,
-                                                         const int64_t* __restrict__ nid = nullptr, int64_t x_rows = 0) {
+// ---- neighbour reduction over a hop: where row j comes from (Rows<Tin, Src>(j)) ----
+//   Dense: x + j * x_stride, the batch's matrix (targets are its first rows).
+//   Table (first layer, opt-in): x is the RESIDENT feature table and row j of the batch is x[nid[j]] (nid = the batch's
+//     n_id, int64) -- the batch's feature matrix is never written and re-read (242 MB each way at papers scale); the
+//     sum runs over the same rows in the same order as over a materialised x[n_id]: bit-identical.  An id outside
+//     [0, x_rows) reads row 0 (no fault).
+//   Refs (first layer, opt-in, partitioned path): the F elements at ADDRESS nid[j] (row references, spp_mfg_out.row_addr:
+//     local partition / VIP cache / received rows / a peer's partition); x and x_stride are unused.
+struct Dense {};
+struct Table {};
+struct Refs {};
+template <typename Tin, class Src>
+struct Rows {
+  const Tin* x;
+  int64_t x_stride;
+  const int64_t* nid;
+  int64_t x_rows;
+  __device__ __forceinline__ const Tin* operator()(int64_t j) const {
+    if constexpr (std::is_same<Src, Refs>::value) return reinterpret_cast<const Tin*>((uintptr_t)nid[j]);
+    if constexpr (std::is_same<Src, Table>::value) {
+      const int64_t g = nid[j];
+      j = (uint64_t)g < (uint64_t)x_rows ? g : 0;
+    }
+    return x + j * x_stride;
+  }
+};
+
+// ---- the epilogues: what a target's sum becomes (the backward kernels take the same types) ----
+//   Mean (SAGEConv): sum / max(deg t, 1), with concat_target followed by the target's own row as fp32 ([mean | x_target]).
+//     kAct (dense fp32 rows, VEC4): x is a PRE-activation; relu + dropout are applied to every row as it is loaded --
+//     the same values a k_relu_dropout_fwd pass over x would have produced (same generator, same indices).
+//   Sum (GINConv): fmaf(s, x[t], sum); with s == 0 the target's row is not read (a foreign x_target is added by the caller).
+template <bool kAct_>
+struct Mean {
+  static constexpr bool kSum = false, kAct = kAct_;
+  static constexpr float s = 0.f;
+  int concat_target;
+  ActArgs act;
+};
+struct Sum {
+  static constexpr bool kSum = true, kAct = false;
+  static constexpr int concat_target = 0;
+  float s;
+};
+
+// LPR lanes share a target row; VEC4: F % 4 == 0 and rows 16-B (fp32) / 8-B (fp16) aligned.  The row's entries are
+// added in CSR order, one at a time.
+template <typename Tin, bool VEC4, class Src, class Epi>
+__global__ __launch_bounds__(kAggNT) void k_agg_fwd(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,
+                                                    int64_t T, const Tin* __restrict__ x, int64_t x_stride, int64_t F,
+                                                    int lpr_log2, float* __restrict__ out, int64_t out_stride, Epi epi,
+                                                    const int64_t* __restrict__ nid, int64_t x_rows) {
+  static_assert(!Epi::kAct || (VEC4 && std::is_same<Tin, float>::value && std::is_same<Src, Dense>::value),
+                "activation on load: dense fp32 rows, vector form");
+  const Rows<Tin, Src> row{x, x_stride, nid, x_rows};
   const int lpr = 1 << lpr_log2;
   const int lane = threadIdx.x & (lpr - 1);
   const int64_t t = ((int64_t)blockIdx.x * kAggNT + threadIdx.x) >> lpr_log2;
   if (t >= T) return;
   const int64_t b = rowptr[t], e = rowptr[t + 1];
-  const float inv = 1.0f / (float)(e > b ? e - b : 1);
-  auto row4 = [&](int64_t j, int64_t c) {  // four columns of row j (activated on load with kAct)
-    if constexpr (kRefs) return load4(reinterpret_cast<const Tin*>((uintptr_t)nid[j]) + c);
-    if constexpr (kTable) {
-      const int64_t g = nid[j];
-      j = (uint64_t)g < (uint64_t)x_rows ? g : 0;
-    }
-    f4 v = load4(x + j * x_stride + c);
-    if constexpr (kAct) v = relu_dropout4(v, (j * x_stride + c) >> 2, act);
-    return v;
-  };
+  const float inv = 1.0f / (float)(e > b ? e - b : 1);  // Mean
+  const Tin* own = epi.s != 0.f ? row(t) : nullptr;      // Sum
   if (VEC4) {
+    auto row4 = [&](int64_t j, int64_t c) {  // four columns of row j (activated on load with kAct)
+      f4 v = load4(row(j) + c);
+      if constexpr (Epi::kAct) v = relu_dropout4(v, (j * x_stride + c) >> 2, epi.act);
+      return v;
+    };
     for (int64_t c = (int64_t)lane * 4; c < F; c += (int64_t)lpr * 4) {
-      if (concat_target) {  // [mean | x_target]: the target's own row (targets are the first rows of x), as fp32
-        const f4 own = row4(t, c);
-        *reinterpret_cast<float4*>(out + t * out_stride + F + c) = make_float4(own.x, own.y, own.z, own.w);
+      if (epi.concat_target) {  // [mean | x_target]: the target's own row (targets are the first rows of x), as fp32
+        const f4 o = row4(t, c);
+        *reinterpret_cast<float4*>(out + t * out_stride + F + c) = make_float4(o.x, o.y, o.z, o.w);
       }
       f4 acc = {0.f, 0.f, 0.f, 0.f};
       int64_t k = b;
@@ -111,40 +146,40 @@ __global__ __launch_bounds__(kAggNT) void k_csr_mean_fwd(const int64_t* __restri
         const f4 v0 = row4(col[k], c);
         acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
       }
-      *reinterpret_cast<float4*>(out + t * out_stride + c) =
-          make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv);
+      if (own) {
+        const f4 o = load4(own + c);
+        acc = {fmaf(epi.s, o.x, acc.x), fmaf(epi.s, o.y, acc.y), fmaf(epi.s, o.z, acc.z), fmaf(epi.s, o.w, acc.w)};
+      }
+      if (!Epi::kSum) acc = {acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv};
+      *reinterpret_cast<float4*>(out + t * out_stride + c) = make_float4(acc.x, acc.y, acc.z, acc.w);
     }
   } else {
-    auto row_of = [&](int64_t j) {
-      if constexpr (kTable) {
-        const int64_t g = nid[j];
-        j = (uint64_t)g < (uint64_t)x_rows ? g : 0;
-      }
-      return j;
-    };
     for (int64_t c = lane; c < F; c += lpr) {
-      if (concat_target) out[t * out_stride + F + c] = load1(x + row_of(t) * x_stride + c);
+      if (epi.concat_target) out[t * out_stride + F + c] = load1(row(t) + c);
       float acc = 0.f;
-      for (int64_t k = b; k < e; ++k) acc += load1(x + row_of(col[k]) * x_stride + c);
-      out[t * out_stride + c] = acc * inv;
-      static_assert(!kRefs || VEC4, "row references use the vector form");
+      for (int64_t k = b; k < e; ++k) acc += load1(row(col[k]) + c);
+      if (own) acc = fmaf(epi.s, load1(own + c), acc);
+      out[t * out_stride + c] = Epi::kSum ? acc : acc * inv;
     }
   }
 }
 
-__global__ __launch_bounds__(kAggNT) void k_csr_mean_bwd(const int64_t* __restrict__ rowptr,
-                                                         const int64_t* __restrict__ col, int64_t T,
-                                                         const float* __restrict__ grad_out, int64_t go_stride,
-                                                         int64_t F, int lpr_log2, float* __restrict__ grad_x) {
+// the input gradient by scatter: grad_x[col[e],:] += w(t) * grad_out[t,:] for every edge (hardware fp32 atomics,
+// summation order not fixed); Mean: w = 1 / deg(t) and empty rows are skipped, Sum: w = 1
+template <class Epi>
+__global__ __launch_bounds__(kAggNT) void k_agg_bwd_scatter(const int64_t* __restrict__ rowptr,
+                                                            const int64_t* __restrict__ col, int64_t T,
+                                                            const float* __restrict__ grad_out, int64_t go_stride,
+                                                            int64_t F, int lpr_log2, float* __restrict__ grad_x) {
   const int lpr = 1 << lpr_log2;
   const int lane = threadIdx.x & (lpr - 1);
   const int64_t t = ((int64_t)blockIdx.x * kAggNT + threadIdx.x) >> lpr_log2;
   if (t >= T) return;
   const int64_t b = rowptr[t], e = rowptr[t + 1];
-  if (e <= b) return;
-  const float inv = 1.0f / (float)(e - b);
+  if (!Epi::kSum && e <= b) return;
+  const float w = Epi::kSum ? 1.f : 1.0f / (float)(e - b);
   for (int64_t c = lane; c < F; c += lpr) {
-    const float g = grad_out[t * go_stride + c] * inv;
+    const float g = grad_out[t * go_stride + c] * w;
     for (int64_t k = b; k < e; ++k) unsafeAtomicAdd(grad_x + col[k] * F + c, g);  // hardware fp32 atomic add
   }
 }
@@ -160,6 +195,16 @@ __global__ __launch_bounds__(kAggNT) void k_grad_init(const float* __restrict__ 
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (srow < T) v = *reinterpret_cast<const float4*>(grad_out + srow * go_stride + F + c);
     reinterpret_cast<float4*>(grad_x)[i] = v;
+  }
+}
+
+// the same for the sum: rows < T start from s * grad_out (the self term), the others from zero; any F
+__global__ __launch_bounds__(kAggNT) void k_sum_grad_init(const float* __restrict__ g, int64_t go_stride, int64_t T,
+                                                          int64_t S, int64_t F, float s, float* __restrict__ grad_x) {
+  const int64_t n = S * F;
+  for (int64_t i = (int64_t)blockIdx.x * kAggNT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kAggNT) {
+    const int64_t r = i / F, c = i - r * F;
+    grad_x[i] = r < T ? s * g[r * go_stride + c] : 0.f;
   }
 }
 
@@ -232,60 +277,84 @@ __global__ __launch_bounds__(kAggNT) void k_tr_count(const int64_t* __restrict__
   for (int64_t k = b; k < e; ++k) atomicAdd(&cnt[col[k]], 1);
 }
 
+// tcol[pos] = t for every entry (t, s) of the hop, pos in source s's segment; with tedge != NULL also tedge[pos] = k,
+// the entry's CSR position (GAT's attention weights are per entry)
 __global__ __launch_bounds__(kAggNT) void k_tr_fill(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,
                                                     int64_t T, const int32_t* __restrict__ start,
-                                                    int32_t* __restrict__ cursor, int32_t* __restrict__ tcol) {
+                                                    int32_t* __restrict__ cursor, int32_t* __restrict__ tcol,
+                                                    int32_t* __restrict__ tedge) {
   const int64_t t = (int64_t)blockIdx.x * kAggNT + threadIdx.x;
   if (t >= T) return;
   const int64_t b = rowptr[t], e = rowptr[t + 1];
   for (int64_t k = b; k < e; ++k) {
     const int64_t s = col[k];
-    tcol[start[s] + atomicAdd(&cursor[s], 1)] = (int32_t)t;
+    const int32_t pos = start[s] + atomicAdd(&cursor[s], 1);
+    tcol[pos] = (int32_t)t;
+    if (tedge) tedge[pos] = (int32_t)k;
   }
 }
 
-// grad_x[s,:] = (s < T ? grad_out[s, F:2F] : 0) + sum over the targets t of s: grad_out[t, :F] / deg(t)
-// kAct: grad_x is the gradient w.r.t. an ACTIVATED input whose pre-activation is z (dense [S, F]): the
-// ReLU + dropout backward (k_relu_dropout_bwd_pre) is applied to the row before it is stored, instead of a
-// separate read-modify-write pass over grad_x.
-template <bool kAct>
-__global__ __launch_bounds__(kAggNT) void k_operand_bwd_gather(const int32_t* __restrict__ start,
-                                                               const int32_t* __restrict__ tcol,
-                                                               const float* __restrict__ inv, int64_t T, int64_t S,
-                                                               const float* __restrict__ g, int64_t go_stride, int64_t F,
-                                                               int lpr_log2, float* __restrict__ grad_x,
-                                                               const float* __restrict__ z, ActArgs act) {
+// the input gradient by GATHER over the targets t of source s (tcol[start[s] .. start[s+1])), two rows at a time:
+//   Mean (SAGE's operand): (s < T ? grad_out[s, F:2F] : 0), added first, + sum_t grad_out[t, :F] * inv[t].  kAct: the
+//     ReLU + dropout backward (k_relu_dropout_bwd_pre) of the pre-activation z (dense [S, F]) is applied to the row
+//     before it is stored, instead of a separate read-modify-write pass over grad_x.
+//   Sum: sum_t grad_out[t, :] (inv is not read), then fmaf(s, grad_out[s, :], acc) for s < T.
+template <bool VEC4, class Epi>
+__global__ __launch_bounds__(kAggNT) void k_agg_bwd_gather(const int32_t* __restrict__ start,
+                                                           const int32_t* __restrict__ tcol,
+                                                           const float* __restrict__ inv, int64_t T, int64_t S,
+                                                           const float* __restrict__ g, int64_t go_stride, int64_t F,
+                                                           int lpr_log2, float* __restrict__ grad_x,
+                                                           const float* __restrict__ z, Epi epi) {
+  static_assert(VEC4 || Epi::kSum, "the operand's gradient has the vector form only");
   const int lpr = 1 << lpr_log2;
   const int lane = threadIdx.x & (lpr - 1);
   const int64_t srow = ((int64_t)blockIdx.x * kAggNT + threadIdx.x) >> lpr_log2;
   if (srow >= S) return;
   const int32_t b = start[srow], e = start[srow + 1];
-  for (int64_t c = (int64_t)lane * 4; c < F; c += (int64_t)lpr * 4) {
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (srow < T) acc = *reinterpret_cast<const float4*>(g + srow * go_stride + F + c);
-    int32_t k = b;
-    for (; k + 1 < e; k += 2) {  // two independent rows in flight
-      const int32_t t0 = tcol[k], t1 = tcol[k + 1];
-      const float w0 = inv[t0], w1 = inv[t1];
-      const float4 v0 = *reinterpret_cast<const float4*>(g + (int64_t)t0 * go_stride + c);
-      const float4 v1 = *reinterpret_cast<const float4*>(g + (int64_t)t1 * go_stride + c);
-      acc.x += v0.x * w0 + v1.x * w1; acc.y += v0.y * w0 + v1.y * w1;
-      acc.z += v0.z * w0 + v1.z * w1; acc.w += v0.w * w0 + v1.w * w1;
+  if constexpr (VEC4) {
+    auto w = [&](int32_t t) {  // the target's weight
+      if constexpr (Epi::kSum) return 1.f;
+      else return inv[t];
+    };
+    auto row4 = [&](int64_t t, int64_t c) { return *reinterpret_cast<const float4*>(g + t * go_stride + c); };
+    for (int64_t c = (int64_t)lane * 4; c < F; c += (int64_t)lpr * 4) {
+      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (!Epi::kSum && srow < T) acc = row4(srow, F + c);
+      int32_t k = b;
+      for (; k + 1 < e; k += 2) {  // two independent rows in flight
+        const int32_t t0 = tcol[k], t1 = tcol[k + 1];
+        const float w0 = w(t0), w1 = w(t1);
+        const float4 v0 = row4(t0, c), v1 = row4(t1, c);
+        acc.x += v0.x * w0 + v1.x * w1; acc.y += v0.y * w0 + v1.y * w1;
+        acc.z += v0.z * w0 + v1.z * w1; acc.w += v0.w * w0 + v1.w * w1;
+      }
+      if (k < e) {
+        const int32_t t0 = tcol[k];
+        const float w0 = w(t0);
+        const float4 v0 = row4(t0, c);
+        acc.x += v0.x * w0; acc.y += v0.y * w0; acc.z += v0.z * w0; acc.w += v0.w * w0;
+      }
+      if (Epi::kSum && srow < T) {
+        const float4 o = row4(srow, c);
+        acc = make_float4(fmaf(epi.s, o.x, acc.x), fmaf(epi.s, o.y, acc.y), fmaf(epi.s, o.z, acc.z), fmaf(epi.s, o.w, acc.w));
+      }
+      if constexpr (Epi::kAct) {
+        const float4 zv = *reinterpret_cast<const float4*>(z + srow * F + c);
+        const f4 m = relu_dropout4(f4{zv.x, zv.y, zv.z, zv.w}, (srow * F + c) >> 2, epi.act);  // > 0: z > 0 and kept
+        const float sc = epi.act.training ? epi.act.scale : 1.f;
+        acc = make_float4(m.x > 0.f ? acc.x * sc : 0.f, m.y > 0.f ? acc.y * sc : 0.f, m.z > 0.f ? acc.z * sc : 0.f,
+                          m.w > 0.f ? acc.w * sc : 0.f);
+      }
+      *reinterpret_cast<float4*>(grad_x + srow * F + c) = acc;
     }
-    if (k < e) {
-      const int32_t t0 = tcol[k];
-      const float w0 = inv[t0];
-      const float4 v0 = *reinterpret_cast<const float4*>(g + (int64_t)t0 * go_stride + c);
-      acc.x += v0.x * w0; acc.y += v0.y * w0; acc.z += v0.z * w0; acc.w += v0.w * w0;
+  } else {  // Sum, any F: one column per lane and step
+    for (int64_t c = lane; c < F; c += lpr) {
+      float acc = 0.f;
+      for (int32_t k = b; k < e; ++k) acc += g[(int64_t)tcol[k] * go_stride + c];
+      if (srow < T) acc = fmaf(epi.s, g[srow * go_stride + c], acc);
+      grad_x[srow * F + c] = acc;
     }
-    if constexpr (kAct) {
-      const float4 zv = *reinterpret_cast<const float4*>(z + srow * F + c);
-      const f4 m = relu_dropout4(f4{zv.x, zv.y, zv.z, zv.w}, (srow * F + c) >> 2, act);  // > 0: z > 0 and kept
-      const float sc = act.training ? act.scale : 1.f;
-      acc = make_float4(m.x > 0.f ? acc.x * sc : 0.f, m.y > 0.f ? acc.y * sc : 0.f, m.z > 0.f ? acc.z * sc : 0.f,
-                        m.w > 0.f ? acc.w * sc : 0.f);
-    }
-    *reinterpret_cast<float4*>(grad_x + srow * F + c) = acc;
   }
 }
 
@@ -295,28 +364,82 @@ static int lanes_log2(int64_t pieces) {
   return l;
 }
 
+// fn(Type<Tin>{}) for fp16 (half) or fp32 rows; with_elem_vec adds std::integral_constant<bool, VEC4>{}
+template <typename T> struct Type { using type = T; };
+template <class Fn>
+static void with_elem(int32_t half, Fn&& fn) {
+  half ? fn(Type<__half>{}) : fn(Type<float>{});
+}
+template <class Fn>
+static void with_elem_vec(int32_t half, bool vec, Fn&& fn) {
+  with_elem(half, [&](auto tin) { vec ? fn(tin, std::true_type{}) : fn(tin, std::false_type{}); });
+}
+
 }  // namespace spp
 
 using namespace spp;
 
-static spp_status mean_forward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
-                               const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t F,
-                               float* out_dev, int64_t out_stride_elems, int concat_target, void* stream,
-                               const int64_t* n_id_dev = nullptr, int64_t table_rows = 0);
+// ---- one launcher per kernel ----
+template <typename Tin, bool VEC4, class Src, class Epi>
+static void launch_agg_fwd(const int64_t* rowptr, const int64_t* col, int64_t T, const void* x, int64_t x_stride,
+                           const int64_t* nid, int64_t x_rows, int64_t F, Epi epi, float* out, int64_t out_stride,
+                           void* stream) {
+  const int lpr_log2 = lanes_log2(VEC4 ? F / 4 : F);
+  const unsigned grid = (unsigned)ceil_div(T << lpr_log2, kAggNT);
+  hipLaunchKernelGGL((k_agg_fwd<Tin, VEC4, Src, Epi>), dim3(grid), dim3(kAggNT), 0, as_stream(stream), rowptr, col, T,
+                     static_cast<const Tin*>(x), x_stride, F, lpr_log2, out, out_stride, epi, nid, x_rows);
+}
+
+template <class Epi>
+static void launch_agg_bwd_scatter(const int64_t* rowptr, const int64_t* col, int64_t T, const float* grad_out,
+                                   int64_t go_stride, int64_t F, float* grad_x, hipStream_t st) {
+  const int lpr_log2 = lanes_log2(F);
+  const unsigned grid = (unsigned)ceil_div(T << lpr_log2, kAggNT);
+  hipLaunchKernelGGL(k_agg_bwd_scatter<Epi>, dim3(grid), dim3(kAggNT), 0, st, rowptr, col, T, grad_out, go_stride, F,
+                     lpr_log2, grad_x);
+}
+
+// The forward entries' shared validation (`who` names the entry in the errors), the vector-width test and the launch.
+// Src: Dense (x = the batch's matrix), Table (x = the resident table, nid = the batch's n_id, x_rows its rows) or Refs
+// (nid = the row addresses; x, x_stride unused).  The sum entries have their row source's buffers checked here, the
+// mean entries check theirs themselves.
+template <class Src, class Epi>
+static spp_status agg_forward(const char* who, const int64_t* rowptr, const int64_t* col, int64_t T, const void* x,
+                              int32_t x_is_half, int64_t x_stride, const int64_t* nid, int64_t x_rows, int64_t F,
+                              Epi epi, float* out, int64_t out_stride, void* stream) {
+  constexpr bool kRefs = std::is_same<Src, Refs>::value;
+  SPP_REQUIRE(T >= 0 && F >= 0, "%s: negative size", who);
+  if (T == 0 || F == 0) return SPP_OK;
+  SPP_REQUIRE(rowptr && out && (!Epi::kSum || (kRefs ? nid != nullptr : x && (x_rows == 0 || nid))), "%s: NULL buffer",
+              who);
+  SPP_REQUIRE(kRefs || x_stride >= F, "%s: row stride smaller than the row", who);
+  if (out_stride <= 0) out_stride = F;
+  SPP_REQUIRE(out_stride >= F, "%s: output stride smaller than the row", who);
+  const int64_t esz = x_is_half ? 2 : 4;
+  // row references: 8-byte aligned fp16 / 16-byte aligned fp32 rows when F % 4 == 0 (spp_mfg_out.row_addr)
+  const bool vec = (F % 4 == 0) && (reinterpret_cast<uintptr_t>(out) % 16 == 0) && (out_stride % 4 == 0) &&
+                   (kRefs || (((x_stride * esz) % (4 * esz) == 0) && (reinterpret_cast<uintptr_t>(x) % (4 * esz) == 0)));
+  with_elem_vec(x_is_half, vec, [&](auto tin, auto v) {
+    launch_agg_fwd<typename decltype(tin)::type, decltype(v)::value, Src>(rowptr, col, T, x, x_stride, nid, x_rows, F,
+                                                                          epi, out, out_stride, stream);
+  });
+  SPP_HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
 
 extern "C" spp_status spp_csr_mean_forward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
                                            const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t F,
                                            float* out_dev, int64_t out_stride_elems, void* stream) {
-  return mean_forward(rowptr_dev, col_dev, num_targets, x_dev, x_is_half, x_stride_elems, F, out_dev, out_stride_elems,
-                      0, stream);
+  return agg_forward<Dense>("spp_csr_mean_forward", rowptr_dev, col_dev, num_targets, x_dev, x_is_half, x_stride_elems,
+                            nullptr, 0, F, Mean<false>{0, {}}, out_dev, out_stride_elems, stream);
 }
 
 extern "C" spp_status spp_sage_operand_forward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
                                                const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t F,
                                                float* out_dev, int64_t out_stride_elems, void* stream) {
   SPP_REQUIRE(out_stride_elems >= 2 * F, "spp_sage_operand_forward: the operand [mean | x_target] needs 2F columns");
-  return mean_forward(rowptr_dev, col_dev, num_targets, x_dev, x_is_half, x_stride_elems, F, out_dev, out_stride_elems,
-                      1, stream);
+  return agg_forward<Dense>("spp_csr_mean_forward", rowptr_dev, col_dev, num_targets, x_dev, x_is_half, x_stride_elems,
+                            nullptr, 0, F, Mean<false>{1, {}}, out_dev, out_stride_elems, stream);
 }
 
 extern "C" spp_status spp_sage_operand_forward_table(const int64_t* rowptr_dev, const int64_t* col_dev,
@@ -327,46 +450,9 @@ extern "C" spp_status spp_sage_operand_forward_table(const int64_t* rowptr_dev, 
   SPP_REQUIRE(out_stride_elems >= 2 * F, "spp_sage_operand_forward_table: the operand [mean | x_target] needs 2F columns");
   SPP_REQUIRE(num_targets == 0 || (n_id_dev && table_dev && table_rows > 0),
               "spp_sage_operand_forward_table: needs the feature table and the batch's node ids");
-  return mean_forward(rowptr_dev, col_dev, num_targets, table_dev, table_is_half, table_stride_elems, F, out_dev,
-                      out_stride_elems, 1, stream, n_id_dev, table_rows);
-}
-
-static spp_status mean_forward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
-                               const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t F,
-                               float* out_dev, int64_t out_stride_elems, int concat_target, void* stream,
-                               const int64_t* n_id_dev, int64_t table_rows) {
-  SPP_REQUIRE(num_targets >= 0 && F >= 0, "spp_csr_mean_forward: negative size");
-  if (num_targets == 0 || F == 0) return SPP_OK;
-  SPP_REQUIRE(rowptr_dev && out_dev, "spp_csr_mean_forward: NULL buffer");
-  SPP_REQUIRE(x_stride_elems >= F, "spp_csr_mean_forward: row stride smaller than the row");
-  if (out_stride_elems <= 0) out_stride_elems = F;
-  SPP_REQUIRE(out_stride_elems >= F, "spp_csr_mean_forward: output stride smaller than the row");
-  hipStream_t st = as_stream(stream);
-  const int64_t esz = x_is_half ? 2 : 4;
-  const bool vec = (F % 4 == 0) && ((x_stride_elems * esz) % (4 * esz) == 0) &&
-                   (reinterpret_cast<uintptr_t>(x_dev) % (4 * esz) == 0) &&
-                   (reinterpret_cast<uintptr_t>(out_dev) % 16 == 0) && (out_stride_elems % 4 == 0);
-  const int lpr_log2 = lanes_log2(vec ? F / 4 : F);
-  const unsigned grid = (unsigned)ceil_div(num_targets << lpr_log2, kAggNT);
-#define SPP_AGG(TIN, V)                                                                                               \
-  do {                                                                                                                \
-    if (n_id_dev)                                                                                                     \
-      hipLaunchKernelGGL((k_csr_mean_fwd<TIN, V, false, true>), dim3(grid), dim3(kAggNT), 0, st, rowptr_dev, col_dev, \
-                         num_targets, static_cast<const TIN*>(x_dev), x_stride_elems, F, lpr_log2, out_dev,           \
-                         out_stride_elems, concat_target, ActArgs{}, n_id_dev, table_rows);                           \
-    else                                                                                                              \
-      hipLaunchKernelGGL((k_csr_mean_fwd<TIN, V>), dim3(grid), dim3(kAggNT), 0, st, rowptr_dev, col_dev, num_targets, \
-                         static_cast<const TIN*>(x_dev), x_stride_elems, F, lpr_log2, out_dev, out_stride_elems,      \
-                         concat_target, ActArgs{}, nullptr, (int64_t)0);                                              \
-  } while (0)
-  if (x_is_half) {
-    if (vec) SPP_AGG(__half, true); else SPP_AGG(__half, false);
-  } else {
-    if (vec) SPP_AGG(float, true); else SPP_AGG(float, false);
-  }
-#undef SPP_AGG
-  SPP_HIP_TRY(hipGetLastError());
-  return SPP_OK;
+  return agg_forward<Table>("spp_csr_mean_forward", rowptr_dev, col_dev, num_targets, table_dev, table_is_half,
+                            table_stride_elems, n_id_dev, table_rows, F, Mean<false>{1, {}}, out_dev, out_stride_elems,
+                            stream);
 }
 
 extern "C" spp_status spp_sage_operand_forward_rows(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
@@ -378,17 +464,10 @@ extern "C" spp_status spp_sage_operand_forward_rows(const int64_t* rowptr_dev, c
   SPP_REQUIRE(out_stride_elems >= 2 * F, "spp_sage_operand_forward_rows: the operand [mean | x_target] needs 2F columns");
   SPP_REQUIRE(F % 4 == 0 && (reinterpret_cast<uintptr_t>(out_dev) % 16 == 0) && (out_stride_elems % 4 == 0),
               "spp_sage_operand_forward_rows: needs F %% 4 == 0 and a 16-byte aligned operand (F = %lld)", (long long)F);
-  hipStream_t st = as_stream(stream);
-  const int lpr_log2 = lanes_log2(F / 4);
-  const unsigned grid = (unsigned)ceil_div(num_targets << lpr_log2, kAggNT);
-  if (rows_are_half)
-    hipLaunchKernelGGL((k_csr_mean_fwd<__half, true, false, false, true>), dim3(grid), dim3(kAggNT), 0, st, rowptr_dev, col_dev,
-                       num_targets, static_cast<const __half*>(nullptr), (int64_t)0, F, lpr_log2, out_dev, out_stride_elems, 1,
-                       ActArgs{}, row_addr_dev, (int64_t)0);
-  else
-    hipLaunchKernelGGL((k_csr_mean_fwd<float, true, false, false, true>), dim3(grid), dim3(kAggNT), 0, st, rowptr_dev, col_dev,
-                       num_targets, static_cast<const float*>(nullptr), (int64_t)0, F, lpr_log2, out_dev, out_stride_elems, 1,
-                       ActArgs{}, row_addr_dev, (int64_t)0);
+  with_elem(rows_are_half, [&](auto tin) {
+    launch_agg_fwd<typename decltype(tin)::type, true, Refs>(rowptr_dev, col_dev, num_targets, nullptr, 0, row_addr_dev,
+                                                             0, F, Mean<false>{1, {}}, out_dev, out_stride_elems, stream);
+  });
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
 }
@@ -412,11 +491,8 @@ extern "C" spp_status spp_sage_operand_forward_act(const int64_t* rowptr_dev, co
   SPP_REQUIRE(rowptr_dev && x_dev && out_dev && out_stride_elems >= 2 * F && F % 4 == 0 && out_stride_elems % 4 == 0 &&
                   reinterpret_cast<uintptr_t>(x_dev) % 16 == 0 && reinterpret_cast<uintptr_t>(out_dev) % 16 == 0,
               "spp_sage_operand_forward_act: needs dense fp32 rows with F %% 4 == 0 and 16-byte aligned buffers");
-  const int lpr_log2 = lanes_log2(F / 4);
-  const unsigned grid = (unsigned)ceil_div(num_targets << lpr_log2, kAggNT);
-  hipLaunchKernelGGL((k_csr_mean_fwd<float, true, true>), dim3(grid), dim3(kAggNT), 0, as_stream(stream), rowptr_dev,
-                     col_dev, num_targets, x_dev, F, F, lpr_log2, out_dev, out_stride_elems, 1, act_args(p, training, seed),
-                     nullptr, (int64_t)0);
+  launch_agg_fwd<float, true, Dense>(rowptr_dev, col_dev, num_targets, x_dev, F, nullptr, 0, F,
+                                     Mean<true>{1, act_args(p, training, seed)}, out_dev, out_stride_elems, stream);
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
 }
@@ -444,10 +520,8 @@ extern "C" spp_status spp_csr_mean_backward(const int64_t* rowptr_dev, const int
   SPP_REQUIRE(rowptr_dev && grad_out_dev && grad_x_dev, "spp_csr_mean_backward: NULL buffer");
   if (grad_out_stride_elems <= 0) grad_out_stride_elems = F;
   SPP_REQUIRE(grad_out_stride_elems >= F, "spp_csr_mean_backward: gradient stride smaller than the row");
-  const int lpr_log2 = lanes_log2(F);
-  const unsigned grid = (unsigned)ceil_div(num_targets << lpr_log2, kAggNT);
-  hipLaunchKernelGGL(k_csr_mean_bwd, dim3(grid), dim3(kAggNT), 0, as_stream(stream), rowptr_dev, col_dev, num_targets,
-                     grad_out_dev, grad_out_stride_elems, F, lpr_log2, grad_x_dev);
+  launch_agg_bwd_scatter<Mean<false>>(rowptr_dev, col_dev, num_targets, grad_out_dev, grad_out_stride_elems, F,
+                                      grad_x_dev, as_stream(stream));
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
 }
@@ -473,32 +547,39 @@ extern "C" spp_status spp_sage_operand_backward(const int64_t* rowptr_dev, const
                                stream);
 }
 
-extern "C" int64_t spp_sage_operand_backward_workspace_bytes(int64_t num_targets, int64_t num_sources,
-                                                               int64_t num_edges) {
+static int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
+
+// The workspace of transpose_hop: cnt/cursor [S+1] | start [S+1] | tcol [E] | tedge [E] (edge_ids) | inv [T] | scan
+// temporaries   (each 16-byte aligned)
+static int64_t transpose_hop_bytes(int64_t T, int64_t S, int64_t E, bool edge_ids) {
   size_t scan_tmp = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tmp, (const int32_t*)nullptr, (int32_t*)nullptr,
-                                         (int)(num_sources + 1));
-  // cnt/cursor [S+1] | start [S+1] | tcol [E] | inv [T] | scan temporaries   (each 16-byte aligned)
-  auto up = [](int64_t v) { return (v + 15) & ~(int64_t)15; };
-  return up(4 * (num_sources + 1)) * 2 + up(4 * num_edges) + up(4 * num_targets) + up((int64_t)scan_tmp) + 64;
+  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tmp, (const int32_t*)nullptr, (int32_t*)nullptr, (int)(S + 1));
+  return align16(4 * (S + 1)) * 2 + align16(4 * E) * (edge_ids ? 2 : 1) + align16(4 * T) + align16((int64_t)scan_tmp) + 64;
 }
 
-// The transposed hop (sources -> targets) in a spp_sage_operand_backward_workspace_bytes workspace: source s's targets
-// are tcol[start[s] .. start[s+1]), inv[t] = 1 / max(deg t, 1).  Count, scan, fill; the callers have checked the sizes.
+extern "C" int64_t spp_sage_operand_backward_workspace_bytes(int64_t num_targets, int64_t num_sources,
+                                                               int64_t num_edges) {
+  return transpose_hop_bytes(num_targets, num_sources, num_edges, false);
+}
+
+struct TransposedHop {
+  const int32_t *start, *tcol, *tedge;
+  const float* inv;
+};
+
+// The transposed hop (sources -> targets) in a transpose_hop_bytes workspace: source s's targets are
+// tcol[start[s] .. start[s+1]), with edge_ids tedge[] holds the CSR entry of each, inv[t] = 1 / max(deg t, 1).
+// Count, scan, fill; the callers have checked the sizes.
 static spp_status transpose_hop(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
-                                int64_t num_sources, int64_t num_edges, void* workspace_dev, int64_t workspace_bytes,
-                                hipStream_t st, const int32_t** start_out, const int32_t** tcol_out,
-                                const float** inv_out) {
-  auto up = [](int64_t v) { return (v + 15) & ~(int64_t)15; };
+                                int64_t num_sources, int64_t num_edges, bool edge_ids, void* workspace_dev,
+                                int64_t workspace_bytes, hipStream_t st, TransposedHop* hop) {
   char* w = static_cast<char*>(workspace_dev);
-  int32_t* cnt = reinterpret_cast<int32_t*>(w);
-  w += up(4 * (num_sources + 1));
-  int32_t* start = reinterpret_cast<int32_t*>(w);
-  w += up(4 * (num_sources + 1));
-  int32_t* tcol = reinterpret_cast<int32_t*>(w);
-  w += up(4 * num_edges);
-  float* inv = reinterpret_cast<float*>(w);
-  w += up(4 * num_targets);
+  auto take = [&](int64_t bytes) { int32_t* p = reinterpret_cast<int32_t*>(w); w += align16(bytes); return p; };
+  int32_t* cnt = take(4 * (num_sources + 1));
+  int32_t* start = take(4 * (num_sources + 1));
+  int32_t* tcol = take(4 * num_edges);
+  int32_t* tedge = edge_ids ? take(4 * num_edges) : nullptr;
+  float* inv = reinterpret_cast<float*>(take(4 * num_targets));
   size_t scan_tmp = (size_t)(workspace_bytes - (w - static_cast<char*>(workspace_dev)));
   SPP_HIP_TRY(hipMemsetAsync(cnt, 0, 4 * (size_t)(num_sources + 1), st));
   const unsigned gt = (unsigned)std::max<int64_t>(1, ceil_div(num_targets, kAggNT));
@@ -507,43 +588,50 @@ static spp_status transpose_hop(const int64_t* rowptr_dev, const int64_t* col_de
   SPP_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(w, scan_tmp, cnt, start, (int)(num_sources + 1), st));
   SPP_HIP_TRY(hipMemsetAsync(cnt, 0, 4 * (size_t)(num_sources + 1), st));
   if (num_targets > 0)
-    hipLaunchKernelGGL(k_tr_fill, dim3(gt), dim3(kAggNT), 0, st, rowptr_dev, col_dev, num_targets, start, cnt, tcol);
-  *start_out = start;
-  *tcol_out = tcol;
-  *inv_out = inv;
+    hipLaunchKernelGGL(k_tr_fill, dim3(gt), dim3(kAggNT), 0, st, rowptr_dev, col_dev, num_targets, start, cnt, tcol,
+                       tedge);
+  *hop = {start, tcol, tedge, inv};
   return SPP_OK;
 }
 
-static spp_status operand_backward_gather(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
-                                          int64_t num_sources, int64_t num_edges, const float* grad_out_dev,
-                                          int64_t grad_out_stride_elems, int64_t F, float* grad_x_dev,
-                                          void* workspace_dev, int64_t workspace_bytes, const float* z_pre_dev,
-                                          ActArgs act, void* stream) {
-  SPP_REQUIRE(num_targets >= 0 && num_sources >= num_targets && F >= 0 && num_edges >= 0,
-              "spp_sage_operand_backward_gather: bad sizes");
+// The gather-form backward entries: their shared validation (`who` names the entry), the transposed hop and the
+// launch of k_agg_bwd_gather.  The operand's (Mean) gradient has the vector form only; the sum's takes any F and row stride.
+template <class Epi>
+static spp_status agg_backward_gather(const char* who, const int64_t* rowptr_dev, const int64_t* col_dev,
+                                      int64_t num_targets, int64_t num_sources, int64_t num_edges,
+                                      const float* grad_out_dev, int64_t grad_out_stride_elems, int64_t F, Epi epi,
+                                      float* grad_x_dev, void* workspace_dev, int64_t workspace_bytes,
+                                      const float* z_pre_dev, void* stream) {
+  SPP_REQUIRE(num_targets >= 0 && num_sources >= num_targets && F >= 0 && num_edges >= 0, "%s: bad sizes", who);
   if (num_sources == 0 || F == 0) return SPP_OK;
-  SPP_REQUIRE(num_sources < (1ll << 31) && num_edges < (1ll << 31), "spp_sage_operand_backward_gather: 32-bit indices");
-  SPP_REQUIRE(grad_x_dev && workspace_dev && (grad_out_dev || num_targets == 0),
-              "spp_sage_operand_backward_gather: NULL buffer");
-  SPP_REQUIRE(F % 4 == 0 && grad_out_stride_elems >= 2 * F && grad_out_stride_elems % 4 == 0 &&
-                  reinterpret_cast<uintptr_t>(grad_out_dev) % 16 == 0 && reinterpret_cast<uintptr_t>(grad_x_dev) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(workspace_dev) % 16 == 0,
-              "spp_sage_operand_backward_gather: needs F %% 4 == 0 and 16-byte aligned buffers");
-  SPP_REQUIRE(workspace_bytes >= spp_sage_operand_backward_workspace_bytes(num_targets, num_sources, num_edges),
-              "spp_sage_operand_backward_gather: workspace too small");
-  hipStream_t st = as_stream(stream);
-  const int32_t *start, *tcol;
-  const float* inv;
-  SPP_TRY(transpose_hop(rowptr_dev, col_dev, num_targets, num_sources, num_edges, workspace_dev, workspace_bytes, st,
-                        &start, &tcol, &inv));
-  const int lpr_log2 = lanes_log2(F / 4);
-  const unsigned grid = (unsigned)ceil_div(num_sources << lpr_log2, kAggNT);
-  if (z_pre_dev)
-    hipLaunchKernelGGL(k_operand_bwd_gather<true>, dim3(grid), dim3(kAggNT), 0, st, start, tcol, inv, num_targets,
-                       num_sources, grad_out_dev, grad_out_stride_elems, F, lpr_log2, grad_x_dev, z_pre_dev, act);
+  SPP_REQUIRE(num_sources < (1ll << 31) && num_edges < (1ll << 31), "%s: 32-bit indices", who);
+  SPP_REQUIRE(grad_x_dev && workspace_dev && ((grad_out_dev && (rowptr_dev || !Epi::kSum)) || num_targets == 0),
+              "%s: NULL buffer", who);
+  if (Epi::kSum && grad_out_stride_elems <= 0) grad_out_stride_elems = F;
+  const bool vec = F % 4 == 0 && grad_out_stride_elems % 4 == 0 &&
+                   (reinterpret_cast<uintptr_t>(grad_out_dev) | reinterpret_cast<uintptr_t>(grad_x_dev)) % 16 == 0;
+  const bool ws_aligned = reinterpret_cast<uintptr_t>(workspace_dev) % 16 == 0;
+  if (Epi::kSum)
+    SPP_REQUIRE(grad_out_stride_elems >= F && ws_aligned,
+                "%s: gradient stride smaller than the row or unaligned workspace", who);
   else
-    hipLaunchKernelGGL(k_operand_bwd_gather<false>, dim3(grid), dim3(kAggNT), 0, st, start, tcol, inv, num_targets,
-                       num_sources, grad_out_dev, grad_out_stride_elems, F, lpr_log2, grad_x_dev, nullptr, ActArgs{});
+    SPP_REQUIRE(vec && grad_out_stride_elems >= 2 * F && ws_aligned, "%s: needs F %% 4 == 0 and 16-byte aligned buffers",
+                who);
+  SPP_REQUIRE(workspace_bytes >= spp_sage_operand_backward_workspace_bytes(num_targets, num_sources, num_edges),
+              "%s: workspace too small", who);
+  hipStream_t st = as_stream(stream);
+  TransposedHop hop;
+  SPP_TRY(transpose_hop(rowptr_dev, col_dev, num_targets, num_sources, num_edges, false, workspace_dev, workspace_bytes,
+                        st, &hop));
+  const int lpr_log2 = lanes_log2(vec ? F / 4 : F);
+  const unsigned grid = (unsigned)ceil_div(num_sources << lpr_log2, kAggNT);
+  auto launch = [&](auto v) {
+    hipLaunchKernelGGL((k_agg_bwd_gather<decltype(v)::value, Epi>), dim3(grid), dim3(kAggNT), 0, st, hop.start, hop.tcol,
+                       hop.inv, num_targets, num_sources, grad_out_dev, grad_out_stride_elems, F, lpr_log2, grad_x_dev,
+                       z_pre_dev, epi);
+  };
+  if (vec) launch(std::true_type{});
+  else if constexpr (Epi::kSum) launch(std::false_type{});
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
 }
@@ -553,9 +641,9 @@ extern "C" spp_status spp_sage_operand_backward_gather(const int64_t* rowptr_dev
                                                        const float* grad_out_dev, int64_t grad_out_stride_elems,
                                                        int64_t F, float* grad_x_dev, void* workspace_dev,
                                                        int64_t workspace_bytes, void* stream) {
-  return operand_backward_gather(rowptr_dev, col_dev, num_targets, num_sources, num_edges, grad_out_dev,
-                                 grad_out_stride_elems, F, grad_x_dev, workspace_dev, workspace_bytes, nullptr, ActArgs{},
-                                 stream);
+  return agg_backward_gather("spp_sage_operand_backward_gather", rowptr_dev, col_dev, num_targets, num_sources,
+                             num_edges, grad_out_dev, grad_out_stride_elems, F, Mean<false>{1, {}}, grad_x_dev,
+                             workspace_dev, workspace_bytes, nullptr, stream);
 }
 
 // the same, followed in the same pass by the ReLU + dropout backward of spp_relu_dropout_backward_pre: grad_x
@@ -568,9 +656,9 @@ extern "C" spp_status spp_sage_operand_backward_gather_act(const int64_t* rowptr
                                                            int32_t training, uint64_t seed, void* stream) {
   SPP_REQUIRE(z_pre_dev && reinterpret_cast<uintptr_t>(z_pre_dev) % 16 == 0 && p >= 0.f && p < 1.f,
               "spp_sage_operand_backward_gather_act: NULL / unaligned pre-activation or bad p");
-  return operand_backward_gather(rowptr_dev, col_dev, num_targets, num_sources, num_edges, grad_out_dev,
-                                 grad_out_stride_elems, F, grad_x_dev, workspace_dev, workspace_bytes, z_pre_dev,
-                                 act_args(p, training, seed), stream);
+  return agg_backward_gather("spp_sage_operand_backward_gather", rowptr_dev, col_dev, num_targets, num_sources,
+                             num_edges, grad_out_dev, grad_out_stride_elems, F, Mean<true>{1, act_args(p, training, seed)},
+                             grad_x_dev, workspace_dev, workspace_bytes, z_pre_dev, stream);
 }
 
 extern "C" spp_status spp_relu_dropout_forward(const float* x_dev, int64_t n, float p, int32_t training, uint64_t seed,
@@ -967,22 +1055,6 @@ __global__ __launch_bounds__(kAggNT) void k_gat_agg_bwd(const int64_t* __restric
   if (live && lane == 0) grad_a_dst[t] = gad;
 }
 
-// transposed hop with the CSR entry of every (source, target) pair kept: tedge[pos] = k, ttgt[pos] = t
-__global__ __launch_bounds__(kAggNT) void k_tr_fill_e(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,
-                                                      int64_t T, const int32_t* __restrict__ start,
-                                                      int32_t* __restrict__ cursor, int32_t* __restrict__ ttgt,
-                                                      int32_t* __restrict__ tedge) {
-  const int64_t t = (int64_t)blockIdx.x * kAggNT + threadIdx.x;
-  if (t >= T) return;
-  const int64_t b = rowptr[t], e = rowptr[t + 1];
-  for (int64_t k = b; k < e; ++k) {
-    const int64_t s = col[k];
-    const int32_t pos = start[s] + atomicAdd(&cursor[s], 1);
-    ttgt[pos] = (int32_t)t;
-    tedge[pos] = (int32_t)k;
-  }
-}
-
 // Input gradient of the aggregate-then-project GAT layer by GATHER (no fp32 atomics, no zero fill, no separate rank-1
 // passes):  grad_x[s,:] = sum over the targets t of s: alpha_ts grad_z[t,:]  (+ the self loop's alpha_ss grad_z[s,:], s < T)
 //                         + grad_a_src[s] v_src  (+ grad_a_dst[s] v_dst, s < T)        -- a_src = x v_src, a_dst = x[:T] v_dst
@@ -1051,12 +1123,11 @@ extern "C" spp_status spp_gat_logits(const void* x_dev, int32_t x_is_half, int64
               "spp_gat_logits: NULL or unaligned buffer");
   const int lpr_log2 = lanes_log2(K / 4);
   const unsigned grid = (unsigned)ceil_div(ceil_div(num_sources, kDotRows) << lpr_log2, kAggNT);
-  if (x_is_half)
-    hipLaunchKernelGGL(k_rowdot2<__half>, dim3(grid), dim3(kAggNT), 0, as_stream(stream), static_cast<const __half*>(x_dev),
+  with_elem(x_is_half, [&](auto tin) {
+    using Tin = typename decltype(tin)::type;
+    hipLaunchKernelGGL(k_rowdot2<Tin>, dim3(grid), dim3(kAggNT), 0, as_stream(stream), static_cast<const Tin*>(x_dev),
                        x_stride_elems, num_sources, num_targets, K, v_src_dev, v_dst_dev, lpr_log2, a_src_dev, a_dst_dev);
-  else
-    hipLaunchKernelGGL(k_rowdot2<float>, dim3(grid), dim3(kAggNT), 0, as_stream(stream), static_cast<const float*>(x_dev),
-                       x_stride_elems, num_sources, num_targets, K, v_src_dev, v_dst_dev, lpr_log2, a_src_dev, a_dst_dev);
+  });
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
 }
@@ -1077,14 +1148,12 @@ extern "C" spp_status spp_gat_logits_backward(const void* x_dev, int32_t x_is_ha
   // between 1024 and 4096 rows each
   const int64_t rows_per_wg = std::max<int64_t>(1024, std::min<int64_t>(4096, ceil_div(num_sources, 256)));
   const unsigned grid = (unsigned)ceil_div(num_sources, rows_per_wg);
-  if (x_is_half)
-    hipLaunchKernelGGL(k_colsum2<__half>, dim3(grid), dim3(kColsumNT), 0, st, static_cast<const __half*>(x_dev), x_stride_elems,
+  with_elem(x_is_half, [&](auto tin) {
+    using Tin = typename decltype(tin)::type;
+    hipLaunchKernelGGL(k_colsum2<Tin>, dim3(grid), dim3(kColsumNT), 0, st, static_cast<const Tin*>(x_dev), x_stride_elems,
                        num_sources, num_targets, K, grad_a_src_dev, grad_a_dst_dev, rows_per_wg, grad_v_src_dev,
                        grad_v_dst_dev);
-  else
-    hipLaunchKernelGGL(k_colsum2<float>, dim3(grid), dim3(kColsumNT), 0, st, static_cast<const float*>(x_dev), x_stride_elems,
-                       num_sources, num_targets, K, grad_a_src_dev, grad_a_dst_dev, rows_per_wg, grad_v_src_dev,
-                       grad_v_dst_dev);
+  });
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
 }
@@ -1100,14 +1169,12 @@ extern "C" spp_status spp_gat_aggregate_forward(const int64_t* rowptr_dev, const
                   reinterpret_cast<uintptr_t>(z_dev) % 16 == 0, "spp_gat_aggregate_forward: NULL or unaligned buffer");
   const int lpr_log2 = lanes_log2(K / 4);
   const unsigned grid = (unsigned)ceil_div(num_targets << lpr_log2, kAggNT);
-  if (x_is_half)
-    hipLaunchKernelGGL(k_gat_agg_fwd<__half>, dim3(grid), dim3(kAggNT), 0, as_stream(stream), rowptr_dev, col_dev,
-                       num_targets, static_cast<const __half*>(x_dev), x_stride_elems, K, a_src_dev, a_dst_dev,
+  with_elem(x_is_half, [&](auto tin) {
+    using Tin = typename decltype(tin)::type;
+    hipLaunchKernelGGL(k_gat_agg_fwd<Tin>, dim3(grid), dim3(kAggNT), 0, as_stream(stream), rowptr_dev, col_dev,
+                       num_targets, static_cast<const Tin*>(x_dev), x_stride_elems, K, a_src_dev, a_dst_dev,
                        negative_slope, lpr_log2, z_dev, row_max_dev, row_sum_dev);
-  else
-    hipLaunchKernelGGL(k_gat_agg_fwd<float>, dim3(grid), dim3(kAggNT), 0, as_stream(stream), rowptr_dev, col_dev,
-                       num_targets, static_cast<const float*>(x_dev), x_stride_elems, K, a_src_dev, a_dst_dev,
-                       negative_slope, lpr_log2, z_dev, row_max_dev, row_sum_dev);
+  });
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
 }
@@ -1145,30 +1212,21 @@ static spp_status gat_aggregate_backward_launch(const int64_t* rowptr_dev, const
   const bool vec = grad_x_dev == nullptr;
   const int lpt_log2 = lanes_log2(vec ? K / 4 : K);
   const unsigned grid = (unsigned)ceil_div(num_targets << lpt_log2, kAggNT);
-#define SPP_GAT_BWD(TIN, V)                                                                                            \
-  hipLaunchKernelGGL((k_gat_agg_bwd<TIN, V>), dim3(grid), dim3(kAggNT), 0, as_stream(stream), rowptr_dev, col_dev,       \
-                     num_targets, static_cast<const TIN*>(x_dev), x_stride_elems, K, a_src_dev, a_dst_dev,            \
-                     negative_slope, z_dev, row_max_dev, row_sum_dev, grad_z_dev, lpt_log2, grad_x_dev, grad_a_src_dev, \
-                     grad_a_dst_dev, alpha_e, alpha_self)
-  if (x_is_half) {
-    if (vec) SPP_GAT_BWD(__half, true); else SPP_GAT_BWD(__half, false);
-  } else {
-    if (vec) SPP_GAT_BWD(float, true); else SPP_GAT_BWD(float, false);
-  }
-#undef SPP_GAT_BWD
+  with_elem_vec(x_is_half, vec, [&](auto tin, auto v) {
+    using Tin = typename decltype(tin)::type;
+    hipLaunchKernelGGL((k_gat_agg_bwd<Tin, decltype(v)::value>), dim3(grid), dim3(kAggNT), 0, as_stream(stream), rowptr_dev,
+                       col_dev, num_targets, static_cast<const Tin*>(x_dev), x_stride_elems, K, a_src_dev, a_dst_dev,
+                       negative_slope, z_dev, row_max_dev, row_sum_dev, grad_z_dev, lpt_log2, grad_x_dev, grad_a_src_dev,
+                       grad_a_dst_dev, alpha_e, alpha_self);
+  });
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
 }
 
 extern "C" int64_t spp_gat_aggregate_backward_gather_workspace_bytes(int64_t num_targets, int64_t num_sources,
                                                                      int64_t num_edges) {
-  size_t scan_tmp = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tmp, (const int32_t*)nullptr, (int32_t*)nullptr,
-                                         (int)(num_sources + 1));
-  // cnt/cursor [S+1] | start [S+1] | ttgt [E] | tedge [E] | alpha_e [E] | alpha_self [T] | inv [T] (k_tr_count's by-product)
-  // | scan temporaries   (each 16-byte aligned)
-  auto up = [](int64_t v) { return (v + 15) & ~(int64_t)15; };
-  return up(4 * (num_sources + 1)) * 2 + 3 * up(4 * num_edges) + 2 * up(4 * num_targets) + up((int64_t)scan_tmp) + 64;
+  // alpha_e [E] | alpha_self [T] | the transposed hop with edge ids   (each 16-byte aligned)
+  return align16(4 * num_edges) + align16(4 * num_targets) + transpose_hop_bytes(num_targets, num_sources, num_edges, true);
 }
 
 // spp_gat_aggregate_backward with the input gradient by GATHER over the transposed hop: grad_x [S, K] is written
@@ -1199,41 +1257,22 @@ extern "C" spp_status spp_gat_aggregate_backward_gather(const int64_t* rowptr_de
   SPP_REQUIRE(workspace_bytes >= spp_gat_aggregate_backward_gather_workspace_bytes(num_targets, num_sources, num_edges),
               "spp_gat_aggregate_backward_gather: workspace too small");
   hipStream_t st = as_stream(stream);
-  auto up = [](int64_t v) { return (v + 15) & ~(int64_t)15; };
-  char* w = static_cast<char*>(workspace_dev);
-  int32_t* cnt = reinterpret_cast<int32_t*>(w);
-  w += up(4 * (num_sources + 1));
-  int32_t* start = reinterpret_cast<int32_t*>(w);
-  w += up(4 * (num_sources + 1));
-  int32_t* ttgt = reinterpret_cast<int32_t*>(w);
-  w += up(4 * num_edges);
-  int32_t* tedge = reinterpret_cast<int32_t*>(w);
-  w += up(4 * num_edges);
-  float* alpha_e = reinterpret_cast<float*>(w);
-  w += up(4 * num_edges);
-  float* alpha_self = reinterpret_cast<float*>(w);
-  w += up(4 * num_targets);
-  float* inv = reinterpret_cast<float*>(w);
-  w += up(4 * num_targets);
-  size_t scan_tmp = (size_t)(workspace_bytes - (w - static_cast<char*>(workspace_dev)));
+  float* alpha_e = static_cast<float*>(workspace_dev);
+  float* alpha_self = alpha_e + align16(4 * num_edges) / 4;
+  const int64_t alpha_bytes = align16(4 * num_edges) + align16(4 * num_targets);
   // the attention weights of every entry + grad_a_src / grad_a_dst (no input gradient by atomics)
   if (num_targets > 0)
     SPP_TRY(gat_aggregate_backward_launch(rowptr_dev, col_dev, num_targets, x_dev, x_is_half, x_stride_elems, K, a_src_dev,
                                           a_dst_dev, negative_slope, z_dev, row_max_dev, row_sum_dev, grad_z_dev, nullptr,
                                           grad_a_src_dev, grad_a_dst_dev, alpha_e, alpha_self, stream));
-  // the transposed hop: count, scan, fill
-  SPP_HIP_TRY(hipMemsetAsync(cnt, 0, 4 * (size_t)(num_sources + 1), st));
-  const unsigned gt = (unsigned)std::max<int64_t>(1, ceil_div(num_targets, kAggNT));
-  if (num_targets > 0)
-    hipLaunchKernelGGL(k_tr_count, dim3(gt), dim3(kAggNT), 0, st, rowptr_dev, col_dev, num_targets, cnt, inv);
-  SPP_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(w, scan_tmp, cnt, start, (int)(num_sources + 1), st));
-  SPP_HIP_TRY(hipMemsetAsync(cnt, 0, 4 * (size_t)(num_sources + 1), st));
-  if (num_targets > 0)
-    hipLaunchKernelGGL(k_tr_fill_e, dim3(gt), dim3(kAggNT), 0, st, rowptr_dev, col_dev, num_targets, start, cnt, ttgt, tedge);
+  TransposedHop hop;
+  SPP_TRY(transpose_hop(rowptr_dev, col_dev, num_targets, num_sources, num_edges, true,
+                        static_cast<char*>(workspace_dev) + alpha_bytes, workspace_bytes - alpha_bytes, st, &hop));
   const int lpr_log2 = lanes_log2(K / 4);
   const unsigned grid = (unsigned)ceil_div(num_sources << lpr_log2, kAggNT);
-  hipLaunchKernelGGL(k_gat_gx_gather, dim3(grid), dim3(kAggNT), 0, st, start, ttgt, tedge, alpha_e, alpha_self, num_targets,
-                     num_sources, grad_z_dev, K, lpr_log2, grad_a_src_dev, grad_a_dst_dev, v_src_dev, v_dst_dev, grad_x_dev);
+  hipLaunchKernelGGL(k_gat_gx_gather, dim3(grid), dim3(kAggNT), 0, st, hop.start, hop.tcol, hop.tedge, alpha_e, alpha_self,
+                     num_targets, num_sources, grad_z_dev, K, lpr_log2, grad_a_src_dev, grad_a_dst_dev, v_src_dev,
+                     v_dst_dev, grad_x_dev);
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
 }
@@ -1278,177 +1317,13 @@ extern "C" spp_status spp_gat_backward(const int64_t* rowptr_dev, const int64_t*
 //     out[t,:]    = s * x[t,:] + sum_{e in row t} x[col[e],:]                    s = 1 + eps   forward
 //     grad_x[j,:] = (j < T ? s * grad_out[j,:] : 0) + sum_{e: col[e] = j} grad_out[row e,:]    backward
 // Every entry of the row counts (duplicates and self edges included); targets are the first T rows of x.
-// Same lane layout as k_csr_mean_fwd, and the same three first-layer inputs (x, table + n_id, row
-// addresses).  The gather backward walks the transposed hop the mean's backward builds (transpose_hop).
+// The mean's kernels and row sources with the Sum epilogue; the same transposed hop for the gather backward.
 // ================================================================================================
-namespace spp {
-
-// s == 0: the target's own row is not read (a foreign x_target is added by the caller)
-template <typename Tin, bool VEC4, bool kTable = false, bool kRefs = false>
-__global__ __launch_bounds__(kAggNT) void k_csr_sum_fwd(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,
-                                                        int64_t T, const Tin* __restrict__ x, int64_t x_stride, int64_t F,
-                                                        int lpr_log2, float s, float* __restrict__ out, int64_t out_stride,
-                                                        const int64_t* __restrict__ nid, int64_t x_rows) {
-  const int lpr = 1 << lpr_log2;
-  const int lane = threadIdx.x & (lpr - 1);
-  const int64_t t = ((int64_t)blockIdx.x * kAggNT + threadIdx.x) >> lpr_log2;
-  if (t >= T) return;
-  const int64_t b = rowptr[t], e = rowptr[t + 1];
-  auto row = [&](int64_t j) -> const Tin* {  // where row j of the batch starts
-    if constexpr (kRefs) return reinterpret_cast<const Tin*>((uintptr_t)nid[j]);
-    if constexpr (kTable) {
-      const int64_t g = nid[j];
-      j = (uint64_t)g < (uint64_t)x_rows ? g : 0;
-    }
-    return x + j * x_stride;
-  };
-  const Tin* own = s != 0.f ? row(t) : nullptr;
-  if (VEC4) {
-    for (int64_t c = (int64_t)lane * 4; c < F; c += (int64_t)lpr * 4) {
-      f4 acc = {0.f, 0.f, 0.f, 0.f};
-      int64_t k = b;
-      for (; k + 1 < e; k += 2) {  // two independent rows in flight
-        const f4 v0 = load4(row(col[k]) + c), v1 = load4(row(col[k + 1]) + c);
-        acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
-        acc.x += v1.x; acc.y += v1.y; acc.z += v1.z; acc.w += v1.w;
-      }
-      if (k < e) {
-        const f4 v0 = load4(row(col[k]) + c);
-        acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
-      }
-      if (own) {
-        const f4 o = load4(own + c);
-        acc.x = fmaf(s, o.x, acc.x); acc.y = fmaf(s, o.y, acc.y); acc.z = fmaf(s, o.z, acc.z); acc.w = fmaf(s, o.w, acc.w);
-      }
-      *reinterpret_cast<float4*>(out + t * out_stride + c) = make_float4(acc.x, acc.y, acc.z, acc.w);
-    }
-  } else {
-    for (int64_t c = lane; c < F; c += lpr) {
-      float acc = 0.f;
-      for (int64_t k = b; k < e; ++k) acc += load1(row(col[k]) + c);
-      if (own) acc = fmaf(s, load1(own + c), acc);
-      out[t * out_stride + c] = acc;
-    }
-  }
-}
-
-// grad_x rows < T start from s * grad_out (the self term), the others from zero; any F
-__global__ __launch_bounds__(kAggNT) void k_sum_grad_init(const float* __restrict__ g, int64_t go_stride, int64_t T,
-                                                          int64_t S, int64_t F, float s, float* __restrict__ grad_x) {
-  const int64_t n = S * F;
-  for (int64_t i = (int64_t)blockIdx.x * kAggNT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kAggNT) {
-    const int64_t r = i / F, c = i - r * F;
-    grad_x[i] = r < T ? s * g[r * go_stride + c] : 0.f;
-  }
-}
-
-// the scatter: grad_x[col[e],:] += grad_out[t,:] (hardware fp32 atomics, summation order not fixed)
-__global__ __launch_bounds__(kAggNT) void k_csr_sum_bwd(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,
-                                                        int64_t T, const float* __restrict__ g, int64_t go_stride, int64_t F,
-                                                        int lpr_log2, float* __restrict__ grad_x) {
-  const int lpr = 1 << lpr_log2;
-  const int lane = threadIdx.x & (lpr - 1);
-  const int64_t t = ((int64_t)blockIdx.x * kAggNT + threadIdx.x) >> lpr_log2;
-  if (t >= T) return;
-  const int64_t b = rowptr[t], e = rowptr[t + 1];
-  for (int64_t c = lane; c < F; c += lpr) {
-    const float v = g[t * go_stride + c];
-    for (int64_t k = b; k < e; ++k) unsafeAtomicAdd(grad_x + col[k] * F + c, v);
-  }
-}
-
-// the same gradient by gather over the transposed hop: source j's targets are tcol[start[j] .. start[j+1])
-template <bool VEC4>
-__global__ __launch_bounds__(kAggNT) void k_sum_bwd_gather(const int32_t* __restrict__ start,
-                                                           const int32_t* __restrict__ tcol, int64_t T, int64_t S,
-                                                           const float* __restrict__ g, int64_t go_stride, int64_t F,
-                                                           int lpr_log2, float s, float* __restrict__ grad_x) {
-  const int lpr = 1 << lpr_log2;
-  const int lane = threadIdx.x & (lpr - 1);
-  const int64_t j = ((int64_t)blockIdx.x * kAggNT + threadIdx.x) >> lpr_log2;
-  if (j >= S) return;
-  const int32_t b = start[j], e = start[j + 1];
-  if (VEC4) {
-    for (int64_t c = (int64_t)lane * 4; c < F; c += (int64_t)lpr * 4) {
-      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-      int32_t k = b;
-      for (; k + 1 < e; k += 2) {  // two independent rows in flight
-        const float4 v0 = *reinterpret_cast<const float4*>(g + (int64_t)tcol[k] * go_stride + c);
-        const float4 v1 = *reinterpret_cast<const float4*>(g + (int64_t)tcol[k + 1] * go_stride + c);
-        acc.x += v0.x + v1.x; acc.y += v0.y + v1.y; acc.z += v0.z + v1.z; acc.w += v0.w + v1.w;
-      }
-      if (k < e) {
-        const float4 v0 = *reinterpret_cast<const float4*>(g + (int64_t)tcol[k] * go_stride + c);
-        acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
-      }
-      if (j < T) {
-        const float4 o = *reinterpret_cast<const float4*>(g + j * go_stride + c);
-        acc.x = fmaf(s, o.x, acc.x); acc.y = fmaf(s, o.y, acc.y); acc.z = fmaf(s, o.z, acc.z); acc.w = fmaf(s, o.w, acc.w);
-      }
-      *reinterpret_cast<float4*>(grad_x + j * F + c) = acc;
-    }
-  } else {
-    for (int64_t c = lane; c < F; c += lpr) {
-      float acc = 0.f;
-      for (int32_t k = b; k < e; ++k) acc += g[(int64_t)tcol[k] * go_stride + c];
-      if (j < T) acc = fmaf(s, g[j * go_stride + c], acc);
-      grad_x[j * F + c] = acc;
-    }
-  }
-}
-
-}  // namespace spp
-
-// x: a dense batch matrix (n_id == NULL), the resident table (n_id != NULL) or -- refs -- nothing (n_id = row addresses)
-static spp_status sum_forward(const char* who, const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
-                              const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t F, float self_scale,
-                              float* out_dev, int64_t out_stride_elems, void* stream, const int64_t* n_id_dev,
-                              int64_t table_rows, bool refs) {
-  SPP_REQUIRE(num_targets >= 0 && F >= 0, "%s: negative size", who);
-  if (num_targets == 0 || F == 0) return SPP_OK;
-  SPP_REQUIRE(rowptr_dev && out_dev && (refs || x_dev) && ((!refs && table_rows == 0) || n_id_dev),
-              "%s: NULL buffer", who);
-  SPP_REQUIRE(refs || x_stride_elems >= F, "%s: row stride smaller than the row", who);
-  if (out_stride_elems <= 0) out_stride_elems = F;
-  SPP_REQUIRE(out_stride_elems >= F, "%s: output stride smaller than the row", who);
-  hipStream_t st = as_stream(stream);
-  const int64_t esz = x_is_half ? 2 : 4;
-  // row references: 8-byte aligned fp16 / 16-byte aligned fp32 rows when F % 4 == 0 (spp_mfg_out.row_addr)
-  const bool vec = (F % 4 == 0) && (reinterpret_cast<uintptr_t>(out_dev) % 16 == 0) && (out_stride_elems % 4 == 0) &&
-                   (refs || (((x_stride_elems * esz) % (4 * esz) == 0) &&
-                             (reinterpret_cast<uintptr_t>(x_dev) % (4 * esz) == 0)));
-  const int lpr_log2 = lanes_log2(vec ? F / 4 : F);
-  const unsigned grid = (unsigned)ceil_div(num_targets << lpr_log2, kAggNT);
-#define SPP_SUM(TIN, V)                                                                                                \
-  do {                                                                                                                 \
-    const TIN* x_ = static_cast<const TIN*>(x_dev);                                                                    \
-    if (refs)                                                                                                          \
-      hipLaunchKernelGGL((k_csr_sum_fwd<TIN, V, false, true>), dim3(grid), dim3(kAggNT), 0, st, rowptr_dev, col_dev,   \
-                         num_targets, x_, (int64_t)0, F, lpr_log2, self_scale, out_dev, out_stride_elems, n_id_dev,    \
-                         (int64_t)0);                                                                                  \
-    else if (n_id_dev)                                                                                                 \
-      hipLaunchKernelGGL((k_csr_sum_fwd<TIN, V, true>), dim3(grid), dim3(kAggNT), 0, st, rowptr_dev, col_dev,          \
-                         num_targets, x_, x_stride_elems, F, lpr_log2, self_scale, out_dev, out_stride_elems, n_id_dev, \
-                         table_rows);                                                                                  \
-    else                                                                                                               \
-      hipLaunchKernelGGL((k_csr_sum_fwd<TIN, V>), dim3(grid), dim3(kAggNT), 0, st, rowptr_dev, col_dev, num_targets,   \
-                         x_, x_stride_elems, F, lpr_log2, self_scale, out_dev, out_stride_elems, nullptr, (int64_t)0); \
-  } while (0)
-  if (x_is_half) {
-    if (vec) SPP_SUM(__half, true); else SPP_SUM(__half, false);
-  } else {
-    if (vec) SPP_SUM(float, true); else SPP_SUM(float, false);
-  }
-#undef SPP_SUM
-  SPP_HIP_TRY(hipGetLastError());
-  return SPP_OK;
-}
-
 extern "C" spp_status spp_csr_sum_forward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
                                           const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t F,
                                           float self_scale, float* out_dev, int64_t out_stride_elems, void* stream) {
-  return sum_forward("spp_csr_sum_forward", rowptr_dev, col_dev, num_targets, x_dev, x_is_half, x_stride_elems, F,
-                     self_scale, out_dev, out_stride_elems, stream, nullptr, 0, false);
+  return agg_forward<Dense>("spp_csr_sum_forward", rowptr_dev, col_dev, num_targets, x_dev, x_is_half, x_stride_elems,
+                            nullptr, 0, F, Sum{self_scale}, out_dev, out_stride_elems, stream);
 }
 
 extern "C" spp_status spp_csr_sum_forward_table(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
@@ -1457,15 +1332,16 @@ extern "C" spp_status spp_csr_sum_forward_table(const int64_t* rowptr_dev, const
                                                 float* out_dev, int64_t out_stride_elems, void* stream) {
   SPP_REQUIRE(num_targets == 0 || (n_id_dev && table_dev && table_rows > 0),
               "spp_csr_sum_forward_table: needs the feature table and the batch's node ids");
-  return sum_forward("spp_csr_sum_forward_table", rowptr_dev, col_dev, num_targets, table_dev, table_is_half,
-                     table_stride_elems, F, self_scale, out_dev, out_stride_elems, stream, n_id_dev, table_rows, false);
+  return agg_forward<Table>("spp_csr_sum_forward_table", rowptr_dev, col_dev, num_targets, table_dev, table_is_half,
+                            table_stride_elems, n_id_dev, table_rows, F, Sum{self_scale}, out_dev, out_stride_elems,
+                            stream);
 }
 
 extern "C" spp_status spp_csr_sum_forward_rows(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
                                                const int64_t* row_addr_dev, int32_t rows_are_half, int64_t F,
                                                float self_scale, float* out_dev, int64_t out_stride_elems, void* stream) {
-  return sum_forward("spp_csr_sum_forward_rows", rowptr_dev, col_dev, num_targets, nullptr, rows_are_half, 0, F,
-                     self_scale, out_dev, out_stride_elems, stream, row_addr_dev, 0, true);
+  return agg_forward<Refs>("spp_csr_sum_forward_rows", rowptr_dev, col_dev, num_targets, nullptr, rows_are_half, 0,
+                           row_addr_dev, 0, F, Sum{self_scale}, out_dev, out_stride_elems, stream);
 }
 
 extern "C" spp_status spp_csr_sum_backward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
@@ -1482,10 +1358,7 @@ extern "C" spp_status spp_csr_sum_backward(const int64_t* rowptr_dev, const int6
                      num_sources, F, self_scale, grad_x_dev);
   SPP_HIP_TRY(hipGetLastError());
   if (num_targets == 0) return SPP_OK;
-  const int lpr_log2 = lanes_log2(F);
-  const unsigned grid = (unsigned)ceil_div(num_targets << lpr_log2, kAggNT);
-  hipLaunchKernelGGL(k_csr_sum_bwd, dim3(grid), dim3(kAggNT), 0, st, rowptr_dev, col_dev, num_targets, grad_out_dev,
-                     grad_out_stride_elems, F, lpr_log2, grad_x_dev);
+  launch_agg_bwd_scatter<Sum>(rowptr_dev, col_dev, num_targets, grad_out_dev, grad_out_stride_elems, F, grad_x_dev, st);
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
 }
@@ -1495,32 +1368,7 @@ extern "C" spp_status spp_csr_sum_backward_gather(const int64_t* rowptr_dev, con
                                                   int64_t grad_out_stride_elems, int64_t F, float self_scale,
                                                   float* grad_x_dev, void* workspace_dev, int64_t workspace_bytes,
                                                   void* stream) {
-  SPP_REQUIRE(num_targets >= 0 && num_sources >= num_targets && F >= 0 && num_edges >= 0,
-              "spp_csr_sum_backward_gather: bad sizes");
-  if (num_sources == 0 || F == 0) return SPP_OK;
-  SPP_REQUIRE(num_sources < (1ll << 31) && num_edges < (1ll << 31), "spp_csr_sum_backward_gather: 32-bit indices");
-  SPP_REQUIRE(grad_x_dev && workspace_dev && ((grad_out_dev && rowptr_dev) || num_targets == 0),
-              "spp_csr_sum_backward_gather: NULL buffer");
-  if (grad_out_stride_elems <= 0) grad_out_stride_elems = F;
-  SPP_REQUIRE(grad_out_stride_elems >= F && reinterpret_cast<uintptr_t>(workspace_dev) % 16 == 0,
-              "spp_csr_sum_backward_gather: gradient stride smaller than the row or unaligned workspace");
-  SPP_REQUIRE(workspace_bytes >= spp_sage_operand_backward_workspace_bytes(num_targets, num_sources, num_edges),
-              "spp_csr_sum_backward_gather: workspace too small");
-  hipStream_t st = as_stream(stream);
-  const int32_t *start, *tcol;
-  const float* inv;
-  SPP_TRY(transpose_hop(rowptr_dev, col_dev, num_targets, num_sources, num_edges, workspace_dev, workspace_bytes, st,
-                        &start, &tcol, &inv));
-  const bool vec = F % 4 == 0 && grad_out_stride_elems % 4 == 0 &&
-                   (reinterpret_cast<uintptr_t>(grad_out_dev) | reinterpret_cast<uintptr_t>(grad_x_dev)) % 16 == 0;
-  const int lpr_log2 = lanes_log2(vec ? F / 4 : F);
-  const unsigned grid = (unsigned)ceil_div(num_sources << lpr_log2, kAggNT);
-  if (vec)
-    hipLaunchKernelGGL(k_sum_bwd_gather<true>, dim3(grid), dim3(kAggNT), 0, st, start, tcol, num_targets, num_sources,
-                       grad_out_dev, grad_out_stride_elems, F, lpr_log2, self_scale, grad_x_dev);
-  else
-    hipLaunchKernelGGL(k_sum_bwd_gather<false>, dim3(grid), dim3(kAggNT), 0, st, start, tcol, num_targets, num_sources,
-                       grad_out_dev, grad_out_stride_elems, F, lpr_log2, self_scale, grad_x_dev);
-  SPP_HIP_TRY(hipGetLastError());
-  return SPP_OK;
+  return agg_backward_gather("spp_csr_sum_backward_gather", rowptr_dev, col_dev, num_targets, num_sources, num_edges,
+                             grad_out_dev, grad_out_stride_elems, F, Sum{self_scale}, grad_x_dev, workspace_dev,
+                             workspace_bytes, nullptr, stream);
 }

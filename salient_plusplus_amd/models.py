@@ -264,6 +264,14 @@ class _Refs:
         self.r = r
 
 
+def _readable(x):
+    """a feature matrix, TableRows or RowRefs the aggregation kernels read in place (fp16 / fp32 rows)"""
+    if isinstance(x, RowRefs):
+        return x.dtype in (torch.float16, torch.float32)
+    m = x.table if isinstance(x, TableRows) else x
+    return m.is_cuda and m.dim() == 2 and m.stride(1) == 1 and m.dtype in (torch.float16, torch.float32)
+
+
 class _SageStack(torch.autograd.Function):
     """The whole SAGE forward (all layers: fused operand, one GEMM, ReLU + dropout; log_softmax) as ONE
     autograd node with a hand-written backward.  The kernels are the ones the layer-wise path uses; what
@@ -273,16 +281,11 @@ class _SageStack(torch.autograd.Function):
 
     @staticmethod
     def usable(model, x, adjs):
-        if isinstance(x, TableRows):                     # (resident table, n_id): the first layer reads the table itself
-            x = x.table
-        if isinstance(x, RowRefs):                       # addresses of the rows
-            if x.dtype not in (torch.float16, torch.float32) or x.width % 4:
-                return False
-            k = x.width
-        elif x.dim() != 2 or x.stride(1) != 1 or x.dtype not in (torch.float16, torch.float32) or x.requires_grad:
+        # a matrix, or the first layer reads the resident table (TableRows) / the rows' addresses (RowRefs) itself
+        rows = x.table if isinstance(x, TableRows) else x
+        if not _readable(x) or (isinstance(rows, torch.Tensor) and rows.requires_grad):
             return False
-        else:
-            k = x.size(1)
+        k = x.size(1)
         for conv in model.convs:
             if conv.lin_l.bias is not None or conv.lin_l.weight.dtype != torch.float32 or k % 4:
                 return False
@@ -626,15 +629,6 @@ class _SumAggregate(torch.autograd.Function):
 def sum_aggregate(x, rowptr, col, num_targets, scale=1.0):
     """scale * x[:T] + the sum of each target's neighbour rows (GINConv's aggregation with scale = 1 + eps)"""
     return _SumAggregate.apply(x, rowptr, col, num_targets, scale)
-
-
-def _readable(x):
-    """a feature matrix, TableRows or RowRefs the sum kernels read as they are (fp16 / fp32 rows)"""
-    if isinstance(x, TableRows):
-        return x.table.is_cuda and x.table.dtype in (torch.float16, torch.float32) and x.table.stride(1) == 1
-    if isinstance(x, RowRefs):
-        return x.dtype in (torch.float16, torch.float32)
-    return x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and x.dtype in (torch.float16, torch.float32)
 
 
 class GINConv(torch.nn.Module):

@@ -28,6 +28,18 @@ def _ref_sum(x, rowptr, col, T, s):
     return torch.zeros((T, x.size(1)), dtype=xf.dtype, device=x.device).index_add_(0, row, xf[col]) + s * xf[:T]
 
 
+def _seq_sum(x, rowptr, col, T, s):
+    """the kernels' exact arithmetic for an s with s * x exact in fp32 (then fmaf(s, x_t, acc) is one add of that
+    product): each row's entries summed in fp32 in CSR order, one at a time, then s * x_t added"""
+    deg = rowptr[1:] - rowptr[:-1]
+    xf = x.float()
+    acc = torch.zeros((T, x.size(1)), dtype=torch.float32, device=x.device)
+    for k in range(int(deg.max()) if T else 0):
+        on = k < deg
+        acc = acc + torch.where(on.unsqueeze(-1), xf[col[torch.where(on, rowptr[:-1] + k, 0)]], 0.0)
+    return acc + xf[:T] * s if s else acc
+
+
 def _ref_mean(x, rowptr, col, T):
     cnt = rowptr[1:] - rowptr[:-1]
     row = torch.repeat_interleave(torch.arange(T, device=x.device), cnt)
@@ -186,7 +198,10 @@ def test_sum_aggregate_forward_backward(F_, dtype, eps):
     rowptr, col = _hop(T, S, 20, F_, dup=True)
     x = torch.randn((S, F_), generator=torch.Generator().manual_seed(1)).to(dtype).cuda()
     s = 1.0 + eps
-    torch.testing.assert_close(sum_aggregate(x, rowptr, col, T, s), _ref_sum(x, rowptr, col, T, s), rtol=1e-5, atol=1e-5)
+    got = sum_aggregate(x, rowptr, col, T, s)
+    torch.testing.assert_close(got, _ref_sum(x, rowptr, col, T, s), rtol=1e-5, atol=1e-5)
+    if dtype == torch.float16 or s == 1.0:                   # s * x exact in fp32
+        assert torch.equal(got, _seq_sum(x, rowptr, col, T, s))
     xg = x.clone().requires_grad_(True)
     xr = x.float().clone().requires_grad_(True)
     w = torch.randn((T, F_), device="cuda")
@@ -273,6 +288,9 @@ def test_sum_forward_table_and_rows_equal_the_materialised_sum():
         nat.check(L.spp_csr_sum_forward_rows(p(rowptr), p(col), T, p(addr), half, F_, 1.5, p(outs[2]), F_, st))
         assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])      # same rows, same order
         torch.testing.assert_close(outs[0], _ref_sum(xm, rowptr, col, T, 1.5), rtol=1e-5, atol=1e-5)
+        if not half:                                         # s * x exact in fp32: s = 2 for fp32 rows
+            nat.check(L.spp_csr_sum_forward(p(rowptr), p(col), T, p(xm), half, F_, F_, 2.0, p(outs[0]), F_, st))
+        assert torch.equal(outs[0], _seq_sum(xm, rowptr, col, T, 1.5 if half else 2.0))
 
 
 def test_sum_entries_refuse_bad_arguments():

@@ -22,6 +22,19 @@ def _ref_mean(x, rowptr, col, T):
     return out / cnt.clamp(min=1).unsqueeze(-1).float()
 
 
+def _seq_mean(x, rowptr, col, T):
+    """the kernels' exact arithmetic: each row's entries summed in fp32 in CSR order, one at a time, then times the fp32
+    reciprocal of the degree"""
+    deg = rowptr[1:] - rowptr[:-1]
+    xf = x.float()
+    acc = torch.zeros((T, x.size(1)), dtype=torch.float32, device=x.device)
+    for k in range(int(deg.max()) if T else 0):
+        on = k < deg
+        acc = acc + torch.where(on.unsqueeze(-1), xf[col[torch.where(on, rowptr[:-1] + k, 0)]], 0.0)
+    inv = (1.0 / deg.clamp(min=1).float().cpu()).to(x.device)
+    return acc * inv.unsqueeze(-1)
+
+
 def _random_hop(T, S, maxdeg, seed):
     g = torch.Generator().manual_seed(seed)
     deg = torch.randint(0, maxdeg + 1, (T,), generator=g)
@@ -42,6 +55,7 @@ def test_mean_aggregate_forward_backward(F, dtype):
     want = _ref_mean(x, rowptr, col, T)
     got = mean_aggregate(x, rowptr, col, T)
     torch.testing.assert_close(got, want, rtol=1e-5, atol=1e-5)
+    assert torch.equal(got, _seq_mean(x, rowptr, col, T))
     if dtype == torch.float32:
         xg = x.clone().requires_grad_(True)
         xr = x.clone().requires_grad_(True)
@@ -320,6 +334,7 @@ def test_sage_operand_forward_backward(T, S, F, maxdeg, dtype):
     got = _MeanAggregate.apply(x, rowptr, col, T, True)
     want = torch.cat([_ref_mean(x, rowptr, col, T), x[:T].float()], dim=1)
     torch.testing.assert_close(got, want, rtol=1e-5, atol=1e-5)
+    assert torch.equal(got, torch.cat([_seq_mean(x, rowptr, col, T), x[:T].float()], dim=1))
     if dtype == torch.float32:
         xg = x.clone().requires_grad_(True)
         xr = x.clone().requires_grad_(True)
