@@ -650,7 +650,8 @@ spp_status spp_gat_backward(const int64_t* rowptr_dev, const int64_t* col_dev, i
  *   spp_gat_logits:            a_src[j] = x_j . v_src (all S rows), a_dst[i] = x_i . v_dst (the first T rows)
  *   spp_gat_aggregate_forward: z_i = sum_j softmax_j(leaky_relu(a_src[j] + a_dst[i])) x_j  over row i of the hop
  *                              (diagonal entry dropped, self loop added, as GATConv's set_diag); the layer's
- *                              output is then z @ W^T.  x rows are fp16 or fp32, K % 4 == 0.
+ *                              output is then z @ W^T.  x rows are fp32, fp16 or bf16 (`x_is_half` is the element
+ *                              code: 0 fp32, 1 fp16, 2 bf16, see spp_elem below), K % 4 == 0; the rest is fp32.
  *   spp_gat_aggregate_backward: from grad_z: grad_a_src [S] (caller zeroes it), grad_a_dst [T], and -- when
  *                              grad_x_dev != NULL (caller zeroes it) -- grad_x[j,:] += alpha_ij grad_z_i.
  *   spp_gat_logits_backward:   grad_v_src[c] = sum_j grad_a_src[j] x[j,c], grad_v_dst[c] = sum_{i<T} grad_a_dst[i] x[i,c]. */
@@ -724,6 +725,98 @@ spp_status spp_csr_sum_backward_gather(const int64_t* rowptr_dev, const int64_t*
                                        int64_t num_sources, int64_t num_edges, const float* grad_out_dev,
                                        int64_t grad_out_stride_elems, int64_t F, float self_scale, float* grad_x_dev,
                                        void* workspace_dev, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * f3  Aggregation by descriptor: the mean / operand / sum kernels above with a choice of element types -- among
+ *     them bf16 activations and gradients for training under torch.autocast(dtype=torch.bfloat16) -- through two
+ *     entries instead of one function per combination.
+ *
+ *   Element codes (spp_elem): SPP_ELEM_F32 = 0, SPP_ELEM_F16 = 1, SPP_ELEM_BF16 = 2.  The GAT entries' `x_is_half`
+ *   argument is this code too (0 and 1 keep their meaning).
+ *   Rounding rule: every load converts to fp32 exactly; every sum and product runs in fp32, in the order of the fp32
+ *   kernels; each stored bf16 element is rounded ONCE, to nearest even.  So a bf16 output equals the fp32 output
+ *   rounded to bf16 bit for bit, and a bf16 input gives the fp32 result on the input converted to fp32.
+ *
+ *   spp_agg_forward: `source` SPP_AGG_DENSE (x = the batch's matrix, rows x_stride_elems apart), SPP_AGG_TABLE
+ *     (x = the resident table with x_rows rows, batch row j = x[n_id[j]]) or SPP_AGG_ROWS (n_id = the row
+ *     addresses of spp_mfg_out.row_addr, x unused); `epilogue`:
+ *       SPP_AGG_MEAN         out [T, F]  = the mean (spp_csr_mean_forward);
+ *       SPP_AGG_OPERAND      out [T, 2F] = [mean | x_target] (spp_sage_operand_forward, _table, _rows);
+ *       SPP_AGG_OPERAND_ACT  the operand of relu_dropout(x) for a PRE-activation x (spp_sage_operand_forward_act:
+ *                            DENSE rows with x_stride_elems == F, F % 4 == 0, x fp32 or bf16, p / training / seed);
+ *                            the dropout decisions depend on the element index only, so a bf16 x drops the same
+ *                            elements as an fp32 x at the same seed;
+ *       SPP_AGG_SUM          out [T, F]  = s * x[t] + the sum (spp_csr_sum_forward, _table, _rows), s = self_scale.
+ *     x_elem: fp32 / fp16 / bf16; out_elem: fp32 / bf16.  out_stride_elems 0 = dense.
+ *
+ *   spp_agg_backward: grad_x [S, F] dense is written COMPLETELY (also for SPP_AGG_MEAN, whose old entry adds):
+ *       SPP_AGG_MEAN (scatter only)  grad_x[s] = sum over the edges (t, s) of grad_out[t] / deg t;
+ *       SPP_AGG_OPERAND              spp_sage_operand_backward / _gather (grad_out [T, 2F]);
+ *       SPP_AGG_OPERAND_ACT          the same followed by the ReLU + dropout backward of the pre-activation z [S, F]
+ *                                    (spp_sage_operand_backward_gather_act; p / training / seed of the forward);
+ *       SPP_AGG_SUM                  spp_csr_sum_backward / _gather.
+ *     grad_elem, out_elem, z_elem: fp32 / bf16 each.  form SPP_AGG_GATHER: over the transposed hop, workspace of
+ *     spp_sage_operand_backward_workspace_bytes(T, S, E) bytes, fixed summation order.  form SPP_AGG_SCATTER: fp32
+ *     atomics into an fp32 buffer (order not fixed), then one pass that applies the activation backward and / or
+ *     rounds: with out_elem != fp32 that buffer is the workspace, 4 * S * F bytes; with fp32 it is grad_x itself and
+ *     no workspace is needed.  Workspaces are 16-byte aligned.
+ *
+ *   An unknown source, epilogue, form or element code, or an element type an epilogue does not take, returns
+ *   SPP_ERR_INVALID before anything is launched.
+ * ------------------------------------------------------------------------- */
+enum { SPP_ELEM_F32 = 0, SPP_ELEM_F16 = 1, SPP_ELEM_BF16 = 2 };
+enum { SPP_AGG_DENSE = 0, SPP_AGG_TABLE = 1, SPP_AGG_ROWS = 2 };
+enum { SPP_AGG_MEAN = 0, SPP_AGG_OPERAND = 1, SPP_AGG_OPERAND_ACT = 2, SPP_AGG_SUM = 3 };
+enum { SPP_AGG_SCATTER = 0, SPP_AGG_GATHER = 1 };
+
+typedef struct spp_agg_fwd_desc {
+  int32_t source;           /* SPP_AGG_DENSE / _TABLE / _ROWS */
+  int32_t epilogue;         /* SPP_AGG_MEAN / _OPERAND / _OPERAND_ACT / _SUM */
+  int32_t x_elem;           /* spp_elem of x's rows */
+  int32_t out_elem;         /* SPP_ELEM_F32 / SPP_ELEM_BF16 */
+  const int64_t* rowptr_dev;
+  const int64_t* col_dev;
+  int64_t num_targets;
+  const void* x_dev;        /* DENSE: the batch's matrix; TABLE: the feature table; ROWS: unused */
+  int64_t x_stride_elems;   /* DENSE / TABLE */
+  int64_t x_rows;           /* TABLE: the table's rows */
+  const int64_t* n_id_dev;  /* TABLE: the batch's node ids; ROWS: the row addresses */
+  int64_t F;
+  void* out_dev;
+  int64_t out_stride_elems; /* 0 = dense */
+  float self_scale;         /* SUM: s = 1 + eps */
+  float p;                  /* OPERAND_ACT: dropout probability, 0 <= p < 1 */
+  int32_t training;         /* OPERAND_ACT */
+  int32_t reserved;
+  uint64_t seed;            /* OPERAND_ACT */
+} spp_agg_fwd_desc;
+
+typedef struct spp_agg_bwd_desc {
+  int32_t form;             /* SPP_AGG_SCATTER / SPP_AGG_GATHER */
+  int32_t epilogue;         /* SPP_AGG_MEAN (scatter) / _OPERAND / _OPERAND_ACT / _SUM */
+  int32_t grad_elem;        /* grad_out: SPP_ELEM_F32 / SPP_ELEM_BF16 */
+  int32_t out_elem;         /* grad_x:   SPP_ELEM_F32 / SPP_ELEM_BF16 */
+  int32_t z_elem;           /* z (OPERAND_ACT): SPP_ELEM_F32 / SPP_ELEM_BF16 */
+  int32_t reserved;
+  const int64_t* rowptr_dev;
+  const int64_t* col_dev;
+  int64_t num_targets;
+  int64_t num_sources;
+  int64_t num_edges;
+  const void* grad_out_dev;
+  int64_t grad_out_stride_elems; /* 0 = dense (F, or 2F for the operand) */
+  int64_t F;
+  void* grad_x_dev;         /* [S, F] dense */
+  const void* z_dev;        /* OPERAND_ACT: the pre-activation [S, F], dense */
+  float self_scale;         /* SUM */
+  float p;                  /* OPERAND_ACT */
+  int32_t training;         /* OPERAND_ACT */
+  int32_t reserved2;
+  uint64_t seed;            /* OPERAND_ACT */
+} spp_agg_bwd_desc;
+
+spp_status spp_agg_forward(const spp_agg_fwd_desc* desc, void* stream);
+spp_status spp_agg_backward(const spp_agg_bwd_desc* desc, void* workspace_dev, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

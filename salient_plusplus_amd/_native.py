@@ -57,6 +57,28 @@ class MfgOut(C.Structure):
                 ("parts", p), ("cached", p), ("perm", p), ("row_addr", p), ("x_remote", p)]
 
 
+# spp_elem and the aggregation descriptor's codes (include/spp.h)
+SPP_ELEM_F32, SPP_ELEM_F16, SPP_ELEM_BF16 = 0, 1, 2
+SPP_AGG_DENSE, SPP_AGG_TABLE, SPP_AGG_ROWS = 0, 1, 2
+SPP_AGG_MEAN, SPP_AGG_OPERAND, SPP_AGG_OPERAND_ACT, SPP_AGG_SUM = 0, 1, 2, 3
+SPP_AGG_SCATTER, SPP_AGG_GATHER = 0, 1
+
+
+class AggFwdDesc(C.Structure):
+    _fields_ = [("source", i32), ("epilogue", i32), ("x_elem", i32), ("out_elem", i32), ("rowptr_dev", p),
+                ("col_dev", p), ("num_targets", i64), ("x_dev", p), ("x_stride_elems", i64), ("x_rows", i64),
+                ("n_id_dev", p), ("F", i64), ("out_dev", p), ("out_stride_elems", i64), ("self_scale", C.c_float),
+                ("p", C.c_float), ("training", i32), ("reserved", i32), ("seed", C.c_uint64)]
+
+
+class AggBwdDesc(C.Structure):
+    _fields_ = [("form", i32), ("epilogue", i32), ("grad_elem", i32), ("out_elem", i32), ("z_elem", i32),
+                ("reserved", i32), ("rowptr_dev", p), ("col_dev", p), ("num_targets", i64), ("num_sources", i64),
+                ("num_edges", i64), ("grad_out_dev", p), ("grad_out_stride_elems", i64), ("F", i64),
+                ("grad_x_dev", p), ("z_dev", p), ("self_scale", C.c_float), ("p", C.c_float), ("training", i32),
+                ("reserved2", i32), ("seed", C.c_uint64)]
+
+
 class GroupOut(C.Structure):
     _fields_ = [("mfg", MfgOut), ("x_out", p), ("y_out", p)]
 
@@ -168,6 +190,8 @@ SIGNATURES = {
     "spp_session_try_next": (C.c_int, [p, C.POINTER(BatchDesc)]),
     "spp_session_quiesce": (C.c_int, [p]),
     "spp_session_exchange_stats": (C.c_int, [p, C.POINTER(i64), C.POINTER(i64)]),
+    "spp_agg_forward": (C.c_int, [C.POINTER(AggFwdDesc), p]),
+    "spp_agg_backward": (C.c_int, [C.POINTER(AggBwdDesc), p, i64, p]),
 }
 SPP_COMM_ID_BYTES = 128
 SPP_IPC_HANDLE_BYTES = 64

@@ -8,6 +8,7 @@
 // over 150 MB).  The linear layers stay library GEMMs.
 #include "spp_internal.h"
 
+#include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 #include <hipcub/hipcub.hpp>
 
@@ -34,6 +35,37 @@ __device__ __forceinline__ f4 load4(const __half* p) {
 }
 __device__ __forceinline__ float load1(const float* p) { return *p; }
 __device__ __forceinline__ float load1(const __half* p) { return __half2float(*p); }
+
+// bf16 rows (torch.autocast(dtype=torch.bfloat16)): bf16 -> fp32 is exact (the 16 bits become the high half); fp32 ->
+// bf16 is rounded once per stored element, to nearest even, by the packed hardware convert (v_cvt_pk_bf16_f32)
+using bf16 = __hip_bfloat16;
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f4 load4(const bf16* p) {
+  const uint2 raw = *reinterpret_cast<const uint2*>(p);
+  return {__uint_as_float(raw.x << 16), __uint_as_float(raw.x & 0xffff0000u), __uint_as_float(raw.y << 16),
+          __uint_as_float(raw.y & 0xffff0000u)};
+}
+__device__ __forceinline__ float load1(const bf16* p) {
+  return __uint_as_float((uint32_t)*reinterpret_cast<const uint16_t*>(p) << 16);
+}
+__device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t){a, b}, bf16x2_t));
+}
+__device__ __forceinline__ void store4(float* p, f4 v) { *reinterpret_cast<float4*>(p) = make_float4(v.x, v.y, v.z, v.w); }
+__device__ __forceinline__ void store4(bf16* p, f4 v) {
+  *reinterpret_cast<uint2*>(p) = make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
+}
+__device__ __forceinline__ void store1(float* p, float v) { *p = v; }
+__device__ __forceinline__ void store1(bf16* p, float v) { *p = __float2bfloat16(v); }
+// the same as float4, element 4*i .. 4*i+3 of p (the backward kernels' form)
+__device__ __forceinline__ float4 ld4(const float* p, int64_t i) { return reinterpret_cast<const float4*>(p)[i]; }
+__device__ __forceinline__ float4 ld4(const bf16* p, int64_t i) {
+  const f4 v = load4(p + 4 * i);
+  return make_float4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ void st4(float* p, int64_t i, float4 v) { reinterpret_cast<float4*>(p)[i] = v; }
+__device__ __forceinline__ void st4(bf16* p, int64_t i, float4 v) { store4(p + 4 * i, f4{v.x, v.y, v.z, v.w}); }
 
 // ---- ReLU + dropout (driver/models.py:47-48: x = F.relu(x); x = F.dropout(x, p=0.5)) ----
 // keep / drop from a counter-based generator: element i of the call with `seed` is kept iff
@@ -107,15 +139,15 @@ struct Sum {
   float s;
 };
 
-// LPR lanes share a target row; VEC4: F % 4 == 0 and rows 16-B (fp32) / 8-B (fp16) aligned.  The row's entries are
-// added in CSR order, one at a time.
-template <typename Tin, bool VEC4, class Src, class Epi>
+// LPR lanes share a target row; VEC4: F % 4 == 0 and rows 16-B (fp32) / 8-B (fp16, bf16) aligned.  The row's entries
+// are added in CSR order, one at a time, in fp32; Tout = bf16 rounds each stored element once.
+template <typename Tin, typename Tout, bool VEC4, class Src, class Epi>
 __global__ __launch_bounds__(kAggNT) void k_agg_fwd(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,
                                                     int64_t T, const Tin* __restrict__ x, int64_t x_stride, int64_t F,
-                                                    int lpr_log2, float* __restrict__ out, int64_t out_stride, Epi epi,
+                                                    int lpr_log2, Tout* __restrict__ out, int64_t out_stride, Epi epi,
                                                     const int64_t* __restrict__ nid, int64_t x_rows) {
-  static_assert(!Epi::kAct || (VEC4 && std::is_same<Tin, float>::value && std::is_same<Src, Dense>::value),
-                "activation on load: dense fp32 rows, vector form");
+  static_assert(!Epi::kAct || (VEC4 && !std::is_same<Tin, __half>::value && std::is_same<Src, Dense>::value),
+                "activation on load: dense fp32 / bf16 rows, vector form");
   const Rows<Tin, Src> row{x, x_stride, nid, x_rows};
   const int lpr = 1 << lpr_log2;
   const int lane = threadIdx.x & (lpr - 1);
@@ -133,7 +165,7 @@ __global__ __launch_bounds__(kAggNT) void k_agg_fwd(const int64_t* __restrict__ 
     for (int64_t c = (int64_t)lane * 4; c < F; c += (int64_t)lpr * 4) {
       if (epi.concat_target) {  // [mean | x_target]: the target's own row (targets are the first rows of x), as fp32
         const f4 o = row4(t, c);
-        *reinterpret_cast<float4*>(out + t * out_stride + F + c) = make_float4(o.x, o.y, o.z, o.w);
+        store4(out + t * out_stride + F + c, o);
       }
       f4 acc = {0.f, 0.f, 0.f, 0.f};
       int64_t k = b;
@@ -151,25 +183,30 @@ __global__ __launch_bounds__(kAggNT) void k_agg_fwd(const int64_t* __restrict__ 
         acc = {fmaf(epi.s, o.x, acc.x), fmaf(epi.s, o.y, acc.y), fmaf(epi.s, o.z, acc.z), fmaf(epi.s, o.w, acc.w)};
       }
       if (!Epi::kSum) acc = {acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv};
-      *reinterpret_cast<float4*>(out + t * out_stride + c) = make_float4(acc.x, acc.y, acc.z, acc.w);
+      store4(out + t * out_stride + c, acc);
     }
   } else {
     for (int64_t c = lane; c < F; c += lpr) {
-      if (epi.concat_target) out[t * out_stride + F + c] = load1(row(t) + c);
+      if (epi.concat_target) {
+        const float o = load1(row(t) + c);
+        store1(out + t * out_stride + F + c, o);
+      }
       float acc = 0.f;
       for (int64_t k = b; k < e; ++k) acc += load1(row(col[k]) + c);
       if (own) acc = fmaf(epi.s, load1(own + c), acc);
-      out[t * out_stride + c] = Epi::kSum ? acc : acc * inv;
+      if (!Epi::kSum) acc *= inv;
+      store1(out + t * out_stride + c, acc);
     }
   }
 }
 
 // the input gradient by scatter: grad_x[col[e],:] += w(t) * grad_out[t,:] for every edge (hardware fp32 atomics,
-// summation order not fixed); Mean: w = 1 / deg(t) and empty rows are skipped, Sum: w = 1
-template <class Epi>
+// summation order not fixed); Mean: w = 1 / deg(t) and empty rows are skipped, Sum: w = 1.  A bf16 grad_out is read
+// exactly; grad_x stays an fp32 buffer (bf16 atomics would round every partial sum)
+template <class Epi, typename Tg>
 __global__ __launch_bounds__(kAggNT) void k_agg_bwd_scatter(const int64_t* __restrict__ rowptr,
                                                             const int64_t* __restrict__ col, int64_t T,
-                                                            const float* __restrict__ grad_out, int64_t go_stride,
+                                                            const Tg* __restrict__ grad_out, int64_t go_stride,
                                                             int64_t F, int lpr_log2, float* __restrict__ grad_x) {
   const int lpr = 1 << lpr_log2;
   const int lane = threadIdx.x & (lpr - 1);
@@ -179,32 +216,38 @@ __global__ __launch_bounds__(kAggNT) void k_agg_bwd_scatter(const int64_t* __res
   if (!Epi::kSum && e <= b) return;
   const float w = Epi::kSum ? 1.f : 1.0f / (float)(e - b);
   for (int64_t c = lane; c < F; c += lpr) {
-    const float g = grad_out[t * go_stride + c] * w;
+    const float g = load1(grad_out + t * go_stride + c) * w;
     for (int64_t k = b; k < e; ++k) unsafeAtomicAdd(grad_x + col[k] * F + c, g);  // hardware fp32 atomic add
   }
 }
 
 // grad_x of the fused SAGE operand before the scatter of the mean's gradient: the first T source rows
 // are the targets themselves and start from the gradient of the x_target half, the rest from zero
-// (replaces a zero fill, the zero-padded gradient of the x[:T] slice and the add of the two).
-__global__ __launch_bounds__(kAggNT) void k_grad_init(const float* __restrict__ grad_out, int64_t go_stride, int64_t T,
+// (replaces a zero fill, the zero-padded gradient of the x[:T] slice and the add of the two).  grad_x is fp32.
+template <typename Tg>
+__global__ __launch_bounds__(kAggNT) void k_grad_init(const Tg* __restrict__ grad_out, int64_t go_stride, int64_t T,
                                                       int64_t S, int64_t F, float* __restrict__ grad_x) {
   const int64_t n4 = S * F / 4;  // F % 4 == 0 (checked by the caller)
   for (int64_t i = (int64_t)blockIdx.x * kAggNT + threadIdx.x; i < n4; i += (int64_t)gridDim.x * kAggNT) {
     const int64_t srow = (i * 4) / F, c = (i * 4) - srow * F;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (srow < T) v = *reinterpret_cast<const float4*>(grad_out + srow * go_stride + F + c);
+    if constexpr (std::is_same<Tg, float>::value) {  // (the fp32 form's own addressing: it compiles tighter)
+      if (srow < T) v = *reinterpret_cast<const float4*>(grad_out + srow * go_stride + F + c);
+    } else {
+      if (srow < T) v = ld4(grad_out + srow * go_stride + F + c, 0);
+    }
     reinterpret_cast<float4*>(grad_x)[i] = v;
   }
 }
 
 // the same for the sum: rows < T start from s * grad_out (the self term), the others from zero; any F
-__global__ __launch_bounds__(kAggNT) void k_sum_grad_init(const float* __restrict__ g, int64_t go_stride, int64_t T,
+template <typename Tg>
+__global__ __launch_bounds__(kAggNT) void k_sum_grad_init(const Tg* __restrict__ g, int64_t go_stride, int64_t T,
                                                           int64_t S, int64_t F, float s, float* __restrict__ grad_x) {
   const int64_t n = S * F;
   for (int64_t i = (int64_t)blockIdx.x * kAggNT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kAggNT) {
     const int64_t r = i / F, c = i - r * F;
-    grad_x[i] = r < T ? s * g[r * go_stride + c] : 0.f;
+    grad_x[i] = r < T ? s * load1(g + r * go_stride + c) : 0.f;
   }
 }
 
@@ -251,16 +294,28 @@ __global__ __launch_bounds__(kAggNT) void k_relu_dropout_bwd(const float* __rest
 }
 
 // the same backward from the PRE-activation z and the generator (no activated copy exists when the forward
-// applied the activation on load): gx = g * scale where z > 0 and the element was kept
-__global__ __launch_bounds__(kAggNT) void k_relu_dropout_bwd_pre(const float* __restrict__ g, const float* __restrict__ z,
-                                                                 int64_t n, ActArgs act, float* __restrict__ gx) {
+// applied the activation on load): gx = g * scale where z > 0 and the element was kept.  g is the fp32 sum of a
+// scatter; z fp32 or bf16; gx fp32 or bf16 (rounded once here).  !kAct: gx = g only (z not read; any n) -- the
+// rounding pass of a bf16 scatter gradient without an activation.
+template <typename Tz, typename Tout, bool kAct>
+__global__ __launch_bounds__(kAggNT) void k_relu_dropout_bwd_pre(const float* __restrict__ g, const Tz* __restrict__ z,
+                                                                 int64_t n, ActArgs act, Tout* __restrict__ gx) {
   const int64_t n4 = n / 4;
   for (int64_t i = (int64_t)blockIdx.x * kAggNT + threadIdx.x; i < n4; i += (int64_t)gridDim.x * kAggNT) {
-    const float4 a = reinterpret_cast<const float4*>(g)[i], b = reinterpret_cast<const float4*>(z)[i];
-    const f4 m = relu_dropout4(f4{b.x, b.y, b.z, b.w}, i, act);  // > 0 exactly where z > 0 and kept
-    const float sc = act.training ? act.scale : 1.f;
-    reinterpret_cast<float4*>(gx)[i] = make_float4(m.x > 0.f ? a.x * sc : 0.f, m.y > 0.f ? a.y * sc : 0.f,
-                                                   m.z > 0.f ? a.z * sc : 0.f, m.w > 0.f ? a.w * sc : 0.f);
+    const float4 a = ld4(g, i);
+    if constexpr (kAct) {
+      const float4 b = ld4(z, i);
+      const f4 m = relu_dropout4(f4{b.x, b.y, b.z, b.w}, i, act);  // > 0 exactly where z > 0 and kept
+      const float sc = act.training ? act.scale : 1.f;
+      st4(gx, i, make_float4(m.x > 0.f ? a.x * sc : 0.f, m.y > 0.f ? a.y * sc : 0.f, m.z > 0.f ? a.z * sc : 0.f,
+                             m.w > 0.f ? a.w * sc : 0.f));
+    } else {
+      st4(gx, i, a);
+    }
+  }
+  if constexpr (!kAct) {
+    const int64_t t = n4 * 4 + threadIdx.x;
+    if (blockIdx.x == 0 && t < n) store1(gx + t, g[t]);
   }
 }
 
@@ -299,13 +354,14 @@ __global__ __launch_bounds__(kAggNT) void k_tr_fill(const int64_t* __restrict__ 
 //     ReLU + dropout backward (k_relu_dropout_bwd_pre) of the pre-activation z (dense [S, F]) is applied to the row
 //     before it is stored, instead of a separate read-modify-write pass over grad_x.
 //   Sum: sum_t grad_out[t, :] (inv is not read), then fmaf(s, grad_out[s, :], acc) for s < T.
-template <bool VEC4, class Epi>
+// grad_out (Tg) and z (Tz) fp32 or bf16, read exactly; fp32 sums; grad_x (Tout) fp32 or bf16, rounded once.
+template <typename Tg, typename Tz, typename Tout, bool VEC4, class Epi>
 __global__ __launch_bounds__(kAggNT) void k_agg_bwd_gather(const int32_t* __restrict__ start,
                                                            const int32_t* __restrict__ tcol,
                                                            const float* __restrict__ inv, int64_t T, int64_t S,
-                                                           const float* __restrict__ g, int64_t go_stride, int64_t F,
-                                                           int lpr_log2, float* __restrict__ grad_x,
-                                                           const float* __restrict__ z, Epi epi) {
+                                                           const Tg* __restrict__ g, int64_t go_stride, int64_t F,
+                                                           int lpr_log2, Tout* __restrict__ grad_x,
+                                                           const Tz* __restrict__ z, Epi epi) {
   static_assert(VEC4 || Epi::kSum, "the operand's gradient has the vector form only");
   const int lpr = 1 << lpr_log2;
   const int lane = threadIdx.x & (lpr - 1);
@@ -317,7 +373,7 @@ __global__ __launch_bounds__(kAggNT) void k_agg_bwd_gather(const int32_t* __rest
       if constexpr (Epi::kSum) return 1.f;
       else return inv[t];
     };
-    auto row4 = [&](int64_t t, int64_t c) { return *reinterpret_cast<const float4*>(g + t * go_stride + c); };
+    auto row4 = [&](int64_t t, int64_t c) { return ld4(g + t * go_stride + c, 0); };
     for (int64_t c = (int64_t)lane * 4; c < F; c += (int64_t)lpr * 4) {
       float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
       if (!Epi::kSum && srow < T) acc = row4(srow, F + c);
@@ -340,23 +396,26 @@ __global__ __launch_bounds__(kAggNT) void k_agg_bwd_gather(const int32_t* __rest
         acc = make_float4(fmaf(epi.s, o.x, acc.x), fmaf(epi.s, o.y, acc.y), fmaf(epi.s, o.z, acc.z), fmaf(epi.s, o.w, acc.w));
       }
       if constexpr (Epi::kAct) {
-        const float4 zv = *reinterpret_cast<const float4*>(z + srow * F + c);
+        const float4 zv = ld4(z + srow * F + c, 0);
         const f4 m = relu_dropout4(f4{zv.x, zv.y, zv.z, zv.w}, (srow * F + c) >> 2, epi.act);  // > 0: z > 0 and kept
         const float sc = epi.act.training ? epi.act.scale : 1.f;
         acc = make_float4(m.x > 0.f ? acc.x * sc : 0.f, m.y > 0.f ? acc.y * sc : 0.f, m.z > 0.f ? acc.z * sc : 0.f,
                           m.w > 0.f ? acc.w * sc : 0.f);
       }
-      *reinterpret_cast<float4*>(grad_x + srow * F + c) = acc;
+      st4(grad_x + srow * F + c, 0, acc);
     }
   } else {  // Sum, any F: one column per lane and step
     for (int64_t c = lane; c < F; c += lpr) {
       float acc = 0.f;
-      for (int32_t k = b; k < e; ++k) acc += g[(int64_t)tcol[k] * go_stride + c];
-      if (srow < T) acc = fmaf(epi.s, g[srow * go_stride + c], acc);
-      grad_x[srow * F + c] = acc;
+      for (int32_t k = b; k < e; ++k) acc += load1(g + (int64_t)tcol[k] * go_stride + c);
+      if (srow < T) acc = fmaf(epi.s, load1(g + srow * go_stride + c), acc);
+      store1(grad_x + srow * F + c, acc);
     }
   }
 }
+
+// the fp16 flag of the entries that predate the element codes: any non-zero value means fp16
+static int32_t half_elem(int32_t is_half) { return is_half ? SPP_ELEM_F16 : SPP_ELEM_F32; }
 
 static int lanes_log2(int64_t pieces) {
   int l = 0;
@@ -364,49 +423,58 @@ static int lanes_log2(int64_t pieces) {
   return l;
 }
 
-// fn(Type<Tin>{}) for fp16 (half) or fp32 rows; with_elem_vec adds std::integral_constant<bool, VEC4>{}
+// fn(Type<T>{}) for the element code `elem` (spp.h: SPP_ELEM_F32 / _F16 / _BF16; the caller has checked it);
+// with_elem_vec adds std::integral_constant<bool, VEC4>{}.  with_f32_bf16: the codes without fp16 (outputs, gradients).
 template <typename T> struct Type { using type = T; };
 template <class Fn>
-static void with_elem(int32_t half, Fn&& fn) {
-  half ? fn(Type<__half>{}) : fn(Type<float>{});
+static void with_elem(int32_t elem, Fn&& fn) {
+  elem == SPP_ELEM_BF16 ? fn(Type<bf16>{}) : elem ? fn(Type<__half>{}) : fn(Type<float>{});
 }
 template <class Fn>
-static void with_elem_vec(int32_t half, bool vec, Fn&& fn) {
-  with_elem(half, [&](auto tin) { vec ? fn(tin, std::true_type{}) : fn(tin, std::false_type{}); });
+static void with_elem_vec(int32_t elem, bool vec, Fn&& fn) {
+  with_elem(elem, [&](auto tin) { vec ? fn(tin, std::true_type{}) : fn(tin, std::false_type{}); });
 }
+template <class Fn>
+static void with_f32_bf16(int32_t elem, Fn&& fn) {
+  elem == SPP_ELEM_BF16 ? fn(Type<bf16>{}) : fn(Type<float>{});
+}
+static bool elem_ok(int32_t elem) { return elem == SPP_ELEM_F32 || elem == SPP_ELEM_F16 || elem == SPP_ELEM_BF16; }
+static bool f32_bf16_ok(int32_t elem) { return elem == SPP_ELEM_F32 || elem == SPP_ELEM_BF16; }
+static int64_t elem_bytes(int32_t elem) { return elem == SPP_ELEM_F32 ? 4 : 2; }
 
 }  // namespace spp
 
 using namespace spp;
 
 // ---- one launcher per kernel ----
-template <typename Tin, bool VEC4, class Src, class Epi>
+template <typename Tin, typename Tout, bool VEC4, class Src, class Epi>
 static void launch_agg_fwd(const int64_t* rowptr, const int64_t* col, int64_t T, const void* x, int64_t x_stride,
-                           const int64_t* nid, int64_t x_rows, int64_t F, Epi epi, float* out, int64_t out_stride,
+                           const int64_t* nid, int64_t x_rows, int64_t F, Epi epi, void* out, int64_t out_stride,
                            void* stream) {
   const int lpr_log2 = lanes_log2(VEC4 ? F / 4 : F);
   const unsigned grid = (unsigned)ceil_div(T << lpr_log2, kAggNT);
-  hipLaunchKernelGGL((k_agg_fwd<Tin, VEC4, Src, Epi>), dim3(grid), dim3(kAggNT), 0, as_stream(stream), rowptr, col, T,
-                     static_cast<const Tin*>(x), x_stride, F, lpr_log2, out, out_stride, epi, nid, x_rows);
+  hipLaunchKernelGGL((k_agg_fwd<Tin, Tout, VEC4, Src, Epi>), dim3(grid), dim3(kAggNT), 0, as_stream(stream), rowptr, col,
+                     T, static_cast<const Tin*>(x), x_stride, F, lpr_log2, static_cast<Tout*>(out), out_stride, epi, nid,
+                     x_rows);
 }
 
-template <class Epi>
-static void launch_agg_bwd_scatter(const int64_t* rowptr, const int64_t* col, int64_t T, const float* grad_out,
+template <class Epi, typename Tg>
+static void launch_agg_bwd_scatter(const int64_t* rowptr, const int64_t* col, int64_t T, const Tg* grad_out,
                                    int64_t go_stride, int64_t F, float* grad_x, hipStream_t st) {
   const int lpr_log2 = lanes_log2(F);
   const unsigned grid = (unsigned)ceil_div(T << lpr_log2, kAggNT);
-  hipLaunchKernelGGL(k_agg_bwd_scatter<Epi>, dim3(grid), dim3(kAggNT), 0, st, rowptr, col, T, grad_out, go_stride, F,
-                     lpr_log2, grad_x);
+  hipLaunchKernelGGL((k_agg_bwd_scatter<Epi, Tg>), dim3(grid), dim3(kAggNT), 0, st, rowptr, col, T, grad_out, go_stride,
+                     F, lpr_log2, grad_x);
 }
 
 // The forward entries' shared validation (`who` names the entry in the errors), the vector-width test and the launch.
 // Src: Dense (x = the batch's matrix), Table (x = the resident table, nid = the batch's n_id, x_rows its rows) or Refs
 // (nid = the row addresses; x, x_stride unused).  The sum entries have their row source's buffers checked here, the
-// mean entries check theirs themselves.
+// mean entries check theirs themselves.  x_elem: fp32 / fp16 / bf16 rows; out_elem: fp32 / bf16 (both checked by the caller).
 template <class Src, class Epi>
 static spp_status agg_forward(const char* who, const int64_t* rowptr, const int64_t* col, int64_t T, const void* x,
-                              int32_t x_is_half, int64_t x_stride, const int64_t* nid, int64_t x_rows, int64_t F,
-                              Epi epi, float* out, int64_t out_stride, void* stream) {
+                              int32_t x_elem, int64_t x_stride, const int64_t* nid, int64_t x_rows, int64_t F,
+                              Epi epi, void* out, int32_t out_elem, int64_t out_stride, void* stream) {
   constexpr bool kRefs = std::is_same<Src, Refs>::value;
   SPP_REQUIRE(T >= 0 && F >= 0, "%s: negative size", who);
   if (T == 0 || F == 0) return SPP_OK;
@@ -415,13 +483,15 @@ static spp_status agg_forward(const char* who, const int64_t* rowptr, const int6
   SPP_REQUIRE(kRefs || x_stride >= F, "%s: row stride smaller than the row", who);
   if (out_stride <= 0) out_stride = F;
   SPP_REQUIRE(out_stride >= F, "%s: output stride smaller than the row", who);
-  const int64_t esz = x_is_half ? 2 : 4;
-  // row references: 8-byte aligned fp16 / 16-byte aligned fp32 rows when F % 4 == 0 (spp_mfg_out.row_addr)
-  const bool vec = (F % 4 == 0) && (reinterpret_cast<uintptr_t>(out) % 16 == 0) && (out_stride % 4 == 0) &&
+  const int64_t esz = elem_bytes(x_elem), osz = elem_bytes(out_elem);
+  // row references: 8-byte aligned fp16 / bf16 / 16-byte aligned fp32 rows when F % 4 == 0 (spp_mfg_out.row_addr)
+  const bool vec = (F % 4 == 0) && (reinterpret_cast<uintptr_t>(out) % (4 * osz) == 0) && (out_stride % 4 == 0) &&
                    (kRefs || (((x_stride * esz) % (4 * esz) == 0) && (reinterpret_cast<uintptr_t>(x) % (4 * esz) == 0)));
-  with_elem_vec(x_is_half, vec, [&](auto tin, auto v) {
-    launch_agg_fwd<typename decltype(tin)::type, decltype(v)::value, Src>(rowptr, col, T, x, x_stride, nid, x_rows, F,
-                                                                          epi, out, out_stride, stream);
+  with_f32_bf16(out_elem, [&](auto tout) {
+    with_elem_vec(x_elem, vec, [&](auto tin, auto v) {
+      launch_agg_fwd<typename decltype(tin)::type, typename decltype(tout)::type, decltype(v)::value, Src>(
+          rowptr, col, T, x, x_stride, nid, x_rows, F, epi, out, out_stride, stream);
+    });
   });
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
@@ -430,16 +500,18 @@ static spp_status agg_forward(const char* who, const int64_t* rowptr, const int6
 extern "C" spp_status spp_csr_mean_forward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
                                            const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t F,
                                            float* out_dev, int64_t out_stride_elems, void* stream) {
-  return agg_forward<Dense>("spp_csr_mean_forward", rowptr_dev, col_dev, num_targets, x_dev, x_is_half, x_stride_elems,
-                            nullptr, 0, F, Mean<false>{0, {}}, out_dev, out_stride_elems, stream);
+  return agg_forward<Dense>("spp_csr_mean_forward", rowptr_dev, col_dev, num_targets, x_dev, half_elem(x_is_half),
+                            x_stride_elems, nullptr, 0, F, Mean<false>{0, {}}, out_dev, SPP_ELEM_F32, out_stride_elems,
+                            stream);
 }
 
 extern "C" spp_status spp_sage_operand_forward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
                                                const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t F,
                                                float* out_dev, int64_t out_stride_elems, void* stream) {
   SPP_REQUIRE(out_stride_elems >= 2 * F, "spp_sage_operand_forward: the operand [mean | x_target] needs 2F columns");
-  return agg_forward<Dense>("spp_csr_mean_forward", rowptr_dev, col_dev, num_targets, x_dev, x_is_half, x_stride_elems,
-                            nullptr, 0, F, Mean<false>{1, {}}, out_dev, out_stride_elems, stream);
+  return agg_forward<Dense>("spp_csr_mean_forward", rowptr_dev, col_dev, num_targets, x_dev, half_elem(x_is_half),
+                            x_stride_elems, nullptr, 0, F, Mean<false>{1, {}}, out_dev, SPP_ELEM_F32, out_stride_elems,
+                            stream);
 }
 
 extern "C" spp_status spp_sage_operand_forward_table(const int64_t* rowptr_dev, const int64_t* col_dev,
@@ -450,9 +522,9 @@ extern "C" spp_status spp_sage_operand_forward_table(const int64_t* rowptr_dev, 
   SPP_REQUIRE(out_stride_elems >= 2 * F, "spp_sage_operand_forward_table: the operand [mean | x_target] needs 2F columns");
   SPP_REQUIRE(num_targets == 0 || (n_id_dev && table_dev && table_rows > 0),
               "spp_sage_operand_forward_table: needs the feature table and the batch's node ids");
-  return agg_forward<Table>("spp_csr_mean_forward", rowptr_dev, col_dev, num_targets, table_dev, table_is_half,
-                            table_stride_elems, n_id_dev, table_rows, F, Mean<false>{1, {}}, out_dev, out_stride_elems,
-                            stream);
+  return agg_forward<Table>("spp_csr_mean_forward", rowptr_dev, col_dev, num_targets, table_dev, half_elem(table_is_half),
+                            table_stride_elems, n_id_dev, table_rows, F, Mean<false>{1, {}}, out_dev, SPP_ELEM_F32,
+                            out_stride_elems, stream);
 }
 
 extern "C" spp_status spp_sage_operand_forward_rows(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
@@ -464,9 +536,10 @@ extern "C" spp_status spp_sage_operand_forward_rows(const int64_t* rowptr_dev, c
   SPP_REQUIRE(out_stride_elems >= 2 * F, "spp_sage_operand_forward_rows: the operand [mean | x_target] needs 2F columns");
   SPP_REQUIRE(F % 4 == 0 && (reinterpret_cast<uintptr_t>(out_dev) % 16 == 0) && (out_stride_elems % 4 == 0),
               "spp_sage_operand_forward_rows: needs F %% 4 == 0 and a 16-byte aligned operand (F = %lld)", (long long)F);
-  with_elem(rows_are_half, [&](auto tin) {
-    launch_agg_fwd<typename decltype(tin)::type, true, Refs>(rowptr_dev, col_dev, num_targets, nullptr, 0, row_addr_dev,
-                                                             0, F, Mean<false>{1, {}}, out_dev, out_stride_elems, stream);
+  with_elem(half_elem(rows_are_half), [&](auto tin) {
+    launch_agg_fwd<typename decltype(tin)::type, float, true, Refs>(rowptr_dev, col_dev, num_targets, nullptr, 0,
+                                                                    row_addr_dev, 0, F, Mean<false>{1, {}}, out_dev,
+                                                                    out_stride_elems, stream);
   });
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
@@ -491,8 +564,8 @@ extern "C" spp_status spp_sage_operand_forward_act(const int64_t* rowptr_dev, co
   SPP_REQUIRE(rowptr_dev && x_dev && out_dev && out_stride_elems >= 2 * F && F % 4 == 0 && out_stride_elems % 4 == 0 &&
                   reinterpret_cast<uintptr_t>(x_dev) % 16 == 0 && reinterpret_cast<uintptr_t>(out_dev) % 16 == 0,
               "spp_sage_operand_forward_act: needs dense fp32 rows with F %% 4 == 0 and 16-byte aligned buffers");
-  launch_agg_fwd<float, true, Dense>(rowptr_dev, col_dev, num_targets, x_dev, F, nullptr, 0, F,
-                                     Mean<true>{1, act_args(p, training, seed)}, out_dev, out_stride_elems, stream);
+  launch_agg_fwd<float, float, true, Dense>(rowptr_dev, col_dev, num_targets, x_dev, F, nullptr, 0, F,
+                                            Mean<true>{1, act_args(p, training, seed)}, out_dev, out_stride_elems, stream);
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
 }
@@ -506,8 +579,8 @@ extern "C" spp_status spp_relu_dropout_backward_pre(const float* grad_dev, const
                    reinterpret_cast<uintptr_t>(grad_x_dev)) % 16 == 0,
               "spp_relu_dropout_backward_pre: needs n %% 4 == 0 and 16-byte aligned buffers");
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n / 4, kAggNT), 256 * 32));
-  hipLaunchKernelGGL(k_relu_dropout_bwd_pre, dim3(grid), dim3(kAggNT), 0, as_stream(stream), grad_dev, z_dev, n,
-                     act_args(p, training, seed), grad_x_dev);
+  hipLaunchKernelGGL((k_relu_dropout_bwd_pre<float, float, true>), dim3(grid), dim3(kAggNT), 0, as_stream(stream),
+                     grad_dev, z_dev, n, act_args(p, training, seed), grad_x_dev);
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
 }
@@ -520,7 +593,7 @@ extern "C" spp_status spp_csr_mean_backward(const int64_t* rowptr_dev, const int
   SPP_REQUIRE(rowptr_dev && grad_out_dev && grad_x_dev, "spp_csr_mean_backward: NULL buffer");
   if (grad_out_stride_elems <= 0) grad_out_stride_elems = F;
   SPP_REQUIRE(grad_out_stride_elems >= F, "spp_csr_mean_backward: gradient stride smaller than the row");
-  launch_agg_bwd_scatter<Mean<false>>(rowptr_dev, col_dev, num_targets, grad_out_dev, grad_out_stride_elems, F,
+  launch_agg_bwd_scatter<Mean<false>, float>(rowptr_dev, col_dev, num_targets, grad_out_dev, grad_out_stride_elems, F,
                                       grad_x_dev, as_stream(stream));
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
@@ -539,7 +612,7 @@ extern "C" spp_status spp_sage_operand_backward(const int64_t* rowptr_dev, const
   hipStream_t st = as_stream(stream);
   const int64_t n4 = num_sources * F / 4;
   const unsigned g0 = (unsigned)std::min<int64_t>(ceil_div(n4, kAggNT), 256 * 32);
-  hipLaunchKernelGGL(k_grad_init, dim3(g0), dim3(kAggNT), 0, st, grad_out_dev, grad_out_stride_elems, num_targets,
+  hipLaunchKernelGGL(k_grad_init<float>, dim3(g0), dim3(kAggNT), 0, st, grad_out_dev, grad_out_stride_elems, num_targets,
                      num_sources, F, grad_x_dev);
   SPP_HIP_TRY(hipGetLastError());
   if (num_targets == 0) return SPP_OK;
@@ -596,12 +669,13 @@ static spp_status transpose_hop(const int64_t* rowptr_dev, const int64_t* col_de
 
 // The gather-form backward entries: their shared validation (`who` names the entry), the transposed hop and the
 // launch of k_agg_bwd_gather.  The operand's (Mean) gradient has the vector form only; the sum's takes any F and row stride.
-template <class Epi>
+// grad_out, z and grad_x are fp32 or bf16 (vector form: rows aligned to 4 elements).
+template <class Epi, typename Tg, typename Tz, typename Tout>
 static spp_status agg_backward_gather(const char* who, const int64_t* rowptr_dev, const int64_t* col_dev,
                                       int64_t num_targets, int64_t num_sources, int64_t num_edges,
-                                      const float* grad_out_dev, int64_t grad_out_stride_elems, int64_t F, Epi epi,
-                                      float* grad_x_dev, void* workspace_dev, int64_t workspace_bytes,
-                                      const float* z_pre_dev, void* stream) {
+                                      const Tg* grad_out_dev, int64_t grad_out_stride_elems, int64_t F, Epi epi,
+                                      Tout* grad_x_dev, void* workspace_dev, int64_t workspace_bytes,
+                                      const Tz* z_pre_dev, void* stream) {
   SPP_REQUIRE(num_targets >= 0 && num_sources >= num_targets && F >= 0 && num_edges >= 0, "%s: bad sizes", who);
   if (num_sources == 0 || F == 0) return SPP_OK;
   SPP_REQUIRE(num_sources < (1ll << 31) && num_edges < (1ll << 31), "%s: 32-bit indices", who);
@@ -609,7 +683,8 @@ static spp_status agg_backward_gather(const char* who, const int64_t* rowptr_dev
               "%s: NULL buffer", who);
   if (Epi::kSum && grad_out_stride_elems <= 0) grad_out_stride_elems = F;
   const bool vec = F % 4 == 0 && grad_out_stride_elems % 4 == 0 &&
-                   (reinterpret_cast<uintptr_t>(grad_out_dev) | reinterpret_cast<uintptr_t>(grad_x_dev)) % 16 == 0;
+                   reinterpret_cast<uintptr_t>(grad_out_dev) % (4 * sizeof(Tg)) == 0 &&
+                   reinterpret_cast<uintptr_t>(grad_x_dev) % (4 * sizeof(Tout)) == 0;
   const bool ws_aligned = reinterpret_cast<uintptr_t>(workspace_dev) % 16 == 0;
   if (Epi::kSum)
     SPP_REQUIRE(grad_out_stride_elems >= F && ws_aligned,
@@ -626,7 +701,7 @@ static spp_status agg_backward_gather(const char* who, const int64_t* rowptr_dev
   const int lpr_log2 = lanes_log2(vec ? F / 4 : F);
   const unsigned grid = (unsigned)ceil_div(num_sources << lpr_log2, kAggNT);
   auto launch = [&](auto v) {
-    hipLaunchKernelGGL((k_agg_bwd_gather<decltype(v)::value, Epi>), dim3(grid), dim3(kAggNT), 0, st, hop.start, hop.tcol,
+    hipLaunchKernelGGL((k_agg_bwd_gather<Tg, Tz, Tout, decltype(v)::value, Epi>), dim3(grid), dim3(kAggNT), 0, st, hop.start, hop.tcol,
                        hop.inv, num_targets, num_sources, grad_out_dev, grad_out_stride_elems, F, lpr_log2, grad_x_dev,
                        z_pre_dev, epi);
   };
@@ -643,7 +718,7 @@ extern "C" spp_status spp_sage_operand_backward_gather(const int64_t* rowptr_dev
                                                        int64_t workspace_bytes, void* stream) {
   return agg_backward_gather("spp_sage_operand_backward_gather", rowptr_dev, col_dev, num_targets, num_sources,
                              num_edges, grad_out_dev, grad_out_stride_elems, F, Mean<false>{1, {}}, grad_x_dev,
-                             workspace_dev, workspace_bytes, nullptr, stream);
+                             workspace_dev, workspace_bytes, (const float*)nullptr, stream);
 }
 
 // the same, followed in the same pass by the ReLU + dropout backward of spp_relu_dropout_backward_pre: grad_x
@@ -1104,26 +1179,28 @@ __global__ __launch_bounds__(kAggNT) void k_gat_gx_gather(const int32_t* __restr
 
 }  // namespace spp
 
-static spp_status gat_check(int64_t K, const void* x, int64_t x_stride, int32_t is_half, const char* who) {
-  const int64_t esz = is_half ? 2 : 4;
+// x_elem: the element code of x's rows (0 fp32, 1 fp16, 2 bf16); the softmax statistics, z and all gradients stay fp32
+static spp_status gat_check(int64_t K, const void* x, int64_t x_stride, int32_t x_elem, const char* who) {
+  SPP_REQUIRE(elem_ok(x_elem), "%s: unknown element code %d", who, (int)x_elem);
+  const int64_t esz = elem_bytes(x_elem);
   SPP_REQUIRE(K > 0 && K % 4 == 0 && K / 4 <= spp::kAggNT && x_stride >= K && (x_stride * esz) % (4 * esz) == 0 &&
                   reinterpret_cast<uintptr_t>(x) % (4 * esz) == 0,
               "%s: needs K %% 4 == 0, K <= %d and rows aligned to 4 elements", who, 4 * spp::kAggNT);
   return SPP_OK;
 }
 
-extern "C" spp_status spp_gat_logits(const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t num_sources,
+extern "C" spp_status spp_gat_logits(const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t num_sources,
                                      int64_t num_targets, int64_t K, const float* v_src_dev, const float* v_dst_dev,
                                      float* a_src_dev, float* a_dst_dev, void* stream) {
   SPP_REQUIRE(num_sources >= num_targets && num_targets >= 0, "spp_gat_logits: bad sizes");
   if (num_sources == 0) return SPP_OK;
-  SPP_TRY(gat_check(K, x_dev, x_stride_elems, x_is_half, "spp_gat_logits"));
+  SPP_TRY(gat_check(K, x_dev, x_stride_elems, x_elem, "spp_gat_logits"));
   SPP_REQUIRE(v_src_dev && v_dst_dev && a_src_dev && (a_dst_dev || num_targets == 0) &&
                   reinterpret_cast<uintptr_t>(v_src_dev) % 16 == 0 && reinterpret_cast<uintptr_t>(v_dst_dev) % 16 == 0,
               "spp_gat_logits: NULL or unaligned buffer");
   const int lpr_log2 = lanes_log2(K / 4);
   const unsigned grid = (unsigned)ceil_div(ceil_div(num_sources, kDotRows) << lpr_log2, kAggNT);
-  with_elem(x_is_half, [&](auto tin) {
+  with_elem(x_elem, [&](auto tin) {
     using Tin = typename decltype(tin)::type;
     hipLaunchKernelGGL(k_rowdot2<Tin>, dim3(grid), dim3(kAggNT), 0, as_stream(stream), static_cast<const Tin*>(x_dev),
                        x_stride_elems, num_sources, num_targets, K, v_src_dev, v_dst_dev, lpr_log2, a_src_dev, a_dst_dev);
@@ -1132,12 +1209,12 @@ extern "C" spp_status spp_gat_logits(const void* x_dev, int32_t x_is_half, int64
   return SPP_OK;
 }
 
-extern "C" spp_status spp_gat_logits_backward(const void* x_dev, int32_t x_is_half, int64_t x_stride_elems,
+extern "C" spp_status spp_gat_logits_backward(const void* x_dev, int32_t x_elem, int64_t x_stride_elems,
                                               int64_t num_sources, int64_t num_targets, int64_t K,
                                               const float* grad_a_src_dev, const float* grad_a_dst_dev,
                                               float* grad_v_src_dev, float* grad_v_dst_dev, void* stream) {
   SPP_REQUIRE(num_sources >= num_targets && num_targets >= 0, "spp_gat_logits_backward: bad sizes");
-  SPP_TRY(gat_check(K, x_dev, x_stride_elems, x_is_half, "spp_gat_logits_backward"));
+  SPP_TRY(gat_check(K, x_dev, x_stride_elems, x_elem, "spp_gat_logits_backward"));
   SPP_REQUIRE(grad_v_src_dev && grad_v_dst_dev, "spp_gat_logits_backward: NULL output");
   hipStream_t st = as_stream(stream);
   SPP_HIP_TRY(hipMemsetAsync(grad_v_src_dev, 0, sizeof(float) * (size_t)K, st));
@@ -1148,7 +1225,7 @@ extern "C" spp_status spp_gat_logits_backward(const void* x_dev, int32_t x_is_ha
   // between 1024 and 4096 rows each
   const int64_t rows_per_wg = std::max<int64_t>(1024, std::min<int64_t>(4096, ceil_div(num_sources, 256)));
   const unsigned grid = (unsigned)ceil_div(num_sources, rows_per_wg);
-  with_elem(x_is_half, [&](auto tin) {
+  with_elem(x_elem, [&](auto tin) {
     using Tin = typename decltype(tin)::type;
     hipLaunchKernelGGL(k_colsum2<Tin>, dim3(grid), dim3(kColsumNT), 0, st, static_cast<const Tin*>(x_dev), x_stride_elems,
                        num_sources, num_targets, K, grad_a_src_dev, grad_a_dst_dev, rows_per_wg, grad_v_src_dev,
@@ -1159,17 +1236,17 @@ extern "C" spp_status spp_gat_logits_backward(const void* x_dev, int32_t x_is_ha
 }
 
 extern "C" spp_status spp_gat_aggregate_forward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
-                                                const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t K,
+                                                const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t K,
                                                 const float* a_src_dev, const float* a_dst_dev, float negative_slope,
                                                 float* z_dev, float* row_max_dev, float* row_sum_dev, void* stream) {
   SPP_REQUIRE(num_targets >= 0, "spp_gat_aggregate_forward: negative size");
   if (num_targets == 0) return SPP_OK;
-  SPP_TRY(gat_check(K, x_dev, x_stride_elems, x_is_half, "spp_gat_aggregate_forward"));
+  SPP_TRY(gat_check(K, x_dev, x_stride_elems, x_elem, "spp_gat_aggregate_forward"));
   SPP_REQUIRE(rowptr_dev && a_src_dev && a_dst_dev && z_dev && row_max_dev && row_sum_dev &&
                   reinterpret_cast<uintptr_t>(z_dev) % 16 == 0, "spp_gat_aggregate_forward: NULL or unaligned buffer");
   const int lpr_log2 = lanes_log2(K / 4);
   const unsigned grid = (unsigned)ceil_div(num_targets << lpr_log2, kAggNT);
-  with_elem(x_is_half, [&](auto tin) {
+  with_elem(x_elem, [&](auto tin) {
     using Tin = typename decltype(tin)::type;
     hipLaunchKernelGGL(k_gat_agg_fwd<Tin>, dim3(grid), dim3(kAggNT), 0, as_stream(stream), rowptr_dev, col_dev,
                        num_targets, static_cast<const Tin*>(x_dev), x_stride_elems, K, a_src_dev, a_dst_dev,
@@ -1180,31 +1257,31 @@ extern "C" spp_status spp_gat_aggregate_forward(const int64_t* rowptr_dev, const
 }
 
 static spp_status gat_aggregate_backward_launch(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
-                                                const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t K,
+                                                const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t K,
                                                 const float* a_src_dev, const float* a_dst_dev, float negative_slope,
                                                 const float* z_dev, const float* row_max_dev, const float* row_sum_dev,
                                                 const float* grad_z_dev, float* grad_x_dev, float* grad_a_src_dev,
                                                 float* grad_a_dst_dev, float* alpha_e, float* alpha_self, void* stream);
 
 extern "C" spp_status spp_gat_aggregate_backward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
-                                                 const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t K,
+                                                 const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t K,
                                                  const float* a_src_dev, const float* a_dst_dev, float negative_slope,
                                                  const float* z_dev, const float* row_max_dev, const float* row_sum_dev,
                                                  const float* grad_z_dev, float* grad_x_dev /* NULL: not wanted */,
                                                  float* grad_a_src_dev, float* grad_a_dst_dev, void* stream) {
   SPP_REQUIRE(num_targets >= 0, "spp_gat_aggregate_backward: negative size");
   if (num_targets == 0) return SPP_OK;
-  SPP_TRY(gat_check(K, x_dev, x_stride_elems, x_is_half, "spp_gat_aggregate_backward"));
+  SPP_TRY(gat_check(K, x_dev, x_stride_elems, x_elem, "spp_gat_aggregate_backward"));
   SPP_REQUIRE(rowptr_dev && a_src_dev && a_dst_dev && z_dev && row_max_dev && row_sum_dev && grad_z_dev &&
                   grad_a_src_dev && grad_a_dst_dev && reinterpret_cast<uintptr_t>(grad_z_dev) % 16 == 0 &&
                   reinterpret_cast<uintptr_t>(z_dev) % 16 == 0, "spp_gat_aggregate_backward: NULL or unaligned buffer");
-  return gat_aggregate_backward_launch(rowptr_dev, col_dev, num_targets, x_dev, x_is_half, x_stride_elems, K, a_src_dev,
+  return gat_aggregate_backward_launch(rowptr_dev, col_dev, num_targets, x_dev, x_elem, x_stride_elems, K, a_src_dev,
                                        a_dst_dev, negative_slope, z_dev, row_max_dev, row_sum_dev, grad_z_dev, grad_x_dev,
                                        grad_a_src_dev, grad_a_dst_dev, nullptr, nullptr, stream);
 }
 
 static spp_status gat_aggregate_backward_launch(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
-                                                const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t K,
+                                                const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t K,
                                                 const float* a_src_dev, const float* a_dst_dev, float negative_slope,
                                                 const float* z_dev, const float* row_max_dev, const float* row_sum_dev,
                                                 const float* grad_z_dev, float* grad_x_dev, float* grad_a_src_dev,
@@ -1212,7 +1289,7 @@ static spp_status gat_aggregate_backward_launch(const int64_t* rowptr_dev, const
   const bool vec = grad_x_dev == nullptr;
   const int lpt_log2 = lanes_log2(vec ? K / 4 : K);
   const unsigned grid = (unsigned)ceil_div(num_targets << lpt_log2, kAggNT);
-  with_elem_vec(x_is_half, vec, [&](auto tin, auto v) {
+  with_elem_vec(x_elem, vec, [&](auto tin, auto v) {
     using Tin = typename decltype(tin)::type;
     hipLaunchKernelGGL((k_gat_agg_bwd<Tin, decltype(v)::value>), dim3(grid), dim3(kAggNT), 0, as_stream(stream), rowptr_dev,
                        col_dev, num_targets, static_cast<const Tin*>(x_dev), x_stride_elems, K, a_src_dev, a_dst_dev,
@@ -1234,7 +1311,7 @@ extern "C" int64_t spp_gat_aggregate_backward_gather_workspace_bytes(int64_t num
 // the atomic form leaves to the caller.  grad_a_src_dev [S] is zeroed by the caller as before.
 extern "C" spp_status spp_gat_aggregate_backward_gather(const int64_t* rowptr_dev, const int64_t* col_dev,
                                                         int64_t num_targets, int64_t num_sources, int64_t num_edges,
-                                                        const void* x_dev, int32_t x_is_half, int64_t x_stride_elems,
+                                                        const void* x_dev, int32_t x_elem, int64_t x_stride_elems,
                                                         int64_t K, const float* a_src_dev, const float* a_dst_dev,
                                                         float negative_slope, const float* z_dev,
                                                         const float* row_max_dev, const float* row_sum_dev,
@@ -1245,7 +1322,7 @@ extern "C" spp_status spp_gat_aggregate_backward_gather(const int64_t* rowptr_de
   SPP_REQUIRE(num_targets >= 0 && num_sources >= num_targets && num_edges >= 0,
               "spp_gat_aggregate_backward_gather: bad sizes");
   if (num_sources == 0) return SPP_OK;
-  SPP_TRY(gat_check(K, x_dev, x_stride_elems, x_is_half, "spp_gat_aggregate_backward_gather"));
+  SPP_TRY(gat_check(K, x_dev, x_stride_elems, x_elem, "spp_gat_aggregate_backward_gather"));
   SPP_REQUIRE(num_sources < (1ll << 31) && num_edges < (1ll << 31), "spp_gat_aggregate_backward_gather: 32-bit indices");
   SPP_REQUIRE(rowptr_dev && a_src_dev && a_dst_dev && z_dev && row_max_dev && row_sum_dev && grad_z_dev && v_src_dev &&
                   v_dst_dev && grad_x_dev && grad_a_src_dev && grad_a_dst_dev && workspace_dev,
@@ -1262,7 +1339,7 @@ extern "C" spp_status spp_gat_aggregate_backward_gather(const int64_t* rowptr_de
   const int64_t alpha_bytes = align16(4 * num_edges) + align16(4 * num_targets);
   // the attention weights of every entry + grad_a_src / grad_a_dst (no input gradient by atomics)
   if (num_targets > 0)
-    SPP_TRY(gat_aggregate_backward_launch(rowptr_dev, col_dev, num_targets, x_dev, x_is_half, x_stride_elems, K, a_src_dev,
+    SPP_TRY(gat_aggregate_backward_launch(rowptr_dev, col_dev, num_targets, x_dev, x_elem, x_stride_elems, K, a_src_dev,
                                           a_dst_dev, negative_slope, z_dev, row_max_dev, row_sum_dev, grad_z_dev, nullptr,
                                           grad_a_src_dev, grad_a_dst_dev, alpha_e, alpha_self, stream));
   TransposedHop hop;
@@ -1322,8 +1399,9 @@ extern "C" spp_status spp_gat_backward(const int64_t* rowptr_dev, const int64_t*
 extern "C" spp_status spp_csr_sum_forward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
                                           const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t F,
                                           float self_scale, float* out_dev, int64_t out_stride_elems, void* stream) {
-  return agg_forward<Dense>("spp_csr_sum_forward", rowptr_dev, col_dev, num_targets, x_dev, x_is_half, x_stride_elems,
-                            nullptr, 0, F, Sum{self_scale}, out_dev, out_stride_elems, stream);
+  return agg_forward<Dense>("spp_csr_sum_forward", rowptr_dev, col_dev, num_targets, x_dev, half_elem(x_is_half),
+                            x_stride_elems, nullptr, 0, F, Sum{self_scale}, out_dev, SPP_ELEM_F32, out_stride_elems,
+                            stream);
 }
 
 extern "C" spp_status spp_csr_sum_forward_table(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
@@ -1332,16 +1410,16 @@ extern "C" spp_status spp_csr_sum_forward_table(const int64_t* rowptr_dev, const
                                                 float* out_dev, int64_t out_stride_elems, void* stream) {
   SPP_REQUIRE(num_targets == 0 || (n_id_dev && table_dev && table_rows > 0),
               "spp_csr_sum_forward_table: needs the feature table and the batch's node ids");
-  return agg_forward<Table>("spp_csr_sum_forward_table", rowptr_dev, col_dev, num_targets, table_dev, table_is_half,
-                            table_stride_elems, n_id_dev, table_rows, F, Sum{self_scale}, out_dev, out_stride_elems,
-                            stream);
+  return agg_forward<Table>("spp_csr_sum_forward_table", rowptr_dev, col_dev, num_targets, table_dev,
+                            half_elem(table_is_half), table_stride_elems, n_id_dev, table_rows, F, Sum{self_scale}, out_dev,
+                            SPP_ELEM_F32, out_stride_elems, stream);
 }
 
 extern "C" spp_status spp_csr_sum_forward_rows(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
                                                const int64_t* row_addr_dev, int32_t rows_are_half, int64_t F,
                                                float self_scale, float* out_dev, int64_t out_stride_elems, void* stream) {
-  return agg_forward<Refs>("spp_csr_sum_forward_rows", rowptr_dev, col_dev, num_targets, nullptr, rows_are_half, 0,
-                           row_addr_dev, 0, F, Sum{self_scale}, out_dev, out_stride_elems, stream);
+  return agg_forward<Refs>("spp_csr_sum_forward_rows", rowptr_dev, col_dev, num_targets, nullptr, half_elem(rows_are_half),
+                           0, row_addr_dev, 0, F, Sum{self_scale}, out_dev, SPP_ELEM_F32, out_stride_elems, stream);
 }
 
 extern "C" spp_status spp_csr_sum_backward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
@@ -1354,11 +1432,11 @@ extern "C" spp_status spp_csr_sum_backward(const int64_t* rowptr_dev, const int6
   SPP_REQUIRE(grad_out_stride_elems >= F, "spp_csr_sum_backward: gradient stride smaller than the row");
   hipStream_t st = as_stream(stream);
   const unsigned g0 = (unsigned)std::min<int64_t>(ceil_div(num_sources * F, kAggNT), 256 * 32);
-  hipLaunchKernelGGL(k_sum_grad_init, dim3(g0), dim3(kAggNT), 0, st, grad_out_dev, grad_out_stride_elems, num_targets,
+  hipLaunchKernelGGL(k_sum_grad_init<float>, dim3(g0), dim3(kAggNT), 0, st, grad_out_dev, grad_out_stride_elems, num_targets,
                      num_sources, F, self_scale, grad_x_dev);
   SPP_HIP_TRY(hipGetLastError());
   if (num_targets == 0) return SPP_OK;
-  launch_agg_bwd_scatter<Sum>(rowptr_dev, col_dev, num_targets, grad_out_dev, grad_out_stride_elems, F, grad_x_dev, st);
+  launch_agg_bwd_scatter<Sum, float>(rowptr_dev, col_dev, num_targets, grad_out_dev, grad_out_stride_elems, F, grad_x_dev, st);
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
 }
@@ -1370,5 +1448,149 @@ extern "C" spp_status spp_csr_sum_backward_gather(const int64_t* rowptr_dev, con
                                                   void* stream) {
   return agg_backward_gather("spp_csr_sum_backward_gather", rowptr_dev, col_dev, num_targets, num_sources, num_edges,
                              grad_out_dev, grad_out_stride_elems, F, Sum{self_scale}, grad_x_dev, workspace_dev,
-                             workspace_bytes, nullptr, stream);
+                             workspace_bytes, (const float*)nullptr, stream);
+}
+
+// ================================================================================================
+// Aggregation by descriptor (include/spp.h: spp_agg_fwd_desc, spp_agg_bwd_desc): the launchers above with the element
+// types chosen per call -- fp32 / fp16 / bf16 rows in, fp32 / bf16 out -- for bf16 autocast training.
+// ================================================================================================
+extern "C" spp_status spp_agg_forward(const spp_agg_fwd_desc* desc, void* stream) {
+  static const char* who = "spp_agg_forward";
+  SPP_REQUIRE(desc, "%s: NULL descriptor", who);
+  const spp_agg_fwd_desc& d = *desc;
+  SPP_REQUIRE(d.source >= SPP_AGG_DENSE && d.source <= SPP_AGG_ROWS, "%s: unknown source %d", who, (int)d.source);
+  SPP_REQUIRE(d.epilogue >= SPP_AGG_MEAN && d.epilogue <= SPP_AGG_SUM, "%s: unknown epilogue %d", who, (int)d.epilogue);
+  SPP_REQUIRE(elem_ok(d.x_elem) && f32_bf16_ok(d.out_elem), "%s: unknown or unsupported element code (x %d, out %d)", who,
+              (int)d.x_elem, (int)d.out_elem);
+  const int64_t T = d.num_targets, F = d.F;
+  SPP_REQUIRE(T >= 0 && F >= 0, "%s: negative size", who);
+  const bool operand = d.epilogue == SPP_AGG_OPERAND || d.epilogue == SPP_AGG_OPERAND_ACT;
+  const int64_t width = operand ? 2 * F : F;
+  const int64_t out_stride = d.out_stride_elems > 0 ? d.out_stride_elems : width;
+  SPP_REQUIRE(out_stride >= width, "%s: output stride smaller than the output row", who);
+  if (T == 0 || F == 0) return SPP_OK;
+  SPP_REQUIRE(d.rowptr_dev && d.out_dev &&
+                  (d.source == SPP_AGG_ROWS ? d.n_id_dev != nullptr
+                                            : d.x_dev && (d.source == SPP_AGG_DENSE || (d.n_id_dev && d.x_rows > 0))),
+              "%s: NULL buffer or empty table", who);
+  if (d.epilogue == SPP_AGG_OPERAND_ACT) {
+    const int64_t esz = elem_bytes(d.x_elem), osz = elem_bytes(d.out_elem);
+    SPP_REQUIRE(d.source == SPP_AGG_DENSE && f32_bf16_ok(d.x_elem) && d.x_stride_elems == F && F % 4 == 0 &&
+                    out_stride % 4 == 0 && reinterpret_cast<uintptr_t>(d.x_dev) % (4 * esz) == 0 &&
+                    reinterpret_cast<uintptr_t>(d.out_dev) % (4 * osz) == 0 && d.p >= 0.f && d.p < 1.f,
+                "%s: the activated operand needs dense fp32 / bf16 rows, F %% 4 == 0, aligned buffers and 0 <= p < 1", who);
+    const Mean<true> epi{1, act_args(d.p, d.training, d.seed)};
+    with_f32_bf16(d.out_elem, [&](auto tout) {
+      with_f32_bf16(d.x_elem, [&](auto tin) {
+        launch_agg_fwd<typename decltype(tin)::type, typename decltype(tout)::type, true, Dense>(
+            d.rowptr_dev, d.col_dev, T, d.x_dev, F, nullptr, 0, F, epi, d.out_dev, out_stride, stream);
+      });
+    });
+    SPP_HIP_TRY(hipGetLastError());
+    return SPP_OK;
+  }
+  auto run = [&](auto src) {
+    using Src = decltype(src);
+    if (d.epilogue == SPP_AGG_SUM)
+      return agg_forward<Src>(who, d.rowptr_dev, d.col_dev, T, d.x_dev, d.x_elem, d.x_stride_elems, d.n_id_dev, d.x_rows,
+                              F, Sum{d.self_scale}, d.out_dev, d.out_elem, out_stride, stream);
+    return agg_forward<Src>(who, d.rowptr_dev, d.col_dev, T, d.x_dev, d.x_elem, d.x_stride_elems, d.n_id_dev, d.x_rows, F,
+                            Mean<false>{operand ? 1 : 0, {}}, d.out_dev, d.out_elem, out_stride, stream);
+  };
+  if (d.source == SPP_AGG_TABLE) return run(Table{});
+  if (d.source == SPP_AGG_ROWS) return run(Refs{});
+  return run(Dense{});
+}
+
+// the backward of one descriptor with its element types resolved (z is read by OPERAND_ACT only)
+template <typename Tg, typename Tz, typename Tout>
+static spp_status agg_backward_typed(const spp_agg_bwd_desc& d, void* workspace_dev, int64_t workspace_bytes,
+                                     void* stream) {
+  static const char* who = "spp_agg_backward";
+  const Tg* g = static_cast<const Tg*>(d.grad_out_dev);
+  const Tz* z = static_cast<const Tz*>(d.z_dev);
+  Tout* gx = static_cast<Tout*>(d.grad_x_dev);
+  const int64_t T = d.num_targets, S = d.num_sources, F = d.F;
+  const bool act = d.epilogue == SPP_AGG_OPERAND_ACT, operand = act || d.epilogue == SPP_AGG_OPERAND;
+  const int64_t gs = d.grad_out_stride_elems > 0 ? d.grad_out_stride_elems : (operand ? 2 * F : F);
+  if (act)
+    SPP_REQUIRE(z && reinterpret_cast<uintptr_t>(z) % (4 * sizeof(Tz)) == 0 && d.p >= 0.f && d.p < 1.f,
+                "%s: NULL / unaligned pre-activation or bad p", who);
+  if (d.form == SPP_AGG_GATHER) {
+    if (act)
+      return agg_backward_gather(who, d.rowptr_dev, d.col_dev, T, S, d.num_edges, g, gs, F,
+                                 Mean<true>{1, act_args(d.p, d.training, d.seed)}, gx, workspace_dev, workspace_bytes, z,
+                                 stream);
+    if (operand)
+      return agg_backward_gather(who, d.rowptr_dev, d.col_dev, T, S, d.num_edges, g, gs, F, Mean<false>{1, {}}, gx,
+                                 workspace_dev, workspace_bytes, (const float*)nullptr, stream);
+    return agg_backward_gather(who, d.rowptr_dev, d.col_dev, T, S, d.num_edges, g, gs, F, Sum{d.self_scale}, gx,
+                               workspace_dev, workspace_bytes, (const float*)nullptr, stream);
+  }
+  // scatter: fp32 atomics into an fp32 buffer (grad_x itself when it is fp32), then one pass that applies the
+  // activation's backward and / or rounds to bf16
+  SPP_REQUIRE(T >= 0 && S >= T && F >= 0, "%s: bad sizes", who);
+  if (S == 0 || F == 0) return SPP_OK;
+  SPP_REQUIRE(gx && ((g && d.rowptr_dev) || T == 0), "%s: NULL buffer", who);
+  SPP_REQUIRE(gs >= (operand ? 2 * F : F), "%s: gradient stride smaller than the row", who);
+  if (operand)
+    SPP_REQUIRE(F % 4 == 0 && gs % 4 == 0 && reinterpret_cast<uintptr_t>(g) % (4 * sizeof(Tg)) == 0 &&
+                    reinterpret_cast<uintptr_t>(gx) % (4 * sizeof(Tout)) == 0,
+                "%s: the operand's gradient needs F %% 4 == 0 and rows aligned to 4 elements", who);
+  const int64_t n = S * F;
+  float* acc = reinterpret_cast<float*>(gx);
+  if (!std::is_same<Tout, float>::value) {
+    SPP_REQUIRE(workspace_dev && reinterpret_cast<uintptr_t>(workspace_dev) % 16 == 0 && workspace_bytes >= 4 * n,
+                "%s: a bf16 scatter gradient needs a 16-byte aligned fp32 workspace of 4 * S * F bytes", who);
+    acc = static_cast<float*>(workspace_dev);
+  }
+  hipStream_t st = as_stream(stream);
+  if (operand) {
+    const unsigned g0 = (unsigned)std::min<int64_t>(ceil_div(n / 4, kAggNT), 256 * 32);
+    hipLaunchKernelGGL(k_grad_init<Tg>, dim3(g0), dim3(kAggNT), 0, st, g, gs, T, S, F, acc);
+    if (T > 0) launch_agg_bwd_scatter<Mean<false>>(d.rowptr_dev, d.col_dev, T, g, gs, F, acc, st);
+  } else if (d.epilogue == SPP_AGG_MEAN) {
+    SPP_HIP_TRY(hipMemsetAsync(acc, 0, 4 * (size_t)n, st));
+    if (T > 0) launch_agg_bwd_scatter<Mean<false>>(d.rowptr_dev, d.col_dev, T, g, gs, F, acc, st);
+  } else {
+    const unsigned g0 = (unsigned)std::min<int64_t>(ceil_div(n, kAggNT), 256 * 32);
+    hipLaunchKernelGGL(k_sum_grad_init<Tg>, dim3(g0), dim3(kAggNT), 0, st, g, gs, T, S, F, d.self_scale, acc);
+    if (T > 0) launch_agg_bwd_scatter<Sum>(d.rowptr_dev, d.col_dev, T, g, gs, F, acc, st);
+  }
+  const unsigned gp = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n / 4, kAggNT), 256 * 32));
+  if (act)
+    hipLaunchKernelGGL((k_relu_dropout_bwd_pre<Tz, Tout, true>), dim3(gp), dim3(kAggNT), 0, st, acc, z, n,
+                       act_args(d.p, d.training, d.seed), gx);
+  else if (!std::is_same<Tout, float>::value)
+    hipLaunchKernelGGL((k_relu_dropout_bwd_pre<float, Tout, false>), dim3(gp), dim3(kAggNT), 0, st, acc,
+                       (const float*)nullptr, n, ActArgs{}, gx);
+  SPP_HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
+
+extern "C" spp_status spp_agg_backward(const spp_agg_bwd_desc* desc, void* workspace_dev, int64_t workspace_bytes,
+                                       void* stream) {
+  static const char* who = "spp_agg_backward";
+  SPP_REQUIRE(desc, "%s: NULL descriptor", who);
+  const spp_agg_bwd_desc& d = *desc;
+  SPP_REQUIRE(d.form == SPP_AGG_SCATTER || d.form == SPP_AGG_GATHER, "%s: unknown form %d", who, (int)d.form);
+  SPP_REQUIRE(d.epilogue >= SPP_AGG_MEAN && d.epilogue <= SPP_AGG_SUM, "%s: unknown epilogue %d", who, (int)d.epilogue);
+  SPP_REQUIRE(f32_bf16_ok(d.grad_elem) && f32_bf16_ok(d.out_elem) && f32_bf16_ok(d.z_elem),
+              "%s: unknown or unsupported element code (grad %d, out %d, z %d)", who, (int)d.grad_elem, (int)d.out_elem,
+              (int)d.z_elem);
+  SPP_REQUIRE(!(d.epilogue == SPP_AGG_MEAN && d.form == SPP_AGG_GATHER), "%s: the plain mean has the scatter form only",
+              who);
+  spp_status rc = SPP_OK;
+  with_f32_bf16(d.grad_elem, [&](auto tg) {
+    with_f32_bf16(d.out_elem, [&](auto tout) {
+      using Tg = typename decltype(tg)::type;
+      using Tout = typename decltype(tout)::type;
+      if (d.epilogue == SPP_AGG_OPERAND_ACT && d.z_elem == SPP_ELEM_BF16)
+        rc = agg_backward_typed<Tg, bf16, Tout>(d, workspace_dev, workspace_bytes, stream);
+      else
+        rc = agg_backward_typed<Tg, float, Tout>(d, workspace_dev, workspace_bytes, stream);
+    });
+  });
+  return rc;
 }

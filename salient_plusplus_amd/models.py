@@ -6,6 +6,7 @@ models follow: GAT, GIN (sum aggregation) and SAGEResInception; ``get_model_type
 
 The constructor, ``reset_parameters`` and ``forward(x, adjs)`` follow the reference; ``adjs`` is
 what the data path delivers: ``[(adj_t, e_id, (S, T)), ...]``, outermost hop first."""
+import contextlib
 import ctypes as C
 
 import torch
@@ -24,6 +25,63 @@ def _stream():
     return C.c_void_p(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
 
 
+# ---- bf16 mixed precision (torch.autocast("cuda", dtype=torch.bfloat16)) ----
+# Under bf16 autocast the HIP nodes store activations, operands and activation gradients in bf16, run their GEMMs in
+# bf16 (fp32 accumulation) and keep parameters and parameter gradients fp32.  The aggregation kernels accumulate in fp32
+# and round every stored element once (include/spp.h, spp_agg_forward).  Under any other autocast dtype the nodes run
+# their fp32 path with autocast disabled inside them.  Each node decides in its forward and records the decision on
+# ctx; its backward uses explicit dtypes only.
+_ELEM = {torch.float32: nat.SPP_ELEM_F32, torch.float16: nat.SPP_ELEM_F16, torch.bfloat16: nat.SPP_ELEM_BF16}
+
+
+def amp_bf16():
+    """True when the HIP nodes take their bf16 path: CUDA autocast is on with dtype bfloat16"""
+    return torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16
+
+
+def _no_autocast():
+    return torch.autocast("cuda", enabled=False) if torch.is_autocast_enabled("cuda") else contextlib.nullcontext()
+
+
+def _a(t):
+    return t.data_ptr() if t is not None and t.numel() > 0 else None
+
+
+def _agg_forward(epilogue, rowptr, col, T, x, x_dtype, Fdim, out, *, source=nat.SPP_AGG_DENSE, x_stride=0, n_id=None,
+                 x_rows=0, scale=0.0, act=(0.0, 0, 0), st=None):
+    """spp_agg_forward: x is the address of the rows (or None), out a dense [T, F or 2F] fp32 / bf16 tensor"""
+    d = nat.AggFwdDesc(source=source, epilogue=epilogue, x_elem=_ELEM[x_dtype], out_elem=_ELEM[out.dtype],
+                       rowptr_dev=_a(rowptr), col_dev=_a(col), num_targets=T, x_dev=x, x_stride_elems=x_stride,
+                       x_rows=x_rows, n_id_dev=_a(n_id), F=Fdim, out_dev=_a(out), out_stride_elems=0,
+                       self_scale=float(scale), p=float(act[0]), training=int(act[1]), seed=int(act[2]) & (2 ** 64 - 1))
+    nat.check(nat.load().spp_agg_forward(C.byref(d), st if st is not None else _stream()))
+
+
+def _agg_backward(epilogue, rowptr, col, T, S, g, Fdim, grad_x, *, gather, z=None, scale=0.0, act=(0.0, 0, 0), st=None):
+    """spp_agg_backward: g [T, F or 2F] (unit column stride), grad_x [S, F] dense; the workspace is allocated here"""
+    L = nat.load()
+    E = col.numel()
+    if gather:
+        nbytes = int(L.spp_sage_operand_backward_workspace_bytes(T, S, E))
+    else:
+        nbytes = 4 * S * Fdim if grad_x.dtype != torch.float32 else 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=grad_x.device) if nbytes else None
+    d = nat.AggBwdDesc(form=nat.SPP_AGG_GATHER if gather else nat.SPP_AGG_SCATTER, epilogue=epilogue,
+                       grad_elem=_ELEM[g.dtype], out_elem=_ELEM[grad_x.dtype],
+                       z_elem=_ELEM[z.dtype] if z is not None else nat.SPP_ELEM_F32, rowptr_dev=_a(rowptr),
+                       col_dev=_a(col), num_targets=T, num_sources=S, num_edges=E, grad_out_dev=_a(g),
+                       grad_out_stride_elems=g.stride(0) if T > 1 else 0, F=Fdim, grad_x_dev=_a(grad_x), z_dev=_a(z),
+                       self_scale=float(scale), p=float(act[0]), training=int(act[1]), seed=int(act[2]) & (2 ** 64 - 1))
+    nat.check(L.spp_agg_backward(C.byref(d), _a(ws), nbytes, st if st is not None else _stream()))
+
+
+def _grad_in(g):
+    """an incoming gradient as the descriptor entries read it: unit column stride, fp32 or bf16"""
+    if g.dtype not in (torch.float32, torch.bfloat16):
+        g = g.float()
+    return g if g.stride(1) == 1 else g.contiguous()
+
+
 class _MeanAggregate(torch.autograd.Function):
     """out[t] = mean_{e in row t} x[col[e]]  (empty rows give 0, as PyG's mean aggregation).
 
@@ -37,13 +95,19 @@ class _MeanAggregate(torch.autograd.Function):
     def forward(ctx, x, rowptr, col, num_targets, concat_target):
         L = nat.load()
         nat.require_device()
-        assert x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and x.dtype in (torch.float16, torch.float32)
+        assert x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and x.dtype in _ELEM
         Fdim = x.size(1)
         width = 2 * Fdim if concat_target else Fdim
-        out = torch.empty((num_targets, width), dtype=torch.float32, device=x.device)
-        fn = L.spp_sage_operand_forward if concat_target else L.spp_csr_mean_forward
-        nat.check(fn(_p(rowptr), _p(col), num_targets, _p(x), int(x.dtype == torch.float16),
-                     x.stride(0) if x.size(0) > 1 else Fdim, Fdim, _p(out), width, _stream()))
+        ctx.amp = amp_bf16()
+        ctx.desc = ctx.amp or x.dtype == torch.bfloat16           # bf16 in or out: the descriptor entry
+        out = torch.empty((num_targets, width), dtype=torch.bfloat16 if ctx.amp else torch.float32, device=x.device)
+        if ctx.desc:
+            _agg_forward(nat.SPP_AGG_OPERAND if concat_target else nat.SPP_AGG_MEAN, rowptr, col, num_targets,
+                         _a(x), x.dtype, Fdim, out, x_stride=x.stride(0) if x.size(0) > 1 else Fdim)
+        else:
+            fn = L.spp_sage_operand_forward if concat_target else L.spp_csr_mean_forward
+            nat.check(fn(_p(rowptr), _p(col), num_targets, _p(x), int(x.dtype == torch.float16),
+                         x.stride(0) if x.size(0) > 1 else Fdim, Fdim, _p(out), width, _stream()))
         ctx.save_for_backward(rowptr, col)
         ctx.shape = (x.size(0), Fdim, num_targets, width)
         ctx.in_dtype = x.dtype
@@ -55,6 +119,21 @@ class _MeanAggregate(torch.autograd.Function):
         rowptr, col = ctx.saved_tensors
         S, Fdim, T, width = ctx.shape
         grad_x = None
+        if ctx.needs_input_grad[0] and ctx.desc:
+            # bf16 / fp32 gradient in, the input's dtype out (fp16 through an fp32 buffer)
+            g = _grad_in(grad_out)
+            odt = ctx.in_dtype if ctx.in_dtype in (torch.float32, torch.bfloat16) else torch.float32
+            grad_x = torch.empty((S, Fdim), dtype=odt, device=g.device)
+            vec = Fdim % 4 == 0 and (T <= 1 or g.stride(0) % 4 == 0) and g.data_ptr() % (4 * g.element_size()) == 0
+            if ctx.concat and vec:
+                _agg_backward(nat.SPP_AGG_OPERAND, rowptr, col, T, S, g, Fdim, grad_x,
+                              gather=col.numel() * Fdim >= (1 << 22))
+            else:
+                _agg_backward(nat.SPP_AGG_MEAN, rowptr, col, T, S, g if not ctx.concat else g[:, :Fdim], Fdim, grad_x,
+                              gather=False)
+                if ctx.concat:
+                    grad_x[:T] += g[:, Fdim:].to(odt)
+            return grad_x.to(ctx.in_dtype), None, None, None, None
         if ctx.needs_input_grad[0]:
             g = grad_out if (grad_out.stride(1) == 1 and grad_out.dtype == torch.float32) else \
                 grad_out.contiguous().to(torch.float32)
@@ -122,16 +201,29 @@ class _TallLinear(torch.autograd.Function):
 
     The weight gradient ``g.T @ a`` is a [N, K] output reduced over T: as one GEMM it has a handful
     of output tiles for 256 CUs (measured 505 us at T=165k, K=200, N=256 -- 27 % of the step).  It is
-    computed as a batched GEMM over row slabs (split-K) and summed instead."""
+    computed as a batched GEMM over row slabs (split-K) and summed instead.
+
+    Under bf16 autocast a and w are used in bf16 (y bf16); the weight gradient comes back in w's dtype (fp32), the input
+    gradient in a's."""
 
     @staticmethod
     def forward(ctx, a, w):
-        ctx.save_for_backward(a, w)
-        return a @ w.t()
+        ctx.amp = amp_bf16()
+        with _no_autocast():
+            if ctx.amp:
+                ctx.dtypes = (a.dtype, w.dtype)
+                a, w = a.to(torch.bfloat16), w.to(torch.bfloat16)
+            ctx.save_for_backward(a, w)
+            return a @ w.t()
 
     @staticmethod
     def backward(ctx, g):
         a, w = ctx.saved_tensors
+        if ctx.amp:
+            g = g.to(torch.bfloat16).contiguous()
+            grad_a = (g @ w).to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None
+            grad_w = _wgrad(g, a).to(ctx.dtypes[1]) if ctx.needs_input_grad[1] else None
+            return grad_a, grad_w
         grad_a = g @ w if ctx.needs_input_grad[0] else None
         grad_w = None
         if ctx.needs_input_grad[1]:
@@ -174,7 +266,8 @@ class SAGEConv(torch.nn.Module):
         if x_target.data_ptr() == x.data_ptr() and x_target.size(1) == x.size(1) and x_target.stride() == x.stride():
             fused = _MeanAggregate.apply(x, rowptr, col, T, True)           # x_target = x[:T] (the MFG contract)
         else:                                                               # a foreign target matrix
-            fused = torch.cat([_MeanAggregate.apply(x, rowptr, col, T, False), x_target.to(torch.float32)], dim=1)
+            mean = _MeanAggregate.apply(x, rowptr, col, T, False)           # (bf16 under bf16 autocast)
+            fused = torch.cat([mean, x_target.to(mean.dtype)], dim=1)
         out = _TallLinear.apply(fused, torch.cat([self.lin_l.weight, self.lin_r.weight], dim=1))
         return out if self.lin_l.bias is None else out + self.lin_l.bias
 
@@ -223,7 +316,12 @@ class SAGE(torch.nn.Module):
 def _wgrad(g, a):
     """g.T @ a for very tall g [T, N], a [T, K]: batched over row slabs and summed (see _TallLinear).  64 slabs of
     >= 2048 rows in the a.T @ g order are what the library runs fastest at T = 164 k, N = K = 256 (162 us against 174-181
-    for 32 slabs and 483 for the single product; tools/gemm_variants.py)"""
+    for 32 slabs and 483 for the single product; tools/gemm_variants.py).
+
+    bf16 g and a (autocast): every slab's product is accumulated in fp32 by the GEMM and rounded to bf16 once, the
+    slabs are summed in fp32, and the result is fp32 (a weight gradient)."""
+    if g.dtype == torch.bfloat16:
+        return _wgrad_bf16(g, a)
     T = a.size(0)
     slabs = min(64, T // 2048)
     if slabs < 2:
@@ -232,6 +330,19 @@ def _wgrad(g, a):
     acc = torch.bmm(a[:slabs * c].view(slabs, c, -1).transpose(1, 2), g[:slabs * c].view(slabs, c, -1)).sum(0)   # [K, N]
     if slabs * c < T:      # the < `slabs` rows left over: accumulated in place (one launch; it was a product + an add)
         acc.addmm_(a[slabs * c:].t(), g[slabs * c:])
+    return acc.t()
+
+
+def _wgrad_bf16(g, a):
+    T = a.size(0)
+    slabs = min(64, T // 2048)
+    if slabs < 2:
+        return (g.t() @ a).float()
+    c = T // slabs
+    acc = torch.bmm(a[:slabs * c].view(slabs, c, -1).transpose(1, 2), g[:slabs * c].view(slabs, c, -1)).sum(
+        0, dtype=torch.float32)                                                                            # [K, N]
+    if slabs * c < T:
+        acc.add_(a[slabs * c:].t() @ g[slabs * c:])
     return acc.t()
 
 
@@ -265,11 +376,11 @@ class _Refs:
 
 
 def _readable(x):
-    """a feature matrix, TableRows or RowRefs the aggregation kernels read in place (fp16 / fp32 rows)"""
+    """a feature matrix, TableRows or RowRefs the aggregation kernels read in place (fp16 / fp32 / bf16 rows)"""
     if isinstance(x, RowRefs):
-        return x.dtype in (torch.float16, torch.float32)
+        return x.dtype in _ELEM
     m = x.table if isinstance(x, TableRows) else x
-    return m.is_cuda and m.dim() == 2 and m.stride(1) == 1 and m.dtype in (torch.float16, torch.float32)
+    return m.is_cuda and m.dim() == 2 and m.stride(1) == 1 and m.dtype in _ELEM
 
 
 class _SageStack(torch.autograd.Function):
@@ -294,6 +405,14 @@ class _SageStack(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, hops, training, p, *weights):
+        ctx.amp = amp_bf16()
+        if ctx.amp:
+            return _SageStack._forward_bf16(ctx, x, hops, training, p, *weights)
+        with _no_autocast():
+            return _SageStack._forward(ctx, x, hops, training, p, *weights)
+
+    @staticmethod
+    def _forward(ctx, x, hops, training, p, *weights):
         L = nat.load()
         nat.require_device()
         n_layers = len(hops)
@@ -344,8 +463,60 @@ class _SageStack(torch.autograd.Function):
         return out
 
     @staticmethod
+    def _forward_bf16(ctx, x, hops, training, p, *weights):
+        """the same stack under bf16 autocast: bf16 operands A [T, 2K], bf16 [W_l | W_r] (cast once per layer), bf16
+        pre-activations Z, activation on load from the bf16 Z; log_softmax in fp32"""
+        nat.require_device()
+        st = _stream()
+        n_layers = len(hops)
+        n_id = refs = None
+        if isinstance(x, tuple):
+            x, n_id = x
+        elif isinstance(x, _Refs):
+            refs = x.r
+            x = refs.addr
+        h = x
+        operands, acts, wcats, seeds = [], [], [], []
+        with _no_autocast():
+            for i, (rowptr, col, T) in enumerate(hops):
+                K = refs.width if (i == 0 and refs is not None) else h.size(1)
+                A = torch.empty((T, 2 * K), dtype=torch.bfloat16, device=x.device)
+                if i == 0 and refs is not None:
+                    _agg_forward(nat.SPP_AGG_OPERAND, rowptr, col, T, None, refs.dtype, K, A, source=nat.SPP_AGG_ROWS,
+                                 n_id=refs.addr, st=st)
+                elif i == 0 and n_id is not None:
+                    _agg_forward(nat.SPP_AGG_OPERAND, rowptr, col, T, _a(h), h.dtype, K, A, source=nat.SPP_AGG_TABLE,
+                                 x_stride=h.stride(0) if h.size(0) > 1 else K, n_id=n_id, x_rows=h.size(0), st=st)
+                elif i == 0:
+                    _agg_forward(nat.SPP_AGG_OPERAND, rowptr, col, T, _a(h), h.dtype, K, A,
+                                 x_stride=h.stride(0) if h.size(0) > 1 else K, st=st)
+                else:
+                    _agg_forward(nat.SPP_AGG_OPERAND_ACT, rowptr, col, T, _a(h), h.dtype, K, A, x_stride=K,
+                                 act=(p, bool(training), seeds[i - 1]), st=st)
+                wl, wr = weights[2 * i], weights[2 * i + 1]
+                W = torch.empty((wl.size(0), 2 * K), dtype=torch.bfloat16, device=x.device)
+                torch.cat([wl, wr], dim=1, out=W)                                  # [N, 2K], cast in the one copy
+                Z = _tall_linear(A, W)                                                            # bf16, fp32 accumulation
+                operands.append(A)
+                wcats.append(W)
+                if i != n_layers - 1:
+                    seeds.append(int(torch.empty((), dtype=torch.int64).random_().item()) if training else 0)
+                    acts.append(Z)
+                    h = Z
+                else:
+                    out = torch.log_softmax(Z, dim=-1, dtype=torch.float32)
+        hop_t = [t for (rowptr, col, _T) in hops for t in (rowptr, col)]
+        ctx.save_for_backward(*operands, *acts, *wcats, out, *hop_t)
+        ctx.hop_T = [int(T) for (_r, _c, T) in hops]
+        ctx.act = (float(p), int(bool(training)), seeds)
+        ctx.src_rows = [(x.numel() if refs is not None else x.size(0)) if n_id is None else n_id.numel()] + [a.size(0) for a in acts]
+        return out
+
+    @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_out):
+        if ctx.amp:
+            return _SageStack._backward_bf16(ctx, g_out)
         L = nat.load()
         st = _stream()
         n_layers = len(ctx.hop_T)
@@ -381,6 +552,35 @@ class _SageStack(torch.autograd.Function):
                 nat.check(L.spp_relu_dropout_backward_pre(_p(gH), _p(acts[i - 1]), gH.numel(), p_, training_,
                                                           seeds[i - 1], _p(gH), st))
             gZ = gH
+        return (None, None, None, None, *grads)
+
+    @staticmethod
+    def _backward_bf16(ctx, g_out):
+        st = _stream()
+        n_layers = len(ctx.hop_T)
+        sv = ctx.saved_tensors
+        operands, acts = sv[:n_layers], sv[n_layers:2 * n_layers - 1]
+        wcats, out = sv[2 * n_layers - 1:3 * n_layers - 1], sv[3 * n_layers - 1]
+        hop_t = sv[3 * n_layers:]
+        hops = [(hop_t[2 * i], hop_t[2 * i + 1], ctx.hop_T[i]) for i in range(n_layers)]
+        with _no_autocast():
+            gZ = torch._log_softmax_backward_data(g_out.float().contiguous(), out, -1, torch.float32).to(torch.bfloat16)
+            grads = [None] * (2 * n_layers)
+            for i in range(n_layers - 1, -1, -1):
+                A, W = operands[i], wcats[i]
+                K = A.size(1) // 2
+                gW = _wgrad(gZ, A)                                              # fp32
+                grads[2 * i], grads[2 * i + 1] = _split_wgrad(gW)
+                if i == 0:
+                    break
+                rowptr, col, T = hops[i]
+                S = ctx.src_rows[i]
+                gA = gZ @ W                                                     # [T, 2K] bf16
+                gH = torch.empty((S, K), dtype=torch.bfloat16, device=gA.device)
+                p_, training_, seeds = ctx.act
+                _agg_backward(nat.SPP_AGG_OPERAND_ACT, rowptr, col, T, S, gA, K, gH, gather=col.numel() * K >= (1 << 22),
+                              z=acts[i - 1], act=(p_, training_, seeds[i - 1]), st=st)
+                gZ = gH
         return (None, None, None, None, *grads)
 
 
@@ -448,7 +648,7 @@ class GATConv(torch.nn.Module):
         x, x_target = x_pair
         rowptr, col, _ = adj_t.csr()
         T, K = x_target.size(0), x.size(1)
-        if (x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and x.dtype in (torch.float16, torch.float32) and
+        if (x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and x.dtype in _ELEM and
                 K % 4 == 0 and K <= 1024 and x_target.data_ptr() == x.data_ptr() and x_target.stride() == x.stride()):
             # aggregate the raw rows with the attention weights, project only the T targets (_GatLayer)
             out = _GatLayer.apply(x, self.lin_src.weight, self.att_src.view(-1), self.att_dst.view(-1), rowptr, col, T,
@@ -469,17 +669,26 @@ class _GatLayer(torch.autograd.Function):
         sum_j alpha_ij (W x_j) = W sum_j alpha_ij x_j   -> aggregate raw rows, project the T targets only
 
     The same function as projecting all S source rows first (PyG's order), with S/T times less GEMM work
-    and -- in the first layer -- 128-wide fp16 rows in the gather instead of 256-wide fp32 ones."""
+    and -- in the first layer -- 128-wide fp16 rows in the gather instead of 256-wide fp32 ones.
+
+    x rows fp32, fp16 or bf16 (the kernels' element code); v, the logits, z and the softmax statistics are fp32.  Under
+    bf16 autocast the projection z @ W^T runs in bf16 (bf16 output), and the backward's GEMMs too."""
 
     @staticmethod
     def forward(ctx, x, W, att_src, att_dst, rowptr, col, T, slope):
+        ctx.amp = amp_bf16()
+        with _no_autocast():
+            return _GatLayer._forward(ctx, x, W, att_src, att_dst, rowptr, col, T, slope)
+
+    @staticmethod
+    def _forward(ctx, x, W, att_src, att_dst, rowptr, col, T, slope):
         L = nat.load()
         nat.require_device()
         st = _stream()
         S, K = x.size(0), x.size(1)
-        half = int(x.dtype == torch.float16)
+        half = _ELEM[x.dtype]                                                # the element code (0 / 1 keep their meaning)
         xs = x.stride(0) if S > 1 else K
-        v = torch.stack([att_src, att_dst]).to(torch.float32) @ W            # [2, K]: W^T att_src, W^T att_dst
+        v = torch.stack([att_src, att_dst]).to(torch.float32) @ W.to(torch.float32)   # [2, K]: W^T att_src, W^T att_dst
         a_src = torch.empty(S, dtype=torch.float32, device=x.device)
         a_dst = torch.empty(T, dtype=torch.float32, device=x.device)
         nat.check(L.spp_gat_logits(_p(x), half, xs, S, T, K, _p(v[0]), _p(v[1]), _p(a_src), _p(a_dst), st))
@@ -490,17 +699,29 @@ class _GatLayer(torch.autograd.Function):
                                               float(slope), _p(z), _p(rmax), _p(rsum), st))
         ctx.save_for_backward(x, W, att_src, att_dst, rowptr, col, a_src, a_dst, z, rmax, rsum, v)
         ctx.dims = (S, T, K, half, xs, float(slope))
+        if ctx.amp:
+            return z.to(torch.bfloat16) @ W.to(torch.bfloat16).t()
         return z @ W.t()
 
     @staticmethod
     def backward(ctx, g_out):
+        with _no_autocast():
+            return _GatLayer._backward(ctx, g_out)
+
+    @staticmethod
+    def _backward(ctx, g_out):
         L = nat.load()
         st = _stream()
         x, W, att_src, att_dst, rowptr, col, a_src, a_dst, z, rmax, rsum, v = ctx.saved_tensors
         S, T, K, half, xs, slope = ctx.dims
         g_out = g_out.contiguous()
-        gW = _wgrad(g_out, z)                                                # [N, K]
-        g_z = g_out @ W                                                      # [T, K]
+        if ctx.amp:                                                          # bf16 GEMMs, fp32 results
+            g16 = g_out.to(torch.bfloat16)
+            gW = _wgrad(g16, z.to(torch.bfloat16))                           # [N, K] fp32
+            g_z = (g16 @ W.to(torch.bfloat16)).float()                       # [T, K]
+        else:
+            gW = _wgrad(g_out, z)                                            # [N, K]
+            g_z = g_out @ W                                                  # [T, K]
         want_gx = ctx.needs_input_grad[0]
         E = col.numel()
         gather = want_gx and E * K >= (1 << 22) and K % 4 == 0
@@ -572,8 +793,9 @@ _SUM_GATHER_MIN_WORK = 1 << 22      # E x F from which the input gradient is gat
 class _SumAggregate(torch.autograd.Function):
     """out[t] = s * x[t] + sum_{e in row t} x[col[e]]  (fp32 [T, F]; targets are the first T rows of x).
 
-    ``x`` is a feature matrix (fp16 / fp32, any row stride), a TableRows or a RowRefs: the latter two are read in
-    place (spp_csr_sum_forward_table / _rows) and get no gradient.  With s == 0 the targets' rows are not read."""
+    ``x`` is a feature matrix (fp16 / fp32 / bf16, any row stride), a TableRows or a RowRefs: the latter two are read in
+    place (spp_csr_sum_forward_table / _rows) and get no gradient.  With s == 0 the targets' rows are not read.
+    Under bf16 autocast the result is bf16 (fp32 sums, rounded once)."""
 
     @staticmethod
     def forward(ctx, x, rowptr, col, num_targets, scale):
@@ -581,11 +803,25 @@ class _SumAggregate(torch.autograd.Function):
         nat.require_device()
         st = _stream()
         S, Fdim = x.size(0), x.size(1)
-        assert x.is_cuda and rowptr.is_cuda and col.is_cuda and _readable(x), "fp16 / fp32 rows on the GPU"
+        assert x.is_cuda and rowptr.is_cuda and col.is_cuda and _readable(x), "fp16 / fp32 / bf16 rows on the GPU"
         assert num_targets <= S or scale == 0.0, "the targets are the first rows of the sources"
-        out = torch.empty((num_targets, Fdim), dtype=torch.float32, device=x.device)
+        ctx.amp = amp_bf16()
+        ctx.desc = ctx.amp or x.dtype == torch.bfloat16           # bf16 in or out: the descriptor entry
+        out = torch.empty((num_targets, Fdim), dtype=torch.bfloat16 if ctx.amp else torch.float32, device=x.device)
         half = int(x.dtype == torch.float16)
-        if isinstance(x, TableRows):
+        if ctx.desc:
+            if isinstance(x, TableRows):
+                tb = x.table
+                _agg_forward(nat.SPP_AGG_SUM, rowptr, col, num_targets, _a(tb), tb.dtype, Fdim, out,
+                             source=nat.SPP_AGG_TABLE, x_stride=tb.stride(0) if tb.size(0) > 1 else Fdim, n_id=x.n_id,
+                             x_rows=tb.size(0), scale=scale, st=st)
+            elif isinstance(x, RowRefs):
+                _agg_forward(nat.SPP_AGG_SUM, rowptr, col, num_targets, None, x.dtype, Fdim, out, source=nat.SPP_AGG_ROWS,
+                             n_id=x.addr, scale=scale, st=st)
+            else:
+                _agg_forward(nat.SPP_AGG_SUM, rowptr, col, num_targets, _a(x), x.dtype, Fdim, out,
+                             x_stride=x.stride(0) if S > 1 else Fdim, scale=scale, st=st)
+        elif isinstance(x, TableRows):
             tb = x.table
             nat.check(L.spp_csr_sum_forward_table(_p(rowptr), _p(col), num_targets, _p(tb), half,
                                                   tb.stride(0) if tb.size(0) > 1 else Fdim, tb.size(0), _p(x.n_id), Fdim,
@@ -608,6 +844,13 @@ class _SumAggregate(torch.autograd.Function):
             return None, None, None, None, None
         rowptr, col = ctx.saved_tensors
         S, Fdim, T = ctx.shape
+        if ctx.desc:
+            g = _grad_in(grad_out)
+            odt = ctx.in_dtype if ctx.in_dtype in (torch.float32, torch.bfloat16) else torch.float32
+            grad_x = torch.empty((S, Fdim), dtype=odt, device=g.device)
+            _agg_backward(nat.SPP_AGG_SUM, rowptr, col, T, S, g, Fdim, grad_x,
+                          gather=col.numel() * Fdim >= _SUM_GATHER_MIN_WORK, scale=ctx.scale)
+            return grad_x.to(ctx.in_dtype), None, None, None, None
         L = nat.load()
         g = grad_out if (grad_out.stride(1) == 1 and grad_out.dtype == torch.float32) else \
             grad_out.contiguous().to(torch.float32)
@@ -679,7 +922,8 @@ class GINConv(torch.nn.Module):
         if prefix:                                                          # x_target = x[:T] (the MFG contract)
             h = _SumAggregate.apply(x, rowptr, col, T, self._scale())
         else:                                                               # a foreign target matrix
-            h = _SumAggregate.apply(x, rowptr, col, T, 0.0) + (1 + self.eps) * x_target.to(torch.float32)
+            h = _SumAggregate.apply(x, rowptr, col, T, 0.0)
+            h = h + (1 + self.eps) * x_target.to(h.dtype)
         return self.nn(h)
 
 

@@ -1,7 +1,9 @@
 """One resident batch of the bench workload, N optimisation steps of one of the models (models.get_model_type: SAGE, GAT,
 GIN, SAGEResInception) on it (fwd + bwd + Adam), timed; run under `rocprofv3 --kernel-trace --stats` for the per-kernel
 table.
-usage: model_step_profile.py [sage|gat|gin|sageresinception] [steps=30] [workload=S-papers]"""
+usage: model_step_profile.py [sage|gat|gin|sageresinception] [steps=30] [workload=S-papers] [--amp bf16]
+--amp bf16: the forward and the loss under torch.autocast("cuda", dtype=torch.bfloat16), as a training loop would wrap them."""
+import contextlib
 import os
 import sys
 import time
@@ -15,9 +17,17 @@ from salient_plusplus_amd.fast_trainer.transferers import DevicePrefetcher  # no
 from salient_plusplus_amd.models import get_model_type  # noqa: E402
 from salient_plusplus_amd.synthetic import make_workload  # noqa: E402
 
-arch = sys.argv[1] if len(sys.argv) > 1 else "sage"
-steps = int(sys.argv[2]) if len(sys.argv) > 2 else 30
-wl = make_workload(sys.argv[3] if len(sys.argv) > 3 else "S-papers", seed=1234, device=torch.device("cuda", 0))
+argv = sys.argv[1:]
+amp = None
+if "--amp" in argv:
+    i = argv.index("--amp")
+    amp = argv[i + 1]
+    del argv[i:i + 2]
+    if amp != "bf16":
+        sys.exit(f"--amp {amp}: only bf16 is supported")
+arch = argv[0] if len(argv) > 0 else "sage"
+steps = int(argv[1]) if len(argv) > 1 else 30
+wl = make_workload(argv[2] if len(argv) > 2 else "S-papers", seed=1234, device=torch.device("cuda", 0))
 dev = torch.device("cuda", 0)
 cfg = FastSamplerConfig(
     x_cpu=wl.x, x_gpu=torch.empty(0), y=wl.y.unsqueeze(-1), rowptr=wl.rowptr, col=wl.col, idx=wl.train_idx[:8 * wl.batch_size],
@@ -31,9 +41,14 @@ model = get_model_type(arch)(wl.x.size(1), 256, 47, 3).to(dev)
 opt = torch.optim.Adam(model.parameters(), lr=1e-3, fused=True)    # one multi-tensor launch per step
 
 
+def autocast():
+    return torch.autocast("cuda", dtype=torch.bfloat16) if amp == "bf16" else contextlib.nullcontext()
+
+
 def step():
     opt.zero_grad(set_to_none=True)
-    loss = torch.nn.functional.nll_loss(model(batch.x, batch.adjs), batch.y.reshape(-1))
+    with autocast():
+        loss = torch.nn.functional.nll_loss(model(batch.x, batch.adjs), batch.y.reshape(-1))
     loss.backward()
     opt.step()
     return loss
@@ -47,5 +62,5 @@ for _ in range(steps):
     loss = step()
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / steps
-print(f"MODEL_STEP {arch} {dt * 1e3:.3f} ms/step on a resident batch: {batch.x.size(0)} nodes, "
+print(f"MODEL_STEP {arch}{' amp=' + amp if amp else ''} {dt * 1e3:.3f} ms/step on a resident batch: {batch.x.size(0)} nodes, "
       f"{[int(a.adj_t.nnz()) for a in batch.adjs]} edges, (S, T) {[tuple(int(v) for v in a.size) for a in batch.adjs]}, loss {float(loss):.4f}", flush=True)
