@@ -688,6 +688,56 @@ spp_status spp_gat_aggregate_backward_gather(const int64_t* rowptr_dev, const in
                                              float* grad_x_dev, float* grad_a_src_dev, float* grad_a_dst_dev,
                                              void* workspace_dev, int64_t workspace_bytes, void* stream);
 
+/* Multi-head GATConv (PyG's `heads` = H in {1, 2, 4, 8}) in the same aggregate-then-project form, per head.
+ * W [H*C, K] holds H blocks W_h of C rows; V_src[h,:] = W_h^T att_src[h], V_dst[h,:] = W_h^T att_dst[h]. Layouts,
+ * all fp32 and row-major: V_src, V_dst [H, K]; a_src [S, H]; a_dst [T, H]; z, grad_z [T, H, K]; row_max, row_sum
+ * [T, H]; grad_a_src [S, H]; grad_a_dst [T, H]; grad_x [S, K].  x rows: element code x_elem (0 fp32, 1 fp16, 2 bf16),
+ * K % 4 == 0, K <= 1024, rows aligned to 4 elements, as above.  The per-head arrays, z, grad_z, V and grad_x are
+ * 16-byte aligned.  A head count outside {1, 2, 4, 8}, an unknown x_elem or a bad K returns SPP_ERR_INVALID before
+ * anything is launched (the workspace query returns SPP_ERR_INVALID for a bad head count).  Each source row is read
+ * once per edge for all H heads.
+ *   spp_gat_mh_logits:           a_src[j,h] = x_j . V_src[h] (all S rows), a_dst[i,h] = x_i . V_dst[h] (the first T)
+ *   spp_gat_mh_aggregate_forward: z[i,h,:] = sum_j softmax_j(leaky_relu(a_src[j,h] + a_dst[i,h])) x_j over row i
+ *                                (diagonal entry dropped, self loop added); head h's output is z[:,h,:] @ W_h^T.  Per head
+ *                                the result equals spp_gat_aggregate_forward's on a_src[:,h], a_dst[:,h].
+ *   spp_gat_mh_aggregate_backward: from grad_z: grad_a_src (caller zeroes it), grad_a_dst, and -- when grad_x_dev !=
+ *                                NULL (caller zeroes it) -- grad_x[j,:] += sum_h alpha_ij^h grad_z[i,h,:] (one fp32
+ *                                atomic per column and edge; the rank-1 logit terms are left to the caller).
+ *   spp_gat_mh_aggregate_backward_gather: the same with grad_x [S, K] written COMPLETELY by gather over the transposed
+ *                                hop, including sum_h grad_a_src[s,h] V_src[h] and, for s < T, sum_h grad_a_dst[s,h]
+ *                                V_dst[h].  workspace: spp_gat_mh_aggregate_backward_gather_workspace_bytes bytes.
+ *   spp_gat_mh_logits_backward:  grad_V_src[h,c] = sum_j grad_a_src[j,h] x[j,c], grad_V_dst[h,c] = sum_{i<T}
+ *                                grad_a_dst[i,h] x[i,c]  (both [H, K], zeroed here). */
+spp_status spp_gat_mh_logits(const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t num_sources,
+                             int64_t num_targets, int64_t K, int32_t heads, const float* v_src_dev,
+                             const float* v_dst_dev, float* a_src_dev, float* a_dst_dev, void* stream);
+spp_status spp_gat_mh_logits_backward(const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t num_sources,
+                                      int64_t num_targets, int64_t K, int32_t heads, const float* grad_a_src_dev,
+                                      const float* grad_a_dst_dev, float* grad_v_src_dev, float* grad_v_dst_dev,
+                                      void* stream);
+spp_status spp_gat_mh_aggregate_forward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                                        const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t K,
+                                        int32_t heads, const float* a_src_dev, const float* a_dst_dev,
+                                        float negative_slope, float* z_dev, float* row_max_dev, float* row_sum_dev,
+                                        void* stream);
+spp_status spp_gat_mh_aggregate_backward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                                         const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t K,
+                                         int32_t heads, const float* a_src_dev, const float* a_dst_dev,
+                                         float negative_slope, const float* z_dev, const float* row_max_dev,
+                                         const float* row_sum_dev, const float* grad_z_dev, float* grad_x_dev,
+                                         float* grad_a_src_dev, float* grad_a_dst_dev, void* stream);
+int64_t spp_gat_mh_aggregate_backward_gather_workspace_bytes(int64_t num_targets, int64_t num_sources,
+                                                             int64_t num_edges, int32_t heads);
+spp_status spp_gat_mh_aggregate_backward_gather(const int64_t* rowptr_dev, const int64_t* col_dev,
+                                                int64_t num_targets, int64_t num_sources, int64_t num_edges,
+                                                const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t K,
+                                                int32_t heads, const float* a_src_dev, const float* a_dst_dev,
+                                                float negative_slope, const float* z_dev, const float* row_max_dev,
+                                                const float* row_sum_dev, const float* grad_z_dev,
+                                                const float* v_src_dev, const float* v_dst_dev, float* grad_x_dev,
+                                                float* grad_a_src_dev, float* grad_a_dst_dev, void* workspace_dev,
+                                                int64_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * f3  Sum aggregation of GINConv over one MFG hop (driver/models.py:234-283: GINConv(nn) with PyG's
  *     defaults eps = 0, train_eps = False, aggr='add', on ((x, x_target), adj_t)); fp32 accumulate and output.

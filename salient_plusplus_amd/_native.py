@@ -177,6 +177,14 @@ SIGNATURES = {
     "spp_gat_aggregate_backward_gather_workspace_bytes": (i64, [i64, i64, i64]),
     "spp_gat_aggregate_backward_gather": (C.c_int, [p, p, i64, i64, i64, p, i32, i64, i64, p, p, C.c_float, p, p, p, p,
                                                     p, p, p, p, p, p, i64, p]),
+    "spp_gat_mh_logits": (C.c_int, [p, i32, i64, i64, i64, i64, i32, p, p, p, p, p]),
+    "spp_gat_mh_logits_backward": (C.c_int, [p, i32, i64, i64, i64, i64, i32, p, p, p, p, p]),
+    "spp_gat_mh_aggregate_forward": (C.c_int, [p, p, i64, p, i32, i64, i64, i32, p, p, C.c_float, p, p, p, p]),
+    "spp_gat_mh_aggregate_backward": (C.c_int, [p, p, i64, p, i32, i64, i64, i32, p, p, C.c_float, p, p, p, p, p, p,
+                                                p, p]),
+    "spp_gat_mh_aggregate_backward_gather_workspace_bytes": (i64, [i64, i64, i64, i32]),
+    "spp_gat_mh_aggregate_backward_gather": (C.c_int, [p, p, i64, i64, i64, p, i32, i64, i64, i32, p, p, C.c_float, p,
+                                                       p, p, p, p, p, p, p, p, p, i64, p]),
     "spp_sage_operand_forward_rows": (C.c_int, [p, p, i64, p, i32, i64, p, i64, p]),
     "spp_gather_row_refs": (C.c_int, [p, i64, i64, p, p]),
     "spp_ipc_export": (C.c_int, [p, p, C.POINTER(i64)]),

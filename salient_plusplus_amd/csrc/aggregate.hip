@@ -1177,6 +1177,419 @@ __global__ __launch_bounds__(kAggNT) void k_gat_gx_gather(const int32_t* __restr
   }
 }
 
+// ================================================================================================
+// Multi-head GATConv (heads = H > 1, PyG's `heads`), aggregate-then-project per head.  W [H*C, K] is H blocks W_h of
+// C rows;  v_src^h = W_h^T att_src[h],  v_dst^h = W_h^T att_dst[h]  (V_src, V_dst: [H, K]).  Per head h:
+//   a_src[j,h] = x_j . v_src^h,  a_dst[i,h] = x_i . v_dst^h,  alpha^h = softmax over row i of leaky_relu(a_src + a_dst),
+//   z[i,h,:] = sum_j alpha_ij^h x_j    (RAW rows, K wide)  -> out_i^h = W_h z[i,h,:].
+// Every kernel below walks the edges ONCE for all heads: one load of the row chunk and one load of the H logits per
+// edge, shared by the heads; what grows with H are the registers (H softmax states and accumulators) and z ([T, H, K]).
+// Layouts: a_src [S, H], a_dst [T, H], V [H, K], z and grad_z [T, H, K], row_max / row_sum [T, H], alpha_e [E, H],
+// alpha_self [T, H]; all fp32, row-major.  Per head, the order of operations is the single-head kernels'.
+// ================================================================================================
+// o[h] = p[h], h < H, in 16-byte (H % 4 == 0) or 8-byte (H == 2) loads: p is 4 * H-byte aligned
+template <int H>
+__device__ __forceinline__ void load_heads(const float* p, float (&o)[H]) {
+  if constexpr (H % 4 == 0) {
+#pragma unroll
+    for (int q = 0; q < H; q += 4) {
+      const float4 v = *reinterpret_cast<const float4*>(p + q);
+      o[q] = v.x; o[q + 1] = v.y; o[q + 2] = v.z; o[q + 3] = v.w;
+    }
+  } else if constexpr (H == 2) {
+    const float2 v = *reinterpret_cast<const float2*>(p);
+    o[0] = v.x; o[1] = v.y;
+  } else {
+    o[0] = *p;
+  }
+}
+template <int H>
+__device__ __forceinline__ void store_heads(float* p, const float (&v)[H]) {
+  if constexpr (H % 4 == 0) {
+#pragma unroll
+    for (int q = 0; q < H; q += 4) *reinterpret_cast<float4*>(p + q) = make_float4(v[q], v[q + 1], v[q + 2], v[q + 3]);
+  } else if constexpr (H == 2) {
+    *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
+  } else {
+    p[0] = v[0];
+  }
+}
+
+// k_rowdot2 with 2H dot products per row; H = 8 takes half as many rows per group (2H accumulators per row)
+template <int H>
+constexpr int mh_dot_rows() { return H <= 4 ? kDotRows : kDotRows / 2; }
+template <typename Tin, int H>
+__global__ __launch_bounds__(kAggNT) void k_gat_mh_rowdot(const Tin* __restrict__ x, int64_t x_stride, int64_t S, int64_t T,
+                                                          int64_t K, const float* __restrict__ v_src,
+                                                          const float* __restrict__ v_dst, int lpr_log2,
+                                                          float* __restrict__ a_src, float* __restrict__ a_dst) {
+  constexpr int R = mh_dot_rows<H>();
+  const int lpr = 1 << lpr_log2;
+  const int lane = threadIdx.x & (lpr - 1);
+  const int64_t j0 = (((int64_t)blockIdx.x * kAggNT + threadIdx.x) >> lpr_log2) * R;
+  if (j0 >= S) return;  // whole groups leave together
+  float ds[R][H], dd[R][H];
+#pragma unroll
+  for (int u = 0; u < R; ++u)
+#pragma unroll
+    for (int h = 0; h < H; ++h) ds[u][h] = dd[u][h] = 0.f;
+  for (int64_t c = (int64_t)lane * 4; c < K; c += (int64_t)lpr * 4) {
+    f4 xv[R];
+#pragma unroll
+    for (int u = 0; u < R; ++u) {  // clamped, unpredicated: all R loads in flight (k_rowdot2)
+      const int64_t j = j0 + u < S ? j0 + u : S - 1;
+      xv[u] = load4(x + j * x_stride + c);
+    }
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+      const f4 vs = load4v(v_src + h * K + c), vd = load4v(v_dst + h * K + c);
+#pragma unroll
+      for (int u = 0; u < R; ++u) {
+        ds[u][h] += xv[u].x * vs.x + xv[u].y * vs.y + xv[u].z * vs.z + xv[u].w * vs.w;
+        dd[u][h] += xv[u].x * vd.x + xv[u].y * vd.y + xv[u].z * vd.z + xv[u].w * vd.w;
+      }
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < R; ++u)
+#pragma unroll
+    for (int h = 0; h < H; ++h)
+      for (int d = lpr >> 1; d >= 1; d >>= 1) {
+        ds[u][h] += __shfl_xor(ds[u][h], d, kWave);
+        dd[u][h] += __shfl_xor(dd[u][h], d, kWave);
+      }
+  if (lane == 0) {
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+      const int64_t j = j0 + u;
+      if (j < S) {
+        store_heads<H>(a_src + j * H, ds[u]);
+        if (j < T) store_heads<H>(a_dst + j * H, dd[u]);
+      }
+    }
+  }
+}
+
+// k_colsum2 for H heads: out_src[h,c] += sum_j w_src[j,h] x[j,c];  out_dst[h,c] += sum_{j<T} w_dst[j,h] x[j,c]
+// (out zeroed by the caller).  The 2H column sums of a workgroup leave through one LDS buffer, one after the other.
+template <typename Tin, int H>
+__global__ __launch_bounds__(kColsumNT) void k_gat_mh_colsum(const Tin* __restrict__ x, int64_t x_stride, int64_t S,
+                                                             int64_t T, int64_t K, const float* __restrict__ w_src,
+                                                             const float* __restrict__ w_dst, int64_t rows_per_wg,
+                                                             float* __restrict__ out_src, float* __restrict__ out_dst) {
+  __shared__ float red[kColsumNT][4];
+  constexpr int kU = H <= 2 ? 4 : 2;            // independent rows in flight
+  const int groups = (int)(K / 4);
+  const int cg = threadIdx.x % groups;
+  const int rsub = threadIdx.x / groups, rstep = kColsumNT / groups;
+  const int64_t r0 = (int64_t)blockIdx.x * rows_per_wg;
+  const int64_t r1 = r0 + rows_per_wg < S ? r0 + rows_per_wg : S;
+  f4 as[H], ad[H];
+#pragma unroll
+  for (int h = 0; h < H; ++h) as[h] = ad[h] = f4{0.f, 0.f, 0.f, 0.f};
+  auto add = [](f4& a, float w, const f4& v) { a.x += w * v.x; a.y += w * v.y; a.z += w * v.z; a.w += w * v.w; };
+  if (rsub < rstep) {
+    int64_t j = r0 + rsub;
+    const int64_t tlast = T > 0 ? T - 1 : 0;
+    const float* __restrict__ wdp = T > 0 ? w_dst : w_src;  // (w_dst may be NULL without targets)
+    for (; j + (kU - 1) * rstep < r1; j += kU * rstep) {
+      f4 xv[kU];
+      float ws[kU][H], wd[kU][H];
+#pragma unroll
+      for (int u = 0; u < kU; ++u) {
+        const int64_t ju = j + u * rstep;
+        xv[u] = load4(x + ju * x_stride + (int64_t)cg * 4);
+        load_heads<H>(w_src + ju * H, ws[u]);
+        load_heads<H>(wdp + (ju < T ? ju : tlast) * H, wd[u]);
+        if (ju >= T)
+#pragma unroll
+          for (int h = 0; h < H; ++h) wd[u][h] = 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < kU; ++u)
+#pragma unroll
+        for (int h = 0; h < H; ++h) {
+          add(as[h], ws[u][h], xv[u]);
+          add(ad[h], wd[u][h], xv[u]);
+        }
+    }
+    for (; j < r1; j += rstep) {
+      const f4 xv = load4(x + j * x_stride + (int64_t)cg * 4);
+      float ws[H];
+      load_heads<H>(w_src + j * H, ws);
+#pragma unroll
+      for (int h = 0; h < H; ++h) add(as[h], ws[h], xv);
+      if (j < T) {
+        float wd[H];
+        load_heads<H>(w_dst + j * H, wd);
+#pragma unroll
+        for (int h = 0; h < H; ++h) add(ad[h], wd[h], xv);
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 0; o < 2 * H; ++o) {
+    const f4 v = o < H ? as[o] : ad[o - H];
+    red[threadIdx.x][0] = v.x; red[threadIdx.x][1] = v.y; red[threadIdx.x][2] = v.z; red[threadIdx.x][3] = v.w;
+    __syncthreads();
+    if (threadIdx.x < groups && (o < H || r0 < T)) {
+      float s4[4] = {0.f, 0.f, 0.f, 0.f};
+      for (int r = 0; r < rstep; ++r)
+        for (int q = 0; q < 4; ++q) s4[q] += red[r * groups + threadIdx.x][q];
+      float* out = o < H ? out_src + o * K : out_dst + (o - H) * K;
+      for (int q = 0; q < 4; ++q) unsafeAtomicAdd(out + threadIdx.x * 4 + q, s4[q]);
+    }
+    __syncthreads();
+  }
+}
+
+// k_gat_agg_fwd for H heads: the same lanes, kNb edge batches and online softmax, with H softmax states and
+// accumulators; per edge one load of the H logits and one of the row chunk, shared by the heads
+template <typename Tin, int H>
+__global__ __launch_bounds__(kAggNT) void k_gat_mh_agg_fwd(const int64_t* __restrict__ rowptr,
+                                                           const int64_t* __restrict__ col, int64_t T,
+                                                           const Tin* __restrict__ x, int64_t x_stride, int64_t K,
+                                                           const float* __restrict__ a_src,
+                                                           const float* __restrict__ a_dst, float slope, int lpr_log2,
+                                                           float* __restrict__ z, float* __restrict__ row_max,
+                                                           float* __restrict__ row_sum) {
+  const int lpr = 1 << lpr_log2;
+  const int lane = threadIdx.x & (lpr - 1);
+  const int64_t t = ((int64_t)blockIdx.x * kAggNT + threadIdx.x) >> lpr_log2;
+  if (t >= T) return;
+  const int64_t b = rowptr[t], e = rowptr[t + 1];
+  float ad[H], self[H];
+  load_heads<H>(a_dst + t * H, ad);
+  load_heads<H>(a_src + t * H, self);
+#pragma unroll
+  for (int h = 0; h < H; ++h) self[h] = lrelu(self[h] + ad[h], slope);
+  for (int64_t c = (int64_t)lane * 4; c < K || c == (int64_t)lane * 4; c += (int64_t)lpr * 4) {
+    const bool has = c < K;
+    const f4 xt = has ? load4(x + t * x_stride + c) : f4{0.f, 0.f, 0.f, 0.f};
+    f4 acc[H];
+    float mm[H], ss[H];
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+      acc[h] = xt;
+      mm[h] = self[h];
+      ss[h] = 1.f;
+    }
+    constexpr int kNb = 4;
+    const int64_t cc = has ? c : 0;
+    for (int64_t k0 = b; k0 < e; k0 += kNb) {
+      int64_t j[kNb];
+#pragma unroll
+      for (int u = 0; u < kNb; ++u) j[u] = col[k0 + u < e ? k0 + u : e - 1];
+      float as[kNb][H];
+      f4 xv[kNb];
+#pragma unroll
+      for (int u = 0; u < kNb; ++u) {
+        load_heads<H>(a_src + j[u] * H, as[u]);
+        xv[u] = load4(x + j[u] * x_stride + cc);
+      }
+#pragma unroll
+      for (int u = 0; u < kNb; ++u) {
+        if (k0 + u >= e || j[u] == t) continue;  // set_diag drops existing diagonal entries
+#pragma unroll
+        for (int h = 0; h < H; ++h) {
+          const float sc = lrelu(as[u][h] + ad[h], slope);
+          if (sc > mm[h]) {
+            const float r = __expf(mm[h] - sc);
+            acc[h].x *= r; acc[h].y *= r; acc[h].z *= r; acc[h].w *= r;
+            ss[h] *= r;
+            mm[h] = sc;
+          }
+          const float w = __expf(sc - mm[h]);
+          ss[h] += w;
+          acc[h].x += w * xv[u].x; acc[h].y += w * xv[u].y; acc[h].z += w * xv[u].z; acc[h].w += w * xv[u].w;
+        }
+      }
+    }
+    if (has) {
+#pragma unroll
+      for (int h = 0; h < H; ++h) {
+        const float inv = 1.f / ss[h];
+        *reinterpret_cast<float4*>(z + (t * H + h) * K + c) =
+            make_float4(acc[h].x * inv, acc[h].y * inv, acc[h].z * inv, acc[h].w * inv);
+      }
+    }
+    if (lane == 0 && c == 0) {
+      store_heads<H>(row_max + t * H, mm);
+      store_heads<H>(row_sum + t * H, ss);
+    }
+  }
+}
+
+// k_gat_agg_bwd for H heads: per head  go^h = g_i^h . z_i^h,  gh^h = g_i^h . x_j,  ge^h = alpha^h (gh^h - go^h) lrelu';
+// grad_a_src[j,h] += ge^h, grad_a_dst[i,h] = sum_j ge^h, and (grad_x != NULL) grad_x[j,:] += sum_h alpha_ij^h g_i^h:
+// the heads are summed first, so there is ONE fp32 atomic per column per edge whatever H is
+template <typename Tin, int H, bool kVec>
+__global__ __launch_bounds__(kAggNT) void k_gat_mh_agg_bwd(
+    const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col, int64_t T, const Tin* __restrict__ x,
+    int64_t x_stride, int64_t K, const float* __restrict__ a_src, const float* __restrict__ a_dst, float slope,
+    const float* __restrict__ z, const float* __restrict__ row_max, const float* __restrict__ row_sum,
+    const float* __restrict__ g, int lpt_log2, float* __restrict__ grad_x, float* __restrict__ grad_a_src,
+    float* __restrict__ grad_a_dst, float* __restrict__ alpha_e, float* __restrict__ alpha_self) {
+  const int lpt = 1 << lpt_log2;
+  const int lane = threadIdx.x & (lpt - 1);
+  const int64_t t = ((int64_t)blockIdx.x * kAggNT + threadIdx.x) >> lpt_log2;
+  const bool live = t < T;
+  const int64_t b = live ? rowptr[t] : 0, e = live ? rowptr[t + 1] : -1;
+  float ad[H], m[H], inv_s[H];
+#pragma unroll
+  for (int h = 0; h < H; ++h) ad[h] = m[h] = inv_s[h] = 0.f;
+  if (live) {
+    load_heads<H>(a_dst + t * H, ad);
+    load_heads<H>(row_max + t * H, m);
+    load_heads<H>(row_sum + t * H, inv_s);
+#pragma unroll
+    for (int h = 0; h < H; ++h) inv_s[h] = 1.f / inv_s[h];
+  }
+  auto group_sum = [&](float v) {
+    for (int d = lpt >> 1; d >= 1; d >>= 1) v += __shfl_xor(v, d, kWave);
+    return v;
+  };
+  const float* __restrict__ gt = g + (live ? t : 0) * H * K;  // target t's [H, K] block of grad_z (and of z)
+  const float* __restrict__ zt = z + (live ? t : 0) * H * K;
+  float go[H];
+#pragma unroll
+  for (int h = 0; h < H; ++h) {
+    go[h] = 0.f;
+    if (live) {
+      if (kVec) {
+        for (int64_t c = (int64_t)lane * 4; c < K; c += (int64_t)lpt * 4) {
+          const f4 gv = load4(gt + h * K + c), zv = load4(zt + h * K + c);
+          go[h] += gv.x * zv.x + gv.y * zv.y + gv.z * zv.z + gv.w * zv.w;
+        }
+      } else {
+        for (int64_t c = lane; c < K; c += lpt) go[h] += gt[h * K + c] * zt[h * K + c];
+      }
+    }
+    go[h] = group_sum(go[h]);
+  }
+  // every group runs to the longest row of its wavefront so that the shuffles stay convergent
+  int64_t n = live ? e - b + 1 : 0;
+  for (int d = lpt; d < kWave; d <<= 1) {
+    const int64_t o = __shfl_xor((long long)n, d, kWave);
+    n = o > n ? o : n;
+  }
+  float gad[H];
+#pragma unroll
+  for (int h = 0; h < H; ++h) gad[h] = 0.f;
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t k = b - 1 + i;  // k == b-1 stands for the self loop
+    const bool on = live && k < e;
+    const int64_t j = !on ? 0 : ((k < b) ? t : col[k]);
+    const bool use = on && !(k >= b && j == t);  // set_diag drops existing diagonal entries
+    float gh[H], a[H], raw[H];
+#pragma unroll
+    for (int h = 0; h < H; ++h) gh[h] = a[h] = raw[h] = 0.f;
+    if (use) {
+      load_heads<H>(a_src + j * H, raw);
+#pragma unroll
+      for (int h = 0; h < H; ++h) {
+        raw[h] += ad[h];
+        a[h] = __expf(lrelu(raw[h], slope) - m[h]) * inv_s[h];
+      }
+      if (kVec) {
+        for (int64_t c = (int64_t)lane * 4; c < K; c += (int64_t)lpt * 4) {
+          const f4 xv = load4(x + j * x_stride + c);
+#pragma unroll
+          for (int h = 0; h < H; ++h) {
+            const f4 gv = load4(gt + h * K + c);
+            gh[h] += gv.x * xv.x + gv.y * xv.y + gv.z * xv.z + gv.w * xv.w;
+          }
+        }
+      } else {
+        for (int64_t c = lane; c < K; c += lpt) {
+          const float xv = load1(x + j * x_stride + c);
+          float gx = 0.f;
+#pragma unroll
+          for (int h = 0; h < H; ++h) {
+            const float gv = gt[h * K + c];
+            gh[h] += gv * xv;
+            gx += a[h] * gv;
+          }
+          unsafeAtomicAdd(grad_x + j * K + c, gx);
+        }
+      }
+    }
+#pragma unroll
+    for (int h = 0; h < H; ++h) gh[h] = group_sum(gh[h]);
+    if (alpha_e && on && lane == 0) store_heads<H>(k < b ? alpha_self + t * H : alpha_e + k * H, a);  // 0: dropped entry
+    if (use) {
+#pragma unroll
+      for (int h = 0; h < H; ++h) {
+        const float ge = a[h] * (gh[h] - go[h]) * (raw[h] > 0.f ? 1.f : slope);
+        gad[h] += ge;
+        if (lane == 0) unsafeAtomicAdd(grad_a_src + j * H + h, ge);
+      }
+    }
+  }
+  if (live && lane == 0) store_heads<H>(grad_a_dst + t * H, gad);
+}
+
+// k_gat_gx_gather for H heads:  grad_x[s,:] = sum over the targets t of s: sum_h alpha_ts^h grad_z[t,h,:]
+//   (+ the self loop's sum_h alpha_ss^h grad_z[s,h,:], s < T) + sum_h grad_a_src[s,h] v_src^h (+ grad_a_dst[s,h] v_dst^h, s < T)
+template <int H>
+__global__ __launch_bounds__(kAggNT) void k_gat_mh_gx_gather(
+    const int32_t* __restrict__ start, const int32_t* __restrict__ ttgt, const int32_t* __restrict__ tedge,
+    const float* __restrict__ alpha_e, const float* __restrict__ alpha_self, int64_t T, int64_t S,
+    const float* __restrict__ g, int64_t K, int lpr_log2, const float* __restrict__ grad_a_src,
+    const float* __restrict__ grad_a_dst, const float* __restrict__ v_src, const float* __restrict__ v_dst,
+    float* __restrict__ grad_x) {
+  const int lpr = 1 << lpr_log2;
+  const int lane = threadIdx.x & (lpr - 1);
+  const int64_t srow = ((int64_t)blockIdx.x * kAggNT + threadIdx.x) >> lpr_log2;
+  if (srow >= S) return;
+  const int32_t b = start[srow], e = start[srow + 1];
+  const bool tgt = srow < T;
+  float gas[H], gad[H], aself[H];
+  load_heads<H>(grad_a_src + srow * H, gas);
+#pragma unroll
+  for (int h = 0; h < H; ++h) gad[h] = aself[h] = 0.f;
+  if (tgt) {
+    load_heads<H>(grad_a_dst + srow * H, gad);
+    load_heads<H>(alpha_self + srow * H, aself);
+  }
+  auto add = [](float4& a, float w, const float4& v) { a.x += w * v.x; a.y += w * v.y; a.z += w * v.z; a.w += w * v.w; };
+  const int64_t HK = H * K;
+  for (int64_t c = (int64_t)lane * 4; c < K; c += (int64_t)lpr * 4) {
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int h = 0; h < H; ++h) add(acc, gas[h], *reinterpret_cast<const float4*>(v_src + h * K + c));
+    if (tgt) {
+#pragma unroll
+      for (int h = 0; h < H; ++h) {
+        add(acc, gad[h], *reinterpret_cast<const float4*>(v_dst + h * K + c));
+        add(acc, aself[h], *reinterpret_cast<const float4*>(g + srow * HK + h * K + c));
+      }
+    }
+    int32_t k = b;
+    for (; k + 1 < e; k += 2) {  // two independent targets in flight
+      const int32_t t0 = ttgt[k], t1 = ttgt[k + 1];
+      float w0[H], w1[H];
+      load_heads<H>(alpha_e + (int64_t)tedge[k] * H, w0);
+      load_heads<H>(alpha_e + (int64_t)tedge[k + 1] * H, w1);
+#pragma unroll
+      for (int h = 0; h < H; ++h) {
+        const float4 v0 = *reinterpret_cast<const float4*>(g + (int64_t)t0 * HK + h * K + c);
+        const float4 v1 = *reinterpret_cast<const float4*>(g + (int64_t)t1 * HK + h * K + c);
+        add(acc, w0[h], v0);
+        add(acc, w1[h], v1);
+      }
+    }
+    if (k < e) {
+      const int32_t t0 = ttgt[k];
+      float w0[H];
+      load_heads<H>(alpha_e + (int64_t)tedge[k] * H, w0);
+#pragma unroll
+      for (int h = 0; h < H; ++h) add(acc, w0[h], *reinterpret_cast<const float4*>(g + (int64_t)t0 * HK + h * K + c));
+    }
+    *reinterpret_cast<float4*>(grad_x + srow * K + c) = acc;
+  }
+}
+
 }  // namespace spp
 
 // x_elem: the element code of x's rows (0 fp32, 1 fp16, 2 bf16); the softmax statistics, z and all gradients stay fp32
@@ -1384,6 +1797,207 @@ extern "C" spp_status spp_gat_backward(const int64_t* rowptr_dev, const int64_t*
   hipLaunchKernelGGL(k_gat_bwd, dim3(grid), dim3(kAggNT), 0, as_stream(stream), rowptr_dev, col_dev, num_targets, h_dev,
                      F, a_src_dev, a_dst_dev, negative_slope, out_dev, row_max_dev, row_sum_dev, grad_out_dev,
                      grad_h_dev, grad_a_src_dev, grad_a_dst_dev);
+  SPP_HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
+
+// ---- multi-head GAT entries (include/spp.h: spp_gat_mh_*) ----
+// fn(std::integral_constant<int, H>{}) for heads = H in {1, 2, 4, 8} (checked by mh_check)
+template <class Fn>
+static void with_heads(int32_t heads, Fn&& fn) {
+  switch (heads) {
+    case 1: fn(std::integral_constant<int, 1>{}); break;
+    case 2: fn(std::integral_constant<int, 2>{}); break;
+    case 4: fn(std::integral_constant<int, 4>{}); break;
+    default: fn(std::integral_constant<int, 8>{}); break;
+  }
+}
+// the checks of gat_check plus the head count; every entry runs them before anything else
+static spp_status mh_check(int32_t heads, int64_t K, const void* x, int64_t x_stride, int32_t x_elem, const char* who) {
+  SPP_REQUIRE(heads == 1 || heads == 2 || heads == 4 || heads == 8, "%s: heads must be 1, 2, 4 or 8 (got %d)", who,
+              (int)heads);
+  return gat_check(K, x, x_stride, x_elem, who);
+}
+// the per-head arrays are read and written H floats at a time (16-byte loads at H = 4, 8)
+static bool al16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+
+extern "C" spp_status spp_gat_mh_logits(const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t num_sources,
+                                        int64_t num_targets, int64_t K, int32_t heads, const float* v_src_dev,
+                                        const float* v_dst_dev, float* a_src_dev, float* a_dst_dev, void* stream) {
+  SPP_TRY(mh_check(heads, K, x_dev, x_stride_elems, x_elem, "spp_gat_mh_logits"));
+  SPP_REQUIRE(num_sources >= num_targets && num_targets >= 0, "spp_gat_mh_logits: bad sizes");
+  if (num_sources == 0) return SPP_OK;
+  SPP_REQUIRE(x_dev && v_src_dev && v_dst_dev && a_src_dev && (a_dst_dev || num_targets == 0) && al16(v_src_dev) &&
+                  al16(v_dst_dev) && al16(a_src_dev) && al16(a_dst_dev),
+              "spp_gat_mh_logits: NULL or unaligned buffer");
+  const int lpr_log2 = lanes_log2(K / 4);
+  with_elem(x_elem, [&](auto tin) {
+    with_heads(heads, [&](auto hh) {
+      using Tin = typename decltype(tin)::type;
+      constexpr int H = decltype(hh)::value;
+      const unsigned grid = (unsigned)ceil_div(ceil_div(num_sources, mh_dot_rows<H>()) << lpr_log2, kAggNT);
+      hipLaunchKernelGGL((k_gat_mh_rowdot<Tin, H>), dim3(grid), dim3(kAggNT), 0, as_stream(stream),
+                         static_cast<const Tin*>(x_dev), x_stride_elems, num_sources, num_targets, K, v_src_dev, v_dst_dev,
+                         lpr_log2, a_src_dev, a_dst_dev);
+    });
+  });
+  SPP_HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
+
+extern "C" spp_status spp_gat_mh_logits_backward(const void* x_dev, int32_t x_elem, int64_t x_stride_elems,
+                                                 int64_t num_sources, int64_t num_targets, int64_t K, int32_t heads,
+                                                 const float* grad_a_src_dev, const float* grad_a_dst_dev,
+                                                 float* grad_v_src_dev, float* grad_v_dst_dev, void* stream) {
+  SPP_TRY(mh_check(heads, K, x_dev, x_stride_elems, x_elem, "spp_gat_mh_logits_backward"));
+  SPP_REQUIRE(num_sources >= num_targets && num_targets >= 0, "spp_gat_mh_logits_backward: bad sizes");
+  SPP_REQUIRE(grad_v_src_dev && grad_v_dst_dev, "spp_gat_mh_logits_backward: NULL output");
+  SPP_REQUIRE(num_sources == 0 || (x_dev && grad_a_src_dev && (grad_a_dst_dev || num_targets == 0) &&
+                                   al16(grad_a_src_dev) && al16(grad_a_dst_dev)),
+              "spp_gat_mh_logits_backward: NULL or unaligned input");
+  hipStream_t st = as_stream(stream);
+  SPP_HIP_TRY(hipMemsetAsync(grad_v_src_dev, 0, sizeof(float) * (size_t)(heads * K), st));
+  SPP_HIP_TRY(hipMemsetAsync(grad_v_dst_dev, 0, sizeof(float) * (size_t)(heads * K), st));
+  if (num_sources == 0) return SPP_OK;
+  const int64_t rows_per_wg = std::max<int64_t>(1024, std::min<int64_t>(4096, ceil_div(num_sources, 256)));
+  const unsigned grid = (unsigned)ceil_div(num_sources, rows_per_wg);
+  with_elem(x_elem, [&](auto tin) {
+    with_heads(heads, [&](auto hh) {
+      using Tin = typename decltype(tin)::type;
+      hipLaunchKernelGGL((k_gat_mh_colsum<Tin, decltype(hh)::value>), dim3(grid), dim3(kColsumNT), 0, st,
+                         static_cast<const Tin*>(x_dev), x_stride_elems, num_sources, num_targets, K, grad_a_src_dev,
+                         grad_a_dst_dev, rows_per_wg, grad_v_src_dev, grad_v_dst_dev);
+    });
+  });
+  SPP_HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
+
+extern "C" spp_status spp_gat_mh_aggregate_forward(const int64_t* rowptr_dev, const int64_t* col_dev,
+                                                   int64_t num_targets, const void* x_dev, int32_t x_elem,
+                                                   int64_t x_stride_elems, int64_t K, int32_t heads,
+                                                   const float* a_src_dev, const float* a_dst_dev, float negative_slope,
+                                                   float* z_dev, float* row_max_dev, float* row_sum_dev, void* stream) {
+  SPP_TRY(mh_check(heads, K, x_dev, x_stride_elems, x_elem, "spp_gat_mh_aggregate_forward"));
+  SPP_REQUIRE(num_targets >= 0, "spp_gat_mh_aggregate_forward: negative size");
+  if (num_targets == 0) return SPP_OK;
+  SPP_REQUIRE(rowptr_dev && x_dev && a_src_dev && a_dst_dev && z_dev && row_max_dev && row_sum_dev && al16(z_dev) &&
+                  al16(a_src_dev) && al16(a_dst_dev) && al16(row_max_dev) && al16(row_sum_dev),
+              "spp_gat_mh_aggregate_forward: NULL or unaligned buffer");
+  const int lpr_log2 = lanes_log2(K / 4);
+  const unsigned grid = (unsigned)ceil_div(num_targets << lpr_log2, kAggNT);
+  with_elem(x_elem, [&](auto tin) {
+    with_heads(heads, [&](auto hh) {
+      using Tin = typename decltype(tin)::type;
+      hipLaunchKernelGGL((k_gat_mh_agg_fwd<Tin, decltype(hh)::value>), dim3(grid), dim3(kAggNT), 0, as_stream(stream),
+                         rowptr_dev, col_dev, num_targets, static_cast<const Tin*>(x_dev), x_stride_elems, K, a_src_dev,
+                         a_dst_dev, negative_slope, lpr_log2, z_dev, row_max_dev, row_sum_dev);
+    });
+  });
+  SPP_HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
+
+// the launch of k_gat_mh_agg_bwd (arguments checked by the caller); grad_x_dev == NULL: the vector form
+static spp_status gat_mh_backward_launch(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                                         const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t K,
+                                         int32_t heads, const float* a_src_dev, const float* a_dst_dev,
+                                         float negative_slope, const float* z_dev, const float* row_max_dev,
+                                         const float* row_sum_dev, const float* grad_z_dev, float* grad_x_dev,
+                                         float* grad_a_src_dev, float* grad_a_dst_dev, float* alpha_e,
+                                         float* alpha_self, void* stream) {
+  const bool vec = grad_x_dev == nullptr;
+  const int lpt_log2 = lanes_log2(vec ? K / 4 : K);
+  const unsigned grid = (unsigned)ceil_div(num_targets << lpt_log2, kAggNT);
+  with_elem_vec(x_elem, vec, [&](auto tin, auto v) {
+    with_heads(heads, [&](auto hh) {
+      using Tin = typename decltype(tin)::type;
+      hipLaunchKernelGGL((k_gat_mh_agg_bwd<Tin, decltype(hh)::value, decltype(v)::value>), dim3(grid), dim3(kAggNT), 0,
+                         as_stream(stream), rowptr_dev, col_dev, num_targets, static_cast<const Tin*>(x_dev),
+                         x_stride_elems, K, a_src_dev, a_dst_dev, negative_slope, z_dev, row_max_dev, row_sum_dev,
+                         grad_z_dev, lpt_log2, grad_x_dev, grad_a_src_dev, grad_a_dst_dev, alpha_e, alpha_self);
+    });
+  });
+  SPP_HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
+
+static bool gat_mh_backward_bufs_ok(const int64_t* rowptr_dev, const void* x_dev, const float* a_src_dev,
+                                    const float* a_dst_dev, const float* z_dev, const float* row_max_dev,
+                                    const float* row_sum_dev, const float* grad_z_dev, const float* grad_a_src_dev,
+                                    const float* grad_a_dst_dev) {
+  return rowptr_dev && x_dev && a_src_dev && a_dst_dev && z_dev && row_max_dev && row_sum_dev && grad_z_dev &&
+         grad_a_src_dev && grad_a_dst_dev && al16(a_src_dev) && al16(a_dst_dev) && al16(z_dev) && al16(row_max_dev) &&
+         al16(row_sum_dev) && al16(grad_z_dev) && al16(grad_a_src_dev) && al16(grad_a_dst_dev);
+}
+
+extern "C" spp_status spp_gat_mh_aggregate_backward(const int64_t* rowptr_dev, const int64_t* col_dev,
+                                                    int64_t num_targets, const void* x_dev, int32_t x_elem,
+                                                    int64_t x_stride_elems, int64_t K, int32_t heads,
+                                                    const float* a_src_dev, const float* a_dst_dev,
+                                                    float negative_slope, const float* z_dev, const float* row_max_dev,
+                                                    const float* row_sum_dev, const float* grad_z_dev,
+                                                    float* grad_x_dev /* NULL: not wanted */, float* grad_a_src_dev,
+                                                    float* grad_a_dst_dev, void* stream) {
+  SPP_TRY(mh_check(heads, K, x_dev, x_stride_elems, x_elem, "spp_gat_mh_aggregate_backward"));
+  SPP_REQUIRE(num_targets >= 0, "spp_gat_mh_aggregate_backward: negative size");
+  if (num_targets == 0) return SPP_OK;
+  SPP_REQUIRE(gat_mh_backward_bufs_ok(rowptr_dev, x_dev, a_src_dev, a_dst_dev, z_dev, row_max_dev, row_sum_dev,
+                                      grad_z_dev, grad_a_src_dev, grad_a_dst_dev),
+              "spp_gat_mh_aggregate_backward: NULL or unaligned buffer");
+  return gat_mh_backward_launch(rowptr_dev, col_dev, num_targets, x_dev, x_elem, x_stride_elems, K, heads, a_src_dev,
+                                a_dst_dev, negative_slope, z_dev, row_max_dev, row_sum_dev, grad_z_dev, grad_x_dev,
+                                grad_a_src_dev, grad_a_dst_dev, nullptr, nullptr, stream);
+}
+
+extern "C" int64_t spp_gat_mh_aggregate_backward_gather_workspace_bytes(int64_t num_targets, int64_t num_sources,
+                                                                        int64_t num_edges, int32_t heads) {
+  if (heads != 1 && heads != 2 && heads != 4 && heads != 8) return SPP_ERR_INVALID;
+  // alpha_e [E, H] | alpha_self [T, H] | the transposed hop with edge ids   (each 16-byte aligned)
+  return align16(4 * heads * num_edges) + align16(4 * heads * num_targets) +
+         transpose_hop_bytes(num_targets, num_sources, num_edges, true);
+}
+
+extern "C" spp_status spp_gat_mh_aggregate_backward_gather(
+    const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets, int64_t num_sources, int64_t num_edges,
+    const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t K, int32_t heads, const float* a_src_dev,
+    const float* a_dst_dev, float negative_slope, const float* z_dev, const float* row_max_dev,
+    const float* row_sum_dev, const float* grad_z_dev, const float* v_src_dev, const float* v_dst_dev,
+    float* grad_x_dev, float* grad_a_src_dev, float* grad_a_dst_dev, void* workspace_dev, int64_t workspace_bytes,
+    void* stream) {
+  const char* who = "spp_gat_mh_aggregate_backward_gather";
+  SPP_TRY(mh_check(heads, K, x_dev, x_stride_elems, x_elem, who));
+  SPP_REQUIRE(num_targets >= 0 && num_sources >= num_targets && num_edges >= 0, "%s: bad sizes", who);
+  if (num_sources == 0) return SPP_OK;
+  SPP_REQUIRE(num_sources < (1ll << 31) && num_edges < (1ll << 31), "%s: 32-bit indices", who);
+  SPP_REQUIRE(num_targets == 0 || gat_mh_backward_bufs_ok(rowptr_dev, x_dev, a_src_dev, a_dst_dev, z_dev, row_max_dev,
+                                                          row_sum_dev, grad_z_dev, grad_a_src_dev, grad_a_dst_dev),
+              "%s: NULL or unaligned buffer", who);
+  SPP_REQUIRE(rowptr_dev && v_src_dev && v_dst_dev && grad_x_dev && grad_a_src_dev && workspace_dev && al16(v_src_dev) &&
+                  al16(v_dst_dev) && al16(grad_x_dev) && al16(grad_a_src_dev) && al16(workspace_dev),
+              "%s: NULL buffer or buffers not 16-byte aligned", who);
+  SPP_REQUIRE(workspace_bytes >=
+                  spp_gat_mh_aggregate_backward_gather_workspace_bytes(num_targets, num_sources, num_edges, heads),
+              "%s: workspace too small", who);
+  hipStream_t st = as_stream(stream);
+  float* alpha_e = static_cast<float*>(workspace_dev);
+  float* alpha_self = alpha_e + align16(4 * heads * num_edges) / 4;
+  const int64_t alpha_bytes = align16(4 * heads * num_edges) + align16(4 * heads * num_targets);
+  // the attention weights of every entry and head + grad_a_src / grad_a_dst (no input gradient by atomics)
+  if (num_targets > 0)
+    SPP_TRY(gat_mh_backward_launch(rowptr_dev, col_dev, num_targets, x_dev, x_elem, x_stride_elems, K, heads, a_src_dev,
+                                   a_dst_dev, negative_slope, z_dev, row_max_dev, row_sum_dev, grad_z_dev, nullptr,
+                                   grad_a_src_dev, grad_a_dst_dev, alpha_e, alpha_self, stream));
+  TransposedHop hop;
+  SPP_TRY(transpose_hop(rowptr_dev, col_dev, num_targets, num_sources, num_edges, true,
+                        static_cast<char*>(workspace_dev) + alpha_bytes, workspace_bytes - alpha_bytes, st, &hop));
+  const int lpr_log2 = lanes_log2(K / 4);
+  const unsigned grid = (unsigned)ceil_div(num_sources << lpr_log2, kAggNT);
+  with_heads(heads, [&](auto hh) {
+    hipLaunchKernelGGL((k_gat_mh_gx_gather<decltype(hh)::value>), dim3(grid), dim3(kAggNT), 0, st, hop.start, hop.tcol,
+                       hop.tedge, alpha_e, alpha_self, num_targets, num_sources, grad_z_dev, K, lpr_log2,
+                       grad_a_src_dev, grad_a_dst_dev, v_src_dev, v_dst_dev, grad_x_dev);
+  });
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
 }

@@ -621,30 +621,41 @@ class _GatAggregate(torch.autograd.Function):
 
 
 class GATConv(torch.nn.Module):
-    """torch_geometric.nn.GATConv(in, out, heads=1, negative_slope=0.2, dropout=0, add_self_loops=True,
+    """torch_geometric.nn.GATConv(in, out, heads=1, concat=True, negative_slope=0.2, dropout=0, add_self_loops=True,
     bias=...) on a bipartite ((x, x_target), adj_t): one shared linear map for sources and targets
-    (an int ``in_channels``), attention vectors att_src / att_dst, softmax over the incoming edges."""
+    (an int ``in_channels``), attention vectors att_src / att_dst, softmax over the incoming edges.
 
-    def __init__(self, in_channels, out_channels, heads=1, negative_slope=0.2, bias=True):
+    ``heads`` = H: W is [H * out, in], att_src / att_dst are [1, H, out] (PyG's layout), every head has its own
+    softmax, and the output is the H heads side by side ([T, H * out], ``concat=True``) or their mean ([T, out]);
+    ``bias`` has the output's width.  heads=1 runs the single-head path; H in {1, 2, 4, 8} with the rows the kernels
+    read takes _GatLayerMH, anything else a plain-torch restatement of the same function (_gat_mh_reference)."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True):
         super().__init__()
-        if heads != 1:
-            raise NotImplementedError("the reference model fixes heads=1 (driver/models.py:197)")
+        if not isinstance(heads, int) or heads < 1:
+            raise ValueError(f"heads must be a positive int, got {heads!r}")
+        self.heads, self.out_channels, self.concat = heads, out_channels, bool(concat)
         self.negative_slope = negative_slope
-        self.lin_src = torch.nn.Linear(in_channels, out_channels, bias=False)
+        self.lin_src = torch.nn.Linear(in_channels, heads * out_channels, bias=False)
         self.lin_dst = self.lin_src
-        self.att_src = torch.nn.Parameter(torch.empty(1, 1, out_channels))
-        self.att_dst = torch.nn.Parameter(torch.empty(1, 1, out_channels))
-        self.bias = torch.nn.Parameter(torch.zeros(out_channels)) if bias else None
+        self.att_src = torch.nn.Parameter(torch.empty(1, heads, out_channels))
+        self.att_dst = torch.nn.Parameter(torch.empty(1, heads, out_channels))
+        width = heads * out_channels if concat else out_channels
+        self.bias = torch.nn.Parameter(torch.zeros(width)) if bias else None
         self.reset_parameters()
 
     def reset_parameters(self):
         self.lin_src.reset_parameters()
-        torch.nn.init.xavier_uniform_(self.att_src)          # PyG: glorot
+        # (xavier_uniform_ on [1, H, C]: bound sqrt(6 / (H*C + C)); PyG's glorot takes sqrt(6 / (H + C)).  Kept as it
+        # was for heads=1, whose initial values must not change; the training tests start from this bound at every H.)
+        torch.nn.init.xavier_uniform_(self.att_src)
         torch.nn.init.xavier_uniform_(self.att_dst)
         if self.bias is not None:
             torch.nn.init.zeros_(self.bias)
 
     def forward(self, x_pair, adj_t):
+        if self.heads != 1:
+            return self._forward_heads(x_pair, adj_t)
         x, x_target = x_pair
         rowptr, col, _ = adj_t.csr()
         T, K = x_target.size(0), x.size(1)
@@ -660,6 +671,147 @@ class GATConv(torch.nn.Module):
         a_dst = (h_t * self.att_dst.view(1, -1)).sum(-1)
         out = _GatAggregate.apply(h, a_src, a_dst, rowptr, col, self.negative_slope)
         return out if self.bias is None else out + self.bias
+
+    def _forward_heads(self, x_pair, adj_t):
+        x, x_target = x_pair
+        rowptr, col, _ = adj_t.csr()
+        T, K, H = x_target.size(0), x.size(1), self.heads
+        att_src, att_dst = self.att_src.view(H, -1), self.att_dst.view(H, -1)
+        if (H in _GAT_MH_HEADS and x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and x.dtype in _ELEM and
+                K % 4 == 0 and K <= 1024 and x_target.data_ptr() == x.data_ptr() and x_target.stride() == x.stride()):
+            out = _GatLayerMH.apply(x, self.lin_src.weight, att_src, att_dst, rowptr, col, T, self.negative_slope,
+                                    self.concat)
+        else:
+            out = _gat_mh_reference(x, x_target, self.lin_src.weight, att_src, att_dst, rowptr, col,
+                                    self.negative_slope, self.concat)
+        return out if self.bias is None else out + self.bias
+
+
+_GAT_MH_HEADS = (1, 2, 4, 8)       # the head counts the multi-head kernels are built for
+
+
+def _gat_mh_reference(x, x_target, W, att_src, att_dst, rowptr, col, slope, concat):
+    """GATConv with H heads in PyG's project-first order, in plain torch ops (the path for inputs the kernels do not
+    read: K % 4 != 0, K > 1024, other head counts, a target block that is not the prefix of x, CPU tensors).
+    x [S, K], x_target [T, K], W [H*C, K], att_* [H, C]; set_diag: diagonal entries dropped, one self loop (i, i) per
+    target, whose message is source row i."""
+    H, Cc = att_src.shape
+    S, T = x.size(0), x_target.size(0)
+    h = F.linear(x.to(W.dtype), W).view(S, H, Cc)
+    h_t = h[:T] if x_target.data_ptr() == x.data_ptr() and x_target.stride() == x.stride() else \
+        F.linear(x_target.to(W.dtype), W).view(T, H, Cc)
+    a_src = (h * att_src).sum(-1)                                           # [S, H]
+    a_dst = (h_t * att_dst).sum(-1)                                         # [T, H]
+    dst = torch.repeat_interleave(torch.arange(T, device=col.device), rowptr[1:] - rowptr[:-1])
+    keep = col != dst
+    loops = torch.arange(T, device=col.device)
+    src, dst = torch.cat([col[keep], loops]), torch.cat([dst[keep], loops])
+    e = F.leaky_relu(a_src[src].float() + a_dst[dst].float(), slope)        # [E', H]
+    emax = torch.full((T, H), float("-inf"), device=e.device).scatter_reduce(0, dst[:, None].expand(-1, H), e, "amax")
+    w = torch.exp(e - emax[dst])
+    den = torch.zeros((T, H), device=e.device).index_add_(0, dst, w)
+    alpha = w / den[dst]
+    out = torch.zeros((T, H, Cc), device=e.device).index_add_(0, dst, alpha[:, :, None] * h[src].float())
+    return out.reshape(T, H * Cc) if concat else out.mean(1)
+
+
+class _GatLayerMH(torch.autograd.Function):
+    """GATConv with H > 1 heads on ((x, x[:T]), adj_t) as ONE node, _GatLayer's aggregate-then-project form per head:
+
+        V_src[h] = W_h^T att_src[h], V_dst[h] = W_h^T att_dst[h]   (W_h: rows h*C .. (h+1)*C of W; V: [H, K])
+        z[i,h,:] = sum_j alpha_ij^h x_j                              (raw rows, each read once per edge for all heads)
+        concat:  out[:, h*C:(h+1)*C] = z[:,h,:] @ W_h^T             (one batched GEMM)
+        mean:    out = z.view(T, H*K) @ [W_0^T; ...; W_{H-1}^T] / H  (one GEMM)
+
+    x rows fp32, fp16 or bf16; V, the logits, z and the softmax statistics fp32.  Under bf16 autocast the projection and
+    the backward's GEMMs run in bf16 (bf16 output); parameters and their gradients stay fp32."""
+
+    @staticmethod
+    def forward(ctx, x, W, att_src, att_dst, rowptr, col, T, slope, concat):
+        ctx.amp = amp_bf16()
+        with _no_autocast():
+            return _GatLayerMH._forward(ctx, x, W, att_src, att_dst, rowptr, col, T, slope, concat)
+
+    @staticmethod
+    def _forward(ctx, x, W, att_src, att_dst, rowptr, col, T, slope, concat):
+        L = nat.load()
+        nat.require_device()
+        st = _stream()
+        S, K = x.size(0), x.size(1)
+        H, Cc = att_src.shape
+        elem = _ELEM[x.dtype]
+        xs = x.stride(0) if S > 1 else K
+        W3 = W.to(torch.float32).view(H, Cc, K)
+        att = torch.stack([att_src, att_dst]).to(torch.float32)                  # [2, H, C]
+        V = torch.einsum("shc,hck->shk", att, W3).contiguous()                   # [2, H, K]: V_src, V_dst
+        f32 = dict(dtype=torch.float32, device=x.device)
+        a_src, a_dst = torch.empty((S, H), **f32), torch.empty((T, H), **f32)
+        nat.check(L.spp_gat_mh_logits(_p(x), elem, xs, S, T, K, H, _p(V[0]), _p(V[1]), _p(a_src), _p(a_dst), st))
+        z = torch.empty((T, H, K), **f32)
+        rmax, rsum = torch.empty((T, H), **f32), torch.empty((T, H), **f32)
+        nat.check(L.spp_gat_mh_aggregate_forward(_p(rowptr), _p(col), T, _p(x), elem, xs, K, H, _p(a_src), _p(a_dst),
+                                                 float(slope), _p(z), _p(rmax), _p(rsum), st))
+        ctx.save_for_backward(x, W, att_src, att_dst, rowptr, col, a_src, a_dst, z, rmax, rsum, V)
+        ctx.dims = (S, T, K, H, Cc, elem, xs, float(slope), bool(concat))
+        dt = torch.bfloat16 if ctx.amp else torch.float32
+        zc, Wc = z.to(dt), W.to(dt).view(H, Cc, K)
+        if concat:                                                               # [H, T, K] @ [H, K, C] -> [T, H, C]
+            return torch.bmm(zc.transpose(0, 1), Wc.transpose(1, 2)).transpose(0, 1).reshape(T, H * Cc)
+        return (zc.view(T, H * K) @ Wc.transpose(1, 2).reshape(H * K, Cc)) * (1.0 / H)
+
+    @staticmethod
+    def backward(ctx, g_out):
+        with _no_autocast():
+            return _GatLayerMH._backward(ctx, g_out)
+
+    @staticmethod
+    def _backward(ctx, g_out):
+        L = nat.load()
+        st = _stream()
+        x, W, att_src, att_dst, rowptr, col, a_src, a_dst, z, rmax, rsum, V = ctx.saved_tensors
+        S, T, K, H, Cc, elem, xs, slope, concat = ctx.dims
+        dt = torch.bfloat16 if ctx.amp else torch.float32
+        g = g_out.to(dt).contiguous()
+        zc, Wc = z.to(dt), W.to(dt).view(H, Cc, K)
+        if concat:
+            g3 = g.view(T, H, Cc).transpose(0, 1)                                # [H, T, C]
+            g_z = torch.bmm(g3, Wc).transpose(0, 1).float().contiguous()        # [T, H, K]
+            gW = torch.bmm(g3.transpose(1, 2), zc.transpose(0, 1)).float().reshape(H * Cc, K)
+        else:
+            g = g * (1.0 / H)
+            g_z = (g @ Wc.transpose(1, 2).reshape(H * K, Cc).t()).float().view(T, H, K)
+            gW = _wgrad(g, zc.view(T, H * K)).view(Cc, H, K).transpose(0, 1).reshape(H * Cc, K)
+        want_gx = ctx.needs_input_grad[0]
+        E = col.numel()
+        gather = want_gx and E * K >= (1 << 22)
+        f32 = dict(dtype=torch.float32, device=x.device)
+        g_as, g_ad = torch.zeros((S, H), **f32), torch.empty((T, H), **f32)
+        if gather:                                  # the input gradient by gather, with the logits' rank-1 terms
+            g_x = torch.empty((S, K), **f32)
+            nbytes = int(L.spp_gat_mh_aggregate_backward_gather_workspace_bytes(T, S, E, H))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+            nat.check(L.spp_gat_mh_aggregate_backward_gather(
+                _p(rowptr), _p(col), T, S, E, _p(x), elem, xs, K, H, _p(a_src), _p(a_dst), slope, _p(z), _p(rmax),
+                _p(rsum), _p(g_z), _p(V[0]), _p(V[1]), _p(g_x), _p(g_as), _p(g_ad), _p(ws), nbytes, st))
+        else:
+            g_x = torch.zeros((S, K), **f32) if want_gx else None
+            nat.check(L.spp_gat_mh_aggregate_backward(_p(rowptr), _p(col), T, _p(x), elem, xs, K, H, _p(a_src),
+                                                      _p(a_dst), slope, _p(z), _p(rmax), _p(rsum), _p(g_z), _p(g_x),
+                                                      _p(g_as), _p(g_ad), st))
+        g_V = torch.empty((2, H, K), **f32)
+        nat.check(L.spp_gat_mh_logits_backward(_p(x), elem, xs, S, T, K, H, _p(g_as), _p(g_ad), _p(g_V[0]),
+                                               _p(g_V[1]), st))
+        if want_gx:                                                              # a_src = x V_src^T, a_dst = x[:T] V_dst^T
+            if not gather:
+                g_x.addmm_(g_as, V[0])
+                g_x[:T].addmm_(g_ad, V[1])
+            g_x = g_x.to(x.dtype)
+        # V[s, h] = att[s, h] @ W_h
+        att = torch.stack([att_src, att_dst]).to(torch.float32)                  # [2, H, C]
+        gW = gW + torch.einsum("shc,shk->hck", att, g_V).reshape(H * Cc, K)
+        g_att = torch.einsum("shk,hck->shc", g_V, W.to(torch.float32).view(H, Cc, K))
+        return (g_x, gW.to(W.dtype), g_att[0].to(att_src.dtype), g_att[1].to(att_dst.dtype), None, None, None, None,
+                None)
 
 
 class _GatLayer(torch.autograd.Function):
@@ -755,15 +907,36 @@ class _GatLayer(torch.autograd.Function):
 
 
 class GAT(torch.nn.Module):
-    def __init__(self, in_channels, hidden_channels, out_channels, num_layers):
+    """The reference's GAT (driver/models.py:195-231): ``num_layers`` GATConv(bias=False), ReLU + dropout 0.5 between
+    layers, log_softmax.
+
+    ``heads`` (keyword only, default 1): heads=1 is the reference model.  heads=H > 1 follows PyG's GAT examples, with
+    the hidden WIDTH kept: every hidden layer is GATConv(d_in, hidden_channels // H, heads=H, concat=True), so its
+    output is still ``hidden_channels`` wide ("3 x 256, heads=4" is four heads of 64), and the last layer is
+    GATConv(hidden_channels, out_channels, heads=H, concat=False), the mean of its heads.  ``hidden_channels`` must be
+    a multiple of ``heads``."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, heads=1):
         super().__init__()
+        if not isinstance(heads, int) or heads < 1:
+            raise ValueError(f"heads must be a positive int, got {heads!r}")
+        if hidden_channels % heads != 0:
+            raise ValueError(f"hidden_channels ({hidden_channels}) must be a multiple of heads ({heads})")
         self.num_layers = num_layers
         self.hidden_channels = hidden_channels
+        self.heads = heads
         self.convs = torch.nn.ModuleList()
-        self.convs.append(GATConv(in_channels, hidden_channels, bias=False, heads=1))
-        for _ in range(num_layers - 2):
-            self.convs.append(GATConv(hidden_channels, hidden_channels, bias=False, heads=1))
-        self.convs.append(GATConv(hidden_channels, out_channels, bias=False, heads=1))
+        if heads == 1:
+            self.convs.append(GATConv(in_channels, hidden_channels, bias=False, heads=1))
+            for _ in range(num_layers - 2):
+                self.convs.append(GATConv(hidden_channels, hidden_channels, bias=False, heads=1))
+            self.convs.append(GATConv(hidden_channels, out_channels, bias=False, heads=1))
+        else:
+            c = hidden_channels // heads
+            self.convs.append(GATConv(in_channels, c, heads=heads, concat=True, bias=False))
+            for _ in range(num_layers - 2):
+                self.convs.append(GATConv(hidden_channels, c, heads=heads, concat=True, bias=False))
+            self.convs.append(GATConv(hidden_channels, out_channels, heads=heads, concat=False, bias=False))
         self.reset_parameters()
 
     def reset_parameters(self):
