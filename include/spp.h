@@ -781,7 +781,7 @@ spp_status spp_csr_sum_backward_gather(const int64_t* rowptr_dev, const int64_t*
  *     them bf16 activations and gradients for training under torch.autocast(dtype=torch.bfloat16) -- through two
  *     entries instead of one function per combination.
  *
- *   Element codes (spp_elem): SPP_ELEM_F32 = 0, SPP_ELEM_F16 = 1, SPP_ELEM_BF16 = 2.  The GAT entries' `x_is_half`
+ *   Element codes (spp_elem): SPP_ELEM_F32 = 0, SPP_ELEM_F16 = 1, SPP_ELEM_BF16 = 2 (SPP_ELEM_FP8_E4M3 = 3: f3c below).  The GAT entries' `x_is_half`
  *   argument is this code too (0 and 1 keep their meaning).
  *   Rounding rule: every load converts to fp32 exactly; every sum and product runs in fp32, in the order of the fp32
  *   kernels; each stored bf16 element is rounded ONCE, to nearest even.  So a bf16 output equals the fp32 output
@@ -814,7 +814,7 @@ spp_status spp_csr_sum_backward_gather(const int64_t* rowptr_dev, const int64_t*
  *   An unknown source, epilogue, form or element code, or an element type an epilogue does not take, returns
  *   SPP_ERR_INVALID before anything is launched.
  * ------------------------------------------------------------------------- */
-enum { SPP_ELEM_F32 = 0, SPP_ELEM_F16 = 1, SPP_ELEM_BF16 = 2 };
+enum { SPP_ELEM_F32 = 0, SPP_ELEM_F16 = 1, SPP_ELEM_BF16 = 2, SPP_ELEM_FP8_E4M3 = 3 /* spp_agg_forward_fp8 only */ };
 enum { SPP_AGG_DENSE = 0, SPP_AGG_TABLE = 1, SPP_AGG_ROWS = 2 };
 enum { SPP_AGG_MEAN = 0, SPP_AGG_OPERAND = 1, SPP_AGG_OPERAND_ACT = 2, SPP_AGG_SUM = 3 };
 enum { SPP_AGG_SCATTER = 0, SPP_AGG_GATHER = 1 };
@@ -867,6 +867,25 @@ typedef struct spp_agg_bwd_desc {
 
 spp_status spp_agg_forward(const spp_agg_fwd_desc* desc, void* stream);
 spp_status spp_agg_backward(const spp_agg_bwd_desc* desc, void* workspace_dev, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * f3c  fp8 feature table (opt-in): one byte per element, OCP e4m3 (the encoding of torch.float8_e4m3fn, converted by
+ *      gfx950's v_cvt_pk_f32_fp8), with one power-of-two exponent per feature COLUMN.
+ *        q          e4m3 [rows, F], row-major, rows exactly F bytes apart, F % 16 == 0, base 16-byte aligned
+ *        scale_log2 int8 [F], every entry in [-64, 63]
+ *      The dequantised value is  v[i, c] = float32(q[i, c]) * 2^scale_log2[c]  -- exact in fp32.  A consumer of fp16
+ *      gets v rounded ONCE, to nearest even.
+ *
+ *   spp_gather_rows_fp8: dst[j, :] = fp16(v[idx[j], :]) for j < n; dst fp16 [n, F] dense, 16-byte aligned; idx int64.
+ *     An index outside [0, src_rows) reads row 0 and raises SPP_AERR_GATHER_INDEX (as spp_gather_rows).
+ *   spp_agg_forward_fp8: spp_agg_forward with x_elem = SPP_ELEM_FP8_E4M3 (x_stride_elems in elements = bytes) and
+ *     source SPP_AGG_DENSE or SPP_AGG_TABLE, epilogue SPP_AGG_MEAN / _OPERAND / _SUM: every load returns v, everything
+ *     after the load is the fp32 kernel's code, so the result equals spp_agg_forward's on the fp32 matrix v bit for bit.
+ *     Needs F % 4 == 0 and 4-byte aligned rows.  Anything else returns SPP_ERR_INVALID before a launch.
+ * ------------------------------------------------------------------------- */
+spp_status spp_gather_rows_fp8(const void* q_dev, int64_t src_rows, int64_t F, const int8_t* scale_log2_dev,
+                               const int64_t* idx_dev, int64_t n, void* dst_dev, void* stream);
+spp_status spp_agg_forward_fp8(const spp_agg_fwd_desc* desc, const int8_t* scale_log2_dev, void* stream);
 
 #ifdef __cplusplus
 }

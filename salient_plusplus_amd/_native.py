@@ -59,6 +59,7 @@ class MfgOut(C.Structure):
 
 # spp_elem and the aggregation descriptor's codes (include/spp.h)
 SPP_ELEM_F32, SPP_ELEM_F16, SPP_ELEM_BF16 = 0, 1, 2
+SPP_ELEM_FP8_E4M3 = 3            # spp_agg_forward_fp8 only
 SPP_AGG_DENSE, SPP_AGG_TABLE, SPP_AGG_ROWS = 0, 1, 2
 SPP_AGG_MEAN, SPP_AGG_OPERAND, SPP_AGG_OPERAND_ACT, SPP_AGG_SUM = 0, 1, 2, 3
 SPP_AGG_SCATTER, SPP_AGG_GATHER = 0, 1
@@ -200,6 +201,8 @@ SIGNATURES = {
     "spp_session_exchange_stats": (C.c_int, [p, C.POINTER(i64), C.POINTER(i64)]),
     "spp_agg_forward": (C.c_int, [C.POINTER(AggFwdDesc), p]),
     "spp_agg_backward": (C.c_int, [C.POINTER(AggBwdDesc), p, i64, p]),
+    "spp_gather_rows_fp8": (C.c_int, [p, i64, i64, p, p, i64, p, p]),
+    "spp_agg_forward_fp8": (C.c_int, [C.POINTER(AggFwdDesc), p, p]),
 }
 SPP_COMM_ID_BYTES = 128
 SPP_IPC_HANDLE_BYTES = 64

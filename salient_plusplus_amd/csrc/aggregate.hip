@@ -67,6 +67,59 @@ __device__ __forceinline__ float4 ld4(const bf16* p, int64_t i) {
 __device__ __forceinline__ void st4(float* p, int64_t i, float4 v) { reinterpret_cast<float4*>(p)[i] = v; }
 __device__ __forceinline__ void st4(bf16* p, int64_t i, float4 v) { store4(p + 4 * i, f4{v.x, v.y, v.z, v.w}); }
 
+// fp8 rows (f3c, include/spp.h): OCP e4m3 bytes with one power-of-two exponent per COLUMN.  A load returns
+// v = float32(code) * 2^e -- both steps exact (v_cvt_pk_f32_fp8; e in [-64, 63]) -- so everything behind the load is the
+// fp32 kernel's arithmetic on v.  The exponents ride in the epilogue record (Fp8<Epi>: a new instantiation of the same
+// kernel, no existing kernel's arguments change); the factors of a lane's columns are built once per column step,
+// outside the loop over the row's entries.
+struct fp8e4m3 {
+  uint8_t bits;
+};
+template <class Epi>
+struct Fp8 : Epi {
+  const int8_t* scale_log2;
+};
+typedef float f32x2_fp8 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float exp2_i8(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }
+// the factors of columns c .. c+3 (ColScale4) / of column c (ColScale1); empty for every other element type
+template <bool kFp8>
+struct ColScale4 {
+  template <class Epi>
+  __device__ __forceinline__ ColScale4(const Epi&, int64_t) {}
+};
+template <>
+struct ColScale4<true> {
+  f4 s;
+  template <class Epi>
+  __device__ __forceinline__ ColScale4(const Epi& epi, int64_t c) {
+    const uint32_t raw = *reinterpret_cast<const uint32_t*>(epi.scale_log2 + c);
+    s = {exp2_i8((int8_t)raw), exp2_i8((int8_t)(raw >> 8)), exp2_i8((int8_t)(raw >> 16)), exp2_i8((int8_t)(raw >> 24))};
+  }
+};
+template <bool kFp8>
+struct ColScale1 {
+  template <class Epi>
+  __device__ __forceinline__ ColScale1(const Epi&, int64_t) {}
+};
+template <>
+struct ColScale1<true> {
+  float s;
+  template <class Epi>
+  __device__ __forceinline__ ColScale1(const Epi& epi, int64_t c) : s(exp2_i8(epi.scale_log2[c])) {}
+};
+template <typename T>
+__device__ __forceinline__ f4 load4(const T* p, const ColScale4<false>&) { return load4(p); }
+template <typename T>
+__device__ __forceinline__ float load1(const T* p, const ColScale1<false>&) { return load1(p); }
+__device__ __forceinline__ f4 load4(const fp8e4m3* p, const ColScale4<true>& sc) {
+  const uint32_t raw = *reinterpret_cast<const uint32_t*>(p);
+  const f32x2_fp8 a = __builtin_amdgcn_cvt_pk_f32_fp8(raw, false), b = __builtin_amdgcn_cvt_pk_f32_fp8(raw, true);
+  return {a.x * sc.s.x, a.y * sc.s.y, b.x * sc.s.z, b.y * sc.s.w};
+}
+__device__ __forceinline__ float load1(const fp8e4m3* p, const ColScale1<true>& sc) {
+  return __builtin_amdgcn_cvt_f32_fp8((uint32_t)p->bits, 0) * sc.s;
+}
+
 // ---- ReLU + dropout (driver/models.py:47-48: x = F.relu(x); x = F.dropout(x, p=0.5)) ----
 // keep / drop from a counter-based generator: element i of the call with `seed` is kept iff
 // hash(seed, i) < (1 - p) * 2^32; the output is relu(x) / (1 - p) where kept, 0 elsewhere.
@@ -148,6 +201,8 @@ __global__ __launch_bounds__(kAggNT) void k_agg_fwd(const int64_t* __restrict__ 
                                                     const int64_t* __restrict__ nid, int64_t x_rows) {
   static_assert(!Epi::kAct || (VEC4 && !std::is_same<Tin, __half>::value && std::is_same<Src, Dense>::value),
                 "activation on load: dense fp32 / bf16 rows, vector form");
+  constexpr bool kFp8 = std::is_same<Tin, fp8e4m3>::value;  // (then Epi is an Fp8<...> and carries the column exponents)
+  static_assert(!kFp8 || !Epi::kAct, "fp8 rows are first-layer inputs: no activation on load");
   const Rows<Tin, Src> row{x, x_stride, nid, x_rows};
   const int lpr = 1 << lpr_log2;
   const int lane = threadIdx.x & (lpr - 1);
@@ -157,29 +212,30 @@ __global__ __launch_bounds__(kAggNT) void k_agg_fwd(const int64_t* __restrict__ 
   const float inv = 1.0f / (float)(e > b ? e - b : 1);  // Mean
   const Tin* own = epi.s != 0.f ? row(t) : nullptr;      // Sum
   if (VEC4) {
-    auto row4 = [&](int64_t j, int64_t c) {  // four columns of row j (activated on load with kAct)
-      f4 v = load4(row(j) + c);
+    auto row4 = [&](int64_t j, int64_t c, const ColScale4<kFp8>& sc) {  // four columns of row j (activated on load with kAct)
+      f4 v = load4(row(j) + c, sc);
       if constexpr (Epi::kAct) v = relu_dropout4(v, (j * x_stride + c) >> 2, epi.act);
       return v;
     };
     for (int64_t c = (int64_t)lane * 4; c < F; c += (int64_t)lpr * 4) {
+      const ColScale4<kFp8> sc(epi, c);
       if (epi.concat_target) {  // [mean | x_target]: the target's own row (targets are the first rows of x), as fp32
-        const f4 o = row4(t, c);
+        const f4 o = row4(t, c, sc);
         store4(out + t * out_stride + F + c, o);
       }
       f4 acc = {0.f, 0.f, 0.f, 0.f};
       int64_t k = b;
       for (; k + 1 < e; k += 2) {  // two independent rows in flight
-        const f4 v0 = row4(col[k], c), v1 = row4(col[k + 1], c);
+        const f4 v0 = row4(col[k], c, sc), v1 = row4(col[k + 1], c, sc);
         acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
         acc.x += v1.x; acc.y += v1.y; acc.z += v1.z; acc.w += v1.w;
       }
       if (k < e) {
-        const f4 v0 = row4(col[k], c);
+        const f4 v0 = row4(col[k], c, sc);
         acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
       }
       if (own) {
-        const f4 o = load4(own + c);
+        const f4 o = load4(own + c, sc);
         acc = {fmaf(epi.s, o.x, acc.x), fmaf(epi.s, o.y, acc.y), fmaf(epi.s, o.z, acc.z), fmaf(epi.s, o.w, acc.w)};
       }
       if (!Epi::kSum) acc = {acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv};
@@ -187,13 +243,14 @@ __global__ __launch_bounds__(kAggNT) void k_agg_fwd(const int64_t* __restrict__ 
     }
   } else {
     for (int64_t c = lane; c < F; c += lpr) {
+      const ColScale1<kFp8> sc(epi, c);
       if (epi.concat_target) {
-        const float o = load1(row(t) + c);
+        const float o = load1(row(t) + c, sc);
         store1(out + t * out_stride + F + c, o);
       }
       float acc = 0.f;
-      for (int64_t k = b; k < e; ++k) acc += load1(row(col[k]) + c);
-      if (own) acc = fmaf(epi.s, load1(own + c), acc);
+      for (int64_t k = b; k < e; ++k) acc += load1(row(col[k]) + c, sc);
+      if (own) acc = fmaf(epi.s, load1(own + c, sc), acc);
       if (!Epi::kSum) acc *= inv;
       store1(out + t * out_stride + c, acc);
     }
@@ -2115,6 +2172,54 @@ extern "C" spp_status spp_agg_forward(const spp_agg_fwd_desc* desc, void* stream
   if (d.source == SPP_AGG_TABLE) return run(Table{});
   if (d.source == SPP_AGG_ROWS) return run(Refs{});
   return run(Dense{});
+}
+
+// spp_agg_forward over an fp8 table (f3c): the same kernel with Tin = fp8e4m3 and the column exponents in Fp8<Epi>
+extern "C" spp_status spp_agg_forward_fp8(const spp_agg_fwd_desc* desc, const int8_t* scale_log2_dev, void* stream) {
+  static const char* who = "spp_agg_forward_fp8";
+  SPP_REQUIRE(desc, "%s: NULL descriptor", who);
+  const spp_agg_fwd_desc& d = *desc;
+  SPP_REQUIRE(d.x_elem == SPP_ELEM_FP8_E4M3, "%s: x_elem must be SPP_ELEM_FP8_E4M3, got %d", who, (int)d.x_elem);
+  SPP_REQUIRE(d.source == SPP_AGG_DENSE || d.source == SPP_AGG_TABLE, "%s: source %d (dense rows or the table)", who,
+              (int)d.source);
+  SPP_REQUIRE(d.epilogue == SPP_AGG_MEAN || d.epilogue == SPP_AGG_OPERAND || d.epilogue == SPP_AGG_SUM,
+              "%s: epilogue %d (mean, operand or sum)", who, (int)d.epilogue);
+  SPP_REQUIRE(f32_bf16_ok(d.out_elem), "%s: unsupported output element code %d", who, (int)d.out_elem);
+  const int64_t T = d.num_targets, F = d.F;
+  SPP_REQUIRE(T >= 0 && F >= 0, "%s: negative size", who);
+  const bool operand = d.epilogue == SPP_AGG_OPERAND;
+  const int64_t width = operand ? 2 * F : F;
+  const int64_t out_stride = d.out_stride_elems > 0 ? d.out_stride_elems : width;
+  SPP_REQUIRE(out_stride >= width, "%s: output stride smaller than the output row", who);
+  if (T == 0 || F == 0) return SPP_OK;
+  SPP_REQUIRE(d.rowptr_dev && d.out_dev && d.x_dev && scale_log2_dev && (d.source == SPP_AGG_DENSE || (d.n_id_dev && d.x_rows > 0)),
+              "%s: NULL buffer or empty table", who);
+  const int64_t osz = elem_bytes(d.out_elem);
+  SPP_REQUIRE(d.x_stride_elems >= F, "%s: row stride smaller than the row", who);
+  SPP_REQUIRE(F % 4 == 0 && d.x_stride_elems % 4 == 0 && reinterpret_cast<uintptr_t>(d.x_dev) % 4 == 0 &&
+                  reinterpret_cast<uintptr_t>(scale_log2_dev) % 4 == 0 && out_stride % 4 == 0 &&
+                  reinterpret_cast<uintptr_t>(d.out_dev) % (4 * osz) == 0,
+              "%s: needs F %% 4 == 0, 4-byte aligned rows and exponents and an aligned output (F = %lld)", who, (long long)F);
+  auto run = [&](auto src, auto epi) {
+    using Src = decltype(src);
+    with_f32_bf16(d.out_elem, [&](auto tout) {
+      launch_agg_fwd<fp8e4m3, typename decltype(tout)::type, true, Src>(
+          d.rowptr_dev, d.col_dev, T, d.x_dev, d.x_stride_elems, d.n_id_dev, d.x_rows, F,
+          Fp8<decltype(epi)>{epi, scale_log2_dev}, d.out_dev, out_stride, stream);
+    });
+  };
+  auto by_epi = [&](auto src) {
+    if (d.epilogue == SPP_AGG_SUM)
+      run(src, Sum{d.self_scale});
+    else
+      run(src, Mean<false>{operand ? 1 : 0, {}});
+  };
+  if (d.source == SPP_AGG_TABLE)
+    by_epi(Table{});
+  else
+    by_epi(Dense{});
+  SPP_HIP_TRY(hipGetLastError());
+  return SPP_OK;
 }
 
 // the backward of one descriptor with its element types resolved (z is read by OPERAND_ACT only)

@@ -27,10 +27,11 @@ from typing import List, Optional, Sequence
 import torch
 
 from .. import _native as nat
+from ..fp8 import Fp8Features
 
 __all__ = ["Config", "Session", "ProtoDistributedBatch", "RangePartitionBook", "Cache", "sample_adj",
            "multilayer_sample", "full_sample", "to_row_major", "serial_index", "NativeComm", "native_comm",
-           "set_native_comm", "async_errors", "set_sampler_options", "sampler_options", "sampler_info", "TableRows", "RowRefs",
+           "set_native_comm", "async_errors", "set_sampler_options", "sampler_options", "sampler_info", "TableRows", "RowRefs", "Fp8Features", "fp8_gather_rows",
            "P2PPeers", "set_p2p_peers", "p2p_open_peers"]
 
 # four slot-sets of 16 batches (~75 MB of workspace per slot at fanout [15,10,5], batch 1024: 4.8 GB).  With two sets, a
@@ -185,16 +186,50 @@ def _as_i64_list(sizes: Sequence[int]) -> List[int]:
 # --------------------------------------------------------------------------------------------
 # the batch's features as (resident table, node ids) -- opt-in, for a consumer that aggregates straight from the table
 # --------------------------------------------------------------------------------------------
+def fp8_gather_rows(table: Fp8Features, n_id: torch.Tensor, out: Optional[torch.Tensor] = None, stream_ptr=None) -> torch.Tensor:
+    """``out[j, :] = fp16(float32(q[n_id[j], :]) * 2^scale_log2)``: the dequantising HIP row gather over a device-resident
+    fp8 table (spp_gather_rows_fp8), on the caller's current stream unless a raw stream handle is given."""
+    n = n_id.numel()
+    if out is None:
+        out = torch.empty((n, table.size(1)), dtype=torch.float16, device=table.device)
+    if n and table.size(1):
+        nat.check(_lib().spp_gather_rows_fp8(_ptr(table.q), table.size(0), table.size(1), _ptr(table.scale_log2), _ptr(n_id), n,
+                                             _ptr(out), C.c_void_p(stream_ptr) if stream_ptr is not None else _stream_ptr()))
+    return out
+
+
+def fp8_session_check(config, row_refs: bool = False) -> bool:
+    """True when the configuration's feature table is an Fp8Features.  The fp8 table is read by the single-GPU,
+    non-distributed session only: anything else is refused here -- at construction, before any device call."""
+    if not isinstance(getattr(config, "x_cpu", None), Fp8Features):
+        if isinstance(getattr(config, "x_gpu", None), Fp8Features):
+            raise RuntimeError("fp8 feature table: hand it over as x_cpu (x_gpu belongs to the partitioned path, which does "
+                               "not read fp8 rows)")
+        return False
+    if bool(config.distributed):
+        raise RuntimeError("fp8 feature table: distributed=True is not supported (the partitioned RCCL / P2P paths exchange "
+                           "fp16 / fp32 rows); use a single-GPU session")
+    cache = getattr(config, "cache", None)
+    if bool(config.use_cache) or (cache is not None and getattr(cache, "cached_vertices", None) is not None and
+                                  cache.cached_vertices.numel() > 0):
+        raise RuntimeError("fp8 feature table: a VIP cache is not supported over fp8 rows")
+    if row_refs:
+        raise RuntimeError("fp8 feature table: row_refs is not supported (row references belong to the partitioned path); "
+                           "use table_features")
+    return True
+
+
 class TableRows:
     """``x = table[n_id]`` without the copy: what a Session with ``table_features`` puts in the place of the batch's
     feature matrix (fast_sampler.cpp:1004-1016 ``serial_index(x_cpu, n_id)``).  ``models.SAGE`` aggregates its first
     layer straight from ``table`` (spp_sage_operand_forward_table: same rows, same summation order, bit-identical
     operand), so the 242 MB of rows a papers-scale batch holds are neither written by the delivery nor read back.
     Everything else still sees a feature matrix through ``materialize()``; sizes / device / dtype read like the
-    tensor's."""
+    tensor's.  ``table`` may be an ``Fp8Features`` (opt-in fp8 table): the models' first layers read it in place with the
+    scales applied on load, and ``materialize()`` dequantises to fp16 (the value rounded once)."""
     __slots__ = ("table", "n_id")
 
-    def __init__(self, table: torch.Tensor, n_id: torch.Tensor):
+    def __init__(self, table, n_id: torch.Tensor):
         self.table, self.n_id = table, n_id
 
     # -- what iterators and records ask of a feature matrix --
@@ -235,6 +270,8 @@ class TableRows:
     def materialize(self) -> torch.Tensor:
         """The feature matrix itself: the HIP row gather on the caller's current stream (a5, serial_index)."""
         t = self.table                                   # (a strided view of the padded resident table)
+        if isinstance(t, Fp8Features):
+            return fp8_gather_rows(t, self.n_id)
         out = torch.empty((self.n_id.numel(), t.size(1)), dtype=t.dtype, device=t.device)
         if out.numel():
             nat.check(_lib().spp_gather_rows_strided(_ptr(t), t.size(0), t.size(1) * t.element_size(), _stride_bytes(t),
@@ -719,6 +756,7 @@ def _host_ranges(n, batch_size, skip_nonfull, force_exact, exact_k):
 # --------------------------------------------------------------------------------------------
 class Session:
     def __init__(self, num_threads: int, max_items_in_queue: int, config: Config):
+        fp8 = fp8_session_check(config)    # an fp8 table outside its scope is refused before any device call
         L = _lib()
         if max_items_in_queue <= 0:
             raise RuntimeError(f"max_items_in_queue ({max_items_in_queue}) must be positive")
@@ -734,7 +772,14 @@ class Session:
         self._distributed = bool(config.distributed)
 
         # features / labels resident in HBM
-        if self._distributed:
+        self._fp8 = None
+        if fp8:
+            # opt-in fp8 table: q and the column exponents resident; the batches' fp16 rows come from the dequantising
+            # gather, launched behind each delivery on its stream (labels, MFG, ordering and buffering are untouched)
+            f = config.x_cpu
+            self._fp8 = Fp8Features._wrap(_resident.get(f.q), _resident.get(f.scale_log2)) if f.numel() else None
+            self._x = None
+        elif self._distributed:
             xg, xc = config.x_gpu, config.x_cpu
             parts = [t for t in (xg, xc) if t is not None and t.dim() == 2 and t.size(0) > 0]
             if len(parts) == 2:
@@ -1100,11 +1145,20 @@ class Session:
         stream = torch.cuda.current_stream(dev)
         nat.check(self._L.spp_session_export_group(self._h, n, outs, xa[0], xa[1], xa[2], xa[3], ya[0], ya[1], ya[2],
                                                    C.c_void_p(stream.cuda_stream)))
+        if self._fp8 is not None:
+            for r in records:
+                self._fp8_deliver(r, stream.cuda_stream)
         ev = torch.cuda.Event()
         ev.record(stream)
         for r in records:
             self._ready.append((self._make_record(r, flags), ev, stream))
         return True
+
+    def _fp8_deliver(self, r, raw_stream):
+        """x = fp16(dequantised table[n_id]) of one batch record, behind its delivery on the same stream"""
+        x, n_id = r[0], r[4]
+        if isinstance(x, torch.Tensor) and n_id is not None:
+            fp8_gather_rows(self._fp8, n_id, x, raw_stream)
 
     def _make_record(self, r, flags):
         (x, y, adjs, rng, n_id, nids, flat, cached, perm, pc, U) = r
@@ -1118,6 +1172,8 @@ class Session:
     def _table_mode(self) -> bool:
         if not self.table_features:
             return False
+        if self._fp8 is not None:
+            return True
         if self._distributed or self._x is None:
             raise RuntimeError("table_features: only single-GPU sessions with a feature table deliver TableRows "
                                "(a partitioned session assembles x from three sources: set row_refs there)")
@@ -1126,6 +1182,8 @@ class Session:
     def _refs_mode(self) -> bool:
         if not self.row_refs:
             return False
+        if self._fp8 is not None:
+            raise RuntimeError("fp8 feature table: row_refs is not supported; use table_features")
         if not (self._distributed and self.native_exchange and self._x is not None):
             raise RuntimeError("row_refs: only partitioned sessions with the native exchange (RCCL or P2P transport) deliver "
                                "RowRefs (single-GPU sessions: table_features)")
@@ -1154,6 +1212,8 @@ class Session:
         raw = self._export_raw if self._export_raw is not None else torch._C._cuda_getCurrentRawStream(self._dev.index)
         nat.check(self._L.spp_session_export(self._h, C.byref(o.mfg), xa[0], xa[1], xa[2], xa[3], o.x_out,
                                              ya[0], ya[1], ya[2], o.y_out, C.c_void_p(raw)))
+        if self._fp8 is not None:
+            self._fp8_deliver(records[i], raw)
         rec = self._make_record(records[i], flags)
         if i + 1 == n:
             self._open = None
@@ -1190,8 +1250,10 @@ class Session:
         want_parts = distributed and (not native or count_remote or not self.compact_native_records)
         table = self._table_mode()
         refs = self._refs_mode()
-        want_n_id = distributed or table
+        fp8 = self._fp8
+        want_n_id = distributed or table or fp8 is not None
         want_x = (self._x is not None) and (native or not distributed) and not table and not refs
+        want_x8 = fp8 is not None and not table     # fp16 rows written by the dequantising gather, not by the delivery
         want_y = self._y is not None
         H = int(self._gdescs[0].counts.num_hops)
         # ---- sizes (host counts of every batch) and the arena layout
@@ -1233,6 +1295,10 @@ class Session:
         base = arena.data_ptr()
         x_views = y_views = None
         row_b = 0
+        if want_x8:
+            F = fp8.size(1)
+            x_arena = torch.empty((_coarse(sum(Us)), F), dtype=torch.float16, device=dev)   # rows of 2F bytes, F % 16 == 0:
+            x_views = x_arena.split(Us + [x_arena.size(0) - sum(Us)])                       # every batch starts 32-byte aligned
         if want_x:
             F = self._x.size(1)
             row_b = F * self._x.element_size()
@@ -1307,7 +1373,9 @@ class Session:
                 off += U
             x = y = None
             if table:
-                x = TableRows(self._x, n_id)
+                x = TableRows(self._x if fp8 is None else fp8, n_id)
+            if want_x8:
+                x = x_views[i]
             if refs:
                 xr = None
                 if n_rem[i]:
@@ -1326,7 +1394,7 @@ class Session:
             records.append((x, y, adjs, (start, stop), n_id, nids, flat, cached, perm, pc, U))
         xa = self._x_args if (want_x and not native) else (None, 0, 0, 0)
         ya = self._y_args if want_y else (None, 0, 0)
-        arenas = [t for t in (arena, x_arena if want_x else None, y_arena if want_y else None, xr_arena) if t is not None]
+        arenas = [t for t in (arena, x_arena if (want_x or want_x8) else None, y_arena if want_y else None, xr_arena) if t is not None]
         return n, outs, records, xa, ya, (distributed, native, count_remote, rank), arenas
 
     def _proto_record(self, x, y, adjs, rng, n_id, nids, flat, cached, perm, pc, native, count_remote, rank):
@@ -1386,10 +1454,13 @@ class Session:
         d = self._desc
         c = d.counts
         table = self._table_mode()
-        out, n_id, adjs = self._alloc_mfg(c, want_n_id=table)          # n_id is not part of the tuple
+        fp8 = self._fp8
+        out, n_id, adjs = self._alloc_mfg(c, want_n_id=table or fp8 is not None)          # n_id is not part of the tuple
         x = y = None
         if table:
             x = None
+        elif fp8 is not None:
+            x = torch.empty((c.num_nodes, fp8.size(1)), dtype=torch.float16, device=self._dev)
         elif self._x is not None:
             x = torch.empty((c.num_nodes, self._x.size(1)), dtype=self._x.dtype, device=self._dev)
         else:
@@ -1397,7 +1468,9 @@ class Session:
         if self._y is not None:
             y = torch.empty((d.stop - d.start, self._y.size(1)), dtype=self._y.dtype, device=self._dev)
         self._export(out, x, y)
-        return (TableRows(self._x, n_id) if table else x, y, adjs, (int(d.start), int(d.stop)))
+        if fp8 is not None and not table:
+            fp8_gather_rows(fp8, n_id, x)
+        return (TableRows(self._x if fp8 is None else fp8, n_id) if table else x, y, adjs, (int(d.start), int(d.stop)))
 
     def try_get_batch(self):
         """Non-blocking (fast_sampler.cpp:658-670): None when no batch is ready yet or none is left."""

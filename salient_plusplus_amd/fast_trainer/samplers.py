@@ -225,6 +225,10 @@ class FastSamplerConfig:
     count_remote_frequency: bool
     use_cache: bool
 
+    def __post_init__(self):
+        # an fp8 feature table (fp8.Fp8Features as x_cpu) is read by the single-GPU session only: refused here otherwise
+        fast_sampler.fp8_session_check(self)
+
     def to_fast_sampler(self) -> fast_sampler.Config:
         native = fast_sampler.Config()
         for f in dataclasses.fields(self):
@@ -328,6 +332,9 @@ class FastSampler(ABCNeighborSampler):
     # not in the reference (samplers.py:381-399 has the three fields above): see FastSamplerIter
     table_features: bool = False
     row_refs: bool = False
+
+    def __post_init__(self):
+        fast_sampler.fp8_session_check(self.cfg, row_refs=self.row_refs)      # (row_refs is known here, not in the config)
 
     def __iter__(self):
         return FastSamplerIter(self.num_threads, self.max_items_in_queue, self.cfg, self.table_features, self.row_refs)

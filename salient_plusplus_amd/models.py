@@ -14,6 +14,7 @@ import torch.nn.functional as F
 
 from . import _native as nat
 from .fast_sampler import RowRefs, TableRows
+from .fp8 import Fp8Features
 
 
 def _p(t):
@@ -49,7 +50,15 @@ def _a(t):
 
 def _agg_forward(epilogue, rowptr, col, T, x, x_dtype, Fdim, out, *, source=nat.SPP_AGG_DENSE, x_stride=0, n_id=None,
                  x_rows=0, scale=0.0, act=(0.0, 0, 0), st=None):
-    """spp_agg_forward: x is the address of the rows (or None), out a dense [T, F or 2F] fp32 / bf16 tensor"""
+    """spp_agg_forward: x is the address of the rows (or None), out a dense [T, F or 2F] fp32 / bf16 tensor.
+    An Fp8Features x (dense rows, or the table with n_id) goes to spp_agg_forward_fp8 with its column exponents."""
+    if isinstance(x, Fp8Features):
+        d = nat.AggFwdDesc(source=nat.SPP_AGG_DENSE if n_id is None else nat.SPP_AGG_TABLE, epilogue=epilogue,
+                           x_elem=nat.SPP_ELEM_FP8_E4M3, out_elem=_ELEM[out.dtype], rowptr_dev=_a(rowptr), col_dev=_a(col),
+                           num_targets=T, x_dev=_a(x.q), x_stride_elems=Fdim, x_rows=x.size(0), n_id_dev=_a(n_id), F=Fdim,
+                           out_dev=_a(out), out_stride_elems=0, self_scale=float(scale))
+        nat.check(nat.load().spp_agg_forward_fp8(C.byref(d), _a(x.scale_log2), st if st is not None else _stream()))
+        return
     d = nat.AggFwdDesc(source=source, epilogue=epilogue, x_elem=_ELEM[x_dtype], out_elem=_ELEM[out.dtype],
                        rowptr_dev=_a(rowptr), col_dev=_a(col), num_targets=T, x_dev=x, x_stride_elems=x_stride,
                        x_rows=x_rows, n_id_dev=_a(n_id), F=Fdim, out_dev=_a(out), out_stride_elems=0,
@@ -75,6 +84,21 @@ def _agg_backward(epilogue, rowptr, col, T, S, g, Fdim, grad_x, *, gather, z=Non
     nat.check(L.spp_agg_backward(C.byref(d), _a(ws), nbytes, st if st is not None else _stream()))
 
 
+def _fp8_rows(x):
+    """(Fp8Features, n_id or None) when x is a dense Fp8Features or a TableRows over one, else None"""
+    if isinstance(x, Fp8Features):
+        return x, None
+    if isinstance(x, TableRows) and isinstance(x.table, Fp8Features):
+        return x.table, x.n_id
+    return None
+
+
+def _no_input_grad(ctx, what):
+    # an fp8 table is no leaf: nothing flows back into it (the first layer's input gets no gradient)
+    if ctx.needs_input_grad[0]:
+        raise RuntimeError(f"{what}: an fp8 feature table cannot receive a gradient")
+
+
 def _grad_in(g):
     """an incoming gradient as the descriptor entries read it: unit column stride, fp32 or bf16"""
     if g.dtype not in (torch.float32, torch.bfloat16):
@@ -95,6 +119,24 @@ class _MeanAggregate(torch.autograd.Function):
     def forward(ctx, x, rowptr, col, num_targets, concat_target):
         L = nat.load()
         nat.require_device()
+        f8 = _fp8_rows(x)
+        if f8 is not None:
+            # fp8 rows read in place (the table with n_id, or dense rows): scales applied on load
+            _no_input_grad(ctx, "mean_aggregate")
+            tb, n_id = f8
+            assert x.is_cuda
+            Fdim = tb.size(1)
+            ctx.amp = amp_bf16()
+            ctx.desc = True
+            out = torch.empty((num_targets, 2 * Fdim if concat_target else Fdim),
+                              dtype=torch.bfloat16 if ctx.amp else torch.float32, device=x.device)
+            epi = nat.SPP_AGG_OPERAND if concat_target else nat.SPP_AGG_MEAN
+            _agg_forward(epi, rowptr, col, num_targets, tb, None, Fdim, out, n_id=n_id)
+            ctx.save_for_backward(rowptr, col)
+            ctx.shape = (x.size(0), Fdim, num_targets, out.size(1))
+            ctx.in_dtype = torch.float32
+            ctx.concat = bool(concat_target)
+            return out
         assert x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and x.dtype in _ELEM
         Fdim = x.size(1)
         width = 2 * Fdim if concat_target else Fdim
@@ -261,6 +303,12 @@ class SAGEConv(torch.nn.Module):
     def forward(self, x_pair, adj_t):
         x, x_target = x_pair
         rowptr, col, _ = adj_t.csr()
+        if _fp8_rows(x) is not None:                     # fp8 rows, read in place: the targets are the first rows of x
+            if x_target is not None and x_target is not x:
+                raise RuntimeError("SAGEConv over fp8 rows: the targets are the first rows of x (pass (x, None))")
+            fused = _MeanAggregate.apply(x, rowptr, col, int(adj_t.sparse_sizes()[0]), True)
+            out = _TallLinear.apply(fused, torch.cat([self.lin_l.weight, self.lin_r.weight], dim=1))
+            return out if self.lin_l.bias is None else out + self.lin_l.bias
         # [mean_j x_j | x_target] @ [W_l | W_r]^T: one GEMM instead of two plus an add
         T = x_target.size(0)
         if x_target.data_ptr() == x.data_ptr() and x_target.size(1) == x.size(1) and x_target.stride() == x.stride():
@@ -305,6 +353,8 @@ class SAGE(torch.nn.Module):
             return _SageStack.apply(x, hops, self.training, 0.5, *weights)
         if isinstance(x, (TableRows, RowRefs)):
             x = x.materialize()
+        elif isinstance(x, Fp8Features):
+            x = x.dequantize(torch.float16)
         for i, (adj_t, _e_id, size) in enumerate(adjs):
             x_target = x[:size[1]]
             x = self.convs[i]((x, x_target), adj_t)
@@ -380,6 +430,8 @@ def _readable(x):
     if isinstance(x, RowRefs):
         return x.dtype in _ELEM
     m = x.table if isinstance(x, TableRows) else x
+    if isinstance(m, Fp8Features):                        # fp8 rows with column scales: spp_agg_forward_fp8
+        return m.is_cuda
     return m.is_cuda and m.dim() == 2 and m.stride(1) == 1 and m.dtype in _ELEM
 
 
@@ -405,6 +457,8 @@ class _SageStack(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, hops, training, p, *weights):
+        if isinstance(x, Fp8Features) or (isinstance(x, tuple) and isinstance(x[0], Fp8Features)):
+            _no_input_grad(ctx, "SAGE")
         ctx.amp = amp_bf16()
         if ctx.amp:
             return _SageStack._forward_bf16(ctx, x, hops, training, p, *weights)
@@ -428,7 +482,9 @@ class _SageStack(torch.autograd.Function):
         for i, (rowptr, col, T) in enumerate(hops):
             K = refs.width if (i == 0 and refs is not None) else h.size(1)
             A = torch.empty((T, 2 * K), dtype=torch.float32, device=x.device)
-            if i == 0 and refs is not None:
+            if i == 0 and isinstance(h, Fp8Features):    # fp8 rows (the table with n_id, or dense): scales applied on load
+                _agg_forward(nat.SPP_AGG_OPERAND, rowptr, col, T, h, None, K, A, n_id=n_id, st=st)
+            elif i == 0 and refs is not None:
                 nat.check(L.spp_sage_operand_forward_rows(_p(rowptr), _p(col), T, _p(refs.addr), int(refs.dtype == torch.float16),
                                                           K, _p(A), 2 * K, st))
             elif i == 0 and n_id is not None:
@@ -481,7 +537,9 @@ class _SageStack(torch.autograd.Function):
             for i, (rowptr, col, T) in enumerate(hops):
                 K = refs.width if (i == 0 and refs is not None) else h.size(1)
                 A = torch.empty((T, 2 * K), dtype=torch.bfloat16, device=x.device)
-                if i == 0 and refs is not None:
+                if i == 0 and isinstance(h, Fp8Features):
+                    _agg_forward(nat.SPP_AGG_OPERAND, rowptr, col, T, h, None, K, A, n_id=n_id, st=st)
+                elif i == 0 and refs is not None:
                     _agg_forward(nat.SPP_AGG_OPERAND, rowptr, col, T, None, refs.dtype, K, A, source=nat.SPP_AGG_ROWS,
                                  n_id=refs.addr, st=st)
                 elif i == 0 and n_id is not None:
@@ -982,7 +1040,11 @@ class _SumAggregate(torch.autograd.Function):
         ctx.desc = ctx.amp or x.dtype == torch.bfloat16           # bf16 in or out: the descriptor entry
         out = torch.empty((num_targets, Fdim), dtype=torch.bfloat16 if ctx.amp else torch.float32, device=x.device)
         half = int(x.dtype == torch.float16)
-        if ctx.desc:
+        f8 = _fp8_rows(x)
+        if f8 is not None:                                        # fp8 rows read in place, scales applied on load
+            _no_input_grad(ctx, "sum_aggregate")
+            _agg_forward(nat.SPP_AGG_SUM, rowptr, col, num_targets, f8[0], None, Fdim, out, n_id=f8[1], scale=scale, st=st)
+        elif ctx.desc:
             if isinstance(x, TableRows):
                 tb = x.table
                 _agg_forward(nat.SPP_AGG_SUM, rowptr, col, num_targets, _a(tb), tb.dtype, Fdim, out,
@@ -1132,7 +1194,7 @@ class GIN(torch.nn.Module):
     def forward(self, x, adjs):
         # the reference converts the features to fp32 first (models.py:272); the sum reads fp16 rows directly (exact)
         for i, (adj_t, _e_id, size) in enumerate(adjs):
-            if isinstance(x, (TableRows, RowRefs)):
+            if isinstance(x, (TableRows, RowRefs, Fp8Features)):
                 x = self.convs[i](x, adj_t, size)
             else:
                 x = self.convs[i]((x, x[:size[1]]), adj_t)
