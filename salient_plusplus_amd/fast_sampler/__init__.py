@@ -222,7 +222,7 @@ def fp8_session_check(config, row_refs: bool = False) -> bool:
 class TableRows:
     """``x = table[n_id]`` without the copy: what a Session with ``table_features`` puts in the place of the batch's
     feature matrix (fast_sampler.cpp:1004-1016 ``serial_index(x_cpu, n_id)``).  ``models.SAGE`` aggregates its first
-    layer straight from ``table`` (spp_sage_operand_forward_table: same rows, same summation order, bit-identical
+    layer straight from ``table`` (spp_agg_forward, source SPP_AGG_TABLE: same rows, same summation order, bit-identical
     operand), so the 242 MB of rows a papers-scale batch holds are neither written by the delivery nor read back.
     Everything else still sees a feature matrix through ``materialize()``; sizes / device / dtype read like the
     tensor's.  ``table`` may be an ``Fp8Features`` (opt-in fp8 table): the models' first layers read it in place with the
@@ -285,7 +285,7 @@ class RowRefs:
     with ``row_refs`` puts in the place of the batch's feature matrix.  ``addr[j]`` is the device address of the feature
     row of MFG node j -- in this rank's resident partition, in the VIP cache, in a peer's partition (P2P transport) or in
     ``x_remote`` (the rows received for this batch over RCCL: the only rows the delivery still copies).  ``models.SAGE``
-    aggregates its first layer straight from these addresses (spp_sage_operand_forward_rows: same rows, same summation
+    aggregates its first layer straight from these addresses (spp_agg_forward, source SPP_AGG_ROWS: same rows, same summation
     order as over the assembled matrix -- bit-identical operand); everything else sees a feature matrix through
     ``materialize()``.  ``keep`` holds the tensors the addresses point into."""
     __slots__ = ("addr", "n_id", "width", "_dtype", "x_remote", "keep")

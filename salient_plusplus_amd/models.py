@@ -31,7 +31,9 @@ def _stream():
 # bf16 (fp32 accumulation) and keep parameters and parameter gradients fp32.  The aggregation kernels accumulate in fp32
 # and round every stored element once (include/spp.h, spp_agg_forward).  Under any other autocast dtype the nodes run
 # their fp32 path with autocast disabled inside them.  Each node decides in its forward and records the decision on
-# ctx; its backward uses explicit dtypes only.
+# ctx; its backward uses explicit dtypes only.  The mean / operand / sum aggregations take one call path for every
+# element type and row source: the descriptor entries spp_agg_forward, spp_agg_forward_fp8 and spp_agg_backward
+# (_agg_forward, _agg_backward below), with the compute dtype as a value.
 _ELEM = {torch.float32: nat.SPP_ELEM_F32, torch.float16: nat.SPP_ELEM_F16, torch.bfloat16: nat.SPP_ELEM_BF16}
 
 
@@ -44,53 +46,81 @@ def _no_autocast():
     return torch.autocast("cuda", enabled=False) if torch.is_autocast_enabled("cuda") else contextlib.nullcontext()
 
 
-def _a(t):
-    return t.data_ptr() if t is not None and t.numel() > 0 else None
+class _Refs:
+    """RowRefs on their way through _SageStack.apply (a non-tensor argument)"""
+    __slots__ = ("r",)
+
+    def __init__(self, r):
+        self.r = r
 
 
-def _agg_forward(epilogue, rowptr, col, T, x, x_dtype, Fdim, out, *, source=nat.SPP_AGG_DENSE, x_stride=0, n_id=None,
-                 x_rows=0, scale=0.0, act=(0.0, 0, 0), st=None):
-    """spp_agg_forward: x is the address of the rows (or None), out a dense [T, F or 2F] fp32 / bf16 tensor.
-    An Fp8Features x (dense rows, or the table with n_id) goes to spp_agg_forward_fp8 with its column exponents."""
-    if isinstance(x, Fp8Features):
-        d = nat.AggFwdDesc(source=nat.SPP_AGG_DENSE if n_id is None else nat.SPP_AGG_TABLE, epilogue=epilogue,
-                           x_elem=nat.SPP_ELEM_FP8_E4M3, out_elem=_ELEM[out.dtype], rowptr_dev=_a(rowptr), col_dev=_a(col),
-                           num_targets=T, x_dev=_a(x.q), x_stride_elems=Fdim, x_rows=x.size(0), n_id_dev=_a(n_id), F=Fdim,
-                           out_dev=_a(out), out_stride_elems=0, self_scale=float(scale))
-        nat.check(nat.load().spp_agg_forward_fp8(C.byref(d), _a(x.scale_log2), st if st is not None else _stream()))
-        return
-    d = nat.AggFwdDesc(source=source, epilogue=epilogue, x_elem=_ELEM[x_dtype], out_elem=_ELEM[out.dtype],
-                       rowptr_dev=_a(rowptr), col_dev=_a(col), num_targets=T, x_dev=x, x_stride_elems=x_stride,
-                       x_rows=x_rows, n_id_dev=_a(n_id), F=Fdim, out_dev=_a(out), out_stride_elems=0,
-                       self_scale=float(scale), p=float(act[0]), training=int(act[1]), seed=int(act[2]) & (2 ** 64 - 1))
-    nat.check(nat.load().spp_agg_forward(C.byref(d), st if st is not None else _stream()))
+def _rows(x):
+    """The row-source fields of spp_agg_fwd_desc (include/spp.h) for x, and the fp8 column exponents (None for fp32 /
+    fp16 / bf16 rows).  x: a dense matrix or Fp8Features, a TableRows over either, a RowRefs, or what _SageStack.apply
+    receives in their place (the tuple (table, n_id), a _Refs)."""
+    if isinstance(x, _Refs):
+        x = x.r
+    if isinstance(x, RowRefs):                           # batch row j = the row at address addr[j]
+        return dict(source=nat.SPP_AGG_ROWS, x_elem=_ELEM[x.dtype], n_id_dev=_p(x.addr), F=x.width), None
+    n_id = exps = None
+    if isinstance(x, TableRows):                         # batch row j = table[n_id[j]]
+        x, n_id = x.table, x.n_id
+    elif isinstance(x, tuple):
+        x, n_id = x
+    if isinstance(x, Fp8Features):                       # one byte per element, the column scales applied on load
+        x, exps, elem = x.q, x.scale_log2, nat.SPP_ELEM_FP8_E4M3
+    else:
+        elem = _ELEM[x.dtype]
+    rows, Fdim = x.shape
+    return dict(source=nat.SPP_AGG_DENSE if n_id is None else nat.SPP_AGG_TABLE, x_elem=elem, x_dev=_p(x),
+                x_stride_elems=x.stride(0) if rows > 1 else Fdim, x_rows=rows if n_id is not None else 0,
+                n_id_dev=_p(n_id), F=Fdim), exps
 
 
-def _agg_backward(epilogue, rowptr, col, T, S, g, Fdim, grad_x, *, gather, z=None, scale=0.0, act=(0.0, 0, 0), st=None):
-    """spp_agg_backward: g [T, F or 2F] (unit column stride), grad_x [S, F] dense; the workspace is allocated here"""
+def _is_fp8(x):
+    """x is a dense Fp8Features, or a TableRows / (table, n_id) over one"""
+    if isinstance(x, TableRows):
+        x = x.table
+    elif isinstance(x, tuple):
+        x = x[0]
+    return isinstance(x, Fp8Features)
+
+
+def _agg_forward(epilogue, rowptr, col, T, x, out_dtype, *, scale=0.0, act=(0.0, 0, 0), st=None):
+    """spp_agg_forward (spp_agg_forward_fp8 for fp8 rows) over the row source x (see _rows): the new dense [T, F or 2F]
+    fp32 / bf16 result"""
+    src, exps = _rows(x)
+    width = src["F"] if epilogue in (nat.SPP_AGG_MEAN, nat.SPP_AGG_SUM) else 2 * src["F"]
+    out = torch.empty((T, width), dtype=out_dtype, device=rowptr.device)
+    d = nat.AggFwdDesc(epilogue=epilogue, out_elem=_ELEM[out_dtype], rowptr_dev=_p(rowptr), col_dev=_p(col),
+                       num_targets=T, out_dev=_p(out), out_stride_elems=0, self_scale=float(scale), p=float(act[0]),
+                       training=int(act[1]), seed=int(act[2]) & (2 ** 64 - 1), **src)
+    L = nat.load()
+    st = st if st is not None else _stream()
+    nat.check(L.spp_agg_forward(C.byref(d), st) if exps is None else L.spp_agg_forward_fp8(C.byref(d), _p(exps), st))
+    return out
+
+
+def _agg_backward(epilogue, rowptr, col, T, S, g, Fdim, out_dtype, *, gather, z=None, scale=0.0, act=(0.0, 0, 0),
+                  st=None):
+    """spp_agg_backward: g [T, F or 2F] (unit column stride) -> the new dense grad_x [S, F]; the workspace is allocated
+    here.  gather: over the transposed hop (built by the entry: count, scan, fill) instead of E x F fp32 atomics."""
     L = nat.load()
     E = col.numel()
+    grad_x = torch.empty((S, Fdim), dtype=out_dtype, device=g.device)
     if gather:
         nbytes = int(L.spp_sage_operand_backward_workspace_bytes(T, S, E))
     else:
-        nbytes = 4 * S * Fdim if grad_x.dtype != torch.float32 else 0
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=grad_x.device) if nbytes else None
+        nbytes = 4 * S * Fdim if out_dtype != torch.float32 else 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=g.device) if nbytes else None
     d = nat.AggBwdDesc(form=nat.SPP_AGG_GATHER if gather else nat.SPP_AGG_SCATTER, epilogue=epilogue,
-                       grad_elem=_ELEM[g.dtype], out_elem=_ELEM[grad_x.dtype],
-                       z_elem=_ELEM[z.dtype] if z is not None else nat.SPP_ELEM_F32, rowptr_dev=_a(rowptr),
-                       col_dev=_a(col), num_targets=T, num_sources=S, num_edges=E, grad_out_dev=_a(g),
-                       grad_out_stride_elems=g.stride(0) if T > 1 else 0, F=Fdim, grad_x_dev=_a(grad_x), z_dev=_a(z),
+                       grad_elem=_ELEM[g.dtype], out_elem=_ELEM[out_dtype],
+                       z_elem=_ELEM[z.dtype] if z is not None else nat.SPP_ELEM_F32, rowptr_dev=_p(rowptr),
+                       col_dev=_p(col), num_targets=T, num_sources=S, num_edges=E, grad_out_dev=_p(g),
+                       grad_out_stride_elems=g.stride(0) if T > 1 else 0, F=Fdim, grad_x_dev=_p(grad_x), z_dev=_p(z),
                        self_scale=float(scale), p=float(act[0]), training=int(act[1]), seed=int(act[2]) & (2 ** 64 - 1))
-    nat.check(L.spp_agg_backward(C.byref(d), _a(ws), nbytes, st if st is not None else _stream()))
-
-
-def _fp8_rows(x):
-    """(Fp8Features, n_id or None) when x is a dense Fp8Features or a TableRows over one, else None"""
-    if isinstance(x, Fp8Features):
-        return x, None
-    if isinstance(x, TableRows) and isinstance(x.table, Fp8Features):
-        return x.table, x.n_id
-    return None
+    nat.check(L.spp_agg_backward(C.byref(d), _p(ws), nbytes, st if st is not None else _stream()))
+    return grad_x
 
 
 def _no_input_grad(ctx, what):
@@ -117,89 +147,37 @@ class _MeanAggregate(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, rowptr, col, num_targets, concat_target):
-        L = nat.load()
         nat.require_device()
-        f8 = _fp8_rows(x)
-        if f8 is not None:
-            # fp8 rows read in place (the table with n_id, or dense rows): scales applied on load
+        assert x.is_cuda and _readable(x), "fp16 / fp32 / bf16 / fp8 rows on the GPU"
+        if _is_fp8(x):
             _no_input_grad(ctx, "mean_aggregate")
-            tb, n_id = f8
-            assert x.is_cuda
-            Fdim = tb.size(1)
-            ctx.amp = amp_bf16()
-            ctx.desc = True
-            out = torch.empty((num_targets, 2 * Fdim if concat_target else Fdim),
-                              dtype=torch.bfloat16 if ctx.amp else torch.float32, device=x.device)
-            epi = nat.SPP_AGG_OPERAND if concat_target else nat.SPP_AGG_MEAN
-            _agg_forward(epi, rowptr, col, num_targets, tb, None, Fdim, out, n_id=n_id)
-            ctx.save_for_backward(rowptr, col)
-            ctx.shape = (x.size(0), Fdim, num_targets, out.size(1))
-            ctx.in_dtype = torch.float32
-            ctx.concat = bool(concat_target)
-            return out
-        assert x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and x.dtype in _ELEM
-        Fdim = x.size(1)
-        width = 2 * Fdim if concat_target else Fdim
-        ctx.amp = amp_bf16()
-        ctx.desc = ctx.amp or x.dtype == torch.bfloat16           # bf16 in or out: the descriptor entry
-        out = torch.empty((num_targets, width), dtype=torch.bfloat16 if ctx.amp else torch.float32, device=x.device)
-        if ctx.desc:
-            _agg_forward(nat.SPP_AGG_OPERAND if concat_target else nat.SPP_AGG_MEAN, rowptr, col, num_targets,
-                         _a(x), x.dtype, Fdim, out, x_stride=x.stride(0) if x.size(0) > 1 else Fdim)
-        else:
-            fn = L.spp_sage_operand_forward if concat_target else L.spp_csr_mean_forward
-            nat.check(fn(_p(rowptr), _p(col), num_targets, _p(x), int(x.dtype == torch.float16),
-                         x.stride(0) if x.size(0) > 1 else Fdim, Fdim, _p(out), width, _stream()))
+        out = _agg_forward(nat.SPP_AGG_OPERAND if concat_target else nat.SPP_AGG_MEAN, rowptr, col, num_targets, x,
+                           torch.bfloat16 if amp_bf16() else torch.float32)
         ctx.save_for_backward(rowptr, col)
-        ctx.shape = (x.size(0), Fdim, num_targets, width)
+        ctx.shape = (x.size(0), x.size(1), num_targets)
         ctx.in_dtype = x.dtype
         ctx.concat = bool(concat_target)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
         rowptr, col = ctx.saved_tensors
-        S, Fdim, T, width = ctx.shape
-        grad_x = None
-        if ctx.needs_input_grad[0] and ctx.desc:
-            # bf16 / fp32 gradient in, the input's dtype out (fp16 through an fp32 buffer)
-            g = _grad_in(grad_out)
-            odt = ctx.in_dtype if ctx.in_dtype in (torch.float32, torch.bfloat16) else torch.float32
-            grad_x = torch.empty((S, Fdim), dtype=odt, device=g.device)
-            vec = Fdim % 4 == 0 and (T <= 1 or g.stride(0) % 4 == 0) and g.data_ptr() % (4 * g.element_size()) == 0
-            if ctx.concat and vec:
-                _agg_backward(nat.SPP_AGG_OPERAND, rowptr, col, T, S, g, Fdim, grad_x,
-                              gather=col.numel() * Fdim >= (1 << 22))
-            else:
-                _agg_backward(nat.SPP_AGG_MEAN, rowptr, col, T, S, g if not ctx.concat else g[:, :Fdim], Fdim, grad_x,
-                              gather=False)
-                if ctx.concat:
-                    grad_x[:T] += g[:, Fdim:].to(odt)
-            return grad_x.to(ctx.in_dtype), None, None, None, None
-        if ctx.needs_input_grad[0]:
-            g = grad_out if (grad_out.stride(1) == 1 and grad_out.dtype == torch.float32) else \
-                grad_out.contiguous().to(torch.float32)
-            L = nat.load()
-            go_stride = g.stride(0) if T > 1 else width
-            if ctx.concat and Fdim % 4 == 0 and go_stride % 4 == 0 and g.data_ptr() % 16 == 0:
-                grad_x = torch.empty((S, Fdim), dtype=torch.float32, device=g.device)
-                E = col.numel()
-                if E * Fdim >= (1 << 22):
-                    # gather over the transposed hop (built here: count, scan, fill) instead of E x F fp32 atomics
-                    nbytes = int(L.spp_sage_operand_backward_workspace_bytes(T, S, E))
-                    ws = torch.empty(nbytes, dtype=torch.uint8, device=g.device)
-                    nat.check(L.spp_sage_operand_backward_gather(_p(rowptr), _p(col), T, S, E, _p(g), go_stride, Fdim,
-                                                                 _p(grad_x), _p(ws), nbytes, _stream()))
-                else:
-                    nat.check(L.spp_sage_operand_backward(_p(rowptr), _p(col), T, S, _p(g), go_stride, Fdim,
-                                                          _p(grad_x), _stream()))
-            else:
-                grad_x = torch.zeros((S, Fdim), dtype=torch.float32, device=g.device)
-                nat.check(L.spp_csr_mean_backward(_p(rowptr), _p(col), T, _p(g), go_stride, Fdim, _p(grad_x), _stream()))
-                if ctx.concat:
-                    grad_x[:T] += g[:, Fdim:]
-            grad_x = grad_x.to(ctx.in_dtype)
-        return grad_x, None, None, None, None
+        S, Fdim, T = ctx.shape
+        # bf16 / fp32 gradient in, the input's dtype out (fp16 through an fp32 buffer)
+        g = _grad_in(grad_out)
+        odt = ctx.in_dtype if ctx.in_dtype in (torch.float32, torch.bfloat16) else torch.float32
+        vec = Fdim % 4 == 0 and (T <= 1 or g.stride(0) % 4 == 0) and g.data_ptr() % (4 * g.element_size()) == 0
+        if ctx.concat and vec:
+            grad_x = _agg_backward(nat.SPP_AGG_OPERAND, rowptr, col, T, S, g, Fdim, odt,
+                                   gather=col.numel() * Fdim >= (1 << 22))
+        else:
+            grad_x = _agg_backward(nat.SPP_AGG_MEAN, rowptr, col, T, S, g if not ctx.concat else g[:, :Fdim], Fdim, odt,
+                                   gather=False)
+            if ctx.concat:
+                grad_x[:T] += g[:, Fdim:].to(odt)
+        return grad_x.to(ctx.in_dtype), None, None, None, None
 
 
 class _ReluDropout(torch.autograd.Function):
@@ -303,7 +281,7 @@ class SAGEConv(torch.nn.Module):
     def forward(self, x_pair, adj_t):
         x, x_target = x_pair
         rowptr, col, _ = adj_t.csr()
-        if _fp8_rows(x) is not None:                     # fp8 rows, read in place: the targets are the first rows of x
+        if _is_fp8(x):                                   # fp8 rows, read in place: the targets are the first rows of x
             if x_target is not None and x_target is not x:
                 raise RuntimeError("SAGEConv over fp8 rows: the targets are the first rows of x (pass (x, None))")
             fused = _MeanAggregate.apply(x, rowptr, col, int(adj_t.sparse_sizes()[0]), True)
@@ -370,20 +348,6 @@ def _wgrad(g, a):
 
     bf16 g and a (autocast): every slab's product is accumulated in fp32 by the GEMM and rounded to bf16 once, the
     slabs are summed in fp32, and the result is fp32 (a weight gradient)."""
-    if g.dtype == torch.bfloat16:
-        return _wgrad_bf16(g, a)
-    T = a.size(0)
-    slabs = min(64, T // 2048)
-    if slabs < 2:
-        return g.t() @ a
-    c = T // slabs
-    acc = torch.bmm(a[:slabs * c].view(slabs, c, -1).transpose(1, 2), g[:slabs * c].view(slabs, c, -1)).sum(0)   # [K, N]
-    if slabs * c < T:      # the < `slabs` rows left over: accumulated in place (one launch; it was a product + an add)
-        acc.addmm_(a[slabs * c:].t(), g[slabs * c:])
-    return acc.t()
-
-
-def _wgrad_bf16(g, a):
     T = a.size(0)
     slabs = min(64, T // 2048)
     if slabs < 2:
@@ -391,8 +355,11 @@ def _wgrad_bf16(g, a):
     c = T // slabs
     acc = torch.bmm(a[:slabs * c].view(slabs, c, -1).transpose(1, 2), g[:slabs * c].view(slabs, c, -1)).sum(
         0, dtype=torch.float32)                                                                            # [K, N]
-    if slabs * c < T:
-        acc.add_(a[slabs * c:].t() @ g[slabs * c:])
+    if slabs * c < T:      # the < `slabs` rows left over
+        if g.dtype == torch.float32:
+            acc.addmm_(a[slabs * c:].t(), g[slabs * c:])   # accumulated in place (one launch; it was a product + an add)
+        else:
+            acc.add_(a[slabs * c:].t() @ g[slabs * c:])    # bf16: the product rounded once, like every slab's
     return acc.t()
 
 
@@ -415,14 +382,6 @@ def _tall_linear(a, w):
     four products is 0.1 ms less host time per step: resident step 1.010-1.015 -> 0.995-0.997 ms, with the data path
     1.140-1.156 -> 1.111-1.121 (tools/overlap_ab.py, SPP_SAGE_ONE_PRODUCT A/B of round 4)."""
     return torch.nn.functional.linear(a, w)
-
-
-class _Refs:
-    """RowRefs on their way through _SageStack.apply (a non-tensor argument)"""
-    __slots__ = ("r",)
-
-    def __init__(self, r):
-        self.r = r
 
 
 def _readable(x):
@@ -457,173 +416,60 @@ class _SageStack(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, hops, training, p, *weights):
-        if isinstance(x, Fp8Features) or (isinstance(x, tuple) and isinstance(x[0], Fp8Features)):
+        """x: a feature matrix or Fp8Features, the (table, n_id) of a TableRows, or a _Refs.  Under bf16 autocast the
+        operands A [T, 2K], [W_l | W_r] (cast once per layer, in the one copy) and the pre-activations Z are bf16, else
+        fp32; log_softmax is fp32 in both."""
+        if _is_fp8(x):
             _no_input_grad(ctx, "SAGE")
-        ctx.amp = amp_bf16()
-        if ctx.amp:
-            return _SageStack._forward_bf16(ctx, x, hops, training, p, *weights)
-        with _no_autocast():
-            return _SageStack._forward(ctx, x, hops, training, p, *weights)
-
-    @staticmethod
-    def _forward(ctx, x, hops, training, p, *weights):
-        L = nat.load()
         nat.require_device()
-        n_layers = len(hops)
+        ctx.amp = amp_bf16()
+        dt = torch.bfloat16 if ctx.amp else torch.float32
         st = _stream()
-        n_id = refs = None
-        if isinstance(x, tuple):                         # (table, n_id) of a TableRows: batch row j = table[n_id[j]]
-            x, n_id = x
-        elif isinstance(x, _Refs):                       # RowRefs: batch row j = the row at address addr[j]
-            refs = x.r
-            x = refs.addr
-        h = x
+        n_layers = len(hops)
         operands, acts, wcats, seeds = [], [], [], []
-        for i, (rowptr, col, T) in enumerate(hops):
-            K = refs.width if (i == 0 and refs is not None) else h.size(1)
-            A = torch.empty((T, 2 * K), dtype=torch.float32, device=x.device)
-            if i == 0 and isinstance(h, Fp8Features):    # fp8 rows (the table with n_id, or dense): scales applied on load
-                _agg_forward(nat.SPP_AGG_OPERAND, rowptr, col, T, h, None, K, A, n_id=n_id, st=st)
-            elif i == 0 and refs is not None:
-                nat.check(L.spp_sage_operand_forward_rows(_p(rowptr), _p(col), T, _p(refs.addr), int(refs.dtype == torch.float16),
-                                                          K, _p(A), 2 * K, st))
-            elif i == 0 and n_id is not None:
-                nat.check(L.spp_sage_operand_forward_table(_p(rowptr), _p(col), T, _p(h), int(h.dtype == torch.float16),
-                                                           h.stride(0) if h.size(0) > 1 else K, h.size(0), _p(n_id), K,
-                                                           _p(A), 2 * K, st))
-            elif i == 0:
-                nat.check(L.spp_sage_operand_forward(_p(rowptr), _p(col), T, _p(h), int(h.dtype == torch.float16),
-                                                     h.stride(0) if h.size(0) > 1 else K, K, _p(A), 2 * K, st))
-            else:
-                # h is the previous layer's PRE-activation: ReLU + dropout are applied to its rows as they are
-                # loaded (no separate pass over the activation, which is never materialised)
-                nat.check(L.spp_sage_operand_forward_act(_p(rowptr), _p(col), T, _p(h), K, _p(A), 2 * K, float(p),
-                                                         int(bool(training)), seeds[i - 1], st))
-            W = torch.cat([weights[2 * i], weights[2 * i + 1]], dim=1)          # [N, 2K] = [W_l | W_r]
-            Z = _tall_linear(A, W)
-            operands.append(A)
-            wcats.append(W)
-            if i != n_layers - 1:
-                seeds.append(int(torch.empty((), dtype=torch.int64).random_().item()) if training else 0)
-                acts.append(Z)                                                  # the pre-activation
-                h = Z
-            else:
-                out = torch.log_softmax(Z, dim=-1)
+        with _no_autocast():
+            for i, (rowptr, col, T) in enumerate(hops):
+                if i == 0:
+                    A = _agg_forward(nat.SPP_AGG_OPERAND, rowptr, col, T, x, dt, st=st)
+                else:
+                    # Z is the previous layer's PRE-activation: ReLU + dropout are applied to its rows as they are
+                    # loaded (no separate pass over the activation, which is never materialised)
+                    A = _agg_forward(nat.SPP_AGG_OPERAND_ACT, rowptr, col, T, Z, dt, act=(p, bool(training), seeds[i - 1]),
+                                     st=st)
+                wl, wr = weights[2 * i], weights[2 * i + 1]
+                W = torch.cat([wl, wr], dim=1, out=torch.empty((wl.size(0), A.size(1)), dtype=dt, device=A.device))
+                Z = _tall_linear(A, W)                                          # W: [N, 2K] = [W_l | W_r]
+                operands.append(A)
+                wcats.append(W)
+                if i != n_layers - 1:
+                    seeds.append(int(torch.empty((), dtype=torch.int64).random_().item()) if training else 0)
+                    acts.append(Z)                                              # the pre-activation
+            out = torch.log_softmax(Z, dim=-1, dtype=torch.float32)
         # tensors through save_for_backward (saved-tensor hooks, in-place version checks, a second backward with
         # retain_graph all behave as autograd users expect); only ints and seeds live on ctx
         hop_t = [t for (rowptr, col, _T) in hops for t in (rowptr, col)]
         ctx.save_for_backward(*operands, *acts, *wcats, out, *hop_t)
         ctx.hop_T = [int(T) for (_r, _c, T) in hops]
         ctx.act = (float(p), int(bool(training)), seeds)
-        ctx.src_rows = [(x.numel() if refs is not None else x.size(0)) if n_id is None else n_id.numel()] + [a.size(0) for a in acts]
-        return out
-
-    @staticmethod
-    def _forward_bf16(ctx, x, hops, training, p, *weights):
-        """the same stack under bf16 autocast: bf16 operands A [T, 2K], bf16 [W_l | W_r] (cast once per layer), bf16
-        pre-activations Z, activation on load from the bf16 Z; log_softmax in fp32"""
-        nat.require_device()
-        st = _stream()
-        n_layers = len(hops)
-        n_id = refs = None
-        if isinstance(x, tuple):
-            x, n_id = x
-        elif isinstance(x, _Refs):
-            refs = x.r
-            x = refs.addr
-        h = x
-        operands, acts, wcats, seeds = [], [], [], []
-        with _no_autocast():
-            for i, (rowptr, col, T) in enumerate(hops):
-                K = refs.width if (i == 0 and refs is not None) else h.size(1)
-                A = torch.empty((T, 2 * K), dtype=torch.bfloat16, device=x.device)
-                if i == 0 and isinstance(h, Fp8Features):
-                    _agg_forward(nat.SPP_AGG_OPERAND, rowptr, col, T, h, None, K, A, n_id=n_id, st=st)
-                elif i == 0 and refs is not None:
-                    _agg_forward(nat.SPP_AGG_OPERAND, rowptr, col, T, None, refs.dtype, K, A, source=nat.SPP_AGG_ROWS,
-                                 n_id=refs.addr, st=st)
-                elif i == 0 and n_id is not None:
-                    _agg_forward(nat.SPP_AGG_OPERAND, rowptr, col, T, _a(h), h.dtype, K, A, source=nat.SPP_AGG_TABLE,
-                                 x_stride=h.stride(0) if h.size(0) > 1 else K, n_id=n_id, x_rows=h.size(0), st=st)
-                elif i == 0:
-                    _agg_forward(nat.SPP_AGG_OPERAND, rowptr, col, T, _a(h), h.dtype, K, A,
-                                 x_stride=h.stride(0) if h.size(0) > 1 else K, st=st)
-                else:
-                    _agg_forward(nat.SPP_AGG_OPERAND_ACT, rowptr, col, T, _a(h), h.dtype, K, A, x_stride=K,
-                                 act=(p, bool(training), seeds[i - 1]), st=st)
-                wl, wr = weights[2 * i], weights[2 * i + 1]
-                W = torch.empty((wl.size(0), 2 * K), dtype=torch.bfloat16, device=x.device)
-                torch.cat([wl, wr], dim=1, out=W)                                  # [N, 2K], cast in the one copy
-                Z = _tall_linear(A, W)                                                            # bf16, fp32 accumulation
-                operands.append(A)
-                wcats.append(W)
-                if i != n_layers - 1:
-                    seeds.append(int(torch.empty((), dtype=torch.int64).random_().item()) if training else 0)
-                    acts.append(Z)
-                    h = Z
-                else:
-                    out = torch.log_softmax(Z, dim=-1, dtype=torch.float32)
-        hop_t = [t for (rowptr, col, _T) in hops for t in (rowptr, col)]
-        ctx.save_for_backward(*operands, *acts, *wcats, out, *hop_t)
-        ctx.hop_T = [int(T) for (_r, _c, T) in hops]
-        ctx.act = (float(p), int(bool(training)), seeds)
-        ctx.src_rows = [(x.numel() if refs is not None else x.size(0)) if n_id is None else n_id.numel()] + [a.size(0) for a in acts]
+        batch_rows = x[1].numel() if isinstance(x, tuple) else x.r.size(0) if isinstance(x, _Refs) else x.size(0)
+        ctx.src_rows = [batch_rows] + [a.size(0) for a in acts]
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_out):
-        if ctx.amp:
-            return _SageStack._backward_bf16(ctx, g_out)
-        L = nat.load()
         st = _stream()
+        dt = torch.bfloat16 if ctx.amp else torch.float32
         n_layers = len(ctx.hop_T)
         sv = ctx.saved_tensors
         operands, acts = sv[:n_layers], sv[n_layers:2 * n_layers - 1]
         wcats, out = sv[2 * n_layers - 1:3 * n_layers - 1], sv[3 * n_layers - 1]
         hop_t = sv[3 * n_layers:]
         hops = [(hop_t[2 * i], hop_t[2 * i + 1], ctx.hop_T[i]) for i in range(n_layers)]
-        gZ = torch._log_softmax_backward_data(g_out.contiguous(), out, -1, out.dtype)
+        p_, training_, seeds = ctx.act
         grads = [None] * (2 * n_layers)
-        for i in range(n_layers - 1, -1, -1):
-            A, W = operands[i], wcats[i]
-            K = A.size(1) // 2
-            gW = _wgrad(gZ, A)
-            grads[2 * i], grads[2 * i + 1] = _split_wgrad(gW)
-            if i == 0:
-                break
-            rowptr, col, T = hops[i]
-            S = ctx.src_rows[i]
-            gA = gZ @ W                                                         # [T, 2K]
-            gH = torch.empty((S, K), dtype=torch.float32, device=gA.device)
-            E = col.numel()
-            p_, training_, seeds = ctx.act
-            if E * K >= (1 << 22):
-                # gather over the transposed hop, with the ReLU + dropout backward applied before the row is stored
-                nbytes = int(L.spp_sage_operand_backward_workspace_bytes(T, S, E))
-                ws = torch.empty(nbytes, dtype=torch.uint8, device=gA.device)
-                nat.check(L.spp_sage_operand_backward_gather_act(_p(rowptr), _p(col), T, S, E, _p(gA), 2 * K, K, _p(gH),
-                                                                 _p(ws), nbytes, _p(acts[i - 1]), p_, training_,
-                                                                 seeds[i - 1], st))
-            else:
-                nat.check(L.spp_sage_operand_backward(_p(rowptr), _p(col), T, S, _p(gA), 2 * K, K, _p(gH), st))
-                nat.check(L.spp_relu_dropout_backward_pre(_p(gH), _p(acts[i - 1]), gH.numel(), p_, training_,
-                                                          seeds[i - 1], _p(gH), st))
-            gZ = gH
-        return (None, None, None, None, *grads)
-
-    @staticmethod
-    def _backward_bf16(ctx, g_out):
-        st = _stream()
-        n_layers = len(ctx.hop_T)
-        sv = ctx.saved_tensors
-        operands, acts = sv[:n_layers], sv[n_layers:2 * n_layers - 1]
-        wcats, out = sv[2 * n_layers - 1:3 * n_layers - 1], sv[3 * n_layers - 1]
-        hop_t = sv[3 * n_layers:]
-        hops = [(hop_t[2 * i], hop_t[2 * i + 1], ctx.hop_T[i]) for i in range(n_layers)]
         with _no_autocast():
-            gZ = torch._log_softmax_backward_data(g_out.float().contiguous(), out, -1, torch.float32).to(torch.bfloat16)
-            grads = [None] * (2 * n_layers)
+            gZ = torch._log_softmax_backward_data(g_out.float().contiguous(), out, -1, torch.float32).to(dt)
             for i in range(n_layers - 1, -1, -1):
                 A, W = operands[i], wcats[i]
                 K = A.size(1) // 2
@@ -632,13 +478,12 @@ class _SageStack(torch.autograd.Function):
                 if i == 0:
                     break
                 rowptr, col, T = hops[i]
-                S = ctx.src_rows[i]
-                gA = gZ @ W                                                     # [T, 2K] bf16
-                gH = torch.empty((S, K), dtype=torch.bfloat16, device=gA.device)
-                p_, training_, seeds = ctx.act
-                _agg_backward(nat.SPP_AGG_OPERAND_ACT, rowptr, col, T, S, gA, K, gH, gather=col.numel() * K >= (1 << 22),
-                              z=acts[i - 1], act=(p_, training_, seeds[i - 1]), st=st)
-                gZ = gH
+                gA = gZ @ W                                                     # [T, 2K]
+                # the input gradient with the ReLU + dropout backward applied before the row is stored: by gather over
+                # the transposed hop, or (small hops) k_grad_init, the scatter and k_relu_dropout_bwd_pre
+                gZ = _agg_backward(nat.SPP_AGG_OPERAND_ACT, rowptr, col, T, ctx.src_rows[i], gA, K, dt,
+                                   gather=col.numel() * K >= (1 << 22), z=acts[i - 1],
+                                   act=(p_, training_, seeds[i - 1]), st=st)
         return (None, None, None, None, *grads)
 
 
@@ -659,7 +504,7 @@ class _GatAggregate(torch.autograd.Function):
         rmax = torch.empty(T, dtype=torch.float32, device=h.device)
         rsum = torch.empty(T, dtype=torch.float32, device=h.device)
         nat.check(L.spp_gat_forward(_p(rowptr), _p(col), T, _p(h), Fdim, _p(a_src), _p(a_dst), float(slope), _p(out),
-                                    _p(rmax), _p(rsum), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                                    _p(rmax), _p(rsum), _stream()))
         ctx.save_for_backward(h, a_src, a_dst, rowptr, col, out, rmax, rsum)
         ctx.slope = float(slope)
         return out
@@ -674,7 +519,7 @@ class _GatAggregate(torch.autograd.Function):
         grad_ad = torch.zeros_like(a_dst)
         nat.check(nat.load().spp_gat_backward(_p(rowptr), _p(col), T, _p(h), Fdim, _p(a_src), _p(a_dst), ctx.slope,
                                               _p(out), _p(rmax), _p(rsum), _p(g), _p(grad_h), _p(grad_as), _p(grad_ad),
-                                              C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                                              _stream()))
         return grad_h, grad_as, grad_ad, None, None, None
 
 
@@ -1025,48 +870,19 @@ class _SumAggregate(torch.autograd.Function):
     """out[t] = s * x[t] + sum_{e in row t} x[col[e]]  (fp32 [T, F]; targets are the first T rows of x).
 
     ``x`` is a feature matrix (fp16 / fp32 / bf16, any row stride), a TableRows or a RowRefs: the latter two are read in
-    place (spp_csr_sum_forward_table / _rows) and get no gradient.  With s == 0 the targets' rows are not read.
+    place (spp_agg_forward's SPP_AGG_TABLE / SPP_AGG_ROWS sources) and get no gradient.  With s == 0 the targets' rows are not read.
     Under bf16 autocast the result is bf16 (fp32 sums, rounded once)."""
 
     @staticmethod
     def forward(ctx, x, rowptr, col, num_targets, scale):
-        L = nat.load()
         nat.require_device()
-        st = _stream()
         S, Fdim = x.size(0), x.size(1)
-        assert x.is_cuda and rowptr.is_cuda and col.is_cuda and _readable(x), "fp16 / fp32 / bf16 rows on the GPU"
+        assert x.is_cuda and rowptr.is_cuda and col.is_cuda and _readable(x), "fp16 / fp32 / bf16 / fp8 rows on the GPU"
         assert num_targets <= S or scale == 0.0, "the targets are the first rows of the sources"
-        ctx.amp = amp_bf16()
-        ctx.desc = ctx.amp or x.dtype == torch.bfloat16           # bf16 in or out: the descriptor entry
-        out = torch.empty((num_targets, Fdim), dtype=torch.bfloat16 if ctx.amp else torch.float32, device=x.device)
-        half = int(x.dtype == torch.float16)
-        f8 = _fp8_rows(x)
-        if f8 is not None:                                        # fp8 rows read in place, scales applied on load
+        if _is_fp8(x):
             _no_input_grad(ctx, "sum_aggregate")
-            _agg_forward(nat.SPP_AGG_SUM, rowptr, col, num_targets, f8[0], None, Fdim, out, n_id=f8[1], scale=scale, st=st)
-        elif ctx.desc:
-            if isinstance(x, TableRows):
-                tb = x.table
-                _agg_forward(nat.SPP_AGG_SUM, rowptr, col, num_targets, _a(tb), tb.dtype, Fdim, out,
-                             source=nat.SPP_AGG_TABLE, x_stride=tb.stride(0) if tb.size(0) > 1 else Fdim, n_id=x.n_id,
-                             x_rows=tb.size(0), scale=scale, st=st)
-            elif isinstance(x, RowRefs):
-                _agg_forward(nat.SPP_AGG_SUM, rowptr, col, num_targets, None, x.dtype, Fdim, out, source=nat.SPP_AGG_ROWS,
-                             n_id=x.addr, scale=scale, st=st)
-            else:
-                _agg_forward(nat.SPP_AGG_SUM, rowptr, col, num_targets, _a(x), x.dtype, Fdim, out,
-                             x_stride=x.stride(0) if S > 1 else Fdim, scale=scale, st=st)
-        elif isinstance(x, TableRows):
-            tb = x.table
-            nat.check(L.spp_csr_sum_forward_table(_p(rowptr), _p(col), num_targets, _p(tb), half,
-                                                  tb.stride(0) if tb.size(0) > 1 else Fdim, tb.size(0), _p(x.n_id), Fdim,
-                                                  float(scale), _p(out), Fdim, st))
-        elif isinstance(x, RowRefs):
-            nat.check(L.spp_csr_sum_forward_rows(_p(rowptr), _p(col), num_targets, _p(x.addr), half, Fdim, float(scale),
-                                                 _p(out), Fdim, st))
-        else:
-            nat.check(L.spp_csr_sum_forward(_p(rowptr), _p(col), num_targets, _p(x), half,
-                                            x.stride(0) if S > 1 else Fdim, Fdim, float(scale), _p(out), Fdim, st))
+        out = _agg_forward(nat.SPP_AGG_SUM, rowptr, col, num_targets, x, torch.bfloat16 if amp_bf16() else torch.float32,
+                           scale=scale)
         ctx.save_for_backward(rowptr, col)
         ctx.shape = (S, Fdim, num_targets)
         ctx.scale = float(scale)
@@ -1079,28 +895,10 @@ class _SumAggregate(torch.autograd.Function):
             return None, None, None, None, None
         rowptr, col = ctx.saved_tensors
         S, Fdim, T = ctx.shape
-        if ctx.desc:
-            g = _grad_in(grad_out)
-            odt = ctx.in_dtype if ctx.in_dtype in (torch.float32, torch.bfloat16) else torch.float32
-            grad_x = torch.empty((S, Fdim), dtype=odt, device=g.device)
-            _agg_backward(nat.SPP_AGG_SUM, rowptr, col, T, S, g, Fdim, grad_x,
-                          gather=col.numel() * Fdim >= _SUM_GATHER_MIN_WORK, scale=ctx.scale)
-            return grad_x.to(ctx.in_dtype), None, None, None, None
-        L = nat.load()
-        g = grad_out if (grad_out.stride(1) == 1 and grad_out.dtype == torch.float32) else \
-            grad_out.contiguous().to(torch.float32)
-        go_stride = g.stride(0) if T > 1 else Fdim
-        grad_x = torch.empty((S, Fdim), dtype=torch.float32, device=g.device)
-        E = col.numel()
-        if E * Fdim >= _SUM_GATHER_MIN_WORK:
-            # gather over the transposed hop (the mean's transposition and workspace) instead of E x F fp32 atomics
-            nbytes = int(L.spp_sage_operand_backward_workspace_bytes(T, S, E))
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=g.device)
-            nat.check(L.spp_csr_sum_backward_gather(_p(rowptr), _p(col), T, S, E, _p(g), go_stride, Fdim, ctx.scale,
-                                                    _p(grad_x), _p(ws), nbytes, _stream()))
-        else:
-            nat.check(L.spp_csr_sum_backward(_p(rowptr), _p(col), T, S, _p(g), go_stride, Fdim, ctx.scale, _p(grad_x),
-                                             _stream()))
+        # bf16 / fp32 gradient in, the input's dtype out (fp16 through an fp32 buffer)
+        odt = ctx.in_dtype if ctx.in_dtype in (torch.float32, torch.bfloat16) else torch.float32
+        grad_x = _agg_backward(nat.SPP_AGG_SUM, rowptr, col, T, S, _grad_in(grad_out), Fdim, odt,
+                               gather=col.numel() * Fdim >= _SUM_GATHER_MIN_WORK, scale=ctx.scale)
         return grad_x.to(ctx.in_dtype), None, None, None, None
 
 

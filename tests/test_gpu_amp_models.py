@@ -231,3 +231,96 @@ def test_end_to_end_training_learns_under_bf16_autocast():
             hit += int((pred == b.y.reshape(-1)).sum())
             tot += pred.numel()
     assert tot == test.numel() and hit / tot > 0.6, hit / tot        # chance is 0.25
+
+
+# ---- one call path: every aggregation of SAGE, GIN and SAGEResInception goes through the descriptor entries ----
+_AGG_ALLOWED = {"spp_agg_forward", "spp_agg_forward_fp8", "spp_agg_backward", "spp_sage_operand_backward_workspace_bytes"}
+_AGG_PREFIXES = ("spp_agg_", "spp_csr_mean_", "spp_csr_sum_", "spp_sage_operand_", "spp_relu_dropout_backward_pre")
+# (last hop's targets, maxdeg, sources of the last hop, sources of the first hop): the small chain is far below the
+# gather threshold E * 256 >= 1 << 22 of the hidden layer's hop, the large one above it (about 24 k edges: 6.1 M)
+_CHAINS = {"small": (64, 5, 200, 500), "large": (3000, 16, 3500, 6000)}
+
+
+class _Recorder:
+    """the native library with every entry's name noted as it is called (spp_agg_backward: with the descriptor's form)"""
+
+    def __init__(self, lib):
+        self._lib, self.names, self.forms = lib, set(), set()
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+
+        def call(*args):
+            self.names.add(name)
+            if name == "spp_agg_backward":
+                self.forms.add(args[0]._obj.form)
+            return fn(*args)
+        return call
+
+
+def _chain(which):
+    """a 2-hop MFG chain (outermost hop first) with fp32 features [S0, 128] and labels for the last hop's targets"""
+    from salient_plusplus_amd.fast_trainer.monkeypatch import SparseTensor
+    T, maxdeg, S1, S0 = _CHAINS[which]
+    g = torch.Generator().manual_seed(T)
+    adjs = []
+    for S, Th in ((S0, S1), (S1, T)):
+        deg = torch.randint(0, maxdeg + 1, (Th,), generator=g)
+        rowptr = torch.zeros(Th + 1, dtype=torch.int64)
+        rowptr[1:] = torch.cumsum(deg, 0)
+        col = torch.randint(0, S, (int(rowptr[-1]),), generator=g)
+        adjs.append((SparseTensor(rowptr=rowptr.cuda(), col=col.cuda(), sparse_sizes=(Th, S)), None, (S, Th)))
+    x = torch.randn((S0, 128), generator=g).cuda()
+    y = torch.randint(0, 10, (T,), generator=g).cuda()
+    return x, adjs, y
+
+
+@pytest.mark.parametrize("which", ["small", "large"])
+def test_every_aggregation_goes_through_the_descriptor_entries(which, monkeypatch):
+    """One seeded training step of SAGE, GIN and SAGEResInception (2 layers, hidden 256) on fp32 rows, fp16 rows, under
+    bf16 autocast and (SAGE, GIN) over a TableRows: no positional aggregation entry is called, SAGE's backward takes the
+    scatter form on the small chain and the gather form on the large one, and on both sides of that threshold the fp32
+    SAGE equals its plain-torch restatement (eval mode) within test_sage_matches_plain_torch_on_a_sampled_batch's
+    tolerances."""
+    import bench
+    from salient_plusplus_amd import _native as nat
+    from salient_plusplus_amd import models
+    from salient_plusplus_amd.fast_sampler import TableRows
+    x, adjs, y = _chain(which)
+    E = adjs[1][0].csr()[1].numel()
+    assert (E * 256 >= 1 << 22) == (which == "large"), E
+    table = torch.randn((2 * x.size(0), 128), generator=torch.Generator().manual_seed(5)).cuda()
+    n_id = torch.randint(0, table.size(0), (x.size(0),), generator=torch.Generator().manual_seed(6)).cuda()
+    rec = _Recorder(nat.load())
+    monkeypatch.setattr(models.nat, "load", lambda: rec)
+    forms = {}
+    for kind in ("sage", "gin", "sageresinception"):
+        torch.manual_seed(7)
+        model = models.get_model_type(kind)(128, 256, 10, 2).cuda().train()
+        runs = [(x, None), (x.half(), None), (x, _bf16())]
+        if kind != "sageresinception":
+            runs.append((TableRows(table, n_id), None))
+        for rows, amp in runs:
+            torch.manual_seed(8)
+            out, grads = _run(model, rows, adjs, y, amp)
+            assert torch.isfinite(out).all() and all(torch.isfinite(g).all() for g in grads.values())
+        forms[kind], rec.forms = rec.forms, set()
+    agg = {n for n in rec.names if n.startswith(_AGG_PREFIXES)}
+    assert {"spp_agg_forward", "spp_agg_backward"} <= agg <= _AGG_ALLOWED, sorted(agg - _AGG_ALLOWED)
+    want_form = nat.SPP_AGG_GATHER if which == "large" else nat.SPP_AGG_SCATTER
+    assert forms["sage"] == {want_form} and forms["gin"] == {want_form}, forms
+    # the fp32 stack against plain torch ops on the same weights
+    torch.manual_seed(0)
+    hip = models.SAGE(128, 256, 10, 2).cuda().eval()
+    ref = bench.TorchSAGE(128, 256, 10, 2).cuda().eval()
+    for i in range(2):
+        ref.lin_l[i].weight.data.copy_(hip.convs[i].lin_l.weight.data)
+        ref.lin_r[i].weight.data.copy_(hip.convs[i].lin_r.weight.data)
+    out_h, out_r = hip(x, adjs), ref(x, adjs)
+    torch.testing.assert_close(out_h, out_r, rtol=1e-4, atol=1e-5)
+    F.nll_loss(out_h, y).backward()
+    F.nll_loss(out_r, y).backward()
+    assert rec.forms == {want_form}
+    for i in range(2):
+        torch.testing.assert_close(hip.convs[i].lin_l.weight.grad, ref.lin_l[i].weight.grad, rtol=1e-3, atol=1e-6)
+        torch.testing.assert_close(hip.convs[i].lin_r.weight.grad, ref.lin_r[i].weight.grad, rtol=1e-3, atol=1e-6)
