@@ -558,6 +558,13 @@ spp_status spp_vip_frequencies(const int64_t* rowptr_dev, const int64_t* col_dev
  *                 half of the [T, 2F] operand of one fused lin_l|lin_r GEMM
  *       backward: grad_x[col[e],:] += grad_out[t,:] / deg t  (grad_x [S,F] fp32, zeroed by the
  *                 caller; hardware fp32 atomics, so the summation order is not fixed)
+ *
+ *     Every entry of this block and of the sum block below except spp_csr_mean_backward (the bare scatter step, which
+ *     adds), spp_relu_dropout_* (element-wise) and the GAT entries is a FIXED-TYPE SPELLING of the descriptor entries
+ *     spp_agg_forward / spp_agg_backward further down: fp32 out / grad / z, x fp32 or fp16 by the `*_is_half` flag
+ *     (any non-zero value = fp16), source / epilogue / form as the name says.  It fills a descriptor and shares the
+ *     descriptor path's validation, defaults and launch; errors name the entry that was called.  What an entry asks
+ *     beyond the descriptor is said at its declaration.
  * ------------------------------------------------------------------------- */
 spp_status spp_csr_mean_forward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
                                 const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t F,
@@ -567,7 +574,9 @@ spp_status spp_csr_mean_backward(const int64_t* rowptr_dev, const int64_t* col_d
                                  float* grad_x_dev, void* stream);
 /* The fused operand of SAGEConv, [mean_j x_j | x_target] (fp32 [T, 2F], one GEMM with [W_l | W_r] then
  * replaces lin_l(mean) + lin_r(x_target)): the targets are the first T rows of x (the MFG contract,
- * driver/models.py:44-45 `x_target = x[:size[1]]`), converted to fp32 in the same pass. */
+ * driver/models.py:44-45 `x_target = x[:size[1]]`), converted to fp32 in the same pass.  The operand entries take an
+ * explicit out_stride_elems >= 2F (their backwards an explicit grad_out_stride_elems >= 2F): 0 is refused, where the
+ * descriptor reads it as dense. */
 spp_status spp_sage_operand_forward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
                                     const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t F,
                                     float* out_dev, int64_t out_stride_elems /* >= 2F */, void* stream);
@@ -582,8 +591,9 @@ spp_status spp_sage_operand_forward_table(const int64_t* rowptr_dev, const int64
                                           int64_t table_rows, const int64_t* n_id_dev, int64_t F, float* out_dev,
                                           int64_t out_stride_elems /* >= 2F */, void* stream);
 /* The same operand from ROW REFERENCES (spp_mfg_out.row_addr): row j of the batch is the F elements at device
- * address row_addr_dev[j] (fp16 or fp32; 8-byte aligned fp16 / 16-byte aligned fp32 rows when F % 4 == 0).  Same rows,
- * same summation order as spp_sage_operand_forward over the assembled x: the operand is bit-identical. */
+ * address row_addr_dev[j] (fp16 or fp32; 8-byte aligned fp16 / 16-byte aligned fp32 rows).  Same rows, same summation
+ * order as spp_sage_operand_forward over the assembled x: the operand is bit-identical.  This entry has the vector form
+ * only: F % 4 == 0, out_dev 16-byte aligned, out_stride_elems % 4 == 0 (the descriptor's SPP_AGG_ROWS takes any F). */
 spp_status spp_sage_operand_forward_rows(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
                                          const int64_t* row_addr_dev, int32_t rows_are_half, int64_t F, float* out_dev,
                                          int64_t out_stride_elems /* >= 2F */, void* stream);

@@ -497,109 +497,16 @@ static void with_f32_bf16(int32_t elem, Fn&& fn) {
 }
 static bool elem_ok(int32_t elem) { return elem == SPP_ELEM_F32 || elem == SPP_ELEM_F16 || elem == SPP_ELEM_BF16; }
 static bool f32_bf16_ok(int32_t elem) { return elem == SPP_ELEM_F32 || elem == SPP_ELEM_BF16; }
-static int64_t elem_bytes(int32_t elem) { return elem == SPP_ELEM_F32 ? 4 : 2; }
+static int64_t elem_bytes(int32_t elem) { return elem == SPP_ELEM_F32 ? 4 : elem == SPP_ELEM_FP8_E4M3 ? 1 : 2; }
+static bool aligned_to(const void* p, int64_t bytes) { return reinterpret_cast<uintptr_t>(p) % (uintptr_t)bytes == 0; }
 
 }  // namespace spp
 
 using namespace spp;
 
-// ---- one launcher per kernel ----
-template <typename Tin, typename Tout, bool VEC4, class Src, class Epi>
-static void launch_agg_fwd(const int64_t* rowptr, const int64_t* col, int64_t T, const void* x, int64_t x_stride,
-                           const int64_t* nid, int64_t x_rows, int64_t F, Epi epi, void* out, int64_t out_stride,
-                           void* stream) {
-  const int lpr_log2 = lanes_log2(VEC4 ? F / 4 : F);
-  const unsigned grid = (unsigned)ceil_div(T << lpr_log2, kAggNT);
-  hipLaunchKernelGGL((k_agg_fwd<Tin, Tout, VEC4, Src, Epi>), dim3(grid), dim3(kAggNT), 0, as_stream(stream), rowptr, col,
-                     T, static_cast<const Tin*>(x), x_stride, F, lpr_log2, static_cast<Tout*>(out), out_stride, epi, nid,
-                     x_rows);
-}
-
-template <class Epi, typename Tg>
-static void launch_agg_bwd_scatter(const int64_t* rowptr, const int64_t* col, int64_t T, const Tg* grad_out,
-                                   int64_t go_stride, int64_t F, float* grad_x, hipStream_t st) {
-  const int lpr_log2 = lanes_log2(F);
-  const unsigned grid = (unsigned)ceil_div(T << lpr_log2, kAggNT);
-  hipLaunchKernelGGL((k_agg_bwd_scatter<Epi, Tg>), dim3(grid), dim3(kAggNT), 0, st, rowptr, col, T, grad_out, go_stride,
-                     F, lpr_log2, grad_x);
-}
-
-// The forward entries' shared validation (`who` names the entry in the errors), the vector-width test and the launch.
-// Src: Dense (x = the batch's matrix), Table (x = the resident table, nid = the batch's n_id, x_rows its rows) or Refs
-// (nid = the row addresses; x, x_stride unused).  The sum entries have their row source's buffers checked here, the
-// mean entries check theirs themselves.  x_elem: fp32 / fp16 / bf16 rows; out_elem: fp32 / bf16 (both checked by the caller).
-template <class Src, class Epi>
-static spp_status agg_forward(const char* who, const int64_t* rowptr, const int64_t* col, int64_t T, const void* x,
-                              int32_t x_elem, int64_t x_stride, const int64_t* nid, int64_t x_rows, int64_t F,
-                              Epi epi, void* out, int32_t out_elem, int64_t out_stride, void* stream) {
-  constexpr bool kRefs = std::is_same<Src, Refs>::value;
-  SPP_REQUIRE(T >= 0 && F >= 0, "%s: negative size", who);
-  if (T == 0 || F == 0) return SPP_OK;
-  SPP_REQUIRE(rowptr && out && (!Epi::kSum || (kRefs ? nid != nullptr : x && (x_rows == 0 || nid))), "%s: NULL buffer",
-              who);
-  SPP_REQUIRE(kRefs || x_stride >= F, "%s: row stride smaller than the row", who);
-  if (out_stride <= 0) out_stride = F;
-  SPP_REQUIRE(out_stride >= F, "%s: output stride smaller than the row", who);
-  const int64_t esz = elem_bytes(x_elem), osz = elem_bytes(out_elem);
-  // row references: 8-byte aligned fp16 / bf16 / 16-byte aligned fp32 rows when F % 4 == 0 (spp_mfg_out.row_addr)
-  const bool vec = (F % 4 == 0) && (reinterpret_cast<uintptr_t>(out) % (4 * osz) == 0) && (out_stride % 4 == 0) &&
-                   (kRefs || (((x_stride * esz) % (4 * esz) == 0) && (reinterpret_cast<uintptr_t>(x) % (4 * esz) == 0)));
-  with_f32_bf16(out_elem, [&](auto tout) {
-    with_elem_vec(x_elem, vec, [&](auto tin, auto v) {
-      launch_agg_fwd<typename decltype(tin)::type, typename decltype(tout)::type, decltype(v)::value, Src>(
-          rowptr, col, T, x, x_stride, nid, x_rows, F, epi, out, out_stride, stream);
-    });
-  });
-  SPP_HIP_TRY(hipGetLastError());
-  return SPP_OK;
-}
-
-extern "C" spp_status spp_csr_mean_forward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
-                                           const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t F,
-                                           float* out_dev, int64_t out_stride_elems, void* stream) {
-  return agg_forward<Dense>("spp_csr_mean_forward", rowptr_dev, col_dev, num_targets, x_dev, half_elem(x_is_half),
-                            x_stride_elems, nullptr, 0, F, Mean<false>{0, {}}, out_dev, SPP_ELEM_F32, out_stride_elems,
-                            stream);
-}
-
-extern "C" spp_status spp_sage_operand_forward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
-                                               const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t F,
-                                               float* out_dev, int64_t out_stride_elems, void* stream) {
-  SPP_REQUIRE(out_stride_elems >= 2 * F, "spp_sage_operand_forward: the operand [mean | x_target] needs 2F columns");
-  return agg_forward<Dense>("spp_csr_mean_forward", rowptr_dev, col_dev, num_targets, x_dev, half_elem(x_is_half),
-                            x_stride_elems, nullptr, 0, F, Mean<false>{1, {}}, out_dev, SPP_ELEM_F32, out_stride_elems,
-                            stream);
-}
-
-extern "C" spp_status spp_sage_operand_forward_table(const int64_t* rowptr_dev, const int64_t* col_dev,
-                                                     int64_t num_targets, const void* table_dev, int32_t table_is_half,
-                                                     int64_t table_stride_elems, int64_t table_rows,
-                                                     const int64_t* n_id_dev, int64_t F, float* out_dev,
-                                                     int64_t out_stride_elems, void* stream) {
-  SPP_REQUIRE(out_stride_elems >= 2 * F, "spp_sage_operand_forward_table: the operand [mean | x_target] needs 2F columns");
-  SPP_REQUIRE(num_targets == 0 || (n_id_dev && table_dev && table_rows > 0),
-              "spp_sage_operand_forward_table: needs the feature table and the batch's node ids");
-  return agg_forward<Table>("spp_csr_mean_forward", rowptr_dev, col_dev, num_targets, table_dev, half_elem(table_is_half),
-                            table_stride_elems, n_id_dev, table_rows, F, Mean<false>{1, {}}, out_dev, SPP_ELEM_F32,
-                            out_stride_elems, stream);
-}
-
-extern "C" spp_status spp_sage_operand_forward_rows(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
-                                                    const int64_t* row_addr_dev, int32_t rows_are_half, int64_t F,
-                                                    float* out_dev, int64_t out_stride_elems, void* stream) {
-  SPP_REQUIRE(num_targets >= 0 && F >= 0, "spp_sage_operand_forward_rows: negative size");
-  if (num_targets == 0 || F == 0) return SPP_OK;
-  SPP_REQUIRE(rowptr_dev && out_dev && row_addr_dev, "spp_sage_operand_forward_rows: NULL buffer");
-  SPP_REQUIRE(out_stride_elems >= 2 * F, "spp_sage_operand_forward_rows: the operand [mean | x_target] needs 2F columns");
-  SPP_REQUIRE(F % 4 == 0 && (reinterpret_cast<uintptr_t>(out_dev) % 16 == 0) && (out_stride_elems % 4 == 0),
-              "spp_sage_operand_forward_rows: needs F %% 4 == 0 and a 16-byte aligned operand (F = %lld)", (long long)F);
-  with_elem(half_elem(rows_are_half), [&](auto tin) {
-    launch_agg_fwd<typename decltype(tin)::type, float, true, Refs>(rowptr_dev, col_dev, num_targets, nullptr, 0,
-                                                                    row_addr_dev, 0, F, Mean<false>{1, {}}, out_dev,
-                                                                    out_stride_elems, stream);
-  });
-  SPP_HIP_TRY(hipGetLastError());
-  return SPP_OK;
+// the grid of an element-wise kernel that strides over `items` work items
+static unsigned elementwise_grid(int64_t items) {
+  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(items, kAggNT), 256 * 32));
 }
 
 static ActArgs act_args(float p, int32_t training, uint64_t seed) {
@@ -612,36 +519,87 @@ static ActArgs act_args(float p, int32_t training, uint64_t seed) {
   return a;
 }
 
-// [mean | x_target] of relu_dropout(x) without materialising the activation (see kAct)
-extern "C" spp_status spp_sage_operand_forward_act(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
-                                                   const float* x_dev, int64_t F, float* out_dev, int64_t out_stride_elems,
-                                                   float p, int32_t training, uint64_t seed, void* stream) {
-  SPP_REQUIRE(num_targets >= 0 && F >= 0 && p >= 0.f && p < 1.f, "spp_sage_operand_forward_act: bad arguments");
-  if (num_targets == 0 || F == 0) return SPP_OK;
-  SPP_REQUIRE(rowptr_dev && x_dev && out_dev && out_stride_elems >= 2 * F && F % 4 == 0 && out_stride_elems % 4 == 0 &&
-                  reinterpret_cast<uintptr_t>(x_dev) % 16 == 0 && reinterpret_cast<uintptr_t>(out_dev) % 16 == 0,
-              "spp_sage_operand_forward_act: needs dense fp32 rows with F %% 4 == 0 and 16-byte aligned buffers");
-  launch_agg_fwd<float, float, true, Dense>(rowptr_dev, col_dev, num_targets, x_dev, F, nullptr, 0, F,
-                                            Mean<true>{1, act_args(p, training, seed)}, out_dev, out_stride_elems, stream);
+// The forward of every mean / operand / sum entry (`who` names the public entry in the errors): validation, the
+// choice of the vector form, the source x epilogue x element-type dispatch and the launch of k_agg_fwd.
+//   source: DENSE (x = the batch's matrix), TABLE (x = the resident table, n_id = the batch's node ids, x_rows its rows)
+//     or ROWS (n_id = the row addresses; x, x_stride unused)
+//   vector form: F % 4 == 0 and every row aligned to 4 elements (row references: 8-byte aligned fp16 / bf16, 16-byte
+//     aligned fp32 rows when F % 4 == 0, spp_mfg_out.row_addr); the activated operand and fp8 rows have no other form
+//   fp8 rows (x_elem = SPP_ELEM_FP8_E4M3, spp_agg_forward_fp8 only): the same kernel with Tin = fp8e4m3 and the column
+//     exponents fp8_scale_log2 in Fp8<Epi>; DENSE or TABLE, no activation on load
+static spp_status agg_forward_desc(const char* who, const spp_agg_fwd_desc& d, const int8_t* fp8_scale_log2,
+                                   void* stream) {
+  const bool fp8 = d.x_elem == SPP_ELEM_FP8_E4M3, refs = d.source == SPP_AGG_ROWS;
+  const bool act = d.epilogue == SPP_AGG_OPERAND_ACT, operand = act || d.epilogue == SPP_AGG_OPERAND;
+  SPP_REQUIRE(d.source >= SPP_AGG_DENSE && d.source <= SPP_AGG_ROWS, "%s: unknown source %d", who, (int)d.source);
+  SPP_REQUIRE(d.epilogue >= SPP_AGG_MEAN && d.epilogue <= SPP_AGG_SUM, "%s: unknown epilogue %d", who, (int)d.epilogue);
+  SPP_REQUIRE((fp8 || elem_ok(d.x_elem)) && f32_bf16_ok(d.out_elem),
+              "%s: unknown or unsupported element code (x %d, out %d)", who, (int)d.x_elem, (int)d.out_elem);
+  SPP_REQUIRE(!fp8 || (!refs && !act), "%s: fp8 rows take dense rows or the table, and the mean, operand or sum epilogue",
+              who);
+  const int64_t T = d.num_targets, F = d.F;
+  SPP_REQUIRE(T >= 0 && F >= 0, "%s: negative size", who);
+  const int64_t width = operand ? 2 * F : F;
+  const int64_t out_stride = d.out_stride_elems > 0 ? d.out_stride_elems : width;
+  SPP_REQUIRE(out_stride >= width, "%s: output stride smaller than the output row", who);
+  SPP_REQUIRE(!act || (d.p >= 0.f && d.p < 1.f), "%s: the activated operand needs 0 <= p < 1", who);
+  if (T == 0 || F == 0) return SPP_OK;
+  SPP_REQUIRE(d.rowptr_dev && d.out_dev && (!fp8 || fp8_scale_log2) &&
+                  (refs ? d.n_id_dev != nullptr : d.x_dev && (d.source == SPP_AGG_DENSE || (d.n_id_dev && d.x_rows > 0))),
+              "%s: NULL buffer or empty table", who);
+  SPP_REQUIRE(refs || d.x_stride_elems >= F, "%s: row stride smaller than the row", who);
+  const bool vec = F % 4 == 0 && out_stride % 4 == 0 && aligned_to(d.out_dev, 4 * elem_bytes(d.out_elem)) &&
+                   (refs || (d.x_stride_elems % 4 == 0 && aligned_to(d.x_dev, 4 * elem_bytes(d.x_elem)))) &&
+                   (!fp8 || aligned_to(fp8_scale_log2, 4));
+  if (act)
+    SPP_REQUIRE(d.source == SPP_AGG_DENSE && f32_bf16_ok(d.x_elem) && d.x_stride_elems == F && vec,
+                "%s: the activated operand needs dense fp32 / bf16 rows, F %% 4 == 0 and aligned buffers", who);
+  if (fp8)
+    SPP_REQUIRE(vec, "%s: needs F %% 4 == 0, 4-byte aligned rows and exponents and an aligned output (F = %lld)", who,
+                (long long)F);
+  const int lpr_log2 = lanes_log2(vec ? F / 4 : F);
+  const unsigned grid = (unsigned)ceil_div(T << lpr_log2, kAggNT);
+  auto launch = [&](auto tin, auto tout, auto v, auto src, auto epi) {
+    using Tin = typename decltype(tin)::type;
+    using Tout = typename decltype(tout)::type;
+    hipLaunchKernelGGL((k_agg_fwd<Tin, Tout, decltype(v)::value, decltype(src), decltype(epi)>), dim3(grid), dim3(kAggNT),
+                       0, as_stream(stream), d.rowptr_dev, d.col_dev, T, static_cast<const Tin*>(d.x_dev),
+                       d.x_stride_elems, F, lpr_log2, static_cast<Tout*>(d.out_dev), out_stride, epi, d.n_id_dev, d.x_rows);
+  };
+  auto by_type = [&](auto src, auto epi) {
+    using Epi = decltype(epi);
+    with_f32_bf16(d.out_elem, [&](auto tout) {
+      if constexpr (Epi::kAct)
+        with_f32_bf16(d.x_elem, [&](auto tin) { launch(tin, tout, std::true_type{}, src, epi); });
+      else if (!fp8)
+        with_elem_vec(d.x_elem, vec, [&](auto tin, auto v) { launch(tin, tout, v, src, epi); });
+      else if constexpr (!std::is_same<decltype(src), Refs>::value)
+        launch(Type<fp8e4m3>{}, tout, std::true_type{}, src, Fp8<Epi>{epi, fp8_scale_log2});
+    });
+  };
+  auto by_epilogue = [&](auto src) {
+    if (d.epilogue == SPP_AGG_SUM)
+      by_type(src, Sum{d.self_scale});
+    else if (!act)
+      by_type(src, Mean<false>{operand ? 1 : 0, {}});
+    else if constexpr (std::is_same<decltype(src), Dense>::value)
+      by_type(src, Mean<true>{1, act_args(d.p, d.training, d.seed)});
+  };
+  d.source == SPP_AGG_TABLE ? by_epilogue(Table{}) : refs ? by_epilogue(Refs{}) : by_epilogue(Dense{});
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
 }
 
-extern "C" spp_status spp_relu_dropout_backward_pre(const float* grad_dev, const float* z_dev, int64_t n, float p,
-                                                    int32_t training, uint64_t seed, float* grad_x_dev, void* stream) {
-  SPP_REQUIRE(n >= 0 && p >= 0.f && p < 1.f, "spp_relu_dropout_backward_pre: bad arguments");
-  if (n == 0) return SPP_OK;
-  SPP_REQUIRE(grad_dev && z_dev && grad_x_dev && n % 4 == 0 &&
-                  (reinterpret_cast<uintptr_t>(grad_dev) | reinterpret_cast<uintptr_t>(z_dev) |
-                   reinterpret_cast<uintptr_t>(grad_x_dev)) % 16 == 0,
-              "spp_relu_dropout_backward_pre: needs n %% 4 == 0 and 16-byte aligned buffers");
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n / 4, kAggNT), 256 * 32));
-  hipLaunchKernelGGL((k_relu_dropout_bwd_pre<float, float, true>), dim3(grid), dim3(kAggNT), 0, as_stream(stream),
-                     grad_dev, z_dev, n, act_args(p, training, seed), grad_x_dev);
-  SPP_HIP_TRY(hipGetLastError());
-  return SPP_OK;
+template <class Epi, typename Tg>
+static void launch_agg_bwd_scatter(const int64_t* rowptr, const int64_t* col, int64_t T, const Tg* grad_out,
+                                   int64_t go_stride, int64_t F, float* grad_x, hipStream_t st) {
+  const int lpr_log2 = lanes_log2(F);
+  const unsigned grid = (unsigned)ceil_div(T << lpr_log2, kAggNT);
+  hipLaunchKernelGGL((k_agg_bwd_scatter<Epi, Tg>), dim3(grid), dim3(kAggNT), 0, st, rowptr, col, T, grad_out, go_stride,
+                     F, lpr_log2, grad_x);
 }
 
+// the bare scatter step of the mean's gradient: no num_sources, and it ADDS into a grad_x the caller zeroed
 extern "C" spp_status spp_csr_mean_backward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
                                             const float* grad_out_dev, int64_t grad_out_stride_elems, int64_t F,
                                             float* grad_x_dev, void* stream) {
@@ -654,27 +612,6 @@ extern "C" spp_status spp_csr_mean_backward(const int64_t* rowptr_dev, const int
                                       grad_x_dev, as_stream(stream));
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
-}
-
-extern "C" spp_status spp_sage_operand_backward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
-                                                int64_t num_sources, const float* grad_out_dev,
-                                                int64_t grad_out_stride_elems, int64_t F, float* grad_x_dev,
-                                                void* stream) {
-  SPP_REQUIRE(num_targets >= 0 && num_sources >= num_targets && F >= 0, "spp_sage_operand_backward: bad sizes");
-  if (num_sources == 0 || F == 0) return SPP_OK;
-  SPP_REQUIRE(grad_x_dev && (grad_out_dev || num_targets == 0), "spp_sage_operand_backward: NULL buffer");
-  SPP_REQUIRE(F % 4 == 0 && grad_out_stride_elems >= 2 * F && grad_out_stride_elems % 4 == 0 &&
-                  reinterpret_cast<uintptr_t>(grad_out_dev) % 16 == 0 && reinterpret_cast<uintptr_t>(grad_x_dev) % 16 == 0,
-              "spp_sage_operand_backward: needs F %% 4 == 0 and 16-byte aligned rows");
-  hipStream_t st = as_stream(stream);
-  const int64_t n4 = num_sources * F / 4;
-  const unsigned g0 = (unsigned)std::min<int64_t>(ceil_div(n4, kAggNT), 256 * 32);
-  hipLaunchKernelGGL(k_grad_init<float>, dim3(g0), dim3(kAggNT), 0, st, grad_out_dev, grad_out_stride_elems, num_targets,
-                     num_sources, F, grad_x_dev);
-  SPP_HIP_TRY(hipGetLastError());
-  if (num_targets == 0) return SPP_OK;
-  return spp_csr_mean_backward(rowptr_dev, col_dev, num_targets, grad_out_dev, grad_out_stride_elems, F, grad_x_dev,
-                               stream);
 }
 
 static int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
@@ -724,48 +661,196 @@ static spp_status transpose_hop(const int64_t* rowptr_dev, const int64_t* col_de
   return SPP_OK;
 }
 
-// The gather-form backward entries: their shared validation (`who` names the entry), the transposed hop and the
-// launch of k_agg_bwd_gather.  The operand's (Mean) gradient has the vector form only; the sum's takes any F and row stride.
-// grad_out, z and grad_x are fp32 or bf16 (vector form: rows aligned to 4 elements).
-template <class Epi, typename Tg, typename Tz, typename Tout>
-static spp_status agg_backward_gather(const char* who, const int64_t* rowptr_dev, const int64_t* col_dev,
-                                      int64_t num_targets, int64_t num_sources, int64_t num_edges,
-                                      const Tg* grad_out_dev, int64_t grad_out_stride_elems, int64_t F, Epi epi,
-                                      Tout* grad_x_dev, void* workspace_dev, int64_t workspace_bytes,
-                                      const Tz* z_pre_dev, void* stream) {
-  SPP_REQUIRE(num_targets >= 0 && num_sources >= num_targets && F >= 0 && num_edges >= 0, "%s: bad sizes", who);
-  if (num_sources == 0 || F == 0) return SPP_OK;
-  SPP_REQUIRE(num_sources < (1ll << 31) && num_edges < (1ll << 31), "%s: 32-bit indices", who);
-  SPP_REQUIRE(grad_x_dev && workspace_dev && ((grad_out_dev && (rowptr_dev || !Epi::kSum)) || num_targets == 0),
+// The backward of every operand / sum / mean entry but spp_csr_mean_backward (`who` names the public entry in the
+// errors); grad_x [S, F] dense is written completely.
+//   gather: the transposed hop in the workspace, then k_agg_bwd_gather (fixed summation order).  The operand's gradient
+//     has the vector form only; the sum's takes any F and row stride.
+//   scatter: fp32 atomics into an fp32 buffer (grad_x itself when it is fp32, else the workspace) that an init pass has
+//     filled with the targets' own term, then one pass that applies the activation's backward and / or rounds to bf16.
+// grad_out, z and grad_x are fp32 or bf16 (vector form: rows aligned to 4 elements); z is read by OPERAND_ACT only.
+static spp_status agg_backward_desc(const char* who, const spp_agg_bwd_desc& d, void* workspace_dev,
+                                    int64_t workspace_bytes, void* stream) {
+  SPP_REQUIRE(d.form == SPP_AGG_SCATTER || d.form == SPP_AGG_GATHER, "%s: unknown form %d", who, (int)d.form);
+  SPP_REQUIRE(d.epilogue >= SPP_AGG_MEAN && d.epilogue <= SPP_AGG_SUM, "%s: unknown epilogue %d", who, (int)d.epilogue);
+  SPP_REQUIRE(f32_bf16_ok(d.grad_elem) && f32_bf16_ok(d.out_elem) && f32_bf16_ok(d.z_elem),
+              "%s: unknown or unsupported element code (grad %d, out %d, z %d)", who, (int)d.grad_elem, (int)d.out_elem,
+              (int)d.z_elem);
+  const bool gather = d.form == SPP_AGG_GATHER, sum = d.epilogue == SPP_AGG_SUM;
+  const bool act = d.epilogue == SPP_AGG_OPERAND_ACT, operand = act || d.epilogue == SPP_AGG_OPERAND;
+  SPP_REQUIRE(!gather || operand || sum, "%s: the plain mean has the scatter form only", who);
+  if (act)
+    SPP_REQUIRE(d.z_dev && aligned_to(d.z_dev, 4 * elem_bytes(d.z_elem)) && d.p >= 0.f && d.p < 1.f,
+                "%s: NULL / unaligned pre-activation or bad p", who);
+  const int64_t T = d.num_targets, S = d.num_sources, E = d.num_edges, F = d.F;
+  SPP_REQUIRE(T >= 0 && S >= T && F >= 0 && (!gather || E >= 0), "%s: bad sizes", who);
+  if (S == 0 || F == 0) return SPP_OK;
+  const int64_t n = S * F;
+  SPP_REQUIRE(!gather || (S < (1ll << 31) && E < (1ll << 31)), "%s: 32-bit indices", who);
+  SPP_REQUIRE(d.grad_x_dev && ((d.grad_out_dev && d.rowptr_dev) || T == 0) && (!gather || workspace_dev),
               "%s: NULL buffer", who);
-  if (Epi::kSum && grad_out_stride_elems <= 0) grad_out_stride_elems = F;
-  const bool vec = F % 4 == 0 && grad_out_stride_elems % 4 == 0 &&
-                   reinterpret_cast<uintptr_t>(grad_out_dev) % (4 * sizeof(Tg)) == 0 &&
-                   reinterpret_cast<uintptr_t>(grad_x_dev) % (4 * sizeof(Tout)) == 0;
-  const bool ws_aligned = reinterpret_cast<uintptr_t>(workspace_dev) % 16 == 0;
-  if (Epi::kSum)
-    SPP_REQUIRE(grad_out_stride_elems >= F && ws_aligned,
-                "%s: gradient stride smaller than the row or unaligned workspace", who);
-  else
-    SPP_REQUIRE(vec && grad_out_stride_elems >= 2 * F && ws_aligned, "%s: needs F %% 4 == 0 and 16-byte aligned buffers",
-                who);
-  SPP_REQUIRE(workspace_bytes >= spp_sage_operand_backward_workspace_bytes(num_targets, num_sources, num_edges),
-              "%s: workspace too small", who);
+  const int64_t width = operand ? 2 * F : F;
+  const int64_t gs = d.grad_out_stride_elems > 0 ? d.grad_out_stride_elems : width;
+  SPP_REQUIRE(gs >= width, "%s: gradient stride smaller than the row", who);
+  const bool vec = F % 4 == 0 && gs % 4 == 0 && aligned_to(d.grad_out_dev, 4 * elem_bytes(d.grad_elem)) &&
+                   aligned_to(d.grad_x_dev, 4 * elem_bytes(d.out_elem));
+  SPP_REQUIRE(vec || !operand, "%s: the operand's gradient needs F %% 4 == 0 and rows aligned to 4 elements", who);
+  const bool rounds = d.out_elem != SPP_ELEM_F32;  // scatter: the atomics' fp32 buffer is the workspace
+  if (gather) {
+    SPP_REQUIRE(aligned_to(workspace_dev, 16), "%s: unaligned workspace", who);
+    SPP_REQUIRE(workspace_bytes >= transpose_hop_bytes(T, S, E, false), "%s: workspace too small", who);
+  } else if (rounds) {
+    SPP_REQUIRE(workspace_dev && aligned_to(workspace_dev, 16) && workspace_bytes >= 4 * n,
+                "%s: a bf16 scatter gradient needs a 16-byte aligned fp32 workspace of 4 * S * F bytes", who);
+  }
   hipStream_t st = as_stream(stream);
-  TransposedHop hop;
-  SPP_TRY(transpose_hop(rowptr_dev, col_dev, num_targets, num_sources, num_edges, false, workspace_dev, workspace_bytes,
-                        st, &hop));
+  const ActArgs aa = act ? act_args(d.p, d.training, d.seed) : ActArgs{};
+  float* acc = static_cast<float*>(rounds ? workspace_dev : d.grad_x_dev);
+  TransposedHop hop{};
+  if (gather)
+    SPP_TRY(transpose_hop(d.rowptr_dev, d.col_dev, T, S, E, false, workspace_dev, workspace_bytes, st, &hop));
+  else if (d.epilogue == SPP_AGG_MEAN)
+    SPP_HIP_TRY(hipMemsetAsync(acc, 0, 4 * (size_t)n, st));
   const int lpr_log2 = lanes_log2(vec ? F / 4 : F);
-  const unsigned grid = (unsigned)ceil_div(num_sources << lpr_log2, kAggNT);
-  auto launch = [&](auto v) {
-    hipLaunchKernelGGL((k_agg_bwd_gather<Tg, Tz, Tout, decltype(v)::value, Epi>), dim3(grid), dim3(kAggNT), 0, st, hop.start, hop.tcol,
-                       hop.inv, num_targets, num_sources, grad_out_dev, grad_out_stride_elems, F, lpr_log2, grad_x_dev,
-                       z_pre_dev, epi);
-  };
-  if (vec) launch(std::true_type{});
-  else if constexpr (Epi::kSum) launch(std::false_type{});
+  const unsigned grid = (unsigned)ceil_div(S << lpr_log2, kAggNT);  // (gather)
+  with_f32_bf16(d.grad_elem, [&](auto tg) {
+    with_f32_bf16(d.out_elem, [&](auto tout) {
+      using Tg = typename decltype(tg)::type;
+      using Tout = typename decltype(tout)::type;
+      const Tg* g = static_cast<const Tg*>(d.grad_out_dev);
+      Tout* gx = static_cast<Tout*>(d.grad_x_dev);
+      auto gather_rows = [&](auto v, auto tz, auto epi) {
+        using Tz = typename decltype(tz)::type;
+        hipLaunchKernelGGL((k_agg_bwd_gather<Tg, Tz, Tout, decltype(v)::value, decltype(epi)>), dim3(grid), dim3(kAggNT), 0,
+                           st, hop.start, hop.tcol, hop.inv, T, S, g, gs, F, lpr_log2, gx,
+                           static_cast<const Tz*>(act ? d.z_dev : nullptr), epi);
+      };
+      if (gather) {
+        if (act)
+          with_f32_bf16(d.z_elem, [&](auto tz) { gather_rows(std::true_type{}, tz, Mean<true>{1, aa}); });
+        else if (operand)
+          gather_rows(std::true_type{}, Type<float>{}, Mean<false>{1, {}});
+        else if (vec)
+          gather_rows(std::true_type{}, Type<float>{}, Sum{d.self_scale});
+        else
+          gather_rows(std::false_type{}, Type<float>{}, Sum{d.self_scale});
+        return;
+      }
+      if (operand)
+        hipLaunchKernelGGL(k_grad_init<Tg>, dim3(elementwise_grid(n / 4)), dim3(kAggNT), 0, st, g, gs, T, S, F, acc);
+      else if (sum)
+        hipLaunchKernelGGL(k_sum_grad_init<Tg>, dim3(elementwise_grid(n)), dim3(kAggNT), 0, st, g, gs, T, S, F,
+                           d.self_scale, acc);
+      if (T > 0)
+        sum ? launch_agg_bwd_scatter<Sum>(d.rowptr_dev, d.col_dev, T, g, gs, F, acc, st)
+            : launch_agg_bwd_scatter<Mean<false>>(d.rowptr_dev, d.col_dev, T, g, gs, F, acc, st);
+      if (act)
+        with_f32_bf16(d.z_elem, [&](auto tz) {
+          using Tz = typename decltype(tz)::type;
+          hipLaunchKernelGGL((k_relu_dropout_bwd_pre<Tz, Tout, true>), dim3(elementwise_grid(n / 4)), dim3(kAggNT), 0, st,
+                             acc, static_cast<const Tz*>(d.z_dev), n, aa, gx);
+        });
+      else if (rounds)
+        hipLaunchKernelGGL((k_relu_dropout_bwd_pre<float, Tout, false>), dim3(elementwise_grid(n / 4)), dim3(kAggNT), 0,
+                           st, acc, (const float*)nullptr, n, ActArgs{}, gx);
+    });
+  });
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
+}
+
+// ---- the entries that predate the descriptors: fixed-type spellings of agg_forward_desc / agg_backward_desc ----
+// fp32 out / grad / z; x fp32 or fp16 by the old flag; each keeps only the restrictions the descriptor path lacks.
+static spp_agg_fwd_desc fwd_desc(int32_t source, int32_t epilogue, const int64_t* rowptr_dev, const int64_t* col_dev,
+                                 int64_t num_targets, const void* x_dev, int32_t x_is_half, int64_t x_stride_elems,
+                                 int64_t x_rows, const int64_t* n_id_dev, int64_t F, float self_scale, float* out_dev,
+                                 int64_t out_stride_elems) {
+  spp_agg_fwd_desc d{};
+  d.source = source, d.epilogue = epilogue, d.x_elem = half_elem(x_is_half), d.out_elem = SPP_ELEM_F32;
+  d.rowptr_dev = rowptr_dev, d.col_dev = col_dev, d.num_targets = num_targets;
+  d.x_dev = x_dev, d.x_stride_elems = x_stride_elems, d.x_rows = x_rows, d.n_id_dev = n_id_dev, d.F = F;
+  d.out_dev = out_dev, d.out_stride_elems = out_stride_elems, d.self_scale = self_scale;
+  return d;
+}
+
+static spp_agg_bwd_desc bwd_desc(int32_t form, int32_t epilogue, const int64_t* rowptr_dev, const int64_t* col_dev,
+                                 int64_t num_targets, int64_t num_sources, int64_t num_edges, const float* grad_out_dev,
+                                 int64_t grad_out_stride_elems, int64_t F, float self_scale, float* grad_x_dev) {
+  spp_agg_bwd_desc d{};
+  d.form = form, d.epilogue = epilogue, d.grad_elem = d.out_elem = d.z_elem = SPP_ELEM_F32;
+  d.rowptr_dev = rowptr_dev, d.col_dev = col_dev;
+  d.num_targets = num_targets, d.num_sources = num_sources, d.num_edges = num_edges;
+  d.grad_out_dev = grad_out_dev, d.grad_out_stride_elems = grad_out_stride_elems, d.F = F;
+  d.grad_x_dev = grad_x_dev, d.self_scale = self_scale;
+  return d;
+}
+
+extern "C" spp_status spp_csr_mean_forward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                                           const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t F,
+                                           float* out_dev, int64_t out_stride_elems, void* stream) {
+  return agg_forward_desc("spp_csr_mean_forward",
+                          fwd_desc(SPP_AGG_DENSE, SPP_AGG_MEAN, rowptr_dev, col_dev, num_targets, x_dev, x_is_half,
+                                   x_stride_elems, 0, nullptr, F, 0.f, out_dev, out_stride_elems),
+                          nullptr, stream);
+}
+
+extern "C" spp_status spp_sage_operand_forward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                                               const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t F,
+                                               float* out_dev, int64_t out_stride_elems, void* stream) {
+  SPP_REQUIRE(out_stride_elems >= 2 * F, "spp_sage_operand_forward: the operand [mean | x_target] needs 2F columns");
+  return agg_forward_desc("spp_sage_operand_forward",
+                          fwd_desc(SPP_AGG_DENSE, SPP_AGG_OPERAND, rowptr_dev, col_dev, num_targets, x_dev, x_is_half,
+                                   x_stride_elems, 0, nullptr, F, 0.f, out_dev, out_stride_elems),
+                          nullptr, stream);
+}
+
+extern "C" spp_status spp_sage_operand_forward_table(const int64_t* rowptr_dev, const int64_t* col_dev,
+                                                     int64_t num_targets, const void* table_dev, int32_t table_is_half,
+                                                     int64_t table_stride_elems, int64_t table_rows,
+                                                     const int64_t* n_id_dev, int64_t F, float* out_dev,
+                                                     int64_t out_stride_elems, void* stream) {
+  SPP_REQUIRE(out_stride_elems >= 2 * F, "spp_sage_operand_forward_table: the operand [mean | x_target] needs 2F columns");
+  SPP_REQUIRE(num_targets == 0 || (n_id_dev && table_dev && table_rows > 0),
+              "spp_sage_operand_forward_table: needs the feature table and the batch's node ids");
+  return agg_forward_desc("spp_sage_operand_forward_table",
+                          fwd_desc(SPP_AGG_TABLE, SPP_AGG_OPERAND, rowptr_dev, col_dev, num_targets, table_dev,
+                                   table_is_half, table_stride_elems, table_rows, n_id_dev, F, 0.f, out_dev,
+                                   out_stride_elems),
+                          nullptr, stream);
+}
+
+extern "C" spp_status spp_sage_operand_forward_rows(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                                                    const int64_t* row_addr_dev, int32_t rows_are_half, int64_t F,
+                                                    float* out_dev, int64_t out_stride_elems, void* stream) {
+  SPP_REQUIRE(out_stride_elems >= 2 * F, "spp_sage_operand_forward_rows: the operand [mean | x_target] needs 2F columns");
+  SPP_REQUIRE(F % 4 == 0 && aligned_to(out_dev, 16) && out_stride_elems % 4 == 0,
+              "spp_sage_operand_forward_rows: needs F %% 4 == 0 and a 16-byte aligned operand (F = %lld)", (long long)F);
+  return agg_forward_desc("spp_sage_operand_forward_rows",
+                          fwd_desc(SPP_AGG_ROWS, SPP_AGG_OPERAND, rowptr_dev, col_dev, num_targets, nullptr,
+                                   rows_are_half, 0, 0, row_addr_dev, F, 0.f, out_dev, out_stride_elems),
+                          nullptr, stream);
+}
+
+// [mean | x_target] of relu_dropout(x) without materialising the activation (see kAct)
+extern "C" spp_status spp_sage_operand_forward_act(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                                                   const float* x_dev, int64_t F, float* out_dev, int64_t out_stride_elems,
+                                                   float p, int32_t training, uint64_t seed, void* stream) {
+  SPP_REQUIRE(out_stride_elems >= 2 * F, "spp_sage_operand_forward_act: the operand [mean | x_target] needs 2F columns");
+  spp_agg_fwd_desc d = fwd_desc(SPP_AGG_DENSE, SPP_AGG_OPERAND_ACT, rowptr_dev, col_dev, num_targets, x_dev, 0, F, 0,
+                                nullptr, F, 0.f, out_dev, out_stride_elems);
+  d.p = p, d.training = training, d.seed = seed;
+  return agg_forward_desc("spp_sage_operand_forward_act", d, nullptr, stream);
+}
+
+// (the operand's backward entries refuse a gradient stride of 0; the descriptor defaults it)
+extern "C" spp_status spp_sage_operand_backward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                                                int64_t num_sources, const float* grad_out_dev,
+                                                int64_t grad_out_stride_elems, int64_t F, float* grad_x_dev,
+                                                void* stream) {
+  SPP_REQUIRE(grad_out_stride_elems >= 2 * F, "spp_sage_operand_backward: the operand's gradient needs 2F columns");
+  return agg_backward_desc("spp_sage_operand_backward",
+                           bwd_desc(SPP_AGG_SCATTER, SPP_AGG_OPERAND, rowptr_dev, col_dev, num_targets, num_sources, 0,
+                                    grad_out_dev, grad_out_stride_elems, F, 0.f, grad_x_dev),
+                           nullptr, 0, stream);
 }
 
 extern "C" spp_status spp_sage_operand_backward_gather(const int64_t* rowptr_dev, const int64_t* col_dev,
@@ -773,9 +858,11 @@ extern "C" spp_status spp_sage_operand_backward_gather(const int64_t* rowptr_dev
                                                        const float* grad_out_dev, int64_t grad_out_stride_elems,
                                                        int64_t F, float* grad_x_dev, void* workspace_dev,
                                                        int64_t workspace_bytes, void* stream) {
-  return agg_backward_gather("spp_sage_operand_backward_gather", rowptr_dev, col_dev, num_targets, num_sources,
-                             num_edges, grad_out_dev, grad_out_stride_elems, F, Mean<false>{1, {}}, grad_x_dev,
-                             workspace_dev, workspace_bytes, (const float*)nullptr, stream);
+  SPP_REQUIRE(grad_out_stride_elems >= 2 * F, "spp_sage_operand_backward_gather: the operand's gradient needs 2F columns");
+  return agg_backward_desc("spp_sage_operand_backward_gather",
+                           bwd_desc(SPP_AGG_GATHER, SPP_AGG_OPERAND, rowptr_dev, col_dev, num_targets, num_sources,
+                                    num_edges, grad_out_dev, grad_out_stride_elems, F, 0.f, grad_x_dev),
+                           workspace_dev, workspace_bytes, stream);
 }
 
 // the same, followed in the same pass by the ReLU + dropout backward of spp_relu_dropout_backward_pre: grad_x
@@ -786,24 +873,24 @@ extern "C" spp_status spp_sage_operand_backward_gather_act(const int64_t* rowptr
                                                            int64_t F, float* grad_x_dev, void* workspace_dev,
                                                            int64_t workspace_bytes, const float* z_pre_dev, float p,
                                                            int32_t training, uint64_t seed, void* stream) {
-  SPP_REQUIRE(z_pre_dev && reinterpret_cast<uintptr_t>(z_pre_dev) % 16 == 0 && p >= 0.f && p < 1.f,
-              "spp_sage_operand_backward_gather_act: NULL / unaligned pre-activation or bad p");
-  return agg_backward_gather("spp_sage_operand_backward_gather", rowptr_dev, col_dev, num_targets, num_sources,
-                             num_edges, grad_out_dev, grad_out_stride_elems, F, Mean<true>{1, act_args(p, training, seed)},
-                             grad_x_dev, workspace_dev, workspace_bytes, z_pre_dev, stream);
+  SPP_REQUIRE(grad_out_stride_elems >= 2 * F,
+              "spp_sage_operand_backward_gather_act: the operand's gradient needs 2F columns");
+  spp_agg_bwd_desc d = bwd_desc(SPP_AGG_GATHER, SPP_AGG_OPERAND_ACT, rowptr_dev, col_dev, num_targets, num_sources,
+                                num_edges, grad_out_dev, grad_out_stride_elems, F, 0.f, grad_x_dev);
+  d.z_dev = z_pre_dev, d.p = p, d.training = training, d.seed = seed;
+  return agg_backward_desc("spp_sage_operand_backward_gather_act", d, workspace_dev, workspace_bytes, stream);
 }
 
+// ---- ReLU + dropout, element-wise (the stand-alone forms) ----
 extern "C" spp_status spp_relu_dropout_forward(const float* x_dev, int64_t n, float p, int32_t training, uint64_t seed,
                                                float* y_dev, void* stream) {
   SPP_REQUIRE(n >= 0 && p >= 0.f && p < 1.f, "spp_relu_dropout_forward: bad arguments");
   if (n == 0) return SPP_OK;
-  SPP_REQUIRE(x_dev && y_dev && reinterpret_cast<uintptr_t>(x_dev) % 16 == 0 && reinterpret_cast<uintptr_t>(y_dev) % 16 == 0,
+  SPP_REQUIRE(x_dev && y_dev && aligned_to(x_dev, 16) && aligned_to(y_dev, 16),
               "spp_relu_dropout_forward: NULL or unaligned buffer");
-  const double keep = 1.0 - (double)p;
-  const uint32_t thr = keep >= 1.0 ? 0xffffffffu : (uint32_t)(keep * 4294967296.0);
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n / 4, kAggNT), 256 * 32));
-  hipLaunchKernelGGL(k_relu_dropout_fwd, dim3(grid), dim3(kAggNT), 0, as_stream(stream), x_dev, n, thr,
-                     (float)(1.0 / keep), seed, training, y_dev);
+  const ActArgs a = act_args(p, training, seed);
+  hipLaunchKernelGGL(k_relu_dropout_fwd, dim3(elementwise_grid(n / 4)), dim3(kAggNT), 0, as_stream(stream), x_dev, n,
+                     a.keep_thr, a.scale, seed, training, y_dev);
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
 }
@@ -813,11 +900,23 @@ extern "C" spp_status spp_relu_dropout_backward(const float* grad_dev, const flo
   SPP_REQUIRE(n >= 0, "spp_relu_dropout_backward: negative size");
   if (n == 0) return SPP_OK;
   SPP_REQUIRE(grad_dev && y_dev && grad_x_dev, "spp_relu_dropout_backward: NULL buffer");
-  SPP_REQUIRE((reinterpret_cast<uintptr_t>(grad_dev) | reinterpret_cast<uintptr_t>(y_dev) |
-               reinterpret_cast<uintptr_t>(grad_x_dev)) % 16 == 0, "spp_relu_dropout_backward: unaligned buffer");
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n / 4, kAggNT), 256 * 32));
-  hipLaunchKernelGGL(k_relu_dropout_bwd, dim3(grid), dim3(kAggNT), 0, as_stream(stream), grad_dev, y_dev, n, scale,
-                     grad_x_dev);
+  SPP_REQUIRE(aligned_to(grad_dev, 16) && aligned_to(y_dev, 16) && aligned_to(grad_x_dev, 16),
+              "spp_relu_dropout_backward: unaligned buffer");
+  hipLaunchKernelGGL(k_relu_dropout_bwd, dim3(elementwise_grid(n / 4)), dim3(kAggNT), 0, as_stream(stream), grad_dev,
+                     y_dev, n, scale, grad_x_dev);
+  SPP_HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
+
+extern "C" spp_status spp_relu_dropout_backward_pre(const float* grad_dev, const float* z_dev, int64_t n, float p,
+                                                    int32_t training, uint64_t seed, float* grad_x_dev, void* stream) {
+  SPP_REQUIRE(n >= 0 && p >= 0.f && p < 1.f, "spp_relu_dropout_backward_pre: bad arguments");
+  if (n == 0) return SPP_OK;
+  SPP_REQUIRE(grad_dev && z_dev && grad_x_dev && n % 4 == 0 && aligned_to(grad_dev, 16) && aligned_to(z_dev, 16) &&
+                  aligned_to(grad_x_dev, 16),
+              "spp_relu_dropout_backward_pre: needs n %% 4 == 0 and 16-byte aligned buffers");
+  hipLaunchKernelGGL((k_relu_dropout_bwd_pre<float, float, true>), dim3(elementwise_grid(n / 4)), dim3(kAggNT), 0,
+                     as_stream(stream), grad_dev, z_dev, n, act_args(p, training, seed), grad_x_dev);
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
 }
@@ -2070,9 +2169,10 @@ extern "C" spp_status spp_gat_mh_aggregate_backward_gather(
 extern "C" spp_status spp_csr_sum_forward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
                                           const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t F,
                                           float self_scale, float* out_dev, int64_t out_stride_elems, void* stream) {
-  return agg_forward<Dense>("spp_csr_sum_forward", rowptr_dev, col_dev, num_targets, x_dev, half_elem(x_is_half),
-                            x_stride_elems, nullptr, 0, F, Sum{self_scale}, out_dev, SPP_ELEM_F32, out_stride_elems,
-                            stream);
+  return agg_forward_desc("spp_csr_sum_forward",
+                          fwd_desc(SPP_AGG_DENSE, SPP_AGG_SUM, rowptr_dev, col_dev, num_targets, x_dev, x_is_half,
+                                   x_stride_elems, 0, nullptr, F, self_scale, out_dev, out_stride_elems),
+                          nullptr, stream);
 }
 
 extern "C" spp_status spp_csr_sum_forward_table(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
@@ -2081,35 +2181,28 @@ extern "C" spp_status spp_csr_sum_forward_table(const int64_t* rowptr_dev, const
                                                 float* out_dev, int64_t out_stride_elems, void* stream) {
   SPP_REQUIRE(num_targets == 0 || (n_id_dev && table_dev && table_rows > 0),
               "spp_csr_sum_forward_table: needs the feature table and the batch's node ids");
-  return agg_forward<Table>("spp_csr_sum_forward_table", rowptr_dev, col_dev, num_targets, table_dev,
-                            half_elem(table_is_half), table_stride_elems, n_id_dev, table_rows, F, Sum{self_scale}, out_dev,
-                            SPP_ELEM_F32, out_stride_elems, stream);
+  return agg_forward_desc("spp_csr_sum_forward_table",
+                          fwd_desc(SPP_AGG_TABLE, SPP_AGG_SUM, rowptr_dev, col_dev, num_targets, table_dev, table_is_half,
+                                   table_stride_elems, table_rows, n_id_dev, F, self_scale, out_dev, out_stride_elems),
+                          nullptr, stream);
 }
 
 extern "C" spp_status spp_csr_sum_forward_rows(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
                                                const int64_t* row_addr_dev, int32_t rows_are_half, int64_t F,
                                                float self_scale, float* out_dev, int64_t out_stride_elems, void* stream) {
-  return agg_forward<Refs>("spp_csr_sum_forward_rows", rowptr_dev, col_dev, num_targets, nullptr, half_elem(rows_are_half),
-                           0, row_addr_dev, 0, F, Sum{self_scale}, out_dev, SPP_ELEM_F32, out_stride_elems, stream);
+  return agg_forward_desc("spp_csr_sum_forward_rows",
+                          fwd_desc(SPP_AGG_ROWS, SPP_AGG_SUM, rowptr_dev, col_dev, num_targets, nullptr, rows_are_half, 0,
+                                   0, row_addr_dev, F, self_scale, out_dev, out_stride_elems),
+                          nullptr, stream);
 }
 
 extern "C" spp_status spp_csr_sum_backward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
                                            int64_t num_sources, const float* grad_out_dev, int64_t grad_out_stride_elems,
                                            int64_t F, float self_scale, float* grad_x_dev, void* stream) {
-  SPP_REQUIRE(num_targets >= 0 && num_sources >= num_targets && F >= 0, "spp_csr_sum_backward: bad sizes");
-  if (num_sources == 0 || F == 0) return SPP_OK;
-  SPP_REQUIRE(grad_x_dev && ((grad_out_dev && rowptr_dev) || num_targets == 0), "spp_csr_sum_backward: NULL buffer");
-  if (grad_out_stride_elems <= 0) grad_out_stride_elems = F;
-  SPP_REQUIRE(grad_out_stride_elems >= F, "spp_csr_sum_backward: gradient stride smaller than the row");
-  hipStream_t st = as_stream(stream);
-  const unsigned g0 = (unsigned)std::min<int64_t>(ceil_div(num_sources * F, kAggNT), 256 * 32);
-  hipLaunchKernelGGL(k_sum_grad_init<float>, dim3(g0), dim3(kAggNT), 0, st, grad_out_dev, grad_out_stride_elems, num_targets,
-                     num_sources, F, self_scale, grad_x_dev);
-  SPP_HIP_TRY(hipGetLastError());
-  if (num_targets == 0) return SPP_OK;
-  launch_agg_bwd_scatter<Sum, float>(rowptr_dev, col_dev, num_targets, grad_out_dev, grad_out_stride_elems, F, grad_x_dev, st);
-  SPP_HIP_TRY(hipGetLastError());
-  return SPP_OK;
+  return agg_backward_desc("spp_csr_sum_backward",
+                           bwd_desc(SPP_AGG_SCATTER, SPP_AGG_SUM, rowptr_dev, col_dev, num_targets, num_sources, 0,
+                                    grad_out_dev, grad_out_stride_elems, F, self_scale, grad_x_dev),
+                           nullptr, 0, stream);
 }
 
 extern "C" spp_status spp_csr_sum_backward_gather(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
@@ -2117,199 +2210,34 @@ extern "C" spp_status spp_csr_sum_backward_gather(const int64_t* rowptr_dev, con
                                                   int64_t grad_out_stride_elems, int64_t F, float self_scale,
                                                   float* grad_x_dev, void* workspace_dev, int64_t workspace_bytes,
                                                   void* stream) {
-  return agg_backward_gather("spp_csr_sum_backward_gather", rowptr_dev, col_dev, num_targets, num_sources, num_edges,
-                             grad_out_dev, grad_out_stride_elems, F, Sum{self_scale}, grad_x_dev, workspace_dev,
-                             workspace_bytes, (const float*)nullptr, stream);
+  return agg_backward_desc("spp_csr_sum_backward_gather",
+                           bwd_desc(SPP_AGG_GATHER, SPP_AGG_SUM, rowptr_dev, col_dev, num_targets, num_sources, num_edges,
+                                    grad_out_dev, grad_out_stride_elems, F, self_scale, grad_x_dev),
+                           workspace_dev, workspace_bytes, stream);
 }
 
 // ================================================================================================
-// Aggregation by descriptor (include/spp.h: spp_agg_fwd_desc, spp_agg_bwd_desc): the launchers above with the element
-// types chosen per call -- fp32 / fp16 / bf16 rows in, fp32 / bf16 out -- for bf16 autocast training.
+// Aggregation by descriptor (include/spp.h: spp_agg_fwd_desc, spp_agg_bwd_desc): agg_forward_desc / agg_backward_desc
+// with the element types chosen per call -- fp32 / fp16 / bf16 (or, through its own entry, fp8) rows in, fp32 / bf16
+// out -- for bf16 autocast training.
 // ================================================================================================
 extern "C" spp_status spp_agg_forward(const spp_agg_fwd_desc* desc, void* stream) {
-  static const char* who = "spp_agg_forward";
-  SPP_REQUIRE(desc, "%s: NULL descriptor", who);
-  const spp_agg_fwd_desc& d = *desc;
-  SPP_REQUIRE(d.source >= SPP_AGG_DENSE && d.source <= SPP_AGG_ROWS, "%s: unknown source %d", who, (int)d.source);
-  SPP_REQUIRE(d.epilogue >= SPP_AGG_MEAN && d.epilogue <= SPP_AGG_SUM, "%s: unknown epilogue %d", who, (int)d.epilogue);
-  SPP_REQUIRE(elem_ok(d.x_elem) && f32_bf16_ok(d.out_elem), "%s: unknown or unsupported element code (x %d, out %d)", who,
-              (int)d.x_elem, (int)d.out_elem);
-  const int64_t T = d.num_targets, F = d.F;
-  SPP_REQUIRE(T >= 0 && F >= 0, "%s: negative size", who);
-  const bool operand = d.epilogue == SPP_AGG_OPERAND || d.epilogue == SPP_AGG_OPERAND_ACT;
-  const int64_t width = operand ? 2 * F : F;
-  const int64_t out_stride = d.out_stride_elems > 0 ? d.out_stride_elems : width;
-  SPP_REQUIRE(out_stride >= width, "%s: output stride smaller than the output row", who);
-  if (T == 0 || F == 0) return SPP_OK;
-  SPP_REQUIRE(d.rowptr_dev && d.out_dev &&
-                  (d.source == SPP_AGG_ROWS ? d.n_id_dev != nullptr
-                                            : d.x_dev && (d.source == SPP_AGG_DENSE || (d.n_id_dev && d.x_rows > 0))),
-              "%s: NULL buffer or empty table", who);
-  if (d.epilogue == SPP_AGG_OPERAND_ACT) {
-    const int64_t esz = elem_bytes(d.x_elem), osz = elem_bytes(d.out_elem);
-    SPP_REQUIRE(d.source == SPP_AGG_DENSE && f32_bf16_ok(d.x_elem) && d.x_stride_elems == F && F % 4 == 0 &&
-                    out_stride % 4 == 0 && reinterpret_cast<uintptr_t>(d.x_dev) % (4 * esz) == 0 &&
-                    reinterpret_cast<uintptr_t>(d.out_dev) % (4 * osz) == 0 && d.p >= 0.f && d.p < 1.f,
-                "%s: the activated operand needs dense fp32 / bf16 rows, F %% 4 == 0, aligned buffers and 0 <= p < 1", who);
-    const Mean<true> epi{1, act_args(d.p, d.training, d.seed)};
-    with_f32_bf16(d.out_elem, [&](auto tout) {
-      with_f32_bf16(d.x_elem, [&](auto tin) {
-        launch_agg_fwd<typename decltype(tin)::type, typename decltype(tout)::type, true, Dense>(
-            d.rowptr_dev, d.col_dev, T, d.x_dev, F, nullptr, 0, F, epi, d.out_dev, out_stride, stream);
-      });
-    });
-    SPP_HIP_TRY(hipGetLastError());
-    return SPP_OK;
-  }
-  auto run = [&](auto src) {
-    using Src = decltype(src);
-    if (d.epilogue == SPP_AGG_SUM)
-      return agg_forward<Src>(who, d.rowptr_dev, d.col_dev, T, d.x_dev, d.x_elem, d.x_stride_elems, d.n_id_dev, d.x_rows,
-                              F, Sum{d.self_scale}, d.out_dev, d.out_elem, out_stride, stream);
-    return agg_forward<Src>(who, d.rowptr_dev, d.col_dev, T, d.x_dev, d.x_elem, d.x_stride_elems, d.n_id_dev, d.x_rows, F,
-                            Mean<false>{operand ? 1 : 0, {}}, d.out_dev, d.out_elem, out_stride, stream);
-  };
-  if (d.source == SPP_AGG_TABLE) return run(Table{});
-  if (d.source == SPP_AGG_ROWS) return run(Refs{});
-  return run(Dense{});
+  SPP_REQUIRE(desc, "spp_agg_forward: NULL descriptor");
+  SPP_REQUIRE(desc->x_elem != SPP_ELEM_FP8_E4M3, "spp_agg_forward: unsupported element code (x %d): fp8 rows and their "
+              "column exponents go through spp_agg_forward_fp8", (int)desc->x_elem);
+  return agg_forward_desc("spp_agg_forward", *desc, nullptr, stream);
 }
 
-// spp_agg_forward over an fp8 table (f3c): the same kernel with Tin = fp8e4m3 and the column exponents in Fp8<Epi>
+// spp_agg_forward over an fp8 table (f3c)
 extern "C" spp_status spp_agg_forward_fp8(const spp_agg_fwd_desc* desc, const int8_t* scale_log2_dev, void* stream) {
-  static const char* who = "spp_agg_forward_fp8";
-  SPP_REQUIRE(desc, "%s: NULL descriptor", who);
-  const spp_agg_fwd_desc& d = *desc;
-  SPP_REQUIRE(d.x_elem == SPP_ELEM_FP8_E4M3, "%s: x_elem must be SPP_ELEM_FP8_E4M3, got %d", who, (int)d.x_elem);
-  SPP_REQUIRE(d.source == SPP_AGG_DENSE || d.source == SPP_AGG_TABLE, "%s: source %d (dense rows or the table)", who,
-              (int)d.source);
-  SPP_REQUIRE(d.epilogue == SPP_AGG_MEAN || d.epilogue == SPP_AGG_OPERAND || d.epilogue == SPP_AGG_SUM,
-              "%s: epilogue %d (mean, operand or sum)", who, (int)d.epilogue);
-  SPP_REQUIRE(f32_bf16_ok(d.out_elem), "%s: unsupported output element code %d", who, (int)d.out_elem);
-  const int64_t T = d.num_targets, F = d.F;
-  SPP_REQUIRE(T >= 0 && F >= 0, "%s: negative size", who);
-  const bool operand = d.epilogue == SPP_AGG_OPERAND;
-  const int64_t width = operand ? 2 * F : F;
-  const int64_t out_stride = d.out_stride_elems > 0 ? d.out_stride_elems : width;
-  SPP_REQUIRE(out_stride >= width, "%s: output stride smaller than the output row", who);
-  if (T == 0 || F == 0) return SPP_OK;
-  SPP_REQUIRE(d.rowptr_dev && d.out_dev && d.x_dev && scale_log2_dev && (d.source == SPP_AGG_DENSE || (d.n_id_dev && d.x_rows > 0)),
-              "%s: NULL buffer or empty table", who);
-  const int64_t osz = elem_bytes(d.out_elem);
-  SPP_REQUIRE(d.x_stride_elems >= F, "%s: row stride smaller than the row", who);
-  SPP_REQUIRE(F % 4 == 0 && d.x_stride_elems % 4 == 0 && reinterpret_cast<uintptr_t>(d.x_dev) % 4 == 0 &&
-                  reinterpret_cast<uintptr_t>(scale_log2_dev) % 4 == 0 && out_stride % 4 == 0 &&
-                  reinterpret_cast<uintptr_t>(d.out_dev) % (4 * osz) == 0,
-              "%s: needs F %% 4 == 0, 4-byte aligned rows and exponents and an aligned output (F = %lld)", who, (long long)F);
-  auto run = [&](auto src, auto epi) {
-    using Src = decltype(src);
-    with_f32_bf16(d.out_elem, [&](auto tout) {
-      launch_agg_fwd<fp8e4m3, typename decltype(tout)::type, true, Src>(
-          d.rowptr_dev, d.col_dev, T, d.x_dev, d.x_stride_elems, d.n_id_dev, d.x_rows, F,
-          Fp8<decltype(epi)>{epi, scale_log2_dev}, d.out_dev, out_stride, stream);
-    });
-  };
-  auto by_epi = [&](auto src) {
-    if (d.epilogue == SPP_AGG_SUM)
-      run(src, Sum{d.self_scale});
-    else
-      run(src, Mean<false>{operand ? 1 : 0, {}});
-  };
-  if (d.source == SPP_AGG_TABLE)
-    by_epi(Table{});
-  else
-    by_epi(Dense{});
-  SPP_HIP_TRY(hipGetLastError());
-  return SPP_OK;
-}
-
-// the backward of one descriptor with its element types resolved (z is read by OPERAND_ACT only)
-template <typename Tg, typename Tz, typename Tout>
-static spp_status agg_backward_typed(const spp_agg_bwd_desc& d, void* workspace_dev, int64_t workspace_bytes,
-                                     void* stream) {
-  static const char* who = "spp_agg_backward";
-  const Tg* g = static_cast<const Tg*>(d.grad_out_dev);
-  const Tz* z = static_cast<const Tz*>(d.z_dev);
-  Tout* gx = static_cast<Tout*>(d.grad_x_dev);
-  const int64_t T = d.num_targets, S = d.num_sources, F = d.F;
-  const bool act = d.epilogue == SPP_AGG_OPERAND_ACT, operand = act || d.epilogue == SPP_AGG_OPERAND;
-  const int64_t gs = d.grad_out_stride_elems > 0 ? d.grad_out_stride_elems : (operand ? 2 * F : F);
-  if (act)
-    SPP_REQUIRE(z && reinterpret_cast<uintptr_t>(z) % (4 * sizeof(Tz)) == 0 && d.p >= 0.f && d.p < 1.f,
-                "%s: NULL / unaligned pre-activation or bad p", who);
-  if (d.form == SPP_AGG_GATHER) {
-    if (act)
-      return agg_backward_gather(who, d.rowptr_dev, d.col_dev, T, S, d.num_edges, g, gs, F,
-                                 Mean<true>{1, act_args(d.p, d.training, d.seed)}, gx, workspace_dev, workspace_bytes, z,
-                                 stream);
-    if (operand)
-      return agg_backward_gather(who, d.rowptr_dev, d.col_dev, T, S, d.num_edges, g, gs, F, Mean<false>{1, {}}, gx,
-                                 workspace_dev, workspace_bytes, (const float*)nullptr, stream);
-    return agg_backward_gather(who, d.rowptr_dev, d.col_dev, T, S, d.num_edges, g, gs, F, Sum{d.self_scale}, gx,
-                               workspace_dev, workspace_bytes, (const float*)nullptr, stream);
-  }
-  // scatter: fp32 atomics into an fp32 buffer (grad_x itself when it is fp32), then one pass that applies the
-  // activation's backward and / or rounds to bf16
-  SPP_REQUIRE(T >= 0 && S >= T && F >= 0, "%s: bad sizes", who);
-  if (S == 0 || F == 0) return SPP_OK;
-  SPP_REQUIRE(gx && ((g && d.rowptr_dev) || T == 0), "%s: NULL buffer", who);
-  SPP_REQUIRE(gs >= (operand ? 2 * F : F), "%s: gradient stride smaller than the row", who);
-  if (operand)
-    SPP_REQUIRE(F % 4 == 0 && gs % 4 == 0 && reinterpret_cast<uintptr_t>(g) % (4 * sizeof(Tg)) == 0 &&
-                    reinterpret_cast<uintptr_t>(gx) % (4 * sizeof(Tout)) == 0,
-                "%s: the operand's gradient needs F %% 4 == 0 and rows aligned to 4 elements", who);
-  const int64_t n = S * F;
-  float* acc = reinterpret_cast<float*>(gx);
-  if (!std::is_same<Tout, float>::value) {
-    SPP_REQUIRE(workspace_dev && reinterpret_cast<uintptr_t>(workspace_dev) % 16 == 0 && workspace_bytes >= 4 * n,
-                "%s: a bf16 scatter gradient needs a 16-byte aligned fp32 workspace of 4 * S * F bytes", who);
-    acc = static_cast<float*>(workspace_dev);
-  }
-  hipStream_t st = as_stream(stream);
-  if (operand) {
-    const unsigned g0 = (unsigned)std::min<int64_t>(ceil_div(n / 4, kAggNT), 256 * 32);
-    hipLaunchKernelGGL(k_grad_init<Tg>, dim3(g0), dim3(kAggNT), 0, st, g, gs, T, S, F, acc);
-    if (T > 0) launch_agg_bwd_scatter<Mean<false>>(d.rowptr_dev, d.col_dev, T, g, gs, F, acc, st);
-  } else if (d.epilogue == SPP_AGG_MEAN) {
-    SPP_HIP_TRY(hipMemsetAsync(acc, 0, 4 * (size_t)n, st));
-    if (T > 0) launch_agg_bwd_scatter<Mean<false>>(d.rowptr_dev, d.col_dev, T, g, gs, F, acc, st);
-  } else {
-    const unsigned g0 = (unsigned)std::min<int64_t>(ceil_div(n, kAggNT), 256 * 32);
-    hipLaunchKernelGGL(k_sum_grad_init<Tg>, dim3(g0), dim3(kAggNT), 0, st, g, gs, T, S, F, d.self_scale, acc);
-    if (T > 0) launch_agg_bwd_scatter<Sum>(d.rowptr_dev, d.col_dev, T, g, gs, F, acc, st);
-  }
-  const unsigned gp = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n / 4, kAggNT), 256 * 32));
-  if (act)
-    hipLaunchKernelGGL((k_relu_dropout_bwd_pre<Tz, Tout, true>), dim3(gp), dim3(kAggNT), 0, st, acc, z, n,
-                       act_args(d.p, d.training, d.seed), gx);
-  else if (!std::is_same<Tout, float>::value)
-    hipLaunchKernelGGL((k_relu_dropout_bwd_pre<float, Tout, false>), dim3(gp), dim3(kAggNT), 0, st, acc,
-                       (const float*)nullptr, n, ActArgs{}, gx);
-  SPP_HIP_TRY(hipGetLastError());
-  return SPP_OK;
+  SPP_REQUIRE(desc, "spp_agg_forward_fp8: NULL descriptor");
+  SPP_REQUIRE(desc->x_elem == SPP_ELEM_FP8_E4M3, "spp_agg_forward_fp8: x_elem must be SPP_ELEM_FP8_E4M3, got %d",
+              (int)desc->x_elem);
+  return agg_forward_desc("spp_agg_forward_fp8", *desc, scale_log2_dev, stream);
 }
 
 extern "C" spp_status spp_agg_backward(const spp_agg_bwd_desc* desc, void* workspace_dev, int64_t workspace_bytes,
                                        void* stream) {
-  static const char* who = "spp_agg_backward";
-  SPP_REQUIRE(desc, "%s: NULL descriptor", who);
-  const spp_agg_bwd_desc& d = *desc;
-  SPP_REQUIRE(d.form == SPP_AGG_SCATTER || d.form == SPP_AGG_GATHER, "%s: unknown form %d", who, (int)d.form);
-  SPP_REQUIRE(d.epilogue >= SPP_AGG_MEAN && d.epilogue <= SPP_AGG_SUM, "%s: unknown epilogue %d", who, (int)d.epilogue);
-  SPP_REQUIRE(f32_bf16_ok(d.grad_elem) && f32_bf16_ok(d.out_elem) && f32_bf16_ok(d.z_elem),
-              "%s: unknown or unsupported element code (grad %d, out %d, z %d)", who, (int)d.grad_elem, (int)d.out_elem,
-              (int)d.z_elem);
-  SPP_REQUIRE(!(d.epilogue == SPP_AGG_MEAN && d.form == SPP_AGG_GATHER), "%s: the plain mean has the scatter form only",
-              who);
-  spp_status rc = SPP_OK;
-  with_f32_bf16(d.grad_elem, [&](auto tg) {
-    with_f32_bf16(d.out_elem, [&](auto tout) {
-      using Tg = typename decltype(tg)::type;
-      using Tout = typename decltype(tout)::type;
-      if (d.epilogue == SPP_AGG_OPERAND_ACT && d.z_elem == SPP_ELEM_BF16)
-        rc = agg_backward_typed<Tg, bf16, Tout>(d, workspace_dev, workspace_bytes, stream);
-      else
-        rc = agg_backward_typed<Tg, float, Tout>(d, workspace_dev, workspace_bytes, stream);
-    });
-  });
-  return rc;
+  SPP_REQUIRE(desc, "spp_agg_backward: NULL descriptor");
+  return agg_backward_desc("spp_agg_backward", *desc, workspace_dev, workspace_bytes, stream);
 }
