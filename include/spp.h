@@ -471,6 +471,17 @@ spp_sampler* spp_session_sampler(spp_session* s);
  *        received rows, VIP cache} in the same launch that delivers the MFG and the labels.
  *        Every rank must run the same number of batches per epoch (force_exact_num_batches,
  *        as the reference's distributed mode requires).
+ *
+ *        fp8 partitions (f3c): with spp_exchange_cfg.x_elem = SPP_ELEM_FP8_E4M3 the partition, the cache and
+ *        everything the exchange moves (served rows, send / receive buffers) are e4m3 bytes, row_bytes = F per
+ *        row -- 4 + F algorithmic bytes per remote row on the wire against 4 + 2F for fp16 -- and only the
+ *        assembly inside the delivery launch knows the element type: it writes fp16 rows
+ *        x[r, c] = fp16(float32(q[r, c]) * 2^scale_log2[c]) (rounded once, to nearest even: the contract of
+ *        spp_gather_rows_fp8), so the OUTPUT row pitch of spp_session_export / spp_session_export_group is
+ *        2 * row_bytes and the caller sizes x_out_dev accordingly.  A row quantised by its owner is
+ *        dequantised by its requester: every rank must hold the same column exponents, which the creation-time
+ *        rendezvous checks (scales_tag).  The three fp8 fields sit at the END of spp_exchange_cfg: a
+ *        zero-initialised struct (x_elem = 0) moves and assembles bytes exactly as before.
  * ------------------------------------------------------------------------- */
 typedef struct spp_comm spp_comm;
 
@@ -515,6 +526,16 @@ typedef struct spp_exchange_cfg {
                                       interleaves collectives of its own communicator, e.g. DDP gradient
                                       all-reduces: both communicators' kernels are then queued in the
                                       same order on every rank.                                      */
+  /* Element type of the rows.  SPP_ELEM_F32 (0) / SPP_ELEM_F16 / SPP_ELEM_BF16: opaque bytes, delivered as they are.
+   * SPP_ELEM_FP8_E4M3: e4m3 rows with per-column exponents, delivered as fp16 (see e1-e3 above).  Needs
+   * row_bytes % 16 == 0, row strides that are multiples of 16, 16-byte aligned x_local_dev / cache_feats_dev /
+   * scale_log2_dev, and the exchange over `comm` (peer_x_dev == NULL). */
+  int32_t x_elem;
+  const int8_t* scale_log2_dev;    /* [row_bytes] column exponents in [-64, 63], HBM; required iff fp8; must stay
+                                      allocated while the Session lives                               */
+  uint64_t scales_tag;             /* hash of the row_bytes exponent bytes (FNV-1a 64; 0 for a non-fp8 session):
+                                      compared across the ranks at creation, a mismatch fails
+                                      spp_session_create on every rank                                */
 } spp_exchange_cfg;
 
 /* Cross-process mapping of a device allocation (hipIpcGetMemHandle / hipIpcOpenMemHandle), for the P2P transport:
@@ -824,7 +845,7 @@ spp_status spp_csr_sum_backward_gather(const int64_t* rowptr_dev, const int64_t*
  *   An unknown source, epilogue, form or element code, or an element type an epilogue does not take, returns
  *   SPP_ERR_INVALID before anything is launched.
  * ------------------------------------------------------------------------- */
-enum { SPP_ELEM_F32 = 0, SPP_ELEM_F16 = 1, SPP_ELEM_BF16 = 2, SPP_ELEM_FP8_E4M3 = 3 /* spp_agg_forward_fp8 only */ };
+enum { SPP_ELEM_F32 = 0, SPP_ELEM_F16 = 1, SPP_ELEM_BF16 = 2, SPP_ELEM_FP8_E4M3 = 3 /* spp_agg_forward_fp8, spp_exchange_cfg.x_elem */ };
 enum { SPP_AGG_DENSE = 0, SPP_AGG_TABLE = 1, SPP_AGG_ROWS = 2 };
 enum { SPP_AGG_MEAN = 0, SPP_AGG_OPERAND = 1, SPP_AGG_OPERAND_ACT = 2, SPP_AGG_SUM = 3 };
 enum { SPP_AGG_SCATTER = 0, SPP_AGG_GATHER = 1 };

@@ -59,7 +59,7 @@ class MfgOut(C.Structure):
 
 # spp_elem and the aggregation descriptor's codes (include/spp.h)
 SPP_ELEM_F32, SPP_ELEM_F16, SPP_ELEM_BF16 = 0, 1, 2
-SPP_ELEM_FP8_E4M3 = 3            # spp_agg_forward_fp8 only
+SPP_ELEM_FP8_E4M3 = 3            # spp_agg_forward_fp8, spp_exchange_cfg.x_elem
 SPP_AGG_DENSE, SPP_AGG_TABLE, SPP_AGG_ROWS = 0, 1, 2
 SPP_AGG_MEAN, SPP_AGG_OPERAND, SPP_AGG_OPERAND_ACT, SPP_AGG_SUM = 0, 1, 2, 3
 SPP_AGG_SCATTER, SPP_AGG_GATHER = 0, 1
@@ -88,7 +88,9 @@ class ExchangeCfg(C.Structure):
     _fields_ = [("comm", p), ("x_local_dev", p), ("x_local_rows", i64), ("row_bytes", i64),
                 ("cache_feats_dev", p), ("cache_rows", i64), ("x_local_stride_bytes", i64),
                 ("cache_stride_bytes", i64), ("peer_x_dev", C.POINTER(p)), ("peer_x_stride_bytes", i64),
-                ("issue_on_consumer", i32)]
+                ("issue_on_consumer", i32),
+                # appended for fp8 partitions; all zero = rows are opaque bytes, as before
+                ("x_elem", i32), ("scale_log2_dev", p), ("scales_tag", C.c_uint64)]
 
 
 class SessionCfg(C.Structure):

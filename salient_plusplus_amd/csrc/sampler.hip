@@ -59,6 +59,7 @@
 #include <mutex>
 #include <tuple>
 
+#include "fp8_body.hip.h"
 #include "gather_body.hip.h"
 #include "partition_common.hip.h"
 
@@ -2096,6 +2097,9 @@ struct DeliverArgs {
   int64_t* addr_out;
   char* xr_dst;
   int32_t xr_cnt[SPP_MAX_PARTS];
+  // fp8 partition (spp_exchange_cfg.x_elem): the three sources hold e4m3 rows of x_row_bytes bytes, x_dst gets fp16 rows
+  // 2 * x_row_bytes apart; the column exponents [x_row_bytes].  Read by the kFp8 instantiations only.
+  const int8_t* x_scales;
 };
 
 // The same for a whole GROUP of batches in ONE launch (spp_session_export_group).  A launch per batch left the
@@ -2118,7 +2122,30 @@ __device__ __forceinline__ const char* deliver_row_address(const DeliverArgs& a,
   return a.xr_dst + (xr_off[c.x] + c.y) * a.x_row_bytes;   // its copy in x_remote (segment-wise, below)
 }
 
-template <int VEC, bool kP2P>
+// fp8 assembly: the fp16 assembly below (own partition / VIP cache / received rows, chosen per row from psrc) with the
+// dequantising loop of k_gather_rows_fp8 in the place of the copy (fp8_body.hip.h).  The received rows' bases go through
+// LDS: a per-lane index into the argument block costs a private copy of it (see the P2P branch).
+__device__ __forceinline__ void assemble_fp8_rows(const DeliverArgs& a, int b) {
+  __shared__ int64_t recv_row0[SPP_MAX_PARTS];
+  for (int m = 0; m < a.P; ++m)
+    if ((int)threadIdx.x == m) recv_row0[m] = a.recv_base[m];
+  __syncthreads();
+  const int2* __restrict__ psrc = a.psrc;
+  const char* xl = a.x_src;
+  const char* xc = a.cache;
+  const char* xr = a.recv;
+  const int64_t xs = a.x_src_stride, cs = a.cache_stride, rb = a.x_row_bytes;
+  const int32_t rank = a.rank, P = a.P;
+  dequant_rows_body([=](int64_t r) { return psrc[r]; },
+                    [=](int2 c) -> const char* {
+                      if (c.x == rank) return xl + (int64_t)c.y * xs;
+                      if (c.x == P) return xc + (int64_t)c.y * cs;
+                      return xr + (recv_row0[c.x] + c.y) * rb;
+                    },
+                    a.x_scales, a.x_rows, rb, a.x_chunks, a.x_lpr_log2, a.x_dst, b, a.nb_x);
+}
+
+template <int VEC, bool kP2P, bool kFp8>
 __device__ __forceinline__ void deliver_body(const DeliverArgs& a, int b) {
   if (b >= a.nb_x && b < a.nb_x + a.nb_a) {
     // row references: one address per row, four rows per thread and round (psrc / n_ids loads of a round in flight together)
@@ -2173,7 +2200,9 @@ __device__ __forceinline__ void deliver_body(const DeliverArgs& a, int b) {
   }
   if (b >= a.nb_x) b -= a.nb_a + a.nb_r;
   if (b < a.nb_x) {
-    if (!a.asm_on) {
+    if constexpr (kFp8) {
+      assemble_fp8_rows(a, b);  // (the host launches this instantiation for an fp8 assembly only: asm_on, no P2P)
+    } else if (!a.asm_on) {
 #ifndef SPP_DELIVER_NT
 #define SPP_DELIVER_NT false   // non-temporal LOADS of the source rows (measurement aid: profiles/r04_ab_INDEX.md)
 #endif
@@ -2243,17 +2272,21 @@ __device__ __forceinline__ void deliver_body(const DeliverArgs& a, int b) {
 #endif
 // kP2P: the assembly reads remote rows in their owners' partitions (a kernel of its own: its wider source records must
 // not cost the default delivery registers -- 76 = six waves per SIMD)
-template <int VEC, bool kP2P = false>
+// kFp8: the assembly dequantises e4m3 rows to fp16 (VEC = 16; a kernel of its own for the same reason: the 16 scale
+// factors and the conversion's temporaries belong to it alone)
+template <int VEC, bool kP2P = false, bool kFp8 = false>
 __global__ __launch_bounds__(kGatherThreads) SPP_DELIVER_ATTR void k_deliver(DeliverArgs a) {
   static_assert(kGatherThreads == kNT, "one workgroup shape for all three parts");
-  deliver_body<VEC, kP2P>(a, (int)blockIdx.x);
+  static_assert(!kFp8 || (VEC == 16 && !kP2P), "the fp8 assembly reads 16-byte pieces over the exchange transport");
+  deliver_body<VEC, kP2P, kFp8>(a, (int)blockIdx.x);
 }
 
-template <int VEC, bool kP2P = false>
+template <int VEC, bool kP2P = false, bool kFp8 = false>
 __global__ __launch_bounds__(kGatherThreads) void k_deliver_group(const DeliverArgs* __restrict__ args, GroupBlocks gb) {
+  static_assert(!kFp8 || (VEC == 16 && !kP2P), "the fp8 assembly reads 16-byte pieces over the exchange transport");
   int i = 0;
   while (i + 1 < gb.n && (int)blockIdx.x >= gb.start[i + 1]) ++i;  // uniform: a handful of scalar compares
-  deliver_body<VEC, kP2P>(args[i], (int)blockIdx.x - gb.start[i]);
+  deliver_body<VEC, kP2P, kFp8>(args[i], (int)blockIdx.x - gb.start[i]);
 }
 
 }  // namespace spp
@@ -3403,6 +3436,11 @@ static spp_status fill_deliver_args(spp_sampler* s, int slot, const spp_mfg_out*
       }
     }
     SPP_REQUIRE(hs->pcnt[s->part.P] == 0 || asrc->cache, "sampler_deliver: cache hits without cache rows");
+    if (asrc->fp8_scales) {
+      SPP_REQUIRE(!asrc->p2p, "sampler_deliver: fp8 rows are not read over the P2P transport");
+      SPP_REQUIRE(!(mfg && mfg->row_addr), "sampler_deliver: row references of an fp8 partition are not supported");
+      a.x_scales = asrc->fp8_scales;
+    }
   }
   // row references instead of rows (spp_mfg_out.row_addr; the caller passes no x destination)
   if (mfg && mfg->row_addr && !x_dst && (x_src || asrc) && U > 0 && x_row_bytes > 0) {
@@ -3444,6 +3482,9 @@ static spp_status fill_deliver_args(spp_sampler* s, int slot, const spp_mfg_out*
                                           /*allow_span=*/!asrc);  // (received rows are dense: no padding to read into)
     a.x_src_stride = x_src_stride;
     vec = gg.vec;
+    // fp8: 16-byte pieces of F-byte source rows (spp_session_create checked the tables; the receive buffers are
+    // allocations of this library); the destination holds fp16 rows of 2 * F bytes
+    SPP_REQUIRE(!a.x_scales || vec == 16, "sampler_deliver: an fp8 assembly needs 16-byte aligned sources and destination");
     a.x_src = static_cast<const char*>(x_src);
     a.x_dst = static_cast<char*>(x_dst);
     a.x_rows = U;
@@ -3475,7 +3516,9 @@ spp_status sampler_deliver(spp_sampler* s, int slot, const spp_mfg_out* mfg, con
   const unsigned grid = (unsigned)(a.nb_x + a.nb_a + a.nb_r + a.nb_e + a.nb_y);
   if (grid == 0) return SPP_OK;
   const int prof = prof_begin(SPP_PROF_GATHER, st, a.x_rows);
-  if (a.p2p && a.nb_x > 0) {
+  if (a.x_scales && a.nb_x > 0) {
+    hipLaunchKernelGGL((k_deliver<16, false, true>), dim3(grid), dim3(kGatherThreads), 0, st, a);
+  } else if (a.p2p && a.nb_x > 0) {
     switch (vec) {
       case 16: hipLaunchKernelGGL((k_deliver<16, true>), dim3(grid), dim3(kGatherThreads), 0, st, a); break;
       case 8: hipLaunchKernelGGL((k_deliver<8, true>), dim3(grid), dim3(kGatherThreads), 0, st, a); break;
@@ -3564,7 +3607,10 @@ spp_status sampler_deliver_group(spp_sampler* s, int set, int first_slot, int n,
   SPP_HIP_TRY(hipMemcpyAsync(s->dargs_dev[set], ha, sizeof(DeliverArgs) * (size_t)n, hipMemcpyHostToDevice, st));
   const int prof = prof_begin(SPP_PROF_GATHER, st, rows);
   const DeliverArgs* da = s->dargs_dev[set];
-  if (asrc && asrc[0].p2p) {
+  if (asrc && asrc[0].fp8_scales) {
+    SPP_REQUIRE(vec == 16, "sampler_deliver_group: an fp8 assembly needs 16-byte aligned sources and destinations");
+    hipLaunchKernelGGL((k_deliver_group<16, false, true>), dim3((unsigned)blocks), dim3(kGatherThreads), 0, st, da, gb);
+  } else if (asrc && asrc[0].p2p) {
     switch (vec) {
       case 16: hipLaunchKernelGGL((k_deliver_group<16, true>), dim3((unsigned)blocks), dim3(kGatherThreads), 0, st, da, gb); break;
       case 8: hipLaunchKernelGGL((k_deliver_group<8, true>), dim3((unsigned)blocks), dim3(kGatherThreads), 0, st, da, gb); break;

@@ -107,6 +107,9 @@ struct AssembleSrc {
   bool p2p = false;
   const char* peer[SPP_MAX_PARTS] = {};
   int64_t peer_stride = 0;
+  // fp8 partition (spp_exchange_cfg.x_elem = SPP_ELEM_FP8_E4M3): all three sources hold e4m3 rows of x_row_bytes
+  // bytes, the assembly writes fp16 rows of twice that; the column exponents [x_row_bytes] (NULL: rows are bytes)
+  const int8_t* fp8_scales = nullptr;
 };
 
 // Fused delivery of the waited batch in `slot` to caller buffers in one launch on `st`:

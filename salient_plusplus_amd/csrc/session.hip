@@ -519,6 +519,24 @@ static spp_status exchange_setup(spp_session* s, const spp_exchange_cfg* xc, con
   if (s->xcfg.cache_stride_bytes <= 0) s->xcfg.cache_stride_bytes = xc->row_bytes;
   SPP_REQUIRE(s->xcfg.x_local_stride_bytes >= xc->row_bytes && s->xcfg.cache_stride_bytes >= xc->row_bytes,
               "spp_session_create: row strides must be at least row_bytes");
+  const bool fp8 = xc->x_elem == SPP_ELEM_FP8_E4M3;
+  SPP_REQUIRE(fp8 || xc->x_elem == SPP_ELEM_F32 || xc->x_elem == SPP_ELEM_F16 || xc->x_elem == SPP_ELEM_BF16,
+              "spp_session_create: unknown spp_exchange_cfg.x_elem %d", xc->x_elem);
+  if (fp8) {
+    // what the dequantising assembly relies on (sampler.hip assemble_fp8_rows): 16-byte pieces everywhere
+    SPP_REQUIRE(xc->row_bytes % 16 == 0, "spp_session_create: fp8 rows must be a multiple of 16 bytes wide (row_bytes %lld)",
+                (long long)xc->row_bytes);
+    SPP_REQUIRE(xc->scale_log2_dev && (reinterpret_cast<uintptr_t>(xc->scale_log2_dev) & 15) == 0,
+                "spp_session_create: an fp8 partition needs its column scales (scale_log2_dev, 16-byte aligned)");
+    SPP_REQUIRE(!p2p, "spp_session_create: fp8 rows are not read over the P2P transport (peer_x_dev must be NULL)");
+    SPP_REQUIRE(s->xcfg.x_local_stride_bytes % 16 == 0 && s->xcfg.cache_stride_bytes % 16 == 0,
+                "spp_session_create: fp8 row strides must be multiples of 16 bytes");
+    SPP_REQUIRE(((reinterpret_cast<uintptr_t>(xc->x_local_dev) | reinterpret_cast<uintptr_t>(xc->cache_feats_dev)) & 15) == 0,
+                "spp_session_create: the fp8 partition and cache rows must be 16-byte aligned");
+  } else {
+    SPP_REQUIRE(!xc->scale_log2_dev && xc->scales_tag == 0,
+                "spp_session_create: column scales (scale_log2_dev / scales_tag) belong to x_elem = SPP_ELEM_FP8_E4M3");
+  }
   s->P = part.num_parts;
   s->rank = part.rank;
   s->rank_offset = part.offsets[part.rank];
@@ -540,7 +558,7 @@ static spp_status exchange_setup(spp_session* s, const spp_exchange_cfg* xc, con
   const size_t cnt_elems = (size_t)s->G * (size_t)s->P;
   for (size_t k = 0; k < s->xsets.size(); ++k) s->xsets[k].b = sampler_xbuf(s->sampler, (int)k);
   for (auto& x : s->xsets) {
-    const size_t cnt_bytes = 8 * (cnt_elems * (size_t)(s->P + 2) + 2 * (size_t)s->P + 2);  // + the creation-time check
+    const size_t cnt_bytes = 8 * (cnt_elems * (size_t)(s->P + 2) + 3 * (size_t)s->P + 3);  // + the creation-time check
     SPP_TRY(sampler_xbuf_counts(s->sampler, x.b, (int64_t)cnt_bytes));
     x.cnt_dev = x.b->cnt_dev;
     x.cnt_host = x.b->cnt_host;
@@ -549,25 +567,36 @@ static spp_status exchange_setup(spp_session* s, const spp_exchange_cfg* xc, con
   }
   // Collective sanity check: the exchange is one collective sequence per group, so every rank must
   // run the same number of batches in groups of the same size (force_exact_num_batches in the
-  // reference's distributed mode); a mismatch would otherwise show up as a hang.
+  // reference's distributed mode); a mismatch would otherwise show up as a hang.  The third word is the tag of the
+  // fp8 column scales (0: rows are bytes): a row quantised by its owner is dequantised by its requester, so ranks whose
+  // exponents differ -- or an fp8 rank that meets an fp16 one -- would deliver wrong values without any other symptom.
+  // Every rank sees every word, so a disagreement fails the creation on all of them.
   {
     XSet& x0 = s->xsets[0];
+    const uint64_t tag = fp8 ? xc->scales_tag : 0;
     x0.cnt_host[0] = (int64_t)s->ranges.size();
     x0.cnt_host[1] = s->G;
-    SPP_HIP_TRY(hipMemcpyAsync(x0.cnt_dev, x0.cnt_host, 16, hipMemcpyHostToDevice, s->comm_stream));
-    SPP_TRY(tr->all_gather(x0.cnt_dev, x0.cnt_dev + 2, 16, s->comm_stream));
-    SPP_HIP_TRY(hipMemcpyAsync(x0.cnt_host + 2, x0.cnt_dev + 2, 16 * (size_t)s->P, hipMemcpyDeviceToHost, s->comm_stream));
+    x0.cnt_host[2] = (int64_t)tag;
+    SPP_HIP_TRY(hipMemcpyAsync(x0.cnt_dev, x0.cnt_host, 24, hipMemcpyHostToDevice, s->comm_stream));
+    SPP_TRY(tr->all_gather(x0.cnt_dev, x0.cnt_dev + 3, 24, s->comm_stream));
+    SPP_HIP_TRY(hipMemcpyAsync(x0.cnt_host + 3, x0.cnt_dev + 3, 24 * (size_t)s->P, hipMemcpyDeviceToHost, s->comm_stream));
     SPP_HIP_TRY(hipEventRecord(x0.cnt_ready, s->comm_stream));
     s->tr = tr;  // wait_peers aborts it on a timeout
     const spp_status wrc = wait_peers(s, x0.cnt_ready, "session creation (batch-count check)", -1);
     s->tr = nullptr;
     SPP_TRY(wrc);
     for (int m = 0; m < s->P; ++m)
-      SPP_REQUIRE(x0.cnt_host[2 + 2 * m] == x0.cnt_host[0] && x0.cnt_host[3 + 2 * m] == x0.cnt_host[1],
+      SPP_REQUIRE(x0.cnt_host[3 + 3 * m] == x0.cnt_host[0] && x0.cnt_host[4 + 3 * m] == x0.cnt_host[1],
                   "spp_session_create: rank %d runs %lld batches in groups of %lld, rank %d runs %lld in groups of %lld "
                   "(every rank must run the same number of batches)",
-                  s->rank, (long long)x0.cnt_host[0], (long long)x0.cnt_host[1], m, (long long)x0.cnt_host[2 + 2 * m],
-                  (long long)x0.cnt_host[3 + 2 * m]);
+                  s->rank, (long long)x0.cnt_host[0], (long long)x0.cnt_host[1], m, (long long)x0.cnt_host[3 + 3 * m],
+                  (long long)x0.cnt_host[4 + 3 * m]);
+    for (int a = 0; a < s->P; ++a)
+      for (int b = a + 1; b < s->P; ++b)
+        SPP_REQUIRE(x0.cnt_host[5 + 3 * a] == x0.cnt_host[5 + 3 * b],
+                    "spp_session_create: the ranks disagree on the fp8 column scales: rank %d has scales tag %016llx, rank %d "
+                    "%016llx (0 = not an fp8 partition); every rank must quantise against the same per-column exponents",
+                    a, (unsigned long long)x0.cnt_host[5 + 3 * a], b, (unsigned long long)x0.cnt_host[5 + 3 * b]);
   }
   s->tr = tr;
   return SPP_OK;
@@ -923,6 +952,7 @@ static void fill_assemble_src(const spp_session* s, int64_t g, int member, Assem
   src->cache = static_cast<const char*>(s->xcfg.cache_feats_dev);
   src->x_local_stride = s->xcfg.x_local_stride_bytes;
   src->cache_stride = s->xcfg.cache_stride_bytes;
+  if (s->xcfg.x_elem == SPP_ELEM_FP8_E4M3) src->fp8_scales = s->xcfg.scale_log2_dev;
   if (s->p2p) {
     src->p2p = true;
     src->peer_stride = s->peer_stride;

@@ -198,17 +198,19 @@ def fp8_gather_rows(table: Fp8Features, n_id: torch.Tensor, out: Optional[torch.
     return out
 
 
-def fp8_session_check(config, row_refs: bool = False) -> bool:
-    """True when the configuration's feature table is an Fp8Features.  The fp8 table is read by the single-GPU,
-    non-distributed session only: anything else is refused here -- at construction, before any device call."""
+def fp8_session_check(config, row_refs: bool = False, table_features: bool = False) -> bool:
+    """True when the configuration's ``x_cpu`` is an Fp8Features: the table of a single-GPU, non-distributed session.
+    An Fp8Features as ``x_gpu`` is this rank's partition of a distributed session (native exchange, optional VIP cache
+    of fp8 rows): checked here too, and False is returned.  Anything outside these two scopes is refused here -- at
+    construction, before any device call."""
     if not isinstance(getattr(config, "x_cpu", None), Fp8Features):
         if isinstance(getattr(config, "x_gpu", None), Fp8Features):
-            raise RuntimeError("fp8 feature table: hand it over as x_cpu (x_gpu belongs to the partitioned path, which does "
-                               "not read fp8 rows)")
+            _fp8_partition_check(config, row_refs, table_features)
         return False
     if bool(config.distributed):
-        raise RuntimeError("fp8 feature table: distributed=True is not supported (the partitioned RCCL / P2P paths exchange "
-                           "fp16 / fp32 rows); use a single-GPU session")
+        raise RuntimeError("fp8 feature table: distributed=True is not supported with the table as x_cpu (the partitioned "
+                           "path reads this rank's fp8 rows from x_gpu, with an empty x_cpu); use a single-GPU session or "
+                           "hand the partition over as x_gpu")
     cache = getattr(config, "cache", None)
     if bool(config.use_cache) or (cache is not None and getattr(cache, "cached_vertices", None) is not None and
                                   cache.cached_vertices.numel() > 0):
@@ -217,6 +219,72 @@ def fp8_session_check(config, row_refs: bool = False) -> bool:
         raise RuntimeError("fp8 feature table: row_refs is not supported (row references belong to the partitioned path); "
                            "use table_features")
     return True
+
+
+def _fp8_partition_check(config, row_refs: bool, table_features: bool) -> None:
+    """x_gpu = Fp8Features: this rank's rows of a partitioned fp8 table (everything checked on the host)"""
+    part = config.x_gpu
+    x_cpu = getattr(config, "x_cpu", None)
+    if x_cpu is not None and x_cpu.numel() > 0:
+        raise RuntimeError("fp8 feature table: an fp8 partition (x_gpu) holds ALL of this rank's rows; x_cpu must be empty "
+                           "(a single-GPU session takes the table as x_cpu instead)")
+    if not bool(config.distributed):
+        raise RuntimeError("fp8 feature table: hand it over as x_cpu (x_gpu is the table argument of the partitioned path: "
+                           "distributed=True with a partition_book)")
+    if getattr(config, "partition_book", None) is None:
+        raise RuntimeError("fp8 feature table: a partitioned session needs a partition_book")
+    if row_refs:
+        raise RuntimeError("fp8 feature table: row_refs is not supported on partitioned sessions (the delivery dequantises "
+                           "while it assembles x)")
+    if table_features:
+        raise RuntimeError("fp8 feature table: table_features is not supported on partitioned sessions (the rows of a batch "
+                           "come from three sources)")
+    cache = getattr(config, "cache", None)
+    cf = getattr(cache, "cached_features", None)
+    if bool(config.use_cache) and cache is not None and cache.cached_vertices.numel() > 0:
+        if not isinstance(cf, Fp8Features):
+            raise RuntimeError("fp8 feature table: the VIP cache of an fp8 partition must hold fp8 rows "
+                               "(Cache(rank, P, cached_vertices, Fp8Features))")
+        if cf.size(1) != part.size(1):
+            raise RuntimeError(f"fp8 feature table: the cache's width ({cf.size(1)}) differs from the partition's "
+                               f"({part.size(1)})")
+        if not torch.equal(cf.scale_log2.cpu(), part.scale_log2.cpu()):
+            raise RuntimeError("fp8 feature table: the cache's column scales differ from the partition's (every rank and "
+                               "every cache must share one scale_log2: fp8.column_scales / quantize_e4m3(x, scale_log2=...))")
+
+
+def _fp8_partition_transport(config):
+    """The native communicator an fp8 partition is exchanged over.  Only the native exchange (RCCL, or the in-process
+    transport of the tests) moves fp8 rows: every other way a partitioned Session can get its remote rows is refused."""
+    mode = os.environ.get("SPP_DIST_TRANSPORT", "rccl").lower()
+    if mode == "p2p":
+        raise RuntimeError("fp8 feature table: the P2P transport (SPP_DIST_TRANSPORT=p2p) does not read fp8 rows; use the "
+                           "native exchange")
+    if mode == "torch":
+        raise RuntimeError("fp8 feature table: the torch-collective transport (SPP_DIST_TRANSPORT=torch) does not move fp8 "
+                           "rows; use the native exchange")
+    if os.environ.get("SPP_ROW_REFS", "0") != "0":
+        raise RuntimeError("fp8 feature table: row_refs (SPP_ROW_REFS) is not supported on partitioned sessions")
+    if os.environ.get("SPP_TABLE_FEATURES", "0") != "0":
+        raise RuntimeError("fp8 feature table: table_features (SPP_TABLE_FEATURES) is not supported on partitioned sessions")
+    comm = native_comm()
+    pb = config.partition_book
+    if comm is None or (comm.world, comm.rank) != (int(pb.world_size), int(pb.rank)):
+        raise RuntimeError("fp8 feature table: no native communicator matches the partition book, and the fallback -- the "
+                           "torch-collective prefetcher -- does not move fp8 rows (NCCL process group, or set_native_comm)")
+    return comm
+
+
+def _fnv1a64(data: bytes) -> int:
+    h = 0xcbf29ce484222325
+    for b in data:
+        h = ((h ^ b) * 0x100000001b3) & 0xffffffffffffffff
+    return h
+
+
+def fp8_scales_tag(scale_log2: torch.Tensor) -> int:
+    """spp_exchange_cfg.scales_tag: FNV-1a (64 bit) of the F exponent bytes; never 0 (0 says: not an fp8 session)"""
+    return _fnv1a64(scale_log2.cpu().contiguous().view(torch.uint8).numpy().tobytes()) or 1
 
 
 class TableRows:
@@ -457,7 +525,8 @@ class RangePartitionBook:
 
 class Cache:
     """``Cache()`` / ``Cache(rank, world_size, cached_vertices, cached_features)``
-    (range_partition_book.hpp:60-91).  The reference's two dense 2e8-entry host tables become one
+    (range_partition_book.hpp:60-91); ``cached_features`` of an fp8 partition is an ``Fp8Features`` with the partition's
+    column scales.  The reference's two dense 2e8-entry host tables become one
     device-resident direct map ``int32[max_id+1]`` (-1 = not cached), built by spp_cache_build_map."""
 
     def __init__(self, rank: int = 0, world_size: int = 0, cached_vertices: Optional[torch.Tensor] = None,
@@ -485,7 +554,11 @@ class Cache:
             self._map = m
         return self._map
 
-    def device_features(self) -> torch.Tensor:
+    def device_features(self):
+        """the cached rows resident in HBM (an Fp8Features stays one)"""
+        if self._features_dev is None and isinstance(self.cached_features, Fp8Features):
+            f = self.cached_features
+            self._features_dev = Fp8Features._wrap(_resident.get(f.q), _resident.get(f.scale_log2))
         if self._features_dev is None:
             self._features_dev = _resident.get_rows(self.cached_features) if self.cached_features.dim() == 2 \
                 else self.cached_features.to(_device()).contiguous()
@@ -757,6 +830,8 @@ def _host_ranges(n, batch_size, skip_nonfull, force_exact, exact_k):
 class Session:
     def __init__(self, num_threads: int, max_items_in_queue: int, config: Config):
         fp8 = fp8_session_check(config)    # an fp8 table outside its scope is refused before any device call
+        pfp8 = config.x_gpu if isinstance(getattr(config, "x_gpu", None), Fp8Features) else None
+        fp8_comm = _fp8_partition_transport(config) if pfp8 is not None else None      # (host checks as well)
         L = _lib()
         if max_items_in_queue <= 0:
             raise RuntimeError(f"max_items_in_queue ({max_items_in_queue}) must be positive")
@@ -773,12 +848,18 @@ class Session:
 
         # features / labels resident in HBM
         self._fp8 = None
+        self._pfp8 = None
         if fp8:
             # opt-in fp8 table: q and the column exponents resident; the batches' fp16 rows come from the dequantising
             # gather, launched behind each delivery on its stream (labels, MFG, ordering and buffering are untouched)
             f = config.x_cpu
             self._fp8 = Fp8Features._wrap(_resident.get(f.q), _resident.get(f.scale_log2)) if f.numel() else None
             self._x = None
+        elif pfp8 is not None:
+            # this rank's partition of an fp8 table: the exchange moves its rows as bytes ([rows, F] uint8, dense), the
+            # delivery's assembly dequantises them to fp16 with the resident column exponents
+            self._pfp8 = Fp8Features._wrap(_resident.get(pfp8.q), _resident.get(pfp8.scale_log2))
+            self._x = self._pfp8.q.view(torch.uint8)
         elif self._distributed:
             xg, xc = config.x_gpu, config.x_cpu
             parts = [t for t in (xg, xc) if t is not None and t.dim() == 2 and t.size(0) > 0]
@@ -859,7 +940,7 @@ class Session:
                 if len(peers.ptrs) != int(pb.world_size):
                     raise RuntimeError(f"P2P transport: {len(peers.ptrs)} peer tables for {int(pb.world_size)} partitions")
                 self._peers = peers
-            comm = None if p2p else native_comm()
+            comm = fp8_comm if fp8_comm is not None else (None if p2p else native_comm())
             if self._x is not None and (p2p or (comm is not None and
                                                 (comm.world, comm.rank) == (int(pb.world_size), int(pb.rank)))):
                 xc = nat.ExchangeCfg()
@@ -876,8 +957,17 @@ class Session:
                 # blocking_get_batch_distributed, at the same program point on every rank (safe next
                 # to the caller's own collectives, e.g. DDP all-reduces) -- the default
                 xc.issue_on_consumer = int(os.environ.get("SPP_EXCHANGE_ISSUE", "consumer").lower() != "thread")
+                if self._pfp8 is not None:
+                    xc.x_elem = nat.SPP_ELEM_FP8_E4M3
+                    xc.scale_log2_dev = self._pfp8.scale_log2.data_ptr()
+                    xc.scales_tag = fp8_scales_tag(pfp8.scale_log2)
                 if bool(config.use_cache):
                     self._cache_feats = config.cache.device_features()
+                    if isinstance(self._cache_feats, Fp8Features):
+                        if self._pfp8 is None:
+                            raise RuntimeError("cached_features: an fp8 cache needs an fp8 partition (x_gpu=Fp8Features)")
+                        self._cache_fp8 = self._cache_feats              # (keeps the resident pair alive)
+                        self._cache_feats = self._cache_feats.q.view(torch.uint8)
                     if self._cache_feats.numel():
                         if self._cache_feats.dtype != self._x.dtype or self._cache_feats.size(1) != self._x.size(1):
                             raise RuntimeError("cached_features must match the feature rows in dtype and width")
@@ -932,6 +1022,8 @@ class Session:
         self._consumer_stream = None
         self._e_id = torch.empty(0, dtype=torch.int64, device=self._dev)
         # (src pointer, rows, row bytes) of the resident feature / label matrices, built once
+        # what the delivery writes: the table's own element type, fp16 for an fp8 partition (dequantised in the assembly)
+        self._out_dtype = torch.float16 if self._pfp8 is not None else (self._x.dtype if self._x is not None else torch.float16)
         self._x_args = (C.c_void_p(self._x.data_ptr()), self._x.size(0), self._x.size(1) * self._x.element_size(),
                         _stride_bytes(self._x)) if self._x is not None and self._x.numel() else (None, 0, 0, 0)
         self._y_args = (C.c_void_p(self._y.data_ptr()), self._y.size(0), self._y.size(1) * self._y.element_size()) \
@@ -1174,6 +1266,8 @@ class Session:
             return False
         if self._fp8 is not None:
             return True
+        if self._pfp8 is not None:
+            raise RuntimeError("fp8 feature table: table_features is not supported on partitioned sessions")
         if self._distributed or self._x is None:
             raise RuntimeError("table_features: only single-GPU sessions with a feature table deliver TableRows "
                                "(a partitioned session assembles x from three sources: set row_refs there)")
@@ -1184,6 +1278,8 @@ class Session:
             return False
         if self._fp8 is not None:
             raise RuntimeError("fp8 feature table: row_refs is not supported; use table_features")
+        if self._pfp8 is not None:
+            raise RuntimeError("fp8 feature table: row_refs is not supported on partitioned sessions")
         if not (self._distributed and self.native_exchange and self._x is not None):
             raise RuntimeError("row_refs: only partitioned sessions with the native exchange (RCCL or P2P transport) deliver "
                                "RowRefs (single-GPU sessions: table_features)")
@@ -1301,7 +1397,7 @@ class Session:
             x_views = x_arena.split(Us + [x_arena.size(0) - sum(Us)])                       # every batch starts 32-byte aligned
         if want_x:
             F = self._x.size(1)
-            row_b = F * self._x.element_size()
+            row_b = F * self._out_dtype.itemsize     # (an fp8 partition delivers fp16: rows of 2F bytes)
             # every batch starts on a 16-byte boundary of the arena (rows of 16k + 8 bytes: on an even row), so that the
             # delivery may store 16-byte pieces whatever the batches before it hold (gather_body.hip.h, kVecSpan)
             x_align = 16 // math.gcd(row_b, 16)
@@ -1309,7 +1405,7 @@ class Session:
             for U in Us:
                 x_split += [U, (-U) % x_align]
             n_rows = sum(x_split)
-            x_arena = torch.empty((_coarse(n_rows), F), dtype=self._x.dtype, device=dev)
+            x_arena = torch.empty((_coarse(n_rows), F), dtype=self._out_dtype, device=dev)
             x_views = x_arena.split(x_split + [x_arena.size(0) - n_rows])[0::2]
             x_base = x_arena.data_ptr()
         xr_arena = xr_views = None
@@ -1400,7 +1496,7 @@ class Session:
     def _proto_record(self, x, y, adjs, rng, n_id, nids, flat, cached, perm, pc, native, count_remote, rank):
         b = ProtoDistributedBatch()
         feat_dim = self._x.size(1) if self._x is not None else 0
-        feat_dtype = self._x.dtype if self._x is not None else torch.float16
+        feat_dtype = self._out_dtype
         if nids is None:                               # compact native record: only what this repository's iterator reads
             nids, flat = [], None
             cached = perm = torch.empty(0, dtype=torch.int64, device=self._dev)
@@ -1544,7 +1640,7 @@ class Session:
             out, n_id, adjs = self._alloc_mfg(c)
             nids, flat = [], None
             cached = perm = torch.empty(0, dtype=torch.int64, device=self._dev)
-        x = torch.empty((c.num_nodes, self._x.size(1)), dtype=self._x.dtype, device=self._dev)
+        x = torch.empty((c.num_nodes, self._x.size(1)), dtype=self._out_dtype, device=self._dev)
         y = None
         if self._y is not None:
             y = torch.empty((d.stop - d.start, self._y.size(1)), dtype=self._y.dtype, device=self._dev)
@@ -1560,7 +1656,7 @@ class Session:
         b.cached_nids = cached
         b.perm_partition_to_mfg = perm
         b.partition_counts = [int(c.part_counts[m]) for m in range(P + 1)]
-        b.sliced_cpu_features = torch.empty((0, self._x.size(1)), dtype=self._x.dtype)
+        b.sliced_cpu_features = torch.empty((0, self._x.size(1)), dtype=self._out_dtype)
         b.sliced_cpu_labels = y if y is not None else torch.zeros(0)
         b.adjs = adjs
         b.idx_range = (int(d.start), int(d.stop))

@@ -226,7 +226,8 @@ class FastSamplerConfig:
     use_cache: bool
 
     def __post_init__(self):
-        # an fp8 feature table (fp8.Fp8Features as x_cpu) is read by the single-GPU session only: refused here otherwise
+        # an fp8 feature table (fp8.Fp8Features) is the x_cpu of a single-GPU session or the x_gpu of a partitioned one
+        # with the native exchange: anything else is refused here
         fast_sampler.fp8_session_check(self)
 
     def to_fast_sampler(self) -> fast_sampler.Config:
@@ -334,7 +335,8 @@ class FastSampler(ABCNeighborSampler):
     row_refs: bool = False
 
     def __post_init__(self):
-        fast_sampler.fp8_session_check(self.cfg, row_refs=self.row_refs)      # (row_refs is known here, not in the config)
+        # (row_refs / table_features are known here, not in the configuration)
+        fast_sampler.fp8_session_check(self.cfg, row_refs=self.row_refs, table_features=self.table_features)
 
     def __iter__(self):
         return FastSamplerIter(self.num_threads, self.max_items_in_queue, self.cfg, self.table_features, self.row_refs)

@@ -67,9 +67,18 @@ def rank_remote_vertices(strategy: str, partition_book, num_nodes: int, num_to_c
     raise ValueError(f"invalid cache strategy {strategy!r}")
 
 
+def _refuse_fp8(x_local):
+    if isinstance(x_local, fs.Fp8Features):
+        raise RuntimeError("VIP cache: fetching cache rows out of an fp8 partition is not supported (the fetch moves typed "
+                           "torch tensors); build the cache from rows quantised with the partition's scale_log2: "
+                           "Cache(rank, P, cached_vertices, fp8.quantize_e4m3(rows, scale_log2=...))")
+
+
 def fetch_cache_rows(partition_book, remote_vertices: torch.Tensor, x_local: torch.Tensor, group=None):
     """(cached_vertices, cached_features): the rows of `remote_vertices` fetched from their owners
-    (ddp.py:497-553: counts, ids, rows -- three synchronous all_to_alls, once per run)."""
+    (ddp.py:497-553: counts, ids, rows -- three synchronous all_to_alls, once per run).  The rows travel as typed
+    tensors (torch.distributed all_to_all of x_local's dtype), not as opaque bytes: an fp8 partition is refused."""
+    _refuse_fp8(x_local)
     L = nat.load()
     dev = remote_vertices.device
     P, rank = int(partition_book.world_size), int(partition_book.rank)
@@ -105,6 +114,7 @@ def create_vip_cache(partition_book, num_nodes: int, x_local: torch.Tensor, cach
                      remote_vertices_ordered_by_freq=None, group=None) -> "fs.Cache":
     """DDPDriver.create_vip_cache (ddp.py:417-570).  cache_size is the replication factor in
     percent of N/P (:421); x_local holds this rank's rows in HBM."""
+    _refuse_fp8(x_local)
     P, rank = int(partition_book.world_size), int(partition_book.rank)
     num_to_cache = int(num_nodes / P * (cache_size / 100))                          # :421
     if x_local.device.type != "cuda":
