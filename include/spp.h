@@ -918,6 +918,61 @@ spp_status spp_gather_rows_fp8(const void* q_dev, int64_t src_rows, int64_t F, c
                                const int64_t* idx_dev, int64_t n, void* dst_dev, void* stream);
 spp_status spp_agg_forward_fp8(const spp_agg_fwd_desc* desc, const int8_t* scale_log2_dev, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * f3g  Aggregation over rows of the RESIDENT graph (exact, layer-wise inference): the mean / operand / sum of
+ *      spp_agg_forward for targets that are ANY nodes of the graph, each with its whole neighbour row.
+ *
+ *        rowptr, col   the graph's CSR, int64: node t's neighbours are col[rowptr[t] .. rowptr[t+1]), global node ids
+ *        x             one row per graph node, [x_rows, F], rows x_stride_elems apart; fp32 / fp16 / bf16
+ *        targets       a slab  (target_row0 >= 0, target_ids_dev NULL):  output row i is node target_row0 + i
+ *                      or a list (target_ids_dev int64 [num_targets], target_row0 < 0): output row i is node
+ *                      target_ids[i]; any order, duplicates allowed
+ *        epilogue      SPP_AGG_MEAN, SPP_AGG_OPERAND ([mean | x[target]]) or SPP_AGG_SUM (self_scale * x[target] + sum),
+ *                      with the meaning and the rounding rule of spp_agg_forward; out_elem fp32 / bf16
+ *
+ *   Summation contract, C = spp_graph_agg_chunk() (a compile-time constant, >= 32):
+ *     a row of d <= C entries is summed in CSR order, one addend at a time, in fp32, and the mean is
+ *       sum * (1.0f / max(d, 1)): bit-identical to spp_agg_forward on the same row;
+ *     a longer row is cut into consecutive chunks of C entries (the last may be shorter); each chunk is summed in CSR
+ *       order in fp32 from zero, and the chunk sums are added in chunk order in fp32;
+ *     the result of a row depends on nothing else -- not the grid, the slab, or the other rows of the call -- and no
+ *       atomic touches the output.
+ *
+ *   Ids that leave the graph: a col entry outside [0, x_rows) reads row 0 (the rule of SPP_AGG_TABLE: no fault, no
+ *   error); a target id outside [0, x_rows) gives an output row of zeros.  A slab that leaves [0, x_rows] is refused.
+ *   Workspace: spp_graph_agg_workspace_bytes(num_targets) bytes, 16-byte aligned, the caller's; its contents mean nothing
+ *   between calls.  The entry enqueues a 16-byte memset and two launches on `stream` and never waits for the device.
+ *   With F % 4 == 0 and rows of x aligned to 4 elements the kernels move four columns per lane, and the output must be
+ *   aligned to 4 elements too (base and stride); other rows of x are read one column per lane, with the same result.
+ *   Refused with SPP_ERR_INVALID before anything is enqueued: both target forms or neither, a slab outside the graph,
+ *   SPP_AGG_OPERAND_ACT or an unknown epilogue, an unknown element code, fp8 rows, such a misaligned output, a missing,
+ *   misaligned or too small workspace.  (The row sources SPP_AGG_TABLE / SPP_AGG_ROWS do not exist here: x IS the table.)
+ * ------------------------------------------------------------------------- */
+typedef struct spp_graph_agg_desc {
+  int32_t epilogue;         /* SPP_AGG_MEAN / _OPERAND / _SUM */
+  int32_t x_elem;           /* SPP_ELEM_F32 / _F16 / _BF16 */
+  int32_t out_elem;         /* SPP_ELEM_F32 / SPP_ELEM_BF16 */
+  int32_t reserved;
+  const int64_t* rowptr_dev;
+  const int64_t* col_dev;
+  const void* x_dev;
+  int64_t x_stride_elems;
+  int64_t x_rows;           /* the graph's nodes = the rows of x */
+  int64_t F;
+  int64_t target_row0;      /* slab: the first target; < 0 with a list */
+  const int64_t* target_ids_dev; /* list: the targets; NULL with a slab */
+  int64_t num_targets;
+  void* out_dev;            /* [num_targets, F or 2F] */
+  int64_t out_stride_elems; /* 0 = dense */
+  float self_scale;         /* SUM: s = 1 + eps */
+  int32_t reserved2;
+} spp_graph_agg_desc;
+
+int64_t spp_graph_agg_chunk(void);
+int64_t spp_graph_agg_workspace_bytes(int64_t num_targets);
+spp_status spp_graph_agg_forward(const spp_graph_agg_desc* desc, void* workspace_dev, int64_t workspace_bytes,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,6 +80,14 @@ class AggBwdDesc(C.Structure):
                 ("reserved2", i32), ("seed", C.c_uint64)]
 
 
+class GraphAggDesc(C.Structure):
+    """spp_graph_agg_desc: targets as a slab (target_row0 >= 0) or a list (target_ids_dev, target_row0 < 0)"""
+    _fields_ = [("epilogue", i32), ("x_elem", i32), ("out_elem", i32), ("reserved", i32), ("rowptr_dev", p),
+                ("col_dev", p), ("x_dev", p), ("x_stride_elems", i64), ("x_rows", i64), ("F", i64),
+                ("target_row0", i64), ("target_ids_dev", p), ("num_targets", i64), ("out_dev", p),
+                ("out_stride_elems", i64), ("self_scale", C.c_float), ("reserved2", i32)]
+
+
 class GroupOut(C.Structure):
     _fields_ = [("mfg", MfgOut), ("x_out", p), ("y_out", p)]
 
@@ -205,6 +213,9 @@ SIGNATURES = {
     "spp_agg_backward": (C.c_int, [C.POINTER(AggBwdDesc), p, i64, p]),
     "spp_gather_rows_fp8": (C.c_int, [p, i64, i64, p, p, i64, p, p]),
     "spp_agg_forward_fp8": (C.c_int, [C.POINTER(AggFwdDesc), p, p]),
+    "spp_graph_agg_chunk": (i64, []),
+    "spp_graph_agg_workspace_bytes": (i64, [i64]),
+    "spp_graph_agg_forward": (C.c_int, [C.POINTER(GraphAggDesc), p, i64, p]),
 }
 SPP_COMM_ID_BYTES = 128
 SPP_IPC_HANDLE_BYTES = 64

@@ -31,7 +31,7 @@ from ..fp8 import Fp8Features
 
 __all__ = ["Config", "Session", "ProtoDistributedBatch", "RangePartitionBook", "Cache", "sample_adj",
            "multilayer_sample", "full_sample", "to_row_major", "serial_index", "NativeComm", "native_comm",
-           "set_native_comm", "async_errors", "set_sampler_options", "sampler_options", "sampler_info", "TableRows", "RowRefs", "Fp8Features", "fp8_gather_rows",
+           "set_native_comm", "async_errors", "set_sampler_options", "sampler_options", "sampler_info", "TableRows", "RowRefs", "Fp8Features", "fp8_gather_rows", "resident_graph",
            "P2PPeers", "set_p2p_peers", "p2p_open_peers"]
 
 # four slot-sets of 16 batches (~75 MB of workspace per slot at fanout [15,10,5], batch 1024: 4.8 GB).  With two sets, a
@@ -827,7 +827,29 @@ def _host_ranges(n, batch_size, skip_nonfull, force_exact, exact_k):
 # --------------------------------------------------------------------------------------------
 # Session   (fast_sampler.cpp:533-936 + worker :963-1274)
 # --------------------------------------------------------------------------------------------
+def resident_graph(config):
+    """(x, rowptr, col): the HBM-resident feature table (a strided view when its rows are padded) and CSR of a
+    single-GPU, non-distributed configuration -- the tensors a Session of ``config`` holds, uploaded on the first use and
+    shared afterwards, never twice.  Read-only: the samplers read them concurrently.  The order is that of
+    ``model.inference(x_all, rowptr, col)``."""
+    if bool(getattr(config, "distributed", False)):
+        raise RuntimeError("resident_graph: a distributed configuration holds one partition of the features, not the "
+                           "graph's table; whole-graph inference is single-GPU")
+    x = getattr(config, "x_cpu", None)
+    if isinstance(x, Fp8Features) or isinstance(getattr(config, "x_gpu", None), Fp8Features):
+        raise RuntimeError("resident_graph: the configuration's features are an fp8 table, which inference does not read")
+    if x is None or x.dim() != 2 or x.numel() == 0:
+        raise RuntimeError("resident_graph: the configuration carries no feature table (x_cpu)")
+    return _resident.get_rows(x), _resident.get(config.rowptr, torch.int64), _resident.get(config.col, torch.int64)
+
+
 class Session:
+    def resident_graph(self):
+        """(x, rowptr, col) device tensors of this session: see ``resident_graph``"""
+        if self._distributed or self._fp8 is not None or self._pfp8 is not None or self._x is None:
+            return resident_graph(self.config)           # (raises with the reason)
+        return self._x, self._rowptr, self._col
+
     def __init__(self, num_threads: int, max_items_in_queue: int, config: Config):
         fp8 = fp8_session_check(config)    # an fp8 table outside its scope is refused before any device call
         pfp8 = config.x_gpu if isinstance(getattr(config, "x_gpu", None), Fp8Features) else None

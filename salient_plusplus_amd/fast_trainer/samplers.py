@@ -344,6 +344,11 @@ class FastSampler(ABCNeighborSampler):
     def __len__(self):
         return self.cfg.get_num_batches()
 
+    def resident_graph(self):
+        """(x, rowptr, col): the resident device tensors this sampler's sessions read (``fast_sampler.resident_graph``),
+        for ``model.inference(*sampler.resident_graph())`` without a second upload.  Single-GPU, non-distributed only."""
+        return fast_sampler.resident_graph(self.cfg)
+
     # the epoch's seeds and the feature cache live in the configuration
     @property
     def idx(self):

@@ -1,0 +1,231 @@
+"""Exact, layer-wise inference over the whole resident graph (reference: driver/models.py:441 ``layerwise_inference``
+with ``SAGE.inference``): every node is scored from ALL its neighbours, one pass per layer over the graph's CSR, with
+no sampling, no dedup and no exchange.  The message passing is the HIP kernel pair of csrc/graph_aggregate.hip
+(``spp_graph_agg_forward``); the layers' own parameters run through the library GEMMs torch dispatches to.
+
+``graph_aggregate`` is the kernel's thin wrapper, ``layerwise_inference`` the driver behind ``SAGE.inference`` and
+``GIN.inference``.  Forward only, one GPU, fp16 / fp32 / bf16 inputs."""
+import ctypes as C
+
+import torch
+
+from . import _native as nat
+from .fast_sampler import RowRefs, TableRows
+from .fp8 import Fp8Features
+from .models import _ELEM, _p, _stream
+
+_EPILOGUES = {"mean": nat.SPP_AGG_MEAN, "operand": nat.SPP_AGG_OPERAND, "sum": nat.SPP_AGG_SUM}
+_OUT_DTYPES = (torch.float32, torch.bfloat16)
+
+
+def graph_agg_chunk():
+    """C of the summation contract (include/spp.h): rows of at most C entries are summed serially in CSR order, longer
+    rows as chunks of C whose sums are added in chunk order"""
+    return int(nat.load().spp_graph_agg_chunk())
+
+
+def graph_agg_workspace_bytes(num_targets):
+    return int(nat.load().spp_graph_agg_workspace_bytes(int(num_targets)))
+
+
+def _check_matrix(x, what):
+    """x as the kernels read it: a 2-D fp16 / fp32 / bf16 matrix with unit column stride that carries no gradient"""
+    if isinstance(x, Fp8Features):
+        raise TypeError(f"{what}: an fp8 feature table (Fp8Features) is not supported as inference input; pass "
+                        "x.dequantize(torch.float16)")
+    if isinstance(x, (TableRows, RowRefs)):
+        raise TypeError(f"{what}: {type(x).__name__} describes the rows of one sampled batch; inference reads the whole "
+                        "feature matrix, one row per graph node")
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{what}: x must be a torch.Tensor, got {type(x).__name__}")
+    if x.dim() != 2 or x.dtype not in _ELEM or (x.size(1) > 1 and x.stride(1) != 1):
+        raise ValueError(f"{what}: x must be a 2-D fp16 / fp32 / bf16 matrix with unit column stride, got "
+                         f"{tuple(x.shape)} {x.dtype} strides {tuple(x.stride())}")
+    if x.requires_grad:
+        raise RuntimeError(f"{what}: x requires grad, and inference is forward only (detach it)")
+
+
+def _check_graph(x, rowptr, col, what):
+    for name, t in (("rowptr", rowptr), ("col", col)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous 1-D int64 tensor")
+    if rowptr.numel() != x.size(0) + 1:
+        raise ValueError(f"{what}: x has {x.size(0)} rows, the graph {rowptr.numel() - 1} nodes (one row per node)")
+
+
+def graph_aggregate(x, rowptr, col, *, row0=None, num_targets=None, target_ids=None, epilogue="mean", self_scale=0.0,
+                    out_dtype=torch.float32, workspace=None):
+    """Aggregation over whole rows of the resident graph (``spp_graph_agg_forward``, include/spp.h).
+
+    ``x`` [N, F]: one row per graph node (fp16 / fp32 / bf16, possibly a strided view); ``rowptr`` / ``col``: the
+    graph's CSR (int64, global ids).  The targets are a slab, ``row0`` and ``num_targets`` (output row i is node
+    row0 + i), or a list, ``target_ids`` (int64, any order, duplicates allowed).  ``epilogue``: "mean" [T, F],
+    "operand" [T, 2F] = [mean | x[target]] or "sum" [T, F] = self_scale * x[target] + sum.  fp32 sums; a bf16 output
+    is rounded once.  A ``col`` entry outside the graph reads row 0, a target id outside it gives a row of zeros.
+
+    Forward only: no autograd node is registered and an input that requires grad is refused.  ``workspace``: a uint8
+    CUDA tensor of at least ``graph_agg_workspace_bytes(T)`` bytes, reusable between calls on one stream; allocated
+    when None.  Nothing here waits for the device."""
+    what = "graph_aggregate"
+    _check_matrix(x, what)
+    _check_graph(x, rowptr, col, what)
+    if epilogue not in _EPILOGUES:
+        raise ValueError(f"{what}: epilogue must be 'mean', 'operand' or 'sum', got {epilogue!r}")
+    if out_dtype not in _OUT_DTYPES:
+        raise ValueError(f"{what}: out_dtype must be torch.float32 or torch.bfloat16, got {out_dtype}")
+    slab = row0 is not None or num_targets is not None
+    if slab == (target_ids is not None):
+        raise ValueError(f"{what}: give the targets either as a slab (row0 and num_targets) or as target_ids"
+                         + (", not both" if slab else ""))
+    N, Fdim = x.shape
+    if slab:
+        if row0 is None or num_targets is None:
+            raise ValueError(f"{what}: a slab needs both row0 and num_targets")
+        row0, T = int(row0), int(num_targets)
+        if row0 < 0 or T < 0 or row0 + T > N:
+            raise ValueError(f"{what}: the slab [{row0}, {row0 + T}) leaves the graph's {N} nodes")
+    else:
+        if not isinstance(target_ids, torch.Tensor) or target_ids.dtype != torch.int64 or target_ids.dim() != 1 \
+                or not target_ids.is_contiguous():
+            raise ValueError(f"{what}: target_ids must be a contiguous 1-D int64 tensor")
+        row0, T = -1, target_ids.numel()
+    nat.require_device()
+    tensors = [x, rowptr, col] + ([target_ids] if not slab else []) + ([workspace] if workspace is not None else [])
+    if not all(t.is_cuda and t.device == x.device for t in tensors):
+        raise ValueError(f"{what}: x, rowptr, col, target_ids and workspace must live on one CUDA device")
+    L = nat.load()
+    nbytes = int(L.spp_graph_agg_workspace_bytes(T))
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < nbytes:
+        raise ValueError(f"{what}: workspace must be a contiguous uint8 tensor of at least {nbytes} bytes")
+    width = 2 * Fdim if epilogue == "operand" else Fdim
+    out = torch.empty((T, width), dtype=out_dtype, device=x.device)
+    d = nat.GraphAggDesc(epilogue=_EPILOGUES[epilogue], x_elem=_ELEM[x.dtype], out_elem=_ELEM[out_dtype],
+                         rowptr_dev=_p(rowptr), col_dev=_p(col), x_dev=_p(x),
+                         x_stride_elems=x.stride(0) if N > 1 else Fdim, x_rows=N, F=Fdim, target_row0=row0,
+                         target_ids_dev=_p(target_ids) if not slab else None, num_targets=T, out_dev=_p(out),
+                         out_stride_elems=0, self_scale=float(self_scale))
+    with torch.cuda.device(x.device):
+        nat.check(L.spp_graph_agg_forward(C.byref(d), C.c_void_p(workspace.data_ptr()), workspace.numel(), _stream()))
+    return out
+
+
+_GEMM_ROWS = 1 << 16
+
+
+def _row_tiles(A):
+    """(first row, rows, tile) over A in tiles of exactly _GEMM_ROWS rows, the last one zero-padded.  The library picks
+    a GEMM kernel -- and with it the order of the sum over K -- by the problem's shape, so the same operand row can
+    come out with different last bits from a [600, K] and a [75, K] product.  With one shape for every call a node's
+    result depends on its own row alone: not on the slab size, and not on whether ``nodes`` selected it."""
+    T = A.size(0)
+    for r in range(0, T, _GEMM_ROWS):
+        n = min(_GEMM_ROWS, T - r)
+        tile = A[r:r + n]
+        if n < _GEMM_ROWS:
+            tile = A.new_zeros((_GEMM_ROWS, A.size(1)))
+            tile[:n] = A[r:r + n]
+        yield r, n, tile
+
+
+def _sage_layer(conv, last, act_dtype):
+    """(epilogue, self_scale, fn): fn maps a slab's fp32 / bf16 operand [T, 2K] to the layer's output rows"""
+    W = torch.cat([conv.lin_l.weight, conv.lin_r.weight], dim=1).to(act_dtype)      # [N, 2K] = [W_l | W_r]
+    bias = conv.lin_l.bias
+
+    def fn(A):
+        Z = A @ W.t()
+        if bias is not None:
+            Z = Z + bias.to(Z.dtype)
+        return Z if last else torch.relu_(Z)             # the inter-layer ReLU; dropout is the identity in eval mode
+    return "operand", 0.0, fn
+
+
+def _gin_layer(conv, amp):
+    def fn(h):
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+            return conv.nn(h)                            # Linear, BatchNorm1d (running statistics), ReLU, Linear, ReLU
+    return "sum", conv._scale(), fn
+
+
+def layerwise_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 << 20, act_dtype=torch.float32):
+    """Exact log-probabilities of every node, [N, classes] fp32 -- or of ``nodes`` (int64, any order, duplicates
+    allowed), [len(nodes), classes] -- for a ``SAGE`` or ``GIN`` model over the whole graph.
+
+    Layer by layer, slab by slab of ``rows_per_slab`` nodes: ``graph_aggregate`` over each node's whole neighbour row,
+    then the layer's own parameters as torch GEMMs (SAGE: [mean | x] @ [W_l | W_r]^T; GIN: ``conv.nn`` with BatchNorm's
+    running statistics), written -- SAGE: through the ReLU -- into the next [N, hidden] activation matrix of dtype
+    ``act_dtype``.  The GEMMs run over row tiles of one fixed height, so a node's result is the same bits whatever the
+    slab size and whether ``nodes`` selected it.  With ``act_dtype=torch.bfloat16`` operands, weights and activations are bf16 as under
+    ``torch.autocast`` in training (fp32 sums, fp32 log_softmax).  With ``nodes`` the last conv layer, GIN's head and
+    the log_softmax are computed for those nodes only.  The model is put in eval mode and its mode restored; nothing
+    records a gradient.  ``x``: a CUDA fp16 / fp32 / bf16 matrix, one row per node, possibly a strided view of the
+    resident table (``FastSampler.resident_graph()``).
+
+    Memory, as arithmetic: an activation matrix is N * hidden * sizeof(act_dtype) bytes and two are live at a layer
+    boundary (layer i-1's is freed as soon as layer i is complete).  At N = 111 M and hidden 256 that is 113 GB each in
+    fp32 and 57 GB in bf16, next to 26 GB of graph and 28 GB of features: fp32 activations do not fit one 288 GB MI355X
+    at papers scale, ``act_dtype=torch.bfloat16`` does (26 + 28 + 2 * 57 = 168 GB)."""
+    from .models import GIN, SAGE
+    what = "layerwise_inference"
+    if not isinstance(model, (SAGE, GIN)):
+        raise NotImplementedError(f"{what}: implemented for SAGE and GIN, not {type(model).__name__}")
+    _check_matrix(x, what)
+    _check_graph(x, rowptr, col, what)
+    if act_dtype not in _OUT_DTYPES:
+        raise ValueError(f"{what}: act_dtype must be torch.float32 or torch.bfloat16, got {act_dtype}")
+    rows_per_slab = int(rows_per_slab)
+    if rows_per_slab < 1:
+        raise ValueError(f"{what}: rows_per_slab must be positive, got {rows_per_slab}")
+    if nodes is not None and (not isinstance(nodes, torch.Tensor) or nodes.dtype != torch.int64 or nodes.dim() != 1):
+        raise ValueError(f"{what}: nodes must be a 1-D int64 tensor")
+    nat.require_device()
+    if not (x.is_cuda and rowptr.device == x.device and col.device == x.device):
+        raise ValueError(f"{what}: x, rowptr and col must live on one CUDA device")
+    N = x.size(0)
+    if nodes is not None:
+        nodes = nodes.to(x.device).contiguous()
+        if nodes.numel() and not (0 <= int(nodes.min()) and int(nodes.max()) < N):      # (one read-back, up front)
+            raise ValueError(f"{what}: nodes outside the graph's {N} nodes")
+    amp = act_dtype == torch.bfloat16
+    gin = isinstance(model, GIN)
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad(), torch.autocast("cuda", enabled=False):
+            n_layers = len(model.convs)
+            ws = torch.empty(graph_agg_workspace_bytes(min(rows_per_slab, max(N, nodes.numel() if nodes is not None else 0))),
+                             dtype=torch.uint8, device=x.device)
+
+            def head(h):                                 # what follows the last conv layer, fp32 log-probabilities
+                if gin:
+                    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+                        h = model.lin2(torch.relu(model.lin1(h)))
+                return torch.log_softmax(h, dim=-1, dtype=torch.float32)
+
+            cur = x
+            for i, conv in enumerate(model.convs):
+                last = i == n_layers - 1
+                epilogue, scale, fn = _gin_layer(conv, amp) if gin else _sage_layer(conv, last, act_dtype)
+                ids = nodes if last else None
+                rows = ids.numel() if ids is not None else N
+                nxt = None
+                for s in range(0, rows, rows_per_slab):
+                    e = min(rows, s + rows_per_slab)
+                    tgt = dict(target_ids=ids[s:e]) if ids is not None else dict(row0=s, num_targets=e - s)
+                    A = graph_aggregate(cur, rowptr, col, epilogue=epilogue, self_scale=scale, out_dtype=act_dtype,
+                                        workspace=ws, **tgt)
+                    for r, n, tile in _row_tiles(A):
+                        h = head(fn(tile)) if last else fn(tile)
+                        if nxt is None:
+                            nxt = torch.empty((rows, h.size(1)), dtype=torch.float32 if last else act_dtype,
+                                              device=x.device)
+                        nxt[s + r:s + r + n] = h[:n]
+                if nxt is None:                          # no rows at all
+                    width = (model.lin2 if gin else conv.lin_l).out_features if last else model.hidden_channels
+                    nxt = torch.empty((0, width), dtype=torch.float32 if last else act_dtype, device=x.device)
+                cur = nxt                                # (drops layer i-1's matrix)
+            return cur
+    finally:
+        model.train(was_training)

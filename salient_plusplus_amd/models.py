@@ -340,6 +340,15 @@ class SAGE(torch.nn.Module):
                 x = relu_dropout(x, 0.5, self.training)       # F.relu + F.dropout(p=0.5) (models.py:47-48)
         return torch.log_softmax(x, dim=-1)
 
+    @torch.no_grad()
+    def inference(self, x_all, rowptr, col, **kw):
+        """Exact log-probabilities of every node (or of ``nodes=``) from the whole graph, layer by layer: see
+        ``inference.layerwise_inference`` (keywords ``nodes``, ``rows_per_slab``, ``act_dtype``).  The reference's
+        ``inference(x_all, device, make_subgraph_iter)`` walks sampled full-neighbour subgraphs; here nothing is sampled:
+        the graph and x_all are resident, so the arguments are the matrix and the graph's CSR."""
+        from .inference import layerwise_inference
+        return layerwise_inference(self, x_all, rowptr, col, **kw)
+
 
 def _wgrad(g, a):
     """g.T @ a for very tall g [T, N], a [T, K]: batched over row slabs and summed (see _TallLinear).  64 slabs of
@@ -859,6 +868,11 @@ class GAT(torch.nn.Module):
                 x = relu_dropout(x, 0.5, self.training)
         return torch.log_softmax(x, dim=-1)
 
+    def inference(self, x_all, rowptr, col, **kw):
+        raise NotImplementedError("GAT.inference: layer-wise inference over whole neighbour rows needs a long-row "
+                                  "softmax (attention over 10^5 entries of a hub), which the GAT kernels do not have; "
+                                  "SAGE and GIN implement inference()")
+
 
 # --------------------------------------------------------------------------------------------
 # GIN  (driver/models.py:234-283: GINConv(Sequential(Linear, BatchNorm1d, ReLU, Linear, ReLU)), eps = 0)
@@ -1000,6 +1014,13 @@ class GIN(torch.nn.Module):
         x = F.dropout(x, p=self.dropout, training=self.training)
         return torch.log_softmax(self.lin2(x), dim=-1)
 
+    @torch.no_grad()
+    def inference(self, x_all, rowptr, col, **kw):
+        """Exact log-probabilities of every node (or of ``nodes=``) from the whole graph, layer by layer, BatchNorm on
+        its running statistics: see ``inference.layerwise_inference``"""
+        from .inference import layerwise_inference
+        return layerwise_inference(self, x_all, rowptr, col, **kw)
+
 
 # --------------------------------------------------------------------------------------------
 # SAGEResInception  (driver/models.py:95-192)
@@ -1085,6 +1106,11 @@ class SAGEResInception(torch.nn.Module):
             x = h + self.res_linears[i](x_target)
             collect.append(x[:end_size])
         return torch.log_softmax(self.mlp(torch.cat(collect, -1)), dim=-1)
+
+    def inference(self, x_all, rowptr, col, **kw):
+        raise NotImplementedError("SAGEResInception.inference: the head concatenates every layer's activations, so a "
+                                  "layer-wise pass would have to keep all layers' matrices of all nodes at once; "
+                                  "SAGE and GIN implement inference()")
 
 
 _UNSUPPORTED_MODELS = {"sageclassic": "not used in the paper", "jknet": "not used in the paper",

@@ -1,0 +1,102 @@
+"""Exact layer-wise inference at papers scale: one ``layerwise_inference`` of SAGE 3 x 256 over make_workload("S-papers")
+with bf16 activations, timed per layer, and layer 1's slabs once more through the hop kernel (spp_agg_forward: MEAN,
+``rowptr + t0``, the full matrix as the Dense source) for comparison.
+
+    python tools/inference_profile.py [--workload S-papers] [--rows-per-slab 1048576] [--hidden 256] [--json out.json]
+
+Per layer: seconds of the aggregation alone (events around every slab's graph_aggregate, summed), edges/s, and the
+algorithmic bytes/s  E * F * s (rows) + 16 * T + 8 * E (indices) + T * W * s_out (output); plus the seconds of the whole
+layer (aggregation, GEMM, activation write).  Also the maximum degree and the share of rows and entries above C."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", default="S-papers")
+    ap.add_argument("--rows-per-slab", type=int, default=1 << 20)
+    ap.add_argument("--hidden", type=int, default=256)
+    ap.add_argument("--classes", type=int, default=172)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    from salient_plusplus_amd import _native as nat
+    from salient_plusplus_amd import inference as inf
+    from salient_plusplus_amd.models import SAGE, _agg_forward
+    from salient_plusplus_amd.synthetic import make_workload
+    dev = torch.device("cuda", 0)
+    t0 = time.time()
+    wl = make_workload(a.workload, device=dev)
+    torch.cuda.synchronize()
+    x, rowptr, col = wl.x, wl.rowptr, wl.col
+    N, E, Cc = wl.num_nodes, col.numel(), inf.graph_agg_chunk()
+    deg = rowptr[1:] - rowptr[:-1]
+    long_rows = deg > Cc
+    res = {"workload": a.workload, "nodes": N, "entries": E, "chunk": Cc, "max_degree": int(deg.max()),
+           "rows_above_chunk": int(long_rows.sum()), "entries_above_chunk": int(deg[long_rows].sum()),
+           "rows_per_slab": a.rows_per_slab, "build_s": round(time.time() - t0, 1), "layers": []}
+    del deg, long_rows
+    print(json.dumps({k: v for k, v in res.items() if k != "layers"}), flush=True)
+
+    # the aggregation of every slab, timed by events inside the one layerwise_inference call
+    spans = []
+    inner = inf.graph_aggregate
+
+    def timed(xm, *args, **kw):
+        b, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        b.record()
+        out = inner(xm, *args, **kw)
+        e.record()
+        spans.append((xm.size(1), xm.element_size(), out.size(0), out.size(1) * out.element_size(), b, e))
+        return out
+    inf.graph_aggregate = timed
+    torch.manual_seed(0)
+    model = SAGE(x.size(1), a.hidden, a.classes, 3).to(dev)
+    torch.cuda.synchronize()
+    t0 = time.time()
+    out = inf.layerwise_inference(model, x, rowptr, col, rows_per_slab=a.rows_per_slab, act_dtype=torch.bfloat16)
+    torch.cuda.synchronize()
+    res["total_s"] = round(time.time() - t0, 3)
+    inf.graph_aggregate = inner
+    assert out.shape == (N, a.classes) and bool(torch.isfinite(out[:: max(1, N // 4096)]).all())
+    del out
+    slabs = -(-N // a.rows_per_slab)
+    for layer in range(3):
+        part = spans[layer * slabs:(layer + 1) * slabs]
+        F_, s_in = part[0][0], part[0][1]
+        agg_s = sum(b.elapsed_time(e) for *_x, b, e in part) / 1e3
+        nbytes = E * F_ * s_in + 16 * N + 8 * E + sum(T * w for _f, _s, T, w, _b, _e in part)
+        res["layers"].append({"layer": layer + 1, "F": F_, "x_bytes_per_elem": s_in, "agg_s": round(agg_s, 4),
+                              "edges_per_s": round(E / agg_s), "algorithmic_TBps": round(nbytes / agg_s / 1e12, 3)})
+        print(json.dumps(res["layers"][-1]), flush=True)
+
+    # layer 1's slabs through the hop kernel: lpr lanes walk each row serially, whatever its length
+    b, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    hop_s, worst = 0.0, (0.0, 0)
+    for s in range(0, N, a.rows_per_slab):
+        T = min(a.rows_per_slab, N - s)
+        b.record()
+        o = _agg_forward(nat.SPP_AGG_MEAN, rowptr[s:], col, T, x, torch.bfloat16)
+        e.record()
+        e.synchronize()
+        ms = b.elapsed_time(e)
+        hop_s += ms / 1e3
+        worst = max(worst, (ms / 1e3, s))
+        del o
+    res["layer1_hop_kernel_s"] = round(hop_s, 4)
+    res["layer1_hop_kernel_worst_slab"] = {"row0": worst[1], "s": round(worst[0], 4)}
+    print(json.dumps({k: res[k] for k in ("total_s", "layer1_hop_kernel_s", "layer1_hop_kernel_worst_slab")}), flush=True)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
