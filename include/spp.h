@@ -973,6 +973,76 @@ int64_t spp_graph_agg_workspace_bytes(int64_t num_targets);
 spp_status spp_graph_agg_forward(const spp_graph_agg_desc* desc, void* workspace_dev, int64_t workspace_bytes,
                                  void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * f3h  GATConv attention over rows of the RESIDENT graph (exact, layer-wise GAT inference), in PyG's project-first
+ *      order: the rows are already projected, h = x W^T, and the logits already taken from them.
+ *
+ *        rowptr, col   the graph's CSR, int64, global node ids (as spp_graph_agg_forward)
+ *        h             one projected row per graph node, [x_rows, F], rows x_stride_elems apart; fp32 / fp16 / bf16;
+ *                      F = heads * C, head k owns columns k*C .. (k+1)*C
+ *        a_src, a_dst  fp32 [x_rows, heads], dense: a_src[n,k] = h[n,k,:] . att_src[k], a_dst likewise
+ *        targets       a slab or a list, exactly as spp_graph_agg_desc
+ *
+ *      For target t and head k (GATConv with add_self_loops, as spp_gat_aggregate_forward states it): the entries are
+ *      col[rowptr[t] .. rowptr[t+1]) with every entry j == t skipped, plus one self loop j = t;
+ *        e_j = leaky_relu(a_src[j,k] + a_dst[t,k], negative_slope),  alpha = softmax_j(e),
+ *        out[i, k*C + c] = sum_j alpha_j h[j, k*C + c],  then max(., 0) if relu != 0;  out_elem fp32 / bf16, a bf16
+ *      output is rounded once, to nearest even.  A node without neighbours gets its own row.  Logits and softmax state
+ *      are fp32.  Any heads >= 1 that divides F.
+ *
+ *   Softmax contract, C_g = spp_graph_gat_chunk() (a compile-time constant, >= 32).  A state is (m, s, acc): the
+ *   maximum logit so far, the denominator and the weighted sum of rows, both at that maximum.  Taking an entry with
+ *   logit e and row v:  if e > m: r = __expf(m - e), acc *= r, s *= r, m = e;  then w = __expf(e - m), s += w,
+ *   acc = fma(w, v, acc).  The result of a state is acc / s.
+ *     a row of at most C_g raw entries (skipped ones count): ONE state, begun as the self loop's (m = e_t, s = 1,
+ *       acc = h[t]), takes the row's entries in CSR order;
+ *     a longer row is cut into consecutive chunks of C_g raw positions (the last may be shorter).  Chunk 0 begins as
+ *       the self loop's state, every other chunk as the empty state (m = -inf, s = 0, acc = 0); each takes its entries
+ *       in CSR order.  The running state is chunk 0's, and chunks 1, 2, ... are merged into it in chunk order:
+ *         m' = max(m1, m2), f1 = __expf(m1 - m'), f2 = __expf(m2 - m'), s' = fma(s2, f2, s1 * f1),
+ *         acc' = fma(f2, acc2, acc1 * f1);
+ *     a chunk whose entries are all skipped stays the empty state; merging it changes nothing (f2 = 0, f1 = 1) and
+ *       produces no NaN: the running state is always finite, because it begins with the self loop;
+ *     the result of a row depends on nothing else -- not the grid, the slab, the order of a list or the other rows of
+ *       the call -- and no atomic touches the output.
+ *
+ *   Ids that leave the graph: a col entry outside [0, x_rows) is node 0 in every respect (its row of h, its logit, and
+ *   the comparison with t); a target id outside [0, x_rows) gives an output row of zeros.  Neither faults.
+ *   Workspace: spp_graph_gat_workspace_bytes(num_targets) bytes, 16-byte aligned, the caller's; its contents mean
+ *   nothing between calls.  The entry enqueues a 16-byte memset and two launches on `stream` and never waits for the
+ *   device.  With C % 4 == 0 and rows of h aligned to 4 elements the kernels move four columns per lane, and the output
+ *   must be aligned to 4 elements too (base and stride); other rows are read one column per lane, with the same rule.
+ *   Refused with SPP_ERR_INVALID before anything is enqueued: a NULL descriptor, both target forms or neither, a slab
+ *   outside the graph, heads < 1 or F % heads != 0, an unknown or fp8 element code, such a misaligned output, a
+ *   missing, misaligned or too small workspace, a stride smaller than the row.  num_targets == 0 or F == 0: SPP_OK.
+ * ------------------------------------------------------------------------- */
+typedef struct spp_graph_gat_desc {
+  int32_t x_elem;           /* h: SPP_ELEM_F32 / _F16 / _BF16 */
+  int32_t out_elem;         /* SPP_ELEM_F32 / SPP_ELEM_BF16 */
+  int32_t heads;
+  int32_t relu;             /* != 0: out = max(out, 0) */
+  const int64_t* rowptr_dev;
+  const int64_t* col_dev;
+  const void* x_dev;        /* h */
+  int64_t x_stride_elems;
+  int64_t x_rows;           /* the graph's nodes = the rows of h, a_src and a_dst */
+  int64_t F;                /* heads * C */
+  const float* a_src_dev;   /* [x_rows, heads] */
+  const float* a_dst_dev;   /* [x_rows, heads] */
+  int64_t target_row0;      /* slab: the first target; < 0 with a list */
+  const int64_t* target_ids_dev; /* list: the targets; NULL with a slab */
+  int64_t num_targets;
+  void* out_dev;            /* [num_targets, F] */
+  int64_t out_stride_elems; /* 0 = dense */
+  float negative_slope;
+  int32_t reserved;
+} spp_graph_gat_desc;
+
+int64_t spp_graph_gat_chunk(void);
+int64_t spp_graph_gat_workspace_bytes(int64_t num_targets);
+spp_status spp_graph_gat_forward(const spp_graph_gat_desc* desc, void* workspace_dev, int64_t workspace_bytes,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -88,6 +88,14 @@ class GraphAggDesc(C.Structure):
                 ("out_stride_elems", i64), ("self_scale", C.c_float), ("reserved2", i32)]
 
 
+class GraphGatDesc(C.Structure):
+    """spp_graph_gat_desc: projected rows h with their logits; targets as in GraphAggDesc"""
+    _fields_ = [("x_elem", i32), ("out_elem", i32), ("heads", i32), ("relu", i32), ("rowptr_dev", p), ("col_dev", p),
+                ("x_dev", p), ("x_stride_elems", i64), ("x_rows", i64), ("F", i64), ("a_src_dev", p), ("a_dst_dev", p),
+                ("target_row0", i64), ("target_ids_dev", p), ("num_targets", i64), ("out_dev", p),
+                ("out_stride_elems", i64), ("negative_slope", C.c_float), ("reserved", i32)]
+
+
 class GroupOut(C.Structure):
     _fields_ = [("mfg", MfgOut), ("x_out", p), ("y_out", p)]
 
@@ -216,6 +224,9 @@ SIGNATURES = {
     "spp_graph_agg_chunk": (i64, []),
     "spp_graph_agg_workspace_bytes": (i64, [i64]),
     "spp_graph_agg_forward": (C.c_int, [C.POINTER(GraphAggDesc), p, i64, p]),
+    "spp_graph_gat_chunk": (i64, []),
+    "spp_graph_gat_workspace_bytes": (i64, [i64]),
+    "spp_graph_gat_forward": (C.c_int, [C.POINTER(GraphGatDesc), p, i64, p]),
 }
 SPP_COMM_ID_BYTES = 128
 SPP_IPC_HANDLE_BYTES = 64

@@ -1,10 +1,12 @@
 """Exact, layer-wise inference over the whole resident graph (reference: driver/models.py:441 ``layerwise_inference``
 with ``SAGE.inference``): every node is scored from ALL its neighbours, one pass per layer over the graph's CSR, with
 no sampling, no dedup and no exchange.  The message passing is the HIP kernel pair of csrc/graph_aggregate.hip
-(``spp_graph_agg_forward``); the layers' own parameters run through the library GEMMs torch dispatches to.
+(``spp_graph_agg_forward``) for SAGE and GIN and of csrc/graph_gat.hip (``spp_graph_gat_forward``) for GAT; the layers'
+own parameters run through the library GEMMs torch dispatches to.
 
-``graph_aggregate`` is the kernel's thin wrapper, ``layerwise_inference`` the driver behind ``SAGE.inference`` and
-``GIN.inference``.  Forward only, one GPU, fp16 / fp32 / bf16 inputs."""
+``graph_aggregate`` and ``graph_gat_aggregate`` are the kernels' thin wrappers, ``layerwise_inference`` the driver
+behind ``SAGE.inference`` and ``GIN.inference`` and the entry point for ``GAT``.  Forward only, one GPU, fp16 / fp32 /
+bf16 inputs."""
 import ctypes as C
 
 import torch
@@ -111,6 +113,90 @@ def graph_aggregate(x, rowptr, col, *, row0=None, num_targets=None, target_ids=N
     return out
 
 
+def graph_gat_chunk():
+    """C_g of the softmax contract (include/spp.h): a row of at most C_g raw entries is one online softmax in CSR order,
+    a longer row is chunks of C_g whose softmax states are merged in chunk order"""
+    return int(nat.load().spp_graph_gat_chunk())
+
+
+def graph_gat_workspace_bytes(num_targets):
+    return int(nat.load().spp_graph_gat_workspace_bytes(int(num_targets)))
+
+
+def _gat_forward(h, a_src, a_dst, rowptr, col, heads, negative_slope, relu, row0, target_ids, T, out, workspace):
+    """spp_graph_gat_forward on checked arguments, into ``out`` [T, F] (rows of another matrix allowed)"""
+    N, Fdim = h.shape
+    d = nat.GraphGatDesc(x_elem=_ELEM[h.dtype], out_elem=_ELEM[out.dtype], heads=heads, relu=int(bool(relu)),
+                         rowptr_dev=_p(rowptr), col_dev=_p(col), x_dev=_p(h),
+                         x_stride_elems=h.stride(0) if N > 1 else Fdim, x_rows=N, F=Fdim, a_src_dev=_p(a_src),
+                         a_dst_dev=_p(a_dst), target_row0=row0, target_ids_dev=_p(target_ids) if target_ids is not None else None,
+                         num_targets=T, out_dev=_p(out), out_stride_elems=out.stride(0) if T > 1 else 0,
+                         negative_slope=float(negative_slope))
+    with torch.cuda.device(h.device):
+        nat.check(nat.load().spp_graph_gat_forward(C.byref(d), C.c_void_p(workspace.data_ptr()), workspace.numel(),
+                                                   _stream()))
+    return out
+
+
+def graph_gat_aggregate(h, a_src, a_dst, rowptr, col, *, heads, negative_slope=0.2, relu=False, row0=None,
+                        num_targets=None, target_ids=None, out_dtype=torch.float32, workspace=None):
+    """GATConv's attention over whole rows of the resident graph (``spp_graph_gat_forward``, include/spp.h).
+
+    ``h`` [N, F]: one PROJECTED row per graph node (fp16 / fp32 / bf16, possibly a strided view), F = heads * C with
+    head k in columns k*C .. (k+1)*C; ``a_src`` / ``a_dst``: contiguous fp32 [N, heads], the logits' two halves;
+    ``rowptr`` / ``col``: the graph's CSR (int64, global ids).  The targets are a slab, ``row0`` and ``num_targets``,
+    or a list, ``target_ids`` (int64, any order, duplicates allowed).  Output row i, head k: the softmax over node t's
+    row without its diagonal entries plus one self loop, of leaky_relu(a_src[j, k] + a_dst[t, k]), applied to the rows
+    h[j, k*C:(k+1)*C]; through a ReLU with ``relu=True``.  fp32 state; a bf16 output is rounded once.  A ``col`` entry
+    outside the graph is node 0, a target id outside it gives a row of zeros.
+
+    Forward only: no autograd node is registered and an input that requires grad is refused.  ``workspace``: a uint8
+    CUDA tensor of at least ``graph_gat_workspace_bytes(T)`` bytes, reusable between calls on one stream; allocated
+    when None.  Nothing here waits for the device."""
+    what = "graph_gat_aggregate"
+    _check_matrix(h, what)
+    _check_graph(h, rowptr, col, what)
+    N, Fdim = h.shape
+    if not isinstance(heads, int) or heads < 1 or Fdim % heads != 0:
+        raise ValueError(f"{what}: heads must be a positive int that divides F = {Fdim}, got {heads!r}")
+    for name, t in (("a_src", a_src), ("a_dst", a_dst)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (N, heads) \
+                or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous fp32 tensor of shape [{N}, {heads}] (nodes, heads)")
+        if t.requires_grad:
+            raise RuntimeError(f"{what}: {name} requires grad, and inference is forward only (detach it)")
+    if out_dtype not in _OUT_DTYPES:
+        raise ValueError(f"{what}: out_dtype must be torch.float32 or torch.bfloat16, got {out_dtype}")
+    slab = row0 is not None or num_targets is not None
+    if slab == (target_ids is not None):
+        raise ValueError(f"{what}: give the targets either as a slab (row0 and num_targets) or as target_ids"
+                         + (", not both" if slab else ""))
+    if slab:
+        if row0 is None or num_targets is None:
+            raise ValueError(f"{what}: a slab needs both row0 and num_targets")
+        row0, T = int(row0), int(num_targets)
+        if row0 < 0 or T < 0 or row0 + T > N:
+            raise ValueError(f"{what}: the slab [{row0}, {row0 + T}) leaves the graph's {N} nodes")
+    else:
+        if not isinstance(target_ids, torch.Tensor) or target_ids.dtype != torch.int64 or target_ids.dim() != 1 \
+                or not target_ids.is_contiguous():
+            raise ValueError(f"{what}: target_ids must be a contiguous 1-D int64 tensor")
+        row0, T = -1, target_ids.numel()
+    nat.require_device()
+    tensors = [h, a_src, a_dst, rowptr, col] + ([target_ids] if not slab else []) \
+        + ([workspace] if workspace is not None else [])
+    if not all(t.is_cuda and t.device == h.device for t in tensors):
+        raise ValueError(f"{what}: h, a_src, a_dst, rowptr, col, target_ids and workspace must live on one CUDA device")
+    nbytes = graph_gat_workspace_bytes(T)
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=h.device)
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < nbytes:
+        raise ValueError(f"{what}: workspace must be a contiguous uint8 tensor of at least {nbytes} bytes")
+    out = torch.empty((T, Fdim), dtype=out_dtype, device=h.device)
+    return _gat_forward(h, a_src, a_dst, rowptr, col, heads, negative_slope, relu, row0, None if slab else target_ids,
+                        T, out, workspace)
+
+
 _GEMM_ROWS = 1 << 16
 
 
@@ -149,9 +235,65 @@ def _gin_layer(conv, amp):
     return "sum", conv._scale(), fn
 
 
+def _gat_inference(model, x, rowptr, col, nodes, rows_per_slab, act_dtype):
+    """layerwise_inference for GAT, in PyG's project-first order (training aggregates first, _GatLayer / _GatLayerMH,
+    because an MFG hop has many sources per target; over the whole graph T = S = N, that saving is gone, and the
+    aggregate-first intermediate would be [T, H, K] fp32 per slab).  Per layer:
+
+      project    h = cur @ W^T for all N rows, [N, H*C] in ``act_dtype``, over ``_row_tiles``
+      logits     [a_src | a_dst] = tile.float() @ V^T with V = W_h^T att (as _GatLayerMH builds it), fp32 [N, H] each:
+                 taken from the layer's input rows, never from the rounded h
+      aggregate  ``spp_graph_gat_forward`` slab by slab over each node's whole row; hidden layers through the fused ReLU
+                 straight into the next [N, hidden] matrix, the last layer ([T, H*classes] fp32 per slab) through the
+                 mean over its heads and log_softmax(dtype=float32)
+
+    Memory, as arithmetic: ``cur`` is dropped once ``h`` is complete and ``h`` once ``nxt`` is, so two [N, hidden]
+    matrices of ``act_dtype`` are live at a time, as for SAGE (57 GB each in bf16 at N = 111 M, hidden 256; layer 1's
+    ``cur`` is the resident table and stays), plus the logits, 2 * N * H * 4 bytes (3.6 GB at H = 4).  The one case
+    worse than SAGE: the last layer's h is [N, H * classes], so H > 1 heads multiply it -- 111 M * 4 * 172 * 2 bytes =
+    153 GB in bf16 for H = 4 and 172 classes, which does not fit next to a 57 GB ``cur``, 26 GB of graph and 28 GB of
+    features on one 288 GB MI355X.  The reference's model has H = 1 (38 GB)."""
+    N, dev = x.size(0), x.device
+    n_layers = len(model.convs)
+    ws = torch.empty(graph_gat_workspace_bytes(min(rows_per_slab, max(N, nodes.numel() if nodes is not None else 0))),
+                     dtype=torch.uint8, device=dev)
+    cur = x
+    for i, conv in enumerate(model.convs):
+        last = i == n_layers - 1
+        H, Cc = conv.heads, conv.out_channels
+        W = conv.lin_src.weight                                                   # [H*C, K]
+        att = torch.stack([conv.att_src.view(H, Cc), conv.att_dst.view(H, Cc)]).to(torch.float32)
+        V = torch.einsum("shc,hck->shk", att, W.to(torch.float32).view(H, Cc, -1)).reshape(2 * H, -1)   # [V_src; V_dst]
+        Wt, Vt = W.to(act_dtype).t(), V.t().contiguous()
+        h = torch.empty((N, H * Cc), dtype=act_dtype, device=dev)
+        a_src, a_dst = (torch.empty((N, H), dtype=torch.float32, device=dev) for _ in range(2))
+        for r, n, tile in _row_tiles(cur):
+            h[r:r + n] = (tile.to(act_dtype) @ Wt)[:n]
+            a = tile.to(torch.float32) @ Vt
+            a_src[r:r + n], a_dst[r:r + n] = a[:n, :H], a[:n, H:]
+        del cur                                          # (layer i-1's matrix; layer 1's is the caller's table)
+        ids = nodes if last else None
+        rows = ids.numel() if ids is not None else N
+        width = Cc if last else H * Cc
+        nxt = torch.empty((rows, width), dtype=torch.float32 if last else act_dtype, device=dev)
+        for s in range(0, rows, rows_per_slab):
+            e = min(rows, s + rows_per_slab)
+            row0, tids = (-1, ids[s:e]) if ids is not None else (s, None)
+            out = nxt[s:e] if not last else torch.empty((e - s, H * Cc), dtype=torch.float32, device=dev)
+            _gat_forward(h, a_src, a_dst, rowptr, col, H, conv.negative_slope, not last, row0, tids, e - s, out, ws)
+            if last:                                     # concat=False: the mean of the heads (H = 1: the head itself)
+                nxt[s:e] = torch.log_softmax(out.view(e - s, H, Cc).mean(1) if H > 1 else out, dim=-1,
+                                             dtype=torch.float32)
+        cur = nxt                                        # (drops h)
+        del h, a_src, a_dst
+    return cur
+
+
 def layerwise_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 << 20, act_dtype=torch.float32):
     """Exact log-probabilities of every node, [N, classes] fp32 -- or of ``nodes`` (int64, any order, duplicates
-    allowed), [len(nodes), classes] -- for a ``SAGE`` or ``GIN`` model over the whole graph.
+    allowed), [len(nodes), classes] -- for a ``SAGE``, ``GIN`` or ``GAT`` model over the whole graph.  (GAT, at any
+    ``heads``: see ``_gat_inference`` for its order of operations and memory; what follows describes SAGE and GIN, and
+    the arguments, the fixed GEMM tiles, eval mode and ``nodes`` mean the same for all three.)
 
     Layer by layer, slab by slab of ``rows_per_slab`` nodes: ``graph_aggregate`` over each node's whole neighbour row,
     then the layer's own parameters as torch GEMMs (SAGE: [mean | x] @ [W_l | W_r]^T; GIN: ``conv.nn`` with BatchNorm's
@@ -167,10 +309,16 @@ def layerwise_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 <<
     boundary (layer i-1's is freed as soon as layer i is complete).  At N = 111 M and hidden 256 that is 113 GB each in
     fp32 and 57 GB in bf16, next to 26 GB of graph and 28 GB of features: fp32 activations do not fit one 288 GB MI355X
     at papers scale, ``act_dtype=torch.bfloat16`` does (26 + 28 + 2 * 57 = 168 GB)."""
-    from .models import GIN, SAGE
+    from .models import GAT, GIN, SAGE
     what = "layerwise_inference"
-    if not isinstance(model, (SAGE, GIN)):
-        raise NotImplementedError(f"{what}: implemented for SAGE and GIN, not {type(model).__name__}")
+    if not isinstance(model, (SAGE, GIN, GAT)):
+        raise NotImplementedError(f"{what}: implemented for SAGE and GIN (and GAT), not {type(model).__name__}")
+    if isinstance(model, GAT):                                # the layers as models.GAT builds them
+        for i, c in enumerate(model.convs):
+            mean_heads = i == len(model.convs) - 1 and c.heads > 1
+            if c.bias is not None or c.concat == mean_heads:
+                raise NotImplementedError(f"{what}: GAT layers need bias=False, and concat=False on the last layer of a "
+                                          "multi-head model only")
     _check_matrix(x, what)
     _check_graph(x, rowptr, col, what)
     if act_dtype not in _OUT_DTYPES:
@@ -194,6 +342,8 @@ def layerwise_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 <<
     model.eval()
     try:
         with torch.no_grad(), torch.autocast("cuda", enabled=False):
+            if isinstance(model, GAT):
+                return _gat_inference(model, x, rowptr, col, nodes, rows_per_slab, act_dtype)
             n_layers = len(model.convs)
             ws = torch.empty(graph_agg_workspace_bytes(min(rows_per_slab, max(N, nodes.numel() if nodes is not None else 0))),
                              dtype=torch.uint8, device=x.device)

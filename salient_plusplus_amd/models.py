@@ -869,9 +869,10 @@ class GAT(torch.nn.Module):
         return torch.log_softmax(x, dim=-1)
 
     def inference(self, x_all, rowptr, col, **kw):
-        raise NotImplementedError("GAT.inference: layer-wise inference over whole neighbour rows needs a long-row "
-                                  "softmax (attention over 10^5 entries of a hub), which the GAT kernels do not have; "
-                                  "SAGE and GIN implement inference()")
+        raise NotImplementedError("GAT.inference: not a method of the model yet; the long-row softmax that layer-wise "
+                                  "inference over whole neighbour rows needs (attention over 10^5 entries of a hub) is "
+                                  "spp_graph_gat_forward: call inference.layerwise_inference(model, x_all, rowptr, col, "
+                                  "...), which accepts GAT at any heads")
 
 
 # --------------------------------------------------------------------------------------------

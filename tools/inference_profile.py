@@ -3,6 +3,11 @@ with bf16 activations, timed per layer, and layer 1's slabs once more through th
 ``rowptr + t0``, the full matrix as the Dense source) for comparison.
 
     python tools/inference_profile.py [--workload S-papers] [--rows-per-slab 1048576] [--hidden 256] [--json out.json]
+    python tools/inference_profile.py --model gat [--heads 4] [--repeats 3] ...
+
+``--model gat``: GAT 3 x hidden at ``--heads`` through spp_graph_gat_forward, ``--repeats`` whole passes in one process
+(the first warms up code objects and the GEMM library's choices; every pass is reported).  Its bytes are the mean's plus
+the logits: 4 * H per entry (a_src) and 8 * H per target (a_src of the self loop, a_dst).
 
 Per layer: seconds of the aggregation alone (events around every slab's graph_aggregate, summed), edges/s, and the
 algorithmic bytes/s  E * F * s (rows) + 16 * T + 8 * E (indices) + T * W * s_out (output); plus the seconds of the whole
@@ -25,6 +30,9 @@ def main():
     ap.add_argument("--hidden", type=int, default=256)
     ap.add_argument("--classes", type=int, default=172)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--model", choices=("sage", "gat"), default="sage")
+    ap.add_argument("--heads", type=int, default=1)
+    ap.add_argument("--repeats", type=int, default=3)
     a = ap.parse_args()
     from salient_plusplus_amd import _native as nat
     from salient_plusplus_amd import inference as inf
@@ -43,6 +51,8 @@ def main():
            "rows_per_slab": a.rows_per_slab, "build_s": round(time.time() - t0, 1), "layers": []}
     del deg, long_rows
     print(json.dumps({k: v for k, v in res.items() if k != "layers"}), flush=True)
+    if a.model == "gat":
+        return gat_leg(a, wl, res)
 
     # the aggregation of every slab, timed by events inside the one layerwise_inference call
     spans = []
@@ -92,6 +102,52 @@ def main():
     res["layer1_hop_kernel_s"] = round(hop_s, 4)
     res["layer1_hop_kernel_worst_slab"] = {"row0": worst[1], "s": round(worst[0], 4)}
     print(json.dumps({k: res[k] for k in ("total_s", "layer1_hop_kernel_s", "layer1_hop_kernel_worst_slab")}), flush=True)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+def gat_leg(a, wl, res):
+    from salient_plusplus_amd import inference as inf
+    from salient_plusplus_amd.models import GAT
+    x, rowptr, col = wl.x, wl.rowptr, wl.col
+    N, E, H = wl.num_nodes, col.numel(), a.heads
+    res.update(model="gat", heads=H, chunk=inf.graph_gat_chunk(), passes=[])
+    spans = []
+    inner = inf._gat_forward
+
+    def timed(h, *args):
+        b, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        b.record()
+        out = inner(h, *args)
+        e.record()
+        spans.append((h.size(1), h.element_size(), out.size(0), out.size(1) * out.element_size(), b, e))
+        return out
+    inf._gat_forward = timed
+    torch.manual_seed(0)
+    model = GAT(x.size(1), a.hidden, a.classes, 3, heads=H).to(x.device)
+    slabs = -(-N // a.rows_per_slab)
+    for rep in range(a.repeats):
+        del spans[:]
+        torch.cuda.synchronize()
+        t0 = time.time()
+        out = inf.layerwise_inference(model, x, rowptr, col, rows_per_slab=a.rows_per_slab, act_dtype=torch.bfloat16)
+        torch.cuda.synchronize()
+        one = {"pass": rep, "total_s": round(time.time() - t0, 3), "layers": []}
+        assert out.shape == (N, a.classes) and bool(torch.isfinite(out[:: max(1, N // 4096)]).all())
+        del out
+        for layer in range(3):
+            part = spans[layer * slabs:(layer + 1) * slabs]
+            F_, s_in = part[0][0], part[0][1]
+            agg_s = sum(b.elapsed_time(e) for *_x, b, e in part) / 1e3
+            nbytes = E * F_ * s_in + 16 * N + 8 * E + sum(T * w for _f, _s, T, w, _b, _e in part) + 4 * H * E + 8 * H * N
+            one["layers"].append({"layer": layer + 1, "F": F_, "x_bytes_per_elem": s_in, "agg_s": round(agg_s, 4),
+                                  "edges_per_s": round(E / agg_s), "algorithmic_TBps": round(nbytes / agg_s / 1e12, 3)})
+        res["passes"].append(one)
+        print(json.dumps(one), flush=True)
+    inf._gat_forward = inner
+    res.pop("layers")
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:
