@@ -1043,6 +1043,57 @@ int64_t spp_graph_gat_workspace_bytes(int64_t num_targets);
 spp_status spp_graph_gat_forward(const spp_graph_gat_desc* desc, void* workspace_dev, int64_t workspace_bytes,
                                  void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * f3i  The layer tail of SAGEResInception in eval mode (exact, layer-wise inference): leaky_relu(BatchNorm(z)) plus
+ *      the residual, one pass over the rows of a GEMM tile, written straight into a slab of the next activation matrix.
+ *
+ *   Arithmetic contract, all in fp32, for i < n and c < C:
+ *        y        = fma(a[c], z[i,c], b[c])                    (one fma)
+ *        y        = y >= 0 ? y : negative_slope * y
+ *        out[i,c] = round_once(y + r[row(i), c])               (no residual: round_once(y))
+ *      a, b are fp32 [C]: the caller folds BatchNorm's running statistics into them, a = gamma / sqrt(var + eps),
+ *      b = beta - mean * a.  Nothing else enters an element.  round_once: fp32 as it is, bf16 to nearest even.
+ *
+ *        z    [n, C], rows z_stride_elems apart; fp32 / bf16
+ *        r    the residual, [r_rows, C], rows r_stride_elems apart; fp32 / fp16 / bf16; NULL = no residual (r_elem,
+ *             r_rows and r_stride_elems are then not read).  Addressed as a slab, row(i) = r_row0 + i (r_row0 >= 0,
+ *             r_ids_dev NULL), or by a list, row(i) = r_ids[i] (int64 [n], any order, duplicates allowed, r_row0 < 0):
+ *             the target convention of spp_graph_agg_desc.  A row index outside [0, r_rows) gives an OUTPUT row of
+ *             zeros, without a fault (the target rule of the graph kernels).
+ *        out  [n, C], rows out_stride_elems apart; fp32 / bf16
+ *      A stride of 0 means dense (C).  out must not overlap z or r rows that other rows of the call still read.
+ *
+ *   One launch on `stream`, no workspace, no atomics; the entry never waits for the device.  The vector form moves
+ *   W = 4 columns per lane when any of z, r, out is fp32 and W = 8 when all are 16-bit (the widest operand in 16-byte
+ *   pieces); it applies when C and the three row strides are multiples of W, the three bases are aligned to W
+ *   elements and a, b to 16 bytes.  Anything else runs one column per lane, with the same result.
+ *   Refused with SPP_ERR_INVALID before anything is enqueued: a NULL descriptor; NULL z_dev, out_dev, a_dev or b_dev;
+ *   an unknown element code (fp16 z or out, fp8 anywhere); C < 1; negative n, strides or r_rows; a non-zero stride
+ *   smaller than C; both a slab and a list; a residual with neither; a residual of no rows with n > 0.
+ *   n == 0: SPP_OK, nothing launched.
+ * ------------------------------------------------------------------------- */
+typedef struct spp_resinc_epilogue_desc {
+  int32_t z_elem;            /* SPP_ELEM_F32 / SPP_ELEM_BF16 */
+  int32_t r_elem;            /* SPP_ELEM_F32 / _F16 / _BF16 (with r_dev) */
+  int32_t out_elem;          /* SPP_ELEM_F32 / SPP_ELEM_BF16 */
+  float negative_slope;
+  const void* z_dev;
+  int64_t z_stride_elems;    /* 0 = dense */
+  const float* a_dev;        /* [C] */
+  const float* b_dev;        /* [C] */
+  const void* r_dev;         /* NULL: no residual */
+  int64_t r_stride_elems;    /* 0 = dense */
+  int64_t r_rows;
+  int64_t r_row0;            /* slab: the residual row of output row 0; < 0 with a list */
+  const int64_t* r_ids_dev;  /* list: the residual row of every output row; NULL with a slab */
+  int64_t n;
+  int64_t C;
+  void* out_dev;
+  int64_t out_stride_elems;  /* 0 = dense */
+} spp_resinc_epilogue_desc;
+
+spp_status spp_resinc_epilogue(const spp_resinc_epilogue_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,14 @@ class GraphGatDesc(C.Structure):
                 ("out_stride_elems", i64), ("negative_slope", C.c_float), ("reserved", i32)]
 
 
+class ResincEpilogueDesc(C.Structure):
+    """spp_resinc_epilogue_desc: out = leaky_relu(a * z + b) + r[row]; rows of r as a slab (r_row0 >= 0) or a list"""
+    _fields_ = [("z_elem", i32), ("r_elem", i32), ("out_elem", i32), ("negative_slope", C.c_float), ("z_dev", p),
+                ("z_stride_elems", i64), ("a_dev", p), ("b_dev", p), ("r_dev", p), ("r_stride_elems", i64),
+                ("r_rows", i64), ("r_row0", i64), ("r_ids_dev", p), ("n", i64), ("C", i64), ("out_dev", p),
+                ("out_stride_elems", i64)]
+
+
 class GroupOut(C.Structure):
     _fields_ = [("mfg", MfgOut), ("x_out", p), ("y_out", p)]
 
@@ -227,6 +235,7 @@ SIGNATURES = {
     "spp_graph_gat_chunk": (i64, []),
     "spp_graph_gat_workspace_bytes": (i64, [i64]),
     "spp_graph_gat_forward": (C.c_int, [C.POINTER(GraphGatDesc), p, i64, p]),
+    "spp_resinc_epilogue": (C.c_int, [C.POINTER(ResincEpilogueDesc), p]),
 }
 SPP_COMM_ID_BYTES = 128
 SPP_IPC_HANDLE_BYTES = 64

@@ -1,12 +1,13 @@
 """Exact, layer-wise inference over the whole resident graph (reference: driver/models.py:441 ``layerwise_inference``
 with ``SAGE.inference``): every node is scored from ALL its neighbours, one pass per layer over the graph's CSR, with
 no sampling, no dedup and no exchange.  The message passing is the HIP kernel pair of csrc/graph_aggregate.hip
-(``spp_graph_agg_forward``) for SAGE and GIN and of csrc/graph_gat.hip (``spp_graph_gat_forward``) for GAT; the layers'
-own parameters run through the library GEMMs torch dispatches to.
+(``spp_graph_agg_forward``) for SAGE, GIN and SAGEResInception and of csrc/graph_gat.hip (``spp_graph_gat_forward``) for
+GAT; SAGEResInception's layer tail is csrc/resinc_epilogue.hip (``spp_resinc_epilogue``); the layers' own parameters run
+through the library GEMMs torch dispatches to.
 
-``graph_aggregate`` and ``graph_gat_aggregate`` are the kernels' thin wrappers, ``layerwise_inference`` the driver
-behind ``SAGE.inference`` and ``GIN.inference`` and the entry point for ``GAT``.  Forward only, one GPU, fp16 / fp32 /
-bf16 inputs."""
+``graph_aggregate``, ``graph_gat_aggregate`` and ``resinc_epilogue`` are the kernels' thin wrappers,
+``layerwise_inference`` the driver behind ``SAGE.inference`` and ``GIN.inference`` and the entry point for ``GAT`` and
+``SAGEResInception``.  Forward only, one GPU, fp16 / fp32 / bf16 inputs."""
 import ctypes as C
 
 import torch
@@ -30,7 +31,7 @@ def graph_agg_workspace_bytes(num_targets):
     return int(nat.load().spp_graph_agg_workspace_bytes(int(num_targets)))
 
 
-def _check_matrix(x, what):
+def _check_matrix(x, what, name="x"):
     """x as the kernels read it: a 2-D fp16 / fp32 / bf16 matrix with unit column stride that carries no gradient"""
     if isinstance(x, Fp8Features):
         raise TypeError(f"{what}: an fp8 feature table (Fp8Features) is not supported as inference input; pass "
@@ -39,12 +40,12 @@ def _check_matrix(x, what):
         raise TypeError(f"{what}: {type(x).__name__} describes the rows of one sampled batch; inference reads the whole "
                         "feature matrix, one row per graph node")
     if not isinstance(x, torch.Tensor):
-        raise TypeError(f"{what}: x must be a torch.Tensor, got {type(x).__name__}")
+        raise TypeError(f"{what}: {name} must be a torch.Tensor, got {type(x).__name__}")
     if x.dim() != 2 or x.dtype not in _ELEM or (x.size(1) > 1 and x.stride(1) != 1):
-        raise ValueError(f"{what}: x must be a 2-D fp16 / fp32 / bf16 matrix with unit column stride, got "
+        raise ValueError(f"{what}: {name} must be a 2-D fp16 / fp32 / bf16 matrix with unit column stride, got "
                          f"{tuple(x.shape)} {x.dtype} strides {tuple(x.stride())}")
     if x.requires_grad:
-        raise RuntimeError(f"{what}: x requires grad, and inference is forward only (detach it)")
+        raise RuntimeError(f"{what}: {name} requires grad, and inference is forward only (detach it)")
 
 
 def _check_graph(x, rowptr, col, what):
@@ -197,6 +198,84 @@ def graph_gat_aggregate(h, a_src, a_dst, rowptr, col, *, heads, negative_slope=0
                         T, out, workspace)
 
 
+def resinc_epilogue(z, scale, shift, *, negative_slope, residual=None, row0=None, row_ids=None, out=None,
+                    out_dtype=None):
+    """SAGEResInception's layer tail in eval mode, one pass (``spp_resinc_epilogue``, include/spp.h):
+
+        out[i, c] = leaky_relu(scale[c] * z[i, c] + shift[c], negative_slope) + residual[row(i), c]
+
+    in fp32 (one fma, the slope, the add), rounded once when ``out`` is bf16.  ``z`` [n, C]: fp32 / bf16, possibly a
+    strided view (the columns of a GEMM tile); ``scale`` / ``shift``: contiguous fp32 [C], BatchNorm's running
+    statistics folded by the caller (scale = gamma / sqrt(var + eps), shift = beta - mean * scale).  ``residual``
+    [R, C]: fp16 / fp32 / bf16, read in place, either as a slab, ``row0`` (row(i) = row0 + i), or by a list,
+    ``row_ids`` (int64 [n], any order, duplicates allowed); a row index outside [0, R) gives an output row of zeros.
+    ``out``: an fp32 / bf16 [n, C] matrix to write into (rows of a larger matrix allowed; must not overlap rows of
+    ``z`` or ``residual`` that the call still reads); allocated in ``out_dtype`` (default fp32) when None.
+
+    Forward only: no autograd node is registered and an input that requires grad is refused.  Nothing here waits for the
+    device."""
+    what = "resinc_epilogue"
+    _check_matrix(z, what, "z")
+    if z.dtype not in _OUT_DTYPES:
+        raise ValueError(f"{what}: z must be fp32 or bf16, got {z.dtype}")
+    n, Cdim = z.shape
+    if Cdim < 1:
+        raise ValueError(f"{what}: z needs at least one column, got {tuple(z.shape)}")
+    for name, t in (("scale", scale), ("shift", shift)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (Cdim,) or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous fp32 tensor of shape [{Cdim}] (one entry per column)")
+        if t.requires_grad:
+            raise RuntimeError(f"{what}: {name} requires grad, and inference is forward only (detach it)")
+    if residual is None:
+        if row0 is not None or row_ids is not None:
+            raise ValueError(f"{what}: row0 / row_ids address the residual's rows, and there is no residual")
+    else:
+        _check_matrix(residual, what, "residual")
+        if residual.size(1) != Cdim or residual.size(0) < 1:
+            raise ValueError(f"{what}: residual must have z's {Cdim} columns and at least one row, got "
+                             f"{tuple(residual.shape)}")
+        if (row0 is None) == (row_ids is None):
+            raise ValueError(f"{what}: address the residual's rows either as a slab (row0) or as row_ids"
+                             + (", not both" if row0 is not None else ""))
+        if row_ids is None:
+            row0 = int(row0)
+            if row0 < 0:
+                raise ValueError(f"{what}: row0 must not be negative, got {row0}")
+        elif not isinstance(row_ids, torch.Tensor) or row_ids.dtype != torch.int64 or tuple(row_ids.shape) != (n,) \
+                or not row_ids.is_contiguous():
+            raise ValueError(f"{what}: row_ids must be a contiguous int64 tensor of shape [{n}] (one entry per row of z)")
+    if out is None:
+        out_dtype = torch.float32 if out_dtype is None else out_dtype
+        if out_dtype not in _OUT_DTYPES:
+            raise ValueError(f"{what}: out_dtype must be torch.float32 or torch.bfloat16, got {out_dtype}")
+    else:
+        if not isinstance(out, torch.Tensor) or out.dtype not in _OUT_DTYPES or tuple(out.shape) != (n, Cdim) \
+                or (Cdim > 1 and out.stride(1) != 1) or out.requires_grad:
+            raise ValueError(f"{what}: out must be an fp32 / bf16 matrix of shape [{n}, {Cdim}] with unit column stride "
+                             "that does not require grad")
+        if out_dtype is not None and out_dtype != out.dtype:
+            raise ValueError(f"{what}: out is {out.dtype}, out_dtype {out_dtype}")
+    nat.require_device()
+    tensors = [z, scale, shift] + [t for t in (residual, row_ids, out) if t is not None]
+    if not all(t.is_cuda and t.device == z.device for t in tensors):
+        raise ValueError(f"{what}: z, scale, shift, residual, row_ids and out must live on one CUDA device")
+    if out is None:
+        out = torch.empty((n, Cdim), dtype=out_dtype, device=z.device)
+    d = nat.ResincEpilogueDesc(z_elem=_ELEM[z.dtype], out_elem=_ELEM[out.dtype], negative_slope=float(negative_slope),
+                               z_dev=_p(z), z_stride_elems=z.stride(0) if n > 1 else Cdim, a_dev=_p(scale),
+                               b_dev=_p(shift), n=n, C=Cdim, out_dev=_p(out),
+                               out_stride_elems=out.stride(0) if n > 1 else Cdim)
+    if residual is not None:
+        R = residual.size(0)
+        d.r_elem, d.r_dev, d.r_rows = _ELEM[residual.dtype], _p(residual), R
+        d.r_stride_elems = residual.stride(0) if R > 1 else Cdim
+        d.r_row0, d.r_ids_dev = (-1, _p(row_ids)) if row_ids is not None else (row0, None)
+    if n:
+        with torch.cuda.device(z.device):
+            nat.check(nat.load().spp_resinc_epilogue(C.byref(d), _stream()))
+    return out
+
+
 _GEMM_ROWS = 1 << 16
 
 
@@ -289,11 +368,96 @@ def _gat_inference(model, x, rowptr, col, nodes, rows_per_slab, act_dtype):
     return cur
 
 
+def _resinc_head(model):
+    """the two bare Linears of SAGEResInception's MLP head (``end_up_with_fc=True``: no BatchNorm, no activation)"""
+    mods = list(model.mlp.module_list)
+    if len(mods) != 2 or not all(isinstance(m, torch.nn.Linear) for m in mods):
+        raise NotImplementedError("layerwise_inference: SAGEResInception's head must be exactly two Linears (its first "
+                                  "one is applied block by block, which needs it to be linear in the concatenation)")
+    return mods
+
+
+def _resinc_inference(model, x, rowptr, col, nodes, rows_per_slab, act_dtype):
+    """layerwise_inference for SAGEResInception.  In eval mode dropout is the identity and the model is
+
+      layer i    h_i = leaky_relu(BatchNorm_i([mean | h_{i-1}] @ [W_l | W_r]^T)) + res_i,   h_0 = x,
+                 res_1 = res_linears[0](x), res_i = h_{i-1} after; per slab ``graph_aggregate`` ("operand"), per fixed
+                 GEMM tile one product and one ``resinc_epilogue`` that writes the tile's rows of the next [N, hidden]
+                 matrix.  Layer 1's residual Linear is stacked into the same product ([0 | W_res] below [W_l | W_r], so
+                 the tile is [z | res]); later residuals are the rows of ``cur`` itself, read in place by slab or, on the
+                 last layer with ``nodes``, by the id list.
+      head       log_softmax(lin2(lin1(cat(x, h_1, .., h_L)))).  lin1 is a bare Linear, so lin1(cat(..)) is
+                 bias + sum_k block_k @ W1[:, block k]^T: an fp32 accumulator ``acc`` [rows, 2 * classes] takes every
+                 block's product when the block is complete, and no layer's matrix outlives the next layer.
+
+    Memory, as arithmetic: two [N, hidden] matrices of ``act_dtype`` at a layer boundary, as for SAGE, plus ``acc``:
+    4 * rows * 2 * classes bytes.  For all N = 111 M nodes and 172 classes that is 153 GB, which does not fit beside
+    2 * 57 + 26 + 28 = 168 GB on one 288 GB MI355X: ``nodes=`` is the papers-scale form."""
+    lin1, lin2 = _resinc_head(model)
+    N, dev = x.size(0), x.device
+    n_layers, hidden = len(model.convs), model.hidden_channels
+    rows_out = nodes.numel() if nodes is not None else N
+    ws = torch.empty(graph_agg_workspace_bytes(min(rows_per_slab, max(N, rows_out))), dtype=torch.uint8, device=dev)
+    acc = torch.zeros((rows_out, lin1.out_features), dtype=torch.float32, device=dev)
+    if lin1.bias is not None:
+        acc += lin1.bias.to(torch.float32)
+
+    def add_block(block, first_col):                     # acc += block @ W1[:, its columns]^T, over the fixed tiles
+        Wb = lin1.weight[:, first_col:first_col + block.size(1)].to(act_dtype).t()
+        for r, n, tile in _row_tiles(block):
+            acc[r:r + n] += (tile.to(act_dtype) @ Wb)[:n]
+
+    add_block(x if nodes is None else x[nodes], 0)
+    cur = x
+    for i, (conv, bn) in enumerate(zip(model.convs, model.bns)):
+        last = i == n_layers - 1
+        # BatchNorm on its running statistics, folded in fp32: a = gamma / sqrt(var + eps), b = beta - mean * a
+        a = bn.weight.to(torch.float32) / torch.sqrt(bn.running_var.to(torch.float32) + bn.eps)
+        b = bn.bias.to(torch.float32) - bn.running_mean.to(torch.float32) * a
+        W = torch.cat([conv.lin_l.weight, conv.lin_r.weight], dim=1)               # [hidden, 2K] = [W_l | W_r]
+        bias = conv.lin_l.bias
+        res = model.res_linears[i]
+        if isinstance(res, torch.nn.Linear):             # (layer 1) stacked: the tile comes out as [z | res(x_t)]
+            W = torch.cat([W, torch.cat([torch.zeros_like(res.weight), res.weight], dim=1)], dim=0)
+            if bias is not None or res.bias is not None:
+                zero = W.new_zeros(hidden)
+                bias = torch.cat([bias if bias is not None else zero, res.bias if res.bias is not None else zero])
+        Wt = W.to(act_dtype).t()
+        bias = bias.to(act_dtype) if bias is not None else None
+        ids = nodes if last else None
+        rows = ids.numel() if ids is not None else N
+        nxt = torch.empty((rows, hidden), dtype=act_dtype, device=dev)
+        for s in range(0, rows, rows_per_slab):
+            e = min(rows, s + rows_per_slab)
+            tgt = dict(target_ids=ids[s:e]) if ids is not None else dict(row0=s, num_targets=e - s)
+            A = graph_aggregate(cur, rowptr, col, epilogue="operand", out_dtype=act_dtype, workspace=ws, **tgt)
+            for r, n, tile in _row_tiles(A):
+                Z = torch.addmm(bias, tile, Wt) if bias is not None else tile @ Wt
+                if Z.size(1) > hidden:
+                    residual = dict(residual=Z[:, hidden:], row0=0)
+                elif ids is not None:
+                    residual = dict(residual=cur, row_ids=ids[s + r:s + r + n])
+                else:
+                    residual = dict(residual=cur, row0=s + r)
+                resinc_epilogue(Z[:n, :hidden], a, b, negative_slope=0.01, out=nxt[s + r:s + r + n], **residual)
+        add_block(nxt if last or nodes is None else nxt[nodes], x.size(1) + i * hidden)
+        cur = nxt                                        # (drops layer i-1's matrix)
+    W2t = lin2.weight.to(act_dtype).t()
+    b2 = lin2.bias.to(act_dtype) if lin2.bias is not None else None
+    out = torch.empty((rows_out, lin2.out_features), dtype=torch.float32, device=dev)
+    for r, n, tile in _row_tiles(acc):
+        h = tile.to(act_dtype)
+        h = torch.addmm(b2, h, W2t) if b2 is not None else h @ W2t
+        out[r:r + n] = torch.log_softmax(h[:n], dim=-1, dtype=torch.float32)
+    return out
+
+
 def layerwise_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 << 20, act_dtype=torch.float32):
     """Exact log-probabilities of every node, [N, classes] fp32 -- or of ``nodes`` (int64, any order, duplicates
-    allowed), [len(nodes), classes] -- for a ``SAGE``, ``GIN`` or ``GAT`` model over the whole graph.  (GAT, at any
-    ``heads``: see ``_gat_inference`` for its order of operations and memory; what follows describes SAGE and GIN, and
-    the arguments, the fixed GEMM tiles, eval mode and ``nodes`` mean the same for all three.)
+    allowed), [len(nodes), classes] -- for a ``SAGE``, ``GIN``, ``GAT`` or ``SAGEResInception`` model over the whole
+    graph.  (GAT, at any ``heads``: see ``_gat_inference`` for its order of operations and memory; SAGEResInception:
+    ``_resinc_inference``; what follows describes SAGE and GIN, and the arguments, the fixed GEMM tiles, eval mode and
+    ``nodes`` mean the same for all four.)
 
     Layer by layer, slab by slab of ``rows_per_slab`` nodes: ``graph_aggregate`` over each node's whole neighbour row,
     then the layer's own parameters as torch GEMMs (SAGE: [mean | x] @ [W_l | W_r]^T; GIN: ``conv.nn`` with BatchNorm's
@@ -309,10 +473,13 @@ def layerwise_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 <<
     boundary (layer i-1's is freed as soon as layer i is complete).  At N = 111 M and hidden 256 that is 113 GB each in
     fp32 and 57 GB in bf16, next to 26 GB of graph and 28 GB of features: fp32 activations do not fit one 288 GB MI355X
     at papers scale, ``act_dtype=torch.bfloat16`` does (26 + 28 + 2 * 57 = 168 GB)."""
-    from .models import GAT, GIN, SAGE
+    from .models import GAT, GIN, SAGE, SAGEResInception
     what = "layerwise_inference"
-    if not isinstance(model, (SAGE, GIN, GAT)):
-        raise NotImplementedError(f"{what}: implemented for SAGE and GIN (and GAT), not {type(model).__name__}")
+    if not isinstance(model, (SAGE, GIN, GAT, SAGEResInception)):
+        raise NotImplementedError(f"{what}: implemented for SAGE and GIN (and GAT, SAGEResInception), not "
+                                  f"{type(model).__name__}")
+    if isinstance(model, SAGEResInception):
+        _resinc_head(model)
     if isinstance(model, GAT):                                # the layers as models.GAT builds them
         for i, c in enumerate(model.convs):
             mean_heads = i == len(model.convs) - 1 and c.heads > 1
@@ -344,6 +511,8 @@ def layerwise_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 <<
         with torch.no_grad(), torch.autocast("cuda", enabled=False):
             if isinstance(model, GAT):
                 return _gat_inference(model, x, rowptr, col, nodes, rows_per_slab, act_dtype)
+            if isinstance(model, SAGEResInception):
+                return _resinc_inference(model, x, rowptr, col, nodes, rows_per_slab, act_dtype)
             n_layers = len(model.convs)
             ws = torch.empty(graph_agg_workspace_bytes(min(rows_per_slab, max(N, nodes.numel() if nodes is not None else 0))),
                              dtype=torch.uint8, device=x.device)

@@ -1109,9 +1109,10 @@ class SAGEResInception(torch.nn.Module):
         return torch.log_softmax(self.mlp(torch.cat(collect, -1)), dim=-1)
 
     def inference(self, x_all, rowptr, col, **kw):
-        raise NotImplementedError("SAGEResInception.inference: the head concatenates every layer's activations, so a "
-                                  "layer-wise pass would have to keep all layers' matrices of all nodes at once; "
-                                  "SAGE and GIN implement inference()")
+        raise NotImplementedError("SAGEResInception.inference: not a method of the model yet; the head concatenates "
+                                  "every layer's activations, which a layer-wise pass replaces by a running "
+                                  "accumulator of the head's first Linear: call inference.layerwise_inference(model, "
+                                  "x_all, rowptr, col, ...), which accepts SAGEResInception")
 
 
 _UNSUPPORTED_MODELS = {"sageclassic": "not used in the paper", "jknet": "not used in the paper",

@@ -4,10 +4,16 @@ with bf16 activations, timed per layer, and layer 1's slabs once more through th
 
     python tools/inference_profile.py [--workload S-papers] [--rows-per-slab 1048576] [--hidden 256] [--json out.json]
     python tools/inference_profile.py --model gat [--heads 4] [--repeats 3] ...
+    python tools/inference_profile.py --model sageresinception [--nodes 1500000] [--torch-epilogue] [--repeats 3] ...
 
 ``--model gat``: GAT 3 x hidden at ``--heads`` through spp_graph_gat_forward, ``--repeats`` whole passes in one process
 (the first warms up code objects and the GEMM library's choices; every pass is reported).  Its bytes are the mean's plus
 the logits: 4 * H per entry (a_src) and 8 * H per target (a_src of the self loop, a_dst).
+
+``--model sageresinception``: SAGEResInception 3 x hidden scored at a random sample of ``--nodes`` nodes; per layer the
+aggregation seconds as above, the epilogue seconds (events around every spp_resinc_epilogue call, summed; bytes: z, the
+residual row and the output row, bf16 each), the whole layer (layer 3's includes the head) and the whole call.
+``--torch-epilogue`` runs the same pass with the layer tail restated as torch ops, the kernel's yardstick.
 
 Per layer: seconds of the aggregation alone (events around every slab's graph_aggregate, summed), edges/s, and the
 algorithmic bytes/s  E * F * s (rows) + 16 * T + 8 * E (indices) + T * W * s_out (output); plus the seconds of the whole
@@ -30,9 +36,11 @@ def main():
     ap.add_argument("--hidden", type=int, default=256)
     ap.add_argument("--classes", type=int, default=172)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--model", choices=("sage", "gat"), default="sage")
+    ap.add_argument("--model", choices=("sage", "gat", "sageresinception"), default="sage")
     ap.add_argument("--heads", type=int, default=1)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--nodes", type=int, default=1_500_000, help="sageresinception: nodes scored (0 = all)")
+    ap.add_argument("--torch-epilogue", action="store_true", help="sageresinception: the layer tail as torch ops")
     a = ap.parse_args()
     from salient_plusplus_amd import _native as nat
     from salient_plusplus_amd import inference as inf
@@ -53,6 +61,8 @@ def main():
     print(json.dumps({k: v for k, v in res.items() if k != "layers"}), flush=True)
     if a.model == "gat":
         return gat_leg(a, wl, res)
+    if a.model == "sageresinception":
+        return resinc_leg(a, wl, res)
 
     # the aggregation of every slab, timed by events inside the one layerwise_inference call
     spans = []
@@ -102,6 +112,85 @@ def main():
     res["layer1_hop_kernel_s"] = round(hop_s, 4)
     res["layer1_hop_kernel_worst_slab"] = {"row0": worst[1], "s": round(worst[0], 4)}
     print(json.dumps({k: res[k] for k in ("total_s", "layer1_hop_kernel_s", "layer1_hop_kernel_worst_slab")}), flush=True)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+def _torch_tail(z, scale, shift, *, negative_slope, residual=None, row0=None, row_ids=None, out=None, out_dtype=None):
+    """resinc_epilogue's contract restated as torch ops (the yardstick of --torch-epilogue): the affine BatchNorm, the
+    leaky_relu, the residual rows and the write into the slab, each its own element-wise pass"""
+    y = torch.nn.functional.leaky_relu(z.float() * scale + shift, negative_slope)
+    if residual is not None:
+        y += (residual[row_ids] if row_ids is not None else residual[row0:row0 + z.size(0)]).float()
+    out.copy_(y)
+    return out
+
+
+def resinc_leg(a, wl, res):
+    """SAGEResInception 3 x hidden, bf16 activations, scored at a sample of ``--nodes`` nodes (``acc`` for all N does
+    not fit at papers scale): per layer the aggregation and the epilogue (events around every call, summed), the whole
+    layer, and the whole call; ``--repeats`` passes, the first a warm-up"""
+    from salient_plusplus_amd import inference as inf
+    from salient_plusplus_amd.models import SAGEResInception
+    x, rowptr, col = wl.x, wl.rowptr, wl.col
+    N, L = wl.num_nodes, 3
+    res.update(model="sageresinception", torch_epilogue=bool(a.torch_epilogue), passes=[])
+    res.pop("layers")
+    torch.manual_seed(0)
+    nodes = torch.randperm(N, device=x.device)[:min(a.nodes, N)] if a.nodes > 0 else None
+    res["scored_nodes"] = int(nodes.numel()) if nodes is not None else N
+    model = SAGEResInception(x.size(1), a.hidden, a.classes, L).to(x.device)
+    agg, epi, marks = [], [], []
+    inner_agg, inner_epi = inf.graph_aggregate, inf.resinc_epilogue
+    tail = _torch_tail if a.torch_epilogue else inner_epi
+
+    def timed(fn, spans):
+        def call(first, *args, **kw):
+            b, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            b.record()
+            out = fn(first, *args, **kw)
+            e.record()
+            spans.append((first.size(0), b, e))
+            return out
+        return call
+
+    def timed_agg(xm, *args, **kw):                       # a layer begins with the first slab's aggregation of a matrix
+        if not marks or marks[-1][0] != xm.data_ptr():
+            m = torch.cuda.Event(enable_timing=True)
+            m.record()
+            marks.append((xm.data_ptr(), len(agg), len(epi), m))
+        return timed(inner_agg, agg)(xm, *args, **kw)
+    inf.graph_aggregate, inf.resinc_epilogue = timed_agg, timed(tail, epi)
+    try:
+        for rep in range(a.repeats):
+            del agg[:], epi[:], marks[:]
+            torch.cuda.synchronize()
+            t0 = time.time()
+            out = inf.layerwise_inference(model, x, rowptr, col, nodes=nodes, rows_per_slab=a.rows_per_slab,
+                                          act_dtype=torch.bfloat16)
+            end = torch.cuda.Event(enable_timing=True)
+            end.record()
+            torch.cuda.synchronize()
+            one = {"pass": rep, "total_s": round(time.time() - t0, 3), "layers": []}
+            assert out.shape == (res["scored_nodes"], a.classes) and bool(torch.isfinite(out[:: max(1, out.size(0) // 4096)]).all())
+            del out
+            assert len(marks) == L, len(marks)
+            for k, (_ptr, a0, e0, m) in enumerate(marks):
+                a1, e1, nxt = (marks[k + 1][1], marks[k + 1][2], marks[k + 1][3]) if k + 1 < L else (len(agg), len(epi), end)
+                rows = sum(n for n, _b, _e in epi[e0:e1])
+                epi_s = sum(b.elapsed_time(e) for _n, b, e in epi[e0:e1]) / 1e3
+                # z, the residual row and the output row, bf16 each (layer 1: the residual is the tile's other half)
+                one["layers"].append({"layer": k + 1, "rows": rows, "epilogue_calls": e1 - e0,
+                                      "agg_s": round(sum(b.elapsed_time(e) for _n, b, e in agg[a0:a1]) / 1e3, 4),
+                                      "epilogue_s": round(epi_s, 4),
+                                      "epilogue_algorithmic_TBps": round(3 * 2 * rows * a.hidden / epi_s / 1e12, 3),
+                                      "layer_s": round(m.elapsed_time(nxt) / 1e3, 4)})
+            res["passes"].append(one)
+            print(json.dumps(one), flush=True)
+    finally:
+        inf.graph_aggregate, inf.resinc_epilogue = inner_agg, inner_epi
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:
