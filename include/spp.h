@@ -974,6 +974,54 @@ spp_status spp_graph_agg_forward(const spp_graph_agg_desc* desc, void* workspace
                                  void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * f3j  The same aggregation over a ROW-PARTITIONED source: x is not one matrix but num_parts row ranges, each in an
+ *      allocation of its own -- the ranks' partitions of the feature table or of a layer's activations, the peers' ones
+ *      mapped into this process with spp_ipc_open (or plain device pointers of in-process ranks).
+ *
+ *        num_parts        P, 1 .. SPP_GRAPH_AGG_MAX_PARTS
+ *        part_offsets     P + 1 entries (host, in the descriptor), non-decreasing, part_offsets[0] == 0: part p holds the
+ *                         global rows [part_offsets[p], part_offsets[p + 1]); x_rows = part_offsets[P]
+ *        x_parts_dev[p]   the address, in this process, of part p's FIRST row; NULL allowed exactly for an empty part
+ *        x_stride_elems   one row stride for all parts
+ *      rowptr, col (the whole graph's CSR, global ids), the targets (a slab or a list of GLOBAL ids), the epilogue, the
+ *      element codes, F, the output and self_scale: as spp_graph_agg_desc.  The entry reads x_rows + 1 entries of rowptr.
+ *
+ *   The summation contract of spp_graph_agg_forward holds word for word, and the result is bit-identical to that entry on
+ *   the concatenation of the parts.  A col entry outside [0, x_rows) reads global row 0, the first row of the first
+ *   non-empty part; a target id outside gives a row of zeros; the target's own row (SPP_AGG_OPERAND, the self term of
+ *   SPP_AGG_SUM) is read through the parts as well.  The vector form (four columns per lane) needs F % 4 == 0,
+ *   x_stride_elems % 4 == 0 and EVERY non-empty part's base aligned to 4 elements; otherwise the rows are read one column
+ *   per lane, with the same result.  An output misaligned for the vector form is refused, as there.  Workspace, stream
+ *   and launches: as spp_graph_agg_forward.  The entry maps nothing and enables no peer access: every base must already
+ *   be readable from the stream's device.
+ *   Refused with SPP_ERR_INVALID before anything is enqueued: num_parts out of range, part_offsets[0] != 0 or decreasing
+ *   offsets, a NULL base of a non-empty part, fp8 rows, and everything spp_graph_agg_forward refuses.
+ * ------------------------------------------------------------------------- */
+#define SPP_GRAPH_AGG_MAX_PARTS 16
+typedef struct spp_graph_agg_parts_desc {
+  int32_t epilogue;         /* SPP_AGG_MEAN / _OPERAND / _SUM */
+  int32_t x_elem;           /* SPP_ELEM_F32 / _F16 / _BF16 */
+  int32_t out_elem;         /* SPP_ELEM_F32 / SPP_ELEM_BF16 */
+  int32_t num_parts;        /* P */
+  const int64_t* rowptr_dev;
+  const int64_t* col_dev;
+  int64_t part_offsets[SPP_GRAPH_AGG_MAX_PARTS + 1];
+  const void* x_parts_dev[SPP_GRAPH_AGG_MAX_PARTS];
+  int64_t x_stride_elems;
+  int64_t F;
+  int64_t target_row0;      /* slab: the first target (a global id); < 0 with a list */
+  const int64_t* target_ids_dev; /* list: the targets (global ids); NULL with a slab */
+  int64_t num_targets;
+  void* out_dev;            /* [num_targets, F or 2F] */
+  int64_t out_stride_elems; /* 0 = dense */
+  float self_scale;         /* SUM: s = 1 + eps */
+  int32_t reserved;
+} spp_graph_agg_parts_desc;
+
+spp_status spp_graph_agg_parts_forward(const spp_graph_agg_parts_desc* desc, void* workspace_dev,
+                                       int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * f3h  GATConv attention over rows of the RESIDENT graph (exact, layer-wise GAT inference), in PyG's project-first
  *      order: the rows are already projected, h = x W^T, and the logits already taken from them.
  *

@@ -88,6 +88,18 @@ class GraphAggDesc(C.Structure):
                 ("out_stride_elems", i64), ("self_scale", C.c_float), ("reserved2", i32)]
 
 
+SPP_GRAPH_AGG_MAX_PARTS = 16
+
+
+class GraphAggPartsDesc(C.Structure):
+    """spp_graph_agg_parts_desc: GraphAggDesc with x as num_parts row ranges (part_offsets, one base address each)"""
+    _fields_ = [("epilogue", i32), ("x_elem", i32), ("out_elem", i32), ("num_parts", i32), ("rowptr_dev", p),
+                ("col_dev", p), ("part_offsets", i64 * (SPP_GRAPH_AGG_MAX_PARTS + 1)),
+                ("x_parts_dev", p * SPP_GRAPH_AGG_MAX_PARTS), ("x_stride_elems", i64), ("F", i64), ("target_row0", i64),
+                ("target_ids_dev", p), ("num_targets", i64), ("out_dev", p), ("out_stride_elems", i64),
+                ("self_scale", C.c_float), ("reserved", i32)]
+
+
 class GraphGatDesc(C.Structure):
     """spp_graph_gat_desc: projected rows h with their logits; targets as in GraphAggDesc"""
     _fields_ = [("x_elem", i32), ("out_elem", i32), ("heads", i32), ("relu", i32), ("rowptr_dev", p), ("col_dev", p),
@@ -232,6 +244,7 @@ SIGNATURES = {
     "spp_graph_agg_chunk": (i64, []),
     "spp_graph_agg_workspace_bytes": (i64, [i64]),
     "spp_graph_agg_forward": (C.c_int, [C.POINTER(GraphAggDesc), p, i64, p]),
+    "spp_graph_agg_parts_forward": (C.c_int, [C.POINTER(GraphAggPartsDesc), p, i64, p]),
     "spp_graph_gat_chunk": (i64, []),
     "spp_graph_gat_workspace_bytes": (i64, [i64]),
     "spp_graph_gat_forward": (C.c_int, [C.POINTER(GraphGatDesc), p, i64, p]),

@@ -16,6 +16,10 @@
 //   k_graph_agg_long  one workgroup per listed row: its 256 / lpr lane groups sum 256 / lpr chunks at a time, park the
 //                     chunk sums in LDS, and group 0 adds them in chunk order (double-buffered: one barrier a round).
 // Every offset is 64-bit (N * F reaches 2.8e10 elements at papers scale).  No atomics touch the output.
+//
+// f3j: the same two kernels over a ROW-PARTITIONED x (spp_graph_agg_parts_forward).  The row source is a template
+// parameter: NodeRows reads one matrix, PartRows finds the part that owns a global row first.  Same arithmetic, same
+// order, same bits.
 #include "spp_internal.h"
 
 #include <hip/hip_bf16.h>
@@ -97,21 +101,62 @@ struct Piece<false> {
   static __device__ __forceinline__ float fma(float s, float o, float a) { return fmaf(s, o, a); }
 };
 
+struct Args;
+
+// The row source of the kernels: Rows::Src is what the launch passes by value, Rows(src, a) what a lane asks for the
+// address of global row g.
 // row g of the full matrix; an id outside [0, x_rows) reads row 0 (the rule of the Table source: no fault)
 template <typename Tin>
 struct NodeRows {
+  using elem = Tin;
+  using Src = const Tin* __restrict__;
   const Tin* x;
   int64_t stride, rows;
+  __device__ __forceinline__ NodeRows(const Tin* src, const Args& a);
   __device__ __forceinline__ const Tin* operator()(int64_t g) const {
     return x + ((uint64_t)g < (uint64_t)rows ? g : 0) * stride;
   }
 };
 
+// The matrix as up to kMaxParts row ranges, each in an allocation of its own (a rank's partition, mapped into this
+// process): entry p holds the first global row of the p-th NON-EMPTY part and its base moved back by that many rows, so
+// that row g of every part is base + g * stride; the entries behind the last part start at INT64_MAX (no row reaches
+// them).  The launch passes the table by value.  Indexing that argument block with a per-lane owner would make the
+// compiler keep a private copy of it in scratch, and walking it entry by entry with scalar loads
+// puts two dependent scalar-load waits per entry in front of every row fetch (measured: 2.1-2.3 times the time of
+// NodeRows).  So thread 0 copies the table into LDS once per workgroup, with compile-time indices, and a lane finds the
+// owner by a branch-free binary search there: four dependent 8-byte LDS reads and one for the base, no loop, and the
+// searches of the four rows in flight overlap.
+constexpr int kMaxParts = SPP_GRAPH_AGG_MAX_PARTS;
+static_assert(kMaxParts == 16, "PartRows::operator() searches exactly 16 entries");
+template <typename Tin>
+struct PartTable {
+  int64_t first[kMaxParts];
+  const Tin* base[kMaxParts];
+};
+template <typename Tin>
+struct PartRows {
+  using elem = Tin;
+  using Src = PartTable<Tin>;
+  const int64_t* first;     // LDS
+  const Tin* const* base;   // LDS
+  int64_t stride, rows;
+  // every thread of the workgroup constructs it, before any of them leaves the kernel (a barrier inside)
+  __device__ __forceinline__ PartRows(const PartTable<Tin>& src, const Args& a);
+  __device__ __forceinline__ const Tin* operator()(int64_t g) const {
+    g = (uint64_t)g < (uint64_t)rows ? g : 0;
+    int p = g >= first[8] ? 8 : 0;  // the last entry with first <= g (first[0] = 0)
+    p += g >= first[p + 4] ? 4 : 0;
+    p += g >= first[p + 2] ? 2 : 0;
+    p += g >= first[p + 1] ? 1 : 0;
+    return base[p] + g * stride;
+  }
+};
+
 // columns c.. of the entries [b, e), added in CSR order one at a time from zero; four rows are in flight
-template <typename Tin, bool VEC4>
-__device__ __forceinline__ typename Piece<VEC4>::type sum_entries(const NodeRows<Tin>& row,
-                                                                  const int64_t* __restrict__ col, int64_t b, int64_t e,
-                                                                  int64_t c) {
+template <typename Rows, bool VEC4>
+__device__ __forceinline__ typename Piece<VEC4>::type sum_entries(const Rows& row, const int64_t* __restrict__ col,
+                                                                  int64_t b, int64_t e, int64_t c) {
   using P = Piece<VEC4>;
   typename P::type acc = P::zero();
   int64_t k = b;
@@ -140,6 +185,20 @@ struct Args {
   unsigned long long* counter;
   int64_t* list;
 };
+template <typename Tin>
+__device__ __forceinline__ NodeRows<Tin>::NodeRows(const Tin* src, const Args& a) : x(src), stride(a.x_stride), rows(a.x_rows) {}
+template <typename Tin>
+__device__ __forceinline__ PartRows<Tin>::PartRows(const PartTable<Tin>& src, const Args& a)
+    : stride(a.x_stride), rows(a.x_rows) {
+  __shared__ int64_t lds_first[kMaxParts];
+  __shared__ const Tin* lds_base[kMaxParts];
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int p = 0; p < kMaxParts; ++p) lds_first[p] = src.first[p], lds_base[p] = src.base[p];
+  }
+  __syncthreads();
+  first = lds_first, base = lds_base;
+}
 
 // what the sum of node t's row becomes, columns c.. of output row o (own: node t's row of x, NULL for a target id
 // outside the graph, whose output row is all zeros)
@@ -156,9 +215,11 @@ __device__ __forceinline__ void finish(const Args& a, typename Piece<VEC4>::type
   P::store(o + c, acc);
 }
 
-template <typename Tin, typename Tout, bool VEC4>
-__global__ __launch_bounds__(kNT) void k_graph_agg_rows(const Tin* __restrict__ x, Tout* __restrict__ out, Args a) {
+template <typename Rows, typename Tout, bool VEC4>
+__global__ __launch_bounds__(kNT) void k_graph_agg_rows(typename Rows::Src src, Tout* __restrict__ out, Args a) {
   using P = Piece<VEC4>;
+  using Tin = typename Rows::elem;
+  const Rows row(src, a);  // (PartRows: the whole workgroup, before anyone returns)
   const int lpr = 1 << a.lpr_log2;
   const int lane = threadIdx.x & (lpr - 1);
   const int64_t i = ((int64_t)blockIdx.x * kNT + threadIdx.x) >> a.lpr_log2;
@@ -170,21 +231,21 @@ __global__ __launch_bounds__(kNT) void k_graph_agg_rows(const Tin* __restrict__ 
     if (lane == 0) a.list[atomicAdd(a.counter, 1ull)] = i;
     return;
   }
-  const NodeRows<Tin> row{x, a.x_stride, a.x_rows};
   const Tin* own = in_graph ? row(t) : nullptr;
   Tout* o = out + i * a.out_stride;
   for (int64_t c = (int64_t)lane * P::kWidth; c < a.F; c += (int64_t)lpr * P::kWidth)
-    finish<Tin, Tout, VEC4>(a, sum_entries<Tin, VEC4>(row, a.col, b, e, c), e - b, own, o, c);
+    finish<Tin, Tout, VEC4>(a, sum_entries<Rows, VEC4>(row, a.col, b, e, c), e - b, own, o, c);
 }
 
-template <typename Tin, typename Tout, bool VEC4>
-__global__ __launch_bounds__(kNT) void k_graph_agg_long(const Tin* __restrict__ x, Tout* __restrict__ out, Args a) {
+template <typename Rows, typename Tout, bool VEC4>
+__global__ __launch_bounds__(kNT) void k_graph_agg_long(typename Rows::Src src, Tout* __restrict__ out, Args a) {
   using P = Piece<VEC4>;
   using piece = typename P::type;
+  using Tin = typename Rows::elem;
   __shared__ piece part[2][kNT];
   const int lpr = 1 << a.lpr_log2, groups = kNT >> a.lpr_log2;
   const int lane = threadIdx.x & (lpr - 1), grp = threadIdx.x >> a.lpr_log2;
-  const NodeRows<Tin> row{x, a.x_stride, a.x_rows};
+  const Rows row(src, a);
   const int64_t n = (int64_t)*a.counter;
   unsigned round = 0;  // (workgroup-uniform, as every loop bound below: all 256 threads reach every barrier)
   for (int64_t r = blockIdx.x; r < n; r += gridDim.x) {
@@ -204,7 +265,7 @@ __global__ __launch_bounds__(kNT) void k_graph_agg_long(const Tin* __restrict__ 
         piece p = P::zero();
         if (active && j < chunks) {
           const int64_t cb = b + j * kGraphChunk;
-          p = sum_entries<Tin, VEC4>(row, a.col, cb, std::min<int64_t>(e, cb + kGraphChunk), c);
+          p = sum_entries<Rows, VEC4>(row, a.col, cb, std::min<int64_t>(e, cb + kGraphChunk), c);
         }
         part[round & 1][threadIdx.x] = p;
         __syncthreads();
@@ -240,46 +301,70 @@ extern "C" int64_t spp_graph_agg_workspace_bytes(int64_t num_targets) {
   return kWorkspaceHeader + 8 * std::max<int64_t>(num_targets, 0);
 }
 
-extern "C" spp_status spp_graph_agg_forward(const spp_graph_agg_desc* desc, void* workspace_dev, int64_t workspace_bytes,
-                                            void* stream) {
-  const char* who = "spp_graph_agg_forward";
-  SPP_REQUIRE(desc, "%s: NULL descriptor", who);
-  const spp_graph_agg_desc& d = *desc;
+namespace {
+
+// what both entries share: spp_graph_agg_desc without its source
+struct Call {
+  int32_t epilogue, x_elem, out_elem;
+  const int64_t* rowptr;
+  const int64_t* col;
+  int64_t x_stride, x_rows, F, row0;
+  const int64_t* ids;
+  int64_t T;
+  void* out;
+  int64_t out_stride;
+  float self_scale;
+};
+
+// the source of spp_graph_agg_parts_forward: the non-empty parts in order
+struct Parts {
+  int n;
+  int64_t first[kMaxParts];
+  const void* base[kMaxParts];
+};
+
+// exactly one of x / parts is given
+spp_status forward(const char* who, const Call& d, const void* x_dev, const Parts* parts, void* workspace_dev,
+                   int64_t workspace_bytes, void* stream) {
   SPP_REQUIRE(d.epilogue == SPP_AGG_MEAN || d.epilogue == SPP_AGG_OPERAND || d.epilogue == SPP_AGG_SUM,
               "%s: epilogue %d (the mean, the operand and the sum; no activation on load)", who, (int)d.epilogue);
   SPP_REQUIRE(d.x_elem != SPP_ELEM_FP8_E4M3, "%s: fp8 rows are not read here (dequantise the table first)", who);
   SPP_REQUIRE((d.x_elem == SPP_ELEM_F32 || d.x_elem == SPP_ELEM_F16 || d.x_elem == SPP_ELEM_BF16) &&
                   (d.out_elem == SPP_ELEM_F32 || d.out_elem == SPP_ELEM_BF16),
               "%s: unknown or unsupported element code (x %d, out %d)", who, (int)d.x_elem, (int)d.out_elem);
-  const bool by_ids = d.target_ids_dev != nullptr, by_slab = d.target_row0 >= 0;
+  const bool by_ids = d.ids != nullptr, by_slab = d.row0 >= 0;
   SPP_REQUIRE(by_ids != by_slab, "%s: give the targets as a slab (target_row0 >= 0) or as a list (target_ids_dev), %s", who,
               by_ids ? "not both" : "one of them");
-  const int64_t T = d.num_targets, F = d.F;
+  const int64_t T = d.T, F = d.F;
   SPP_REQUIRE(T >= 0 && F >= 0 && d.x_rows >= 0, "%s: negative size", who);
-  SPP_REQUIRE(by_ids || (d.target_row0 <= d.x_rows && T <= d.x_rows - d.target_row0),
-              "%s: the slab [%lld, %lld) leaves the graph's %lld rows", who, (long long)d.target_row0,
-              (long long)(d.target_row0 + T), (long long)d.x_rows);
+  SPP_REQUIRE(by_ids || (d.row0 <= d.x_rows && T <= d.x_rows - d.row0),
+              "%s: the slab [%lld, %lld) leaves the graph's %lld rows", who, (long long)d.row0, (long long)(d.row0 + T),
+              (long long)d.x_rows);
   const int64_t width = d.epilogue == SPP_AGG_OPERAND ? 2 * F : F;
-  const int64_t out_stride = d.out_stride_elems > 0 ? d.out_stride_elems : width;
+  const int64_t out_stride = d.out_stride > 0 ? d.out_stride : width;
   SPP_REQUIRE(out_stride >= width, "%s: output stride smaller than the output row", who);
   SPP_REQUIRE(workspace_dev && aligned_to(workspace_dev, 16) && workspace_bytes >= spp_graph_agg_workspace_bytes(T),
               "%s: needs a 16-byte aligned workspace of spp_graph_agg_workspace_bytes(num_targets) = %lld bytes", who,
               (long long)spp_graph_agg_workspace_bytes(T));
   if (T == 0 || F == 0) return SPP_OK;
-  SPP_REQUIRE(d.rowptr_dev && d.col_dev && d.x_dev && d.out_dev && d.x_rows > 0, "%s: NULL buffer or empty graph", who);
-  SPP_REQUIRE(d.x_stride_elems >= F, "%s: row stride smaller than the row", who);
-  // the vector form: four columns per lane.  Rows of x that do not allow it are read one column per lane instead; an
-  // output that does not is refused (the caller allocates it)
-  const bool vec = F % 4 == 0 && d.x_stride_elems % 4 == 0 && aligned_to(d.x_dev, 4 * elem_bytes(d.x_elem));
-  SPP_REQUIRE(!vec || (out_stride % 4 == 0 && aligned_to(d.out_dev, 4 * elem_bytes(d.out_elem))),
+  SPP_REQUIRE(d.rowptr && d.col && (parts || x_dev) && d.out && d.x_rows > 0, "%s: NULL buffer or empty graph", who);
+  SPP_REQUIRE(d.x_stride >= F, "%s: row stride smaller than the row", who);
+  // the vector form: four columns per lane.  Rows of x that do not allow it (with parts: the rows of any of them) are
+  // read one column per lane instead; an output that does not is refused (the caller allocates it)
+  bool vec = F % 4 == 0 && d.x_stride % 4 == 0;
+  if (parts)
+    for (int p = 0; p < parts->n; ++p) vec = vec && aligned_to(parts->base[p], 4 * elem_bytes(d.x_elem));
+  else
+    vec = vec && aligned_to(x_dev, 4 * elem_bytes(d.x_elem));
+  SPP_REQUIRE(!vec || (out_stride % 4 == 0 && aligned_to(d.out, 4 * elem_bytes(d.out_elem))),
               "%s: F %% 4 == 0 needs the output aligned to 4 elements (base and stride)", who);
   const int lpr_log2 = lanes_log2(vec ? F / 4 : F);
   const int64_t grid = ceil_div(T << lpr_log2, kNT);
   SPP_REQUIRE(grid < (1ll << 31), "%s: too many targets for one launch (%lld)", who, (long long)T);
   hipStream_t st = as_stream(stream);
   Args a{};
-  a.rowptr = d.rowptr_dev, a.col = d.col_dev, a.ids = d.target_ids_dev, a.row0 = by_ids ? 0 : d.target_row0, a.T = T;
-  a.x_stride = d.x_stride_elems, a.x_rows = d.x_rows, a.F = F, a.out_stride = out_stride;
+  a.rowptr = d.rowptr, a.col = d.col, a.ids = d.ids, a.row0 = by_ids ? 0 : d.row0, a.T = T;
+  a.x_stride = d.x_stride, a.x_rows = d.x_rows, a.F = F, a.out_stride = out_stride;
   a.epilogue = d.epilogue, a.self_scale = d.self_scale, a.lpr_log2 = lpr_log2;
   a.counter = static_cast<unsigned long long*>(workspace_dev);
   a.list = reinterpret_cast<int64_t*>(static_cast<char*>(workspace_dev) + kWorkspaceHeader);
@@ -289,10 +374,24 @@ extern "C" spp_status spp_graph_agg_forward(const spp_graph_agg_desc* desc, void
     using Tin = typename decltype(tin)::type;
     using Tout = typename decltype(tout)::type;
     constexpr bool V = decltype(v)::value;
-    const Tin* x = static_cast<const Tin*>(d.x_dev);
-    Tout* out = static_cast<Tout*>(d.out_dev);
-    hipLaunchKernelGGL((k_graph_agg_rows<Tin, Tout, V>), dim3((unsigned)grid), dim3(kNT), 0, st, x, out, a);
-    hipLaunchKernelGGL((k_graph_agg_long<Tin, Tout, V>), dim3(long_grid), dim3(kNT), 0, st, x, out, a);
+    Tout* out = static_cast<Tout*>(d.out);
+    if (parts) {
+      // each base moved back by its part's first row (never dereferenced below that row; integer arithmetic, the
+      // address may lie before the allocation)
+      PartTable<Tin> t{};
+      for (int p = 0; p < kMaxParts; ++p) t.first[p] = INT64_MAX;  // (behind the last part: never the owner)
+      for (int p = 0; p < parts->n; ++p) {
+        t.first[p] = parts->first[p];
+        t.base[p] = reinterpret_cast<const Tin*>(reinterpret_cast<uintptr_t>(parts->base[p]) -
+                                                 (uintptr_t)parts->first[p] * (uintptr_t)d.x_stride * sizeof(Tin));
+      }
+      hipLaunchKernelGGL((k_graph_agg_rows<PartRows<Tin>, Tout, V>), dim3((unsigned)grid), dim3(kNT), 0, st, t, out, a);
+      hipLaunchKernelGGL((k_graph_agg_long<PartRows<Tin>, Tout, V>), dim3(long_grid), dim3(kNT), 0, st, t, out, a);
+    } else {
+      const Tin* x = static_cast<const Tin*>(x_dev);
+      hipLaunchKernelGGL((k_graph_agg_rows<NodeRows<Tin>, Tout, V>), dim3((unsigned)grid), dim3(kNT), 0, st, x, out, a);
+      hipLaunchKernelGGL((k_graph_agg_long<NodeRows<Tin>, Tout, V>), dim3(long_grid), dim3(kNT), 0, st, x, out, a);
+    }
   };
   auto by_out = [&](auto tin, auto v) {
     d.out_elem == SPP_ELEM_BF16 ? launch(tin, Type<bf16>{}, v) : launch(tin, Type<float>{}, v);
@@ -304,4 +403,39 @@ extern "C" spp_status spp_graph_agg_forward(const spp_graph_agg_desc* desc, void
   vec ? by_in(std::true_type{}) : by_in(std::false_type{});
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
+}
+
+}  // namespace
+
+extern "C" spp_status spp_graph_agg_forward(const spp_graph_agg_desc* desc, void* workspace_dev, int64_t workspace_bytes,
+                                            void* stream) {
+  const char* who = "spp_graph_agg_forward";
+  SPP_REQUIRE(desc, "%s: NULL descriptor", who);
+  const spp_graph_agg_desc& d = *desc;
+  const Call c{d.epilogue,    d.x_elem,         d.out_elem,    d.rowptr_dev, d.col_dev,          d.x_stride_elems, d.x_rows, d.F,
+               d.target_row0, d.target_ids_dev, d.num_targets, d.out_dev,    d.out_stride_elems, d.self_scale};
+  return forward(who, c, d.x_dev, nullptr, workspace_dev, workspace_bytes, stream);
+}
+
+extern "C" spp_status spp_graph_agg_parts_forward(const spp_graph_agg_parts_desc* desc, void* workspace_dev,
+                                                  int64_t workspace_bytes, void* stream) {
+  const char* who = "spp_graph_agg_parts_forward";
+  SPP_REQUIRE(desc, "%s: NULL descriptor", who);
+  const spp_graph_agg_parts_desc& d = *desc;
+  SPP_REQUIRE(d.num_parts >= 1 && d.num_parts <= SPP_GRAPH_AGG_MAX_PARTS, "%s: num_parts %d outside 1..%d", who,
+              (int)d.num_parts, (int)SPP_GRAPH_AGG_MAX_PARTS);
+  SPP_REQUIRE(d.part_offsets[0] == 0, "%s: part_offsets[0] must be 0, got %lld", who, (long long)d.part_offsets[0]);
+  Parts parts{};
+  for (int p = 0; p < d.num_parts; ++p) {
+    SPP_REQUIRE(d.part_offsets[p + 1] >= d.part_offsets[p], "%s: part_offsets decrease at part %d (%lld after %lld)", who, p,
+                (long long)d.part_offsets[p + 1], (long long)d.part_offsets[p]);
+    if (d.part_offsets[p + 1] == d.part_offsets[p]) continue;  // an empty part owns no row: its base may be NULL
+    SPP_REQUIRE(d.x_parts_dev[p], "%s: part %d holds the rows [%lld, %lld) and its base is NULL", who, p,
+                (long long)d.part_offsets[p], (long long)d.part_offsets[p + 1]);
+    parts.first[parts.n] = d.part_offsets[p], parts.base[parts.n] = d.x_parts_dev[p], ++parts.n;
+  }
+  const Call c{d.epilogue,    d.x_elem,         d.out_elem,    d.rowptr_dev, d.col_dev,          d.x_stride_elems,
+               d.part_offsets[d.num_parts],     d.F,
+               d.target_row0, d.target_ids_dev, d.num_targets, d.out_dev,    d.out_stride_elems, d.self_scale};
+  return forward(who, c, nullptr, &parts, workspace_dev, workspace_bytes, stream);
 }

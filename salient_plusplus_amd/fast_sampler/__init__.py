@@ -31,7 +31,7 @@ from ..fp8 import Fp8Features
 
 __all__ = ["Config", "Session", "ProtoDistributedBatch", "RangePartitionBook", "Cache", "sample_adj",
            "multilayer_sample", "full_sample", "to_row_major", "serial_index", "NativeComm", "native_comm",
-           "set_native_comm", "async_errors", "set_sampler_options", "sampler_options", "sampler_info", "TableRows", "RowRefs", "Fp8Features", "fp8_gather_rows", "resident_graph",
+           "set_native_comm", "async_errors", "set_sampler_options", "sampler_options", "sampler_info", "TableRows", "RowRefs", "Fp8Features", "fp8_gather_rows", "resident_graph", "resident_partition",
            "P2PPeers", "set_p2p_peers", "p2p_open_peers"]
 
 # four slot-sets of 16 batches (~75 MB of workspace per slot at fanout [15,10,5], batch 1024: 4.8 GB).  With two sets, a
@@ -841,6 +841,39 @@ def resident_graph(config):
     if x is None or x.dim() != 2 or x.numel() == 0:
         raise RuntimeError("resident_graph: the configuration carries no feature table (x_cpu)")
     return _resident.get_rows(x), _resident.get(config.rowptr, torch.int64), _resident.get(config.col, torch.int64)
+
+
+def resident_partition(config):
+    """(x_local, rowptr, col, part_offsets, rank) of a DISTRIBUTED, non-fp8 configuration: this rank's resident partition
+    of the feature table (``x_gpu`` then ``x_cpu``, as its Sessions hold it: uploaded once, rows padded by the resident
+    tables' rule), the whole graph's resident CSR, the partition book's offsets (host int64, P + 1 entries) and the rank --
+    the arguments of ``inference.partitioned_layerwise_inference``.  Read-only: the samplers read them concurrently."""
+    if not bool(getattr(config, "distributed", False)):
+        raise RuntimeError("resident_partition: not a distributed configuration; its whole table is resident_graph()'s")
+    xg, xc = getattr(config, "x_gpu", None), getattr(config, "x_cpu", None)
+    if isinstance(xg, Fp8Features) or isinstance(xc, Fp8Features):
+        raise RuntimeError("resident_partition: the configuration's features are an fp8 table, which inference does not read")
+    pb = getattr(config, "partition_book", None)
+    if pb is None:
+        raise RuntimeError("resident_partition: the configuration carries no partition book")
+    offs = pb._offsets_host()
+    rank = int(pb.rank)
+    if not 0 <= rank < offs.numel() - 1:
+        raise RuntimeError(f"resident_partition: rank {rank} outside the book's {offs.numel() - 1} partitions")
+    parts = [t for t in (xg, xc) if t is not None and t.dim() == 2 and t.size(0) > 0]
+    if len(parts) == 2:
+        x = _resident_concat(xg, xc)
+    elif len(parts) == 1:
+        x = _resident.get_rows(parts[0])
+    else:
+        wide = [t for t in (xg, xc) if t is not None and t.dim() == 2 and t.size(1) > 0]
+        if not wide:
+            raise RuntimeError("resident_partition: the configuration carries no feature table (x_gpu / x_cpu)")
+        x = torch.empty((0, wide[0].size(1)), dtype=wide[0].dtype, device=_device())
+    n_local = int(offs[rank + 1] - offs[rank])
+    if x.size(0) != n_local:
+        raise RuntimeError(f"resident_partition: the partition holds {x.size(0)} rows, the book gives rank {rank} {n_local}")
+    return x, _resident.get(config.rowptr, torch.int64), _resident.get(config.col, torch.int64), offs, rank
 
 
 class Session:

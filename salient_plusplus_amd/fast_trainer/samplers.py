@@ -349,6 +349,11 @@ class FastSampler(ABCNeighborSampler):
         for ``model.inference(*sampler.resident_graph())`` without a second upload.  Single-GPU, non-distributed only."""
         return fast_sampler.resident_graph(self.cfg)
 
+    def resident_partition(self):
+        """(x_local, rowptr, col, part_offsets, rank) of a distributed, non-fp8 configuration
+        (``fast_sampler.resident_partition``): the arguments of ``inference.partitioned_layerwise_inference``."""
+        return fast_sampler.resident_partition(self.cfg)
+
     # the epoch's seeds and the feature cache live in the configuration
     @property
     def idx(self):

@@ -7,13 +7,19 @@ through the library GEMMs torch dispatches to.
 
 ``graph_aggregate``, ``graph_gat_aggregate`` and ``resinc_epilogue`` are the kernels' thin wrappers,
 ``layerwise_inference`` the driver behind ``SAGE.inference`` and ``GIN.inference`` and the entry point for ``GAT`` and
-``SAGEResInception``.  Forward only, one GPU, fp16 / fp32 / bf16 inputs."""
+``SAGEResInception``.  Forward only, one GPU, fp16 / fp32 / bf16 inputs.
+
+Over a row-PARTITIONED feature table (one range of nodes per rank, the peers' partitions mapped into the process):
+``graph_aggregate_parts`` (``spp_graph_agg_parts_forward``) and ``partitioned_layerwise_inference`` for SAGE and GIN, with
+``LocalPeers`` (ranks as threads of one process) or ``IpcPeers`` (one process per rank on one node) between the ranks."""
 import ctypes as C
+import threading
 
 import torch
 
 from . import _native as nat
-from .fast_sampler import RowRefs, TableRows
+from .fast_sampler import P2PPeers, RowRefs, TableRows, _common_stride, _row_stride_elems, _table_stride_bytes, \
+    p2p_open_peers
 from .fp8 import Fp8Features
 from .models import _ELEM, _p, _stream
 
@@ -111,6 +117,147 @@ def graph_aggregate(x, rowptr, col, *, row0=None, num_targets=None, target_ids=N
                          out_stride_elems=0, self_scale=float(self_scale))
     with torch.cuda.device(x.device):
         nat.check(L.spp_graph_agg_forward(C.byref(d), C.c_void_p(workspace.data_ptr()), workspace.numel(), _stream()))
+    return out
+
+
+def _check_offsets(part_offsets, what):
+    """part_offsets as a list of P + 1 ints: P in 1..SPP_GRAPH_AGG_MAX_PARTS, first entry 0, non-decreasing"""
+    if isinstance(part_offsets, torch.Tensor):
+        part_offsets = part_offsets.detach().cpu().tolist()
+    off = [int(v) for v in part_offsets]
+    P = len(off) - 1
+    if not 1 <= P <= nat.SPP_GRAPH_AGG_MAX_PARTS:
+        raise ValueError(f"{what}: part_offsets must hold 2..{nat.SPP_GRAPH_AGG_MAX_PARTS + 1} entries (one part to "
+                         f"{nat.SPP_GRAPH_AGG_MAX_PARTS}), got {len(off)}")
+    if off[0] != 0 or any(b < a for a, b in zip(off, off[1:])):
+        raise ValueError(f"{what}: part_offsets must start at 0 and never decrease, got {off}")
+    return off
+
+
+def _parts_source(parts, off, dtype, F, what):
+    """(base addresses [P], row stride in elements, dtype, F, device or None) of the two forms of ``parts``"""
+    P = len(off) - 1
+    if isinstance(parts, P2PPeers):
+        if dtype not in _ELEM or not isinstance(F, int) or F < 0:
+            raise ValueError(f"{what}: a P2PPeers source needs dtype= (fp16 / fp32 / bf16) and F= (the row width)")
+        if len(parts.ptrs) != P:
+            raise ValueError(f"{what}: {len(parts.ptrs)} peer tables for {P} parts")
+        esize = torch.empty(0, dtype=dtype).element_size()
+        if parts.stride % esize:
+            raise ValueError(f"{what}: the peers' row stride ({parts.stride} bytes) is no multiple of the element size")
+        for p in range(P):
+            if off[p + 1] > off[p] and not parts.ptrs[p]:
+                raise ValueError(f"{what}: part {p} holds the rows [{off[p]}, {off[p + 1]}) and has no address")
+        return list(parts.ptrs), parts.stride // esize, dtype, F, None
+    if dtype is not None or F is not None:
+        raise ValueError(f"{what}: dtype= and F= describe a P2PPeers source; tensors carry their own")
+    tabs = list(parts)
+    if len(tabs) != P:
+        raise ValueError(f"{what}: {len(tabs)} parts for {P} ranges of part_offsets")
+    live = []
+    for p, t in enumerate(tabs):
+        rows = off[p + 1] - off[p]
+        if t is None:
+            if rows:
+                raise ValueError(f"{what}: part {p} holds the rows [{off[p]}, {off[p + 1]}) and is None")
+            continue
+        _check_matrix(t, what, f"part {p}")
+        if t.size(0) != rows:
+            raise ValueError(f"{what}: part {p} has {t.size(0)} rows, part_offsets gives it {rows}")
+        if rows:
+            live.append((p, t))
+    if not live:
+        raise ValueError(f"{what}: every part is empty")
+    first = live[0][1]
+    if any(t.dtype != first.dtype or t.size(1) != first.size(1) for _p, t in live):
+        raise ValueError(f"{what}: the parts must share one dtype and one row width, got "
+                         f"{sorted({(str(t.dtype), t.size(1)) for _p, t in live})}")
+    if any(t.device != first.device for _p, t in live):
+        raise ValueError(f"{what}: in-process parts on different devices "
+                         f"({sorted({str(t.device) for _p, t in live})}); parts of other devices are mapped by their "
+                         "owners' handles (p2p_open_peers), nothing here enables peer access")
+    strides = sorted({t.stride(0) for _p, t in live if t.size(0) > 1})     # (a part of one row has no stride of its own)
+    if len(strides) > 1:
+        raise ValueError(f"{what}: the parts must share one row stride, got {strides} elements")
+    stride = strides[0] if strides else first.size(1)
+    ptrs = [0] * P
+    for p, t in live:
+        ptrs[p] = t.data_ptr()
+    return ptrs, stride, first.dtype, first.size(1), first.device
+
+
+def graph_aggregate_parts(parts, part_offsets, rowptr, col, *, row0=None, num_targets=None, target_ids=None,
+                          epilogue="mean", self_scale=0.0, out_dtype=torch.float32, workspace=None, out=None,
+                          dtype=None, F=None):
+    """``graph_aggregate`` over a row-partitioned source (``spp_graph_agg_parts_forward``, include/spp.h): part p holds
+    the global rows [part_offsets[p], part_offsets[p + 1]) of x, in an allocation of its own.  The result is the bits of
+    ``graph_aggregate(torch.cat(parts), ...)``.
+
+    ``parts``: a list of P CUDA tensors on one device (an empty part may be None or have 0 rows) that share dtype, width
+    and row stride -- or a ``P2PPeers`` (the ranks' partitions as addresses in this process, ``p2p_open_peers``) with
+    ``dtype=`` and ``F=``.  ``rowptr`` / ``col``: the WHOLE graph's CSR with global ids; the targets, ``epilogue``,
+    ``self_scale``, ``out_dtype`` and ``workspace`` as ``graph_aggregate``, the ids global.  ``out``: an fp32 / bf16
+    [T, F or 2F] matrix to write into (rows of a larger one allowed).  Nothing here maps memory or enables peer access,
+    and nothing waits for the device."""
+    what = "graph_aggregate_parts"
+    off = _check_offsets(part_offsets, what)
+    ptrs, stride, x_dtype, Fdim, dev = _parts_source(parts, off, dtype, F, what)
+    N = off[-1]
+    for name, t in (("rowptr", rowptr), ("col", col)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous 1-D int64 tensor")
+    if rowptr.numel() != N + 1:
+        raise ValueError(f"{what}: the parts hold {N} rows, the graph {rowptr.numel() - 1} nodes (one row per node)")
+    if epilogue not in _EPILOGUES:
+        raise ValueError(f"{what}: epilogue must be 'mean', 'operand' or 'sum', got {epilogue!r}")
+    if out_dtype not in _OUT_DTYPES:
+        raise ValueError(f"{what}: out_dtype must be torch.float32 or torch.bfloat16, got {out_dtype}")
+    slab = row0 is not None or num_targets is not None
+    if slab == (target_ids is not None):
+        raise ValueError(f"{what}: give the targets either as a slab (row0 and num_targets) or as target_ids"
+                         + (", not both" if slab else ""))
+    if slab:
+        if row0 is None or num_targets is None:
+            raise ValueError(f"{what}: a slab needs both row0 and num_targets")
+        row0, T = int(row0), int(num_targets)
+        if row0 < 0 or T < 0 or row0 + T > N:
+            raise ValueError(f"{what}: the slab [{row0}, {row0 + T}) leaves the graph's {N} nodes")
+    else:
+        if not isinstance(target_ids, torch.Tensor) or target_ids.dtype != torch.int64 or target_ids.dim() != 1 \
+                or not target_ids.is_contiguous():
+            raise ValueError(f"{what}: target_ids must be a contiguous 1-D int64 tensor")
+        row0, T = -1, target_ids.numel()
+    width = 2 * Fdim if epilogue == "operand" else Fdim
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != out_dtype or tuple(out.shape) != (T, width) \
+                or (width > 1 and out.stride(1) != 1) or out.requires_grad:
+            raise ValueError(f"{what}: out must be a {out_dtype} matrix of shape [{T}, {width}] with unit column stride "
+                             "that does not require grad")
+    nat.require_device()
+    dev = rowptr.device if dev is None else dev
+    tensors = [rowptr, col] + [t for t in (None if slab else target_ids, workspace, out) if t is not None]
+    if dev.type != "cuda" or not all(t.is_cuda and t.device == dev for t in tensors):
+        raise ValueError(f"{what}: the parts, rowptr, col, target_ids, workspace and out must live on one CUDA device")
+    L = nat.load()
+    nbytes = int(L.spp_graph_agg_workspace_bytes(T))
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < nbytes:
+        raise ValueError(f"{what}: workspace must be a contiguous uint8 tensor of at least {nbytes} bytes")
+    if out is None:
+        out = torch.empty((T, width), dtype=out_dtype, device=dev)
+    d = nat.GraphAggPartsDesc(epilogue=_EPILOGUES[epilogue], x_elem=_ELEM[x_dtype], out_elem=_ELEM[out_dtype],
+                              num_parts=len(off) - 1, rowptr_dev=_p(rowptr), col_dev=_p(col), x_stride_elems=stride,
+                              F=Fdim, target_row0=row0, target_ids_dev=_p(target_ids) if not slab else None,
+                              num_targets=T, out_dev=_p(out), out_stride_elems=out.stride(0) if T > 1 else 0,
+                              self_scale=float(self_scale))
+    for p, v in enumerate(off):
+        d.part_offsets[p] = v
+    for p, v in enumerate(ptrs):
+        d.x_parts_dev[p] = v or None
+    with torch.cuda.device(dev):
+        nat.check(L.spp_graph_agg_parts_forward(C.byref(d), C.c_void_p(workspace.data_ptr()), workspace.numel(),
+                                                _stream()))
     return out
 
 
@@ -547,4 +694,202 @@ def layerwise_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 <<
                 cur = nxt                                # (drops layer i-1's matrix)
             return cur
     finally:
+        model.train(was_training)
+
+
+class LocalPeers:
+    """``peers`` of ``partitioned_layerwise_inference`` for ranks that are THREADS of one process on one device: one
+    object shared by the threads.  ``share`` hands every rank the others' tensors as plain device addresses; ``barrier``
+    is a ``threading.Barrier`` with a timeout.  A rank that fails calls ``abort`` (the driver does), which breaks the
+    barrier: the other ranks raise instead of waiting.  ``bind(rank)`` tells the object which rank the calling thread is."""
+
+    def __init__(self, world, timeout=120.0):
+        self.world = int(world)
+        if self.world < 1:
+            raise ValueError(f"LocalPeers: world must be positive, got {world}")
+        self._barrier = threading.Barrier(self.world, timeout=float(timeout))
+        self._slots = [None] * self.world
+        self._tls = threading.local()
+
+    def bind(self, rank):
+        if not 0 <= int(rank) < self.world:
+            raise ValueError(f"LocalPeers: rank {rank} outside the world of {self.world}")
+        self._tls.rank = int(rank)
+
+    def barrier(self):
+        try:
+            self._barrier.wait()
+        except threading.BrokenBarrierError:
+            raise RuntimeError("LocalPeers: another rank failed or did not arrive within the timeout") from None
+
+    def abort(self):
+        self._barrier.abort()
+
+    def share(self, tensor):
+        rank = getattr(self._tls, "rank", None)
+        if rank is None:
+            raise RuntimeError("LocalPeers: bind(rank) first (which rank is this thread?)")
+        self._slots[rank] = tensor
+        self.barrier()                                   # every rank has posted
+        tabs = list(self._slots)
+        self.barrier()                                   # every rank has read: the slots may be posted again
+        live = [t for t in tabs if t is not None and t.numel()]
+        if len({t.device for t in live}) > 1:
+            raise ValueError("LocalPeers: the ranks' tensors live on different devices; in-process ranks share one")
+        return P2PPeers([t.data_ptr() if t is not None and t.numel() else 0 for t in tabs],
+                        _common_stride([_table_stride_bytes(t) for t in live]) if live else 0, keep=tabs)
+
+    def close(self):
+        pass
+
+
+class IpcPeers:
+    """``peers`` of ``partitioned_layerwise_inference`` for one PROCESS per rank on one node, over a torch.distributed
+    group of any backend: ``share`` is ``p2p_open_peers`` (HIP IPC handles by all_gather_object; peer access is enabled by
+    the mapping call, nowhere else), a fresh set of mappings per call that its ``P2PPeers.close()`` unmaps -- nothing is
+    cached between calls, so no address outlives the allocation it was opened for.  ``barrier`` is
+    ``dist.monitored_barrier`` with a timeout where the backend has it (gloo), a plain barrier otherwise."""
+
+    def __init__(self, group=None, timeout=300.0):
+        self.group, self.timeout = group, float(timeout)
+
+    def share(self, tensor):
+        return p2p_open_peers(tensor, self.group)
+
+    def barrier(self):
+        import datetime
+        import torch.distributed as dist
+        if dist.get_backend(self.group) == "gloo":
+            dist.monitored_barrier(self.group, timeout=datetime.timedelta(seconds=self.timeout))
+        else:
+            dist.barrier(self.group)
+
+    def close(self):
+        pass
+
+
+def partitioned_layerwise_inference(model, x_local, rowptr, col, *, part_offsets, rank, peers, nodes=None,
+                                    rows_per_slab=1 << 20, act_dtype=torch.float32):
+    """``layerwise_inference`` for SAGE and GIN when the feature table is row-partitioned over the ranks: every rank calls
+    this with its own partition ``x_local`` (the global rows [part_offsets[rank], part_offsets[rank + 1])), the WHOLE
+    graph's CSR (global ids) and the same ``model``, and gets the fp32 log-probabilities of ITS node range,
+    [n_local, classes] -- or of ``nodes`` (global ids, all inside the rank's range).  The bits are those of
+    ``layerwise_inference`` over the concatenated table, rows [part_offsets[rank], part_offsets[rank + 1]).
+
+    Per rank: the ping-pong activation buffers [n_local, hidden] of ``act_dtype`` are allocated up front (one for a
+    two-layer model) and published with ``x_local`` once through ``peers``; each layer aggregates the rank's own slabs with
+    ``graph_aggregate_parts`` over ALL ranks' previous-layer parts, runs the layer's parameters over the same fixed GEMM
+    tiles as ``layerwise_inference`` and writes its rows of the next layer into its own buffer; then the rank synchronises
+    its stream and waits in ``peers.barrier()`` before anyone reads the layer or reuses a buffer.  After the last barrier
+    the mappings are closed.
+
+    ``peers``: ``share(tensor) -> P2PPeers`` (collective, same order on every rank), ``barrier()``, ``close()``; optional
+    ``bind(rank)`` and ``abort()``.  ``LocalPeers`` and ``IpcPeers`` are the two implementations.  GAT and
+    SAGEResInception over parts are not built.
+
+    Memory, as arithmetic (S-mag, N = 121.8 M, F = 768 fp16, hidden 256, bf16): per rank of P, 187 / P GB of table and
+    2 * 62 / P GB of activations next to its copy of the 22 GB graph."""
+    from .models import GAT, GIN, SAGE, SAGEResInception
+    what = "partitioned_layerwise_inference"
+    if isinstance(model, (GAT, SAGEResInception)):
+        raise NotImplementedError(f"{what}: {type(model).__name__} over a partitioned table is not built (its layers "
+                                  "need the long-row softmax / the fused layer tail over parts); SAGE and GIN are")
+    if not isinstance(model, (SAGE, GIN)):
+        raise NotImplementedError(f"{what}: implemented for SAGE and GIN, not {type(model).__name__}")
+    _check_matrix(x_local, what, "x_local")
+    off = _check_offsets(part_offsets, what)
+    P = len(off) - 1
+    rank = int(rank)
+    if not 0 <= rank < P:
+        raise ValueError(f"{what}: rank {rank} outside the {P} parts")
+    lo, hi = off[rank], off[rank + 1]
+    n_local, N = hi - lo, off[-1]
+    if x_local.size(0) != n_local:
+        raise ValueError(f"{what}: x_local has {x_local.size(0)} rows, part_offsets gives rank {rank} {n_local}")
+    for name, t in (("rowptr", rowptr), ("col", col)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous 1-D int64 tensor")
+    if rowptr.numel() != N + 1:
+        raise ValueError(f"{what}: the parts hold {N} rows, the graph {rowptr.numel() - 1} nodes (one row per node)")
+    if act_dtype not in _OUT_DTYPES:
+        raise ValueError(f"{what}: act_dtype must be torch.float32 or torch.bfloat16, got {act_dtype}")
+    rows_per_slab = int(rows_per_slab)
+    if rows_per_slab < 1:
+        raise ValueError(f"{what}: rows_per_slab must be positive, got {rows_per_slab}")
+    if nodes is not None:
+        if not isinstance(nodes, torch.Tensor) or nodes.dtype != torch.int64 or nodes.dim() != 1:
+            raise ValueError(f"{what}: nodes must be a 1-D int64 tensor")
+        if nodes.numel() and not (lo <= int(nodes.min()) and int(nodes.max()) < hi):     # (one read-back, up front)
+            raise ValueError(f"{what}: nodes outside rank {rank}'s range [{lo}, {hi}) (global ids; every rank scores its own)")
+    for name in ("share", "barrier", "close"):
+        if not callable(getattr(peers, name, None)):
+            raise TypeError(f"{what}: peers must provide share(tensor), barrier() and close()")
+    nat.require_device()
+    dev = x_local.device
+    if not (x_local.is_cuda and rowptr.device == dev and col.device == dev):
+        raise ValueError(f"{what}: x_local, rowptr and col must live on one CUDA device")
+    if nodes is not None:
+        nodes = nodes.to(dev).contiguous()
+    amp = act_dtype == torch.bfloat16
+    gin = isinstance(model, GIN)
+    n_layers, hidden = len(model.convs), model.hidden_channels
+    was_training = model.training
+    model.eval()
+    shared = []
+    try:
+        with torch.no_grad(), torch.autocast("cuda", enabled=False), torch.cuda.device(dev):
+            if hasattr(peers, "bind"):
+                peers.bind(rank)
+            # the buffers follow the resident tables' row-stride rule, so that every rank's have one stride whatever its
+            # row count (a one-row part has no stride of its own)
+            esize = torch.empty(0, dtype=act_dtype).element_size()
+            se = _row_stride_elems(hidden, esize)
+            bufs = [torch.empty((n_local, se), dtype=act_dtype, device=dev)[:, :hidden] for _ in range(min(2, n_layers - 1))]
+            shared = [(peers.share(x_local), x_local.dtype, x_local.size(1))]
+            shared += [(peers.share(b), act_dtype, hidden) for b in bufs]
+            rows_out = nodes.numel() if nodes is not None else n_local
+            ws = torch.empty(graph_agg_workspace_bytes(min(rows_per_slab, max(n_local, rows_out))), dtype=torch.uint8,
+                             device=dev)
+
+            def head(h):                                 # what follows the last conv layer, fp32 log-probabilities
+                if gin:
+                    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+                        h = model.lin2(torch.relu(model.lin1(h)))
+                return torch.log_softmax(h, dim=-1, dtype=torch.float32)
+
+            result = None
+            for i, conv in enumerate(model.convs):
+                last = i == n_layers - 1
+                epilogue, scale, fn = _gin_layer(conv, amp) if gin else _sage_layer(conv, last, act_dtype)
+                src, src_dtype, src_F = shared[0] if i == 0 else shared[1 + (i - 1) % len(bufs)]
+                ids = nodes if last else None
+                rows = ids.numel() if ids is not None else n_local
+                nxt = None if last else bufs[i % len(bufs)]
+                for s in range(0, rows, rows_per_slab):
+                    e = min(rows, s + rows_per_slab)
+                    tgt = dict(target_ids=ids[s:e]) if ids is not None else dict(row0=lo + s, num_targets=e - s)
+                    A = graph_aggregate_parts(src, off, rowptr, col, dtype=src_dtype, F=src_F, epilogue=epilogue,
+                                              self_scale=scale, out_dtype=act_dtype, workspace=ws, **tgt)
+                    for r, n, tile in _row_tiles(A):
+                        h = head(fn(tile)) if last else fn(tile)
+                        if nxt is None:
+                            nxt = torch.empty((rows, h.size(1)), dtype=torch.float32, device=dev)
+                        nxt[s + r:s + r + n] = h[:n]
+                if last:
+                    if nxt is None:                      # no rows at all
+                        width = (model.lin2 if gin else conv.lin_l).out_features
+                        nxt = torch.empty((0, width), dtype=torch.float32, device=dev)
+                    result = nxt
+                # layer i is complete HERE before any rank reads it, and every rank has finished reading layer i-1 before
+                # its buffer is written again (after the last layer: before anyone unmaps)
+                torch.cuda.current_stream(dev).synchronize()
+                peers.barrier()
+            return result
+    except BaseException:
+        if hasattr(peers, "abort"):
+            peers.abort()
+        raise
+    finally:
+        for sh, _dt, _f in shared:
+            sh.close()
         model.train(was_training)

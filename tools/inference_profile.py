@@ -5,6 +5,7 @@ with bf16 activations, timed per layer, and layer 1's slabs once more through th
     python tools/inference_profile.py [--workload S-papers] [--rows-per-slab 1048576] [--hidden 256] [--json out.json]
     python tools/inference_profile.py --model gat [--heads 4] [--repeats 3] ...
     python tools/inference_profile.py --model sageresinception [--nodes 1500000] [--torch-epilogue] [--repeats 3] ...
+    python tools/inference_profile.py --parts 8 --workload S-products [--repeats 5] ...
 
 ``--model gat``: GAT 3 x hidden at ``--heads`` through spp_graph_gat_forward, ``--repeats`` whole passes in one process
 (the first warms up code objects and the GEMM library's choices; every pass is reported).  Its bytes are the mean's plus
@@ -14,6 +15,12 @@ the logits: 4 * H per entry (a_src) and 8 * H per target (a_src of the self loop
 aggregation seconds as above, the epilogue seconds (events around every spp_resinc_epilogue call, summed; bytes: z, the
 residual row and the output row, bf16 each), the whole layer (layer 3's includes the head) and the whole call.
 ``--torch-epilogue`` runs the same pass with the layer tail restated as torch ops, the kernel's yardstick.
+
+``--parts P``: the cost of the owner lookup.  The workload's matrix cut into P equal row ranges, each copied into an
+allocation of its own on the one GPU, and every slab's MEAN aggregated twice: ``spp_graph_agg_forward`` on the whole
+matrix (the baseline) and ``spp_graph_agg_parts_forward`` on the parts, at the table's own width (fp16) and at ``--hidden``
+(bf16 rows); ``--repeats`` alternating passes after one warm-up pass of each, every pass reported, the ratio taken
+between the medians.  One slab's outputs are compared bit for bit first.
 
 Per layer: seconds of the aggregation alone (events around every slab's graph_aggregate, summed), edges/s, and the
 algorithmic bytes/s  E * F * s (rows) + 16 * T + 8 * E (indices) + T * W * s_out (output); plus the seconds of the whole
@@ -41,6 +48,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--nodes", type=int, default=1_500_000, help="sageresinception: nodes scored (0 = all)")
     ap.add_argument("--torch-epilogue", action="store_true", help="sageresinception: the layer tail as torch ops")
+    ap.add_argument("--parts", type=int, default=0, help="P > 0: time the aggregation over P row ranges against the whole matrix")
     a = ap.parse_args()
     from salient_plusplus_amd import _native as nat
     from salient_plusplus_amd import inference as inf
@@ -59,6 +67,8 @@ def main():
            "rows_per_slab": a.rows_per_slab, "build_s": round(time.time() - t0, 1), "layers": []}
     del deg, long_rows
     print(json.dumps({k: v for k, v in res.items() if k != "layers"}), flush=True)
+    if a.parts > 0:
+        return parts_leg(a, wl, res)
     if a.model == "gat":
         return gat_leg(a, wl, res)
     if a.model == "sageresinception":
@@ -191,6 +201,63 @@ def resinc_leg(a, wl, res):
             print(json.dumps(one), flush=True)
     finally:
         inf.graph_aggregate, inf.resinc_epilogue = inner_agg, inner_epi
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+SWEEPS = 10     # sweeps over all slabs inside one timed window of the --parts leg (seconds are per sweep)
+
+
+def parts_leg(a, wl, res):
+    from salient_plusplus_amd import inference as inf
+    rowptr, col = wl.rowptr, wl.col
+    N, E, P = wl.num_nodes, col.numel(), a.parts
+    off = [N * p // P for p in range(P + 1)]
+    res.update(parts=P, part_offsets=off, widths=[])
+    res.pop("layers")
+    ws = torch.empty(inf.graph_agg_workspace_bytes(min(a.rows_per_slab, N)), dtype=torch.uint8, device=rowptr.device)
+    torch.manual_seed(0)
+    for x in (wl.x, torch.randn((N, a.hidden), device=rowptr.device).to(torch.bfloat16)):
+        stride = x.stride(0)
+        parts = []
+        for p in range(P):                               # an allocation per part, rows as far apart as the matrix's
+            buf = torch.empty((off[p + 1] - off[p], stride), dtype=x.dtype, device=x.device)[:, :x.size(1)]
+            buf.copy_(x[off[p]:off[p + 1]])
+            parts.append(buf)
+        slabs = [(s, min(a.rows_per_slab, N - s)) for s in range(0, N, a.rows_per_slab)]
+
+        def whole(s, T):
+            return inf.graph_aggregate(x, rowptr, col, row0=s, num_targets=T, out_dtype=torch.bfloat16, workspace=ws)
+
+        def parted(s, T):
+            return inf.graph_aggregate_parts(parts, off, rowptr, col, row0=s, num_targets=T, out_dtype=torch.bfloat16,
+                                             workspace=ws)
+        s0, T0 = slabs[len(slabs) // 2]
+        assert torch.equal(whole(s0, T0).view(torch.int16), parted(s0, T0).view(torch.int16)), "the parts change bits"
+        times = {"whole": [], "parts": []}
+        b, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for rep in range(a.repeats + 1):                 # (pass 0 warms up both)
+            for name, fn in (("whole", whole), ("parts", parted)):
+                torch.cuda.synchronize()
+                b.record()
+                for _sweep in range(SWEEPS):
+                    for s, T in slabs:
+                        fn(s, T)
+                e.record()
+                e.synchronize()
+                if rep:
+                    times[name].append(round(b.elapsed_time(e) / 1e3 / SWEEPS, 6))
+        med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+        nbytes = E * x.size(1) * x.element_size() + 16 * N + 8 * E + N * x.size(1) * 2
+        one = {"F": x.size(1), "x_dtype": str(x.dtype), "x_stride_elems": stride, "whole_s": times["whole"],
+               "parts_s": times["parts"], "whole_median_s": med["whole"], "parts_median_s": med["parts"],
+               "ratio_parts_over_whole": round(med["parts"] / med["whole"], 4),
+               "whole_algorithmic_TBps": round(nbytes / med["whole"] / 1e12, 3)}
+        res["widths"].append(one)
+        print(json.dumps(one), flush=True)
+        del parts
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:

@@ -33,5 +33,5 @@ for (mangled, r), name in zip(rows.items(), demangle):
     name = re.sub(r"\(.*", "", name).replace("spp::", "")
     if filters and not any(f in name for f in filters):
         continue
-    print(f"{name[:70]:70s} {r.get('VGPRs', '?'):>5s} {r.get('AGPRs', '?'):>5s} {r.get('SGPRs', '?'):>5s} {r.get('Occupancy [waves/SIMD]', '?'):>4s} "
+    print(f"{name[:70]:70s} {r.get('VGPRs', '?'):>5s} {r.get('AGPRs', '?'):>5s} {r.get('TotalSGPRs', r.get('SGPRs', '?')):>5s} {r.get('Occupancy [waves/SIMD]', '?'):>4s} "
           f"{r.get('LDS Size [bytes/block]', '?'):>7s} {r.get('ScratchSize [bytes/lane]', '?'):>8s} {r.get('VGPRs Spill', '?'):>6s} {r.get('SGPRs Spill', '?'):>6s}")
