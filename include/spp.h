@@ -1092,6 +1092,65 @@ spp_status spp_graph_gat_forward(const spp_graph_gat_desc* desc, void* workspace
                                  void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * f3k  The same attention over a ROW-PARTITIONED h: the projected rows and their logits are not one matrix each but
+ *      num_parts row ranges, each in allocations of its own -- the ranks' parts of a layer's h and logits, the peers'
+ *      ones mapped into this process with spp_ipc_open (or plain device pointers of in-process ranks).
+ *
+ *        num_parts        P, 1 .. SPP_GRAPH_AGG_MAX_PARTS
+ *        part_offsets     P + 1 entries (host, in the descriptor), non-decreasing, part_offsets[0] == 0: part p holds the
+ *                         global rows [part_offsets[p], part_offsets[p + 1]); x_rows = part_offsets[P]
+ *        h_parts_dev[p]   the address, in this process, of part p's FIRST projected row; NULL exactly for an empty part
+ *        x_stride_elems   one row stride of h for all parts
+ *        a_parts_dev[p]   part p's logits as ONE fp32 matrix [rows_p, 2 * heads]: a_src in columns [0, heads), a_dst in
+ *                         [heads, 2 * heads) -- the product of the layer's input rows with [V_src; V_dst]^T as it comes
+ *                         out of one GEMM; NULL exactly for an empty part
+ *        a_stride_elems   one row stride of the logits for all parts; 0 = dense (2 * heads)
+ *      rowptr, col (the whole graph's CSR, global ids), the targets (a slab or a list of GLOBAL ids), heads, relu,
+ *      negative_slope, the element codes, F and the output: as spp_graph_gat_desc.  The entry reads x_rows + 1 entries
+ *      of rowptr.
+ *
+ *   The softmax contract of spp_graph_gat_forward holds word for word, and the result is bit-identical to that entry on
+ *   the concatenation of the parts (h, and a_src / a_dst as the two halves of the concatenated logits).  A col entry
+ *   outside [0, x_rows) is global node 0 in every respect (its row of h, its logit, and the comparison with t): the
+ *   first row of the first non-empty part.  A target id outside [0, x_rows) gives a row of zeros.  The target's own row
+ *   and both of its logits are read through the parts as well.  One owner lookup per entry serves the row of h and the
+ *   logit.  The vector form (four columns of one head per lane) needs C % 4 == 0, x_stride_elems % 4 == 0 and EVERY
+ *   non-empty part's h base aligned to 4 elements; otherwise the rows are read one column per lane, with the same
+ *   result.  An output misaligned for the vector form is refused, as there.  Workspace
+ *   (spp_graph_gat_workspace_bytes), stream and launches (a 16-byte memset and two): as spp_graph_gat_forward.  The
+ *   entry maps nothing and enables no peer access: every base must already be readable from the stream's device.
+ *   Refused with SPP_ERR_INVALID before anything is enqueued: num_parts out of range, part_offsets[0] != 0 or
+ *   decreasing offsets, a NULL h or logits base of a non-empty part, a negative a_stride_elems or a non-zero one below
+ *   2 * heads, and everything spp_graph_gat_forward refuses.  num_targets == 0 or F == 0: SPP_OK.
+ * ------------------------------------------------------------------------- */
+typedef struct spp_graph_gat_parts_desc {
+  int32_t x_elem;           /* h: SPP_ELEM_F32 / _F16 / _BF16 */
+  int32_t out_elem;         /* SPP_ELEM_F32 / SPP_ELEM_BF16 */
+  int32_t heads;
+  int32_t relu;             /* != 0: out = max(out, 0) */
+  int32_t num_parts;        /* P */
+  int32_t reserved;
+  const int64_t* rowptr_dev;
+  const int64_t* col_dev;
+  int64_t part_offsets[SPP_GRAPH_AGG_MAX_PARTS + 1];
+  const void* h_parts_dev[SPP_GRAPH_AGG_MAX_PARTS];
+  const float* a_parts_dev[SPP_GRAPH_AGG_MAX_PARTS];   /* [rows_p, 2 * heads] = [a_src | a_dst] */
+  int64_t x_stride_elems;
+  int64_t a_stride_elems;   /* 0 = dense (2 * heads) */
+  int64_t F;                /* heads * C */
+  int64_t target_row0;      /* slab: the first target (a global id); < 0 with a list */
+  const int64_t* target_ids_dev; /* list: the targets (global ids); NULL with a slab */
+  int64_t num_targets;
+  void* out_dev;            /* [num_targets, F] */
+  int64_t out_stride_elems; /* 0 = dense */
+  float negative_slope;
+  int32_t reserved2;
+} spp_graph_gat_parts_desc;
+
+spp_status spp_graph_gat_parts_forward(const spp_graph_gat_parts_desc* desc, void* workspace_dev,
+                                       int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * f3i  The layer tail of SAGEResInception in eval mode (exact, layer-wise inference): leaky_relu(BatchNorm(z)) plus
  *      the residual, one pass over the rows of a GEMM tile, written straight into a slab of the next activation matrix.
  *

@@ -108,6 +108,17 @@ class GraphGatDesc(C.Structure):
                 ("out_stride_elems", i64), ("negative_slope", C.c_float), ("reserved", i32)]
 
 
+class GraphGatPartsDesc(C.Structure):
+    """spp_graph_gat_parts_desc: GraphGatDesc with h and its logits as num_parts row ranges (part_offsets, one h base and
+    one [a_src | a_dst] base each)"""
+    _fields_ = [("x_elem", i32), ("out_elem", i32), ("heads", i32), ("relu", i32), ("num_parts", i32), ("reserved", i32),
+                ("rowptr_dev", p), ("col_dev", p), ("part_offsets", i64 * (SPP_GRAPH_AGG_MAX_PARTS + 1)),
+                ("h_parts_dev", p * SPP_GRAPH_AGG_MAX_PARTS), ("a_parts_dev", p * SPP_GRAPH_AGG_MAX_PARTS),
+                ("x_stride_elems", i64), ("a_stride_elems", i64), ("F", i64), ("target_row0", i64), ("target_ids_dev", p),
+                ("num_targets", i64), ("out_dev", p), ("out_stride_elems", i64), ("negative_slope", C.c_float),
+                ("reserved2", i32)]
+
+
 class ResincEpilogueDesc(C.Structure):
     """spp_resinc_epilogue_desc: out = leaky_relu(a * z + b) + r[row]; rows of r as a slab (r_row0 >= 0) or a list"""
     _fields_ = [("z_elem", i32), ("r_elem", i32), ("out_elem", i32), ("negative_slope", C.c_float), ("z_dev", p),
@@ -248,6 +259,7 @@ SIGNATURES = {
     "spp_graph_gat_chunk": (i64, []),
     "spp_graph_gat_workspace_bytes": (i64, [i64]),
     "spp_graph_gat_forward": (C.c_int, [C.POINTER(GraphGatDesc), p, i64, p]),
+    "spp_graph_gat_parts_forward": (C.c_int, [C.POINTER(GraphGatPartsDesc), p, i64, p]),
     "spp_resinc_epilogue": (C.c_int, [C.POINTER(ResincEpilogueDesc), p]),
 }
 SPP_COMM_ID_BYTES = 128

@@ -20,6 +20,11 @@
 // Every lane keeps the state of the head its columns belong to (head = column / C at run time); all lanes of a head
 // walk the same entries, so the states need no exchange.  Every offset is 64-bit.  No atomics touch the output.
 // (load4 / Piece / NodeRows are restated from graph_aggregate.hip, which stays as it is.)
+//
+// f3k: the same two kernels over a ROW-PARTITIONED h with its logits (spp_graph_gat_parts_forward).  The row source is a
+// template parameter: NodeRows reads one matrix h and the two logit matrices, PartRows finds the part that owns a
+// global row first and takes the row of h AND the row of [a_src | a_dst] from that one lookup.  Same arithmetic, same
+// order, same bits.
 #include "spp_internal.h"
 
 #include <hip/hip_bf16.h>
@@ -152,12 +157,82 @@ struct Args {
   int64_t* list;
 };
 
+// The row source of the kernels: Rows::Src is what the launch passes by value; Rows(src, a) answers, for a global row g
+// INSIDE [0, x_rows): owner(g), then the address of g's row of h and g's two logits through that owner.
+// one matrix h [x_rows, F] and the logits as two dense [x_rows, H] matrices (Args): nothing to find
+template <typename Tin>
+struct NodeRows {
+  using elem = Tin;
+  using Src = const Tin* __restrict__;
+  using Owner = int;
+  const Tin* __restrict__ x;
+  const Args& a;
+  __device__ __forceinline__ NodeRows(const Tin* __restrict__ src, const Args& args) : x(src), a(args) {}
+  __device__ __forceinline__ Owner owner(int64_t) const { return 0; }
+  __device__ __forceinline__ const Tin* h(Owner, int64_t g, int64_t c) const { return x + g * a.x_stride + c; }
+  __device__ __forceinline__ float src(Owner, int64_t g, int hd) const { return a.a_src[g * a.H + hd]; }
+  __device__ __forceinline__ float dst(Owner, int64_t g, int hd) const { return a.a_dst[g * a.H + hd]; }
+};
+
+// h and the logits as up to kMaxParts row ranges, each pair in allocations of its own (a rank's buffers, mapped into
+// this process).  Entry p holds the first global row of the p-th NON-EMPTY part, its h base moved back by that many
+// rows of h and its logits base ([rows, a_stride] fp32, a_src in columns [0, H), a_dst in [H, 2H)) moved back by that
+// many rows of logits, so that row g of every part is base + g * stride; the entries behind the last part start at
+// INT64_MAX (no row reaches them).  The launch passes the table by value.  Indexing that argument block with a per-lane
+// owner would make the compiler keep a private copy of it in scratch, and a scalar loop over it
+// was measured at 2.1-2.3 times NodeRows for the plain aggregation (f3j).  So thread 0 copies the three tables into LDS
+// (384 bytes) once per workgroup, with compile-time indices, and a lane finds the owner by a branch-free binary search
+// there: four dependent 8-byte LDS reads, then one for each base.  One search serves the row and its logit.
+constexpr int kMaxParts = SPP_GRAPH_AGG_MAX_PARTS;
+static_assert(kMaxParts == 16, "PartRows::owner searches exactly 16 entries");
+template <typename Tin>
+struct PartTable {
+  int64_t first[kMaxParts];
+  const Tin* h[kMaxParts];
+  const float* a[kMaxParts];
+  int64_t a_stride;
+};
+template <typename Tin>
+struct PartRows {
+  using elem = Tin;
+  using Src = PartTable<Tin>;
+  using Owner = int;
+  const int64_t* first;       // LDS
+  const Tin* const* hb;       // LDS
+  const float* const* ab;     // LDS
+  int64_t stride, a_stride;
+  int H;
+  // every thread of the workgroup constructs it, before any of them leaves the kernel (a barrier inside)
+  __device__ __forceinline__ PartRows(const PartTable<Tin>& src, const Args& a)
+      : stride(a.x_stride), a_stride(src.a_stride), H(a.H) {
+    __shared__ int64_t lds_first[kMaxParts];
+    __shared__ const Tin* lds_h[kMaxParts];
+    __shared__ const float* lds_a[kMaxParts];
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int p = 0; p < kMaxParts; ++p) lds_first[p] = src.first[p], lds_h[p] = src.h[p], lds_a[p] = src.a[p];
+    }
+    __syncthreads();
+    first = lds_first, hb = lds_h, ab = lds_a;
+  }
+  __device__ __forceinline__ Owner owner(int64_t g) const {
+    int p = g >= first[8] ? 8 : 0;  // the last entry with first <= g (first[0] = 0)
+    p += g >= first[p + 4] ? 4 : 0;
+    p += g >= first[p + 2] ? 2 : 0;
+    p += g >= first[p + 1] ? 1 : 0;
+    return p;
+  }
+  __device__ __forceinline__ const Tin* h(Owner p, int64_t g, int64_t c) const { return hb[p] + g * stride + c; }
+  __device__ __forceinline__ float src(Owner p, int64_t g, int hd) const { return ab[p][g * a_stride + hd]; }
+  __device__ __forceinline__ float dst(Owner p, int64_t g, int hd) const { return ab[p][g * a_stride + H + hd]; }
+};
+
 // the state of target t's entries col[b .. e) (every entry equal to t skipped), columns c.. of head hd, continued
 // from st in CSR order; four rows and their logits are in flight.  An entry outside [0, x_rows) is node 0: its row,
 // its logit, and the comparison with t.
-template <typename Tin, bool VEC4>
-__device__ __forceinline__ void walk(State<VEC4>& st, const Args& a, const Tin* __restrict__ x, int64_t t, float ad,
-                                     int hd, int64_t b, int64_t e, int64_t c) {
+template <typename Rows, bool VEC4>
+__device__ __forceinline__ void walk(State<VEC4>& st, const Args& a, const Rows& row, int64_t t, float ad, int hd,
+                                     int64_t b, int64_t e, int64_t c) {
   using P = Piece<VEC4>;
   auto node = [&](int64_t k) {
     const int64_t j = a.col[k];
@@ -166,10 +241,10 @@ __device__ __forceinline__ void walk(State<VEC4>& st, const Args& a, const Tin* 
   int64_t k = b;
   for (; k + 3 < e; k += 4) {
     const int64_t j0 = node(k), j1 = node(k + 1), j2 = node(k + 2), j3 = node(k + 3);
-    const float s0 = a.a_src[j0 * a.H + hd], s1 = a.a_src[j1 * a.H + hd], s2 = a.a_src[j2 * a.H + hd],
-                s3 = a.a_src[j3 * a.H + hd];
-    const auto v0 = P::load(x + j0 * a.x_stride + c), v1 = P::load(x + j1 * a.x_stride + c),
-               v2 = P::load(x + j2 * a.x_stride + c), v3 = P::load(x + j3 * a.x_stride + c);
+    const auto o0 = row.owner(j0), o1 = row.owner(j1), o2 = row.owner(j2), o3 = row.owner(j3);
+    const float s0 = row.src(o0, j0, hd), s1 = row.src(o1, j1, hd), s2 = row.src(o2, j2, hd), s3 = row.src(o3, j3, hd);
+    const auto v0 = P::load(row.h(o0, j0, c)), v1 = P::load(row.h(o1, j1, c)), v2 = P::load(row.h(o2, j2, c)),
+               v3 = P::load(row.h(o3, j3, c));
     if (j0 != t) st.take(lrelu(s0 + ad, a.slope), v0);
     if (j1 != t) st.take(lrelu(s1 + ad, a.slope), v1);
     if (j2 != t) st.take(lrelu(s2 + ad, a.slope), v2);
@@ -177,17 +252,18 @@ __device__ __forceinline__ void walk(State<VEC4>& st, const Args& a, const Tin* 
   }
   for (; k < e; ++k) {
     const int64_t j = node(k);
-    const float s = a.a_src[j * a.H + hd];
-    const auto v = P::load(x + j * a.x_stride + c);
+    const auto o = row.owner(j);
+    const float s = row.src(o, j, hd);
+    const auto v = P::load(row.h(o, j, c));
     if (j != t) st.take(lrelu(s + ad, a.slope), v);
   }
 }
 
-// the self loop's state of target t (inside the graph)
-template <typename Tin, bool VEC4>
-__device__ __forceinline__ State<VEC4> self_state(const Args& a, const Tin* __restrict__ x, int64_t t, float ad, int hd,
-                                                  int64_t c) {
-  return {lrelu(a.a_src[t * a.H + hd] + ad, a.slope), 1.f, Piece<VEC4>::load(x + t * a.x_stride + c)};
+// the self loop's state of target t (inside the graph, owned by ot)
+template <typename Rows, bool VEC4>
+__device__ __forceinline__ State<VEC4> self_state(const Args& a, const Rows& row, typename Rows::Owner ot, int64_t t,
+                                                  float ad, int hd, int64_t c) {
+  return {lrelu(row.src(ot, t, hd) + ad, a.slope), 1.f, Piece<VEC4>::load(row.h(ot, t, c))};
 }
 
 template <typename Tout, bool VEC4>
@@ -197,9 +273,10 @@ __device__ __forceinline__ void finish(const Args& a, const State<VEC4>& st, Tou
   P::store(o + c, a.relu ? P::relu(r) : r);
 }
 
-template <typename Tin, typename Tout, bool VEC4>
-__global__ __launch_bounds__(kNT) void k_graph_gat_rows(const Tin* __restrict__ x, Tout* __restrict__ out, Args a) {
+template <typename Rows, typename Tout, bool VEC4>
+__global__ __launch_bounds__(kNT) void k_graph_gat_rows(typename Rows::Src src, Tout* __restrict__ out, Args a) {
   using P = Piece<VEC4>;
+  const Rows row(src, a);  // (PartRows: the whole workgroup, before anyone returns)
   const int lpr = 1 << a.lpr_log2;
   const int lane = threadIdx.x & (lpr - 1);
   const int64_t i = ((int64_t)blockIdx.x * kNT + threadIdx.x) >> a.lpr_log2;
@@ -215,21 +292,23 @@ __global__ __launch_bounds__(kNT) void k_graph_gat_rows(const Tin* __restrict__ 
     if (lane == 0) a.list[atomicAdd(a.counter, 1ull)] = i;
     return;
   }
+  const auto ot = row.owner(t);
   for (int64_t c = (int64_t)lane * P::kWidth; c < a.F; c += (int64_t)lpr * P::kWidth) {
     const int hd = (int)c / a.C;
-    const float ad = a.a_dst[t * a.H + hd];
-    State<VEC4> st = self_state<Tin, VEC4>(a, x, t, ad, hd, c);
-    walk<Tin, VEC4>(st, a, x, t, ad, hd, b, e, c);
+    const float ad = row.dst(ot, t, hd);
+    State<VEC4> st = self_state<Rows, VEC4>(a, row, ot, t, ad, hd, c);
+    walk<Rows, VEC4>(st, a, row, t, ad, hd, b, e, c);
     finish<Tout, VEC4>(a, st, o, c);
   }
 }
 
-template <typename Tin, typename Tout, bool VEC4>
-__global__ __launch_bounds__(kNT) void k_graph_gat_long(const Tin* __restrict__ x, Tout* __restrict__ out, Args a) {
+template <typename Rows, typename Tout, bool VEC4>
+__global__ __launch_bounds__(kNT) void k_graph_gat_long(typename Rows::Src src, Tout* __restrict__ out, Args a) {
   using P = Piece<VEC4>;
   using piece = typename P::type;
   __shared__ piece part_acc[2][kNT];
   __shared__ float part_m[2][kNT], part_s[2][kNT];
+  const Rows row(src, a);
   const int lpr = 1 << a.lpr_log2, groups = kNT >> a.lpr_log2;
   const int lane = threadIdx.x & (lpr - 1), grp = threadIdx.x >> a.lpr_log2;
   const int64_t n = (int64_t)*a.counter;
@@ -240,11 +319,12 @@ __global__ __launch_bounds__(kNT) void k_graph_gat_long(const Tin* __restrict__ 
     const int64_t b = a.rowptr[t], e = a.rowptr[t + 1];
     const int64_t chunks = (e - b + kGatChunk - 1) / kGatChunk;
     Tout* o = out + i * a.out_stride;
+    const auto ot = row.owner(t);
     for (int64_t c0 = 0; c0 < a.F; c0 += (int64_t)lpr * P::kWidth) {
       const int64_t c = c0 + (int64_t)lane * P::kWidth;
       const bool active = c < a.F;
       const int hd = active ? (int)c / a.C : 0;
-      const float ad = a.a_dst[t * a.H + hd];
+      const float ad = row.dst(ot, t, hd);
       State<VEC4> total = State<VEC4>::empty();  // (set from chunk 0's state in the first round)
       for (int64_t j0 = 0; j0 < chunks; j0 += groups, ++round) {
         // group g runs chunk j0 + g; round k parks its states in part_*[k & 1], which are written again in round
@@ -253,8 +333,8 @@ __global__ __launch_bounds__(kNT) void k_graph_gat_long(const Tin* __restrict__ 
         State<VEC4> st = State<VEC4>::empty();
         if (active && j < chunks) {
           const int64_t cb = b + j * kGatChunk;
-          if (j == 0) st = self_state<Tin, VEC4>(a, x, t, ad, hd, c);
-          walk<Tin, VEC4>(st, a, x, t, ad, hd, cb, std::min<int64_t>(e, cb + kGatChunk), c);
+          if (j == 0) st = self_state<Rows, VEC4>(a, row, ot, t, ad, hd, c);
+          walk<Rows, VEC4>(st, a, row, t, ad, hd, cb, std::min<int64_t>(e, cb + kGatChunk), c);
         }
         const int buf = round & 1;
         part_acc[buf][threadIdx.x] = st.acc;
@@ -297,50 +377,86 @@ extern "C" int64_t spp_graph_gat_workspace_bytes(int64_t num_targets) {
   return kWorkspaceHeader + 8 * std::max<int64_t>(num_targets, 0);
 }
 
-extern "C" spp_status spp_graph_gat_forward(const spp_graph_gat_desc* desc, void* workspace_dev, int64_t workspace_bytes,
-                                            void* stream) {
-  const char* who = "spp_graph_gat_forward";
-  SPP_REQUIRE(desc, "%s: NULL descriptor", who);
-  const spp_graph_gat_desc& d = *desc;
+namespace {
+
+// what both entries share: spp_graph_gat_desc without its sources
+struct Call {
+  int32_t x_elem, out_elem, heads, relu;
+  const int64_t* rowptr;
+  const int64_t* col;
+  int64_t x_stride, x_rows, F, row0;
+  const int64_t* ids;
+  int64_t T;
+  void* out;
+  int64_t out_stride;
+  float slope;
+};
+
+// the sources of spp_graph_gat_forward: one matrix h and the two logit matrices
+struct Whole {
+  const void* x;
+  const float* a_src;
+  const float* a_dst;
+};
+
+// the sources of spp_graph_gat_parts_forward: the non-empty parts in order
+struct Parts {
+  int n;
+  int64_t first[kMaxParts];
+  const void* h[kMaxParts];
+  const float* a[kMaxParts];
+  int64_t a_stride;  // as given: 0 = dense
+};
+
+// exactly one of whole / parts is given
+spp_status forward(const char* who, const Call& d, const Whole* whole, const Parts* parts, void* workspace_dev,
+                   int64_t workspace_bytes, void* stream) {
   SPP_REQUIRE(d.x_elem != SPP_ELEM_FP8_E4M3 && d.out_elem != SPP_ELEM_FP8_E4M3,
               "%s: fp8 rows are not read or written here (x_elem %d, out_elem %d)", who, (int)d.x_elem, (int)d.out_elem);
   SPP_REQUIRE((d.x_elem == SPP_ELEM_F32 || d.x_elem == SPP_ELEM_F16 || d.x_elem == SPP_ELEM_BF16) &&
                   (d.out_elem == SPP_ELEM_F32 || d.out_elem == SPP_ELEM_BF16),
               "%s: unknown or unsupported element code (x_elem %d, out_elem %d)", who, (int)d.x_elem, (int)d.out_elem);
-  const bool by_ids = d.target_ids_dev != nullptr, by_slab = d.target_row0 >= 0;
+  const bool by_ids = d.ids != nullptr, by_slab = d.row0 >= 0;
   SPP_REQUIRE(by_ids != by_slab, "%s: give the targets as a slab (target_row0 >= 0) or as a list (target_ids_dev), %s", who,
               by_ids ? "not both" : "one of them");
-  const int64_t T = d.num_targets, F = d.F;
+  const int64_t T = d.T, F = d.F;
   SPP_REQUIRE(T >= 0 && F >= 0 && d.x_rows >= 0, "%s: negative size (num_targets, F or x_rows)", who);
-  SPP_REQUIRE(by_ids || (d.target_row0 <= d.x_rows && T <= d.x_rows - d.target_row0),
+  SPP_REQUIRE(by_ids || (d.row0 <= d.x_rows && T <= d.x_rows - d.row0),
               "%s: the slab [%lld, %lld) (target_row0, num_targets) leaves the graph's %lld rows", who,
-              (long long)d.target_row0, (long long)(d.target_row0 + T), (long long)d.x_rows);
+              (long long)d.row0, (long long)(d.row0 + T), (long long)d.x_rows);
   SPP_REQUIRE(d.heads >= 1 && F % d.heads == 0 && F < (1ll << 31), "%s: heads %d must be positive and divide F = %lld (< 2^31)",
               who, (int)d.heads, (long long)F);
-  const int64_t out_stride = d.out_stride_elems > 0 ? d.out_stride_elems : F;
+  SPP_REQUIRE(!parts || parts->a_stride == 0 || parts->a_stride >= 2 * (int64_t)d.heads,
+              "%s: a_stride_elems %lld smaller than the logits' row of 2 * heads = %d", who,
+              parts ? (long long)parts->a_stride : 0ll, 2 * (int)d.heads);
+  const int64_t out_stride = d.out_stride > 0 ? d.out_stride : F;
   SPP_REQUIRE(out_stride >= F, "%s: out_stride_elems smaller than the output row", who);
-  SPP_REQUIRE(d.x_stride_elems >= F, "%s: x_stride_elems smaller than the row", who);
-  // the vector form: four columns of one head per lane.  Rows of h that do not allow it are read one column per lane
-  // instead; an output that does not is refused (the caller allocates it)
+  SPP_REQUIRE(d.x_stride >= F, "%s: x_stride_elems smaller than the row", who);
+  // the vector form: four columns of one head per lane.  Rows of h that do not allow it (with parts: the rows of any of
+  // them) are read one column per lane instead; an output that does not is refused (the caller allocates it)
   const int64_t Cw = F / d.heads;
-  const bool vec = F > 0 && Cw % 4 == 0 && d.x_stride_elems % 4 == 0 && aligned_to(d.x_dev, 4 * elem_bytes(d.x_elem));
-  SPP_REQUIRE(!vec || (out_stride % 4 == 0 && aligned_to(d.out_dev, 4 * elem_bytes(d.out_elem))),
+  bool vec = F > 0 && Cw % 4 == 0 && d.x_stride % 4 == 0;
+  if (parts)
+    for (int p = 0; p < parts->n; ++p) vec = vec && aligned_to(parts->h[p], 4 * elem_bytes(d.x_elem));
+  else
+    vec = vec && aligned_to(whole->x, 4 * elem_bytes(d.x_elem));
+  SPP_REQUIRE(!vec || (out_stride % 4 == 0 && aligned_to(d.out, 4 * elem_bytes(d.out_elem))),
               "%s: C %% 4 == 0 needs out_dev aligned to 4 elements (base and stride)", who);
   SPP_REQUIRE(workspace_dev && aligned_to(workspace_dev, 16) && workspace_bytes >= spp_graph_gat_workspace_bytes(T),
               "%s: needs a 16-byte aligned workspace of spp_graph_gat_workspace_bytes(num_targets) = %lld bytes", who,
               (long long)spp_graph_gat_workspace_bytes(T));
   if (T == 0 || F == 0) return SPP_OK;
-  SPP_REQUIRE(d.rowptr_dev && d.col_dev && d.x_dev && d.a_src_dev && d.a_dst_dev && d.out_dev && d.x_rows > 0,
+  SPP_REQUIRE(d.rowptr && d.col && (parts || (whole->x && whole->a_src && whole->a_dst)) && d.out && d.x_rows > 0,
               "%s: NULL buffer or empty graph", who);
   const int lpr_log2 = lanes_log2(vec ? F / 4 : F);
   const int64_t grid = ceil_div(T << lpr_log2, kNT);
   SPP_REQUIRE(grid < (1ll << 31), "%s: too many targets for one launch (num_targets %lld)", who, (long long)T);
   hipStream_t st = as_stream(stream);
   Args a{};
-  a.rowptr = d.rowptr_dev, a.col = d.col_dev, a.ids = d.target_ids_dev, a.row0 = by_ids ? 0 : d.target_row0, a.T = T;
-  a.x_stride = d.x_stride_elems, a.x_rows = d.x_rows, a.F = F, a.out_stride = out_stride;
-  a.a_src = d.a_src_dev, a.a_dst = d.a_dst_dev, a.H = d.heads, a.C = (int32_t)Cw;
-  a.slope = d.negative_slope, a.relu = d.relu != 0, a.lpr_log2 = lpr_log2;
+  a.rowptr = d.rowptr, a.col = d.col, a.ids = d.ids, a.row0 = by_ids ? 0 : d.row0, a.T = T;
+  a.x_stride = d.x_stride, a.x_rows = d.x_rows, a.F = F, a.out_stride = out_stride;
+  a.a_src = parts ? nullptr : whole->a_src, a.a_dst = parts ? nullptr : whole->a_dst, a.H = d.heads, a.C = (int32_t)Cw;
+  a.slope = d.slope, a.relu = d.relu != 0, a.lpr_log2 = lpr_log2;
   a.counter = static_cast<unsigned long long*>(workspace_dev);
   a.list = reinterpret_cast<int64_t*>(static_cast<char*>(workspace_dev) + kWorkspaceHeader);
   SPP_HIP_TRY(hipMemsetAsync(workspace_dev, 0, kWorkspaceHeader, st));
@@ -349,10 +465,27 @@ extern "C" spp_status spp_graph_gat_forward(const spp_graph_gat_desc* desc, void
     using Tin = typename decltype(tin)::type;
     using Tout = typename decltype(tout)::type;
     constexpr bool V = decltype(v)::value;
-    const Tin* x = static_cast<const Tin*>(d.x_dev);
-    Tout* out = static_cast<Tout*>(d.out_dev);
-    hipLaunchKernelGGL((k_graph_gat_rows<Tin, Tout, V>), dim3((unsigned)grid), dim3(kNT), 0, st, x, out, a);
-    hipLaunchKernelGGL((k_graph_gat_long<Tin, Tout, V>), dim3(long_grid), dim3(kNT), 0, st, x, out, a);
+    Tout* out = static_cast<Tout*>(d.out);
+    if (parts) {
+      // each base moved back by its part's first row (never dereferenced below that row; integer arithmetic, the
+      // address may lie before the allocation)
+      PartTable<Tin> t{};
+      t.a_stride = parts->a_stride > 0 ? parts->a_stride : 2 * (int64_t)d.heads;
+      for (int p = 0; p < kMaxParts; ++p) t.first[p] = INT64_MAX;  // (behind the last part: never the owner)
+      for (int p = 0; p < parts->n; ++p) {
+        t.first[p] = parts->first[p];
+        t.h[p] = reinterpret_cast<const Tin*>(reinterpret_cast<uintptr_t>(parts->h[p]) -
+                                              (uintptr_t)parts->first[p] * (uintptr_t)d.x_stride * sizeof(Tin));
+        t.a[p] = reinterpret_cast<const float*>(reinterpret_cast<uintptr_t>(parts->a[p]) -
+                                                (uintptr_t)parts->first[p] * (uintptr_t)t.a_stride * sizeof(float));
+      }
+      hipLaunchKernelGGL((k_graph_gat_rows<PartRows<Tin>, Tout, V>), dim3((unsigned)grid), dim3(kNT), 0, st, t, out, a);
+      hipLaunchKernelGGL((k_graph_gat_long<PartRows<Tin>, Tout, V>), dim3(long_grid), dim3(kNT), 0, st, t, out, a);
+    } else {
+      const Tin* x = static_cast<const Tin*>(whole->x);
+      hipLaunchKernelGGL((k_graph_gat_rows<NodeRows<Tin>, Tout, V>), dim3((unsigned)grid), dim3(kNT), 0, st, x, out, a);
+      hipLaunchKernelGGL((k_graph_gat_long<NodeRows<Tin>, Tout, V>), dim3(long_grid), dim3(kNT), 0, st, x, out, a);
+    }
   };
   auto by_out = [&](auto tin, auto v) {
     d.out_elem == SPP_ELEM_BF16 ? launch(tin, Type<bf16>{}, v) : launch(tin, Type<float>{}, v);
@@ -364,4 +497,46 @@ extern "C" spp_status spp_graph_gat_forward(const spp_graph_gat_desc* desc, void
   vec ? by_in(std::true_type{}) : by_in(std::false_type{});
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
+}
+
+}  // namespace
+
+extern "C" spp_status spp_graph_gat_forward(const spp_graph_gat_desc* desc, void* workspace_dev, int64_t workspace_bytes,
+                                            void* stream) {
+  const char* who = "spp_graph_gat_forward";
+  SPP_REQUIRE(desc, "%s: NULL descriptor", who);
+  const spp_graph_gat_desc& d = *desc;
+  const Call c{d.x_elem, d.out_elem,    d.heads,          d.relu,        d.rowptr_dev, d.col_dev,          d.x_stride_elems,
+               d.x_rows, d.F,           d.target_row0,    d.target_ids_dev, d.num_targets, d.out_dev, d.out_stride_elems,
+               d.negative_slope};
+  const Whole w{d.x_dev, d.a_src_dev, d.a_dst_dev};
+  return forward(who, c, &w, nullptr, workspace_dev, workspace_bytes, stream);
+}
+
+extern "C" spp_status spp_graph_gat_parts_forward(const spp_graph_gat_parts_desc* desc, void* workspace_dev,
+                                                  int64_t workspace_bytes, void* stream) {
+  const char* who = "spp_graph_gat_parts_forward";
+  SPP_REQUIRE(desc, "%s: NULL descriptor", who);
+  const spp_graph_gat_parts_desc& d = *desc;
+  SPP_REQUIRE(d.num_parts >= 1 && d.num_parts <= SPP_GRAPH_AGG_MAX_PARTS, "%s: num_parts %d outside 1..%d", who,
+              (int)d.num_parts, (int)SPP_GRAPH_AGG_MAX_PARTS);
+  SPP_REQUIRE(d.part_offsets[0] == 0, "%s: part_offsets[0] must be 0, got %lld", who, (long long)d.part_offsets[0]);
+  SPP_REQUIRE(d.a_stride_elems >= 0, "%s: a_stride_elems %lld is negative", who, (long long)d.a_stride_elems);
+  Parts parts{};
+  parts.a_stride = d.a_stride_elems;
+  for (int p = 0; p < d.num_parts; ++p) {
+    SPP_REQUIRE(d.part_offsets[p + 1] >= d.part_offsets[p], "%s: part_offsets decrease at part %d (%lld after %lld)", who, p,
+                (long long)d.part_offsets[p + 1], (long long)d.part_offsets[p]);
+    if (d.part_offsets[p + 1] == d.part_offsets[p]) continue;  // an empty part owns no row: its bases may be NULL
+    SPP_REQUIRE(d.h_parts_dev[p], "%s: part %d holds the rows [%lld, %lld) and its h base (h_parts_dev) is NULL", who, p,
+                (long long)d.part_offsets[p], (long long)d.part_offsets[p + 1]);
+    SPP_REQUIRE(d.a_parts_dev[p], "%s: part %d holds the rows [%lld, %lld) and its logits base (a_parts_dev) is NULL", who,
+                p, (long long)d.part_offsets[p], (long long)d.part_offsets[p + 1]);
+    parts.first[parts.n] = d.part_offsets[p], parts.h[parts.n] = d.h_parts_dev[p], parts.a[parts.n] = d.a_parts_dev[p];
+    ++parts.n;
+  }
+  const Call c{d.x_elem, d.out_elem, d.heads, d.relu, d.rowptr_dev, d.col_dev, d.x_stride_elems,
+               d.part_offsets[d.num_parts], d.F, d.target_row0, d.target_ids_dev, d.num_targets, d.out_dev,
+               d.out_stride_elems, d.negative_slope};
+  return forward(who, c, nullptr, &parts, workspace_dev, workspace_bytes, stream);
 }

@@ -10,8 +10,10 @@ through the library GEMMs torch dispatches to.
 ``SAGEResInception``.  Forward only, one GPU, fp16 / fp32 / bf16 inputs.
 
 Over a row-PARTITIONED feature table (one range of nodes per rank, the peers' partitions mapped into the process):
-``graph_aggregate_parts`` (``spp_graph_agg_parts_forward``) and ``partitioned_layerwise_inference`` for SAGE and GIN, with
-``LocalPeers`` (ranks as threads of one process) or ``IpcPeers`` (one process per rank on one node) between the ranks."""
+``graph_aggregate_parts`` (``spp_graph_agg_parts_forward``), ``graph_gat_aggregate_parts``
+(``spp_graph_gat_parts_forward``) and ``partitioned_inference`` for all four models (``partitioned_layerwise_inference``
+is its SAGE / GIN half), with ``LocalPeers`` (ranks as threads of one process) or ``IpcPeers`` (one process per rank on
+one node) between the ranks."""
 import ctypes as C
 import threading
 
@@ -134,7 +136,7 @@ def _check_offsets(part_offsets, what):
     return off
 
 
-def _parts_source(parts, off, dtype, F, what):
+def _parts_source(parts, off, dtype, F, what, name="part"):
     """(base addresses [P], row stride in elements, dtype, F, device or None) of the two forms of ``parts``"""
     P = len(off) - 1
     if isinstance(parts, P2PPeers):
@@ -147,7 +149,7 @@ def _parts_source(parts, off, dtype, F, what):
             raise ValueError(f"{what}: the peers' row stride ({parts.stride} bytes) is no multiple of the element size")
         for p in range(P):
             if off[p + 1] > off[p] and not parts.ptrs[p]:
-                raise ValueError(f"{what}: part {p} holds the rows [{off[p]}, {off[p + 1]}) and has no address")
+                raise ValueError(f"{what}: {name} {p} holds the rows [{off[p]}, {off[p + 1]}) and has no address")
         return list(parts.ptrs), parts.stride // esize, dtype, F, None
     if dtype is not None or F is not None:
         raise ValueError(f"{what}: dtype= and F= describe a P2PPeers source; tensors carry their own")
@@ -159,11 +161,11 @@ def _parts_source(parts, off, dtype, F, what):
         rows = off[p + 1] - off[p]
         if t is None:
             if rows:
-                raise ValueError(f"{what}: part {p} holds the rows [{off[p]}, {off[p + 1]}) and is None")
+                raise ValueError(f"{what}: {name} {p} holds the rows [{off[p]}, {off[p + 1]}) and is None")
             continue
-        _check_matrix(t, what, f"part {p}")
+        _check_matrix(t, what, f"{name} {p}")
         if t.size(0) != rows:
-            raise ValueError(f"{what}: part {p} has {t.size(0)} rows, part_offsets gives it {rows}")
+            raise ValueError(f"{what}: {name} {p} has {t.size(0)} rows, part_offsets gives it {rows}")
         if rows:
             live.append((p, t))
     if not live:
@@ -343,6 +345,98 @@ def graph_gat_aggregate(h, a_src, a_dst, rowptr, col, *, heads, negative_slope=0
     out = torch.empty((T, Fdim), dtype=out_dtype, device=h.device)
     return _gat_forward(h, a_src, a_dst, rowptr, col, heads, negative_slope, relu, row0, None if slab else target_ids,
                         T, out, workspace)
+
+
+def _check_targets(what, N, row0, num_targets, target_ids):
+    """(slab?, row0 or -1, T) of the two target forms: a slab inside the graph's N nodes, or a contiguous int64 list"""
+    slab = row0 is not None or num_targets is not None
+    if slab == (target_ids is not None):
+        raise ValueError(f"{what}: give the targets either as a slab (row0 and num_targets) or as target_ids"
+                         + (", not both" if slab else ""))
+    if slab:
+        if row0 is None or num_targets is None:
+            raise ValueError(f"{what}: a slab needs both row0 and num_targets")
+        row0, T = int(row0), int(num_targets)
+        if row0 < 0 or T < 0 or row0 + T > N:
+            raise ValueError(f"{what}: the slab [{row0}, {row0 + T}) leaves the graph's {N} nodes")
+        return True, row0, T
+    if not isinstance(target_ids, torch.Tensor) or target_ids.dtype != torch.int64 or target_ids.dim() != 1 \
+            or not target_ids.is_contiguous():
+        raise ValueError(f"{what}: target_ids must be a contiguous 1-D int64 tensor")
+    return False, -1, target_ids.numel()
+
+
+def graph_gat_aggregate_parts(h_parts, a_parts, part_offsets, rowptr, col, *, heads, negative_slope=0.2, relu=False,
+                              row0=None, num_targets=None, target_ids=None, out_dtype=torch.float32, out=None,
+                              workspace=None, dtype=None, F=None):
+    """``graph_gat_aggregate`` over a row-partitioned h with its logits (``spp_graph_gat_parts_forward``, include/spp.h):
+    part p holds the global rows [part_offsets[p], part_offsets[p + 1]) of h and of the logits, in allocations of its own.
+    The result is the bits of ``graph_gat_aggregate(torch.cat(h_parts), a[:, :heads], a[:, heads:], ...)`` with
+    ``a = torch.cat(a_parts)``.
+
+    ``h_parts``: a list of P CUDA tensors on one device (an empty part may be None or have 0 rows) that share dtype,
+    width F = heads * C and row stride -- or a ``P2PPeers`` with ``dtype=`` and ``F=`` (the width read, which may be less
+    than the published buffer's).  ``a_parts``: each part's logits as ONE fp32 matrix [rows_p, 2 * heads] = [a_src | a_dst]
+    (unit column stride, one row stride for all parts, which may exceed 2 * heads) -- or a ``P2PPeers``.  ``rowptr`` /
+    ``col``: the WHOLE graph's CSR with global ids; ``heads``, ``negative_slope``, ``relu``, the targets (global ids),
+    ``out_dtype`` and ``workspace`` as ``graph_gat_aggregate``.  ``out``: an fp32 / bf16 [T, F] matrix to write into (rows
+    of a larger one allowed).  Nothing here maps memory or enables peer access, and nothing waits for the device."""
+    what = "graph_gat_aggregate_parts"
+    off = _check_offsets(part_offsets, what)
+    ptrs, stride, x_dtype, Fdim, dev = _parts_source(h_parts, off, dtype, F, what)
+    if not isinstance(heads, int) or heads < 1 or Fdim % heads != 0:
+        raise ValueError(f"{what}: heads must be a positive int that divides F = {Fdim}, got {heads!r}")
+    peer_logits = isinstance(a_parts, P2PPeers)
+    a_ptrs, a_stride, a_dtype, a_width, a_dev = _parts_source(
+        a_parts, off, torch.float32 if peer_logits else None, 2 * heads if peer_logits else None, what, "logits part")
+    if a_dtype != torch.float32 or a_width != 2 * heads:
+        raise ValueError(f"{what}: every logits part must be an fp32 matrix [rows, 2 * heads = {2 * heads}] "
+                         f"([a_src | a_dst]), got {a_dtype} of width {a_width}")
+    if a_stride < 2 * heads:
+        raise ValueError(f"{what}: the logits' row stride ({a_stride} elements) is smaller than 2 * heads = {2 * heads}")
+    if dev is not None and a_dev is not None and dev != a_dev:
+        raise ValueError(f"{what}: h_parts ({dev}) and a_parts ({a_dev}) live on different devices")
+    dev = a_dev if dev is None else dev
+    N = off[-1]
+    for name, t in (("rowptr", rowptr), ("col", col)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous 1-D int64 tensor")
+    if rowptr.numel() != N + 1:
+        raise ValueError(f"{what}: the parts hold {N} rows, the graph {rowptr.numel() - 1} nodes (one row per node)")
+    if out_dtype not in _OUT_DTYPES:
+        raise ValueError(f"{what}: out_dtype must be torch.float32 or torch.bfloat16, got {out_dtype}")
+    slab, row0, T = _check_targets(what, N, row0, num_targets, target_ids)
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != out_dtype or tuple(out.shape) != (T, Fdim) \
+                or (Fdim > 1 and out.stride(1) != 1) or out.requires_grad:
+            raise ValueError(f"{what}: out must be a {out_dtype} matrix of shape [{T}, {Fdim}] with unit column stride "
+                             "that does not require grad")
+    nat.require_device()
+    dev = rowptr.device if dev is None else dev
+    tensors = [rowptr, col] + [t for t in (None if slab else target_ids, workspace, out) if t is not None]
+    if dev.type != "cuda" or not all(t.is_cuda and t.device == dev for t in tensors):
+        raise ValueError(f"{what}: the parts, rowptr, col, target_ids, workspace and out must live on one CUDA device")
+    L = nat.load()
+    nbytes = int(L.spp_graph_gat_workspace_bytes(T))
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < nbytes:
+        raise ValueError(f"{what}: workspace must be a contiguous uint8 tensor of at least {nbytes} bytes")
+    if out is None:
+        out = torch.empty((T, Fdim), dtype=out_dtype, device=dev)
+    d = nat.GraphGatPartsDesc(x_elem=_ELEM[x_dtype], out_elem=_ELEM[out_dtype], heads=heads, relu=int(bool(relu)),
+                              num_parts=len(off) - 1, rowptr_dev=_p(rowptr), col_dev=_p(col), x_stride_elems=stride,
+                              a_stride_elems=a_stride, F=Fdim, target_row0=row0,
+                              target_ids_dev=_p(target_ids) if not slab else None, num_targets=T, out_dev=_p(out),
+                              out_stride_elems=out.stride(0) if T > 1 else 0, negative_slope=float(negative_slope))
+    for p, v in enumerate(off):
+        d.part_offsets[p] = v
+    for p, (hv, av) in enumerate(zip(ptrs, a_ptrs)):
+        d.h_parts_dev[p], d.a_parts_dev[p] = hv or None, av or None
+    with torch.cuda.device(dev):
+        nat.check(L.spp_graph_gat_parts_forward(C.byref(d), C.c_void_p(workspace.data_ptr()), workspace.numel(),
+                                                _stream()))
+    return out
 
 
 def resinc_epilogue(z, scale, shift, *, negative_slope, residual=None, row0=None, row_ids=None, out=None,
@@ -599,6 +693,19 @@ def _resinc_inference(model, x, rowptr, col, nodes, rows_per_slab, act_dtype):
     return out
 
 
+def _check_model_shape(model, what):
+    """what the GAT and SAGEResInception drivers need of the model's layers (SAGE and GIN: nothing)"""
+    from .models import GAT, SAGEResInception
+    if isinstance(model, SAGEResInception):
+        _resinc_head(model)
+    if isinstance(model, GAT):                                # the layers as models.GAT builds them
+        for i, c in enumerate(model.convs):
+            mean_heads = i == len(model.convs) - 1 and c.heads > 1
+            if c.bias is not None or c.concat == mean_heads:
+                raise NotImplementedError(f"{what}: GAT layers need bias=False, and concat=False on the last layer of a "
+                                          "multi-head model only")
+
+
 def layerwise_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 << 20, act_dtype=torch.float32):
     """Exact log-probabilities of every node, [N, classes] fp32 -- or of ``nodes`` (int64, any order, duplicates
     allowed), [len(nodes), classes] -- for a ``SAGE``, ``GIN``, ``GAT`` or ``SAGEResInception`` model over the whole
@@ -625,14 +732,7 @@ def layerwise_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 <<
     if not isinstance(model, (SAGE, GIN, GAT, SAGEResInception)):
         raise NotImplementedError(f"{what}: implemented for SAGE and GIN (and GAT, SAGEResInception), not "
                                   f"{type(model).__name__}")
-    if isinstance(model, SAGEResInception):
-        _resinc_head(model)
-    if isinstance(model, GAT):                                # the layers as models.GAT builds them
-        for i, c in enumerate(model.convs):
-            mean_heads = i == len(model.convs) - 1 and c.heads > 1
-            if c.bias is not None or c.concat == mean_heads:
-                raise NotImplementedError(f"{what}: GAT layers need bias=False, and concat=False on the last layer of a "
-                                          "multi-head model only")
+    _check_model_shape(model, what)
     _check_matrix(x, what)
     _check_graph(x, rowptr, col, what)
     if act_dtype not in _OUT_DTYPES:
@@ -768,34 +868,9 @@ class IpcPeers:
         pass
 
 
-def partitioned_layerwise_inference(model, x_local, rowptr, col, *, part_offsets, rank, peers, nodes=None,
-                                    rows_per_slab=1 << 20, act_dtype=torch.float32):
-    """``layerwise_inference`` for SAGE and GIN when the feature table is row-partitioned over the ranks: every rank calls
-    this with its own partition ``x_local`` (the global rows [part_offsets[rank], part_offsets[rank + 1])), the WHOLE
-    graph's CSR (global ids) and the same ``model``, and gets the fp32 log-probabilities of ITS node range,
-    [n_local, classes] -- or of ``nodes`` (global ids, all inside the rank's range).  The bits are those of
-    ``layerwise_inference`` over the concatenated table, rows [part_offsets[rank], part_offsets[rank + 1]).
-
-    Per rank: the ping-pong activation buffers [n_local, hidden] of ``act_dtype`` are allocated up front (one for a
-    two-layer model) and published with ``x_local`` once through ``peers``; each layer aggregates the rank's own slabs with
-    ``graph_aggregate_parts`` over ALL ranks' previous-layer parts, runs the layer's parameters over the same fixed GEMM
-    tiles as ``layerwise_inference`` and writes its rows of the next layer into its own buffer; then the rank synchronises
-    its stream and waits in ``peers.barrier()`` before anyone reads the layer or reuses a buffer.  After the last barrier
-    the mappings are closed.
-
-    ``peers``: ``share(tensor) -> P2PPeers`` (collective, same order on every rank), ``barrier()``, ``close()``; optional
-    ``bind(rank)`` and ``abort()``.  ``LocalPeers`` and ``IpcPeers`` are the two implementations.  GAT and
-    SAGEResInception over parts are not built.
-
-    Memory, as arithmetic (S-mag, N = 121.8 M, F = 768 fp16, hidden 256, bf16): per rank of P, 187 / P GB of table and
-    2 * 62 / P GB of activations next to its copy of the 22 GB graph."""
-    from .models import GAT, GIN, SAGE, SAGEResInception
-    what = "partitioned_layerwise_inference"
-    if isinstance(model, (GAT, SAGEResInception)):
-        raise NotImplementedError(f"{what}: {type(model).__name__} over a partitioned table is not built (its layers "
-                                  "need the long-row softmax / the fused layer tail over parts); SAGE and GIN are")
-    if not isinstance(model, (SAGE, GIN)):
-        raise NotImplementedError(f"{what}: implemented for SAGE and GIN, not {type(model).__name__}")
+def _check_partitioned(what, x_local, rowptr, col, part_offsets, rank, peers, nodes, rows_per_slab, act_dtype):
+    """the arguments every partitioned driver shares, checked before ``peers`` is touched; the device is required last.
+    Returns (offsets as a list, rank, nodes on the device or None, rows_per_slab)"""
     _check_matrix(x_local, what, "x_local")
     off = _check_offsets(part_offsets, what)
     P = len(off) - 1
@@ -830,6 +905,41 @@ def partitioned_layerwise_inference(model, x_local, rowptr, col, *, part_offsets
         raise ValueError(f"{what}: x_local, rowptr and col must live on one CUDA device")
     if nodes is not None:
         nodes = nodes.to(dev).contiguous()
+    return off, rank, nodes, rows_per_slab
+
+
+def partitioned_layerwise_inference(model, x_local, rowptr, col, *, part_offsets, rank, peers, nodes=None,
+                                    rows_per_slab=1 << 20, act_dtype=torch.float32):
+    """``layerwise_inference`` for SAGE and GIN when the feature table is row-partitioned over the ranks: every rank calls
+    this with its own partition ``x_local`` (the global rows [part_offsets[rank], part_offsets[rank + 1])), the WHOLE
+    graph's CSR (global ids) and the same ``model``, and gets the fp32 log-probabilities of ITS node range,
+    [n_local, classes] -- or of ``nodes`` (global ids, all inside the rank's range).  The bits are those of
+    ``layerwise_inference`` over the concatenated table, rows [part_offsets[rank], part_offsets[rank + 1]).
+
+    Per rank: the ping-pong activation buffers [n_local, hidden] of ``act_dtype`` are allocated up front (one for a
+    two-layer model) and published with ``x_local`` once through ``peers``; each layer aggregates the rank's own slabs with
+    ``graph_aggregate_parts`` over ALL ranks' previous-layer parts, runs the layer's parameters over the same fixed GEMM
+    tiles as ``layerwise_inference`` and writes its rows of the next layer into its own buffer; then the rank synchronises
+    its stream and waits in ``peers.barrier()`` before anyone reads the layer or reuses a buffer.  After the last barrier
+    the mappings are closed.
+
+    ``peers``: ``share(tensor) -> P2PPeers`` (collective, same order on every rank), ``barrier()``, ``close()``; optional
+    ``bind(rank)`` and ``abort()``.  ``LocalPeers`` and ``IpcPeers`` are the two implementations.  GAT and
+    SAGEResInception are refused here and scored by ``partitioned_inference``, the entry for all four models.
+
+    Memory, as arithmetic (S-mag, N = 121.8 M, F = 768 fp16, hidden 256, bf16): per rank of P, 187 / P GB of table and
+    2 * 62 / P GB of activations next to its copy of the 22 GB graph."""
+    from .models import GAT, GIN, SAGE, SAGEResInception
+    what = "partitioned_layerwise_inference"
+    if isinstance(model, (GAT, SAGEResInception)):
+        raise NotImplementedError(f"{what}: {type(model).__name__} over a partitioned table is not scored by this entry "
+                                  "(its layers need the long-row softmax / the fused layer tail over parts); SAGE and GIN "
+                                  "are.  partitioned_inference scores all four models")
+    if not isinstance(model, (SAGE, GIN)):
+        raise NotImplementedError(f"{what}: implemented for SAGE and GIN, not {type(model).__name__}")
+    off, rank, nodes, rows_per_slab = _check_partitioned(what, x_local, rowptr, col, part_offsets, rank, peers, nodes,
+                                                         rows_per_slab, act_dtype)
+    lo, n_local, dev = off[rank], off[rank + 1] - off[rank], x_local.device
     amp = act_dtype == torch.bfloat16
     gin = isinstance(model, GIN)
     n_layers, hidden = len(model.convs), model.hidden_channels
@@ -891,5 +1001,196 @@ def partitioned_layerwise_inference(model, x_local, rowptr, col, *, part_offsets
         raise
     finally:
         for sh, _dt, _f in shared:
+            sh.close()
+        model.train(was_training)
+
+
+def _tiles_contiguous(A):
+    """``_row_tiles`` with every tile contiguous: a full tile of a padded buffer is a strided view, and the GEMM's
+    operand layout is part of its shape (the whole-table drivers multiply contiguous matrices)"""
+    for r, n, tile in _row_tiles(A):
+        yield r, n, tile.contiguous()
+
+
+def _gat_partitioned(model, x_local, rowptr, col, off, rank, peers, nodes, rows_per_slab, act_dtype, shared):
+    """``_gat_inference`` for one rank of a row-partitioned table: the same operations on the same fixed tiles, so the
+    same bits.  Projection and logits are LOCAL (a rank's own rows of the layer's input), so no rank reads a peer's
+    feature rows and ``x_local`` is not published.  Two buffers are, once: h [n_local, max H*C] of ``act_dtype`` and the
+    logits [n_local, 2 * max H] fp32 = [a_src | a_dst], both laid out by the resident tables' row-stride rule (one stride
+    on every rank); a layer narrower than the buffer reads its leading columns at the buffer's stride.  Per layer: write
+    the rank's h and logits; synchronise and barrier (every rank's h is complete); attend the rank's slabs with
+    ``graph_gat_aggregate_parts`` over all ranks' parts into a local matrix; synchronise and barrier (everyone has
+    finished reading h before the next layer overwrites it, or, after the last layer, before anyone unmaps)."""
+    lo, dev = off[rank], x_local.device
+    n_local = off[rank + 1] - lo
+    n_layers = len(model.convs)
+    Fmax = max(c.heads * c.out_channels for c in model.convs)
+    Hmax = max(c.heads for c in model.convs)
+    esize = torch.empty(0, dtype=act_dtype).element_size()
+    hbuf = torch.empty((n_local, _row_stride_elems(Fmax, esize)), dtype=act_dtype, device=dev)[:, :Fmax]
+    abuf = torch.empty((n_local, _row_stride_elems(2 * Hmax, 4)), dtype=torch.float32, device=dev)[:, :2 * Hmax]
+    shared.append(peers.share(hbuf))
+    shared.append(peers.share(abuf))
+    h_peers, a_peers = shared
+    rows_out = nodes.numel() if nodes is not None else n_local
+    ws = torch.empty(graph_gat_workspace_bytes(min(rows_per_slab, max(n_local, rows_out))), dtype=torch.uint8, device=dev)
+    cur = x_local
+    for i, conv in enumerate(model.convs):
+        last = i == n_layers - 1
+        H, Cc = conv.heads, conv.out_channels
+        W = conv.lin_src.weight                                                   # [H*C, K]
+        att = torch.stack([conv.att_src.view(H, Cc), conv.att_dst.view(H, Cc)]).to(torch.float32)
+        V = torch.einsum("shc,hck->shk", att, W.to(torch.float32).view(H, Cc, -1)).reshape(2 * H, -1)   # [V_src; V_dst]
+        Wt, Vt = W.to(act_dtype).t(), V.t().contiguous()
+        for r, n, tile in _row_tiles(cur):
+            hbuf[r:r + n, :H * Cc] = (tile.to(act_dtype) @ Wt)[:n]
+            abuf[r:r + n, :2 * H] = (tile.to(torch.float32) @ Vt)[:n]
+        del cur
+        torch.cuda.current_stream(dev).synchronize()
+        peers.barrier()                                  # every rank's h and logits of this layer are complete
+        ids = nodes if last else None
+        rows = ids.numel() if ids is not None else n_local
+        width = Cc if last else H * Cc
+        nxt = torch.empty((rows, width), dtype=torch.float32 if last else act_dtype, device=dev)
+        for s in range(0, rows, rows_per_slab):
+            e = min(rows, s + rows_per_slab)
+            tgt = dict(target_ids=ids[s:e]) if ids is not None else dict(row0=lo + s, num_targets=e - s)
+            out = nxt[s:e] if not last else torch.empty((e - s, H * Cc), dtype=torch.float32, device=dev)
+            graph_gat_aggregate_parts(h_peers, a_peers, off, rowptr, col, heads=H, negative_slope=conv.negative_slope,
+                                      relu=not last, out_dtype=out.dtype, out=out, workspace=ws, dtype=act_dtype,
+                                      F=H * Cc, **tgt)
+            if last:                                     # concat=False: the mean of the heads (H = 1: the head itself)
+                nxt[s:e] = torch.log_softmax(out.view(e - s, H, Cc).mean(1) if H > 1 else out, dim=-1,
+                                             dtype=torch.float32)
+        cur = nxt
+        torch.cuda.current_stream(dev).synchronize()
+        peers.barrier()                                  # every rank has finished reading this layer's h
+    return cur
+
+
+def _resinc_partitioned(model, x_local, rowptr, col, off, rank, peers, nodes, rows_per_slab, act_dtype, shared):
+    """``_resinc_inference`` for one rank of a row-partitioned table.  ``x_local`` and the ping-pong [n_local, hidden]
+    buffers are published once; each layer aggregates with ``graph_aggregate_parts`` ("operand") over all ranks' parts,
+    and everything behind the aggregation is local: the GEMM tiles, ``resinc_epilogue`` (the residual of layers >= 2 is
+    the rank's OWN previous buffer, by local slab or by ``ids - lo``), the head accumulator.  One synchronise and barrier
+    per layer."""
+    lin1, lin2 = _resinc_head(model)
+    lo, dev = off[rank], x_local.device
+    n_local = off[rank + 1] - lo
+    n_layers, hidden = len(model.convs), model.hidden_channels
+    esize = torch.empty(0, dtype=act_dtype).element_size()
+    se = _row_stride_elems(hidden, esize)
+    bufs = [torch.empty((n_local, se), dtype=act_dtype, device=dev)[:, :hidden] for _ in range(min(2, n_layers - 1))]
+    shared.append(peers.share(x_local))
+    for b in bufs:
+        shared.append(peers.share(b))
+    rows_out = nodes.numel() if nodes is not None else n_local
+    local = nodes - lo if nodes is not None else None    # the rank's own rows of ``nodes``
+    ws = torch.empty(graph_agg_workspace_bytes(min(rows_per_slab, max(n_local, rows_out))), dtype=torch.uint8, device=dev)
+    acc = torch.zeros((rows_out, lin1.out_features), dtype=torch.float32, device=dev)
+    if lin1.bias is not None:
+        acc += lin1.bias.to(torch.float32)
+
+    def add_block(block, first_col):                     # acc += block @ W1[:, its columns]^T, over the fixed tiles
+        Wb = lin1.weight[:, first_col:first_col + block.size(1)].to(act_dtype).t()
+        for r, n, tile in _tiles_contiguous(block):
+            acc[r:r + n] += (tile.to(act_dtype) @ Wb)[:n]
+
+    add_block(x_local if local is None else x_local[local], 0)
+    cur = x_local
+    for i, (conv, bn) in enumerate(zip(model.convs, model.bns)):
+        last = i == n_layers - 1
+        a = bn.weight.to(torch.float32) / torch.sqrt(bn.running_var.to(torch.float32) + bn.eps)
+        b = bn.bias.to(torch.float32) - bn.running_mean.to(torch.float32) * a
+        W = torch.cat([conv.lin_l.weight, conv.lin_r.weight], dim=1)               # [hidden, 2K] = [W_l | W_r]
+        bias = conv.lin_l.bias
+        res = model.res_linears[i]
+        if isinstance(res, torch.nn.Linear):             # (layer 1) stacked: the tile comes out as [z | res(x_t)]
+            W = torch.cat([W, torch.cat([torch.zeros_like(res.weight), res.weight], dim=1)], dim=0)
+            if bias is not None or res.bias is not None:
+                zero = W.new_zeros(hidden)
+                bias = torch.cat([bias if bias is not None else zero, res.bias if res.bias is not None else zero])
+        Wt = W.to(act_dtype).t()
+        bias = bias.to(act_dtype) if bias is not None else None
+        src = shared[0] if i == 0 else shared[1 + (i - 1) % len(bufs)]
+        ids = nodes if last else None
+        rows = ids.numel() if ids is not None else n_local
+        nxt = torch.empty((rows, hidden), dtype=act_dtype, device=dev) if last else bufs[i % len(bufs)]
+        for s in range(0, rows, rows_per_slab):
+            e = min(rows, s + rows_per_slab)
+            tgt = dict(target_ids=ids[s:e]) if ids is not None else dict(row0=lo + s, num_targets=e - s)
+            A = graph_aggregate_parts(src, off, rowptr, col, dtype=cur.dtype, F=cur.size(1), epilogue="operand",
+                                      out_dtype=act_dtype, workspace=ws, **tgt)
+            for r, n, tile in _row_tiles(A):
+                Z = torch.addmm(bias, tile, Wt) if bias is not None else tile @ Wt
+                if Z.size(1) > hidden:
+                    residual = dict(residual=Z[:, hidden:], row0=0)
+                elif ids is not None:
+                    residual = dict(residual=cur, row_ids=local[s + r:s + r + n])
+                else:
+                    residual = dict(residual=cur, row0=s + r)
+                resinc_epilogue(Z[:n, :hidden], a, b, negative_slope=0.01, out=nxt[s + r:s + r + n], **residual)
+        add_block(nxt if last or local is None else nxt[local], x_local.size(1) + i * hidden)
+        cur = nxt
+        # layer i is complete HERE before any rank reads it, and every rank has finished reading layer i-1 before its
+        # buffer is written again (after the last layer: before anyone unmaps)
+        torch.cuda.current_stream(dev).synchronize()
+        peers.barrier()
+    W2t = lin2.weight.to(act_dtype).t()
+    b2 = lin2.bias.to(act_dtype) if lin2.bias is not None else None
+    out = torch.empty((rows_out, lin2.out_features), dtype=torch.float32, device=dev)
+    for r, n, tile in _row_tiles(acc):
+        h = tile.to(act_dtype)
+        h = torch.addmm(b2, h, W2t) if b2 is not None else h @ W2t
+        out[r:r + n] = torch.log_softmax(h[:n], dim=-1, dtype=torch.float32)
+    return out
+
+
+def partitioned_inference(model, x_local, rowptr, col, *, part_offsets, rank, peers, nodes=None, rows_per_slab=1 << 20,
+                          act_dtype=torch.float32):
+    """``layerwise_inference`` for ``SAGE``, ``GIN``, ``GAT`` and ``SAGEResInception`` when the feature table is
+    row-partitioned over the ranks.  Every rank calls this with its own partition ``x_local`` (the global rows
+    [part_offsets[rank], part_offsets[rank + 1])), the WHOLE graph's CSR (global ids) and the same ``model``, and gets the
+    fp32 log-probabilities of ITS node range, [n_local, classes] -- or of ``nodes`` (global ids, all inside the rank's
+    range).  The bits are those of ``layerwise_inference`` over the concatenated table, those rows.
+
+    SAGE and GIN: ``partitioned_layerwise_inference``, whose arguments, ``peers`` protocol and failure rule (``abort()``
+    when a rank fails, ``close()`` of every mapping at the end) hold here.  GAT: ``_gat_partitioned`` (local projection,
+    h and logits published once, two barriers a layer); SAGEResInception: ``_resinc_partitioned`` (one barrier a layer).
+    The model-shape refusals are ``layerwise_inference``'s, and like every argument check they come before ``peers`` is
+    touched.
+
+    Memory per rank of P, as arithmetic (GAT at papers scale: N = 111 M, hidden 256, 172 classes, H = 1, bf16, P = 8, so
+    13.9 M rows a rank): the h buffer 13.9 M * 256 * 2 B = 7.1 GB and the logits 13.9 M * 8 B = 0.11 GB, both live for the
+    whole call; one [n_local, 256] bf16 activation matrix at a time beside them (``cur`` while a layer projects, ``nxt``
+    while it attends), 7.1 GB; the last layer's [n_local, 172] fp32 result, 9.5 GB; 3.6 GB of table and the rank's copy
+    of the 26 GB graph: about 47 GB at the peak, against 168 GB on one device."""
+    from .models import GAT, GIN, SAGE, SAGEResInception
+    what = "partitioned_inference"
+    if not isinstance(model, (SAGE, GIN, GAT, SAGEResInception)):
+        raise NotImplementedError(f"{what}: implemented for SAGE, GIN, GAT and SAGEResInception, not "
+                                  f"{type(model).__name__}")
+    if isinstance(model, (SAGE, GIN)):
+        return partitioned_layerwise_inference(model, x_local, rowptr, col, part_offsets=part_offsets, rank=rank,
+                                               peers=peers, nodes=nodes, rows_per_slab=rows_per_slab, act_dtype=act_dtype)
+    _check_model_shape(model, what)
+    off, rank, nodes, rows_per_slab = _check_partitioned(what, x_local, rowptr, col, part_offsets, rank, peers, nodes,
+                                                         rows_per_slab, act_dtype)
+    dev = x_local.device
+    run = _gat_partitioned if isinstance(model, GAT) else _resinc_partitioned
+    was_training = model.training
+    model.eval()
+    shared = []
+    try:
+        with torch.no_grad(), torch.autocast("cuda", enabled=False), torch.cuda.device(dev):
+            if hasattr(peers, "bind"):
+                peers.bind(rank)
+            return run(model, x_local, rowptr, col, off, rank, peers, nodes, rows_per_slab, act_dtype, shared)
+    except BaseException:
+        if hasattr(peers, "abort"):
+            peers.abort()
+        raise
+    finally:
+        for sh in shared:
             sh.close()
         model.train(was_training)

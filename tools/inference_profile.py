@@ -6,6 +6,7 @@ with bf16 activations, timed per layer, and layer 1's slabs once more through th
     python tools/inference_profile.py --model gat [--heads 4] [--repeats 3] ...
     python tools/inference_profile.py --model sageresinception [--nodes 1500000] [--torch-epilogue] [--repeats 3] ...
     python tools/inference_profile.py --parts 8 --workload S-products [--repeats 5] ...
+    python tools/inference_profile.py --parts 8 --model gat --workload S-products [--heads 1] [--repeats 9] ...
 
 ``--model gat``: GAT 3 x hidden at ``--heads`` through spp_graph_gat_forward, ``--repeats`` whole passes in one process
 (the first warms up code objects and the GEMM library's choices; every pass is reported).  Its bytes are the mean's plus
@@ -21,6 +22,10 @@ allocation of its own on the one GPU, and every slab's MEAN aggregated twice: ``
 matrix (the baseline) and ``spp_graph_agg_parts_forward`` on the parts, at the table's own width (fp16) and at ``--hidden``
 (bf16 rows); ``--repeats`` alternating passes after one warm-up pass of each, every pass reported, the ratio taken
 between the medians.  One slab's outputs are compared bit for bit first.
+
+``--parts P --model gat``: the same for the attention.  A random bf16 h [N, hidden] and fp32 logits [N, 2 * heads], cut
+into P equal row ranges, an allocation per part and kind; every slab attended twice: ``spp_graph_gat_forward`` on the
+whole matrices and ``spp_graph_gat_parts_forward`` on the parts, alternating, after one slab is compared bit for bit.
 
 Per layer: seconds of the aggregation alone (events around every slab's graph_aggregate, summed), edges/s, and the
 algorithmic bytes/s  E * F * s (rows) + 16 * T + 8 * E (indices) + T * W * s_out (output); plus the seconds of the whole
@@ -68,7 +73,7 @@ def main():
     del deg, long_rows
     print(json.dumps({k: v for k, v in res.items() if k != "layers"}), flush=True)
     if a.parts > 0:
-        return parts_leg(a, wl, res)
+        return gat_parts_leg(a, wl, res) if a.model == "gat" else parts_leg(a, wl, res)
     if a.model == "gat":
         return gat_leg(a, wl, res)
     if a.model == "sageresinception":
@@ -258,6 +263,66 @@ def parts_leg(a, wl, res):
         res["widths"].append(one)
         print(json.dumps(one), flush=True)
         del parts
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+def gat_parts_leg(a, wl, res):
+    from salient_plusplus_amd import inference as inf
+    rowptr, col = wl.rowptr, wl.col
+    dev = rowptr.device
+    N, E, P, H = wl.num_nodes, col.numel(), a.parts, a.heads
+    off = [N * p // P for p in range(P + 1)]
+    res.update(model="gat", heads=H, chunk=inf.graph_gat_chunk(), parts=P, part_offsets=off)
+    res.pop("layers")
+    ws = torch.empty(inf.graph_gat_workspace_bytes(min(a.rows_per_slab, N)), dtype=torch.uint8, device=dev)
+    torch.manual_seed(0)
+    h = torch.randn((N, a.hidden), device=dev).to(torch.bfloat16)
+    logits = torch.randn((N, 2 * H), device=dev)
+    a_src, a_dst = logits[:, :H].contiguous(), logits[:, H:].contiguous()
+
+    def cut(m):                                          # an allocation per part, rows as far apart as the matrix's
+        parts = []
+        for p in range(P):
+            buf = torch.empty((off[p + 1] - off[p], m.stride(0)), dtype=m.dtype, device=dev)[:, :m.size(1)]
+            buf.copy_(m[off[p]:off[p + 1]])
+            parts.append(buf)
+        return parts
+    hp, lp = cut(h), cut(logits)
+    del logits
+    slabs = [(s, min(a.rows_per_slab, N - s)) for s in range(0, N, a.rows_per_slab)]
+    kw = dict(heads=H, relu=True, out_dtype=torch.bfloat16, workspace=ws)
+
+    def whole(s, T):
+        return inf.graph_gat_aggregate(h, a_src, a_dst, rowptr, col, row0=s, num_targets=T, **kw)
+
+    def parted(s, T):
+        return inf.graph_gat_aggregate_parts(hp, lp, off, rowptr, col, row0=s, num_targets=T, **kw)
+    s0, T0 = slabs[len(slabs) // 2]
+    assert torch.equal(whole(s0, T0).view(torch.int16), parted(s0, T0).view(torch.int16)), "the parts change bits"
+    times = {"whole": [], "parts": []}
+    b, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for rep in range(a.repeats + 1):                     # (pass 0 warms up both)
+        for name, fn in (("whole", whole), ("parts", parted)):
+            torch.cuda.synchronize()
+            b.record()
+            for _sweep in range(SWEEPS):
+                for s, T in slabs:
+                    fn(s, T)
+            e.record()
+            e.synchronize()
+            if rep:
+                times[name].append(round(b.elapsed_time(e) / 1e3 / SWEEPS, 6))
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    nbytes = E * a.hidden * 2 + 16 * N + 8 * E + N * a.hidden * 2 + 4 * H * E + 8 * H * N
+    res.update(F=a.hidden, x_dtype=str(h.dtype), x_stride_elems=h.stride(0), whole_s=times["whole"],
+               parts_s=times["parts"], whole_median_s=med["whole"], parts_median_s=med["parts"],
+               ratio_parts_over_whole=round(med["parts"] / med["whole"], 4),
+               whole_algorithmic_TBps=round(nbytes / med["whole"] / 1e12, 3))
+    print(json.dumps({k: res[k] for k in ("F", "heads", "whole_s", "parts_s", "whole_median_s", "parts_median_s",
+                                          "ratio_parts_over_whole", "whole_algorithmic_TBps")}), flush=True)
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:
