@@ -1,19 +1,24 @@
-"""Exact, layer-wise inference over the whole resident graph (reference: driver/models.py:441 ``layerwise_inference``
-with ``SAGE.inference``): every node is scored from ALL its neighbours, one pass per layer over the graph's CSR, with
-no sampling, no dedup and no exchange.  The message passing is the HIP kernel pair of csrc/graph_aggregate.hip
-(``spp_graph_agg_forward``) for SAGE, GIN and SAGEResInception and of csrc/graph_gat.hip (``spp_graph_gat_forward``) for
-GAT; SAGEResInception's layer tail is csrc/resinc_epilogue.hip (``spp_resinc_epilogue``); the layers' own parameters run
-through the library GEMMs torch dispatches to.
+"""Exact, layer-wise inference over the whole graph (reference: driver/models.py:441 ``layerwise_inference`` with
+``SAGE.inference``): every node is scored from ALL its neighbours, one pass per layer over the graph's CSR, with no
+sampling, no dedup and no exchange.  The message passing is the HIP kernel pair of csrc/graph_aggregate.hip for SAGE,
+GIN and SAGEResInception and of csrc/graph_gat.hip for GAT; SAGEResInception's layer tail is csrc/resinc_epilogue.hip
+(``spp_resinc_epilogue``); the layers' own parameters run through the library GEMMs torch dispatches to.  Forward only,
+fp16 / fp32 / bf16 inputs.
 
-``graph_aggregate``, ``graph_gat_aggregate`` and ``resinc_epilogue`` are the kernels' thin wrappers,
-``layerwise_inference`` the driver behind ``SAGE.inference`` and ``GIN.inference`` and the entry point for ``GAT`` and
-``SAGEResInception``.  Forward only, one GPU, fp16 / fp32 / bf16 inputs.
+The kernels' wrappers: ``graph_aggregate`` (``spp_graph_agg_forward``) and ``graph_gat_aggregate``
+(``spp_graph_gat_forward``) read one resident matrix, ``graph_aggregate_parts`` (``spp_graph_agg_parts_forward``) and
+``graph_gat_aggregate_parts`` (``spp_graph_gat_parts_forward``) a row-PARTITIONED one (one range of nodes per rank, the
+peers' partitions mapped into the process), ``resinc_epilogue`` is the layer tail.  Each wrapper checks its arguments
+with the helpers they share and hands them to its kernel's launch function (``_agg_launch``, ``_gat_launch``,
+``_agg_parts_launch``, ``_gat_parts_launch``), which the drivers call directly, slab by slab.
 
-Over a row-PARTITIONED feature table (one range of nodes per rank, the peers' partitions mapped into the process):
-``graph_aggregate_parts`` (``spp_graph_agg_parts_forward``), ``graph_gat_aggregate_parts``
-(``spp_graph_gat_parts_forward``) and ``partitioned_inference`` for all four models (``partitioned_layerwise_inference``
-is its SAGE / GIN half), with ``LocalPeers`` (ranks as threads of one process) or ``IpcPeers`` (one process per rank on
-one node) between the ranks."""
+The drivers: one layer loop per model (``_conv_layers`` for SAGE and GIN, ``_gat_layers``, ``_resinc_layers``), written
+against a placement that says where the table lives -- ``_Resident`` (one matrix, the whole-table kernels, no waits) or
+``_Partitioned`` (the parts kernels over buffers published through ``peers``, a synchronise and a barrier at every layer
+boundary) -- inside one frame (``_score``).  ``layerwise_inference`` is the resident entry (behind ``SAGE.inference``
+and ``GIN.inference``), ``partitioned_inference`` the partitioned one for all four models
+(``partitioned_layerwise_inference`` admits SAGE and GIN only), with ``LocalPeers`` (ranks as threads of one process)
+or ``IpcPeers`` (one process per rank on one node) between the ranks."""
 import ctypes as C
 import threading
 
@@ -39,6 +44,17 @@ def graph_agg_workspace_bytes(num_targets):
     return int(nat.load().spp_graph_agg_workspace_bytes(int(num_targets)))
 
 
+def graph_gat_chunk():
+    """C_g of the softmax contract (include/spp.h): a row of at most C_g raw entries is one online softmax in CSR order,
+    a longer row is chunks of C_g whose softmax states are merged in chunk order"""
+    return int(nat.load().spp_graph_gat_chunk())
+
+
+def graph_gat_workspace_bytes(num_targets):
+    return int(nat.load().spp_graph_gat_workspace_bytes(int(num_targets)))
+
+
+# ---- the argument checks the wrappers and the drivers share; ``what`` is the caller's name in the message -----------
 def _check_matrix(x, what, name="x"):
     """x as the kernels read it: a 2-D fp16 / fp32 / bf16 matrix with unit column stride that carries no gradient"""
     if isinstance(x, Fp8Features):
@@ -56,70 +72,65 @@ def _check_matrix(x, what, name="x"):
         raise RuntimeError(f"{what}: {name} requires grad, and inference is forward only (detach it)")
 
 
-def _check_graph(x, rowptr, col, what):
+def _check_graph(what, N, rowptr, col, parts=False):
+    """the whole graph's CSR, one row for each of the N rows of the matrix (or of the parts together)"""
     for name, t in (("rowptr", rowptr), ("col", col)):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous():
             raise ValueError(f"{what}: {name} must be a contiguous 1-D int64 tensor")
-    if rowptr.numel() != x.size(0) + 1:
-        raise ValueError(f"{what}: x has {x.size(0)} rows, the graph {rowptr.numel() - 1} nodes (one row per node)")
+    if rowptr.numel() != N + 1:
+        raise ValueError(f"{what}: {f'the parts hold {N} rows' if parts else f'x has {N} rows'}, the graph "
+                         f"{rowptr.numel() - 1} nodes (one row per node)")
 
 
-def graph_aggregate(x, rowptr, col, *, row0=None, num_targets=None, target_ids=None, epilogue="mean", self_scale=0.0,
-                    out_dtype=torch.float32, workspace=None):
-    """Aggregation over whole rows of the resident graph (``spp_graph_agg_forward``, include/spp.h).
-
-    ``x`` [N, F]: one row per graph node (fp16 / fp32 / bf16, possibly a strided view); ``rowptr`` / ``col``: the
-    graph's CSR (int64, global ids).  The targets are a slab, ``row0`` and ``num_targets`` (output row i is node
-    row0 + i), or a list, ``target_ids`` (int64, any order, duplicates allowed).  ``epilogue``: "mean" [T, F],
-    "operand" [T, 2F] = [mean | x[target]] or "sum" [T, F] = self_scale * x[target] + sum.  fp32 sums; a bf16 output
-    is rounded once.  A ``col`` entry outside the graph reads row 0, a target id outside it gives a row of zeros.
-
-    Forward only: no autograd node is registered and an input that requires grad is refused.  ``workspace``: a uint8
-    CUDA tensor of at least ``graph_agg_workspace_bytes(T)`` bytes, reusable between calls on one stream; allocated
-    when None.  Nothing here waits for the device."""
-    what = "graph_aggregate"
-    _check_matrix(x, what)
-    _check_graph(x, rowptr, col, what)
-    if epilogue not in _EPILOGUES:
-        raise ValueError(f"{what}: epilogue must be 'mean', 'operand' or 'sum', got {epilogue!r}")
+def _check_out_dtype(what, out_dtype):
     if out_dtype not in _OUT_DTYPES:
         raise ValueError(f"{what}: out_dtype must be torch.float32 or torch.bfloat16, got {out_dtype}")
+
+
+def _check_heads(what, heads, Fdim):
+    if not isinstance(heads, int) or heads < 1 or Fdim % heads != 0:
+        raise ValueError(f"{what}: heads must be a positive int that divides F = {Fdim}, got {heads!r}")
+
+
+def _check_targets(what, N, row0, num_targets, target_ids):
+    """(row0 or -1, target_ids or None, T) of the two target forms: a slab inside the graph's N nodes, or a contiguous
+    int64 list"""
     slab = row0 is not None or num_targets is not None
     if slab == (target_ids is not None):
         raise ValueError(f"{what}: give the targets either as a slab (row0 and num_targets) or as target_ids"
                          + (", not both" if slab else ""))
-    N, Fdim = x.shape
     if slab:
         if row0 is None or num_targets is None:
             raise ValueError(f"{what}: a slab needs both row0 and num_targets")
         row0, T = int(row0), int(num_targets)
         if row0 < 0 or T < 0 or row0 + T > N:
             raise ValueError(f"{what}: the slab [{row0}, {row0 + T}) leaves the graph's {N} nodes")
-    else:
-        if not isinstance(target_ids, torch.Tensor) or target_ids.dtype != torch.int64 or target_ids.dim() != 1 \
-                or not target_ids.is_contiguous():
-            raise ValueError(f"{what}: target_ids must be a contiguous 1-D int64 tensor")
-        row0, T = -1, target_ids.numel()
+        return row0, None, T
+    if not isinstance(target_ids, torch.Tensor) or target_ids.dtype != torch.int64 or target_ids.dim() != 1 \
+            or not target_ids.is_contiguous():
+        raise ValueError(f"{what}: target_ids must be a contiguous 1-D int64 tensor")
+    return -1, target_ids, target_ids.numel()
+
+
+def _check_out(what, out, out_dtype, T, width):
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != out_dtype
+                            or tuple(out.shape) != (T, width) or (width > 1 and out.stride(1) != 1) or out.requires_grad):
+        raise ValueError(f"{what}: out must be a {out_dtype} matrix of shape [{T}, {width}] with unit column stride "
+                         "that does not require grad")
+
+
+def _on_device(what, names, dev, tensors, workspace, workspace_bytes, T):
+    """what follows the argument checks: the device is required, every tensor given lives on ``dev``, and the workspace
+    (returned; allocated when None) holds ``workspace_bytes(T)`` bytes"""
     nat.require_device()
-    tensors = [x, rowptr, col] + ([target_ids] if not slab else []) + ([workspace] if workspace is not None else [])
-    if not all(t.is_cuda and t.device == x.device for t in tensors):
-        raise ValueError(f"{what}: x, rowptr, col, target_ids and workspace must live on one CUDA device")
-    L = nat.load()
-    nbytes = int(L.spp_graph_agg_workspace_bytes(T))
+    if dev.type != "cuda" or not all(t.is_cuda and t.device == dev for t in tensors + [workspace] if t is not None):
+        raise ValueError(f"{what}: {names} must live on one CUDA device")
+    nbytes = workspace_bytes(T)
     if workspace is None:
-        workspace = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < nbytes:
+        return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < nbytes:
         raise ValueError(f"{what}: workspace must be a contiguous uint8 tensor of at least {nbytes} bytes")
-    width = 2 * Fdim if epilogue == "operand" else Fdim
-    out = torch.empty((T, width), dtype=out_dtype, device=x.device)
-    d = nat.GraphAggDesc(epilogue=_EPILOGUES[epilogue], x_elem=_ELEM[x.dtype], out_elem=_ELEM[out_dtype],
-                         rowptr_dev=_p(rowptr), col_dev=_p(col), x_dev=_p(x),
-                         x_stride_elems=x.stride(0) if N > 1 else Fdim, x_rows=N, F=Fdim, target_row0=row0,
-                         target_ids_dev=_p(target_ids) if not slab else None, num_targets=T, out_dev=_p(out),
-                         out_stride_elems=0, self_scale=float(self_scale))
-    with torch.cuda.device(x.device):
-        nat.check(L.spp_graph_agg_forward(C.byref(d), C.c_void_p(workspace.data_ptr()), workspace.numel(), _stream()))
-    return out
+    return workspace
 
 
 def _check_offsets(part_offsets, what):
@@ -188,6 +199,94 @@ def _parts_source(parts, off, dtype, F, what, name="part"):
     return ptrs, stride, first.dtype, first.size(1), first.device
 
 
+# ---- the kernels' launch functions: checked arguments in, ``out`` [T, width] (rows of a larger matrix allowed) written
+def _request(rowptr, col, row0, target_ids, T, out):
+    """the descriptor fields all four kernels share: the graph, the targets and where their rows go"""
+    return dict(rowptr_dev=_p(rowptr), col_dev=_p(col), target_row0=row0, target_ids_dev=_p(target_ids), num_targets=T,
+                out_elem=_ELEM[out.dtype], out_dev=_p(out), out_stride_elems=out.stride(0) if T > 1 else 0)
+
+
+def _launch(entry, d, workspace, out):
+    with torch.cuda.device(out.device):
+        nat.check(entry(C.byref(d), C.c_void_p(workspace.data_ptr()), workspace.numel(), _stream()))
+    return out
+
+
+def _agg_launch(x, rowptr, col, epilogue, self_scale, row0, target_ids, T, out, workspace):
+    """spp_graph_agg_forward: x [N, F] is one matrix"""
+    N, Fdim = x.shape
+    d = nat.GraphAggDesc(epilogue=_EPILOGUES[epilogue], x_elem=_ELEM[x.dtype], x_dev=_p(x),
+                         x_stride_elems=x.stride(0) if N > 1 else Fdim, x_rows=N, F=Fdim, self_scale=float(self_scale),
+                         **_request(rowptr, col, row0, target_ids, T, out))
+    return _launch(nat.load().spp_graph_agg_forward, d, workspace, out)
+
+
+def _agg_parts_launch(src, off, rowptr, col, epilogue, self_scale, row0, target_ids, T, out, workspace):
+    """spp_graph_agg_parts_forward: ``src`` is ``_parts_source``'s (base addresses, row stride, dtype, F)"""
+    ptrs, stride, x_dtype, Fdim = src
+    d = nat.GraphAggPartsDesc(epilogue=_EPILOGUES[epilogue], x_elem=_ELEM[x_dtype], num_parts=len(off) - 1,
+                              x_stride_elems=stride, F=Fdim, self_scale=float(self_scale),
+                              **_request(rowptr, col, row0, target_ids, T, out))
+    for p, v in enumerate(off):
+        d.part_offsets[p] = v
+    for p, v in enumerate(ptrs):
+        d.x_parts_dev[p] = v or None
+    return _launch(nat.load().spp_graph_agg_parts_forward, d, workspace, out)
+
+
+def _gat_launch(h, a_src, a_dst, rowptr, col, heads, negative_slope, relu, row0, target_ids, T, out, workspace):
+    """spp_graph_gat_forward: h [N, F] is one matrix, its logits two contiguous fp32 [N, heads]"""
+    N, Fdim = h.shape
+    d = nat.GraphGatDesc(x_elem=_ELEM[h.dtype], heads=heads, relu=int(bool(relu)), x_dev=_p(h),
+                         x_stride_elems=h.stride(0) if N > 1 else Fdim, x_rows=N, F=Fdim, a_src_dev=_p(a_src),
+                         a_dst_dev=_p(a_dst), negative_slope=float(negative_slope),
+                         **_request(rowptr, col, row0, target_ids, T, out))
+    return _launch(nat.load().spp_graph_gat_forward, d, workspace, out)
+
+
+def _gat_parts_launch(src, a_src, off, rowptr, col, heads, negative_slope, relu, row0, target_ids, T, out, workspace):
+    """spp_graph_gat_parts_forward: ``src`` as for ``_agg_parts_launch``, ``a_src`` the logits' (base addresses, row
+    stride)"""
+    ptrs, stride, x_dtype, Fdim = src
+    a_ptrs, a_stride = a_src
+    d = nat.GraphGatPartsDesc(x_elem=_ELEM[x_dtype], heads=heads, relu=int(bool(relu)), num_parts=len(off) - 1,
+                              x_stride_elems=stride, a_stride_elems=a_stride, F=Fdim,
+                              negative_slope=float(negative_slope), **_request(rowptr, col, row0, target_ids, T, out))
+    for p, v in enumerate(off):
+        d.part_offsets[p] = v
+    for p, (hv, av) in enumerate(zip(ptrs, a_ptrs)):
+        d.h_parts_dev[p], d.a_parts_dev[p] = hv or None, av or None
+    return _launch(nat.load().spp_graph_gat_parts_forward, d, workspace, out)
+
+
+# ---- the kernels' public wrappers ------------------------------------------------------------------------------------
+def graph_aggregate(x, rowptr, col, *, row0=None, num_targets=None, target_ids=None, epilogue="mean", self_scale=0.0,
+                    out_dtype=torch.float32, workspace=None):
+    """Aggregation over whole rows of the resident graph (``spp_graph_agg_forward``, include/spp.h).
+
+    ``x`` [N, F]: one row per graph node (fp16 / fp32 / bf16, possibly a strided view); ``rowptr`` / ``col``: the
+    graph's CSR (int64, global ids).  The targets are a slab, ``row0`` and ``num_targets`` (output row i is node
+    row0 + i), or a list, ``target_ids`` (int64, any order, duplicates allowed).  ``epilogue``: "mean" [T, F],
+    "operand" [T, 2F] = [mean | x[target]] or "sum" [T, F] = self_scale * x[target] + sum.  fp32 sums; a bf16 output
+    is rounded once.  A ``col`` entry outside the graph reads row 0, a target id outside it gives a row of zeros.
+
+    Forward only: no autograd node is registered and an input that requires grad is refused.  ``workspace``: a uint8
+    CUDA tensor of at least ``graph_agg_workspace_bytes(T)`` bytes, reusable between calls on one stream; allocated
+    when None.  Nothing here waits for the device."""
+    what = "graph_aggregate"
+    _check_matrix(x, what)
+    N, Fdim = x.shape
+    _check_graph(what, N, rowptr, col)
+    if epilogue not in _EPILOGUES:
+        raise ValueError(f"{what}: epilogue must be 'mean', 'operand' or 'sum', got {epilogue!r}")
+    _check_out_dtype(what, out_dtype)
+    row0, target_ids, T = _check_targets(what, N, row0, num_targets, target_ids)
+    workspace = _on_device(what, "x, rowptr, col, target_ids and workspace", x.device, [x, rowptr, col, target_ids],
+                           workspace, graph_agg_workspace_bytes, T)
+    out = torch.empty((T, 2 * Fdim if epilogue == "operand" else Fdim), dtype=out_dtype, device=x.device)
+    return _agg_launch(x, rowptr, col, epilogue, self_scale, row0, target_ids, T, out, workspace)
+
+
 def graph_aggregate_parts(parts, part_offsets, rowptr, col, *, row0=None, num_targets=None, target_ids=None,
                           epilogue="mean", self_scale=0.0, out_dtype=torch.float32, workspace=None, out=None,
                           dtype=None, F=None):
@@ -203,89 +302,20 @@ def graph_aggregate_parts(parts, part_offsets, rowptr, col, *, row0=None, num_ta
     and nothing waits for the device."""
     what = "graph_aggregate_parts"
     off = _check_offsets(part_offsets, what)
-    ptrs, stride, x_dtype, Fdim, dev = _parts_source(parts, off, dtype, F, what)
-    N = off[-1]
-    for name, t in (("rowptr", rowptr), ("col", col)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be a contiguous 1-D int64 tensor")
-    if rowptr.numel() != N + 1:
-        raise ValueError(f"{what}: the parts hold {N} rows, the graph {rowptr.numel() - 1} nodes (one row per node)")
+    *src, dev = _parts_source(parts, off, dtype, F, what)
+    _check_graph(what, off[-1], rowptr, col, parts=True)
     if epilogue not in _EPILOGUES:
         raise ValueError(f"{what}: epilogue must be 'mean', 'operand' or 'sum', got {epilogue!r}")
-    if out_dtype not in _OUT_DTYPES:
-        raise ValueError(f"{what}: out_dtype must be torch.float32 or torch.bfloat16, got {out_dtype}")
-    slab = row0 is not None or num_targets is not None
-    if slab == (target_ids is not None):
-        raise ValueError(f"{what}: give the targets either as a slab (row0 and num_targets) or as target_ids"
-                         + (", not both" if slab else ""))
-    if slab:
-        if row0 is None or num_targets is None:
-            raise ValueError(f"{what}: a slab needs both row0 and num_targets")
-        row0, T = int(row0), int(num_targets)
-        if row0 < 0 or T < 0 or row0 + T > N:
-            raise ValueError(f"{what}: the slab [{row0}, {row0 + T}) leaves the graph's {N} nodes")
-    else:
-        if not isinstance(target_ids, torch.Tensor) or target_ids.dtype != torch.int64 or target_ids.dim() != 1 \
-                or not target_ids.is_contiguous():
-            raise ValueError(f"{what}: target_ids must be a contiguous 1-D int64 tensor")
-        row0, T = -1, target_ids.numel()
-    width = 2 * Fdim if epilogue == "operand" else Fdim
-    if out is not None:
-        if not isinstance(out, torch.Tensor) or out.dtype != out_dtype or tuple(out.shape) != (T, width) \
-                or (width > 1 and out.stride(1) != 1) or out.requires_grad:
-            raise ValueError(f"{what}: out must be a {out_dtype} matrix of shape [{T}, {width}] with unit column stride "
-                             "that does not require grad")
-    nat.require_device()
+    _check_out_dtype(what, out_dtype)
+    row0, target_ids, T = _check_targets(what, off[-1], row0, num_targets, target_ids)
+    width = 2 * src[3] if epilogue == "operand" else src[3]
+    _check_out(what, out, out_dtype, T, width)
     dev = rowptr.device if dev is None else dev
-    tensors = [rowptr, col] + [t for t in (None if slab else target_ids, workspace, out) if t is not None]
-    if dev.type != "cuda" or not all(t.is_cuda and t.device == dev for t in tensors):
-        raise ValueError(f"{what}: the parts, rowptr, col, target_ids, workspace and out must live on one CUDA device")
-    L = nat.load()
-    nbytes = int(L.spp_graph_agg_workspace_bytes(T))
-    if workspace is None:
-        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < nbytes:
-        raise ValueError(f"{what}: workspace must be a contiguous uint8 tensor of at least {nbytes} bytes")
+    workspace = _on_device(what, "the parts, rowptr, col, target_ids, workspace and out", dev,
+                           [rowptr, col, target_ids, out], workspace, graph_agg_workspace_bytes, T)
     if out is None:
         out = torch.empty((T, width), dtype=out_dtype, device=dev)
-    d = nat.GraphAggPartsDesc(epilogue=_EPILOGUES[epilogue], x_elem=_ELEM[x_dtype], out_elem=_ELEM[out_dtype],
-                              num_parts=len(off) - 1, rowptr_dev=_p(rowptr), col_dev=_p(col), x_stride_elems=stride,
-                              F=Fdim, target_row0=row0, target_ids_dev=_p(target_ids) if not slab else None,
-                              num_targets=T, out_dev=_p(out), out_stride_elems=out.stride(0) if T > 1 else 0,
-                              self_scale=float(self_scale))
-    for p, v in enumerate(off):
-        d.part_offsets[p] = v
-    for p, v in enumerate(ptrs):
-        d.x_parts_dev[p] = v or None
-    with torch.cuda.device(dev):
-        nat.check(L.spp_graph_agg_parts_forward(C.byref(d), C.c_void_p(workspace.data_ptr()), workspace.numel(),
-                                                _stream()))
-    return out
-
-
-def graph_gat_chunk():
-    """C_g of the softmax contract (include/spp.h): a row of at most C_g raw entries is one online softmax in CSR order,
-    a longer row is chunks of C_g whose softmax states are merged in chunk order"""
-    return int(nat.load().spp_graph_gat_chunk())
-
-
-def graph_gat_workspace_bytes(num_targets):
-    return int(nat.load().spp_graph_gat_workspace_bytes(int(num_targets)))
-
-
-def _gat_forward(h, a_src, a_dst, rowptr, col, heads, negative_slope, relu, row0, target_ids, T, out, workspace):
-    """spp_graph_gat_forward on checked arguments, into ``out`` [T, F] (rows of another matrix allowed)"""
-    N, Fdim = h.shape
-    d = nat.GraphGatDesc(x_elem=_ELEM[h.dtype], out_elem=_ELEM[out.dtype], heads=heads, relu=int(bool(relu)),
-                         rowptr_dev=_p(rowptr), col_dev=_p(col), x_dev=_p(h),
-                         x_stride_elems=h.stride(0) if N > 1 else Fdim, x_rows=N, F=Fdim, a_src_dev=_p(a_src),
-                         a_dst_dev=_p(a_dst), target_row0=row0, target_ids_dev=_p(target_ids) if target_ids is not None else None,
-                         num_targets=T, out_dev=_p(out), out_stride_elems=out.stride(0) if T > 1 else 0,
-                         negative_slope=float(negative_slope))
-    with torch.cuda.device(h.device):
-        nat.check(nat.load().spp_graph_gat_forward(C.byref(d), C.c_void_p(workspace.data_ptr()), workspace.numel(),
-                                                   _stream()))
-    return out
+    return _agg_parts_launch(src, off, rowptr, col, epilogue, self_scale, row0, target_ids, T, out, workspace)
 
 
 def graph_gat_aggregate(h, a_src, a_dst, rowptr, col, *, heads, negative_slope=0.2, relu=False, row0=None,
@@ -305,65 +335,21 @@ def graph_gat_aggregate(h, a_src, a_dst, rowptr, col, *, heads, negative_slope=0
     when None.  Nothing here waits for the device."""
     what = "graph_gat_aggregate"
     _check_matrix(h, what)
-    _check_graph(h, rowptr, col, what)
     N, Fdim = h.shape
-    if not isinstance(heads, int) or heads < 1 or Fdim % heads != 0:
-        raise ValueError(f"{what}: heads must be a positive int that divides F = {Fdim}, got {heads!r}")
+    _check_graph(what, N, rowptr, col)
+    _check_heads(what, heads, Fdim)
     for name, t in (("a_src", a_src), ("a_dst", a_dst)):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (N, heads) \
                 or not t.is_contiguous():
             raise ValueError(f"{what}: {name} must be a contiguous fp32 tensor of shape [{N}, {heads}] (nodes, heads)")
         if t.requires_grad:
             raise RuntimeError(f"{what}: {name} requires grad, and inference is forward only (detach it)")
-    if out_dtype not in _OUT_DTYPES:
-        raise ValueError(f"{what}: out_dtype must be torch.float32 or torch.bfloat16, got {out_dtype}")
-    slab = row0 is not None or num_targets is not None
-    if slab == (target_ids is not None):
-        raise ValueError(f"{what}: give the targets either as a slab (row0 and num_targets) or as target_ids"
-                         + (", not both" if slab else ""))
-    if slab:
-        if row0 is None or num_targets is None:
-            raise ValueError(f"{what}: a slab needs both row0 and num_targets")
-        row0, T = int(row0), int(num_targets)
-        if row0 < 0 or T < 0 or row0 + T > N:
-            raise ValueError(f"{what}: the slab [{row0}, {row0 + T}) leaves the graph's {N} nodes")
-    else:
-        if not isinstance(target_ids, torch.Tensor) or target_ids.dtype != torch.int64 or target_ids.dim() != 1 \
-                or not target_ids.is_contiguous():
-            raise ValueError(f"{what}: target_ids must be a contiguous 1-D int64 tensor")
-        row0, T = -1, target_ids.numel()
-    nat.require_device()
-    tensors = [h, a_src, a_dst, rowptr, col] + ([target_ids] if not slab else []) \
-        + ([workspace] if workspace is not None else [])
-    if not all(t.is_cuda and t.device == h.device for t in tensors):
-        raise ValueError(f"{what}: h, a_src, a_dst, rowptr, col, target_ids and workspace must live on one CUDA device")
-    nbytes = graph_gat_workspace_bytes(T)
-    if workspace is None:
-        workspace = torch.empty(nbytes, dtype=torch.uint8, device=h.device)
-    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < nbytes:
-        raise ValueError(f"{what}: workspace must be a contiguous uint8 tensor of at least {nbytes} bytes")
+    _check_out_dtype(what, out_dtype)
+    row0, target_ids, T = _check_targets(what, N, row0, num_targets, target_ids)
+    workspace = _on_device(what, "h, a_src, a_dst, rowptr, col, target_ids and workspace", h.device,
+                           [h, a_src, a_dst, rowptr, col, target_ids], workspace, graph_gat_workspace_bytes, T)
     out = torch.empty((T, Fdim), dtype=out_dtype, device=h.device)
-    return _gat_forward(h, a_src, a_dst, rowptr, col, heads, negative_slope, relu, row0, None if slab else target_ids,
-                        T, out, workspace)
-
-
-def _check_targets(what, N, row0, num_targets, target_ids):
-    """(slab?, row0 or -1, T) of the two target forms: a slab inside the graph's N nodes, or a contiguous int64 list"""
-    slab = row0 is not None or num_targets is not None
-    if slab == (target_ids is not None):
-        raise ValueError(f"{what}: give the targets either as a slab (row0 and num_targets) or as target_ids"
-                         + (", not both" if slab else ""))
-    if slab:
-        if row0 is None or num_targets is None:
-            raise ValueError(f"{what}: a slab needs both row0 and num_targets")
-        row0, T = int(row0), int(num_targets)
-        if row0 < 0 or T < 0 or row0 + T > N:
-            raise ValueError(f"{what}: the slab [{row0}, {row0 + T}) leaves the graph's {N} nodes")
-        return True, row0, T
-    if not isinstance(target_ids, torch.Tensor) or target_ids.dtype != torch.int64 or target_ids.dim() != 1 \
-            or not target_ids.is_contiguous():
-        raise ValueError(f"{what}: target_ids must be a contiguous 1-D int64 tensor")
-    return False, -1, target_ids.numel()
+    return _gat_launch(h, a_src, a_dst, rowptr, col, heads, negative_slope, relu, row0, target_ids, T, out, workspace)
 
 
 def graph_gat_aggregate_parts(h_parts, a_parts, part_offsets, rowptr, col, *, heads, negative_slope=0.2, relu=False,
@@ -383,9 +369,9 @@ def graph_gat_aggregate_parts(h_parts, a_parts, part_offsets, rowptr, col, *, he
     of a larger one allowed).  Nothing here maps memory or enables peer access, and nothing waits for the device."""
     what = "graph_gat_aggregate_parts"
     off = _check_offsets(part_offsets, what)
-    ptrs, stride, x_dtype, Fdim, dev = _parts_source(h_parts, off, dtype, F, what)
-    if not isinstance(heads, int) or heads < 1 or Fdim % heads != 0:
-        raise ValueError(f"{what}: heads must be a positive int that divides F = {Fdim}, got {heads!r}")
+    *src, dev = _parts_source(h_parts, off, dtype, F, what)
+    Fdim = src[3]
+    _check_heads(what, heads, Fdim)
     peer_logits = isinstance(a_parts, P2PPeers)
     a_ptrs, a_stride, a_dtype, a_width, a_dev = _parts_source(
         a_parts, off, torch.float32 if peer_logits else None, 2 * heads if peer_logits else None, what, "logits part")
@@ -397,46 +383,17 @@ def graph_gat_aggregate_parts(h_parts, a_parts, part_offsets, rowptr, col, *, he
     if dev is not None and a_dev is not None and dev != a_dev:
         raise ValueError(f"{what}: h_parts ({dev}) and a_parts ({a_dev}) live on different devices")
     dev = a_dev if dev is None else dev
-    N = off[-1]
-    for name, t in (("rowptr", rowptr), ("col", col)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be a contiguous 1-D int64 tensor")
-    if rowptr.numel() != N + 1:
-        raise ValueError(f"{what}: the parts hold {N} rows, the graph {rowptr.numel() - 1} nodes (one row per node)")
-    if out_dtype not in _OUT_DTYPES:
-        raise ValueError(f"{what}: out_dtype must be torch.float32 or torch.bfloat16, got {out_dtype}")
-    slab, row0, T = _check_targets(what, N, row0, num_targets, target_ids)
-    if out is not None:
-        if not isinstance(out, torch.Tensor) or out.dtype != out_dtype or tuple(out.shape) != (T, Fdim) \
-                or (Fdim > 1 and out.stride(1) != 1) or out.requires_grad:
-            raise ValueError(f"{what}: out must be a {out_dtype} matrix of shape [{T}, {Fdim}] with unit column stride "
-                             "that does not require grad")
-    nat.require_device()
+    _check_graph(what, off[-1], rowptr, col, parts=True)
+    _check_out_dtype(what, out_dtype)
+    row0, target_ids, T = _check_targets(what, off[-1], row0, num_targets, target_ids)
+    _check_out(what, out, out_dtype, T, Fdim)
     dev = rowptr.device if dev is None else dev
-    tensors = [rowptr, col] + [t for t in (None if slab else target_ids, workspace, out) if t is not None]
-    if dev.type != "cuda" or not all(t.is_cuda and t.device == dev for t in tensors):
-        raise ValueError(f"{what}: the parts, rowptr, col, target_ids, workspace and out must live on one CUDA device")
-    L = nat.load()
-    nbytes = int(L.spp_graph_gat_workspace_bytes(T))
-    if workspace is None:
-        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < nbytes:
-        raise ValueError(f"{what}: workspace must be a contiguous uint8 tensor of at least {nbytes} bytes")
+    workspace = _on_device(what, "the parts, rowptr, col, target_ids, workspace and out", dev,
+                           [rowptr, col, target_ids, out], workspace, graph_gat_workspace_bytes, T)
     if out is None:
         out = torch.empty((T, Fdim), dtype=out_dtype, device=dev)
-    d = nat.GraphGatPartsDesc(x_elem=_ELEM[x_dtype], out_elem=_ELEM[out_dtype], heads=heads, relu=int(bool(relu)),
-                              num_parts=len(off) - 1, rowptr_dev=_p(rowptr), col_dev=_p(col), x_stride_elems=stride,
-                              a_stride_elems=a_stride, F=Fdim, target_row0=row0,
-                              target_ids_dev=_p(target_ids) if not slab else None, num_targets=T, out_dev=_p(out),
-                              out_stride_elems=out.stride(0) if T > 1 else 0, negative_slope=float(negative_slope))
-    for p, v in enumerate(off):
-        d.part_offsets[p] = v
-    for p, (hv, av) in enumerate(zip(ptrs, a_ptrs)):
-        d.h_parts_dev[p], d.a_parts_dev[p] = hv or None, av or None
-    with torch.cuda.device(dev):
-        nat.check(L.spp_graph_gat_parts_forward(C.byref(d), C.c_void_p(workspace.data_ptr()), workspace.numel(),
-                                                _stream()))
-    return out
+    return _gat_parts_launch(src, (a_ptrs, a_stride), off, rowptr, col, heads, negative_slope, relu, row0, target_ids, T,
+                             out, workspace)
 
 
 def resinc_epilogue(z, scale, shift, *, negative_slope, residual=None, row0=None, row_ids=None, out=None,
@@ -487,8 +444,7 @@ def resinc_epilogue(z, scale, shift, *, negative_slope, residual=None, row0=None
             raise ValueError(f"{what}: row_ids must be a contiguous int64 tensor of shape [{n}] (one entry per row of z)")
     if out is None:
         out_dtype = torch.float32 if out_dtype is None else out_dtype
-        if out_dtype not in _OUT_DTYPES:
-            raise ValueError(f"{what}: out_dtype must be torch.float32 or torch.bfloat16, got {out_dtype}")
+        _check_out_dtype(what, out_dtype)
     else:
         if not isinstance(out, torch.Tensor) or out.dtype not in _OUT_DTYPES or tuple(out.shape) != (n, Cdim) \
                 or (Cdim > 1 and out.stride(1) != 1) or out.requires_grad:
@@ -535,6 +491,133 @@ def _row_tiles(A):
         yield r, n, tile
 
 
+def _tiles_contiguous(A):
+    """``_row_tiles`` with every tile contiguous: a full tile of a padded buffer is a strided view, and the GEMM's
+    operand layout is part of its shape (the resident matrices the drivers allocate are contiguous)"""
+    for r, n, tile in _row_tiles(A):
+        yield r, n, tile.contiguous()
+
+
+# ---- where the table lives: the two placements the drivers below are written against --------------------------------
+class _Resident:
+    """One rank owns the rows [0, N) of one matrix ``x``: the whole-table kernels, every layer in a matrix of its own
+    that is dropped when the next layer is complete, nothing to publish and nothing to wait for at a layer boundary"""
+    lo = 0
+    head_tiles = staticmethod(_row_tiles)                 # the tiles of a block of SAGEResInception's head, as they are
+
+    def __init__(self, x, rowptr, col):
+        self.x, self.rowptr, self.col = x, rowptr, col
+        self.n_local, self.dev = x.size(0), x.device
+
+    def bind(self):
+        pass
+
+    abort = close = boundary = bind
+
+    def local(self, ids):
+        """global ids as rows of the rank's own matrices"""
+        return ids
+
+    def open(self, n_bufs, width, dtype):
+        pass
+
+    open_gat = open
+
+    def layer_rows(self, i, last, rows, width, dtype):
+        """where layer i's rows go: [rows, width], read back as ``cur`` (and as the residual) by layer i + 1"""
+        return torch.empty((rows, width), dtype=dtype, device=self.dev)
+
+    def aggregate(self, i, cur, epilogue, self_scale, s, ids, T, out, ws):
+        """layer i's input ``cur`` aggregated for the rank's local slab [s, s + T), or for the global ``ids``"""
+        return _agg_launch(cur, self.rowptr, self.col, epilogue, self_scale, -1 if ids is not None else s, ids, T, out, ws)
+
+    def gat_rows(self, H, Cc, dtype):
+        """(h, logits) of a GAT layer: the projected rows [n_local, H * Cc] and where ``put_logits`` writes"""
+        h = torch.empty((self.n_local, H * Cc), dtype=dtype, device=self.dev)
+        return h, tuple(torch.empty((self.n_local, H), dtype=torch.float32, device=self.dev) for _ in range(2))
+
+    def put_logits(self, logits, r, n, a):
+        H = a.size(1) // 2
+        logits[0][r:r + n], logits[1][r:r + n] = a[:n, :H], a[:n, H:]
+
+    def attend(self, h, logits, conv, relu, s, ids, T, out, ws):
+        return _gat_launch(h, logits[0], logits[1], self.rowptr, self.col, conv.heads, conv.negative_slope, relu,
+                           -1 if ids is not None else s, ids, T, out, ws)
+
+
+class _Partitioned:
+    """Rank ``rank`` owns the rows [off[rank], off[rank + 1]) and reads the others' through ``peers``: the parts kernels
+    over buffers that are allocated up front, laid out by the resident tables' row-stride rule (one stride on every rank
+    whatever its row count: a one-row part has no stride of its own) and published once.  A layer boundary is a
+    synchronise of the rank's stream and a barrier: what was written is complete before any rank reads it, and every rank
+    has finished reading a buffer before it is written again (after the last layer: before anyone unmaps)."""
+    head_tiles = staticmethod(_tiles_contiguous)          # a full tile of a padded buffer is strided: the GEMM gets a copy
+
+    def __init__(self, what, x_local, rowptr, col, off, rank, peers):
+        self.what, self.x, self.rowptr, self.col, self.off, self.rank, self.peers = what, x_local, rowptr, col, off, rank, peers
+        self.lo, self.n_local, self.dev = off[rank], off[rank + 1] - off[rank], x_local.device
+        self.shared = []
+
+    def bind(self):
+        if hasattr(self.peers, "bind"):
+            self.peers.bind(self.rank)
+
+    def abort(self):
+        if hasattr(self.peers, "abort"):
+            self.peers.abort()
+
+    def close(self):
+        for sh in self.shared:
+            sh.close()
+
+    def boundary(self):
+        torch.cuda.current_stream(self.dev).synchronize()
+        self.peers.barrier()
+
+    def local(self, ids):
+        return ids - self.lo
+
+    def _buffer(self, width, dtype):
+        stride = _row_stride_elems(width, torch.empty(0, dtype=dtype).element_size())
+        return torch.empty((self.n_local, stride), dtype=dtype, device=self.dev)[:, :width]
+
+    def _share(self, t, name="part"):
+        """publish t (collective); its parts as the launch functions take them"""
+        self.shared.append(self.peers.share(t))
+        return _parts_source(self.shared[-1], self.off, t.dtype, t.size(1), self.what, name)[:4]
+
+    def open(self, n_bufs, width, dtype):
+        """SAGE, GIN, SAGEResInception: the table and the ping-pong activation buffers [n_local, width]"""
+        self.bufs = [self._buffer(width, dtype) for _ in range(n_bufs)]
+        self.sources = [self._share(t) for t in [self.x] + self.bufs]
+
+    def layer_rows(self, i, last, rows, width, dtype):
+        return torch.empty((rows, width), dtype=dtype, device=self.dev) if last else self.bufs[i % len(self.bufs)]
+
+    def aggregate(self, i, cur, epilogue, self_scale, s, ids, T, out, ws):
+        src = self.sources[0] if i == 0 else self.sources[1 + (i - 1) % len(self.bufs)]      # (``cur``, as published)
+        return _agg_parts_launch(src, self.off, self.rowptr, self.col, epilogue, self_scale,
+                                 -1 if ids is not None else self.lo + s, ids, T, out, ws)
+
+    def open_gat(self, Fmax, Hmax, dtype):
+        """GAT: h [n_local, max H * C] and the logits [n_local, 2 * max H] fp32 = [a_src | a_dst]; a layer narrower than
+        a buffer reads its leading columns at the buffer's stride.  Projection is local: the table is not published."""
+        self.hbuf, self.abuf = self._buffer(Fmax, dtype), self._buffer(2 * Hmax, torch.float32)
+        self.h_src, self.a_src = self._share(self.hbuf), self._share(self.abuf, "logits part")
+
+    def gat_rows(self, H, Cc, dtype):
+        return self.hbuf[:, :H * Cc], self.abuf[:, :2 * H]
+
+    def put_logits(self, logits, r, n, a):
+        logits[r:r + n] = a[:n]
+
+    def attend(self, h, logits, conv, relu, s, ids, T, out, ws):
+        return _gat_parts_launch(self.h_src[:2] + (h.dtype, h.size(1)), self.a_src[:2], self.off, self.rowptr, self.col,
+                                 conv.heads, conv.negative_slope, relu, -1 if ids is not None else self.lo + s, ids, T,
+                                 out, ws)
+
+
+# ---- the drivers: one layer loop per model, over a placement ---------------------------------------------------------
 def _sage_layer(conv, last, act_dtype):
     """(epilogue, self_scale, fn): fn maps a slab's fp32 / bf16 operand [T, 2K] to the layer's output rows"""
     W = torch.cat([conv.lin_l.weight, conv.lin_r.weight], dim=1).to(act_dtype)      # [N, 2K] = [W_l | W_r]
@@ -555,29 +638,82 @@ def _gin_layer(conv, amp):
     return "sum", conv._scale(), fn
 
 
-def _gat_inference(model, x, rowptr, col, nodes, rows_per_slab, act_dtype):
-    """layerwise_inference for GAT, in PyG's project-first order (training aggregates first, _GatLayer / _GatLayerMH,
-    because an MFG hop has many sources per target; over the whole graph T = S = N, that saving is gone, and the
-    aggregate-first intermediate would be [T, H, K] fp32 per slab).  Per layer:
+def _slabs(place, ids, rows_per_slab):
+    """(first row, rows, the slab's ids or None) over the rank's own rows, or over ``ids``"""
+    rows = ids.numel() if ids is not None else place.n_local
+    for s in range(0, rows, rows_per_slab):
+        e = min(rows, s + rows_per_slab)
+        yield s, e - s, ids[s:e] if ids is not None else None
 
-      project    h = cur @ W^T for all N rows, [N, H*C] in ``act_dtype``, over ``_row_tiles``
-      logits     [a_src | a_dst] = tile.float() @ V^T with V = W_h^T att (as _GatLayerMH builds it), fp32 [N, H] each:
+
+def _conv_layers(model, place, nodes, rows_per_slab, act_dtype):
+    """SAGE and GIN, as ``layerwise_inference`` describes them.  Resident, layer i-1's matrix is dropped as soon as layer
+    i is complete, so two [N, hidden] matrices are live at a boundary; partitioned, the layers alternate between the (at
+    most two) published buffers."""
+    from .models import GIN
+    gin, amp = isinstance(model, GIN), act_dtype == torch.bfloat16
+    n_layers, dev = len(model.convs), place.dev
+    place.open(min(2, n_layers - 1), model.hidden_channels, act_dtype)
+    ws = torch.empty(graph_agg_workspace_bytes(min(rows_per_slab, max(place.n_local, nodes.numel() if nodes is not None else 0))),
+                     dtype=torch.uint8, device=dev)
+
+    def head(h):                                         # what follows the last conv layer, fp32 log-probabilities
+        if gin:
+            with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+                h = model.lin2(torch.relu(model.lin1(h)))
+        return torch.log_softmax(h, dim=-1, dtype=torch.float32)
+
+    cur = place.x
+    for i, conv in enumerate(model.convs):
+        last = i == n_layers - 1
+        epilogue, scale, fn = _gin_layer(conv, amp) if gin else _sage_layer(conv, last, act_dtype)
+        ids = nodes if last else None
+        rows = ids.numel() if ids is not None else place.n_local
+        out_dtype = torch.float32 if last else act_dtype
+        nxt = None
+        for s, T, tids in _slabs(place, ids, rows_per_slab):
+            A = torch.empty((T, cur.size(1) * (2 if epilogue == "operand" else 1)), dtype=act_dtype, device=dev)
+            place.aggregate(i, cur, epilogue, scale, s, tids, T, A, ws)
+            for r, n, tile in _row_tiles(A):
+                h = head(fn(tile)) if last else fn(tile)
+                if nxt is None:
+                    nxt = place.layer_rows(i, last, rows, h.size(1), out_dtype)
+                nxt[s + r:s + r + n] = h[:n]
+        if nxt is None:                                  # no rows at all
+            width = (model.lin2 if gin else conv.lin_l).out_features if last else model.hidden_channels
+            nxt = place.layer_rows(i, last, 0, width, out_dtype)
+        cur = nxt                                        # (resident: drops layer i-1's matrix)
+        place.boundary()
+    return cur
+
+
+def _gat_layers(model, place, nodes, rows_per_slab, act_dtype):
+    """GAT, in PyG's project-first order (training aggregates first, _GatLayer / _GatLayerMH, because an MFG hop has
+    many sources per target; over the whole graph T = S = N, that saving is gone, and the aggregate-first intermediate
+    would be [T, H, K] fp32 per slab).  Per layer:
+
+      project    h = cur @ W^T for all the rank's rows, [n, H*C] in ``act_dtype``, over ``_row_tiles``
+      logits     [a_src | a_dst] = tile.float() @ V^T with V = W_h^T att (as _GatLayerMH builds it), fp32 [n, H] each:
                  taken from the layer's input rows, never from the rounded h
-      aggregate  ``spp_graph_gat_forward`` slab by slab over each node's whole row; hidden layers through the fused ReLU
-                 straight into the next [N, hidden] matrix, the last layer ([T, H*classes] fp32 per slab) through the
+      aggregate  the attention kernel slab by slab over each node's whole row; hidden layers through the fused ReLU
+                 straight into the next [n, hidden] matrix, the last layer ([T, H*classes] fp32 per slab) through the
                  mean over its heads and log_softmax(dtype=float32)
 
-    Memory, as arithmetic: ``cur`` is dropped once ``h`` is complete and ``h`` once ``nxt`` is, so two [N, hidden]
-    matrices of ``act_dtype`` are live at a time, as for SAGE (57 GB each in bf16 at N = 111 M, hidden 256; layer 1's
-    ``cur`` is the resident table and stays), plus the logits, 2 * N * H * 4 bytes (3.6 GB at H = 4).  The one case
-    worse than SAGE: the last layer's h is [N, H * classes], so H > 1 heads multiply it -- 111 M * 4 * 172 * 2 bytes =
-    153 GB in bf16 for H = 4 and 172 classes, which does not fit next to a 57 GB ``cur``, 26 GB of graph and 28 GB of
-    features on one 288 GB MI355X.  The reference's model has H = 1 (38 GB)."""
-    N, dev = x.size(0), x.device
-    n_layers = len(model.convs)
-    ws = torch.empty(graph_gat_workspace_bytes(min(rows_per_slab, max(N, nodes.numel() if nodes is not None else 0))),
+    Partitioned, projection and logits are LOCAL (a rank's own rows of the layer's input), so no rank reads a peer's
+    feature rows; h and the logits are the two published buffers, and a layer has two boundaries: every rank's h and
+    logits are complete before anyone attends, and everyone has finished reading h before the next layer overwrites it.
+
+    Memory, as arithmetic (resident): ``cur`` is dropped once ``h`` is complete and ``h`` once ``nxt`` is, so two
+    [N, hidden] matrices of ``act_dtype`` are live at a time, as for SAGE (57 GB each in bf16 at N = 111 M, hidden 256;
+    layer 1's ``cur`` is the resident table and stays), plus the logits, 2 * N * H * 4 bytes (3.6 GB at H = 4).  The one
+    case worse than SAGE: the last layer's h is [N, H * classes], so H > 1 heads multiply it -- 111 M * 4 * 172 * 2 bytes
+    = 153 GB in bf16 for H = 4 and 172 classes, which does not fit next to a 57 GB ``cur``, 26 GB of graph and 28 GB of
+    features on one 288 GB MI355X.  The reference's model has H = 1 (38 GB).  Partitioned: ``partitioned_inference``."""
+    n_layers, dev = len(model.convs), place.dev
+    place.open_gat(max(c.heads * c.out_channels for c in model.convs), max(c.heads for c in model.convs), act_dtype)
+    ws = torch.empty(graph_gat_workspace_bytes(min(rows_per_slab, max(place.n_local, nodes.numel() if nodes is not None else 0))),
                      dtype=torch.uint8, device=dev)
-    cur = x
+    cur = place.x
     for i, conv in enumerate(model.convs):
         last = i == n_layers - 1
         H, Cc = conv.heads, conv.out_channels
@@ -585,27 +721,24 @@ def _gat_inference(model, x, rowptr, col, nodes, rows_per_slab, act_dtype):
         att = torch.stack([conv.att_src.view(H, Cc), conv.att_dst.view(H, Cc)]).to(torch.float32)
         V = torch.einsum("shc,hck->shk", att, W.to(torch.float32).view(H, Cc, -1)).reshape(2 * H, -1)   # [V_src; V_dst]
         Wt, Vt = W.to(act_dtype).t(), V.t().contiguous()
-        h = torch.empty((N, H * Cc), dtype=act_dtype, device=dev)
-        a_src, a_dst = (torch.empty((N, H), dtype=torch.float32, device=dev) for _ in range(2))
+        h, logits = place.gat_rows(H, Cc, act_dtype)
         for r, n, tile in _row_tiles(cur):
             h[r:r + n] = (tile.to(act_dtype) @ Wt)[:n]
-            a = tile.to(torch.float32) @ Vt
-            a_src[r:r + n], a_dst[r:r + n] = a[:n, :H], a[:n, H:]
+            place.put_logits(logits, r, n, tile.to(torch.float32) @ Vt)
         del cur                                          # (layer i-1's matrix; layer 1's is the caller's table)
+        place.boundary()                                 # every rank's h and logits of this layer are complete
         ids = nodes if last else None
-        rows = ids.numel() if ids is not None else N
-        width = Cc if last else H * Cc
-        nxt = torch.empty((rows, width), dtype=torch.float32 if last else act_dtype, device=dev)
-        for s in range(0, rows, rows_per_slab):
-            e = min(rows, s + rows_per_slab)
-            row0, tids = (-1, ids[s:e]) if ids is not None else (s, None)
-            out = nxt[s:e] if not last else torch.empty((e - s, H * Cc), dtype=torch.float32, device=dev)
-            _gat_forward(h, a_src, a_dst, rowptr, col, H, conv.negative_slope, not last, row0, tids, e - s, out, ws)
+        rows = ids.numel() if ids is not None else place.n_local
+        nxt = torch.empty((rows, Cc if last else H * Cc), dtype=torch.float32 if last else act_dtype, device=dev)
+        for s, T, tids in _slabs(place, ids, rows_per_slab):
+            out = nxt[s:s + T] if not last else torch.empty((T, H * Cc), dtype=torch.float32, device=dev)
+            place.attend(h, logits, conv, not last, s, tids, T, out, ws)
             if last:                                     # concat=False: the mean of the heads (H = 1: the head itself)
-                nxt[s:e] = torch.log_softmax(out.view(e - s, H, Cc).mean(1) if H > 1 else out, dim=-1,
-                                             dtype=torch.float32)
-        cur = nxt                                        # (drops h)
-        del h, a_src, a_dst
+                nxt[s:s + T] = torch.log_softmax(out.view(T, H, Cc).mean(1) if H > 1 else out, dim=-1,
+                                                 dtype=torch.float32)
+        cur = nxt
+        del h, logits                                    # (resident: drops them)
+        place.boundary()                                 # every rank has finished reading this layer's h
     return cur
 
 
@@ -618,37 +751,43 @@ def _resinc_head(model):
     return mods
 
 
-def _resinc_inference(model, x, rowptr, col, nodes, rows_per_slab, act_dtype):
-    """layerwise_inference for SAGEResInception.  In eval mode dropout is the identity and the model is
+def _resinc_layers(model, place, nodes, rows_per_slab, act_dtype):
+    """SAGEResInception.  In eval mode dropout is the identity and the model is
 
       layer i    h_i = leaky_relu(BatchNorm_i([mean | h_{i-1}] @ [W_l | W_r]^T)) + res_i,   h_0 = x,
-                 res_1 = res_linears[0](x), res_i = h_{i-1} after; per slab ``graph_aggregate`` ("operand"), per fixed
-                 GEMM tile one product and one ``resinc_epilogue`` that writes the tile's rows of the next [N, hidden]
-                 matrix.  Layer 1's residual Linear is stacked into the same product ([0 | W_res] below [W_l | W_r], so
-                 the tile is [z | res]); later residuals are the rows of ``cur`` itself, read in place by slab or, on the
-                 last layer with ``nodes``, by the id list.
+                 res_1 = res_linears[0](x), res_i = h_{i-1} after; per slab one aggregation ("operand"), per fixed GEMM
+                 tile one product and one ``resinc_epilogue`` that writes the tile's rows of the next [n, hidden] matrix.
+                 Layer 1's residual Linear is stacked into the same product ([0 | W_res] below [W_l | W_r], so the tile
+                 is [z | res]); later residuals are the rows of ``cur`` itself -- the rank's OWN previous matrix -- read
+                 in place by local slab or, on the last layer with ``nodes``, by the local id list.
       head       log_softmax(lin2(lin1(cat(x, h_1, .., h_L)))).  lin1 is a bare Linear, so lin1(cat(..)) is
                  bias + sum_k block_k @ W1[:, block k]^T: an fp32 accumulator ``acc`` [rows, 2 * classes] takes every
                  block's product when the block is complete, and no layer's matrix outlives the next layer.
 
-    Memory, as arithmetic: two [N, hidden] matrices of ``act_dtype`` at a layer boundary, as for SAGE, plus ``acc``:
-    4 * rows * 2 * classes bytes.  For all N = 111 M nodes and 172 classes that is 153 GB, which does not fit beside
-    2 * 57 + 26 + 28 = 168 GB on one 288 GB MI355X: ``nodes=`` is the papers-scale form."""
+    Everything behind the aggregation is local to a rank; partitioned, the table and the ping-pong [n_local, hidden]
+    buffers are published, one boundary a layer.
+
+    Memory, as arithmetic (resident): two [N, hidden] matrices of ``act_dtype`` at a layer boundary, as for SAGE, plus
+    ``acc``: 4 * rows * 2 * classes bytes.  For all N = 111 M nodes and 172 classes that is 153 GB, which does not fit
+    beside 2 * 57 + 26 + 28 = 168 GB on one 288 GB MI355X: ``nodes=`` is the papers-scale form."""
     lin1, lin2 = _resinc_head(model)
-    N, dev = x.size(0), x.device
+    x, dev = place.x, place.dev
     n_layers, hidden = len(model.convs), model.hidden_channels
-    rows_out = nodes.numel() if nodes is not None else N
-    ws = torch.empty(graph_agg_workspace_bytes(min(rows_per_slab, max(N, rows_out))), dtype=torch.uint8, device=dev)
+    place.open(min(2, n_layers - 1), hidden, act_dtype)
+    rows_out = nodes.numel() if nodes is not None else place.n_local
+    local = place.local(nodes) if nodes is not None else None         # the rank's own rows of ``nodes``
+    ws = torch.empty(graph_agg_workspace_bytes(min(rows_per_slab, max(place.n_local, rows_out))), dtype=torch.uint8,
+                     device=dev)
     acc = torch.zeros((rows_out, lin1.out_features), dtype=torch.float32, device=dev)
     if lin1.bias is not None:
         acc += lin1.bias.to(torch.float32)
 
     def add_block(block, first_col):                     # acc += block @ W1[:, its columns]^T, over the fixed tiles
         Wb = lin1.weight[:, first_col:first_col + block.size(1)].to(act_dtype).t()
-        for r, n, tile in _row_tiles(block):
+        for r, n, tile in place.head_tiles(block):
             acc[r:r + n] += (tile.to(act_dtype) @ Wb)[:n]
 
-    add_block(x if nodes is None else x[nodes], 0)
+    add_block(x if local is None else x[local], 0)
     cur = x
     for i, (conv, bn) in enumerate(zip(model.convs, model.bns)):
         last = i == n_layers - 1
@@ -666,23 +805,22 @@ def _resinc_inference(model, x, rowptr, col, nodes, rows_per_slab, act_dtype):
         Wt = W.to(act_dtype).t()
         bias = bias.to(act_dtype) if bias is not None else None
         ids = nodes if last else None
-        rows = ids.numel() if ids is not None else N
-        nxt = torch.empty((rows, hidden), dtype=act_dtype, device=dev)
-        for s in range(0, rows, rows_per_slab):
-            e = min(rows, s + rows_per_slab)
-            tgt = dict(target_ids=ids[s:e]) if ids is not None else dict(row0=s, num_targets=e - s)
-            A = graph_aggregate(cur, rowptr, col, epilogue="operand", out_dtype=act_dtype, workspace=ws, **tgt)
+        nxt = place.layer_rows(i, last, ids.numel() if ids is not None else place.n_local, hidden, act_dtype)
+        for s, T, tids in _slabs(place, ids, rows_per_slab):
+            A = torch.empty((T, 2 * cur.size(1)), dtype=act_dtype, device=dev)
+            place.aggregate(i, cur, "operand", 0.0, s, tids, T, A, ws)
             for r, n, tile in _row_tiles(A):
                 Z = torch.addmm(bias, tile, Wt) if bias is not None else tile @ Wt
                 if Z.size(1) > hidden:
                     residual = dict(residual=Z[:, hidden:], row0=0)
                 elif ids is not None:
-                    residual = dict(residual=cur, row_ids=ids[s + r:s + r + n])
+                    residual = dict(residual=cur, row_ids=local[s + r:s + r + n])
                 else:
                     residual = dict(residual=cur, row0=s + r)
                 resinc_epilogue(Z[:n, :hidden], a, b, negative_slope=0.01, out=nxt[s + r:s + r + n], **residual)
-        add_block(nxt if last or nodes is None else nxt[nodes], x.size(1) + i * hidden)
-        cur = nxt                                        # (drops layer i-1's matrix)
+        add_block(nxt if last or local is None else nxt[local], x.size(1) + i * hidden)
+        cur = nxt                                        # (resident: drops layer i-1's matrix)
+        place.boundary()
     W2t = lin2.weight.to(act_dtype).t()
     b2 = lin2.bias.to(act_dtype) if lin2.bias is not None else None
     out = torch.empty((rows_out, lin2.out_features), dtype=torch.float32, device=dev)
@@ -693,9 +831,11 @@ def _resinc_inference(model, x, rowptr, col, nodes, rows_per_slab, act_dtype):
     return out
 
 
-def _check_model_shape(model, what):
-    """what the GAT and SAGEResInception drivers need of the model's layers (SAGE and GIN: nothing)"""
-    from .models import GAT, SAGEResInception
+def _check_model(model, what, names):
+    """one of the four models, with what the GAT and SAGEResInception drivers need of its layers (SAGE and GIN: nothing)"""
+    from .models import GAT, GIN, SAGE, SAGEResInception
+    if not isinstance(model, (SAGE, GIN, GAT, SAGEResInception)):
+        raise NotImplementedError(f"{what}: implemented for {names}, not {type(model).__name__}")
     if isinstance(model, SAGEResInception):
         _resinc_head(model)
     if isinstance(model, GAT):                                # the layers as models.GAT builds them
@@ -706,35 +846,8 @@ def _check_model_shape(model, what):
                                           "multi-head model only")
 
 
-def layerwise_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 << 20, act_dtype=torch.float32):
-    """Exact log-probabilities of every node, [N, classes] fp32 -- or of ``nodes`` (int64, any order, duplicates
-    allowed), [len(nodes), classes] -- for a ``SAGE``, ``GIN``, ``GAT`` or ``SAGEResInception`` model over the whole
-    graph.  (GAT, at any ``heads``: see ``_gat_inference`` for its order of operations and memory; SAGEResInception:
-    ``_resinc_inference``; what follows describes SAGE and GIN, and the arguments, the fixed GEMM tiles, eval mode and
-    ``nodes`` mean the same for all four.)
-
-    Layer by layer, slab by slab of ``rows_per_slab`` nodes: ``graph_aggregate`` over each node's whole neighbour row,
-    then the layer's own parameters as torch GEMMs (SAGE: [mean | x] @ [W_l | W_r]^T; GIN: ``conv.nn`` with BatchNorm's
-    running statistics), written -- SAGE: through the ReLU -- into the next [N, hidden] activation matrix of dtype
-    ``act_dtype``.  The GEMMs run over row tiles of one fixed height, so a node's result is the same bits whatever the
-    slab size and whether ``nodes`` selected it.  With ``act_dtype=torch.bfloat16`` operands, weights and activations are bf16 as under
-    ``torch.autocast`` in training (fp32 sums, fp32 log_softmax).  With ``nodes`` the last conv layer, GIN's head and
-    the log_softmax are computed for those nodes only.  The model is put in eval mode and its mode restored; nothing
-    records a gradient.  ``x``: a CUDA fp16 / fp32 / bf16 matrix, one row per node, possibly a strided view of the
-    resident table (``FastSampler.resident_graph()``).
-
-    Memory, as arithmetic: an activation matrix is N * hidden * sizeof(act_dtype) bytes and two are live at a layer
-    boundary (layer i-1's is freed as soon as layer i is complete).  At N = 111 M and hidden 256 that is 113 GB each in
-    fp32 and 57 GB in bf16, next to 26 GB of graph and 28 GB of features: fp32 activations do not fit one 288 GB MI355X
-    at papers scale, ``act_dtype=torch.bfloat16`` does (26 + 28 + 2 * 57 = 168 GB)."""
-    from .models import GAT, GIN, SAGE, SAGEResInception
-    what = "layerwise_inference"
-    if not isinstance(model, (SAGE, GIN, GAT, SAGEResInception)):
-        raise NotImplementedError(f"{what}: implemented for SAGE and GIN (and GAT, SAGEResInception), not "
-                                  f"{type(model).__name__}")
-    _check_model_shape(model, what)
-    _check_matrix(x, what)
-    _check_graph(x, rowptr, col, what)
+def _check_run(what, act_dtype, rows_per_slab, nodes):
+    """the drivers' own arguments; returns rows_per_slab as an int"""
     if act_dtype not in _OUT_DTYPES:
         raise ValueError(f"{what}: act_dtype must be torch.float32 or torch.bfloat16, got {act_dtype}")
     rows_per_slab = int(rows_per_slab)
@@ -742,59 +855,65 @@ def layerwise_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 <<
         raise ValueError(f"{what}: rows_per_slab must be positive, got {rows_per_slab}")
     if nodes is not None and (not isinstance(nodes, torch.Tensor) or nodes.dtype != torch.int64 or nodes.dim() != 1):
         raise ValueError(f"{what}: nodes must be a 1-D int64 tensor")
+    return rows_per_slab
+
+
+def _score(model, place, nodes, rows_per_slab, act_dtype):
+    """the frame of every driver: eval mode (restored), no gradient, autocast off, the table's device current; a rank
+    that fails aborts the placement, so that its peers raise instead of waiting, and every mapping is closed"""
+    from .models import GAT, SAGEResInception
+    layers = _gat_layers if isinstance(model, GAT) else _resinc_layers if isinstance(model, SAGEResInception) \
+        else _conv_layers
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad(), torch.autocast("cuda", enabled=False), torch.cuda.device(place.dev):
+            place.bind()
+            return layers(model, place, nodes, rows_per_slab, act_dtype)
+    except BaseException:
+        place.abort()
+        raise
+    finally:
+        place.close()
+        model.train(was_training)
+
+
+def layerwise_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 << 20, act_dtype=torch.float32):
+    """Exact log-probabilities of every node, [N, classes] fp32 -- or of ``nodes`` (int64, any order, duplicates
+    allowed), [len(nodes), classes] -- for a ``SAGE``, ``GIN``, ``GAT`` or ``SAGEResInception`` model over the whole
+    graph.  (GAT, at any ``heads``: see ``_gat_layers`` for its order of operations and memory; SAGEResInception:
+    ``_resinc_layers``; what follows describes SAGE and GIN, ``_conv_layers``, and the arguments, the fixed GEMM tiles,
+    eval mode and ``nodes`` mean the same for all four.)
+
+    Layer by layer, slab by slab of ``rows_per_slab`` nodes: ``spp_graph_agg_forward`` over each node's whole neighbour
+    row, then the layer's own parameters as torch GEMMs (SAGE: [mean | x] @ [W_l | W_r]^T; GIN: ``conv.nn`` with
+    BatchNorm's running statistics), written -- SAGE: through the ReLU -- into the next [N, hidden] activation matrix of
+    dtype ``act_dtype``.  The GEMMs run over row tiles of one fixed height, so a node's result is the same bits whatever
+    the slab size and whether ``nodes`` selected it.  With ``act_dtype=torch.bfloat16`` operands, weights and activations
+    are bf16 as under ``torch.autocast`` in training (fp32 sums, fp32 log_softmax).  With ``nodes`` the last conv layer,
+    GIN's head and the log_softmax are computed for those nodes only.  The model is put in eval mode and its mode
+    restored; nothing records a gradient.  ``x``: a CUDA fp16 / fp32 / bf16 matrix, one row per node, possibly a strided
+    view of the resident table (``FastSampler.resident_graph()``).  Nothing waits for the device but the range check of
+    ``nodes``, up front.
+
+    Memory, as arithmetic: an activation matrix is N * hidden * sizeof(act_dtype) bytes and two are live at a layer
+    boundary (layer i-1's is freed as soon as layer i is complete).  At N = 111 M and hidden 256 that is 113 GB each in
+    fp32 and 57 GB in bf16, next to 26 GB of graph and 28 GB of features: fp32 activations do not fit one 288 GB MI355X
+    at papers scale, ``act_dtype=torch.bfloat16`` does (26 + 28 + 2 * 57 = 168 GB)."""
+    what = "layerwise_inference"
+    _check_model(model, what, "SAGE and GIN (and GAT, SAGEResInception)")
+    _check_matrix(x, what)
+    N = x.size(0)
+    _check_graph(what, N, rowptr, col)
+    rows_per_slab = _check_run(what, act_dtype, rows_per_slab, nodes)
     nat.require_device()
     if not (x.is_cuda and rowptr.device == x.device and col.device == x.device):
         raise ValueError(f"{what}: x, rowptr and col must live on one CUDA device")
-    N = x.size(0)
     if nodes is not None:
         nodes = nodes.to(x.device).contiguous()
         if nodes.numel() and not (0 <= int(nodes.min()) and int(nodes.max()) < N):      # (one read-back, up front)
             raise ValueError(f"{what}: nodes outside the graph's {N} nodes")
-    amp = act_dtype == torch.bfloat16
-    gin = isinstance(model, GIN)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad(), torch.autocast("cuda", enabled=False):
-            if isinstance(model, GAT):
-                return _gat_inference(model, x, rowptr, col, nodes, rows_per_slab, act_dtype)
-            if isinstance(model, SAGEResInception):
-                return _resinc_inference(model, x, rowptr, col, nodes, rows_per_slab, act_dtype)
-            n_layers = len(model.convs)
-            ws = torch.empty(graph_agg_workspace_bytes(min(rows_per_slab, max(N, nodes.numel() if nodes is not None else 0))),
-                             dtype=torch.uint8, device=x.device)
-
-            def head(h):                                 # what follows the last conv layer, fp32 log-probabilities
-                if gin:
-                    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
-                        h = model.lin2(torch.relu(model.lin1(h)))
-                return torch.log_softmax(h, dim=-1, dtype=torch.float32)
-
-            cur = x
-            for i, conv in enumerate(model.convs):
-                last = i == n_layers - 1
-                epilogue, scale, fn = _gin_layer(conv, amp) if gin else _sage_layer(conv, last, act_dtype)
-                ids = nodes if last else None
-                rows = ids.numel() if ids is not None else N
-                nxt = None
-                for s in range(0, rows, rows_per_slab):
-                    e = min(rows, s + rows_per_slab)
-                    tgt = dict(target_ids=ids[s:e]) if ids is not None else dict(row0=s, num_targets=e - s)
-                    A = graph_aggregate(cur, rowptr, col, epilogue=epilogue, self_scale=scale, out_dtype=act_dtype,
-                                        workspace=ws, **tgt)
-                    for r, n, tile in _row_tiles(A):
-                        h = head(fn(tile)) if last else fn(tile)
-                        if nxt is None:
-                            nxt = torch.empty((rows, h.size(1)), dtype=torch.float32 if last else act_dtype,
-                                              device=x.device)
-                        nxt[s + r:s + r + n] = h[:n]
-                if nxt is None:                          # no rows at all
-                    width = (model.lin2 if gin else conv.lin_l).out_features if last else model.hidden_channels
-                    nxt = torch.empty((0, width), dtype=torch.float32 if last else act_dtype, device=x.device)
-                cur = nxt                                # (drops layer i-1's matrix)
-            return cur
-    finally:
-        model.train(was_training)
+    return _score(model, _Resident(x, rowptr, col), nodes, rows_per_slab, act_dtype)
 
 
 class LocalPeers:
@@ -868,9 +987,10 @@ class IpcPeers:
         pass
 
 
-def _check_partitioned(what, x_local, rowptr, col, part_offsets, rank, peers, nodes, rows_per_slab, act_dtype):
-    """the arguments every partitioned driver shares, checked before ``peers`` is touched; the device is required last.
-    Returns (offsets as a list, rank, nodes on the device or None, rows_per_slab)"""
+def _partitioned(what, names, model, x_local, rowptr, col, part_offsets, rank, peers, nodes, rows_per_slab, act_dtype):
+    """the partitioned entries behind their model filters.  Every argument and model-shape check comes before ``peers``
+    is touched, and the device is required last: a refused call publishes nothing and waits for nobody."""
+    _check_model(model, what, names)
     _check_matrix(x_local, what, "x_local")
     off = _check_offsets(part_offsets, what)
     P = len(off) - 1
@@ -878,24 +998,12 @@ def _check_partitioned(what, x_local, rowptr, col, part_offsets, rank, peers, no
     if not 0 <= rank < P:
         raise ValueError(f"{what}: rank {rank} outside the {P} parts")
     lo, hi = off[rank], off[rank + 1]
-    n_local, N = hi - lo, off[-1]
-    if x_local.size(0) != n_local:
-        raise ValueError(f"{what}: x_local has {x_local.size(0)} rows, part_offsets gives rank {rank} {n_local}")
-    for name, t in (("rowptr", rowptr), ("col", col)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be a contiguous 1-D int64 tensor")
-    if rowptr.numel() != N + 1:
-        raise ValueError(f"{what}: the parts hold {N} rows, the graph {rowptr.numel() - 1} nodes (one row per node)")
-    if act_dtype not in _OUT_DTYPES:
-        raise ValueError(f"{what}: act_dtype must be torch.float32 or torch.bfloat16, got {act_dtype}")
-    rows_per_slab = int(rows_per_slab)
-    if rows_per_slab < 1:
-        raise ValueError(f"{what}: rows_per_slab must be positive, got {rows_per_slab}")
-    if nodes is not None:
-        if not isinstance(nodes, torch.Tensor) or nodes.dtype != torch.int64 or nodes.dim() != 1:
-            raise ValueError(f"{what}: nodes must be a 1-D int64 tensor")
-        if nodes.numel() and not (lo <= int(nodes.min()) and int(nodes.max()) < hi):     # (one read-back, up front)
-            raise ValueError(f"{what}: nodes outside rank {rank}'s range [{lo}, {hi}) (global ids; every rank scores its own)")
+    if x_local.size(0) != hi - lo:
+        raise ValueError(f"{what}: x_local has {x_local.size(0)} rows, part_offsets gives rank {rank} {hi - lo}")
+    _check_graph(what, off[-1], rowptr, col, parts=True)
+    rows_per_slab = _check_run(what, act_dtype, rows_per_slab, nodes)
+    if nodes is not None and nodes.numel() and not (lo <= int(nodes.min()) and int(nodes.max()) < hi):
+        raise ValueError(f"{what}: nodes outside rank {rank}'s range [{lo}, {hi}) (global ids; every rank scores its own)")
     for name in ("share", "barrier", "close"):
         if not callable(getattr(peers, name, None)):
             raise TypeError(f"{what}: peers must provide share(tensor), barrier() and close()")
@@ -905,245 +1013,7 @@ def _check_partitioned(what, x_local, rowptr, col, part_offsets, rank, peers, no
         raise ValueError(f"{what}: x_local, rowptr and col must live on one CUDA device")
     if nodes is not None:
         nodes = nodes.to(dev).contiguous()
-    return off, rank, nodes, rows_per_slab
-
-
-def partitioned_layerwise_inference(model, x_local, rowptr, col, *, part_offsets, rank, peers, nodes=None,
-                                    rows_per_slab=1 << 20, act_dtype=torch.float32):
-    """``layerwise_inference`` for SAGE and GIN when the feature table is row-partitioned over the ranks: every rank calls
-    this with its own partition ``x_local`` (the global rows [part_offsets[rank], part_offsets[rank + 1])), the WHOLE
-    graph's CSR (global ids) and the same ``model``, and gets the fp32 log-probabilities of ITS node range,
-    [n_local, classes] -- or of ``nodes`` (global ids, all inside the rank's range).  The bits are those of
-    ``layerwise_inference`` over the concatenated table, rows [part_offsets[rank], part_offsets[rank + 1]).
-
-    Per rank: the ping-pong activation buffers [n_local, hidden] of ``act_dtype`` are allocated up front (one for a
-    two-layer model) and published with ``x_local`` once through ``peers``; each layer aggregates the rank's own slabs with
-    ``graph_aggregate_parts`` over ALL ranks' previous-layer parts, runs the layer's parameters over the same fixed GEMM
-    tiles as ``layerwise_inference`` and writes its rows of the next layer into its own buffer; then the rank synchronises
-    its stream and waits in ``peers.barrier()`` before anyone reads the layer or reuses a buffer.  After the last barrier
-    the mappings are closed.
-
-    ``peers``: ``share(tensor) -> P2PPeers`` (collective, same order on every rank), ``barrier()``, ``close()``; optional
-    ``bind(rank)`` and ``abort()``.  ``LocalPeers`` and ``IpcPeers`` are the two implementations.  GAT and
-    SAGEResInception are refused here and scored by ``partitioned_inference``, the entry for all four models.
-
-    Memory, as arithmetic (S-mag, N = 121.8 M, F = 768 fp16, hidden 256, bf16): per rank of P, 187 / P GB of table and
-    2 * 62 / P GB of activations next to its copy of the 22 GB graph."""
-    from .models import GAT, GIN, SAGE, SAGEResInception
-    what = "partitioned_layerwise_inference"
-    if isinstance(model, (GAT, SAGEResInception)):
-        raise NotImplementedError(f"{what}: {type(model).__name__} over a partitioned table is not scored by this entry "
-                                  "(its layers need the long-row softmax / the fused layer tail over parts); SAGE and GIN "
-                                  "are.  partitioned_inference scores all four models")
-    if not isinstance(model, (SAGE, GIN)):
-        raise NotImplementedError(f"{what}: implemented for SAGE and GIN, not {type(model).__name__}")
-    off, rank, nodes, rows_per_slab = _check_partitioned(what, x_local, rowptr, col, part_offsets, rank, peers, nodes,
-                                                         rows_per_slab, act_dtype)
-    lo, n_local, dev = off[rank], off[rank + 1] - off[rank], x_local.device
-    amp = act_dtype == torch.bfloat16
-    gin = isinstance(model, GIN)
-    n_layers, hidden = len(model.convs), model.hidden_channels
-    was_training = model.training
-    model.eval()
-    shared = []
-    try:
-        with torch.no_grad(), torch.autocast("cuda", enabled=False), torch.cuda.device(dev):
-            if hasattr(peers, "bind"):
-                peers.bind(rank)
-            # the buffers follow the resident tables' row-stride rule, so that every rank's have one stride whatever its
-            # row count (a one-row part has no stride of its own)
-            esize = torch.empty(0, dtype=act_dtype).element_size()
-            se = _row_stride_elems(hidden, esize)
-            bufs = [torch.empty((n_local, se), dtype=act_dtype, device=dev)[:, :hidden] for _ in range(min(2, n_layers - 1))]
-            shared = [(peers.share(x_local), x_local.dtype, x_local.size(1))]
-            shared += [(peers.share(b), act_dtype, hidden) for b in bufs]
-            rows_out = nodes.numel() if nodes is not None else n_local
-            ws = torch.empty(graph_agg_workspace_bytes(min(rows_per_slab, max(n_local, rows_out))), dtype=torch.uint8,
-                             device=dev)
-
-            def head(h):                                 # what follows the last conv layer, fp32 log-probabilities
-                if gin:
-                    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
-                        h = model.lin2(torch.relu(model.lin1(h)))
-                return torch.log_softmax(h, dim=-1, dtype=torch.float32)
-
-            result = None
-            for i, conv in enumerate(model.convs):
-                last = i == n_layers - 1
-                epilogue, scale, fn = _gin_layer(conv, amp) if gin else _sage_layer(conv, last, act_dtype)
-                src, src_dtype, src_F = shared[0] if i == 0 else shared[1 + (i - 1) % len(bufs)]
-                ids = nodes if last else None
-                rows = ids.numel() if ids is not None else n_local
-                nxt = None if last else bufs[i % len(bufs)]
-                for s in range(0, rows, rows_per_slab):
-                    e = min(rows, s + rows_per_slab)
-                    tgt = dict(target_ids=ids[s:e]) if ids is not None else dict(row0=lo + s, num_targets=e - s)
-                    A = graph_aggregate_parts(src, off, rowptr, col, dtype=src_dtype, F=src_F, epilogue=epilogue,
-                                              self_scale=scale, out_dtype=act_dtype, workspace=ws, **tgt)
-                    for r, n, tile in _row_tiles(A):
-                        h = head(fn(tile)) if last else fn(tile)
-                        if nxt is None:
-                            nxt = torch.empty((rows, h.size(1)), dtype=torch.float32, device=dev)
-                        nxt[s + r:s + r + n] = h[:n]
-                if last:
-                    if nxt is None:                      # no rows at all
-                        width = (model.lin2 if gin else conv.lin_l).out_features
-                        nxt = torch.empty((0, width), dtype=torch.float32, device=dev)
-                    result = nxt
-                # layer i is complete HERE before any rank reads it, and every rank has finished reading layer i-1 before
-                # its buffer is written again (after the last layer: before anyone unmaps)
-                torch.cuda.current_stream(dev).synchronize()
-                peers.barrier()
-            return result
-    except BaseException:
-        if hasattr(peers, "abort"):
-            peers.abort()
-        raise
-    finally:
-        for sh, _dt, _f in shared:
-            sh.close()
-        model.train(was_training)
-
-
-def _tiles_contiguous(A):
-    """``_row_tiles`` with every tile contiguous: a full tile of a padded buffer is a strided view, and the GEMM's
-    operand layout is part of its shape (the whole-table drivers multiply contiguous matrices)"""
-    for r, n, tile in _row_tiles(A):
-        yield r, n, tile.contiguous()
-
-
-def _gat_partitioned(model, x_local, rowptr, col, off, rank, peers, nodes, rows_per_slab, act_dtype, shared):
-    """``_gat_inference`` for one rank of a row-partitioned table: the same operations on the same fixed tiles, so the
-    same bits.  Projection and logits are LOCAL (a rank's own rows of the layer's input), so no rank reads a peer's
-    feature rows and ``x_local`` is not published.  Two buffers are, once: h [n_local, max H*C] of ``act_dtype`` and the
-    logits [n_local, 2 * max H] fp32 = [a_src | a_dst], both laid out by the resident tables' row-stride rule (one stride
-    on every rank); a layer narrower than the buffer reads its leading columns at the buffer's stride.  Per layer: write
-    the rank's h and logits; synchronise and barrier (every rank's h is complete); attend the rank's slabs with
-    ``graph_gat_aggregate_parts`` over all ranks' parts into a local matrix; synchronise and barrier (everyone has
-    finished reading h before the next layer overwrites it, or, after the last layer, before anyone unmaps)."""
-    lo, dev = off[rank], x_local.device
-    n_local = off[rank + 1] - lo
-    n_layers = len(model.convs)
-    Fmax = max(c.heads * c.out_channels for c in model.convs)
-    Hmax = max(c.heads for c in model.convs)
-    esize = torch.empty(0, dtype=act_dtype).element_size()
-    hbuf = torch.empty((n_local, _row_stride_elems(Fmax, esize)), dtype=act_dtype, device=dev)[:, :Fmax]
-    abuf = torch.empty((n_local, _row_stride_elems(2 * Hmax, 4)), dtype=torch.float32, device=dev)[:, :2 * Hmax]
-    shared.append(peers.share(hbuf))
-    shared.append(peers.share(abuf))
-    h_peers, a_peers = shared
-    rows_out = nodes.numel() if nodes is not None else n_local
-    ws = torch.empty(graph_gat_workspace_bytes(min(rows_per_slab, max(n_local, rows_out))), dtype=torch.uint8, device=dev)
-    cur = x_local
-    for i, conv in enumerate(model.convs):
-        last = i == n_layers - 1
-        H, Cc = conv.heads, conv.out_channels
-        W = conv.lin_src.weight                                                   # [H*C, K]
-        att = torch.stack([conv.att_src.view(H, Cc), conv.att_dst.view(H, Cc)]).to(torch.float32)
-        V = torch.einsum("shc,hck->shk", att, W.to(torch.float32).view(H, Cc, -1)).reshape(2 * H, -1)   # [V_src; V_dst]
-        Wt, Vt = W.to(act_dtype).t(), V.t().contiguous()
-        for r, n, tile in _row_tiles(cur):
-            hbuf[r:r + n, :H * Cc] = (tile.to(act_dtype) @ Wt)[:n]
-            abuf[r:r + n, :2 * H] = (tile.to(torch.float32) @ Vt)[:n]
-        del cur
-        torch.cuda.current_stream(dev).synchronize()
-        peers.barrier()                                  # every rank's h and logits of this layer are complete
-        ids = nodes if last else None
-        rows = ids.numel() if ids is not None else n_local
-        width = Cc if last else H * Cc
-        nxt = torch.empty((rows, width), dtype=torch.float32 if last else act_dtype, device=dev)
-        for s in range(0, rows, rows_per_slab):
-            e = min(rows, s + rows_per_slab)
-            tgt = dict(target_ids=ids[s:e]) if ids is not None else dict(row0=lo + s, num_targets=e - s)
-            out = nxt[s:e] if not last else torch.empty((e - s, H * Cc), dtype=torch.float32, device=dev)
-            graph_gat_aggregate_parts(h_peers, a_peers, off, rowptr, col, heads=H, negative_slope=conv.negative_slope,
-                                      relu=not last, out_dtype=out.dtype, out=out, workspace=ws, dtype=act_dtype,
-                                      F=H * Cc, **tgt)
-            if last:                                     # concat=False: the mean of the heads (H = 1: the head itself)
-                nxt[s:e] = torch.log_softmax(out.view(e - s, H, Cc).mean(1) if H > 1 else out, dim=-1,
-                                             dtype=torch.float32)
-        cur = nxt
-        torch.cuda.current_stream(dev).synchronize()
-        peers.barrier()                                  # every rank has finished reading this layer's h
-    return cur
-
-
-def _resinc_partitioned(model, x_local, rowptr, col, off, rank, peers, nodes, rows_per_slab, act_dtype, shared):
-    """``_resinc_inference`` for one rank of a row-partitioned table.  ``x_local`` and the ping-pong [n_local, hidden]
-    buffers are published once; each layer aggregates with ``graph_aggregate_parts`` ("operand") over all ranks' parts,
-    and everything behind the aggregation is local: the GEMM tiles, ``resinc_epilogue`` (the residual of layers >= 2 is
-    the rank's OWN previous buffer, by local slab or by ``ids - lo``), the head accumulator.  One synchronise and barrier
-    per layer."""
-    lin1, lin2 = _resinc_head(model)
-    lo, dev = off[rank], x_local.device
-    n_local = off[rank + 1] - lo
-    n_layers, hidden = len(model.convs), model.hidden_channels
-    esize = torch.empty(0, dtype=act_dtype).element_size()
-    se = _row_stride_elems(hidden, esize)
-    bufs = [torch.empty((n_local, se), dtype=act_dtype, device=dev)[:, :hidden] for _ in range(min(2, n_layers - 1))]
-    shared.append(peers.share(x_local))
-    for b in bufs:
-        shared.append(peers.share(b))
-    rows_out = nodes.numel() if nodes is not None else n_local
-    local = nodes - lo if nodes is not None else None    # the rank's own rows of ``nodes``
-    ws = torch.empty(graph_agg_workspace_bytes(min(rows_per_slab, max(n_local, rows_out))), dtype=torch.uint8, device=dev)
-    acc = torch.zeros((rows_out, lin1.out_features), dtype=torch.float32, device=dev)
-    if lin1.bias is not None:
-        acc += lin1.bias.to(torch.float32)
-
-    def add_block(block, first_col):                     # acc += block @ W1[:, its columns]^T, over the fixed tiles
-        Wb = lin1.weight[:, first_col:first_col + block.size(1)].to(act_dtype).t()
-        for r, n, tile in _tiles_contiguous(block):
-            acc[r:r + n] += (tile.to(act_dtype) @ Wb)[:n]
-
-    add_block(x_local if local is None else x_local[local], 0)
-    cur = x_local
-    for i, (conv, bn) in enumerate(zip(model.convs, model.bns)):
-        last = i == n_layers - 1
-        a = bn.weight.to(torch.float32) / torch.sqrt(bn.running_var.to(torch.float32) + bn.eps)
-        b = bn.bias.to(torch.float32) - bn.running_mean.to(torch.float32) * a
-        W = torch.cat([conv.lin_l.weight, conv.lin_r.weight], dim=1)               # [hidden, 2K] = [W_l | W_r]
-        bias = conv.lin_l.bias
-        res = model.res_linears[i]
-        if isinstance(res, torch.nn.Linear):             # (layer 1) stacked: the tile comes out as [z | res(x_t)]
-            W = torch.cat([W, torch.cat([torch.zeros_like(res.weight), res.weight], dim=1)], dim=0)
-            if bias is not None or res.bias is not None:
-                zero = W.new_zeros(hidden)
-                bias = torch.cat([bias if bias is not None else zero, res.bias if res.bias is not None else zero])
-        Wt = W.to(act_dtype).t()
-        bias = bias.to(act_dtype) if bias is not None else None
-        src = shared[0] if i == 0 else shared[1 + (i - 1) % len(bufs)]
-        ids = nodes if last else None
-        rows = ids.numel() if ids is not None else n_local
-        nxt = torch.empty((rows, hidden), dtype=act_dtype, device=dev) if last else bufs[i % len(bufs)]
-        for s in range(0, rows, rows_per_slab):
-            e = min(rows, s + rows_per_slab)
-            tgt = dict(target_ids=ids[s:e]) if ids is not None else dict(row0=lo + s, num_targets=e - s)
-            A = graph_aggregate_parts(src, off, rowptr, col, dtype=cur.dtype, F=cur.size(1), epilogue="operand",
-                                      out_dtype=act_dtype, workspace=ws, **tgt)
-            for r, n, tile in _row_tiles(A):
-                Z = torch.addmm(bias, tile, Wt) if bias is not None else tile @ Wt
-                if Z.size(1) > hidden:
-                    residual = dict(residual=Z[:, hidden:], row0=0)
-                elif ids is not None:
-                    residual = dict(residual=cur, row_ids=local[s + r:s + r + n])
-                else:
-                    residual = dict(residual=cur, row0=s + r)
-                resinc_epilogue(Z[:n, :hidden], a, b, negative_slope=0.01, out=nxt[s + r:s + r + n], **residual)
-        add_block(nxt if last or local is None else nxt[local], x_local.size(1) + i * hidden)
-        cur = nxt
-        # layer i is complete HERE before any rank reads it, and every rank has finished reading layer i-1 before its
-        # buffer is written again (after the last layer: before anyone unmaps)
-        torch.cuda.current_stream(dev).synchronize()
-        peers.barrier()
-    W2t = lin2.weight.to(act_dtype).t()
-    b2 = lin2.bias.to(act_dtype) if lin2.bias is not None else None
-    out = torch.empty((rows_out, lin2.out_features), dtype=torch.float32, device=dev)
-    for r, n, tile in _row_tiles(acc):
-        h = tile.to(act_dtype)
-        h = torch.addmm(b2, h, W2t) if b2 is not None else h @ W2t
-        out[r:r + n] = torch.log_softmax(h[:n], dim=-1, dtype=torch.float32)
-    return out
+    return _score(model, _Partitioned(what, x_local, rowptr, col, off, rank, peers), nodes, rows_per_slab, act_dtype)
 
 
 def partitioned_inference(model, x_local, rowptr, col, *, part_offsets, rank, peers, nodes=None, rows_per_slab=1 << 20,
@@ -1152,45 +1022,42 @@ def partitioned_inference(model, x_local, rowptr, col, *, part_offsets, rank, pe
     row-partitioned over the ranks.  Every rank calls this with its own partition ``x_local`` (the global rows
     [part_offsets[rank], part_offsets[rank + 1])), the WHOLE graph's CSR (global ids) and the same ``model``, and gets the
     fp32 log-probabilities of ITS node range, [n_local, classes] -- or of ``nodes`` (global ids, all inside the rank's
-    range).  The bits are those of ``layerwise_inference`` over the concatenated table, those rows.
+    range).  The bits are those of ``layerwise_inference`` over the concatenated table, those rows: the layer loops are
+    the same code (``_conv_layers``, ``_gat_layers``, ``_resinc_layers``) over the same fixed GEMM tiles.
 
-    SAGE and GIN: ``partitioned_layerwise_inference``, whose arguments, ``peers`` protocol and failure rule (``abort()``
-    when a rank fails, ``close()`` of every mapping at the end) hold here.  GAT: ``_gat_partitioned`` (local projection,
-    h and logits published once, two barriers a layer); SAGEResInception: ``_resinc_partitioned`` (one barrier a layer).
-    The model-shape refusals are ``layerwise_inference``'s, and like every argument check they come before ``peers`` is
-    touched.
+    Per rank (``_Partitioned``): the buffers the other ranks read are allocated up front and published once through
+    ``peers`` -- SAGE, GIN and SAGEResInception: ``x_local`` and the ping-pong activation buffers [n_local, hidden] of
+    ``act_dtype`` (one for a two-layer model); GAT: h and the logits, the projection being local.  Each layer aggregates
+    the rank's own slabs with the parts kernels over ALL ranks' parts and writes its rows of the next layer into its own
+    buffer; then the rank synchronises its stream and waits in ``peers.barrier()`` before anyone reads the layer or
+    reuses a buffer (GAT: twice a layer, after h and the logits are written and after the layer is attended).  After the
+    last barrier the mappings are closed.
 
-    Memory per rank of P, as arithmetic (GAT at papers scale: N = 111 M, hidden 256, 172 classes, H = 1, bf16, P = 8, so
-    13.9 M rows a rank): the h buffer 13.9 M * 256 * 2 B = 7.1 GB and the logits 13.9 M * 8 B = 0.11 GB, both live for the
-    whole call; one [n_local, 256] bf16 activation matrix at a time beside them (``cur`` while a layer projects, ``nxt``
-    while it attends), 7.1 GB; the last layer's [n_local, 172] fp32 result, 9.5 GB; 3.6 GB of table and the rank's copy
-    of the 26 GB graph: about 47 GB at the peak, against 168 GB on one device."""
-    from .models import GAT, GIN, SAGE, SAGEResInception
-    what = "partitioned_inference"
-    if not isinstance(model, (SAGE, GIN, GAT, SAGEResInception)):
-        raise NotImplementedError(f"{what}: implemented for SAGE, GIN, GAT and SAGEResInception, not "
-                                  f"{type(model).__name__}")
-    if isinstance(model, (SAGE, GIN)):
-        return partitioned_layerwise_inference(model, x_local, rowptr, col, part_offsets=part_offsets, rank=rank,
-                                               peers=peers, nodes=nodes, rows_per_slab=rows_per_slab, act_dtype=act_dtype)
-    _check_model_shape(model, what)
-    off, rank, nodes, rows_per_slab = _check_partitioned(what, x_local, rowptr, col, part_offsets, rank, peers, nodes,
-                                                         rows_per_slab, act_dtype)
-    dev = x_local.device
-    run = _gat_partitioned if isinstance(model, GAT) else _resinc_partitioned
-    was_training = model.training
-    model.eval()
-    shared = []
-    try:
-        with torch.no_grad(), torch.autocast("cuda", enabled=False), torch.cuda.device(dev):
-            if hasattr(peers, "bind"):
-                peers.bind(rank)
-            return run(model, x_local, rowptr, col, off, rank, peers, nodes, rows_per_slab, act_dtype, shared)
-    except BaseException:
-        if hasattr(peers, "abort"):
-            peers.abort()
-        raise
-    finally:
-        for sh in shared:
-            sh.close()
-        model.train(was_training)
+    ``peers``: ``share(tensor) -> P2PPeers`` (collective, same order on every rank), ``barrier()``, ``close()``; optional
+    ``bind(rank)`` and ``abort()`` (called when a rank fails, so that the others raise instead of waiting).
+    ``LocalPeers`` and ``IpcPeers`` are the two implementations.  The model-shape refusals are
+    ``layerwise_inference``'s, and like every argument check they come before ``peers`` is touched.
+
+    Memory, as arithmetic (SAGE on S-mag, N = 121.8 M, F = 768 fp16, hidden 256, bf16): per rank of P, 187 / P GB of
+    table and 2 * 62 / P GB of activations next to its copy of the 22 GB graph.  GAT at papers scale (N = 111 M, hidden
+    256, 172 classes, H = 1, bf16, P = 8, so 13.9 M rows a rank): the h buffer 13.9 M * 256 * 2 B = 7.1 GB and the logits
+    13.9 M * 8 B = 0.11 GB, both live for the whole call; one [n_local, 256] bf16 activation matrix at a time beside them
+    (``cur`` while a layer projects, ``nxt`` while it attends), 7.1 GB; the last layer's [n_local, 172] fp32 result,
+    9.5 GB; 3.6 GB of table and the rank's copy of the 26 GB graph: about 47 GB at the peak, against 168 GB on one
+    device."""
+    return _partitioned("partitioned_inference", "SAGE, GIN, GAT and SAGEResInception", model, x_local, rowptr, col,
+                        part_offsets, rank, peers, nodes, rows_per_slab, act_dtype)
+
+
+def partitioned_layerwise_inference(model, x_local, rowptr, col, *, part_offsets, rank, peers, nodes=None,
+                                    rows_per_slab=1 << 20, act_dtype=torch.float32):
+    """``partitioned_inference`` for SAGE and GIN only, the entry that came first: GAT and SAGEResInception are refused
+    here and scored there; everything else is that entry's."""
+    from .models import GAT, SAGEResInception
+    what = "partitioned_layerwise_inference"
+    if isinstance(model, (GAT, SAGEResInception)):
+        raise NotImplementedError(f"{what}: {type(model).__name__} over a partitioned table is not scored by this entry "
+                                  "(its layers need the long-row softmax / the fused layer tail over parts); SAGE and GIN "
+                                  "are.  partitioned_inference scores all four models")
+    return _partitioned(what, "SAGE and GIN", model, x_local, rowptr, col, part_offsets, rank, peers, nodes,
+                        rows_per_slab, act_dtype)

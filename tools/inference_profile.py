@@ -27,9 +27,10 @@ between the medians.  One slab's outputs are compared bit for bit first.
 into P equal row ranges, an allocation per part and kind; every slab attended twice: ``spp_graph_gat_forward`` on the
 whole matrices and ``spp_graph_gat_parts_forward`` on the parts, alternating, after one slab is compared bit for bit.
 
-Per layer: seconds of the aggregation alone (events around every slab's graph_aggregate, summed), edges/s, and the
-algorithmic bytes/s  E * F * s (rows) + 16 * T + 8 * E (indices) + T * W * s_out (output); plus the seconds of the whole
-layer (aggregation, GEMM, activation write).  Also the maximum degree and the share of rows and entries above C."""
+Per layer: seconds of the aggregation alone (events around every slab's launch, the drivers' ``inference._agg_launch`` /
+``_gat_launch`` replaced by a timed one for the run, summed), edges/s, and the algorithmic bytes/s
+E * F * s (rows) + 16 * T + 8 * E (indices) + T * W * s_out (output); plus the seconds of the whole layer (aggregation,
+GEMM, activation write).  Also the maximum degree and the share of rows and entries above C."""
 import argparse
 import json
 import os
@@ -81,7 +82,7 @@ def main():
 
     # the aggregation of every slab, timed by events inside the one layerwise_inference call
     spans = []
-    inner = inf.graph_aggregate
+    inner = inf._agg_launch
 
     def timed(xm, *args, **kw):
         b, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -90,7 +91,7 @@ def main():
         e.record()
         spans.append((xm.size(1), xm.element_size(), out.size(0), out.size(1) * out.element_size(), b, e))
         return out
-    inf.graph_aggregate = timed
+    inf._agg_launch = timed
     torch.manual_seed(0)
     model = SAGE(x.size(1), a.hidden, a.classes, 3).to(dev)
     torch.cuda.synchronize()
@@ -98,7 +99,7 @@ def main():
     out = inf.layerwise_inference(model, x, rowptr, col, rows_per_slab=a.rows_per_slab, act_dtype=torch.bfloat16)
     torch.cuda.synchronize()
     res["total_s"] = round(time.time() - t0, 3)
-    inf.graph_aggregate = inner
+    inf._agg_launch = inner
     assert out.shape == (N, a.classes) and bool(torch.isfinite(out[:: max(1, N // 4096)]).all())
     del out
     slabs = -(-N // a.rows_per_slab)
@@ -158,7 +159,7 @@ def resinc_leg(a, wl, res):
     res["scored_nodes"] = int(nodes.numel()) if nodes is not None else N
     model = SAGEResInception(x.size(1), a.hidden, a.classes, L).to(x.device)
     agg, epi, marks = [], [], []
-    inner_agg, inner_epi = inf.graph_aggregate, inf.resinc_epilogue
+    inner_agg, inner_epi = inf._agg_launch, inf.resinc_epilogue
     tail = _torch_tail if a.torch_epilogue else inner_epi
 
     def timed(fn, spans):
@@ -177,7 +178,7 @@ def resinc_leg(a, wl, res):
             m.record()
             marks.append((xm.data_ptr(), len(agg), len(epi), m))
         return timed(inner_agg, agg)(xm, *args, **kw)
-    inf.graph_aggregate, inf.resinc_epilogue = timed_agg, timed(tail, epi)
+    inf._agg_launch, inf.resinc_epilogue = timed_agg, timed(tail, epi)
     try:
         for rep in range(a.repeats):
             del agg[:], epi[:], marks[:]
@@ -205,7 +206,7 @@ def resinc_leg(a, wl, res):
             res["passes"].append(one)
             print(json.dumps(one), flush=True)
     finally:
-        inf.graph_aggregate, inf.resinc_epilogue = inner_agg, inner_epi
+        inf._agg_launch, inf.resinc_epilogue = inner_agg, inner_epi
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:
@@ -336,7 +337,7 @@ def gat_leg(a, wl, res):
     N, E, H = wl.num_nodes, col.numel(), a.heads
     res.update(model="gat", heads=H, chunk=inf.graph_gat_chunk(), passes=[])
     spans = []
-    inner = inf._gat_forward
+    inner = inf._gat_launch
 
     def timed(h, *args):
         b, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -345,7 +346,7 @@ def gat_leg(a, wl, res):
         e.record()
         spans.append((h.size(1), h.element_size(), out.size(0), out.size(1) * out.element_size(), b, e))
         return out
-    inf._gat_forward = timed
+    inf._gat_launch = timed
     torch.manual_seed(0)
     model = GAT(x.size(1), a.hidden, a.classes, 3, heads=H).to(x.device)
     slabs = -(-N // a.rows_per_slab)
@@ -367,7 +368,7 @@ def gat_leg(a, wl, res):
                                   "edges_per_s": round(E / agg_s), "algorithmic_TBps": round(nbytes / agg_s / 1e12, 3)})
         res["passes"].append(one)
         print(json.dumps(one), flush=True)
-    inf._gat_forward = inner
+    inf._gat_launch = inner
     res.pop("layers")
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
