@@ -1201,6 +1201,54 @@ typedef struct spp_resinc_epilogue_desc {
 
 spp_status spp_resinc_epilogue(const spp_resinc_epilogue_desc* desc, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * f3m  The tail all models' exact inference shares: the predicted class and the negative log-likelihood of every row
+ *      of a tile of logits, one pass, so that no [rows, classes] matrix of log-probabilities has to exist.
+ *
+ *   Contract, for i < n, everything in fp32 after an exact upcast of bf16:
+ *        pred[i] = the index of the largest z[i,c] by torch.argmax's rules: the smallest index on ties, a NaN is larger
+ *                  than everything and the first NaN wins.  Exact: the argmax of the LOGITS.
+ *        m       = max_c z[i,c]
+ *        nll[i]  = log(sum_c exp(z[i,c] - m)) - (z[i,y] - m),  y = the row's label; 0.0f when the row has none
+ *      exp(t) is 2^(t * log2(e)) (one rounded product, the device's 2^x), log the device library's logf; the last bit
+ *      is therefore not torch's.  |nll - exact| <= (C + 8) * 2^-24 * (1 + |z_y - m| + log C).
+ *
+ *        z     [n, C], rows z_stride_elems apart (0 = dense); fp32 / bf16
+ *        y     int64 [y_rows], NULL = no labels (y_rows, y_row0 and row_ids_dev then select nothing).  Addressed as
+ *              spp_resinc_epilogue's residual: a slab, row i reads y[y_row0 + i] (y_row0 >= 0, row_ids_dev NULL), or a
+ *              list, row i reads y[row_ids[i]] (int64 [n], any order, duplicates allowed, y_row0 < 0).  An index
+ *              outside [0, y_rows) is "no label", without a fault; so is a label outside [0, C) (-1 for an
+ *              unlabelled node).
+ *        pred  int64 [n], NULL = not wanted;  nll  fp32 [n], NULL = not wanted;  at least one of the two.
+ *
+ *   A row's pred and nll are a function of its C logits, its label, C and the element type ONLY -- not of n, the row's
+ *   position in the call, the stride, the alignment or the load form -- and the same bits run to run: lpr lanes (a power
+ *   of two <= 64, fixed by C and the type) own a row, column c belongs to lane (c / W) % lpr with W = 4 (fp32) or 8
+ *   (bf16), a lane folds its columns in ascending order and the lanes' partial results meet in an xor-shuffle tree that
+ *   carries the index through the maximum.  Loads move 16 bytes where the base, the stride and C are multiples of W
+ *   elements, 8 or 4 bytes or one element otherwise; a row of more than 64 * W columns is walked twice (maximum, then sum).
+ *   One launch on `stream`, no workspace, no atomics; the entry never waits for the device.
+ *   Refused with SPP_ERR_INVALID before anything is enqueued: a NULL descriptor; NULL z_dev; pred_dev and nll_dev both
+ *   NULL; an unknown element code (fp16, fp8); C outside [1, 2^31); negative n, stride or y_rows; a non-zero stride
+ *   smaller than C; both a slab and a list; labels with neither.  n == 0: SPP_OK, nothing launched.
+ * ------------------------------------------------------------------------- */
+typedef struct spp_classify_desc {
+  int32_t z_elem;              /* SPP_ELEM_F32 / SPP_ELEM_BF16 */
+  int32_t reserved;
+  const void* z_dev;
+  int64_t z_stride_elems;      /* 0 = dense */
+  int64_t n;
+  int64_t C;
+  const int64_t* y_dev;        /* NULL: no labels */
+  int64_t y_rows;
+  int64_t y_row0;              /* slab: the label row of output row 0; < 0 with a list */
+  const int64_t* row_ids_dev;  /* list: the label row of every output row; NULL with a slab */
+  int64_t* pred_dev;           /* NULL: not wanted */
+  float* nll_dev;              /* NULL: not wanted */
+} spp_classify_desc;
+
+spp_status spp_classify_rows(const spp_classify_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,12 @@ class ResincEpilogueDesc(C.Structure):
                 ("out_stride_elems", i64)]
 
 
+class ClassifyDesc(C.Structure):
+    """spp_classify_desc: pred = argmax z, nll = logsumexp(z) - z[y]; labels as a slab (y_row0 >= 0) or a list"""
+    _fields_ = [("z_elem", i32), ("reserved", i32), ("z_dev", p), ("z_stride_elems", i64), ("n", i64), ("C", i64),
+                ("y_dev", p), ("y_rows", i64), ("y_row0", i64), ("row_ids_dev", p), ("pred_dev", p), ("nll_dev", p)]
+
+
 class GroupOut(C.Structure):
     _fields_ = [("mfg", MfgOut), ("x_out", p), ("y_out", p)]
 
@@ -261,6 +267,7 @@ SIGNATURES = {
     "spp_graph_gat_forward": (C.c_int, [C.POINTER(GraphGatDesc), p, i64, p]),
     "spp_graph_gat_parts_forward": (C.c_int, [C.POINTER(GraphGatPartsDesc), p, i64, p]),
     "spp_resinc_epilogue": (C.c_int, [C.POINTER(ResincEpilogueDesc), p]),
+    "spp_classify_rows": (C.c_int, [C.POINTER(ClassifyDesc), p]),
 }
 SPP_COMM_ID_BYTES = 128
 SPP_IPC_HANDLE_BYTES = 64

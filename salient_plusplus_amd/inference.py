@@ -8,7 +8,8 @@ fp16 / fp32 / bf16 inputs.
 The kernels' wrappers: ``graph_aggregate`` (``spp_graph_agg_forward``) and ``graph_gat_aggregate``
 (``spp_graph_gat_forward``) read one resident matrix, ``graph_aggregate_parts`` (``spp_graph_agg_parts_forward``) and
 ``graph_gat_aggregate_parts`` (``spp_graph_gat_parts_forward``) a row-PARTITIONED one (one range of nodes per rank, the
-peers' partitions mapped into the process), ``resinc_epilogue`` is the layer tail.  Each wrapper checks its arguments
+peers' partitions mapped into the process), ``resinc_epilogue`` is SAGEResInception's layer tail, ``classify_rows`` (``spp_classify_rows``, csrc/classify.hip) the
+tail all models share: argmax and negative log-likelihood of a tile of logits.  Each wrapper checks its arguments
 with the helpers they share and hands them to its kernel's launch function (``_agg_launch``, ``_gat_launch``,
 ``_agg_parts_launch``, ``_gat_parts_launch``), which the drivers call directly, slab by slab.
 
@@ -18,7 +19,10 @@ against a placement that says where the table lives -- ``_Resident`` (one matrix
 boundary) -- inside one frame (``_score``).  ``layerwise_inference`` is the resident entry (behind ``SAGE.inference``
 and ``GIN.inference``), ``partitioned_inference`` the partitioned one for all four models
 (``partitioned_layerwise_inference`` admits SAGE and GIN only), with ``LocalPeers`` (ranks as threads of one process)
-or ``IpcPeers`` (one process per rank on one node) between the ranks."""
+or ``IpcPeers`` (one process per rank on one node) between the ranks.  Every driver hands its last layer's logits, tile by
+tile, to a sink: ``_LogProbs`` (log_softmax into the [rows, classes] matrix those entries return) or ``_Classify``
+(``classify_rows`` into pred [rows] and nll [rows]), which is what ``evaluate`` and ``partitioned_evaluate`` run: the same
+pass, predictions, per-split accuracy and loss out, and no [rows, classes] matrix anywhere."""
 import ctypes as C
 import threading
 
@@ -473,6 +477,80 @@ def resinc_epilogue(z, scale, shift, *, negative_slope, residual=None, row0=None
     return out
 
 
+def _check_vector(what, name, t, dtype, n):
+    """a caller-provided output of ``classify_rows``: a contiguous 1-D ``dtype`` tensor of n entries, no gradient"""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (n,) or not t.is_contiguous() \
+            or t.requires_grad:
+        raise ValueError(f"{what}: {name} must be a contiguous {dtype} tensor of shape [{n}] (one entry per row of z) "
+                         "that does not require grad")
+
+
+def classify_rows(z, y=None, *, row0=None, row_ids=None, pred=None, nll=None):
+    """The predicted class and the negative log-likelihood of every row of logits, one pass over ``z`` and no
+    [n, C] intermediate (``spp_classify_rows``, include/spp.h).  Returns ``(pred, nll)``:
+
+        pred[i] = torch.argmax(z[i].float())                  exactly: smallest index on ties, the first NaN wins
+        nll[i]  = logsumexp(z[i]) - z[i, y[row(i)]]           fp32; 0.0 where row i has no label in [0, C)
+
+    ``z`` [n, C]: fp32 / bf16, possibly a strided view (the rows of a GEMM tile).  ``y``: contiguous int64 [R], read in
+    place either as a slab, ``row0`` (row(i) = row0 + i), or by a list, ``row_ids`` (int64 [n], any order, duplicates
+    allowed); an index outside [0, R) and a label outside [0, C) (-1: unlabelled) both mean "no label".  Without ``y``
+    only ``pred`` is computed and ``nll`` is None.  ``pred`` (int64 [n]) / ``nll`` (fp32 [n]): contiguous vectors to write
+    into (slices of longer ones allowed); allocated when None.  A row's two results are the same bits wherever the row
+    stands in ``z``, whatever the stride, and from run to run.  |nll - exact| <= (C + 8) * 2^-24 * (1 + |z_y - max| +
+    log C).
+
+    Forward only: no autograd node is registered and an input that requires grad is refused.  Nothing here waits for the
+    device."""
+    what = "classify_rows"
+    _check_matrix(z, what, "z")
+    if z.dtype not in _OUT_DTYPES:
+        raise ValueError(f"{what}: z must be fp32 or bf16, got {z.dtype}")
+    n, Cdim = z.shape
+    if Cdim < 1:
+        raise ValueError(f"{what}: z needs at least one column, got {tuple(z.shape)}")
+    if y is None:
+        if row0 is not None or row_ids is not None:
+            raise ValueError(f"{what}: row0 / row_ids address the labels y, and there is no y")
+        if nll is not None:
+            raise ValueError(f"{what}: nll needs the labels y")
+    else:
+        if not isinstance(y, torch.Tensor):
+            raise TypeError(f"{what}: y must be a torch.Tensor, got {type(y).__name__}")
+        if y.dtype != torch.int64 or y.dim() != 1 or not y.is_contiguous():
+            raise ValueError(f"{what}: y must be a contiguous 1-D int64 tensor, got {tuple(y.shape)} {y.dtype}")
+        if (row0 is None) == (row_ids is None):
+            raise ValueError(f"{what}: address the labels y either as a slab (row0) or as row_ids"
+                             + (", not both" if row0 is not None else ""))
+        if row_ids is None:
+            row0 = int(row0)
+            if row0 < 0:
+                raise ValueError(f"{what}: row0 must not be negative, got {row0}")
+        elif not isinstance(row_ids, torch.Tensor) or row_ids.dtype != torch.int64 or tuple(row_ids.shape) != (n,) \
+                or not row_ids.is_contiguous():
+            raise ValueError(f"{what}: row_ids must be a contiguous int64 tensor of shape [{n}] (one entry per row of z)")
+    if pred is not None:
+        _check_vector(what, "pred", pred, torch.int64, n)
+    if nll is not None:
+        _check_vector(what, "nll", nll, torch.float32, n)
+    nat.require_device()
+    if not all(t.is_cuda and t.device == z.device for t in (z, y, row_ids, pred, nll) if t is not None):
+        raise ValueError(f"{what}: z, y, row_ids, pred and nll must live on one CUDA device")
+    if pred is None:
+        pred = torch.empty(n, dtype=torch.int64, device=z.device)
+    if nll is None and y is not None:
+        nll = torch.empty(n, dtype=torch.float32, device=z.device)
+    d = nat.ClassifyDesc(z_elem=_ELEM[z.dtype], z_dev=_p(z), z_stride_elems=z.stride(0) if n > 1 else Cdim, n=n, C=Cdim,
+                         y_row0=-1, pred_dev=_p(pred), nll_dev=_p(nll))
+    if y is not None:
+        d.y_dev, d.y_rows = _p(y), y.numel()
+        d.y_row0, d.row_ids_dev = (-1, _p(row_ids)) if row_ids is not None else (row0, None)
+    if n:
+        with torch.cuda.device(z.device):
+            nat.check(nat.load().spp_classify_rows(C.byref(d), _stream()))
+    return pred, nll
+
+
 _GEMM_ROWS = 1 << 16
 
 
@@ -617,6 +695,87 @@ class _Partitioned:
                                  out, ws)
 
 
+# ---- where the last layer's logits go: the two tails the drivers below end in ---------------------------------------
+class _LogProbs:
+    """fp32 log-probabilities, [rows, classes]: ``log_softmax(dtype=float32)`` per tile, copied into the matrix that
+    ``layerwise_inference`` and ``partitioned_inference`` return"""
+
+    def open(self, place, rows, classes):
+        self.out = torch.empty((rows, classes), dtype=torch.float32, device=place.dev)
+
+    def put(self, r, n, logits, ids):
+        """output rows [r, r + n) from the first n rows of ``logits`` (fp32 / bf16); ``ids``: their global ids when the
+        call scores ``nodes``, None when they are the rank's rows r .. r + n"""
+        self.out[r:r + n] = torch.log_softmax(logits, dim=-1, dtype=torch.float32)[:n]
+
+    def result(self):
+        return self.out
+
+
+class _Classify:
+    """``classify_rows`` per tile, straight into pred [rows] and nll [rows]: nothing of [rows, classes] exists.  ``y``:
+    the rank's labels by local id, or None"""
+
+    def __init__(self, y):
+        self.y = y
+
+    def open(self, place, rows, classes):
+        self.place, self.classes = place, classes
+        self.pred = torch.empty(rows, dtype=torch.int64, device=place.dev)
+        self.nll = torch.empty(rows, dtype=torch.float32, device=place.dev) if self.y is not None else None
+
+    def put(self, r, n, logits, ids):
+        if self.y is None:
+            classify_rows(logits[:n], pred=self.pred[r:r + n])
+        elif ids is None:
+            classify_rows(logits[:n], self.y, row0=r, pred=self.pred[r:r + n], nll=self.nll[r:r + n])
+        else:
+            classify_rows(logits[:n], self.y, row_ids=self.place.local(ids), pred=self.pred[r:r + n],
+                          nll=self.nll[r:r + n])
+
+    def result(self):
+        return self
+
+
+class Evaluation:
+    """What ``evaluate`` and ``partitioned_evaluate`` return.  ``pred`` int64 [rows] and ``nll`` fp32 [rows] (None
+    without labels) stay on the device, in the order of the rows scored.  With labels: ``labelled`` (rows whose label
+    lies in [0, classes)), ``correct`` (labelled rows with pred == label) and ``loss`` (the mean nll over the labelled
+    rows, summed in float64 from ``nll``; nan when there are none) as Python numbers, and ``splits``: the same three per
+    split name, as {name: {"labelled", "correct", "loss"}} (empty without ``splits=``).  ``accuracy`` is correct /
+    labelled."""
+
+    def __init__(self, pred, nll, labelled=None, correct=None, loss=None, splits=None):
+        self.pred, self.nll, self.labelled, self.correct, self.loss = pred, nll, labelled, correct, loss
+        self.splits = splits or {}
+
+    @property
+    def accuracy(self):
+        return self.correct / self.labelled if self.labelled else float("nan")
+
+    def __repr__(self):
+        return (f"Evaluation(rows={self.pred.numel()}, labelled={self.labelled}, correct={self.correct}, "
+                f"loss={self.loss}, splits={self.splits})")
+
+
+def _evaluation(sink, y, label_rows, segments):
+    """the counts of a finished ``_Classify``: ``label_rows`` are the scored rows' indices into ``y`` (None: the rows
+    0 .. rows of y in order), ``segments`` {name: (first, end)} the splits' ranges of the scored rows.  Everything is
+    reduced on the device and read back ONCE, as one float64 vector (counts below 2^53 are exact in it)."""
+    pred, nll = sink.pred, sink.nll
+    if y is None:
+        return Evaluation(pred, None)
+    yv = y if label_rows is None else y[label_rows]
+    labelled = (yv >= 0) & (yv < sink.classes)
+    correct = labelled & (pred == yv)
+    nll64 = nll.to(torch.float64)                        # (0.0 on the unlabelled rows: the sums are over the labelled)
+    ranges = [(0, pred.numel())] + list(segments.values())
+    stats = torch.stack([torch.stack([labelled[a:b].sum().to(torch.float64), correct[a:b].sum().to(torch.float64),
+                                      nll64[a:b].sum()]) for a, b in ranges]).cpu().tolist()
+    rec = [dict(labelled=int(l), correct=int(c), loss=t / l if l else float("nan")) for l, c, t in stats]
+    return Evaluation(pred, nll, splits=dict(zip(segments, rec[1:])), **rec[0])
+
+
 # ---- the drivers: one layer loop per model, over a placement ---------------------------------------------------------
 def _sage_layer(conv, last, act_dtype):
     """(epilogue, self_scale, fn): fn maps a slab's fp32 / bf16 operand [T, 2K] to the layer's output rows"""
@@ -646,10 +805,10 @@ def _slabs(place, ids, rows_per_slab):
         yield s, e - s, ids[s:e] if ids is not None else None
 
 
-def _conv_layers(model, place, nodes, rows_per_slab, act_dtype):
-    """SAGE and GIN, as ``layerwise_inference`` describes them.  Resident, layer i-1's matrix is dropped as soon as layer
-    i is complete, so two [N, hidden] matrices are live at a boundary; partitioned, the layers alternate between the (at
-    most two) published buffers."""
+def _conv_layers(model, place, nodes, rows_per_slab, act_dtype, sink):
+    """SAGE and GIN, as ``layerwise_inference`` describes them; the last layer's logits go to ``sink``, tile by tile.
+    Resident, layer i-1's matrix is dropped as soon as layer i is complete, so two [N, hidden] matrices are live at a
+    boundary; partitioned, the layers alternate between the (at most two) published buffers."""
     from .models import GIN
     gin, amp = isinstance(model, GIN), act_dtype == torch.bfloat16
     n_layers, dev = len(model.convs), place.dev
@@ -657,11 +816,11 @@ def _conv_layers(model, place, nodes, rows_per_slab, act_dtype):
     ws = torch.empty(graph_agg_workspace_bytes(min(rows_per_slab, max(place.n_local, nodes.numel() if nodes is not None else 0))),
                      dtype=torch.uint8, device=dev)
 
-    def head(h):                                         # what follows the last conv layer, fp32 log-probabilities
+    def head(h):                                         # what follows the last conv layer: the logits
         if gin:
             with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
                 h = model.lin2(torch.relu(model.lin1(h)))
-        return torch.log_softmax(h, dim=-1, dtype=torch.float32)
+        return h
 
     cur = place.x
     for i, conv in enumerate(model.convs):
@@ -669,25 +828,28 @@ def _conv_layers(model, place, nodes, rows_per_slab, act_dtype):
         epilogue, scale, fn = _gin_layer(conv, amp) if gin else _sage_layer(conv, last, act_dtype)
         ids = nodes if last else None
         rows = ids.numel() if ids is not None else place.n_local
-        out_dtype = torch.float32 if last else act_dtype
         nxt = None
+        if last:
+            sink.open(place, rows, (model.lin2 if gin else conv.lin_l).out_features)
         for s, T, tids in _slabs(place, ids, rows_per_slab):
             A = torch.empty((T, cur.size(1) * (2 if epilogue == "operand" else 1)), dtype=act_dtype, device=dev)
             place.aggregate(i, cur, epilogue, scale, s, tids, T, A, ws)
             for r, n, tile in _row_tiles(A):
-                h = head(fn(tile)) if last else fn(tile)
+                if last:
+                    sink.put(s + r, n, head(fn(tile)), tids[r:r + n] if tids is not None else None)
+                    continue
+                h = fn(tile)
                 if nxt is None:
-                    nxt = place.layer_rows(i, last, rows, h.size(1), out_dtype)
+                    nxt = place.layer_rows(i, last, rows, h.size(1), act_dtype)
                 nxt[s + r:s + r + n] = h[:n]
-        if nxt is None:                                  # no rows at all
-            width = (model.lin2 if gin else conv.lin_l).out_features if last else model.hidden_channels
-            nxt = place.layer_rows(i, last, 0, width, out_dtype)
+        if nxt is None and not last:                     # no rows at all
+            nxt = place.layer_rows(i, last, 0, model.hidden_channels, act_dtype)
         cur = nxt                                        # (resident: drops layer i-1's matrix)
         place.boundary()
-    return cur
+    return sink.result()
 
 
-def _gat_layers(model, place, nodes, rows_per_slab, act_dtype):
+def _gat_layers(model, place, nodes, rows_per_slab, act_dtype, sink):
     """GAT, in PyG's project-first order (training aggregates first, _GatLayer / _GatLayerMH, because an MFG hop has
     many sources per target; over the whole graph T = S = N, that saving is gone, and the aggregate-first intermediate
     would be [T, H, K] fp32 per slab).  Per layer:
@@ -697,7 +859,7 @@ def _gat_layers(model, place, nodes, rows_per_slab, act_dtype):
                  taken from the layer's input rows, never from the rounded h
       aggregate  the attention kernel slab by slab over each node's whole row; hidden layers through the fused ReLU
                  straight into the next [n, hidden] matrix, the last layer ([T, H*classes] fp32 per slab) through the
-                 mean over its heads and log_softmax(dtype=float32)
+                 mean over its heads into ``sink`` (log_softmax(dtype=float32), or ``classify_rows``)
 
     Partitioned, projection and logits are LOCAL (a rank's own rows of the layer's input), so no rank reads a peer's
     feature rows; h and the logits are the two published buffers, and a layer has two boundaries: every rank's h and
@@ -729,17 +891,20 @@ def _gat_layers(model, place, nodes, rows_per_slab, act_dtype):
         place.boundary()                                 # every rank's h and logits of this layer are complete
         ids = nodes if last else None
         rows = ids.numel() if ids is not None else place.n_local
-        nxt = torch.empty((rows, Cc if last else H * Cc), dtype=torch.float32 if last else act_dtype, device=dev)
+        if last:
+            nxt = None
+            sink.open(place, rows, Cc)
+        else:
+            nxt = torch.empty((rows, H * Cc), dtype=act_dtype, device=dev)
         for s, T, tids in _slabs(place, ids, rows_per_slab):
             out = nxt[s:s + T] if not last else torch.empty((T, H * Cc), dtype=torch.float32, device=dev)
             place.attend(h, logits, conv, not last, s, tids, T, out, ws)
             if last:                                     # concat=False: the mean of the heads (H = 1: the head itself)
-                nxt[s:s + T] = torch.log_softmax(out.view(T, H, Cc).mean(1) if H > 1 else out, dim=-1,
-                                                 dtype=torch.float32)
+                sink.put(s, T, out.view(T, H, Cc).mean(1) if H > 1 else out, tids)
         cur = nxt
         del h, logits                                    # (resident: drops them)
         place.boundary()                                 # every rank has finished reading this layer's h
-    return cur
+    return sink.result()
 
 
 def _resinc_head(model):
@@ -751,7 +916,7 @@ def _resinc_head(model):
     return mods
 
 
-def _resinc_layers(model, place, nodes, rows_per_slab, act_dtype):
+def _resinc_layers(model, place, nodes, rows_per_slab, act_dtype, sink):
     """SAGEResInception.  In eval mode dropout is the identity and the model is
 
       layer i    h_i = leaky_relu(BatchNorm_i([mean | h_{i-1}] @ [W_l | W_r]^T)) + res_i,   h_0 = x,
@@ -760,8 +925,8 @@ def _resinc_layers(model, place, nodes, rows_per_slab, act_dtype):
                  Layer 1's residual Linear is stacked into the same product ([0 | W_res] below [W_l | W_r], so the tile
                  is [z | res]); later residuals are the rows of ``cur`` itself -- the rank's OWN previous matrix -- read
                  in place by local slab or, on the last layer with ``nodes``, by the local id list.
-      head       log_softmax(lin2(lin1(cat(x, h_1, .., h_L)))).  lin1 is a bare Linear, so lin1(cat(..)) is
-                 bias + sum_k block_k @ W1[:, block k]^T: an fp32 accumulator ``acc`` [rows, 2 * classes] takes every
+      head       lin2(lin1(cat(x, h_1, .., h_L))), handed to ``sink`` tile by tile (log_softmax, or ``classify_rows``).
+                 lin1 is a bare Linear, so lin1(cat(..)) is bias + sum_k block_k @ W1[:, block k]^T: an fp32 accumulator ``acc`` [rows, 2 * classes] takes every
                  block's product when the block is complete, and no layer's matrix outlives the next layer.
 
     Everything behind the aggregation is local to a rank; partitioned, the table and the ping-pong [n_local, hidden]
@@ -823,12 +988,12 @@ def _resinc_layers(model, place, nodes, rows_per_slab, act_dtype):
         place.boundary()
     W2t = lin2.weight.to(act_dtype).t()
     b2 = lin2.bias.to(act_dtype) if lin2.bias is not None else None
-    out = torch.empty((rows_out, lin2.out_features), dtype=torch.float32, device=dev)
+    sink.open(place, rows_out, lin2.out_features)
     for r, n, tile in _row_tiles(acc):
         h = tile.to(act_dtype)
         h = torch.addmm(b2, h, W2t) if b2 is not None else h @ W2t
-        out[r:r + n] = torch.log_softmax(h[:n], dim=-1, dtype=torch.float32)
-    return out
+        sink.put(r, n, h[:n], nodes[r:r + n] if nodes is not None else None)
+    return sink.result()
 
 
 def _check_model(model, what, names):
@@ -858,7 +1023,7 @@ def _check_run(what, act_dtype, rows_per_slab, nodes):
     return rows_per_slab
 
 
-def _score(model, place, nodes, rows_per_slab, act_dtype):
+def _score(model, place, nodes, rows_per_slab, act_dtype, sink):
     """the frame of every driver: eval mode (restored), no gradient, autocast off, the table's device current; a rank
     that fails aborts the placement, so that its peers raise instead of waiting, and every mapping is closed"""
     from .models import GAT, SAGEResInception
@@ -869,7 +1034,7 @@ def _score(model, place, nodes, rows_per_slab, act_dtype):
     try:
         with torch.no_grad(), torch.autocast("cuda", enabled=False), torch.cuda.device(place.dev):
             place.bind()
-            return layers(model, place, nodes, rows_per_slab, act_dtype)
+            return layers(model, place, nodes, rows_per_slab, act_dtype, sink)
     except BaseException:
         place.abort()
         raise
@@ -900,20 +1065,75 @@ def layerwise_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 <<
     boundary (layer i-1's is freed as soon as layer i is complete).  At N = 111 M and hidden 256 that is 113 GB each in
     fp32 and 57 GB in bf16, next to 26 GB of graph and 28 GB of features: fp32 activations do not fit one 288 GB MI355X
     at papers scale, ``act_dtype=torch.bfloat16`` does (26 + 28 + 2 * 57 = 168 GB)."""
-    what = "layerwise_inference"
+    return _resident("layerwise_inference", model, x, rowptr, col, nodes, rows_per_slab, act_dtype, None, _LogProbs())
+
+
+def _check_labels(what, name, y, rows):
+    if not isinstance(y, torch.Tensor):
+        raise TypeError(f"{what}: {name} must be a torch.Tensor, got {type(y).__name__}")
+    if y.dtype != torch.int64 or tuple(y.shape) != (rows,) or not y.is_contiguous():
+        raise ValueError(f"{what}: {name} must be a contiguous int64 tensor of shape [{rows}] (one label per node, -1: none), got "
+                         f"{tuple(y.shape)} {y.dtype}")
+
+
+def _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, y, sink):
+    """the resident entries: every argument check, then the device, then the pass into ``sink``"""
     _check_model(model, what, "SAGE and GIN (and GAT, SAGEResInception)")
     _check_matrix(x, what)
     N = x.size(0)
     _check_graph(what, N, rowptr, col)
     rows_per_slab = _check_run(what, act_dtype, rows_per_slab, nodes)
+    if y is not None:
+        _check_labels(what, "y", y, N)
     nat.require_device()
     if not (x.is_cuda and rowptr.device == x.device and col.device == x.device):
         raise ValueError(f"{what}: x, rowptr and col must live on one CUDA device")
+    if y is not None and y.device != x.device:
+        raise ValueError(f"{what}: y must live on x's device")
     if nodes is not None:
         nodes = nodes.to(x.device).contiguous()
         if nodes.numel() and not (0 <= int(nodes.min()) and int(nodes.max()) < N):      # (one read-back, up front)
             raise ValueError(f"{what}: nodes outside the graph's {N} nodes")
-    return _score(model, _Resident(x, rowptr, col), nodes, rows_per_slab, act_dtype)
+    return _score(model, _Resident(x, rowptr, col), nodes, rows_per_slab, act_dtype, sink)
+
+
+def _check_splits(what, splits, nodes):
+    """(nodes, segments) of ``splits``: the concatenation of its id lists and {name: (first, end)} within it"""
+    if splits is None:
+        return nodes, {}
+    if nodes is not None:
+        raise ValueError(f"{what}: give either nodes or splits, not both (splits scores the concatenation of its lists)")
+    if not isinstance(splits, dict) or not splits:
+        raise TypeError(f"{what}: splits must be a non-empty dict of name -> 1-D int64 tensor of node ids")
+    segments, first = {}, 0
+    for name, ids in splits.items():
+        if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64 or ids.dim() != 1:
+            raise ValueError(f"{what}: splits[{name!r}] must be a 1-D int64 tensor of node ids")
+        segments[name] = (first, first + ids.numel())
+        first += ids.numel()
+    devs = {ids.device for ids in splits.values()}
+    if len(devs) > 1:
+        raise ValueError(f"{what}: the lists of splits live on different devices ({sorted(map(str, devs))})")
+    return torch.cat(list(splits.values())), segments
+
+
+def evaluate(model, x, rowptr, col, y=None, *, nodes=None, splits=None, rows_per_slab=1 << 20, act_dtype=torch.float32):
+    """Exact whole-graph evaluation: ``layerwise_inference``'s pass -- the same checks, layer loops, fixed GEMM tiles and
+    eval-mode frame -- with the other tail: each tile of the last layer's logits goes through ``classify_rows``
+    (``spp_classify_rows``) into its rows of ``pred`` and ``nll``, and no [rows, classes] matrix is ever allocated
+    (at N = 111 M and 172 classes that matrix is 76 GB of fp32).  Returns an ``Evaluation``.
+
+    ``y``: int64 [N] on x's device, indexed by global node id; a label outside [0, classes) (-1) marks an unlabelled
+    node, which counts nowhere and has nll 0.  Without ``y`` only ``pred`` is computed.  ``nodes`` (int64, any order,
+    duplicates allowed) scores those nodes only; ``splits`` = {"valid": ids, "test": ids, ...} scores the concatenation
+    of the lists once (``pred`` and ``nll`` follow it) and also returns labelled / correct / loss per name.  A node's
+    ``pred`` and ``nll`` are the same bits whatever ``rows_per_slab`` is and whether ``nodes`` selected it; ``pred[i]`` is
+    the argmax of the logits, so ``layerwise_inference``'s row attains its maximum there.  The counts are reduced on the
+    device and read back once, at the end."""
+    what = "evaluate"
+    nodes, segments = _check_splits(what, splits, nodes)
+    sink = _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, y, _Classify(y))
+    return _evaluation(sink, y, None if nodes is None else nodes.to(x.device), segments)
 
 
 class LocalPeers:
@@ -987,7 +1207,8 @@ class IpcPeers:
         pass
 
 
-def _partitioned(what, names, model, x_local, rowptr, col, part_offsets, rank, peers, nodes, rows_per_slab, act_dtype):
+def _partitioned(what, names, model, x_local, rowptr, col, part_offsets, rank, peers, nodes, rows_per_slab, act_dtype,
+                 y_local=None, sink=None):
     """the partitioned entries behind their model filters.  Every argument and model-shape check comes before ``peers``
     is touched, and the device is required last: a refused call publishes nothing and waits for nobody."""
     _check_model(model, what, names)
@@ -1004,6 +1225,8 @@ def _partitioned(what, names, model, x_local, rowptr, col, part_offsets, rank, p
     rows_per_slab = _check_run(what, act_dtype, rows_per_slab, nodes)
     if nodes is not None and nodes.numel() and not (lo <= int(nodes.min()) and int(nodes.max()) < hi):
         raise ValueError(f"{what}: nodes outside rank {rank}'s range [{lo}, {hi}) (global ids; every rank scores its own)")
+    if y_local is not None:
+        _check_labels(what, "y_local", y_local, hi - lo)
     for name in ("share", "barrier", "close"):
         if not callable(getattr(peers, name, None)):
             raise TypeError(f"{what}: peers must provide share(tensor), barrier() and close()")
@@ -1011,9 +1234,12 @@ def _partitioned(what, names, model, x_local, rowptr, col, part_offsets, rank, p
     dev = x_local.device
     if not (x_local.is_cuda and rowptr.device == dev and col.device == dev):
         raise ValueError(f"{what}: x_local, rowptr and col must live on one CUDA device")
+    if y_local is not None and y_local.device != dev:
+        raise ValueError(f"{what}: y_local must live on x_local's device")
     if nodes is not None:
         nodes = nodes.to(dev).contiguous()
-    return _score(model, _Partitioned(what, x_local, rowptr, col, off, rank, peers), nodes, rows_per_slab, act_dtype)
+    return _score(model, _Partitioned(what, x_local, rowptr, col, off, rank, peers), nodes, rows_per_slab, act_dtype,
+                  _LogProbs() if sink is None else sink)
 
 
 def partitioned_inference(model, x_local, rowptr, col, *, part_offsets, rank, peers, nodes=None, rows_per_slab=1 << 20,
@@ -1047,6 +1273,21 @@ def partitioned_inference(model, x_local, rowptr, col, *, part_offsets, rank, pe
     device."""
     return _partitioned("partitioned_inference", "SAGE, GIN, GAT and SAGEResInception", model, x_local, rowptr, col,
                         part_offsets, rank, peers, nodes, rows_per_slab, act_dtype)
+
+
+def partitioned_evaluate(model, x_local, rowptr, col, y_local=None, *, part_offsets, rank, peers, nodes=None,
+                         rows_per_slab=1 << 20, act_dtype=torch.float32):
+    """``evaluate`` when the feature table is row-partitioned over the ranks: ``partitioned_inference``'s pass (same
+    arguments, same collective behaviour through ``peers``) ending in ``classify_rows`` instead of the [n_local, classes]
+    matrix.  Every rank scores its own rows -- or ``nodes``, global ids inside its range -- and gets an ``Evaluation`` of
+    them; the ranks' ``pred`` and ``nll`` concatenated are the bits of ``evaluate`` over the concatenated table.
+    ``y_local``: int64 [n_local] on x_local's device, the rank's labels by LOCAL id (-1: unlabelled).  ``labelled``,
+    ``correct`` and ``loss`` cover the rank's rows: the caller adds the counts (and ``loss * labelled``) across ranks."""
+    what = "partitioned_evaluate"
+    sink = _partitioned(what, "SAGE, GIN, GAT and SAGEResInception", model, x_local, rowptr, col, part_offsets, rank,
+                        peers, nodes, rows_per_slab, act_dtype, y_local, _Classify(y_local))
+    lo = sink.place.lo
+    return _evaluation(sink, y_local, None if nodes is None else nodes.to(x_local.device) - lo, {})
 
 
 def partitioned_layerwise_inference(model, x_local, rowptr, col, *, part_offsets, rank, peers, nodes=None,

@@ -5,6 +5,7 @@ with bf16 activations, timed per layer, and layer 1's slabs once more through th
     python tools/inference_profile.py [--workload S-papers] [--rows-per-slab 1048576] [--hidden 256] [--json out.json]
     python tools/inference_profile.py --model gat [--heads 4] [--repeats 3] ...
     python tools/inference_profile.py --model sageresinception [--nodes 1500000] [--torch-epilogue] [--repeats 3] ...
+    python tools/inference_profile.py --evaluate [--repeats 3] ...
     python tools/inference_profile.py --parts 8 --workload S-products [--repeats 5] ...
     python tools/inference_profile.py --parts 8 --model gat --workload S-products [--heads 1] [--repeats 9] ...
 
@@ -16,6 +17,13 @@ the logits: 4 * H per entry (a_src) and 8 * H per target (a_src of the self loop
 aggregation seconds as above, the epilogue seconds (events around every spp_resinc_epilogue call, summed; bytes: z, the
 residual row and the output row, bf16 each), the whole layer (layer 3's includes the head) and the whole call.
 ``--torch-epilogue`` runs the same pass with the layer tail restated as torch ops, the kernel's yardstick.
+
+``--evaluate``: the same SAGE 3 x hidden through ``evaluate`` with random labels (a fifth of them -1).  Events around every
+``classify_rows`` call, summed (algorithmic bytes: rows * C * sizeof + 16 * rows), and around the torch tail it replaces,
+run on the same tile in the same pass right behind it (both behind a 300 us spin kernel, so that the device finds them
+queued and the events time the device, not the host): ``log_softmax(dtype=float32)``, the copy into a [tile, C] fp32
+buffer, ``argmax`` and ``nll_loss`` of that buffer.  Before the timed passes, ``torch.cuda.max_memory_allocated`` above the
+baseline for one ``evaluate`` and for one ``layerwise_inference`` followed by ``argmax``.
 
 ``--parts P``: the cost of the owner lookup.  The workload's matrix cut into P equal row ranges, each copied into an
 allocation of its own on the one GPU, and every slab's MEAN aggregated twice: ``spp_graph_agg_forward`` on the whole
@@ -54,6 +62,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--nodes", type=int, default=1_500_000, help="sageresinception: nodes scored (0 = all)")
     ap.add_argument("--torch-epilogue", action="store_true", help="sageresinception: the layer tail as torch ops")
+    ap.add_argument("--evaluate", action="store_true", help="sage: the pass through evaluate, its tail against the torch tail")
     ap.add_argument("--parts", type=int, default=0, help="P > 0: time the aggregation over P row ranges against the whole matrix")
     a = ap.parse_args()
     from salient_plusplus_amd import _native as nat
@@ -79,6 +88,8 @@ def main():
         return gat_leg(a, wl, res)
     if a.model == "sageresinception":
         return resinc_leg(a, wl, res)
+    if a.evaluate:
+        return evaluate_leg(a, wl, res)
 
     # the aggregation of every slab, timed by events inside the one layerwise_inference call
     spans = []
@@ -207,6 +218,104 @@ def resinc_leg(a, wl, res):
             print(json.dumps(one), flush=True)
     finally:
         inf._agg_launch, inf.resinc_epilogue = inner_agg, inner_epi
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+def evaluate_leg(a, wl, res):
+    """SAGE 3 x hidden, bf16 activations, through ``evaluate``: peak memory against ``layerwise_inference`` + argmax
+    first (one untimed pass each, which also warms up), then ``--repeats`` passes with every ``classify_rows`` call and
+    the torch tail on the same tile timed by events"""
+    import torch.nn.functional as F
+    from salient_plusplus_amd import inference as inf
+    from salient_plusplus_amd.models import SAGE
+    x, rowptr, col = wl.x, wl.rowptr, wl.col
+    N, dev = wl.num_nodes, x.device
+    res.update(model="sage", evaluate=True, classes=a.classes, passes=[])
+    res.pop("layers")
+    torch.manual_seed(0)
+    model = SAGE(x.size(1), a.hidden, a.classes, 3).to(dev)
+    y = torch.randint(0, a.classes, (N,), device=dev)
+    y[::5] = -1
+    kw = dict(rows_per_slab=a.rows_per_slab, act_dtype=torch.bfloat16)
+
+    def peak(fn):
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        t0 = time.time()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, torch.cuda.max_memory_allocated() - base, round(time.time() - t0, 3)
+
+    ev, ev_peak, ev_s = peak(lambda: inf.evaluate(model, x, rowptr, col, y, **kw))
+    pred = ev.pred
+    res["evaluate"] = {"peak_bytes_above_baseline": ev_peak, "first_pass_s": ev_s, "labelled": ev.labelled,
+                       "correct": ev.correct, "loss": ev.loss}
+    del ev
+    lp_pred, lp_peak, lp_s = peak(lambda: inf.layerwise_inference(model, x, rowptr, col, **kw).argmax(-1))
+    res["layerwise_inference_then_argmax"] = {"peak_bytes_above_baseline": lp_peak, "first_pass_s": lp_s,
+                                              "matrix_bytes": N * a.classes * 4,
+                                              "pred_equal_to_evaluate": bool(torch.equal(lp_pred, pred))}
+    del lp_pred, pred
+    print(json.dumps({k: res[k] for k in ("evaluate", "layerwise_inference_then_argmax")}), flush=True)
+
+    # With an idle device an event pair times the host's way through the wrapper, not the kernel: a spin kernel of about
+    # 300 us ahead of every timed tile keeps the queue full while the host enqueues both tails behind it.
+    b, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda._sleep(1_000_000)
+    b.record()
+    torch.cuda._sleep(20_000_000)
+    e.record()
+    e.synchronize()
+    spin = int(300e-6 * 20_000_000 / (b.elapsed_time(e) / 1e3))
+    res["spin_cycles_per_tile"] = spin
+    spans = []
+    inner = inf.classify_rows
+    buf = torch.empty((inf._GEMM_ROWS, a.classes), dtype=torch.float32, device=dev)      # the tile's rows of ``out``
+    wrong = torch.zeros((), dtype=torch.int64, device=dev)
+
+    def timed(z, labels=None, *, row0=None, **kw2):
+        ev3 = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        torch.cuda._sleep(spin)
+        ev3[0].record()
+        out = inner(z, labels, row0=row0, **kw2)
+        ev3[1].record()
+        rows = buf[:z.size(0)]
+        rows.copy_(torch.log_softmax(z, dim=-1, dtype=torch.float32))
+        p = rows.argmax(-1)
+        F.nll_loss(rows, labels[row0:row0 + z.size(0)], ignore_index=-1, reduction="none")
+        ev3[2].record()
+        wrong.add_((p != out[0]).sum())
+        spans.append((z.size(0), z.size(1), z.element_size(), ev3))
+        return out
+    inf.classify_rows = timed
+    try:
+        for rep in range(a.repeats):
+            del spans[:]
+            wrong.zero_()
+            torch.cuda.synchronize()
+            t0 = time.time()
+            ev = inf.evaluate(model, x, rowptr, col, y, **kw)
+            torch.cuda.synchronize()
+            total = time.time() - t0
+            k_s = sum(e[0].elapsed_time(e[1]) for *_x, e in spans) / 1e3
+            t_s = sum(e[1].elapsed_time(e[2]) for *_x, e in spans) / 1e3
+            nbytes = sum(n * Cn * es + 16 * n for n, Cn, es, _e in spans)
+            one = {"pass": rep, "total_s_with_both_tails_and_spins": round(total, 3), "calls": len(spans),
+                   "rows": sum(n for n, *_r in spans), "classify_rows_s": round(k_s, 5), "torch_tail_s": round(t_s, 5),
+                   "torch_over_kernel": round(t_s / k_s, 2), "algorithmic_bytes": nbytes,
+                   "classify_rows_algorithmic_TBps": round(nbytes / k_s / 1e12, 3),
+                   "fraction_of_8_TBps_hbm_peak": round(nbytes / k_s / 8e12, 3),
+                   "rows_where_torch_argmax_differs": int(wrong), "correct": ev.correct, "loss": ev.loss}
+            res["passes"].append(one)
+            print(json.dumps(one), flush=True)
+            del ev
+    finally:
+        inf.classify_rows = inner
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:
