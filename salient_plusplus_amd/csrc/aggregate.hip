@@ -6,10 +6,8 @@
 // 16-B pieces; the first layer reads the batch's fp16 features directly (fp16 -> fp32 is exact, so
 // this equals converting the whole matrix first, which the reference model does, minus one pass
 // over 150 MB).  The linear layers stay library GEMMs.
-#include "spp_internal.h"
+#include "elem_io.hip.h"
 
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -19,45 +17,6 @@ namespace spp {
 
 constexpr int kAggNT = 256;
 
-struct f4 {
-  float x, y, z, w;
-};
-
-__device__ __forceinline__ f4 load4(const float* p) {
-  const float4 v = *reinterpret_cast<const float4*>(p);
-  return {v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ f4 load4(const __half* p) {
-  const uint2 raw = *reinterpret_cast<const uint2*>(p);
-  const __half2 a = *reinterpret_cast<const __half2*>(&raw.x), b = *reinterpret_cast<const __half2*>(&raw.y);
-  const float2 fa = __half22float2(a), fb = __half22float2(b);
-  return {fa.x, fa.y, fb.x, fb.y};
-}
-__device__ __forceinline__ float load1(const float* p) { return *p; }
-__device__ __forceinline__ float load1(const __half* p) { return __half2float(*p); }
-
-// bf16 rows (torch.autocast(dtype=torch.bfloat16)): bf16 -> fp32 is exact (the 16 bits become the high half); fp32 ->
-// bf16 is rounded once per stored element, to nearest even, by the packed hardware convert (v_cvt_pk_bf16_f32)
-using bf16 = __hip_bfloat16;
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f4 load4(const bf16* p) {
-  const uint2 raw = *reinterpret_cast<const uint2*>(p);
-  return {__uint_as_float(raw.x << 16), __uint_as_float(raw.x & 0xffff0000u), __uint_as_float(raw.y << 16),
-          __uint_as_float(raw.y & 0xffff0000u)};
-}
-__device__ __forceinline__ float load1(const bf16* p) {
-  return __uint_as_float((uint32_t)*reinterpret_cast<const uint16_t*>(p) << 16);
-}
-__device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t){a, b}, bf16x2_t));
-}
-__device__ __forceinline__ void store4(float* p, f4 v) { *reinterpret_cast<float4*>(p) = make_float4(v.x, v.y, v.z, v.w); }
-__device__ __forceinline__ void store4(bf16* p, f4 v) {
-  *reinterpret_cast<uint2*>(p) = make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
-}
-__device__ __forceinline__ void store1(float* p, float v) { *p = v; }
-__device__ __forceinline__ void store1(bf16* p, float v) { *p = __float2bfloat16(v); }
 // the same as float4, element 4*i .. 4*i+3 of p (the backward kernels' form)
 __device__ __forceinline__ float4 ld4(const float* p, int64_t i) { return reinterpret_cast<const float4*>(p)[i]; }
 __device__ __forceinline__ float4 ld4(const bf16* p, int64_t i) {
@@ -473,32 +432,6 @@ __global__ __launch_bounds__(kAggNT) void k_agg_bwd_gather(const int32_t* __rest
 
 // the fp16 flag of the entries that predate the element codes: any non-zero value means fp16
 static int32_t half_elem(int32_t is_half) { return is_half ? SPP_ELEM_F16 : SPP_ELEM_F32; }
-
-static int lanes_log2(int64_t pieces) {
-  int l = 0;
-  while ((1 << l) < pieces && l < 6) ++l;
-  return l;
-}
-
-// fn(Type<T>{}) for the element code `elem` (spp.h: SPP_ELEM_F32 / _F16 / _BF16; the caller has checked it);
-// with_elem_vec adds std::integral_constant<bool, VEC4>{}.  with_f32_bf16: the codes without fp16 (outputs, gradients).
-template <typename T> struct Type { using type = T; };
-template <class Fn>
-static void with_elem(int32_t elem, Fn&& fn) {
-  elem == SPP_ELEM_BF16 ? fn(Type<bf16>{}) : elem ? fn(Type<__half>{}) : fn(Type<float>{});
-}
-template <class Fn>
-static void with_elem_vec(int32_t elem, bool vec, Fn&& fn) {
-  with_elem(elem, [&](auto tin) { vec ? fn(tin, std::true_type{}) : fn(tin, std::false_type{}); });
-}
-template <class Fn>
-static void with_f32_bf16(int32_t elem, Fn&& fn) {
-  elem == SPP_ELEM_BF16 ? fn(Type<bf16>{}) : fn(Type<float>{});
-}
-static bool elem_ok(int32_t elem) { return elem == SPP_ELEM_F32 || elem == SPP_ELEM_F16 || elem == SPP_ELEM_BF16; }
-static bool f32_bf16_ok(int32_t elem) { return elem == SPP_ELEM_F32 || elem == SPP_ELEM_BF16; }
-static int64_t elem_bytes(int32_t elem) { return elem == SPP_ELEM_F32 ? 4 : elem == SPP_ELEM_FP8_E4M3 ? 1 : 2; }
-static bool aligned_to(const void* p, int64_t bytes) { return reinterpret_cast<uintptr_t>(p) % (uintptr_t)bytes == 0; }
 
 }  // namespace spp
 

@@ -22,12 +22,9 @@
 // dependent loads (id, label, the label's logit) one kind at a time, and the four xor trees step in one loop -- so a
 // wave has four independent chains in flight through the shuffles.
 // No atomics, no LDS, no workspace, every offset 64-bit.
-#include "spp_internal.h"
-
-#include <hip/hip_bf16.h>
+#include "elem_io.hip.h"
 
 #include <limits>
-#include <type_traits>
 
 namespace spp {
 namespace classify {
@@ -36,21 +33,11 @@ constexpr int kNT = 256;
 constexpr int kUnroll = 4;            // rows per lane group
 constexpr int kNoIndex = 0x7fffffff;  // loses every tie: no column has it (C < 2^31)
 
-using bf16 = __hip_bfloat16;
-
 template <typename T> constexpr int piece_width() { return 16 / (int)sizeof(T); }
-
-template <int W>
-struct Piece {
-  float v[W];
-};
-
-__device__ __forceinline__ float bf16_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf16_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
 
 // V columns from p (aligned to V elements) into o.v[k ..], converted to fp32 exactly
 template <int V, int W>
-__device__ __forceinline__ void load_cols(const float* p, Piece<W>& o, int k) {
+__device__ __forceinline__ void load_cols(const float* p, PieceN<W>& o, int k) {
   if constexpr (V == 4) {
     const float4 q = *reinterpret_cast<const float4*>(p);
     o.v[k] = q.x, o.v[k + 1] = q.y, o.v[k + 2] = q.z, o.v[k + 3] = q.w;
@@ -62,7 +49,7 @@ __device__ __forceinline__ void load_cols(const float* p, Piece<W>& o, int k) {
   }
 }
 template <int V, int W>
-__device__ __forceinline__ void load_cols(const bf16* p, Piece<W>& o, int k) {
+__device__ __forceinline__ void load_cols(const bf16* p, PieceN<W>& o, int k) {
   if constexpr (V == 8) {
     const uint4 q = *reinterpret_cast<const uint4*>(p);
     o.v[k] = bf16_lo(q.x), o.v[k + 1] = bf16_hi(q.x), o.v[k + 2] = bf16_lo(q.y), o.v[k + 3] = bf16_hi(q.y);
@@ -74,16 +61,16 @@ __device__ __forceinline__ void load_cols(const bf16* p, Piece<W>& o, int k) {
     const uint32_t q = *reinterpret_cast<const uint32_t*>(p);
     o.v[k] = bf16_lo(q), o.v[k + 1] = bf16_hi(q);
   } else {
-    o.v[k] = __uint_as_float((uint32_t)*reinterpret_cast<const uint16_t*>(p) << 16);
+    o.v[k] = bf16_lo(*reinterpret_cast<const uint16_t*>(p));
   }
 }
 
 // the first `valid` (0 .. W, a multiple of V: V divides C) columns of the piece at column c0 of `row`.  No branch: a
 // chunk of V columns past them is loaded from the row's first V columns instead (C >= V) and its slots are never used.
 template <typename T, int V>
-__device__ __forceinline__ Piece<piece_width<T>()> load_piece(const T* row, int64_t c0, int valid) {
+__device__ __forceinline__ PieceN<piece_width<T>()> load_piece(const T* row, int64_t c0, int valid) {
   constexpr int W = piece_width<T>();
-  Piece<W> o;
+  PieceN<W> o;
 #pragma unroll
   for (int k = 0; k < W; k += V) load_cols<V, W>(row + (k + V <= valid ? c0 + k : 0), o, k);
   return o;
@@ -113,7 +100,7 @@ __device__ __forceinline__ bool beats(float av, int ai, float bv, int bi) {
 // it is strictly above, or the first NaN.  !(v <= b.v) is "above or NaN"; a column past the row's end counts as -inf,
 // which that never takes.  (The lane starts at (-inf, its first column): a row of -inf predicts its first column.)
 template <int W>
-__device__ __forceinline__ void max_piece(Best& b, const Piece<W>& p, int c0, int valid) {
+__device__ __forceinline__ void max_piece(Best& b, const PieceN<W>& p, int c0, int valid) {
   const float ninf = -std::numeric_limits<float>::infinity();
 #pragma unroll
   for (int k = 0; k < W; ++k) {
@@ -142,7 +129,7 @@ __device__ __forceinline__ float exp_term(float z, float m) {
   return __builtin_amdgcn_exp2f(__fmul_rn(__fsub_rn(z, m), 1.44269504088896340736f));
 }
 template <int W>
-__device__ __forceinline__ void sum_piece(float& s, const Piece<W>& p, float m, int valid) {
+__device__ __forceinline__ void sum_piece(float& s, const PieceN<W>& p, float m, int valid) {
 #pragma unroll
   for (int k = 0; k < W; ++k) {
     const float t = __fadd_rn(s, exp_term(p.v[k], m));
@@ -164,7 +151,7 @@ __device__ __forceinline__ float nll_of(float s, float zy, float m, bool has) {
 
 template <typename T>
 __device__ __forceinline__ float load_one(const T* p) {
-  Piece<1> o;
+  PieceN<1> o;
   load_cols<1, 1>(p, o, 0);
   return o.v[0];
 }
@@ -219,7 +206,7 @@ __global__ __launch_bounds__(kNT) void k_classify_rows(const T* __restrict__ z, 
   }
   // one round: the rows' pieces, loaded once and kept; issued ahead of the labels' dependent loads
   const int c0 = l * W, valid = valid_cols<W>(c0, C);
-  Piece<W> p[kUnroll];
+  PieceN<W> p[kUnroll];
   if constexpr (kOneRound) {
 #pragma unroll
     for (int u = 0; u < kUnroll; ++u) p[u] = load_piece<T, V>(row[u], c0, valid);
@@ -280,8 +267,6 @@ __global__ __launch_bounds__(kNT) void k_classify_rows(const T* __restrict__ z, 
   }
 }
 
-template <typename T> struct Type { using type = T; };
-
 }  // namespace classify
 }  // namespace spp
 
@@ -308,13 +293,12 @@ extern "C" spp_status spp_classify_rows(const spp_classify_desc* desc, void* str
   SPP_REQUIRE(!lab || d.y_rows >= 0, "%s: negative y_rows (%lld)", who, (long long)d.y_rows);
   if (n == 0) return SPP_OK;
   const bool use_y = lab && d.y_rows >= 1;  // (labels of no rows: every row is unlabelled)
-  const int esize = d.z_elem == SPP_ELEM_F32 ? 4 : 2, W = 16 / esize;
+  const int esize = (int)elem_bytes(d.z_elem), W = 16 / esize;
   const int64_t pieces = ceil_div(C, (int64_t)W);
-  int lpr_log2 = 0;
-  while ((1ll << lpr_log2) < pieces && lpr_log2 < 6) ++lpr_log2;
+  const int lpr_log2 = lanes_log2(pieces);
   const bool one_round = pieces <= (1ll << lpr_log2);
   int V = W;  // columns per load: what the base, the stride and the row are multiples of
-  while (V > 1 && (reinterpret_cast<uintptr_t>(d.z_dev) % (uintptr_t)(V * esize) != 0 || z_stride % V != 0 || C % V != 0))
+  while (V > 1 && (!aligned_to(d.z_dev, V * esize) || z_stride % V != 0 || C % V != 0))
     V >>= 1;
   const int64_t grid = ceil_div(n, (int64_t)(kNT >> lpr_log2) * kUnroll);
   SPP_REQUIRE(grid < (1ll << 31), "%s: too many rows for one launch (n %lld)", who, (long long)n);

@@ -15,12 +15,7 @@
 // and the OUTPUT row is zeros (the target rule of the graph kernels): a select, not a branch.  The vector form moves
 // W = 4 columns per lane when any of z, r, out is fp32 and W = 8 when all are 16-bit, so the widest operand moves in
 // 16-byte pieces; the scalar form is the same code with W = 1.  No atomics, no LDS, every offset 64-bit.
-#include "spp_internal.h"
-
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
-
-#include <type_traits>
+#include "elem_io.hip.h"
 
 namespace spp {
 namespace resinc {
@@ -28,24 +23,14 @@ namespace resinc {
 constexpr int kNT = 256;
 constexpr int kUnroll = 4;  // rows in flight per lane group
 
-using bf16 = __hip_bfloat16;
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 struct NoRes {};  // the residual's element type when there is none
 
-template <int W>
-struct Piece {
-  float v[W];
-};
-
-__device__ __forceinline__ float bf16_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf16_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
 __device__ __forceinline__ float2 half2_of(uint32_t w) { return __half22float2(*reinterpret_cast<const __half2*>(&w)); }
 
-// loads convert to fp32 exactly
+// loads convert to fp32 exactly (elem_io.hip.h: PieceN, the bf16 halves and the packed store convert)
 template <int W>
-__device__ __forceinline__ Piece<W> load(const float* p) {
-  Piece<W> o;
+__device__ __forceinline__ PieceN<W> load(const float* p) {
+  PieceN<W> o;
   if constexpr (W == 1) {
     o.v[0] = *p;
   } else {
@@ -58,8 +43,8 @@ __device__ __forceinline__ Piece<W> load(const float* p) {
   return o;
 }
 template <int W>
-__device__ __forceinline__ Piece<W> load(const bf16* p) {
-  Piece<W> o;
+__device__ __forceinline__ PieceN<W> load(const bf16* p) {
+  PieceN<W> o;
   if constexpr (W == 1) {
     o.v[0] = __uint_as_float((uint32_t)*reinterpret_cast<const uint16_t*>(p) << 16);
   } else if constexpr (W == 4) {
@@ -73,8 +58,8 @@ __device__ __forceinline__ Piece<W> load(const bf16* p) {
   return o;
 }
 template <int W>
-__device__ __forceinline__ Piece<W> load(const __half* p) {
-  Piece<W> o;
+__device__ __forceinline__ PieceN<W> load(const __half* p) {
+  PieceN<W> o;
   if constexpr (W == 1) {
     o.v[0] = __half2float(*p);
   } else if constexpr (W == 4) {
@@ -89,16 +74,13 @@ __device__ __forceinline__ Piece<W> load(const __half* p) {
   return o;
 }
 template <int W>
-__device__ __forceinline__ Piece<W> load(const NoRes*) {
-  return Piece<W>{};
+__device__ __forceinline__ PieceN<W> load(const NoRes*) {
+  return PieceN<W>{};
 }
 
-__device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t){a, b}, bf16x2_t));
-}
 // a bf16 store rounds once, to nearest even
 template <int W>
-__device__ __forceinline__ void store(float* p, const Piece<W>& o) {
+__device__ __forceinline__ void store(float* p, const PieceN<W>& o) {
   if constexpr (W == 1) {
     *p = o.v[0];
   } else {
@@ -107,7 +89,7 @@ __device__ __forceinline__ void store(float* p, const Piece<W>& o) {
   }
 }
 template <int W>
-__device__ __forceinline__ void store(bf16* p, const Piece<W>& o) {
+__device__ __forceinline__ void store(bf16* p, const PieceN<W>& o) {
   if constexpr (W == 1) {
     *p = __float2bfloat16(o.v[0]);
   } else if constexpr (W == 4) {
@@ -170,8 +152,8 @@ __device__ __forceinline__ void tile_body(const Tz* __restrict__ z, const Tr* __
     const int64_t p = p0 + l;
     const bool on = kFull || p < pieces;
     const int64_t c = (on ? p : 0) * W;
-    const Piece<W> av = load<W>(a.a + c), bv = load<W>(a.b + c);
-    Piece<W> zv[kUnroll], rv[kUnroll];
+    const PieceN<W> av = load<W>(a.a + c), bv = load<W>(a.b + c);
+    PieceN<W> zv[kUnroll], rv[kUnroll];
 #pragma unroll
     for (int u = 0; u < kUnroll; ++u) zv[u] = load<W>(z + i[u] * a.z_stride + c);
     if constexpr (kRes) {
@@ -180,7 +162,7 @@ __device__ __forceinline__ void tile_body(const Tz* __restrict__ z, const Tr* __
     }
 #pragma unroll
     for (int u = 0; u < kUnroll; ++u) {
-      Piece<W> o;
+      PieceN<W> o;
 #pragma unroll
       for (int k = 0; k < W; ++k) {
         const float y = tail<kRes>(av.v[k], zv[u].v[k], bv.v[k], a.slope, kRes ? rv[u].v[k] : 0.f);
@@ -207,11 +189,6 @@ __global__ __launch_bounds__(kNT) void k_resinc_epilogue(const Tz* __restrict__ 
   else
     tile_body<Tz, Tr, Tout, W, false>(z, r, out, a, base);
 }
-
-static int64_t elem_bytes(int32_t elem) { return elem == SPP_ELEM_F32 ? 4 : 2; }
-static bool aligned_to(const void* p, int64_t bytes) { return reinterpret_cast<uintptr_t>(p) % (uintptr_t)bytes == 0; }
-
-template <typename T> struct Type { using type = T; };
 
 }  // namespace resinc
 }  // namespace spp
@@ -253,9 +230,7 @@ extern "C" spp_status spp_resinc_epilogue(const spp_resinc_epilogue_desc* desc, 
   const bool vec = C % W == 0 && z_stride % W == 0 && out_stride % W == 0 && (!res || r_stride % W == 0) &&
                    aligned_to(d.z_dev, W * elem_bytes(d.z_elem)) && aligned_to(d.out_dev, W * elem_bytes(d.out_elem)) &&
                    (!res || aligned_to(d.r_dev, W * elem_bytes(d.r_elem))) && aligned_to(d.a_dev, 16) && aligned_to(d.b_dev, 16);
-  const int64_t pieces = vec ? C / W : C;
-  int lpr_log2 = 0;
-  while ((1 << lpr_log2) < pieces && lpr_log2 < 6) ++lpr_log2;
+  const int lpr_log2 = lanes_log2(vec ? C / W : C);
   const int64_t grid = ceil_div(n, (int64_t)(kNT >> lpr_log2) * kUnroll);
   SPP_REQUIRE(grid < (1ll << 31), "%s: too many rows for one launch (n %lld)", who, (long long)n);
   Args a{};

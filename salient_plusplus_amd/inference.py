@@ -96,6 +96,36 @@ def _check_heads(what, heads, Fdim):
         raise ValueError(f"{what}: heads must be a positive int that divides F = {Fdim}, got {heads!r}")
 
 
+def _check_epilogue(what, epilogue):
+    if epilogue not in _EPILOGUES:
+        raise ValueError(f"{what}: epilogue must be 'mean', 'operand' or 'sum', got {epilogue!r}")
+
+
+def _check_fp32(what, name, t, shape, meaning):
+    """a contiguous fp32 tensor of exactly ``shape`` that carries no gradient"""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) \
+            or not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be a contiguous fp32 tensor of shape {list(shape)} ({meaning})")
+    if t.requires_grad:
+        raise RuntimeError(f"{what}: {name} requires grad, and inference is forward only (detach it)")
+
+
+def _check_row_address(what, noun, n, row0, row_ids):
+    """the rows that go with the n rows of z: a slab (``row0`` >= 0) xor a list (``row_ids``: contiguous int64 [n]).
+    Returns row0 as an int, None with a list."""
+    if (row0 is None) == (row_ids is None):
+        raise ValueError(f"{what}: address {noun} either as a slab (row0) or as row_ids"
+                         + (", not both" if row0 is not None else ""))
+    if row_ids is None:
+        row0 = int(row0)
+        if row0 < 0:
+            raise ValueError(f"{what}: row0 must not be negative, got {row0}")
+    elif not isinstance(row_ids, torch.Tensor) or row_ids.dtype != torch.int64 or tuple(row_ids.shape) != (n,) \
+            or not row_ids.is_contiguous():
+        raise ValueError(f"{what}: row_ids must be a contiguous int64 tensor of shape [{n}] (one entry per row of z)")
+    return row0
+
+
 def _check_targets(what, N, row0, num_targets, target_ids):
     """(row0 or -1, target_ids or None, T) of the two target forms: a slab inside the graph's N nodes, or a contiguous
     int64 list"""
@@ -281,8 +311,7 @@ def graph_aggregate(x, rowptr, col, *, row0=None, num_targets=None, target_ids=N
     _check_matrix(x, what)
     N, Fdim = x.shape
     _check_graph(what, N, rowptr, col)
-    if epilogue not in _EPILOGUES:
-        raise ValueError(f"{what}: epilogue must be 'mean', 'operand' or 'sum', got {epilogue!r}")
+    _check_epilogue(what, epilogue)
     _check_out_dtype(what, out_dtype)
     row0, target_ids, T = _check_targets(what, N, row0, num_targets, target_ids)
     workspace = _on_device(what, "x, rowptr, col, target_ids and workspace", x.device, [x, rowptr, col, target_ids],
@@ -308,8 +337,7 @@ def graph_aggregate_parts(parts, part_offsets, rowptr, col, *, row0=None, num_ta
     off = _check_offsets(part_offsets, what)
     *src, dev = _parts_source(parts, off, dtype, F, what)
     _check_graph(what, off[-1], rowptr, col, parts=True)
-    if epilogue not in _EPILOGUES:
-        raise ValueError(f"{what}: epilogue must be 'mean', 'operand' or 'sum', got {epilogue!r}")
+    _check_epilogue(what, epilogue)
     _check_out_dtype(what, out_dtype)
     row0, target_ids, T = _check_targets(what, off[-1], row0, num_targets, target_ids)
     width = 2 * src[3] if epilogue == "operand" else src[3]
@@ -343,11 +371,7 @@ def graph_gat_aggregate(h, a_src, a_dst, rowptr, col, *, heads, negative_slope=0
     _check_graph(what, N, rowptr, col)
     _check_heads(what, heads, Fdim)
     for name, t in (("a_src", a_src), ("a_dst", a_dst)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (N, heads) \
-                or not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be a contiguous fp32 tensor of shape [{N}, {heads}] (nodes, heads)")
-        if t.requires_grad:
-            raise RuntimeError(f"{what}: {name} requires grad, and inference is forward only (detach it)")
+        _check_fp32(what, name, t, (N, heads), "nodes, heads")
     _check_out_dtype(what, out_dtype)
     row0, target_ids, T = _check_targets(what, N, row0, num_targets, target_ids)
     workspace = _on_device(what, "h, a_src, a_dst, rowptr, col, target_ids and workspace", h.device,
@@ -424,10 +448,7 @@ def resinc_epilogue(z, scale, shift, *, negative_slope, residual=None, row0=None
     if Cdim < 1:
         raise ValueError(f"{what}: z needs at least one column, got {tuple(z.shape)}")
     for name, t in (("scale", scale), ("shift", shift)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (Cdim,) or not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be a contiguous fp32 tensor of shape [{Cdim}] (one entry per column)")
-        if t.requires_grad:
-            raise RuntimeError(f"{what}: {name} requires grad, and inference is forward only (detach it)")
+        _check_fp32(what, name, t, (Cdim,), "one entry per column")
     if residual is None:
         if row0 is not None or row_ids is not None:
             raise ValueError(f"{what}: row0 / row_ids address the residual's rows, and there is no residual")
@@ -436,16 +457,7 @@ def resinc_epilogue(z, scale, shift, *, negative_slope, residual=None, row0=None
         if residual.size(1) != Cdim or residual.size(0) < 1:
             raise ValueError(f"{what}: residual must have z's {Cdim} columns and at least one row, got "
                              f"{tuple(residual.shape)}")
-        if (row0 is None) == (row_ids is None):
-            raise ValueError(f"{what}: address the residual's rows either as a slab (row0) or as row_ids"
-                             + (", not both" if row0 is not None else ""))
-        if row_ids is None:
-            row0 = int(row0)
-            if row0 < 0:
-                raise ValueError(f"{what}: row0 must not be negative, got {row0}")
-        elif not isinstance(row_ids, torch.Tensor) or row_ids.dtype != torch.int64 or tuple(row_ids.shape) != (n,) \
-                or not row_ids.is_contiguous():
-            raise ValueError(f"{what}: row_ids must be a contiguous int64 tensor of shape [{n}] (one entry per row of z)")
+        row0 = _check_row_address(what, "the residual's rows", n, row0, row_ids)
     if out is None:
         out_dtype = torch.float32 if out_dtype is None else out_dtype
         _check_out_dtype(what, out_dtype)
@@ -519,16 +531,7 @@ def classify_rows(z, y=None, *, row0=None, row_ids=None, pred=None, nll=None):
             raise TypeError(f"{what}: y must be a torch.Tensor, got {type(y).__name__}")
         if y.dtype != torch.int64 or y.dim() != 1 or not y.is_contiguous():
             raise ValueError(f"{what}: y must be a contiguous 1-D int64 tensor, got {tuple(y.shape)} {y.dtype}")
-        if (row0 is None) == (row_ids is None):
-            raise ValueError(f"{what}: address the labels y either as a slab (row0) or as row_ids"
-                             + (", not both" if row0 is not None else ""))
-        if row_ids is None:
-            row0 = int(row0)
-            if row0 < 0:
-                raise ValueError(f"{what}: row0 must not be negative, got {row0}")
-        elif not isinstance(row_ids, torch.Tensor) or row_ids.dtype != torch.int64 or tuple(row_ids.shape) != (n,) \
-                or not row_ids.is_contiguous():
-            raise ValueError(f"{what}: row_ids must be a contiguous int64 tensor of shape [{n}] (one entry per row of z)")
+        row0 = _check_row_address(what, "the labels y", n, row0, row_ids)
     if pred is not None:
         _check_vector(what, "pred", pred, torch.int64, n)
     if nll is not None:
