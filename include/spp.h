@@ -1249,6 +1249,54 @@ typedef struct spp_classify_desc {
 
 spp_status spp_classify_rows(const spp_classify_desc* desc, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * f3n  The receptive field of a few nodes: what touches the resident graph's rows when the nodes within h hops of
+ *      `nodes` are numbered and their rows copied into a compact CSR that the f3g kernels run on unchanged.
+ *
+ *      The field's nodes carry SLOTS: depth 0 is the distinct ids of `nodes`, depth d every neighbour of a node of depth
+ *      d-1 that has no smaller depth; slots count depth by depth, in ascending id order within a depth.  The caller keeps
+ *        slot   int32 [num_nodes], -1 = not in the field
+ *        flag   one byte per node, all 0 between hops
+ *      and numbers a depth between the two entries (compact the flags into the ascending list of new ids, scatter their
+ *      slots, clear the flags); no atomic decides a slot.
+ *
+ *   spp_field_mark: flag[j] = 1 for every entry j of the row of every frontier node ids[i], i < num_ids, that lies in
+ *     [0, num_nodes) and has slot[j] < 0.  Plain byte stores; every writer of a flag stores the same value, so the result
+ *     is the same from run to run.  Reads slot, writes flag only.
+ *   spp_field_rows: for i < num_ids, fcol[frowptr[i] + k] = slot[col[rowptr[ids[i]] + k]] for every k of the node's row:
+ *     the WHOLE row in CSR order, every entry replaced by its slot (multi-edges and self-loops stay, the degree is
+ *     unchanged).  frowptr int64 [num_ids + 1] is the prefix sum of those degrees, fcol int64 [fcol_len].  An entry
+ *     outside [0, num_nodes) or without a slot is written as -1 (a correctly built field has none).  If frowptr gives a
+ *     row less room than its degree, or leaves [0, fcol_len], the copy is cut to what fits: nothing is written outside
+ *     [frowptr[i], frowptr[i + 1]) or outside fcol.
+ *
+ *   An id outside [0, num_nodes) is an empty row in both entries: no fault, no error.  Load balance as f3g: lane groups
+ *   finish the rows of at most C_f = spp_field_chunk() entries, a longer row's index goes to a list in the workspace and a
+ *   second launch gives each listed row a workgroup.  Every offset is 64-bit.  Workspace: spp_field_workspace_bytes(num_ids)
+ *   bytes, 16-byte aligned, the caller's; its contents mean nothing between calls.  Each entry enqueues a 16-byte memset and
+ *   two launches on `stream` and never waits for the device.
+ *   Refused with SPP_ERR_INVALID before anything is enqueued: a NULL descriptor; a negative num_nodes, num_ids or
+ *   fcol_len; a missing, misaligned or too small workspace; and, unless num_ids == 0 (SPP_OK, nothing enqueued), a NULL
+ *   rowptr, col, ids or slot, an empty graph, a NULL flag (mark), a NULL frowptr or a NULL fcol with fcol_len > 0 (rows).
+ * ------------------------------------------------------------------------- */
+typedef struct spp_field_desc {
+  const int64_t* rowptr_dev;
+  const int64_t* col_dev;
+  int64_t num_nodes;          /* N: the graph's nodes */
+  const int64_t* ids_dev;     /* mark: the frontier; rows: the field's rows by slot.  int64 [num_ids], global ids */
+  int64_t num_ids;
+  const int32_t* slot_dev;    /* int32 [num_nodes], -1 = not in the field */
+  uint8_t* flag_dev;          /* mark: [num_nodes] bytes; unused by rows */
+  const int64_t* frowptr_dev; /* rows: int64 [num_ids + 1]; unused by mark */
+  int64_t* fcol_dev;          /* rows: int64 [fcol_len] */
+  int64_t fcol_len;           /* rows: frowptr[num_ids]; 0 for mark */
+} spp_field_desc;
+
+int64_t spp_field_chunk(void);
+int64_t spp_field_workspace_bytes(int64_t num_ids);
+spp_status spp_field_mark(const spp_field_desc* desc, void* workspace_dev, int64_t workspace_bytes, void* stream);
+spp_status spp_field_rows(const spp_field_desc* desc, void* workspace_dev, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,6 +133,13 @@ class ClassifyDesc(C.Structure):
                 ("y_dev", p), ("y_rows", i64), ("y_row0", i64), ("row_ids_dev", p), ("pred_dev", p), ("nll_dev", p)]
 
 
+class FieldDesc(C.Structure):
+    """spp_field_desc: the frontier (spp_field_mark) or the field's rows by slot (spp_field_rows) over the graph, with the
+    slot map, the flags (mark) and the field's CSR (rows)"""
+    _fields_ = [("rowptr_dev", p), ("col_dev", p), ("num_nodes", i64), ("ids_dev", p), ("num_ids", i64), ("slot_dev", p),
+                ("flag_dev", p), ("frowptr_dev", p), ("fcol_dev", p), ("fcol_len", i64)]
+
+
 class GroupOut(C.Structure):
     _fields_ = [("mfg", MfgOut), ("x_out", p), ("y_out", p)]
 
@@ -268,6 +275,10 @@ SIGNATURES = {
     "spp_graph_gat_parts_forward": (C.c_int, [C.POINTER(GraphGatPartsDesc), p, i64, p]),
     "spp_resinc_epilogue": (C.c_int, [C.POINTER(ResincEpilogueDesc), p]),
     "spp_classify_rows": (C.c_int, [C.POINTER(ClassifyDesc), p]),
+    "spp_field_chunk": (i64, []),
+    "spp_field_workspace_bytes": (i64, [i64]),
+    "spp_field_mark": (C.c_int, [C.POINTER(FieldDesc), p, i64, p]),
+    "spp_field_rows": (C.c_int, [C.POINTER(FieldDesc), p, i64, p]),
 }
 SPP_COMM_ID_BYTES = 128
 SPP_IPC_HANDLE_BYTES = 64

@@ -22,7 +22,12 @@ and ``GIN.inference``), ``partitioned_inference`` the partitioned one for all fo
 or ``IpcPeers`` (one process per rank on one node) between the ranks.  Every driver hands its last layer's logits, tile by
 tile, to a sink: ``_LogProbs`` (log_softmax into the [rows, classes] matrix those entries return) or ``_Classify``
 (``classify_rows`` into pred [rows] and nll [rows]), which is what ``evaluate`` and ``partitioned_evaluate`` run: the same
-pass, predictions, per-split accuracy and loss out, and no [rows, classes] matrix anywhere."""
+pass, predictions, per-split accuracy and loss out, and no [rows, classes] matrix anywhere.
+
+A layer loop follows a plan, one ``_Step`` a layer: which rows it computes, over which graph.  The whole-graph entries'
+plan is every row of every layer but the last; ``field_inference`` and ``field_evaluate`` score a few ``nodes`` with the
+same loops over a plan built from their receptive field -- the nodes within L - 1 hops, numbered and copied into a compact
+CSR by ``ReceptiveFields`` (csrc/field.hip: ``spp_field_mark``, ``spp_field_rows``) -- and return the same bits."""
 import ctypes as C
 import threading
 
@@ -608,21 +613,25 @@ class _Resident:
         """where layer i's rows go: [rows, width], read back as ``cur`` (and as the residual) by layer i + 1"""
         return torch.empty((rows, width), dtype=dtype, device=self.dev)
 
-    def aggregate(self, i, cur, epilogue, self_scale, s, ids, T, out, ws):
-        """layer i's input ``cur`` aggregated for the rank's local slab [s, s + T), or for the global ``ids``"""
-        return _agg_launch(cur, self.rowptr, self.col, epilogue, self_scale, -1 if ids is not None else s, ids, T, out, ws)
+    def aggregate(self, i, cur, epilogue, self_scale, s, ids, T, out, ws, graph=None):
+        """layer i's input ``cur`` aggregated for the rank's local slab [s, s + T), or for the global ``ids``; over
+        ``graph`` = (rowptr, col) whose ids are rows of ``cur`` when the layer's plan names one (a receptive field's)"""
+        rowptr, col = graph or (self.rowptr, self.col)
+        return _agg_launch(cur, rowptr, col, epilogue, self_scale, -1 if ids is not None else s, ids, T, out, ws)
 
-    def gat_rows(self, H, Cc, dtype):
-        """(h, logits) of a GAT layer: the projected rows [n_local, H * Cc] and where ``put_logits`` writes"""
-        h = torch.empty((self.n_local, H * Cc), dtype=dtype, device=self.dev)
-        return h, tuple(torch.empty((self.n_local, H), dtype=torch.float32, device=self.dev) for _ in range(2))
+    def gat_rows(self, rows, H, Cc, dtype):
+        """(h, logits) of a GAT layer over ``rows`` input rows: the projected rows [rows, H * Cc] and where
+        ``put_logits`` writes"""
+        h = torch.empty((rows, H * Cc), dtype=dtype, device=self.dev)
+        return h, tuple(torch.empty((rows, H), dtype=torch.float32, device=self.dev) for _ in range(2))
 
     def put_logits(self, logits, r, n, a):
         H = a.size(1) // 2
         logits[0][r:r + n], logits[1][r:r + n] = a[:n, :H], a[:n, H:]
 
-    def attend(self, h, logits, conv, relu, s, ids, T, out, ws):
-        return _gat_launch(h, logits[0], logits[1], self.rowptr, self.col, conv.heads, conv.negative_slope, relu,
+    def attend(self, h, logits, conv, relu, s, ids, T, out, ws, graph=None):
+        rowptr, col = graph or (self.rowptr, self.col)
+        return _gat_launch(h, logits[0], logits[1], rowptr, col, conv.heads, conv.negative_slope, relu,
                            -1 if ids is not None else s, ids, T, out, ws)
 
 
@@ -675,7 +684,7 @@ class _Partitioned:
     def layer_rows(self, i, last, rows, width, dtype):
         return torch.empty((rows, width), dtype=dtype, device=self.dev) if last else self.bufs[i % len(self.bufs)]
 
-    def aggregate(self, i, cur, epilogue, self_scale, s, ids, T, out, ws):
+    def aggregate(self, i, cur, epilogue, self_scale, s, ids, T, out, ws, graph=None):
         src = self.sources[0] if i == 0 else self.sources[1 + (i - 1) % len(self.bufs)]      # (``cur``, as published)
         return _agg_parts_launch(src, self.off, self.rowptr, self.col, epilogue, self_scale,
                                  -1 if ids is not None else self.lo + s, ids, T, out, ws)
@@ -686,13 +695,13 @@ class _Partitioned:
         self.hbuf, self.abuf = self._buffer(Fmax, dtype), self._buffer(2 * Hmax, torch.float32)
         self.h_src, self.a_src = self._share(self.hbuf), self._share(self.abuf, "logits part")
 
-    def gat_rows(self, H, Cc, dtype):
+    def gat_rows(self, rows, H, Cc, dtype):
         return self.hbuf[:, :H * Cc], self.abuf[:, :2 * H]
 
     def put_logits(self, logits, r, n, a):
         logits[r:r + n] = a[:n]
 
-    def attend(self, h, logits, conv, relu, s, ids, T, out, ws):
+    def attend(self, h, logits, conv, relu, s, ids, T, out, ws, graph=None):
         return _gat_parts_launch(self.h_src[:2] + (h.dtype, h.size(1)), self.a_src[:2], self.off, self.rowptr, self.col,
                                  conv.heads, conv.negative_slope, relu, -1 if ids is not None else self.lo + s, ids, T,
                                  out, ws)
@@ -800,23 +809,54 @@ def _gin_layer(conv, amp):
     return "sum", conv._scale(), fn
 
 
-def _slabs(place, ids, rows_per_slab):
-    """(first row, rows, the slab's ids or None) over the rank's own rows, or over ``ids``"""
-    rows = ids.numel() if ids is not None else place.n_local
+def _slabs(rows, ids, rows_per_slab):
+    """(first row, rows, the slab's ids or None) over the rows [0, rows), or over the ``rows`` entries of ``ids``"""
     for s in range(0, rows, rows_per_slab):
         e = min(rows, s + rows_per_slab)
         yield s, e - s, ids[s:e] if ids is not None else None
 
 
-def _conv_layers(model, place, nodes, rows_per_slab, act_dtype, sink):
+class _Step:
+    """One conv layer of a plan: the layer computes ``rows`` output rows -- the targets ``ids`` (a list) or, with None,
+    the slab [0, rows) -- over ``graph`` = (rowptr, col), None for the placement's own.  ``names``: the output rows'
+    global ids as the sink of the last layer wants them, None when they are the rank's rows 0 .. rows in order."""
+
+    def __init__(self, rows, ids=None, graph=None, names=None):
+        self.rows, self.ids, self.graph, self.names = rows, ids, graph, names
+
+
+def _whole_graph_plan(place, nodes, n_layers):
+    """the plan of the whole-graph entries: every layer for all the rank's rows over the placement's graph, the last one
+    for ``nodes`` only when they are given"""
+    last = _Step(place.n_local) if nodes is None else _Step(nodes.numel(), ids=nodes, names=nodes)
+    return [_Step(place.n_local) for _ in range(n_layers - 1)] + [last]
+
+
+def _field_plan(field, n_layers):
+    """the plan of ``field_inference`` over a field of h = n_layers - 1 hops: layer 0 reads the table in place over the
+    ORIGINAL graph, for every node of the field (``target_ids=field.ids``); layer i >= 1 runs on the field's CSR as the
+    slab [0, sizes[h - i]) and reads layer i - 1's rows, which are the slots below sizes[h - i + 1] that its rows name;
+    the last layer leaves the distinct nodes' rows, which the sink labels by their global ids"""
+    h = n_layers - 1
+    if field.hops != h:
+        raise ValueError(f"a model of {n_layers} conv layers is scored over a field of {h} hops, got one of {field.hops}")
+    graph = (field.rowptr, field.col)
+    steps = [_Step(field.sizes[h], ids=field.ids)] + [_Step(field.sizes[h - i], graph=graph) for i in range(1, n_layers)]
+    steps[-1].names = field.ids[:field.sizes[0]]
+    return steps
+
+
+def _conv_layers(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None):
     """SAGE and GIN, as ``layerwise_inference`` describes them; the last layer's logits go to ``sink``, tile by tile.
     Resident, layer i-1's matrix is dropped as soon as layer i is complete, so two [N, hidden] matrices are live at a
-    boundary; partitioned, the layers alternate between the (at most two) published buffers."""
+    boundary; partitioned, the layers alternate between the (at most two) published buffers.  ``plan``: one ``_Step`` a
+    layer (rows, targets and graph); None is ``_whole_graph_plan``."""
     from .models import GIN
     gin, amp = isinstance(model, GIN), act_dtype == torch.bfloat16
     n_layers, dev = len(model.convs), place.dev
+    plan = plan or _whole_graph_plan(place, nodes, n_layers)
     place.open(min(2, n_layers - 1), model.hidden_channels, act_dtype)
-    ws = torch.empty(graph_agg_workspace_bytes(min(rows_per_slab, max(place.n_local, nodes.numel() if nodes is not None else 0))),
+    ws = torch.empty(graph_agg_workspace_bytes(min(rows_per_slab, max([place.n_local] + [st.rows for st in plan]))),
                      dtype=torch.uint8, device=dev)
 
     def head(h):                                         # what follows the last conv layer: the logits
@@ -829,17 +869,17 @@ def _conv_layers(model, place, nodes, rows_per_slab, act_dtype, sink):
     for i, conv in enumerate(model.convs):
         last = i == n_layers - 1
         epilogue, scale, fn = _gin_layer(conv, amp) if gin else _sage_layer(conv, last, act_dtype)
-        ids = nodes if last else None
-        rows = ids.numel() if ids is not None else place.n_local
+        step = plan[i]
+        rows, names = step.rows, step.names
         nxt = None
         if last:
             sink.open(place, rows, (model.lin2 if gin else conv.lin_l).out_features)
-        for s, T, tids in _slabs(place, ids, rows_per_slab):
+        for s, T, tids in _slabs(rows, step.ids, rows_per_slab):
             A = torch.empty((T, cur.size(1) * (2 if epilogue == "operand" else 1)), dtype=act_dtype, device=dev)
-            place.aggregate(i, cur, epilogue, scale, s, tids, T, A, ws)
+            place.aggregate(i, cur, epilogue, scale, s, tids, T, A, ws, step.graph)
             for r, n, tile in _row_tiles(A):
                 if last:
-                    sink.put(s + r, n, head(fn(tile)), tids[r:r + n] if tids is not None else None)
+                    sink.put(s + r, n, head(fn(tile)), names[s + r:s + r + n] if names is not None else None)
                     continue
                 h = fn(tile)
                 if nxt is None:
@@ -852,7 +892,7 @@ def _conv_layers(model, place, nodes, rows_per_slab, act_dtype, sink):
     return sink.result()
 
 
-def _gat_layers(model, place, nodes, rows_per_slab, act_dtype, sink):
+def _gat_layers(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None):
     """GAT, in PyG's project-first order (training aggregates first, _GatLayer / _GatLayerMH, because an MFG hop has
     many sources per target; over the whole graph T = S = N, that saving is gone, and the aggregate-first intermediate
     would be [T, H, K] fp32 per slab).  Per layer:
@@ -875,8 +915,9 @@ def _gat_layers(model, place, nodes, rows_per_slab, act_dtype, sink):
     = 153 GB in bf16 for H = 4 and 172 classes, which does not fit next to a 57 GB ``cur``, 26 GB of graph and 28 GB of
     features on one 288 GB MI355X.  The reference's model has H = 1 (38 GB).  Partitioned: ``partitioned_inference``."""
     n_layers, dev = len(model.convs), place.dev
+    plan = plan or _whole_graph_plan(place, nodes, n_layers)     # (one ``_Step`` a layer, as in ``_conv_layers``)
     place.open_gat(max(c.heads * c.out_channels for c in model.convs), max(c.heads for c in model.convs), act_dtype)
-    ws = torch.empty(graph_gat_workspace_bytes(min(rows_per_slab, max(place.n_local, nodes.numel() if nodes is not None else 0))),
+    ws = torch.empty(graph_gat_workspace_bytes(min(rows_per_slab, max([place.n_local] + [st.rows for st in plan]))),
                      dtype=torch.uint8, device=dev)
     cur = place.x
     for i, conv in enumerate(model.convs):
@@ -886,24 +927,24 @@ def _gat_layers(model, place, nodes, rows_per_slab, act_dtype, sink):
         att = torch.stack([conv.att_src.view(H, Cc), conv.att_dst.view(H, Cc)]).to(torch.float32)
         V = torch.einsum("shc,hck->shk", att, W.to(torch.float32).view(H, Cc, -1)).reshape(2 * H, -1)   # [V_src; V_dst]
         Wt, Vt = W.to(act_dtype).t(), V.t().contiguous()
-        h, logits = place.gat_rows(H, Cc, act_dtype)
+        h, logits = place.gat_rows(cur.size(0), H, Cc, act_dtype)
         for r, n, tile in _row_tiles(cur):
             h[r:r + n] = (tile.to(act_dtype) @ Wt)[:n]
             place.put_logits(logits, r, n, tile.to(torch.float32) @ Vt)
         del cur                                          # (layer i-1's matrix; layer 1's is the caller's table)
         place.boundary()                                 # every rank's h and logits of this layer are complete
-        ids = nodes if last else None
-        rows = ids.numel() if ids is not None else place.n_local
+        step = plan[i]
+        rows, names = step.rows, step.names
         if last:
             nxt = None
             sink.open(place, rows, Cc)
         else:
             nxt = torch.empty((rows, H * Cc), dtype=act_dtype, device=dev)
-        for s, T, tids in _slabs(place, ids, rows_per_slab):
+        for s, T, tids in _slabs(rows, step.ids, rows_per_slab):
             out = nxt[s:s + T] if not last else torch.empty((T, H * Cc), dtype=torch.float32, device=dev)
-            place.attend(h, logits, conv, not last, s, tids, T, out, ws)
+            place.attend(h, logits, conv, not last, s, tids, T, out, ws, step.graph)
             if last:                                     # concat=False: the mean of the heads (H = 1: the head itself)
-                sink.put(s, T, out.view(T, H, Cc).mean(1) if H > 1 else out, tids)
+                sink.put(s, T, out.view(T, H, Cc).mean(1) if H > 1 else out, names[s:s + T] if names is not None else None)
         cur = nxt
         del h, logits                                    # (resident: drops them)
         place.boundary()                                 # every rank has finished reading this layer's h
@@ -973,8 +1014,9 @@ def _resinc_layers(model, place, nodes, rows_per_slab, act_dtype, sink):
         Wt = W.to(act_dtype).t()
         bias = bias.to(act_dtype) if bias is not None else None
         ids = nodes if last else None
-        nxt = place.layer_rows(i, last, ids.numel() if ids is not None else place.n_local, hidden, act_dtype)
-        for s, T, tids in _slabs(place, ids, rows_per_slab):
+        rows = ids.numel() if ids is not None else place.n_local
+        nxt = place.layer_rows(i, last, rows, hidden, act_dtype)
+        for s, T, tids in _slabs(rows, ids, rows_per_slab):
             A = torch.empty((T, 2 * cur.size(1)), dtype=act_dtype, device=dev)
             place.aggregate(i, cur, "operand", 0.0, s, tids, T, A, ws)
             for r, n, tile in _row_tiles(A):
@@ -1026,7 +1068,7 @@ def _check_run(what, act_dtype, rows_per_slab, nodes):
     return rows_per_slab
 
 
-def _score(model, place, nodes, rows_per_slab, act_dtype, sink):
+def _score(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None):
     """the frame of every driver: eval mode (restored), no gradient, autocast off, the table's device current; a rank
     that fails aborts the placement, so that its peers raise instead of waiting, and every mapping is closed"""
     from .models import GAT, SAGEResInception
@@ -1037,6 +1079,8 @@ def _score(model, place, nodes, rows_per_slab, act_dtype, sink):
     try:
         with torch.no_grad(), torch.autocast("cuda", enabled=False), torch.cuda.device(place.dev):
             place.bind()
+            if plan is not None:                         # (a receptive field's: SAGE, GIN and GAT)
+                return layers(model, place, nodes, rows_per_slab, act_dtype, sink, plan)
             return layers(model, place, nodes, rows_per_slab, act_dtype, sink)
     except BaseException:
         place.abort()
@@ -1137,6 +1181,257 @@ def evaluate(model, x, rowptr, col, y=None, *, nodes=None, splits=None, rows_per
     nodes, segments = _check_splits(what, splits, nodes)
     sink = _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, y, _Classify(y))
     return _evaluation(sink, y, None if nodes is None else nodes.to(x.device), segments)
+
+
+# ---- f3n: a few nodes scored exactly over their receptive field only -------------------------------------------------
+def field_chunk():
+    """C_f (include/spp.h, f3n): the field kernels finish a row of at most C_f entries with a lane group and give a
+    longer one a workgroup"""
+    return int(nat.load().spp_field_chunk())
+
+
+def field_workspace_bytes(num_ids):
+    return int(nat.load().spp_field_workspace_bytes(int(num_ids)))
+
+
+def _field_call(entry, rowptr, col, N, ids, slot, flag=None, frowptr=None, fcol=None):
+    """one of the two entries of csrc/field.hip over ``ids``, with a workspace of its own"""
+    ws = torch.empty(field_workspace_bytes(ids.numel()), dtype=torch.uint8, device=slot.device)
+    d = nat.FieldDesc(rowptr_dev=_p(rowptr), col_dev=_p(col), num_nodes=N, ids_dev=_p(ids), num_ids=ids.numel(),
+                      slot_dev=_p(slot), flag_dev=_p(flag), frowptr_dev=_p(frowptr), fcol_dev=_p(fcol),
+                      fcol_len=fcol.numel() if fcol is not None else 0)
+    with torch.cuda.device(slot.device):
+        nat.check(entry(C.byref(d), C.c_void_p(ws.data_ptr()), ws.numel(), _stream()))
+
+
+def _field_mark(rowptr, col, N, frontier, slot, flag):
+    """``spp_field_mark``: flag[j] = 1 for every neighbour j of a frontier node that has no slot"""
+    if frontier.numel() and col.numel():
+        _field_call(nat.load().spp_field_mark, rowptr, col, N, frontier, slot, flag=flag)
+
+
+def _field_rows(rowptr, col, N, ids, slot, frowptr, fcol):
+    """``spp_field_rows``: the rows of ``ids`` in CSR order, every entry replaced by its slot"""
+    if ids.numel() and fcol.numel():
+        _field_call(nat.load().spp_field_rows, rowptr, col, N, ids, slot, frowptr=frowptr, fcol=fcol)
+
+
+def _check_nodes(what, nodes, N):
+    """``nodes`` of the field entries: a 1-D int64 tensor inside [0, N) (one read-back when it lives on a device)"""
+    if not isinstance(nodes, torch.Tensor):
+        raise TypeError(f"{what}: nodes must be a torch.Tensor, got {type(nodes).__name__}")
+    if nodes.dtype != torch.int64 or nodes.dim() != 1:
+        raise ValueError(f"{what}: nodes must be a 1-D int64 tensor, got {tuple(nodes.shape)} {nodes.dtype}")
+    if nodes.numel():
+        lo, hi = torch.stack([nodes.min(), nodes.max()]).tolist()
+        if lo < 0 or hi >= N:
+            raise ValueError(f"{what}: nodes outside the graph's {N} nodes (from {lo} to {hi})")
+
+
+def _check_hops(what, hops):
+    if not isinstance(hops, int) or isinstance(hops, bool):
+        raise TypeError(f"{what}: hops must be an int, got {type(hops).__name__}")
+    if hops < 0:
+        raise ValueError(f"{what}: hops must not be negative, got {hops}")
+
+
+def _check_csr(what, rowptr, col):
+    """a graph's CSR on its own (no matrix gives N): contiguous 1-D int64 tensors, N + 1 >= 1 entries of rowptr"""
+    for name, t in (("rowptr", rowptr), ("col", col)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous 1-D int64 tensor")
+    if rowptr.numel() < 1:
+        raise ValueError(f"{what}: rowptr must hold N + 1 entries, got none")
+
+
+class Field:
+    """The receptive field of ``nodes`` over ``hops`` = h hops, as ``ReceptiveFields.field`` builds it.  Depth 0 is the
+    distinct ids of ``nodes``, depth d every neighbour of a node of depth d - 1 that has no smaller depth; SLOTS count
+    the field's nodes depth by depth, in ascending id order within a depth.
+
+    ``ids`` int64 [n_h]: the global id of every slot.  ``sizes``: a list, sizes[d] = the nodes of depth <= d, d = 0..h.
+    ``pos`` int64 [len(nodes)]: the slot of each given node (< sizes[0]).  ``rowptr`` int64 [sizes[h-1] + 1] and ``col``
+    int64: the rows of every node of depth <= h - 1 in slot order, each the node's WHOLE row of the graph in CSR order
+    with every entry replaced by its slot (with h = 0: no rows, rowptr == [0]).  The rows [0, sizes[d]) refer only to
+    slots below sizes[d + 1]: a nest of prefixes, as a sampled MFG is."""
+
+    def __init__(self, ids, sizes, pos, rowptr, col):
+        self.ids, self.sizes, self.pos, self.rowptr, self.col = ids, sizes, pos, rowptr, col
+
+    @property
+    def hops(self):
+        return len(self.sizes) - 1
+
+    def __repr__(self):
+        return f"Field(hops={self.hops}, sizes={self.sizes}, edges={self.col.numel()})"
+
+
+class ReceptiveFields:
+    """What building fields over one resident graph needs, allocated once: the slot map (int32 [N], -1 = not in the
+    field) and the flags (one byte per node), 5 bytes a node (555 MB at N = 111 M).  ``field(nodes, hops)`` leaves both as
+    it found them -- also when it raises -- by resetting the entries it touched, so a call costs what its own field costs
+    plus, per hop, one pass over the flags (``nonzero``: N bytes read, and the hop's count read back)."""
+
+    def __init__(self, rowptr, col):
+        what = "ReceptiveFields"
+        _check_csr(what, rowptr, col)
+        nat.require_device()
+        if not (rowptr.is_cuda and col.device == rowptr.device):
+            raise ValueError(f"{what}: rowptr and col must live on one CUDA device")
+        self.rowptr, self.col, self.N, self.dev = rowptr, col, rowptr.numel() - 1, rowptr.device
+        self.slot = torch.full((self.N,), -1, dtype=torch.int32, device=self.dev)
+        self.flag = torch.zeros(self.N, dtype=torch.uint8, device=self.dev)
+
+    def field(self, nodes, hops):
+        """The ``Field`` of ``nodes`` (int64, any order, duplicates allowed, all inside the graph) over ``hops`` >= 0
+        hops.  Deterministic: ``spp_field_mark`` flags the next depth with plain stores of one value, the flags are
+        compacted in ascending id order, and ``spp_field_rows`` copies the rows.  Waits for the device once for the
+        range check, once per hop (the depth's count), once for the field's edge count and once for the check that
+        every entry of ``col`` found its slot."""
+        what = "ReceptiveFields.field"
+        _check_hops(what, hops)
+        _check_nodes(what, nodes, self.N)
+        return self._build(nodes.to(self.dev).contiguous(), hops)
+
+    def _build(self, nodes, hops):
+        """``field`` behind its checks"""
+        rowptr, col, N, slot, flag, dev = self.rowptr, self.col, self.N, self.slot, self.flag, self.dev
+        depths, marked = [], False
+        try:
+            with torch.no_grad(), torch.cuda.device(dev):
+                first, pos = torch.unique(nodes, return_inverse=True)          # ascending; pos: each node's slot
+                depths.append(first)
+                sizes = [first.numel()]
+                slot[first] = torch.arange(sizes[0], dtype=torch.int32, device=dev)
+                for _ in range(hops):
+                    frontier = depths[-1]
+                    if frontier.numel():                 # (an empty depth ends the field: the later ones are empty too)
+                        marked = True
+                        _field_mark(rowptr, col, N, frontier, slot, flag)
+                        new = flag.nonzero().view(-1)    # ascending ids; N bytes read, the count read back
+                        flag[new] = 0
+                        marked = False
+                        slot[new] = torch.arange(sizes[-1], sizes[-1] + new.numel(), dtype=torch.int32, device=dev)
+                    else:
+                        new = frontier
+                    depths.append(new)
+                    sizes.append(sizes[-1] + new.numel())
+                ids = torch.cat(depths)
+                rows = ids[:sizes[hops - 1]] if hops else ids[:0]
+                frowptr = torch.zeros(rows.numel() + 1, dtype=torch.int64, device=dev)
+                torch.cumsum(rowptr[rows + 1] - rowptr[rows], 0, out=frowptr[1:])
+                fcol = torch.empty(int(frowptr[-1]) if rows.numel() else 0, dtype=torch.int64, device=dev)
+                _field_rows(rowptr, col, N, rows, slot, frowptr, fcol)
+                if fcol.numel() and int(fcol.min()) < 0:
+                    raise RuntimeError("ReceptiveFields.field: an entry of the field's rows has no slot (the graph's col "
+                                       "leaves [0, N), or rowptr / col changed during the call)")
+                return Field(ids, sizes, pos, frowptr, fcol)
+        finally:
+            for d in depths:
+                slot[d] = -1
+            if marked:                                   # raised between a mark and its clear: which flags is unknown
+                flag.zero_()
+
+
+def receptive_field(rowptr, col, nodes, hops):
+    """``ReceptiveFields(rowptr, col).field(nodes, hops)``: the one-shot form (it allocates and fills the 5 bytes a node)"""
+    what = "receptive_field"
+    _check_hops(what, hops)
+    _check_csr(what, rowptr, col)
+    _check_nodes(what, nodes, rowptr.numel() - 1)
+    return ReceptiveFields(rowptr, col)._build(nodes.to(rowptr.device).contiguous(), hops)
+
+
+def _classes(model):
+    """the width of the model's logits"""
+    from .models import GAT, GIN
+    return model.lin2.out_features if isinstance(model, GIN) else model.convs[-1].out_channels if isinstance(model, GAT) \
+        else model.convs[-1].lin_l.out_features
+
+
+def _field_score(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, fields, y, sink):
+    """the field entries: every argument check, then the device, then the field of ``nodes`` and the pass over it into
+    ``sink``.  Returns (nodes on x's device, each node's row of the sink or None without nodes)."""
+    from .models import SAGEResInception
+    _check_model(model, what, "SAGE, GIN and GAT")
+    if isinstance(model, SAGEResInception):
+        raise NotImplementedError(f"{what}: SAGEResInception is not scored over a receptive field: its head accumulates a "
+                                  "block of every layer for the scored nodes, and the field's layers have different row "
+                                  "counts in slot order; layerwise_inference(nodes=...) scores it")
+    if isinstance(x, (list, tuple, P2PPeers)):
+        raise NotImplementedError(f"{what}: a row-partitioned table is not scored over a receptive field (layer 0 reads "
+                                  "one resident matrix in place and the field's layers live on one device); "
+                                  "partitioned_inference(nodes=...) scores it")
+    _check_matrix(x, what)
+    N = x.size(0)
+    _check_graph(what, N, rowptr, col)
+    rows_per_slab = _check_run(what, act_dtype, rows_per_slab, None)
+    if y is not None:
+        _check_labels(what, "y", y, N)
+    if fields is not None:
+        if not isinstance(fields, ReceptiveFields):
+            raise TypeError(f"{what}: fields must be a ReceptiveFields, got {type(fields).__name__}")
+        if fields.rowptr.data_ptr() != rowptr.data_ptr() or fields.col.data_ptr() != col.data_ptr() or fields.N != N:
+            raise ValueError(f"{what}: fields was made for another graph than rowptr / col")
+    _check_nodes(what, nodes, N)                          # (one read-back, up front)
+    nat.require_device()
+    if not (x.is_cuda and rowptr.device == x.device and col.device == x.device):
+        raise ValueError(f"{what}: x, rowptr and col must live on one CUDA device")
+    if y is not None and y.device != x.device:
+        raise ValueError(f"{what}: y must live on x's device")
+    nodes = nodes.to(x.device).contiguous()
+    if not nodes.numel():
+        return nodes, None
+    n_layers = len(model.convs)
+    field = (fields or ReceptiveFields(rowptr, col))._build(nodes, n_layers - 1)
+    _score(model, _Resident(x, rowptr, col), None, rows_per_slab, act_dtype, sink, _field_plan(field, n_layers))
+    return nodes, field.pos
+
+
+def field_inference(model, x, rowptr, col, nodes, *, rows_per_slab=1 << 20, act_dtype=torch.float32, fields=None):
+    """``layerwise_inference(model, x, rowptr, col, nodes=nodes, ...)`` -- the same bits, [len(nodes), classes] fp32
+    log-probabilities -- computed over the receptive field of ``nodes`` only: for a model of L conv layers the nodes
+    within L - 1 hops (``ReceptiveFields``, ``Field``), not all N.  ``SAGE``, ``GIN`` and ``GAT`` (any ``heads``) over a
+    resident table; SAGEResInception and a partitioned table are refused with the reason.
+
+    The plan (``_field_plan``): layer 0 runs on the ORIGINAL graph and table with ``target_ids=field.ids`` -- the table
+    is read in place, nothing of it is gathered, and the widest hop never exists as a matrix (GAT: the first projection
+    stays whole-table, the attention takes the list); layer i >= 1 runs on the field's CSR as a slab, for the slots
+    below sizes[L-1-i], reading layer i-1's rows; the last layer leaves the DISTINCT nodes' logits, which go through the
+    sink and are expanded by ``field.pos``.  Kernels and the fixed GEMM tiles are ``layerwise_inference``'s, and a row's
+    bits depend on its own row alone, so the two entries agree bit for bit.
+
+    ``fields``: a ``ReceptiveFields`` of this graph to reuse (5 bytes a node, allocated once); without one a temporary is
+    made.  When NOT to use this entry: the field of a few thousand nodes of a small-world graph can approach the whole
+    graph after two hops, and then the field (its build, its CSR copy, layer 0 by list) costs more than the plain pass;
+    ``ReceptiveFields.field(nodes, L - 1).sizes`` tells before the model runs."""
+    what = "field_inference"
+    sink = _LogProbs()
+    _nodes, pos = _field_score(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, fields, None, sink)
+    if pos is None:                                      # no nodes: nothing was launched
+        return torch.empty((0, _classes(model)), dtype=torch.float32, device=x.device)
+    return sink.out[pos]
+
+
+def field_evaluate(model, x, rowptr, col, y=None, *, nodes=None, splits=None, rows_per_slab=1 << 20,
+                   act_dtype=torch.float32, fields=None):
+    """``evaluate(model, x, rowptr, col, y, nodes= / splits=, ...)`` over the receptive field of the scored nodes only:
+    ``field_inference``'s pass ended in ``classify_rows``.  Distinct nodes are scored once (their labels read as
+    ``y[ids]``) and ``pos`` expands ``pred`` and ``nll`` to the order given; ``pred``, ``nll``, the counts, the loss and
+    ``splits`` equal ``evaluate``'s exactly.  One of ``nodes`` and ``splits`` is required: ``evaluate`` scores every node."""
+    what = "field_evaluate"
+    nodes, segments = _check_splits(what, splits, nodes)
+    if nodes is None:
+        raise ValueError(f"{what}: give nodes or splits (the nodes whose field is scored); evaluate scores every node")
+    sink = _Classify(y)
+    nodes, pos = _field_score(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, fields, y, sink)
+    if pos is None:
+        sink.classes = _classes(model)
+        sink.pred = torch.empty(0, dtype=torch.int64, device=x.device)
+        sink.nll = torch.empty(0, dtype=torch.float32, device=x.device) if y is not None else None
+    else:
+        sink.pred, sink.nll = sink.pred[pos], sink.nll[pos] if sink.nll is not None else None
+    return _evaluation(sink, y, nodes, segments)
 
 
 class LocalPeers:
