@@ -950,7 +950,7 @@ spp_status spp_agg_forward_fp8(const spp_agg_fwd_desc* desc, const int8_t* scale
  * ------------------------------------------------------------------------- */
 typedef struct spp_graph_agg_desc {
   int32_t epilogue;         /* SPP_AGG_MEAN / _OPERAND / _SUM */
-  int32_t x_elem;           /* SPP_ELEM_F32 / _F16 / _BF16 */
+  int32_t x_elem;           /* SPP_ELEM_F32 / _F16 / _BF16 (SPP_ELEM_FP8_E4M3: spp_graph_agg_forward_fp8 only, f3o) */
   int32_t out_elem;         /* SPP_ELEM_F32 / SPP_ELEM_BF16 */
   int32_t reserved;
   const int64_t* rowptr_dev;
@@ -1000,7 +1000,7 @@ spp_status spp_graph_agg_forward(const spp_graph_agg_desc* desc, void* workspace
 #define SPP_GRAPH_AGG_MAX_PARTS 16
 typedef struct spp_graph_agg_parts_desc {
   int32_t epilogue;         /* SPP_AGG_MEAN / _OPERAND / _SUM */
-  int32_t x_elem;           /* SPP_ELEM_F32 / _F16 / _BF16 */
+  int32_t x_elem;           /* SPP_ELEM_F32 / _F16 / _BF16 (SPP_ELEM_FP8_E4M3: spp_graph_agg_parts_forward_fp8 only, f3o) */
   int32_t out_elem;         /* SPP_ELEM_F32 / SPP_ELEM_BF16 */
   int32_t num_parts;        /* P */
   const int64_t* rowptr_dev;
@@ -1020,6 +1020,40 @@ typedef struct spp_graph_agg_parts_desc {
 
 spp_status spp_graph_agg_parts_forward(const spp_graph_agg_parts_desc* desc, void* workspace_dev,
                                        int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * f3o  Exact inference that reads an fp8 feature table (f3c: q e4m3 [rows, F], scale_log2 int8 [F]) IN PLACE.  Opt-in,
+ *      beside the entries above, which keep refusing SPP_ELEM_FP8_E4M3: nothing the existing entries do changes.
+ *
+ *   spp_graph_agg_forward_fp8: spp_graph_agg_forward over the rows of q.  The descriptor is spp_graph_agg_desc with
+ *     x_elem == SPP_ELEM_FP8_E4M3, x_dev = q and x_stride_elems in elements = BYTES; scale_log2_dev: the F column
+ *     exponents on the device, 4-byte aligned.  Every load returns v[i, c] = float32(q[i, c]) * 2^scale_log2[c] (exact,
+ *     for every exponent in [-64, 63]) and everything behind the load is the code of the fp32 rows, so the result is
+ *     spp_graph_agg_forward's on the fp32 matrix v BIT FOR BIT: the summation contract, the epilogues, the target's own
+ *     row (the right half of SPP_AGG_OPERAND, the self term of SPP_AGG_SUM), the rules for ids outside the graph, the
+ *     workspace and the launches are that entry's.  A lane takes one dword, four columns: always the vector form, so
+ *     out_dev must be aligned to 4 elements (base and stride).  A NaN code (0x7f, 0xff) gives a NaN; its payload is
+ *     not part of the contract.
+ *     Refused with SPP_ERR_INVALID before anything is enqueued: any other x_elem, F % 16 != 0, fp8 as out_elem, a NULL or
+ *     not 4-byte aligned scale_log2_dev, a base or a row stride that is no multiple of 4 bytes, and everything
+ *     spp_graph_agg_forward refuses.
+ *   spp_graph_agg_parts_forward_fp8: the same over a ROW-PARTITIONED q, as spp_graph_agg_parts_forward: the descriptor is
+ *     spp_graph_agg_parts_desc with x_elem == SPP_ELEM_FP8_E4M3 and the stride in bytes.  ONE exponent vector serves all
+ *     parts: that the owners of the parts quantised against the same exponents is the caller's duty, as on the exchange
+ *     path (spp_exchange_cfg.scales_tag).  Bit-identical to spp_graph_agg_forward_fp8 on the concatenation of the parts.
+ *   spp_fp8_rows_f32: rows of the table as dense fp32, dst[j, :] = v[row(j), :] for j < n, dst fp32 [n, F] -- the exact
+ *     values, nothing rounded: the tiles the GEMMs of exact inference take from an fp8 table.  The rows are a slab
+ *     (row0 >= 0, ids_dev NULL: row(j) = row0 + j, which must stay inside [0, src_rows]) or a list (ids_dev int64 [n],
+ *     row0 < 0: any order, duplicates allowed); an id outside [0, src_rows) reads row 0 and raises SPP_AERR_GATHER_INDEX
+ *     (as spp_gather_rows_fp8).  q and dst 16-byte aligned, scale_log2_dev 4-byte aligned, F % 16 == 0; anything else
+ *     returns SPP_ERR_INVALID before a launch.  n == 0 or F == 0: nothing is enqueued.
+ * ------------------------------------------------------------------------- */
+spp_status spp_graph_agg_forward_fp8(const spp_graph_agg_desc* desc, const int8_t* scale_log2_dev, void* workspace_dev,
+                                     int64_t workspace_bytes, void* stream);
+spp_status spp_graph_agg_parts_forward_fp8(const spp_graph_agg_parts_desc* desc, const int8_t* scale_log2_dev,
+                                           void* workspace_dev, int64_t workspace_bytes, void* stream);
+spp_status spp_fp8_rows_f32(const void* q_dev, int64_t src_rows, int64_t F, const int8_t* scale_log2_dev, int64_t row0,
+                            const int64_t* ids_dev, int64_t n, void* dst_dev, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * f3h  GATConv attention over rows of the RESIDENT graph (exact, layer-wise GAT inference), in PyG's project-first

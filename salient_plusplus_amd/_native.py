@@ -59,7 +59,7 @@ class MfgOut(C.Structure):
 
 # spp_elem and the aggregation descriptor's codes (include/spp.h)
 SPP_ELEM_F32, SPP_ELEM_F16, SPP_ELEM_BF16 = 0, 1, 2
-SPP_ELEM_FP8_E4M3 = 3            # spp_agg_forward_fp8, spp_exchange_cfg.x_elem
+SPP_ELEM_FP8_E4M3 = 3            # spp_agg_forward_fp8, spp_graph_agg_*_forward_fp8, spp_exchange_cfg.x_elem
 SPP_AGG_DENSE, SPP_AGG_TABLE, SPP_AGG_ROWS = 0, 1, 2
 SPP_AGG_MEAN, SPP_AGG_OPERAND, SPP_AGG_OPERAND_ACT, SPP_AGG_SUM = 0, 1, 2, 3
 SPP_AGG_SCATTER, SPP_AGG_GATHER = 0, 1
@@ -269,6 +269,9 @@ SIGNATURES = {
     "spp_graph_agg_workspace_bytes": (i64, [i64]),
     "spp_graph_agg_forward": (C.c_int, [C.POINTER(GraphAggDesc), p, i64, p]),
     "spp_graph_agg_parts_forward": (C.c_int, [C.POINTER(GraphAggPartsDesc), p, i64, p]),
+    "spp_graph_agg_forward_fp8": (C.c_int, [C.POINTER(GraphAggDesc), p, p, i64, p]),
+    "spp_graph_agg_parts_forward_fp8": (C.c_int, [C.POINTER(GraphAggPartsDesc), p, p, i64, p]),
+    "spp_fp8_rows_f32": (C.c_int, [p, i64, i64, p, i64, p, i64, p, p]),
     "spp_graph_gat_chunk": (i64, []),
     "spp_graph_gat_workspace_bytes": (i64, [i64]),
     "spp_graph_gat_forward": (C.c_int, [C.POINTER(GraphGatDesc), p, i64, p]),

@@ -20,6 +20,12 @@
 // f3j: the same two kernels over a ROW-PARTITIONED x (spp_graph_agg_parts_forward).  The row source is a template
 // parameter: NodeRows reads one matrix, PartRows finds the part that owns a global row first.  Same arithmetic, same
 // order, same bits.
+//
+// f3o: the same two kernels over an fp8 TABLE read in place (spp_graph_agg_forward_fp8, spp_graph_agg_parts_forward_fp8):
+// rows of e4m3 bytes with one power-of-two exponent per column (include/spp.h, f3c).  A load returns
+// v = float32(code) * 2^e -- both steps exact -- so everything behind the load is the fp32 rows' arithmetic on v: same
+// order, same bits as over the table dequantised to fp32.  The exponents ride with the row source (Fp8NodeRows /
+// Fp8PartRows: new instantiations, no existing kernel's arguments change).
 #include "graph_rows.hip.h"
 
 namespace spp {
@@ -37,7 +43,9 @@ struct Args : Targets {
 };
 
 // The row source of the kernels: Rows::Src is what the launch passes by value, Rows(src, a) what a lane asks for the
-// address of global row g.
+// address of global row g, and cols(c) what a load of the columns c.. needs besides the address: nothing (NoScale) for
+// fp32 / fp16 / bf16 rows, the columns' factors for fp8 rows (f3o, below).
+struct NoScale {};
 // row g of the full matrix; an id outside [0, x_rows) reads row 0 (the rule of the Table source: no fault)
 template <typename Tin>
 struct NodeRows {
@@ -49,6 +57,7 @@ struct NodeRows {
   __device__ __forceinline__ const Tin* operator()(int64_t g) const {
     return x + ((uint64_t)g < (uint64_t)rows ? g : 0) * stride;
   }
+  __device__ __forceinline__ NoScale cols(int64_t) const { return {}; }
 };
 
 // row g of the part that owns it (graph_rows.hip.h: the tables and the owner search), NodeRows' rule for an id outside
@@ -74,38 +83,81 @@ struct PartRows {
     g = (uint64_t)g < (uint64_t)rows ? g : 0;
     return base[part_owner(first, g)] + g * stride;
   }
+  __device__ __forceinline__ NoScale cols(int64_t) const { return {}; }
 };
 
+// fp8 rows (f3o): OCP e4m3 bytes, one power-of-two exponent per COLUMN (the load of aggregate.hip's fp8 kernels,
+// repeated here so that those come out unchanged).  A lane's piece is one dword: four columns, always the vector form
+// (F % 16 == 0, rows F bytes apart).
+struct e4m3 {
+  uint8_t bits;
+};
+typedef float f32x2_fp8 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float exp2_i8(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }  // e in [-64, 63]
+
+// cols(c) of an e4m3 source: the factors 2^e of the columns c .. c+3 -- built once per column piece, outside the loop
+// over the row's entries, and again for every piece of a lane that takes several
+struct Fp8Scale4 {
+  f4 s;
+  __device__ __forceinline__ Fp8Scale4(const int8_t* __restrict__ scale_log2, int64_t c) {
+    const uint32_t raw = *reinterpret_cast<const uint32_t*>(scale_log2 + c);
+    s = {exp2_i8((int8_t)raw), exp2_i8((int8_t)(raw >> 8)), exp2_i8((int8_t)(raw >> 16)), exp2_i8((int8_t)(raw >> 24))};
+  }
+};
+template <class P, typename Tin>
+__device__ __forceinline__ typename P::type load_piece(const Tin* p, NoScale) { return P::load(p); }
+template <class P>
+__device__ __forceinline__ f4 load_piece(const e4m3* p, const Fp8Scale4& sc) {
+  const uint32_t raw = *reinterpret_cast<const uint32_t*>(p);
+  const f32x2_fp8 a = __builtin_amdgcn_cvt_pk_f32_fp8(raw, false), b = __builtin_amdgcn_cvt_pk_f32_fp8(raw, true);
+  return {a.x * sc.s.x, a.y * sc.s.y, b.x * sc.s.z, b.y * sc.s.w};
+}
+
+// the two row sources over an e4m3 table: Src adds the exponents to what the launch passes by value
+template <class Base>
+struct Fp8Rows : Base {
+  struct Src {
+    typename Base::Src rows;
+    const int8_t* scale_log2;
+  };
+  const int8_t* scale_log2;
+  __device__ __forceinline__ Fp8Rows(const Src& src, const Args& a) : Base(src.rows, a), scale_log2(src.scale_log2) {}
+  __device__ __forceinline__ Fp8Scale4 cols(int64_t c) const { return Fp8Scale4(scale_log2, c); }
+};
+using Fp8NodeRows = Fp8Rows<NodeRows<e4m3>>;
+using Fp8PartRows = Fp8Rows<PartRows<e4m3>>;
+
 // columns c.. of the entries [b, e), added in CSR order one at a time from zero; four rows are in flight
-template <typename Rows, bool VEC4>
+template <typename Rows, bool VEC4, class Scale>
 __device__ __forceinline__ typename Piece<VEC4>::type sum_entries(const Rows& row, const int64_t* __restrict__ col,
-                                                                  int64_t b, int64_t e, int64_t c) {
+                                                                  int64_t b, int64_t e, int64_t c, const Scale& sc) {
   using P = Piece<VEC4>;
   typename P::type acc = P::zero();
   int64_t k = b;
   for (; k + 3 < e; k += 4) {
     const int64_t j0 = col[k], j1 = col[k + 1], j2 = col[k + 2], j3 = col[k + 3];
-    const auto v0 = P::load(row(j0) + c), v1 = P::load(row(j1) + c), v2 = P::load(row(j2) + c), v3 = P::load(row(j3) + c);
+    const auto v0 = load_piece<P>(row(j0) + c, sc), v1 = load_piece<P>(row(j1) + c, sc), v2 = load_piece<P>(row(j2) + c, sc),
+               v3 = load_piece<P>(row(j3) + c, sc);
     P::add(acc, v0);
     P::add(acc, v1);
     P::add(acc, v2);
     P::add(acc, v3);
   }
-  for (; k < e; ++k) P::add(acc, P::load(row(col[k]) + c));
+  for (; k < e; ++k) P::add(acc, load_piece<P>(row(col[k]) + c, sc));
   return acc;
 }
 
 // what the sum of node t's row becomes, columns c.. of output row o (own: node t's row of x, NULL for a target id
 // outside the graph, whose output row is all zeros)
-template <typename Tin, typename Tout, bool VEC4>
+template <typename Tin, typename Tout, bool VEC4, class Scale>
 __device__ __forceinline__ void finish(const Args& a, typename Piece<VEC4>::type acc, int64_t deg, const Tin* own,
-                                       Tout* o, int64_t c) {
+                                       Tout* o, int64_t c, const Scale& sc) {
   using P = Piece<VEC4>;
   if (a.epilogue == SPP_AGG_SUM) {
-    if (a.self_scale != 0.f && own) acc = P::fma(a.self_scale, P::load(own + c), acc);
+    if (a.self_scale != 0.f && own) acc = P::fma(a.self_scale, load_piece<P>(own + c, sc), acc);
   } else {
     acc = P::scaled(acc, 1.0f / (float)(deg > 0 ? deg : 1));
-    if (a.epilogue == SPP_AGG_OPERAND) P::store(o + a.F + c, own ? P::load(own + c) : P::zero());
+    if (a.epilogue == SPP_AGG_OPERAND) P::store(o + a.F + c, own ? load_piece<P>(own + c, sc) : P::zero());
   }
   P::store(o + c, acc);
 }
@@ -128,8 +180,10 @@ __global__ __launch_bounds__(kNT) void k_graph_agg_rows(typename Rows::Src src, 
   }
   const Tin* own = in_graph ? row(t) : nullptr;
   Tout* o = out + i * a.out_stride;
-  for (int64_t c = (int64_t)lane * P::kWidth; c < a.F; c += (int64_t)lpr * P::kWidth)
-    finish<Tin, Tout, VEC4>(a, sum_entries<Rows, VEC4>(row, a.col, b, e, c), e - b, own, o, c);
+  for (int64_t c = (int64_t)lane * P::kWidth; c < a.F; c += (int64_t)lpr * P::kWidth) {
+    const auto sc = row.cols(c);
+    finish<Tin, Tout, VEC4>(a, sum_entries<Rows, VEC4>(row, a.col, b, e, c, sc), e - b, own, o, c, sc);
+  }
 }
 
 template <typename Rows, typename Tout, bool VEC4>
@@ -152,6 +206,7 @@ __global__ __launch_bounds__(kNT) void k_graph_agg_long(typename Rows::Src src, 
     for (int64_t c0 = 0; c0 < a.F; c0 += (int64_t)lpr * P::kWidth) {
       const int64_t c = c0 + (int64_t)lane * P::kWidth;
       const bool active = c < a.F;
+      const auto sc = row.cols(active ? c : 0);  // (a lane behind the row's last piece loads nothing past the scales)
       piece total = P::zero();
       for (int64_t j0 = 0; j0 < chunks; j0 += groups, ++round) {
         // group g sums chunk j0 + g; round k parks its sums in part[k & 1], which is written again in round k + 2,
@@ -160,7 +215,7 @@ __global__ __launch_bounds__(kNT) void k_graph_agg_long(typename Rows::Src src, 
         piece p = P::zero();
         if (active && j < chunks) {
           const int64_t cb = b + j * kGraphChunk;
-          p = sum_entries<Rows, VEC4>(row, a.col, cb, std::min<int64_t>(e, cb + kGraphChunk), c);
+          p = sum_entries<Rows, VEC4>(row, a.col, cb, std::min<int64_t>(e, cb + kGraphChunk), c, sc);
         }
         part[round & 1][threadIdx.x] = p;
         __syncthreads();
@@ -169,7 +224,7 @@ __global__ __launch_bounds__(kNT) void k_graph_agg_long(typename Rows::Src src, 
           for (int g = 0; g < m; ++g) P::add(total, part[round & 1][(g << a.lpr_log2) + lane]);
         }
       }
-      if (grp == 0 && active) finish<Tin, Tout, VEC4>(a, total, e - b, row(t), o, c);
+      if (grp == 0 && active) finish<Tin, Tout, VEC4>(a, total, e - b, row(t), o, c, sc);
     }
   }
 }
@@ -186,57 +241,99 @@ extern "C" int64_t spp_graph_agg_workspace_bytes(int64_t num_targets) { return w
 
 namespace {
 
-// what both entries share; exactly one of x / parts is given
+template <typename Rows, typename Tout, bool V>
+void launch(const Launch& l, const typename Rows::Src& src, void* out, const Args& a, hipStream_t st) {
+  hipLaunchKernelGGL((k_graph_agg_rows<Rows, Tout, V>), dim3(l.grid), dim3(kNT), 0, st, src, static_cast<Tout*>(out), a);
+  hipLaunchKernelGGL((k_graph_agg_long<Rows, Tout, V>), dim3(l.long_grid), dim3(kNT), 0, st, src, static_cast<Tout*>(out), a);
+}
+
+// what the four entries share; exactly one of x / parts is given.  scale_log2 (the _fp8 entries; NULL elsewhere): the
+// rows are e4m3 bytes read in place with these per-column exponents.
 spp_status forward(const char* who, const Common& d, int32_t epilogue, float self_scale, const void* x_dev,
-                   const Parts* parts, void* workspace_dev, int64_t workspace_bytes, void* stream) {
+                   const Parts* parts, const int8_t* scale_log2, bool fp8, void* workspace_dev, int64_t workspace_bytes,
+                   void* stream) {
   SPP_REQUIRE(epilogue == SPP_AGG_MEAN || epilogue == SPP_AGG_OPERAND || epilogue == SPP_AGG_SUM,
               "%s: epilogue %d (the mean, the operand and the sum; no activation on load)", who, (int)epilogue);
+  if (fp8) {
+    SPP_REQUIRE(d.x_elem == SPP_ELEM_FP8_E4M3,
+                "%s: x_elem %d: this entry reads an fp8 table in place (SPP_ELEM_FP8_E4M3); other rows go to the entry without _fp8",
+                who, (int)d.x_elem);
+    SPP_REQUIRE(d.F % 16 == 0, "%s: F (%lld) must be a multiple of 16 (fp8 rows, include/spp.h f3c)", who, (long long)d.F);
+  }
   Launch l;
   SPP_TRY(check_common(who, d, epilogue == SPP_AGG_OPERAND ? 2 * d.F : d.F, d.F, parts ? parts->base[0] : &x_dev,
-                       parts ? parts->n : 1, true, workspace_dev, workspace_bytes, &l));
+                       parts ? parts->n : 1, true, workspace_dev, workspace_bytes, &l, fp8));
   if (l.empty) return SPP_OK;
+  if (fp8) {
+    SPP_REQUIRE(scale_log2 && aligned_to(scale_log2, 4), "%s: scale_log2_dev must be there and 4-byte aligned (int8 [F])", who);
+    SPP_REQUIRE(l.vec, "%s: fp8 rows are read a dword at a time: every base and x_stride_elems (bytes) must be a multiple of 4",
+                who);
+  }
   hipStream_t st = as_stream(stream);
   const Args a{l.targets, epilogue, self_scale, l.lpr_log2, l.long_rows};
   SPP_HIP_TRY(hipMemsetAsync(workspace_dev, 0, kWorkspaceHeader, st));
-  with_in_out_vec(d.x_elem, d.out_elem, l.vec, [&](auto tin, auto tout, auto v) {
-    using Tin = typename decltype(tin)::type;
-    using Tout = typename decltype(tout)::type;
-    constexpr bool V = decltype(v)::value;
-    Tout* out = static_cast<Tout*>(d.out);
-    if (parts) {
-      const PartTable<1> t = part_table<1>(*parts, {d.x_stride * (int64_t)sizeof(Tin)});
-      hipLaunchKernelGGL((k_graph_agg_rows<PartRows<Tin>, Tout, V>), dim3(l.grid), dim3(kNT), 0, st, t, out, a);
-      hipLaunchKernelGGL((k_graph_agg_long<PartRows<Tin>, Tout, V>), dim3(l.long_grid), dim3(kNT), 0, st, t, out, a);
-    } else {
-      const Tin* x = static_cast<const Tin*>(x_dev);
-      hipLaunchKernelGGL((k_graph_agg_rows<NodeRows<Tin>, Tout, V>), dim3(l.grid), dim3(kNT), 0, st, x, out, a);
-      hipLaunchKernelGGL((k_graph_agg_long<NodeRows<Tin>, Tout, V>), dim3(l.long_grid), dim3(kNT), 0, st, x, out, a);
-    }
-  });
+  if (fp8) {
+    with_f32_bf16(d.out_elem, [&](auto tout) {
+      using Tout = typename decltype(tout)::type;
+      if (parts)
+        launch<Fp8PartRows, Tout, true>(l, {part_table<1>(*parts, {d.x_stride}), scale_log2}, d.out, a, st);
+      else
+        launch<Fp8NodeRows, Tout, true>(l, {static_cast<const e4m3*>(x_dev), scale_log2}, d.out, a, st);
+    });
+  } else {
+    with_in_out_vec(d.x_elem, d.out_elem, l.vec, [&](auto tin, auto tout, auto v) {
+      using Tin = typename decltype(tin)::type;
+      using Tout = typename decltype(tout)::type;
+      constexpr bool V = decltype(v)::value;
+      if (parts)
+        launch<PartRows<Tin>, Tout, V>(l, part_table<1>(*parts, {d.x_stride * (int64_t)sizeof(Tin)}), d.out, a, st);
+      else
+        launch<NodeRows<Tin>, Tout, V>(l, static_cast<const Tin*>(x_dev), d.out, a, st);
+    });
+  }
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
 }
 
-}  // namespace
-
-extern "C" spp_status spp_graph_agg_forward(const spp_graph_agg_desc* desc, void* workspace_dev, int64_t workspace_bytes,
-                                            void* stream) {
-  const char* who = "spp_graph_agg_forward";
+spp_status whole(const char* who, const spp_graph_agg_desc* desc, const int8_t* scale_log2, bool fp8, void* workspace_dev,
+                 int64_t workspace_bytes, void* stream) {
   SPP_REQUIRE(desc, "%s: NULL descriptor", who);
   const spp_graph_agg_desc& d = *desc;
   const Common c{d.x_elem, d.out_elem,    d.rowptr_dev,     d.col_dev,     d.x_stride_elems, d.x_rows,
                  d.F,      d.target_row0, d.target_ids_dev, d.num_targets, d.out_dev,        d.out_stride_elems};
-  return forward(who, c, d.epilogue, d.self_scale, d.x_dev, nullptr, workspace_dev, workspace_bytes, stream);
+  return forward(who, c, d.epilogue, d.self_scale, d.x_dev, nullptr, scale_log2, fp8, workspace_dev, workspace_bytes, stream);
 }
 
-extern "C" spp_status spp_graph_agg_parts_forward(const spp_graph_agg_parts_desc* desc, void* workspace_dev,
-                                                  int64_t workspace_bytes, void* stream) {
-  const char* who = "spp_graph_agg_parts_forward";
+spp_status over_parts(const char* who, const spp_graph_agg_parts_desc* desc, const int8_t* scale_log2, bool fp8,
+                      void* workspace_dev, int64_t workspace_bytes, void* stream) {
   SPP_REQUIRE(desc, "%s: NULL descriptor", who);
   const spp_graph_agg_parts_desc& d = *desc;
   Parts parts;
   SPP_TRY(check_parts(who, d.num_parts, d.part_offsets, d.x_parts_dev, "base (x_parts_dev)", nullptr, nullptr, &parts));
   const Common c{d.x_elem, d.out_elem,    d.rowptr_dev,     d.col_dev,     d.x_stride_elems, d.part_offsets[d.num_parts],
                  d.F,      d.target_row0, d.target_ids_dev, d.num_targets, d.out_dev,        d.out_stride_elems};
-  return forward(who, c, d.epilogue, d.self_scale, nullptr, &parts, workspace_dev, workspace_bytes, stream);
+  return forward(who, c, d.epilogue, d.self_scale, nullptr, &parts, scale_log2, fp8, workspace_dev, workspace_bytes, stream);
+}
+
+}  // namespace
+
+extern "C" spp_status spp_graph_agg_forward(const spp_graph_agg_desc* desc, void* workspace_dev, int64_t workspace_bytes,
+                                            void* stream) {
+  return whole("spp_graph_agg_forward", desc, nullptr, false, workspace_dev, workspace_bytes, stream);
+}
+
+extern "C" spp_status spp_graph_agg_parts_forward(const spp_graph_agg_parts_desc* desc, void* workspace_dev,
+                                                  int64_t workspace_bytes, void* stream) {
+  return over_parts("spp_graph_agg_parts_forward", desc, nullptr, false, workspace_dev, workspace_bytes, stream);
+}
+
+// f3o: the same entries over an fp8 table read in place; one exponent vector for the whole table (all parts)
+extern "C" spp_status spp_graph_agg_forward_fp8(const spp_graph_agg_desc* desc, const int8_t* scale_log2_dev,
+                                                void* workspace_dev, int64_t workspace_bytes, void* stream) {
+  return whole("spp_graph_agg_forward_fp8", desc, scale_log2_dev, true, workspace_dev, workspace_bytes, stream);
+}
+
+extern "C" spp_status spp_graph_agg_parts_forward_fp8(const spp_graph_agg_parts_desc* desc, const int8_t* scale_log2_dev,
+                                                      void* workspace_dev, int64_t workspace_bytes, void* stream) {
+  return over_parts("spp_graph_agg_parts_forward_fp8", desc, scale_log2_dev, true, workspace_dev, workspace_bytes, stream);
 }

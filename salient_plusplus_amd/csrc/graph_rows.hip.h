@@ -132,15 +132,16 @@ struct Launch {
 // columns that must be a multiple of 4 for the vector form (F, or the columns of a head); x_bases: the base of x or
 // of each non-empty part; others: the entry's further buffers are there.  The vector form moves four columns per
 // lane: rows of x that do not allow it (with parts: the rows of any of them) are read one column per lane instead; an
-// output that does not is refused (the caller allocates it).
+// output that does not is refused (the caller allocates it).  fp8_rows: the entry reads e4m3 rows in place (f3o, the
+// _fp8 entries of graph_aggregate.hip: x_elem is SPP_ELEM_FP8_E4M3, an element is a byte); everywhere else they are refused.
 inline spp_status check_common(const char* who, const Common& d, int64_t out_width, int64_t vec_cols,
                                const void* const* x_bases, int n_bases, bool others, void* workspace_dev,
-                               int64_t workspace_bytes_given, Launch* l) {
-  SPP_REQUIRE(d.x_elem != SPP_ELEM_FP8_E4M3 && d.out_elem != SPP_ELEM_FP8_E4M3,
+                               int64_t workspace_bytes_given, Launch* l, bool fp8_rows = false) {
+  SPP_REQUIRE((fp8_rows || d.x_elem != SPP_ELEM_FP8_E4M3) && d.out_elem != SPP_ELEM_FP8_E4M3,
               "%s: fp8 rows are not read or written here (x_elem %d, out_elem %d; dequantise the table first)", who,
               (int)d.x_elem, (int)d.out_elem);
-  SPP_REQUIRE(elem_ok(d.x_elem) && f32_bf16_ok(d.out_elem), "%s: unknown or unsupported element code (x_elem %d, out_elem %d)",
-              who, (int)d.x_elem, (int)d.out_elem);
+  SPP_REQUIRE((fp8_rows ? d.x_elem == SPP_ELEM_FP8_E4M3 : elem_ok(d.x_elem)) && f32_bf16_ok(d.out_elem),
+              "%s: unknown or unsupported element code (x_elem %d, out_elem %d)", who, (int)d.x_elem, (int)d.out_elem);
   const bool by_ids = d.ids != nullptr, by_slab = d.row0 >= 0;
   SPP_REQUIRE(by_ids != by_slab, "%s: give the targets as a slab (target_row0 >= 0) or as a list (target_ids_dev), %s", who,
               by_ids ? "not both" : "one of them");

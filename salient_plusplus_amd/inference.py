@@ -63,12 +63,79 @@ def graph_gat_workspace_bytes(num_targets):
     return int(nat.load().spp_graph_gat_workspace_bytes(int(num_targets)))
 
 
+class Fp8Table:
+    """``Fp8Table(features)``: "read this fp8 table in place" (f3o).  The wrapped ``Fp8Features`` (q e4m3 [N, F],
+    scale_log2 int8 [F], on the GPU) is accepted as ``x`` by ``graph_aggregate``, as every element of ``parts`` by
+    ``graph_aggregate_parts`` and as ``x`` by the resident drivers -- ``layerwise_inference`` (``SAGE.inference``,
+    ``GIN.inference``), ``evaluate``, ``field_inference``, ``field_evaluate`` -- for all four models.  Layer 0's
+    aggregation reads the e4m3 rows through ``spp_graph_agg_forward_fp8`` and the GEMM tiles of the table's own rows come
+    from ``spp_fp8_rows_f32``; both yield v = float32(q) * 2^scale_log2 exactly, so every result is the bits of the same
+    call on ``features.dequantize(torch.float32)`` -- without that matrix (4 bytes an element) or an fp16 copy (2) beside
+    the table (1).  A bare ``Fp8Features`` keeps being refused everywhere: reading in place is asked for, never assumed.
+
+    ``table[ids]`` (int64 1-D tensor on the table's device) names rows of the table without copying them."""
+    __slots__ = ("features", "ids")
+
+    def __init__(self, features):
+        if not isinstance(features, Fp8Features):
+            raise TypeError(f"Fp8Table: wraps an Fp8Features (fp8.quantize_e4m3, fp8.load), got {type(features).__name__}")
+        self.features, self.ids = features, None
+
+    q = property(lambda self: self.features.q)
+    scale_log2 = property(lambda self: self.features.scale_log2)
+    device = property(lambda self: self.features.q.device)
+    is_cuda = property(lambda self: self.features.q.is_cuda)
+    dtype = property(lambda self: self.features.dtype)
+    requires_grad = False
+
+    @property
+    def shape(self):
+        return torch.Size((self.size(0), self.size(1)))
+
+    def size(self, dim=None):
+        if dim is None:
+            return self.shape
+        return self.features.q.size(1) if dim in (1, -1) else self.ids.numel() if self.ids is not None else self.features.q.size(0)
+
+    def dim(self):
+        return 2
+
+    def __getitem__(self, ids):
+        if self.ids is not None or not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64 or ids.dim() != 1 \
+                or ids.device != self.device:
+            raise TypeError("Fp8Table: rows are named by one 1-D int64 tensor on the table's device")
+        rows = Fp8Table(self.features)
+        rows.ids = ids.contiguous()
+        return rows
+
+    def __repr__(self):
+        return f"Fp8Table(shape={tuple(self.shape)}, device={self.device})"
+
+    def rows_f32(self, out, row0=None):
+        """``spp_fp8_rows_f32``: out[j] = v[row0 + j], or v[ids[j]] for ``table[ids]``; ``out`` contiguous fp32 [n, F]"""
+        f = self.features
+        if out.size(0):
+            with torch.cuda.device(out.device):
+                nat.check(nat.load().spp_fp8_rows_f32(_p(f.q), f.q.size(0), f.q.size(1), _p(f.scale_log2),
+                                                      -1 if self.ids is not None else int(row0),
+                                                      _p(self.ids[row0:row0 + out.size(0)]) if self.ids is not None else None,
+                                                      out.size(0), _p(out), _stream()))
+        return out
+
+
 # ---- the argument checks the wrappers and the drivers share; ``what`` is the caller's name in the message -----------
-def _check_matrix(x, what, name="x"):
+_FP8_TABLE_READERS = ("an fp8 table is read in place only as x of graph_aggregate, in parts of graph_aggregate_parts and as "
+                      "x of layerwise_inference, evaluate, field_inference and field_evaluate")
+
+
+def _check_matrix(x, what, name="x", fp8_reason="this argument is a matrix of activations or projected rows (fp16 / fp32 / "
+                                                  "bf16), which no fp8 table is"):
     """x as the kernels read it: a 2-D fp16 / fp32 / bf16 matrix with unit column stride that carries no gradient"""
     if isinstance(x, Fp8Features):
         raise TypeError(f"{what}: an fp8 feature table (Fp8Features) is not supported as inference input; pass "
-                        "x.dequantize(torch.float16)")
+                        "x.dequantize(torch.float16), or inference.Fp8Table(x) where the table is read in place")
+    if isinstance(x, Fp8Table):
+        raise TypeError(f"{what}: {name} is an Fp8Table; {_FP8_TABLE_READERS}: {fp8_reason}")
     if isinstance(x, (TableRows, RowRefs)):
         raise TypeError(f"{what}: {type(x).__name__} describes the rows of one sampled batch; inference reads the whole "
                         "feature matrix, one row per graph node")
@@ -79,6 +146,14 @@ def _check_matrix(x, what, name="x"):
                          f"{tuple(x.shape)} {x.dtype} strides {tuple(x.stride())}")
     if x.requires_grad:
         raise RuntimeError(f"{what}: {name} requires grad, and inference is forward only (detach it)")
+
+
+def _check_table(x, what):
+    """``x`` of the entries that read an fp8 table in place: an ``Fp8Table`` of whole rows, or ``_check_matrix``"""
+    if not isinstance(x, Fp8Table):
+        return _check_matrix(x, what)
+    if x.ids is not None:
+        raise TypeError(f"{what}: x must be the whole Fp8Table (one row per graph node), not rows of it")
 
 
 def _check_graph(what, N, rowptr, col, parts=False):
@@ -186,8 +261,23 @@ def _check_offsets(part_offsets, what):
     return off
 
 
-def _parts_source(parts, off, dtype, F, what, name="part"):
-    """(base addresses [P], row stride in elements, dtype, F, device or None) of the two forms of ``parts``"""
+def _fp8_parts(parts, what):
+    """(the parts' e4m3 matrices, the exponents) when ``parts`` is a list of ``Fp8Table``; (parts, None) otherwise.  One
+    exponent vector serves all parts, the first non-empty part's: that every part was quantised against the same
+    exponents is the caller's duty, as on the exchange path (comparing them here would wait for the device)."""
+    if isinstance(parts, P2PPeers) or not any(isinstance(t, Fp8Table) for t in parts):
+        return parts, None
+    tabs = list(parts)
+    if not all(t is None or (isinstance(t, Fp8Table) and t.ids is None) for t in tabs):
+        raise TypeError(f"{what}: fp8 parts are read in place when EVERY part is a whole Fp8Table (None for an empty "
+                        f"one), got {sorted({type(t).__name__ for t in tabs})}")
+    live = [t for t in tabs if t is not None and t.size(0)]
+    return [None if t is None else t.q for t in tabs], (live or [t for t in tabs if t is not None])[0].scale_log2
+
+
+def _parts_source(parts, off, dtype, F, what, name="part", fp8=False):
+    """(base addresses [P], row stride in elements, dtype, F, device or None) of the two forms of ``parts``; ``fp8``:
+    the tensors are ``_fp8_parts``' e4m3 matrices (an element is a byte)"""
     P = len(off) - 1
     if isinstance(parts, P2PPeers):
         if dtype not in _ELEM or not isinstance(F, int) or F < 0:
@@ -213,7 +303,8 @@ def _parts_source(parts, off, dtype, F, what, name="part"):
             if rows:
                 raise ValueError(f"{what}: {name} {p} holds the rows [{off[p]}, {off[p + 1]}) and is None")
             continue
-        _check_matrix(t, what, f"{name} {p}")
+        if not fp8:
+            _check_matrix(t, what, f"{name} {p}")
         if t.size(0) != rows:
             raise ValueError(f"{what}: {name} {p} has {t.size(0)} rows, part_offsets gives it {rows}")
         if rows:
@@ -245,32 +336,42 @@ def _request(rowptr, col, row0, target_ids, T, out):
                 out_elem=_ELEM[out.dtype], out_dev=_p(out), out_stride_elems=out.stride(0) if T > 1 else 0)
 
 
-def _launch(entry, d, workspace, out):
+def _launch(entry, d, workspace, out, scale_log2=None):
+    """``scale_log2``: the exponents of an fp8 table, the _fp8 entries' second argument"""
     with torch.cuda.device(out.device):
-        nat.check(entry(C.byref(d), C.c_void_p(workspace.data_ptr()), workspace.numel(), _stream()))
+        nat.check(entry(C.byref(d), *([] if scale_log2 is None else [_p(scale_log2)]),
+                        C.c_void_p(workspace.data_ptr()), workspace.numel(), _stream()))
     return out
 
 
 def _agg_launch(x, rowptr, col, epilogue, self_scale, row0, target_ids, T, out, workspace):
-    """spp_graph_agg_forward: x [N, F] is one matrix"""
+    """spp_graph_agg_forward: x [N, F] is one matrix; spp_graph_agg_forward_fp8: an ``Fp8Table`` read in place"""
     N, Fdim = x.shape
+    if isinstance(x, Fp8Table):
+        d = nat.GraphAggDesc(epilogue=_EPILOGUES[epilogue], x_elem=nat.SPP_ELEM_FP8_E4M3, x_dev=_p(x.q), x_stride_elems=Fdim,
+                             x_rows=N, F=Fdim, self_scale=float(self_scale), **_request(rowptr, col, row0, target_ids, T, out))
+        return _launch(nat.load().spp_graph_agg_forward_fp8, d, workspace, out, x.scale_log2)
     d = nat.GraphAggDesc(epilogue=_EPILOGUES[epilogue], x_elem=_ELEM[x.dtype], x_dev=_p(x),
                          x_stride_elems=x.stride(0) if N > 1 else Fdim, x_rows=N, F=Fdim, self_scale=float(self_scale),
                          **_request(rowptr, col, row0, target_ids, T, out))
     return _launch(nat.load().spp_graph_agg_forward, d, workspace, out)
 
 
-def _agg_parts_launch(src, off, rowptr, col, epilogue, self_scale, row0, target_ids, T, out, workspace):
-    """spp_graph_agg_parts_forward: ``src`` is ``_parts_source``'s (base addresses, row stride, dtype, F)"""
+def _agg_parts_launch(src, off, rowptr, col, epilogue, self_scale, row0, target_ids, T, out, workspace, scale_log2=None):
+    """spp_graph_agg_parts_forward: ``src`` is ``_parts_source``'s (base addresses, row stride, dtype, F); with
+    ``scale_log2`` spp_graph_agg_parts_forward_fp8 over e4m3 parts"""
     ptrs, stride, x_dtype, Fdim = src
-    d = nat.GraphAggPartsDesc(epilogue=_EPILOGUES[epilogue], x_elem=_ELEM[x_dtype], num_parts=len(off) - 1,
+    fp8 = scale_log2 is not None
+    d = nat.GraphAggPartsDesc(epilogue=_EPILOGUES[epilogue], x_elem=nat.SPP_ELEM_FP8_E4M3 if fp8 else _ELEM[x_dtype],
+                              num_parts=len(off) - 1,
                               x_stride_elems=stride, F=Fdim, self_scale=float(self_scale),
                               **_request(rowptr, col, row0, target_ids, T, out))
     for p, v in enumerate(off):
         d.part_offsets[p] = v
     for p, v in enumerate(ptrs):
         d.x_parts_dev[p] = v or None
-    return _launch(nat.load().spp_graph_agg_parts_forward, d, workspace, out)
+    L = nat.load()
+    return _launch(L.spp_graph_agg_parts_forward_fp8 if fp8 else L.spp_graph_agg_parts_forward, d, workspace, out, scale_log2)
 
 
 def _gat_launch(h, a_src, a_dst, rowptr, col, heads, negative_slope, relu, row0, target_ids, T, out, workspace):
@@ -303,8 +404,9 @@ def graph_aggregate(x, rowptr, col, *, row0=None, num_targets=None, target_ids=N
                     out_dtype=torch.float32, workspace=None):
     """Aggregation over whole rows of the resident graph (``spp_graph_agg_forward``, include/spp.h).
 
-    ``x`` [N, F]: one row per graph node (fp16 / fp32 / bf16, possibly a strided view); ``rowptr`` / ``col``: the
-    graph's CSR (int64, global ids).  The targets are a slab, ``row0`` and ``num_targets`` (output row i is node
+    ``x`` [N, F]: one row per graph node (fp16 / fp32 / bf16, possibly a strided view) -- or an ``Fp8Table``, read in
+    place by ``spp_graph_agg_forward_fp8`` with the bits of the same call on its fp32 dequantisation; ``rowptr`` /
+    ``col``: the graph's CSR (int64, global ids).  The targets are a slab, ``row0`` and ``num_targets`` (output row i is node
     row0 + i), or a list, ``target_ids`` (int64, any order, duplicates allowed).  ``epilogue``: "mean" [T, F],
     "operand" [T, 2F] = [mean | x[target]] or "sum" [T, F] = self_scale * x[target] + sum.  fp32 sums; a bf16 output
     is rounded once.  A ``col`` entry outside the graph reads row 0, a target id outside it gives a row of zeros.
@@ -313,13 +415,14 @@ def graph_aggregate(x, rowptr, col, *, row0=None, num_targets=None, target_ids=N
     CUDA tensor of at least ``graph_agg_workspace_bytes(T)`` bytes, reusable between calls on one stream; allocated
     when None.  Nothing here waits for the device."""
     what = "graph_aggregate"
-    _check_matrix(x, what)
+    _check_table(x, what)
     N, Fdim = x.shape
     _check_graph(what, N, rowptr, col)
     _check_epilogue(what, epilogue)
     _check_out_dtype(what, out_dtype)
     row0, target_ids, T = _check_targets(what, N, row0, num_targets, target_ids)
-    workspace = _on_device(what, "x, rowptr, col, target_ids and workspace", x.device, [x, rowptr, col, target_ids],
+    workspace = _on_device(what, "x, rowptr, col, target_ids and workspace", x.device,
+                           [x.q if isinstance(x, Fp8Table) else x, rowptr, col, target_ids],
                            workspace, graph_agg_workspace_bytes, T)
     out = torch.empty((T, 2 * Fdim if epilogue == "operand" else Fdim), dtype=out_dtype, device=x.device)
     return _agg_launch(x, rowptr, col, epilogue, self_scale, row0, target_ids, T, out, workspace)
@@ -334,13 +437,16 @@ def graph_aggregate_parts(parts, part_offsets, rowptr, col, *, row0=None, num_ta
 
     ``parts``: a list of P CUDA tensors on one device (an empty part may be None or have 0 rows) that share dtype, width
     and row stride -- or a ``P2PPeers`` (the ranks' partitions as addresses in this process, ``p2p_open_peers``) with
-    ``dtype=`` and ``F=``.  ``rowptr`` / ``col``: the WHOLE graph's CSR with global ids; the targets, ``epilogue``,
+    ``dtype=`` and ``F=`` -- or a list of ``Fp8Table`` (None for an empty part), read in place by
+    ``spp_graph_agg_parts_forward_fp8`` with the first non-empty part's exponents for all of them (that the parts agree on
+    the exponents is the caller's duty).  ``rowptr`` / ``col``: the WHOLE graph's CSR with global ids; the targets, ``epilogue``,
     ``self_scale``, ``out_dtype`` and ``workspace`` as ``graph_aggregate``, the ids global.  ``out``: an fp32 / bf16
     [T, F or 2F] matrix to write into (rows of a larger one allowed).  Nothing here maps memory or enables peer access,
     and nothing waits for the device."""
     what = "graph_aggregate_parts"
     off = _check_offsets(part_offsets, what)
-    *src, dev = _parts_source(parts, off, dtype, F, what)
+    parts, scale_log2 = _fp8_parts(parts, what)
+    *src, dev = _parts_source(parts, off, dtype, F, what, fp8=scale_log2 is not None)
     _check_graph(what, off[-1], rowptr, col, parts=True)
     _check_epilogue(what, epilogue)
     _check_out_dtype(what, out_dtype)
@@ -349,10 +455,10 @@ def graph_aggregate_parts(parts, part_offsets, rowptr, col, *, row0=None, num_ta
     _check_out(what, out, out_dtype, T, width)
     dev = rowptr.device if dev is None else dev
     workspace = _on_device(what, "the parts, rowptr, col, target_ids, workspace and out", dev,
-                           [rowptr, col, target_ids, out], workspace, graph_agg_workspace_bytes, T)
+                           [rowptr, col, target_ids, out, scale_log2], workspace, graph_agg_workspace_bytes, T)
     if out is None:
         out = torch.empty((T, width), dtype=out_dtype, device=dev)
-    return _agg_parts_launch(src, off, rowptr, col, epilogue, self_scale, row0, target_ids, T, out, workspace)
+    return _agg_parts_launch(src, off, rowptr, col, epilogue, self_scale, row0, target_ids, T, out, workspace, scale_log2)
 
 
 def graph_gat_aggregate(h, a_src, a_dst, rowptr, col, *, heads, negative_slope=0.2, relu=False, row0=None,
@@ -566,10 +672,18 @@ def _row_tiles(A):
     """(first row, rows, tile) over A in tiles of exactly _GEMM_ROWS rows, the last one zero-padded.  The library picks
     a GEMM kernel -- and with it the order of the sum over K -- by the problem's shape, so the same operand row can
     come out with different last bits from a [600, K] and a [75, K] product.  With one shape for every call a node's
-    result depends on its own row alone: not on the slab size, and not on whether ``nodes`` selected it."""
+    result depends on its own row alone: not on the slab size, and not on whether ``nodes`` selected it.  The tiles of an
+    ``Fp8Table`` (or of ``table[ids]``) are fp32, straight from ``spp_fp8_rows_f32``: the same shape, the same zero
+    padding and exactly the values of the table dequantised to fp32."""
     T = A.size(0)
     for r in range(0, T, _GEMM_ROWS):
         n = min(_GEMM_ROWS, T - r)
+        if isinstance(A, Fp8Table):
+            tile = (torch.empty if n == _GEMM_ROWS else torch.zeros)((_GEMM_ROWS, A.size(1)), dtype=torch.float32,
+                                                                      device=A.device)
+            A.rows_f32(tile[:n], r)
+            yield r, n, tile
+            continue
         tile = A[r:r + n]
         if n < _GEMM_ROWS:
             tile = A.new_zeros((_GEMM_ROWS, A.size(1)))
@@ -587,7 +701,9 @@ def _tiles_contiguous(A):
 # ---- where the table lives: the two placements the drivers below are written against --------------------------------
 class _Resident:
     """One rank owns the rows [0, N) of one matrix ``x``: the whole-table kernels, every layer in a matrix of its own
-    that is dropped when the next layer is complete, nothing to publish and nothing to wait for at a layer boundary"""
+    that is dropped when the next layer is complete, nothing to publish and nothing to wait for at a layer boundary.
+    ``x`` may be an ``Fp8Table``: layer 0's ``aggregate`` goes to the fp8 entry (``_agg_launch``), ``_row_tiles(x)`` and
+    ``_row_tiles(x[ids])`` are fp32 tiles, and every later layer reads activations as before."""
     lo = 0
     head_tiles = staticmethod(_row_tiles)                 # the tiles of a block of SAGEResInception's head, as they are
 
@@ -1105,7 +1221,8 @@ def layerwise_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 <<
     are bf16 as under ``torch.autocast`` in training (fp32 sums, fp32 log_softmax).  With ``nodes`` the last conv layer,
     GIN's head and the log_softmax are computed for those nodes only.  The model is put in eval mode and its mode
     restored; nothing records a gradient.  ``x``: a CUDA fp16 / fp32 / bf16 matrix, one row per node, possibly a strided
-    view of the resident table (``FastSampler.resident_graph()``).  Nothing waits for the device but the range check of
+    view of the resident table (``FastSampler.resident_graph()``) -- or an ``Fp8Table``, read in place with the bits of
+    the same call on its fp32 dequantisation (all four models; ``evaluate`` and the field entries too).  Nothing waits for the device but the range check of
     ``nodes``, up front.
 
     Memory, as arithmetic: an activation matrix is N * hidden * sizeof(act_dtype) bytes and two are live at a layer
@@ -1126,7 +1243,7 @@ def _check_labels(what, name, y, rows):
 def _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, y, sink):
     """the resident entries: every argument check, then the device, then the pass into ``sink``"""
     _check_model(model, what, "SAGE and GIN (and GAT, SAGEResInception)")
-    _check_matrix(x, what)
+    _check_table(x, what)
     N = x.size(0)
     _check_graph(what, N, rowptr, col)
     rows_per_slab = _check_run(what, act_dtype, rows_per_slab, nodes)
@@ -1362,7 +1479,7 @@ def _field_score(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, f
         raise NotImplementedError(f"{what}: a row-partitioned table is not scored over a receptive field (layer 0 reads "
                                   "one resident matrix in place and the field's layers live on one device); "
                                   "partitioned_inference(nodes=...) scores it")
-    _check_matrix(x, what)
+    _check_table(x, what)
     N = x.size(0)
     _check_graph(what, N, rowptr, col)
     rows_per_slab = _check_run(what, act_dtype, rows_per_slab, None)
@@ -1510,7 +1627,8 @@ def _partitioned(what, names, model, x_local, rowptr, col, part_offsets, rank, p
     """the partitioned entries behind their model filters.  Every argument and model-shape check comes before ``peers``
     is touched, and the device is required last: a refused call publishes nothing and waits for nobody."""
     _check_model(model, what, names)
-    _check_matrix(x_local, what, "x_local")
+    _check_matrix(x_local, what, "x_local", "the partitioned drivers do not carry fp8 partitions through peers.share yet "
+                  "(graph_aggregate_parts reads them); dequantise the partition, or score the table on one device")
     off = _check_offsets(part_offsets, what)
     P = len(off) - 1
     rank = int(rank)

@@ -8,6 +8,7 @@ with bf16 activations, timed per layer, and layer 1's slabs once more through th
     python tools/inference_profile.py --evaluate [--repeats 3] ...
     python tools/inference_profile.py --parts 8 --workload S-products [--repeats 5] ...
     python tools/inference_profile.py --parts 8 --model gat --workload S-products [--heads 1] [--repeats 9] ...
+    python tools/inference_profile.py --fp8 [--repeats 5] ...
 
 ``--model gat``: GAT 3 x hidden at ``--heads`` through spp_graph_gat_forward, ``--repeats`` whole passes in one process
 (the first warms up code objects and the GEMM library's choices; every pass is reported).  Its bytes are the mean's plus
@@ -34,6 +35,13 @@ between the medians.  One slab's outputs are compared bit for bit first.
 ``--parts P --model gat``: the same for the attention.  A random bf16 h [N, hidden] and fp32 logits [N, 2 * heads], cut
 into P equal row ranges, an allocation per part and kind; every slab attended twice: ``spp_graph_gat_forward`` on the
 whole matrices and ``spp_graph_gat_parts_forward`` on the parts, alternating, after one slab is compared bit for bit.
+
+``--fp8``: layer 1's aggregation from an fp8 table read in place.  The workload's fp16 table quantised to e4m3 on the
+device (``fp8.quantize_e4m3``), and every slab's OPERAND aggregation with a bf16 output -- SAGE's first layer as the driver
+launches it -- run twice: ``spp_graph_agg_forward`` on the fp16 table (the baseline; its kernels are the parent commit's,
+instruction for instruction) and ``spp_graph_agg_forward_fp8`` on the e4m3 table; ``--repeats`` alternating passes after one
+warm-up pass of each, every pass reported, the ratio taken between the medians.  Then the whole table once through
+``spp_fp8_rows_f32`` in the drivers' GEMM tiles (what GAT's first projection reads).
 
 Per layer: seconds of the aggregation alone (events around every slab's launch, the drivers' ``inference._agg_launch`` /
 ``_gat_launch`` replaced by a timed one for the run, summed), edges/s, and the algorithmic bytes/s
@@ -64,6 +72,7 @@ def main():
     ap.add_argument("--torch-epilogue", action="store_true", help="sageresinception: the layer tail as torch ops")
     ap.add_argument("--evaluate", action="store_true", help="sage: the pass through evaluate, its tail against the torch tail")
     ap.add_argument("--parts", type=int, default=0, help="P > 0: time the aggregation over P row ranges against the whole matrix")
+    ap.add_argument("--fp8", action="store_true", help="time layer 1's aggregation from the table as fp8, read in place, against fp16")
     a = ap.parse_args()
     from salient_plusplus_amd import _native as nat
     from salient_plusplus_amd import inference as inf
@@ -82,6 +91,8 @@ def main():
            "rows_per_slab": a.rows_per_slab, "build_s": round(time.time() - t0, 1), "layers": []}
     del deg, long_rows
     print(json.dumps({k: v for k, v in res.items() if k != "layers"}), flush=True)
+    if a.fp8:
+        return fp8_leg(a, wl, res)
     if a.parts > 0:
         return gat_parts_leg(a, wl, res) if a.model == "gat" else parts_leg(a, wl, res)
     if a.model == "gat":
@@ -373,6 +384,62 @@ def parts_leg(a, wl, res):
         res["widths"].append(one)
         print(json.dumps(one), flush=True)
         del parts
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+def fp8_leg(a, wl, res):
+    from salient_plusplus_amd import fp8
+    from salient_plusplus_amd import inference as inf
+    x, rowptr, col = wl.x, wl.rowptr, wl.col
+    N, E, F_ = wl.num_nodes, col.numel(), wl.x.size(1)
+    res.pop("layers")
+    t0 = time.time()
+    x8 = inf.Fp8Table(fp8.quantize_e4m3(x))
+    torch.cuda.synchronize()
+    res.update(fp8=True, F=F_, quantise_s=round(time.time() - t0, 1), epilogue="operand", out_dtype="bfloat16")
+    ws = torch.empty(inf.graph_agg_workspace_bytes(min(a.rows_per_slab, N)), dtype=torch.uint8, device=x.device)
+    slabs = [(s, min(a.rows_per_slab, N - s)) for s in range(0, N, a.rows_per_slab)]
+    out = torch.empty((min(a.rows_per_slab, N), 2 * F_), dtype=torch.bfloat16, device=x.device)
+
+    def run(table):
+        for s, T in slabs:
+            inf._agg_launch(table, rowptr, col, "operand", 0.0, s, None, T, out[:T], ws)
+    times = {"fp16": [], "fp8": []}
+    b, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for rep in range(a.repeats + 1):                     # (pass 0 warms up both)
+        for name, table in (("fp16", x), ("fp8", x8)):
+            torch.cuda.synchronize()
+            b.record()
+            run(table)
+            e.record()
+            e.synchronize()
+            assert bool(torch.isfinite(out[:: max(1, out.size(0) // 4096)].float()).all())
+            if rep:
+                times[name].append(round(b.elapsed_time(e) / 1e3, 5))
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    nbytes = {k: (E + N) * F_ * w + 16 * N + 8 * E + N * 2 * F_ * 2 for k, w in (("fp16", 2), ("fp8", 1))}
+    res.update(fp16_s=times["fp16"], fp8_s=times["fp8"], fp16_median_s=med["fp16"], fp8_median_s=med["fp8"],
+               ratio_fp8_over_fp16=round(med["fp8"] / med["fp16"], 4),
+               fp16_algorithmic_TBps=round(nbytes["fp16"] / med["fp16"] / 1e12, 3),
+               fp8_algorithmic_TBps=round(nbytes["fp8"] / med["fp8"] / 1e12, 3))
+    # the whole table as the drivers' fp32 GEMM tiles (one buffer: the tiles' consumer is not what is timed)
+    tile = torch.empty((inf._GEMM_ROWS, F_), dtype=torch.float32, device=x.device)
+    tiles_s = []
+    for rep in range(a.repeats + 1):
+        torch.cuda.synchronize()
+        b.record()
+        for r in range(0, N, inf._GEMM_ROWS):
+            x8.rows_f32(tile[:min(inf._GEMM_ROWS, N - r)], r)
+        e.record()
+        e.synchronize()
+        if rep:
+            tiles_s.append(round(b.elapsed_time(e) / 1e3, 5))
+    tmed = sorted(tiles_s)[len(tiles_s) // 2]
+    res.update(rows_f32_s=tiles_s, rows_f32_median_s=tmed, rows_f32_algorithmic_TBps=round(N * F_ * 5 / tmed / 1e12, 3))
+    print(json.dumps({k: v for k, v in res.items() if k.startswith(("fp", "ratio", "rows_f32", "quant"))}), flush=True)
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:
