@@ -685,7 +685,10 @@ spp_status spp_gat_backward(const int64_t* rowptr_dev, const int64_t* col_dev, i
  *                              code: 0 fp32, 1 fp16, 2 bf16, see spp_elem below), K % 4 == 0; the rest is fp32.
  *   spp_gat_aggregate_backward: from grad_z: grad_a_src [S] (caller zeroes it), grad_a_dst [T], and -- when
  *                              grad_x_dev != NULL (caller zeroes it) -- grad_x[j,:] += alpha_ij grad_z_i.
- *   spp_gat_logits_backward:   grad_v_src[c] = sum_j grad_a_src[j] x[j,c], grad_v_dst[c] = sum_{i<T} grad_a_dst[i] x[i,c]. */
+ *   spp_gat_logits_backward:   grad_v_src[c] = sum_j grad_a_src[j] x[j,c], grad_v_dst[c] = sum_{i<T} grad_a_dst[i] x[i,c].
+ * Each of these (and spp_gat_aggregate_backward_gather below) is the heads = 1 spelling of its spp_gat_mh_* entry:
+ * the same implementation, checks and kernels with the head count fixed at 1, so a_src, a_dst, row_max, row_sum and
+ * grad_a_* are plain float arrays (4-byte aligned); z, grad_z, v_*, grad_x and the workspace are 16-byte aligned. */
 spp_status spp_gat_logits(const void* x_dev, int32_t x_is_half, int64_t x_stride_elems, int64_t num_sources,
                           int64_t num_targets, int64_t K, const float* v_src_dev, const float* v_dst_dev,
                           float* a_src_dev, float* a_dst_dev, void* stream);
@@ -708,7 +711,9 @@ spp_status spp_gat_aggregate_backward(const int64_t* rowptr_dev, const int64_t* 
  * scan, fill) instead of E x K fp32 atomics: grad_x_dev [S, K] fp32 is written COMPLETELY, including the rank-1
  * terms of the logits -- grad_a_src[s] v_src for every source and grad_a_dst[s] v_dst for the first T -- that
  * the atomic form leaves to the caller (a_src = x v_src, a_dst = x[:T] v_dst).  grad_a_src_dev [S] is zeroed by the
- * caller as before.  workspace_dev: spp_gat_aggregate_backward_gather_workspace_bytes(T, S, E) bytes, 16-byte aligned. */
+ * caller as before.  workspace_dev: spp_gat_aggregate_backward_gather_workspace_bytes(T, S, E) bytes, 16-byte aligned
+ * (= spp_gat_mh_aggregate_backward_gather_workspace_bytes(T, S, E, 1)).  The heads = 1 spelling of
+ * spp_gat_mh_aggregate_backward_gather. */
 int64_t spp_gat_aggregate_backward_gather_workspace_bytes(int64_t num_targets, int64_t num_sources, int64_t num_edges);
 spp_status spp_gat_aggregate_backward_gather(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
                                              int64_t num_sources, int64_t num_edges, const void* x_dev,
@@ -723,8 +728,10 @@ spp_status spp_gat_aggregate_backward_gather(const int64_t* rowptr_dev, const in
  * W [H*C, K] holds H blocks W_h of C rows; V_src[h,:] = W_h^T att_src[h], V_dst[h,:] = W_h^T att_dst[h]. Layouts,
  * all fp32 and row-major: V_src, V_dst [H, K]; a_src [S, H]; a_dst [T, H]; z, grad_z [T, H, K]; row_max, row_sum
  * [T, H]; grad_a_src [S, H]; grad_a_dst [T, H]; grad_x [S, K].  x rows: element code x_elem (0 fp32, 1 fp16, 2 bf16),
- * K % 4 == 0, K <= 1024, rows aligned to 4 elements, as above.  The per-head arrays, z, grad_z, V and grad_x are
- * 16-byte aligned.  A head count outside {1, 2, 4, 8}, an unknown x_elem or a bad K returns SPP_ERR_INVALID before
+ * K % 4 == 0, K <= 1024, rows aligned to 4 elements, as above.  z, grad_z, V, grad_x and the workspace are 16-byte
+ * aligned; the per-head arrays (a_src, a_dst, row_max, row_sum, grad_a_src, grad_a_dst) are read and written H floats
+ * at a time and need 4 * min(H, 4) bytes: 4 at H = 1, 8 at H = 2, 16 at H = 4 and 8.  Every entry checks the head
+ * count, x_elem and K first, then the sizes (an empty hop returns SPP_OK here), then the buffers.  A head count outside {1, 2, 4, 8}, an unknown x_elem or a bad K returns SPP_ERR_INVALID before
  * anything is launched (the workspace query returns SPP_ERR_INVALID for a bad head count).  Each source row is read
  * once per edge for all H heads.
  *   spp_gat_mh_logits:           a_src[j,h] = x_j . V_src[h] (all S rows), a_dst[i,h] = x_i . V_dst[h] (the first T)

@@ -955,328 +955,20 @@ __global__ __launch_bounds__(kAggNT) void k_gat_bwd(const int64_t* __restrict__ 
 // v_dst = W^T att_dst, the aggregation runs over the RAW rows (128-wide fp16 in layer 1 instead of
 // 256-wide fp32) and only the T aggregated target rows are projected: layer 1 of the papers-scale batch
 // drops from a 947 k-row GEMM (62 GFLOP, and as much again for its weight gradient) to a 164 k-row one.
+//
+// With PyG's `heads` = H, W [H*C, K] is H blocks W_h of C rows;  v_src^h = W_h^T att_src[h],  v_dst^h = W_h^T att_dst[h]
+// (V_src, V_dst: [H, K]).  Per head h:
+//   a_src[j,h] = x_j . v_src^h,  a_dst[i,h] = x_i . v_dst^h,  alpha^h = softmax over row i of leaky_relu(a_src + a_dst),
+//   z[i,h,:] = sum_j alpha_ij^h x_j    (RAW rows, K wide)  -> out_i^h = W_h z[i,h,:].
+// Every kernel below is templated on H (1, 2, 4 or 8; heads = 1 is the H = 1 instance, not code of its own) and walks
+// the edges ONCE for all heads: one load of the row chunk and one load of the H logits per edge, shared by the heads;
+// what grows with H are the registers (H softmax states and accumulators) and z ([T, H, K]).
+// Layouts: a_src [S, H], a_dst [T, H], V [H, K], z and grad_z [T, H, K], row_max / row_sum [T, H], alpha_e [E, H],
+// alpha_self [T, H]; all fp32, row-major.  Per head, the order of operations does not depend on H.
 // ================================================================================================
 __device__ __forceinline__ f4 load4v(const float* p) { return load4(p); }
 
-// a_src[j] = x_j . v_src  (all S rows);  a_dst[j] = x_j . v_dst  (the first T rows: the targets)
-// A group of lpr lanes takes kDotRows consecutive rows; their loads are issued back to back (row index clamped,
-// not predicated: with one row per group and a predicate the kernel had ONE load in flight per lane and ran
-// at a third of the HBM rate).
-constexpr int kDotRows = 8;
-template <typename Tin>
-__global__ __launch_bounds__(kAggNT) void k_rowdot2(const Tin* __restrict__ x, int64_t x_stride, int64_t S, int64_t T,
-                                                    int64_t K, const float* __restrict__ v_src,
-                                                    const float* __restrict__ v_dst, int lpr_log2,
-                                                    float* __restrict__ a_src, float* __restrict__ a_dst) {
-  const int lpr = 1 << lpr_log2;
-  const int lane = threadIdx.x & (lpr - 1);
-  const int64_t j0 = (((int64_t)blockIdx.x * kAggNT + threadIdx.x) >> lpr_log2) * kDotRows;
-  if (j0 >= S) return;  // whole groups leave together (the shuffles below stay inside a group)
-  float ds[kDotRows], dd[kDotRows];
-#pragma unroll
-  for (int u = 0; u < kDotRows; ++u) ds[u] = dd[u] = 0.f;
-  for (int64_t c = (int64_t)lane * 4; c < K; c += (int64_t)lpr * 4) {
-    f4 xv[kDotRows];
-#pragma unroll
-    for (int u = 0; u < kDotRows; ++u) {
-      const int64_t j = j0 + u < S ? j0 + u : S - 1;
-      xv[u] = load4(x + j * x_stride + c);
-    }
-    const f4 vs = load4v(v_src + c), vd = load4v(v_dst + c);
-#pragma unroll
-    for (int u = 0; u < kDotRows; ++u) {
-      ds[u] += xv[u].x * vs.x + xv[u].y * vs.y + xv[u].z * vs.z + xv[u].w * vs.w;
-      dd[u] += xv[u].x * vd.x + xv[u].y * vd.y + xv[u].z * vd.z + xv[u].w * vd.w;
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < kDotRows; ++u) {
-    for (int d = lpr >> 1; d >= 1; d >>= 1) {  // the lpr lanes of a row are consecutive lanes of one wavefront
-      ds[u] += __shfl_xor(ds[u], d, kWave);
-      dd[u] += __shfl_xor(dd[u], d, kWave);
-    }
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int u = 0; u < kDotRows; ++u) {
-      const int64_t j = j0 + u;
-      if (j < S) {
-        a_src[j] = ds[u];
-        if (j < T) a_dst[j] = dd[u];
-      }
-    }
-  }
-}
-
-// out_src[c] += sum_j w_src[j] x[j,c] over all rows; out_dst[c] += sum_{j<T} w_dst[j] x[j,c]   (out zeroed by the caller)
-// (1024 threads and 4096 rows per workgroup: every workgroup ends in K atomics onto the SAME K addresses, and with
-// 256-thread / 1024-row workgroups those 924 x 256 same-address adds were most of the kernel's time)
-constexpr int kColsumNT = 1024;
-template <typename Tin>
-__global__ __launch_bounds__(kColsumNT) void k_colsum2(const Tin* __restrict__ x, int64_t x_stride, int64_t S, int64_t T,
-                                                       int64_t K, const float* __restrict__ w_src,
-                                                       const float* __restrict__ w_dst, int64_t rows_per_wg,
-                                                       float* __restrict__ out_src, float* __restrict__ out_dst) {
-  __shared__ float red[2][kColsumNT][4];
-  const int groups = (int)(K / 4);              // threads that share a row (K/4 <= kColsumNT)
-  const int cg = threadIdx.x % groups;          // this thread's 4 columns
-  const int rsub = threadIdx.x / groups, rstep = kColsumNT / groups;
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_wg;
-  const int64_t r1 = r0 + rows_per_wg < S ? r0 + rows_per_wg : S;
-  f4 as = {0.f, 0.f, 0.f, 0.f}, ad = {0.f, 0.f, 0.f, 0.f};
-  if (rsub < rstep) {
-    int64_t j = r0 + rsub;
-    const int64_t tlast = T > 0 ? T - 1 : 0;
-    const float* __restrict__ wdp = T > 0 ? w_dst : w_src;  // (w_dst may be NULL without targets)
-    for (; j + 3 * rstep < r1; j += 4 * rstep) {  // four independent rows in flight, no predicate on a load (eight: slower)
-      f4 xv[4];
-      float ws[4], wd[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int64_t ju = j + u * rstep;
-        xv[u] = load4(x + ju * x_stride + (int64_t)cg * 4);
-        ws[u] = w_src[ju];
-        wd[u] = wdp[ju < T ? ju : tlast];
-        if (ju >= T) wd[u] = 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        as.x += ws[u] * xv[u].x; as.y += ws[u] * xv[u].y; as.z += ws[u] * xv[u].z; as.w += ws[u] * xv[u].w;
-        ad.x += wd[u] * xv[u].x; ad.y += wd[u] * xv[u].y; ad.z += wd[u] * xv[u].z; ad.w += wd[u] * xv[u].w;
-      }
-    }
-    for (; j < r1; j += rstep) {
-      const f4 xv = load4(x + j * x_stride + (int64_t)cg * 4);
-      const float ws = w_src[j];
-      as.x += ws * xv.x; as.y += ws * xv.y; as.z += ws * xv.z; as.w += ws * xv.w;
-      if (j < T) {
-        const float wd = w_dst[j];
-        ad.x += wd * xv.x; ad.y += wd * xv.y; ad.z += wd * xv.z; ad.w += wd * xv.w;
-      }
-    }
-  }
-  red[0][threadIdx.x][0] = as.x; red[0][threadIdx.x][1] = as.y; red[0][threadIdx.x][2] = as.z; red[0][threadIdx.x][3] = as.w;
-  red[1][threadIdx.x][0] = ad.x; red[1][threadIdx.x][1] = ad.y; red[1][threadIdx.x][2] = ad.z; red[1][threadIdx.x][3] = ad.w;
-  __syncthreads();
-  if (threadIdx.x < groups) {  // one thread per column group sums the row sub-lanes, then one atomic per column
-    float s4[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    for (int r = 0; r < rstep; ++r)
-      for (int q = 0; q < 4; ++q) {
-        s4[0][q] += red[0][r * groups + threadIdx.x][q];
-        s4[1][q] += red[1][r * groups + threadIdx.x][q];
-      }
-    for (int q = 0; q < 4; ++q) {
-      unsafeAtomicAdd(out_src + threadIdx.x * 4 + q, s4[0][q]);
-      if (r0 < T) unsafeAtomicAdd(out_dst + threadIdx.x * 4 + q, s4[1][q]);
-    }
-  }
-}
-
-// z_i = sum_j alpha_ij x_j over row i (its diagonal entry dropped) plus the self loop; x rows fp16 or fp32,
-// 4 columns per lane, online softmax (every lane of a row's group walks the same edges)
-template <typename Tin>
-__global__ __launch_bounds__(kAggNT) void k_gat_agg_fwd(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,
-                                                        int64_t T, const Tin* __restrict__ x, int64_t x_stride, int64_t K,
-                                                        const float* __restrict__ a_src, const float* __restrict__ a_dst,
-                                                        float slope, int lpr_log2, float* __restrict__ z,
-                                                        float* __restrict__ row_max, float* __restrict__ row_sum) {
-  const int lpr = 1 << lpr_log2;
-  const int lane = threadIdx.x & (lpr - 1);
-  const int64_t t = ((int64_t)blockIdx.x * kAggNT + threadIdx.x) >> lpr_log2;
-  if (t >= T) return;
-  const int64_t b = rowptr[t], e = rowptr[t + 1];
-  const float ad = a_dst[t];
-  const float self = lrelu(a_src[t] + ad, slope);
-  for (int64_t c = (int64_t)lane * 4; c < K || c == (int64_t)lane * 4; c += (int64_t)lpr * 4) {
-    const bool has = c < K;
-    f4 acc = has ? load4(x + t * x_stride + c) : f4{0.f, 0.f, 0.f, 0.f};
-    float mm = self, ss = 1.f;
-    // kNb neighbours per round: their ids, then their logits and rows, each issued back to back (clamped
-    // indices, no predicated load); the online softmax then runs over registers.  One neighbour at a time
-    // was two dependent round trips per edge.
-    constexpr int kNb = 4;
-    const int64_t cc = has ? c : 0;
-    for (int64_t k0 = b; k0 < e; k0 += kNb) {
-      int64_t j[kNb];
-#pragma unroll
-      for (int u = 0; u < kNb; ++u) j[u] = col[k0 + u < e ? k0 + u : e - 1];
-      float as[kNb];
-      f4 xv[kNb];
-#pragma unroll
-      for (int u = 0; u < kNb; ++u) {
-        as[u] = a_src[j[u]];
-        xv[u] = load4(x + j[u] * x_stride + cc);
-      }
-#pragma unroll
-      for (int u = 0; u < kNb; ++u) {
-        if (k0 + u >= e || j[u] == t) continue;  // set_diag drops existing diagonal entries
-        const float sc = lrelu(as[u] + ad, slope);
-        if (sc > mm) {
-          const float r = __expf(mm - sc);
-          acc.x *= r; acc.y *= r; acc.z *= r; acc.w *= r;
-          ss *= r;
-          mm = sc;
-        }
-        const float w = __expf(sc - mm);
-        ss += w;
-        acc.x += w * xv[u].x; acc.y += w * xv[u].y; acc.z += w * xv[u].z; acc.w += w * xv[u].w;
-      }
-    }
-    if (has) {
-      const float inv = 1.f / ss;
-      *reinterpret_cast<float4*>(z + t * K + c) = make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv);
-    }
-    if (lane == 0 && c == 0) {
-      row_max[t] = mm;
-      row_sum[t] = ss;
-    }
-  }
-}
-
-// One wavefront per target i:  grad_e_ij = alpha_ij (g_i . x_j - g_i . z_i) lrelu'(raw);  grad_a_src[j] += grad_e_ij;
-// grad_a_dst[i] = sum_j grad_e_ij;  grad_x[j,:] += alpha_ij g_i  (only when grad_x != NULL: the first layer's
-// input needs no gradient, which saves E x K atomics)
-// kVec: 4 columns per lane (no input gradient wanted: only dot products, 8/16-byte loads);
-// otherwise one column per lane and step, so that the fp32 atomics of a group are contiguous
-template <typename Tin, bool kVec>
-__global__ __launch_bounds__(kAggNT) void k_gat_agg_bwd(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,
-                                                        int64_t T, const Tin* __restrict__ x, int64_t x_stride, int64_t K,
-                                                        const float* __restrict__ a_src, const float* __restrict__ a_dst,
-                                                        float slope, const float* __restrict__ z,
-                                                        const float* __restrict__ row_max, const float* __restrict__ row_sum,
-                                                        const float* __restrict__ g, int lpt_log2, float* __restrict__ grad_x,
-                                                        float* __restrict__ grad_a_src, float* __restrict__ grad_a_dst,
-                                                        float* __restrict__ alpha_e, float* __restrict__ alpha_self) {
-  // alpha_e / alpha_self (optional): the attention weight of every CSR entry (0 for a dropped diagonal entry) and of
-  // every target's self loop -- what the input gradient by GATHER over the transposed hop needs (k_gat_gx_gather)
-  // lpt = min(64, K rounded up to a power of two) lanes per target
-  const int lpt = 1 << lpt_log2;
-  const int lane = threadIdx.x & (lpt - 1);
-  const int64_t t = ((int64_t)blockIdx.x * kAggNT + threadIdx.x) >> lpt_log2;
-  const bool live = t < T;
-  const int64_t b = live ? rowptr[t] : 0, e = live ? rowptr[t + 1] : -1;
-  const float ad = live ? a_dst[t] : 0.f, m = live ? row_max[t] : 0.f, inv_s = live ? 1.f / row_sum[t] : 0.f;
-  auto group_sum = [&](float v) {
-    for (int d = lpt >> 1; d >= 1; d >>= 1) v += __shfl_xor(v, d, kWave);
-    return v;
-  };
-  // column c = lane + lpt * i: consecutive lanes touch consecutive columns, so a group's loads and --
-  // what matters -- its fp32 atomics are contiguous 4 * lpt-byte segments (the atomic units run at full
-  // rate on contiguous 256-byte wave instructions and ~17x slower on scattered ones)
-  float go = 0.f;  // g_i . z_i
-  if (live) {
-    if (kVec) {
-      for (int64_t c = (int64_t)lane * 4; c < K; c += (int64_t)lpt * 4) {
-        const f4 gv = load4(g + t * K + c), zv = load4(z + t * K + c);
-        go += gv.x * zv.x + gv.y * zv.y + gv.z * zv.z + gv.w * zv.w;
-      }
-    } else {
-      for (int64_t c = lane; c < K; c += lpt) go += g[t * K + c] * z[t * K + c];
-    }
-  }
-  go = group_sum(go);
-  // the targets sharing a wavefront have different degrees: every group runs to the longest row of its
-  // wavefront so that the shuffles stay convergent
-  int64_t n = live ? e - b + 1 : 0;
-  for (int d = lpt; d < kWave; d <<= 1) {
-    const int64_t o = __shfl_xor((long long)n, d, kWave);
-    n = o > n ? o : n;
-  }
-  float gad = 0.f;
-  for (int64_t i = 0; i < n; ++i) {
-    const int64_t k = b - 1 + i;  // k == b-1 stands for the self loop
-    const bool on = live && k < e;
-    const int64_t j = !on ? 0 : ((k < b) ? t : col[k]);
-    const bool use = on && !(k >= b && j == t);  // set_diag drops existing diagonal entries
-    float gh = 0.f, a = 0.f, raw = 0.f;
-    if (use) {
-      raw = a_src[j] + ad;
-      a = __expf(lrelu(raw, slope) - m) * inv_s;
-      if (kVec) {
-        for (int64_t c = (int64_t)lane * 4; c < K; c += (int64_t)lpt * 4) {
-          const f4 gv = load4(g + t * K + c), xv = load4(x + j * x_stride + c);
-          gh += gv.x * xv.x + gv.y * xv.y + gv.z * xv.z + gv.w * xv.w;
-        }
-      } else {
-        for (int64_t c = lane; c < K; c += lpt) {
-          const float gv = g[t * K + c];
-          gh += gv * load1(x + j * x_stride + c);
-          unsafeAtomicAdd(grad_x + j * K + c, a * gv);
-        }
-      }
-    }
-    gh = group_sum(gh);
-    if (alpha_e && on && lane == 0) {
-      if (k < b) alpha_self[t] = a;
-      else alpha_e[k] = a;  // (a == 0 for a dropped diagonal entry)
-    }
-    if (use) {
-      const float ge = a * (gh - go) * (raw > 0.f ? 1.f : slope);
-      gad += ge;
-      if (lane == 0) unsafeAtomicAdd(grad_a_src + j, ge);
-    }
-  }
-  if (live && lane == 0) grad_a_dst[t] = gad;
-}
-
-// Input gradient of the aggregate-then-project GAT layer by GATHER (no fp32 atomics, no zero fill, no separate rank-1
-// passes):  grad_x[s,:] = sum over the targets t of s: alpha_ts grad_z[t,:]  (+ the self loop's alpha_ss grad_z[s,:], s < T)
-//                         + grad_a_src[s] v_src  (+ grad_a_dst[s] v_dst, s < T)        -- a_src = x v_src, a_dst = x[:T] v_dst
-__global__ __launch_bounds__(kAggNT) void k_gat_gx_gather(const int32_t* __restrict__ start, const int32_t* __restrict__ ttgt,
-                                                          const int32_t* __restrict__ tedge, const float* __restrict__ alpha_e,
-                                                          const float* __restrict__ alpha_self, int64_t T, int64_t S,
-                                                          const float* __restrict__ g, int64_t K, int lpr_log2,
-                                                          const float* __restrict__ grad_a_src,
-                                                          const float* __restrict__ grad_a_dst,
-                                                          const float* __restrict__ v_src, const float* __restrict__ v_dst,
-                                                          float* __restrict__ grad_x) {
-  const int lpr = 1 << lpr_log2;
-  const int lane = threadIdx.x & (lpr - 1);
-  const int64_t srow = ((int64_t)blockIdx.x * kAggNT + threadIdx.x) >> lpr_log2;
-  if (srow >= S) return;
-  const int32_t b = start[srow], e = start[srow + 1];
-  const float gas = grad_a_src[srow];
-  const float gad = srow < T ? grad_a_dst[srow] : 0.f;
-  const float aself = srow < T ? alpha_self[srow] : 0.f;
-  for (int64_t c = (int64_t)lane * 4; c < K; c += (int64_t)lpr * 4) {
-    const float4 vs = *reinterpret_cast<const float4*>(v_src + c);
-    float4 acc = make_float4(gas * vs.x, gas * vs.y, gas * vs.z, gas * vs.w);
-    if (srow < T) {
-      const float4 vd = *reinterpret_cast<const float4*>(v_dst + c);
-      const float4 gs = *reinterpret_cast<const float4*>(g + srow * K + c);
-      acc.x += gad * vd.x + aself * gs.x; acc.y += gad * vd.y + aself * gs.y;
-      acc.z += gad * vd.z + aself * gs.z; acc.w += gad * vd.w + aself * gs.w;
-    }
-    int32_t k = b;
-    for (; k + 1 < e; k += 2) {  // two independent rows in flight
-      const int32_t t0 = ttgt[k], t1 = ttgt[k + 1];
-      const float w0 = alpha_e[tedge[k]], w1 = alpha_e[tedge[k + 1]];
-      const float4 v0 = *reinterpret_cast<const float4*>(g + (int64_t)t0 * K + c);
-      const float4 v1 = *reinterpret_cast<const float4*>(g + (int64_t)t1 * K + c);
-      acc.x += v0.x * w0 + v1.x * w1; acc.y += v0.y * w0 + v1.y * w1;
-      acc.z += v0.z * w0 + v1.z * w1; acc.w += v0.w * w0 + v1.w * w1;
-    }
-    if (k < e) {
-      const int32_t t0 = ttgt[k];
-      const float w0 = alpha_e[tedge[k]];
-      const float4 v0 = *reinterpret_cast<const float4*>(g + (int64_t)t0 * K + c);
-      acc.x += v0.x * w0; acc.y += v0.y * w0; acc.z += v0.z * w0; acc.w += v0.w * w0;
-    }
-    *reinterpret_cast<float4*>(grad_x + srow * K + c) = acc;
-  }
-}
-
-// ================================================================================================
-// Multi-head GATConv (heads = H > 1, PyG's `heads`), aggregate-then-project per head.  W [H*C, K] is H blocks W_h of
-// C rows;  v_src^h = W_h^T att_src[h],  v_dst^h = W_h^T att_dst[h]  (V_src, V_dst: [H, K]).  Per head h:
-//   a_src[j,h] = x_j . v_src^h,  a_dst[i,h] = x_i . v_dst^h,  alpha^h = softmax over row i of leaky_relu(a_src + a_dst),
-//   z[i,h,:] = sum_j alpha_ij^h x_j    (RAW rows, K wide)  -> out_i^h = W_h z[i,h,:].
-// Every kernel below walks the edges ONCE for all heads: one load of the row chunk and one load of the H logits per
-// edge, shared by the heads; what grows with H are the registers (H softmax states and accumulators) and z ([T, H, K]).
-// Layouts: a_src [S, H], a_dst [T, H], V [H, K], z and grad_z [T, H, K], row_max / row_sum [T, H], alpha_e [E, H],
-// alpha_self [T, H]; all fp32, row-major.  Per head, the order of operations is the single-head kernels'.
-// ================================================================================================
-// o[h] = p[h], h < H, in 16-byte (H % 4 == 0) or 8-byte (H == 2) loads: p is 4 * H-byte aligned
+// o[h] = p[h], h < H, in 16-byte (H % 4 == 0), 8-byte (H == 2) or scalar (H == 1) loads: p is 4 * min(H, 4)-byte aligned
 template <int H>
 __device__ __forceinline__ void load_heads(const float* p, float (&o)[H]) {
   if constexpr (H % 4 == 0) {
@@ -1304,7 +996,12 @@ __device__ __forceinline__ void store_heads(float* p, const float (&v)[H]) {
   }
 }
 
-// k_rowdot2 with 2H dot products per row; H = 8 takes half as many rows per group (2H accumulators per row)
+// a_src[j,h] = x_j . v_src^h  (all S rows);  a_dst[j,h] = x_j . v_dst^h  (the first T rows: the targets)
+// A group of lpr lanes takes kDotRows consecutive rows; their loads are issued back to back (row index clamped,
+// not predicated: with one row per group and a predicate the kernel had ONE load in flight per lane and ran
+// at a third of the HBM rate).  2H dot products per row; H = 8 takes half as many rows per group (2H accumulators
+// per row).
+constexpr int kDotRows = 8;
 template <int H>
 constexpr int mh_dot_rows() { return H <= 4 ? kDotRows : kDotRows / 2; }
 template <typename Tin, int H>
@@ -1316,7 +1013,7 @@ __global__ __launch_bounds__(kAggNT) void k_gat_mh_rowdot(const Tin* __restrict_
   const int lpr = 1 << lpr_log2;
   const int lane = threadIdx.x & (lpr - 1);
   const int64_t j0 = (((int64_t)blockIdx.x * kAggNT + threadIdx.x) >> lpr_log2) * R;
-  if (j0 >= S) return;  // whole groups leave together
+  if (j0 >= S) return;  // whole groups leave together (the shuffles below stay inside a group)
   float ds[R][H], dd[R][H];
 #pragma unroll
   for (int u = 0; u < R; ++u)
@@ -1325,7 +1022,7 @@ __global__ __launch_bounds__(kAggNT) void k_gat_mh_rowdot(const Tin* __restrict_
   for (int64_t c = (int64_t)lane * 4; c < K; c += (int64_t)lpr * 4) {
     f4 xv[R];
 #pragma unroll
-    for (int u = 0; u < R; ++u) {  // clamped, unpredicated: all R loads in flight (k_rowdot2)
+    for (int u = 0; u < R; ++u) {  // clamped, unpredicated: all R loads in flight
       const int64_t j = j0 + u < S ? j0 + u : S - 1;
       xv[u] = load4(x + j * x_stride + c);
     }
@@ -1343,7 +1040,7 @@ __global__ __launch_bounds__(kAggNT) void k_gat_mh_rowdot(const Tin* __restrict_
   for (int u = 0; u < R; ++u)
 #pragma unroll
     for (int h = 0; h < H; ++h)
-      for (int d = lpr >> 1; d >= 1; d >>= 1) {
+      for (int d = lpr >> 1; d >= 1; d >>= 1) {  // the lpr lanes of a row are consecutive lanes of one wavefront
         ds[u][h] += __shfl_xor(ds[u][h], d, kWave);
         dd[u][h] += __shfl_xor(dd[u][h], d, kWave);
       }
@@ -1359,17 +1056,22 @@ __global__ __launch_bounds__(kAggNT) void k_gat_mh_rowdot(const Tin* __restrict_
   }
 }
 
-// k_colsum2 for H heads: out_src[h,c] += sum_j w_src[j,h] x[j,c];  out_dst[h,c] += sum_{j<T} w_dst[j,h] x[j,c]
-// (out zeroed by the caller).  The 2H column sums of a workgroup leave through one LDS buffer, one after the other.
+// out_src[h,c] += sum_j w_src[j,h] x[j,c] over all rows;  out_dst[h,c] += sum_{j<T} w_dst[j,h] x[j,c]
+// (out zeroed by the caller).  The 2H column sums of a workgroup leave through one LDS buffer, one after the other;
+// H = 1 has room for both of its sums (32 KiB) and takes a single barrier round.
+// (1024 threads and 4096 rows per workgroup: every workgroup ends in K atomics per head onto the SAME addresses, and
+// with 256-thread / 1024-row workgroups those 924 x 256 same-address adds were most of the single-head kernel's time)
+constexpr int kColsumNT = 1024;
 template <typename Tin, int H>
 __global__ __launch_bounds__(kColsumNT) void k_gat_mh_colsum(const Tin* __restrict__ x, int64_t x_stride, int64_t S,
                                                              int64_t T, int64_t K, const float* __restrict__ w_src,
                                                              const float* __restrict__ w_dst, int64_t rows_per_wg,
                                                              float* __restrict__ out_src, float* __restrict__ out_dst) {
-  __shared__ float red[kColsumNT][4];
-  constexpr int kU = H <= 2 ? 4 : 2;            // independent rows in flight
-  const int groups = (int)(K / 4);
-  const int cg = threadIdx.x % groups;
+  constexpr int kPer = H == 1 ? 2 : 1;          // column sums per barrier round
+  __shared__ float red[kPer][kColsumNT][4];
+  constexpr int kU = H <= 2 ? 4 : 2;            // independent rows in flight, no predicate on a load (8 at H = 1: slower)
+  const int groups = (int)(K / 4);              // threads that share a row (K/4 <= kColsumNT)
+  const int cg = threadIdx.x % groups;          // this thread's 4 columns
   const int rsub = threadIdx.x / groups, rstep = kColsumNT / groups;
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_wg;
   const int64_t r1 = r0 + rows_per_wg < S ? r0 + rows_per_wg : S;
@@ -1417,22 +1119,33 @@ __global__ __launch_bounds__(kColsumNT) void k_gat_mh_colsum(const Tin* __restri
     }
   }
 #pragma unroll
-  for (int o = 0; o < 2 * H; ++o) {
-    const f4 v = o < H ? as[o] : ad[o - H];
-    red[threadIdx.x][0] = v.x; red[threadIdx.x][1] = v.y; red[threadIdx.x][2] = v.z; red[threadIdx.x][3] = v.w;
-    __syncthreads();
-    if (threadIdx.x < groups && (o < H || r0 < T)) {
-      float s4[4] = {0.f, 0.f, 0.f, 0.f};
-      for (int r = 0; r < rstep; ++r)
-        for (int q = 0; q < 4; ++q) s4[q] += red[r * groups + threadIdx.x][q];
-      float* out = o < H ? out_src + o * K : out_dst + (o - H) * K;
-      for (int q = 0; q < 4; ++q) unsafeAtomicAdd(out + threadIdx.x * 4 + q, s4[q]);
+  for (int o = 0; o < 2 * H; o += kPer) {
+#pragma unroll
+    for (int p = 0; p < kPer; ++p) {
+      const f4 v = o + p < H ? as[o + p] : ad[o + p - H];
+      float* r = red[p][threadIdx.x];
+      r[0] = v.x; r[1] = v.y; r[2] = v.z; r[3] = v.w;
     }
     __syncthreads();
+    if (threadIdx.x < groups) {  // one thread per column group sums the row sub-lanes, then one atomic per column
+      float s4[kPer][4] = {};
+      for (int r = 0; r < rstep; ++r)
+#pragma unroll
+        for (int p = 0; p < kPer; ++p)
+          for (int q = 0; q < 4; ++q) s4[p][q] += red[p][r * groups + threadIdx.x][q];
+#pragma unroll
+      for (int p = 0; p < kPer; ++p) {
+        if (o + p >= H && r0 >= T) continue;  // no target among this workgroup's rows
+        float* out = o + p < H ? out_src + (o + p) * K : out_dst + (o + p - H) * K;
+        for (int q = 0; q < 4; ++q) unsafeAtomicAdd(out + threadIdx.x * 4 + q, s4[p][q]);
+      }
+    }
+    if (o + kPer < 2 * H) __syncthreads();
   }
 }
 
-// k_gat_agg_fwd for H heads: the same lanes, kNb edge batches and online softmax, with H softmax states and
+// z[i,h,:] = sum_j alpha_ij^h x_j over row i (its diagonal entry dropped) plus the self loop; x rows fp16, bf16 or fp32,
+// 4 columns per lane, online softmax (every lane of a row's group walks the same edges) with H softmax states and
 // accumulators; per edge one load of the H logits and one of the row chunk, shared by the heads
 template <typename Tin, int H>
 __global__ __launch_bounds__(kAggNT) void k_gat_mh_agg_fwd(const int64_t* __restrict__ rowptr,
@@ -1463,6 +1176,9 @@ __global__ __launch_bounds__(kAggNT) void k_gat_mh_agg_fwd(const int64_t* __rest
       mm[h] = self[h];
       ss[h] = 1.f;
     }
+    // kNb neighbours per round: their ids, then their logits and rows, each issued back to back (clamped
+    // indices, no predicated load); the online softmax then runs over registers.  One neighbour at a time
+    // was two dependent round trips per edge.
     constexpr int kNb = 4;
     const int64_t cc = has ? c : 0;
     for (int64_t k0 = b; k0 < e; k0 += kNb) {
@@ -1509,9 +1225,17 @@ __global__ __launch_bounds__(kAggNT) void k_gat_mh_agg_fwd(const int64_t* __rest
   }
 }
 
-// k_gat_agg_bwd for H heads: per head  go^h = g_i^h . z_i^h,  gh^h = g_i^h . x_j,  ge^h = alpha^h (gh^h - go^h) lrelu';
-// grad_a_src[j,h] += ge^h, grad_a_dst[i,h] = sum_j ge^h, and (grad_x != NULL) grad_x[j,:] += sum_h alpha_ij^h g_i^h:
-// the heads are summed first, so there is ONE fp32 atomic per column per edge whatever H is
+// One wavefront per target i (lpt = min(64, K rounded up to a power of two) lanes; K/4 for kVec).  Per head
+// go^h = g_i^h . z_i^h,  gh^h = g_i^h . x_j,  ge^h = alpha_ij^h (gh^h - go^h) lrelu'(raw);  grad_a_src[j,h] += ge^h,
+// grad_a_dst[i,h] = sum_j ge^h, and grad_x[j,:] += sum_h alpha_ij^h g_i^h  (only when grad_x != NULL: the first layer's
+// input needs no gradient, which saves E x K atomics): the heads are summed first, so there is ONE fp32 atomic per
+// column per edge whatever H is.
+// kVec: 4 columns per lane (no input gradient wanted: only dot products, 8/16-byte loads);
+// otherwise one column per lane and step, c = lane + lpt * i: consecutive lanes touch consecutive columns, so a group's
+// loads and -- what matters -- its fp32 atomics are contiguous 4 * lpt-byte segments (the atomic units run at full
+// rate on contiguous 256-byte wave instructions and ~17x slower on scattered ones).
+// alpha_e / alpha_self (optional): the attention weights of every CSR entry (0 for a dropped diagonal entry) and of
+// every target's self loop -- what the input gradient by GATHER over the transposed hop needs (k_gat_mh_gx_gather).
 template <typename Tin, int H, bool kVec>
 __global__ __launch_bounds__(kAggNT) void k_gat_mh_agg_bwd(
     const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col, int64_t T, const Tin* __restrict__ x,
@@ -1556,7 +1280,8 @@ __global__ __launch_bounds__(kAggNT) void k_gat_mh_agg_bwd(
     }
     go[h] = group_sum(go[h]);
   }
-  // every group runs to the longest row of its wavefront so that the shuffles stay convergent
+  // the targets sharing a wavefront have different degrees: every group runs to the longest row of its
+  // wavefront so that the shuffles stay convergent
   int64_t n = live ? e - b + 1 : 0;
   for (int d = lpt; d < kWave; d <<= 1) {
     const int64_t o = __shfl_xor((long long)n, d, kWave);
@@ -1575,12 +1300,7 @@ __global__ __launch_bounds__(kAggNT) void k_gat_mh_agg_bwd(
     for (int h = 0; h < H; ++h) gh[h] = a[h] = raw[h] = 0.f;
     if (use) {
       load_heads<H>(a_src + j * H, raw);
-#pragma unroll
-      for (int h = 0; h < H; ++h) {
-        raw[h] += ad[h];
-        a[h] = __expf(lrelu(raw[h], slope) - m[h]) * inv_s[h];
-      }
-      if (kVec) {
+      if (kVec) {  // before the logits are used: their load and the rows' are in flight together
         for (int64_t c = (int64_t)lane * 4; c < K; c += (int64_t)lpt * 4) {
           const f4 xv = load4(x + j * x_stride + c);
 #pragma unroll
@@ -1589,7 +1309,13 @@ __global__ __launch_bounds__(kAggNT) void k_gat_mh_agg_bwd(
             gh[h] += gv.x * xv.x + gv.y * xv.y + gv.z * xv.z + gv.w * xv.w;
           }
         }
-      } else {
+      }
+#pragma unroll
+      for (int h = 0; h < H; ++h) {
+        raw[h] += ad[h];
+        a[h] = __expf(lrelu(raw[h], slope) - m[h]) * inv_s[h];
+      }
+      if (!kVec) {
         for (int64_t c = lane; c < K; c += lpt) {
           const float xv = load1(x + j * x_stride + c);
           float gx = 0.f;
@@ -1618,8 +1344,10 @@ __global__ __launch_bounds__(kAggNT) void k_gat_mh_agg_bwd(
   if (live && lane == 0) store_heads<H>(grad_a_dst + t * H, gad);
 }
 
-// k_gat_gx_gather for H heads:  grad_x[s,:] = sum over the targets t of s: sum_h alpha_ts^h grad_z[t,h,:]
+// Input gradient of the layer by GATHER (no fp32 atomics, no zero fill, no separate rank-1 passes):
+//   grad_x[s,:] = sum over the targets t of s: sum_h alpha_ts^h grad_z[t,h,:]
 //   (+ the self loop's sum_h alpha_ss^h grad_z[s,h,:], s < T) + sum_h grad_a_src[s,h] v_src^h (+ grad_a_dst[s,h] v_dst^h, s < T)
+//   -- a_src = x V_src^T, a_dst = x[:T] V_dst^T.  Every term is added to the accumulator on its own, in this order.
 template <int H>
 __global__ __launch_bounds__(kAggNT) void k_gat_mh_gx_gather(
     const int32_t* __restrict__ start, const int32_t* __restrict__ ttgt, const int32_t* __restrict__ tedge,
@@ -1681,181 +1409,6 @@ __global__ __launch_bounds__(kAggNT) void k_gat_mh_gx_gather(
 
 }  // namespace spp
 
-// x_elem: the element code of x's rows (0 fp32, 1 fp16, 2 bf16); the softmax statistics, z and all gradients stay fp32
-static spp_status gat_check(int64_t K, const void* x, int64_t x_stride, int32_t x_elem, const char* who) {
-  SPP_REQUIRE(elem_ok(x_elem), "%s: unknown element code %d", who, (int)x_elem);
-  const int64_t esz = elem_bytes(x_elem);
-  SPP_REQUIRE(K > 0 && K % 4 == 0 && K / 4 <= spp::kAggNT && x_stride >= K && (x_stride * esz) % (4 * esz) == 0 &&
-                  reinterpret_cast<uintptr_t>(x) % (4 * esz) == 0,
-              "%s: needs K %% 4 == 0, K <= %d and rows aligned to 4 elements", who, 4 * spp::kAggNT);
-  return SPP_OK;
-}
-
-extern "C" spp_status spp_gat_logits(const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t num_sources,
-                                     int64_t num_targets, int64_t K, const float* v_src_dev, const float* v_dst_dev,
-                                     float* a_src_dev, float* a_dst_dev, void* stream) {
-  SPP_REQUIRE(num_sources >= num_targets && num_targets >= 0, "spp_gat_logits: bad sizes");
-  if (num_sources == 0) return SPP_OK;
-  SPP_TRY(gat_check(K, x_dev, x_stride_elems, x_elem, "spp_gat_logits"));
-  SPP_REQUIRE(v_src_dev && v_dst_dev && a_src_dev && (a_dst_dev || num_targets == 0) &&
-                  reinterpret_cast<uintptr_t>(v_src_dev) % 16 == 0 && reinterpret_cast<uintptr_t>(v_dst_dev) % 16 == 0,
-              "spp_gat_logits: NULL or unaligned buffer");
-  const int lpr_log2 = lanes_log2(K / 4);
-  const unsigned grid = (unsigned)ceil_div(ceil_div(num_sources, kDotRows) << lpr_log2, kAggNT);
-  with_elem(x_elem, [&](auto tin) {
-    using Tin = typename decltype(tin)::type;
-    hipLaunchKernelGGL(k_rowdot2<Tin>, dim3(grid), dim3(kAggNT), 0, as_stream(stream), static_cast<const Tin*>(x_dev),
-                       x_stride_elems, num_sources, num_targets, K, v_src_dev, v_dst_dev, lpr_log2, a_src_dev, a_dst_dev);
-  });
-  SPP_HIP_TRY(hipGetLastError());
-  return SPP_OK;
-}
-
-extern "C" spp_status spp_gat_logits_backward(const void* x_dev, int32_t x_elem, int64_t x_stride_elems,
-                                              int64_t num_sources, int64_t num_targets, int64_t K,
-                                              const float* grad_a_src_dev, const float* grad_a_dst_dev,
-                                              float* grad_v_src_dev, float* grad_v_dst_dev, void* stream) {
-  SPP_REQUIRE(num_sources >= num_targets && num_targets >= 0, "spp_gat_logits_backward: bad sizes");
-  SPP_TRY(gat_check(K, x_dev, x_stride_elems, x_elem, "spp_gat_logits_backward"));
-  SPP_REQUIRE(grad_v_src_dev && grad_v_dst_dev, "spp_gat_logits_backward: NULL output");
-  hipStream_t st = as_stream(stream);
-  SPP_HIP_TRY(hipMemsetAsync(grad_v_src_dev, 0, sizeof(float) * (size_t)K, st));
-  SPP_HIP_TRY(hipMemsetAsync(grad_v_dst_dev, 0, sizeof(float) * (size_t)K, st));
-  if (num_sources == 0) return SPP_OK;
-  SPP_REQUIRE(grad_a_src_dev && (grad_a_dst_dev || num_targets == 0), "spp_gat_logits_backward: NULL input");
-  // 4 rows in flight per lane; K atomics onto the same K addresses per workgroup: about one workgroup per CU,
-  // between 1024 and 4096 rows each
-  const int64_t rows_per_wg = std::max<int64_t>(1024, std::min<int64_t>(4096, ceil_div(num_sources, 256)));
-  const unsigned grid = (unsigned)ceil_div(num_sources, rows_per_wg);
-  with_elem(x_elem, [&](auto tin) {
-    using Tin = typename decltype(tin)::type;
-    hipLaunchKernelGGL(k_colsum2<Tin>, dim3(grid), dim3(kColsumNT), 0, st, static_cast<const Tin*>(x_dev), x_stride_elems,
-                       num_sources, num_targets, K, grad_a_src_dev, grad_a_dst_dev, rows_per_wg, grad_v_src_dev,
-                       grad_v_dst_dev);
-  });
-  SPP_HIP_TRY(hipGetLastError());
-  return SPP_OK;
-}
-
-extern "C" spp_status spp_gat_aggregate_forward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
-                                                const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t K,
-                                                const float* a_src_dev, const float* a_dst_dev, float negative_slope,
-                                                float* z_dev, float* row_max_dev, float* row_sum_dev, void* stream) {
-  SPP_REQUIRE(num_targets >= 0, "spp_gat_aggregate_forward: negative size");
-  if (num_targets == 0) return SPP_OK;
-  SPP_TRY(gat_check(K, x_dev, x_stride_elems, x_elem, "spp_gat_aggregate_forward"));
-  SPP_REQUIRE(rowptr_dev && a_src_dev && a_dst_dev && z_dev && row_max_dev && row_sum_dev &&
-                  reinterpret_cast<uintptr_t>(z_dev) % 16 == 0, "spp_gat_aggregate_forward: NULL or unaligned buffer");
-  const int lpr_log2 = lanes_log2(K / 4);
-  const unsigned grid = (unsigned)ceil_div(num_targets << lpr_log2, kAggNT);
-  with_elem(x_elem, [&](auto tin) {
-    using Tin = typename decltype(tin)::type;
-    hipLaunchKernelGGL(k_gat_agg_fwd<Tin>, dim3(grid), dim3(kAggNT), 0, as_stream(stream), rowptr_dev, col_dev,
-                       num_targets, static_cast<const Tin*>(x_dev), x_stride_elems, K, a_src_dev, a_dst_dev,
-                       negative_slope, lpr_log2, z_dev, row_max_dev, row_sum_dev);
-  });
-  SPP_HIP_TRY(hipGetLastError());
-  return SPP_OK;
-}
-
-static spp_status gat_aggregate_backward_launch(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
-                                                const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t K,
-                                                const float* a_src_dev, const float* a_dst_dev, float negative_slope,
-                                                const float* z_dev, const float* row_max_dev, const float* row_sum_dev,
-                                                const float* grad_z_dev, float* grad_x_dev, float* grad_a_src_dev,
-                                                float* grad_a_dst_dev, float* alpha_e, float* alpha_self, void* stream);
-
-extern "C" spp_status spp_gat_aggregate_backward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
-                                                 const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t K,
-                                                 const float* a_src_dev, const float* a_dst_dev, float negative_slope,
-                                                 const float* z_dev, const float* row_max_dev, const float* row_sum_dev,
-                                                 const float* grad_z_dev, float* grad_x_dev /* NULL: not wanted */,
-                                                 float* grad_a_src_dev, float* grad_a_dst_dev, void* stream) {
-  SPP_REQUIRE(num_targets >= 0, "spp_gat_aggregate_backward: negative size");
-  if (num_targets == 0) return SPP_OK;
-  SPP_TRY(gat_check(K, x_dev, x_stride_elems, x_elem, "spp_gat_aggregate_backward"));
-  SPP_REQUIRE(rowptr_dev && a_src_dev && a_dst_dev && z_dev && row_max_dev && row_sum_dev && grad_z_dev &&
-                  grad_a_src_dev && grad_a_dst_dev && reinterpret_cast<uintptr_t>(grad_z_dev) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(z_dev) % 16 == 0, "spp_gat_aggregate_backward: NULL or unaligned buffer");
-  return gat_aggregate_backward_launch(rowptr_dev, col_dev, num_targets, x_dev, x_elem, x_stride_elems, K, a_src_dev,
-                                       a_dst_dev, negative_slope, z_dev, row_max_dev, row_sum_dev, grad_z_dev, grad_x_dev,
-                                       grad_a_src_dev, grad_a_dst_dev, nullptr, nullptr, stream);
-}
-
-static spp_status gat_aggregate_backward_launch(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
-                                                const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t K,
-                                                const float* a_src_dev, const float* a_dst_dev, float negative_slope,
-                                                const float* z_dev, const float* row_max_dev, const float* row_sum_dev,
-                                                const float* grad_z_dev, float* grad_x_dev, float* grad_a_src_dev,
-                                                float* grad_a_dst_dev, float* alpha_e, float* alpha_self, void* stream) {
-  const bool vec = grad_x_dev == nullptr;
-  const int lpt_log2 = lanes_log2(vec ? K / 4 : K);
-  const unsigned grid = (unsigned)ceil_div(num_targets << lpt_log2, kAggNT);
-  with_elem_vec(x_elem, vec, [&](auto tin, auto v) {
-    using Tin = typename decltype(tin)::type;
-    hipLaunchKernelGGL((k_gat_agg_bwd<Tin, decltype(v)::value>), dim3(grid), dim3(kAggNT), 0, as_stream(stream), rowptr_dev,
-                       col_dev, num_targets, static_cast<const Tin*>(x_dev), x_stride_elems, K, a_src_dev, a_dst_dev,
-                       negative_slope, z_dev, row_max_dev, row_sum_dev, grad_z_dev, lpt_log2, grad_x_dev, grad_a_src_dev,
-                       grad_a_dst_dev, alpha_e, alpha_self);
-  });
-  SPP_HIP_TRY(hipGetLastError());
-  return SPP_OK;
-}
-
-extern "C" int64_t spp_gat_aggregate_backward_gather_workspace_bytes(int64_t num_targets, int64_t num_sources,
-                                                                     int64_t num_edges) {
-  // alpha_e [E] | alpha_self [T] | the transposed hop with edge ids   (each 16-byte aligned)
-  return align16(4 * num_edges) + align16(4 * num_targets) + transpose_hop_bytes(num_targets, num_sources, num_edges, true);
-}
-
-// spp_gat_aggregate_backward with the input gradient by GATHER over the transposed hop: grad_x [S, K] is written
-// completely, including the rank-1 terms of the logits (grad_a_src[s] v_src, grad_a_dst[s] v_dst for s < T) that
-// the atomic form leaves to the caller.  grad_a_src_dev [S] is zeroed by the caller as before.
-extern "C" spp_status spp_gat_aggregate_backward_gather(const int64_t* rowptr_dev, const int64_t* col_dev,
-                                                        int64_t num_targets, int64_t num_sources, int64_t num_edges,
-                                                        const void* x_dev, int32_t x_elem, int64_t x_stride_elems,
-                                                        int64_t K, const float* a_src_dev, const float* a_dst_dev,
-                                                        float negative_slope, const float* z_dev,
-                                                        const float* row_max_dev, const float* row_sum_dev,
-                                                        const float* grad_z_dev, const float* v_src_dev,
-                                                        const float* v_dst_dev, float* grad_x_dev, float* grad_a_src_dev,
-                                                        float* grad_a_dst_dev, void* workspace_dev, int64_t workspace_bytes,
-                                                        void* stream) {
-  SPP_REQUIRE(num_targets >= 0 && num_sources >= num_targets && num_edges >= 0,
-              "spp_gat_aggregate_backward_gather: bad sizes");
-  if (num_sources == 0) return SPP_OK;
-  SPP_TRY(gat_check(K, x_dev, x_stride_elems, x_elem, "spp_gat_aggregate_backward_gather"));
-  SPP_REQUIRE(num_sources < (1ll << 31) && num_edges < (1ll << 31), "spp_gat_aggregate_backward_gather: 32-bit indices");
-  SPP_REQUIRE(rowptr_dev && a_src_dev && a_dst_dev && z_dev && row_max_dev && row_sum_dev && grad_z_dev && v_src_dev &&
-                  v_dst_dev && grad_x_dev && grad_a_src_dev && grad_a_dst_dev && workspace_dev,
-              "spp_gat_aggregate_backward_gather: NULL buffer");
-  SPP_REQUIRE(reinterpret_cast<uintptr_t>(grad_z_dev) % 16 == 0 && reinterpret_cast<uintptr_t>(z_dev) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(grad_x_dev) % 16 == 0 && reinterpret_cast<uintptr_t>(v_src_dev) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(v_dst_dev) % 16 == 0 && reinterpret_cast<uintptr_t>(workspace_dev) % 16 == 0,
-              "spp_gat_aggregate_backward_gather: buffers must be 16-byte aligned");
-  SPP_REQUIRE(workspace_bytes >= spp_gat_aggregate_backward_gather_workspace_bytes(num_targets, num_sources, num_edges),
-              "spp_gat_aggregate_backward_gather: workspace too small");
-  hipStream_t st = as_stream(stream);
-  float* alpha_e = static_cast<float*>(workspace_dev);
-  float* alpha_self = alpha_e + align16(4 * num_edges) / 4;
-  const int64_t alpha_bytes = align16(4 * num_edges) + align16(4 * num_targets);
-  // the attention weights of every entry + grad_a_src / grad_a_dst (no input gradient by atomics)
-  if (num_targets > 0)
-    SPP_TRY(gat_aggregate_backward_launch(rowptr_dev, col_dev, num_targets, x_dev, x_elem, x_stride_elems, K, a_src_dev,
-                                          a_dst_dev, negative_slope, z_dev, row_max_dev, row_sum_dev, grad_z_dev, nullptr,
-                                          grad_a_src_dev, grad_a_dst_dev, alpha_e, alpha_self, stream));
-  TransposedHop hop;
-  SPP_TRY(transpose_hop(rowptr_dev, col_dev, num_targets, num_sources, num_edges, true,
-                        static_cast<char*>(workspace_dev) + alpha_bytes, workspace_bytes - alpha_bytes, st, &hop));
-  const int lpr_log2 = lanes_log2(K / 4);
-  const unsigned grid = (unsigned)ceil_div(num_sources << lpr_log2, kAggNT);
-  hipLaunchKernelGGL(k_gat_gx_gather, dim3(grid), dim3(kAggNT), 0, st, hop.start, hop.tcol, hop.tedge, alpha_e, alpha_self,
-                     num_targets, num_sources, grad_z_dev, K, lpr_log2, grad_a_src_dev, grad_a_dst_dev, v_src_dev,
-                     v_dst_dev, grad_x_dev);
-  SPP_HIP_TRY(hipGetLastError());
-  return SPP_OK;
-}
-
 extern "C" spp_status spp_gat_forward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
                                       const float* h_dev, int64_t F, const float* a_src_dev, const float* a_dst_dev,
                                       float negative_slope, float* out_dev, float* row_max_dev, float* row_sum_dev,
@@ -1890,8 +1443,9 @@ extern "C" spp_status spp_gat_backward(const int64_t* rowptr_dev, const int64_t*
   return SPP_OK;
 }
 
-// ---- multi-head GAT entries (include/spp.h: spp_gat_mh_*) ----
-// fn(std::integral_constant<int, H>{}) for heads = H in {1, 2, 4, 8} (checked by mh_check)
+// ---- the aggregate-then-project GAT entries (include/spp.h: spp_gat_mh_* and, as their heads = 1 spelling, the
+// spp_gat_logits / spp_gat_aggregate_* entries that predate the head count) ----
+// fn(std::integral_constant<int, H>{}) for heads = H in {1, 2, 4, 8} (checked by gat_check)
 template <class Fn>
 static void with_heads(int32_t heads, Fn&& fn) {
   switch (heads) {
@@ -1901,24 +1455,33 @@ static void with_heads(int32_t heads, Fn&& fn) {
     default: fn(std::integral_constant<int, 8>{}); break;
   }
 }
-// the checks of gat_check plus the head count; every entry runs them before anything else
-static spp_status mh_check(int32_t heads, int64_t K, const void* x, int64_t x_stride, int32_t x_elem, const char* who) {
+// The head count, and x: x_elem is the element code of its rows (0 fp32, 1 fp16, 2 bf16); the softmax statistics, z and
+// all gradients stay fp32.  Every entry runs these checks before anything else.
+static spp_status gat_check(int32_t heads, int64_t K, const void* x, int64_t x_stride, int32_t x_elem, const char* who) {
   SPP_REQUIRE(heads == 1 || heads == 2 || heads == 4 || heads == 8, "%s: heads must be 1, 2, 4 or 8 (got %d)", who,
               (int)heads);
-  return gat_check(K, x, x_stride, x_elem, who);
+  SPP_REQUIRE(elem_ok(x_elem), "%s: unknown element code %d", who, (int)x_elem);
+  const int64_t esz = elem_bytes(x_elem);
+  SPP_REQUIRE(K > 0 && K % 4 == 0 && K / 4 <= spp::kAggNT && x_stride >= K && (x_stride * esz) % (4 * esz) == 0 &&
+                  reinterpret_cast<uintptr_t>(x) % (4 * esz) == 0,
+              "%s: needs K %% 4 == 0, K <= %d and rows aligned to 4 elements", who, 4 * spp::kAggNT);
+  return SPP_OK;
 }
-// the per-head arrays are read and written H floats at a time (16-byte loads at H = 4, 8)
 static bool al16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+// the per-head arrays are read and written H floats at a time (load_heads): 4, 8 and 16-byte accesses at H = 1, 2, >= 4
+static bool al_heads(const void* p, int32_t heads) {
+  return reinterpret_cast<uintptr_t>(p) % (4 * std::min<int32_t>(heads, 4)) == 0;
+}
 
-extern "C" spp_status spp_gat_mh_logits(const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t num_sources,
-                                        int64_t num_targets, int64_t K, int32_t heads, const float* v_src_dev,
-                                        const float* v_dst_dev, float* a_src_dev, float* a_dst_dev, void* stream) {
-  SPP_TRY(mh_check(heads, K, x_dev, x_stride_elems, x_elem, "spp_gat_mh_logits"));
-  SPP_REQUIRE(num_sources >= num_targets && num_targets >= 0, "spp_gat_mh_logits: bad sizes");
+static spp_status gat_logits(const char* who, const void* x_dev, int32_t x_elem, int64_t x_stride_elems,
+                             int64_t num_sources, int64_t num_targets, int64_t K, int32_t heads, const float* v_src_dev,
+                             const float* v_dst_dev, float* a_src_dev, float* a_dst_dev, void* stream) {
+  SPP_TRY(gat_check(heads, K, x_dev, x_stride_elems, x_elem, who));
+  SPP_REQUIRE(num_sources >= num_targets && num_targets >= 0, "%s: bad sizes", who);
   if (num_sources == 0) return SPP_OK;
   SPP_REQUIRE(x_dev && v_src_dev && v_dst_dev && a_src_dev && (a_dst_dev || num_targets == 0) && al16(v_src_dev) &&
-                  al16(v_dst_dev) && al16(a_src_dev) && al16(a_dst_dev),
-              "spp_gat_mh_logits: NULL or unaligned buffer");
+                  al16(v_dst_dev) && al_heads(a_src_dev, heads) && al_heads(a_dst_dev, heads),
+              "%s: NULL or unaligned buffer", who);
   const int lpr_log2 = lanes_log2(K / 4);
   with_elem(x_elem, [&](auto tin) {
     with_heads(heads, [&](auto hh) {
@@ -1934,20 +1497,22 @@ extern "C" spp_status spp_gat_mh_logits(const void* x_dev, int32_t x_elem, int64
   return SPP_OK;
 }
 
-extern "C" spp_status spp_gat_mh_logits_backward(const void* x_dev, int32_t x_elem, int64_t x_stride_elems,
-                                                 int64_t num_sources, int64_t num_targets, int64_t K, int32_t heads,
-                                                 const float* grad_a_src_dev, const float* grad_a_dst_dev,
-                                                 float* grad_v_src_dev, float* grad_v_dst_dev, void* stream) {
-  SPP_TRY(mh_check(heads, K, x_dev, x_stride_elems, x_elem, "spp_gat_mh_logits_backward"));
-  SPP_REQUIRE(num_sources >= num_targets && num_targets >= 0, "spp_gat_mh_logits_backward: bad sizes");
-  SPP_REQUIRE(grad_v_src_dev && grad_v_dst_dev, "spp_gat_mh_logits_backward: NULL output");
+static spp_status gat_logits_backward(const char* who, const void* x_dev, int32_t x_elem, int64_t x_stride_elems,
+                                      int64_t num_sources, int64_t num_targets, int64_t K, int32_t heads,
+                                      const float* grad_a_src_dev, const float* grad_a_dst_dev, float* grad_v_src_dev,
+                                      float* grad_v_dst_dev, void* stream) {
+  SPP_TRY(gat_check(heads, K, x_dev, x_stride_elems, x_elem, who));
+  SPP_REQUIRE(num_sources >= num_targets && num_targets >= 0, "%s: bad sizes", who);
+  SPP_REQUIRE(grad_v_src_dev && grad_v_dst_dev, "%s: NULL output", who);
   SPP_REQUIRE(num_sources == 0 || (x_dev && grad_a_src_dev && (grad_a_dst_dev || num_targets == 0) &&
-                                   al16(grad_a_src_dev) && al16(grad_a_dst_dev)),
-              "spp_gat_mh_logits_backward: NULL or unaligned input");
+                                   al_heads(grad_a_src_dev, heads) && al_heads(grad_a_dst_dev, heads)),
+              "%s: NULL or unaligned input", who);
   hipStream_t st = as_stream(stream);
   SPP_HIP_TRY(hipMemsetAsync(grad_v_src_dev, 0, sizeof(float) * (size_t)(heads * K), st));
   SPP_HIP_TRY(hipMemsetAsync(grad_v_dst_dev, 0, sizeof(float) * (size_t)(heads * K), st));
   if (num_sources == 0) return SPP_OK;
+  // every workgroup ends in atomics onto the SAME 2 H K addresses: about one workgroup per CU, between 1024 and 4096
+  // rows each
   const int64_t rows_per_wg = std::max<int64_t>(1024, std::min<int64_t>(4096, ceil_div(num_sources, 256)));
   const unsigned grid = (unsigned)ceil_div(num_sources, rows_per_wg);
   with_elem(x_elem, [&](auto tin) {
@@ -1962,17 +1527,18 @@ extern "C" spp_status spp_gat_mh_logits_backward(const void* x_dev, int32_t x_el
   return SPP_OK;
 }
 
-extern "C" spp_status spp_gat_mh_aggregate_forward(const int64_t* rowptr_dev, const int64_t* col_dev,
-                                                   int64_t num_targets, const void* x_dev, int32_t x_elem,
-                                                   int64_t x_stride_elems, int64_t K, int32_t heads,
-                                                   const float* a_src_dev, const float* a_dst_dev, float negative_slope,
-                                                   float* z_dev, float* row_max_dev, float* row_sum_dev, void* stream) {
-  SPP_TRY(mh_check(heads, K, x_dev, x_stride_elems, x_elem, "spp_gat_mh_aggregate_forward"));
-  SPP_REQUIRE(num_targets >= 0, "spp_gat_mh_aggregate_forward: negative size");
+static spp_status gat_aggregate_forward(const char* who, const int64_t* rowptr_dev, const int64_t* col_dev,
+                                        int64_t num_targets, const void* x_dev, int32_t x_elem, int64_t x_stride_elems,
+                                        int64_t K, int32_t heads, const float* a_src_dev, const float* a_dst_dev,
+                                        float negative_slope, float* z_dev, float* row_max_dev, float* row_sum_dev,
+                                        void* stream) {
+  SPP_TRY(gat_check(heads, K, x_dev, x_stride_elems, x_elem, who));
+  SPP_REQUIRE(num_targets >= 0, "%s: negative size", who);
   if (num_targets == 0) return SPP_OK;
   SPP_REQUIRE(rowptr_dev && x_dev && a_src_dev && a_dst_dev && z_dev && row_max_dev && row_sum_dev && al16(z_dev) &&
-                  al16(a_src_dev) && al16(a_dst_dev) && al16(row_max_dev) && al16(row_sum_dev),
-              "spp_gat_mh_aggregate_forward: NULL or unaligned buffer");
+                  al_heads(a_src_dev, heads) && al_heads(a_dst_dev, heads) && al_heads(row_max_dev, heads) &&
+                  al_heads(row_sum_dev, heads),
+              "%s: NULL or unaligned buffer", who);
   const int lpr_log2 = lanes_log2(K / 4);
   const unsigned grid = (unsigned)ceil_div(num_targets << lpr_log2, kAggNT);
   with_elem(x_elem, [&](auto tin) {
@@ -1988,13 +1554,13 @@ extern "C" spp_status spp_gat_mh_aggregate_forward(const int64_t* rowptr_dev, co
 }
 
 // the launch of k_gat_mh_agg_bwd (arguments checked by the caller); grad_x_dev == NULL: the vector form
-static spp_status gat_mh_backward_launch(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
-                                         const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t K,
-                                         int32_t heads, const float* a_src_dev, const float* a_dst_dev,
-                                         float negative_slope, const float* z_dev, const float* row_max_dev,
-                                         const float* row_sum_dev, const float* grad_z_dev, float* grad_x_dev,
-                                         float* grad_a_src_dev, float* grad_a_dst_dev, float* alpha_e,
-                                         float* alpha_self, void* stream) {
+static spp_status gat_backward_launch(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                                      const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t K,
+                                      int32_t heads, const float* a_src_dev, const float* a_dst_dev,
+                                      float negative_slope, const float* z_dev, const float* row_max_dev,
+                                      const float* row_sum_dev, const float* grad_z_dev, float* grad_x_dev,
+                                      float* grad_a_src_dev, float* grad_a_dst_dev, float* alpha_e, float* alpha_self,
+                                      void* stream) {
   const bool vec = grad_x_dev == nullptr;
   const int lpt_log2 = lanes_log2(vec ? K / 4 : K);
   const unsigned grid = (unsigned)ceil_div(num_targets << lpt_log2, kAggNT);
@@ -2011,32 +1577,32 @@ static spp_status gat_mh_backward_launch(const int64_t* rowptr_dev, const int64_
   return SPP_OK;
 }
 
-static bool gat_mh_backward_bufs_ok(const int64_t* rowptr_dev, const void* x_dev, const float* a_src_dev,
-                                    const float* a_dst_dev, const float* z_dev, const float* row_max_dev,
-                                    const float* row_sum_dev, const float* grad_z_dev, const float* grad_a_src_dev,
-                                    const float* grad_a_dst_dev) {
+static bool gat_backward_bufs_ok(int32_t heads, const int64_t* rowptr_dev, const void* x_dev, const float* a_src_dev,
+                                 const float* a_dst_dev, const float* z_dev, const float* row_max_dev,
+                                 const float* row_sum_dev, const float* grad_z_dev, const float* grad_a_src_dev,
+                                 const float* grad_a_dst_dev) {
   return rowptr_dev && x_dev && a_src_dev && a_dst_dev && z_dev && row_max_dev && row_sum_dev && grad_z_dev &&
-         grad_a_src_dev && grad_a_dst_dev && al16(a_src_dev) && al16(a_dst_dev) && al16(z_dev) && al16(row_max_dev) &&
-         al16(row_sum_dev) && al16(grad_z_dev) && al16(grad_a_src_dev) && al16(grad_a_dst_dev);
+         grad_a_src_dev && grad_a_dst_dev && al16(z_dev) && al16(grad_z_dev) && al_heads(a_src_dev, heads) &&
+         al_heads(a_dst_dev, heads) && al_heads(row_max_dev, heads) && al_heads(row_sum_dev, heads) &&
+         al_heads(grad_a_src_dev, heads) && al_heads(grad_a_dst_dev, heads);
 }
 
-extern "C" spp_status spp_gat_mh_aggregate_backward(const int64_t* rowptr_dev, const int64_t* col_dev,
-                                                    int64_t num_targets, const void* x_dev, int32_t x_elem,
-                                                    int64_t x_stride_elems, int64_t K, int32_t heads,
-                                                    const float* a_src_dev, const float* a_dst_dev,
-                                                    float negative_slope, const float* z_dev, const float* row_max_dev,
-                                                    const float* row_sum_dev, const float* grad_z_dev,
-                                                    float* grad_x_dev /* NULL: not wanted */, float* grad_a_src_dev,
-                                                    float* grad_a_dst_dev, void* stream) {
-  SPP_TRY(mh_check(heads, K, x_dev, x_stride_elems, x_elem, "spp_gat_mh_aggregate_backward"));
-  SPP_REQUIRE(num_targets >= 0, "spp_gat_mh_aggregate_backward: negative size");
+static spp_status gat_aggregate_backward(const char* who, const int64_t* rowptr_dev, const int64_t* col_dev,
+                                         int64_t num_targets, const void* x_dev, int32_t x_elem, int64_t x_stride_elems,
+                                         int64_t K, int32_t heads, const float* a_src_dev, const float* a_dst_dev,
+                                         float negative_slope, const float* z_dev, const float* row_max_dev,
+                                         const float* row_sum_dev, const float* grad_z_dev,
+                                         float* grad_x_dev /* NULL: not wanted */, float* grad_a_src_dev,
+                                         float* grad_a_dst_dev, void* stream) {
+  SPP_TRY(gat_check(heads, K, x_dev, x_stride_elems, x_elem, who));
+  SPP_REQUIRE(num_targets >= 0, "%s: negative size", who);
   if (num_targets == 0) return SPP_OK;
-  SPP_REQUIRE(gat_mh_backward_bufs_ok(rowptr_dev, x_dev, a_src_dev, a_dst_dev, z_dev, row_max_dev, row_sum_dev,
-                                      grad_z_dev, grad_a_src_dev, grad_a_dst_dev),
-              "spp_gat_mh_aggregate_backward: NULL or unaligned buffer");
-  return gat_mh_backward_launch(rowptr_dev, col_dev, num_targets, x_dev, x_elem, x_stride_elems, K, heads, a_src_dev,
-                                a_dst_dev, negative_slope, z_dev, row_max_dev, row_sum_dev, grad_z_dev, grad_x_dev,
-                                grad_a_src_dev, grad_a_dst_dev, nullptr, nullptr, stream);
+  SPP_REQUIRE(gat_backward_bufs_ok(heads, rowptr_dev, x_dev, a_src_dev, a_dst_dev, z_dev, row_max_dev, row_sum_dev,
+                                   grad_z_dev, grad_a_src_dev, grad_a_dst_dev),
+              "%s: NULL or unaligned buffer", who);
+  return gat_backward_launch(rowptr_dev, col_dev, num_targets, x_dev, x_elem, x_stride_elems, K, heads, a_src_dev,
+                             a_dst_dev, negative_slope, z_dev, row_max_dev, row_sum_dev, grad_z_dev, grad_x_dev,
+                             grad_a_src_dev, grad_a_dst_dev, nullptr, nullptr, stream);
 }
 
 extern "C" int64_t spp_gat_mh_aggregate_backward_gather_workspace_bytes(int64_t num_targets, int64_t num_sources,
@@ -2047,24 +1613,27 @@ extern "C" int64_t spp_gat_mh_aggregate_backward_gather_workspace_bytes(int64_t 
          transpose_hop_bytes(num_targets, num_sources, num_edges, true);
 }
 
-extern "C" spp_status spp_gat_mh_aggregate_backward_gather(
-    const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets, int64_t num_sources, int64_t num_edges,
-    const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t K, int32_t heads, const float* a_src_dev,
-    const float* a_dst_dev, float negative_slope, const float* z_dev, const float* row_max_dev,
+// gat_aggregate_backward with the input gradient by GATHER over the transposed hop: grad_x [S, K] is written
+// completely, including the rank-1 terms of the logits (grad_a_src[s,h] v_src^h, grad_a_dst[s,h] v_dst^h for s < T)
+// that the atomic form leaves to the caller.  grad_a_src_dev [S, H] is zeroed by the caller as before.
+static spp_status gat_aggregate_backward_gather(
+    const char* who, const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets, int64_t num_sources,
+    int64_t num_edges, const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t K, int32_t heads,
+    const float* a_src_dev, const float* a_dst_dev, float negative_slope, const float* z_dev, const float* row_max_dev,
     const float* row_sum_dev, const float* grad_z_dev, const float* v_src_dev, const float* v_dst_dev,
     float* grad_x_dev, float* grad_a_src_dev, float* grad_a_dst_dev, void* workspace_dev, int64_t workspace_bytes,
     void* stream) {
-  const char* who = "spp_gat_mh_aggregate_backward_gather";
-  SPP_TRY(mh_check(heads, K, x_dev, x_stride_elems, x_elem, who));
+  SPP_TRY(gat_check(heads, K, x_dev, x_stride_elems, x_elem, who));
   SPP_REQUIRE(num_targets >= 0 && num_sources >= num_targets && num_edges >= 0, "%s: bad sizes", who);
   if (num_sources == 0) return SPP_OK;
   SPP_REQUIRE(num_sources < (1ll << 31) && num_edges < (1ll << 31), "%s: 32-bit indices", who);
-  SPP_REQUIRE(num_targets == 0 || gat_mh_backward_bufs_ok(rowptr_dev, x_dev, a_src_dev, a_dst_dev, z_dev, row_max_dev,
-                                                          row_sum_dev, grad_z_dev, grad_a_src_dev, grad_a_dst_dev),
+  SPP_REQUIRE(num_targets == 0 || gat_backward_bufs_ok(heads, rowptr_dev, x_dev, a_src_dev, a_dst_dev, z_dev,
+                                                       row_max_dev, row_sum_dev, grad_z_dev, grad_a_src_dev,
+                                                       grad_a_dst_dev),
               "%s: NULL or unaligned buffer", who);
   SPP_REQUIRE(rowptr_dev && v_src_dev && v_dst_dev && grad_x_dev && grad_a_src_dev && workspace_dev && al16(v_src_dev) &&
-                  al16(v_dst_dev) && al16(grad_x_dev) && al16(grad_a_src_dev) && al16(workspace_dev),
-              "%s: NULL buffer or buffers not 16-byte aligned", who);
+                  al16(v_dst_dev) && al16(grad_x_dev) && al_heads(grad_a_src_dev, heads) && al16(workspace_dev),
+              "%s: NULL or unaligned buffer (v, grad_x and the workspace: 16 bytes)", who);
   SPP_REQUIRE(workspace_bytes >=
                   spp_gat_mh_aggregate_backward_gather_workspace_bytes(num_targets, num_sources, num_edges, heads),
               "%s: workspace too small", who);
@@ -2074,9 +1643,9 @@ extern "C" spp_status spp_gat_mh_aggregate_backward_gather(
   const int64_t alpha_bytes = align16(4 * heads * num_edges) + align16(4 * heads * num_targets);
   // the attention weights of every entry and head + grad_a_src / grad_a_dst (no input gradient by atomics)
   if (num_targets > 0)
-    SPP_TRY(gat_mh_backward_launch(rowptr_dev, col_dev, num_targets, x_dev, x_elem, x_stride_elems, K, heads, a_src_dev,
-                                   a_dst_dev, negative_slope, z_dev, row_max_dev, row_sum_dev, grad_z_dev, nullptr,
-                                   grad_a_src_dev, grad_a_dst_dev, alpha_e, alpha_self, stream));
+    SPP_TRY(gat_backward_launch(rowptr_dev, col_dev, num_targets, x_dev, x_elem, x_stride_elems, K, heads, a_src_dev,
+                                a_dst_dev, negative_slope, z_dev, row_max_dev, row_sum_dev, grad_z_dev, nullptr,
+                                grad_a_src_dev, grad_a_dst_dev, alpha_e, alpha_self, stream));
   TransposedHop hop;
   SPP_TRY(transpose_hop(rowptr_dev, col_dev, num_targets, num_sources, num_edges, true,
                         static_cast<char*>(workspace_dev) + alpha_bytes, workspace_bytes - alpha_bytes, st, &hop));
@@ -2089,6 +1658,112 @@ extern "C" spp_status spp_gat_mh_aggregate_backward_gather(
   });
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
+}
+
+// the exported spellings: with the head count, and -- the entries that predate it -- with heads fixed at 1
+extern "C" spp_status spp_gat_mh_logits(const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t num_sources,
+                                        int64_t num_targets, int64_t K, int32_t heads, const float* v_src_dev,
+                                        const float* v_dst_dev, float* a_src_dev, float* a_dst_dev, void* stream) {
+  return gat_logits("spp_gat_mh_logits", x_dev, x_elem, x_stride_elems, num_sources, num_targets, K, heads, v_src_dev,
+                    v_dst_dev, a_src_dev, a_dst_dev, stream);
+}
+
+extern "C" spp_status spp_gat_logits(const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t num_sources,
+                                     int64_t num_targets, int64_t K, const float* v_src_dev, const float* v_dst_dev,
+                                     float* a_src_dev, float* a_dst_dev, void* stream) {
+  return gat_logits("spp_gat_logits", x_dev, x_elem, x_stride_elems, num_sources, num_targets, K, 1, v_src_dev,
+                    v_dst_dev, a_src_dev, a_dst_dev, stream);
+}
+
+extern "C" spp_status spp_gat_mh_logits_backward(const void* x_dev, int32_t x_elem, int64_t x_stride_elems,
+                                                 int64_t num_sources, int64_t num_targets, int64_t K, int32_t heads,
+                                                 const float* grad_a_src_dev, const float* grad_a_dst_dev,
+                                                 float* grad_v_src_dev, float* grad_v_dst_dev, void* stream) {
+  return gat_logits_backward("spp_gat_mh_logits_backward", x_dev, x_elem, x_stride_elems, num_sources, num_targets, K,
+                             heads, grad_a_src_dev, grad_a_dst_dev, grad_v_src_dev, grad_v_dst_dev, stream);
+}
+
+extern "C" spp_status spp_gat_logits_backward(const void* x_dev, int32_t x_elem, int64_t x_stride_elems,
+                                              int64_t num_sources, int64_t num_targets, int64_t K,
+                                              const float* grad_a_src_dev, const float* grad_a_dst_dev,
+                                              float* grad_v_src_dev, float* grad_v_dst_dev, void* stream) {
+  return gat_logits_backward("spp_gat_logits_backward", x_dev, x_elem, x_stride_elems, num_sources, num_targets, K, 1,
+                             grad_a_src_dev, grad_a_dst_dev, grad_v_src_dev, grad_v_dst_dev, stream);
+}
+
+extern "C" spp_status spp_gat_mh_aggregate_forward(const int64_t* rowptr_dev, const int64_t* col_dev,
+                                                   int64_t num_targets, const void* x_dev, int32_t x_elem,
+                                                   int64_t x_stride_elems, int64_t K, int32_t heads,
+                                                   const float* a_src_dev, const float* a_dst_dev, float negative_slope,
+                                                   float* z_dev, float* row_max_dev, float* row_sum_dev, void* stream) {
+  return gat_aggregate_forward("spp_gat_mh_aggregate_forward", rowptr_dev, col_dev, num_targets, x_dev, x_elem,
+                               x_stride_elems, K, heads, a_src_dev, a_dst_dev, negative_slope, z_dev, row_max_dev,
+                               row_sum_dev, stream);
+}
+
+extern "C" spp_status spp_gat_aggregate_forward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                                                const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t K,
+                                                const float* a_src_dev, const float* a_dst_dev, float negative_slope,
+                                                float* z_dev, float* row_max_dev, float* row_sum_dev, void* stream) {
+  return gat_aggregate_forward("spp_gat_aggregate_forward", rowptr_dev, col_dev, num_targets, x_dev, x_elem,
+                               x_stride_elems, K, 1, a_src_dev, a_dst_dev, negative_slope, z_dev, row_max_dev,
+                               row_sum_dev, stream);
+}
+
+extern "C" spp_status spp_gat_mh_aggregate_backward(const int64_t* rowptr_dev, const int64_t* col_dev,
+                                                    int64_t num_targets, const void* x_dev, int32_t x_elem,
+                                                    int64_t x_stride_elems, int64_t K, int32_t heads,
+                                                    const float* a_src_dev, const float* a_dst_dev,
+                                                    float negative_slope, const float* z_dev, const float* row_max_dev,
+                                                    const float* row_sum_dev, const float* grad_z_dev, float* grad_x_dev,
+                                                    float* grad_a_src_dev, float* grad_a_dst_dev, void* stream) {
+  return gat_aggregate_backward("spp_gat_mh_aggregate_backward", rowptr_dev, col_dev, num_targets, x_dev, x_elem,
+                                x_stride_elems, K, heads, a_src_dev, a_dst_dev, negative_slope, z_dev, row_max_dev,
+                                row_sum_dev, grad_z_dev, grad_x_dev, grad_a_src_dev, grad_a_dst_dev, stream);
+}
+
+extern "C" spp_status spp_gat_aggregate_backward(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                                                 const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t K,
+                                                 const float* a_src_dev, const float* a_dst_dev, float negative_slope,
+                                                 const float* z_dev, const float* row_max_dev, const float* row_sum_dev,
+                                                 const float* grad_z_dev, float* grad_x_dev, float* grad_a_src_dev,
+                                                 float* grad_a_dst_dev, void* stream) {
+  return gat_aggregate_backward("spp_gat_aggregate_backward", rowptr_dev, col_dev, num_targets, x_dev, x_elem,
+                                x_stride_elems, K, 1, a_src_dev, a_dst_dev, negative_slope, z_dev, row_max_dev,
+                                row_sum_dev, grad_z_dev, grad_x_dev, grad_a_src_dev, grad_a_dst_dev, stream);
+}
+
+extern "C" int64_t spp_gat_aggregate_backward_gather_workspace_bytes(int64_t num_targets, int64_t num_sources,
+                                                                     int64_t num_edges) {
+  return spp_gat_mh_aggregate_backward_gather_workspace_bytes(num_targets, num_sources, num_edges, 1);
+}
+
+extern "C" spp_status spp_gat_mh_aggregate_backward_gather(
+    const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets, int64_t num_sources, int64_t num_edges,
+    const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t K, int32_t heads, const float* a_src_dev,
+    const float* a_dst_dev, float negative_slope, const float* z_dev, const float* row_max_dev,
+    const float* row_sum_dev, const float* grad_z_dev, const float* v_src_dev, const float* v_dst_dev,
+    float* grad_x_dev, float* grad_a_src_dev, float* grad_a_dst_dev, void* workspace_dev, int64_t workspace_bytes,
+    void* stream) {
+  return gat_aggregate_backward_gather("spp_gat_mh_aggregate_backward_gather", rowptr_dev, col_dev, num_targets,
+                                       num_sources, num_edges, x_dev, x_elem, x_stride_elems, K, heads, a_src_dev,
+                                       a_dst_dev, negative_slope, z_dev, row_max_dev, row_sum_dev, grad_z_dev, v_src_dev,
+                                       v_dst_dev, grad_x_dev, grad_a_src_dev, grad_a_dst_dev, workspace_dev,
+                                       workspace_bytes, stream);
+}
+
+extern "C" spp_status spp_gat_aggregate_backward_gather(
+    const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets, int64_t num_sources, int64_t num_edges,
+    const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t K, const float* a_src_dev,
+    const float* a_dst_dev, float negative_slope, const float* z_dev, const float* row_max_dev,
+    const float* row_sum_dev, const float* grad_z_dev, const float* v_src_dev, const float* v_dst_dev,
+    float* grad_x_dev, float* grad_a_src_dev, float* grad_a_dst_dev, void* workspace_dev, int64_t workspace_bytes,
+    void* stream) {
+  return gat_aggregate_backward_gather("spp_gat_aggregate_backward_gather", rowptr_dev, col_dev, num_targets,
+                                       num_sources, num_edges, x_dev, x_elem, x_stride_elems, K, 1, a_src_dev, a_dst_dev,
+                                       negative_slope, z_dev, row_max_dev, row_sum_dev, grad_z_dev, v_src_dev, v_dst_dev,
+                                       grad_x_dev, grad_a_src_dev, grad_a_dst_dev, workspace_dev, workspace_bytes,
+                                       stream);
 }
 
 // ================================================================================================

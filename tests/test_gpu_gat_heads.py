@@ -1,5 +1,6 @@
 """GPU: multi-head GAT.  The spp_gat_mh_* kernels against a plain-torch multi-head restatement (every head count they
-are built for, fp32 / fp16 / bf16 rows), their per-head identity with the single-head kernels, GATConv(heads > 1) on
+are built for, fp32 / fp16 / bf16 rows), their per-head identity with the single-head entries (which are their heads = 1
+spelling, checked entry by entry, 4-byte aligned per-head arrays included), GATConv(heads > 1) on
 the kernel path and on the plain-torch path against PyG's project-then-aggregate order, and GAT(heads=4) end to end.
 
 Tolerances are those of test_gpu_model_step.py's aggregate-then-project check: forward rtol 2e-4 / atol 2e-5 (sums
@@ -71,10 +72,14 @@ def _st():
 
 
 class _Run:
-    """the multi-head entries on one hop; every output is a fresh fp32 tensor"""
+    """the multi-head entries on one hop (single=True: the entries without a head count, which are their heads = 1
+    spelling); every output is a fresh fp32 tensor.  off > 0: the per-head arrays ([n, H]) start `off` floats into
+    their allocation, so they are 4-byte and not 16-byte aligned at off = 1."""
 
-    def __init__(self, x, rowptr, col, T, H, V):
+    def __init__(self, x, rowptr, col, T, H, V, single=False, off=0):
         self.x, self.rowptr, self.col, self.T, self.H, self.V = x, rowptr, col, T, H, V
+        self.single, self.off = single, off
+        assert H == 1 or not single
         self.S, self.K = x.shape
         self.E = col.numel()
         self.elem = ELEM[x.dtype]
@@ -83,50 +88,61 @@ class _Run:
     def _f(self, *shape):
         return torch.empty(shape, dtype=torch.float32, device="cuda")
 
+    def _heads(self, n, zero=False):
+        buf = (torch.zeros if zero else torch.empty)(self.off + n * self.H, dtype=torch.float32, device="cuda")
+        out = buf[self.off:].view(n, self.H)
+        assert out.data_ptr() % 16 == (4 * self.off) % 16
+        return out
+
+    def _call(self, name, *args):
+        """args hold the head count as an int32 right after K; the single-head spelling has no such argument"""
+        if self.single:
+            name, args = name.replace("_mh_", "_"), [a for a in args if a is not self._H]
+        else:
+            args = [self.H if a is self._H else a for a in args]
+        rc = getattr(_lib(), name)(*args)
+        assert rc == 0, (name, rc)
+
+    _H = object()                                            # the place of the head count in an argument list
+
     def logits(self):
-        a_src, a_dst = self._f(self.S, self.H), self._f(self.T, self.H)
-        rc = _lib().spp_gat_mh_logits(_p(self.x), self.elem, self.xs, self.S, self.T, self.K, self.H, _p(self.V[0]),
-                                      _p(self.V[1]), _p(a_src), _p(a_dst), _st())
-        assert rc == 0
+        a_src, a_dst = self._heads(self.S), self._heads(self.T)
+        self._call("spp_gat_mh_logits", _p(self.x), self.elem, self.xs, self.S, self.T, self.K, self._H, _p(self.V[0]),
+                   _p(self.V[1]), _p(a_src), _p(a_dst), _st())
         return a_src, a_dst
 
     def forward(self, a_src, a_dst):
-        z, rmax, rsum = self._f(self.T, self.H, self.K), self._f(self.T, self.H), self._f(self.T, self.H)
-        rc = _lib().spp_gat_mh_aggregate_forward(_p(self.rowptr), _p(self.col), self.T, _p(self.x), self.elem, self.xs,
-                                                 self.K, self.H, _p(a_src), _p(a_dst), 0.2, _p(z), _p(rmax), _p(rsum),
-                                                 _st())
-        assert rc == 0
+        z, rmax, rsum = self._f(self.T, self.H, self.K), self._heads(self.T), self._heads(self.T)
+        self._call("spp_gat_mh_aggregate_forward", _p(self.rowptr), _p(self.col), self.T, _p(self.x), self.elem,
+                   self.xs, self.K, self._H, _p(a_src), _p(a_dst), 0.2, _p(z), _p(rmax), _p(rsum), _st())
         return z, rmax, rsum
 
     def backward_atomic(self, a_src, a_dst, z, rmax, rsum, g_z, want_gx=True):
         g_x = torch.zeros((self.S, self.K), dtype=torch.float32, device="cuda") if want_gx else None
-        g_as = torch.zeros((self.S, self.H), dtype=torch.float32, device="cuda")
-        g_ad = self._f(self.T, self.H)
-        rc = _lib().spp_gat_mh_aggregate_backward(_p(self.rowptr), _p(self.col), self.T, _p(self.x), self.elem, self.xs,
-                                                  self.K, self.H, _p(a_src), _p(a_dst), 0.2, _p(z), _p(rmax), _p(rsum),
-                                                  _p(g_z), _p(g_x), _p(g_as), _p(g_ad), _st())
-        assert rc == 0
+        g_as, g_ad = self._heads(self.S, zero=True), self._heads(self.T)
+        self._call("spp_gat_mh_aggregate_backward", _p(self.rowptr), _p(self.col), self.T, _p(self.x), self.elem,
+                   self.xs, self.K, self._H, _p(a_src), _p(a_dst), 0.2, _p(z), _p(rmax), _p(rsum), _p(g_z), _p(g_x),
+                   _p(g_as), _p(g_ad), _st())
         return g_x, g_as, g_ad
 
     def backward_gather(self, a_src, a_dst, z, rmax, rsum, g_z):
         L = _lib()
         g_x = self._f(self.S, self.K)
-        g_as = torch.zeros((self.S, self.H), dtype=torch.float32, device="cuda")
-        g_ad = self._f(self.T, self.H)
-        nbytes = int(L.spp_gat_mh_aggregate_backward_gather_workspace_bytes(self.T, self.S, self.E, self.H))
+        g_as, g_ad = self._heads(self.S, zero=True), self._heads(self.T)
+        if self.single:
+            nbytes = int(L.spp_gat_aggregate_backward_gather_workspace_bytes(self.T, self.S, self.E))
+        else:
+            nbytes = int(L.spp_gat_mh_aggregate_backward_gather_workspace_bytes(self.T, self.S, self.E, self.H))
         ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device="cuda")
-        rc = L.spp_gat_mh_aggregate_backward_gather(_p(self.rowptr), _p(self.col), self.T, self.S, self.E, _p(self.x),
-                                                    self.elem, self.xs, self.K, self.H, _p(a_src), _p(a_dst), 0.2,
-                                                    _p(z), _p(rmax), _p(rsum), _p(g_z), _p(self.V[0]), _p(self.V[1]),
-                                                    _p(g_x), _p(g_as), _p(g_ad), _p(ws), nbytes, _st())
-        assert rc == 0
+        self._call("spp_gat_mh_aggregate_backward_gather", _p(self.rowptr), _p(self.col), self.T, self.S, self.E,
+                   _p(self.x), self.elem, self.xs, self.K, self._H, _p(a_src), _p(a_dst), 0.2, _p(z), _p(rmax),
+                   _p(rsum), _p(g_z), _p(self.V[0]), _p(self.V[1]), _p(g_x), _p(g_as), _p(g_ad), _p(ws), nbytes, _st())
         return g_x, g_as, g_ad
 
     def logits_backward(self, g_as, g_ad):
         g_V = self._f(2, self.H, self.K)
-        rc = _lib().spp_gat_mh_logits_backward(_p(self.x), self.elem, self.xs, self.S, self.T, self.K, self.H,
-                                               _p(g_as), _p(g_ad), _p(g_V[0]), _p(g_V[1]), _st())
-        assert rc == 0
+        self._call("spp_gat_mh_logits_backward", _p(self.x), self.elem, self.xs, self.S, self.T, self.K, self._H,
+                   _p(g_as), _p(g_ad), _p(g_V[0]), _p(g_V[1]), _st())
         return g_V
 
 
@@ -234,6 +250,87 @@ def test_mh_forward_equals_the_single_head_kernel_per_head(H, dtype, K):
                                            _p(adst), 0.2, _p(z1), _p(m1), _p(s1), _st()) == 0
         assert torch.equal(z[:, h], z1), h
         assert torch.equal(rmax[:, h], m1) and torch.equal(rsum[:, h], s1), h
+
+
+def _same_entries(one, two, g_z, exact=torch.equal):
+    """every entry through `one` and through `two` on the same inputs: what is written without atomics is bit-identical,
+    what fp32 atomics accumulate (grad_a_src, the atomic form's grad_x, grad_v) agrees within BWD"""
+    close = torch.testing.assert_close
+    la, lb = one.logits(), two.logits()
+    assert exact(la[0], lb[0]) and exact(la[1], lb[1])
+    a_src, a_dst = la
+    fa, fb = one.forward(a_src, a_dst), two.forward(a_src, a_dst)
+    assert exact(fa[0], fb[0]) and exact(fa[1], fb[1]) and exact(fa[2], fb[2])
+    z, rmax, rsum = fa
+    for want_gx in (True, False):
+        ga = one.backward_atomic(a_src, a_dst, z, rmax, rsum, g_z, want_gx)
+        gb = two.backward_atomic(a_src, a_dst, z, rmax, rsum, g_z, want_gx)
+        assert exact(ga[2], gb[2])                                           # grad_a_dst
+        close(ga[1], gb[1], **BWD)                                           # grad_a_src
+        if want_gx:
+            close(ga[0], gb[0], **BWD)
+    gas, gad = ga[1], ga[2]
+    ta = one.backward_gather(a_src, a_dst, z, rmax, rsum, g_z)
+    tb = two.backward_gather(a_src, a_dst, z, rmax, rsum, g_z)
+    assert exact(ta[2], tb[2])
+    close(ta[1], tb[1], **BWD)
+    close(ta[0], tb[0], **BWD)
+    # the gather form's grad_x row s is written without atomics from grad_a_src[s]: identical wherever that is
+    same = (ta[1] == tb[1]).all(1)
+    assert same.any() and exact(ta[0][same], tb[0][same])
+    va, vb = one.logits_backward(gas, gad), two.logits_backward(gas, gad)
+    close(va, vb, **BWD)
+    assert torch.isfinite(ta[0]).all() and torch.isfinite(va).all()
+
+
+def _small_hop_inputs(K, H, dtype):
+    T, S = 37, 90
+    x, rowptr, col, V, g_z = _inputs(T, S, K, H, dtype, seed=K + H, maxdeg=12)
+    deg = rowptr[1:] - rowptr[:-1]
+    row = torch.repeat_interleave(torch.arange(T, device="cuda"), deg)
+    assert (deg == 0).any() and (col == row).any()           # a target without entries, and diagonal entries
+    return x, rowptr, col, T, V, g_z
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("K", [8, 100])
+def test_single_head_entries_are_the_heads1_spelling(K, dtype):
+    """spp_gat_logits / spp_gat_aggregate_* against spp_gat_mh_* with heads = 1 on the same buffers"""
+    x, rowptr, col, T, V, g_z = _small_hop_inputs(K, 1, dtype)
+    _same_entries(_Run(x, rowptr, col, T, 1, V, single=True), _Run(x, rowptr, col, T, 1, V), g_z)
+
+
+def test_single_head_entries_accept_4_byte_aligned_head_arrays():
+    """The per-head arrays need 4 * min(H, 4) bytes: one float into an allocation they serve heads = 1 (all five
+    entries, the results of the aligned call) and are refused at heads = 4 before anything is launched."""
+    K = 8
+    x, rowptr, col, T, V, g_z = _small_hop_inputs(K, 1, torch.float32)
+    _same_entries(_Run(x, rowptr, col, T, 1, V, single=True, off=1), _Run(x, rowptr, col, T, 1, V, single=True), g_z)
+    L = _lib()
+    S, E, H, st = x.size(0), col.numel(), 4, _st()
+    V4 = torch.randn((2, H, K), device="cuda")
+    g_z4 = torch.randn((T, H, K), device="cuda")
+    sent = lambda *shape: torch.full(shape, 7.0, device="cuda")
+    off1 = lambda n: sent(1 + n * H)[1:].view(n, H)         # 4-byte aligned, not 16
+    a_src, a_dst, rm, rs, gas, gad = off1(S), off1(T), off1(T), off1(T), off1(S), off1(T)
+    assert all(t.data_ptr() % 16 == 4 for t in (a_src, a_dst, rm, rs, gas, gad))
+    z, gx, gV = sent(T, H, K), sent(S, K), sent(2, H, K)
+    ws = torch.zeros(1 << 20, dtype=torch.uint8, device="cuda")
+    rcs = [
+        L.spp_gat_mh_logits(_p(x), 0, K, S, T, K, H, _p(V4[0]), _p(V4[1]), _p(a_src), _p(a_dst), st),
+        L.spp_gat_mh_aggregate_forward(_p(rowptr), _p(col), T, _p(x), 0, K, K, H, _p(a_src), _p(a_dst), 0.2, _p(z),
+                                       _p(rm), _p(rs), st),
+        L.spp_gat_mh_aggregate_backward(_p(rowptr), _p(col), T, _p(x), 0, K, K, H, _p(a_src), _p(a_dst), 0.2, _p(g_z4),
+                                        _p(rm), _p(rs), _p(g_z4), _p(gx), _p(gas), _p(gad), st),
+        L.spp_gat_mh_aggregate_backward_gather(_p(rowptr), _p(col), T, S, E, _p(x), 0, K, K, H, _p(a_src), _p(a_dst),
+                                               0.2, _p(g_z4), _p(rm), _p(rs), _p(g_z4), _p(V4[0]), _p(V4[1]), _p(gx),
+                                               _p(gas), _p(gad), _p(ws), ws.numel(), st),
+        L.spp_gat_mh_logits_backward(_p(x), 0, K, S, T, K, H, _p(gas), _p(gad), _p(gV[0]), _p(gV[1]), st),
+    ]
+    torch.cuda.synchronize()
+    assert rcs == [-1] * 5, rcs
+    for t in (a_src, a_dst, rm, rs, gas, gad, z, gx, gV):
+        assert torch.equal(t, torch.full_like(t, 7.0))
 
 
 @pytest.mark.parametrize("heads,elem", [(3, 0), (0, 0), (16, 1), (-4, 2), (4, 3), (2, -1)])

@@ -116,6 +116,25 @@ def test_gat_mh_symbols_are_declared_and_bound():
         assert L.spp_gat_mh_aggregate_backward_gather_workspace_bytes(10, 20, 30, 4) > 0
 
 
+@pytest.mark.parametrize("T,S,E", [(0, 0, 0), (0, 5, 0), (1, 1, 1), (37, 90, 231), (1500, 5000, 9001),
+                                   (164_000, 947_000, 1_640_003)])
+def test_single_head_gather_workspace_is_the_heads1_spelling(T, S, E):
+    """alpha_e [E, H] | alpha_self [T, H] | the transposed hop with edge ids, each part rounded up to 16 bytes; the
+    transposed hop with edge ids is spp_sage_operand_backward_workspace_bytes' (without them) plus tedge [E]"""
+    from salient_plusplus_amd import _native as nat
+    L = nat.load()
+
+    def a16(v):
+        return (v + 15) & ~15
+
+    def want(H):
+        return a16(4 * H * E) + a16(4 * H * T) + int(L.spp_sage_operand_backward_workspace_bytes(T, S, E)) + a16(4 * E)
+
+    one = int(L.spp_gat_aggregate_backward_gather_workspace_bytes(T, S, E))
+    assert one == int(L.spp_gat_mh_aggregate_backward_gather_workspace_bytes(T, S, E, 1)) == want(1)
+    assert int(L.spp_gat_mh_aggregate_backward_gather_workspace_bytes(T, S, E, 4)) == want(4)
+
+
 def _per_edge_gat(x, x_t, W, att_src, att_dst, rowptr, col, slope, concat):
     """PyG's GATConv written edge by edge in float64 (set_diag: diagonal entries dropped, one self loop per target)"""
     H, C = att_src.shape
