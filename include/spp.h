@@ -1338,6 +1338,98 @@ int64_t spp_field_workspace_bytes(int64_t num_ids);
 spp_status spp_field_mark(const spp_field_desc* desc, void* workspace_dev, int64_t workspace_bytes, void* stream);
 spp_status spp_field_rows(const spp_field_desc* desc, void* workspace_dev, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * f3p  The TRAINING form of the layer tail that follows a GEMM in GIN and SAGEResInception:
+ *      y = dropout(act(BatchNorm(z))) [+ r], on batch statistics, forward and backward (f3i is its eval-only, forward-only
+ *      relative on folded running statistics).
+ *
+ *   z, r, y are [n, C], row-major and dense, fp32 or bf16 each on its own; C >= 1 is any value.  A bf16 value is read as
+ *   its fp32 value, every per-element operation is fp32 and a bf16 output is rounded once, to nearest even.  gamma, beta,
+ *   the running statistics, mean, invstd, dgamma and dbeta are fp32 [C].
+ *
+ *   spp_bn_act_forward, training != 0 (n >= 2):
+ *        mean[c]   = the mean, var[c] the BIASED variance of column c over the n rows
+ *        invstd[c] = 1 / sqrt(var[c] + eps)
+ *        u         = gamma[c] * (z[i,c] - mean[c]) * invstd[c] + beta[c]      of the fp32 operands, rounded once: the
+ *                    rounding errors of the fp32 operations are recovered (two-sums, fma residuals) and added back
+ *                    before the last rounding, so u is within about half an ulp of the exact expression
+ *        a         = u (SPP_BN_ACT_NONE) | u > 0 ? u : 0 (SPP_BN_ACT_RELU) | u > 0 ? u : negative_slope * u (_LEAKY_RELU)
+ *        y[i,c]    = round_once((keep(i*C + c) ? a * (1 / (1 - p)) : 0) + r[i,c])          (p == 0: a itself; no r: no add)
+ *      keep(e) is the generator of spp_relu_dropout_forward over a dense array of n*C elements at the same (seed, p):
+ *      an array of n*C positive values passed through that entry keeps exactly the same elements.
+ *      mean and invstd are written (backward reads them), and the running buffers are updated as torch.nn.BatchNorm1d
+ *      does, with f = momentum, or f = 1 / *num_batches_tracked_dev when momentum < 0 (the cumulative average; the
+ *      CALLER has already counted this batch):
+ *        running_mean = (1 - f) * running_mean + f * mean
+ *        running_var  = (1 - f) * running_var  + f * var * n / (n - 1)                     (the UNBIASED variance)
+ *      running_mean_dev / running_var_dev may both be NULL in training (nothing is tracked).
+ *      Statistics: z is read once, no float atomics.  The rows are cut into slabs of SPP_BN_ACT_SLAB_ROWS, one workgroup
+ *      per slab folds its rows into per-column (mean, M2) by Welford's update, and a second kernel combines the slabs in
+ *      a fixed order by Chan's update (in fp64) and writes mean, invstd and the running buffers: the same bits from call
+ *      to call on the same input.
+ *   spp_bn_act_forward, training == 0: no statistics pass and no dropout (p and seed are not read); mean = running_mean,
+ *      invstd = 1 / sqrt(running_var + eps), both written to mean_dev / invstd_dev; the running buffers are only read.
+ *
+ *   spp_bn_act_backward reads g (the gradient of y, [n, C], g_elem), z, mean, invstd, gamma, beta and the seed -- neither
+ *   y nor a mask: the sign of u and keep(e) are recomputed, by the forward's own expressions.
+ *        xh        = (z[i,c] - mean[c]) * invstd[c]                        (two fp32 operations)
+ *        g_a       = g[i,c] * (keep ? 1 / (1 - p) : 0) * act'(u)          act'(u) = 1 for u > 0, else 0 / negative_slope
+ *        dbeta[c]  = sum_i g_a        dgamma[c] = sum_i g_a * xh          (slab partials, combined in a fixed order in fp64)
+ *        dz[i,c]   = round_once(gamma * invstd * (g_a - dbeta / n - xh * dgamma / n))      training
+ *        dz[i,c]   = round_once(gamma * invstd * g_a)                                     training == 0
+ *      dz has z's element type.  The gradient of r is g itself: no kernel runs for it.
+ *
+ *   The 16-byte vector form (4 columns per lane) applies when C % 4 == 0 and every matrix base is aligned to 4 of its
+ *   elements, a workgroup-uniform choice; anything else runs one column per lane with the same result.
+ *   Workspace: spp_bn_act_workspace_bytes(n, C) bytes, 16-byte aligned, the caller's; its contents mean nothing between
+ *   calls.  The entries enqueue their launches on `stream` and never wait for the device.
+ *   Refused with SPP_ERR_INVALID before anything is enqueued, in a message that names the entry: a NULL descriptor;
+ *   n < 2 in training ("more than 1 value per channel"), negative n; C outside [1, 2^31); p outside [0, 1); an unknown
+ *   act or element code (fp16, fp8); a NULL required pointer (z, gamma, beta, mean, invstd; y forward; g, dz, dgamma,
+ *   dbeta backward; the running buffers in eval; num_batches_tracked_dev with momentum < 0 and running buffers); a
+ *   missing, misaligned or too small workspace.  n == 0 in eval: SPP_OK, nothing enqueued, nothing written.
+ * ------------------------------------------------------------------------- */
+#define SPP_BN_ACT_SLAB_ROWS 32
+enum { SPP_BN_ACT_NONE = 0, SPP_BN_ACT_RELU = 1, SPP_BN_ACT_LEAKY_RELU = 2 };
+
+typedef struct spp_bn_act_desc {
+  int32_t z_elem;            /* SPP_ELEM_F32 / SPP_ELEM_BF16; dz has the same */
+  int32_t r_elem;            /* forward, with r_dev */
+  int32_t y_elem;            /* forward */
+  int32_t g_elem;            /* backward */
+  int32_t act;               /* SPP_BN_ACT_* */
+  int32_t training;
+  float negative_slope;
+  float p;                   /* dropout probability, [0, 1); training only */
+  float eps;
+  int32_t reserved;
+  double momentum;           /* < 0: the cumulative average, 1 / *num_batches_tracked_dev */
+  uint64_t seed;
+  int64_t n;
+  int64_t C;
+  const void* z_dev;
+  const float* gamma_dev;
+  const float* beta_dev;
+  float* running_mean_dev;   /* training: updated (NULL with running_var_dev: not tracked); eval: read */
+  float* running_var_dev;
+  const int64_t* num_batches_tracked_dev; /* read when momentum < 0; already counts this batch */
+  const void* r_dev;         /* forward: the residual, NULL = none */
+  void* y_dev;               /* forward: out */
+  float* mean_dev;           /* forward: out; backward: in */
+  float* invstd_dev;         /* forward: out; backward: in */
+  const void* g_dev;         /* backward: the gradient of y */
+  void* dz_dev;              /* backward: out */
+  float* dgamma_dev;         /* backward: out */
+  float* dbeta_dev;          /* backward: out */
+  void* workspace_dev;
+  int64_t workspace_bytes;
+} spp_bn_act_desc;
+
+int64_t spp_bn_act_slab_rows(void);
+int64_t spp_bn_act_workspace_bytes(int64_t n, int64_t C);
+spp_status spp_bn_act_forward(const spp_bn_act_desc* desc, void* stream);
+spp_status spp_bn_act_backward(const spp_bn_act_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

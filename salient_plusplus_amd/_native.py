@@ -59,6 +59,7 @@ class MfgOut(C.Structure):
 
 # spp_elem and the aggregation descriptor's codes (include/spp.h)
 SPP_ELEM_F32, SPP_ELEM_F16, SPP_ELEM_BF16 = 0, 1, 2
+SPP_BN_ACT_NONE, SPP_BN_ACT_RELU, SPP_BN_ACT_LEAKY_RELU = 0, 1, 2
 SPP_ELEM_FP8_E4M3 = 3            # spp_agg_forward_fp8, spp_graph_agg_*_forward_fp8, spp_exchange_cfg.x_elem
 SPP_AGG_DENSE, SPP_AGG_TABLE, SPP_AGG_ROWS = 0, 1, 2
 SPP_AGG_MEAN, SPP_AGG_OPERAND, SPP_AGG_OPERAND_ACT, SPP_AGG_SUM = 0, 1, 2, 3
@@ -125,6 +126,16 @@ class ResincEpilogueDesc(C.Structure):
                 ("z_stride_elems", i64), ("a_dev", p), ("b_dev", p), ("r_dev", p), ("r_stride_elems", i64),
                 ("r_rows", i64), ("r_row0", i64), ("r_ids_dev", p), ("n", i64), ("C", i64), ("out_dev", p),
                 ("out_stride_elems", i64)]
+
+
+class BnActDesc(C.Structure):
+    """spp_bn_act_desc: y = dropout(act(BatchNorm(z))) [+ r] on batch statistics, and its backward"""
+    _fields_ = [("z_elem", i32), ("r_elem", i32), ("y_elem", i32), ("g_elem", i32), ("act", i32), ("training", i32),
+                ("negative_slope", C.c_float), ("p", C.c_float), ("eps", C.c_float), ("reserved", i32),
+                ("momentum", C.c_double), ("seed", C.c_uint64), ("n", i64), ("C", i64), ("z_dev", p), ("gamma_dev", p),
+                ("beta_dev", p), ("running_mean_dev", p), ("running_var_dev", p), ("num_batches_tracked_dev", p),
+                ("r_dev", p), ("y_dev", p), ("mean_dev", p), ("invstd_dev", p), ("g_dev", p), ("dz_dev", p),
+                ("dgamma_dev", p), ("dbeta_dev", p), ("workspace_dev", p), ("workspace_bytes", i64)]
 
 
 class ClassifyDesc(C.Structure):
@@ -282,6 +293,10 @@ SIGNATURES = {
     "spp_field_workspace_bytes": (i64, [i64]),
     "spp_field_mark": (C.c_int, [C.POINTER(FieldDesc), p, i64, p]),
     "spp_field_rows": (C.c_int, [C.POINTER(FieldDesc), p, i64, p]),
+    "spp_bn_act_slab_rows": (i64, []),
+    "spp_bn_act_workspace_bytes": (i64, [i64, i64]),
+    "spp_bn_act_forward": (C.c_int, [C.POINTER(BnActDesc), p]),
+    "spp_bn_act_backward": (C.c_int, [C.POINTER(BnActDesc), p]),
 }
 SPP_COMM_ID_BYTES = 128
 SPP_IPC_HANDLE_BYTES = 64

@@ -1,0 +1,63 @@
+// The keep / drop rule of every dropout this library applies (aggregate.hip: k_relu_dropout_*, the activated operand;
+// bn_act.hip: the BatchNorm tail), from a counter-based generator: element i of the call with `seed` is kept iff
+// hash(seed, i) < (1 - p) * 2^32.  One 64-bit hash serves two elements; the n % 4 elements at the end of an array take
+// a hash of their own (the tail of k_relu_dropout_fwd).
+#pragma once
+
+#include "elem_io.hip.h"
+
+namespace spp {
+
+__device__ __forceinline__ uint64_t mix64(uint64_t z) {  // splitmix64 finaliser
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+struct ActArgs {
+  uint32_t keep_thr;
+  float scale;
+  uint64_t seed;
+  int32_t training;
+};
+
+// keep / drop of the four elements 4*i4 .. 4*i4+3 of a dense array
+struct Keep4 {
+  bool x, y, z, w;
+};
+__device__ __forceinline__ Keep4 keep4(int64_t i4, const ActArgs& a) {
+  const uint64_t r0 = mix64(a.seed + 2ull * (uint64_t)i4 * 0x9E3779B97F4A7C15ull);
+  const uint64_t r1 = mix64(a.seed + (2ull * (uint64_t)i4 + 1ull) * 0x9E3779B97F4A7C15ull);
+  return {(uint32_t)r0 < a.keep_thr, (uint32_t)(r0 >> 32) < a.keep_thr, (uint32_t)r1 < a.keep_thr,
+          (uint32_t)(r1 >> 32) < a.keep_thr};
+}
+// keep / drop of element i of a dense array of n: the same answer keep4 gives for i < n - n % 4, the tail's hash after
+__device__ __forceinline__ bool keep1(int64_t i, int64_t n, const ActArgs& a) {
+  if (i >= n - (n & 3)) return (uint32_t)mix64(a.seed + (uint64_t)i * 0xD1B54A32D192ED03ull) < a.keep_thr;
+  const uint64_t r = mix64(a.seed + (uint64_t)(i >> 1) * 0x9E3779B97F4A7C15ull);
+  return (uint32_t)(i & 1 ? r >> 32 : r) < a.keep_thr;
+}
+
+// the activation of the four elements 4*i4 .. 4*i4+3 of a dense array, exactly as k_relu_dropout_fwd computes it
+__device__ __forceinline__ f4 relu_dropout4(f4 v, int64_t i4, const ActArgs& a) {
+  if (!a.training) return {fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
+  const uint64_t r0 = mix64(a.seed + 2ull * (uint64_t)i4 * 0x9E3779B97F4A7C15ull);
+  const uint64_t r1 = mix64(a.seed + (2ull * (uint64_t)i4 + 1ull) * 0x9E3779B97F4A7C15ull);
+  f4 o;
+  o.x = (v.x > 0.f && (uint32_t)r0 < a.keep_thr) ? v.x * a.scale : 0.f;
+  o.y = (v.y > 0.f && (uint32_t)(r0 >> 32) < a.keep_thr) ? v.y * a.scale : 0.f;
+  o.z = (v.z > 0.f && (uint32_t)r1 < a.keep_thr) ? v.z * a.scale : 0.f;
+  o.w = (v.w > 0.f && (uint32_t)(r1 >> 32) < a.keep_thr) ? v.w * a.scale : 0.f;
+  return o;
+}
+
+static inline ActArgs act_args(float p, int32_t training, uint64_t seed) {
+  const double keep = 1.0 - (double)p;
+  ActArgs a{};
+  a.keep_thr = keep >= 1.0 ? 0xffffffffu : (uint32_t)(keep * 4294967296.0);
+  a.scale = (float)(1.0 / keep);
+  a.seed = seed;
+  a.training = training ? 1 : 0;
+  return a;
+}
+
+}  // namespace spp

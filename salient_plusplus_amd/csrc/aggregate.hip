@@ -6,6 +6,7 @@
 // 16-B pieces; the first layer reads the batch's fp16 features directly (fp16 -> fp32 is exact, so
 // this equals converting the whole matrix first, which the reference model does, minus one pass
 // over 150 MB).  The linear layers stay library GEMMs.
+#include "act_keep.hip.h"
 #include "elem_io.hip.h"
 
 #include <hipcub/hipcub.hpp>
@@ -82,29 +83,7 @@ __device__ __forceinline__ float load1(const fp8e4m3* p, const ColScale1<true>& 
 // ---- ReLU + dropout (driver/models.py:47-48: x = F.relu(x); x = F.dropout(x, p=0.5)) ----
 // keep / drop from a counter-based generator: element i of the call with `seed` is kept iff
 // hash(seed, i) < (1 - p) * 2^32; the output is relu(x) / (1 - p) where kept, 0 elsewhere.
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {  // splitmix64 finaliser
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-struct ActArgs {
-  uint32_t keep_thr;
-  float scale;
-  uint64_t seed;
-  int32_t training;
-};
-// the activation of the four elements 4*i4 .. 4*i4+3 of a dense array, exactly as k_relu_dropout_fwd computes it
-__device__ __forceinline__ f4 relu_dropout4(f4 v, int64_t i4, const ActArgs& a) {
-  if (!a.training) return {fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
-  const uint64_t r0 = mix64(a.seed + 2ull * (uint64_t)i4 * 0x9E3779B97F4A7C15ull);
-  const uint64_t r1 = mix64(a.seed + (2ull * (uint64_t)i4 + 1ull) * 0x9E3779B97F4A7C15ull);
-  f4 o;
-  o.x = (v.x > 0.f && (uint32_t)r0 < a.keep_thr) ? v.x * a.scale : 0.f;
-  o.y = (v.y > 0.f && (uint32_t)(r0 >> 32) < a.keep_thr) ? v.y * a.scale : 0.f;
-  o.z = (v.z > 0.f && (uint32_t)r1 < a.keep_thr) ? v.z * a.scale : 0.f;
-  o.w = (v.w > 0.f && (uint32_t)(r1 >> 32) < a.keep_thr) ? v.w * a.scale : 0.f;
-  return o;
-}
+// mix64, ActArgs and relu_dropout4 (the keep rule) live in act_keep.hip.h, shared with bn_act.hip
 
 // ---- neighbour reduction over a hop: where row j comes from (Rows<Tin, Src>(j)) ----
 //   Dense: x + j * x_stride, the batch's matrix (targets are its first rows).
@@ -440,16 +419,6 @@ using namespace spp;
 // the grid of an element-wise kernel that strides over `items` work items
 static unsigned elementwise_grid(int64_t items) {
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(items, kAggNT), 256 * 32));
-}
-
-static ActArgs act_args(float p, int32_t training, uint64_t seed) {
-  const double keep = 1.0 - (double)p;
-  ActArgs a{};
-  a.keep_thr = keep >= 1.0 ? 0xffffffffu : (uint32_t)(keep * 4294967296.0);
-  a.scale = (float)(1.0 / keep);
-  a.seed = seed;
-  a.training = training ? 1 : 0;
-  return a;
 }
 
 // The forward of every mean / operand / sum entry (`who` names the public entry in the errors): validation, the

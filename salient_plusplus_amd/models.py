@@ -216,6 +216,115 @@ def mean_aggregate(x, rowptr, col, num_targets):
     return _MeanAggregate.apply(x, rowptr, col, num_targets, False)
 
 
+# ---- the training tail behind a GEMM: dropout(act(BatchNorm(z))) [+ residual]  (csrc/bn_act.hip, spp.h f3p) ----
+_BN_ACTS = {"none": nat.SPP_BN_ACT_NONE, "relu": nat.SPP_BN_ACT_RELU, "leaky_relu": nat.SPP_BN_ACT_LEAKY_RELU}
+
+
+class _BatchNormAct(torch.autograd.Function):
+    """One node for BatchNorm1d (batch statistics in training, running statistics in eval), the activation, dropout and
+    the residual add.  Saves z, mean, invstd, gamma and beta and keeps the seed: neither the output nor a mask; the
+    backward recomputes the sign of the pre-activation and the keep pattern (spp_bn_act_backward)."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, residual, bn, act, slope, p, training):
+        L = nat.load()
+        n, Cdim = z.shape
+        if training:
+            if n < 2:       # torch's message, before any buffer is touched
+                raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(z.shape)}")
+            # the seed comes from torch's CPU generator, so torch.manual_seed makes a run repeatable
+            seed = int(torch.empty((), dtype=torch.int64).random_().item()) & 0xFFFFFFFFFFFFFFFF if p > 0 else 0
+            bn.num_batches_tracked.add_(1)
+        else:
+            seed = 0
+        y_dtype = torch.promote_types(z.dtype, residual.dtype) if residual is not None else z.dtype
+        y = torch.empty((n, Cdim), dtype=y_dtype, device=z.device)
+        mean = torch.empty(Cdim, dtype=torch.float32, device=z.device)
+        invstd = torch.empty_like(mean)
+        ws = torch.empty(L.spp_bn_act_workspace_bytes(n, Cdim), dtype=torch.uint8, device=z.device)
+        d = nat.BnActDesc(z_elem=_ELEM[z.dtype], r_elem=_ELEM[residual.dtype] if residual is not None else 0,
+                          y_elem=_ELEM[y_dtype], act=_BN_ACTS[act], training=int(training), negative_slope=float(slope),
+                          p=float(p), eps=float(bn.eps), momentum=-1.0 if bn.momentum is None else float(bn.momentum),
+                          seed=seed, n=n, C=Cdim, z_dev=_p(z), gamma_dev=_p(gamma), beta_dev=_p(beta),
+                          running_mean_dev=_p(bn.running_mean), running_var_dev=_p(bn.running_var),
+                          num_batches_tracked_dev=_p(bn.num_batches_tracked), r_dev=_p(residual), y_dev=_p(y),
+                          mean_dev=_p(mean), invstd_dev=_p(invstd), workspace_dev=_p(ws), workspace_bytes=ws.numel())
+        nat.check(L.spp_bn_act_forward(C.byref(d), _stream()))
+        ctx.save_for_backward(z, gamma, beta, mean, invstd)
+        ctx.cfg = (_BN_ACTS[act], float(slope), float(p), int(training), seed, float(bn.eps))
+        ctx.res_dtype = residual.dtype if residual is not None else None
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        L = nat.load()
+        z, gamma, beta, mean, invstd = ctx.saved_tensors
+        act, slope, p, training, seed, eps = ctx.cfg
+        n, Cdim = z.shape
+        gc = g.contiguous()
+        if gc.dtype not in (torch.float32, torch.bfloat16):
+            gc = gc.to(torch.float32)
+        g_res = g.to(ctx.res_dtype) if ctx.needs_input_grad[3] else None
+        dz = torch.empty_like(z)
+        dgamma = torch.empty(Cdim, dtype=torch.float32, device=z.device)
+        dbeta = torch.empty_like(dgamma)
+        if n > 0:
+            ws = torch.empty(L.spp_bn_act_workspace_bytes(n, Cdim), dtype=torch.uint8, device=z.device)
+            d = nat.BnActDesc(z_elem=_ELEM[z.dtype], g_elem=_ELEM[gc.dtype], act=act, training=training,
+                              negative_slope=slope, p=p, eps=eps, seed=seed, n=n, C=Cdim, z_dev=_p(z), gamma_dev=_p(gamma),
+                              beta_dev=_p(beta), mean_dev=_p(mean), invstd_dev=_p(invstd), g_dev=_p(gc), dz_dev=_p(dz),
+                              dgamma_dev=_p(dgamma), dbeta_dev=_p(dbeta), workspace_dev=_p(ws), workspace_bytes=ws.numel())
+            nat.check(L.spp_bn_act_backward(C.byref(d), _stream()))
+        else:
+            dgamma.zero_(), dbeta.zero_()
+        return dz, dgamma.to(gamma.dtype), dbeta.to(beta.dtype), g_res, None, None, None, None, None
+
+
+def _bn_act_torch(z, bn, act, negative_slope, p, training, residual):
+    """The plain torch composition: F.dropout(act(bn(z)), p, training) + residual"""
+    if training == bn.training:
+        h = bn(z)
+    else:                                           # BatchNorm1d.forward with the other mode
+        was = bn.training
+        bn.train(training)
+        try:
+            h = bn(z)
+        finally:
+            bn.train(was)
+    if act == "relu":
+        h = F.relu(h)
+    elif act == "leaky_relu":
+        h = F.leaky_relu(h, negative_slope)
+    h = F.dropout(h, p=p, training=training)
+    return h if residual is None else h + residual
+
+
+def batch_norm_act(z, bn, *, act="none", negative_slope=0.01, p=0.0, training=None, residual=None):
+    """``F.dropout(act(bn(z)), p, training) + residual`` as one autograd node on HIP kernels (csrc/bn_act.hip).
+
+    ``bn`` is a ``torch.nn.BatchNorm1d``: its weight, bias, running buffers, ``momentum``, ``eps`` and
+    ``num_batches_tracked`` are used and updated as the module's own forward would; ``training`` defaults to
+    ``bn.training``.  ``act`` is "none", "relu" or "leaky_relu" (``negative_slope``); ``residual`` has z's shape.
+    Dropout draws its seed from torch's CPU generator (``torch.manual_seed`` makes a run repeatable); its keep pattern
+    is this library's counter-based generator, not torch's.
+
+    Contiguous fp32 / bf16 CUDA matrices take the kernels.  Everything else -- CPU tensors, other dtypes or shapes,
+    ``affine=False`` or ``track_running_stats=False`` modules -- runs the plain torch composition.  Double backward
+    through the kernel path is not supported."""
+    if act not in _BN_ACTS:
+        raise ValueError(f"batch_norm_act: act must be one of {sorted(_BN_ACTS)}, got {act!r}")
+    training = bn.training if training is None else bool(training)
+    ok = lambda t: (t.is_cuda and t.dim() == 2 and t.is_contiguous() and t.dtype in (torch.float32, torch.bfloat16))
+    fused = (isinstance(bn, torch.nn.BatchNorm1d) and bn.affine and bn.track_running_stats and ok(z)
+             and z.size(1) == bn.num_features and (training or z.size(0) > 0) and 0.0 <= p < 1.0
+             and bn.weight.dtype == torch.float32 and bn.weight.is_cuda and bn.weight.device == z.device
+             and (residual is None or (ok(residual) and residual.shape == z.shape and residual.device == z.device)))
+    if not fused:
+        return _bn_act_torch(z, bn, act, negative_slope, p, training, residual)
+    return _BatchNormAct.apply(z, bn.weight, bn.bias, residual, bn, act, negative_slope, p, training)
+
+
 class _TallLinear(torch.autograd.Function):
     """y = a @ w.T for a very tall ``a`` ([T, K], T ~ 1e5) and a small ``w`` ([N, K]).
 
@@ -929,11 +1038,13 @@ class GINConv(torch.nn.Module):
     ``forward(x, adj_t, size)`` with a single ``x`` (a matrix, TableRows or RowRefs) takes the first size[1] rows
     as the targets (the MFG contract)."""
 
-    def __init__(self, nn, eps=0., train_eps=False):
+    def __init__(self, nn, eps=0., train_eps=False, fused_norm=False):
         super().__init__()
         if train_eps:
             raise NotImplementedError("the reference models use GINConv with a fixed eps (train_eps=False)")
         self.nn = nn
+        # fused_norm: nn is _gin_mlp's Sequential and its BatchNorm1d + ReLU run as batch_norm_act
+        self.fused_norm = fused_norm
         self.initial_eps = eps
         self.register_buffer("eps", torch.empty(1))
         self._scale_key = self._scale_val = None
@@ -972,6 +1083,9 @@ class GINConv(torch.nn.Module):
         else:                                                               # a foreign target matrix
             h = _SumAggregate.apply(x, rowptr, col, T, 0.0)
             h = h + (1 + self.eps) * x_target.to(h.dtype)
+        if self.fused_norm:
+            h = batch_norm_act(self.nn[0](h), self.nn[1], act="relu")
+            return F.relu(self.nn[3](h))
         return self.nn(h)
 
 
@@ -982,17 +1096,19 @@ def _gin_mlp(d_in, d_hidden):
 
 class GIN(torch.nn.Module):
     """``num_layers`` GINConv (in -> hidden, then hidden -> hidden, the last one included), then lin1, ReLU, dropout,
-    lin2, log_softmax.  The first layer reads a TableRows / RowRefs input in place."""
+    lin2, log_softmax.  The first layer reads a TableRows / RowRefs input in place.  ``fused_norm=True`` runs every
+    conv's BatchNorm1d + ReLU as ``batch_norm_act`` (same modules, same state dict)."""
 
-    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, dropout=0.5):
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, dropout=0.5, fused_norm=False):
         super().__init__()
         self.num_layers = num_layers
         self.hidden_channels = hidden_channels
         self.dropout = dropout
+        self.fused_norm = fused_norm
         self.convs = torch.nn.ModuleList()
-        self.convs.append(GINConv(_gin_mlp(in_channels, hidden_channels)))
+        self.convs.append(GINConv(_gin_mlp(in_channels, hidden_channels), fused_norm=fused_norm))
         for _ in range(num_layers - 1):
-            self.convs.append(GINConv(_gin_mlp(hidden_channels, hidden_channels)))
+            self.convs.append(GINConv(_gin_mlp(hidden_channels, hidden_channels), fused_norm=fused_norm))
         self.lin1 = torch.nn.Linear(hidden_channels, hidden_channels)
         self.lin2 = torch.nn.Linear(hidden_channels, out_channels)
         self.reset_parameters()
@@ -1061,13 +1177,16 @@ def _dropout(x, p, training):
 class SAGEResInception(torch.nn.Module):
     """SAGEConv layers (in -> hidden, then hidden -> hidden: the last one outputs hidden too), each followed by
     BatchNorm1d, leaky_relu and dropout, with a residual (Linear for the first layer, identity after); the input
-    and every layer's rows of the final targets are concatenated into a two-Linear MLP head."""
+    and every layer's rows of the final targets are concatenated into a two-Linear MLP head.  ``fused_norm=True`` runs
+    each layer's BatchNorm1d, leaky_relu, dropout and residual add as ``batch_norm_act`` (same modules, same state
+    dict; the dropouts of the conv's inputs stay torch's)."""
 
-    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, dropout=0.1):
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, dropout=0.1, fused_norm=False):
         super().__init__()
         self.num_layers = num_layers
         self.hidden_channels = hidden_channels
         self.dropout = dropout
+        self.fused_norm = fused_norm
         self.convs = torch.nn.ModuleList()
         self.bns = torch.nn.ModuleList()
         self.res_linears = torch.nn.ModuleList()
@@ -1101,10 +1220,13 @@ class SAGEResInception(torch.nn.Module):
         for i, (adj_t, _e_id, size) in enumerate(adjs):
             x_target = x[:size[1]]
             h = self.convs[i]((_dropout(x, p, tr), _dropout(x_target, p, tr)), adj_t)
-            h = _dropout(F.leaky_relu(self.bns[i](h)), p, tr)
             # the reference stores the view h[:end_size] and then adds the residual to h IN PLACE, which writes through
             # the view: what is concatenated are the rows after the residual add
-            x = h + self.res_linears[i](x_target)
+            if self.fused_norm:
+                x = batch_norm_act(h, self.bns[i], act="leaky_relu", p=p, residual=self.res_linears[i](x_target))
+            else:
+                h = _dropout(F.leaky_relu(self.bns[i](h)), p, tr)
+                x = h + self.res_linears[i](x_target)
             collect.append(x[:end_size])
         return torch.log_softmax(self.mlp(torch.cat(collect, -1)), dim=-1)
 
