@@ -854,7 +854,8 @@ spp_status spp_csr_sum_backward_gather(const int64_t* rowptr_dev, const int64_t*
  * ------------------------------------------------------------------------- */
 enum { SPP_ELEM_F32 = 0, SPP_ELEM_F16 = 1, SPP_ELEM_BF16 = 2, SPP_ELEM_FP8_E4M3 = 3 /* spp_agg_forward_fp8, spp_exchange_cfg.x_elem */ };
 enum { SPP_AGG_DENSE = 0, SPP_AGG_TABLE = 1, SPP_AGG_ROWS = 2 };
-enum { SPP_AGG_MEAN = 0, SPP_AGG_OPERAND = 1, SPP_AGG_OPERAND_ACT = 2, SPP_AGG_SUM = 3 };
+enum { SPP_AGG_MEAN = 0, SPP_AGG_OPERAND = 1, SPP_AGG_OPERAND_ACT = 2, SPP_AGG_SUM = 3,
+       SPP_AGG_MAX = 4, SPP_AGG_MAX_OPERAND = 5 /* spp_graph_agg_forward / _fp8 only (f3g); training: spp_agg_max_forward, f3q */ };
 enum { SPP_AGG_SCATTER = 0, SPP_AGG_GATHER = 1 };
 
 typedef struct spp_agg_fwd_desc {
@@ -945,6 +946,13 @@ spp_status spp_agg_forward_fp8(const spp_agg_fwd_desc* desc, const int8_t* scale
  *     the result of a row depends on nothing else -- not the grid, the slab, or the other rows of the call -- and no
  *       atomic touches the output.
  *
+ *   The maximum (f3q): epilogue SPP_AGG_MAX gives out [T, F] = the element-wise maximum over the row, SPP_AGG_MAX_OPERAND
+ *     [T, 2F] = [max | x[target]], by the comparison rule of spp_agg_max_forward: the best starts as the row's first entry,
+ *     a later entry replaces it only if !(v <= best) and the best is no NaN; an empty row gives 0.  A long row's chunk
+ *     maxima are combined by the same rule in chunk order.  Nothing is rounded before the store, so the result equals
+ *     spp_agg_max_forward's on the same row bit for bit for EVERY row length.  spp_graph_agg_forward and
+ *     spp_graph_agg_forward_fp8 take these two values; the entries over parts (f3j) refuse them.
+ *
  *   Ids that leave the graph: a col entry outside [0, x_rows) reads row 0 (the rule of SPP_AGG_TABLE: no fault, no
  *   error); a target id outside [0, x_rows) gives an output row of zeros.  A slab that leaves [0, x_rows] is refused.
  *   Workspace: spp_graph_agg_workspace_bytes(num_targets) bytes, 16-byte aligned, the caller's; its contents mean nothing
@@ -956,7 +964,7 @@ spp_status spp_agg_forward_fp8(const spp_agg_fwd_desc* desc, const int8_t* scale
  *   misaligned or too small workspace.  (The row sources SPP_AGG_TABLE / SPP_AGG_ROWS do not exist here: x IS the table.)
  * ------------------------------------------------------------------------- */
 typedef struct spp_graph_agg_desc {
-  int32_t epilogue;         /* SPP_AGG_MEAN / _OPERAND / _SUM */
+  int32_t epilogue;         /* SPP_AGG_MEAN / _OPERAND / _SUM / _MAX / _MAX_OPERAND */
   int32_t x_elem;           /* SPP_ELEM_F32 / _F16 / _BF16 (SPP_ELEM_FP8_E4M3: spp_graph_agg_forward_fp8 only, f3o) */
   int32_t out_elem;         /* SPP_ELEM_F32 / SPP_ELEM_BF16 */
   int32_t reserved;
@@ -1429,6 +1437,80 @@ int64_t spp_bn_act_slab_rows(void);
 int64_t spp_bn_act_workspace_bytes(int64_t n, int64_t C);
 spp_status spp_bn_act_forward(const spp_bn_act_desc* desc, void* stream);
 spp_status spp_bn_act_backward(const spp_bn_act_desc* desc, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * f3q  MAX aggregation over an MFG hop's CSR: the message passing of SAGEConv(aggr="max"), forward and backward, with
+ *      descriptors of its own (spp_agg_forward / spp_agg_backward accept what they accepted).
+ *
+ *   spp_agg_max_forward, for every target t < T and column c < F:
+ *        out[t,c] = max over k in [rowptr[t], rowptr[t+1]) of x_row(col[k])[c]
+ *        arg[t,c] = col[k*] as int32 (the batch-local source row), k* the FIRST entry in CSR order that attains out[t,c]
+ *      an empty row gives out = 0 and arg = -1 (the fill of PyG's scatter-max).
+ *      Comparison rule (the one of spp_classify_rows): the best starts as the row's FIRST entry -- not 0, not -FLT_MAX --
+ *      and a later entry v replaces it only if !(v <= best) and best is not a NaN.  So the first NaN wins and stays (as
+ *      torch.amax propagates it), otherwise the first strict maximum wins, and -0.0 and +0.0 tie: the earlier one stays.
+ *      No arithmetic touches a value, so the result does not depend on how a row is cut or in which order its pieces
+ *      are combined by the same rule in CSR order: it is the bits of one of the row's entries.
+ *      Row sources: `source` SPP_AGG_DENSE / _TABLE / _ROWS with x_dev, x_stride_elems, x_rows and n_id_dev exactly as
+ *      in spp_agg_fwd_desc, the rule that a TABLE id outside [0, x_rows) reads row 0 included (arg still names the batch
+ *      row).  x_elem fp32 / fp16 / bf16, or SPP_ELEM_FP8_E4M3 (DENSE / TABLE) with the per-column exponents
+ *      scale_log2_dev (f3c; a load returns the exact v, and the maximum is taken over v).  out_elem fp32 / bf16; a bf16
+ *      output rounds each stored element once (an fp16 / bf16 / e4m3 input's maximum is unchanged by it only where it
+ *      fits).  concat_target != 0: out is [T, 2F] = [max | x_target], x_target = batch row t, as SPP_AGG_OPERAND.
+ *      arg_dev: int32 [T, F] dense, or NULL (inference, no gradient): then no argmax is written, out is the same.
+ *      The vector form (four columns per lane) runs when F % 4 == 0 and x's rows, out's rows and arg are aligned to 4
+ *      elements (fp8: exponents to 4 bytes); anything else runs one column per lane with the same result.  Lanes as in
+ *      the mean's kernel: LPR lanes share a target, two independent rows are in flight.
+ *
+ *   spp_agg_max_backward: grad_x [S, F] dense is written COMPLETELY: zero, then grad_x[arg[t,c], c] += g[t,c] for every
+ *      arg[t,c] >= 0 by fp32 atomics (T * F of them, not E * F; an arg outside [0, S) is skipped), and with concat_target
+ *      (g is [T, 2F]) rows t < T start from g[t, F + c] instead of zero.  grad_elem, out_elem fp32 / bf16.  The atomics
+ *      run in an fp32 buffer: grad_x itself when out_elem is fp32, else the workspace (4 * S * F bytes, 16-byte
+ *      aligned), rounded once into grad_x by a last pass.
+ *
+ *   Refused with SPP_ERR_INVALID before anything is enqueued, in a message that names the entry: a NULL descriptor; an
+ *   unknown source or element code; fp8 rows with SPP_AGG_ROWS or without exponents; negative T, F or S, S < T, T * F
+ *   or S * F beyond 2^62, S beyond 2^31 (arg is int32); a stride smaller than its row; a NULL required pointer (rowptr,
+ *   col, out, x or n_id as the source needs; arg, grad_out, grad_x backward); an out, arg, grad or workspace pointer not
+ *   aligned to its element; a missing or too small workspace.  T == 0 or F == 0: SPP_OK (backward still zeroes grad_x).
+ * ------------------------------------------------------------------------- */
+typedef struct spp_agg_max_fwd_desc {
+  int32_t source;           /* SPP_AGG_DENSE / _TABLE / _ROWS */
+  int32_t x_elem;           /* spp_elem of x's rows, SPP_ELEM_FP8_E4M3 included */
+  int32_t out_elem;         /* SPP_ELEM_F32 / SPP_ELEM_BF16 */
+  int32_t concat_target;    /* != 0: out is [T, 2F] = [max | x_target] */
+  const int64_t* rowptr_dev;
+  const int64_t* col_dev;
+  int64_t num_targets;
+  const void* x_dev;        /* DENSE: the batch's matrix; TABLE: the feature table; ROWS: unused */
+  int64_t x_stride_elems;   /* DENSE / TABLE */
+  int64_t x_rows;           /* TABLE: the table's rows */
+  const int64_t* n_id_dev;  /* TABLE: the batch's node ids; ROWS: the row addresses */
+  const int8_t* scale_log2_dev; /* fp8 rows: int8 [F] */
+  int64_t F;
+  void* out_dev;
+  int64_t out_stride_elems; /* 0 = dense */
+  int32_t* arg_dev;         /* int32 [T, F] dense, or NULL */
+} spp_agg_max_fwd_desc;
+
+typedef struct spp_agg_max_bwd_desc {
+  int32_t grad_elem;        /* grad_out: SPP_ELEM_F32 / SPP_ELEM_BF16 */
+  int32_t out_elem;         /* grad_x:   SPP_ELEM_F32 / SPP_ELEM_BF16 */
+  int32_t concat_target;    /* != 0: grad_out is [T, 2F] */
+  int32_t reserved;
+  const int32_t* arg_dev;   /* int32 [T, F] dense: the forward's */
+  int64_t num_targets;
+  int64_t num_sources;
+  const void* grad_out_dev;
+  int64_t grad_out_stride_elems; /* 0 = dense (F, or 2F with concat_target) */
+  int64_t F;
+  void* grad_x_dev;         /* [S, F] dense */
+  void* workspace_dev;      /* out_elem != fp32: 4 * S * F bytes */
+  int64_t workspace_bytes;
+} spp_agg_max_bwd_desc;
+
+spp_status spp_agg_max_forward(const spp_agg_max_fwd_desc* desc, void* stream);
+spp_status spp_agg_max_backward(const spp_agg_max_bwd_desc* desc, void* stream);
 
 #ifdef __cplusplus
 }

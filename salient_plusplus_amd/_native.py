@@ -64,6 +64,7 @@ SPP_ELEM_FP8_E4M3 = 3            # spp_agg_forward_fp8, spp_graph_agg_*_forward_
 SPP_AGG_DENSE, SPP_AGG_TABLE, SPP_AGG_ROWS = 0, 1, 2
 SPP_AGG_MEAN, SPP_AGG_OPERAND, SPP_AGG_OPERAND_ACT, SPP_AGG_SUM = 0, 1, 2, 3
 SPP_AGG_SCATTER, SPP_AGG_GATHER = 0, 1
+SPP_AGG_MAX, SPP_AGG_MAX_OPERAND = 4, 5   # spp_graph_agg_forward / _fp8 only (spp_agg_max_forward has its own descriptor)
 
 
 class AggFwdDesc(C.Structure):
@@ -79,6 +80,21 @@ class AggBwdDesc(C.Structure):
                 ("num_edges", i64), ("grad_out_dev", p), ("grad_out_stride_elems", i64), ("F", i64),
                 ("grad_x_dev", p), ("z_dev", p), ("self_scale", C.c_float), ("p", C.c_float), ("training", i32),
                 ("reserved2", i32), ("seed", C.c_uint64)]
+
+
+class AggMaxFwdDesc(C.Structure):
+    """spp_agg_max_fwd_desc: out = max over the row (first occurrence in arg), optionally [max | x_target]"""
+    _fields_ = [("source", i32), ("x_elem", i32), ("out_elem", i32), ("concat_target", i32), ("rowptr_dev", p),
+                ("col_dev", p), ("num_targets", i64), ("x_dev", p), ("x_stride_elems", i64), ("x_rows", i64),
+                ("n_id_dev", p), ("scale_log2_dev", p), ("F", i64), ("out_dev", p), ("out_stride_elems", i64),
+                ("arg_dev", p)]
+
+
+class AggMaxBwdDesc(C.Structure):
+    """spp_agg_max_bwd_desc: grad_x[arg[t, c], c] += g[t, c] (+ the target half with concat_target)"""
+    _fields_ = [("grad_elem", i32), ("out_elem", i32), ("concat_target", i32), ("reserved", i32), ("arg_dev", p),
+                ("num_targets", i64), ("num_sources", i64), ("grad_out_dev", p), ("grad_out_stride_elems", i64),
+                ("F", i64), ("grad_x_dev", p), ("workspace_dev", p), ("workspace_bytes", i64)]
 
 
 class GraphAggDesc(C.Structure):
@@ -297,6 +313,8 @@ SIGNATURES = {
     "spp_bn_act_workspace_bytes": (i64, [i64, i64]),
     "spp_bn_act_forward": (C.c_int, [C.POINTER(BnActDesc), p]),
     "spp_bn_act_backward": (C.c_int, [C.POINTER(BnActDesc), p]),
+    "spp_agg_max_forward": (C.c_int, [C.POINTER(AggMaxFwdDesc), p]),
+    "spp_agg_max_backward": (C.c_int, [C.POINTER(AggMaxBwdDesc), p]),
 }
 SPP_COMM_ID_BYTES = 128
 SPP_IPC_HANDLE_BYTES = 64

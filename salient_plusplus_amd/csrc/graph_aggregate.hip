@@ -26,6 +26,11 @@
 // v = float32(code) * 2^e -- both steps exact -- so everything behind the load is the fp32 rows' arithmetic on v: same
 // order, same bits as over the table dequantised to fp32.  The exponents ride with the row source (Fp8NodeRows /
 // Fp8PartRows: new instantiations, no existing kernel's arguments change).
+//
+// f3q: the MAXIMUM over the row instead of its sum (SPP_AGG_MAX / SPP_AGG_MAX_OPERAND; one matrix only, not the parts):
+// kMax instantiations of the same two kernels.  The best starts as the first entry and a later one replaces it by the
+// rule of spp_agg_max_forward; a long row's chunk maxima are combined by that rule in chunk order.  Nothing is rounded, so
+// the result is the bits of spp_agg_max_forward on the same row for EVERY row length.
 #include "graph_rows.hip.h"
 
 namespace spp {
@@ -36,7 +41,7 @@ using namespace graph_rows;
 constexpr int64_t kGraphChunk = 64;           // C
 
 struct Args : Targets {
-  int32_t epilogue;     // SPP_AGG_MEAN / _OPERAND / _SUM
+  int32_t epilogue;     // SPP_AGG_MEAN / _OPERAND / _SUM; kMax kernels: SPP_AGG_MAX / _MAX_OPERAND
   float self_scale;
   int lpr_log2;
   LongRows long_rows;
@@ -147,13 +152,51 @@ __device__ __forceinline__ typename Piece<VEC4>::type sum_entries(const Rows& ro
   return acc;
 }
 
+// the comparison rule of the maximum (include/spp.h f3q): v, a LATER value, replaces the best only if !(v <= best) and
+// the best is not a NaN
+__device__ __forceinline__ void take_max(float& best, float v) { best = (!(v <= best) && best == best) ? v : best; }
+__device__ __forceinline__ void take_max(f4& best, f4 v) {
+  take_max(best.x, v.x);
+  take_max(best.y, v.y);
+  take_max(best.z, v.z);
+  take_max(best.w, v.w);
+}
+
+// columns c.. of the entries [b, e): their maximum, from the first entry on in CSR order (an empty range gives zero);
+// two rows are in flight, as in k_agg_max_fwd
+template <typename Rows, bool VEC4, class Scale>
+__device__ __forceinline__ typename Piece<VEC4>::type max_entries(const Rows& row, const int64_t* __restrict__ col,
+                                                                  int64_t b, int64_t e, int64_t c, const Scale& sc) {
+  using P = Piece<VEC4>;
+  if (b >= e) return P::zero();
+  typename P::type best = load_piece<P>(row(col[b]) + c, sc);
+  int64_t k = b + 1;
+  for (; k + 1 < e; k += 2) {
+    const int64_t j0 = col[k], j1 = col[k + 1];
+    const auto v0 = load_piece<P>(row(j0) + c, sc), v1 = load_piece<P>(row(j1) + c, sc);
+    take_max(best, v0);
+    take_max(best, v1);
+  }
+  if (k < e) take_max(best, load_piece<P>(row(col[k]) + c, sc));
+  return best;
+}
+
+template <typename Rows, bool VEC4, bool kMax, class Scale>
+__device__ __forceinline__ typename Piece<VEC4>::type reduce_entries(const Rows& row, const int64_t* __restrict__ col,
+                                                                     int64_t b, int64_t e, int64_t c, const Scale& sc) {
+  if constexpr (kMax) return max_entries<Rows, VEC4>(row, col, b, e, c, sc);
+  else return sum_entries<Rows, VEC4>(row, col, b, e, c, sc);
+}
+
 // what the sum of node t's row becomes, columns c.. of output row o (own: node t's row of x, NULL for a target id
 // outside the graph, whose output row is all zeros)
-template <typename Tin, typename Tout, bool VEC4, class Scale>
+template <typename Tin, typename Tout, bool VEC4, bool kMax, class Scale>
 __device__ __forceinline__ void finish(const Args& a, typename Piece<VEC4>::type acc, int64_t deg, const Tin* own,
                                        Tout* o, int64_t c, const Scale& sc) {
   using P = Piece<VEC4>;
-  if (a.epilogue == SPP_AGG_SUM) {
+  if constexpr (kMax) {  // the maximum as it is; [max | x[target]] for the operand
+    if (a.epilogue == SPP_AGG_MAX_OPERAND) P::store(o + a.F + c, own ? load_piece<P>(own + c, sc) : P::zero());
+  } else if (a.epilogue == SPP_AGG_SUM) {
     if (a.self_scale != 0.f && own) acc = P::fma(a.self_scale, load_piece<P>(own + c, sc), acc);
   } else {
     acc = P::scaled(acc, 1.0f / (float)(deg > 0 ? deg : 1));
@@ -162,7 +205,7 @@ __device__ __forceinline__ void finish(const Args& a, typename Piece<VEC4>::type
   P::store(o + c, acc);
 }
 
-template <typename Rows, typename Tout, bool VEC4>
+template <typename Rows, typename Tout, bool VEC4, bool kMax>
 __global__ __launch_bounds__(kNT) void k_graph_agg_rows(typename Rows::Src src, Tout* __restrict__ out, Args a) {
   using P = Piece<VEC4>;
   using Tin = typename Rows::elem;
@@ -182,11 +225,11 @@ __global__ __launch_bounds__(kNT) void k_graph_agg_rows(typename Rows::Src src, 
   Tout* o = out + i * a.out_stride;
   for (int64_t c = (int64_t)lane * P::kWidth; c < a.F; c += (int64_t)lpr * P::kWidth) {
     const auto sc = row.cols(c);
-    finish<Tin, Tout, VEC4>(a, sum_entries<Rows, VEC4>(row, a.col, b, e, c, sc), e - b, own, o, c, sc);
+    finish<Tin, Tout, VEC4, kMax>(a, reduce_entries<Rows, VEC4, kMax>(row, a.col, b, e, c, sc), e - b, own, o, c, sc);
   }
 }
 
-template <typename Rows, typename Tout, bool VEC4>
+template <typename Rows, typename Tout, bool VEC4, bool kMax>
 __global__ __launch_bounds__(kNT) void k_graph_agg_long(typename Rows::Src src, Tout* __restrict__ out, Args a) {
   using P = Piece<VEC4>;
   using piece = typename P::type;
@@ -215,16 +258,21 @@ __global__ __launch_bounds__(kNT) void k_graph_agg_long(typename Rows::Src src, 
         piece p = P::zero();
         if (active && j < chunks) {
           const int64_t cb = b + j * kGraphChunk;
-          p = sum_entries<Rows, VEC4>(row, a.col, cb, std::min<int64_t>(e, cb + kGraphChunk), c, sc);
+          p = reduce_entries<Rows, VEC4, kMax>(row, a.col, cb, std::min<int64_t>(e, cb + kGraphChunk), c, sc);
         }
         part[round & 1][threadIdx.x] = p;
         __syncthreads();
         if (grp == 0) {
           const int m = (int)std::min<int64_t>(groups, chunks - j0);
-          for (int g = 0; g < m; ++g) P::add(total, part[round & 1][(g << a.lpr_log2) + lane]);
+          for (int g = 0; g < m; ++g) {
+            const piece q = part[round & 1][(g << a.lpr_log2) + lane];
+            if constexpr (!kMax) P::add(total, q);
+            else if (j0 == 0 && g == 0) total = q;  // (the maximum starts from the first chunk's, not from zero)
+            else take_max(total, q);
+          }
         }
       }
-      if (grp == 0 && active) finish<Tin, Tout, VEC4>(a, total, e - b, row(t), o, c, sc);
+      if (grp == 0 && active) finish<Tin, Tout, VEC4, kMax>(a, total, e - b, row(t), o, c, sc);
     }
   }
 }
@@ -241,10 +289,10 @@ extern "C" int64_t spp_graph_agg_workspace_bytes(int64_t num_targets) { return w
 
 namespace {
 
-template <typename Rows, typename Tout, bool V>
+template <typename Rows, typename Tout, bool V, bool kMax = false>
 void launch(const Launch& l, const typename Rows::Src& src, void* out, const Args& a, hipStream_t st) {
-  hipLaunchKernelGGL((k_graph_agg_rows<Rows, Tout, V>), dim3(l.grid), dim3(kNT), 0, st, src, static_cast<Tout*>(out), a);
-  hipLaunchKernelGGL((k_graph_agg_long<Rows, Tout, V>), dim3(l.long_grid), dim3(kNT), 0, st, src, static_cast<Tout*>(out), a);
+  hipLaunchKernelGGL((k_graph_agg_rows<Rows, Tout, V, kMax>), dim3(l.grid), dim3(kNT), 0, st, src, static_cast<Tout*>(out), a);
+  hipLaunchKernelGGL((k_graph_agg_long<Rows, Tout, V, kMax>), dim3(l.long_grid), dim3(kNT), 0, st, src, static_cast<Tout*>(out), a);
 }
 
 // what the four entries share; exactly one of x / parts is given.  scale_log2 (the _fp8 entries; NULL elsewhere): the
@@ -252,8 +300,10 @@ void launch(const Launch& l, const typename Rows::Src& src, void* out, const Arg
 spp_status forward(const char* who, const Common& d, int32_t epilogue, float self_scale, const void* x_dev,
                    const Parts* parts, const int8_t* scale_log2, bool fp8, void* workspace_dev, int64_t workspace_bytes,
                    void* stream) {
-  SPP_REQUIRE(epilogue == SPP_AGG_MEAN || epilogue == SPP_AGG_OPERAND || epilogue == SPP_AGG_SUM,
-              "%s: epilogue %d (the mean, the operand and the sum; no activation on load)", who, (int)epilogue);
+  const bool max = epilogue == SPP_AGG_MAX || epilogue == SPP_AGG_MAX_OPERAND;
+  SPP_REQUIRE(epilogue == SPP_AGG_MEAN || epilogue == SPP_AGG_OPERAND || epilogue == SPP_AGG_SUM || (max && !parts),
+              "%s: epilogue %d (the mean, the operand and the sum; no activation on load%s)", who, (int)epilogue,
+              parts ? "; the maximum is not built over parts" : "; the maximum and its operand");
   if (fp8) {
     SPP_REQUIRE(d.x_elem == SPP_ELEM_FP8_E4M3,
                 "%s: x_elem %d: this entry reads an fp8 table in place (SPP_ELEM_FP8_E4M3); other rows go to the entry without _fp8",
@@ -261,7 +311,7 @@ spp_status forward(const char* who, const Common& d, int32_t epilogue, float sel
     SPP_REQUIRE(d.F % 16 == 0, "%s: F (%lld) must be a multiple of 16 (fp8 rows, include/spp.h f3c)", who, (long long)d.F);
   }
   Launch l;
-  SPP_TRY(check_common(who, d, epilogue == SPP_AGG_OPERAND ? 2 * d.F : d.F, d.F, parts ? parts->base[0] : &x_dev,
+  SPP_TRY(check_common(who, d, epilogue == SPP_AGG_OPERAND || epilogue == SPP_AGG_MAX_OPERAND ? 2 * d.F : d.F, d.F, parts ? parts->base[0] : &x_dev,
                        parts ? parts->n : 1, true, workspace_dev, workspace_bytes, &l, fp8));
   if (l.empty) return SPP_OK;
   if (fp8) {
@@ -277,6 +327,8 @@ spp_status forward(const char* who, const Common& d, int32_t epilogue, float sel
       using Tout = typename decltype(tout)::type;
       if (parts)
         launch<Fp8PartRows, Tout, true>(l, {part_table<1>(*parts, {d.x_stride}), scale_log2}, d.out, a, st);
+      else if (max)
+        launch<Fp8NodeRows, Tout, true, true>(l, {static_cast<const e4m3*>(x_dev), scale_log2}, d.out, a, st);
       else
         launch<Fp8NodeRows, Tout, true>(l, {static_cast<const e4m3*>(x_dev), scale_log2}, d.out, a, st);
     });
@@ -287,6 +339,8 @@ spp_status forward(const char* who, const Common& d, int32_t epilogue, float sel
       constexpr bool V = decltype(v)::value;
       if (parts)
         launch<PartRows<Tin>, Tout, V>(l, part_table<1>(*parts, {d.x_stride * (int64_t)sizeof(Tin)}), d.out, a, st);
+      else if (max)
+        launch<NodeRows<Tin>, Tout, V, true>(l, static_cast<const Tin*>(x_dev), d.out, a, st);
       else
         launch<NodeRows<Tin>, Tout, V>(l, static_cast<const Tin*>(x_dev), d.out, a, st);
     });

@@ -39,7 +39,12 @@ from .fast_sampler import P2PPeers, RowRefs, TableRows, _common_stride, _row_str
 from .fp8 import Fp8Features
 from .models import _ELEM, _p, _stream
 
-_EPILOGUES = {"mean": nat.SPP_AGG_MEAN, "operand": nat.SPP_AGG_OPERAND, "sum": nat.SPP_AGG_SUM}
+_EPILOGUES = {"mean": nat.SPP_AGG_MEAN, "operand": nat.SPP_AGG_OPERAND, "sum": nat.SPP_AGG_SUM,
+              "max": nat.SPP_AGG_MAX, "max_operand": nat.SPP_AGG_MAX_OPERAND}
+_MAX_EPILOGUES = ("max", "max_operand")                  # one resident matrix only: the entries over parts refuse them
+_WIDE_EPILOGUES = ("operand", "max_operand")             # [T, 2F] = [reduction | x[target]]
+_MAX_OVER_PARTS = ("max aggregation (aggr='max') is not built over a row-partitioned table: the parts kernels have no "
+                   "max instantiation yet; score the model on one device (layerwise_inference, evaluate, field_inference)")
 _OUT_DTYPES = (torch.float32, torch.bfloat16)
 
 
@@ -176,9 +181,17 @@ def _check_heads(what, heads, Fdim):
         raise ValueError(f"{what}: heads must be a positive int that divides F = {Fdim}, got {heads!r}")
 
 
-def _check_epilogue(what, epilogue):
+def _check_epilogue(what, epilogue, parts=False):
+    if parts and epilogue in _MAX_EPILOGUES:
+        raise NotImplementedError(f"{what}: epilogue {epilogue!r}: {_MAX_OVER_PARTS}")
     if epilogue not in _EPILOGUES:
-        raise ValueError(f"{what}: epilogue must be 'mean', 'operand' or 'sum', got {epilogue!r}")
+        raise ValueError(f"{what}: epilogue must be 'mean', 'operand', 'sum'{'' if parts else ', max or max_operand'}, "
+                         f"got {epilogue!r}")
+
+
+def _refuse_max_over_parts(what, model):
+    if getattr(model, "aggr", "mean") == "max":
+        raise NotImplementedError(f"{what}: {_MAX_OVER_PARTS}")
 
 
 def _check_fp32(what, name, t, shape, meaning):
@@ -408,8 +421,9 @@ def graph_aggregate(x, rowptr, col, *, row0=None, num_targets=None, target_ids=N
     place by ``spp_graph_agg_forward_fp8`` with the bits of the same call on its fp32 dequantisation; ``rowptr`` /
     ``col``: the graph's CSR (int64, global ids).  The targets are a slab, ``row0`` and ``num_targets`` (output row i is node
     row0 + i), or a list, ``target_ids`` (int64, any order, duplicates allowed).  ``epilogue``: "mean" [T, F],
-    "operand" [T, 2F] = [mean | x[target]] or "sum" [T, F] = self_scale * x[target] + sum.  fp32 sums; a bf16 output
-    is rounded once.  A ``col`` entry outside the graph reads row 0, a target id outside it gives a row of zeros.
+    "operand" [T, 2F] = [mean | x[target]], "sum" [T, F] = self_scale * x[target] + sum, "max" [T, F] = the element-wise
+    maximum over the row (the bits of ``models.max_aggregate`` for every row length; an empty row gives 0) or
+    "max_operand" [T, 2F] = [max | x[target]].  fp32 sums; a bf16 output is rounded once.  A ``col`` entry outside the graph reads row 0, a target id outside it gives a row of zeros.
 
     Forward only: no autograd node is registered and an input that requires grad is refused.  ``workspace``: a uint8
     CUDA tensor of at least ``graph_agg_workspace_bytes(T)`` bytes, reusable between calls on one stream; allocated
@@ -424,7 +438,7 @@ def graph_aggregate(x, rowptr, col, *, row0=None, num_targets=None, target_ids=N
     workspace = _on_device(what, "x, rowptr, col, target_ids and workspace", x.device,
                            [x.q if isinstance(x, Fp8Table) else x, rowptr, col, target_ids],
                            workspace, graph_agg_workspace_bytes, T)
-    out = torch.empty((T, 2 * Fdim if epilogue == "operand" else Fdim), dtype=out_dtype, device=x.device)
+    out = torch.empty((T, 2 * Fdim if epilogue in _WIDE_EPILOGUES else Fdim), dtype=out_dtype, device=x.device)
     return _agg_launch(x, rowptr, col, epilogue, self_scale, row0, target_ids, T, out, workspace)
 
 
@@ -444,11 +458,13 @@ def graph_aggregate_parts(parts, part_offsets, rowptr, col, *, row0=None, num_ta
     [T, F or 2F] matrix to write into (rows of a larger one allowed).  Nothing here maps memory or enables peer access,
     and nothing waits for the device."""
     what = "graph_aggregate_parts"
+    if epilogue in _MAX_EPILOGUES:
+        _check_epilogue(what, epilogue, parts=True)      # (refused whatever the parts are)
     off = _check_offsets(part_offsets, what)
     parts, scale_log2 = _fp8_parts(parts, what)
     *src, dev = _parts_source(parts, off, dtype, F, what, fp8=scale_log2 is not None)
     _check_graph(what, off[-1], rowptr, col, parts=True)
-    _check_epilogue(what, epilogue)
+    _check_epilogue(what, epilogue, parts=True)
     _check_out_dtype(what, out_dtype)
     row0, target_ids, T = _check_targets(what, off[-1], row0, num_targets, target_ids)
     width = 2 * src[3] if epilogue == "operand" else src[3]
@@ -915,7 +931,7 @@ def _sage_layer(conv, last, act_dtype):
         if bias is not None:
             Z = Z + bias.to(Z.dtype)
         return Z if last else torch.relu_(Z)             # the inter-layer ReLU; dropout is the identity in eval mode
-    return "operand", 0.0, fn
+    return "max_operand" if getattr(conv, "aggr", "mean") == "max" else "operand", 0.0, fn
 
 
 def _gin_layer(conv, amp):
@@ -991,7 +1007,7 @@ def _conv_layers(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None)
         if last:
             sink.open(place, rows, (model.lin2 if gin else conv.lin_l).out_features)
         for s, T, tids in _slabs(rows, step.ids, rows_per_slab):
-            A = torch.empty((T, cur.size(1) * (2 if epilogue == "operand" else 1)), dtype=act_dtype, device=dev)
+            A = torch.empty((T, cur.size(1) * (2 if epilogue in _WIDE_EPILOGUES else 1)), dtype=act_dtype, device=dev)
             place.aggregate(i, cur, epilogue, scale, s, tids, T, A, ws, step.graph)
             for r, n, tile in _row_tiles(A):
                 if last:
@@ -1627,6 +1643,7 @@ def _partitioned(what, names, model, x_local, rowptr, col, part_offsets, rank, p
     """the partitioned entries behind their model filters.  Every argument and model-shape check comes before ``peers``
     is touched, and the device is required last: a refused call publishes nothing and waits for nobody."""
     _check_model(model, what, names)
+    _refuse_max_over_parts(what, model)
     _check_matrix(x_local, what, "x_local", "the partitioned drivers do not carry fp8 partitions through peers.share yet "
                   "(graph_aggregate_parts reads them); dequantise the partition, or score the table on one device")
     off = _check_offsets(part_offsets, what)
@@ -1716,5 +1733,6 @@ def partitioned_layerwise_inference(model, x_local, rowptr, col, *, part_offsets
         raise NotImplementedError(f"{what}: {type(model).__name__} over a partitioned table is not scored by this entry "
                                   "(its layers need the long-row softmax / the fused layer tail over parts); SAGE and GIN "
                                   "are.  partitioned_inference scores all four models")
+    _refuse_max_over_parts(what, model)
     return _partitioned(what, "SAGE and GIN", model, x_local, rowptr, col, part_offsets, rank, peers, nodes,
                         rows_per_slab, act_dtype)

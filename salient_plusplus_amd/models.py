@@ -216,6 +216,112 @@ def mean_aggregate(x, rowptr, col, num_targets):
     return _MeanAggregate.apply(x, rowptr, col, num_targets, False)
 
 
+# ---- max aggregation (SAGEConv(aggr="max"); csrc/aggregate_max.hip, spp.h f3q) ----
+def _max_reference(x, rowptr, col, T):
+    """Plain torch restatement of spp_agg_max_forward on a dense x: (out fp32 [T, F], arg int32 [T, F]).  out[t, c] is
+    the maximum of column c over the rows x[col[k]] of row t, arg[t, c] the col entry of the FIRST k that attains it: the
+    first NaN if the column holds one (it propagates, as torch.amax), else the first of the equal maxima (-0.0 == +0.0:
+    the earlier stays).  An empty row gives 0 and -1."""
+    x = x.float()
+    Fdim = x.size(1)
+    out = torch.zeros((T, Fdim), dtype=torch.float32, device=x.device)
+    arg = torch.full((T, Fdim), -1, dtype=torch.int32, device=x.device)
+    ptr = rowptr.tolist()
+    for t in range(T):
+        b, e = ptr[t], ptr[t + 1]
+        if e <= b:
+            continue
+        idx = col[b:e]
+        rows = x[idx]                                                   # [d, F]
+        pos = torch.arange(e - b, device=x.device).unsqueeze(1).expand_as(rows)
+        nan = rows.isnan()
+        hit = torch.where(nan.any(0, keepdim=True), nan, rows == rows.amax(0, keepdim=True))
+        k = torch.where(hit, pos, e - b).amin(0)                        # the first hit of every column
+        out[t] = rows.gather(0, k.unsqueeze(0))[0]
+        arg[t] = idx[k].to(torch.int32)
+    return out, arg
+
+
+def _agg_max_forward(rowptr, col, T, x, out_dtype, concat, want_arg):
+    """spp_agg_max_forward over the row source x (see _rows): the new dense [T, F or 2F] fp32 / bf16 result and the
+    int32 [T, F] argmax (None unless want_arg)"""
+    src, exps = _rows(x)
+    Fdim = src["F"]
+    out = torch.empty((T, 2 * Fdim if concat else Fdim), dtype=out_dtype, device=rowptr.device)
+    arg = torch.empty((T, Fdim), dtype=torch.int32, device=rowptr.device) if want_arg else None
+    d = nat.AggMaxFwdDesc(out_elem=_ELEM[out_dtype], concat_target=int(bool(concat)), rowptr_dev=_p(rowptr),
+                          col_dev=_p(col), num_targets=T, scale_log2_dev=_p(exps), out_dev=_p(out), out_stride_elems=0,
+                          arg_dev=_p(arg), **src)
+    nat.check(nat.load().spp_agg_max_forward(C.byref(d), _stream()))
+    return out, arg
+
+
+class _MaxAggregate(torch.autograd.Function):
+    """out[t] = max_{e in row t} x[col[e]], element-wise (empty rows give 0, as PyG's max aggregation); with
+    ``concat_target`` the operand [max | x_target] of shape [T, 2F], x_target = x[:T], as _MeanAggregate's.  The
+    gradient of out[t, c] goes to the one source row the forward recorded (the first that attains the maximum)."""
+
+    @staticmethod
+    def forward(ctx, x, rowptr, col, num_targets, concat_target):
+        nat.require_device()
+        assert x.is_cuda and _readable(x), "fp16 / fp32 / bf16 / fp8 rows on the GPU"
+        if _is_fp8(x):
+            _no_input_grad(ctx, "max_aggregate")
+        out, arg = _agg_max_forward(rowptr, col, num_targets, x, torch.bfloat16 if amp_bf16() else torch.float32,
+                                    concat_target, ctx.needs_input_grad[0])
+        if arg is not None:
+            ctx.save_for_backward(arg)
+        ctx.shape = (x.size(0), x.size(1), num_targets)
+        ctx.in_dtype = x.dtype
+        ctx.concat = bool(concat_target)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        (arg,) = ctx.saved_tensors
+        S, Fdim, T = ctx.shape
+        g = _grad_in(grad_out)                           # bf16 / fp32 in, the input's dtype out (fp16 through fp32)
+        odt = ctx.in_dtype if ctx.in_dtype in (torch.float32, torch.bfloat16) else torch.float32
+        grad_x = torch.empty((S, Fdim), dtype=odt, device=g.device)
+        nbytes = 4 * S * Fdim if odt != torch.float32 else 0
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=g.device) if nbytes else None
+        d = nat.AggMaxBwdDesc(grad_elem=_ELEM[g.dtype], out_elem=_ELEM[odt], concat_target=int(ctx.concat), arg_dev=_p(arg),
+                              num_targets=T, num_sources=S, grad_out_dev=_p(g),
+                              grad_out_stride_elems=g.stride(0) if T > 1 else 0, F=Fdim, grad_x_dev=_p(grad_x),
+                              workspace_dev=_p(ws), workspace_bytes=nbytes)
+        nat.check(nat.load().spp_agg_max_backward(C.byref(d), _stream()))
+        return grad_x.to(ctx.in_dtype), None, None, None, None
+
+
+def _check_max_source(what, x):
+    """what the max kernels read, checked before any device call"""
+    m = x.table if isinstance(x, TableRows) else x
+    if isinstance(x, RowRefs) or isinstance(m, Fp8Features):
+        return
+    if not isinstance(m, torch.Tensor):
+        raise TypeError(f"{what}: x must be a tensor, a TableRows, a RowRefs or fp8 features, got {type(x).__name__}")
+    if m.dim() != 2 or m.dtype not in _ELEM:
+        raise ValueError(f"{what}: x must be a 2-D fp32 / fp16 / bf16 matrix, got {tuple(m.shape)} of {m.dtype}")
+
+
+def max_aggregate(x, rowptr, col, num_targets):
+    """The element-wise maximum over every target's neighbour rows, [num_targets, F] (an empty row gives 0); the
+    gradient goes to the first row that attains each maximum.  x: as mean_aggregate's."""
+    _check_max_source("max_aggregate", x)
+    return _MaxAggregate.apply(x, rowptr, col, num_targets, False)
+
+
+_SAGE_AGGRS = ("mean", "max")
+
+
+def _check_aggr(what, aggr):
+    if aggr not in _SAGE_AGGRS:
+        raise ValueError(f"{what}: aggr must be 'mean' or 'max', got {aggr!r}")
+    return aggr
+
+
 # ---- the training tail behind a GEMM: dropout(act(BatchNorm(z))) [+ residual]  (csrc/bn_act.hip, spp.h f3p) ----
 _BN_ACTS = {"none": nat.SPP_BN_ACT_NONE, "relu": nat.SPP_BN_ACT_RELU, "leaky_relu": nat.SPP_BN_ACT_LEAKY_RELU}
 
@@ -375,11 +481,13 @@ def init_weights(m):                                     # driver/models.py:12-1
 
 
 class SAGEConv(torch.nn.Module):
-    """torch_geometric.nn.SAGEConv(in, out, aggr='mean', root_weight=True, bias=...) on a bipartite
-    ((x, x_target), adj_t):  lin_l(mean_j x_j) + lin_r(x_target); only lin_l carries the bias."""
+    """torch_geometric.nn.SAGEConv(in, out, aggr='mean' | 'max', root_weight=True, bias=...) on a bipartite
+    ((x, x_target), adj_t):  lin_l(aggr_j x_j) + lin_r(x_target); only lin_l carries the bias.  ``aggr`` chooses the
+    neighbour reduction (the mean, or the element-wise maximum); the parameters are the same for both."""
 
-    def __init__(self, in_channels, out_channels, bias=True):
+    def __init__(self, in_channels, out_channels, bias=True, *, aggr="mean"):
         super().__init__()
+        self.aggr = _check_aggr("SAGEConv", aggr)
         self.lin_l = torch.nn.Linear(in_channels, out_channels, bias=bias)
         self.lin_r = torch.nn.Linear(in_channels, out_channels, bias=False)
 
@@ -390,33 +498,38 @@ class SAGEConv(torch.nn.Module):
     def forward(self, x_pair, adj_t):
         x, x_target = x_pair
         rowptr, col, _ = adj_t.csr()
-        if _is_fp8(x):                                   # fp8 rows, read in place: the targets are the first rows of x
+        aggregate = _MaxAggregate if self.aggr == "max" else _MeanAggregate
+        if _is_fp8(x) or isinstance(x, (TableRows, RowRefs)):   # rows read in place: the targets are the first rows of x
             if x_target is not None and x_target is not x:
                 raise RuntimeError("SAGEConv over fp8 rows: the targets are the first rows of x (pass (x, None))")
-            fused = _MeanAggregate.apply(x, rowptr, col, int(adj_t.sparse_sizes()[0]), True)
+            fused = aggregate.apply(x, rowptr, col, int(adj_t.sparse_sizes()[0]), True)
             out = _TallLinear.apply(fused, torch.cat([self.lin_l.weight, self.lin_r.weight], dim=1))
             return out if self.lin_l.bias is None else out + self.lin_l.bias
         # [mean_j x_j | x_target] @ [W_l | W_r]^T: one GEMM instead of two plus an add
         T = x_target.size(0)
         if x_target.data_ptr() == x.data_ptr() and x_target.size(1) == x.size(1) and x_target.stride() == x.stride():
-            fused = _MeanAggregate.apply(x, rowptr, col, T, True)           # x_target = x[:T] (the MFG contract)
+            fused = aggregate.apply(x, rowptr, col, T, True)                # x_target = x[:T] (the MFG contract)
         else:                                                               # a foreign target matrix
-            mean = _MeanAggregate.apply(x, rowptr, col, T, False)           # (bf16 under bf16 autocast)
+            mean = aggregate.apply(x, rowptr, col, T, False)                # (bf16 under bf16 autocast)
             fused = torch.cat([mean, x_target.to(mean.dtype)], dim=1)
         out = _TallLinear.apply(fused, torch.cat([self.lin_l.weight, self.lin_r.weight], dim=1))
         return out if self.lin_l.bias is None else out + self.lin_l.bias
 
 
 class SAGE(torch.nn.Module):
-    def __init__(self, in_channels, hidden_channels, out_channels, num_layers):
+    """``aggr="max"`` (keyword only) replaces every layer's mean by the element-wise maximum over the neighbours
+    (PyG's SAGEConv(aggr="max")); parameters and state-dict keys are those of the default."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, aggr="mean"):
         super().__init__()
+        self.aggr = _check_aggr("SAGE", aggr)
         self.num_layers = num_layers
         self.hidden_channels = hidden_channels
         self.convs = torch.nn.ModuleList()
-        self.convs.append(SAGEConv(in_channels, hidden_channels, bias=False))
+        self.convs.append(SAGEConv(in_channels, hidden_channels, bias=False, aggr=aggr))
         for _ in range(num_layers - 2):
-            self.convs.append(SAGEConv(hidden_channels, hidden_channels, bias=False))
-        self.convs.append(SAGEConv(hidden_channels, out_channels, bias=False))
+            self.convs.append(SAGEConv(hidden_channels, hidden_channels, bias=False, aggr=aggr))
+        self.convs.append(SAGEConv(hidden_channels, out_channels, bias=False, aggr=aggr))
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -427,6 +540,8 @@ class SAGE(torch.nn.Module):
     def forward(self, x, adjs):
         # the reference converts the whole feature matrix to fp32 first (models.py:43); the first
         # aggregation reads the fp16 rows directly instead (exact) and only the targets are converted
+        if self.aggr == "max":
+            return self._forward_max(x, adjs)
         if x.is_cuda and _SageStack.usable(self, x, adjs):
             hops = []
             for adj_t, _e_id, size in adjs:
@@ -447,6 +562,16 @@ class SAGE(torch.nn.Module):
             x = self.convs[i]((x, x_target), adj_t)
             if i != self.num_layers - 1:
                 x = relu_dropout(x, 0.5, self.training)       # F.relu + F.dropout(p=0.5) (models.py:47-48)
+        return torch.log_softmax(x, dim=-1)
+
+    def _forward_max(self, x, adjs):
+        """aggr="max", layer by layer: max_aggregate's operand [max | x_target], one tall GEMM, ReLU + dropout.  The
+        first layer reads a TableRows, a RowRefs or fp8 rows in place, as the mean's fused first layer does."""
+        for i, (adj_t, _e_id, size) in enumerate(adjs):
+            in_place = _is_fp8(x) or isinstance(x, (TableRows, RowRefs))
+            x = self.convs[i]((x, None if in_place else x[:size[1]]), adj_t)
+            if i != self.num_layers - 1:
+                x = relu_dropout(x, 0.5, self.training)
         return torch.log_softmax(x, dim=-1)
 
     @torch.no_grad()
