@@ -1512,6 +1512,134 @@ typedef struct spp_agg_max_bwd_desc {
 spp_status spp_agg_max_forward(const spp_agg_max_fwd_desc* desc, void* stream);
 spp_status spp_agg_max_backward(const spp_agg_max_bwd_desc* desc, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * f3r  EDGE-WEIGHTED sum aggregation over an MFG hop's CSR, one fp32 weight per entry: the message passing of GCNConv
+ *      and of any layer with importance-sampling, precomputed or learned edge weights.  Forward, input gradient, weight
+ *      gradient and PyG's gcn_norm, with descriptors of their own (spp_agg_forward / spp_agg_backward accept what they
+ *      accepted; SPP_ABI_VERSION stays 6).
+ *
+ *   spp_agg_weighted_forward, for every target t < T and column c < F:
+ *        acc = 0
+ *        for k in [rowptr[t], rowptr[t+1]), in CSR order, one entry at a time:  acc = fmaf(w[k], x_row(col[k])[c], acc)
+ *        if self_w_dev != NULL:                                                 acc = fmaf(self_w[t], x_row(t)[c], acc)
+ *        out[t,c] = acc                                   (an empty row without a self term gives 0)
+ *      Summation rule: exactly this fmaf chain in fp32, the self term LAST (as SPP_AGG_SUM's), so a row's result depends
+ *      on the row alone -- not on the grid, the other rows of the call, or how the kernel pairs the entries it loads.
+ *      Row sources: `source` SPP_AGG_DENSE / _TABLE / _ROWS with x_dev, x_stride_elems, x_rows and n_id_dev exactly as in
+ *      spp_agg_max_fwd_desc; a TABLE id outside [0, x_rows) reads row 0.  x_elem fp32 / fp16 / bf16 (read exactly).
+ *      SPP_ELEM_FP8_E4M3 rows are REFUSED.  w_dev fp32 [E] and self_w_dev fp32 [T] (may be NULL), 4-byte aligned.
+ *      out_elem fp32 / bf16, each stored element rounded once; out_stride_elems 0 = dense.  There is no operand
+ *      ([sum | x_target]) form.  The vector form (four columns per lane) runs when F % 4 == 0 and x's and out's rows are
+ *      aligned to 4 elements; anything else runs one column per lane with the same result.
+ *
+ *   spp_agg_weighted_backward writes grad_x [S, F] dense COMPLETELY:
+ *        grad_x[s,c] = sum over the entries k = (t, s) of w[k] * g[t,c]  +  (s < T and self_w ? self_w[s] * g[s,c] : 0)
+ *      as a gather over the transposed hop with edge ids, built in the workspace (count, scan, fill): one fp32 fmaf chain
+ *      per element, the self term last, no atomic on an accumulator.  The order of a source's entries in the chain is
+ *      the order the fill pass left them in, which is not fixed between runs.  g fp32 / bf16, grad_x fp32 / bf16
+ *      (rounded once); vector and scalar forms as in the forward.  Workspace: 16-byte aligned,
+ *      spp_agg_weighted_backward_workspace_bytes(T, S, E) bytes (-1 for sizes the entry refuses).
+ *
+ *   spp_agg_weighted_wgrad: the gradient of the weights, one dot product per entry, fp32:
+ *        grad_w[k]      = sum_c g[t,c] * x_row(col[k])[c]     for k in row t
+ *        grad_self_w[t] = sum_c g[t,c] * x_row(t)[c]          (only when grad_self_w_dev != NULL)
+ *      Row sources and x_elem as in the forward; g fp32 / bf16.  The lanes of a target keep their columns of g[t,:] in
+ *      registers over the row's entries, accumulate their columns in fp32 by fmaf in column order and reduce in a fixed
+ *      butterfly; one lane stores.  No atomics, no LDS: the result is the same bits in every run.
+ *
+ *   spp_gcn_norm: PyG's gcn_norm of the hop padded to [S, S] (its first T rows are the hop, the others are empty):
+ *        deg[i]  = fill + sum of row i's w  (w = 1 when w_dev is NULL) for i < T, = fill otherwise
+ *        dinv    = 1.0f / sqrtf(deg), 0 where that is inf
+ *        coef[k] = dinv[t] * w[k] * dinv[col[k]]          self_coef[t] = fill * dinv[t]^2
+ *      fill 1, 2 (`improved`) or 0 (no self loops).  Two passes: dinv over the targets into dinv_dev (fp32 [T], the
+ *      caller's: a workspace, or an output to keep), then the coefficients.  A source col[k] >= T has dinv = fill^-1/2
+ *      (0 for fill 0) without a read.  With T == S == N this is PyG's normalisation of the whole graph.
+ *      self_coef_dev may be NULL.
+ *
+ *   Refused with SPP_ERR_INVALID before anything is enqueued, in a message that names the entry: a NULL descriptor; an
+ *   unknown source, element code or fill; fp8 rows; negative T, F, S or E, S < T, T * F or S * F beyond 2^62, S or E
+ *   beyond 2^31 (backward); a stride smaller than its row; a NULL required pointer (SPP_AGG_ROWS without n_id_dev,
+ *   SPP_AGG_TABLE without ids or rows included); a pointer not aligned to its element; a missing, misaligned or too small
+ *   workspace (backward; gcn_norm: dinv_dev).  T == 0 or F == 0: SPP_OK (backward: S == 0 or F == 0; wgrad with F == 0
+ *   writes zeros).
+ * ------------------------------------------------------------------------- */
+typedef struct spp_agg_weighted_fwd_desc {
+  int32_t source;           /* SPP_AGG_DENSE / _TABLE / _ROWS */
+  int32_t x_elem;           /* SPP_ELEM_F32 / _F16 / _BF16 */
+  int32_t out_elem;         /* SPP_ELEM_F32 / SPP_ELEM_BF16 */
+  int32_t reserved;
+  const int64_t* rowptr_dev;
+  const int64_t* col_dev;
+  int64_t num_targets;
+  int64_t num_edges;
+  const void* x_dev;        /* DENSE: the batch's matrix; TABLE: the feature table; ROWS: unused */
+  int64_t x_stride_elems;   /* DENSE / TABLE */
+  int64_t x_rows;           /* TABLE: the table's rows */
+  const int64_t* n_id_dev;  /* TABLE: the batch's node ids; ROWS: the row addresses */
+  int64_t F;
+  const float* w_dev;       /* fp32 [E] */
+  const float* self_w_dev;  /* fp32 [T], or NULL */
+  void* out_dev;
+  int64_t out_stride_elems; /* 0 = dense */
+} spp_agg_weighted_fwd_desc;
+
+typedef struct spp_agg_weighted_bwd_desc {
+  int32_t grad_elem;        /* grad_out: SPP_ELEM_F32 / SPP_ELEM_BF16 */
+  int32_t out_elem;         /* grad_x:   SPP_ELEM_F32 / SPP_ELEM_BF16 */
+  const int64_t* rowptr_dev;
+  const int64_t* col_dev;
+  int64_t num_targets;
+  int64_t num_sources;
+  int64_t num_edges;
+  const void* grad_out_dev;
+  int64_t grad_out_stride_elems; /* 0 = dense */
+  int64_t F;
+  const float* w_dev;       /* fp32 [E] */
+  const float* self_w_dev;  /* fp32 [T], or NULL */
+  void* grad_x_dev;         /* [S, F] dense */
+} spp_agg_weighted_bwd_desc;
+
+typedef struct spp_agg_weighted_wgrad_desc {
+  int32_t source;           /* SPP_AGG_DENSE / _TABLE / _ROWS */
+  int32_t x_elem;           /* SPP_ELEM_F32 / _F16 / _BF16 */
+  int32_t grad_elem;        /* grad_out: SPP_ELEM_F32 / SPP_ELEM_BF16 */
+  int32_t reserved;
+  const int64_t* rowptr_dev;
+  const int64_t* col_dev;
+  int64_t num_targets;
+  int64_t num_edges;
+  const void* x_dev;
+  int64_t x_stride_elems;
+  int64_t x_rows;
+  const int64_t* n_id_dev;
+  int64_t F;
+  const void* grad_out_dev;
+  int64_t grad_out_stride_elems; /* 0 = dense */
+  float* grad_w_dev;        /* fp32 [E] */
+  float* grad_self_w_dev;   /* fp32 [T], or NULL */
+} spp_agg_weighted_wgrad_desc;
+
+typedef struct spp_gcn_norm_desc {
+  int32_t fill;             /* 1; 2 = improved; 0 = no self loops */
+  int32_t reserved;
+  const int64_t* rowptr_dev;
+  const int64_t* col_dev;
+  int64_t num_targets;
+  int64_t num_sources;
+  int64_t num_edges;
+  const float* w_dev;       /* fp32 [E], or NULL: ones */
+  float* dinv_dev;          /* fp32 [T]: the first pass's result */
+  float* coef_dev;          /* fp32 [E] */
+  float* self_coef_dev;     /* fp32 [T], or NULL */
+} spp_gcn_norm_desc;
+
+spp_status spp_agg_weighted_forward(const spp_agg_weighted_fwd_desc* desc, void* stream);
+int64_t spp_agg_weighted_backward_workspace_bytes(int64_t num_targets, int64_t num_sources, int64_t num_edges);
+spp_status spp_agg_weighted_backward(const spp_agg_weighted_bwd_desc* desc, void* workspace_dev, int64_t workspace_bytes,
+                                     void* stream);
+spp_status spp_agg_weighted_wgrad(const spp_agg_weighted_wgrad_desc* desc, void* stream);
+spp_status spp_gcn_norm(const spp_gcn_norm_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,6 +97,36 @@ class AggMaxBwdDesc(C.Structure):
                 ("F", i64), ("grad_x_dev", p), ("workspace_dev", p), ("workspace_bytes", i64)]
 
 
+class AggWeightedFwdDesc(C.Structure):
+    """spp_agg_weighted_fwd_desc: out[t] = sum_k w[k] * x[col[k]] (+ self_w[t] * x[t], last), one fmaf per entry"""
+    _fields_ = [("source", i32), ("x_elem", i32), ("out_elem", i32), ("reserved", i32), ("rowptr_dev", p),
+                ("col_dev", p), ("num_targets", i64), ("num_edges", i64), ("x_dev", p), ("x_stride_elems", i64),
+                ("x_rows", i64), ("n_id_dev", p), ("F", i64), ("w_dev", p), ("self_w_dev", p), ("out_dev", p),
+                ("out_stride_elems", i64)]
+
+
+class AggWeightedBwdDesc(C.Structure):
+    """spp_agg_weighted_bwd_desc: grad_x[s] = sum_{k = (t, s)} w[k] * g[t] (+ self_w[s] * g[s]), a gather"""
+    _fields_ = [("grad_elem", i32), ("out_elem", i32), ("rowptr_dev", p), ("col_dev", p), ("num_targets", i64),
+                ("num_sources", i64), ("num_edges", i64), ("grad_out_dev", p), ("grad_out_stride_elems", i64), ("F", i64),
+                ("w_dev", p), ("self_w_dev", p), ("grad_x_dev", p)]
+
+
+class AggWeightedWgradDesc(C.Structure):
+    """spp_agg_weighted_wgrad_desc: grad_w[k] = <g[t], x[col[k]]>, grad_self_w[t] = <g[t], x[t]>"""
+    _fields_ = [("source", i32), ("x_elem", i32), ("grad_elem", i32), ("reserved", i32), ("rowptr_dev", p),
+                ("col_dev", p), ("num_targets", i64), ("num_edges", i64), ("x_dev", p), ("x_stride_elems", i64),
+                ("x_rows", i64), ("n_id_dev", p), ("F", i64), ("grad_out_dev", p), ("grad_out_stride_elems", i64),
+                ("grad_w_dev", p), ("grad_self_w_dev", p)]
+
+
+class GcnNormDesc(C.Structure):
+    """spp_gcn_norm_desc: PyG's gcn_norm of a hop padded to [S, S]"""
+    _fields_ = [("fill", i32), ("reserved", i32), ("rowptr_dev", p), ("col_dev", p), ("num_targets", i64),
+                ("num_sources", i64), ("num_edges", i64), ("w_dev", p), ("dinv_dev", p), ("coef_dev", p),
+                ("self_coef_dev", p)]
+
+
 class GraphAggDesc(C.Structure):
     """spp_graph_agg_desc: targets as a slab (target_row0 >= 0) or a list (target_ids_dev, target_row0 < 0)"""
     _fields_ = [("epilogue", i32), ("x_elem", i32), ("out_elem", i32), ("reserved", i32), ("rowptr_dev", p),
@@ -315,6 +345,11 @@ SIGNATURES = {
     "spp_bn_act_backward": (C.c_int, [C.POINTER(BnActDesc), p]),
     "spp_agg_max_forward": (C.c_int, [C.POINTER(AggMaxFwdDesc), p]),
     "spp_agg_max_backward": (C.c_int, [C.POINTER(AggMaxBwdDesc), p]),
+    "spp_agg_weighted_forward": (C.c_int, [C.POINTER(AggWeightedFwdDesc), p]),
+    "spp_agg_weighted_backward_workspace_bytes": (i64, [i64, i64, i64]),
+    "spp_agg_weighted_backward": (C.c_int, [C.POINTER(AggWeightedBwdDesc), p, i64, p]),
+    "spp_agg_weighted_wgrad": (C.c_int, [C.POINTER(AggWeightedWgradDesc), p]),
+    "spp_gcn_norm": (C.c_int, [C.POINTER(GcnNormDesc), p]),
 }
 SPP_COMM_ID_BYTES = 128
 SPP_IPC_HANDLE_BYTES = 64

@@ -9,6 +9,7 @@
 #include "act_keep.hip.h"
 #include "agg_rows.hip.h"
 #include "elem_io.hip.h"
+#include "transpose_hop.hip.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -16,8 +17,6 @@
 #include <type_traits>
 
 namespace spp {
-
-constexpr int kAggNT = 256;
 
 // the same as float4, element 4*i .. 4*i+3 of p (the backward kernels' form)
 __device__ __forceinline__ float4 ld4(const float* p, int64_t i) { return reinterpret_cast<const float4*>(p)[i]; }
@@ -237,36 +236,7 @@ __global__ __launch_bounds__(kAggNT) void k_relu_dropout_bwd_pre(const float* __
   }
 }
 
-// ---- backward of the fused operand by GATHER over the transposed hop ----------------------------
-// 42 M fp32 atomics (163 k edges x 256 columns) run at the chip's atomic rate (~325 G/s: 140 us); the
-// transposed adjacency (sources -> targets) costs three small integer passes per step and turns the
-// backward into the same gather-reduce as the forward.
-__global__ __launch_bounds__(kAggNT) void k_tr_count(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,
-                                                     int64_t T, int32_t* __restrict__ cnt, float* __restrict__ inv) {
-  const int64_t t = (int64_t)blockIdx.x * kAggNT + threadIdx.x;
-  if (t >= T) return;
-  const int64_t b = rowptr[t], e = rowptr[t + 1];
-  inv[t] = 1.0f / (float)(e > b ? e - b : 1);
-  for (int64_t k = b; k < e; ++k) atomicAdd(&cnt[col[k]], 1);
-}
-
-// tcol[pos] = t for every entry (t, s) of the hop, pos in source s's segment; with tedge != NULL also tedge[pos] = k,
-// the entry's CSR position (GAT's attention weights are per entry)
-__global__ __launch_bounds__(kAggNT) void k_tr_fill(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,
-                                                    int64_t T, const int32_t* __restrict__ start,
-                                                    int32_t* __restrict__ cursor, int32_t* __restrict__ tcol,
-                                                    int32_t* __restrict__ tedge) {
-  const int64_t t = (int64_t)blockIdx.x * kAggNT + threadIdx.x;
-  if (t >= T) return;
-  const int64_t b = rowptr[t], e = rowptr[t + 1];
-  for (int64_t k = b; k < e; ++k) {
-    const int64_t s = col[k];
-    const int32_t pos = start[s] + atomicAdd(&cursor[s], 1);
-    tcol[pos] = (int32_t)t;
-    if (tedge) tedge[pos] = (int32_t)k;
-  }
-}
-
+// ---- backward of the fused operand by GATHER over the transposed hop: k_tr_count, k_tr_fill (transpose_hop.hip.h) ----
 // the input gradient by GATHER over the targets t of source s (tcol[start[s] .. start[s+1])), two rows at a time:
 //   Mean (SAGE's operand): (s < T ? grad_out[s, F:2F] : 0), added first, + sum_t grad_out[t, :F] * inv[t].  kAct: the
 //     ReLU + dropout backward (k_relu_dropout_bwd_pre) of the pre-activation z (dense [S, F]) is applied to the row
@@ -439,51 +409,10 @@ extern "C" spp_status spp_csr_mean_backward(const int64_t* rowptr_dev, const int
   return SPP_OK;
 }
 
-static int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
-// The workspace of transpose_hop: cnt/cursor [S+1] | start [S+1] | tcol [E] | tedge [E] (edge_ids) | inv [T] | scan
-// temporaries   (each 16-byte aligned)
-static int64_t transpose_hop_bytes(int64_t T, int64_t S, int64_t E, bool edge_ids) {
-  size_t scan_tmp = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tmp, (const int32_t*)nullptr, (int32_t*)nullptr, (int)(S + 1));
-  return align16(4 * (S + 1)) * 2 + align16(4 * E) * (edge_ids ? 2 : 1) + align16(4 * T) + align16((int64_t)scan_tmp) + 64;
-}
-
+// transpose_hop_bytes, TransposedHop and transpose_hop: transpose_hop.hip.h
 extern "C" int64_t spp_sage_operand_backward_workspace_bytes(int64_t num_targets, int64_t num_sources,
                                                                int64_t num_edges) {
   return transpose_hop_bytes(num_targets, num_sources, num_edges, false);
-}
-
-struct TransposedHop {
-  const int32_t *start, *tcol, *tedge;
-  const float* inv;
-};
-
-// The transposed hop (sources -> targets) in a transpose_hop_bytes workspace: source s's targets are
-// tcol[start[s] .. start[s+1]), with edge_ids tedge[] holds the CSR entry of each, inv[t] = 1 / max(deg t, 1).
-// Count, scan, fill; the callers have checked the sizes.
-static spp_status transpose_hop(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
-                                int64_t num_sources, int64_t num_edges, bool edge_ids, void* workspace_dev,
-                                int64_t workspace_bytes, hipStream_t st, TransposedHop* hop) {
-  char* w = static_cast<char*>(workspace_dev);
-  auto take = [&](int64_t bytes) { int32_t* p = reinterpret_cast<int32_t*>(w); w += align16(bytes); return p; };
-  int32_t* cnt = take(4 * (num_sources + 1));
-  int32_t* start = take(4 * (num_sources + 1));
-  int32_t* tcol = take(4 * num_edges);
-  int32_t* tedge = edge_ids ? take(4 * num_edges) : nullptr;
-  float* inv = reinterpret_cast<float*>(take(4 * num_targets));
-  size_t scan_tmp = (size_t)(workspace_bytes - (w - static_cast<char*>(workspace_dev)));
-  SPP_HIP_TRY(hipMemsetAsync(cnt, 0, 4 * (size_t)(num_sources + 1), st));
-  const unsigned gt = (unsigned)std::max<int64_t>(1, ceil_div(num_targets, kAggNT));
-  if (num_targets > 0)
-    hipLaunchKernelGGL(k_tr_count, dim3(gt), dim3(kAggNT), 0, st, rowptr_dev, col_dev, num_targets, cnt, inv);
-  SPP_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(w, scan_tmp, cnt, start, (int)(num_sources + 1), st));
-  SPP_HIP_TRY(hipMemsetAsync(cnt, 0, 4 * (size_t)(num_sources + 1), st));
-  if (num_targets > 0)
-    hipLaunchKernelGGL(k_tr_fill, dim3(gt), dim3(kAggNT), 0, st, rowptr_dev, col_dev, num_targets, start, cnt, tcol,
-                       tedge);
-  *hop = {start, tcol, tedge, inv};
-  return SPP_OK;
 }
 
 // The backward of every operand / sum / mean entry but spp_csr_mean_backward (`who` names the public entry in the

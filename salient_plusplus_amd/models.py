@@ -1265,6 +1265,301 @@ class GIN(torch.nn.Module):
 
 
 # --------------------------------------------------------------------------------------------
+# Edge-weighted aggregation, gcn_norm, GCNConv and GCN  (driver/models.py:343-381; csrc/aggregate_weighted.hip, spp.h f3r)
+# --------------------------------------------------------------------------------------------
+def _entry_rows(rowptr, col, T):
+    """(the target row of every entry [E], E) of the hop's first T rows"""
+    E = int(rowptr[T])
+    deg = rowptr[1:T + 1] - rowptr[:T]
+    return torch.repeat_interleave(torch.arange(T, device=col.device), deg, output_size=E), E
+
+
+def _weighted_reference(x, rowptr, col, weight, T, self_weight=None):
+    """Plain torch restatement of spp_agg_weighted_forward on a dense x: out[t] = sum_k w[k] * x[col[k]] over row t
+    (+ self_weight[t] * x[t]), [T, F].  Computed in fp32 -- in float64 when x is float64 -- on x's device, and
+    differentiable in x, weight and self_weight."""
+    dt = torch.float64 if x.dtype == torch.float64 else torch.float32
+    x = x.to(dt)
+    row, E = _entry_rows(rowptr, col, T)
+    out = torch.zeros((T, x.size(1)), dtype=dt, device=x.device)
+    out = out.index_add(0, row, x[col[:E]] * weight[:E].to(dt).unsqueeze(1))
+    if self_weight is not None:
+        out = out + self_weight.to(dt).unsqueeze(1) * x[:T]
+    return out
+
+
+def _gcn_fill(add_self_loops, improved):
+    return (2 if improved else 1) if add_self_loops else 0
+
+
+def _gcn_norm_reference(rowptr, col, T, edge_weight=None, *, add_self_loops=True, improved=False, dtype=None):
+    """Plain torch restatement of spp_gcn_norm: PyG's gcn_norm of the hop padded to a square (rows >= T are empty), so a
+    source that is no target has degree ``fill``.  (coef [E], self_coef [T]) in ``dtype`` (default: float64 if
+    edge_weight is, else fp32)."""
+    if dtype is None:
+        dtype = torch.float64 if edge_weight is not None and edge_weight.dtype == torch.float64 else torch.float32
+    fill = float(_gcn_fill(add_self_loops, improved))
+    row, E = _entry_rows(rowptr, col, T)
+    w = torch.ones(E, dtype=dtype, device=col.device) if edge_weight is None else edge_weight[:E].to(dtype)
+    deg = torch.full((T,), fill, dtype=dtype, device=col.device).index_add(0, row, w)
+    dinv = deg.pow(-0.5)
+    dinv = dinv.masked_fill(dinv == float("inf"), 0.0)
+    c = col[:E]
+    foreign = torch.full((), fill ** -0.5 if fill > 0 else 0.0, dtype=dtype, device=col.device)
+    dsrc = torch.where(c < T, dinv[c.clamp(max=max(T - 1, 0))], foreign) if T > 0 else foreign.expand(E)
+    return dinv[row] * w * dsrc, fill * dinv * dinv
+
+
+def _check_hop(what, rowptr, col, num_targets):
+    for name, t in (("rowptr", rowptr), ("col", col)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1:
+            raise ValueError(f"{what}: {name} must be a 1-D int64 tensor")
+    if not isinstance(num_targets, int) or num_targets < 0 or rowptr.numel() < num_targets + 1:
+        raise ValueError(f"{what}: num_targets must be an int in [0, {rowptr.numel() - 1}] (rowptr has "
+                         f"{rowptr.numel()} entries), got {num_targets!r}")
+
+
+def _check_weights(what, name, w, n):
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or w.dim() != 1 or w.numel() != n:
+        got = f"{tuple(w.shape)} of {w.dtype}" if isinstance(w, torch.Tensor) else type(w).__name__
+        raise ValueError(f"{what}: {name} must be a 1-D fp32 tensor of {n} values, got {got}")
+
+
+def _check_weighted_source(what, x):
+    """what the weighted kernels read, checked before any device call"""
+    m = x.table if isinstance(x, TableRows) else x
+    if isinstance(m, Fp8Features):
+        raise ValueError(f"{what}: fp8 rows are not supported (fp32, fp16 or bf16 rows)")
+    if isinstance(x, RowRefs):
+        if x.dtype not in _ELEM:
+            raise ValueError(f"{what}: row references must name fp32 / fp16 / bf16 rows, got {x.dtype}")
+        return
+    if not isinstance(m, torch.Tensor):
+        raise TypeError(f"{what}: x must be a tensor, a TableRows or a RowRefs, got {type(x).__name__}")
+    if m.dim() != 2 or m.dtype not in _ELEM or m.stride(1) != 1:
+        raise ValueError(f"{what}: x must be a 2-D fp32 / fp16 / bf16 matrix with unit column stride, got "
+                         f"{tuple(m.shape)} of {m.dtype}")
+
+
+class _WeightedAggregate(torch.autograd.Function):
+    """out[t] = sum_{k in row t} weight[k] * x[col[k]]  (+ self_weight[t] * x[t]; targets are the first T rows of x).
+
+    ``x`` is a feature matrix (fp16 / fp32 / bf16, any row stride), a TableRows or a RowRefs: the latter two are read in
+    place and get no gradient.  fp32 fmaf chain in CSR order, the self term last; under bf16 autocast the result is bf16
+    (rounded once).  ``weight`` and ``self_weight`` get their gradients (one dot product per entry) only if they
+    require one."""
+
+    @staticmethod
+    def forward(ctx, x, rowptr, col, weight, self_weight, num_targets):
+        nat.require_device()
+        src, _ = _rows(x)
+        T, E = num_targets, col.numel()
+        out = torch.empty((T, src["F"]), dtype=torch.bfloat16 if amp_bf16() else torch.float32, device=rowptr.device)
+        weight = weight.contiguous()
+        self_weight = self_weight.contiguous() if self_weight is not None else None
+        d = nat.AggWeightedFwdDesc(out_elem=_ELEM[out.dtype], rowptr_dev=_p(rowptr), col_dev=_p(col), num_targets=T,
+                                   num_edges=E, w_dev=_p(weight), self_w_dev=_p(self_weight), out_dev=_p(out),
+                                   out_stride_elems=0, **src)
+        nat.check(nat.load().spp_agg_weighted_forward(C.byref(d), _stream()))
+        wgrad = ctx.needs_input_grad[3] or ctx.needs_input_grad[4]
+        ctx.save_for_backward(rowptr, col, weight, self_weight, x if wgrad and isinstance(x, torch.Tensor) else None)
+        ctx.rows = x if wgrad and not isinstance(x, torch.Tensor) else None      # a TableRows / RowRefs, read again
+        ctx.shape = (x.size(0), src["F"], T)
+        ctx.in_dtype = x.dtype
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        rowptr, col, weight, self_weight, x = ctx.saved_tensors
+        S, Fdim, T = ctx.shape
+        E = col.numel()
+        L = nat.load()
+        g = _grad_in(grad_out)
+        gs = g.stride(0) if T > 1 else 0
+        grad_x = grad_w = grad_sw = None
+        if ctx.needs_input_grad[0]:
+            # bf16 / fp32 gradient in, the input's dtype out (fp16 through an fp32 buffer)
+            odt = ctx.in_dtype if ctx.in_dtype in (torch.float32, torch.bfloat16) else torch.float32
+            grad_x = torch.empty((S, Fdim), dtype=odt, device=g.device)
+            nbytes = int(L.spp_agg_weighted_backward_workspace_bytes(T, S, E))
+            ws = torch.empty(max(nbytes, 0), dtype=torch.uint8, device=g.device)
+            d = nat.AggWeightedBwdDesc(grad_elem=_ELEM[g.dtype], out_elem=_ELEM[odt], rowptr_dev=_p(rowptr),
+                                       col_dev=_p(col), num_targets=T, num_sources=S, num_edges=E, grad_out_dev=_p(g),
+                                       grad_out_stride_elems=gs, F=Fdim, w_dev=_p(weight), self_w_dev=_p(self_weight),
+                                       grad_x_dev=_p(grad_x))
+            nat.check(L.spp_agg_weighted_backward(C.byref(d), _p(ws), nbytes, _stream()))
+            grad_x = grad_x.to(ctx.in_dtype)
+        if ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
+            src, _ = _rows(x if x is not None else ctx.rows)
+            grad_w = torch.empty(E, dtype=torch.float32, device=g.device)
+            grad_sw = torch.empty(T, dtype=torch.float32, device=g.device) if ctx.needs_input_grad[4] else None
+            d = nat.AggWeightedWgradDesc(grad_elem=_ELEM[g.dtype], rowptr_dev=_p(rowptr), col_dev=_p(col), num_targets=T,
+                                         num_edges=E, grad_out_dev=_p(g), grad_out_stride_elems=gs,
+                                         grad_w_dev=_p(grad_w), grad_self_w_dev=_p(grad_sw), **src)
+            nat.check(L.spp_agg_weighted_wgrad(C.byref(d), _stream()))
+            if not ctx.needs_input_grad[3]:
+                grad_w = None
+        return grad_x, None, None, grad_w, grad_sw, None
+
+
+def weighted_aggregate(x, rowptr, col, weight, num_targets, self_weight=None):
+    """The edge-weighted neighbour sum ``out[t] = sum_k weight[k] * x[col[k]]`` over the entries k of target t's row,
+    ``+ self_weight[t] * x[t]`` when ``self_weight`` is given: [num_targets, F], fp32 (bf16 under bf16 autocast).
+
+    ``x``: an fp32 / fp16 / bf16 matrix, a TableRows or a RowRefs (read in place, no gradient); the targets are its first
+    ``num_targets`` rows.  ``weight`` fp32 [E] and ``self_weight`` fp32 [num_targets]: one value per entry / target;
+    both are differentiable.  On the GPU this is one autograd node on HIP kernels; CPU tensors take the plain torch
+    restatement."""
+    what = "weighted_aggregate"
+    _check_weighted_source(what, x)
+    _check_hop(what, rowptr, col, num_targets)
+    _check_weights(what, "weight", weight, col.numel())
+    if self_weight is not None:
+        _check_weights(what, "self_weight", self_weight, num_targets)
+        if num_targets > x.size(0):
+            raise ValueError(f"{what}: the targets are the first rows of x: {num_targets} targets, {x.size(0)} rows")
+    if not x.is_cuda:
+        if not isinstance(x, torch.Tensor):
+            x = x.materialize()
+        return _weighted_reference(x, rowptr, col, weight, num_targets, self_weight)
+    return _WeightedAggregate.apply(x, rowptr, col, weight, self_weight, num_targets)
+
+
+def gcn_norm(rowptr, col, num_targets, edge_weight=None, *, add_self_loops=True, improved=False):
+    """PyG's ``gcn_norm`` of an MFG hop: ``(coef [E], self_coef [num_targets])``, fp32, with
+    ``coef[k] = deg[t]^-1/2 * w[k] * deg[col[k]]^-1/2`` and ``self_coef[t] = fill / deg[t]``, where ``deg`` is the row sum
+    of ``A + fill * I`` on the hop padded to a square: ``fill + sum_row w`` for a target, ``fill`` for a source that is no
+    target (``fill`` = 1, 2 with ``improved``, 0 without self loops).  When the hop is a whole graph (targets = sources)
+    this is PyG's normalisation.  Not differentiable: an ``edge_weight`` that requires grad is refused."""
+    what = "gcn_norm"
+    _check_hop(what, rowptr, col, num_targets)
+    if edge_weight is not None:
+        _check_weights(what, "edge_weight", edge_weight, col.numel())
+        if edge_weight.requires_grad:
+            raise ValueError(f"{what}: edge_weight requires grad, and gcn_norm is not differentiable; pass "
+                             "edge_weight.detach(), or normalise differentiable weights in torch")
+    if not rowptr.is_cuda:
+        return _gcn_norm_reference(rowptr, col, num_targets, edge_weight, add_self_loops=add_self_loops,
+                                   improved=improved, dtype=torch.float32)
+    nat.require_device()
+    T, E = num_targets, col.numel()
+    w = edge_weight.contiguous() if edge_weight is not None else None
+    dinv = torch.empty(T, dtype=torch.float32, device=rowptr.device)
+    coef = torch.empty(E, dtype=torch.float32, device=rowptr.device)
+    self_coef = torch.empty(T, dtype=torch.float32, device=rowptr.device)
+    d = nat.GcnNormDesc(fill=_gcn_fill(add_self_loops, improved), rowptr_dev=_p(rowptr), col_dev=_p(col), num_targets=T,
+                        num_sources=T, num_edges=E, w_dev=_p(w),       # (a source beyond T is never read: S = T will do)
+                        dinv_dev=_p(dinv), coef_dev=_p(coef), self_coef_dev=_p(self_coef))
+    nat.check(nat.load().spp_gcn_norm(C.byref(d), _stream()))
+    return coef, self_coef
+
+
+class GCNConv(torch.nn.Module):
+    """torch_geometric.nn.GCNConv(in, out, improved=..., add_self_loops=..., normalize=..., bias=...) on an MFG hop
+    ``adj_t`` ([T, S] CSR; the targets are the first T source rows): ``lin(sum_k w_k x_k [+ self_coef * x_target]) + bias``.
+
+    The entry weights are ``adj_t``'s values if it has any, else ones.  ``normalize=True`` passes them through
+    ``gcn_norm`` (PyG's symmetric normalisation of the hop padded to a square) and adds the self term;
+    ``normalize=False`` -- the reference model's setting -- is the bare weighted sum, without a self term.  The rows are
+    aggregated FIRST and projected second (the GEMM has T rows instead of S); PyG projects first: the same value up to
+    rounding.  Parameters: ``lin.weight`` and ``bias``, as in PyG.
+
+    ``forward(x, adj_t, size)`` with a single ``x`` (a matrix, TableRows or RowRefs) takes the first size[1] rows as the
+    targets; ``forward((x, x_target), adj_t)`` takes ``x_target`` for the self term."""
+
+    def __init__(self, in_channels, out_channels, bias=True, *, normalize=True, improved=False, add_self_loops=True):
+        super().__init__()
+        self.normalize, self.improved, self.add_self_loops = bool(normalize), bool(improved), bool(add_self_loops)
+        self.lin = torch.nn.Linear(in_channels, out_channels, bias=False)
+        if bias:
+            self.bias = torch.nn.Parameter(torch.empty(out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        torch.nn.init.xavier_uniform_(self.lin.weight)                   # PyG: glorot weight, zero bias
+        if self.bias is not None:
+            torch.nn.init.zeros_(self.bias)
+
+    def forward(self, x, adj_t, size=None):
+        rowptr, col, value = adj_t.csr()
+        x_target = None
+        if isinstance(x, tuple):
+            x, x_target = x
+        if x_target is not None:
+            T = x_target.size(0)
+        else:
+            T = int(size[1]) if size is not None else int(adj_t.sparse_sizes()[0])
+        if isinstance(x, torch.Tensor) and x.dtype not in _ELEM:
+            x = x.to(torch.float32)
+        prefix = x_target is None or (isinstance(x, torch.Tensor) and x_target.data_ptr() == x.data_ptr() and
+                                      x_target.stride() == x.stride() and x_target.size(1) == x.size(1))
+        w = value.to(torch.float32) if value is not None else None
+        self_w = None
+        if self.normalize:
+            w, self_w = gcn_norm(rowptr, col, T, w, add_self_loops=self.add_self_loops, improved=self.improved)
+            if not self.add_self_loops:
+                self_w = None                                                # (all zeros)
+        elif w is None:
+            w = torch.ones(col.numel(), dtype=torch.float32, device=col.device)
+        if prefix or self_w is None:
+            h = weighted_aggregate(x, rowptr, col, w, T, self_w)
+        else:                                                                # a foreign target matrix
+            h = weighted_aggregate(x, rowptr, col, w, T)
+            h = h + self_w.unsqueeze(1).to(h.dtype) * x_target.to(h.dtype)
+        out = _tall_linear(h, self.lin.weight)
+        return out if self.bias is None else out + self.bias
+
+
+class GCN(torch.nn.Module):
+    """The reference's GCN (driver/models.py:343-381): ``num_layers`` GCNConv(bias=False, improved=False), each but the
+    last followed by BatchNorm1d, ReLU and dropout 0.5, then log_softmax; ``bns`` holds ``num_layers`` BatchNorm1d(hidden)
+    of which the last is unused, as in the reference.  ``normalize`` (keyword only; the reference: False) is handed to
+    every conv.  ``fused_norm=True`` runs each tail as ``batch_norm_act(act="relu", p=0.5)`` (same modules, same state
+    dict).  The first layer reads a TableRows / RowRefs input in place."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, normalize=False, fused_norm=False):
+        super().__init__()
+        kwargs = dict(normalize=normalize, bias=False, improved=False)
+        self.num_layers = num_layers
+        self.hidden_channels = hidden_channels
+        self.normalize = bool(normalize)
+        self.fused_norm = fused_norm
+        self.convs = torch.nn.ModuleList()
+        self.bns = torch.nn.ModuleList()
+        self.convs.append(GCNConv(in_channels, hidden_channels, **kwargs))
+        self.bns.append(torch.nn.BatchNorm1d(hidden_channels))
+        for _ in range(num_layers - 2):
+            self.convs.append(GCNConv(hidden_channels, hidden_channels, **kwargs))
+            self.bns.append(torch.nn.BatchNorm1d(hidden_channels))
+        self.convs.append(GCNConv(hidden_channels, out_channels, **kwargs))
+        self.bns.append(torch.nn.BatchNorm1d(hidden_channels))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for conv in self.convs:
+            conv.reset_parameters()
+            conv.apply(init_weights)
+
+    def forward(self, x, adjs):
+        # the reference converts the features to fp32 first (models.py:372); the sum reads fp16 rows directly (exact)
+        for i, (adj_t, _e_id, size) in enumerate(adjs):
+            x = self.convs[i](x, adj_t, size)
+            if i != self.num_layers - 1:
+                if self.fused_norm:
+                    x = batch_norm_act(x, self.bns[i], act="relu", p=0.5)
+                else:
+                    x = F.dropout(F.relu(self.bns[i](x)), p=0.5, training=self.training)
+        return torch.log_softmax(x, dim=-1)
+
+    def inference(self, x_all, rowptr, col, **kw):
+        raise NotImplementedError("GCN.inference: exact layer-wise GCN inference is not built (the resident-graph "
+                                  "aggregation entries take no edge weights)")
+
+
+# --------------------------------------------------------------------------------------------
 # SAGEResInception  (driver/models.py:95-192)
 # --------------------------------------------------------------------------------------------
 class MLP(torch.nn.Module):

@@ -1,9 +1,10 @@
 """One resident batch of the bench workload, N optimisation steps of one of the models (models.get_model_type: SAGE, GAT,
-GIN, SAGEResInception) on it (fwd + bwd + Adam), timed; run under `rocprofv3 --kernel-trace --stats` for the per-kernel
+GIN, SAGEResInception; and models.GCN) on it (fwd + bwd + Adam), timed; run under `rocprofv3 --kernel-trace --stats` for the per-kernel
 table.
-usage: model_step_profile.py [sage|gat|gin|sageresinception] [steps=30] [workload=S-papers] [fused] [max] [--amp bf16] [--heads H]
+usage: model_step_profile.py [sage|gat|gin|sageresinception|gcn] [steps=30] [workload=S-papers] [fused] [max] [norm] [--amp bf16] [--heads H]
+norm: GCN built with normalize=True (gcn_norm's coefficients and the self term; the reference model's setting is False).
 max: SAGE built with aggr="max" (csrc/aggregate_max.hip, layer by layer) instead of the mean's fused stack.
-fused: GIN / SAGEResInception built with fused_norm=True (the BatchNorm tail on csrc/bn_act.hip).
+fused: GIN / SAGEResInception / GCN built with fused_norm=True (the BatchNorm tail on csrc/bn_act.hip).
 --amp bf16: the forward and the loss under torch.autocast("cuda", dtype=torch.bfloat16), as a training loop would wrap them.
 --heads H: GAT(..., heads=H) (default 1: the reference model): hidden layers of H heads of 256 // H, the last one averaged."""
 import contextlib
@@ -17,7 +18,7 @@ import torch  # noqa: E402
 from salient_plusplus_amd import fast_sampler as fs  # noqa: E402
 from salient_plusplus_amd.fast_trainer.samplers import FastSampler, FastSamplerConfig  # noqa: E402
 from salient_plusplus_amd.fast_trainer.transferers import DevicePrefetcher  # noqa: E402
-from salient_plusplus_amd.models import get_model_type  # noqa: E402
+from salient_plusplus_amd.models import GCN, get_model_type  # noqa: E402
 from salient_plusplus_amd.synthetic import make_workload  # noqa: E402
 
 argv = sys.argv[1:]
@@ -35,7 +36,8 @@ if "--heads" in argv:
     del argv[i:i + 2]
 fused = "fused" in argv
 use_max = "max" in argv
-argv = [a for a in argv if a not in ("fused", "max")]
+norm = "norm" in argv
+argv = [a for a in argv if a not in ("fused", "max", "norm")]
 arch = argv[0] if len(argv) > 0 else "sage"
 steps = int(argv[1]) if len(argv) > 1 else 30
 wl = make_workload(argv[2] if len(argv) > 2 else "S-papers", seed=1234, device=torch.device("cuda", 0))
@@ -50,8 +52,10 @@ batch = next(it)[0]
 torch.cuda.synchronize()
 if heads != 1 and arch != "gat":
     sys.exit("--heads: GAT only")
-if fused and arch not in ("gin", "sageresinception"):
-    sys.exit("fused: GIN and SAGEResInception only")
+if fused and arch not in ("gin", "sageresinception", "gcn"):
+    sys.exit("fused: GIN, SAGEResInception and GCN only")
+if norm and arch != "gcn":
+    sys.exit("norm: GCN only")
 if use_max and arch != "sage":
     sys.exit("max: SAGE only")
 kw = {"heads": heads} if heads != 1 else {}
@@ -59,7 +63,9 @@ if use_max:
     kw["aggr"] = "max"
 if fused:
     kw["fused_norm"] = True
-model = get_model_type(arch)(wl.x.size(1), 256, 47, 3, **kw).to(dev)
+if norm:
+    kw["normalize"] = True
+model = (GCN if arch == "gcn" else get_model_type(arch))(wl.x.size(1), 256, 47, 3, **kw).to(dev)
 if arch == "gat":
     assert [c.heads for c in model.convs] == [heads] * 3, "the model was not built with --heads"
 opt = torch.optim.Adam(model.parameters(), lr=1e-3, fused=True)    # one multi-tensor launch per step
@@ -86,5 +92,5 @@ for _ in range(steps):
     loss = step()
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / steps
-print(f"MODEL_STEP {arch}{' aggr=max' if use_max else ''}{f' heads={heads}' if heads != 1 else ''}{' fused_norm' if fused else ''}{' amp=' + amp if amp else ''} {dt * 1e3:.3f} ms/step on a resident batch: {batch.x.size(0)} nodes, "
+print(f"MODEL_STEP {arch}{' aggr=max' if use_max else ''}{' normalize' if norm else ''}{f' heads={heads}' if heads != 1 else ''}{' fused_norm' if fused else ''}{' amp=' + amp if amp else ''} {dt * 1e3:.3f} ms/step on a resident batch: {batch.x.size(0)} nodes, "
       f"{[int(a.adj_t.nnz()) for a in batch.adjs]} edges, (S, T) {[tuple(int(v) for v in a.size) for a in batch.adjs]}, loss {float(loss):.4f}", flush=True)
