@@ -1640,6 +1640,79 @@ spp_status spp_agg_weighted_backward(const spp_agg_weighted_bwd_desc* desc, void
 spp_status spp_agg_weighted_wgrad(const spp_agg_weighted_wgrad_desc* desc, void* stream);
 spp_status spp_gcn_norm(const spp_gcn_norm_desc* desc, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * f3s  EDGE-WEIGHTED sum aggregation over rows of the RESIDENT graph: the weighted member of the f3g family, the message
+ *      passing of exact, layer-wise GCN inference.  The graph, x, the targets (a slab or a list) and the output are
+ *      spp_graph_agg_desc's, unchanged in meaning; the weights come in one of two forms:
+ *
+ *        explicit   (dinv_dev NULL)  the weight of entry k is  c_k = w_dev ? w[k] : 1.0f,  and when self_w_dev is given the
+ *                   target's own row is added with the weight self_w[t] (fp32 [x_rows], indexed by the GLOBAL node id t)
+ *        in-kernel  (dinv_dev given: fp32 [x_rows], spp_gcn_dinv's result)  PyG's gcn_norm formed on the fly,
+ *                       c_k    = dinv[t] * (w_dev ? w[k] : 1.f) * dinv[col[k]]
+ *                       self_c = dinv[t] * fill * dinv[t]          (fill 0 / 1 / 2 as in spp_gcn_norm; no self term for 0)
+ *                   -- the fp32 expressions of spp_gcn_norm, evaluated left to right: the bits of its coef / self_coef
+ *                   for the whole graph as one hop (T = S = N), without the fp32 [E] array (12.8 GB at E = 3.2 G).
+ *                   fill is read only in this form.  A col[k] outside [0, x_rows) reads dinv[0], as the row source
+ *                   reads row 0.
+ *
+ *   Summation contract, C = spp_graph_agg_chunk() (f3g's constant):
+ *     a row of d <= C entries: acc = 0, then acc = fmaf(c_k, x[col[k]], acc) once per entry in CSR order, then the self
+ *       term LAST as one more fmaf(self_c, x[t], acc): the arithmetic of spp_agg_weighted_forward, bit-identical to it on
+ *       the same row;
+ *     a longer row is cut into consecutive chunks of C entries (the last may be shorter); each chunk is such an fmaf chain
+ *       from zero, the chunk sums are added in chunk order in fp32, and the self term is one fmaf on the total;
+ *     a target id outside [0, x_rows) gives a row of zeros; the result of a row depends on nothing else -- not the grid,
+ *       the slab, or the other rows of the call; a bf16 output rounds each stored element once; no atomic touches the
+ *       output.
+ *
+ *   Load balance, workspace (spp_graph_agg_workspace_bytes(num_targets), 16-byte aligned), the vector and scalar forms
+ *   and what is enqueued (a 16-byte memset and two launches, no wait): as spp_graph_agg_forward.  Per entry the kernels
+ *   stream 8 bytes of col and 4 bytes of w, or gather 4 bytes of dinv, next to the F * sizeof(x_elem) bytes of the row.
+ *   Refused with SPP_ERR_INVALID before anything is enqueued: everything spp_graph_agg_forward refuses (fp8 rows among
+ *   it: there is no _fp8 form), dinv_dev together with self_w_dev, fill outside 0..2 with dinv_dev, and w_dev, dinv_dev
+ *   or self_w_dev not 4-byte aligned.  Not built: a row-partitioned x, fp8 tables, weights in the receptive-field entries.
+ *
+ *   spp_gcn_dinv: the first pass of spp_gcn_norm alone, over the num_nodes rows of rowptr:
+ *        dinv[t] = 1.0f / sqrtf(fill + sum of row t's w in CSR order), 0 where that is inf; the row LENGTH when w_dev is NULL
+ *      -- the same kernel, so the bits of the dinv inside spp_gcn_norm -- without the [E] coefficient array.  With weights
+ *      one thread walks a whole row, a hub's 10^5 entries included: it runs once per model evaluation and is not tuned.
+ *      Refused: a NULL descriptor, fill outside 0..2, a negative or out-of-range num_nodes, NULL rowptr_dev or dinv_dev,
+ *      w_dev or dinv_dev not 4-byte aligned.  num_nodes == 0: SPP_OK.
+ * ------------------------------------------------------------------------- */
+typedef struct spp_graph_agg_weighted_desc {
+  int32_t x_elem;           /* SPP_ELEM_F32 / _F16 / _BF16 */
+  int32_t out_elem;         /* SPP_ELEM_F32 / SPP_ELEM_BF16 */
+  int32_t fill;             /* with dinv_dev: 1; 2 = improved; 0 = no self loops */
+  int32_t reserved;
+  const int64_t* rowptr_dev;
+  const int64_t* col_dev;
+  const void* x_dev;
+  int64_t x_stride_elems;
+  int64_t x_rows;           /* the graph's nodes = the rows of x */
+  int64_t F;
+  int64_t target_row0;      /* slab: the first target; < 0 with a list */
+  const int64_t* target_ids_dev; /* list: the targets; NULL with a slab */
+  int64_t num_targets;
+  void* out_dev;            /* [num_targets, F] */
+  int64_t out_stride_elems; /* 0 = dense */
+  const float* w_dev;       /* fp32, one value per entry of col; NULL: ones */
+  const float* dinv_dev;    /* fp32 [x_rows], or NULL */
+  const float* self_w_dev;  /* fp32 [x_rows] by global node id, or NULL; not with dinv_dev */
+} spp_graph_agg_weighted_desc;
+
+typedef struct spp_gcn_dinv_desc {
+  int32_t fill;             /* 1; 2 = improved; 0 = no self loops */
+  int32_t reserved;
+  const int64_t* rowptr_dev;
+  int64_t num_nodes;
+  const float* w_dev;       /* fp32, one value per entry, or NULL: ones */
+  float* dinv_dev;          /* fp32 [num_nodes] */
+} spp_gcn_dinv_desc;
+
+spp_status spp_graph_agg_weighted_forward(const spp_graph_agg_weighted_desc* desc, void* workspace_dev,
+                                          int64_t workspace_bytes, void* stream);
+spp_status spp_gcn_dinv(const spp_gcn_dinv_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

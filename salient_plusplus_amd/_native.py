@@ -127,6 +127,20 @@ class GcnNormDesc(C.Structure):
                 ("self_coef_dev", p)]
 
 
+class GcnDinvDesc(C.Structure):
+    """spp_gcn_dinv_desc: gcn_norm's first pass alone, dinv [num_nodes] over a whole graph"""
+    _fields_ = [("fill", i32), ("reserved", i32), ("rowptr_dev", p), ("num_nodes", i64), ("w_dev", p), ("dinv_dev", p)]
+
+
+class GraphAggWeightedDesc(C.Structure):
+    """spp_graph_agg_weighted_desc: GraphAggDesc's graph, x, targets and output; the weights explicit (w_dev, self_w_dev)
+    or formed in the kernel from dinv_dev and fill"""
+    _fields_ = [("x_elem", i32), ("out_elem", i32), ("fill", i32), ("reserved", i32), ("rowptr_dev", p), ("col_dev", p),
+                ("x_dev", p), ("x_stride_elems", i64), ("x_rows", i64), ("F", i64), ("target_row0", i64),
+                ("target_ids_dev", p), ("num_targets", i64), ("out_dev", p), ("out_stride_elems", i64), ("w_dev", p),
+                ("dinv_dev", p), ("self_w_dev", p)]
+
+
 class GraphAggDesc(C.Structure):
     """spp_graph_agg_desc: targets as a slab (target_row0 >= 0) or a list (target_ids_dev, target_row0 < 0)"""
     _fields_ = [("epilogue", i32), ("x_elem", i32), ("out_elem", i32), ("reserved", i32), ("rowptr_dev", p),
@@ -350,6 +364,8 @@ SIGNATURES = {
     "spp_agg_weighted_backward": (C.c_int, [C.POINTER(AggWeightedBwdDesc), p, i64, p]),
     "spp_agg_weighted_wgrad": (C.c_int, [C.POINTER(AggWeightedWgradDesc), p]),
     "spp_gcn_norm": (C.c_int, [C.POINTER(GcnNormDesc), p]),
+    "spp_graph_agg_weighted_forward": (C.c_int, [C.POINTER(GraphAggWeightedDesc), p, i64, p]),
+    "spp_gcn_dinv": (C.c_int, [C.POINTER(GcnDinvDesc), p]),
 }
 SPP_COMM_ID_BYTES = 128
 SPP_IPC_HANDLE_BYTES = 64

@@ -387,3 +387,23 @@ extern "C" spp_status spp_gcn_norm(const spp_gcn_norm_desc* desc, void* stream) 
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
 }
+
+// f3s: the first pass alone, over all the rows of a graph -- the per-node factors spp_graph_agg_weighted_forward forms its
+// coefficients from.  The same kernel as above, so the same bits; no [E] array.  (With weights one thread walks a whole
+// row, a hub's included: once per model evaluation.)
+extern "C" spp_status spp_gcn_dinv(const spp_gcn_dinv_desc* desc, void* stream) {
+  const char* who = "spp_gcn_dinv";
+  SPP_REQUIRE(desc, "%s: NULL descriptor", who);
+  const spp_gcn_dinv_desc& d = *desc;
+  SPP_REQUIRE(d.fill >= 0 && d.fill <= 2, "%s: unknown fill %d (1, 2 for improved, 0 for no self loops)", who, (int)d.fill);
+  const int64_t N = d.num_nodes;
+  SPP_REQUIRE(N >= 0 && N < kMaxIndex * kNT, "%s: num_nodes %lld negative or too many for one launch", who, (long long)N);
+  if (N == 0) return SPP_OK;
+  SPP_REQUIRE(d.rowptr_dev && d.dinv_dev, "%s: NULL buffer (rowptr or dinv)", who);
+  SPP_REQUIRE(aligned_to(d.w_dev, 4) && aligned_to(d.dinv_dev, 4),
+              "%s: misaligned buffer (w or dinv is not aligned to its element)", who);
+  hipLaunchKernelGGL(k_gcn_dinv, dim3((unsigned)ceil_div(N, kNT)), dim3(kNT), 0, as_stream(stream), d.rowptr_dev, d.w_dev, N,
+                     (float)d.fill, d.dinv_dev);
+  SPP_HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}

@@ -38,8 +38,6 @@ namespace graph_agg {
 
 using namespace graph_rows;
 
-constexpr int64_t kGraphChunk = 64;           // C
-
 struct Args : Targets {
   int32_t epilogue;     // SPP_AGG_MEAN / _OPERAND / _SUM; kMax kernels: SPP_AGG_MAX / _MAX_OPERAND
   float self_scale;

@@ -13,6 +13,7 @@ namespace graph_rows {
 constexpr int kNT = 256;
 constexpr int64_t kWorkspaceHeader = 16;      // the counter (8 bytes) and padding; the list follows
 constexpr unsigned kLongGrid = 16384;         // workgroups of the long-row launch (they stride over the list)
+constexpr int64_t kGraphChunk = 64;           // C of the sums' contract (graph_aggregate.hip, graph_agg_weighted.hip)
 
 // ---- device: what both families' Args begin and end with ----
 // the graph, the targets of the call and the geometry of x and out

@@ -2,8 +2,9 @@
 ``SAGE.inference``): every node is scored from ALL its neighbours, one pass per layer over the graph's CSR, with no
 sampling, no dedup and no exchange.  The message passing is the HIP kernel pair of csrc/graph_aggregate.hip for SAGE,
 GIN and SAGEResInception and of csrc/graph_gat.hip for GAT; SAGEResInception's layer tail is csrc/resinc_epilogue.hip
-(``spp_resinc_epilogue``); the layers' own parameters run through the library GEMMs torch dispatches to.  Forward only,
-fp16 / fp32 / bf16 inputs.
+(``spp_resinc_epilogue``); GCN's weighted sums are the pair of csrc/graph_agg_weighted.hip (``graph_weighted_aggregate``,
+with ``gcn_dinv`` for the per-node factors of its normalisation; resident entries only).  The layers' own parameters run
+through the library GEMMs torch dispatches to.  Forward only, fp16 / fp32 / bf16 inputs.
 
 The kernels' wrappers: ``graph_aggregate`` (``spp_graph_agg_forward``) and ``graph_gat_aggregate``
 (``spp_graph_gat_forward``) read one resident matrix, ``graph_aggregate_parts`` (``spp_graph_agg_parts_forward``) and
@@ -370,6 +371,17 @@ def _agg_launch(x, rowptr, col, epilogue, self_scale, row0, target_ids, T, out, 
     return _launch(nat.load().spp_graph_agg_forward, d, workspace, out)
 
 
+def _agg_weighted_launch(x, rowptr, col, weight, dinv, fill, self_weight, row0, target_ids, T, out, workspace):
+    """spp_graph_agg_weighted_forward: x [N, F] is one matrix; the weights explicit (``weight`` [E] or None for ones,
+    ``self_weight`` [N] or None) or, with ``dinv`` [N], formed in the kernel from it and ``fill``"""
+    N, Fdim = x.shape
+    d = nat.GraphAggWeightedDesc(x_elem=_ELEM[x.dtype], fill=int(fill), x_dev=_p(x),
+                                 x_stride_elems=x.stride(0) if N > 1 else Fdim, x_rows=N, F=Fdim, w_dev=_p(weight),
+                                 dinv_dev=_p(dinv), self_w_dev=_p(self_weight),
+                                 **_request(rowptr, col, row0, target_ids, T, out))
+    return _launch(nat.load().spp_graph_agg_weighted_forward, d, workspace, out)
+
+
 def _agg_parts_launch(src, off, rowptr, col, epilogue, self_scale, row0, target_ids, T, out, workspace, scale_log2=None):
     """spp_graph_agg_parts_forward: ``src`` is ``_parts_source``'s (base addresses, row stride, dtype, F); with
     ``scale_log2`` spp_graph_agg_parts_forward_fp8 over e4m3 parts"""
@@ -440,6 +452,92 @@ def graph_aggregate(x, rowptr, col, *, row0=None, num_targets=None, target_ids=N
                            workspace, graph_agg_workspace_bytes, T)
     out = torch.empty((T, 2 * Fdim if epilogue in _WIDE_EPILOGUES else Fdim), dtype=out_dtype, device=x.device)
     return _agg_launch(x, rowptr, col, epilogue, self_scale, row0, target_ids, T, out, workspace)
+
+
+_WEIGHTS_NOT_BUILT = ("the weighted aggregation reads one resident fp16 / fp32 / bf16 matrix: a row-partitioned x, fp8 tables "
+                      "and the receptive-field entries take no edge weights")
+
+
+def _check_fill(what, fill):
+    if isinstance(fill, bool) or not isinstance(fill, int) or not 0 <= fill <= 2:
+        raise ValueError(f"{what}: fill must be 0 (no self loops), 1 or 2 (improved), got {fill!r}")
+
+
+def graph_weighted_aggregate(x, rowptr, col, *, weight=None, dinv=None, fill=1, self_weight=None, row0=None,
+                             num_targets=None, target_ids=None, out_dtype=torch.float32, out=None, workspace=None):
+    """The edge-weighted sum over whole rows of the resident graph (``spp_graph_agg_weighted_forward``, include/spp.h
+    f3s): ``out[i] = sum_k c_k * x[col[k]]`` over target i's row, plus a self term, [T, F] fp32 or bf16.
+
+    ``x``, ``rowptr`` / ``col``, the targets (``row0`` and ``num_targets``, or ``target_ids``), ``out_dtype`` and
+    ``workspace`` as ``graph_aggregate``; ``out``: an fp32 / bf16 [T, F] matrix to write into (rows of a larger one
+    allowed).  The weights, all contiguous fp32 without gradient:
+
+      ``weight`` [E]       one value per entry of ``col``; None: every entry weighs 1
+      ``self_weight`` [N]  by global node id: ``self_weight[t] * x[t]`` is added last; None: no self term
+      ``dinv`` [N]         (``gcn_dinv``) instead of ``self_weight``: the kernel forms PyG's gcn_norm itself,
+                           ``c_k = dinv[t] * weight[k] * dinv[col[k]]`` and the self term ``dinv[t] * fill * dinv[t]``
+                           (``fill`` 0, 1 or 2; none for 0) -- the bits of ``models.gcn_norm``'s coefficients over the
+                           whole graph, without an [E] array.  ``fill`` is read only with ``dinv``.
+
+    One fp32 fmaf per entry in CSR order from zero, the self term last: for a row of at most ``graph_agg_chunk()``
+    entries the bits of ``models.weighted_aggregate``; a longer row is chunks of that many entries whose sums are added in
+    chunk order.  An ``Fp8Table``, fp8 features and a row-partitioned ``x`` are refused.  Forward only; nothing here
+    waits for the device."""
+    what = "graph_weighted_aggregate"
+    if isinstance(x, (list, tuple, P2PPeers)):
+        raise NotImplementedError(f"{what}: x is row-partitioned ({type(x).__name__}); {_WEIGHTS_NOT_BUILT}")
+    _check_matrix(x, what, fp8_reason=_WEIGHTS_NOT_BUILT)
+    N, Fdim = x.shape
+    _check_graph(what, N, rowptr, col)
+    if weight is not None:
+        _check_fp32(what, "weight", weight, (col.numel(),), "one value per entry of col")
+    if dinv is not None:
+        if self_weight is not None:
+            raise ValueError(f"{what}: give dinv or self_weight, not both (with dinv the self term is "
+                             "dinv[t] * fill * dinv[t])")
+        _check_fp32(what, "dinv", dinv, (N,), "one value per graph node: gcn_dinv")
+        _check_fill(what, fill)
+    if self_weight is not None:
+        _check_fp32(what, "self_weight", self_weight, (N,), "one value per graph node, by global id")
+    _check_out_dtype(what, out_dtype)
+    row0, target_ids, T = _check_targets(what, N, row0, num_targets, target_ids)
+    _check_out(what, out, out_dtype, T, Fdim)
+    workspace = _on_device(what, "x, rowptr, col, weight, dinv, self_weight, target_ids, workspace and out", x.device,
+                           [x, rowptr, col, weight, dinv, self_weight, target_ids, out], workspace,
+                           graph_agg_workspace_bytes, T)
+    if out is None:
+        out = torch.empty((T, Fdim), dtype=out_dtype, device=x.device)
+    return _agg_weighted_launch(x, rowptr, col, weight, dinv, fill if dinv is not None else 0, self_weight, row0,
+                                target_ids, T, out, workspace)
+
+
+def gcn_dinv(rowptr, edge_weight=None, *, add_self_loops=True, improved=False):
+    """``deg^-1/2`` of PyG's gcn_norm over the whole graph (``spp_gcn_dinv``): fp32 [N] with
+    ``dinv[t] = (fill + sum of row t's edge_weight)^-1/2`` in CSR order -- the row length without ``edge_weight`` -- and 0
+    where that is inf; ``fill`` = 1, 2 with ``improved``, 0 without self loops.  The first pass of ``models.gcn_norm``
+    (the same kernel, the same bits) without its [E] coefficients: ``graph_weighted_aggregate(dinv=...)`` forms those.
+    One thread walks a row, a hub's included; it runs once per evaluation."""
+    what = "gcn_dinv"
+    if not isinstance(rowptr, torch.Tensor) or rowptr.dtype != torch.int64 or rowptr.dim() != 1 or rowptr.numel() < 1 \
+            or not rowptr.is_contiguous():
+        raise ValueError(f"{what}: rowptr must be a contiguous 1-D int64 tensor of N + 1 entries")
+    if edge_weight is not None:
+        if not isinstance(edge_weight, torch.Tensor) or edge_weight.dtype != torch.float32 or edge_weight.dim() != 1 \
+                or not edge_weight.is_contiguous():
+            raise ValueError(f"{what}: edge_weight must be a contiguous 1-D fp32 tensor (one value per entry of col)")
+        if edge_weight.requires_grad:
+            raise RuntimeError(f"{what}: edge_weight requires grad, and inference is forward only (detach it)")
+    nat.require_device()
+    if not rowptr.is_cuda or (edge_weight is not None and edge_weight.device != rowptr.device):
+        raise ValueError(f"{what}: rowptr and edge_weight must live on one CUDA device")
+    from .models import _gcn_fill
+    N = rowptr.numel() - 1
+    dinv = torch.empty(N, dtype=torch.float32, device=rowptr.device)
+    d = nat.GcnDinvDesc(fill=_gcn_fill(add_self_loops, improved), rowptr_dev=_p(rowptr), num_nodes=N, w_dev=_p(edge_weight),
+                        dinv_dev=_p(dinv))
+    with torch.cuda.device(rowptr.device):
+        nat.check(nat.load().spp_gcn_dinv(C.byref(d), _stream()))
+    return dinv
 
 
 def graph_aggregate_parts(parts, part_offsets, rowptr, col, *, row0=None, num_targets=None, target_ids=None,
@@ -723,8 +821,8 @@ class _Resident:
     lo = 0
     head_tiles = staticmethod(_row_tiles)                 # the tiles of a block of SAGEResInception's head, as they are
 
-    def __init__(self, x, rowptr, col):
-        self.x, self.rowptr, self.col = x, rowptr, col
+    def __init__(self, x, rowptr, col, edge_weight=None):
+        self.x, self.rowptr, self.col, self.edge_weight = x, rowptr, col, edge_weight      # (edge_weight: GCN only)
         self.n_local, self.dev = x.size(0), x.device
 
     def bind(self):
@@ -750,6 +848,12 @@ class _Resident:
         ``graph`` = (rowptr, col) whose ids are rows of ``cur`` when the layer's plan names one (a receptive field's)"""
         rowptr, col = graph or (self.rowptr, self.col)
         return _agg_launch(cur, rowptr, col, epilogue, self_scale, -1 if ids is not None else s, ids, T, out, ws)
+
+    def aggregate_weighted(self, cur, dinv, fill, s, ids, T, out, ws):
+        """GCN: ``cur`` summed with the placement's edge weights (ones without) for the slab [s, s + T) or the global
+        ``ids``; with ``dinv`` the kernel forms gcn_norm's coefficients and the self term from it and ``fill``"""
+        return _agg_weighted_launch(cur, self.rowptr, self.col, self.edge_weight, dinv, fill, None,
+                                    -1 if ids is not None else s, ids, T, out, ws)
 
     def gat_rows(self, rows, H, Cc, dtype):
         """(h, logits) of a GAT layer over ``rows`` input rows: the projected rows [rows, H * Cc] and where
@@ -1173,9 +1277,75 @@ def _resinc_layers(model, place, nodes, rows_per_slab, act_dtype, sink):
     return sink.result()
 
 
-def _check_model(model, what, names):
-    """one of the four models, with what the GAT and SAGEResInception drivers need of its layers (SAGE and GIN: nothing)"""
-    from .models import GAT, GIN, SAGE, SAGEResInception
+def _gcn_layers(model, place, nodes, rows_per_slab, act_dtype, sink):
+    """GCN over one resident matrix (f3s), in ``GCNConv.forward``'s order -- aggregate first, project second.  Per layer,
+    slab by slab:
+
+      aggregate  ``spp_graph_agg_weighted_forward`` over each node's whole row of the layer's input, [T, K] in
+                 ``act_dtype``.  ``normalize=False`` (the reference's model): the entries weigh ``edge_weight`` (ones
+                 without), no self term.  ``normalize=True``: PyG's gcn_norm of the whole graph, formed IN the kernel from
+                 ``dinv`` = ``gcn_dinv(rowptr, edge_weight)`` -- fp32 [N], computed once per call and ``fill`` -- with
+                 the self term ``fill * dinv[t]^2``.
+      project    tile @ lin.weight^T (+ bias) over the fixed row tiles
+      tail       every layer but the last: relu(BatchNorm) on the running statistics, under bf16 autocast when
+                 ``act_dtype`` is bf16 (as GIN's ``conv.nn``); dropout is the identity.  The last layer's logits go to
+                 ``sink`` tile by tile.
+
+    Memory, as arithmetic: two [N, hidden] matrices of ``act_dtype`` at a layer boundary, as for SAGE, plus a slab's
+    [rows_per_slab, K] aggregate and, with ``normalize=True``, ``dinv``: 4 * N bytes (0.44 GB at N = 111 M).  NO [E]
+    array is allocated on either path: the coefficients PyG would materialise are 4 * E bytes (12.8 GB at E = 3.2 G),
+    and so are the ones of a valueless ``adj_t``; a caller's ``edge_weight`` is read in place."""
+    from .models import _gcn_fill
+    amp = act_dtype == torch.bfloat16
+    n_layers, dev = len(model.convs), place.dev
+    plan = _whole_graph_plan(place, nodes, n_layers)
+    ws = torch.empty(graph_agg_workspace_bytes(min(rows_per_slab, max([place.n_local] + [st.rows for st in plan]))),
+                     dtype=torch.uint8, device=dev)
+    dinvs = {}                                           # fill -> dinv [N]: once per call (the convs share one setting)
+    cur = place.x
+    for i, conv in enumerate(model.convs):
+        last = i == n_layers - 1
+        dinv, fill = None, 0
+        if conv.normalize:
+            fill = _gcn_fill(conv.add_self_loops, conv.improved)
+            if fill not in dinvs:
+                dinvs[fill] = gcn_dinv(place.rowptr, place.edge_weight, add_self_loops=conv.add_self_loops,
+                                       improved=conv.improved)
+            dinv = dinvs[fill]
+        Wt = conv.lin.weight.to(act_dtype).t()
+        bias = conv.bias.to(act_dtype) if conv.bias is not None else None
+        bn = model.bns[i]
+        step = plan[i]
+        rows, names = step.rows, step.names
+        nxt = None
+        if last:
+            sink.open(place, rows, conv.lin.out_features)
+        for s, T, tids in _slabs(rows, step.ids, rows_per_slab):
+            A = torch.empty((T, cur.size(1)), dtype=act_dtype, device=dev)
+            place.aggregate_weighted(cur, dinv, fill, s, tids, T, A, ws)
+            for r, n, tile in _row_tiles(A):
+                Z = torch.addmm(bias, tile, Wt) if bias is not None else tile @ Wt
+                if last:
+                    sink.put(s + r, n, Z, names[s + r:s + r + n] if names is not None else None)
+                    continue
+                with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+                    h = torch.relu(bn(Z))                # (eval mode: the running statistics)
+                if nxt is None:
+                    nxt = place.layer_rows(i, last, rows, h.size(1), act_dtype)
+                nxt[s + r:s + r + n] = h[:n]
+        if nxt is None and not last:                     # no rows at all
+            nxt = place.layer_rows(i, last, 0, model.hidden_channels, act_dtype)
+        cur = nxt                                        # (drops layer i-1's matrix)
+        place.boundary()
+    return sink.result()
+
+
+def _check_model(model, what, names, gcn=False):
+    """one of the four models -- or, for the resident whole-graph entries (``gcn``), GCN -- with what the GAT and
+    SAGEResInception drivers need of its layers (SAGE, GIN and GCN: nothing)"""
+    from .models import GAT, GCN, GIN, SAGE, SAGEResInception
+    if gcn and isinstance(model, GCN):
+        return
     if not isinstance(model, (SAGE, GIN, GAT, SAGEResInception)):
         raise NotImplementedError(f"{what}: implemented for {names}, not {type(model).__name__}")
     if isinstance(model, SAGEResInception):
@@ -1203,9 +1373,9 @@ def _check_run(what, act_dtype, rows_per_slab, nodes):
 def _score(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None):
     """the frame of every driver: eval mode (restored), no gradient, autocast off, the table's device current; a rank
     that fails aborts the placement, so that its peers raise instead of waiting, and every mapping is closed"""
-    from .models import GAT, SAGEResInception
+    from .models import GAT, GCN, SAGEResInception
     layers = _gat_layers if isinstance(model, GAT) else _resinc_layers if isinstance(model, SAGEResInception) \
-        else _conv_layers
+        else _gcn_layers if isinstance(model, GCN) else _conv_layers
     was_training = model.training
     model.eval()
     try:
@@ -1222,12 +1392,19 @@ def _score(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None):
         model.train(was_training)
 
 
-def layerwise_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 << 20, act_dtype=torch.float32):
+def layerwise_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 << 20, act_dtype=torch.float32,
+                        edge_weight=None):
     """Exact log-probabilities of every node, [N, classes] fp32 -- or of ``nodes`` (int64, any order, duplicates
-    allowed), [len(nodes), classes] -- for a ``SAGE``, ``GIN``, ``GAT`` or ``SAGEResInception`` model over the whole
-    graph.  (GAT, at any ``heads``: see ``_gat_layers`` for its order of operations and memory; SAGEResInception:
-    ``_resinc_layers``; what follows describes SAGE and GIN, ``_conv_layers``, and the arguments, the fixed GEMM tiles,
-    eval mode and ``nodes`` mean the same for all four.)
+    allowed), [len(nodes), classes] -- for a ``SAGE``, ``GIN``, ``GAT``, ``SAGEResInception`` or ``GCN`` model over the
+    whole graph.  (GAT, at any ``heads``: see ``_gat_layers`` for its order of operations and memory; SAGEResInception:
+    ``_resinc_layers``; GCN: ``_gcn_layers``; what follows describes SAGE and GIN, ``_conv_layers``, and the arguments,
+    the fixed GEMM tiles, eval mode and ``nodes`` mean the same for all five.)
+
+    ``edge_weight`` (GCN only; a ``ValueError`` with any other model): contiguous fp32 [E], one value per entry of
+    ``col`` -- what ``adj_t`` carries in training; None: every entry weighs 1.  GCN reads one resident fp16 / fp32 / bf16
+    matrix through ``spp_graph_agg_weighted_forward``: with ``normalize=True`` the kernel forms PyG's coefficients from
+    ``gcn_dinv``'s fp32 [N] (4 * N bytes, 0.44 GB at N = 111 M), so neither path allocates an [E] array (12.8 GB of
+    fp32 at E = 3.2 G); an ``Fp8Table`` and the partitioned and field entries take no weights and refuse the model.
 
     Layer by layer, slab by slab of ``rows_per_slab`` nodes: ``spp_graph_agg_forward`` over each node's whole neighbour
     row, then the layer's own parameters as torch GEMMs (SAGE: [mean | x] @ [W_l | W_r]^T; GIN: ``conv.nn`` with
@@ -1245,7 +1422,8 @@ def layerwise_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 <<
     boundary (layer i-1's is freed as soon as layer i is complete).  At N = 111 M and hidden 256 that is 113 GB each in
     fp32 and 57 GB in bf16, next to 26 GB of graph and 28 GB of features: fp32 activations do not fit one 288 GB MI355X
     at papers scale, ``act_dtype=torch.bfloat16`` does (26 + 28 + 2 * 57 = 168 GB)."""
-    return _resident("layerwise_inference", model, x, rowptr, col, nodes, rows_per_slab, act_dtype, None, _LogProbs())
+    return _resident("layerwise_inference", model, x, rowptr, col, nodes, rows_per_slab, act_dtype, None, _LogProbs(),
+                     edge_weight)
 
 
 def _check_labels(what, name, y, rows):
@@ -1256,12 +1434,26 @@ def _check_labels(what, name, y, rows):
                          f"{tuple(y.shape)} {y.dtype}")
 
 
-def _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, y, sink):
+def _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, y, sink, edge_weight=None):
     """the resident entries: every argument check, then the device, then the pass into ``sink``"""
-    _check_model(model, what, "SAGE and GIN (and GAT, SAGEResInception)")
-    _check_table(x, what)
+    from .models import GCN
+    _check_model(model, what, "SAGE and GIN (and GAT, SAGEResInception, GCN)", gcn=True)
+    gcn = isinstance(model, GCN)
+    if edge_weight is not None and not gcn:
+        raise ValueError(f"{what}: edge_weight is GCN's (the values its adj_t carries in training); "
+                         f"{type(model).__name__} has no weighted aggregation")
+    if gcn:
+        if isinstance(x, (list, tuple, P2PPeers)):
+            raise NotImplementedError(f"{what}: GCN over a row-partitioned x ({type(x).__name__}); {_WEIGHTS_NOT_BUILT}")
+        _check_matrix(x, what, fp8_reason=f"GCN: {_WEIGHTS_NOT_BUILT}")
+    else:
+        _check_table(x, what)
     N = x.size(0)
     _check_graph(what, N, rowptr, col)
+    if edge_weight is not None:
+        _check_fp32(what, "edge_weight", edge_weight, (col.numel(),), "one value per entry of col, as adj_t carries them")
+        if edge_weight.device != col.device:
+            raise ValueError(f"{what}: edge_weight must live on col's device")
     rows_per_slab = _check_run(what, act_dtype, rows_per_slab, nodes)
     if y is not None:
         _check_labels(what, "y", y, N)
@@ -1274,7 +1466,7 @@ def _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, y, s
         nodes = nodes.to(x.device).contiguous()
         if nodes.numel() and not (0 <= int(nodes.min()) and int(nodes.max()) < N):      # (one read-back, up front)
             raise ValueError(f"{what}: nodes outside the graph's {N} nodes")
-    return _score(model, _Resident(x, rowptr, col), nodes, rows_per_slab, act_dtype, sink)
+    return _score(model, _Resident(x, rowptr, col, edge_weight), nodes, rows_per_slab, act_dtype, sink)
 
 
 def _check_splits(what, splits, nodes):
@@ -1297,7 +1489,8 @@ def _check_splits(what, splits, nodes):
     return torch.cat(list(splits.values())), segments
 
 
-def evaluate(model, x, rowptr, col, y=None, *, nodes=None, splits=None, rows_per_slab=1 << 20, act_dtype=torch.float32):
+def evaluate(model, x, rowptr, col, y=None, *, nodes=None, splits=None, rows_per_slab=1 << 20, act_dtype=torch.float32,
+             edge_weight=None):
     """Exact whole-graph evaluation: ``layerwise_inference``'s pass -- the same checks, layer loops, fixed GEMM tiles and
     eval-mode frame -- with the other tail: each tile of the last layer's logits goes through ``classify_rows``
     (``spp_classify_rows``) into its rows of ``pred`` and ``nll``, and no [rows, classes] matrix is ever allocated
@@ -1309,10 +1502,10 @@ def evaluate(model, x, rowptr, col, y=None, *, nodes=None, splits=None, rows_per
     of the lists once (``pred`` and ``nll`` follow it) and also returns labelled / correct / loss per name.  A node's
     ``pred`` and ``nll`` are the same bits whatever ``rows_per_slab`` is and whether ``nodes`` selected it; ``pred[i]`` is
     the argmax of the logits, so ``layerwise_inference``'s row attains its maximum there.  The counts are reduced on the
-    device and read back once, at the end."""
+    device and read back once, at the end.  ``edge_weight``: GCN's entry weights, as ``layerwise_inference`` takes them."""
     what = "evaluate"
     nodes, segments = _check_splits(what, splits, nodes)
-    sink = _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, y, _Classify(y))
+    sink = _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, y, _Classify(y), edge_weight)
     return _evaluation(sink, y, None if nodes is None else nodes.to(x.device), segments)
 
 

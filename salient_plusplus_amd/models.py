@@ -1555,8 +1555,10 @@ class GCN(torch.nn.Module):
         return torch.log_softmax(x, dim=-1)
 
     def inference(self, x_all, rowptr, col, **kw):
-        raise NotImplementedError("GCN.inference: exact layer-wise GCN inference is not built (the resident-graph "
-                                  "aggregation entries take no edge weights)")
+        raise NotImplementedError("GCN.inference: not a method of the model yet; the weighted sum over whole neighbour "
+                                  "rows that layer-wise inference needs is spp_graph_agg_weighted_forward: call "
+                                  "inference.layerwise_inference(model, x_all, rowptr, col, edge_weight=..., ...) or "
+                                  "inference.evaluate, which accept GCN on a resident table")
 
 
 # --------------------------------------------------------------------------------------------

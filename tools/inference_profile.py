@@ -5,6 +5,7 @@ with bf16 activations, timed per layer, and layer 1's slabs once more through th
     python tools/inference_profile.py [--workload S-papers] [--rows-per-slab 1048576] [--hidden 256] [--json out.json]
     python tools/inference_profile.py --model gat [--heads 4] [--repeats 3] ...
     python tools/inference_profile.py --model sageresinception [--nodes 1500000] [--torch-epilogue] [--repeats 3] ...
+    python tools/inference_profile.py --model gcn [--repeats 3] ...      (``gcn_leg``: the weighted kernels against the sum)
     python tools/inference_profile.py --evaluate [--repeats 3] ...
     python tools/inference_profile.py --parts 8 --workload S-products [--repeats 5] ...
     python tools/inference_profile.py --parts 8 --model gat --workload S-products [--heads 1] [--repeats 9] ...
@@ -65,7 +66,7 @@ def main():
     ap.add_argument("--hidden", type=int, default=256)
     ap.add_argument("--classes", type=int, default=172)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--model", choices=("sage", "gat", "sageresinception"), default="sage")
+    ap.add_argument("--model", choices=("sage", "gat", "sageresinception", "gcn"), default="sage")
     ap.add_argument("--heads", type=int, default=1)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--nodes", type=int, default=1_500_000, help="sageresinception: nodes scored (0 = all)")
@@ -99,6 +100,8 @@ def main():
         return gat_leg(a, wl, res)
     if a.model == "sageresinception":
         return resinc_leg(a, wl, res)
+    if a.model == "gcn":
+        return gcn_leg(a, wl, res)
     if a.evaluate:
         return evaluate_leg(a, wl, res)
 
@@ -150,6 +153,79 @@ def main():
     res["layer1_hop_kernel_s"] = round(hop_s, 4)
     res["layer1_hop_kernel_worst_slab"] = {"row0": worst[1], "s": round(worst[0], 4)}
     print(json.dumps({k: res[k] for k in ("total_s", "layer1_hop_kernel_s", "layer1_hop_kernel_worst_slab")}), flush=True)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+def gcn_leg(a, wl, res):
+    """``--model gcn``: (1) the weighted kernel pair against the plain sum on the same rows -- every slab of the table
+    (F = 128 fp16 -> fp32) through ``graph_aggregate(epilogue="sum")``, ``graph_weighted_aggregate()`` (weights of one)
+    and ``graph_weighted_aggregate(dinv=...)`` (gcn_norm formed in the kernel), one warm-up pass over all slabs and then
+    ``--repeats`` passes with the three alternating slab by slab, events around each call, the median pass per variant;
+    (2) one ``layerwise_inference`` of GCN 3 x hidden (bf16 activations), ``normalize`` False and True, next to SAGE's
+    on the same graph in the same process, the median of ``--repeats`` each after a warm-up"""
+    from salient_plusplus_amd import inference as inf
+    from salient_plusplus_amd.models import GCN, SAGE
+    x, rowptr, col = wl.x, wl.rowptr, wl.col
+    N, dev = x.size(0), x.device
+    res.update(model="gcn", F=x.size(1), x_bytes_per_elem=x.element_size())
+    ws = torch.empty(inf.graph_agg_workspace_bytes(min(a.rows_per_slab, N)), dtype=torch.uint8, device=dev)
+    out = torch.empty((min(a.rows_per_slab, N), x.size(1)), dtype=torch.float32, device=dev)
+    b, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    b.record()
+    dinv = inf.gcn_dinv(rowptr)
+    e.record()
+    e.synchronize()
+    res["gcn_dinv_s"] = round(b.elapsed_time(e) / 1e3, 4)
+    variants = {
+        "sum": lambda s, T: inf.graph_aggregate(x, rowptr, col, row0=s, num_targets=T, epilogue="sum", workspace=ws),
+        "weighted_ones": lambda s, T: inf.graph_weighted_aggregate(x, rowptr, col, row0=s, num_targets=T, out=out[:T],
+                                                                   workspace=ws),
+        "weighted_dinv": lambda s, T: inf.graph_weighted_aggregate(x, rowptr, col, dinv=dinv, fill=1, row0=s,
+                                                                   num_targets=T, out=out[:T], workspace=ws),
+    }
+    passes = {k: [] for k in variants}
+    for p in range(a.repeats + 1):                        # pass 0 warms up
+        tot = dict.fromkeys(variants, 0.0)
+        for s in range(0, N, a.rows_per_slab):
+            T = min(a.rows_per_slab, N - s)
+            for k, fn in variants.items():
+                b.record()
+                o = fn(s, T)
+                e.record()
+                e.synchronize()
+                tot[k] += b.elapsed_time(e) / 1e3
+                del o
+        if p:
+            for k in variants:
+                passes[k].append(round(tot[k], 4))
+    med = {k: sorted(v)[len(v) // 2] for k, v in passes.items()}
+    res["kernel_passes_s"], res["kernel_median_s"] = passes, med
+    res["ratio_ones_over_sum"] = round(med["weighted_ones"] / med["sum"], 3)
+    res["ratio_dinv_over_sum"] = round(med["weighted_dinv"] / med["sum"], 3)
+    print(json.dumps({k: res[k] for k in ("gcn_dinv_s", "kernel_median_s", "ratio_ones_over_sum", "ratio_dinv_over_sum")}),
+          flush=True)
+    del out, dinv
+    torch.manual_seed(0)
+    models = {"sage": SAGE(x.size(1), a.hidden, a.classes, 3), "gcn": GCN(x.size(1), a.hidden, a.classes, 3),
+              "gcn_normalize": GCN(x.size(1), a.hidden, a.classes, 3, normalize=True)}
+    res["layerwise_inference_s"] = {}
+    for name, model in models.items():
+        model = model.to(dev)
+        times = []
+        for p in range(a.repeats + 1):
+            torch.cuda.synchronize()
+            t0 = time.time()
+            lp = inf.layerwise_inference(model, x, rowptr, col, rows_per_slab=a.rows_per_slab, act_dtype=torch.bfloat16)
+            torch.cuda.synchronize()
+            if p:
+                times.append(round(time.time() - t0, 3))
+            assert lp.shape == (N, a.classes)
+            del lp
+        res["layerwise_inference_s"][name] = {"passes": times, "median": sorted(times)[len(times) // 2]}
+        print(json.dumps({name: res["layerwise_inference_s"][name]}), flush=True)
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:
