@@ -776,6 +776,53 @@ spp_status spp_gat_mh_aggregate_backward_gather(const int64_t* rowptr_dev, const
                                                 float* grad_a_src_dev, float* grad_a_dst_dev, void* workspace_dev,
                                                 int64_t workspace_bytes, void* stream);
 
+/* f3t  ATTENTION DROPOUT: PyG's GATConv(dropout=p), F.dropout(alpha, p, training) on the attention coefficients.  The
+ *      three aggregate entries above with (p, training, seed) appended after `stream`; everything else as above.
+ *        alpha_ij = softmax_j(leaky_relu(a_src[j,h] + a_dst[i,h]))   over ALL entries: the mask never enters the softmax
+ *        q_ij     = keep_ij / (1 - p)        keep in {0, 1} per (entry, head), the self loop included
+ *        z[i,h,:] = sum_j q_ij alpha_ij x_j
+ *      row_max and row_sum are exactly the values of the entry without dropout.  Backward, with go = g_i . z_i on the
+ *      saved (dropped) z and gh = g_i . x_j:  ge = alpha_ij (q_ij gh - go) lrelu'(raw) (a dropped entry still sends
+ *      -alpha go to its logits: dL/dalpha_ij = q_ij gh and sum_k alpha_ik q_ik gh_ik = go);  grad_x[j,:] += sum_h q_ij
+ *      alpha_ij g_i^h;  the gather form's alpha_e / alpha_self hold q alpha.  Forward and backward take the same (p, seed).
+ *   Keep rule (csrc/act_keep.hip.h attn_keep_heads; mix64 = the splitmix64 finaliser, keep_thr = (uint32_t)((1 - p) * 2^32),
+ *   2^32 - 1 at p = 0, of spp_relu_dropout_forward), with E = rowptr[T] entries, T targets, H heads:
+ *        draw index  i = k * H + h          for CSR entry k (a dropped diagonal entry consumes its index),
+ *                    i = (E + t) * H + h    for target t's self loop;
+ *        draw(i) = the low (i even) or high (i odd) 32 bits of mix64(seed + (i >> 1) * 0x9E3779B97F4A7C15);
+ *        kept iff draw(i) < keep_thr.   One hash serves two heads (at H = 1, two neighbouring entries).
+ *   Refusals: those of the entry each extends, in its order, with `0 <= p < 1` checked right after the head count,
+ *   x_elem and K (so before the sizes and the buffers; a NaN p is refused).  training = 0 or p = 0 runs the kernels of
+ *   the entry without dropout: the same bits.  spp_gat_mh_attn_keep writes the mask keep_dev [(E + T), H] (one byte, 0 / 1,
+ *   entry-major: the E CSR entries, then the T self loops) with the device function the kernels call; it refuses
+ *   negative sizes, a head count outside {1, 2, 4, 8} and p outside [0, 1), in this order.  SPP_ABI_VERSION stays 6. */
+spp_status spp_gat_mh_aggregate_forward_drop(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                                             const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t K,
+                                             int32_t heads, const float* a_src_dev, const float* a_dst_dev,
+                                             float negative_slope, float* z_dev, float* row_max_dev,
+                                             float* row_sum_dev, void* stream, float p, int32_t training,
+                                             uint64_t seed);
+spp_status spp_gat_mh_aggregate_backward_drop(const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets,
+                                              const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t K,
+                                              int32_t heads, const float* a_src_dev, const float* a_dst_dev,
+                                              float negative_slope, const float* z_dev, const float* row_max_dev,
+                                              const float* row_sum_dev, const float* grad_z_dev, float* grad_x_dev,
+                                              float* grad_a_src_dev, float* grad_a_dst_dev, void* stream, float p,
+                                              int32_t training, uint64_t seed);
+spp_status spp_gat_mh_aggregate_backward_gather_drop(const int64_t* rowptr_dev, const int64_t* col_dev,
+                                                     int64_t num_targets, int64_t num_sources, int64_t num_edges,
+                                                     const void* x_dev, int32_t x_elem, int64_t x_stride_elems,
+                                                     int64_t K, int32_t heads, const float* a_src_dev,
+                                                     const float* a_dst_dev, float negative_slope, const float* z_dev,
+                                                     const float* row_max_dev, const float* row_sum_dev,
+                                                     const float* grad_z_dev, const float* v_src_dev,
+                                                     const float* v_dst_dev, float* grad_x_dev, float* grad_a_src_dev,
+                                                     float* grad_a_dst_dev, void* workspace_dev,
+                                                     int64_t workspace_bytes, void* stream, float p, int32_t training,
+                                                     uint64_t seed);
+spp_status spp_gat_mh_attn_keep(int64_t num_edges, int64_t num_targets, int32_t heads, float p, uint64_t seed,
+                                uint8_t* keep_dev, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * f3  Sum aggregation of GINConv over one MFG hop (driver/models.py:234-283: GINConv(nn) with PyG's
  *     defaults eps = 0, train_eps = False, aggr='add', on ((x, x_target), adj_t)); fp32 accumulate and output.

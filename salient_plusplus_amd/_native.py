@@ -319,6 +319,15 @@ SIGNATURES = {
     "spp_gat_mh_aggregate_backward_gather_workspace_bytes": (i64, [i64, i64, i64, i32]),
     "spp_gat_mh_aggregate_backward_gather": (C.c_int, [p, p, i64, i64, i64, p, i32, i64, i64, i32, p, p, C.c_float, p,
                                                        p, p, p, p, p, p, p, p, p, i64, p]),
+    # attention dropout (spp.h f3t): the three entries above + (p, training, seed), and the mask they use
+    "spp_gat_mh_aggregate_forward_drop": (C.c_int, [p, p, i64, p, i32, i64, i64, i32, p, p, C.c_float, p, p, p, p,
+                                                    C.c_float, i32, C.c_uint64]),
+    "spp_gat_mh_aggregate_backward_drop": (C.c_int, [p, p, i64, p, i32, i64, i64, i32, p, p, C.c_float, p, p, p, p, p,
+                                                     p, p, p, C.c_float, i32, C.c_uint64]),
+    "spp_gat_mh_aggregate_backward_gather_drop": (C.c_int, [p, p, i64, i64, i64, p, i32, i64, i64, i32, p, p, C.c_float,
+                                                            p, p, p, p, p, p, p, p, p, p, i64, p, C.c_float, i32,
+                                                            C.c_uint64]),
+    "spp_gat_mh_attn_keep": (C.c_int, [i64, i64, i32, C.c_float, C.c_uint64, p, p]),
     "spp_sage_operand_forward_rows": (C.c_int, [p, p, i64, p, i32, i64, p, i64, p]),
     "spp_gather_row_refs": (C.c_int, [p, i64, i64, p, p]),
     "spp_ipc_export": (C.c_int, [p, p, C.POINTER(i64)]),

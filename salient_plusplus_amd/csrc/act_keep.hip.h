@@ -50,6 +50,25 @@ __device__ __forceinline__ f4 relu_dropout4(f4 v, int64_t i4, const ActArgs& a) 
   return o;
 }
 
+// Attention dropout (GATConv's dropout=, spp.h f3t): keep / drop of the H heads of softmax entry `entry` -- CSR entry k
+// is entry k, target t's self loop is entry E + t -- draw index i = entry * H + h, the low (i even) or high (i odd) half
+// of mix64(seed + (i >> 1) * 0x9E3779B97F4A7C15): one hash serves two heads, and at H = 1 two neighbouring entries.
+template <int H>
+__device__ __forceinline__ void attn_keep_heads(uint64_t entry, const ActArgs& a, bool (&keep)[H]) {
+  if constexpr (H == 1) {
+    const uint64_t r = mix64(a.seed + (entry >> 1) * 0x9E3779B97F4A7C15ull);
+    keep[0] = (uint32_t)(entry & 1 ? r >> 32 : r) < a.keep_thr;
+  } else {
+    const uint64_t base = a.seed + entry * (uint64_t)(H / 2) * 0x9E3779B97F4A7C15ull;  // (i >> 1) = entry * H/2 + h/2
+#pragma unroll
+    for (int q = 0; q < H / 2; ++q) {
+      const uint64_t r = mix64(base + (uint64_t)q * 0x9E3779B97F4A7C15ull);
+      keep[2 * q] = (uint32_t)r < a.keep_thr;
+      keep[2 * q + 1] = (uint32_t)(r >> 32) < a.keep_thr;
+    }
+  }
+}
+
 static inline ActArgs act_args(float p, int32_t training, uint64_t seed) {
   const double keep = 1.0 - (double)p;
   ActArgs a{};

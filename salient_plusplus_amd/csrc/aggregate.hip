@@ -967,15 +967,19 @@ __global__ __launch_bounds__(kColsumNT) void k_gat_mh_colsum(const Tin* __restri
 
 // z[i,h,:] = sum_j alpha_ij^h x_j over row i (its diagonal entry dropped) plus the self loop; x rows fp16, bf16 or fp32,
 // 4 columns per lane, online softmax (every lane of a row's group walks the same edges) with H softmax states and
-// accumulators; per edge one load of the H logits and one of the row chunk, shared by the heads
-template <typename Tin, int H>
+// accumulators; per edge one load of the H logits and one of the row chunk, shared by the heads.
+// kDrop (attention dropout, spp.h f3t): z[i,h,:] = sum_j q_ij^h alpha_ij^h x_j, q = keep / (1 - p) per (entry, head)
+// from attn_keep_heads (entry k for CSR entry k, E + t for t's self loop).  The softmax runs over ALL entries (row_max
+// and row_sum are the kDrop = false values); only the accumulator skips a dropped entry.  Every lane of a row's group
+// hashes for itself: the walk has no cross-lane step to hand a draw over in, and the hashes overlap the loads' latency.
+template <typename Tin, int H, bool kDrop>
 __global__ __launch_bounds__(kAggNT) void k_gat_mh_agg_fwd(const int64_t* __restrict__ rowptr,
                                                            const int64_t* __restrict__ col, int64_t T,
                                                            const Tin* __restrict__ x, int64_t x_stride, int64_t K,
                                                            const float* __restrict__ a_src,
                                                            const float* __restrict__ a_dst, float slope, int lpr_log2,
                                                            float* __restrict__ z, float* __restrict__ row_max,
-                                                           float* __restrict__ row_sum) {
+                                                           float* __restrict__ row_sum, ActArgs drop) {
   const int lpr = 1 << lpr_log2;
   const int lane = threadIdx.x & (lpr - 1);
   const int64_t t = ((int64_t)blockIdx.x * kAggNT + threadIdx.x) >> lpr_log2;
@@ -986,6 +990,8 @@ __global__ __launch_bounds__(kAggNT) void k_gat_mh_agg_fwd(const int64_t* __rest
   load_heads<H>(a_src + t * H, self);
 #pragma unroll
   for (int h = 0; h < H; ++h) self[h] = lrelu(self[h] + ad[h], slope);
+  [[maybe_unused]] bool kself[H];
+  if constexpr (kDrop) attn_keep_heads<H>((uint64_t)(rowptr[T] + t), drop, kself);  // E = rowptr[T]
   for (int64_t c = (int64_t)lane * 4; c < K || c == (int64_t)lane * 4; c += (int64_t)lpr * 4) {
     const bool has = c < K;
     const f4 xt = has ? load4(x + t * x_stride + c) : f4{0.f, 0.f, 0.f, 0.f};
@@ -994,6 +1000,8 @@ __global__ __launch_bounds__(kAggNT) void k_gat_mh_agg_fwd(const int64_t* __rest
 #pragma unroll
     for (int h = 0; h < H; ++h) {
       acc[h] = xt;
+      if constexpr (kDrop)
+        if (!kself[h]) acc[h] = f4{0.f, 0.f, 0.f, 0.f};
       mm[h] = self[h];
       ss[h] = 1.f;
     }
@@ -1016,6 +1024,8 @@ __global__ __launch_bounds__(kAggNT) void k_gat_mh_agg_fwd(const int64_t* __rest
 #pragma unroll
       for (int u = 0; u < kNb; ++u) {
         if (k0 + u >= e || j[u] == t) continue;  // set_diag drops existing diagonal entries
+        [[maybe_unused]] bool keep[H];
+        if constexpr (kDrop) attn_keep_heads<H>((uint64_t)(k0 + u), drop, keep);
 #pragma unroll
         for (int h = 0; h < H; ++h) {
           const float sc = lrelu(as[u][h] + ad[h], slope);
@@ -1027,6 +1037,8 @@ __global__ __launch_bounds__(kAggNT) void k_gat_mh_agg_fwd(const int64_t* __rest
           }
           const float w = __expf(sc - mm[h]);
           ss[h] += w;
+          if constexpr (kDrop)
+            if (!keep[h]) continue;
           acc[h].x += w * xv[u].x; acc[h].y += w * xv[u].y; acc[h].z += w * xv[u].z; acc[h].w += w * xv[u].w;
         }
       }
@@ -1034,7 +1046,7 @@ __global__ __launch_bounds__(kAggNT) void k_gat_mh_agg_fwd(const int64_t* __rest
     if (has) {
 #pragma unroll
       for (int h = 0; h < H; ++h) {
-        const float inv = 1.f / ss[h];
+        const float inv = (kDrop ? drop.scale : 1.f) / ss[h];
         *reinterpret_cast<float4*>(z + (t * H + h) * K + c) =
             make_float4(acc[h].x * inv, acc[h].y * inv, acc[h].z * inv, acc[h].w * inv);
       }
@@ -1057,18 +1069,22 @@ __global__ __launch_bounds__(kAggNT) void k_gat_mh_agg_fwd(const int64_t* __rest
 // rate on contiguous 256-byte wave instructions and ~17x slower on scattered ones).
 // alpha_e / alpha_self (optional): the attention weights of every CSR entry (0 for a dropped diagonal entry) and of
 // every target's self loop -- what the input gradient by GATHER over the transposed hop needs (k_gat_mh_gx_gather).
-template <typename Tin, int H, bool kVec>
+// kDrop (attention dropout, the forward's (p, seed)): go is taken on the saved DROPPED z, so sum_k alpha_ik q_ik gh_ik = go
+// and ge^h = alpha (q gh - go) lrelu'(raw) -- a dropped entry still sends -alpha go to its logits;  grad_x takes q alpha,
+// and alpha_e / alpha_self hold q alpha (what k_gat_mh_gx_gather multiplies by); ge uses the plain alpha.
+template <typename Tin, int H, bool kVec, bool kDrop>
 __global__ __launch_bounds__(kAggNT) void k_gat_mh_agg_bwd(
     const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col, int64_t T, const Tin* __restrict__ x,
     int64_t x_stride, int64_t K, const float* __restrict__ a_src, const float* __restrict__ a_dst, float slope,
     const float* __restrict__ z, const float* __restrict__ row_max, const float* __restrict__ row_sum,
     const float* __restrict__ g, int lpt_log2, float* __restrict__ grad_x, float* __restrict__ grad_a_src,
-    float* __restrict__ grad_a_dst, float* __restrict__ alpha_e, float* __restrict__ alpha_self) {
+    float* __restrict__ grad_a_dst, float* __restrict__ alpha_e, float* __restrict__ alpha_self, ActArgs drop) {
   const int lpt = 1 << lpt_log2;
   const int lane = threadIdx.x & (lpt - 1);
   const int64_t t = ((int64_t)blockIdx.x * kAggNT + threadIdx.x) >> lpt_log2;
   const bool live = t < T;
   const int64_t b = live ? rowptr[t] : 0, e = live ? rowptr[t + 1] : -1;
+  [[maybe_unused]] const int64_t E = kDrop ? rowptr[T] : 0;  // the self loops' draws come after the E entries'
   float ad[H], m[H], inv_s[H];
 #pragma unroll
   for (int h = 0; h < H; ++h) ad[h] = m[h] = inv_s[h] = 0.f;
@@ -1117,10 +1133,21 @@ __global__ __launch_bounds__(kAggNT) void k_gat_mh_agg_bwd(
     const int64_t j = !on ? 0 : ((k < b) ? t : col[k]);
     const bool use = on && !(k >= b && j == t);  // set_diag drops existing diagonal entries
     float gh[H], a[H], raw[H];
+    [[maybe_unused]] float q[H];  // kDrop: keep / (1 - p)
 #pragma unroll
     for (int h = 0; h < H; ++h) gh[h] = a[h] = raw[h] = 0.f;
+    if constexpr (kDrop) {
+#pragma unroll
+      for (int h = 0; h < H; ++h) q[h] = 0.f;
+    }
     if (use) {
       load_heads<H>(a_src + j * H, raw);
+      if constexpr (kDrop) {
+        bool keep[H];
+        attn_keep_heads<H>((uint64_t)(k < b ? E + t : k), drop, keep);
+#pragma unroll
+        for (int h = 0; h < H; ++h) q[h] = keep[h] ? drop.scale : 0.f;
+      }
       if (kVec) {  // before the logits are used: their load and the rows' are in flight together
         for (int64_t c = (int64_t)lane * 4; c < K; c += (int64_t)lpt * 4) {
           const f4 xv = load4(x + j * x_stride + c);
@@ -1144,7 +1171,7 @@ __global__ __launch_bounds__(kAggNT) void k_gat_mh_agg_bwd(
           for (int h = 0; h < H; ++h) {
             const float gv = gt[h * K + c];
             gh[h] += gv * xv;
-            gx += a[h] * gv;
+            gx += (kDrop ? q[h] * a[h] : a[h]) * gv;
           }
           unsafeAtomicAdd(grad_x + j * K + c, gx);
         }
@@ -1152,11 +1179,20 @@ __global__ __launch_bounds__(kAggNT) void k_gat_mh_agg_bwd(
     }
 #pragma unroll
     for (int h = 0; h < H; ++h) gh[h] = group_sum(gh[h]);
-    if (alpha_e && on && lane == 0) store_heads<H>(k < b ? alpha_self + t * H : alpha_e + k * H, a);  // 0: dropped entry
+    if (alpha_e && on && lane == 0) {  // 0: dropped entry
+      if constexpr (kDrop) {
+        float qa[H];
+#pragma unroll
+        for (int h = 0; h < H; ++h) qa[h] = q[h] * a[h];
+        store_heads<H>(k < b ? alpha_self + t * H : alpha_e + k * H, qa);
+      } else {
+        store_heads<H>(k < b ? alpha_self + t * H : alpha_e + k * H, a);
+      }
+    }
     if (use) {
 #pragma unroll
       for (int h = 0; h < H; ++h) {
-        const float ge = a[h] * (gh[h] - go[h]) * (raw[h] > 0.f ? 1.f : slope);
+        const float ge = a[h] * ((kDrop ? q[h] * gh[h] : gh[h]) - go[h]) * (raw[h] > 0.f ? 1.f : slope);
         gad[h] += ge;
         if (lane == 0) unsafeAtomicAdd(grad_a_src + j * H + h, ge);
       }
@@ -1289,6 +1325,25 @@ static spp_status gat_check(int32_t heads, int64_t K, const void* x, int64_t x_s
   return SPP_OK;
 }
 static bool al16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+// Attention dropout of the spp_gat_mh_*_drop entries (spp.h f3t); the entries without it pass GatDrop{}.  p is checked
+// right after gat_check, before the sizes; training = 0 or p = 0 runs the kDrop = false kernels.
+struct GatDrop {
+  bool given = false;
+  float p = 0.f;
+  int32_t training = 0;
+  uint64_t seed = 0;
+  bool on() const { return given && training && p > 0.f; }
+  ActArgs args() const { return act_args(p, training, seed); }
+};
+static spp_status gat_drop_check(const GatDrop& dr, const char* who) {
+  SPP_REQUIRE(!dr.given || (dr.p >= 0.f && dr.p < 1.f), "%s: attention dropout needs 0 <= p < 1", who);
+  return SPP_OK;
+}
+// fn(std::bool_constant<kDrop>{})
+template <class Fn>
+static void with_drop(bool on, Fn&& fn) {
+  if (on) fn(std::true_type{}); else fn(std::false_type{});
+}
 // the per-head arrays are read and written H floats at a time (load_heads): 4, 8 and 16-byte accesses at H = 1, 2, >= 4
 static bool al_heads(const void* p, int32_t heads) {
   return reinterpret_cast<uintptr_t>(p) % (4 * std::min<int32_t>(heads, 4)) == 0;
@@ -1352,8 +1407,9 @@ static spp_status gat_aggregate_forward(const char* who, const int64_t* rowptr_d
                                         int64_t num_targets, const void* x_dev, int32_t x_elem, int64_t x_stride_elems,
                                         int64_t K, int32_t heads, const float* a_src_dev, const float* a_dst_dev,
                                         float negative_slope, float* z_dev, float* row_max_dev, float* row_sum_dev,
-                                        void* stream) {
+                                        void* stream, const GatDrop& dr = GatDrop{}) {
   SPP_TRY(gat_check(heads, K, x_dev, x_stride_elems, x_elem, who));
+  SPP_TRY(gat_drop_check(dr, who));
   SPP_REQUIRE(num_targets >= 0, "%s: negative size", who);
   if (num_targets == 0) return SPP_OK;
   SPP_REQUIRE(rowptr_dev && x_dev && a_src_dev && a_dst_dev && z_dev && row_max_dev && row_sum_dev && al16(z_dev) &&
@@ -1362,12 +1418,16 @@ static spp_status gat_aggregate_forward(const char* who, const int64_t* rowptr_d
               "%s: NULL or unaligned buffer", who);
   const int lpr_log2 = lanes_log2(K / 4);
   const unsigned grid = (unsigned)ceil_div(num_targets << lpr_log2, kAggNT);
+  const ActArgs da = dr.on() ? dr.args() : ActArgs{};
   with_elem(x_elem, [&](auto tin) {
     with_heads(heads, [&](auto hh) {
-      using Tin = typename decltype(tin)::type;
-      hipLaunchKernelGGL((k_gat_mh_agg_fwd<Tin, decltype(hh)::value>), dim3(grid), dim3(kAggNT), 0, as_stream(stream),
-                         rowptr_dev, col_dev, num_targets, static_cast<const Tin*>(x_dev), x_stride_elems, K, a_src_dev,
-                         a_dst_dev, negative_slope, lpr_log2, z_dev, row_max_dev, row_sum_dev);
+      with_drop(dr.on(), [&](auto drop) {
+        using Tin = typename decltype(tin)::type;
+        hipLaunchKernelGGL((k_gat_mh_agg_fwd<Tin, decltype(hh)::value, decltype(drop)::value>), dim3(grid),
+                           dim3(kAggNT), 0, as_stream(stream), rowptr_dev, col_dev, num_targets,
+                           static_cast<const Tin*>(x_dev), x_stride_elems, K, a_src_dev, a_dst_dev, negative_slope,
+                           lpr_log2, z_dev, row_max_dev, row_sum_dev, da);
+      });
     });
   });
   SPP_HIP_TRY(hipGetLastError());
@@ -1381,17 +1441,21 @@ static spp_status gat_backward_launch(const int64_t* rowptr_dev, const int64_t* 
                                       float negative_slope, const float* z_dev, const float* row_max_dev,
                                       const float* row_sum_dev, const float* grad_z_dev, float* grad_x_dev,
                                       float* grad_a_src_dev, float* grad_a_dst_dev, float* alpha_e, float* alpha_self,
-                                      void* stream) {
+                                      void* stream, const GatDrop& dr) {
   const bool vec = grad_x_dev == nullptr;
+  const ActArgs da = dr.on() ? dr.args() : ActArgs{};
   const int lpt_log2 = lanes_log2(vec ? K / 4 : K);
   const unsigned grid = (unsigned)ceil_div(num_targets << lpt_log2, kAggNT);
   with_elem_vec(x_elem, vec, [&](auto tin, auto v) {
     with_heads(heads, [&](auto hh) {
-      using Tin = typename decltype(tin)::type;
-      hipLaunchKernelGGL((k_gat_mh_agg_bwd<Tin, decltype(hh)::value, decltype(v)::value>), dim3(grid), dim3(kAggNT), 0,
-                         as_stream(stream), rowptr_dev, col_dev, num_targets, static_cast<const Tin*>(x_dev),
-                         x_stride_elems, K, a_src_dev, a_dst_dev, negative_slope, z_dev, row_max_dev, row_sum_dev,
-                         grad_z_dev, lpt_log2, grad_x_dev, grad_a_src_dev, grad_a_dst_dev, alpha_e, alpha_self);
+      with_drop(dr.on(), [&](auto drop) {
+        using Tin = typename decltype(tin)::type;
+        hipLaunchKernelGGL((k_gat_mh_agg_bwd<Tin, decltype(hh)::value, decltype(v)::value, decltype(drop)::value>),
+                           dim3(grid), dim3(kAggNT), 0, as_stream(stream), rowptr_dev, col_dev, num_targets,
+                           static_cast<const Tin*>(x_dev), x_stride_elems, K, a_src_dev, a_dst_dev, negative_slope,
+                           z_dev, row_max_dev, row_sum_dev, grad_z_dev, lpt_log2, grad_x_dev, grad_a_src_dev,
+                           grad_a_dst_dev, alpha_e, alpha_self, da);
+      });
     });
   });
   SPP_HIP_TRY(hipGetLastError());
@@ -1414,8 +1478,9 @@ static spp_status gat_aggregate_backward(const char* who, const int64_t* rowptr_
                                          float negative_slope, const float* z_dev, const float* row_max_dev,
                                          const float* row_sum_dev, const float* grad_z_dev,
                                          float* grad_x_dev /* NULL: not wanted */, float* grad_a_src_dev,
-                                         float* grad_a_dst_dev, void* stream) {
+                                         float* grad_a_dst_dev, void* stream, const GatDrop& dr = GatDrop{}) {
   SPP_TRY(gat_check(heads, K, x_dev, x_stride_elems, x_elem, who));
+  SPP_TRY(gat_drop_check(dr, who));
   SPP_REQUIRE(num_targets >= 0, "%s: negative size", who);
   if (num_targets == 0) return SPP_OK;
   SPP_REQUIRE(gat_backward_bufs_ok(heads, rowptr_dev, x_dev, a_src_dev, a_dst_dev, z_dev, row_max_dev, row_sum_dev,
@@ -1423,7 +1488,7 @@ static spp_status gat_aggregate_backward(const char* who, const int64_t* rowptr_
               "%s: NULL or unaligned buffer", who);
   return gat_backward_launch(rowptr_dev, col_dev, num_targets, x_dev, x_elem, x_stride_elems, K, heads, a_src_dev,
                              a_dst_dev, negative_slope, z_dev, row_max_dev, row_sum_dev, grad_z_dev, grad_x_dev,
-                             grad_a_src_dev, grad_a_dst_dev, nullptr, nullptr, stream);
+                             grad_a_src_dev, grad_a_dst_dev, nullptr, nullptr, stream, dr);
 }
 
 extern "C" int64_t spp_gat_mh_aggregate_backward_gather_workspace_bytes(int64_t num_targets, int64_t num_sources,
@@ -1443,8 +1508,9 @@ static spp_status gat_aggregate_backward_gather(
     const float* a_src_dev, const float* a_dst_dev, float negative_slope, const float* z_dev, const float* row_max_dev,
     const float* row_sum_dev, const float* grad_z_dev, const float* v_src_dev, const float* v_dst_dev,
     float* grad_x_dev, float* grad_a_src_dev, float* grad_a_dst_dev, void* workspace_dev, int64_t workspace_bytes,
-    void* stream) {
+    void* stream, const GatDrop& dr = GatDrop{}) {
   SPP_TRY(gat_check(heads, K, x_dev, x_stride_elems, x_elem, who));
+  SPP_TRY(gat_drop_check(dr, who));
   SPP_REQUIRE(num_targets >= 0 && num_sources >= num_targets && num_edges >= 0, "%s: bad sizes", who);
   if (num_sources == 0) return SPP_OK;
   SPP_REQUIRE(num_sources < (1ll << 31) && num_edges < (1ll << 31), "%s: 32-bit indices", who);
@@ -1466,7 +1532,7 @@ static spp_status gat_aggregate_backward_gather(
   if (num_targets > 0)
     SPP_TRY(gat_backward_launch(rowptr_dev, col_dev, num_targets, x_dev, x_elem, x_stride_elems, K, heads, a_src_dev,
                                 a_dst_dev, negative_slope, z_dev, row_max_dev, row_sum_dev, grad_z_dev, nullptr,
-                                grad_a_src_dev, grad_a_dst_dev, alpha_e, alpha_self, stream));
+                                grad_a_src_dev, grad_a_dst_dev, alpha_e, alpha_self, stream, dr));
   TransposedHop hop;
   SPP_TRY(transpose_hop(rowptr_dev, col_dev, num_targets, num_sources, num_edges, true,
                         static_cast<char*>(workspace_dev) + alpha_bytes, workspace_bytes - alpha_bytes, st, &hop));
@@ -1585,6 +1651,78 @@ extern "C" spp_status spp_gat_aggregate_backward_gather(
                                        negative_slope, z_dev, row_max_dev, row_sum_dev, grad_z_dev, v_src_dev, v_dst_dev,
                                        grad_x_dev, grad_a_src_dev, grad_a_dst_dev, workspace_dev, workspace_bytes,
                                        stream);
+}
+
+// ---- attention dropout (spp.h f3t): the three aggregate entries with (p, training, seed), and the mask they use ----
+extern "C" spp_status spp_gat_mh_aggregate_forward_drop(const int64_t* rowptr_dev, const int64_t* col_dev,
+                                                        int64_t num_targets, const void* x_dev, int32_t x_elem,
+                                                        int64_t x_stride_elems, int64_t K, int32_t heads,
+                                                        const float* a_src_dev, const float* a_dst_dev,
+                                                        float negative_slope, float* z_dev, float* row_max_dev,
+                                                        float* row_sum_dev, void* stream, float p, int32_t training,
+                                                        uint64_t seed) {
+  return gat_aggregate_forward("spp_gat_mh_aggregate_forward_drop", rowptr_dev, col_dev, num_targets, x_dev, x_elem,
+                               x_stride_elems, K, heads, a_src_dev, a_dst_dev, negative_slope, z_dev, row_max_dev,
+                               row_sum_dev, stream, GatDrop{true, p, training, seed});
+}
+
+extern "C" spp_status spp_gat_mh_aggregate_backward_drop(
+    const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets, const void* x_dev, int32_t x_elem,
+    int64_t x_stride_elems, int64_t K, int32_t heads, const float* a_src_dev, const float* a_dst_dev,
+    float negative_slope, const float* z_dev, const float* row_max_dev, const float* row_sum_dev,
+    const float* grad_z_dev, float* grad_x_dev, float* grad_a_src_dev, float* grad_a_dst_dev, void* stream, float p,
+    int32_t training, uint64_t seed) {
+  return gat_aggregate_backward("spp_gat_mh_aggregate_backward_drop", rowptr_dev, col_dev, num_targets, x_dev, x_elem,
+                                x_stride_elems, K, heads, a_src_dev, a_dst_dev, negative_slope, z_dev, row_max_dev,
+                                row_sum_dev, grad_z_dev, grad_x_dev, grad_a_src_dev, grad_a_dst_dev, stream,
+                                GatDrop{true, p, training, seed});
+}
+
+extern "C" spp_status spp_gat_mh_aggregate_backward_gather_drop(
+    const int64_t* rowptr_dev, const int64_t* col_dev, int64_t num_targets, int64_t num_sources, int64_t num_edges,
+    const void* x_dev, int32_t x_elem, int64_t x_stride_elems, int64_t K, int32_t heads, const float* a_src_dev,
+    const float* a_dst_dev, float negative_slope, const float* z_dev, const float* row_max_dev,
+    const float* row_sum_dev, const float* grad_z_dev, const float* v_src_dev, const float* v_dst_dev,
+    float* grad_x_dev, float* grad_a_src_dev, float* grad_a_dst_dev, void* workspace_dev, int64_t workspace_bytes,
+    void* stream, float p, int32_t training, uint64_t seed) {
+  return gat_aggregate_backward_gather("spp_gat_mh_aggregate_backward_gather_drop", rowptr_dev, col_dev, num_targets,
+                                       num_sources, num_edges, x_dev, x_elem, x_stride_elems, K, heads, a_src_dev,
+                                       a_dst_dev, negative_slope, z_dev, row_max_dev, row_sum_dev, grad_z_dev, v_src_dev,
+                                       v_dst_dev, grad_x_dev, grad_a_src_dev, grad_a_dst_dev, workspace_dev,
+                                       workspace_bytes, stream, GatDrop{true, p, training, seed});
+}
+
+namespace spp {
+// keep[entry, h] (0 / 1) of the E + T softmax entries, by the device function the aggregate kernels call
+template <int H>
+__global__ __launch_bounds__(kAggNT) void k_gat_mh_attn_keep(int64_t n, ActArgs drop, uint8_t* __restrict__ keep_out) {
+  const int64_t entry = (int64_t)blockIdx.x * kAggNT + threadIdx.x;
+  if (entry >= n) return;
+  bool keep[H];
+  attn_keep_heads<H>((uint64_t)entry, drop, keep);
+#pragma unroll
+  for (int h = 0; h < H; ++h) keep_out[entry * H + h] = keep[h] ? 1 : 0;
+}
+}  // namespace spp
+
+extern "C" spp_status spp_gat_mh_attn_keep(int64_t num_edges, int64_t num_targets, int32_t heads, float p, uint64_t seed,
+                                           uint8_t* keep_dev, void* stream) {
+  const char* who = "spp_gat_mh_attn_keep";
+  SPP_REQUIRE(num_edges >= 0 && num_targets >= 0, "%s: negative size", who);
+  SPP_REQUIRE(heads == 1 || heads == 2 || heads == 4 || heads == 8, "%s: heads must be 1, 2, 4 or 8 (got %d)", who,
+              (int)heads);
+  SPP_REQUIRE(p >= 0.f && p < 1.f, "%s: attention dropout needs 0 <= p < 1", who);
+  const int64_t n = num_edges + num_targets;
+  SPP_REQUIRE(n < (1ll << 31) * (int64_t)kAggNT, "%s: size out of range", who);
+  if (n == 0) return SPP_OK;
+  SPP_REQUIRE(keep_dev, "%s: NULL buffer", who);
+  const ActArgs da = act_args(p, 1, seed);
+  with_heads(heads, [&](auto hh) {
+    hipLaunchKernelGGL((k_gat_mh_attn_keep<decltype(hh)::value>), dim3((unsigned)ceil_div(n, kAggNT)), dim3(kAggNT), 0,
+                       as_stream(stream), n, da, keep_dev);
+  });
+  SPP_HIP_TRY(hipGetLastError());
+  return SPP_OK;
 }
 
 // ================================================================================================

@@ -774,14 +774,24 @@ class GATConv(torch.nn.Module):
     ``heads`` = H: W is [H * out, in], att_src / att_dst are [1, H, out] (PyG's layout), every head has its own
     softmax, and the output is the H heads side by side ([T, H * out], ``concat=True``) or their mean ([T, out]);
     ``bias`` has the output's width.  heads=1 runs the single-head path; H in {1, 2, 4, 8} with the rows the kernels
-    read takes _GatLayerMH, anything else a plain-torch restatement of the same function (_gat_mh_reference)."""
+    read takes _GatLayerMH, anything else a plain-torch restatement of the same function (_gat_mh_reference).
 
-    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True):
+    ``dropout`` = p in [0, 1): F.dropout(alpha, p, training) on the attention coefficients of every (entry, head), the
+    self loop included (PyG's self loops are edges like any other); the softmax itself runs over all entries.  p = 0 and
+    eval mode run exactly the paths above.  In training with p > 0, the inputs the kernels read (any H in {1, 2, 4, 8},
+    heads=1 too) take _GatLayerMH with the mask generated inside its kernels from a seed drawn from torch's CPU generator
+    (spp.h f3t; _attn_keep_reference restates it); everything else takes _gat_mh_reference with F.dropout on its alpha:
+    torch's own mask there, not the kernels'.  No parameter or buffer: the state dict does not change."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, bias=True):
         super().__init__()
         if not isinstance(heads, int) or heads < 1:
             raise ValueError(f"heads must be a positive int, got {heads!r}")
+        if isinstance(dropout, bool) or not isinstance(dropout, (int, float)) or not 0.0 <= dropout < 1.0:
+            raise ValueError(f"dropout must be a number in [0, 1), got {dropout!r}")
         self.heads, self.out_channels, self.concat = heads, out_channels, bool(concat)
         self.negative_slope = negative_slope
+        self.dropout = float(dropout)
         self.lin_src = torch.nn.Linear(in_channels, heads * out_channels, bias=False)
         self.lin_dst = self.lin_src
         self.att_src = torch.nn.Parameter(torch.empty(1, heads, out_channels))
@@ -800,7 +810,7 @@ class GATConv(torch.nn.Module):
             torch.nn.init.zeros_(self.bias)
 
     def forward(self, x_pair, adj_t):
-        if self.heads != 1:
+        if self.heads != 1 or (self.training and self.dropout > 0.0):
             return self._forward_heads(x_pair, adj_t)
         x, x_target = x_pair
         rowptr, col, _ = adj_t.csr()
@@ -823,24 +833,48 @@ class GATConv(torch.nn.Module):
         rowptr, col, _ = adj_t.csr()
         T, K, H = x_target.size(0), x.size(1), self.heads
         att_src, att_dst = self.att_src.view(H, -1), self.att_dst.view(H, -1)
+        p = self.dropout if self.training else 0.0
         if (H in _GAT_MH_HEADS and x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and x.dtype in _ELEM and
                 K % 4 == 0 and K <= 1024 and x_target.data_ptr() == x.data_ptr() and x_target.stride() == x.stride()):
             out = _GatLayerMH.apply(x, self.lin_src.weight, att_src, att_dst, rowptr, col, T, self.negative_slope,
-                                    self.concat)
+                                    self.concat, p)
         else:
             out = _gat_mh_reference(x, x_target, self.lin_src.weight, att_src, att_dst, rowptr, col,
-                                    self.negative_slope, self.concat)
+                                    self.negative_slope, self.concat, p)
         return out if self.bias is None else out + self.bias
 
 
 _GAT_MH_HEADS = (1, 2, 4, 8)       # the head counts the multi-head kernels are built for
 
 
-def _gat_mh_reference(x, x_target, W, att_src, att_dst, rowptr, col, slope, concat):
+def _attn_keep_reference(E, T, H, p, seed):
+    """The keep rule of the attention dropout kernels (spp.h f3t) in numpy uint64: keep [(E + T), H] uint8, entry-major
+    (the E CSR entries, then the T self loops); what spp_gat_mh_attn_keep writes.  Draw index i = entry * H + h is the low
+    (i even) or high (i odd) half of mix64(seed + (i >> 1) * 0x9E3779B97F4A7C15), kept iff below (1 - p) * 2^32."""
+    import numpy as np
+    keep = 1.0 - float(np.float32(p))                                       # the entries take p as a C float
+    thr = np.uint64(0xFFFFFFFF if keep >= 1.0 else int(keep * 4294967296.0))
+    i = np.arange((E + T) * H, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        z = np.uint64(seed & 0xFFFFFFFFFFFFFFFF) + (i >> np.uint64(1)) * np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)      # mix64: the splitmix64 finaliser
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    draw = np.where(i & np.uint64(1), z >> np.uint64(32), z & np.uint64(0xFFFFFFFF))
+    return (draw < thr).astype(np.uint8).reshape(E + T, H)
+
+
+def _attn_seed():
+    """a 64-bit seed from torch's CPU generator, as _ReluDropout takes its: torch.manual_seed makes a run repeatable"""
+    return int(torch.empty((), dtype=torch.int64).random_().item()) & 0xFFFFFFFFFFFFFFFF
+
+
+def _gat_mh_reference(x, x_target, W, att_src, att_dst, rowptr, col, slope, concat, p=0.0):
     """GATConv with H heads in PyG's project-first order, in plain torch ops (the path for inputs the kernels do not
     read: K % 4 != 0, K > 1024, other head counts, a target block that is not the prefix of x, CPU tensors).
     x [S, K], x_target [T, K], W [H*C, K], att_* [H, C]; set_diag: diagonal entries dropped, one self loop (i, i) per
-    target, whose message is source row i."""
+    target, whose message is source row i.  p > 0 (training): F.dropout on alpha -- torch's own mask, from the
+    generator of alpha's device, NOT the kernels' counter-based one (_attn_keep_reference)."""
     H, Cc = att_src.shape
     S, T = x.size(0), x_target.size(0)
     h = F.linear(x.to(W.dtype), W).view(S, H, Cc)
@@ -857,6 +891,8 @@ def _gat_mh_reference(x, x_target, W, att_src, att_dst, rowptr, col, slope, conc
     w = torch.exp(e - emax[dst])
     den = torch.zeros((T, H), device=e.device).index_add_(0, dst, w)
     alpha = w / den[dst]
+    if p > 0.0:
+        alpha = F.dropout(alpha, p, training=True)
     out = torch.zeros((T, H, Cc), device=e.device).index_add_(0, dst, alpha[:, :, None] * h[src].float())
     return out.reshape(T, H * Cc) if concat else out.mean(1)
 
@@ -873,13 +909,13 @@ class _GatLayerMH(torch.autograd.Function):
     the backward's GEMMs run in bf16 (bf16 output); parameters and their gradients stay fp32."""
 
     @staticmethod
-    def forward(ctx, x, W, att_src, att_dst, rowptr, col, T, slope, concat):
+    def forward(ctx, x, W, att_src, att_dst, rowptr, col, T, slope, concat, p=0.0):
         ctx.amp = amp_bf16()
         with _no_autocast():
-            return _GatLayerMH._forward(ctx, x, W, att_src, att_dst, rowptr, col, T, slope, concat)
+            return _GatLayerMH._forward(ctx, x, W, att_src, att_dst, rowptr, col, T, slope, concat, float(p))
 
     @staticmethod
-    def _forward(ctx, x, W, att_src, att_dst, rowptr, col, T, slope, concat):
+    def _forward(ctx, x, W, att_src, att_dst, rowptr, col, T, slope, concat, p):
         L = nat.load()
         nat.require_device()
         st = _stream()
@@ -895,8 +931,14 @@ class _GatLayerMH(torch.autograd.Function):
         nat.check(L.spp_gat_mh_logits(_p(x), elem, xs, S, T, K, H, _p(V[0]), _p(V[1]), _p(a_src), _p(a_dst), st))
         z = torch.empty((T, H, K), **f32)
         rmax, rsum = torch.empty((T, H), **f32), torch.empty((T, H), **f32)
-        nat.check(L.spp_gat_mh_aggregate_forward(_p(rowptr), _p(col), T, _p(x), elem, xs, K, H, _p(a_src), _p(a_dst),
-                                                 float(slope), _p(z), _p(rmax), _p(rsum), st))
+        # p > 0: attention dropout inside the kernels (spp.h f3t); the seed is kept for the backward's identical mask
+        ctx.drop = (p, _attn_seed()) if p > 0.0 else None
+        args = (_p(rowptr), _p(col), T, _p(x), elem, xs, K, H, _p(a_src), _p(a_dst), float(slope), _p(z), _p(rmax),
+                _p(rsum), st)
+        if ctx.drop:
+            nat.check(L.spp_gat_mh_aggregate_forward_drop(*args, p, 1, ctx.drop[1]))
+        else:
+            nat.check(L.spp_gat_mh_aggregate_forward(*args))
         ctx.save_for_backward(x, W, att_src, att_dst, rowptr, col, a_src, a_dst, z, rmax, rsum, V)
         ctx.dims = (S, T, K, H, Cc, elem, xs, float(slope), bool(concat))
         dt = torch.bfloat16 if ctx.amp else torch.float32
@@ -936,14 +978,20 @@ class _GatLayerMH(torch.autograd.Function):
             g_x = torch.empty((S, K), **f32)
             nbytes = int(L.spp_gat_mh_aggregate_backward_gather_workspace_bytes(T, S, E, H))
             ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-            nat.check(L.spp_gat_mh_aggregate_backward_gather(
-                _p(rowptr), _p(col), T, S, E, _p(x), elem, xs, K, H, _p(a_src), _p(a_dst), slope, _p(z), _p(rmax),
-                _p(rsum), _p(g_z), _p(V[0]), _p(V[1]), _p(g_x), _p(g_as), _p(g_ad), _p(ws), nbytes, st))
+            args = (_p(rowptr), _p(col), T, S, E, _p(x), elem, xs, K, H, _p(a_src), _p(a_dst), slope, _p(z), _p(rmax),
+                    _p(rsum), _p(g_z), _p(V[0]), _p(V[1]), _p(g_x), _p(g_as), _p(g_ad), _p(ws), nbytes, st)
+            if ctx.drop:
+                nat.check(L.spp_gat_mh_aggregate_backward_gather_drop(*args, ctx.drop[0], 1, ctx.drop[1]))
+            else:
+                nat.check(L.spp_gat_mh_aggregate_backward_gather(*args))
         else:
             g_x = torch.zeros((S, K), **f32) if want_gx else None
-            nat.check(L.spp_gat_mh_aggregate_backward(_p(rowptr), _p(col), T, _p(x), elem, xs, K, H, _p(a_src),
-                                                      _p(a_dst), slope, _p(z), _p(rmax), _p(rsum), _p(g_z), _p(g_x),
-                                                      _p(g_as), _p(g_ad), st))
+            args = (_p(rowptr), _p(col), T, _p(x), elem, xs, K, H, _p(a_src), _p(a_dst), slope, _p(z), _p(rmax),
+                    _p(rsum), _p(g_z), _p(g_x), _p(g_as), _p(g_ad), st)
+            if ctx.drop:
+                nat.check(L.spp_gat_mh_aggregate_backward_drop(*args, ctx.drop[0], 1, ctx.drop[1]))
+            else:
+                nat.check(L.spp_gat_mh_aggregate_backward(*args))
         g_V = torch.empty((2, H, K), **f32)
         nat.check(L.spp_gat_mh_logits_backward(_p(x), elem, xs, S, T, K, H, _p(g_as), _p(g_ad), _p(g_V[0]),
                                                _p(g_V[1]), st))
@@ -957,7 +1005,7 @@ class _GatLayerMH(torch.autograd.Function):
         gW = gW + torch.einsum("shc,shk->hck", att, g_V).reshape(H * Cc, K)
         g_att = torch.einsum("shk,hck->shc", g_V, W.to(torch.float32).view(H, Cc, K))
         return (g_x, gW.to(W.dtype), g_att[0].to(att_src.dtype), g_att[1].to(att_dst.dtype), None, None, None, None,
-                None)
+                None, None)
 
 
 class _GatLayer(torch.autograd.Function):
@@ -1060,9 +1108,13 @@ class GAT(torch.nn.Module):
     the hidden WIDTH kept: every hidden layer is GATConv(d_in, hidden_channels // H, heads=H, concat=True), so its
     output is still ``hidden_channels`` wide ("3 x 256, heads=4" is four heads of 64), and the last layer is
     GATConv(hidden_channels, out_channels, heads=H, concat=False), the mean of its heads.  ``hidden_channels`` must be
-    a multiple of ``heads``."""
+    a multiple of ``heads``.
 
-    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, heads=1):
+    ``attn_dropout`` (keyword only, default 0): GATConv's ``dropout`` of every conv, PyG's dropout on the attention
+    coefficients (p = 0.6 in the GAT paper).  Training only: eval mode and the inference drivers score the model exactly
+    as the same model with 0."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, heads=1, attn_dropout=0.0):
         super().__init__()
         if not isinstance(heads, int) or heads < 1:
             raise ValueError(f"heads must be a positive int, got {heads!r}")
@@ -1072,17 +1124,18 @@ class GAT(torch.nn.Module):
         self.hidden_channels = hidden_channels
         self.heads = heads
         self.convs = torch.nn.ModuleList()
+        p = attn_dropout
         if heads == 1:
-            self.convs.append(GATConv(in_channels, hidden_channels, bias=False, heads=1))
+            self.convs.append(GATConv(in_channels, hidden_channels, bias=False, heads=1, dropout=p))
             for _ in range(num_layers - 2):
-                self.convs.append(GATConv(hidden_channels, hidden_channels, bias=False, heads=1))
-            self.convs.append(GATConv(hidden_channels, out_channels, bias=False, heads=1))
+                self.convs.append(GATConv(hidden_channels, hidden_channels, bias=False, heads=1, dropout=p))
+            self.convs.append(GATConv(hidden_channels, out_channels, bias=False, heads=1, dropout=p))
         else:
             c = hidden_channels // heads
-            self.convs.append(GATConv(in_channels, c, heads=heads, concat=True, bias=False))
+            self.convs.append(GATConv(in_channels, c, heads=heads, concat=True, bias=False, dropout=p))
             for _ in range(num_layers - 2):
-                self.convs.append(GATConv(hidden_channels, c, heads=heads, concat=True, bias=False))
-            self.convs.append(GATConv(hidden_channels, out_channels, heads=heads, concat=False, bias=False))
+                self.convs.append(GATConv(hidden_channels, c, heads=heads, concat=True, bias=False, dropout=p))
+            self.convs.append(GATConv(hidden_channels, out_channels, heads=heads, concat=False, bias=False, dropout=p))
         self.reset_parameters()
 
     def reset_parameters(self):

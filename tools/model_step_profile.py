@@ -1,11 +1,12 @@
 """One resident batch of the bench workload, N optimisation steps of one of the models (models.get_model_type: SAGE, GAT,
 GIN, SAGEResInception; and models.GCN) on it (fwd + bwd + Adam), timed; run under `rocprofv3 --kernel-trace --stats` for the per-kernel
 table.
-usage: model_step_profile.py [sage|gat|gin|sageresinception|gcn] [steps=30] [workload=S-papers] [fused] [max] [norm] [--amp bf16] [--heads H]
+usage: model_step_profile.py [sage|gat|gin|sageresinception|gcn] [steps=30] [workload=S-papers] [fused] [max] [norm] [--amp bf16] [--heads H] [attn=P]
 norm: GCN built with normalize=True (gcn_norm's coefficients and the self term; the reference model's setting is False).
 max: SAGE built with aggr="max" (csrc/aggregate_max.hip, layer by layer) instead of the mean's fused stack.
 fused: GIN / SAGEResInception / GCN built with fused_norm=True (the BatchNorm tail on csrc/bn_act.hip).
 --amp bf16: the forward and the loss under torch.autocast("cuda", dtype=torch.bfloat16), as a training loop would wrap them.
+attn=P: GAT(..., attn_dropout=P): PyG's dropout on the attention coefficients, inside the GAT kernels (spp.h f3t); default 0.
 --heads H: GAT(..., heads=H) (default 1: the reference model): hidden layers of H heads of 256 // H, the last one averaged."""
 import contextlib
 import os
@@ -34,6 +35,10 @@ if "--heads" in argv:
     i = argv.index("--heads")
     heads = int(argv[i + 1])
     del argv[i:i + 2]
+attn = 0.0
+for a in [a for a in argv if a.startswith("attn=")]:
+    attn = float(a.split("=", 1)[1])
+    argv.remove(a)
 fused = "fused" in argv
 use_max = "max" in argv
 norm = "norm" in argv
@@ -52,6 +57,8 @@ batch = next(it)[0]
 torch.cuda.synchronize()
 if heads != 1 and arch != "gat":
     sys.exit("--heads: GAT only")
+if attn and arch != "gat":
+    sys.exit("attn=: GAT only")
 if fused and arch not in ("gin", "sageresinception", "gcn"):
     sys.exit("fused: GIN, SAGEResInception and GCN only")
 if norm and arch != "gcn":
@@ -59,6 +66,8 @@ if norm and arch != "gcn":
 if use_max and arch != "sage":
     sys.exit("max: SAGE only")
 kw = {"heads": heads} if heads != 1 else {}
+if attn:
+    kw["attn_dropout"] = attn
 if use_max:
     kw["aggr"] = "max"
 if fused:
@@ -92,5 +101,5 @@ for _ in range(steps):
     loss = step()
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / steps
-print(f"MODEL_STEP {arch}{' aggr=max' if use_max else ''}{' normalize' if norm else ''}{f' heads={heads}' if heads != 1 else ''}{' fused_norm' if fused else ''}{' amp=' + amp if amp else ''} {dt * 1e3:.3f} ms/step on a resident batch: {batch.x.size(0)} nodes, "
+print(f"MODEL_STEP {arch}{' aggr=max' if use_max else ''}{' normalize' if norm else ''}{f' heads={heads}' if heads != 1 else ''}{f' attn={attn:g}' if attn else ''}{' fused_norm' if fused else ''}{' amp=' + amp if amp else ''} {dt * 1e3:.3f} ms/step on a resident batch: {batch.x.size(0)} nodes, "
       f"{[int(a.adj_t.nnz()) for a in batch.adjs]} edges, (S, T) {[tuple(int(v) for v in a.size) for a in batch.adjs]}, loss {float(loss):.4f}", flush=True)
