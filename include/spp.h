@@ -676,7 +676,7 @@ spp_status spp_gat_backward(const int64_t* rowptr_dev, const int64_t* col_dev, i
                             const float* row_sum_dev, const float* grad_out_dev, float* grad_h_dev,
                             float* grad_a_src_dev, float* grad_a_dst_dev, void* stream);
 
-/* GATConv in aggregate-then-project form (same function, far less work: see csrc/aggregate.hip).
+/* GATConv in aggregate-then-project form (same function, far less work: see csrc/gat.hip).
  * With v_src = W^T att_src, v_dst = W^T att_dst (K-vectors):
  *   spp_gat_logits:            a_src[j] = x_j . v_src (all S rows), a_dst[i] = x_i . v_dst (the first T rows)
  *   spp_gat_aggregate_forward: z_i = sum_j softmax_j(leaky_relu(a_src[j] + a_dst[i])) x_j  over row i of the hop

@@ -1,5 +1,5 @@
 // The keep / drop rule of every dropout this library applies (aggregate.hip: k_relu_dropout_*, the activated operand;
-// bn_act.hip: the BatchNorm tail), from a counter-based generator: element i of the call with `seed` is kept iff
+// bn_act.hip: the BatchNorm tail; gat.hip: the attention dropout), from a counter-based generator: element i of the call with `seed` is kept iff
 // hash(seed, i) < (1 - p) * 2^32.  One 64-bit hash serves two elements; the n % 4 elements at the end of an array take
 // a hash of their own (the tail of k_relu_dropout_fwd).
 #pragma once

@@ -1,4 +1,4 @@
-// Element I/O of the aggregation and inference kernels (aggregate.hip, graph_aggregate.hip, graph_gat.hip,
+// Element I/O of the aggregation and inference kernels (aggregate.hip, gat.hip, graph_aggregate.hip, graph_gat.hip,
 // resinc_epilogue.hip, classify.hip): fp32 / fp16 / bf16 rows as fp32 pieces on the device, and on the host the
 // element-code helpers and the dispatch from element codes to kernel template arguments.
 #pragma once

@@ -2,7 +2,7 @@
 // (reference: driver/models.py:228 GAT.inference through layerwise_inference, line 441), in PyG's project-first order:
 //     e^h_tj = leaky_relu(a_src[j,h] + a_dst[t,h], slope)     j in col[rowptr[t] .. rowptr[t+1]) without j == t, plus j = t
 //     out[i, h*C + c] = sum_j softmax_j(e^h_t.)_j * h[j, h*C + c]          t = target_row0 + i  or  target_ids[i]
-// What differs from a sampled hop (aggregate.hip, k_gat_fwd / k_gat_mh_agg_fwd): the targets are any rows of h, a row
+// What differs from a sampled hop (gat.hip, k_gat_fwd / k_gat_mh_agg_fwd): the targets are any rows of h, a row
 // is as long as the node's degree, and the rows of h are already projected, so a head owns C columns of the row.
 //
 // Softmax contract (include/spp.h, spp_graph_gat_forward): C_g = kGatChunk.  A state is (m, s, acc): the running

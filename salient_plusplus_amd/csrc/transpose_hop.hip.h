@@ -1,6 +1,7 @@
-// The transposed hop (sources -> targets) that the gather backwards share (aggregate.hip: the operand's, the sum's and
-// GAT's; aggregate_weighted.hip: the weighted sum's): its kernels, its workspace layout and the count / scan / fill
-// that builds it.  Moved out of aggregate.hip unchanged, but for the kernels' `static`: two translation units hold them.
+// The transposed hop (sources -> targets) that the gather backwards share (aggregate.hip: the operand's and the sum's;
+// gat.hip: GAT's; aggregate_weighted.hip: the weighted sum's): its kernels, its workspace layout and the count / scan /
+// fill that builds it.  Moved out of aggregate.hip unchanged, but for the kernels' `static`: each of the three
+// translation units holds its own copy of them (and of hipcub's scan).
 #pragma once
 
 #include "spp_internal.h"

@@ -2,7 +2,7 @@
 ``SAGE`` (driver/models.py:19-56: ``num_layers`` x SAGEConv(bias=False, mean aggregation), ReLU +
 dropout 0.5 between layers, log_softmax) on the MFG's CSR, with the message passing on HIP kernels
 (csrc/aggregate.hip) and the linear layers on the library GEMMs torch dispatches to.  The reference's other working
-models follow: GAT, GIN (sum aggregation) and SAGEResInception; ``get_model_type`` maps their names (driver/main.py:74-95).
+models follow: GAT (csrc/gat.hip), GIN (sum aggregation) and SAGEResInception; ``get_model_type`` maps their names (driver/main.py:74-95).
 
 The constructor, ``reset_parameters`` and ``forward(x, adjs)`` follow the reference; ``adjs`` is
 what the data path delivers: ``[(adj_t, e_id, (S, T)), ...]``, outermost hop first."""
@@ -897,6 +897,73 @@ def _gat_mh_reference(x, x_target, W, att_src, att_dst, rowptr, col, slope, conc
     return out.reshape(T, H * Cc) if concat else out.mean(1)
 
 
+def _gat_aggregate_call(L, name, args, drop):
+    """the aggregate entry `name`, or with attention dropout (drop = (p, seed)) its _drop spelling, which takes
+    (p, training = 1, seed) after the same arguments: the one place that picks between the two"""
+    if drop:
+        nat.check(getattr(L, name + "_drop")(*args, drop[0], 1, drop[1]))
+    else:
+        nat.check(getattr(L, name)(*args))
+
+
+def _gat_kernels_forward(x, V_src, V_dst, rowptr, col, T, H, slope, p=0.0):
+    """The kernel calls of a GAT layer's forward, the spp_gat_mh_* entries with heads = H (_GatLayer: H = 1): the
+    logits a_src [S, H], a_dst [T, H] of x's rows (fp32, fp16 or bf16) with V_src, V_dst [H, K], then z [T, H, K] with
+    the softmax statistics rmax, rsum [T, H]; all fp32.  p > 0: attention dropout inside the kernels (spp.h f3t).
+    Returns (a_src, a_dst, z, rmax, rsum, drop), drop = (p, seed) for the backward's identical mask, or None."""
+    L = nat.load()
+    nat.require_device()
+    st = _stream()
+    S, K = x.size(0), x.size(1)
+    elem = _ELEM[x.dtype]
+    xs = x.stride(0) if S > 1 else K
+    f32 = dict(dtype=torch.float32, device=x.device)
+    a_src, a_dst = torch.empty((S, H), **f32), torch.empty((T, H), **f32)
+    nat.check(L.spp_gat_mh_logits(_p(x), elem, xs, S, T, K, H, _p(V_src), _p(V_dst), _p(a_src), _p(a_dst), st))
+    z = torch.empty((T, H, K), **f32)
+    rmax, rsum = torch.empty((T, H), **f32), torch.empty((T, H), **f32)
+    drop = (p, _attn_seed()) if p > 0.0 else None
+    _gat_aggregate_call(L, "spp_gat_mh_aggregate_forward",
+                        (_p(rowptr), _p(col), T, _p(x), elem, xs, K, H, _p(a_src), _p(a_dst), float(slope), _p(z),
+                         _p(rmax), _p(rsum), st), drop)
+    return a_src, a_dst, z, rmax, rsum, drop
+
+
+def _gat_kernels_backward(x, rowptr, col, a_src, a_dst, z, rmax, rsum, g_z, V, slope, want_gx, drop):
+    """The kernel calls of a GAT layer's backward from g_z [T, H, K] fp32 (the forward's buffers and drop as
+    _gat_kernels_forward returned them; V = [V_src, V_dst], [2, H, K], read by the gather form only).  Returns (g_x, g_as, g_ad, g_V, gathered): g_as [S, H] and g_ad [T, H], the
+    logits' gradients; g_V [2, H, K], those of V_src, V_dst; g_x [S, K] fp32, None unless want_gx.  From E * K = 2^22 on
+    g_x comes by gather over the transposed hop and is complete (gathered); below, by atomics, and the caller still adds
+    the logits' terms g_as V_src + g_ad V_dst (rows :T)."""
+    L = nat.load()
+    st = _stream()
+    S, K = x.size(0), x.size(1)
+    T, H = a_dst.shape
+    elem = _ELEM[x.dtype]
+    xs = x.stride(0) if S > 1 else K
+    E = col.numel()
+    gather = want_gx and E * K >= (1 << 22)
+    f32 = dict(dtype=torch.float32, device=x.device)
+    g_as, g_ad = torch.zeros((S, H), **f32), torch.empty((T, H), **f32)
+    if gather:      # no E x K fp32 atomics, no zero fill, and the logits' rank-1 terms are added in the same pass
+        g_x = torch.empty((S, K), **f32)
+        nbytes = int(L.spp_gat_mh_aggregate_backward_gather_workspace_bytes(T, S, E, H))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        _gat_aggregate_call(L, "spp_gat_mh_aggregate_backward_gather",
+                            (_p(rowptr), _p(col), T, S, E, _p(x), elem, xs, K, H, _p(a_src), _p(a_dst), slope, _p(z),
+                             _p(rmax), _p(rsum), _p(g_z), _p(V[0]), _p(V[1]), _p(g_x), _p(g_as), _p(g_ad), _p(ws),
+                             nbytes, st), drop)
+    else:
+        g_x = torch.zeros((S, K), **f32) if want_gx else None
+        _gat_aggregate_call(L, "spp_gat_mh_aggregate_backward",
+                            (_p(rowptr), _p(col), T, _p(x), elem, xs, K, H, _p(a_src), _p(a_dst), slope, _p(z),
+                             _p(rmax), _p(rsum), _p(g_z), _p(g_x), _p(g_as), _p(g_ad), st), drop)
+    g_V = torch.empty((2, H, K), **f32)
+    nat.check(L.spp_gat_mh_logits_backward(_p(x), elem, xs, S, T, K, H, _p(g_as), _p(g_ad), _p(g_V[0]), _p(g_V[1]),
+                                           st))
+    return g_x, g_as, g_ad, g_V, gather
+
+
 class _GatLayerMH(torch.autograd.Function):
     """GATConv with H > 1 heads on ((x, x[:T]), adj_t) as ONE node, _GatLayer's aggregate-then-project form per head:
 
@@ -916,31 +983,14 @@ class _GatLayerMH(torch.autograd.Function):
 
     @staticmethod
     def _forward(ctx, x, W, att_src, att_dst, rowptr, col, T, slope, concat, p):
-        L = nat.load()
-        nat.require_device()
-        st = _stream()
-        S, K = x.size(0), x.size(1)
+        K = x.size(1)
         H, Cc = att_src.shape
-        elem = _ELEM[x.dtype]
-        xs = x.stride(0) if S > 1 else K
         W3 = W.to(torch.float32).view(H, Cc, K)
         att = torch.stack([att_src, att_dst]).to(torch.float32)                  # [2, H, C]
         V = torch.einsum("shc,hck->shk", att, W3).contiguous()                   # [2, H, K]: V_src, V_dst
-        f32 = dict(dtype=torch.float32, device=x.device)
-        a_src, a_dst = torch.empty((S, H), **f32), torch.empty((T, H), **f32)
-        nat.check(L.spp_gat_mh_logits(_p(x), elem, xs, S, T, K, H, _p(V[0]), _p(V[1]), _p(a_src), _p(a_dst), st))
-        z = torch.empty((T, H, K), **f32)
-        rmax, rsum = torch.empty((T, H), **f32), torch.empty((T, H), **f32)
-        # p > 0: attention dropout inside the kernels (spp.h f3t); the seed is kept for the backward's identical mask
-        ctx.drop = (p, _attn_seed()) if p > 0.0 else None
-        args = (_p(rowptr), _p(col), T, _p(x), elem, xs, K, H, _p(a_src), _p(a_dst), float(slope), _p(z), _p(rmax),
-                _p(rsum), st)
-        if ctx.drop:
-            nat.check(L.spp_gat_mh_aggregate_forward_drop(*args, p, 1, ctx.drop[1]))
-        else:
-            nat.check(L.spp_gat_mh_aggregate_forward(*args))
+        a_src, a_dst, z, rmax, rsum, ctx.drop = _gat_kernels_forward(x, V[0], V[1], rowptr, col, T, H, slope, p)
         ctx.save_for_backward(x, W, att_src, att_dst, rowptr, col, a_src, a_dst, z, rmax, rsum, V)
-        ctx.dims = (S, T, K, H, Cc, elem, xs, float(slope), bool(concat))
+        ctx.dims = (T, K, H, Cc, float(slope), bool(concat))
         dt = torch.bfloat16 if ctx.amp else torch.float32
         zc, Wc = z.to(dt), W.to(dt).view(H, Cc, K)
         if concat:                                                               # [H, T, K] @ [H, K, C] -> [T, H, C]
@@ -954,10 +1004,8 @@ class _GatLayerMH(torch.autograd.Function):
 
     @staticmethod
     def _backward(ctx, g_out):
-        L = nat.load()
-        st = _stream()
         x, W, att_src, att_dst, rowptr, col, a_src, a_dst, z, rmax, rsum, V = ctx.saved_tensors
-        S, T, K, H, Cc, elem, xs, slope, concat = ctx.dims
+        T, K, H, Cc, slope, concat = ctx.dims
         dt = torch.bfloat16 if ctx.amp else torch.float32
         g = g_out.to(dt).contiguous()
         zc, Wc = z.to(dt), W.to(dt).view(H, Cc, K)
@@ -970,33 +1018,10 @@ class _GatLayerMH(torch.autograd.Function):
             g_z = (g @ Wc.transpose(1, 2).reshape(H * K, Cc).t()).float().view(T, H, K)
             gW = _wgrad(g, zc.view(T, H * K)).view(Cc, H, K).transpose(0, 1).reshape(H * Cc, K)
         want_gx = ctx.needs_input_grad[0]
-        E = col.numel()
-        gather = want_gx and E * K >= (1 << 22)
-        f32 = dict(dtype=torch.float32, device=x.device)
-        g_as, g_ad = torch.zeros((S, H), **f32), torch.empty((T, H), **f32)
-        if gather:                                  # the input gradient by gather, with the logits' rank-1 terms
-            g_x = torch.empty((S, K), **f32)
-            nbytes = int(L.spp_gat_mh_aggregate_backward_gather_workspace_bytes(T, S, E, H))
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-            args = (_p(rowptr), _p(col), T, S, E, _p(x), elem, xs, K, H, _p(a_src), _p(a_dst), slope, _p(z), _p(rmax),
-                    _p(rsum), _p(g_z), _p(V[0]), _p(V[1]), _p(g_x), _p(g_as), _p(g_ad), _p(ws), nbytes, st)
-            if ctx.drop:
-                nat.check(L.spp_gat_mh_aggregate_backward_gather_drop(*args, ctx.drop[0], 1, ctx.drop[1]))
-            else:
-                nat.check(L.spp_gat_mh_aggregate_backward_gather(*args))
-        else:
-            g_x = torch.zeros((S, K), **f32) if want_gx else None
-            args = (_p(rowptr), _p(col), T, _p(x), elem, xs, K, H, _p(a_src), _p(a_dst), slope, _p(z), _p(rmax),
-                    _p(rsum), _p(g_z), _p(g_x), _p(g_as), _p(g_ad), st)
-            if ctx.drop:
-                nat.check(L.spp_gat_mh_aggregate_backward_drop(*args, ctx.drop[0], 1, ctx.drop[1]))
-            else:
-                nat.check(L.spp_gat_mh_aggregate_backward(*args))
-        g_V = torch.empty((2, H, K), **f32)
-        nat.check(L.spp_gat_mh_logits_backward(_p(x), elem, xs, S, T, K, H, _p(g_as), _p(g_ad), _p(g_V[0]),
-                                               _p(g_V[1]), st))
+        g_x, g_as, g_ad, g_V, gathered = _gat_kernels_backward(x, rowptr, col, a_src, a_dst, z, rmax, rsum, g_z, V,
+                                                               slope, want_gx, ctx.drop)
         if want_gx:                                                              # a_src = x V_src^T, a_dst = x[:T] V_dst^T
-            if not gather:
+            if not gathered:
                 g_x.addmm_(g_as, V[0])
                 g_x[:T].addmm_(g_ad, V[1])
             g_x = g_x.to(x.dtype)
@@ -1028,23 +1053,12 @@ class _GatLayer(torch.autograd.Function):
 
     @staticmethod
     def _forward(ctx, x, W, att_src, att_dst, rowptr, col, T, slope):
-        L = nat.load()
-        nat.require_device()
-        st = _stream()
-        S, K = x.size(0), x.size(1)
-        half = _ELEM[x.dtype]                                                # the element code (0 / 1 keep their meaning)
-        xs = x.stride(0) if S > 1 else K
         v = torch.stack([att_src, att_dst]).to(torch.float32) @ W.to(torch.float32)   # [2, K]: W^T att_src, W^T att_dst
-        a_src = torch.empty(S, dtype=torch.float32, device=x.device)
-        a_dst = torch.empty(T, dtype=torch.float32, device=x.device)
-        nat.check(L.spp_gat_logits(_p(x), half, xs, S, T, K, _p(v[0]), _p(v[1]), _p(a_src), _p(a_dst), st))
-        z = torch.empty((T, K), dtype=torch.float32, device=x.device)
-        rmax = torch.empty(T, dtype=torch.float32, device=x.device)
-        rsum = torch.empty(T, dtype=torch.float32, device=x.device)
-        nat.check(L.spp_gat_aggregate_forward(_p(rowptr), _p(col), T, _p(x), half, xs, K, _p(a_src), _p(a_dst),
-                                              float(slope), _p(z), _p(rmax), _p(rsum), st))
+        # the H = 1 buffers ([S, 1], [T, 1], [T, 1, K]) are the [S], [T], [T, K] ones: views where torch wants those
+        a_src, a_dst, z, rmax, rsum, _ = _gat_kernels_forward(x, v[0], v[1], rowptr, col, T, 1, slope)
+        z = z.view(T, x.size(1))
         ctx.save_for_backward(x, W, att_src, att_dst, rowptr, col, a_src, a_dst, z, rmax, rsum, v)
-        ctx.dims = (S, T, K, half, xs, float(slope))
+        ctx.dims = (T, float(slope))
         if ctx.amp:
             return z.to(torch.bfloat16) @ W.to(torch.bfloat16).t()
         return z @ W.t()
@@ -1056,10 +1070,8 @@ class _GatLayer(torch.autograd.Function):
 
     @staticmethod
     def _backward(ctx, g_out):
-        L = nat.load()
-        st = _stream()
         x, W, att_src, att_dst, rowptr, col, a_src, a_dst, z, rmax, rsum, v = ctx.saved_tensors
-        S, T, K, half, xs, slope = ctx.dims
+        T, slope = ctx.dims
         g_out = g_out.contiguous()
         if ctx.amp:                                                          # bf16 GEMMs, fp32 results
             g16 = g_out.to(torch.bfloat16)
@@ -1069,29 +1081,13 @@ class _GatLayer(torch.autograd.Function):
             gW = _wgrad(g_out, z)                                            # [N, K]
             g_z = g_out @ W                                                  # [T, K]
         want_gx = ctx.needs_input_grad[0]
-        E = col.numel()
-        gather = want_gx and E * K >= (1 << 22) and K % 4 == 0
-        g_as = torch.zeros(S, dtype=torch.float32, device=x.device)
-        g_ad = torch.empty(T, dtype=torch.float32, device=x.device)
-        if gather:
-            # input gradient by gather over the transposed hop: no E x K fp32 atomics, no zero fill, and the two
-            # rank-1 terms of the logits (a_src = x v_src, a_dst = x[:T] v_dst) are added in the same pass
-            g_x = torch.empty((S, K), dtype=torch.float32, device=x.device)
-            nbytes = int(L.spp_gat_aggregate_backward_gather_workspace_bytes(T, S, E))
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-            nat.check(L.spp_gat_aggregate_backward_gather(_p(rowptr), _p(col), T, S, E, _p(x), half, xs, K, _p(a_src),
-                                                          _p(a_dst), slope, _p(z), _p(rmax), _p(rsum), _p(g_z), _p(v[0]),
-                                                          _p(v[1]), _p(g_x), _p(g_as), _p(g_ad), _p(ws), nbytes, st))
-        else:
-            g_x = torch.zeros((S, K), dtype=torch.float32, device=x.device) if want_gx else None
-            nat.check(L.spp_gat_aggregate_backward(_p(rowptr), _p(col), T, _p(x), half, xs, K, _p(a_src), _p(a_dst), slope,
-                                                   _p(z), _p(rmax), _p(rsum), _p(g_z), _p(g_x), _p(g_as), _p(g_ad), st))
-        g_v = torch.empty((2, K), dtype=torch.float32, device=x.device)
-        nat.check(L.spp_gat_logits_backward(_p(x), half, xs, S, T, K, _p(g_as), _p(g_ad), _p(g_v[0]), _p(g_v[1]), st))
+        g_x, g_as, g_ad, g_v, gathered = _gat_kernels_backward(x, rowptr, col, a_src, a_dst, z, rmax, rsum, g_z, v,
+                                                               slope, want_gx, None)
+        g_v = g_v.view(2, -1)                                                # [2, 1, K] as [2, K]
         if want_gx:                                                          # a_src = x v_src, a_dst = x[:T] v_dst
-            if not gather:
-                g_x.addr_(g_as, v[0])
-                g_x[:T].addr_(g_ad, v[1])
+            if not gathered:
+                g_x.addr_(g_as.view(-1), v[0])
+                g_x[:T].addr_(g_ad.view(-1), v[1])
             g_x = g_x.to(x.dtype)
         # v = [att_src; att_dst] @ W
         att = torch.stack([att_src, att_dst]).to(torch.float32)

@@ -1,9 +1,9 @@
-"""Float64 restatement of the GAT training kernels (csrc/aggregate.hip: k_gat_mh_rowdot, k_gat_mh_agg_fwd,
+"""Float64 restatement of the GAT training kernels (csrc/gat.hip: k_gat_mh_rowdot, k_gat_mh_agg_fwd,
 k_gat_mh_agg_bwd, k_gat_mh_gx_gather, k_gat_mh_colsum, k_gat_fwd, k_gat_bwd) with a per-element rounding bound next to
 every value, and the planted hop and logit regimes the tests run them on.  A helper: no tests in here.  Everything is on
 the CPU, vectorised, in float64; the fp32 / fp16 / bf16 inputs convert to float64 exactly.
 
-The formulas (H heads, the header comments of aggregate.hip).  Row i's softmax entries are its CSR entries without the
+The formulas (H heads, the header comments of gat.hip).  Row i's softmax entries are its CSR entries without the
 diagonal ones (col == i) plus one self loop; n_i counts them.
   logits    a_src = x Vsrc^T [S, H],  a_dst = x[:T] Vdst^T [T, H]
   forward   raw_ij = a_src[j] + a_dst[i],  e_ij = raw > 0 ? raw : raw * slope,  m_i = max_j e_ij,  w_ij = exp(e_ij - m_i),

@@ -1,4 +1,4 @@
-"""-m gpu: attention dropout of the GAT training kernels (spp.h f3t; csrc/aggregate.hip k_gat_mh_agg_fwd / _bwd with
+"""-m gpu: attention dropout of the GAT training kernels (spp.h f3t; csrc/gat.hip k_gat_mh_agg_fwd / _bwd with
 kDrop, spp_gat_mh_attn_keep) on tests/gat_f64.py's planted hop (T = 70, S = 200: degrees 0 ... 130, empty rows, diagonal
 entries, sinks), K in {4, 64, 132}, H in {1, 2, 4, 8}, rows fp32 / fp16 / bf16, p in {0.5, 0.6}.
 

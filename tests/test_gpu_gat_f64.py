@@ -1,4 +1,4 @@
-"""-m gpu: the GAT training kernels (csrc/aggregate.hip: spp_gat_mh_logits, _aggregate_forward, _aggregate_backward in its
+"""-m gpu: the GAT training kernels (csrc/gat.hip: spp_gat_mh_logits, _aggregate_forward, _aggregate_backward in its
 atomic and vector forms, _aggregate_backward_gather, _logits_backward; spp_gat_forward / spp_gat_backward) against the
 float64 restatement and the per-element bounds of tests/gat_f64.py, on its planted hop and logit regimes.
 
