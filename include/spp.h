@@ -1760,6 +1760,76 @@ spp_status spp_graph_agg_weighted_forward(const spp_graph_agg_weighted_desc* des
                                           int64_t workspace_bytes, void* stream);
 spp_status spp_gcn_dinv(const spp_gcn_dinv_desc* desc, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * f3v  GATv2Conv ("dynamic attention", PyG's GATv2Conv) over an MFG hop, on rows the caller has projected:
+ *        x_l [S, H, C] = lin_l(x)          x_r [T, H, C] = lin_r(x_target)          D = H * C
+ *        e_ij^h     = sum_c att[h,c] * leaky_relu(x_l[j,h,c] + x_r[i,h,c], negative_slope)
+ *        alpha^h    = softmax_j(e_ij^h)
+ *        out[i,h,:] = sum_j alpha_ij^h * x_l[j,h,:]
+ *      Row i runs over its CSR entries with col == i dropped, plus one self loop (i, i) whose message is SOURCE row
+ *      x_l[i] (the set_diag convention of the GAT entries); a target with no kept entry returns x_l[i] exactly.
+ *      The nonlinearity sits between the projection and att, so the aggregate-then-project form of the GAT entries does
+ *      not apply: the logit of every entry is a C-wide dot product per head.
+ *
+ *   Layouts: x_l [S, D] and x_r [T, D], rows of x_elem (SPP_ELEM_F32 / _F16 / _BF16, one code for both), each with its own
+ *   row stride in elements; x_r may alias x_l (share_weights: x_r = x_l[:T]) or not -- neither is assumed.  att [H, C],
+ *   out and grad_out [T, D], row_max and row_sum [T, H], grad_x_l [S, D], grad_x_r [T, D], grad_att [H, C]: fp32, dense,
+ *   row-major.  Alignment: the rows of x_l / x_r to 4 elements (base and stride); att, out, grad_out, grad_x_l, grad_x_r,
+ *   grad_att to 16 bytes; row_max, row_sum to 4; rowptr, col to 8.
+ *   Shapes: heads in {1, 2, 4, 8}; C % 4 == 0 and C / 4 A POWER OF TWO (the per-head reduction is an xor butterfly over
+ *   aligned lane segments: C = 12, 20, 24, ... are refused, and the caller computes them another way); D <= 1024;
+ *   0 <= T <= S.  col may be NULL when the hop has no entries.
+ *
+ *   spp_gatv2_forward: writes out, row_max (the row's largest logit) and row_sum (sum_j exp(e_ij - row_max)).  One pass
+ *      over the row with a running maximum per head, in the order self loop, then CSR order (the order of
+ *      spp_gat_mh_aggregate_forward); weights by expf (the library function, not the __expf of the GAT entries: the
+ *      model-level comparison of DESIGN section 7 f3v is why).  A lane's four products of a logit, its chunks, and the
+ *      butterfly across the head's lanes are added in an order fixed by (H, C), which this header does not spell out:
+ *      compare row_max within the rounding of a C-term dot product, not bit for bit.  No atomics: the same bits in every run.
+ *   spp_gatv2_backward: reads the forward's out, row_max, row_sum and grad_out (g).  Per head, with
+ *      alpha_ij = expf(e_ij - row_max) / row_sum (e recomputed; no [E, H] array), pre = x_l[j,h,c] + x_r[i,h,c] and
+ *      d = pre > 0 ? 1 : negative_slope  (so lrelu'(0) = negative_slope):
+ *        go = g_i . out_i     gh = g_i . x_l[j]     ge = alpha (gh - go)
+ *        grad_x_l[j,h,c] += alpha * g[i,h,c] + ge * att[h,c] * d     fp32 atomics, one per column per entry, on
+ *                                                                     buffers the CALLER has zeroed; NULL: not wanted
+ *        grad_x_r[i,h,c]  = sum_j ge * att[h,c] * d                   written completely
+ *        grad_att[h,c]    = sum_ij ge * leaky_relu(pre)               zeroed by the entry, then one atomic per column
+ *                                                                     per workgroup
+ *
+ *   Refused with SPP_ERR_INVALID before anything is enqueued, checked in this order: a NULL descriptor; heads outside
+ *   {1, 2, 4, 8}; an unknown x_elem; C <= 0 or C % 4 != 0; C / 4 not a power of two; D > 1024; T < 0 or S < T;
+ *   (backward: a NULL or misaligned grad_att;)  -- T == 0 returns SPP_OK here (the backward after zeroing grad_att) --
+ *   a row stride below D or not a multiple of 4; a NULL rowptr, x_l, x_r, att, out, row_max or row_sum; one of them, or
+ *   col, misaligned; (backward: a NULL grad_out or grad_x_r; a misaligned grad_out, grad_x_l or grad_x_r).
+ *   T > 0 with no entries is a hop like any other.  SPP_ABI_VERSION stays 6.
+ * ------------------------------------------------------------------------- */
+typedef struct spp_gatv2_desc {
+  int32_t heads;              /* H: 1, 2, 4 or 8 */
+  int32_t x_elem;             /* x_l and x_r: SPP_ELEM_F32 / _F16 / _BF16 */
+  float negative_slope;
+  int32_t reserved;
+  const int64_t* rowptr_dev;
+  const int64_t* col_dev;
+  int64_t num_targets;        /* T */
+  int64_t num_sources;        /* S >= T */
+  int64_t C;                  /* channels per head */
+  const void* x_l_dev;        /* [S, D] */
+  int64_t x_l_stride_elems;
+  const void* x_r_dev;        /* [T, D]; may alias x_l_dev */
+  int64_t x_r_stride_elems;
+  const float* att_dev;       /* fp32 [H, C] */
+  float* out_dev;             /* fp32 [T, D]: written by the forward, read by the backward */
+  float* row_max_dev;         /* fp32 [T, H]: likewise */
+  float* row_sum_dev;         /* fp32 [T, H]: likewise */
+  const float* grad_out_dev;  /* backward: fp32 [T, D] */
+  float* grad_x_l_dev;        /* backward: fp32 [S, D], zeroed by the caller; NULL: not wanted */
+  float* grad_x_r_dev;        /* backward: fp32 [T, D] */
+  float* grad_att_dev;        /* backward: fp32 [H, C], zeroed by the entry */
+} spp_gatv2_desc;
+
+spp_status spp_gatv2_forward(const spp_gatv2_desc* desc, void* stream);
+spp_status spp_gatv2_backward(const spp_gatv2_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

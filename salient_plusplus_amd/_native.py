@@ -127,6 +127,15 @@ class GcnNormDesc(C.Structure):
                 ("self_coef_dev", p)]
 
 
+class Gatv2Desc(C.Structure):
+    """spp_gatv2_desc: GATv2Conv over a hop on projected rows x_l [S, H*C], x_r [T, H*C]; forward and backward"""
+    _fields_ = [("heads", i32), ("x_elem", i32), ("negative_slope", C.c_float), ("reserved", i32), ("rowptr_dev", p),
+                ("col_dev", p), ("num_targets", i64), ("num_sources", i64), ("C", i64), ("x_l_dev", p),
+                ("x_l_stride_elems", i64), ("x_r_dev", p), ("x_r_stride_elems", i64), ("att_dev", p), ("out_dev", p),
+                ("row_max_dev", p), ("row_sum_dev", p), ("grad_out_dev", p), ("grad_x_l_dev", p), ("grad_x_r_dev", p),
+                ("grad_att_dev", p)]
+
+
 class GcnDinvDesc(C.Structure):
     """spp_gcn_dinv_desc: gcn_norm's first pass alone, dinv [num_nodes] over a whole graph"""
     _fields_ = [("fill", i32), ("reserved", i32), ("rowptr_dev", p), ("num_nodes", i64), ("w_dev", p), ("dinv_dev", p)]
@@ -375,6 +384,8 @@ SIGNATURES = {
     "spp_gcn_norm": (C.c_int, [C.POINTER(GcnNormDesc), p]),
     "spp_graph_agg_weighted_forward": (C.c_int, [C.POINTER(GraphAggWeightedDesc), p, i64, p]),
     "spp_gcn_dinv": (C.c_int, [C.POINTER(GcnDinvDesc), p]),
+    "spp_gatv2_forward": (C.c_int, [C.POINTER(Gatv2Desc), p]),
+    "spp_gatv2_backward": (C.c_int, [C.POINTER(Gatv2Desc), p]),
 }
 SPP_COMM_ID_BYTES = 128
 SPP_IPC_HANDLE_BYTES = 64

@@ -1,0 +1,372 @@
+// f3v: GATv2Conv ("dynamic attention", Brody et al.) training over an MFG hop: the forward / backward pair behind
+// spp_gatv2_forward / spp_gatv2_backward of include/spp.h.
+//     x_l [S, H, C] = lin_l(x),   x_r [T, H, C] = lin_r(x_target)     (projected by the caller; x_r may alias x_l)
+//     e_ij^h     = sum_c att[h,c] * leaky_relu(x_l[j,h,c] + x_r[i,h,c], slope)
+//     out[i,h,:] = sum_j softmax_j(e_ij^h) * x_l[j,h,:]
+// over row i without its diagonal entries (col == i) plus one self loop (i, i) whose message is SOURCE row i: the set_diag
+// convention of gat.hip.  The nonlinearity sits between the projection and att, so GAT's aggregate-first trick
+// (att . (W x_j) = x_j . (W^T att)) does not apply: every edge's logit is a C-wide dot product per head, reduced across
+// lanes, and the hot loops below are their own.  What they keep from gat.hip: the per-head online softmax in the order
+// self loop, then CSR; several neighbours' loads in flight per round; one fp32 atomic per column per edge on contiguous
+// wave-wide segments for grad_xl; element I/O and the entry checks of elem_io.hip.h.
+// Built for C / 4 a power of two (the per-head reduction is an xor butterfly over aligned lane segments); with H in
+// {1, 2, 4, 8} D = H * C is then a power of two as well, 4 <= D <= 1024.
+#include "elem_io.hip.h"
+
+#include <algorithm>
+#include <type_traits>
+
+namespace spp {
+
+constexpr int kV2NT = 256;
+
+__device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
+__device__ __forceinline__ float dot_lrelu(const f4& a, const f4& x, const f4& r, float slope) {
+  return a.x * lrelu(x.x + r.x, slope) + a.y * lrelu(x.y + r.y, slope) + a.z * lrelu(x.z + r.z, slope) +
+         a.w * lrelu(x.w + r.w, slope);
+}
+
+// Forward.  4 columns per lane: piece p = q * lpr + lane holds columns 4p .. 4p + 3, q < NQ chunks of lpr = min(64, D / 4)
+// lanes.  A head is G = C / 4 consecutive pieces: G <= lpr lanes of one chunk (CPH = 1: a lane sees NQ heads, one per
+// chunk) or CPH = G / lpr whole chunks (a lane sees NQ / CPH heads).  A lane's partial dot of a head is the sum over its
+// CPH chunks, four products each; the partials are added by an xor butterfly over the min(G, lpr) lanes of the head's
+// segment, so every lane of the segment holds the logit and runs the head's online softmax for its own columns.
+// NB neighbours per round: ids, then rows, then partial dots, then ONE butterfly whose steps carry all NB * HL values
+// (one dependent reduction per edge was the slow version).  No atomics: the same bits in every run.
+template <typename Tin, int NQ, int CPH>
+__global__ __launch_bounds__(kV2NT) void k_gatv2_fwd(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,
+                                                     int64_t T, const Tin* xl, int64_t xl_stride, const Tin* xr,
+                                                     int64_t xr_stride, const float* __restrict__ att, float slope,
+                                                     int lpr_log2, int seg_log2, int g_log2, int H,
+                                                     float* __restrict__ out, float* __restrict__ row_max,
+                                                     float* __restrict__ row_sum) {
+  constexpr int HL = NQ / CPH;           // heads a lane takes part in
+  constexpr int NB = NQ <= 2 ? 4 : 2;    // neighbours in flight (NQ = 4: 16 columns per lane and neighbour)
+  const int lpr = 1 << lpr_log2;
+  const int lane = threadIdx.x & (lpr - 1);
+  const int64_t t = ((int64_t)blockIdx.x * kV2NT + threadIdx.x) >> lpr_log2;
+  if (t >= T) return;  // whole groups leave together (the shuffles below stay inside a group)
+  const int64_t D = (int64_t)NQ * lpr * 4;
+  const int64_t b = rowptr[t], e = rowptr[t + 1];
+  f4 av[NQ], rv[NQ], acc[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const int64_t c = ((int64_t)q * lpr + lane) * 4;
+    av[q] = load4(att + c);
+    rv[q] = load4(xr + t * xr_stride + c);
+    acc[q] = load4(xl + t * xl_stride + c);  // the self loop's message: source row t
+  }
+  float mm[HL], ss[HL];
+#pragma unroll
+  for (int hl = 0; hl < HL; ++hl) {
+    float pd = 0.f;
+#pragma unroll
+    for (int q = hl * CPH; q < (hl + 1) * CPH; ++q) pd += dot_lrelu(av[q], acc[q], rv[q], slope);
+    mm[hl] = pd;
+    ss[hl] = 1.f;
+  }
+  for (int d = (1 << seg_log2) >> 1; d >= 1; d >>= 1)
+#pragma unroll
+    for (int hl = 0; hl < HL; ++hl) mm[hl] += __shfl_xor(mm[hl], d, kWave);
+  for (int64_t k0 = b; k0 < e; k0 += NB) {
+    int64_t j[NB];
+#pragma unroll
+    for (int u = 0; u < NB; ++u) j[u] = col[k0 + u < e ? k0 + u : e - 1];  // clamped, unpredicated
+    f4 xv[NB][NQ];
+#pragma unroll
+    for (int u = 0; u < NB; ++u)
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) xv[u][q] = load4(xl + j[u] * xl_stride + ((int64_t)q * lpr + lane) * 4);
+    float pd[NB][HL];
+#pragma unroll
+    for (int u = 0; u < NB; ++u)
+#pragma unroll
+      for (int hl = 0; hl < HL; ++hl) {
+        pd[u][hl] = 0.f;
+#pragma unroll
+        for (int q = hl * CPH; q < (hl + 1) * CPH; ++q) pd[u][hl] += dot_lrelu(av[q], xv[u][q], rv[q], slope);
+      }
+    for (int d = (1 << seg_log2) >> 1; d >= 1; d >>= 1)
+#pragma unroll
+      for (int u = 0; u < NB; ++u)
+#pragma unroll
+        for (int hl = 0; hl < HL; ++hl) pd[u][hl] += __shfl_xor(pd[u][hl], d, kWave);
+#pragma unroll
+    for (int u = 0; u < NB; ++u) {
+      if (k0 + u >= e || j[u] == t) continue;  // set_diag drops existing diagonal entries
+#pragma unroll
+      for (int hl = 0; hl < HL; ++hl) {
+        const float sc = pd[u][hl];
+        if (sc > mm[hl]) {
+          const float r = expf(mm[hl] - sc);
+#pragma unroll
+          for (int q = hl * CPH; q < (hl + 1) * CPH; ++q) {
+            acc[q].x *= r; acc[q].y *= r; acc[q].z *= r; acc[q].w *= r;
+          }
+          ss[hl] *= r;
+          mm[hl] = sc;
+        }
+        const float w = expf(sc - mm[hl]);
+        ss[hl] += w;
+#pragma unroll
+        for (int q = hl * CPH; q < (hl + 1) * CPH; ++q) {
+          acc[q].x += w * xv[u][q].x; acc[q].y += w * xv[u][q].y; acc[q].z += w * xv[u][q].z; acc[q].w += w * xv[u][q].w;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const int hl = q / CPH;
+    const int p = q * lpr + lane;
+    const float inv = 1.f / ss[hl];
+    *reinterpret_cast<float4*>(out + t * D + (int64_t)p * 4) =
+        make_float4(acc[q].x * inv, acc[q].y * inv, acc[q].z * inv, acc[q].w * inv);
+    if ((p & ((1 << g_log2) - 1)) == 0) {  // the head's first piece
+      row_max[t * H + (p >> g_log2)] = mm[hl];
+      row_sum[t * H + (p >> g_log2)] = ss[hl];
+    }
+  }
+}
+
+// Backward.  ONE column per lane and step, c = lane + lpt * i, i < NS, lpt = min(64, D) lanes per target: a group's
+// loads and -- what matters -- its fp32 atomics on grad_xl are contiguous 4 * lpt-byte segments (gat.hip,
+// k_gat_mh_agg_bwd: the atomic units run at full rate on contiguous 256-byte wave instructions and ~17x slower on
+// scattered ones); one atomic per column per edge.  A head is C consecutive columns: C <= lpt lanes of one step
+// (SPH = 1) or SPH = C / 64 whole steps; a lane takes part in HL = NS / SPH heads.  Per entry the logit e^h (recomputed;
+// alpha = expf(e - row_max) / row_sum, no [E, H] array) and gh^h = g_i . x_l[j] are reduced by one butterfly.
+// A group walks tpg consecutive targets; its lanes keep the grad_att sums of their columns in registers over all of
+// them, and a workgroup adds them up (across the groups of a wavefront by shuffles, across wavefronts through LDS) before
+// its D atomics on grad_att (k_gat_mh_colsum's rule: every workgroup ends on the SAME addresses).
+// lrelu'(0) = slope (v > 0 ? 1 : slope).
+template <typename Tin, int NS, int SPH>
+__global__ __launch_bounds__(kV2NT) void k_gatv2_bwd(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,
+                                                     int64_t T, const Tin* xl, int64_t xl_stride, const Tin* xr,
+                                                     int64_t xr_stride, const float* __restrict__ att, float slope,
+                                                     int lpt_log2, int seg_log2, int c_log2, int H,
+                                                     const float* __restrict__ out, const float* __restrict__ row_max,
+                                                     const float* __restrict__ row_sum, const float* __restrict__ g,
+                                                     int64_t tpg, float* __restrict__ grad_xl,
+                                                     float* __restrict__ grad_xr, float* __restrict__ grad_att) {
+  constexpr int HL = NS / SPH;
+  __shared__ float red[kV2NT / kWave][NS][kWave];
+  const int lpt = 1 << lpt_log2;
+  const int lane = threadIdx.x & (lpt - 1);
+  const int64_t D = (int64_t)NS * lpt;
+  const int64_t gid = ((int64_t)blockIdx.x * kV2NT + threadIdx.x) >> lpt_log2;
+  const int64_t t0 = gid * tpg < T ? gid * tpg : T;
+  const int64_t t1 = t0 + tpg < T ? t0 + tpg : T;
+  float av[NS], ga[NS];
+#pragma unroll
+  for (int i = 0; i < NS; ++i) {
+    av[i] = att[lane + lpt * i];
+    ga[i] = 0.f;
+  }
+  for (int64_t t = t0; t < t1; ++t) {
+    const int64_t b = rowptr[t], e = rowptr[t + 1];
+    float gv[NS], rv[NS], gr[NS], go[HL], m[HL], inv_s[HL];
+#pragma unroll
+    for (int hl = 0; hl < HL; ++hl) {
+      const int head = (lane + lpt * hl * SPH) >> c_log2;
+      m[hl] = row_max[t * H + head];
+      inv_s[hl] = 1.f / row_sum[t * H + head];
+      go[hl] = 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      const int64_t c = lane + lpt * i;
+      gv[i] = g[t * D + c];
+      rv[i] = load1(xr + t * xr_stride + c);
+      gr[i] = 0.f;
+      go[i / SPH] += gv[i] * out[t * D + c];
+    }
+    for (int d = (1 << seg_log2) >> 1; d >= 1; d >>= 1)
+#pragma unroll
+      for (int hl = 0; hl < HL; ++hl) go[hl] += __shfl_xor(go[hl], d, kWave);
+    for (int64_t k = b - 1; k < e; ++k) {  // k == b - 1 stands for the self loop
+      const int64_t j = k < b ? t : col[k];
+      if (k >= b && j == t) continue;  // set_diag drops existing diagonal entries
+      float xv[NS], pe[HL], gh[HL];
+#pragma unroll
+      for (int i = 0; i < NS; ++i) xv[i] = load1(xl + j * xl_stride + lane + lpt * i);
+#pragma unroll
+      for (int hl = 0; hl < HL; ++hl) pe[hl] = gh[hl] = 0.f;
+#pragma unroll
+      for (int i = 0; i < NS; ++i) {
+        pe[i / SPH] += av[i] * lrelu(xv[i] + rv[i], slope);
+        gh[i / SPH] += gv[i] * xv[i];
+      }
+      for (int d = (1 << seg_log2) >> 1; d >= 1; d >>= 1)
+#pragma unroll
+        for (int hl = 0; hl < HL; ++hl) {
+          pe[hl] += __shfl_xor(pe[hl], d, kWave);
+          gh[hl] += __shfl_xor(gh[hl], d, kWave);
+        }
+      float a[HL], ge[HL];
+#pragma unroll
+      for (int hl = 0; hl < HL; ++hl) {
+        a[hl] = expf(pe[hl] - m[hl]) * inv_s[hl];
+        ge[hl] = a[hl] * (gh[hl] - go[hl]);
+      }
+#pragma unroll
+      for (int i = 0; i < NS; ++i) {
+        const float pre = xv[i] + rv[i];
+        const float tt = ge[i / SPH] * av[i] * (pre > 0.f ? 1.f : slope);
+        gr[i] += tt;
+        ga[i] += ge[i / SPH] * lrelu(pre, slope);
+        if (grad_xl) unsafeAtomicAdd(grad_xl + j * D + lane + lpt * i, a[i / SPH] * gv[i] + tt);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < NS; ++i) grad_xr[t * D + lane + lpt * i] = gr[i];
+  }
+  // grad_att: the groups of a wavefront hold the same columns (lpt < 64), then the wavefronts of the workgroup
+  const int wl = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+#pragma unroll
+  for (int i = 0; i < NS; ++i) {
+    float v = ga[i];
+    for (int d = lpt; d < kWave; d <<= 1) v += __shfl_xor(v, d, kWave);
+    red[wave][i][wl] = v;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < lpt) {
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      float s = 0.f;
+#pragma unroll
+      for (int w = 0; w < kV2NT / kWave; ++w) s += red[w][i][threadIdx.x];
+      unsafeAtomicAdd(grad_att + threadIdx.x + lpt * i, s);
+    }
+  }
+}
+
+}  // namespace spp
+
+using namespace spp;
+
+static int log2_of(int64_t v) {
+  int l = 0;
+  while ((1ll << l) < v) ++l;
+  return l;
+}
+static bool pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
+
+template <int N> using IC = std::integral_constant<int, N>;
+// fn(IC<NQ>{}, IC<CPH>{}): the forward's chunks per lane and chunks per head
+template <class Fn>
+static void with_fwd_shape(int nq, int cph, Fn&& fn) {
+  switch (nq * 8 + cph) {
+    case 1 * 8 + 1: fn(IC<1>{}, IC<1>{}); break;
+    case 2 * 8 + 1: fn(IC<2>{}, IC<1>{}); break;
+    case 2 * 8 + 2: fn(IC<2>{}, IC<2>{}); break;
+    case 4 * 8 + 1: fn(IC<4>{}, IC<1>{}); break;
+    case 4 * 8 + 2: fn(IC<4>{}, IC<2>{}); break;
+    default: fn(IC<4>{}, IC<4>{}); break;
+  }
+}
+// fn(IC<NS>{}, IC<SPH>{}): the backward's steps per lane and steps per head (NS / SPH <= 8 heads)
+template <class Fn>
+static void with_bwd_shape(int ns, int sph, Fn&& fn) {
+  switch (ns * 32 + sph) {
+    case 1 * 32 + 1: fn(IC<1>{}, IC<1>{}); break;
+    case 2 * 32 + 1: fn(IC<2>{}, IC<1>{}); break;
+    case 2 * 32 + 2: fn(IC<2>{}, IC<2>{}); break;
+    case 4 * 32 + 1: fn(IC<4>{}, IC<1>{}); break;
+    case 4 * 32 + 2: fn(IC<4>{}, IC<2>{}); break;
+    case 4 * 32 + 4: fn(IC<4>{}, IC<4>{}); break;
+    case 8 * 32 + 1: fn(IC<8>{}, IC<1>{}); break;
+    case 8 * 32 + 2: fn(IC<8>{}, IC<2>{}); break;
+    case 8 * 32 + 4: fn(IC<8>{}, IC<4>{}); break;
+    case 8 * 32 + 8: fn(IC<8>{}, IC<8>{}); break;
+    case 16 * 32 + 2: fn(IC<16>{}, IC<2>{}); break;
+    case 16 * 32 + 4: fn(IC<16>{}, IC<4>{}); break;
+    case 16 * 32 + 8: fn(IC<16>{}, IC<8>{}); break;
+    default: fn(IC<16>{}, IC<16>{}); break;
+  }
+}
+
+// The checks of both entries, in the order include/spp.h documents: descriptor, head count, element code, C, D, sizes
+// (T == 0 is decided by the caller right after), strides, NULL buffers, alignment.  Nothing here touches the device.
+static spp_status gatv2_check_shape(const spp_gatv2_desc* d, const char* who) {
+  SPP_REQUIRE(d != nullptr, "%s: NULL descriptor", who);
+  SPP_REQUIRE(d->heads == 1 || d->heads == 2 || d->heads == 4 || d->heads == 8,
+              "%s: heads must be 1, 2, 4 or 8 (got %d)", who, (int)d->heads);
+  SPP_REQUIRE(elem_ok(d->x_elem), "%s: unknown element code %d", who, (int)d->x_elem);
+  SPP_REQUIRE(d->C > 0 && d->C % 4 == 0, "%s: needs C > 0 and C %% 4 == 0 (got %lld)", who, (long long)d->C);
+  SPP_REQUIRE(pow2(d->C / 4), "%s: built for C / 4 a power of two (got C = %lld)", who, (long long)d->C);
+  SPP_REQUIRE(d->C <= 1024 && d->heads * d->C <= 1024, "%s: needs D = heads * C <= 1024", who);
+  SPP_REQUIRE(d->num_targets >= 0 && d->num_sources >= d->num_targets, "%s: needs 0 <= T <= S", who);
+  return SPP_OK;
+}
+static spp_status gatv2_check_rows(const spp_gatv2_desc* d, const char* who) {
+  const int64_t D = d->heads * d->C, esz = elem_bytes(d->x_elem);
+  SPP_REQUIRE(d->x_l_stride_elems >= D && d->x_r_stride_elems >= D && d->x_l_stride_elems % 4 == 0 &&
+                  d->x_r_stride_elems % 4 == 0,
+              "%s: a row stride is smaller than D or not a multiple of 4 elements", who);
+  SPP_REQUIRE(d->rowptr_dev && d->x_l_dev && d->x_r_dev && d->att_dev && d->out_dev && d->row_max_dev && d->row_sum_dev,
+              "%s: NULL buffer", who);
+  SPP_REQUIRE(aligned_to(d->x_l_dev, 4 * esz) && aligned_to(d->x_r_dev, 4 * esz) && aligned_to(d->att_dev, 16) &&
+                  aligned_to(d->out_dev, 16) && aligned_to(d->row_max_dev, 4) && aligned_to(d->row_sum_dev, 4) &&
+                  aligned_to(d->rowptr_dev, 8) && aligned_to(d->col_dev, 8),
+              "%s: misaligned buffer (rows: 4 elements; att, out: 16 bytes)", who);
+  return SPP_OK;
+}
+
+extern "C" spp_status spp_gatv2_forward(const spp_gatv2_desc* d, void* stream) {
+  const char* who = "spp_gatv2_forward";
+  SPP_TRY(gatv2_check_shape(d, who));
+  if (d->num_targets == 0) return SPP_OK;
+  SPP_TRY(gatv2_check_rows(d, who));
+  const int64_t T = d->num_targets, G = d->C / 4, P = d->heads * G;
+  const int lpr_log2 = lanes_log2(P), lpr = 1 << lpr_log2;
+  const int nq = (int)(P / lpr), cph = (int)std::max<int64_t>(1, G / lpr);
+  const int seg_log2 = log2_of(std::min<int64_t>(G, lpr)), g_log2 = log2_of(G);
+  const unsigned grid = (unsigned)ceil_div(T << lpr_log2, kV2NT);
+  with_elem(d->x_elem, [&](auto tin) {
+    with_fwd_shape(nq, cph, [&](auto q, auto c) {
+      using Tin = typename decltype(tin)::type;
+      hipLaunchKernelGGL((k_gatv2_fwd<Tin, decltype(q)::value, decltype(c)::value>), dim3(grid), dim3(kV2NT), 0,
+                         as_stream(stream), d->rowptr_dev, d->col_dev, T, static_cast<const Tin*>(d->x_l_dev),
+                         d->x_l_stride_elems, static_cast<const Tin*>(d->x_r_dev), d->x_r_stride_elems, d->att_dev,
+                         d->negative_slope, lpr_log2, seg_log2, g_log2, (int)d->heads, d->out_dev, d->row_max_dev,
+                         d->row_sum_dev);
+    });
+  });
+  SPP_HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
+
+extern "C" spp_status spp_gatv2_backward(const spp_gatv2_desc* d, void* stream) {
+  const char* who = "spp_gatv2_backward";
+  SPP_TRY(gatv2_check_shape(d, who));
+  const int64_t T = d->num_targets, D = d->heads * d->C;
+  SPP_REQUIRE(d->grad_att_dev && aligned_to(d->grad_att_dev, 16), "%s: NULL or misaligned grad_att", who);
+  if (T > 0) {
+    SPP_TRY(gatv2_check_rows(d, who));
+    SPP_REQUIRE(d->grad_out_dev && d->grad_x_r_dev, "%s: NULL buffer", who);
+    SPP_REQUIRE(aligned_to(d->grad_out_dev, 16) && aligned_to(d->grad_x_r_dev, 16) && aligned_to(d->grad_x_l_dev, 16),
+                "%s: misaligned buffer (grad_out, grad_x_l, grad_x_r: 16 bytes)", who);
+  }
+  hipStream_t st = as_stream(stream);
+  SPP_HIP_TRY(hipMemsetAsync(d->grad_att_dev, 0, sizeof(float) * (size_t)D, st));
+  if (T == 0) return SPP_OK;
+  const int lpt_log2 = log2_of(std::min<int64_t>(D, kWave)), lpt = 1 << lpt_log2;
+  const int ns = (int)(D / lpt), sph = (int)std::max<int64_t>(1, d->C / kWave);
+  const int seg_log2 = log2_of(std::min<int64_t>(d->C, lpt)), c_log2 = log2_of(d->C);
+  // every workgroup ends in D atomics onto the same addresses: about 1024 workgroups, whatever T is
+  const int64_t gpb = kV2NT / lpt;
+  const int64_t tpg = std::max<int64_t>(1, ceil_div(T, 1024 * gpb));
+  const unsigned grid = (unsigned)ceil_div(ceil_div(T, tpg), gpb);
+  with_elem(d->x_elem, [&](auto tin) {
+    with_bwd_shape(ns, sph, [&](auto n, auto s) {
+      using Tin = typename decltype(tin)::type;
+      hipLaunchKernelGGL((k_gatv2_bwd<Tin, decltype(n)::value, decltype(s)::value>), dim3(grid), dim3(kV2NT), 0, st,
+                         d->rowptr_dev, d->col_dev, T, static_cast<const Tin*>(d->x_l_dev), d->x_l_stride_elems,
+                         static_cast<const Tin*>(d->x_r_dev), d->x_r_stride_elems, d->att_dev, d->negative_slope,
+                         lpt_log2, seg_log2, c_log2, (int)d->heads, d->out_dev, d->row_max_dev, d->row_sum_dev,
+                         d->grad_out_dev, tpg, d->grad_x_l_dev, d->grad_x_r_dev, d->grad_att_dev);
+    });
+  });
+  SPP_HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}

@@ -1159,6 +1159,208 @@ class GAT(torch.nn.Module):
 
 
 # --------------------------------------------------------------------------------------------
+# GATv2  (PyG's GATv2Conv, "dynamic attention": csrc/gatv2.hip, spp.h f3v)
+# --------------------------------------------------------------------------------------------
+_GATV2_HEADS = (1, 2, 4, 8)        # the head counts spp_gatv2_forward / _backward are built for
+
+
+def _gatv2_reference(x_l, x_r, att, rowptr, col, slope, p=0.0):
+    """GATv2Conv's message passing in PyG's order, in plain torch ops, on the projected rows: x_l [S, H, C] = lin_l(x),
+    x_r [T, H, C] = lin_r(x_target), att [H, C] -> out [T, H, C] (fp32; float64 for float64 rows).  The path for
+    everything the kernels do not read: CPU tensors, head counts outside {1, 2, 4, 8}, C with C / 4 not a power of two,
+    H * C > 1024, share_weights with a target block that is not the prefix of x, and training with dropout.
+    set_diag: diagonal entries dropped, one self loop (i, i) per target, whose message is source row i.
+    p > 0 (training): F.dropout on alpha -- torch's own mask, from the generator of alpha's device."""
+    T, H = x_r.size(0), att.size(0)
+    dt = torch.float64 if x_l.dtype == torch.float64 else torch.float32
+    x_l, x_r, att = x_l.to(dt), x_r.to(dt), att.to(dt)
+    dst = torch.repeat_interleave(torch.arange(T, device=col.device), rowptr[1:] - rowptr[:-1])
+    keep = col != dst
+    loops = torch.arange(T, device=col.device)
+    src, dst = torch.cat([col[keep], loops]), torch.cat([dst[keep], loops])
+    e = (F.leaky_relu(x_l[src] + x_r[dst], slope) * att).sum(-1)            # [E', H]
+    emax = torch.full((T, H), float("-inf"), dtype=dt, device=e.device)
+    emax = emax.scatter_reduce(0, dst[:, None].expand(-1, H), e, "amax")
+    w = torch.exp(e - emax[dst])
+    den = torch.zeros((T, H), dtype=dt, device=e.device).index_add_(0, dst, w)
+    alpha = w / den[dst]
+    if p > 0.0:
+        alpha = F.dropout(alpha, p, training=True)
+    return torch.zeros((T,) + tuple(x_l.shape[1:]), dtype=dt, device=e.device).index_add_(0, dst, alpha[:, :, None] * x_l[src])
+
+
+def _gatv2_desc(x_l, x_r, att, rowptr, col, slope, out, rmax, rsum, **grads):
+    """spp_gatv2_desc for projected rows x_l [S, D], x_r [T, D] (unit column stride, one dtype) and att [H, C] fp32"""
+    H, Cc = att.shape
+    S, T, D = x_l.size(0), x_r.size(0), H * Cc
+    return nat.Gatv2Desc(heads=H, x_elem=_ELEM[x_l.dtype], negative_slope=float(slope), rowptr_dev=_p(rowptr),
+                         col_dev=_p(col), num_targets=T, num_sources=S, C=Cc, x_l_dev=_p(x_l),
+                         x_l_stride_elems=x_l.stride(0) if S > 1 else D, x_r_dev=_p(x_r),
+                         x_r_stride_elems=x_r.stride(0) if T > 1 else D, att_dev=_p(att), out_dev=_p(out),
+                         row_max_dev=_p(rmax), row_sum_dev=_p(rsum), **{k: _p(v) for k, v in grads.items()})
+
+
+def _gatv2_kernels_read(x_l, x_r, H, Cc):
+    """the rows and widths spp_gatv2_forward accepts (spp.h f3v)"""
+    g = Cc // 4
+    return (x_l.is_cuda and H in _GATV2_HEADS and Cc > 0 and Cc % 4 == 0 and g & (g - 1) == 0 and H * Cc <= 1024 and
+            x_l.dtype in _ELEM and x_r.dtype == x_l.dtype and x_l.dim() == 2 and x_r.dim() == 2 and
+            all(t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % (4 * t.element_size()) == 0
+                for t in (x_l, x_r)))
+
+
+class _GATv2Layer(torch.autograd.Function):
+    """GATv2Conv's message passing as ONE node on the projected rows: (x_l [S, D], x_r [T, D], att [H, C]) -> out
+    [T, H, C] fp32, spp_gatv2_forward / spp_gatv2_backward.  The rows are fp32, fp16 or bf16 (under bf16 autocast the
+    projections outside the node give bf16 rows, which the kernels read as such); x_r may be a view of x_l
+    (share_weights).  The node runs with autocast off, returns fp32 and casts grad_xl / grad_xr back to the rows' dtype;
+    att and its gradient are fp32."""
+
+    @staticmethod
+    def forward(ctx, x_l, x_r, att, rowptr, col, slope):
+        with _no_autocast():
+            L = nat.load()
+            nat.require_device()
+            H, Cc = att.shape
+            T = x_r.size(0)
+            att32 = att.detach().to(torch.float32).contiguous()
+            f32 = dict(dtype=torch.float32, device=x_l.device)
+            out = torch.empty((T, H, Cc), **f32)
+            rmax, rsum = torch.empty((T, H), **f32), torch.empty((T, H), **f32)
+            d = _gatv2_desc(x_l, x_r, att32, rowptr, col, slope, out, rmax, rsum)
+            nat.check(L.spp_gatv2_forward(C.byref(d), _stream()))
+            ctx.save_for_backward(x_l, x_r, att32, rowptr, col, out, rmax, rsum)
+            ctx.slope, ctx.att_dtype = float(slope), att.dtype
+            return out
+
+    @staticmethod
+    def backward(ctx, g):
+        with _no_autocast():
+            x_l, x_r, att32, rowptr, col, out, rmax, rsum = ctx.saved_tensors
+            H, Cc = att32.shape
+            S, T, D = x_l.size(0), x_r.size(0), H * Cc
+            g = g.to(torch.float32).contiguous()
+            f32 = dict(dtype=torch.float32, device=x_l.device)
+            g_xl = torch.zeros((S, D), **f32) if ctx.needs_input_grad[0] else None
+            g_xr, g_att = torch.empty((T, D), **f32), torch.empty((H, Cc), **f32)
+            d = _gatv2_desc(x_l, x_r, att32, rowptr, col, ctx.slope, out, rmax, rsum, grad_out_dev=g, grad_x_l_dev=g_xl,
+                            grad_x_r_dev=g_xr, grad_att_dev=g_att)
+            nat.check(nat.load().spp_gatv2_backward(C.byref(d), _stream()))
+            return (g_xl.to(x_l.dtype) if g_xl is not None else None,
+                    g_xr.to(x_r.dtype) if ctx.needs_input_grad[1] else None, g_att.to(ctx.att_dtype), None, None, None)
+
+
+class GATv2Conv(torch.nn.Module):
+    """torch_geometric.nn.GATv2Conv(in, out, heads=1, concat=True, negative_slope=0.2, dropout=0, add_self_loops=True,
+    bias=True, share_weights=False) on a bipartite ((x, x_target), adj_t), with PyG's parameter names (a PyG state dict
+    loads): lin_l (sources) and lin_r (targets; the SAME module as lin_l with share_weights), both [H * out, in] with a
+    bias when ``bias``; att [1, H, out]; bias of the output's width (H * out with ``concat``, else out).
+
+        x_l = lin_l(x) [S, H, C],  x_r = lin_r(x_target) [T, H, C]
+        e_ij^h = att[h] . leaky_relu(x_l[j,h] + x_r[i,h]),   out[i,h] = sum_j softmax_j(e_ij^h) x_l[j,h]
+
+    over row i without its diagonal entries plus one self loop whose message is source row i (GATConv's convention
+    here).  The projections are ordinary F.linear calls; the message passing is _GATv2Layer (csrc/gatv2.hip) for CUDA
+    rows with H in {1, 2, 4, 8}, C % 4 == 0 with C / 4 a power of two and H * C <= 1024, and _gatv2_reference, the same
+    function in plain torch ops, for everything else.  With share_weights and x_target the prefix of x, x_r is the view
+    x_l[:T]: no second GEMM, and autograd sums the two gradients through the view; share_weights with any other
+    x_target takes the reference path.  ``dropout`` = p: F.dropout on the attention coefficients in training -- the
+    reference path with torch's own mask (the in-kernel mask of the GAT kernels is not built for GATv2)."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, bias=True,
+                 share_weights=False):
+        super().__init__()
+        if not isinstance(heads, int) or heads < 1:
+            raise ValueError(f"heads must be a positive int, got {heads!r}")
+        if isinstance(dropout, bool) or not isinstance(dropout, (int, float)) or not 0.0 <= dropout < 1.0:
+            raise ValueError(f"dropout must be a number in [0, 1), got {dropout!r}")
+        self.heads, self.out_channels, self.concat = heads, out_channels, bool(concat)
+        self.negative_slope = negative_slope
+        self.dropout = float(dropout)
+        self.share_weights = bool(share_weights)
+        self.lin_l = torch.nn.Linear(in_channels, heads * out_channels, bias=bool(bias))
+        self.lin_r = self.lin_l if share_weights else torch.nn.Linear(in_channels, heads * out_channels, bias=bool(bias))
+        self.att = torch.nn.Parameter(torch.empty(1, heads, out_channels))
+        width = heads * out_channels if concat else out_channels
+        self.bias = torch.nn.Parameter(torch.zeros(width)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for lin in (self.lin_l, self.lin_r):                    # PyG: glorot weights, zero biases
+            torch.nn.init.xavier_uniform_(lin.weight)
+            if lin.bias is not None:
+                torch.nn.init.zeros_(lin.bias)
+        torch.nn.init.xavier_uniform_(self.att)
+        if self.bias is not None:
+            torch.nn.init.zeros_(self.bias)
+
+    def forward(self, x_pair, adj_t):
+        x, x_target = x_pair
+        rowptr, col, _ = adj_t.csr()
+        S, T, H, Cc = x.size(0), x_target.size(0), self.heads, self.out_channels
+        prefix = x_target.data_ptr() == x.data_ptr() and x_target.stride() == x.stride() and T <= S
+        if not torch.is_autocast_enabled(x.device.type):        # (autocast casts the GEMM's operands itself)
+            x, x_target = x.to(self.lin_l.weight.dtype), x_target.to(self.lin_r.weight.dtype)
+        x_l = self.lin_l(x)
+        x_r = x_l[:T] if self.share_weights and prefix else self.lin_r(x_target)
+        att = self.att.view(H, Cc)
+        p = self.dropout if self.training else 0.0
+        if p == 0.0 and (prefix or not self.share_weights) and _gatv2_kernels_read(x_l, x_r, H, Cc):
+            out = _GATv2Layer.apply(x_l, x_r, att, rowptr, col, self.negative_slope)
+        else:
+            out = _gatv2_reference(x_l.view(S, H, Cc), x_r.view(T, H, Cc), att, rowptr, col, self.negative_slope, p)
+        out = out.reshape(T, H * Cc) if self.concat else out.mean(1)
+        return out if self.bias is None else out + self.bias
+
+
+class GATv2(torch.nn.Module):
+    """GAT's shape with GATv2Conv layers: ``num_layers`` GATv2Conv(bias=False), ReLU + dropout 0.5 between layers,
+    log_softmax.  Every hidden layer is ``heads`` heads of ``hidden_channels // heads`` channels, concatenated (the hidden
+    width stays ``hidden_channels``, which must be a multiple of ``heads``); the last layer is the mean of its heads.
+    ``share_weights`` and ``attn_dropout`` are every conv's ``share_weights`` and ``dropout``."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, heads=1, share_weights=False,
+                 attn_dropout=0.0):
+        super().__init__()
+        if not isinstance(heads, int) or heads < 1:
+            raise ValueError(f"heads must be a positive int, got {heads!r}")
+        if hidden_channels % heads != 0:
+            raise ValueError(f"hidden_channels ({hidden_channels}) must be a multiple of heads ({heads})")
+        self.num_layers = num_layers
+        self.hidden_channels = hidden_channels
+        self.heads = heads
+        kw = dict(heads=heads, bias=False, share_weights=share_weights, dropout=attn_dropout)
+        c = hidden_channels // heads
+        self.convs = torch.nn.ModuleList()
+        self.convs.append(GATv2Conv(in_channels, c, concat=True, **kw))
+        for _ in range(num_layers - 2):
+            self.convs.append(GATv2Conv(hidden_channels, c, concat=True, **kw))
+        self.convs.append(GATv2Conv(hidden_channels, out_channels, concat=False, **kw))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for conv in self.convs:
+            conv.reset_parameters()
+            conv.apply(init_weights)
+
+    def forward(self, x, adjs):
+        if isinstance(x, (TableRows, RowRefs)):
+            x = x.materialize()
+        for i, (adj_t, _e_id, size) in enumerate(adjs):
+            x_target = x[:size[1]]
+            x = self.convs[i]((x, x_target), adj_t)
+            if i != self.num_layers - 1:
+                x = relu_dropout(x, 0.5, self.training)
+        return torch.log_softmax(x, dim=-1)
+
+    def inference(self, x_all, rowptr, col, **kw):
+        raise NotImplementedError("GATv2.inference: not a method of the model yet; layer-wise inference over whole "
+                                  "neighbour rows needs a long-row form of the GATv2 softmax (a C-wide dot product per "
+                                  "entry and head), which is not built: inference.layerwise_inference and its siblings "
+                                  "refuse a GATv2 model")
+
+
+# --------------------------------------------------------------------------------------------
 # GIN  (driver/models.py:234-283: GINConv(Sequential(Linear, BatchNorm1d, ReLU, Linear, ReLU)), eps = 0)
 # --------------------------------------------------------------------------------------------
 _SUM_GATHER_MIN_WORK = 1 << 22      # E x F from which the input gradient is gathered, as in the mean's backward
@@ -1713,9 +1915,10 @@ _UNSUPPORTED_MODELS = {"sageclassic": "not used in the paper", "jknet": "not use
 
 
 def get_model_type(model_name):
-    """driver/main.py:74-95 for the four models the reference marks as working (names case-insensitive)"""
+    """driver/main.py:74-95 for the four models the reference marks as working (names case-insensitive), and "gatv2"
+    (GATv2, which the reference does not have)"""
     name = model_name.lower()
-    models = {"sage": SAGE, "gat": GAT, "gin": GIN, "sageresinception": SAGEResInception}
+    models = {"sage": SAGE, "gat": GAT, "gin": GIN, "sageresinception": SAGEResInception, "gatv2": GATv2}
     if name in models:
         return models[name]
     if name in _UNSUPPORTED_MODELS:

@@ -1,13 +1,14 @@
 """One resident batch of the bench workload, N optimisation steps of one of the models (models.get_model_type: SAGE, GAT,
 GIN, SAGEResInception; and models.GCN) on it (fwd + bwd + Adam), timed; run under `rocprofv3 --kernel-trace --stats` for the per-kernel
 table.
-usage: model_step_profile.py [sage|gat|gin|sageresinception|gcn] [steps=30] [workload=S-papers] [fused] [max] [norm] [--amp bf16] [--heads H] [attn=P]
+usage: model_step_profile.py [sage|gat|gatv2|gin|sageresinception|gcn] [steps=30] [workload=S-papers] [fused] [max] [norm] [--amp bf16] [--heads H] [attn=P]
 norm: GCN built with normalize=True (gcn_norm's coefficients and the self term; the reference model's setting is False).
 max: SAGE built with aggr="max" (csrc/aggregate_max.hip, layer by layer) instead of the mean's fused stack.
 fused: GIN / SAGEResInception / GCN built with fused_norm=True (the BatchNorm tail on csrc/bn_act.hip).
 --amp bf16: the forward and the loss under torch.autocast("cuda", dtype=torch.bfloat16), as a training loop would wrap them.
 attn=P: GAT(..., attn_dropout=P): PyG's dropout on the attention coefficients, inside the GAT kernels (spp.h f3t); default 0.
---heads H: GAT(..., heads=H) (default 1: the reference model): hidden layers of H heads of 256 // H, the last one averaged."""
+--heads H: GAT(..., heads=H) (default 1: the reference model): hidden layers of H heads of 256 // H, the last one averaged.
+gatv2: models.GATv2 (csrc/gatv2.hip), with --heads and attn= as GAT."""
 import contextlib
 import os
 import sys
@@ -55,10 +56,10 @@ cfg = FastSamplerConfig(
 it = DevicePrefetcher([dev], iter(FastSampler(2, 8, cfg)))
 batch = next(it)[0]
 torch.cuda.synchronize()
-if heads != 1 and arch != "gat":
-    sys.exit("--heads: GAT only")
-if attn and arch != "gat":
-    sys.exit("attn=: GAT only")
+if heads != 1 and arch not in ("gat", "gatv2"):
+    sys.exit("--heads: GAT and GATv2 only")
+if attn and arch not in ("gat", "gatv2"):
+    sys.exit("attn=: GAT and GATv2 only")
 if fused and arch not in ("gin", "sageresinception", "gcn"):
     sys.exit("fused: GIN, SAGEResInception and GCN only")
 if norm and arch != "gcn":
@@ -75,7 +76,7 @@ if fused:
 if norm:
     kw["normalize"] = True
 model = (GCN if arch == "gcn" else get_model_type(arch))(wl.x.size(1), 256, 47, 3, **kw).to(dev)
-if arch == "gat":
+if arch in ("gat", "gatv2"):
     assert [c.heads for c in model.convs] == [heads] * 3, "the model was not built with --heads"
 opt = torch.optim.Adam(model.parameters(), lr=1e-3, fused=True)    # one multi-tensor launch per step
 
