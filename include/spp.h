@@ -1830,6 +1830,88 @@ typedef struct spp_gatv2_desc {
 spp_status spp_gatv2_forward(const spp_gatv2_desc* desc, void* stream);
 spp_status spp_gatv2_backward(const spp_gatv2_desc* desc, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * f3w  GATv2Conv attention over rows of the RESIDENT graph (exact, layer-wise GATv2 inference), on rows the caller has
+ *      projected.  Forward only.
+ *
+ *        rowptr, col   the graph's CSR, int64, global node ids (as spp_graph_agg_forward)
+ *        x_l, x_r      [x_rows, D] each, D = heads * C, head h in columns h*C .. (h+1)*C; fp32 / fp16 / bf16, one code
+ *                      for both, each with its own row stride; BOTH indexed by global node id.  x_r may be the very
+ *                      pointer of x_l (share_weights); neither is assumed.
+ *        att           fp32 [heads, C], dense
+ *        targets       a slab or a list, exactly as spp_graph_gat_desc
+ *
+ *      For target t and head h (GATv2Conv's convention here, as spp_gatv2_forward states it): the entries are
+ *      col[rowptr[t] .. rowptr[t+1]) with every entry j == t skipped, plus one self loop j = t whose message is x_l[t];
+ *        e_j = sum_c att[h,c] * leaky_relu(x_l[j,h,c] + x_r[t,h,c], negative_slope),  alpha = softmax_j(e),
+ *        out[i,h,:] = sum_j alpha_j x_l[j,h,:],  then max(., 0) if relu != 0;  out_elem fp32 / bf16, a bf16 output is
+ *      rounded once, to nearest even.  A node without neighbours gets x_l[t].  Logits and softmax state are fp32.
+ *      Shapes, as the training pair: heads in {1, 2, 4, 8}; C % 4 == 0 with C / 4 a power of two; D <= 1024; the rows
+ *      of x_l and x_r aligned to 4 elements (base and stride), att to 16 bytes, the output to 4 elements.
+ *
+ *   Softmax contract, C_g = spp_graph_gatv2_chunk() (a compile-time constant, >= 32).  A state is PER HEAD (m, s, acc):
+ *   the maximum logit so far, the denominator and the weighted sum of the head's C columns of x_l, both at that maximum.
+ *   Taking an entry with logit e and row v:  if e > m: r = expf(m - e), acc *= r, s *= r, m = e;  then w = expf(e - m),
+ *   s += w, acc += w * v.  The result of a state is acc * (1 / s).  expf is the library function, as in
+ *   spp_gatv2_forward and for the reason f3v records -- not the __expf of f3h.
+ *     a row of at most C_g raw entries (skipped ones count): ONE state, begun as the self loop's (m = e_tt, s = 1,
+ *       acc = x_l[t]), takes the row's entries in CSR order;
+ *     a longer row is cut into consecutive chunks of C_g raw positions (the last may be shorter).  Chunk 0 begins as
+ *       the self loop's state, every other chunk as the empty state (m = -inf, s = 0, acc = 0); each takes its entries
+ *       in CSR order.  The running state is chunk 0's, and chunks 1, 2, ... are merged into it in chunk order:
+ *         m' = max(m1, m2), f1 = expf(m1 - m'), f2 = expf(m2 - m'), s' = fma(s2, f2, s1 * f1),
+ *         acc' = fma(f2, acc2, acc1 * f1);
+ *     a chunk whose entries are all skipped stays the empty state; merging it changes nothing (f2 = 0, f1 = 1) and
+ *       produces no NaN: the running state is always finite, because it begins with the self loop;
+ *     the dot product of a logit is added in an order fixed by (heads, C) -- a lane's four products per 4-column piece,
+ *       its pieces of the head, then an xor butterfly over the head's lanes, widest step first -- the same for every
+ *       entry, whatever the row's length, its chunk, its lane group, the grid, the slab or the list order;
+ *     the result of a row depends on nothing else -- not the grid, the slab, the order of a list or the other rows of
+ *       the call -- and no atomic touches the output.  The only atomic is the counter of the long-row list in the
+ *       workspace, which the entry zeroes.
+ *   For a call whose rows all have at most C_g raw entries, fp32 output and relu == 0, the output is BIT-IDENTICAL to
+ *   spp_gatv2_forward's out on the same rows with the hop the whole graph (T = S = x_rows): both run one body
+ *   (csrc/gatv2_core.hip.h), written with contraction off and every fused multiply-add spelled fmaf.
+ *
+ *   Ids that leave the graph: a col entry outside [0, x_rows) is node 0 in every respect (its row of x_l and the
+ *   comparison with t); a target id outside [0, x_rows) gives an output row of zeros.  Neither faults.  Every offset is
+ *   64-bit.  Workspace: spp_graph_gatv2_workspace_bytes(num_targets) bytes, 16-byte aligned, the caller's; its contents
+ *   mean nothing between calls.  The entry enqueues a 16-byte memset and two launches on `stream` and never waits for
+ *   the device.
+ *   Refused with SPP_ERR_INVALID before anything is enqueued: a NULL descriptor; heads outside {1, 2, 4, 8}; C <= 0 or
+ *   C % 4 != 0; C / 4 not a power of two; D > 1024; an unknown or fp8 element code; both target forms or neither; a slab
+ *   outside the graph; an output stride smaller than the row; a missing, misaligned or too small workspace; -- here
+ *   num_targets == 0 returns SPP_OK -- a NULL buffer; a row stride smaller than the row; rows of x_l / x_r or an output
+ *   not aligned to 4 elements (base and stride); att not aligned to 16 bytes.  SPP_ABI_VERSION stays 6.
+ * ------------------------------------------------------------------------- */
+typedef struct spp_graph_gatv2_desc {
+  int32_t x_elem;           /* x_l and x_r: SPP_ELEM_F32 / _F16 / _BF16 */
+  int32_t out_elem;         /* SPP_ELEM_F32 / SPP_ELEM_BF16 */
+  int32_t heads;            /* 1, 2, 4 or 8 */
+  int32_t relu;             /* != 0: out = max(out, 0) */
+  const int64_t* rowptr_dev;
+  const int64_t* col_dev;
+  const void* x_l_dev;      /* [x_rows, D] */
+  int64_t x_l_stride_elems;
+  const void* x_r_dev;      /* [x_rows, D]; may be x_l_dev */
+  int64_t x_r_stride_elems;
+  int64_t x_rows;           /* the graph's nodes = the rows of x_l and x_r */
+  int64_t C;                /* channels per head; D = heads * C */
+  const float* att_dev;     /* fp32 [heads, C] */
+  int64_t target_row0;      /* slab: the first target; < 0 with a list */
+  const int64_t* target_ids_dev; /* list: the targets; NULL with a slab */
+  int64_t num_targets;
+  void* out_dev;            /* [num_targets, D] */
+  int64_t out_stride_elems; /* 0 = dense */
+  float negative_slope;
+  int32_t reserved;
+} spp_graph_gatv2_desc;
+
+int64_t spp_graph_gatv2_chunk(void);
+int64_t spp_graph_gatv2_workspace_bytes(int64_t num_targets);
+spp_status spp_graph_gatv2_forward(const spp_graph_gatv2_desc* desc, void* workspace_dev, int64_t workspace_bytes,
+                                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

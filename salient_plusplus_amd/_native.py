@@ -178,6 +178,15 @@ class GraphGatDesc(C.Structure):
                 ("out_stride_elems", i64), ("negative_slope", C.c_float), ("reserved", i32)]
 
 
+class GraphGatv2Desc(C.Structure):
+    """spp_graph_gatv2_desc: projected rows x_l and x_r [x_rows, heads * C] by global id and att; targets as in
+    GraphAggDesc"""
+    _fields_ = [("x_elem", i32), ("out_elem", i32), ("heads", i32), ("relu", i32), ("rowptr_dev", p), ("col_dev", p),
+                ("x_l_dev", p), ("x_l_stride_elems", i64), ("x_r_dev", p), ("x_r_stride_elems", i64), ("x_rows", i64),
+                ("C", i64), ("att_dev", p), ("target_row0", i64), ("target_ids_dev", p), ("num_targets", i64),
+                ("out_dev", p), ("out_stride_elems", i64), ("negative_slope", C.c_float), ("reserved", i32)]
+
+
 class GraphGatPartsDesc(C.Structure):
     """spp_graph_gat_parts_desc: GraphGatDesc with h and its logits as num_parts row ranges (part_offsets, one h base and
     one [a_src | a_dst] base each)"""
@@ -386,6 +395,9 @@ SIGNATURES = {
     "spp_gcn_dinv": (C.c_int, [C.POINTER(GcnDinvDesc), p]),
     "spp_gatv2_forward": (C.c_int, [C.POINTER(Gatv2Desc), p]),
     "spp_gatv2_backward": (C.c_int, [C.POINTER(Gatv2Desc), p]),
+    "spp_graph_gatv2_chunk": (i64, []),
+    "spp_graph_gatv2_workspace_bytes": (i64, [i64]),
+    "spp_graph_gatv2_forward": (C.c_int, [C.POINTER(GraphGatv2Desc), p, i64, p]),
 }
 SPP_COMM_ID_BYTES = 128
 SPP_IPC_HANDLE_BYTES = 64

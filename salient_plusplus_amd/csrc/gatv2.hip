@@ -11,28 +11,17 @@
 // wave-wide segments for grad_xl; element I/O and the entry checks of elem_io.hip.h.
 // Built for C / 4 a power of two (the per-head reduction is an xor butterfly over aligned lane segments); with H in
 // {1, 2, 4, 8} D = H * C is then a power of two as well, 4 <= D <= 1024.
-#include "elem_io.hip.h"
-
-#include <algorithm>
-#include <type_traits>
+#include "gatv2_core.hip.h"
 
 namespace spp {
 
+using namespace gatv2;
+
 constexpr int kV2NT = 256;
 
-__device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
-__device__ __forceinline__ float dot_lrelu(const f4& a, const f4& x, const f4& r, float slope) {
-  return a.x * lrelu(x.x + r.x, slope) + a.y * lrelu(x.y + r.y, slope) + a.z * lrelu(x.z + r.z, slope) +
-         a.w * lrelu(x.w + r.w, slope);
-}
-
-// Forward.  4 columns per lane: piece p = q * lpr + lane holds columns 4p .. 4p + 3, q < NQ chunks of lpr = min(64, D / 4)
-// lanes.  A head is G = C / 4 consecutive pieces: G <= lpr lanes of one chunk (CPH = 1: a lane sees NQ heads, one per
-// chunk) or CPH = G / lpr whole chunks (a lane sees NQ / CPH heads).  A lane's partial dot of a head is the sum over its
-// CPH chunks, four products each; the partials are added by an xor butterfly over the min(G, lpr) lanes of the head's
-// segment, so every lane of the segment holds the logit and runs the head's online softmax for its own columns.
-// NB neighbours per round: ids, then rows, then partial dots, then ONE butterfly whose steps carry all NB * HL values
-// (one dependent reduction per edge was the slow version).  No atomics: the same bits in every run.
+// Forward.  The lane mapping, the logit, the online softmax and the walk over a row are gatv2_core.hip.h's (shared with
+// the long-row kernels of graph_gatv2.hip): lpr lanes per target, 4 columns per lane and chunk, NB neighbours in flight,
+// one butterfly per round.  The targets are the first T rows of x_l.  No atomics: the same bits in every run.
 template <typename Tin, int NQ, int CPH>
 __global__ __launch_bounds__(kV2NT) void k_gatv2_fwd(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,
                                                      int64_t T, const Tin* xl, int64_t xl_stride, const Tin* xr,
@@ -40,91 +29,24 @@ __global__ __launch_bounds__(kV2NT) void k_gatv2_fwd(const int64_t* __restrict__
                                                      int lpr_log2, int seg_log2, int g_log2, int H,
                                                      float* __restrict__ out, float* __restrict__ row_max,
                                                      float* __restrict__ row_sum) {
-  constexpr int HL = NQ / CPH;           // heads a lane takes part in
-  constexpr int NB = NQ <= 2 ? 4 : 2;    // neighbours in flight (NQ = 4: 16 columns per lane and neighbour)
-  const int lpr = 1 << lpr_log2;
-  const int lane = threadIdx.x & (lpr - 1);
+  Lane<NQ, CPH> L;
+  L.slope = slope, L.lpr = 1 << lpr_log2, L.lane = threadIdx.x & (L.lpr - 1), L.seg_log2 = seg_log2;
   const int64_t t = ((int64_t)blockIdx.x * kV2NT + threadIdx.x) >> lpr_log2;
   if (t >= T) return;  // whole groups leave together (the shuffles below stay inside a group)
-  const int64_t D = (int64_t)NQ * lpr * 4;
-  const int64_t b = rowptr[t], e = rowptr[t + 1];
-  f4 av[NQ], rv[NQ], acc[NQ];
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) {
-    const int64_t c = ((int64_t)q * lpr + lane) * 4;
-    av[q] = load4(att + c);
-    rv[q] = load4(xr + t * xr_stride + c);
-    acc[q] = load4(xl + t * xl_stride + c);  // the self loop's message: source row t
-  }
-  float mm[HL], ss[HL];
-#pragma unroll
-  for (int hl = 0; hl < HL; ++hl) {
-    float pd = 0.f;
-#pragma unroll
-    for (int q = hl * CPH; q < (hl + 1) * CPH; ++q) pd += dot_lrelu(av[q], acc[q], rv[q], slope);
-    mm[hl] = pd;
-    ss[hl] = 1.f;
-  }
-  for (int d = (1 << seg_log2) >> 1; d >= 1; d >>= 1)
-#pragma unroll
-    for (int hl = 0; hl < HL; ++hl) mm[hl] += __shfl_xor(mm[hl], d, kWave);
-  for (int64_t k0 = b; k0 < e; k0 += NB) {
-    int64_t j[NB];
-#pragma unroll
-    for (int u = 0; u < NB; ++u) j[u] = col[k0 + u < e ? k0 + u : e - 1];  // clamped, unpredicated
-    f4 xv[NB][NQ];
-#pragma unroll
-    for (int u = 0; u < NB; ++u)
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) xv[u][q] = load4(xl + j[u] * xl_stride + ((int64_t)q * lpr + lane) * 4);
-    float pd[NB][HL];
-#pragma unroll
-    for (int u = 0; u < NB; ++u)
-#pragma unroll
-      for (int hl = 0; hl < HL; ++hl) {
-        pd[u][hl] = 0.f;
-#pragma unroll
-        for (int q = hl * CPH; q < (hl + 1) * CPH; ++q) pd[u][hl] += dot_lrelu(av[q], xv[u][q], rv[q], slope);
-      }
-    for (int d = (1 << seg_log2) >> 1; d >= 1; d >>= 1)
-#pragma unroll
-      for (int u = 0; u < NB; ++u)
-#pragma unroll
-        for (int hl = 0; hl < HL; ++hl) pd[u][hl] += __shfl_xor(pd[u][hl], d, kWave);
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-      if (k0 + u >= e || j[u] == t) continue;  // set_diag drops existing diagonal entries
-#pragma unroll
-      for (int hl = 0; hl < HL; ++hl) {
-        const float sc = pd[u][hl];
-        if (sc > mm[hl]) {
-          const float r = expf(mm[hl] - sc);
-#pragma unroll
-          for (int q = hl * CPH; q < (hl + 1) * CPH; ++q) {
-            acc[q].x *= r; acc[q].y *= r; acc[q].z *= r; acc[q].w *= r;
-          }
-          ss[hl] *= r;
-          mm[hl] = sc;
-        }
-        const float w = expf(sc - mm[hl]);
-        ss[hl] += w;
-#pragma unroll
-        for (int q = hl * CPH; q < (hl + 1) * CPH; ++q) {
-          acc[q].x += w * xv[u][q].x; acc[q].y += w * xv[u][q].y; acc[q].z += w * xv[u][q].z; acc[q].w += w * xv[u][q].w;
-        }
-      }
-    }
-  }
+  const int64_t D = (int64_t)NQ * L.lpr * 4;
+  L.load(att, xr + t * xr_stride);
+  State<NQ, CPH> st;
+  self_state(st, L, xl + t * xl_stride);  // the self loop's message: source row t
+  walk(st, L, xl, xl_stride, col, rowptr[t], rowptr[t + 1], t, (int64_t)-1);
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
     const int hl = q / CPH;
-    const int p = q * lpr + lane;
-    const float inv = 1.f / ss[hl];
-    *reinterpret_cast<float4*>(out + t * D + (int64_t)p * 4) =
-        make_float4(acc[q].x * inv, acc[q].y * inv, acc[q].z * inv, acc[q].w * inv);
+    const int p = q * L.lpr + L.lane;
+    const f4 r = st.result(q);
+    *reinterpret_cast<float4*>(out + t * D + (int64_t)p * 4) = make_float4(r.x, r.y, r.z, r.w);
     if ((p & ((1 << g_log2) - 1)) == 0) {  // the head's first piece
-      row_max[t * H + (p >> g_log2)] = mm[hl];
-      row_sum[t * H + (p >> g_log2)] = ss[hl];
+      row_max[t * H + (p >> g_log2)] = st.mm[hl];
+      row_sum[t * H + (p >> g_log2)] = st.ss[hl];
     }
   }
 }
@@ -243,27 +165,8 @@ __global__ __launch_bounds__(kV2NT) void k_gatv2_bwd(const int64_t* __restrict__
 }  // namespace spp
 
 using namespace spp;
+using namespace spp::gatv2;
 
-static int log2_of(int64_t v) {
-  int l = 0;
-  while ((1ll << l) < v) ++l;
-  return l;
-}
-static bool pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
-
-template <int N> using IC = std::integral_constant<int, N>;
-// fn(IC<NQ>{}, IC<CPH>{}): the forward's chunks per lane and chunks per head
-template <class Fn>
-static void with_fwd_shape(int nq, int cph, Fn&& fn) {
-  switch (nq * 8 + cph) {
-    case 1 * 8 + 1: fn(IC<1>{}, IC<1>{}); break;
-    case 2 * 8 + 1: fn(IC<2>{}, IC<1>{}); break;
-    case 2 * 8 + 2: fn(IC<2>{}, IC<2>{}); break;
-    case 4 * 8 + 1: fn(IC<4>{}, IC<1>{}); break;
-    case 4 * 8 + 2: fn(IC<4>{}, IC<2>{}); break;
-    default: fn(IC<4>{}, IC<4>{}); break;
-  }
-}
 // fn(IC<NS>{}, IC<SPH>{}): the backward's steps per lane and steps per head (NS / SPH <= 8 heads)
 template <class Fn>
 static void with_bwd_shape(int ns, int sph, Fn&& fn) {
@@ -317,10 +220,9 @@ extern "C" spp_status spp_gatv2_forward(const spp_gatv2_desc* d, void* stream) {
   SPP_TRY(gatv2_check_shape(d, who));
   if (d->num_targets == 0) return SPP_OK;
   SPP_TRY(gatv2_check_rows(d, who));
-  const int64_t T = d->num_targets, G = d->C / 4, P = d->heads * G;
-  const int lpr_log2 = lanes_log2(P), lpr = 1 << lpr_log2;
-  const int nq = (int)(P / lpr), cph = (int)std::max<int64_t>(1, G / lpr);
-  const int seg_log2 = log2_of(std::min<int64_t>(G, lpr)), g_log2 = log2_of(G);
+  const int64_t T = d->num_targets;
+  const Shape sh = shape_of(d->heads, d->C);
+  const int lpr_log2 = sh.lpr_log2, seg_log2 = sh.seg_log2, g_log2 = sh.g_log2, nq = sh.nq, cph = sh.cph;
   const unsigned grid = (unsigned)ceil_div(T << lpr_log2, kV2NT);
   with_elem(d->x_elem, [&](auto tin) {
     with_fwd_shape(nq, cph, [&](auto q, auto c) {

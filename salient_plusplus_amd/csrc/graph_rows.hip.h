@@ -135,9 +135,12 @@ struct Launch {
 // lane: rows of x that do not allow it (with parts: the rows of any of them) are read one column per lane instead; an
 // output that does not is refused (the caller allocates it).  fp8_rows: the entry reads e4m3 rows in place (f3o, the
 // _fp8 entries of graph_aggregate.hip: x_elem is SPP_ELEM_FP8_E4M3, an element is a byte); everywhere else they are refused.
+// ws_fn, stride_name: the entry's own workspace function and row-stride field, as its messages name them.
 inline spp_status check_common(const char* who, const Common& d, int64_t out_width, int64_t vec_cols,
                                const void* const* x_bases, int n_bases, bool others, void* workspace_dev,
-                               int64_t workspace_bytes_given, Launch* l, bool fp8_rows = false) {
+                               int64_t workspace_bytes_given, Launch* l, bool fp8_rows = false,
+                               const char* ws_fn = "spp_graph_agg_ / spp_graph_gat_workspace_bytes",
+                               const char* stride_name = "x_stride_elems") {
   SPP_REQUIRE((fp8_rows || d.x_elem != SPP_ELEM_FP8_E4M3) && d.out_elem != SPP_ELEM_FP8_E4M3,
               "%s: fp8 rows are not read or written here (x_elem %d, out_elem %d; dequantise the table first)", who,
               (int)d.x_elem, (int)d.out_elem);
@@ -154,8 +157,8 @@ inline spp_status check_common(const char* who, const Common& d, int64_t out_wid
   const int64_t out_stride = d.out_stride > 0 ? d.out_stride : out_width;
   SPP_REQUIRE(out_stride >= out_width, "%s: output stride (out_stride_elems) smaller than the output row", who);
   SPP_REQUIRE(workspace_dev && aligned_to(workspace_dev, 16) && workspace_bytes_given >= workspace_bytes(T),
-              "%s: needs a 16-byte aligned workspace of %lld bytes (spp_graph_agg_ / spp_graph_gat_workspace_bytes(num_targets))",
-              who, (long long)workspace_bytes(T));
+              "%s: needs a 16-byte aligned workspace of %lld bytes (%s(num_targets))", who,
+              (long long)workspace_bytes(T), ws_fn);
   *l = Launch{};
   l->empty = T == 0 || F == 0;
   if (l->empty) return SPP_OK;
@@ -163,7 +166,7 @@ inline spp_status check_common(const char* who, const Common& d, int64_t out_wid
   for (int p = 0; p < n_bases; ++p)
     x_there = x_there && x_bases[p], x_aligned = x_aligned && aligned_to(x_bases[p], 4 * elem_bytes(d.x_elem));
   SPP_REQUIRE(d.rowptr && d.col && x_there && others && d.out && d.x_rows > 0, "%s: NULL buffer or empty graph", who);
-  SPP_REQUIRE(d.x_stride >= F, "%s: row stride (x_stride_elems) smaller than the row", who);
+  SPP_REQUIRE(d.x_stride >= F, "%s: row stride (%s) smaller than the row", who, stride_name);
   l->vec = vec_cols % 4 == 0 && d.x_stride % 4 == 0 && x_aligned;
   SPP_REQUIRE(!l->vec || (out_stride % 4 == 0 && aligned_to(d.out, 4 * elem_bytes(d.out_elem))),
               "%s: the vector form (4 columns a lane) needs out_dev aligned to 4 elements (base and stride)", who);

@@ -4,7 +4,9 @@ sampling, no dedup and no exchange.  The message passing is the HIP kernel pair 
 GIN and SAGEResInception and of csrc/graph_gat.hip for GAT; SAGEResInception's layer tail is csrc/resinc_epilogue.hip
 (``spp_resinc_epilogue``); GCN's weighted sums are the pair of csrc/graph_agg_weighted.hip (``graph_weighted_aggregate``,
 with ``gcn_dinv`` for the per-node factors of its normalisation; resident entries only).  The layers' own parameters run
-through the library GEMMs torch dispatches to.  Forward only, fp16 / fp32 / bf16 inputs.
+through the library GEMMs torch dispatches to.  Forward only, fp16 / fp32 / bf16 inputs.  GATv2 (f3w): the long-row
+pair of csrc/graph_gatv2.hip behind ``graph_gatv2_aggregate`` (``spp_graph_gatv2_forward``), the driver ``_gatv2_layers``
+and the entries ``gatv2_inference`` and ``evaluate``; resident only.
 
 The kernels' wrappers: ``graph_aggregate`` (``spp_graph_agg_forward``) and ``graph_gat_aggregate``
 (``spp_graph_gat_forward``) read one resident matrix, ``graph_aggregate_parts`` (``spp_graph_agg_parts_forward``) and
@@ -67,6 +69,16 @@ def graph_gat_chunk():
 
 def graph_gat_workspace_bytes(num_targets):
     return int(nat.load().spp_graph_gat_workspace_bytes(int(num_targets)))
+
+
+def graph_gatv2_chunk():
+    """C_g of GATv2's softmax contract (include/spp.h f3w): a row of at most C_g raw entries is one online softmax per
+    head in CSR order, a longer row is chunks of C_g whose per-head states are merged in chunk order"""
+    return int(nat.load().spp_graph_gatv2_chunk())
+
+
+def graph_gatv2_workspace_bytes(num_targets):
+    return int(nat.load().spp_graph_gatv2_workspace_bytes(int(num_targets)))
 
 
 class Fp8Table:
@@ -409,6 +421,17 @@ def _gat_launch(h, a_src, a_dst, rowptr, col, heads, negative_slope, relu, row0,
     return _launch(nat.load().spp_graph_gat_forward, d, workspace, out)
 
 
+def _gatv2_launch(x_l, x_r, att, rowptr, col, negative_slope, relu, row0, target_ids, T, out, workspace):
+    """spp_graph_gatv2_forward: x_l and x_r [N, H * C] by global id (x_r may be x_l), att contiguous fp32 [H, C]"""
+    N, D = x_l.shape
+    H, Cc = att.shape
+    d = nat.GraphGatv2Desc(x_elem=_ELEM[x_l.dtype], heads=H, relu=int(bool(relu)), x_l_dev=_p(x_l),
+                           x_l_stride_elems=x_l.stride(0) if N > 1 else D, x_r_dev=_p(x_r),
+                           x_r_stride_elems=x_r.stride(0) if N > 1 else D, x_rows=N, C=Cc, att_dev=_p(att),
+                           negative_slope=float(negative_slope), **_request(rowptr, col, row0, target_ids, T, out))
+    return _launch(nat.load().spp_graph_gatv2_forward, d, workspace, out)
+
+
 def _gat_parts_launch(src, a_src, off, rowptr, col, heads, negative_slope, relu, row0, target_ids, T, out, workspace):
     """spp_graph_gat_parts_forward: ``src`` as for ``_agg_parts_launch``, ``a_src`` the logits' (base addresses, row
     stride)"""
@@ -603,6 +626,76 @@ def graph_gat_aggregate(h, a_src, a_dst, rowptr, col, *, heads, negative_slope=0
                            [h, a_src, a_dst, rowptr, col, target_ids], workspace, graph_gat_workspace_bytes, T)
     out = torch.empty((T, Fdim), dtype=out_dtype, device=h.device)
     return _gat_launch(h, a_src, a_dst, rowptr, col, heads, negative_slope, relu, row0, target_ids, T, out, workspace)
+
+
+_GATV2_HEADS = (1, 2, 4, 8)                              # the head counts the GATv2 kernels are built for
+_GATV2_MAX_D = 1024                                      # ... and their widest row, heads * C
+
+
+def _gatv2_pad(Cc):
+    """the smallest Cp >= Cc with Cp % 4 == 0 and Cp / 4 a power of two: the channels per head the kernels take"""
+    g = 1
+    while 4 * g < Cc:
+        g *= 2
+    return 4 * g
+
+
+def _check_gatv2_rows(what, name, t):
+    if t.stride(0) % 4 != 0 or t.data_ptr() % (4 * t.element_size()) != 0:
+        raise ValueError(f"{what}: the rows of {name} must be aligned to 4 elements, base and stride (the kernels move "
+                         f"four columns per lane); got stride {t.stride(0)} elements, address % {4 * t.element_size()} = "
+                         f"{t.data_ptr() % (4 * t.element_size())}")
+
+
+def graph_gatv2_aggregate(x_l, x_r, att, rowptr, col, *, negative_slope=0.2, relu=False, row0=None, num_targets=None,
+                          target_ids=None, out_dtype=torch.float32, out=None, workspace=None):
+    """GATv2Conv's attention over whole rows of the resident graph (``spp_graph_gatv2_forward``, include/spp.h f3w).
+
+    ``x_l`` / ``x_r`` [N, H * C]: the PROJECTED rows lin_l(x) and lin_r(x), one per graph node and both indexed by
+    global node id (fp16 / fp32 / bf16, one dtype, possibly strided views with rows aligned to 4 elements); ``x_r`` may
+    be ``x_l`` itself (share_weights).  ``att``: contiguous fp32 [H, C].  ``rowptr`` / ``col``: the graph's CSR (int64,
+    global ids).  The targets are a slab, ``row0`` and ``num_targets``, or a list, ``target_ids`` (int64, any order,
+    duplicates allowed).  Output row i, head h: the softmax over node t's row without its diagonal entries plus one self
+    loop, of e_j = att[h] . leaky_relu(x_l[j, h] + x_r[t, h]), applied to the rows x_l[j, h*C:(h+1)*C]; through a ReLU
+    with ``relu=True``.  fp32 state; a bf16 output is rounded once.  A ``col`` entry outside the graph is node 0, a
+    target id outside it gives a row of zeros.  The kernels are built for H in {1, 2, 4, 8}, C % 4 == 0 with C / 4 a
+    power of two and H * C <= 1024; any other shape is a ``ValueError`` (``gatv2_inference`` pads C itself).
+
+    Forward only: no autograd node is registered and an input that requires grad is refused.  ``out``: where the rows
+    go ([T, H * C] of ``out_dtype``, rows aligned to 4 elements; allocated when None).  ``workspace``: a uint8 CUDA
+    tensor of at least ``graph_gatv2_workspace_bytes(T)`` bytes, reusable between calls on one stream; allocated when
+    None.  Nothing here waits for the device."""
+    what = "graph_gatv2_aggregate"
+    _check_matrix(x_l, what, name="x_l")
+    _check_matrix(x_r, what, name="x_r")
+    N, D = x_l.shape
+    if tuple(x_r.shape) != (N, D) or x_r.dtype != x_l.dtype:
+        raise ValueError(f"{what}: x_r must have x_l's shape and dtype ({[N, D]} {x_l.dtype}: both are indexed by global "
+                         f"node id), got {list(x_r.shape)} {x_r.dtype}")
+    _check_graph(what, N, rowptr, col)
+    if not isinstance(att, torch.Tensor) or att.dim() != 2:
+        raise ValueError(f"{what}: att must be a contiguous fp32 tensor of shape [heads, C]")
+    H, Cc = att.shape
+    _check_fp32(what, "att", att, (H, Cc), "heads, channels per head")
+    if H not in _GATV2_HEADS:
+        raise ValueError(f"{what}: heads must be 1, 2, 4 or 8 (the kernels' head counts), got att of {H} rows")
+    if Cc < 4 or _gatv2_pad(Cc) != Cc:
+        raise ValueError(f"{what}: C must be a multiple of 4 with C / 4 a power of two (the per-head reduction is a "
+                         f"butterfly over aligned lane segments), got C = {Cc}; zero-pad the channels to {_gatv2_pad(Cc)}")
+    if H * Cc != D or D > _GATV2_MAX_D:
+        raise ValueError(f"{what}: the rows must be heads * C = {H} * {Cc} = {H * Cc} <= {_GATV2_MAX_D} wide, got {D}")
+    _check_gatv2_rows(what, "x_l", x_l)
+    _check_gatv2_rows(what, "x_r", x_r)
+    _check_out_dtype(what, out_dtype)
+    row0, target_ids, T = _check_targets(what, N, row0, num_targets, target_ids)
+    _check_out(what, out, out_dtype, T, D)
+    if out is not None:
+        _check_gatv2_rows(what, "out", out)
+    workspace = _on_device(what, "x_l, x_r, att, rowptr, col, target_ids, out and workspace", x_l.device,
+                           [x_l, x_r, att, rowptr, col, target_ids, out], workspace, graph_gatv2_workspace_bytes, T)
+    if out is None:
+        out = torch.empty((T, D), dtype=out_dtype, device=x_l.device)
+    return _gatv2_launch(x_l, x_r, att, rowptr, col, negative_slope, relu, row0, target_ids, T, out, workspace)
 
 
 def graph_gat_aggregate_parts(h_parts, a_parts, part_offsets, rowptr, col, *, heads, negative_slope=0.2, relu=False,
@@ -1167,6 +1260,7 @@ def _gat_layers(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None):
         for r, n, tile in _row_tiles(cur):
             h[r:r + n] = (tile.to(act_dtype) @ Wt)[:n]
             place.put_logits(logits, r, n, tile.to(torch.float32) @ Vt)
+        tile = None                                      # (a full tile is a VIEW of cur)
         del cur                                          # (layer i-1's matrix; layer 1's is the caller's table)
         place.boundary()                                 # every rank's h and logits of this layer are complete
         step = plan[i]
@@ -1181,9 +1275,87 @@ def _gat_layers(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None):
             place.attend(h, logits, conv, not last, s, tids, T, out, ws, step.graph)
             if last:                                     # concat=False: the mean of the heads (H = 1: the head itself)
                 sink.put(s, T, out.view(T, H, Cc).mean(1) if H > 1 else out, names[s:s + T] if names is not None else None)
-        cur = nxt
+            out = None                                   # (a hidden layer's slab is a VIEW of nxt)
+        cur, nxt = nxt, None                             # ONE name holds the matrix: ``del cur`` above must free it
         del h, logits                                    # (resident: drops them)
         place.boundary()                                 # every rank has finished reading this layer's h
+    return sink.result()
+
+
+def _gatv2_layers(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None):
+    """GATv2 over one resident matrix (f3w), project-first as ``GATv2Conv.forward``.  Per layer:
+
+      project    x_l = cur @ W_l^T and x_r = cur @ W_r^T for all rows, [n, H*Cp] each in ``act_dtype``, over
+                 ``_row_tiles``; with ``share_weights`` x_r IS x_l and no second GEMM runs
+      aggregate  ``spp_graph_gatv2_forward`` slab by slab over each node's whole row; hidden layers through the fused
+                 ReLU straight into the next [n, hidden] matrix, the last layer ([T, H*Cp] fp32 per slab) through the
+                 mean over its heads into ``sink``
+
+    Channel padding: the kernels take C % 4 == 0 with C / 4 a power of two, and a last layer has C = classes (47, 172).
+    Cp is the next such width (48 -> 64, 172 -> 256): W_l / W_r get Cp - C zero rows per head and att Cp - C zero
+    columns, and the padded output columns are sliced away before the mean.  The padding is exact: a padded channel
+    has x_l = x_r = 0, so its term of every logit is att * lrelu(0 + 0) = 0 * 0 = +0, added to a dot product -- and its
+    position in the butterfly is fixed by (H, Cp), the same for every entry.
+
+    Memory, as arithmetic: ``cur`` is dropped once x_l and x_r are complete (no other name or view holds it), so at the
+    worst moment THREE [N, hidden] matrices of ``act_dtype`` are live (cur, x_l, x_r while projecting, with two GEMM tiles
+    of 65 536 rows on top; then x_l, x_r and nxt): at N = 111 M and hidden 256, 57 GB each in bf16, next to 26 GB
+    of graph and 28 GB of features: 3 * 57 + 26 + 28 = 225 GB of one 288 GB MI355X.  With ``share_weights`` two are live
+    (2 * 57 + 26 + 28 = 168 GB, as SAGE).  The one case worse: the last layer's x_l and x_r are [N, H * Cp] -- for H = 4
+    and 172 classes (Cp = 256) 111 M * 4 * 256 * 2 bytes = 227 GB EACH in bf16, which does not fit next to anything;
+    H = 1 is 57 GB each (2 * 57 + 57 of ``cur`` + 26 + 28 = 225 GB; 168 GB shared).  A multi-head model of many classes
+    at that scale needs ``share_weights`` and fewer heads, or several devices (not built for GATv2)."""
+    n_layers, dev = len(model.convs), place.dev
+    plan = plan or _whole_graph_plan(place, nodes, n_layers)     # (one ``_Step`` a layer, as in ``_conv_layers``)
+    ws = torch.empty(graph_gatv2_workspace_bytes(min(rows_per_slab, max([place.n_local] + [st.rows for st in plan]))),
+                     dtype=torch.uint8, device=dev)
+    cur = place.x
+    for i, conv in enumerate(model.convs):
+        last = i == n_layers - 1
+        H, Cc = conv.heads, conv.out_channels
+        Cp = _gatv2_pad(Cc)
+
+        def padded_t(W):                                 # [H*C, K] -> [K, H*Cp] in act_dtype, zero rows behind each head's C
+            if Cp != Cc:
+                Wp = W.new_zeros((H, Cp, W.size(1)))
+                Wp[:, :Cc] = W.view(H, Cc, -1)
+                W = Wp.view(H * Cp, -1)
+            return W.to(act_dtype).t()
+        shared = conv.lin_r is conv.lin_l
+        Wl, Wr = padded_t(conv.lin_l.weight), None if shared else padded_t(conv.lin_r.weight)
+        att = torch.zeros((H, Cp), dtype=torch.float32, device=dev)
+        att[:, :Cc] = conv.att.view(H, Cc)
+        x_l = torch.empty((cur.size(0), H * Cp), dtype=act_dtype, device=dev)
+        x_r = x_l if shared else torch.empty_like(x_l)
+        for r, n, tile in _row_tiles(cur):
+            tile = tile.to(act_dtype)
+            x_l[r:r + n] = (tile @ Wl)[:n]
+            if not shared:
+                x_r[r:r + n] = (tile @ Wr)[:n]
+        tile = None                                      # (a full tile is a VIEW of cur)
+        del cur                                          # (layer i-1's matrix; layer 1's is the caller's table)
+        step = plan[i]
+        rows, names = step.rows, step.names
+        rowptr, col = step.graph or (place.rowptr, place.col)
+        if last:
+            nxt = None
+            sink.open(place, rows, Cc)
+        else:
+            nxt = torch.empty((rows, H * Cc), dtype=act_dtype, device=dev)
+        for s, T, tids in _slabs(rows, step.ids, rows_per_slab):
+            direct = not last and Cp == Cc               # the rows go straight into the next activation matrix
+            out = nxt[s:s + T] if direct else torch.empty((T, H * Cp), dtype=act_dtype if not last else torch.float32,
+                                                          device=dev)
+            _gatv2_launch(x_l, x_r, att, rowptr, col, conv.negative_slope, not last, -1 if tids is not None else s, tids,
+                          T, out, ws)
+            if last:                                     # concat=False: the mean of the heads (H = 1: the head itself)
+                z = out.view(T, H, Cp)[:, :, :Cc]
+                sink.put(s, T, z.mean(1) if H > 1 else z.reshape(T, Cc), names[s:s + T] if names is not None else None)
+            elif not direct:
+                nxt[s:s + T] = out.view(T, H, Cp)[:, :, :Cc].reshape(T, H * Cc)
+            out = None                                   # (a hidden layer's slab is a VIEW of nxt)
+        cur, nxt = nxt, None                             # ONE name holds the matrix: ``del cur`` above must free it
+        del x_l, x_r
     return sink.result()
 
 
@@ -1340,12 +1512,38 @@ def _gcn_layers(model, place, nodes, rows_per_slab, act_dtype, sink):
     return sink.result()
 
 
-def _check_model(model, what, names, gcn=False):
-    """one of the four models -- or, for the resident whole-graph entries (``gcn``), GCN -- with what the GAT and
-    SAGEResInception drivers need of its layers (SAGE, GIN and GCN: nothing)"""
-    from .models import GAT, GCN, GIN, SAGE, SAGEResInception
+_GATV2_ENTRIES = ("a GATv2 model is scored over one resident fp16 / fp32 / bf16 matrix by inference.gatv2_inference "
+                  "(log-probabilities) and inference.evaluate (predictions, accuracy, loss); layerwise_inference, an "
+                  "Fp8Table input, the field entries and the partitioned entries are not built for GATv2")
+
+
+def _check_gatv2(model, what):
+    """the layers as ``models.GATv2`` builds them, in shapes ``_gatv2_layers`` can put on the kernels"""
+    for i, c in enumerate(model.convs):
+        last = i == len(model.convs) - 1
+        if c.bias is not None or c.lin_l.bias is not None or c.lin_r.bias is not None or c.concat == last:
+            raise NotImplementedError(f"{what}: GATv2 layers need bias=False, and concat=False on the last layer only "
+                                      "(as models.GATv2 builds them)")
+        H, Cc, Cp = c.heads, c.out_channels, _gatv2_pad(c.out_channels)
+        if H not in _GATV2_HEADS:
+            raise NotImplementedError(f"{what}: layer {i} has heads = {H}; the GATv2 kernels are built for heads in "
+                                      f"{{1, 2, 4, 8}} (heads * C = {H} * {Cc} is not the limit that was hit)")
+        if H * Cp > _GATV2_MAX_D:
+            raise NotImplementedError(f"{what}: layer {i} needs rows of heads * Cp = {H} * {Cp} = {H * Cp} columns "
+                                      f"(C = {Cc} padded to Cp = {Cp}, the next multiple of 4 with Cp / 4 a power of "
+                                      f"two), above the kernels' {_GATV2_MAX_D} (heads = {H} is not the limit that was hit)")
+
+
+def _check_model(model, what, names, gcn=False, gatv2=False):
+    """one of the four models -- or, for the resident whole-graph entries, GCN (``gcn``) or GATv2 (``gatv2``) -- with
+    what the GAT, GATv2 and SAGEResInception drivers need of its layers (SAGE, GIN and GCN: nothing)"""
+    from .models import GAT, GATv2, GCN, GIN, SAGE, SAGEResInception
     if gcn and isinstance(model, GCN):
         return
+    if isinstance(model, GATv2):
+        if not gatv2:
+            raise NotImplementedError(f"{what}: not built for GATv2: {_GATV2_ENTRIES}")
+        return _check_gatv2(model, what)
     if not isinstance(model, (SAGE, GIN, GAT, SAGEResInception)):
         raise NotImplementedError(f"{what}: implemented for {names}, not {type(model).__name__}")
     if isinstance(model, SAGEResInception):
@@ -1373,9 +1571,9 @@ def _check_run(what, act_dtype, rows_per_slab, nodes):
 def _score(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None):
     """the frame of every driver: eval mode (restored), no gradient, autocast off, the table's device current; a rank
     that fails aborts the placement, so that its peers raise instead of waiting, and every mapping is closed"""
-    from .models import GAT, GCN, SAGEResInception
+    from .models import GAT, GATv2, GCN, SAGEResInception
     layers = _gat_layers if isinstance(model, GAT) else _resinc_layers if isinstance(model, SAGEResInception) \
-        else _gcn_layers if isinstance(model, GCN) else _conv_layers
+        else _gcn_layers if isinstance(model, GCN) else _gatv2_layers if isinstance(model, GATv2) else _conv_layers
     was_training = model.training
     model.eval()
     try:
@@ -1434,10 +1632,11 @@ def _check_labels(what, name, y, rows):
                          f"{tuple(y.shape)} {y.dtype}")
 
 
-def _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, y, sink, edge_weight=None):
-    """the resident entries: every argument check, then the device, then the pass into ``sink``"""
-    from .models import GCN
-    _check_model(model, what, "SAGE and GIN (and GAT, SAGEResInception, GCN)", gcn=True)
+def _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, y, sink, edge_weight=None, gatv2=False):
+    """the resident entries: every argument check, then the device, then the pass into ``sink``.  ``gatv2``: the entry
+    admits a GATv2 model (``gatv2_inference``, ``evaluate``)"""
+    from .models import GATv2, GCN
+    _check_model(model, what, "SAGE and GIN (and GAT, SAGEResInception, GCN)", gcn=True, gatv2=gatv2)
     gcn = isinstance(model, GCN)
     if edge_weight is not None and not gcn:
         raise ValueError(f"{what}: edge_weight is GCN's (the values its adj_t carries in training); "
@@ -1446,6 +1645,8 @@ def _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, y, s
         if isinstance(x, (list, tuple, P2PPeers)):
             raise NotImplementedError(f"{what}: GCN over a row-partitioned x ({type(x).__name__}); {_WEIGHTS_NOT_BUILT}")
         _check_matrix(x, what, fp8_reason=f"GCN: {_WEIGHTS_NOT_BUILT}")
+    elif isinstance(model, GATv2):
+        _check_matrix(x, what, fp8_reason=f"GATv2: {_GATV2_ENTRIES}")
     else:
         _check_table(x, what)
     N = x.size(0)
@@ -1502,11 +1703,32 @@ def evaluate(model, x, rowptr, col, y=None, *, nodes=None, splits=None, rows_per
     of the lists once (``pred`` and ``nll`` follow it) and also returns labelled / correct / loss per name.  A node's
     ``pred`` and ``nll`` are the same bits whatever ``rows_per_slab`` is and whether ``nodes`` selected it; ``pred[i]`` is
     the argmax of the logits, so ``layerwise_inference``'s row attains its maximum there.  The counts are reduced on the
-    device and read back once, at the end.  ``edge_weight``: GCN's entry weights, as ``layerwise_inference`` takes them."""
+    device and read back once, at the end.  ``edge_weight``: GCN's entry weights, as ``layerwise_inference`` takes them.
+    A ``GATv2`` model is accepted too (one resident matrix, no ``Fp8Table``): ``gatv2_inference``'s pass, this tail."""
     what = "evaluate"
     nodes, segments = _check_splits(what, splits, nodes)
-    sink = _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, y, _Classify(y), edge_weight)
+    sink = _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, y, _Classify(y), edge_weight,
+                     gatv2=True)
     return _evaluation(sink, y, None if nodes is None else nodes.to(x.device), segments)
+
+
+def gatv2_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 << 20, act_dtype=torch.float32):
+    """Exact log-probabilities of every node, [N, classes] fp32 -- or of ``nodes`` (int64, any order, duplicates
+    allowed), [len(nodes), classes] -- for a ``models.GATv2`` model over the whole graph: ``layerwise_inference``'s
+    contract (arguments, fixed GEMM tiles, eval mode restored, no gradient, nothing waits for the device but the range
+    check of ``nodes``) with GATv2's own layer loop, ``_gatv2_layers``: both projections as torch GEMMs, then
+    ``spp_graph_gatv2_forward`` (csrc/graph_gatv2.hip) over each node's whole neighbour row.  A node's result is the same
+    bits whatever ``rows_per_slab`` is and whether ``nodes`` selected it.  ``x``: one resident CUDA fp16 / fp32 / bf16
+    matrix, one row per node.  Heads in {1, 2, 4, 8}; any number of channels per head and classes with heads * Cp <= 1024
+    (Cp: the channels padded as ``_gatv2_layers`` describes, where its memory arithmetic is too).  ``evaluate`` runs the
+    same pass into predictions and losses.  (``layerwise_inference`` itself keeps refusing the model; see DESIGN
+    section 8.)"""
+    from .models import GATv2
+    what = "gatv2_inference"
+    if not isinstance(model, GATv2):
+        raise NotImplementedError(f"{what}: implemented for GATv2, not {type(model).__name__} (the other models: "
+                                  "layerwise_inference)")
+    return _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, None, _LogProbs(), gatv2=True)
 
 
 # ---- f3n: a few nodes scored exactly over their receptive field only -------------------------------------------------

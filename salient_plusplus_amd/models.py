@@ -1354,10 +1354,10 @@ class GATv2(torch.nn.Module):
         return torch.log_softmax(x, dim=-1)
 
     def inference(self, x_all, rowptr, col, **kw):
-        raise NotImplementedError("GATv2.inference: not a method of the model yet; layer-wise inference over whole "
-                                  "neighbour rows needs a long-row form of the GATv2 softmax (a C-wide dot product per "
-                                  "entry and head), which is not built: inference.layerwise_inference and its siblings "
-                                  "refuse a GATv2 model")
+        raise NotImplementedError("GATv2.inference: not a method of the model yet; exact layer-wise scoring over whole "
+                                  "neighbour rows runs on the long-row GATv2 softmax of spp_graph_gatv2_forward: call "
+                                  "inference.gatv2_inference(model, x_all, rowptr, col, ...) for log-probabilities or "
+                                  "inference.evaluate(model, x_all, rowptr, col, y, ...) for predictions and losses")
 
 
 # --------------------------------------------------------------------------------------------

@@ -4,6 +4,7 @@ with bf16 activations, timed per layer, and layer 1's slabs once more through th
 
     python tools/inference_profile.py [--workload S-papers] [--rows-per-slab 1048576] [--hidden 256] [--json out.json]
     python tools/inference_profile.py --model gat [--heads 4] [--repeats 3] ...
+    python tools/inference_profile.py --model gatv2 [--heads 4] [--share-weights] [--repeats 3] ...
     python tools/inference_profile.py --model sageresinception [--nodes 1500000] [--torch-epilogue] [--repeats 3] ...
     python tools/inference_profile.py --model gcn [--repeats 3] ...      (``gcn_leg``: the weighted kernels against the sum)
     python tools/inference_profile.py --evaluate [--repeats 3] ...
@@ -14,6 +15,11 @@ with bf16 activations, timed per layer, and layer 1's slabs once more through th
 ``--model gat``: GAT 3 x hidden at ``--heads`` through spp_graph_gat_forward, ``--repeats`` whole passes in one process
 (the first warms up code objects and the GEMM library's choices; every pass is reported).  Its bytes are the mean's plus
 the logits: 4 * H per entry (a_src) and 8 * H per target (a_src of the self loop, a_dst).
+
+``--model gatv2``: GATv2 3 x hidden at ``--heads`` (1, 2, 4 or 8; ``--share-weights``) through spp_graph_gatv2_forward inside
+``gatv2_inference``, passes as for gat.  Run it in the same session as ``--model gat`` at the same heads and width, which is its
+yardstick.  At S-papers the last layer's projected rows are [N, heads * Cp] twice (172 classes pad to Cp = 256): heads = 1, or
+``--share-weights`` with fewer classes, is what fits one device (inference._gatv2_layers has the arithmetic).
 
 ``--model sageresinception``: SAGEResInception 3 x hidden scored at a random sample of ``--nodes`` nodes; per layer the
 aggregation seconds as above, the epilogue seconds (events around every spp_resinc_epilogue call, summed; bytes: z, the
@@ -66,7 +72,8 @@ def main():
     ap.add_argument("--hidden", type=int, default=256)
     ap.add_argument("--classes", type=int, default=172)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--model", choices=("sage", "gat", "sageresinception", "gcn"), default="sage")
+    ap.add_argument("--model", choices=("sage", "gat", "gatv2", "sageresinception", "gcn"), default="sage")
+    ap.add_argument("--share-weights", action="store_true", help="gatv2: lin_r is lin_l (one projection, x_r = x_l)")
     ap.add_argument("--heads", type=int, default=1)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--nodes", type=int, default=1_500_000, help="sageresinception: nodes scored (0 = all)")
@@ -98,6 +105,8 @@ def main():
         return gat_parts_leg(a, wl, res) if a.model == "gat" else parts_leg(a, wl, res)
     if a.model == "gat":
         return gat_leg(a, wl, res)
+    if a.model == "gatv2":
+        return gatv2_leg(a, wl, res)
     if a.model == "sageresinception":
         return resinc_leg(a, wl, res)
     if a.model == "gcn":
@@ -621,6 +630,54 @@ def gat_leg(a, wl, res):
         res["passes"].append(one)
         print(json.dumps(one), flush=True)
     inf._gat_launch = inner
+    res.pop("layers")
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+def gatv2_leg(a, wl, res):
+    """``gat_leg`` for GATv2: the slabs' ``inference._gatv2_launch`` timed inside whole ``gatv2_inference`` passes.  The
+    bytes: the entries' rows of x_l, per target its rows of x_l (the self loop) and x_r, the indices and the output."""
+    from salient_plusplus_amd import inference as inf
+    from salient_plusplus_amd.models import GATv2
+    x, rowptr, col = wl.x, wl.rowptr, wl.col
+    N, E, H = wl.num_nodes, col.numel(), a.heads
+    res.update(model="gatv2", heads=H, share_weights=bool(a.share_weights), chunk=inf.graph_gatv2_chunk(), passes=[])
+    spans = []
+    inner = inf._gatv2_launch
+
+    def timed(x_l, *args):
+        b, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        b.record()
+        out = inner(x_l, *args)
+        e.record()
+        spans.append((x_l.size(1), x_l.element_size(), out.size(0), out.size(1) * out.element_size(), b, e))
+        return out
+    inf._gatv2_launch = timed
+    torch.manual_seed(0)
+    model = GATv2(x.size(1), a.hidden, a.classes, 3, heads=H, share_weights=a.share_weights).to(x.device)
+    slabs = -(-N // a.rows_per_slab)
+    for rep in range(a.repeats):
+        del spans[:]
+        torch.cuda.synchronize()
+        t0 = time.time()
+        out = inf.gatv2_inference(model, x, rowptr, col, rows_per_slab=a.rows_per_slab, act_dtype=torch.bfloat16)
+        torch.cuda.synchronize()
+        one = {"pass": rep, "total_s": round(time.time() - t0, 3), "layers": []}
+        assert out.shape == (N, a.classes) and bool(torch.isfinite(out[:: max(1, N // 4096)]).all())
+        del out
+        for layer in range(3):
+            part = spans[layer * slabs:(layer + 1) * slabs]
+            F_, s_in = part[0][0], part[0][1]                # (the last layer's F is heads * the padded classes)
+            agg_s = sum(b.elapsed_time(e) for *_x, b, e in part) / 1e3
+            nbytes = (E + 2 * N) * F_ * s_in + 16 * N + 8 * E + sum(T * w for _f, _s, T, w, _b, _e in part)
+            one["layers"].append({"layer": layer + 1, "F": F_, "x_bytes_per_elem": s_in, "agg_s": round(agg_s, 4),
+                                  "edges_per_s": round(E / agg_s), "algorithmic_TBps": round(nbytes / agg_s / 1e12, 3)})
+        res["passes"].append(one)
+        print(json.dumps(one), flush=True)
+    inf._gatv2_launch = inner
     res.pop("layers")
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
