@@ -1912,6 +1912,31 @@ int64_t spp_graph_gatv2_workspace_bytes(int64_t num_targets);
 spp_status spp_graph_gatv2_forward(const spp_graph_gatv2_desc* desc, void* workspace_dev, int64_t workspace_bytes,
                                    void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * f3x  ATTENTION DROPOUT for GATv2Conv: PyG's GATv2Conv(dropout=p), F.dropout(alpha, p, training) on the attention
+ *      coefficients.  The pair of f3v with (p, training, seed) appended after `stream`; the descriptor, the layouts,
+ *      the shapes and everything else as f3v states them.
+ *        alpha_ij = softmax_j(e_ij)          over ALL entries, exactly as f3v: the mask never enters the softmax
+ *        q_ij     = keep_ij / (1 - p)        keep in {0, 1} per (entry, head), the self loop dropped like any other entry
+ *        out[i,h,:] = sum_j q_ij alpha_ij x_l[j,h,:]
+ *      row_max and row_sum are the values of spp_gatv2_forward on the same inputs, bit for bit.  Backward, with
+ *      go = g_i . out_i on the saved (dropped) out and gh = g_i . x_l[j]:
+ *        ge = alpha (q gh - go)              a dropped entry still sends -alpha go to its logit: dL/dalpha_ij = q_ij gh
+ *                                            and sum_k alpha_ik q_ik gh_ik = go, so this is the softmax gradient (f3t)
+ *        grad_x_l[j,h,c] += q alpha g[i,h,c] + ge att[h,c] d,     grad_x_r and grad_att from ge as in f3v.
+ *      Forward and backward take the same (p, seed).
+ *   Keep rule: f3t's, unchanged, with E = rowptr[T] (read by the kernels), T targets, H heads: draw index i = k * H + h for
+ *   CSR entry k (a skipped diagonal entry consumes its index), i = (E + t) * H + h for target t's self loop; draw(i) = the
+ *   low (i even) or high (i odd) 32 bits of mix64(seed + (i >> 1) * 0x9E3779B97F4A7C15); kept iff draw(i) < keep_thr.
+ *   spp_gat_mh_attn_keep(E, T, H, p, seed, ...) therefore writes the mask these entries apply.
+ *   Refusals: those of the entry each extends, in its order, with `0 <= p < 1` checked right after the shape (D <= 1024
+ *   and 0 <= T <= S), so before the backward's grad_att, the T == 0 return and the rows; a NaN p is refused.
+ *   training = 0 or p = 0 launches the kernels of the entry without dropout: the same bits.  spp_gatv2_desc is untouched;
+ *   SPP_ABI_VERSION stays 6.
+ * ------------------------------------------------------------------------- */
+spp_status spp_gatv2_forward_drop(const spp_gatv2_desc* desc, void* stream, float p, int32_t training, uint64_t seed);
+spp_status spp_gatv2_backward_drop(const spp_gatv2_desc* desc, void* stream, float p, int32_t training, uint64_t seed);
+
 #ifdef __cplusplus
 }
 #endif

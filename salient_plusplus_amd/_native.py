@@ -398,6 +398,9 @@ SIGNATURES = {
     "spp_graph_gatv2_chunk": (i64, []),
     "spp_graph_gatv2_workspace_bytes": (i64, [i64]),
     "spp_graph_gatv2_forward": (C.c_int, [C.POINTER(GraphGatv2Desc), p, i64, p]),
+    # attention dropout (spp.h f3x): the training pair + (p, training, seed); the mask is spp_gat_mh_attn_keep's
+    "spp_gatv2_forward_drop": (C.c_int, [C.POINTER(Gatv2Desc), p, C.c_float, i32, C.c_uint64]),
+    "spp_gatv2_backward_drop": (C.c_int, [C.POINTER(Gatv2Desc), p, C.c_float, i32, C.c_uint64]),
 }
 SPP_COMM_ID_BYTES = 128
 SPP_IPC_HANDLE_BYTES = 64

@@ -1,5 +1,5 @@
 // The keep / drop rule of every dropout this library applies (aggregate.hip: k_relu_dropout_*, the activated operand;
-// bn_act.hip: the BatchNorm tail; gat.hip: the attention dropout), from a counter-based generator: element i of the call with `seed` is kept iff
+// bn_act.hip: the BatchNorm tail; gat.hip, gatv2.hip: the attention dropout), from a counter-based generator: element i of the call with `seed` is kept iff
 // hash(seed, i) < (1 - p) * 2^32.  One 64-bit hash serves two elements; the n % 4 elements at the end of an array take
 // a hash of their own (the tail of k_relu_dropout_fwd).
 #pragma once
@@ -67,6 +67,14 @@ __device__ __forceinline__ void attn_keep_heads(uint64_t entry, const ActArgs& a
       keep[2 * q + 1] = (uint32_t)(r >> 32) < a.keep_thr;
     }
   }
+}
+
+// The same draw for ONE head h of H (spp.h f3x): for kernels whose lanes serve only some of the heads (gatv2.hip), so a
+// lane hashes for the heads it holds and no others.  attn_keep_heads<H>(entry, a, keep)[h] for every H, entry and h.
+__device__ __forceinline__ bool attn_keep_head(uint64_t entry, int H, int h, const ActArgs& a) {
+  const uint64_t i = entry * (uint64_t)H + (uint64_t)h;
+  const uint64_t r = mix64(a.seed + (i >> 1) * 0x9E3779B97F4A7C15ull);
+  return (uint32_t)(i & 1 ? r >> 32 : r) < a.keep_thr;
 }
 
 static inline ActArgs act_args(float p, int32_t training, uint64_t seed) {

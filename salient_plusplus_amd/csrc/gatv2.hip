@@ -22,13 +22,19 @@ constexpr int kV2NT = 256;
 // Forward.  The lane mapping, the logit, the online softmax and the walk over a row are gatv2_core.hip.h's (shared with
 // the long-row kernels of graph_gatv2.hip): lpr lanes per target, 4 columns per lane and chunk, NB neighbours in flight,
 // one butterfly per round.  The targets are the first T rows of x_l.  No atomics: the same bits in every run.
-template <typename Tin, int NQ, int CPH>
+// kDrop (attention dropout, spp.h f3x): out[i,h,:] = sum_j q_ij^h alpha_ij^h x_l[j,h,:], q = keep / (1 - p) per (entry,
+// head) by the keep rule of f3t (entry k for CSR entry k, E + t for t's self loop, E = rowptr[T]).  The softmax runs
+// over ALL entries -- row_max and row_sum are the kDrop = false bits -- and only acc skips a dropped entry, the self
+// loop's x_l[t] included.  The lane's head hl is global head ((hl * CPH) * lpr + lane) >> g_log2; every lane hashes for
+// the heads it holds (the lanes of a head's segment draw the same bits).
+template <typename Tin, int NQ, int CPH, bool kDrop>
 __global__ __launch_bounds__(kV2NT) void k_gatv2_fwd(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,
                                                      int64_t T, const Tin* xl, int64_t xl_stride, const Tin* xr,
                                                      int64_t xr_stride, const float* __restrict__ att, float slope,
                                                      int lpr_log2, int seg_log2, int g_log2, int H,
                                                      float* __restrict__ out, float* __restrict__ row_max,
-                                                     float* __restrict__ row_sum) {
+                                                     float* __restrict__ row_sum, ActArgs drop) {
+  constexpr int HL = NQ / CPH;
   Lane<NQ, CPH> L;
   L.slope = slope, L.lpr = 1 << lpr_log2, L.lane = threadIdx.x & (L.lpr - 1), L.seg_log2 = seg_log2;
   const int64_t t = ((int64_t)blockIdx.x * kV2NT + threadIdx.x) >> lpr_log2;
@@ -37,12 +43,27 @@ __global__ __launch_bounds__(kV2NT) void k_gatv2_fwd(const int64_t* __restrict__
   L.load(att, xr + t * xr_stride);
   State<NQ, CPH> st;
   self_state(st, L, xl + t * xl_stride);  // the self loop's message: source row t
-  walk(st, L, xl, xl_stride, col, rowptr[t], rowptr[t + 1], t, (int64_t)-1);
+  if constexpr (kDrop) {
+    Drop<HL> dr;
+    dr.a = drop, dr.H = H;
+#pragma unroll
+    for (int hl = 0; hl < HL; ++hl) dr.head[hl] = ((hl * CPH) * L.lpr + L.lane) >> g_log2;
+    const uint64_t self = (uint64_t)(rowptr[T] + t);  // the self loops' draws come after the E = rowptr[T] entries'
+#pragma unroll
+    for (int hl = 0; hl < HL; ++hl) {
+      if (attn_keep_head(self, H, dr.head[hl], drop)) continue;
+#pragma unroll
+      for (int q = hl * CPH; q < (hl + 1) * CPH; ++q) st.acc[q] = {0.f, 0.f, 0.f, 0.f};
+    }
+    walk<true>(st, L, xl, xl_stride, col, rowptr[t], rowptr[t + 1], t, (int64_t)-1, &dr);
+  } else {
+    walk(st, L, xl, xl_stride, col, rowptr[t], rowptr[t + 1], t, (int64_t)-1);
+  }
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
     const int hl = q / CPH;
     const int p = q * L.lpr + L.lane;
-    const f4 r = st.result(q);
+    const f4 r = st.template result<kDrop>(q, drop.scale);
     *reinterpret_cast<float4*>(out + t * D + (int64_t)p * 4) = make_float4(r.x, r.y, r.z, r.w);
     if ((p & ((1 << g_log2) - 1)) == 0) {  // the head's first piece
       row_max[t * H + (p >> g_log2)] = st.mm[hl];
@@ -61,7 +82,11 @@ __global__ __launch_bounds__(kV2NT) void k_gatv2_fwd(const int64_t* __restrict__
 // them, and a workgroup adds them up (across the groups of a wavefront by shuffles, across wavefronts through LDS) before
 // its D atomics on grad_att (k_gat_mh_colsum's rule: every workgroup ends on the SAME addresses).
 // lrelu'(0) = slope (v > 0 ? 1 : slope).
-template <typename Tin, int NS, int SPH>
+// kDrop (attention dropout, the forward's (p, seed)): go is taken on the saved DROPPED out, so sum_j q alpha gh = go and
+// ge = alpha (q gh - go) is the softmax gradient again -- a dropped entry (q = 0) still sends -alpha go to its logit --
+// and grad_xl[j] takes q alpha g_i + ge att d.  q = keep ? 1 / (1 - p) : 0 per (entry, head), the forward's draws: the
+// lane's head hl is global head (lane + lpt * hl * SPH) >> c_log2, and every lane hashes for the heads it holds.
+template <typename Tin, int NS, int SPH, bool kDrop>
 __global__ __launch_bounds__(kV2NT) void k_gatv2_bwd(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,
                                                      int64_t T, const Tin* xl, int64_t xl_stride, const Tin* xr,
                                                      int64_t xr_stride, const float* __restrict__ att, float slope,
@@ -69,7 +94,8 @@ __global__ __launch_bounds__(kV2NT) void k_gatv2_bwd(const int64_t* __restrict__
                                                      const float* __restrict__ out, const float* __restrict__ row_max,
                                                      const float* __restrict__ row_sum, const float* __restrict__ g,
                                                      int64_t tpg, float* __restrict__ grad_xl,
-                                                     float* __restrict__ grad_xr, float* __restrict__ grad_att) {
+                                                     float* __restrict__ grad_xr, float* __restrict__ grad_att,
+                                                     ActArgs drop) {
   constexpr int HL = NS / SPH;
   __shared__ float red[kV2NT / kWave][NS][kWave];
   const int lpt = 1 << lpt_log2;
@@ -83,6 +109,12 @@ __global__ __launch_bounds__(kV2NT) void k_gatv2_bwd(const int64_t* __restrict__
   for (int i = 0; i < NS; ++i) {
     av[i] = att[lane + lpt * i];
     ga[i] = 0.f;
+  }
+  [[maybe_unused]] const int64_t E = kDrop ? rowptr[T] : 0;  // the self loops' draws come after the E entries'
+  [[maybe_unused]] int head[HL];
+  if constexpr (kDrop) {
+#pragma unroll
+    for (int hl = 0; hl < HL; ++hl) head[hl] = (lane + lpt * hl * SPH) >> c_log2;
   }
   for (int64_t t = t0; t < t1; ++t) {
     const int64_t b = rowptr[t], e = rowptr[t + 1];
@@ -111,6 +143,12 @@ __global__ __launch_bounds__(kV2NT) void k_gatv2_bwd(const int64_t* __restrict__
       float xv[NS], pe[HL], gh[HL];
 #pragma unroll
       for (int i = 0; i < NS; ++i) xv[i] = load1(xl + j * xl_stride + lane + lpt * i);
+      [[maybe_unused]] float q[HL];  // kDrop: keep / (1 - p)
+      if constexpr (kDrop) {
+#pragma unroll
+        for (int hl = 0; hl < HL; ++hl)
+          q[hl] = attn_keep_head((uint64_t)(k < b ? E + t : k), H, head[hl], drop) ? drop.scale : 0.f;
+      }
 #pragma unroll
       for (int hl = 0; hl < HL; ++hl) pe[hl] = gh[hl] = 0.f;
 #pragma unroll
@@ -128,7 +166,8 @@ __global__ __launch_bounds__(kV2NT) void k_gatv2_bwd(const int64_t* __restrict__
 #pragma unroll
       for (int hl = 0; hl < HL; ++hl) {
         a[hl] = expf(pe[hl] - m[hl]) * inv_s[hl];
-        ge[hl] = a[hl] * (gh[hl] - go[hl]);
+        ge[hl] = a[hl] * ((kDrop ? q[hl] * gh[hl] : gh[hl]) - go[hl]);
+        if constexpr (kDrop) a[hl] *= q[hl];  // from here on a is the message's weight q alpha
       }
 #pragma unroll
       for (int i = 0; i < NS; ++i) {
@@ -215,32 +254,55 @@ static spp_status gatv2_check_rows(const spp_gatv2_desc* d, const char* who) {
   return SPP_OK;
 }
 
-extern "C" spp_status spp_gatv2_forward(const spp_gatv2_desc* d, void* stream) {
-  const char* who = "spp_gatv2_forward";
+// Attention dropout of the spp_gatv2_*_drop entries (spp.h f3x); the entries without it pass V2Drop{}.  p is checked
+// right after the shape, before the T == 0 return and the rows; training = 0 or p = 0 runs the kDrop = false kernels.
+struct V2Drop {
+  bool given = false;
+  float p = 0.f;
+  int32_t training = 0;
+  uint64_t seed = 0;
+  bool on() const { return given && training && p > 0.f; }
+  ActArgs args() const { return act_args(on() ? p : 0.f, training, seed); }
+};
+static spp_status gatv2_check_drop(const V2Drop& dr, const char* who) {
+  SPP_REQUIRE(!dr.given || (dr.p >= 0.f && dr.p < 1.f), "%s: attention dropout needs 0 <= p < 1", who);
+  return SPP_OK;
+}
+// fn(std::bool_constant<kDrop>{})
+template <class Fn>
+static void with_drop(bool on, Fn&& fn) {
+  if (on) fn(std::true_type{}); else fn(std::false_type{});
+}
+
+static spp_status gatv2_forward(const spp_gatv2_desc* d, void* stream, const char* who, const V2Drop& dr) {
   SPP_TRY(gatv2_check_shape(d, who));
+  SPP_TRY(gatv2_check_drop(dr, who));
   if (d->num_targets == 0) return SPP_OK;
   SPP_TRY(gatv2_check_rows(d, who));
   const int64_t T = d->num_targets;
   const Shape sh = shape_of(d->heads, d->C);
   const int lpr_log2 = sh.lpr_log2, seg_log2 = sh.seg_log2, g_log2 = sh.g_log2, nq = sh.nq, cph = sh.cph;
   const unsigned grid = (unsigned)ceil_div(T << lpr_log2, kV2NT);
+  const ActArgs da = dr.args();
   with_elem(d->x_elem, [&](auto tin) {
     with_fwd_shape(nq, cph, [&](auto q, auto c) {
-      using Tin = typename decltype(tin)::type;
-      hipLaunchKernelGGL((k_gatv2_fwd<Tin, decltype(q)::value, decltype(c)::value>), dim3(grid), dim3(kV2NT), 0,
-                         as_stream(stream), d->rowptr_dev, d->col_dev, T, static_cast<const Tin*>(d->x_l_dev),
-                         d->x_l_stride_elems, static_cast<const Tin*>(d->x_r_dev), d->x_r_stride_elems, d->att_dev,
-                         d->negative_slope, lpr_log2, seg_log2, g_log2, (int)d->heads, d->out_dev, d->row_max_dev,
-                         d->row_sum_dev);
+      with_drop(dr.on(), [&](auto drop) {
+        using Tin = typename decltype(tin)::type;
+        hipLaunchKernelGGL((k_gatv2_fwd<Tin, decltype(q)::value, decltype(c)::value, decltype(drop)::value>),
+                           dim3(grid), dim3(kV2NT), 0, as_stream(stream), d->rowptr_dev, d->col_dev, T,
+                           static_cast<const Tin*>(d->x_l_dev), d->x_l_stride_elems,
+                           static_cast<const Tin*>(d->x_r_dev), d->x_r_stride_elems, d->att_dev, d->negative_slope,
+                           lpr_log2, seg_log2, g_log2, (int)d->heads, d->out_dev, d->row_max_dev, d->row_sum_dev, da);
+      });
     });
   });
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
 }
 
-extern "C" spp_status spp_gatv2_backward(const spp_gatv2_desc* d, void* stream) {
-  const char* who = "spp_gatv2_backward";
+static spp_status gatv2_backward(const spp_gatv2_desc* d, void* stream, const char* who, const V2Drop& dr) {
   SPP_TRY(gatv2_check_shape(d, who));
+  SPP_TRY(gatv2_check_drop(dr, who));
   const int64_t T = d->num_targets, D = d->heads * d->C;
   SPP_REQUIRE(d->grad_att_dev && aligned_to(d->grad_att_dev, 16), "%s: NULL or misaligned grad_att", who);
   if (T > 0) {
@@ -259,16 +321,36 @@ extern "C" spp_status spp_gatv2_backward(const spp_gatv2_desc* d, void* stream) 
   const int64_t gpb = kV2NT / lpt;
   const int64_t tpg = std::max<int64_t>(1, ceil_div(T, 1024 * gpb));
   const unsigned grid = (unsigned)ceil_div(ceil_div(T, tpg), gpb);
+  const ActArgs da = dr.args();
   with_elem(d->x_elem, [&](auto tin) {
     with_bwd_shape(ns, sph, [&](auto n, auto s) {
-      using Tin = typename decltype(tin)::type;
-      hipLaunchKernelGGL((k_gatv2_bwd<Tin, decltype(n)::value, decltype(s)::value>), dim3(grid), dim3(kV2NT), 0, st,
-                         d->rowptr_dev, d->col_dev, T, static_cast<const Tin*>(d->x_l_dev), d->x_l_stride_elems,
-                         static_cast<const Tin*>(d->x_r_dev), d->x_r_stride_elems, d->att_dev, d->negative_slope,
-                         lpt_log2, seg_log2, c_log2, (int)d->heads, d->out_dev, d->row_max_dev, d->row_sum_dev,
-                         d->grad_out_dev, tpg, d->grad_x_l_dev, d->grad_x_r_dev, d->grad_att_dev);
+      with_drop(dr.on(), [&](auto drop) {
+        using Tin = typename decltype(tin)::type;
+        hipLaunchKernelGGL((k_gatv2_bwd<Tin, decltype(n)::value, decltype(s)::value, decltype(drop)::value>),
+                           dim3(grid), dim3(kV2NT), 0, st, d->rowptr_dev, d->col_dev, T,
+                           static_cast<const Tin*>(d->x_l_dev), d->x_l_stride_elems,
+                           static_cast<const Tin*>(d->x_r_dev), d->x_r_stride_elems, d->att_dev, d->negative_slope,
+                           lpt_log2, seg_log2, c_log2, (int)d->heads, d->out_dev, d->row_max_dev, d->row_sum_dev,
+                           d->grad_out_dev, tpg, d->grad_x_l_dev, d->grad_x_r_dev, d->grad_att_dev, da);
+      });
     });
   });
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
+}
+
+extern "C" spp_status spp_gatv2_forward(const spp_gatv2_desc* d, void* stream) {
+  return gatv2_forward(d, stream, "spp_gatv2_forward", V2Drop{});
+}
+extern "C" spp_status spp_gatv2_backward(const spp_gatv2_desc* d, void* stream) {
+  return gatv2_backward(d, stream, "spp_gatv2_backward", V2Drop{});
+}
+// with attention dropout (spp.h f3x): (p, training, seed) after `stream`
+extern "C" spp_status spp_gatv2_forward_drop(const spp_gatv2_desc* d, void* stream, float p, int32_t training,
+                                             uint64_t seed) {
+  return gatv2_forward(d, stream, "spp_gatv2_forward_drop", V2Drop{true, p, training, seed});
+}
+extern "C" spp_status spp_gatv2_backward_drop(const spp_gatv2_desc* d, void* stream, float p, int32_t training,
+                                              uint64_t seed) {
+  return gatv2_backward(d, stream, "spp_gatv2_backward_drop", V2Drop{true, p, training, seed});
 }

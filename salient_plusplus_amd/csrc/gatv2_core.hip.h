@@ -9,9 +9,13 @@
 // chunks, four products each, from 0.f in chunk order; the partials are added by an xor butterfly over the min(G, lpr)
 // lanes of the head's segment, widest step first, so every lane of the segment holds the logit and runs the head's
 // online softmax for its own columns.  That order is fixed by (H, C) and by nothing else.
+//
+// kDrop (attention dropout of the training pair, spp.h f3x) is a compile-time parameter of take, result and walk that
+// defaults to false: the graph kernels and the p = 0 training forward instantiate the bodies they always had.  With
+// kDrop the softmax (mm, ss) takes every entry as before and only acc skips a dropped one.
 #pragma once
 
-#include "elem_io.hip.h"
+#include "act_keep.hip.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -74,8 +78,10 @@ struct State {
 #pragma unroll
     for (int hl = 0; hl < HL; ++hl) mm[hl] = -INFINITY, ss[hl] = 0.f;
   }
-  // one more entry of head hl with logit sc and row pieces xv (expf: spp.h f3v says why)
-  __device__ __forceinline__ void take(int hl, float sc, const f4 (&xv)[NQ]) {
+  // one more entry of head hl with logit sc and row pieces xv (expf: spp.h f3v says why).  kDrop: an entry with
+  // keep = false counts in (mm, ss) like any other and leaves acc alone
+  template <bool kDrop = false>
+  __device__ __forceinline__ void take(int hl, float sc, const f4 (&xv)[NQ], [[maybe_unused]] bool keep = true) {
 #pragma clang fp contract(off)
     if (sc > mm[hl]) {
       const float r = expf(mm[hl] - sc);  // (m = -inf: r = 0, and s, acc are 0)
@@ -88,6 +94,8 @@ struct State {
     }
     const float w = expf(sc - mm[hl]);
     ss[hl] += w;
+    if constexpr (kDrop)
+      if (!keep) return;
 #pragma unroll
     for (int q = hl * CPH; q < (hl + 1) * CPH; ++q) {
       acc[q] = {fmaf(w, xv[q].x, acc[q].x), fmaf(w, xv[q].y, acc[q].y), fmaf(w, xv[q].z, acc[q].z),
@@ -110,10 +118,11 @@ struct State {
       mm[hl] = m;
     }
   }
-  // piece q of the result: acc / s, as a product by the reciprocal
-  __device__ __forceinline__ f4 result(int q) const {
+  // piece q of the result: acc / s, as a product by the reciprocal; kDrop: by scale / s, scale = 1 / (1 - p)
+  template <bool kDrop = false>
+  __device__ __forceinline__ f4 result(int q, [[maybe_unused]] float scale = 1.f) const {
 #pragma clang fp contract(off)
-    const float inv = 1.f / ss[q / CPH];
+    const float inv = (kDrop ? scale : 1.f) / ss[q / CPH];
     return {acc[q].x * inv, acc[q].y * inv, acc[q].z * inv, acc[q].w * inv};
   }
 };
@@ -126,6 +135,15 @@ __device__ __forceinline__ void butterfly(float (&v)[N], int seg_log2) {
 #pragma unroll
     for (int i = 0; i < N; ++i) v[i] += __shfl_xor(v[i], d, kWave);
 }
+
+// kDrop: what a lane needs to draw the keep bits of its heads (act_keep.hip.h attn_keep_head): the call's threshold and
+// seed, the head count, and the global head behind each of the lane's HL local ones
+template <int HL>
+struct Drop {
+  ActArgs a;
+  int H;
+  int head[HL];
+};
 
 // the self loop's state of a target whose SOURCE row is xl_row: m = e_tt, s = 1, acc = x_l[t]
 template <typename Tin, int NQ, int CPH>
@@ -142,9 +160,12 @@ __device__ __forceinline__ void self_state(State<NQ, CPH>& st, const Lane<NQ, CP
 // round: ids, then rows, then partial dots, then ONE butterfly whose steps carry all NB * HL values (one dependent
 // reduction per entry was the slow version).  x_rows >= 0: an entry outside [0, x_rows) is node 0 in every respect;
 // x_rows < 0: the ids are taken as they are (an MFG hop's).  b, e and t are the same for all lanes of the group.
-template <typename Tin, int NQ, int CPH>
+// kDrop: CSR entry k is softmax entry k of the keep rule (a skipped diagonal entry still owns its index); every lane
+// draws for its own heads, dr->head, and the draws are issued with the rows' loads, ahead of the butterfly.
+template <bool kDrop = false, typename Tin, int NQ, int CPH>
 __device__ __forceinline__ void walk(State<NQ, CPH>& st, const Lane<NQ, CPH>& L, const Tin* xl, int64_t xl_stride,
-                                     const int64_t* __restrict__ col, int64_t b, int64_t e, int64_t t, int64_t x_rows) {
+                                     const int64_t* __restrict__ col, int64_t b, int64_t e, int64_t t, int64_t x_rows,
+                                     [[maybe_unused]] const Drop<NQ / CPH>* dr = nullptr) {
   constexpr int HL = NQ / CPH, NB = Lane<NQ, CPH>::NB;
   for (int64_t k0 = b; k0 < e; k0 += NB) {
     int64_t j[NB];
@@ -158,6 +179,14 @@ __device__ __forceinline__ void walk(State<NQ, CPH>& st, const Lane<NQ, CPH>& L,
     for (int u = 0; u < NB; ++u)
 #pragma unroll
       for (int q = 0; q < NQ; ++q) xv[u][q] = load4(xl + j[u] * xl_stride + L.col0(q));
+    [[maybe_unused]] bool keep[NB * HL];
+    if constexpr (kDrop) {
+#pragma unroll
+      for (int u = 0; u < NB; ++u)
+#pragma unroll
+        for (int hl = 0; hl < HL; ++hl)
+          keep[u * HL + hl] = attn_keep_head((uint64_t)(k0 + u), dr->H, dr->head[hl], dr->a);
+    }
     float pd[NB * HL];
 #pragma unroll
     for (int u = 0; u < NB; ++u) {
@@ -171,7 +200,10 @@ __device__ __forceinline__ void walk(State<NQ, CPH>& st, const Lane<NQ, CPH>& L,
     for (int u = 0; u < NB; ++u) {
       if (k0 + u >= e || j[u] == t) continue;  // set_diag drops existing diagonal entries
 #pragma unroll
-      for (int hl = 0; hl < HL; ++hl) st.take(hl, pd[u * HL + hl], xv[u]);
+      for (int hl = 0; hl < HL; ++hl) {
+        if constexpr (kDrop) st.template take<true>(hl, pd[u * HL + hl], xv[u], keep[u * HL + hl]);
+        else st.take(hl, pd[u * HL + hl], xv[u]);
+      }
     }
   }
 }

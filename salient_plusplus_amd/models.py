@@ -1168,9 +1168,10 @@ def _gatv2_reference(x_l, x_r, att, rowptr, col, slope, p=0.0):
     """GATv2Conv's message passing in PyG's order, in plain torch ops, on the projected rows: x_l [S, H, C] = lin_l(x),
     x_r [T, H, C] = lin_r(x_target), att [H, C] -> out [T, H, C] (fp32; float64 for float64 rows).  The path for
     everything the kernels do not read: CPU tensors, head counts outside {1, 2, 4, 8}, C with C / 4 not a power of two,
-    H * C > 1024, share_weights with a target block that is not the prefix of x, and training with dropout.
+    H * C > 1024, and share_weights with a target block that is not the prefix of x.
     set_diag: diagonal entries dropped, one self loop (i, i) per target, whose message is source row i.
-    p > 0 (training): F.dropout on alpha -- torch's own mask, from the generator of alpha's device."""
+    p > 0 (training): F.dropout on alpha -- torch's own mask, from the generator of alpha's device, NOT the kernels'
+    counter-based one (_attn_keep_reference), which the rows the kernels read get (spp.h f3x)."""
     T, H = x_r.size(0), att.size(0)
     dt = torch.float64 if x_l.dtype == torch.float64 else torch.float32
     x_l, x_r, att = x_l.to(dt), x_r.to(dt), att.to(dt)
@@ -1214,10 +1215,19 @@ class _GATv2Layer(torch.autograd.Function):
     [T, H, C] fp32, spp_gatv2_forward / spp_gatv2_backward.  The rows are fp32, fp16 or bf16 (under bf16 autocast the
     projections outside the node give bf16 rows, which the kernels read as such); x_r may be a view of x_l
     (share_weights).  The node runs with autocast off, returns fp32 and casts grad_xl / grad_xr back to the rows' dtype;
-    att and its gradient are fp32."""
+    att and its gradient are fp32.  p > 0: attention dropout inside the kernels (spp.h f3x) -- the forward draws a seed
+    from torch's CPU generator (_attn_seed), and both directions call the _drop entries with (p, training = 1, seed),
+    so the backward applies the forward's mask; p = 0 calls the entries without dropout."""
 
     @staticmethod
-    def forward(ctx, x_l, x_r, att, rowptr, col, slope):
+    def _call(L, name, d, drop):
+        if drop:
+            nat.check(getattr(L, name + "_drop")(C.byref(d), _stream(), drop[0], 1, drop[1]))
+        else:
+            nat.check(getattr(L, name)(C.byref(d), _stream()))
+
+    @staticmethod
+    def forward(ctx, x_l, x_r, att, rowptr, col, slope, p=0.0):
         with _no_autocast():
             L = nat.load()
             nat.require_device()
@@ -1228,7 +1238,8 @@ class _GATv2Layer(torch.autograd.Function):
             out = torch.empty((T, H, Cc), **f32)
             rmax, rsum = torch.empty((T, H), **f32), torch.empty((T, H), **f32)
             d = _gatv2_desc(x_l, x_r, att32, rowptr, col, slope, out, rmax, rsum)
-            nat.check(L.spp_gatv2_forward(C.byref(d), _stream()))
+            ctx.drop = (float(p), _attn_seed()) if p > 0.0 else None
+            _GATv2Layer._call(L, "spp_gatv2_forward", d, ctx.drop)
             ctx.save_for_backward(x_l, x_r, att32, rowptr, col, out, rmax, rsum)
             ctx.slope, ctx.att_dtype = float(slope), att.dtype
             return out
@@ -1245,9 +1256,10 @@ class _GATv2Layer(torch.autograd.Function):
             g_xr, g_att = torch.empty((T, D), **f32), torch.empty((H, Cc), **f32)
             d = _gatv2_desc(x_l, x_r, att32, rowptr, col, ctx.slope, out, rmax, rsum, grad_out_dev=g, grad_x_l_dev=g_xl,
                             grad_x_r_dev=g_xr, grad_att_dev=g_att)
-            nat.check(nat.load().spp_gatv2_backward(C.byref(d), _stream()))
+            _GATv2Layer._call(nat.load(), "spp_gatv2_backward", d, ctx.drop)
             return (g_xl.to(x_l.dtype) if g_xl is not None else None,
-                    g_xr.to(x_r.dtype) if ctx.needs_input_grad[1] else None, g_att.to(ctx.att_dtype), None, None, None)
+                    g_xr.to(x_r.dtype) if ctx.needs_input_grad[1] else None, g_att.to(ctx.att_dtype), None, None, None,
+                    None)
 
 
 class GATv2Conv(torch.nn.Module):
@@ -1264,8 +1276,14 @@ class GATv2Conv(torch.nn.Module):
     rows with H in {1, 2, 4, 8}, C % 4 == 0 with C / 4 a power of two and H * C <= 1024, and _gatv2_reference, the same
     function in plain torch ops, for everything else.  With share_weights and x_target the prefix of x, x_r is the view
     x_l[:T]: no second GEMM, and autograd sums the two gradients through the view; share_weights with any other
-    x_target takes the reference path.  ``dropout`` = p: F.dropout on the attention coefficients in training -- the
-    reference path with torch's own mask (the in-kernel mask of the GAT kernels is not built for GATv2)."""
+    x_target takes the reference path.
+
+    ``dropout`` = p in [0, 1): F.dropout(alpha, p, training) on the attention coefficients of every (entry, head), the
+    self loop included; the softmax itself runs over all entries.  p = 0 and eval mode run exactly the paths above.  In
+    training with p > 0 the rows the kernels read take _GATv2Layer with the mask generated inside its kernels from a
+    seed drawn from torch's CPU generator (spp.h f3x; GATConv's rule, _attn_keep_reference restates it: torch.manual_seed
+    makes a run repeatable); everything else takes _gatv2_reference with F.dropout on its alpha: torch's own mask there,
+    not the kernels'.  No parameter or buffer: the state dict does not change."""
 
     def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, bias=True,
                  share_weights=False):
@@ -1305,8 +1323,8 @@ class GATv2Conv(torch.nn.Module):
         x_r = x_l[:T] if self.share_weights and prefix else self.lin_r(x_target)
         att = self.att.view(H, Cc)
         p = self.dropout if self.training else 0.0
-        if p == 0.0 and (prefix or not self.share_weights) and _gatv2_kernels_read(x_l, x_r, H, Cc):
-            out = _GATv2Layer.apply(x_l, x_r, att, rowptr, col, self.negative_slope)
+        if (prefix or not self.share_weights) and _gatv2_kernels_read(x_l, x_r, H, Cc):
+            out = _GATv2Layer.apply(x_l, x_r, att, rowptr, col, self.negative_slope, p)
         else:
             out = _gatv2_reference(x_l.view(S, H, Cc), x_r.view(T, H, Cc), att, rowptr, col, self.negative_slope, p)
         out = out.reshape(T, H * Cc) if self.concat else out.mean(1)
