@@ -5,8 +5,8 @@ GIN and SAGEResInception and of csrc/graph_gat.hip for GAT; SAGEResInception's l
 (``spp_resinc_epilogue``); GCN's weighted sums are the pair of csrc/graph_agg_weighted.hip (``graph_weighted_aggregate``,
 with ``gcn_dinv`` for the per-node factors of its normalisation; resident entries only).  The layers' own parameters run
 through the library GEMMs torch dispatches to.  Forward only, fp16 / fp32 / bf16 inputs.  GATv2 (f3w): the long-row
-pair of csrc/graph_gatv2.hip behind ``graph_gatv2_aggregate`` (``spp_graph_gatv2_forward``), the driver ``_gatv2_layers``
-and the entries ``gatv2_inference`` and ``evaluate``; resident only.
+pair of csrc/graph_gatv2.hip behind ``graph_gatv2_aggregate`` (``spp_graph_gatv2_forward``) and the driver
+``_gatv2_layers``; resident entries only.
 
 The kernels' wrappers: ``graph_aggregate`` (``spp_graph_agg_forward``) and ``graph_gat_aggregate``
 (``spp_graph_gat_forward``) read one resident matrix, ``graph_aggregate_parts`` (``spp_graph_agg_parts_forward``) and
@@ -16,13 +16,14 @@ tail all models share: argmax and negative log-likelihood of a tile of logits.  
 with the helpers they share and hands them to its kernel's launch function (``_agg_launch``, ``_gat_launch``,
 ``_agg_parts_launch``, ``_gat_parts_launch``), which the drivers call directly, slab by slab.
 
-The drivers: one layer loop per model (``_conv_layers`` for SAGE and GIN, ``_gat_layers``, ``_resinc_layers``), written
-against a placement that says where the table lives -- ``_Resident`` (one matrix, the whole-table kernels, no waits) or
-``_Partitioned`` (the parts kernels over buffers published through ``peers``, a synchronise and a barrier at every layer
-boundary) -- inside one frame (``_score``).  ``layerwise_inference`` is the resident entry (behind ``SAGE.inference``
-and ``GIN.inference``), ``partitioned_inference`` the partitioned one for all four models
-(``partitioned_layerwise_inference`` admits SAGE and GIN only), with ``LocalPeers`` (ranks as threads of one process)
-or ``IpcPeers`` (one process per rank on one node) between the ranks.  Every driver hands its last layer's logits, tile by
+The drivers: one layer loop per model (``_conv_layers`` for SAGE, GIN and GCN, ``_gat_layers``, ``_gatv2_layers``,
+``_resinc_layers``), written against a placement that says where the table lives -- ``_Resident`` (one matrix, the
+whole-table kernels, no waits) or ``_Partitioned`` (the parts kernels over buffers published through ``peers``, a
+synchronise and a barrier at every layer boundary) -- inside one frame (``_score``).  ``layerwise_inference`` is the
+resident entry for all six models (behind every model's ``.inference``; ``gatv2_inference`` is its older name for
+GATv2), ``partitioned_inference`` the partitioned one for SAGE, GIN, GAT and SAGEResInception
+(``partitioned_layerwise_inference`` is its older name), with ``LocalPeers`` (ranks as threads of one process) or
+``IpcPeers`` (one process per rank on one node) between the ranks.  Every driver hands its last layer's logits, tile by
 tile, to a sink: ``_LogProbs`` (log_softmax into the [rows, classes] matrix those entries return) or ``_Classify``
 (``classify_rows`` into pred [rows] and nll [rows]), which is what ``evaluate`` and ``partitioned_evaluate`` run: the same
 pass, predictions, per-split accuracy and loss out, and no [rows, classes] matrix anywhere.
@@ -40,7 +41,7 @@ from . import _native as nat
 from .fast_sampler import P2PPeers, RowRefs, TableRows, _common_stride, _row_stride_elems, _table_stride_bytes, \
     p2p_open_peers
 from .fp8 import Fp8Features
-from .models import _ELEM, _p, _stream
+from .models import GAT, GATv2, GCN, GIN, SAGE, SAGEResInception, _ELEM, _gcn_fill, _p, _stream
 
 _EPILOGUES = {"mean": nat.SPP_AGG_MEAN, "operand": nat.SPP_AGG_OPERAND, "sum": nat.SPP_AGG_SUM,
               "max": nat.SPP_AGG_MAX, "max_operand": nat.SPP_AGG_MAX_OPERAND}
@@ -553,7 +554,6 @@ def gcn_dinv(rowptr, edge_weight=None, *, add_self_loops=True, improved=False):
     nat.require_device()
     if not rowptr.is_cuda or (edge_weight is not None and edge_weight.device != rowptr.device):
         raise ValueError(f"{what}: rowptr and edge_weight must live on one CUDA device")
-    from .models import _gcn_fill
     N = rowptr.numel() - 1
     dinv = torch.empty(N, dtype=torch.float32, device=rowptr.device)
     d = nat.GcnDinvDesc(fill=_gcn_fill(add_self_loops, improved), rowptr_dev=_p(rowptr), num_nodes=N, w_dev=_p(edge_weight),
@@ -1118,24 +1118,85 @@ def _evaluation(sink, y, label_rows, segments):
 
 
 # ---- the drivers: one layer loop per model, over a placement ---------------------------------------------------------
-def _sage_layer(conv, last, act_dtype):
-    """(epilogue, self_scale, fn): fn maps a slab's fp32 / bf16 operand [T, 2K] to the layer's output rows"""
-    W = torch.cat([conv.lin_l.weight, conv.lin_r.weight], dim=1).to(act_dtype)      # [N, 2K] = [W_l | W_r]
-    bias = conv.lin_l.bias
+def _sage_layer(model, place, act_dtype):
+    """SAGE's layers for ``_conv_layers``.  Every recipe returns ``layer(i, last)`` -> (aggregate, wide, fn, classes):
+    ``aggregate(cur, s, ids, T, A, ws, graph)`` fills a slab's operand A [T, wide * K] from the layer's input ``cur``
+    [n, K] through the placement, ``fn`` maps a fixed tile of A to the layer's output rows -- on the last layer the
+    logits, ``classes`` wide"""
+    def layer(i, last):
+        conv = model.convs[i]
+        W = torch.cat([conv.lin_l.weight, conv.lin_r.weight], dim=1).to(act_dtype)      # [N, 2K] = [W_l | W_r]
+        bias = conv.lin_l.bias
+        epilogue = "max_operand" if getattr(conv, "aggr", "mean") == "max" else "operand"
 
-    def fn(A):
-        Z = A @ W.t()
-        if bias is not None:
-            Z = Z + bias.to(Z.dtype)
-        return Z if last else torch.relu_(Z)             # the inter-layer ReLU; dropout is the identity in eval mode
-    return "max_operand" if getattr(conv, "aggr", "mean") == "max" else "operand", 0.0, fn
+        def fn(A):
+            Z = A @ W.t()
+            if bias is not None:
+                Z = Z + bias.to(Z.dtype)
+            return Z if last else torch.relu_(Z)         # the inter-layer ReLU; dropout is the identity in eval mode
+        return (lambda cur, *slab: place.aggregate(i, cur, epilogue, 0.0, *slab)), 2, fn, conv.lin_l.out_features
+    return layer
 
 
-def _gin_layer(conv, amp):
-    def fn(h):
-        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
-            return conv.nn(h)                            # Linear, BatchNorm1d (running statistics), ReLU, Linear, ReLU
-    return "sum", conv._scale(), fn
+def _gin_layer(model, place, act_dtype):
+    amp = act_dtype == torch.bfloat16
+
+    def layer(i, last):
+        conv = model.convs[i]
+        scale = conv._scale()
+
+        def fn(h):
+            with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+                h = conv.nn(h)                           # Linear, BatchNorm1d (running statistics), ReLU, Linear, ReLU
+            if last:                                     # what follows the last conv layer: the logits
+                with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+                    h = model.lin2(torch.relu(model.lin1(h)))
+            return h
+        return (lambda cur, *slab: place.aggregate(i, cur, "sum", scale, *slab)), 1, fn, model.lin2.out_features
+    return layer
+
+
+def _gcn_layer(model, place, act_dtype):
+    """GCN over one resident matrix (f3s), in ``GCNConv.forward``'s order -- aggregate first, project second:
+
+      aggregate  ``spp_graph_agg_weighted_forward`` over each node's whole row of the layer's input, [T, K] in
+                 ``act_dtype``.  ``normalize=False`` (the reference's model): the entries weigh ``edge_weight`` (ones
+                 without), no self term.  ``normalize=True``: PyG's gcn_norm of the whole graph, formed IN the kernel from
+                 ``dinv`` = ``gcn_dinv(rowptr, edge_weight)`` -- fp32 [N], computed once per call and ``fill`` -- with
+                 the self term ``fill * dinv[t]^2``.
+      project    tile @ lin.weight^T (+ bias) over the fixed row tiles
+      tail       every layer but the last: relu(BatchNorm) on the running statistics, under bf16 autocast when
+                 ``act_dtype`` is bf16 (as GIN's ``conv.nn``); dropout is the identity.  The last layer's logits go to
+                 the sink untouched.
+
+    Memory, as arithmetic: two [N, hidden] matrices of ``act_dtype`` at a layer boundary, as for SAGE, plus a slab's
+    [rows_per_slab, K] aggregate and, with ``normalize=True``, ``dinv``: 4 * N bytes (0.44 GB at N = 111 M).  NO [E]
+    array is allocated on either path: the coefficients PyG would materialise are 4 * E bytes (12.8 GB at E = 3.2 G),
+    and so are the ones of a valueless ``adj_t``; a caller's ``edge_weight`` is read in place."""
+    amp = act_dtype == torch.bfloat16
+    dinvs = {}                                           # fill -> dinv [N]: once per call (the convs share one setting)
+
+    def layer(i, last):
+        conv, bn = model.convs[i], model.bns[i]
+        dinv, fill = None, 0
+        if conv.normalize:
+            fill = _gcn_fill(conv.add_self_loops, conv.improved)
+            if fill not in dinvs:
+                dinvs[fill] = gcn_dinv(place.rowptr, place.edge_weight, add_self_loops=conv.add_self_loops,
+                                       improved=conv.improved)
+            dinv = dinvs[fill]
+        Wt = conv.lin.weight.to(act_dtype).t()
+        bias = conv.bias.to(act_dtype) if conv.bias is not None else None
+
+        def fn(tile):
+            Z = torch.addmm(bias, tile, Wt) if bias is not None else tile @ Wt
+            if last:
+                return Z
+            with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+                return torch.relu(bn(Z))                 # (eval mode: the running statistics)
+        return (lambda cur, s, ids, T, A, ws, _graph: place.aggregate_weighted(cur, dinv, fill, s, ids, T, A, ws)), 1, \
+            fn, conv.lin.out_features
+    return layer
 
 
 def _slabs(rows, ids, rows_per_slab):
@@ -1176,41 +1237,34 @@ def _field_plan(field, n_layers):
 
 
 def _conv_layers(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None):
-    """SAGE and GIN, as ``layerwise_inference`` describes them; the last layer's logits go to ``sink``, tile by tile.
-    Resident, layer i-1's matrix is dropped as soon as layer i is complete, so two [N, hidden] matrices are live at a
-    boundary; partitioned, the layers alternate between the (at most two) published buffers.  ``plan``: one ``_Step`` a
-    layer (rows, targets and graph); None is ``_whole_graph_plan``."""
-    from .models import GIN
-    gin, amp = isinstance(model, GIN), act_dtype == torch.bfloat16
+    """SAGE, GIN and GCN (``_sage_layer``, ``_gin_layer``, ``_gcn_layer``: what a layer aggregates and what follows), as
+    ``layerwise_inference`` describes them; the last layer's logits go to ``sink``, tile by tile.  Resident, layer i-1's
+    matrix is dropped as soon as layer i is complete, so two [N, hidden] matrices are live at a boundary; partitioned,
+    the layers alternate between the (at most two) published buffers.  ``plan``: one ``_Step`` a layer (rows, targets
+    and graph); None is ``_whole_graph_plan``."""
+    recipe = _gin_layer if isinstance(model, GIN) else _gcn_layer if isinstance(model, GCN) else _sage_layer
+    layer = recipe(model, place, act_dtype)
     n_layers, dev = len(model.convs), place.dev
     plan = plan or _whole_graph_plan(place, nodes, n_layers)
     place.open(min(2, n_layers - 1), model.hidden_channels, act_dtype)
     ws = torch.empty(graph_agg_workspace_bytes(min(rows_per_slab, max([place.n_local] + [st.rows for st in plan]))),
                      dtype=torch.uint8, device=dev)
-
-    def head(h):                                         # what follows the last conv layer: the logits
-        if gin:
-            with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
-                h = model.lin2(torch.relu(model.lin1(h)))
-        return h
-
     cur = place.x
-    for i, conv in enumerate(model.convs):
+    for i, step in enumerate(plan):
         last = i == n_layers - 1
-        epilogue, scale, fn = _gin_layer(conv, amp) if gin else _sage_layer(conv, last, act_dtype)
-        step = plan[i]
+        aggregate, wide, fn, classes = layer(i, last)
         rows, names = step.rows, step.names
         nxt = None
         if last:
-            sink.open(place, rows, (model.lin2 if gin else conv.lin_l).out_features)
+            sink.open(place, rows, classes)
         for s, T, tids in _slabs(rows, step.ids, rows_per_slab):
-            A = torch.empty((T, cur.size(1) * (2 if epilogue in _WIDE_EPILOGUES else 1)), dtype=act_dtype, device=dev)
-            place.aggregate(i, cur, epilogue, scale, s, tids, T, A, ws, step.graph)
+            A = torch.empty((T, cur.size(1) * wide), dtype=act_dtype, device=dev)
+            aggregate(cur, s, tids, T, A, ws, step.graph)
             for r, n, tile in _row_tiles(A):
-                if last:
-                    sink.put(s + r, n, head(fn(tile)), names[s + r:s + r + n] if names is not None else None)
-                    continue
                 h = fn(tile)
+                if last:
+                    sink.put(s + r, n, h, names[s + r:s + r + n] if names is not None else None)
+                    continue
                 if nxt is None:
                     nxt = place.layer_rows(i, last, rows, h.size(1), act_dtype)
                 nxt[s + r:s + r + n] = h[:n]
@@ -1449,72 +1503,12 @@ def _resinc_layers(model, place, nodes, rows_per_slab, act_dtype, sink):
     return sink.result()
 
 
-def _gcn_layers(model, place, nodes, rows_per_slab, act_dtype, sink):
-    """GCN over one resident matrix (f3s), in ``GCNConv.forward``'s order -- aggregate first, project second.  Per layer,
-    slab by slab:
-
-      aggregate  ``spp_graph_agg_weighted_forward`` over each node's whole row of the layer's input, [T, K] in
-                 ``act_dtype``.  ``normalize=False`` (the reference's model): the entries weigh ``edge_weight`` (ones
-                 without), no self term.  ``normalize=True``: PyG's gcn_norm of the whole graph, formed IN the kernel from
-                 ``dinv`` = ``gcn_dinv(rowptr, edge_weight)`` -- fp32 [N], computed once per call and ``fill`` -- with
-                 the self term ``fill * dinv[t]^2``.
-      project    tile @ lin.weight^T (+ bias) over the fixed row tiles
-      tail       every layer but the last: relu(BatchNorm) on the running statistics, under bf16 autocast when
-                 ``act_dtype`` is bf16 (as GIN's ``conv.nn``); dropout is the identity.  The last layer's logits go to
-                 ``sink`` tile by tile.
-
-    Memory, as arithmetic: two [N, hidden] matrices of ``act_dtype`` at a layer boundary, as for SAGE, plus a slab's
-    [rows_per_slab, K] aggregate and, with ``normalize=True``, ``dinv``: 4 * N bytes (0.44 GB at N = 111 M).  NO [E]
-    array is allocated on either path: the coefficients PyG would materialise are 4 * E bytes (12.8 GB at E = 3.2 G),
-    and so are the ones of a valueless ``adj_t``; a caller's ``edge_weight`` is read in place."""
-    from .models import _gcn_fill
-    amp = act_dtype == torch.bfloat16
-    n_layers, dev = len(model.convs), place.dev
-    plan = _whole_graph_plan(place, nodes, n_layers)
-    ws = torch.empty(graph_agg_workspace_bytes(min(rows_per_slab, max([place.n_local] + [st.rows for st in plan]))),
-                     dtype=torch.uint8, device=dev)
-    dinvs = {}                                           # fill -> dinv [N]: once per call (the convs share one setting)
-    cur = place.x
-    for i, conv in enumerate(model.convs):
-        last = i == n_layers - 1
-        dinv, fill = None, 0
-        if conv.normalize:
-            fill = _gcn_fill(conv.add_self_loops, conv.improved)
-            if fill not in dinvs:
-                dinvs[fill] = gcn_dinv(place.rowptr, place.edge_weight, add_self_loops=conv.add_self_loops,
-                                       improved=conv.improved)
-            dinv = dinvs[fill]
-        Wt = conv.lin.weight.to(act_dtype).t()
-        bias = conv.bias.to(act_dtype) if conv.bias is not None else None
-        bn = model.bns[i]
-        step = plan[i]
-        rows, names = step.rows, step.names
-        nxt = None
-        if last:
-            sink.open(place, rows, conv.lin.out_features)
-        for s, T, tids in _slabs(rows, step.ids, rows_per_slab):
-            A = torch.empty((T, cur.size(1)), dtype=act_dtype, device=dev)
-            place.aggregate_weighted(cur, dinv, fill, s, tids, T, A, ws)
-            for r, n, tile in _row_tiles(A):
-                Z = torch.addmm(bias, tile, Wt) if bias is not None else tile @ Wt
-                if last:
-                    sink.put(s + r, n, Z, names[s + r:s + r + n] if names is not None else None)
-                    continue
-                with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
-                    h = torch.relu(bn(Z))                # (eval mode: the running statistics)
-                if nxt is None:
-                    nxt = place.layer_rows(i, last, rows, h.size(1), act_dtype)
-                nxt[s + r:s + r + n] = h[:n]
-        if nxt is None and not last:                     # no rows at all
-            nxt = place.layer_rows(i, last, 0, model.hidden_channels, act_dtype)
-        cur = nxt                                        # (drops layer i-1's matrix)
-        place.boundary()
-    return sink.result()
-
-
-_GATV2_ENTRIES = ("a GATv2 model is scored over one resident fp16 / fp32 / bf16 matrix by inference.gatv2_inference "
-                  "(log-probabilities) and inference.evaluate (predictions, accuracy, loss); layerwise_inference, an "
-                  "Fp8Table input, the field entries and the partitioned entries are not built for GATv2")
+_PARTITIONED_MODELS = (SAGE, GIN, GAT, SAGEResInception)    # what an entry admits, in the order its refusal names them
+_RESIDENT_MODELS = _PARTITIONED_MODELS + (GCN, GATv2)
+_FIELD_MODELS = (SAGE, GIN, GAT)
+_GATV2_RESIDENT = ("a GATv2 model is scored over one resident fp16 / fp32 / bf16 matrix by inference.layerwise_inference "
+                   "(gatv2_inference is the same call) and inference.evaluate; an Fp8Table input, the field entries and "
+                   "the partitioned entries are not built for GATv2")
 
 
 def _check_gatv2(model, what):
@@ -1534,18 +1528,17 @@ def _check_gatv2(model, what):
                                       f"two), above the kernels' {_GATV2_MAX_D} (heads = {H} is not the limit that was hit)")
 
 
-def _check_model(model, what, names, gcn=False, gatv2=False):
-    """one of the four models -- or, for the resident whole-graph entries, GCN (``gcn``) or GATv2 (``gatv2``) -- with
-    what the GAT, GATv2 and SAGEResInception drivers need of its layers (SAGE, GIN and GCN: nothing)"""
-    from .models import GAT, GATv2, GCN, GIN, SAGE, SAGEResInception
-    if gcn and isinstance(model, GCN):
-        return
+def _check_model(model, what, admits):
+    """one of the model classes the entry admits, with what the GAT, GATv2 and SAGEResInception drivers need of its
+    layers (SAGE, GIN and GCN: nothing)"""
+    if not isinstance(model, admits):
+        if isinstance(model, GATv2):
+            raise NotImplementedError(f"{what}: not built for GATv2: {_GATV2_RESIDENT}")
+        names = [c.__name__ for c in admits]
+        raise NotImplementedError(f"{what}: implemented for {', '.join(names[:-1])} and {names[-1]}, not "
+                                  f"{type(model).__name__}")
     if isinstance(model, GATv2):
-        if not gatv2:
-            raise NotImplementedError(f"{what}: not built for GATv2: {_GATV2_ENTRIES}")
-        return _check_gatv2(model, what)
-    if not isinstance(model, (SAGE, GIN, GAT, SAGEResInception)):
-        raise NotImplementedError(f"{what}: implemented for {names}, not {type(model).__name__}")
+        _check_gatv2(model, what)
     if isinstance(model, SAGEResInception):
         _resinc_head(model)
     if isinstance(model, GAT):                                # the layers as models.GAT builds them
@@ -1571,9 +1564,8 @@ def _check_run(what, act_dtype, rows_per_slab, nodes):
 def _score(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None):
     """the frame of every driver: eval mode (restored), no gradient, autocast off, the table's device current; a rank
     that fails aborts the placement, so that its peers raise instead of waiting, and every mapping is closed"""
-    from .models import GAT, GATv2, GCN, SAGEResInception
     layers = _gat_layers if isinstance(model, GAT) else _resinc_layers if isinstance(model, SAGEResInception) \
-        else _gcn_layers if isinstance(model, GCN) else _gatv2_layers if isinstance(model, GATv2) else _conv_layers
+        else _gatv2_layers if isinstance(model, GATv2) else _conv_layers
     was_training = model.training
     model.eval()
     try:
@@ -1593,10 +1585,12 @@ def _score(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None):
 def layerwise_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 << 20, act_dtype=torch.float32,
                         edge_weight=None):
     """Exact log-probabilities of every node, [N, classes] fp32 -- or of ``nodes`` (int64, any order, duplicates
-    allowed), [len(nodes), classes] -- for a ``SAGE``, ``GIN``, ``GAT``, ``SAGEResInception`` or ``GCN`` model over the
-    whole graph.  (GAT, at any ``heads``: see ``_gat_layers`` for its order of operations and memory; SAGEResInception:
-    ``_resinc_layers``; GCN: ``_gcn_layers``; what follows describes SAGE and GIN, ``_conv_layers``, and the arguments,
-    the fixed GEMM tiles, eval mode and ``nodes`` mean the same for all five.)
+    allowed), [len(nodes), classes] -- for a ``SAGE``, ``GIN``, ``GAT``, ``SAGEResInception``, ``GCN`` or ``GATv2`` model
+    over the whole graph; every model's ``.inference`` is this call.  Each driver's docstring has its order of operations
+    and its memory: ``_conv_layers`` (SAGE, GIN and, through ``_gcn_layer``, GCN), ``_gat_layers`` (GAT at any ``heads``),
+    ``_gatv2_layers`` (GATv2: heads in {1, 2, 4, 8}, heads * padded channels <= 1024, one resident matrix and no
+    ``Fp8Table``) and ``_resinc_layers`` (SAGEResInception).  What follows describes SAGE and GIN; the arguments, the
+    fixed GEMM tiles, eval mode and ``nodes`` mean the same for all six.
 
     ``edge_weight`` (GCN only; a ``ValueError`` with any other model): contiguous fp32 [E], one value per entry of
     ``col`` -- what ``adj_t`` carries in training; None: every entry weighs 1.  GCN reads one resident fp16 / fp32 / bf16
@@ -1613,8 +1607,8 @@ def layerwise_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 <<
     GIN's head and the log_softmax are computed for those nodes only.  The model is put in eval mode and its mode
     restored; nothing records a gradient.  ``x``: a CUDA fp16 / fp32 / bf16 matrix, one row per node, possibly a strided
     view of the resident table (``FastSampler.resident_graph()``) -- or an ``Fp8Table``, read in place with the bits of
-    the same call on its fp32 dequantisation (all four models; ``evaluate`` and the field entries too).  Nothing waits for the device but the range check of
-    ``nodes``, up front.
+    the same call on its fp32 dequantisation (SAGE, GIN, GAT and SAGEResInception; ``evaluate`` and the field entries
+    too).  Nothing waits for the device but the range check of ``nodes``, up front.
 
     Memory, as arithmetic: an activation matrix is N * hidden * sizeof(act_dtype) bytes and two are live at a layer
     boundary (layer i-1's is freed as soon as layer i is complete).  At N = 111 M and hidden 256 that is 113 GB each in
@@ -1632,11 +1626,9 @@ def _check_labels(what, name, y, rows):
                          f"{tuple(y.shape)} {y.dtype}")
 
 
-def _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, y, sink, edge_weight=None, gatv2=False):
-    """the resident entries: every argument check, then the device, then the pass into ``sink``.  ``gatv2``: the entry
-    admits a GATv2 model (``gatv2_inference``, ``evaluate``)"""
-    from .models import GATv2, GCN
-    _check_model(model, what, "SAGE and GIN (and GAT, SAGEResInception, GCN)", gcn=True, gatv2=gatv2)
+def _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, y, sink, edge_weight=None):
+    """the resident entries: every argument check, then the device, then the pass into ``sink``"""
+    _check_model(model, what, _RESIDENT_MODELS)
     gcn = isinstance(model, GCN)
     if edge_weight is not None and not gcn:
         raise ValueError(f"{what}: edge_weight is GCN's (the values its adj_t carries in training); "
@@ -1646,7 +1638,7 @@ def _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, y, s
             raise NotImplementedError(f"{what}: GCN over a row-partitioned x ({type(x).__name__}); {_WEIGHTS_NOT_BUILT}")
         _check_matrix(x, what, fp8_reason=f"GCN: {_WEIGHTS_NOT_BUILT}")
     elif isinstance(model, GATv2):
-        _check_matrix(x, what, fp8_reason=f"GATv2: {_GATV2_ENTRIES}")
+        _check_matrix(x, what, fp8_reason=f"GATv2: {_GATV2_RESIDENT}")
     else:
         _check_table(x, what)
     N = x.size(0)
@@ -1704,31 +1696,20 @@ def evaluate(model, x, rowptr, col, y=None, *, nodes=None, splits=None, rows_per
     ``pred`` and ``nll`` are the same bits whatever ``rows_per_slab`` is and whether ``nodes`` selected it; ``pred[i]`` is
     the argmax of the logits, so ``layerwise_inference``'s row attains its maximum there.  The counts are reduced on the
     device and read back once, at the end.  ``edge_weight``: GCN's entry weights, as ``layerwise_inference`` takes them.
-    A ``GATv2`` model is accepted too (one resident matrix, no ``Fp8Table``): ``gatv2_inference``'s pass, this tail."""
+    The six models of ``layerwise_inference``, each through the driver named there."""
     what = "evaluate"
     nodes, segments = _check_splits(what, splits, nodes)
-    sink = _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, y, _Classify(y), edge_weight,
-                     gatv2=True)
+    sink = _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, y, _Classify(y), edge_weight)
     return _evaluation(sink, y, None if nodes is None else nodes.to(x.device), segments)
 
 
 def gatv2_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 << 20, act_dtype=torch.float32):
-    """Exact log-probabilities of every node, [N, classes] fp32 -- or of ``nodes`` (int64, any order, duplicates
-    allowed), [len(nodes), classes] -- for a ``models.GATv2`` model over the whole graph: ``layerwise_inference``'s
-    contract (arguments, fixed GEMM tiles, eval mode restored, no gradient, nothing waits for the device but the range
-    check of ``nodes``) with GATv2's own layer loop, ``_gatv2_layers``: both projections as torch GEMMs, then
-    ``spp_graph_gatv2_forward`` (csrc/graph_gatv2.hip) over each node's whole neighbour row.  A node's result is the same
-    bits whatever ``rows_per_slab`` is and whether ``nodes`` selected it.  ``x``: one resident CUDA fp16 / fp32 / bf16
-    matrix, one row per node.  Heads in {1, 2, 4, 8}; any number of channels per head and classes with heads * Cp <= 1024
-    (Cp: the channels padded as ``_gatv2_layers`` describes, where its memory arithmetic is too).  ``evaluate`` runs the
-    same pass into predictions and losses.  (``layerwise_inference`` itself keeps refusing the model; see DESIGN
-    section 8.)"""
-    from .models import GATv2
+    """``layerwise_inference`` under the name GATv2's entry had first: the same call, for a ``models.GATv2`` model only"""
     what = "gatv2_inference"
     if not isinstance(model, GATv2):
         raise NotImplementedError(f"{what}: implemented for GATv2, not {type(model).__name__} (the other models: "
                                   "layerwise_inference)")
-    return _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, None, _LogProbs(), gatv2=True)
+    return _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, None, _LogProbs())
 
 
 # ---- f3n: a few nodes scored exactly over their receptive field only -------------------------------------------------
@@ -1892,7 +1873,6 @@ def receptive_field(rowptr, col, nodes, hops):
 
 def _classes(model):
     """the width of the model's logits"""
-    from .models import GAT, GIN
     return model.lin2.out_features if isinstance(model, GIN) else model.convs[-1].out_channels if isinstance(model, GAT) \
         else model.convs[-1].lin_l.out_features
 
@@ -1900,12 +1880,11 @@ def _classes(model):
 def _field_score(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, fields, y, sink):
     """the field entries: every argument check, then the device, then the field of ``nodes`` and the pass over it into
     ``sink``.  Returns (nodes on x's device, each node's row of the sink or None without nodes)."""
-    from .models import SAGEResInception
-    _check_model(model, what, "SAGE, GIN and GAT")
     if isinstance(model, SAGEResInception):
         raise NotImplementedError(f"{what}: SAGEResInception is not scored over a receptive field: its head accumulates a "
                                   "block of every layer for the scored nodes, and the field's layers have different row "
                                   "counts in slot order; layerwise_inference(nodes=...) scores it")
+    _check_model(model, what, _FIELD_MODELS)
     if isinstance(x, (list, tuple, P2PPeers)):
         raise NotImplementedError(f"{what}: a row-partitioned table is not scored over a receptive field (layer 0 reads "
                                   "one resident matrix in place and the field's layers live on one device); "
@@ -2053,11 +2032,11 @@ class IpcPeers:
         pass
 
 
-def _partitioned(what, names, model, x_local, rowptr, col, part_offsets, rank, peers, nodes, rows_per_slab, act_dtype,
+def _partitioned(what, model, x_local, rowptr, col, part_offsets, rank, peers, nodes, rows_per_slab, act_dtype,
                  y_local=None, sink=None):
-    """the partitioned entries behind their model filters.  Every argument and model-shape check comes before ``peers``
+    """the partitioned entries.  Every argument and model-shape check comes before ``peers``
     is touched, and the device is required last: a refused call publishes nothing and waits for nobody."""
-    _check_model(model, what, names)
+    _check_model(model, what, _PARTITIONED_MODELS)
     _refuse_max_over_parts(what, model)
     _check_matrix(x_local, what, "x_local", "the partitioned drivers do not carry fp8 partitions through peers.share yet "
                   "(graph_aggregate_parts reads them); dequantise the partition, or score the table on one device")
@@ -2119,8 +2098,8 @@ def partitioned_inference(model, x_local, rowptr, col, *, part_offsets, rank, pe
     (``cur`` while a layer projects, ``nxt`` while it attends), 7.1 GB; the last layer's [n_local, 172] fp32 result,
     9.5 GB; 3.6 GB of table and the rank's copy of the 26 GB graph: about 47 GB at the peak, against 168 GB on one
     device."""
-    return _partitioned("partitioned_inference", "SAGE, GIN, GAT and SAGEResInception", model, x_local, rowptr, col,
-                        part_offsets, rank, peers, nodes, rows_per_slab, act_dtype)
+    return _partitioned("partitioned_inference", model, x_local, rowptr, col, part_offsets, rank, peers, nodes,
+                        rows_per_slab, act_dtype)
 
 
 def partitioned_evaluate(model, x_local, rowptr, col, y_local=None, *, part_offsets, rank, peers, nodes=None,
@@ -2132,22 +2111,14 @@ def partitioned_evaluate(model, x_local, rowptr, col, y_local=None, *, part_offs
     ``y_local``: int64 [n_local] on x_local's device, the rank's labels by LOCAL id (-1: unlabelled).  ``labelled``,
     ``correct`` and ``loss`` cover the rank's rows: the caller adds the counts (and ``loss * labelled``) across ranks."""
     what = "partitioned_evaluate"
-    sink = _partitioned(what, "SAGE, GIN, GAT and SAGEResInception", model, x_local, rowptr, col, part_offsets, rank,
-                        peers, nodes, rows_per_slab, act_dtype, y_local, _Classify(y_local))
+    sink = _partitioned(what, model, x_local, rowptr, col, part_offsets, rank, peers, nodes, rows_per_slab, act_dtype,
+                        y_local, _Classify(y_local))
     lo = sink.place.lo
     return _evaluation(sink, y_local, None if nodes is None else nodes.to(x_local.device) - lo, {})
 
 
 def partitioned_layerwise_inference(model, x_local, rowptr, col, *, part_offsets, rank, peers, nodes=None,
                                     rows_per_slab=1 << 20, act_dtype=torch.float32):
-    """``partitioned_inference`` for SAGE and GIN only, the entry that came first: GAT and SAGEResInception are refused
-    here and scored there; everything else is that entry's."""
-    from .models import GAT, SAGEResInception
-    what = "partitioned_layerwise_inference"
-    if isinstance(model, (GAT, SAGEResInception)):
-        raise NotImplementedError(f"{what}: {type(model).__name__} over a partitioned table is not scored by this entry "
-                                  "(its layers need the long-row softmax / the fused layer tail over parts); SAGE and GIN "
-                                  "are.  partitioned_inference scores all four models")
-    _refuse_max_over_parts(what, model)
-    return _partitioned(what, "SAGE and GIN", model, x_local, rowptr, col, part_offsets, rank, peers, nodes,
+    """``partitioned_inference`` under the name the entry had first: the same call, its own name in the errors"""
+    return _partitioned("partitioned_layerwise_inference", model, x_local, rowptr, col, part_offsets, rank, peers, nodes,
                         rows_per_slab, act_dtype)

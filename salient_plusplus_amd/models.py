@@ -1151,11 +1151,11 @@ class GAT(torch.nn.Module):
                 x = relu_dropout(x, 0.5, self.training)
         return torch.log_softmax(x, dim=-1)
 
+    @torch.no_grad()
     def inference(self, x_all, rowptr, col, **kw):
-        raise NotImplementedError("GAT.inference: not a method of the model yet; the long-row softmax that layer-wise "
-                                  "inference over whole neighbour rows needs (attention over 10^5 entries of a hub) is "
-                                  "spp_graph_gat_forward: call inference.layerwise_inference(model, x_all, rowptr, col, "
-                                  "...), which accepts GAT at any heads")
+        """as ``SAGE.inference``: ``inference.layerwise_inference`` (the long-row softmax of ``_gat_layers``)"""
+        from .inference import layerwise_inference
+        return layerwise_inference(self, x_all, rowptr, col, **kw)
 
 
 # --------------------------------------------------------------------------------------------
@@ -1371,11 +1371,11 @@ class GATv2(torch.nn.Module):
                 x = relu_dropout(x, 0.5, self.training)
         return torch.log_softmax(x, dim=-1)
 
+    @torch.no_grad()
     def inference(self, x_all, rowptr, col, **kw):
-        raise NotImplementedError("GATv2.inference: not a method of the model yet; exact layer-wise scoring over whole "
-                                  "neighbour rows runs on the long-row GATv2 softmax of spp_graph_gatv2_forward: call "
-                                  "inference.gatv2_inference(model, x_all, rowptr, col, ...) for log-probabilities or "
-                                  "inference.evaluate(model, x_all, rowptr, col, y, ...) for predictions and losses")
+        """as ``SAGE.inference``: ``inference.layerwise_inference`` (``_gatv2_layers``)"""
+        from .inference import layerwise_inference
+        return layerwise_inference(self, x_all, rowptr, col, **kw)
 
 
 # --------------------------------------------------------------------------------------------
@@ -1823,11 +1823,11 @@ class GCN(torch.nn.Module):
                     x = F.dropout(F.relu(self.bns[i](x)), p=0.5, training=self.training)
         return torch.log_softmax(x, dim=-1)
 
+    @torch.no_grad()
     def inference(self, x_all, rowptr, col, **kw):
-        raise NotImplementedError("GCN.inference: not a method of the model yet; the weighted sum over whole neighbour "
-                                  "rows that layer-wise inference needs is spp_graph_agg_weighted_forward: call "
-                                  "inference.layerwise_inference(model, x_all, rowptr, col, edge_weight=..., ...) or "
-                                  "inference.evaluate, which accept GCN on a resident table")
+        """as ``SAGE.inference``: ``inference.layerwise_inference`` (keyword ``edge_weight``: what ``adj_t`` carries in training)"""
+        from .inference import layerwise_inference
+        return layerwise_inference(self, x_all, rowptr, col, **kw)
 
 
 # --------------------------------------------------------------------------------------------
@@ -1921,22 +1921,22 @@ class SAGEResInception(torch.nn.Module):
             collect.append(x[:end_size])
         return torch.log_softmax(self.mlp(torch.cat(collect, -1)), dim=-1)
 
+    @torch.no_grad()
     def inference(self, x_all, rowptr, col, **kw):
-        raise NotImplementedError("SAGEResInception.inference: not a method of the model yet; the head concatenates "
-                                  "every layer's activations, which a layer-wise pass replaces by a running "
-                                  "accumulator of the head's first Linear: call inference.layerwise_inference(model, "
-                                  "x_all, rowptr, col, ...), which accepts SAGEResInception")
+        """as ``SAGE.inference``: ``inference.layerwise_inference`` (the head as a running accumulator: ``_resinc_layers``)"""
+        from .inference import layerwise_inference
+        return layerwise_inference(self, x_all, rowptr, col, **kw)
 
 
 _UNSUPPORTED_MODELS = {"sageclassic": "not used in the paper", "jknet": "not used in the paper",
-                       "gcn": "not used in the paper", "arma": "broken in the reference"}
+                       "arma": "broken in the reference"}
 
 
 def get_model_type(model_name):
-    """driver/main.py:74-95 for the four models the reference marks as working (names case-insensitive), and "gatv2"
-    (GATv2, which the reference does not have)"""
+    """driver/main.py:74-95 for the four models the reference marks as working (names case-insensitive), "gcn" (GCN,
+    which the reference leaves unused) and "gatv2" (GATv2, which the reference does not have)"""
     name = model_name.lower()
-    models = {"sage": SAGE, "gat": GAT, "gin": GIN, "sageresinception": SAGEResInception, "gatv2": GATv2}
+    models = {"sage": SAGE, "gat": GAT, "gin": GIN, "sageresinception": SAGEResInception, "gcn": GCN, "gatv2": GATv2}
     if name in models:
         return models[name]
     if name in _UNSUPPORTED_MODELS:

@@ -322,12 +322,12 @@ def test_gcn_state_dict_is_the_reference_tree():
     assert sorted(GCNConv(4, 6).state_dict()) == ["bias", "lin.weight"]          # PyG's names
 
 
-def test_get_model_type_still_refuses_gcn():
-    from salient_plusplus_amd.models import get_model_type
-    with pytest.raises(NotImplementedError):
-        get_model_type("gcn")
-    with pytest.raises(NotImplementedError):
-        get_model_type("GCN")
+def test_get_model_type_resolves_gcn():
+    from salient_plusplus_amd.models import GCN, _UNSUPPORTED_MODELS, get_model_type
+    assert get_model_type("gcn") is GCN and get_model_type("GCN") is GCN and get_model_type("Gcn") is GCN
+    assert "gcn" not in _UNSUPPORTED_MODELS
+    m = get_model_type("gcn")(128, 256, 47, 3)               # built as the reference's: no bias, no normalisation
+    assert all(c.bias is None and not c.normalize for c in m.convs)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16, torch.float64])
@@ -491,5 +491,7 @@ def test_cpu_gcn_forward_is_the_dense_formula(normalize):
         got = model(x, adjs)
         assert got.shape == (3, 3) and got.dtype == torch.float32
         torch.testing.assert_close(got.double(), want, rtol=1e-4, atol=1e-5)
-    with pytest.raises(NotImplementedError, match="GCN.inference"):
-        model.inference(x, None, None)
+    from inference_method import assert_method_is_the_function
+    rowptr = torch.arange(15, dtype=torch.int64)             # 14 nodes of one entry each
+    assert_method_is_the_function(model, x, rowptr, torch.arange(14), edge_weight=torch.ones(14))
+    assert not model.training

@@ -196,17 +196,21 @@ def test_layerwise_inference_of_gat_validates_before_the_device(no_device):
     biased.convs[0] = GATConv(4, 4, bias=True)
     with pytest.raises(NotImplementedError, match="bias=False"):
         layerwise_inference(biased, x, rowptr, col)
-    with pytest.raises(NotImplementedError, match="SAGE and GIN"):
+    with pytest.raises(NotImplementedError, match="^layerwise_inference: implemented for SAGE, GIN, GAT, SAGEResInception, GCN and GATv2, not Linear$"):
         layerwise_inference(torch.nn.Linear(4, 2), x, rowptr, col)
 
 
-def test_valid_gat_arguments_need_the_device_and_the_method_still_points_there():
+def test_valid_gat_arguments_need_the_device_and_the_method_is_the_function():
+    from inference_method import assert_method_is_the_function
     from salient_plusplus_amd.inference import layerwise_inference
-    from salient_plusplus_amd.models import GAT
+    from salient_plusplus_amd.models import GAT, GATConv
     x, _a, _b, rowptr, col = _tiny()
-    with pytest.raises(NotImplementedError, match="long-row softmax") as info:
-        GAT(4, 4, 2, 2).inference(x, rowptr, col)
-    assert "layerwise_inference" in str(info.value)
+    for heads in (1, 2, 4):
+        assert_method_is_the_function(GAT(4, 4, 2, 2, heads=heads), x, rowptr, col)
+    biased = GAT(4, 4, 2, 2)
+    biased.convs[0] = GATConv(4, 4, bias=True)
+    with pytest.raises(NotImplementedError, match="^layerwise_inference: GAT layers need bias=False"):
+        biased.inference(x, rowptr, col)
     if not torch.cuda.is_available():                         # no CPU fallback: valid arguments need the device
         from salient_plusplus_amd import _native as nat
         model = GAT(4, 4, 2, 2, heads=2)

@@ -151,9 +151,9 @@ def test_get_model_type_and_the_inference_refusals():
     from salient_plusplus_amd import inference, models
     assert models.get_model_type("gatv2") is models.GATv2 and models.get_model_type("GATv2") is models.GATv2
     for name, cls in (("sage", models.SAGE), ("gat", models.GAT), ("gin", models.GIN),
-                      ("sageresinception", models.SAGEResInception)):
+                      ("sageresinception", models.SAGEResInception), ("gcn", models.GCN)):
         assert models.get_model_type(name) is cls
-    for name in ("sageclassic", "jknet", "gcn", "arma"):
+    for name in ("sageclassic", "jknet", "arma"):
         with pytest.raises(NotImplementedError):
             models.get_model_type(name)
     with pytest.raises(ValueError):
@@ -162,10 +162,10 @@ def test_get_model_type_and_the_inference_refusals():
     assert [(c.heads, c.out_channels, c.concat, c.bias is None) for c in model.convs] == \
         [(4, 8, True, True), (4, 8, True, True), (4, 5, False, True)]
     x, rowptr, col = torch.zeros(4, 16), torch.zeros(5, dtype=torch.int64), torch.zeros(0, dtype=torch.int64)
-    with pytest.raises(NotImplementedError, match="GATv2.inference"):
-        model.inference(x, rowptr, col)
-    with pytest.raises(NotImplementedError, match="GATv2"):
-        inference.layerwise_inference(model, x, rowptr, col)
+    from inference_method import assert_method_is_the_function
+    assert_method_is_the_function(model, x, rowptr, col)     # the method is layerwise_inference, which takes the model
+    with pytest.raises(NotImplementedError, match=r"^layerwise_inference: layer 0 has heads = 3"):
+        models.GATv2(16, 36, 5, 2, heads=3).inference(x, rowptr, col)
 
 
 # ------------------------------------------------------------------------------------------------ the restatement

@@ -320,3 +320,38 @@ def test_smallest_shapes():
         x.grad = None
         coef, self_coef = gcn_norm(rp, none, T)
         assert coef.shape == (0,) and self_coef.tolist() == [1.0] * T
+
+
+@pytest.mark.parametrize("normalize", [False, True], ids=["plain", "normalize"])
+def test_get_model_type_gcn_builds_a_model_that_takes_a_training_step(normalize):
+    """the name resolves to ``models.GCN``; the class it returns trains on a two-hop MFG of this file's hops (outermost
+    first: 70 sources -> 70 targets -> 20 targets) with their weights' magnitudes as ``adj_t``'s values"""
+    import torch.nn.functional as F
+    from salient_plusplus_amd.fast_trainer.monkeypatch import Adj, SparseTensor
+    from salient_plusplus_amd.models import GCN, get_model_type
+    cls = get_model_type("gcn")
+    assert cls is GCN and get_model_type("GCN") is GCN
+    adjs = []
+    for T, S in ((70, 70), (20, 70)):
+        rowptr, col, w, _sw = hop(T, S)
+        m = SparseTensor(rowptr=rowptr.cuda(), row=None, col=col.cuda(), value=w.abs().cuda(), sparse_sizes=(T, S),
+                         is_sorted=True, trust_data=True)
+        adjs.append(Adj(m, None, (S, T)))
+    torch.manual_seed(3)
+    model = cls(64, 32, 5, 2, normalize=normalize).cuda().train()
+    opt = torch.optim.SGD(model.parameters(), lr=0.1)
+    x = values(64, 70, torch.float16).cuda()
+    y = torch.randint(0, 5, (20,), generator=torch.Generator().manual_seed(2)).cuda()
+    before = [p.detach().clone() for p in model.parameters()]
+    out = model(x, adjs)
+    assert out.shape == (20, 5) and out.dtype == torch.float32
+    loss = F.nll_loss(out, y)
+    loss.backward()
+    opt.step()
+    assert bool(torch.isfinite(loss))
+    for i, conv in enumerate(model.convs):
+        g = conv.lin.weight.grad
+        assert g is not None and bool(torch.isfinite(g).all()) and float(g.abs().max()) > 0, i
+    moved = [not torch.equal(a, p.detach()) for a, p in zip(before, model.parameters())]
+    assert any(moved) and all(bool(torch.isfinite(p).all()) for p in model.parameters())
+    assert int(model.bns[0].num_batches_tracked) == 1

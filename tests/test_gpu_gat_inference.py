@@ -276,6 +276,18 @@ def test_gat_inference_matches_the_forward_over_full_hops(heads, layers, hidden,
         layerwise_inference(model, x, rowptr, col, nodes=torch.tensor([0, N]))
 
 
+@pytest.mark.parametrize("act_dtype", OUT_DTYPES, ids=_name)
+@pytest.mark.parametrize("heads,layers,hidden", [(1, 3, 16), (4, 2, 16)])
+def test_the_model_method_is_the_function(heads, layers, hidden, act_dtype):
+    from inference_method import assert_method_equals_function
+    rowptr, col = _graph()
+    g = torch.Generator().manual_seed(1)
+    nodes = torch.cat([torch.randperm(N, generator=g)[:70], torch.tensor([N - 1, 300, 300, 0, 11, EMPTY_CHUNK_ROW, DEG0])])
+    model = _model(heads, layers, hidden).train()
+    sub = assert_method_equals_function(model, _features(), rowptr, col, nodes, act_dtype)
+    assert sub.shape == (nodes.numel(), CLASSES)
+
+
 def test_gat_inference_through_the_sampler_resident_graph():
     from salient_plusplus_amd import fast_sampler as fs
     from salient_plusplus_amd.fast_trainer.samplers import FastSampler, FastSamplerConfig

@@ -188,6 +188,24 @@ def test_shapes_the_kernels_do_not_take_are_refused_with_the_arithmetic():
             entry(GATv2(FIN, 36, 5, 2, heads=3).cuda(), x, rowptr, col)
         with pytest.raises(NotImplementedError, match=r"8 \* 256 = 2048"):
             entry(GATv2(FIN, 32, 172, 2, heads=8).cuda(), x, rowptr, col)
-    from salient_plusplus_amd.inference import layerwise_inference
-    with pytest.raises(NotImplementedError, match="gatv2_inference"):
-        layerwise_inference(_model(1, 5, False), x, rowptr, col)
+    with pytest.raises(NotImplementedError, match=r"^layerwise_inference: layer 0 has heads = 3"):
+        GATv2(FIN, 36, 5, 2, heads=3).cuda().inference(x, rowptr, col)
+
+
+@pytest.mark.parametrize("act_dtype", [torch.float32, torch.bfloat16], ids=_name)
+@pytest.mark.parametrize("H,classes,share", [(4, 5, False), (4, 8, True), (1, 5, False)])
+def test_the_method_and_both_entries_return_the_same_bits(H, classes, share, act_dtype):
+    """``layerwise_inference`` takes the model, ``gatv2_inference`` is that call and ``GATv2.inference`` is too"""
+    from inference_method import assert_method_equals_function
+    from salient_plusplus_amd.inference import gatv2_inference, layerwise_inference
+    rowptr, col = _graph()
+    x = _features()
+    model = _model(H, classes, share).train()
+    g = torch.Generator().manual_seed(1)
+    nodes = torch.cat([torch.randperm(N, generator=g)[:70], torch.tensor([N - 1, HUB, HUB, 0, 3, HUB])])
+    sub = assert_method_equals_function(model, x, rowptr, col, nodes, act_dtype)
+    assert sub.shape == (nodes.numel(), classes)
+    for kw in (dict(), dict(nodes=nodes), dict(rows_per_slab=64), dict(nodes=nodes, rows_per_slab=64)):
+        assert torch.equal(layerwise_inference(model, x, rowptr, col, act_dtype=act_dtype, **kw),
+                           gatv2_inference(model, x, rowptr, col, act_dtype=act_dtype, **kw)), sorted(kw)
+    assert model.training

@@ -241,3 +241,17 @@ def test_bf16_activations_stay_inside_the_propagated_bound(normalize, weighted):
     assert bool((err <= bound).all())
     for rows in (130, 7):                                      # and the bf16 bits do not depend on the slab either
         assert torch.equal(_run(normalize, weighted, act_dtype=torch.bfloat16, rows_per_slab=rows), lp16)
+
+
+@pytest.mark.parametrize("act_dtype", [torch.float32, torch.bfloat16], ids=lambda d: str(d).split(".")[-1])
+@pytest.mark.parametrize("normalize,weighted", CASES, ids=_IDS)
+def test_the_model_method_is_the_function(normalize, weighted, act_dtype):
+    """``GCN.inference`` is ``layerwise_inference``: the same bits, ``edge_weight`` handed on, for every node and ``nodes=``"""
+    from inference_method import assert_method_equals_function
+    x, rowptr, col, w = _dev()
+    N = x.size(0)
+    g = torch.Generator().manual_seed(5)
+    nodes = torch.cat([torch.randperm(N, generator=g)[:150], torch.tensor([200, 200, 0, 131, 259])]).cuda()
+    kw = dict(edge_weight=w) if weighted else {}
+    sub = assert_method_equals_function(_model(normalize), x, rowptr, col, nodes, act_dtype, **kw)
+    assert sub.shape == (nodes.numel(), CLASSES) and torch.equal(sub, _full(normalize, weighted, act_dtype)[nodes])

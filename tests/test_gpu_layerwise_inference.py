@@ -103,16 +103,17 @@ def test_inference_matches_the_forward_over_full_hops(kind, layers, act_dtype):
         assert torch.equal(torch.cat(parts), whole)
 
 
-def test_models_without_inference_and_inputs_it_does_not_read():
-    """the refusals of item 10"""
+def test_every_models_method_is_the_function_and_inputs_it_does_not_read():
+    """the refusals of item 10; GAT's and SAGEResInception's methods are ``layerwise_inference`` as SAGE's is"""
+    from inference_method import assert_method_equals_function
     from salient_plusplus_amd import fp8
     from salient_plusplus_amd.fast_sampler import TableRows
     from salient_plusplus_amd.models import GAT, SAGE, SAGEResInception
     x, rowptr, col = _graph()
-    with pytest.raises(NotImplementedError, match="softmax"):
-        GAT(FIN, HID, CLASSES, 2).cuda().inference(x, rowptr, col)
-    with pytest.raises(NotImplementedError, match="every layer"):
-        SAGEResInception(FIN, HID, CLASSES, 2).cuda().inference(x, rowptr, col)
+    nodes = torch.tensor([N - 1, 300, 300, 0, 11, 7])
+    torch.manual_seed(9)
+    for other in (GAT(FIN, HID, CLASSES, 2).cuda(), SAGEResInception(FIN, HID, CLASSES, 2).cuda()):
+        assert assert_method_equals_function(other, x, rowptr, col, nodes, torch.float32).shape == (6, CLASSES)
     model = SAGE(FIN, HID, CLASSES, 2).cuda()
     with pytest.raises(TypeError, match="fp8"):
         model.inference(fp8.quantize_e4m3(x), rowptr, col)

@@ -40,10 +40,10 @@ def _graph():
 
 
 def _model(kind):
-    from salient_plusplus_amd.models import GAT, SAGE, SAGEResInception
+    from salient_plusplus_amd.models import GAT, GIN, SAGE, SAGEResInception
     torch.manual_seed(31)
-    if kind == "sage":
-        return SAGE(FIN, HID, CLASSES, 3)
+    if kind in ("sage", "gin"):
+        return (SAGE if kind == "sage" else GIN)(FIN, HID, CLASSES, 3)
     name, *rest = kind.split("-")
     layers = int(rest[-1][1:])
     if name == "gat":                                          # (h2: the last layer's h, 2 * 7 wide, is narrower than
@@ -145,11 +145,13 @@ def test_one_rank_owning_everything_and_the_model_left_in_its_mode(kind):
     assert model.training and all(p.grad is None for p in model.parameters())
 
 
-def test_sage_through_the_common_entry_is_the_older_entry():
+@pytest.mark.parametrize("kind", ["sage", "gin", "gat-h1-l2", "gat-h2-l3", "resinc-l2"])
+def test_the_common_entry_is_the_older_entry(kind):
+    """``partitioned_layerwise_inference`` is ``partitioned_inference`` for every model the two admit"""
     from salient_plusplus_amd.inference import LocalPeers, partitioned_inference, partitioned_layerwise_inference
     x, rowptr, col = _graph()
     off = OFFSETS[3]
-    model = _model("sage").cuda().eval()
+    model = _model(kind).cuda().eval()
     parts = [_partition(x, off[r], off[r + 1]) for r in range(3)]
     results = []
     for entry in (partitioned_inference, partitioned_layerwise_inference):
@@ -158,8 +160,8 @@ def test_sage_through_the_common_entry_is_the_older_entry():
                                                       peers=peers, act_dtype=torch.bfloat16))
         assert not errors, errors
         results.append(got)
-    for a, b in zip(*results):
-        assert torch.equal(a.view(torch.int32), b.view(torch.int32))
+    for r, (a, b) in enumerate(zip(*results)):
+        assert a.shape == (off[r + 1] - off[r], CLASSES) and torch.equal(a.view(torch.int32), b.view(torch.int32)), r
     assert not model.training
 
 

@@ -96,16 +96,27 @@ def test_inference_matches_the_forward_over_full_hops(layers, act_dtype):
     assert empty.shape == (0, CLASSES) and empty.dtype == torch.float32
 
 
-def test_a_head_that_is_not_two_linears_is_refused_and_the_model_method_still_raises():
+@pytest.mark.parametrize("act_dtype", ACT_DTYPES, ids=lambda d: str(d).split(".")[-1])
+def test_the_model_method_is_the_function(act_dtype):
+    from inference_method import assert_method_equals_function
+    x, rowptr, col = _graph()
+    g = torch.Generator().manual_seed(1)
+    nodes = torch.cat([torch.randperm(N, generator=g)[:70], torch.tensor([N - 1, 300, 300, 0, 11])])
+    for model in (_model(3).train(), _model(2).eval()):
+        assert assert_method_equals_function(model, x, rowptr, col, nodes, act_dtype).shape == (nodes.numel(), CLASSES)
+
+
+def test_a_head_that_is_not_two_linears_is_refused_by_the_function_and_the_method():
     from salient_plusplus_amd.inference import layerwise_inference
     from salient_plusplus_amd.models import MLP
     x, rowptr, col = _graph()
     model = _model(2)
-    with pytest.raises(NotImplementedError, match="every layer's activations"):
-        model.inference(x, rowptr, col)
     model.mlp = MLP(FIN + HID * 2, 2 * CLASSES, CLASSES, num_layers=2, bn=True, act="LeakyReLU").cuda()
     with pytest.raises(NotImplementedError, match="exactly two Linears"):
         layerwise_inference(model, x, rowptr, col)
+    with pytest.raises(NotImplementedError, match="^layerwise_inference: SAGEResInception's head must be exactly two "
+                                                  "Linears"):
+        model.inference(x, rowptr, col)
     with pytest.raises(ValueError, match="outside the graph"):
         layerwise_inference(_model(2), x, rowptr, col, nodes=torch.tensor([0, N]))
 

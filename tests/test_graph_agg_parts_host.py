@@ -184,11 +184,13 @@ def test_partitioned_inference_validates_and_models_refuse_with_a_reason():
     x = parts[1]
     kw = dict(part_offsets=off, rank=1, peers=_NoPeers())
     sage = SAGE(8, 4, 2, 2)
-    with pytest.raises(NotImplementedError, match="partitioned_layerwise_inference: GAT"):
-        pli(GAT(8, 4, 2, 2), x, rowptr, col, **kw)
-    with pytest.raises(NotImplementedError, match="partitioned_layerwise_inference: SAGEResInception"):
-        pli(SAGEResInception(8, 4, 2, 2), x, rowptr, col, **kw)
-    with pytest.raises(NotImplementedError, match="SAGE and GIN"):
+    for admitted in (GAT(8, 4, 2, 2), SAGEResInception(8, 4, 2, 2)):     # past the model filter: the next check answers
+        with pytest.raises(TypeError, match="^partitioned_layerwise_inference: an fp8 feature table"):
+            pli(admitted, fp8.quantize_e4m3(torch.zeros((2, 16))), rowptr, col, **kw)
+        with pytest.raises(ValueError, match="^partitioned_layerwise_inference: rank 2 outside"):
+            pli(admitted, x, rowptr, col, **{**kw, "rank": 2})
+    with pytest.raises(NotImplementedError, match="^partitioned_layerwise_inference: implemented for SAGE, GIN, GAT and "
+                                                  "SAGEResInception, not Linear$"):
         pli(torch.nn.Linear(8, 2), x, rowptr, col, **kw)
     with pytest.raises(TypeError, match="fp8 feature table"):
         pli(sage, fp8.quantize_e4m3(torch.zeros((2, 16))), rowptr, col, **kw)

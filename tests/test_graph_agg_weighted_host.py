@@ -286,18 +286,25 @@ def test_parts_and_fields_still_refuse_gcn_with_their_messages(no_device):
         with pytest.raises(TypeError, match="edge_weight"):  # no weights in the field entries
             fn(m, x, rowptr, col, nodes=nodes, edge_weight=torch.ones(9))
     kw = dict(part_offsets=[0, 3, 6], rank=0, peers=_NoPeers())
-    for fn, names in ((inf.partitioned_inference, "SAGE, GIN, GAT and SAGEResInception"),
-                      (inf.partitioned_evaluate, "SAGE, GIN, GAT and SAGEResInception"),
-                      (inf.partitioned_layerwise_inference, "SAGE and GIN")):
-        with pytest.raises(NotImplementedError, match=rf"^{fn.__name__}: implemented for {names}.*, not GCN$"):
+    for fn in (inf.partitioned_inference, inf.partitioned_evaluate, inf.partitioned_layerwise_inference):
+        with pytest.raises(NotImplementedError,
+                           match=rf"^{fn.__name__}: implemented for SAGE, GIN, GAT and SAGEResInception, not GCN$"):
             fn(m, x[:3], rowptr, col, **kw)
         with pytest.raises(TypeError, match="edge_weight"):
             fn(m, x[:3], rowptr, col, edge_weight=torch.ones(9), **kw)
 
 
-def test_gcn_inference_method_points_to_the_driver():
-    with pytest.raises(NotImplementedError, match="GCN.inference.*inference.layerwise_inference"):
-        _gcn().inference(torch.zeros((6, 4)), None, None)
+def test_gcn_inference_method_is_the_driver():
+    from inference_method import assert_method_is_the_function
+    rowptr, col = _graph()
+    x = torch.zeros((6, 4), dtype=torch.float16)
+    for normalize in (False, True):
+        assert_method_is_the_function(_gcn(normalize), x, rowptr, col)
+        assert_method_is_the_function(_gcn(normalize), x, rowptr, col, edge_weight=torch.ones(9))
+    for bad in (torch.ones(8), torch.ones(9).double()):      # the method hands edge_weight on: the function's refusal
+        with pytest.raises(ValueError, match=r"^layerwise_inference: edge_weight must be a contiguous fp32 tensor of "
+                                             r"shape \[9\]"):
+            _gcn().inference(x, rowptr, col, edge_weight=bad)
 
 
 def test_no_device_means_an_error_not_a_fallback():

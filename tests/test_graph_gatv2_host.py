@@ -1,8 +1,9 @@
 """CPU-only: the host side of exact layer-wise GATv2 inference (spp.h f3w) -- the exported entries and the ctypes layout
 of spp_graph_gatv2_desc against the header, every refusal of spp_graph_gatv2_forward that needs no device, the argument
 validation of inference.graph_gatv2_aggregate / gatv2_inference / evaluate before any device call, the entries that keep
-refusing a GATv2 model, the float64 helper's own check (tests/graph_gatv2_f64.py: a correct chunked fp32 computation
-stays inside every bound, three planted faults leave them), and the channel-padding identity of the driver."""
+refusing a GATv2 model (the field and partitioned ones) and the three spellings of the resident one, the float64
+helper's own check (tests/graph_gatv2_f64.py: a correct chunked fp32 computation stays inside every bound, three
+planted faults leave them), and the channel-padding identity of the driver."""
 import ctypes
 import os
 import subprocess
@@ -218,13 +219,20 @@ def test_gatv2_inference_validates_before_the_device(no_device):
         inference.evaluate(model, x, rowptr, col, edge_weight=torch.ones(3))
 
 
-def test_the_other_entries_still_refuse_gatv2_and_name_the_new_ones(no_device):
+def test_the_other_entries_still_refuse_gatv2_and_name_the_resident_ones(no_device):
     from salient_plusplus_amd import inference
     from salient_plusplus_amd.models import GATv2
     x, rowptr, col = torch.zeros((3, 4)), torch.tensor([0, 1, 2, 3]), torch.tensor([0, 1, 2])
     model = GATv2(4, 8, 3, 2, heads=2)
-    with pytest.raises(NotImplementedError, match="GATv2.*gatv2_inference.*evaluate"):
-        inference.layerwise_inference(model, x, rowptr, col)
+    for call in (lambda: inference.layerwise_inference(model, x, rowptr, col), lambda: model.inference(x, rowptr, col)):
+        with pytest.raises(AssertionError, match="before the arguments were refused"):       # valid: it reaches the device
+            call()
+    for fn, kw in ((inference.field_inference, dict(nodes=torch.tensor([0]))),
+                   (inference.field_evaluate, dict(nodes=torch.tensor([0]))),
+                   (inference.partitioned_inference, dict(part_offsets=[0, 3], rank=0, peers=inference.LocalPeers(1)))):
+        with pytest.raises(NotImplementedError, match=rf"^{fn.__name__}: not built for GATv2.*layerwise_inference.*"
+                                                      "evaluate"):
+            fn(model, x, rowptr, col, **kw)
     with pytest.raises(NotImplementedError, match="GATv2.*gatv2_inference"):
         inference.field_inference(model, x, rowptr, col, torch.tensor([0]))
     with pytest.raises(NotImplementedError, match="GATv2.*gatv2_inference"):
@@ -232,8 +240,29 @@ def test_the_other_entries_still_refuse_gatv2_and_name_the_new_ones(no_device):
     with pytest.raises(NotImplementedError, match="GATv2.*gatv2_inference"):
         inference.partitioned_inference(model, x, rowptr, col, part_offsets=[0, 3], rank=0,
                                         peers=inference.LocalPeers(1))
-    with pytest.raises(NotImplementedError, match="gatv2_inference.*evaluate"):
-        model.inference(x, rowptr, col)
+
+
+def test_gatv2_method_and_both_entries_raise_the_same(no_device):
+    """layerwise_inference takes a GATv2 model with gatv2_inference's checks (each under its own name), and the method
+    is layerwise_inference"""
+    from salient_plusplus_amd import inference
+    from salient_plusplus_amd.models import GATv2
+    x, rowptr, col = torch.zeros((3, 4)), torch.tensor([0, 1, 2, 3]), torch.tensor([0, 1, 2])
+    model = GATv2(4, 8, 3, 2, heads=2)
+    bad = [dict(act_dtype=torch.float16), dict(rows_per_slab=0), dict(nodes=torch.tensor([0.5]))]
+    for model_, kw in [(model, k) for k in bad] + [(GATv2(4, 6, 3, 2, heads=3), {}), (GATv2(4, 8, 172, 2, heads=8), {})]:
+        seen = []
+        for call in (lambda: inference.layerwise_inference(model_, x, rowptr, col, **kw),
+                     lambda: model_.inference(x, rowptr, col, **kw),
+                     lambda: inference.gatv2_inference(model_, x, rowptr, col, **kw)):
+            with pytest.raises((ValueError, NotImplementedError)) as info:
+                call()
+            seen.append((type(info.value), str(info.value)))
+        assert seen[0] == seen[1] and seen[0][1].startswith("layerwise_inference: ")
+        assert seen[2] == (seen[0][0], "gatv2_inference: " + seen[0][1][len("layerwise_inference: "):])
+    with pytest.raises(TypeError, match="^layerwise_inference: x is an Fp8Table.*GATv2"):
+        from salient_plusplus_amd import fp8
+        model.inference(inference.Fp8Table(fp8.quantize_e4m3(torch.zeros((3, 16)))), rowptr, col)
 
 
 # ---------------------------------------------------------------------------------------------------- the helper's own check

@@ -1,6 +1,6 @@
 """CPU-only: the host side of exact layer-wise inference -- argument validation of inference.graph_aggregate and
-layerwise_inference (before any device call), the models that refuse inference and why, the resident-graph accessor's
-refusals, and the ctypes layout of spp_graph_agg_desc against the header."""
+layerwise_inference (before any device call), every model's ``.inference`` being that function, the resident-graph
+accessor's refusals, and the ctypes layout of spp_graph_agg_desc against the header."""
 import ctypes
 import os
 import subprocess
@@ -93,11 +93,10 @@ def test_layerwise_inference_validates_and_models_refuse_with_a_reason():
     from salient_plusplus_amd.models import GAT, GIN, SAGE, SAGEResInception
     x, rowptr, col = _tiny()
     sage = SAGE(4, 4, 2, 2)
-    with pytest.raises(NotImplementedError, match="long-row softmax"):
-        GAT(4, 4, 2, 2).inference(x, rowptr, col)
-    with pytest.raises(NotImplementedError, match="every layer's activations"):
-        SAGEResInception(4, 4, 2, 2).inference(x, rowptr, col)
-    with pytest.raises(NotImplementedError, match="SAGE and GIN"):
+    from inference_method import assert_method_is_the_function
+    for model in (GAT(4, 4, 2, 2), GAT(4, 4, 2, 2, heads=2), SAGEResInception(4, 4, 2, 2), sage, GIN(4, 4, 2, 2)):
+        assert_method_is_the_function(model, x, rowptr, col)
+    with pytest.raises(NotImplementedError, match="^layerwise_inference: implemented for SAGE, GIN, GAT, SAGEResInception, GCN and GATv2, not Linear$"):
         layerwise_inference(torch.nn.Linear(4, 2), x, rowptr, col)
     with pytest.raises(TypeError, match="fp8 feature table"):
         sage.inference(fp8.quantize_e4m3(torch.zeros((3, 16))), rowptr, col)

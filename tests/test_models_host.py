@@ -46,9 +46,9 @@ def _sage_ri_keys(in_c, hid, out_c, L):
 def test_get_model_type_maps_the_four_working_models():
     from salient_plusplus_amd import models as M
     for name, cls in (("sage", M.SAGE), ("GAT", M.GAT), ("Gin", M.GIN), ("SAGEResInception", M.SAGEResInception),
-                      ("sageresinception", M.SAGEResInception)):
+                      ("sageresinception", M.SAGEResInception), ("gcn", M.GCN), ("GCN", M.GCN)):
         assert M.get_model_type(name) is cls
-    for name in ("sageclassic", "JKNet", "gcn", "ARMA"):
+    for name in ("sageclassic", "JKNet", "ARMA"):
         with pytest.raises(NotImplementedError, match="not implemented"):
             M.get_model_type(name)
     with pytest.raises(ValueError):

@@ -185,12 +185,16 @@ def test_wrapper_needs_the_device_for_valid_arguments():
         resinc_epilogue(torch.zeros((3, 4)), torch.ones(4), torch.zeros(4), negative_slope=0.01)
 
 
-def test_model_inference_still_raises_and_names_the_driver():
-    from salient_plusplus_amd.models import SAGEResInception
+def test_model_inference_is_the_driver():
+    from inference_method import assert_method_is_the_function
+    from salient_plusplus_amd.models import MLP, SAGEResInception
     x, rowptr, col = torch.zeros((3, 4)), torch.tensor([0, 1, 2, 3]), torch.tensor([0, 1, 2])
-    with pytest.raises(NotImplementedError, match="every layer's activations") as e:
-        SAGEResInception(4, 4, 2, 2).inference(x, rowptr, col)
-    assert "layerwise_inference(model" in str(e.value)
+    model = SAGEResInception(4, 4, 2, 2)
+    assert_method_is_the_function(model, x, rowptr, col)
+    model.mlp = MLP(4 + 4 * 2, 4, 2, num_layers=3, end_up_with_fc=True)
+    with pytest.raises(NotImplementedError, match="^layerwise_inference: SAGEResInception's head must be exactly two "
+                                                  "Linears"):
+        model.inference(x, rowptr, col)
 
 
 def test_driver_refusals_for_sageresinception(no_device):
@@ -209,7 +213,7 @@ def test_driver_refusals_for_sageresinception(no_device):
         layerwise_inference(model, RowRefs(torch.zeros(3, dtype=torch.int64), None, 4, torch.float16, None, ()), rowptr, col)
     with pytest.raises(ValueError, match="act_dtype"):
         layerwise_inference(model, x, rowptr, col, act_dtype=torch.float16)
-    with pytest.raises(NotImplementedError, match="SAGE and GIN"):
+    with pytest.raises(NotImplementedError, match="^layerwise_inference: implemented for SAGE, GIN, GAT, SAGEResInception, GCN and GATv2, not Linear$"):
         layerwise_inference(torch.nn.Linear(4, 2), x, rowptr, col)
     model.mlp = MLP(4 + 4 * 2, 4, 2, num_layers=2, bn=True, end_up_with_fc=False, act="LeakyReLU")
     with pytest.raises(NotImplementedError, match="exactly two Linears"):
