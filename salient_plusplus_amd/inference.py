@@ -5,8 +5,8 @@ GIN and SAGEResInception and of csrc/graph_gat.hip for GAT; SAGEResInception's l
 (``spp_resinc_epilogue``); GCN's weighted sums are the pair of csrc/graph_agg_weighted.hip (``graph_weighted_aggregate``,
 with ``gcn_dinv`` for the per-node factors of its normalisation; resident entries only).  The layers' own parameters run
 through the library GEMMs torch dispatches to.  Forward only, fp16 / fp32 / bf16 inputs.  GATv2 (f3w): the long-row
-pair of csrc/graph_gatv2.hip behind ``graph_gatv2_aggregate`` (``spp_graph_gatv2_forward``) and the driver
-``_gatv2_layers``; resident entries only.
+pair of csrc/graph_gatv2.hip behind ``graph_gatv2_aggregate`` (``spp_graph_gatv2_forward``) and the recipe
+``_gatv2_layer`` of the attention driver; resident entries only.
 
 The kernels' wrappers: ``graph_aggregate`` (``spp_graph_agg_forward``) and ``graph_gat_aggregate``
 (``spp_graph_gat_forward``) read one resident matrix, ``graph_aggregate_parts`` (``spp_graph_agg_parts_forward``) and
@@ -16,9 +16,9 @@ tail all models share: argmax and negative log-likelihood of a tile of logits.  
 with the helpers they share and hands them to its kernel's launch function (``_agg_launch``, ``_gat_launch``,
 ``_agg_parts_launch``, ``_gat_parts_launch``), which the drivers call directly, slab by slab.
 
-The drivers: one layer loop per model (``_conv_layers`` for SAGE, GIN and GCN, ``_gat_layers``, ``_gatv2_layers``,
-``_resinc_layers``), written against a placement that says where the table lives -- ``_Resident`` (one matrix, the
-whole-table kernels, no waits) or ``_Partitioned`` (the parts kernels over buffers published through ``peers``, a
+The drivers: ``_conv_layers`` (SAGE, GIN, GCN) and ``_attn_layers`` (GAT, GATv2), each one layer loop plus a recipe per
+model, and ``_resinc_layers``, written against a placement that says where the table lives -- ``_Resident`` (one matrix,
+the whole-table kernels, no waits) or ``_Partitioned`` (the parts kernels over buffers published through ``peers``, a
 synchronise and a barrier at every layer boundary) -- inside one frame (``_score``).  ``layerwise_inference`` is the
 resident entry for all six models (behind every model's ``.inference``; ``gatv2_inference`` is its older name for
 GATv2), ``partitioned_inference`` the partitioned one for SAGE, GIN, GAT and SAGEResInception
@@ -1275,21 +1275,16 @@ def _conv_layers(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None)
     return sink.result()
 
 
-def _gat_layers(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None):
-    """GAT, in PyG's project-first order (training aggregates first, _GatLayer / _GatLayerMH, because an MFG hop has
-    many sources per target; over the whole graph T = S = N, that saving is gone, and the aggregate-first intermediate
-    would be [T, H, K] fp32 per slab).  Per layer:
+def _gat_layer(model, place, act_dtype):
+    """GAT's layers for ``_attn_layers``, in PyG's project-first order (training aggregates first, _GatLayer /
+    _GatLayerMH, because an MFG hop has many sources per target; over the whole graph T = S = N, that saving is gone,
+    and the aggregate-first intermediate would be [T, H, K] fp32 per slab):
 
-      project    h = cur @ W^T for all the rank's rows, [n, H*C] in ``act_dtype``, over ``_row_tiles``
+      project    h = cur @ W^T for all the rank's rows, [n, H*C] in ``act_dtype``
       logits     [a_src | a_dst] = tile.float() @ V^T with V = W_h^T att (as _GatLayerMH builds it), fp32 [n, H] each:
                  taken from the layer's input rows, never from the rounded h
-      aggregate  the attention kernel slab by slab over each node's whole row; hidden layers through the fused ReLU
-                 straight into the next [n, hidden] matrix, the last layer ([T, H*classes] fp32 per slab) through the
-                 mean over its heads into ``sink`` (log_softmax(dtype=float32), or ``classify_rows``)
-
-    Partitioned, projection and logits are LOCAL (a rank's own rows of the layer's input), so no rank reads a peer's
-    feature rows; h and the logits are the two published buffers, and a layer has two boundaries: every rank's h and
-    logits are complete before anyone attends, and everyone has finished reading h before the next layer overwrites it.
+      attend     ``place.attend``: ``spp_graph_gat_forward``; partitioned, the parts kernel over h and the logits, the
+                 two published buffers.  Projection and logits are LOCAL: no rank reads a peer's feature rows.
 
     Memory, as arithmetic (resident): ``cur`` is dropped once ``h`` is complete and ``h`` once ``nxt`` is, so two
     [N, hidden] matrices of ``act_dtype`` are live at a time, as for SAGE (57 GB each in bf16 at N = 111 M, hidden 256;
@@ -1297,77 +1292,49 @@ def _gat_layers(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None):
     case worse than SAGE: the last layer's h is [N, H * classes], so H > 1 heads multiply it -- 111 M * 4 * 172 * 2 bytes
     = 153 GB in bf16 for H = 4 and 172 classes, which does not fit next to a 57 GB ``cur``, 26 GB of graph and 28 GB of
     features on one 288 GB MI355X.  The reference's model has H = 1 (38 GB).  Partitioned: ``partitioned_inference``."""
-    n_layers, dev = len(model.convs), place.dev
-    plan = plan or _whole_graph_plan(place, nodes, n_layers)     # (one ``_Step`` a layer, as in ``_conv_layers``)
     place.open_gat(max(c.heads * c.out_channels for c in model.convs), max(c.heads for c in model.convs), act_dtype)
-    ws = torch.empty(graph_gat_workspace_bytes(min(rows_per_slab, max([place.n_local] + [st.rows for st in plan]))),
-                     dtype=torch.uint8, device=dev)
-    cur = place.x
-    for i, conv in enumerate(model.convs):
-        last = i == n_layers - 1
-        H, Cc = conv.heads, conv.out_channels
-        W = conv.lin_src.weight                                                   # [H*C, K]
+
+    def layer(i):
+        conv = model.convs[i]
+        H, Cc, W = conv.heads, conv.out_channels, conv.lin_src.weight             # W: [H*C, K]
         att = torch.stack([conv.att_src.view(H, Cc), conv.att_dst.view(H, Cc)]).to(torch.float32)
         V = torch.einsum("shc,hck->shk", att, W.to(torch.float32).view(H, Cc, -1)).reshape(2 * H, -1)   # [V_src; V_dst]
         Wt, Vt = W.to(act_dtype).t(), V.t().contiguous()
-        h, logits = place.gat_rows(cur.size(0), H, Cc, act_dtype)
-        for r, n, tile in _row_tiles(cur):
-            h[r:r + n] = (tile.to(act_dtype) @ Wt)[:n]
-            place.put_logits(logits, r, n, tile.to(torch.float32) @ Vt)
-        tile = None                                      # (a full tile is a VIEW of cur)
-        del cur                                          # (layer i-1's matrix; layer 1's is the caller's table)
-        place.boundary()                                 # every rank's h and logits of this layer are complete
-        step = plan[i]
-        rows, names = step.rows, step.names
-        if last:
-            nxt = None
-            sink.open(place, rows, Cc)
-        else:
-            nxt = torch.empty((rows, H * Cc), dtype=act_dtype, device=dev)
-        for s, T, tids in _slabs(rows, step.ids, rows_per_slab):
-            out = nxt[s:s + T] if not last else torch.empty((T, H * Cc), dtype=torch.float32, device=dev)
-            place.attend(h, logits, conv, not last, s, tids, T, out, ws, step.graph)
-            if last:                                     # concat=False: the mean of the heads (H = 1: the head itself)
-                sink.put(s, T, out.view(T, H, Cc).mean(1) if H > 1 else out, names[s:s + T] if names is not None else None)
-            out = None                                   # (a hidden layer's slab is a VIEW of nxt)
-        cur, nxt = nxt, None                             # ONE name holds the matrix: ``del cur`` above must free it
-        del h, logits                                    # (resident: drops them)
-        place.boundary()                                 # every rank has finished reading this layer's h
-    return sink.result()
+
+        def project(cur):
+            h, logits = place.gat_rows(cur.size(0), H, Cc, act_dtype)
+            for r, n, tile in _row_tiles(cur):
+                h[r:r + n] = (tile.to(act_dtype) @ Wt)[:n]
+                place.put_logits(logits, r, n, tile.to(torch.float32) @ Vt)
+            return h, logits
+        return H, Cc, Cc, project, lambda operands, *slab: place.attend(*operands, conv, *slab)
+    return graph_gat_workspace_bytes, layer
 
 
-def _gatv2_layers(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None):
-    """GATv2 over one resident matrix (f3w), project-first as ``GATv2Conv.forward``.  Per layer:
+def _gatv2_layer(model, place, act_dtype):
+    """GATv2 over one resident matrix (f3w), project-first as ``GATv2Conv.forward``:
 
-      project    x_l = cur @ W_l^T and x_r = cur @ W_r^T for all rows, [n, H*Cp] each in ``act_dtype``, over
-                 ``_row_tiles``; with ``share_weights`` x_r IS x_l and no second GEMM runs
-      aggregate  ``spp_graph_gatv2_forward`` slab by slab over each node's whole row; hidden layers through the fused
-                 ReLU straight into the next [n, hidden] matrix, the last layer ([T, H*Cp] fp32 per slab) through the
-                 mean over its heads into ``sink``
+      project    x_l = cur @ W_l^T and x_r = cur @ W_r^T for all rows, [n, H*Cp] each in ``act_dtype``; with
+                 ``share_weights`` x_r IS x_l and no second GEMM runs
+      attend     ``spp_graph_gatv2_forward`` (``_gatv2_launch``) over the step's graph or the placement's
 
     Channel padding: the kernels take C % 4 == 0 with C / 4 a power of two, and a last layer has C = classes (47, 172).
     Cp is the next such width (48 -> 64, 172 -> 256): W_l / W_r get Cp - C zero rows per head and att Cp - C zero
-    columns, and the padded output columns are sliced away before the mean.  The padding is exact: a padded channel
-    has x_l = x_r = 0, so its term of every logit is att * lrelu(0 + 0) = 0 * 0 = +0, added to a dot product -- and its
+    columns, and the driver slices the padded output columns away.  The padding is exact: a padded channel has
+    x_l = x_r = 0, so its term of every logit is att * lrelu(0 + 0) = 0 * 0 = +0, added to a dot product -- and its
     position in the butterfly is fixed by (H, Cp), the same for every entry.
 
-    Memory, as arithmetic: ``cur`` is dropped once x_l and x_r are complete (no other name or view holds it), so at the
-    worst moment THREE [N, hidden] matrices of ``act_dtype`` are live (cur, x_l, x_r while projecting, with two GEMM tiles
-    of 65 536 rows on top; then x_l, x_r and nxt): at N = 111 M and hidden 256, 57 GB each in bf16, next to 26 GB
-    of graph and 28 GB of features: 3 * 57 + 26 + 28 = 225 GB of one 288 GB MI355X.  With ``share_weights`` two are live
+    Memory, as arithmetic: ``cur`` is dropped once x_l and x_r are complete (``_attn_layers``), so at the worst moment
+    THREE [N, hidden] matrices of ``act_dtype`` are live (cur, x_l, x_r while projecting, with two GEMM tiles of 65 536
+    rows on top; then x_l, x_r and nxt): at N = 111 M and hidden 256, 57 GB each in bf16, next to 26 GB of graph and
+    28 GB of features: 3 * 57 + 26 + 28 = 225 GB of one 288 GB MI355X.  With ``share_weights`` two are live
     (2 * 57 + 26 + 28 = 168 GB, as SAGE).  The one case worse: the last layer's x_l and x_r are [N, H * Cp] -- for H = 4
     and 172 classes (Cp = 256) 111 M * 4 * 256 * 2 bytes = 227 GB EACH in bf16, which does not fit next to anything;
     H = 1 is 57 GB each (2 * 57 + 57 of ``cur`` + 26 + 28 = 225 GB; 168 GB shared).  A multi-head model of many classes
     at that scale needs ``share_weights`` and fewer heads, or several devices (not built for GATv2)."""
-    n_layers, dev = len(model.convs), place.dev
-    plan = plan or _whole_graph_plan(place, nodes, n_layers)     # (one ``_Step`` a layer, as in ``_conv_layers``)
-    ws = torch.empty(graph_gatv2_workspace_bytes(min(rows_per_slab, max([place.n_local] + [st.rows for st in plan]))),
-                     dtype=torch.uint8, device=dev)
-    cur = place.x
-    for i, conv in enumerate(model.convs):
-        last = i == n_layers - 1
-        H, Cc = conv.heads, conv.out_channels
-        Cp = _gatv2_pad(Cc)
+    def layer(i):
+        conv = model.convs[i]
+        H, Cc, Cp = conv.heads, conv.out_channels, _gatv2_pad(conv.out_channels)
 
         def padded_t(W):                                 # [H*C, K] -> [K, H*Cp] in act_dtype, zero rows behind each head's C
             if Cp != Cc:
@@ -1377,31 +1344,57 @@ def _gatv2_layers(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None
             return W.to(act_dtype).t()
         shared = conv.lin_r is conv.lin_l
         Wl, Wr = padded_t(conv.lin_l.weight), None if shared else padded_t(conv.lin_r.weight)
-        att = torch.zeros((H, Cp), dtype=torch.float32, device=dev)
+        att = torch.zeros((H, Cp), dtype=torch.float32, device=place.dev)
         att[:, :Cc] = conv.att.view(H, Cc)
-        x_l = torch.empty((cur.size(0), H * Cp), dtype=act_dtype, device=dev)
-        x_r = x_l if shared else torch.empty_like(x_l)
-        for r, n, tile in _row_tiles(cur):
-            tile = tile.to(act_dtype)
-            x_l[r:r + n] = (tile @ Wl)[:n]
-            if not shared:
-                x_r[r:r + n] = (tile @ Wr)[:n]
-        tile = None                                      # (a full tile is a VIEW of cur)
+
+        def project(cur):
+            x_l = torch.empty((cur.size(0), H * Cp), dtype=act_dtype, device=place.dev)
+            x_r = x_l if shared else torch.empty_like(x_l)
+            for r, n, tile in _row_tiles(cur):
+                tile = tile.to(act_dtype)
+                x_l[r:r + n] = (tile @ Wl)[:n]
+                if not shared:
+                    x_r[r:r + n] = (tile @ Wr)[:n]
+            return x_l, x_r
+
+        def attend(operands, relu, s, ids, T, out, ws, graph):
+            return _gatv2_launch(*operands, att, *(graph or (place.rowptr, place.col)), conv.negative_slope, relu,
+                                 -1 if ids is not None else s, ids, T, out, ws)
+        return H, Cc, Cp, project, attend
+    return graph_gatv2_workspace_bytes, layer
+
+
+def _attn_layers(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None):
+    """GAT and GATv2.  A recipe (``_gat_layer``, ``_gatv2_layer``) opens the placement and returns (workspace_bytes,
+    layer); ``layer(i)`` -> (H, Cc, Cp, project, attend): heads, channels a head, channels a head as the kernel writes
+    them, ``project(cur)`` -> the projected operands of all the rank's rows, over ``_row_tiles(cur)``, and
+    ``attend(operands, relu, s, ids, T, out, ws, graph)``, a slab's launch over each node's whole row.  Hidden layers go
+    through the fused ReLU straight into the next [n, hidden] matrix (Cp != Cc: into a [T, H*Cp] slab whose leading
+    columns are copied), the last layer ([T, H*Cp] fp32 per slab) through the mean over its heads into ``sink``.  Two
+    boundaries a layer: the projected rows are complete before anyone attends, and read by everyone before the next
+    layer overwrites them.  The recipes' memory arithmetic rests on ONE name each for ``cur``, the operands and ``nxt``
+    and no view left behind (a tile dies with ``project``'s frame).  ``plan``: as in ``_conv_layers``."""
+    workspace_bytes, layer = (_gatv2_layer if isinstance(model, GATv2) else _gat_layer)(model, place, act_dtype)
+    n_layers, dev = len(model.convs), place.dev
+    plan = plan or _whole_graph_plan(place, nodes, n_layers)
+    ws = torch.empty(workspace_bytes(min(rows_per_slab, max([place.n_local] + [st.rows for st in plan]))),
+                     dtype=torch.uint8, device=dev)
+    cur = place.x
+    for i, step in enumerate(plan):
+        last = i == n_layers - 1
+        H, Cc, Cp, project, attend = layer(i)
+        operands = project(cur)
         del cur                                          # (layer i-1's matrix; layer 1's is the caller's table)
-        step = plan[i]
+        place.boundary()                                 # every rank's projected rows of this layer are complete
         rows, names = step.rows, step.names
-        rowptr, col = step.graph or (place.rowptr, place.col)
+        nxt = None if last else torch.empty((rows, H * Cc), dtype=act_dtype, device=dev)
         if last:
-            nxt = None
             sink.open(place, rows, Cc)
-        else:
-            nxt = torch.empty((rows, H * Cc), dtype=act_dtype, device=dev)
+        direct = not last and Cp == Cc                   # the rows go straight into the next activation matrix
         for s, T, tids in _slabs(rows, step.ids, rows_per_slab):
-            direct = not last and Cp == Cc               # the rows go straight into the next activation matrix
             out = nxt[s:s + T] if direct else torch.empty((T, H * Cp), dtype=act_dtype if not last else torch.float32,
                                                           device=dev)
-            _gatv2_launch(x_l, x_r, att, rowptr, col, conv.negative_slope, not last, -1 if tids is not None else s, tids,
-                          T, out, ws)
+            attend(operands, not last, s, tids, T, out, ws, step.graph)
             if last:                                     # concat=False: the mean of the heads (H = 1: the head itself)
                 z = out.view(T, H, Cp)[:, :, :Cc]
                 sink.put(s, T, z.mean(1) if H > 1 else z.reshape(T, Cc), names[s:s + T] if names is not None else None)
@@ -1409,7 +1402,8 @@ def _gatv2_layers(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None
                 nxt[s:s + T] = out.view(T, H, Cp)[:, :, :Cc].reshape(T, H * Cc)
             out = None                                   # (a hidden layer's slab is a VIEW of nxt)
         cur, nxt = nxt, None                             # ONE name holds the matrix: ``del cur`` above must free it
-        del x_l, x_r
+        del operands                                     # (resident: drops them)
+        place.boundary()                                 # every rank has finished reading this layer's projected rows
     return sink.result()
 
 
@@ -1511,8 +1505,16 @@ _GATV2_RESIDENT = ("a GATv2 model is scored over one resident fp16 / fp32 / bf16
                    "the partitioned entries are not built for GATv2")
 
 
+def _check_gat(model, what):
+    """the layers as ``models.GAT`` builds them"""
+    for i, c in enumerate(model.convs):
+        if c.bias is not None or c.concat == (i == len(model.convs) - 1 and c.heads > 1):
+            raise NotImplementedError(f"{what}: GAT layers need bias=False, and concat=False on the last layer of a "
+                                      "multi-head model only")
+
+
 def _check_gatv2(model, what):
-    """the layers as ``models.GATv2`` builds them, in shapes ``_gatv2_layers`` can put on the kernels"""
+    """the layers as ``models.GATv2`` builds them, in shapes ``_gatv2_layer`` can put on the kernels"""
     for i, c in enumerate(model.convs):
         last = i == len(model.convs) - 1
         if c.bias is not None or c.lin_l.bias is not None or c.lin_r.bias is not None or c.concat == last:
@@ -1541,12 +1543,8 @@ def _check_model(model, what, admits):
         _check_gatv2(model, what)
     if isinstance(model, SAGEResInception):
         _resinc_head(model)
-    if isinstance(model, GAT):                                # the layers as models.GAT builds them
-        for i, c in enumerate(model.convs):
-            mean_heads = i == len(model.convs) - 1 and c.heads > 1
-            if c.bias is not None or c.concat == mean_heads:
-                raise NotImplementedError(f"{what}: GAT layers need bias=False, and concat=False on the last layer of a "
-                                          "multi-head model only")
+    if isinstance(model, GAT):
+        _check_gat(model, what)
 
 
 def _check_run(what, act_dtype, rows_per_slab, nodes):
@@ -1564,8 +1562,8 @@ def _check_run(what, act_dtype, rows_per_slab, nodes):
 def _score(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None):
     """the frame of every driver: eval mode (restored), no gradient, autocast off, the table's device current; a rank
     that fails aborts the placement, so that its peers raise instead of waiting, and every mapping is closed"""
-    layers = _gat_layers if isinstance(model, GAT) else _resinc_layers if isinstance(model, SAGEResInception) \
-        else _gatv2_layers if isinstance(model, GATv2) else _conv_layers
+    layers = _attn_layers if isinstance(model, (GAT, GATv2)) else \
+        _resinc_layers if isinstance(model, SAGEResInception) else _conv_layers
     was_training = model.training
     model.eval()
     try:
@@ -1587,10 +1585,10 @@ def layerwise_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 <<
     """Exact log-probabilities of every node, [N, classes] fp32 -- or of ``nodes`` (int64, any order, duplicates
     allowed), [len(nodes), classes] -- for a ``SAGE``, ``GIN``, ``GAT``, ``SAGEResInception``, ``GCN`` or ``GATv2`` model
     over the whole graph; every model's ``.inference`` is this call.  Each driver's docstring has its order of operations
-    and its memory: ``_conv_layers`` (SAGE, GIN and, through ``_gcn_layer``, GCN), ``_gat_layers`` (GAT at any ``heads``),
-    ``_gatv2_layers`` (GATv2: heads in {1, 2, 4, 8}, heads * padded channels <= 1024, one resident matrix and no
-    ``Fp8Table``) and ``_resinc_layers`` (SAGEResInception).  What follows describes SAGE and GIN; the arguments, the
-    fixed GEMM tiles, eval mode and ``nodes`` mean the same for all six.
+    and its memory: ``_conv_layers`` (SAGE, GIN and, through ``_gcn_layer``, GCN), ``_attn_layers`` with ``_gat_layer``
+    (GAT at any ``heads``) and ``_gatv2_layer`` (GATv2: heads in {1, 2, 4, 8}, heads * padded channels <= 1024, one
+    resident matrix and no ``Fp8Table``) and ``_resinc_layers`` (SAGEResInception).  What follows describes SAGE and
+    GIN; the arguments, the fixed GEMM tiles, eval mode and ``nodes`` mean the same for all six.
 
     ``edge_weight`` (GCN only; a ``ValueError`` with any other model): contiguous fp32 [E], one value per entry of
     ``col`` -- what ``adj_t`` carries in training; None: every entry weighs 1.  GCN reads one resident fp16 / fp32 / bf16
@@ -2076,7 +2074,7 @@ def partitioned_inference(model, x_local, rowptr, col, *, part_offsets, rank, pe
     [part_offsets[rank], part_offsets[rank + 1])), the WHOLE graph's CSR (global ids) and the same ``model``, and gets the
     fp32 log-probabilities of ITS node range, [n_local, classes] -- or of ``nodes`` (global ids, all inside the rank's
     range).  The bits are those of ``layerwise_inference`` over the concatenated table, those rows: the layer loops are
-    the same code (``_conv_layers``, ``_gat_layers``, ``_resinc_layers``) over the same fixed GEMM tiles.
+    the same code (``_conv_layers``, ``_attn_layers``, ``_resinc_layers``) over the same fixed GEMM tiles.
 
     Per rank (``_Partitioned``): the buffers the other ranks read are allocated up front and published once through
     ``peers`` -- SAGE, GIN and SAGEResInception: ``x_local`` and the ping-pong activation buffers [n_local, hidden] of

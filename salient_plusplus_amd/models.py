@@ -1153,7 +1153,7 @@ class GAT(torch.nn.Module):
 
     @torch.no_grad()
     def inference(self, x_all, rowptr, col, **kw):
-        """as ``SAGE.inference``: ``inference.layerwise_inference`` (the long-row softmax of ``_gat_layers``)"""
+        """as ``SAGE.inference``: ``inference.layerwise_inference`` (the long-row softmax behind ``_attn_layers`` / ``_gat_layer``)"""
         from .inference import layerwise_inference
         return layerwise_inference(self, x_all, rowptr, col, **kw)
 
@@ -1373,7 +1373,7 @@ class GATv2(torch.nn.Module):
 
     @torch.no_grad()
     def inference(self, x_all, rowptr, col, **kw):
-        """as ``SAGE.inference``: ``inference.layerwise_inference`` (``_gatv2_layers``)"""
+        """as ``SAGE.inference``: ``inference.layerwise_inference`` (``_attn_layers`` / ``_gatv2_layer``)"""
         from .inference import layerwise_inference
         return layerwise_inference(self, x_all, rowptr, col, **kw)
 

@@ -1,4 +1,4 @@
-"""inference.gatv2_inference / evaluate over a GATv2 model (the driver ``_gatv2_layers`` on spp_graph_gatv2_forward):
+"""inference.gatv2_inference / evaluate over a GATv2 model (the driver ``_attn_layers`` with ``_gatv2_layer`` on spp_graph_gatv2_forward):
 against the model restated in float64 and against the model's own device forward over L identical full hops, bit for
 bit against itself (slab sizes, ``nodes=``), and ``evaluate``'s predictions and losses against the log-probabilities.
 
@@ -147,7 +147,7 @@ def test_evaluate_is_the_argmax_and_the_nll_of_the_log_probabilities(H, classes,
 
 @pytest.mark.parametrize("share", [False, True], ids=["two_projections", "share_weights"])
 def test_live_activation_matrices_are_what_the_docstring_counts(share):
-    """``_gatv2_layers`` states its memory as arithmetic: three [N, hidden] matrices live at the worst moment (cur, x_l,
+    """``_gatv2_layer`` states its memory as arithmetic: three [N, hidden] matrices live at the worst moment (cur, x_l,
     x_r while projecting; x_l, x_r, nxt while attending), two with share_weights -- the previous layer's matrix must be
     gone once the projections are complete.  Four layers at 400 000 nodes and hidden 256 in fp32: a matrix is
     M = 409.6 MB.  On top the projection holds two GEMM tiles of 65 536 rows (the zero-padded last tile and a product,

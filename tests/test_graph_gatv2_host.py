@@ -337,7 +337,7 @@ def test_planted_faults_leave_the_bounds(fault):
 # ------------------------------------------------------------------------------------------------------ the padding identity
 @pytest.mark.parametrize("H,Cc", [(1, 5), (4, 5), (2, 47), (1, 172)])
 def test_zero_padded_channels_change_nothing(H, Cc):
-    """what ``_gatv2_layers`` relies on: zero rows of W_l / W_r (here: zero columns of the projected rows) and zero
+    """what ``_gatv2_layer`` relies on: zero rows of W_l / W_r (here: zero columns of the projected rows) and zero
     columns of att, sliced away afterwards, give the unpadded result -- ``_gatv2_reference`` on both, float64, so that
     the comparison is of the formula and not of a summation order"""
     from salient_plusplus_amd.inference import _gatv2_pad

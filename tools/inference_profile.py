@@ -19,7 +19,7 @@ the logits: 4 * H per entry (a_src) and 8 * H per target (a_src of the self loop
 ``--model gatv2``: GATv2 3 x hidden at ``--heads`` (1, 2, 4 or 8; ``--share-weights``) through spp_graph_gatv2_forward inside
 ``gatv2_inference``, passes as for gat.  Run it in the same session as ``--model gat`` at the same heads and width, which is its
 yardstick.  At S-papers the last layer's projected rows are [N, heads * Cp] twice (172 classes pad to Cp = 256): heads = 1, or
-``--share-weights`` with fewer classes, is what fits one device (inference._gatv2_layers has the arithmetic).
+``--share-weights`` with fewer classes, is what fits one device (inference._gatv2_layer has the arithmetic).
 
 ``--model sageresinception``: SAGEResInception 3 x hidden scored at a random sample of ``--nodes`` nodes; per layer the
 aggregation seconds as above, the epilogue seconds (events around every spp_resinc_epilogue call, summed; bytes: z, the
