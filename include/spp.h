@@ -1937,6 +1937,81 @@ spp_status spp_graph_gatv2_forward(const spp_graph_gatv2_desc* desc, void* works
 spp_status spp_gatv2_forward_drop(const spp_gatv2_desc* desc, void* stream, float p, int32_t training, uint64_t seed);
 spp_status spp_gatv2_backward_drop(const spp_gatv2_desc* desc, void* stream, float p, int32_t training, uint64_t seed);
 
+/* ------------------------------------------------------------------------- *
+ * f3y  TransformerConv (scaled dot-product attention; Shi et al., "Masked Label Prediction"; PyG's TransformerConv)
+ *      over an MFG hop, on rows the caller has projected:
+ *        q [T, H, C] = lin_query(x_target)     k [S, H, C] = lin_key(x)     v [S, H, C] = lin_value(x)     D = H * C
+ *        e_ij^h     = scale * sum_c q[i,h,c] * k[j,h,c]          (scale: fp32, below; the layer passes 1 / sqrt(C))
+ *        alpha^h    = softmax_j(e_ij^h)
+ *        out[i,h,:] = sum_j alpha_ij^h * v[j,h,:]
+ *      Row i runs over ALL its CSR entries, in CSR order: NO self loop is added, diagonal entries (col == i) are kept,
+ *      and a repeated entry counts as often as it appears (PyG's TransformerConv; not the set_diag convention of the
+ *      GAT and GATv2 entries).
+ *      EMPTY ROWS are therefore a real case: a target without entries gets out = 0, row_sum = 0 and row_max = 0 --
+ *      defined values -- and in the backward grad_q = 0 and nothing else; no NaN, nothing is divided by zero.
+ *
+ *   Layouts: q [T, D], k [S, D] and v [S, D] are rows of x_elem (SPP_ELEM_F32 / _F16 / _BF16, one code for the three),
+ *   each with its own base pointer and its own row stride in elements: k and v may be the two halves of one [S, 2 D]
+ *   matrix (v = k + D, both strides 2 D) or separate matrices; no aliasing is assumed either way.  out and grad_out
+ *   [T, D], row_max and row_sum [T, H], grad_q [T, D], grad_k and grad_v [S, D]: fp32, dense, row-major.
+ *   Alignment, as f3v: the rows of q / k / v to 4 elements (base and stride); out, grad_out, grad_q, grad_k, grad_v to
+ *   16 bytes; row_max, row_sum to 4; rowptr, col to 8.
+ *   Shapes, as f3v: heads in {1, 2, 4, 8}; C % 4 == 0 and C / 4 a power of two; D <= 1024; 0 <= T <= S.  col may be
+ *   NULL when the hop has no entries.  The inputs are finite.
+ *
+ *   spp_transformer_forward: writes out, row_max (the row's largest logit) and row_sum (sum_j exp(e_ij - row_max)).
+ *      One pass over the row with a running maximum per head, from the empty state, in CSR order; weights by expf (the
+ *      library function: DESIGN section 7 f3v records why).  The dot product of a logit is added in ONE order, fixed
+ *      by C alone and walked by both entries: the C products q[c] k[c], each rounded, are added pairwise by xor
+ *      distance of the column index within the head, in the order 1, 2, then C / 2, C / 4, ..., 4, every addition a
+ *      rounded fp32 addition and none fused with a product; then ONE rounded product by scale.  The online softmax is
+ *      csrc/gatv2_core.hip.h's State, unchanged (contraction off, its fused multiply-adds spelled fmaf).  No atomics:
+ *      the same bits in every run.
+ *   spp_transformer_backward: reads the forward's out, row_max, row_sum and grad_out (g).  Per head, with
+ *      alpha_ij = expf(e_ij - row_max) / row_sum (e recomputed, THE FORWARD'S BITS: the order above; no [E, H] array):
+ *        go = g_i . out_i     gv = g_i . v[j]     ge = alpha (gv - go)
+ *        grad_v[j,h,c] += alpha * g[i,h,c]             fp32 atomics, one per column per entry, on a buffer the CALLER
+ *                                                      has zeroed; NULL: not wanted
+ *        grad_k[j,h,c] += ge * scale * q[i,h,c]        likewise, independently NULL-able
+ *        grad_q[i,h,c]  = sum_j ge * scale * k[j,h,c]  written completely, every row, zeros for an empty one
+ *
+ *   Refused with SPP_ERR_INVALID before anything is enqueued, checked in this order (f3v's where the cases coincide):
+ *   a NULL descriptor; heads outside {1, 2, 4, 8}; an unknown x_elem; C <= 0 or C % 4 != 0; C / 4 not a power of two;
+ *   D > 1024; T < 0 or S < T;  -- T == 0 returns SPP_OK here, and touches nothing --  a row stride of q, k or v below
+ *   D or not a multiple of 4; a NULL rowptr, q, k, v, out, row_max or row_sum (backward: or grad_out or grad_q); one
+ *   of them, or col, misaligned (backward: then a misaligned grad_out, grad_q, grad_k or grad_v); a scale that is not
+ *   finite or not positive.  spp_last_error names the failing condition.  SPP_ABI_VERSION stays 6.
+ *   Not built: attention dropout inside the kernels, edge features (PyG's edge_dim), and entries over the resident
+ *   graph.
+ * ------------------------------------------------------------------------- */
+typedef struct spp_transformer_desc {
+  int32_t heads;              /* H: 1, 2, 4 or 8 */
+  int32_t x_elem;             /* q, k and v: SPP_ELEM_F32 / _F16 / _BF16 */
+  float scale;                /* > 0, finite; the logit is scale * (q . k) */
+  int32_t reserved;
+  const int64_t* rowptr_dev;
+  const int64_t* col_dev;
+  int64_t num_targets;        /* T */
+  int64_t num_sources;        /* S >= T */
+  int64_t C;                  /* channels per head */
+  const void* q_dev;          /* [T, D] */
+  int64_t q_stride_elems;
+  const void* k_dev;          /* [S, D] */
+  int64_t k_stride_elems;
+  const void* v_dev;          /* [S, D]; may be k_dev + D of one [S, 2 D] matrix */
+  int64_t v_stride_elems;
+  float* out_dev;             /* fp32 [T, D]: written by the forward, read by the backward */
+  float* row_max_dev;         /* fp32 [T, H]: likewise */
+  float* row_sum_dev;         /* fp32 [T, H]: likewise */
+  const float* grad_out_dev;  /* backward: fp32 [T, D] */
+  float* grad_q_dev;          /* backward: fp32 [T, D] */
+  float* grad_k_dev;          /* backward: fp32 [S, D], zeroed by the caller; NULL: not wanted */
+  float* grad_v_dev;          /* backward: fp32 [S, D], zeroed by the caller; NULL: not wanted */
+} spp_transformer_desc;
+
+spp_status spp_transformer_forward(const spp_transformer_desc* desc, void* stream);
+spp_status spp_transformer_backward(const spp_transformer_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,6 +136,16 @@ class Gatv2Desc(C.Structure):
                 ("grad_att_dev", p)]
 
 
+class TransformerDesc(C.Structure):
+    """spp_transformer_desc: TransformerConv over a hop on projected rows q [T, H*C], k and v [S, H*C]; forward and
+    backward"""
+    _fields_ = [("heads", i32), ("x_elem", i32), ("scale", C.c_float), ("reserved", i32), ("rowptr_dev", p),
+                ("col_dev", p), ("num_targets", i64), ("num_sources", i64), ("C", i64), ("q_dev", p),
+                ("q_stride_elems", i64), ("k_dev", p), ("k_stride_elems", i64), ("v_dev", p), ("v_stride_elems", i64),
+                ("out_dev", p), ("row_max_dev", p), ("row_sum_dev", p), ("grad_out_dev", p), ("grad_q_dev", p),
+                ("grad_k_dev", p), ("grad_v_dev", p)]
+
+
 class GcnDinvDesc(C.Structure):
     """spp_gcn_dinv_desc: gcn_norm's first pass alone, dinv [num_nodes] over a whole graph"""
     _fields_ = [("fill", i32), ("reserved", i32), ("rowptr_dev", p), ("num_nodes", i64), ("w_dev", p), ("dinv_dev", p)]
@@ -401,6 +411,9 @@ SIGNATURES = {
     # attention dropout (spp.h f3x): the training pair + (p, training, seed); the mask is spp_gat_mh_attn_keep's
     "spp_gatv2_forward_drop": (C.c_int, [C.POINTER(Gatv2Desc), p, C.c_float, i32, C.c_uint64]),
     "spp_gatv2_backward_drop": (C.c_int, [C.POINTER(Gatv2Desc), p, C.c_float, i32, C.c_uint64]),
+    # TransformerConv over a hop (spp.h f3y)
+    "spp_transformer_forward": (C.c_int, [C.POINTER(TransformerDesc), p]),
+    "spp_transformer_backward": (C.c_int, [C.POINTER(TransformerDesc), p]),
 }
 SPP_COMM_ID_BYTES = 128
 SPP_IPC_HANDLE_BYTES = 64

@@ -1,0 +1,326 @@
+// f3y: TransformerConv (Shi et al., "Masked Label Prediction"; PyG's TransformerConv) training over an MFG hop: the
+// forward / backward pair behind spp_transformer_forward / spp_transformer_backward of include/spp.h.
+//     q [T, H, C] = lin_query(x_target),   k [S, H, C] = lin_key(x),   v [S, H, C] = lin_value(x)   (projected by the caller)
+//     e_ij^h     = scale * sum_c q[i,h,c] * k[j,h,c]
+//     out[i,h,:] = sum_j softmax_j(e_ij^h) * v[j,h,:]
+// over ALL CSR entries of row i in CSR order: no self loop, diagonal entries kept, a repeated entry counted as often as
+// it appears.  A row without entries is a real case: out = 0, row_max = 0, row_sum = 0, grad_q = 0.
+// What differs from gatv2.hip: the logit is a plain dot product, the message row (v) is not the key row (k), the
+// backward has three row gradients, and there is no grad_att (so no LDS reduction and one group per target).  What is
+// kept: gatv2_core.hip.h's lane mapping, per-head online softmax (State), butterfly and (NQ, CPH) dispatch, unchanged;
+// several neighbours' loads in flight per round; one fp32 atomic per column per entry on contiguous wave-wide segments.
+// Not here: attention dropout in the kernels, edge features, and kernels over the resident graph.
+#include "gatv2_core.hip.h"
+
+#include <cmath>
+
+namespace spp {
+
+using namespace gatv2;
+
+constexpr int kTfNT = 256;
+
+// THE LOGIT'S SUMMATION TREE, walked bit for bit by both kernels.  The C products q[c] k[c] of a head, each rounded,
+// are added pairwise by xor distance of the column index within the head, in the order 1, 2, then C / 2, C / 4, ..., 4;
+// every addition is a rounded fp32 addition of two partial sums that are the same bits on both sides, so whoever
+// holds a partner ends with the same bits.  Then ONE rounded product by scale.  No fused multiply-add anywhere in it
+// (contraction is off in both kernels).  The backward recomputes alpha = expf(e - row_max) / row_sum from THIS e:
+// with a logit added in another order, a row dominated by one entry got alpha = 1 + (e' - e) -- 1e-6 off at logits of
+// 18, seen at model level -- where the forward's own weight is 1 to the bit.
+// Forward: distances 1 and 2 are inside a lane's 4-column piece (piece4), distances >= 4 are piece distances: chunks of
+// the head in the lane first (widest), then the butterfly over the head's lanes, widest first.
+__device__ __forceinline__ float piece4(const f4& a, const f4& b) {
+#pragma clang fp contract(off)
+  return (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w);
+}
+
+// neighbours in flight per round: every one is a k piece set AND a v piece set, twice gatv2's Lane::NB row data, so at
+// NQ = 4 (16 columns per lane and row) one fewer than there: 2 * 2 * 16 = 64 registers of rows, as NQ = 2 has with 4
+template <int NQ>
+constexpr int tf_nb() { return NQ <= 2 ? 4 : 2; }
+
+// Forward.  lpr lanes per target, 4 columns per lane and chunk (gatv2_core.hip.h's mapping); the lane keeps its pieces of
+// q[t] for the whole row.  Per round: NB ids, then their k and v pieces, then the partial dots, then ONE butterfly that
+// carries all NB * HL values (the logit's tree above); the logit is the butterfly's sum times scale (one product, the
+// same bits in every lane of the head's segment); State::take does the online softmax on the v pieces.  The row starts from the empty state.
+// No atomics: the same bits in every run.
+template <typename Tin, int NQ, int CPH>
+__global__ __launch_bounds__(kTfNT) void k_transformer_fwd(const int64_t* __restrict__ rowptr,
+                                                           const int64_t* __restrict__ col, int64_t T, const Tin* qm,
+                                                           int64_t q_stride, const Tin* km, int64_t k_stride,
+                                                           const Tin* vm, int64_t v_stride, float scale, int lpr_log2,
+                                                           int seg_log2, int g_log2, int H, float* __restrict__ out,
+                                                           float* __restrict__ row_max, float* __restrict__ row_sum) {
+#pragma clang fp contract(off)
+  constexpr int HL = NQ / CPH, NB = tf_nb<NQ>();
+  const int lpr = 1 << lpr_log2, lane = threadIdx.x & (lpr - 1);
+  const int64_t t = ((int64_t)blockIdx.x * kTfNT + threadIdx.x) >> lpr_log2;
+  if (t >= T) return;  // whole groups leave together (the shuffles below stay inside a group)
+  const int64_t D = (int64_t)NQ * lpr * 4;
+  int64_t c0[NQ];
+  f4 qv[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    c0[q] = ((int64_t)q * lpr + lane) * 4;
+    qv[q] = load4(qm + t * q_stride + c0[q]);
+  }
+  State<NQ, CPH> st;
+  st.clear();
+  const int64_t b = rowptr[t], e = rowptr[t + 1];
+  for (int64_t k0 = b; k0 < e; k0 += NB) {
+    int64_t j[NB];
+#pragma unroll
+    for (int u = 0; u < NB; ++u) j[u] = col[k0 + u < e ? k0 + u : e - 1];  // clamped, unpredicated
+    f4 kv[NB][NQ], vv[NB][NQ];
+#pragma unroll
+    for (int u = 0; u < NB; ++u)
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        kv[u][q] = load4(km + j[u] * k_stride + c0[q]);
+        vv[u][q] = load4(vm + j[u] * v_stride + c0[q]);
+      }
+    float pd[NB * HL];
+#pragma unroll
+    for (int u = 0; u < NB; ++u)
+#pragma unroll
+      for (int hl = 0; hl < HL; ++hl) {
+        float ch[CPH];  // the head's chunks: piece distance 64 * (chunk distance), the widest of the tree's >= 4 part
+#pragma unroll
+        for (int q = 0; q < CPH; ++q) ch[q] = piece4(qv[hl * CPH + q], kv[u][hl * CPH + q]);
+#pragma unroll
+        for (int d = CPH / 2; d >= 1; d >>= 1)
+#pragma unroll
+          for (int q = 0; q < d; ++q) ch[q] += ch[q + d];
+        pd[u * HL + hl] = ch[0];
+      }
+    butterfly(pd, seg_log2);
+#pragma unroll
+    for (int u = 0; u < NB; ++u) {
+      if (k0 + u >= e) continue;
+#pragma unroll
+      for (int hl = 0; hl < HL; ++hl) st.take(hl, pd[u * HL + hl] * scale, vv[u]);
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const int hl = q / CPH;
+    const int p = q * lpr + lane;
+    const bool empty = st.ss[hl] == 0.f;  // a row without entries: out, row_max and row_sum are 0, nothing is divided
+    f4 r = {0.f, 0.f, 0.f, 0.f};
+    if (!empty) r = st.result(q);
+    *reinterpret_cast<float4*>(out + t * D + (int64_t)p * 4) = make_float4(r.x, r.y, r.z, r.w);
+    if ((p & ((1 << g_log2) - 1)) == 0) {  // the head's first piece
+      row_max[t * H + (p >> g_log2)] = empty ? 0.f : st.mm[hl];
+      row_sum[t * H + (p >> g_log2)] = st.ss[hl];
+    }
+  }
+}
+
+// Backward.  ONE column per lane and step, c = lane + lpt * i, i < NS, lpt = min(64, D) lanes per target, as k_gatv2_bwd:
+// the fp32 atomics of an entry on grad_k and grad_v are contiguous 4 * lpt-byte segments, one atomic per column per
+// entry and buffer.  A head is C consecutive columns: C <= lpt lanes of one step (SPH = 1) or SPH = C / 64 whole steps;
+// a lane takes part in HL = NS / SPH heads.  Per entry the logit (recomputed; alpha = expf(e - row_max) / row_sum, no
+// [E, H] array) and gv^h = g_i . v[j] are reduced by one butterfly; grad_q stays in registers across the row and is
+// written once, zeros for a row without entries (whose row_sum = 0 is never divided by).  The logit is the forward's,
+// bit for bit (the tree at the top of the file; contraction off, so that the product by scale is rounded before
+// row_max is subtracted, as it is there).
+template <typename Tin, int NS, int SPH>
+__global__ __launch_bounds__(kTfNT) void k_transformer_bwd(const int64_t* __restrict__ rowptr,
+                                                           const int64_t* __restrict__ col, int64_t T, const Tin* qm,
+                                                           int64_t q_stride, const Tin* km, int64_t k_stride,
+                                                           const Tin* vm, int64_t v_stride, float scale, int lpt_log2,
+                                                           int seg_log2, int c_log2, int H,
+                                                           const float* __restrict__ out,
+                                                           const float* __restrict__ row_max,
+                                                           const float* __restrict__ row_sum,
+                                                           const float* __restrict__ g, float* __restrict__ grad_q,
+                                                           float* grad_k, float* grad_v) {
+#pragma clang fp contract(off)
+  constexpr int HL = NS / SPH;
+  const int lpt = 1 << lpt_log2;
+  const int lane = threadIdx.x & (lpt - 1);
+  const int64_t D = (int64_t)NS * lpt;
+  const int64_t t = ((int64_t)blockIdx.x * kTfNT + threadIdx.x) >> lpt_log2;
+  if (t >= T) return;  // whole groups leave together
+  const int64_t b = rowptr[t], e = rowptr[t + 1];
+  float gv[NS], qv[NS], gq[NS], go[HL], m[HL], inv_s[HL];
+#pragma unroll
+  for (int hl = 0; hl < HL; ++hl) {
+    const int head = (lane + lpt * hl * SPH) >> c_log2;
+    const float s = row_sum[t * H + head];
+    m[hl] = row_max[t * H + head];
+    inv_s[hl] = s > 0.f ? 1.f / s : 0.f;
+    go[hl] = 0.f;
+  }
+#pragma unroll
+  for (int i = 0; i < NS; ++i) {
+    const int64_t c = lane + lpt * i;
+    gv[i] = g[t * D + c];
+    qv[i] = load1(qm + t * q_stride + c);
+    gq[i] = 0.f;
+    go[i / SPH] += gv[i] * out[t * D + c];
+  }
+  for (int d = (1 << seg_log2) >> 1; d >= 1; d >>= 1)
+#pragma unroll
+    for (int hl = 0; hl < HL; ++hl) go[hl] += __shfl_xor(go[hl], d, kWave);
+  int64_t jn = b < e ? col[b] : 0;  // the next entry's id is read one entry ahead of its rows
+  for (int64_t k = b; k < e; ++k) {
+    const int64_t j = jn;
+    jn = col[k + 1 < e ? k + 1 : k];
+    float kx[NS], vx[NS], pp[NS], pe[HL], gh[HL];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      kx[i] = load1(km + j * k_stride + lane + lpt * i);
+      vx[i] = load1(vm + j * v_stride + lane + lpt * i);
+    }
+#pragma unroll
+    for (int hl = 0; hl < HL; ++hl) gh[hl] = 0.f;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      pp[i] = qv[i] * kx[i];
+      gh[i / SPH] += gv[i] * vx[i];
+    }
+    // the logit's tree (top of the file) with one column per lane and step: column distances 1 and 2 are lane
+    // distances, every step's value on its own; then the head's steps (column distance 64 * step distance), widest
+    // first; then the lane distances from the segment's half down to 4
+#pragma unroll
+    for (int d = 1; d <= 2; d <<= 1)
+#pragma unroll
+      for (int i = 0; i < NS; ++i) pp[i] += __shfl_xor(pp[i], d, kWave);
+#pragma unroll
+    for (int hl = 0; hl < HL; ++hl) {
+#pragma unroll
+      for (int d = SPH / 2; d >= 1; d >>= 1)
+#pragma unroll
+        for (int i = 0; i < d; ++i) pp[hl * SPH + i] += pp[hl * SPH + i + d];
+      pe[hl] = pp[hl * SPH];
+    }
+    for (int d = (1 << seg_log2) >> 1; d >= 4; d >>= 1)
+#pragma unroll
+      for (int hl = 0; hl < HL; ++hl) pe[hl] += __shfl_xor(pe[hl], d, kWave);
+    for (int d = (1 << seg_log2) >> 1; d >= 1; d >>= 1)
+#pragma unroll
+      for (int hl = 0; hl < HL; ++hl) gh[hl] += __shfl_xor(gh[hl], d, kWave);
+    float a[HL], ges[HL];
+#pragma unroll
+    for (int hl = 0; hl < HL; ++hl) {
+      a[hl] = expf(pe[hl] * scale - m[hl]) * inv_s[hl];
+      ges[hl] = a[hl] * (gh[hl] - go[hl]) * scale;  // ge * scale
+    }
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      gq[i] += ges[i / SPH] * kx[i];
+      if (grad_k) unsafeAtomicAdd(grad_k + j * D + lane + lpt * i, ges[i / SPH] * qv[i]);
+      if (grad_v) unsafeAtomicAdd(grad_v + j * D + lane + lpt * i, a[i / SPH] * gv[i]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NS; ++i) grad_q[t * D + lane + lpt * i] = gq[i];
+}
+
+}  // namespace spp
+
+using namespace spp;
+using namespace spp::gatv2;
+
+// fn(IC<NS>{}, IC<SPH>{}): the backward's steps per lane and steps per head (NS / SPH <= 8 heads)
+template <class Fn>
+static void with_tf_bwd_shape(int ns, int sph, Fn&& fn) {
+  switch (ns * 32 + sph) {
+    case 1 * 32 + 1: fn(IC<1>{}, IC<1>{}); break;
+    case 2 * 32 + 1: fn(IC<2>{}, IC<1>{}); break;
+    case 2 * 32 + 2: fn(IC<2>{}, IC<2>{}); break;
+    case 4 * 32 + 1: fn(IC<4>{}, IC<1>{}); break;
+    case 4 * 32 + 2: fn(IC<4>{}, IC<2>{}); break;
+    case 4 * 32 + 4: fn(IC<4>{}, IC<4>{}); break;
+    case 8 * 32 + 1: fn(IC<8>{}, IC<1>{}); break;
+    case 8 * 32 + 2: fn(IC<8>{}, IC<2>{}); break;
+    case 8 * 32 + 4: fn(IC<8>{}, IC<4>{}); break;
+    case 8 * 32 + 8: fn(IC<8>{}, IC<8>{}); break;
+    case 16 * 32 + 2: fn(IC<16>{}, IC<2>{}); break;
+    case 16 * 32 + 4: fn(IC<16>{}, IC<4>{}); break;
+    case 16 * 32 + 8: fn(IC<16>{}, IC<8>{}); break;
+    default: fn(IC<16>{}, IC<16>{}); break;
+  }
+}
+
+// The checks of both entries, in the order include/spp.h documents: descriptor, head count, element code, C, power of
+// two, D, sizes (T == 0 is decided by the caller right after), strides, NULL buffers, alignment, scale.  Nothing here
+// touches the device.
+static spp_status tf_check_shape(const spp_transformer_desc* d, const char* who) {
+  SPP_REQUIRE(d != nullptr, "%s: NULL descriptor", who);
+  SPP_REQUIRE(d->heads == 1 || d->heads == 2 || d->heads == 4 || d->heads == 8,
+              "%s: heads must be 1, 2, 4 or 8 (got %d)", who, (int)d->heads);
+  SPP_REQUIRE(elem_ok(d->x_elem), "%s: unknown element code %d", who, (int)d->x_elem);
+  SPP_REQUIRE(d->C > 0 && d->C % 4 == 0, "%s: needs C > 0 and C %% 4 == 0 (got %lld)", who, (long long)d->C);
+  SPP_REQUIRE(pow2(d->C / 4), "%s: built for C / 4 a power of two (got C = %lld)", who, (long long)d->C);
+  SPP_REQUIRE(d->C <= 1024 && d->heads * d->C <= 1024, "%s: needs D = heads * C <= 1024", who);
+  SPP_REQUIRE(d->num_targets >= 0 && d->num_sources >= d->num_targets, "%s: needs 0 <= T <= S", who);
+  return SPP_OK;
+}
+static spp_status tf_check_rows(const spp_transformer_desc* d, const char* who, bool backward) {
+  const int64_t D = d->heads * d->C, esz = elem_bytes(d->x_elem);
+  SPP_REQUIRE(d->q_stride_elems >= D && d->k_stride_elems >= D && d->v_stride_elems >= D &&
+                  d->q_stride_elems % 4 == 0 && d->k_stride_elems % 4 == 0 && d->v_stride_elems % 4 == 0,
+              "%s: a row stride is smaller than D or not a multiple of 4 elements", who);
+  SPP_REQUIRE(d->rowptr_dev && d->q_dev && d->k_dev && d->v_dev && d->out_dev && d->row_max_dev && d->row_sum_dev &&
+                  (!backward || (d->grad_out_dev && d->grad_q_dev)),
+              "%s: NULL buffer", who);
+  SPP_REQUIRE(aligned_to(d->q_dev, 4 * esz) && aligned_to(d->k_dev, 4 * esz) && aligned_to(d->v_dev, 4 * esz) &&
+                  aligned_to(d->out_dev, 16) && aligned_to(d->row_max_dev, 4) && aligned_to(d->row_sum_dev, 4) &&
+                  aligned_to(d->rowptr_dev, 8) && aligned_to(d->col_dev, 8),
+              "%s: misaligned buffer (rows: 4 elements; out: 16 bytes)", who);
+  SPP_REQUIRE(!backward || (aligned_to(d->grad_out_dev, 16) && aligned_to(d->grad_q_dev, 16) &&
+                            aligned_to(d->grad_k_dev, 16) && aligned_to(d->grad_v_dev, 16)),
+              "%s: misaligned buffer (grad_out, grad_q, grad_k, grad_v: 16 bytes)", who);
+  SPP_REQUIRE(std::isfinite(d->scale) && d->scale > 0.f, "%s: scale must be finite and positive", who);
+  return SPP_OK;
+}
+
+extern "C" spp_status spp_transformer_forward(const spp_transformer_desc* d, void* stream) {
+  const char* who = "spp_transformer_forward";
+  SPP_TRY(tf_check_shape(d, who));
+  if (d->num_targets == 0) return SPP_OK;
+  SPP_TRY(tf_check_rows(d, who, false));
+  const int64_t T = d->num_targets;
+  const Shape sh = shape_of(d->heads, d->C);
+  const int lpr_log2 = sh.lpr_log2, seg_log2 = sh.seg_log2, g_log2 = sh.g_log2, nq = sh.nq, cph = sh.cph;
+  const unsigned grid = (unsigned)ceil_div(T << lpr_log2, kTfNT);
+  with_elem(d->x_elem, [&](auto tin) {
+    with_fwd_shape(nq, cph, [&](auto q, auto c) {
+      using Tin = typename decltype(tin)::type;
+      hipLaunchKernelGGL((k_transformer_fwd<Tin, decltype(q)::value, decltype(c)::value>), dim3(grid), dim3(kTfNT), 0,
+                         as_stream(stream), d->rowptr_dev, d->col_dev, T, static_cast<const Tin*>(d->q_dev),
+                         d->q_stride_elems, static_cast<const Tin*>(d->k_dev), d->k_stride_elems,
+                         static_cast<const Tin*>(d->v_dev), d->v_stride_elems, d->scale, lpr_log2, seg_log2, g_log2,
+                         (int)d->heads, d->out_dev, d->row_max_dev, d->row_sum_dev);
+    });
+  });
+  SPP_HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
+
+extern "C" spp_status spp_transformer_backward(const spp_transformer_desc* d, void* stream) {
+  const char* who = "spp_transformer_backward";
+  SPP_TRY(tf_check_shape(d, who));
+  if (d->num_targets == 0) return SPP_OK;  // nothing is touched: grad_k / grad_v stay as the caller zeroed them
+  SPP_TRY(tf_check_rows(d, who, true));
+  const int64_t T = d->num_targets, D = d->heads * d->C;
+  const int lpt_log2 = log2_of(std::min<int64_t>(D, kWave)), lpt = 1 << lpt_log2;
+  const int ns = (int)(D / lpt), sph = (int)std::max<int64_t>(1, d->C / kWave);
+  const int seg_log2 = log2_of(std::min<int64_t>(d->C, lpt)), c_log2 = log2_of(d->C);
+  const unsigned grid = (unsigned)ceil_div(T << lpt_log2, kTfNT);
+  with_elem(d->x_elem, [&](auto tin) {
+    with_tf_bwd_shape(ns, sph, [&](auto n, auto s) {
+      using Tin = typename decltype(tin)::type;
+      hipLaunchKernelGGL((k_transformer_bwd<Tin, decltype(n)::value, decltype(s)::value>), dim3(grid), dim3(kTfNT), 0,
+                         as_stream(stream), d->rowptr_dev, d->col_dev, T, static_cast<const Tin*>(d->q_dev),
+                         d->q_stride_elems, static_cast<const Tin*>(d->k_dev), d->k_stride_elems,
+                         static_cast<const Tin*>(d->v_dev), d->v_stride_elems, d->scale, lpt_log2, seg_log2, c_log2,
+                         (int)d->heads, d->out_dev, d->row_max_dev, d->row_sum_dev, d->grad_out_dev, d->grad_q_dev,
+                         d->grad_k_dev, d->grad_v_dev);
+    });
+  });
+  SPP_HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}

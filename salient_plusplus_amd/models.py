@@ -1379,6 +1379,213 @@ class GATv2(torch.nn.Module):
 
 
 # --------------------------------------------------------------------------------------------
+# GraphTransformer  (PyG's TransformerConv, scaled dot-product attention: csrc/transformer_conv.hip, spp.h f3y)
+# --------------------------------------------------------------------------------------------
+_TRANSFORMER_HEADS = (1, 2, 4, 8)   # the head counts spp_transformer_forward / _backward are built for
+
+
+def _transformer_reference(q, k, v, rowptr, col, scale, p=0.0):
+    """TransformerConv's message passing in plain torch ops, on the projected rows: q [T, H, C] = lin_query(x_target),
+    k [S, H, C] = lin_key(x), v [S, H, C] = lin_value(x) -> out [T, H, C] (fp32; float64 for float64 rows):
+    e_ij^h = scale * q[i,h] . k[j,h], alpha = softmax_j(e), out[i,h] = sum_j alpha_ij^h v[j,h] over ALL CSR entries of
+    row i -- no self loop, diagonal entries kept, a repeated entry counted as often as it appears -- and zeros for a
+    row without entries.  The path for everything the kernels do not read: CPU tensors, head counts outside
+    {1, 2, 4, 8}, C with C / 4 not a power of two, H * C > 1024; and for p > 0 in training, where F.dropout on alpha
+    draws torch's own mask (attention dropout inside the kernels is not built for this layer)."""
+    T, H = q.size(0), q.size(1)
+    dt = torch.float64 if q.dtype == torch.float64 else torch.float32
+    q, k, v = q.to(dt), k.to(dt), v.to(dt)
+    dst = torch.repeat_interleave(torch.arange(T, device=col.device), rowptr[1:] - rowptr[:-1])
+    e = (q[dst] * k[col]).sum(-1) * scale                                   # [E, H]
+    emax = torch.full((T, H), float("-inf"), dtype=dt, device=e.device)
+    emax = emax.scatter_reduce(0, dst[:, None].expand(-1, H), e, "amax")
+    w = torch.exp(e - emax[dst])
+    den = torch.zeros((T, H), dtype=dt, device=e.device).index_add_(0, dst, w)
+    alpha = w / den[dst]
+    if p > 0.0:
+        alpha = F.dropout(alpha, p, training=True)
+    return torch.zeros((T,) + tuple(v.shape[1:]), dtype=dt, device=e.device).index_add_(0, dst, alpha[:, :, None] * v[col])
+
+
+def _transformer_desc(q, k, v, H, rowptr, col, scale, out, rmax, rsum, **grads):
+    """spp_transformer_desc for projected rows q [T, D], k and v [S, D] (unit column stride, one dtype)"""
+    S, T, D = k.size(0), q.size(0), q.size(1)
+    return nat.TransformerDesc(heads=H, x_elem=_ELEM[q.dtype], scale=float(scale), rowptr_dev=_p(rowptr),
+                               col_dev=_p(col), num_targets=T, num_sources=S, C=D // H, q_dev=_p(q),
+                               q_stride_elems=q.stride(0) if T > 1 else D, k_dev=_p(k),
+                               k_stride_elems=k.stride(0) if S > 1 else D, v_dev=_p(v),
+                               v_stride_elems=v.stride(0) if S > 1 else D, out_dev=_p(out), row_max_dev=_p(rmax),
+                               row_sum_dev=_p(rsum), **{n: _p(t) for n, t in grads.items() if t is not None})
+
+
+def _transformer_kernels_read(q, k, v, H, Cc):
+    """the rows and widths spp_transformer_forward accepts (spp.h f3y)"""
+    g = Cc // 4
+    return (q.is_cuda and H in _TRANSFORMER_HEADS and Cc > 0 and Cc % 4 == 0 and g & (g - 1) == 0 and H * Cc <= 1024 and
+            q.dtype in _ELEM and k.dtype == q.dtype and v.dtype == q.dtype and
+            all(t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 4 == 0 and
+                t.data_ptr() % (4 * t.element_size()) == 0 for t in (q, k, v)))
+
+
+class _TransformerLayer(torch.autograd.Function):
+    """TransformerConv's message passing as ONE node on the projected rows: (q [T, D], k [S, D], v [S, D]) -> out
+    [T, H, C] fp32, spp_transformer_forward / spp_transformer_backward.  The rows are fp32, fp16 or bf16 (under bf16
+    autocast the projections outside the node give bf16 rows, which the kernels read as such); k and v may be views
+    of one [S, 2 D] matrix.  The node runs with autocast off, returns fp32 and casts grad_q / grad_k / grad_v back to
+    the rows' dtype; a gradient nobody needs is not computed (NULL in the descriptor)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, rowptr, col, heads, scale):
+        with _no_autocast():
+            L = nat.load()
+            nat.require_device()
+            T, D = q.shape
+            f32 = dict(dtype=torch.float32, device=q.device)
+            out = torch.empty((T, heads, D // heads), **f32)
+            rmax, rsum = torch.empty((T, heads), **f32), torch.empty((T, heads), **f32)
+            nat.check(L.spp_transformer_forward(
+                C.byref(_transformer_desc(q, k, v, heads, rowptr, col, scale, out, rmax, rsum)), _stream()))
+            ctx.save_for_backward(q, k, v, rowptr, col, out, rmax, rsum)
+            ctx.heads, ctx.scale = int(heads), float(scale)
+            return out
+
+    @staticmethod
+    def backward(ctx, g):
+        with _no_autocast():
+            q, k, v, rowptr, col, out, rmax, rsum = ctx.saved_tensors
+            (T, D), S = q.shape, k.size(0)
+            g = g.to(torch.float32).contiguous()
+            f32 = dict(dtype=torch.float32, device=q.device)
+            g_q = torch.empty((T, D), **f32)
+            g_k = torch.zeros((S, D), **f32) if ctx.needs_input_grad[1] else None
+            g_v = torch.zeros((S, D), **f32) if ctx.needs_input_grad[2] else None
+            d = _transformer_desc(q, k, v, ctx.heads, rowptr, col, ctx.scale, out, rmax, rsum, grad_out_dev=g,
+                                  grad_q_dev=g_q, grad_k_dev=g_k, grad_v_dev=g_v)
+            nat.check(nat.load().spp_transformer_backward(C.byref(d), _stream()))
+            return (g_q.to(q.dtype) if ctx.needs_input_grad[0] else None, g_k.to(k.dtype) if g_k is not None else None,
+                    g_v.to(v.dtype) if g_v is not None else None, None, None, None, None)
+
+
+class TransformerConv(torch.nn.Module):
+    """torch_geometric.nn.TransformerConv(in, out, heads=1, concat=True, beta=False, dropout=0, edge_dim=None,
+    bias=True, root_weight=True) (Shi et al., "Masked Label Prediction: Unified Message Passing Model for
+    Semi-Supervised Classification") on a bipartite ((x, x_target), adj_t), with PyG's parameter names (a PyG state
+    dict loads): lin_key, lin_query, lin_value, each [H * out, in] with a bias; with ``root_weight`` lin_skip of the
+    output's width (H * out with ``concat``, else out), whose bias is ``bias``; with ``beta and root_weight`` lin_beta
+    [1, 3 * width] without a bias.
+
+        q = lin_query(x_target) [T, H, C],  k = lin_key(x) [S, H, C],  v = lin_value(x) [S, H, C]
+        e_ij^h = q[i,h] . k[j,h] / sqrt(C),   out[i,h] = sum_j softmax_j(e_ij^h) v[j,h]
+
+    over ALL entries of row i as adj_t has them: no self loop is added, diagonal entries stay, a repeated entry counts
+    as often as it appears, and a target without entries gets zeros.  Then the heads are concatenated or averaged;
+    with ``root_weight`` x_r = lin_skip(x_target) is added, or, with ``beta``, out = b x_r + (1 - b) out with
+    b = sigmoid(lin_beta([out, x_r, out - x_r])).  The projections, the skip and the gate are plain torch; the message
+    passing is _TransformerLayer (csrc/transformer_conv.hip) for CUDA rows with H in {1, 2, 4, 8}, C % 4 == 0 with
+    C / 4 a power of two and H * C <= 1024, and _transformer_reference, the same function in plain torch ops, for
+    everything else.
+
+    ``dropout`` = p in [0, 1): F.dropout(alpha, p, training) on the attention coefficients.  p = 0 and eval mode run
+    exactly the paths above; training with p > 0 takes _transformer_reference with torch's own mask (attention dropout
+    inside the kernels is not built for this layer).  ``edge_dim`` other than None (edge features) is not built:
+    NotImplementedError."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, beta=False, dropout=0.0, edge_dim=None,
+                 bias=True, root_weight=True):
+        super().__init__()
+        if edge_dim is not None:
+            raise NotImplementedError("TransformerConv: edge features (edge_dim) are not built; use edge_dim=None")
+        if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
+            raise ValueError(f"heads must be a positive int, got {heads!r}")
+        if isinstance(dropout, bool) or not isinstance(dropout, (int, float)) or not 0.0 <= dropout < 1.0:
+            raise ValueError(f"dropout must be a number in [0, 1), got {dropout!r}")
+        self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
+        self.concat, self.root_weight = bool(concat), bool(root_weight)
+        self.beta = bool(beta) and self.root_weight
+        self.dropout = float(dropout)
+        self.lin_key = torch.nn.Linear(in_channels, heads * out_channels)
+        self.lin_query = torch.nn.Linear(in_channels, heads * out_channels)
+        self.lin_value = torch.nn.Linear(in_channels, heads * out_channels)
+        width = heads * out_channels if concat else out_channels
+        self.lin_skip = torch.nn.Linear(in_channels, width, bias=bool(bias)) if self.root_weight else None
+        self.lin_beta = torch.nn.Linear(3 * width, 1, bias=False) if self.beta else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for lin in (self.lin_key, self.lin_query, self.lin_value, self.lin_skip, self.lin_beta):   # PyG: each Linear's own
+            if lin is not None:
+                lin.reset_parameters()
+
+    def forward(self, x_pair, adj_t):
+        x, x_target = x_pair
+        rowptr, col, _ = adj_t.csr()
+        S, T, H, Cc = x.size(0), x_target.size(0), self.heads, self.out_channels
+        if not torch.is_autocast_enabled(x.device.type):        # (autocast casts the GEMM's operands itself)
+            x, x_target = x.to(self.lin_key.weight.dtype), x_target.to(self.lin_query.weight.dtype)
+        q, k, v = self.lin_query(x_target), self.lin_key(x), self.lin_value(x)
+        scale = 1.0 / float(Cc) ** 0.5
+        p = self.dropout if self.training else 0.0
+        if p == 0.0 and _transformer_kernels_read(q, k, v, H, Cc):
+            out = _TransformerLayer.apply(q, k, v, rowptr, col, H, scale)
+        else:
+            out = _transformer_reference(q.view(T, H, Cc), k.view(S, H, Cc), v.view(S, H, Cc), rowptr, col, scale, p)
+        out = out.reshape(T, H * Cc) if self.concat else out.mean(1)
+        if self.root_weight:
+            x_r = self.lin_skip(x_target)
+            if self.lin_beta is not None:
+                b = torch.sigmoid(self.lin_beta(torch.cat([out, x_r, out - x_r], -1)))
+                out = b * x_r + (1 - b) * out
+            else:
+                out = out + x_r
+        return out
+
+
+class GraphTransformer(torch.nn.Module):
+    """GAT's shape with TransformerConv layers (the UniMP model without label propagation): ``num_layers``
+    TransformerConv, ReLU + dropout 0.5 between layers, log_softmax.  Every hidden layer is ``heads`` heads of
+    ``hidden_channels // heads`` channels, concatenated (the hidden width stays ``hidden_channels``, which must be a
+    multiple of ``heads``); the last layer is the mean of its heads.  ``beta`` and ``attn_dropout`` are every conv's
+    ``beta`` and ``dropout``.
+
+    There is no ``inference`` method: exact layer-wise scoring over the resident graph (and the partitioned, field
+    and fp8 entries) is not built for this model.  Evaluate it batch-wise, through this forward on sampled batches in
+    eval mode, as the reference evaluates its models."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, heads=1, beta=False, attn_dropout=0.0):
+        super().__init__()
+        if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
+            raise ValueError(f"heads must be a positive int, got {heads!r}")
+        if hidden_channels % heads != 0:
+            raise ValueError(f"hidden_channels ({hidden_channels}) must be a multiple of heads ({heads})")
+        self.num_layers = num_layers
+        self.hidden_channels = hidden_channels
+        self.heads = heads
+        kw = dict(heads=heads, beta=beta, dropout=attn_dropout)
+        c = hidden_channels // heads
+        self.convs = torch.nn.ModuleList()
+        self.convs.append(TransformerConv(in_channels, c, concat=True, **kw))
+        for _ in range(num_layers - 2):
+            self.convs.append(TransformerConv(hidden_channels, c, concat=True, **kw))
+        self.convs.append(TransformerConv(hidden_channels, out_channels, concat=False, **kw))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for conv in self.convs:
+            conv.reset_parameters()
+            conv.apply(init_weights)
+
+    def forward(self, x, adjs):
+        if isinstance(x, (TableRows, RowRefs)):
+            x = x.materialize()
+        for i, (adj_t, _e_id, size) in enumerate(adjs):
+            x_target = x[:size[1]]
+            x = self.convs[i]((x, x_target), adj_t)
+            if i != self.num_layers - 1:
+                x = relu_dropout(x, 0.5, self.training)
+        return torch.log_softmax(x, dim=-1)
+
+
+# --------------------------------------------------------------------------------------------
 # GIN  (driver/models.py:234-283: GINConv(Sequential(Linear, BatchNorm1d, ReLU, Linear, ReLU)), eps = 0)
 # --------------------------------------------------------------------------------------------
 _SUM_GATHER_MIN_WORK = 1 << 22      # E x F from which the input gradient is gathered, as in the mean's backward
@@ -1934,9 +2141,11 @@ _UNSUPPORTED_MODELS = {"sageclassic": "not used in the paper", "jknet": "not use
 
 def get_model_type(model_name):
     """driver/main.py:74-95 for the four models the reference marks as working (names case-insensitive), "gcn" (GCN,
-    which the reference leaves unused) and "gatv2" (GATv2, which the reference does not have)"""
+    which the reference leaves unused), "gatv2" (GATv2) and "transformer" (GraphTransformer), which the reference does
+    not have"""
     name = model_name.lower()
-    models = {"sage": SAGE, "gat": GAT, "gin": GIN, "sageresinception": SAGEResInception, "gcn": GCN, "gatv2": GATv2}
+    models = {"sage": SAGE, "gat": GAT, "gin": GIN, "sageresinception": SAGEResInception, "gcn": GCN, "gatv2": GATv2,
+              "transformer": GraphTransformer}
     if name in models:
         return models[name]
     if name in _UNSUPPORTED_MODELS:
