@@ -1981,8 +1981,8 @@ spp_status spp_gatv2_backward_drop(const spp_gatv2_desc* desc, void* stream, flo
  *   D or not a multiple of 4; a NULL rowptr, q, k, v, out, row_max or row_sum (backward: or grad_out or grad_q); one
  *   of them, or col, misaligned (backward: then a misaligned grad_out, grad_q, grad_k or grad_v); a scale that is not
  *   finite or not positive.  spp_last_error names the failing condition.  SPP_ABI_VERSION stays 6.
- *   Not built: attention dropout inside the kernels, edge features (PyG's edge_dim), and entries over the resident
- *   graph.
+ *   Not built: attention dropout inside the kernels and edge features (PyG's edge_dim).  The entry over the resident
+ *   graph is f3z, below.
  * ------------------------------------------------------------------------- */
 typedef struct spp_transformer_desc {
   int32_t heads;              /* H: 1, 2, 4 or 8 */
@@ -2011,6 +2011,87 @@ typedef struct spp_transformer_desc {
 
 spp_status spp_transformer_forward(const spp_transformer_desc* desc, void* stream);
 spp_status spp_transformer_backward(const spp_transformer_desc* desc, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * f3z  TransformerConv attention over rows of the RESIDENT graph (exact, layer-wise GraphTransformer inference), on
+ *      rows the caller has projected.  Forward only.
+ *
+ *        rowptr, col   the graph's CSR, int64, global node ids (as spp_graph_agg_forward)
+ *        q, k, v       [x_rows, D] each, D = heads * C, head h in columns h*C .. (h+1)*C; fp32 / fp16 / bf16, one code
+ *                      for the three, each with its own base and row stride; ALL indexed by global node id.  k and v
+ *                      may be the halves of one [x_rows, 2 D] matrix (v = k + D, both strides 2 D).
+ *        skip          NULL, or rows of x_elem [x_rows, D] with their own stride, indexed by global node id (the
+ *                      layer's lin_skip(x))
+ *        targets       a slab or a list, exactly as spp_graph_gatv2_desc
+ *
+ *      For target t and head h (f3y's convention): EVERY entry of col[rowptr[t] .. rowptr[t+1]) in CSR order; no self
+ *      loop is added, diagonal entries are kept, a repeated entry counts as often as it appears.
+ *        e_j = scale * sum_c q[t,h,c] * k[j,h,c],   alpha = softmax_j(e),   r[h,:] = sum_j alpha_j v[j,h,:]
+ *      A row without entries has r = 0: decided by s == 0, nothing is divided.  Epilogue, in this order: r = r + skip[t]
+ *      if skip is given (one rounded fp32 addition per column); max(r, 0) if relu != 0; one rounding to out_elem
+ *      (fp32 / bf16; bf16 to nearest even).  A target id outside [0, x_rows) gives an output row of zeros and NO skip is
+ *      added; a col entry outside [0, x_rows) is node 0.  Neither faults.
+ *      Shapes, as f3y: heads in {1, 2, 4, 8}; C % 4 == 0 with C / 4 a power of two; D <= 1024; the rows of q / k / v /
+ *      skip aligned to 4 elements (base and stride), the output to 4 elements.
+ *
+ *   Aliasing: skip may alias out when the skip row of target t and output row i are the same addresses (the same element
+ *   type, a slab over a [x_rows, D] matrix).  A lane reads its columns of the skip row before it writes them and no other
+ *   lane touches them.  q, k and v must not overlap out.
+ *
+ *   Softmax contract, C_g = spp_graph_transformer_chunk() (a compile-time constant, >= 32): f3w's State, take, merge and
+ *   result, weights by expf, with ONE difference: every chunk, chunk 0 included, begins from the empty state
+ *   (m = -inf, s = 0, acc = 0).
+ *     a row of at most C_g entries: ONE state from the empty state takes the row's entries in CSR order;
+ *     a longer row is cut into consecutive chunks of C_g entries (the last may be shorter); each begins empty and takes
+ *       its entries in CSR order; the running state is chunk 0's and chunks 1, 2, ... are merged into it in chunk order
+ *       (f3w's merge).  Every chunk of such a row holds at least one entry and every entry is taken, so both states of a
+ *       merge are finite: two empty states are never merged (that would be expf(-inf + inf)).
+ *     the logit's summation tree is f3y's, fixed by C alone; the result of a row depends on nothing else -- not the
+ *       grid, the slab, the order of a list or the other rows of the call -- and no atomic touches the output.
+ *   For a call whose rows all have at most C_g entries, fp32 output, no skip and relu == 0, the output is BIT-IDENTICAL
+ *   to spp_transformer_forward's out with the hop the whole graph (T = S = x_rows): both run one body
+ *   (csrc/transformer_core.hip.h).
+ *
+ *   Workspace: spp_graph_transformer_workspace_bytes(num_targets) bytes, 16-byte aligned, the caller's.  The entry
+ *   enqueues a 16-byte memset and two launches on `stream` and never waits for the device.
+ *   Refused with SPP_ERR_INVALID before anything is enqueued, in this order: f3w's refusals (a NULL descriptor; heads;
+ *   C; C / 4 not a power of two; D > 1024; element codes; both target forms or neither; a slab outside the graph; an
+ *   output stride smaller than the row; the workspace; -- here num_targets == 0 returns SPP_OK and touches nothing --
+ *   a NULL rowptr, col, q, k, v or out, or x_rows == 0; k_stride_elems smaller than the row; an output not aligned to 4
+ *   elements); then a stride of q, v or skip smaller than the row; rows of q / k / v / skip not aligned to 4 elements
+ *   (base and stride); last a scale that is not finite or not positive.  SPP_ABI_VERSION stays 6.
+ *   Not built: attention dropout, edge features, partitioned or fp8 rows.
+ * ------------------------------------------------------------------------- */
+typedef struct spp_graph_transformer_desc {
+  int32_t x_elem;           /* q, k, v and skip: SPP_ELEM_F32 / _F16 / _BF16 */
+  int32_t out_elem;         /* SPP_ELEM_F32 / SPP_ELEM_BF16 */
+  int32_t heads;            /* 1, 2, 4 or 8 */
+  int32_t relu;             /* != 0: out = max(out, 0), after the skip */
+  const int64_t* rowptr_dev;
+  const int64_t* col_dev;
+  const void* q_dev;        /* [x_rows, D] */
+  int64_t q_stride_elems;
+  const void* k_dev;        /* [x_rows, D] */
+  int64_t k_stride_elems;
+  const void* v_dev;        /* [x_rows, D]; may be k_dev + D of one [x_rows, 2 D] matrix */
+  int64_t v_stride_elems;
+  int64_t x_rows;           /* the graph's nodes = the rows of q, k, v and skip */
+  int64_t C;                /* channels per head; D = heads * C */
+  int64_t target_row0;      /* slab: the first target; < 0 with a list */
+  const int64_t* target_ids_dev; /* list: the targets; NULL with a slab */
+  int64_t num_targets;
+  void* out_dev;            /* [num_targets, D] */
+  int64_t out_stride_elems; /* 0 = dense */
+  const void* skip_dev;     /* NULL, or [x_rows, D] rows of x_elem; may alias out_dev (above) */
+  int64_t skip_stride_elems;
+  float scale;              /* > 0, finite; the logit is scale * (q . k) */
+  int32_t reserved;
+} spp_graph_transformer_desc;
+
+int64_t spp_graph_transformer_chunk(void);
+int64_t spp_graph_transformer_workspace_bytes(int64_t num_targets);
+spp_status spp_graph_transformer_forward(const spp_graph_transformer_desc* desc, void* workspace_dev,
+                                         int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

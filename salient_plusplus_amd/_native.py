@@ -197,6 +197,16 @@ class GraphGatv2Desc(C.Structure):
                 ("out_dev", p), ("out_stride_elems", i64), ("negative_slope", C.c_float), ("reserved", i32)]
 
 
+class GraphTransformerDesc(C.Structure):
+    """spp_graph_transformer_desc: projected rows q, k, v (and optionally skip) [x_rows, heads * C] by global id; targets
+    as in GraphAggDesc"""
+    _fields_ = [("x_elem", i32), ("out_elem", i32), ("heads", i32), ("relu", i32), ("rowptr_dev", p), ("col_dev", p),
+                ("q_dev", p), ("q_stride_elems", i64), ("k_dev", p), ("k_stride_elems", i64), ("v_dev", p),
+                ("v_stride_elems", i64), ("x_rows", i64), ("C", i64), ("target_row0", i64), ("target_ids_dev", p),
+                ("num_targets", i64), ("out_dev", p), ("out_stride_elems", i64), ("skip_dev", p),
+                ("skip_stride_elems", i64), ("scale", C.c_float), ("reserved", i32)]
+
+
 class GraphGatPartsDesc(C.Structure):
     """spp_graph_gat_parts_desc: GraphGatDesc with h and its logits as num_parts row ranges (part_offsets, one h base and
     one [a_src | a_dst] base each)"""
@@ -414,6 +424,10 @@ SIGNATURES = {
     # TransformerConv over a hop (spp.h f3y)
     "spp_transformer_forward": (C.c_int, [C.POINTER(TransformerDesc), p]),
     "spp_transformer_backward": (C.c_int, [C.POINTER(TransformerDesc), p]),
+    # TransformerConv over rows of the resident graph (spp.h f3z)
+    "spp_graph_transformer_chunk": (i64, []),
+    "spp_graph_transformer_workspace_bytes": (i64, [i64]),
+    "spp_graph_transformer_forward": (C.c_int, [C.POINTER(GraphTransformerDesc), p, i64, p]),
 }
 SPP_COMM_ID_BYTES = 128
 SPP_IPC_HANDLE_BYTES = 64

@@ -10,7 +10,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libspp_hip.so")
 SOURCES = ["api.hip", "mt19937.hip", "gather.hip", "gather_fp8.hip", "sampler.hip", "partition.hip", "session.hip", "exchange.hip", "vip.hip", "aggregate.hip", "aggregate_max.hip", "aggregate_weighted.hip", "gat.hip", "gatv2.hip", "transformer_conv.hip",
-           "graph_aggregate.hip", "graph_agg_weighted.hip", "graph_gat.hip", "graph_gatv2.hip", "resinc_epilogue.hip", "classify.hip", "field.hip", "bn_act.hip"]
+           "graph_aggregate.hip", "graph_agg_weighted.hip", "graph_gat.hip", "graph_gatv2.hip", "graph_transformer.hip", "resinc_epilogue.hip", "classify.hip", "field.hip", "bn_act.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
          "-I" + CSRC, "-Wall", "-Wno-unused-function"] + os.environ.get("SPP_EXTRA_FLAGS", "").split()

@@ -9,38 +9,24 @@
 // backward has three row gradients, and there is no grad_att (so no LDS reduction and one group per target).  What is
 // kept: gatv2_core.hip.h's lane mapping, per-head online softmax (State), butterfly and (NQ, CPH) dispatch, unchanged;
 // several neighbours' loads in flight per round; one fp32 atomic per column per entry on contiguous wave-wide segments.
-// Not here: attention dropout in the kernels, edge features, and kernels over the resident graph.
-#include "gatv2_core.hip.h"
+// Not here: attention dropout in the kernels and edge features.  The kernels over the resident graph are
+// graph_transformer.hip's; the forward's per-entry body is shared with them (transformer_core.hip.h).
+#include "transformer_core.hip.h"
 
 #include <cmath>
 
 namespace spp {
 
 using namespace gatv2;
+using namespace transformer;
 
 constexpr int kTfNT = 256;
 
-// THE LOGIT'S SUMMATION TREE, walked bit for bit by both kernels.  The C products q[c] k[c] of a head, each rounded,
-// are added pairwise by xor distance of the column index within the head, in the order 1, 2, then C / 2, C / 4, ..., 4;
-// every addition is a rounded fp32 addition of two partial sums that are the same bits on both sides, so whoever
-// holds a partner ends with the same bits.  Then ONE rounded product by scale.  No fused multiply-add anywhere in it
-// (contraction is off in both kernels).  The backward recomputes alpha = expf(e - row_max) / row_sum from THIS e:
-// with a logit added in another order, a row dominated by one entry got alpha = 1 + (e' - e) -- 1e-6 off at logits of
-// 18, seen at model level -- where the forward's own weight is 1 to the bit.
-// Forward: distances 1 and 2 are inside a lane's 4-column piece (piece4), distances >= 4 are piece distances: chunks of
-// the head in the lane first (widest), then the butterfly over the head's lanes, widest first.
-__device__ __forceinline__ float piece4(const f4& a, const f4& b) {
-#pragma clang fp contract(off)
-  return (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w);
-}
-
-// neighbours in flight per round: every one is a k piece set AND a v piece set, twice gatv2's Lane::NB row data, so at
-// NQ = 4 (16 columns per lane and row) one fewer than there: 2 * 2 * 16 = 64 registers of rows, as NQ = 2 has with 4
-template <int NQ>
-constexpr int tf_nb() { return NQ <= 2 ? 4 : 2; }
+// THE LOGIT'S SUMMATION TREE (transformer_core.hip.h states it, with piece4 and the forward's walk) is walked bit for bit
+// by both kernels: the backward recomputes alpha = expf(e - row_max) / row_sum from the forward's e.
 
 // Forward.  lpr lanes per target, 4 columns per lane and chunk (gatv2_core.hip.h's mapping); the lane keeps its pieces of
-// q[t] for the whole row.  Per round: NB ids, then their k and v pieces, then the partial dots, then ONE butterfly that
+// q[t] for the whole row; the row itself is transformer_core.hip.h's walk.  Per round: NB ids, then their k and v pieces, then the partial dots, then ONE butterfly that
 // carries all NB * HL values (the logit's tree above); the logit is the butterfly's sum times scale (one product, the
 // same bits in every lane of the head's segment); State::take does the online softmax on the v pieces.  The row starts from the empty state.
 // No atomics: the same bits in every run.
@@ -52,7 +38,7 @@ __global__ __launch_bounds__(kTfNT) void k_transformer_fwd(const int64_t* __rest
                                                            int seg_log2, int g_log2, int H, float* __restrict__ out,
                                                            float* __restrict__ row_max, float* __restrict__ row_sum) {
 #pragma clang fp contract(off)
-  constexpr int HL = NQ / CPH, NB = tf_nb<NQ>();
+  constexpr int NB = tf_nb<NQ>();
   const int lpr = 1 << lpr_log2, lane = threadIdx.x & (lpr - 1);
   const int64_t t = ((int64_t)blockIdx.x * kTfNT + threadIdx.x) >> lpr_log2;
   if (t >= T) return;  // whole groups leave together (the shuffles below stay inside a group)
@@ -67,40 +53,7 @@ __global__ __launch_bounds__(kTfNT) void k_transformer_fwd(const int64_t* __rest
   State<NQ, CPH> st;
   st.clear();
   const int64_t b = rowptr[t], e = rowptr[t + 1];
-  for (int64_t k0 = b; k0 < e; k0 += NB) {
-    int64_t j[NB];
-#pragma unroll
-    for (int u = 0; u < NB; ++u) j[u] = col[k0 + u < e ? k0 + u : e - 1];  // clamped, unpredicated
-    f4 kv[NB][NQ], vv[NB][NQ];
-#pragma unroll
-    for (int u = 0; u < NB; ++u)
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) {
-        kv[u][q] = load4(km + j[u] * k_stride + c0[q]);
-        vv[u][q] = load4(vm + j[u] * v_stride + c0[q]);
-      }
-    float pd[NB * HL];
-#pragma unroll
-    for (int u = 0; u < NB; ++u)
-#pragma unroll
-      for (int hl = 0; hl < HL; ++hl) {
-        float ch[CPH];  // the head's chunks: piece distance 64 * (chunk distance), the widest of the tree's >= 4 part
-#pragma unroll
-        for (int q = 0; q < CPH; ++q) ch[q] = piece4(qv[hl * CPH + q], kv[u][hl * CPH + q]);
-#pragma unroll
-        for (int d = CPH / 2; d >= 1; d >>= 1)
-#pragma unroll
-          for (int q = 0; q < d; ++q) ch[q] += ch[q + d];
-        pd[u * HL + hl] = ch[0];
-      }
-    butterfly(pd, seg_log2);
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-      if (k0 + u >= e) continue;
-#pragma unroll
-      for (int hl = 0; hl < HL; ++hl) st.take(hl, pd[u * HL + hl] * scale, vv[u]);
-    }
-  }
+  walk<NB>(st, qv, c0, km, k_stride, vm, v_stride, col, b, e, (int64_t)-1, scale, seg_log2);  // (an MFG hop: ids as they are)
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
     const int hl = q / CPH;

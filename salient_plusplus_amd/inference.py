@@ -6,7 +6,9 @@ GIN and SAGEResInception and of csrc/graph_gat.hip for GAT; SAGEResInception's l
 with ``gcn_dinv`` for the per-node factors of its normalisation; resident entries only).  The layers' own parameters run
 through the library GEMMs torch dispatches to.  Forward only, fp16 / fp32 / bf16 inputs.  GATv2 (f3w): the long-row
 pair of csrc/graph_gatv2.hip behind ``graph_gatv2_aggregate`` (``spp_graph_gatv2_forward``) and the recipe
-``_gatv2_layer`` of the attention driver; resident entries only.
+``_gatv2_layer`` of the attention driver; resident entries only.  GraphTransformer (f3z): the long-row pair of
+csrc/graph_transformer.hip behind ``graph_transformer_aggregate`` (``spp_graph_transformer_forward``) and the recipe
+``_transformer_layer`` of the same driver, with lin_skip and the ReLU in the kernel's epilogue; resident entries only.
 
 The kernels' wrappers: ``graph_aggregate`` (``spp_graph_agg_forward``) and ``graph_gat_aggregate``
 (``spp_graph_gat_forward``) read one resident matrix, ``graph_aggregate_parts`` (``spp_graph_agg_parts_forward``) and
@@ -16,12 +18,12 @@ tail all models share: argmax and negative log-likelihood of a tile of logits.  
 with the helpers they share and hands them to its kernel's launch function (``_agg_launch``, ``_gat_launch``,
 ``_agg_parts_launch``, ``_gat_parts_launch``), which the drivers call directly, slab by slab.
 
-The drivers: ``_conv_layers`` (SAGE, GIN, GCN) and ``_attn_layers`` (GAT, GATv2), each one layer loop plus a recipe per
+The drivers: ``_conv_layers`` (SAGE, GIN, GCN) and ``_attn_layers`` (GAT, GATv2, GraphTransformer), each one layer loop plus a recipe per
 model, and ``_resinc_layers``, written against a placement that says where the table lives -- ``_Resident`` (one matrix,
 the whole-table kernels, no waits) or ``_Partitioned`` (the parts kernels over buffers published through ``peers``, a
 synchronise and a barrier at every layer boundary) -- inside one frame (``_score``).  ``layerwise_inference`` is the
-resident entry for all six models (behind every model's ``.inference``; ``gatv2_inference`` is its older name for
-GATv2), ``partitioned_inference`` the partitioned one for SAGE, GIN, GAT and SAGEResInception
+resident entry for all seven models (behind the ``.inference`` of the six that have one; ``gatv2_inference`` and
+``transformer_inference`` are its names for one model each), ``partitioned_inference`` the partitioned one for SAGE, GIN, GAT and SAGEResInception
 (``partitioned_layerwise_inference`` is its older name), with ``LocalPeers`` (ranks as threads of one process) or
 ``IpcPeers`` (one process per rank on one node) between the ranks.  Every driver hands its last layer's logits, tile by
 tile, to a sink: ``_LogProbs`` (log_softmax into the [rows, classes] matrix those entries return) or ``_Classify``
@@ -41,7 +43,7 @@ from . import _native as nat
 from .fast_sampler import P2PPeers, RowRefs, TableRows, _common_stride, _row_stride_elems, _table_stride_bytes, \
     p2p_open_peers
 from .fp8 import Fp8Features
-from .models import GAT, GATv2, GCN, GIN, SAGE, SAGEResInception, _ELEM, _gcn_fill, _p, _stream
+from .models import GAT, GATv2, GCN, GIN, SAGE, GraphTransformer, SAGEResInception, _ELEM, _gcn_fill, _p, _stream
 
 _EPILOGUES = {"mean": nat.SPP_AGG_MEAN, "operand": nat.SPP_AGG_OPERAND, "sum": nat.SPP_AGG_SUM,
               "max": nat.SPP_AGG_MAX, "max_operand": nat.SPP_AGG_MAX_OPERAND}
@@ -80,6 +82,17 @@ def graph_gatv2_chunk():
 
 def graph_gatv2_workspace_bytes(num_targets):
     return int(nat.load().spp_graph_gatv2_workspace_bytes(int(num_targets)))
+
+
+def graph_transformer_chunk():
+    """C_g of TransformerConv's softmax contract (include/spp.h f3z): a row of at most C_g entries is one online softmax
+    per head in CSR order from the empty state, a longer row is chunks of C_g, each from the empty state, whose per-head
+    states are merged in chunk order"""
+    return int(nat.load().spp_graph_transformer_chunk())
+
+
+def graph_transformer_workspace_bytes(num_targets):
+    return int(nat.load().spp_graph_transformer_workspace_bytes(int(num_targets)))
 
 
 class Fp8Table:
@@ -433,6 +446,19 @@ def _gatv2_launch(x_l, x_r, att, rowptr, col, negative_slope, relu, row0, target
     return _launch(nat.load().spp_graph_gatv2_forward, d, workspace, out)
 
 
+def _transformer_launch(q, k, v, skip, heads, scale, rowptr, col, relu, row0, target_ids, T, out, workspace):
+    """spp_graph_transformer_forward: q, k, v [N, H * C] by global id (k and v may be the halves of one matrix), skip
+    None or [N, H * C] of their dtype (it may be the matrix ``out`` is a slab of)"""
+    N, D = q.shape
+    stride = lambda t: t.stride(0) if N > 1 else D
+    d = nat.GraphTransformerDesc(x_elem=_ELEM[q.dtype], heads=heads, relu=int(bool(relu)), q_dev=_p(q),
+                                 q_stride_elems=stride(q), k_dev=_p(k), k_stride_elems=stride(k), v_dev=_p(v),
+                                 v_stride_elems=stride(v), x_rows=N, C=D // heads, skip_dev=_p(skip),
+                                 skip_stride_elems=stride(skip) if skip is not None else 0, scale=float(scale),
+                                 **_request(rowptr, col, row0, target_ids, T, out))
+    return _launch(nat.load().spp_graph_transformer_forward, d, workspace, out)
+
+
 def _gat_parts_launch(src, a_src, off, rowptr, col, heads, negative_slope, relu, row0, target_ids, T, out, workspace):
     """spp_graph_gat_parts_forward: ``src`` as for ``_agg_parts_launch``, ``a_src`` the logits' (base addresses, row
     stride)"""
@@ -696,6 +722,63 @@ def graph_gatv2_aggregate(x_l, x_r, att, rowptr, col, *, negative_slope=0.2, rel
     if out is None:
         out = torch.empty((T, D), dtype=out_dtype, device=x_l.device)
     return _gatv2_launch(x_l, x_r, att, rowptr, col, negative_slope, relu, row0, target_ids, T, out, workspace)
+
+
+def graph_transformer_aggregate(q, k, v, rowptr, col, *, heads, scale, skip=None, relu=False, row0=None,
+                                num_targets=None, target_ids=None, out_dtype=torch.float32, out=None, workspace=None):
+    """TransformerConv's attention over whole rows of the resident graph (``spp_graph_transformer_forward``,
+    include/spp.h f3z).
+
+    ``q`` / ``k`` / ``v`` [N, H * C]: the PROJECTED rows lin_query(x), lin_key(x) and lin_value(x), one per graph node
+    and all indexed by global node id (fp16 / fp32 / bf16, one dtype, possibly strided views with rows aligned to 4
+    elements: ``k`` and ``v`` may be the halves of one [N, 2 * H * C] matrix).  ``rowptr`` / ``col``: the graph's CSR
+    (int64, global ids).  The targets are a slab, ``row0`` and ``num_targets``, or a list, ``target_ids`` (int64, any
+    order, duplicates allowed).  Output row i, head h: the softmax over EVERY entry of node t's row -- no self loop,
+    diagonal entries kept, repeats counted -- of e_j = ``scale`` * q[t, h] . k[j, h], applied to the rows
+    v[j, h*C:(h+1)*C]; a row without entries gives zeros.  Then ``skip[t]`` is added (``skip``: [N, H * C] of the rows'
+    dtype, by global id; None: nothing), then the ReLU with ``relu=True``, then one rounding to ``out_dtype``.  fp32
+    state.  A ``col`` entry outside the graph is node 0, a target id outside it gives a row of zeros (no skip).
+    ``skip`` may be the matrix ``out`` is a slab of (``out = skip[row0:row0 + num_targets]``): a lane reads its columns
+    before it writes them.  The kernels are built for H in {1, 2, 4, 8}, C % 4 == 0 with C / 4 a power of two and
+    H * C <= 1024; any other shape is a ``ValueError`` (``layerwise_inference`` pads C itself).
+
+    Forward only: no autograd node is registered and an input that requires grad is refused.  ``out``: where the rows
+    go ([T, H * C] of ``out_dtype``, rows aligned to 4 elements; allocated when None).  ``workspace``: a uint8 CUDA
+    tensor of at least ``graph_transformer_workspace_bytes(T)`` bytes, reusable between calls on one stream; allocated
+    when None.  Nothing here waits for the device."""
+    what = "graph_transformer_aggregate"
+    _check_matrix(q, what, name="q")
+    N, D = q.shape
+    rows = [("k", k), ("v", v)] + ([("skip", skip)] if skip is not None else [])
+    for name, t in rows:
+        _check_matrix(t, what, name=name)
+        if tuple(t.shape) != (N, D) or t.dtype != q.dtype:
+            raise ValueError(f"{what}: {name} must have q's shape and dtype ({[N, D]} {q.dtype}: all are indexed by global "
+                             f"node id), got {list(t.shape)} {t.dtype}")
+    _check_graph(what, N, rowptr, col)
+    if isinstance(heads, bool) or not isinstance(heads, int) or heads not in _GATV2_HEADS:
+        raise ValueError(f"{what}: heads must be 1, 2, 4 or 8 (the kernels' head counts), got {heads!r}")
+    Cc = D // heads
+    if D % heads != 0 or Cc < 4 or _gatv2_pad(Cc) != Cc:
+        raise ValueError(f"{what}: C = D / heads must be a multiple of 4 with C / 4 a power of two (the per-head reduction "
+                         f"is a butterfly over aligned lane segments), got D = {D} with heads = {heads}; zero-pad the "
+                         f"channels to {_gatv2_pad(max(-(-D // heads), 1))}")
+    if D > _GATV2_MAX_D:
+        raise ValueError(f"{what}: the rows must be heads * C = {heads} * {Cc} = {D} <= {_GATV2_MAX_D} wide")
+    if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not (0.0 < float(scale) < float("inf")):
+        raise ValueError(f"{what}: scale must be a finite positive number (the layer's is 1 / sqrt(C)), got {scale!r}")
+    for name, t in [("q", q)] + rows:
+        _check_gatv2_rows(what, name, t)
+    _check_out_dtype(what, out_dtype)
+    row0, target_ids, T = _check_targets(what, N, row0, num_targets, target_ids)
+    _check_out(what, out, out_dtype, T, D)
+    if out is not None:
+        _check_gatv2_rows(what, "out", out)
+    workspace = _on_device(what, "q, k, v, skip, rowptr, col, target_ids, out and workspace", q.device,
+                           [q, k, v, skip, rowptr, col, target_ids, out], workspace, graph_transformer_workspace_bytes, T)
+    if out is None:
+        out = torch.empty((T, D), dtype=out_dtype, device=q.device)
+    return _transformer_launch(q, k, v, skip, heads, scale, rowptr, col, relu, row0, target_ids, T, out, workspace)
 
 
 def graph_gat_aggregate_parts(h_parts, a_parts, part_offsets, rowptr, col, *, heads, negative_slope=0.2, relu=False,
@@ -1364,9 +1447,122 @@ def _gatv2_layer(model, place, act_dtype):
     return graph_gatv2_workspace_bytes, layer
 
 
+class _Tail:
+    """What a layer of ``_attn_layers`` does behind its kernel when that is more than the fused ReLU or the mean of the
+    heads (``_transformer_layer``; GAT and GATv2 have none).  ``slab_dtype``: the dtype of a hidden layer's slab.
+    ``nxt(operands, rows, ids)``: the matrix the hidden layer's rows go into when the recipe already holds it (the
+    projected skip, which the kernel reads and overwrites row by row), or None.  ``hidden(h, operands, s, T, ids)``:
+    None when the kernel's rows are the layer's output, else [T, H * Cc] of the slab's dtype -> the layer's output rows.
+    ``last(z, operands, s, T, ids)``: the mean of the heads [T, Cc] fp32 -> the logits."""
+
+    def __init__(self, slab_dtype, nxt, hidden, last):
+        self.slab_dtype, self.nxt, self.hidden, self.last = slab_dtype, nxt, hidden, last
+
+
+def _transformer_layer(model, place, act_dtype):
+    """GraphTransformer over one resident matrix (f3z), project-first as ``TransformerConv.forward``:
+
+      project    over ``_row_tiles(cur)``, biases included, all in ``act_dtype``: q = lin_query(cur) [n, H*Cp],
+                 [k | v] = ONE [n, 2*H*Cp] matrix from one GEMM (lin_key's and lin_value's weights stacked), and with
+                 ``root_weight`` skip = lin_skip(cur)
+      attend     ``spp_graph_transformer_forward`` (``_transformer_launch``) over the step's graph or the placement's,
+                 scale = 1 / sqrt(Cc) from the UNPADDED width
+
+    Channel padding is ``_gatv2_pad``'s: Cp - Cc zero weight rows and zero bias entries per head, so a padded channel
+    has q = k = v = 0, adds a product 0 * 0 = +0 to every logit at a position fixed by (H, Cp), and is a zero column of
+    the output that the driver slices away.
+
+    Hidden layers, ``beta=False``: the kernel adds the skip row and applies the ReLU, and writes the next activation
+    matrix.  With Cp == Cc and ``root_weight`` the skip is projected INTO that matrix and the kernel reads and overwrites
+    it in place (spp.h f3z, aliasing); with Cp != Cc the skip is padded like q and the leading columns of a slab are
+    copied; without ``root_weight`` there is no skip anywhere.  ``beta=True``: the kernel writes the bare attention as an
+    fp32 slab, and b = sigmoid(lin_beta([out, x_r, out - x_r])), b x_r + (1 - b) out and the ReLU are plain torch per
+    slab, in fp32 (lin_beta's GEMM over ``_row_tiles``, so that a row's bits do not depend on the slab).  Last layer
+    (concat=False): an fp32 slab, the leading Cc columns, the mean of the heads, then the [rows, Cc] skip (gathered by
+    ``nodes`` when they are given) added or gated in torch.
+
+    Memory, as arithmetic: ``cur``, q, [k | v] (two matrices' worth) and skip (which becomes ``nxt``) are FIVE
+    [N, hidden] matrices of ``act_dtype`` at the end of the projection, with the GEMM tiles of 65 536 rows on top, and
+    four while attending (``cur`` is dropped).  At N = 111 M and hidden 256 a matrix is 57 GB in bf16, next to 26 GB of
+    graph and 28 GB of features: 5 * 57 + 26 + 28 = 339 GB.  That does NOT fit one 288 GB MI355X; a GraphTransformer of
+    hidden 256 cannot be scored at papers scale on one device by this driver (hidden 128: 5 * 28 + 54 = 196 GB does).
+    The follow-up that would bring it to four matrices (4 * 57 + 54 = 282 GB) is projecting q and skip per slab, next
+    to the kernel's launch, instead of for all rows up front; it is not built.  With ``beta`` the skip is a matrix of
+    its own next to ``nxt`` while attending (five there too)."""
+    def layer(i):
+        conv = model.convs[i]
+        H, Cc, Cp = conv.heads, conv.out_channels, _gatv2_pad(conv.out_channels)
+        last = i == len(model.convs) - 1
+        fused = not last and conv.lin_skip is not None and conv.lin_beta is None    # the skip rides in the kernel
+        scale = 1.0 / float(Cc) ** 0.5
+
+        def padded(lin):                                 # [H*C, K], [H*C] -> ([K, H*Cp], [H*Cp]) in act_dtype
+            W = lin.weight
+            b = lin.bias if lin.bias is not None else W.new_zeros(W.size(0))
+            if Cp != Cc:
+                Wp, bp = W.new_zeros((H, Cp, W.size(1))), b.new_zeros((H, Cp))
+                Wp[:, :Cc], bp[:, :Cc] = W.view(H, Cc, -1), b.view(H, Cc)
+                W, b = Wp.view(H * Cp, -1), bp.view(H * Cp)
+            return W.to(act_dtype).t(), b.to(act_dtype)
+        Wq, bq = padded(conv.lin_query)
+        (Wk, bk), (Wv, bv) = padded(conv.lin_key), padded(conv.lin_value)
+        Wkv, bkv = torch.cat([Wk, Wv], 1).contiguous(), torch.cat([bk, bv])
+        Ws = bs = None
+        if conv.lin_skip is not None:
+            if fused:
+                Ws, bs = padded(conv.lin_skip)
+            else:                                        # added in torch: the layer's own width, unpadded
+                Ws = conv.lin_skip.weight.to(act_dtype).t()
+                bs = conv.lin_skip.bias.to(act_dtype) if conv.lin_skip.bias is not None else None
+        Wb = conv.lin_beta.weight.to(torch.float32).t().contiguous() if conv.lin_beta is not None else None
+
+        def project(cur):
+            n_rows = cur.size(0)
+            q = torch.empty((n_rows, H * Cp), dtype=act_dtype, device=place.dev)
+            kv = torch.empty((n_rows, 2 * H * Cp), dtype=act_dtype, device=place.dev)
+            skip = torch.empty((n_rows, Ws.size(1)), dtype=act_dtype, device=place.dev) if Ws is not None else None
+            for r, n, tile in _row_tiles(cur):
+                tile = tile.to(act_dtype)
+                q[r:r + n] = torch.addmm(bq, tile, Wq)[:n]          # (one product live at a time)
+                kv[r:r + n] = torch.addmm(bkv, tile, Wkv)[:n]
+                if skip is not None:
+                    skip[r:r + n] = (torch.addmm(bs, tile, Ws) if bs is not None else tile @ Ws)[:n]
+            return q, kv, skip
+
+        def attend(operands, relu, s, ids, T, out, ws, graph):
+            q, kv, skip = operands
+            return _transformer_launch(q, kv[:, :H * Cp], kv[:, H * Cp:], skip if fused else None, H, scale,
+                                       *(graph or (place.rowptr, place.col)), relu and conv.lin_beta is None,
+                                       -1 if ids is not None else s, ids, T, out, ws)
+
+        def root(out, operands, s, T, ids):              # out [T, width] fp32 -> with the root term, as the layer's forward
+            skip = operands[2]
+            if skip is None:
+                return out
+            x_r = (skip[ids] if ids is not None else skip[s:s + T]).to(torch.float32)
+            if Wb is None:
+                return out + x_r
+            g = torch.cat([out, x_r, out - x_r], -1)
+            b = torch.empty((T, 1), dtype=torch.float32, device=place.dev)
+            for r, n, tile in _row_tiles(g):
+                b[r:r + n] = (tile @ Wb)[:n]
+            b = torch.sigmoid(b)
+            return b * x_r + (1 - b) * out
+
+        def nxt(operands, rows, ids):
+            skip = operands[2]
+            return skip if fused and Cp == Cc and ids is None and rows == skip.size(0) else None
+        gated = conv.lin_beta is not None and not last
+        tail = _Tail(torch.float32 if gated else act_dtype, nxt,
+                     (lambda h, *slab: torch.relu(root(h, *slab))) if gated else None, root)
+        return H, Cc, Cp, project, attend, tail
+    return graph_transformer_workspace_bytes, layer
+
+
 def _attn_layers(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None):
-    """GAT and GATv2.  A recipe (``_gat_layer``, ``_gatv2_layer``) opens the placement and returns (workspace_bytes,
-    layer); ``layer(i)`` -> (H, Cc, Cp, project, attend): heads, channels a head, channels a head as the kernel writes
+    """GAT, GATv2 and GraphTransformer.  A recipe (``_gat_layer``, ``_gatv2_layer``, ``_transformer_layer``) opens the
+    placement and returns (workspace_bytes, layer); ``layer(i)`` -> (H, Cc, Cp, project, attend) and, for
+    GraphTransformer alone, a ``_Tail`` behind them (GAT and GATv2 run exactly the ops they ran without it): heads, channels a head, channels a head as the kernel writes
     them, ``project(cur)`` -> the projected operands of all the rank's rows, over ``_row_tiles(cur)``, and
     ``attend(operands, relu, s, ids, T, out, ws, graph)``, a slab's launch over each node's whole row.  Hidden layers go
     through the fused ReLU straight into the next [n, hidden] matrix (Cp != Cc: into a [T, H*Cp] slab whose leading
@@ -1374,7 +1570,9 @@ def _attn_layers(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None)
     boundaries a layer: the projected rows are complete before anyone attends, and read by everyone before the next
     layer overwrites them.  The recipes' memory arithmetic rests on ONE name each for ``cur``, the operands and ``nxt``
     and no view left behind (a tile dies with ``project``'s frame).  ``plan``: as in ``_conv_layers``."""
-    workspace_bytes, layer = (_gatv2_layer if isinstance(model, GATv2) else _gat_layer)(model, place, act_dtype)
+    recipe = _gatv2_layer if isinstance(model, GATv2) else _transformer_layer if isinstance(model, GraphTransformer) \
+        else _gat_layer
+    workspace_bytes, layer = recipe(model, place, act_dtype)
     n_layers, dev = len(model.convs), place.dev
     plan = plan or _whole_graph_plan(place, nodes, n_layers)
     ws = torch.empty(workspace_bytes(min(rows_per_slab, max([place.n_local] + [st.rows for st in plan]))),
@@ -1382,24 +1580,32 @@ def _attn_layers(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None)
     cur = place.x
     for i, step in enumerate(plan):
         last = i == n_layers - 1
-        H, Cc, Cp, project, attend = layer(i)
+        H, Cc, Cp, project, attend, *tail = layer(i)
+        tail = tail[0] if tail else None                 # (GraphTransformer's; None: the fused ReLU / the mean is all)
         operands = project(cur)
         del cur                                          # (layer i-1's matrix; layer 1's is the caller's table)
         place.boundary()                                 # every rank's projected rows of this layer are complete
         rows, names = step.rows, step.names
-        nxt = None if last else torch.empty((rows, H * Cc), dtype=act_dtype, device=dev)
+        nxt = None if last or tail is None else tail.nxt(operands, rows, step.ids)
+        if nxt is None and not last:
+            nxt = torch.empty((rows, H * Cc), dtype=act_dtype, device=dev)
         if last:
             sink.open(place, rows, Cc)
-        direct = not last and Cp == Cc                   # the rows go straight into the next activation matrix
+        # the rows go straight into the next activation matrix
+        direct = not last and Cp == Cc and (tail is None or tail.hidden is None)
+        slab_dtype = torch.float32 if last else act_dtype if tail is None else tail.slab_dtype
         for s, T, tids in _slabs(rows, step.ids, rows_per_slab):
-            out = nxt[s:s + T] if direct else torch.empty((T, H * Cp), dtype=act_dtype if not last else torch.float32,
-                                                          device=dev)
+            out = nxt[s:s + T] if direct else torch.empty((T, H * Cp), dtype=slab_dtype, device=dev)
             attend(operands, not last, s, tids, T, out, ws, step.graph)
             if last:                                     # concat=False: the mean of the heads (H = 1: the head itself)
                 z = out.view(T, H, Cp)[:, :, :Cc]
-                sink.put(s, T, z.mean(1) if H > 1 else z.reshape(T, Cc), names[s:s + T] if names is not None else None)
+                z = z.mean(1) if H > 1 else z.reshape(T, Cc)
+                if tail is not None:
+                    z = tail.last(z, operands, s, T, tids)
+                sink.put(s, T, z, names[s:s + T] if names is not None else None)
             elif not direct:
-                nxt[s:s + T] = out.view(T, H, Cp)[:, :, :Cc].reshape(T, H * Cc)
+                h = out.view(T, H, Cp)[:, :, :Cc].reshape(T, H * Cc)
+                nxt[s:s + T] = h if tail is None or tail.hidden is None else tail.hidden(h, operands, s, T, tids)
             out = None                                   # (a hidden layer's slab is a VIEW of nxt)
         cur, nxt = nxt, None                             # ONE name holds the matrix: ``del cur`` above must free it
         del operands                                     # (resident: drops them)
@@ -1505,6 +1711,11 @@ _GATV2_RESIDENT = ("a GATv2 model is scored over one resident fp16 / fp32 / bf16
                    "the partitioned entries are not built for GATv2")
 
 
+_TRANSFORMER_RESIDENT = ("a GraphTransformer model is scored over one resident fp16 / fp32 / bf16 matrix by "
+                         "inference.layerwise_inference (transformer_inference is the same call) and inference.evaluate; an "
+                         "Fp8Table input, the field entries and the partitioned entries are not built for GraphTransformer")
+
+
 def _check_gat(model, what):
     """the layers as ``models.GAT`` builds them"""
     for i, c in enumerate(model.convs):
@@ -1530,9 +1741,30 @@ def _check_gatv2(model, what):
                                       f"two), above the kernels' {_GATV2_MAX_D} (heads = {H} is not the limit that was hit)")
 
 
+def _check_transformer(model, what):
+    """the layers as ``models.GraphTransformer`` builds them, in shapes ``_transformer_layer`` can put on the kernels"""
+    for i, c in enumerate(model.convs):
+        last = i == len(model.convs) - 1
+        if c.concat == last or c.lin_key.bias is None or c.lin_query.bias is None or c.lin_value.bias is None:
+            raise NotImplementedError(f"{what}: GraphTransformer layers need concat=False on the last layer only and "
+                                      "biased key / query / value projections (as models.GraphTransformer builds them)")
+        H, Cc, Cp = c.heads, c.out_channels, _gatv2_pad(c.out_channels)
+        if H not in _GATV2_HEADS:
+            raise NotImplementedError(f"{what}: layer {i} has heads = {H}; the TransformerConv kernels are built for "
+                                      f"heads in {{1, 2, 4, 8}} (heads * C = {H} * {Cc} is not the limit that was hit)")
+        if H * Cp > _GATV2_MAX_D:
+            raise NotImplementedError(f"{what}: layer {i} needs rows of heads * Cp = {H} * {Cp} = {H * Cp} columns "
+                                      f"(C = {Cc} padded to Cp = {Cp}, the next multiple of 4 with Cp / 4 a power of "
+                                      f"two), above the kernels' {_GATV2_MAX_D} (heads = {H} is not the limit that was hit)")
+
+
 def _check_model(model, what, admits):
     """one of the model classes the entry admits, with what the GAT, GATv2 and SAGEResInception drivers need of its
     layers (SAGE, GIN and GCN: nothing)"""
+    if isinstance(model, GraphTransformer):              # admitted next to _RESIDENT_MODELS, whose refusal keeps its wording
+        if admits is not _RESIDENT_MODELS:
+            raise NotImplementedError(f"{what}: not built for GraphTransformer: {_TRANSFORMER_RESIDENT}")
+        return _check_transformer(model, what)
     if not isinstance(model, admits):
         if isinstance(model, GATv2):
             raise NotImplementedError(f"{what}: not built for GATv2: {_GATV2_RESIDENT}")
@@ -1562,7 +1794,7 @@ def _check_run(what, act_dtype, rows_per_slab, nodes):
 def _score(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None):
     """the frame of every driver: eval mode (restored), no gradient, autocast off, the table's device current; a rank
     that fails aborts the placement, so that its peers raise instead of waiting, and every mapping is closed"""
-    layers = _attn_layers if isinstance(model, (GAT, GATv2)) else \
+    layers = _attn_layers if isinstance(model, (GAT, GATv2, GraphTransformer)) else \
         _resinc_layers if isinstance(model, SAGEResInception) else _conv_layers
     was_training = model.training
     model.eval()
@@ -1584,7 +1816,10 @@ def layerwise_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 <<
                         edge_weight=None):
     """Exact log-probabilities of every node, [N, classes] fp32 -- or of ``nodes`` (int64, any order, duplicates
     allowed), [len(nodes), classes] -- for a ``SAGE``, ``GIN``, ``GAT``, ``SAGEResInception``, ``GCN`` or ``GATv2`` model
-    over the whole graph; every model's ``.inference`` is this call.  Each driver's docstring has its order of operations
+    over the whole graph; every model's ``.inference`` is this call.  The seventh model, ``GraphTransformer``, has no
+    ``.inference`` method and is scored by this call directly (``_attn_layers`` with ``_transformer_layer``: heads in
+    {1, 2, 4, 8}, heads * padded channels <= 1024, one resident matrix, no ``Fp8Table``, no ``edge_weight``; its five
+    live matrices are that recipe's arithmetic).  Each driver's docstring has its order of operations
     and its memory: ``_conv_layers`` (SAGE, GIN and, through ``_gcn_layer``, GCN), ``_attn_layers`` with ``_gat_layer``
     (GAT at any ``heads``) and ``_gatv2_layer`` (GATv2: heads in {1, 2, 4, 8}, heads * padded channels <= 1024, one
     resident matrix and no ``Fp8Table``) and ``_resinc_layers`` (SAGEResInception).  What follows describes SAGE and
@@ -1637,6 +1872,11 @@ def _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, y, s
         _check_matrix(x, what, fp8_reason=f"GCN: {_WEIGHTS_NOT_BUILT}")
     elif isinstance(model, GATv2):
         _check_matrix(x, what, fp8_reason=f"GATv2: {_GATV2_RESIDENT}")
+    elif isinstance(model, GraphTransformer):
+        if isinstance(x, (list, tuple, P2PPeers)):
+            raise NotImplementedError(f"{what}: GraphTransformer over a row-partitioned x ({type(x).__name__}); "
+                                      f"{_TRANSFORMER_RESIDENT}")
+        _check_matrix(x, what, fp8_reason=f"GraphTransformer: {_TRANSFORMER_RESIDENT}")
     else:
         _check_table(x, what)
     N = x.size(0)
@@ -1694,7 +1934,7 @@ def evaluate(model, x, rowptr, col, y=None, *, nodes=None, splits=None, rows_per
     ``pred`` and ``nll`` are the same bits whatever ``rows_per_slab`` is and whether ``nodes`` selected it; ``pred[i]`` is
     the argmax of the logits, so ``layerwise_inference``'s row attains its maximum there.  The counts are reduced on the
     device and read back once, at the end.  ``edge_weight``: GCN's entry weights, as ``layerwise_inference`` takes them.
-    The six models of ``layerwise_inference``, each through the driver named there."""
+    The seven models of ``layerwise_inference`` (``GraphTransformer`` included), each through the driver named there."""
     what = "evaluate"
     nodes, segments = _check_splits(what, splits, nodes)
     sink = _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, y, _Classify(y), edge_weight)
@@ -1707,6 +1947,16 @@ def gatv2_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 << 20,
     if not isinstance(model, GATv2):
         raise NotImplementedError(f"{what}: implemented for GATv2, not {type(model).__name__} (the other models: "
                                   "layerwise_inference)")
+    return _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, None, _LogProbs())
+
+
+def transformer_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 << 20, act_dtype=torch.float32):
+    """``layerwise_inference`` under GraphTransformer's own name: the same call, for a ``models.GraphTransformer`` model
+    only (``_transformer_layer`` has the order of operations and the memory)"""
+    what = "transformer_inference"
+    if not isinstance(model, GraphTransformer):
+        raise NotImplementedError(f"{what}: implemented for GraphTransformer, not {type(model).__name__} (the other "
+                                  "models: layerwise_inference)")
     return _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, None, _LogProbs())
 
 

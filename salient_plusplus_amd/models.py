@@ -1547,9 +1547,11 @@ class GraphTransformer(torch.nn.Module):
     multiple of ``heads``); the last layer is the mean of its heads.  ``beta`` and ``attn_dropout`` are every conv's
     ``beta`` and ``dropout``.
 
-    There is no ``inference`` method: exact layer-wise scoring over the resident graph (and the partitioned, field
-    and fp8 entries) is not built for this model.  Evaluate it batch-wise, through this forward on sampled batches in
-    eval mode, as the reference evaluates its models."""
+    There is no ``inference`` method.  Exact layer-wise scoring over the resident graph is
+    ``inference.layerwise_inference(model, ...)`` (``inference.evaluate`` for predictions and loss;
+    csrc/graph_transformer.hip); the partitioned, field and fp8 entries are not built for this model.  It can also be
+    evaluated batch-wise, through this forward on sampled batches in eval mode, as the reference evaluates its
+    models."""
 
     def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, heads=1, beta=False, attn_dropout=0.0):
         super().__init__()

@@ -20,6 +20,9 @@ the logits: 4 * H per entry (a_src) and 8 * H per target (a_src of the self loop
 ``gatv2_inference``, passes as for gat.  Run it in the same session as ``--model gat`` at the same heads and width, which is its
 yardstick.  At S-papers the last layer's projected rows are [N, heads * Cp] twice (172 classes pad to Cp = 256): heads = 1, or
 ``--share-weights`` with fewer classes, is what fits one device (inference._gatv2_layer has the arithmetic).
+``--model transformer``: GraphTransformer 3 x hidden at ``--heads`` (``--beta``: the gated skip) through
+spp_graph_transformer_forward inside ``layerwise_inference``, passes as for gatv2.  Five [N, hidden] matrices are live
+(inference._transformer_layer has the arithmetic): S-papers at hidden 256 does not fit one device.
 
 ``--model sageresinception``: SAGEResInception 3 x hidden scored at a random sample of ``--nodes`` nodes; per layer the
 aggregation seconds as above, the epilogue seconds (events around every spp_resinc_epilogue call, summed; bytes: z, the
@@ -72,7 +75,8 @@ def main():
     ap.add_argument("--hidden", type=int, default=256)
     ap.add_argument("--classes", type=int, default=172)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--model", choices=("sage", "gat", "gatv2", "sageresinception", "gcn"), default="sage")
+    ap.add_argument("--model", choices=("sage", "gat", "gatv2", "transformer", "sageresinception", "gcn"), default="sage")
+    ap.add_argument("--beta", action="store_true", help="transformer: every conv's beta gate (torch ops per slab)")
     ap.add_argument("--share-weights", action="store_true", help="gatv2: lin_r is lin_l (one projection, x_r = x_l)")
     ap.add_argument("--heads", type=int, default=1)
     ap.add_argument("--repeats", type=int, default=3)
@@ -107,6 +111,8 @@ def main():
         return gat_leg(a, wl, res)
     if a.model == "gatv2":
         return gatv2_leg(a, wl, res)
+    if a.model == "transformer":
+        return transformer_leg(a, wl, res)
     if a.model == "sageresinception":
         return resinc_leg(a, wl, res)
     if a.model == "gcn":
@@ -678,6 +684,57 @@ def gatv2_leg(a, wl, res):
         res["passes"].append(one)
         print(json.dumps(one), flush=True)
     inf._gatv2_launch = inner
+    res.pop("layers")
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+def transformer_leg(a, wl, res):
+    """``gatv2_leg`` for GraphTransformer: the slabs' ``inference._transformer_launch`` timed inside whole
+    ``layerwise_inference`` passes.  The bytes: the entries' rows of k and v, per target its rows of q and (when the
+    kernel adds it) skip, the indices and the output."""
+    from salient_plusplus_amd import inference as inf
+    from salient_plusplus_amd.models import GraphTransformer
+    x, rowptr, col = wl.x, wl.rowptr, wl.col
+    N, E, H = wl.num_nodes, col.numel(), a.heads
+    res.update(model="transformer", heads=H, beta=bool(a.beta), chunk=inf.graph_transformer_chunk(), passes=[])
+    spans = []
+    inner = inf._transformer_launch
+
+    def timed(q, k, v, skip, *args):
+        b, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        b.record()
+        out = inner(q, k, v, skip, *args)
+        e.record()
+        spans.append((q.size(1), q.element_size(), out.size(0), out.size(1) * out.element_size(), skip is not None, b, e))
+        return out
+    inf._transformer_launch = timed
+    torch.manual_seed(0)
+    model = GraphTransformer(x.size(1), a.hidden, a.classes, 3, heads=H, beta=a.beta).to(x.device)
+    slabs = -(-N // a.rows_per_slab)
+    for rep in range(a.repeats):
+        del spans[:]
+        torch.cuda.synchronize()
+        t0 = time.time()
+        out = inf.layerwise_inference(model, x, rowptr, col, rows_per_slab=a.rows_per_slab, act_dtype=torch.bfloat16)
+        torch.cuda.synchronize()
+        one = {"pass": rep, "total_s": round(time.time() - t0, 3), "layers": []}
+        assert out.shape == (N, a.classes) and bool(torch.isfinite(out[:: max(1, N // 4096)]).all())
+        del out
+        for layer in range(3):
+            part = spans[layer * slabs:(layer + 1) * slabs]
+            F_, s_in, fused = part[0][0], part[0][1], part[0][4]      # (the last layer's F is heads * the padded classes)
+            agg_s = sum(b.elapsed_time(e) for *_x, b, e in part) / 1e3
+            nbytes = (2 * E + (2 if fused else 1) * N) * F_ * s_in + 16 * N + 8 * E + sum(p[2] * p[3] for p in part)
+            one["layers"].append({"layer": layer + 1, "F": F_, "x_bytes_per_elem": s_in, "agg_s": round(agg_s, 4),
+                                  "edges_per_s": round(E / agg_s), "algorithmic_TBps": round(nbytes / agg_s / 1e12, 3)})
+        one["kernel_s"] = round(sum(l["agg_s"] for l in one["layers"]), 4)
+        one["kernel_share"] = round(one["kernel_s"] / one["total_s"], 3)
+        res["passes"].append(one)
+        print(json.dumps(one), flush=True)
+    inf._transformer_launch = inner
     res.pop("layers")
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
