@@ -1,7 +1,10 @@
 // What the GATv2 forward kernels share (gatv2.hip: k_gatv2_fwd over an MFG hop; graph_gatv2.hip: k_graph_gatv2_rows /
 // k_graph_gatv2_long over rows of the resident graph): the lane mapping, the logit of an entry, the step of a head's
-// online softmax, the merge of two states, and on the host the (NQ, CPH) dispatch.  ONE body for both translation units:
-// a short row of the graph kernels is the bits of k_gatv2_fwd because it runs these very functions.
+// online softmax and the merge of two states.  ONE body for both translation units: a short row of the graph kernels
+// is the bits of k_gatv2_fwd because it runs these very functions.  The lane mapping, State and butterfly are
+// TransformerConv's as well (transformer_core.hip.h), and so is the host section for all four translation units
+// (gatv2.hip, transformer_conv.hip, graph_gatv2.hip, graph_transformer.hip): the refusals of (heads, C), the launch
+// geometry, and the forward's (NQ, CPH) and the backward's (NS, SPH) dispatch.
 //
 // 4 columns per lane: piece p = q * lpr + lane holds columns 4p .. 4p + 3, q < NQ chunks of lpr = min(64, D / 4) lanes.
 // A head is G = C / 4 consecutive pieces: G <= lpr lanes of one chunk (CPH = 1: a lane sees NQ heads, one per chunk) or
@@ -216,6 +219,21 @@ static inline int log2_of(int64_t v) {
 }
 static inline bool pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
 
+// The shapes the kernels are built for, refused in the order and the words include/spp.h documents for every GATv2 and
+// TransformerConv entry, training and graph alike.  Two helpers: the training entries check their element code between
+// the head count and C.
+static inline spp_status check_heads(const char* who, int32_t heads) {
+  SPP_REQUIRE(heads == 1 || heads == 2 || heads == 4 || heads == 8, "%s: heads must be 1, 2, 4 or 8 (got %d)", who,
+              (int)heads);
+  return SPP_OK;
+}
+static inline spp_status check_channels(const char* who, int64_t heads, int64_t C) {
+  SPP_REQUIRE(C > 0 && C % 4 == 0, "%s: needs C > 0 and C %% 4 == 0 (got %lld)", who, (long long)C);
+  SPP_REQUIRE(pow2(C / 4), "%s: built for C / 4 a power of two (got C = %lld)", who, (long long)C);
+  SPP_REQUIRE(C <= 1024 && heads * C <= 1024, "%s: needs D = heads * C <= 1024", who);
+  return SPP_OK;
+}
+
 // the launch geometry of D = heads * C columns (heads in {1, 2, 4, 8}, C / 4 a power of two, D <= 1024)
 struct Shape {
   int lpr_log2, seg_log2, g_log2, nq, cph;
@@ -241,6 +259,26 @@ static void with_fwd_shape(int nq, int cph, Fn&& fn) {
     case 4 * 8 + 1: fn(IC<4>{}, IC<1>{}); break;
     case 4 * 8 + 2: fn(IC<4>{}, IC<2>{}); break;
     default: fn(IC<4>{}, IC<4>{}); break;
+  }
+}
+// fn(IC<NS>{}, IC<SPH>{}): the backward's steps per lane and steps per head (NS / SPH <= 8 heads)
+template <class Fn>
+static void with_bwd_shape(int ns, int sph, Fn&& fn) {
+  switch (ns * 32 + sph) {
+    case 1 * 32 + 1: fn(IC<1>{}, IC<1>{}); break;
+    case 2 * 32 + 1: fn(IC<2>{}, IC<1>{}); break;
+    case 2 * 32 + 2: fn(IC<2>{}, IC<2>{}); break;
+    case 4 * 32 + 1: fn(IC<4>{}, IC<1>{}); break;
+    case 4 * 32 + 2: fn(IC<4>{}, IC<2>{}); break;
+    case 4 * 32 + 4: fn(IC<4>{}, IC<4>{}); break;
+    case 8 * 32 + 1: fn(IC<8>{}, IC<1>{}); break;
+    case 8 * 32 + 2: fn(IC<8>{}, IC<2>{}); break;
+    case 8 * 32 + 4: fn(IC<8>{}, IC<4>{}); break;
+    case 8 * 32 + 8: fn(IC<8>{}, IC<8>{}); break;
+    case 16 * 32 + 2: fn(IC<16>{}, IC<2>{}); break;
+    case 16 * 32 + 4: fn(IC<16>{}, IC<4>{}); break;
+    case 16 * 32 + 8: fn(IC<16>{}, IC<8>{}); break;
+    default: fn(IC<16>{}, IC<16>{}); break;
   }
 }
 

@@ -153,12 +153,8 @@ extern "C" spp_status spp_graph_gatv2_forward(const spp_graph_gatv2_desc* desc, 
   const char* who = "spp_graph_gatv2_forward";
   SPP_REQUIRE(desc, "%s: NULL descriptor", who);
   const spp_graph_gatv2_desc& d = *desc;
-  // the shapes of spp_gatv2_forward, in its order
-  SPP_REQUIRE(d.heads == 1 || d.heads == 2 || d.heads == 4 || d.heads == 8, "%s: heads must be 1, 2, 4 or 8 (got %d)", who,
-              (int)d.heads);
-  SPP_REQUIRE(d.C > 0 && d.C % 4 == 0, "%s: needs C > 0 and C %% 4 == 0 (got %lld)", who, (long long)d.C);
-  SPP_REQUIRE(pow2(d.C / 4), "%s: built for C / 4 a power of two (got C = %lld)", who, (long long)d.C);
-  SPP_REQUIRE(d.C <= 1024 && d.heads * d.C <= 1024, "%s: needs D = heads * C <= 1024", who);
+  SPP_TRY(check_heads(who, d.heads));  // the shapes of spp_gatv2_forward, in its order
+  SPP_TRY(check_channels(who, d.heads, d.C));
   const int64_t D = d.heads * d.C;
   const Common c{d.x_elem, d.out_elem,    d.rowptr_dev,     d.col_dev,     d.x_l_stride_elems, d.x_rows,
                  D,        d.target_row0, d.target_ids_dev, d.num_targets, d.out_dev,          d.out_stride_elems};

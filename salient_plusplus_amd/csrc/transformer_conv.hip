@@ -176,38 +176,14 @@ __global__ __launch_bounds__(kTfNT) void k_transformer_bwd(const int64_t* __rest
 using namespace spp;
 using namespace spp::gatv2;
 
-// fn(IC<NS>{}, IC<SPH>{}): the backward's steps per lane and steps per head (NS / SPH <= 8 heads)
-template <class Fn>
-static void with_tf_bwd_shape(int ns, int sph, Fn&& fn) {
-  switch (ns * 32 + sph) {
-    case 1 * 32 + 1: fn(IC<1>{}, IC<1>{}); break;
-    case 2 * 32 + 1: fn(IC<2>{}, IC<1>{}); break;
-    case 2 * 32 + 2: fn(IC<2>{}, IC<2>{}); break;
-    case 4 * 32 + 1: fn(IC<4>{}, IC<1>{}); break;
-    case 4 * 32 + 2: fn(IC<4>{}, IC<2>{}); break;
-    case 4 * 32 + 4: fn(IC<4>{}, IC<4>{}); break;
-    case 8 * 32 + 1: fn(IC<8>{}, IC<1>{}); break;
-    case 8 * 32 + 2: fn(IC<8>{}, IC<2>{}); break;
-    case 8 * 32 + 4: fn(IC<8>{}, IC<4>{}); break;
-    case 8 * 32 + 8: fn(IC<8>{}, IC<8>{}); break;
-    case 16 * 32 + 2: fn(IC<16>{}, IC<2>{}); break;
-    case 16 * 32 + 4: fn(IC<16>{}, IC<4>{}); break;
-    case 16 * 32 + 8: fn(IC<16>{}, IC<8>{}); break;
-    default: fn(IC<16>{}, IC<16>{}); break;
-  }
-}
-
 // The checks of both entries, in the order include/spp.h documents: descriptor, head count, element code, C, power of
 // two, D, sizes (T == 0 is decided by the caller right after), strides, NULL buffers, alignment, scale.  Nothing here
 // touches the device.
 static spp_status tf_check_shape(const spp_transformer_desc* d, const char* who) {
   SPP_REQUIRE(d != nullptr, "%s: NULL descriptor", who);
-  SPP_REQUIRE(d->heads == 1 || d->heads == 2 || d->heads == 4 || d->heads == 8,
-              "%s: heads must be 1, 2, 4 or 8 (got %d)", who, (int)d->heads);
+  SPP_TRY(check_heads(who, d->heads));
   SPP_REQUIRE(elem_ok(d->x_elem), "%s: unknown element code %d", who, (int)d->x_elem);
-  SPP_REQUIRE(d->C > 0 && d->C % 4 == 0, "%s: needs C > 0 and C %% 4 == 0 (got %lld)", who, (long long)d->C);
-  SPP_REQUIRE(pow2(d->C / 4), "%s: built for C / 4 a power of two (got C = %lld)", who, (long long)d->C);
-  SPP_REQUIRE(d->C <= 1024 && d->heads * d->C <= 1024, "%s: needs D = heads * C <= 1024", who);
+  SPP_TRY(check_channels(who, d->heads, d->C));
   SPP_REQUIRE(d->num_targets >= 0 && d->num_sources >= d->num_targets, "%s: needs 0 <= T <= S", who);
   return SPP_OK;
 }
@@ -264,7 +240,7 @@ extern "C" spp_status spp_transformer_backward(const spp_transformer_desc* d, vo
   const int seg_log2 = log2_of(std::min<int64_t>(d->C, lpt)), c_log2 = log2_of(d->C);
   const unsigned grid = (unsigned)ceil_div(T << lpt_log2, kTfNT);
   with_elem(d->x_elem, [&](auto tin) {
-    with_tf_bwd_shape(ns, sph, [&](auto n, auto s) {
+    with_bwd_shape(ns, sph, [&](auto n, auto s) {
       using Tin = typename decltype(tin)::type;
       hipLaunchKernelGGL((k_transformer_bwd<Tin, decltype(n)::value, decltype(s)::value>), dim3(grid), dim3(kTfNT), 0,
                          as_stream(stream), d->rowptr_dev, d->col_dev, T, static_cast<const Tin*>(d->q_dev),
