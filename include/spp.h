@@ -1981,8 +1981,8 @@ spp_status spp_gatv2_backward_drop(const spp_gatv2_desc* desc, void* stream, flo
  *   D or not a multiple of 4; a NULL rowptr, q, k, v, out, row_max or row_sum (backward: or grad_out or grad_q); one
  *   of them, or col, misaligned (backward: then a misaligned grad_out, grad_q, grad_k or grad_v); a scale that is not
  *   finite or not positive.  spp_last_error names the failing condition.  SPP_ABI_VERSION stays 6.
- *   Not built: attention dropout inside the kernels and edge features (PyG's edge_dim).  The entry over the resident
- *   graph is f3z, below.
+ *   Not built: edge features (PyG's edge_dim).  Attention dropout is f4a, the entry over the resident graph f3z, both
+ *   below.
  * ------------------------------------------------------------------------- */
 typedef struct spp_transformer_desc {
   int32_t heads;              /* H: 1, 2, 4 or 8 */
@@ -2092,6 +2092,43 @@ int64_t spp_graph_transformer_chunk(void);
 int64_t spp_graph_transformer_workspace_bytes(int64_t num_targets);
 spp_status spp_graph_transformer_forward(const spp_graph_transformer_desc* desc, void* workspace_dev,
                                          int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * f4a  ATTENTION DROPOUT for TransformerConv: PyG's TransformerConv(dropout=p), F.dropout(alpha, p, training) on the
+ *      attention coefficients.  The pair of f3y with (p, training, seed) appended after `stream`, exactly as f3x extends
+ *      f3v; the descriptor, the layouts, the shapes and everything else as f3y states them.  Per target i and head h,
+ *      over ALL CSR entries of row i in CSR order (f3y's convention: no self loop, diagonal entries kept, repeats
+ *      counted):
+ *        alpha_ij = softmax_j(scale * q_i . k_j)   over ALL entries, exactly as f3y: the mask never enters the softmax
+ *        d_ij     = keep_ij / (1 - p)              keep in {0, 1} per (entry, head)
+ *        out[i,h,:] = sum_j d_ij alpha_ij v[j,h,:]     computed as acc * (drop_scale / row_sum), drop_scale the fp32
+ *                                                      value of 1 / (1 - p), acc taking only the kept entries
+ *      row_max and row_sum are the values of spp_transformer_forward on the same inputs, bit for bit.  A row without
+ *      entries gives exact zeros (f3y's row_sum == 0 guard); a (target, head) whose every entry is dropped gives exact
+ *      zeros in out, with the row_max / row_sum of the p = 0 call.  Backward, with go = g_i . out_i on the saved
+ *      (dropped) out, gh = g_i . v_j and d = keep ? drop_scale : 0:
+ *        ge = alpha (d gh - go)                    a dropped entry still sends -alpha go to its logit: dL/dalpha_ij = d_ij gh
+ *                                                  and sum_k alpha_ik d_ik gh_ik = go, so this is the softmax gradient (f3t)
+ *        grad_q[i,h,c]  = sum_j ge * scale * k[j,h,c]
+ *        grad_k[j,h,c] += ge * scale * q[i,h,c]
+ *        grad_v[j,h,c] += d * alpha * g[i,h,c]
+ *      alpha is recomputed from the forward's logit through f3y's summation tree, bit for bit; grad_k and grad_v are
+ *      independently NULL-able as in f3y.  Forward and backward take the same (p, seed).
+ *   Keep rule: f3t's, unchanged, WITHOUT self-loop draws: draw index i = k * H + h for CSR entry k (its absolute position
+ *   in col, so a hop's mask does not depend on which workgroup handles the row); draw(i) = the low (i even) or high
+ *   (i odd) 32 bits of mix64(seed + (i >> 1) * 0x9E3779B97F4A7C15); kept iff draw(i) < keep_thr.  The first E * H bytes of
+ *   spp_gat_mh_attn_keep(E, T, H, p, seed, ...) are therefore the mask these entries apply.
+ *   Refusals: those of the entry each extends, in f3y's order, with `0 <= p < 1` checked right after the shape checks
+ *   (through 0 <= T <= S), so before the T == 0 return, the strides, the NULL and alignment checks and scale; a NaN p is
+ *   refused, and p is checked with training = 0 too.
+ *   training = 0 or p = 0 launches the kernels of the entry without dropout: the same bits.  spp_transformer_desc is
+ *   untouched; SPP_ABI_VERSION stays 6.
+ *   Not built: dropout in the entry over the resident graph (f3z scores in eval mode).
+ * ------------------------------------------------------------------------- */
+spp_status spp_transformer_forward_drop(const spp_transformer_desc* desc, void* stream, float p, int32_t training,
+                                        uint64_t seed);
+spp_status spp_transformer_backward_drop(const spp_transformer_desc* desc, void* stream, float p, int32_t training,
+                                         uint64_t seed);
 
 #ifdef __cplusplus
 }

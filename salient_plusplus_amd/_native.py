@@ -424,6 +424,10 @@ SIGNATURES = {
     # TransformerConv over a hop (spp.h f3y)
     "spp_transformer_forward": (C.c_int, [C.POINTER(TransformerDesc), p]),
     "spp_transformer_backward": (C.c_int, [C.POINTER(TransformerDesc), p]),
+    # attention dropout (spp.h f4a): the training pair + (p, training, seed); the mask is the first E * H bytes of
+    # spp_gat_mh_attn_keep's
+    "spp_transformer_forward_drop": (C.c_int, [C.POINTER(TransformerDesc), p, C.c_float, i32, C.c_uint64]),
+    "spp_transformer_backward_drop": (C.c_int, [C.POINTER(TransformerDesc), p, C.c_float, i32, C.c_uint64]),
     # TransformerConv over rows of the resident graph (spp.h f3z)
     "spp_graph_transformer_chunk": (i64, []),
     "spp_graph_transformer_workspace_bytes": (i64, [i64]),

@@ -9,8 +9,10 @@
 // backward has three row gradients, and there is no grad_att (so no LDS reduction and one group per target).  What is
 // kept: gatv2_core.hip.h's lane mapping, per-head online softmax (State), butterfly and (NQ, CPH) dispatch, unchanged;
 // several neighbours' loads in flight per round; one fp32 atomic per column per entry on contiguous wave-wide segments.
-// Not here: attention dropout in the kernels and edge features.  The kernels over the resident graph are
-// graph_transformer.hip's; the forward's per-entry body is shared with them (transformer_core.hip.h).
+// Attention dropout (spp_transformer_forward_drop / spp_transformer_backward_drop, spp.h f4a) is the kDrop = true
+// instantiation of the same two kernels: the keep rule of f3t without self-loop draws, the mask never in the softmax.
+// Not here: edge features.  The kernels over the resident graph are graph_transformer.hip's; the forward's per-entry
+// body is shared with them (transformer_core.hip.h).
 #include "transformer_core.hip.h"
 
 #include <cmath>
@@ -30,13 +32,18 @@ constexpr int kTfNT = 256;
 // carries all NB * HL values (the logit's tree above); the logit is the butterfly's sum times scale (one product, the
 // same bits in every lane of the head's segment); State::take does the online softmax on the v pieces.  The row starts from the empty state.
 // No atomics: the same bits in every run.
-template <typename Tin, int NQ, int CPH>
+// kDrop: out[i,h,:] = sum_j d_ij^h alpha_ij^h v[j,h,:], d = keep / (1 - p) per (entry, head) by the keep rule of f3t
+// (entry k for CSR entry k, no self loop).  The softmax runs over ALL entries -- row_max and row_sum are the
+// kDrop = false bits -- and only acc skips a dropped entry.  The lane's head hl is global head
+// ((hl * CPH) * lpr + lane) >> g_log2, the expression that finds row_max's head below.
+template <typename Tin, int NQ, int CPH, bool kDrop>
 __global__ __launch_bounds__(kTfNT) void k_transformer_fwd(const int64_t* __restrict__ rowptr,
                                                            const int64_t* __restrict__ col, int64_t T, const Tin* qm,
                                                            int64_t q_stride, const Tin* km, int64_t k_stride,
                                                            const Tin* vm, int64_t v_stride, float scale, int lpr_log2,
                                                            int seg_log2, int g_log2, int H, float* __restrict__ out,
-                                                           float* __restrict__ row_max, float* __restrict__ row_sum) {
+                                                           float* __restrict__ row_max, float* __restrict__ row_sum,
+                                                           [[maybe_unused]] ActArgs drop) {
 #pragma clang fp contract(off)
   constexpr int NB = tf_nb<NQ>();
   const int lpr = 1 << lpr_log2, lane = threadIdx.x & (lpr - 1);
@@ -53,19 +60,57 @@ __global__ __launch_bounds__(kTfNT) void k_transformer_fwd(const int64_t* __rest
   State<NQ, CPH> st;
   st.clear();
   const int64_t b = rowptr[t], e = rowptr[t + 1];
-  walk<NB>(st, qv, c0, km, k_stride, vm, v_stride, col, b, e, (int64_t)-1, scale, seg_log2);  // (an MFG hop: ids as they are)
+  if constexpr (kDrop) {
+    constexpr int HL = NQ / CPH;
+    Drop<HL> dr;
+    dr.a = drop, dr.H = H;
+#pragma unroll
+    for (int hl = 0; hl < HL; ++hl) dr.head[hl] = ((hl * CPH) * lpr + lane) >> g_log2;
+    walk<NB, true>(st, qv, c0, km, k_stride, vm, v_stride, col, b, e, (int64_t)-1, scale, seg_log2, &dr);
+  } else {
+    walk<NB>(st, qv, c0, km, k_stride, vm, v_stride, col, b, e, (int64_t)-1, scale, seg_log2);  // (an MFG hop: ids as they are)
+  }
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
     const int hl = q / CPH;
     const int p = q * lpr + lane;
     const bool empty = st.ss[hl] == 0.f;  // a row without entries: out, row_max and row_sum are 0, nothing is divided
     f4 r = {0.f, 0.f, 0.f, 0.f};
-    if (!empty) r = st.result(q);
+    if (!empty) r = st.template result<kDrop>(q, drop.scale);  // kDrop: acc * (drop_scale / ss)
     *reinterpret_cast<float4*>(out + t * D + (int64_t)p * 4) = make_float4(r.x, r.y, r.z, r.w);
     if ((p & ((1 << g_log2) - 1)) == 0) {  // the head's first piece
       row_max[t * H + (p >> g_log2)] = empty ? 0.f : st.mm[hl];
       row_sum[t * H + (p >> g_log2)] = st.ss[hl];
     }
+  }
+}
+
+// The backward's draw of (entry, head): attn_keep_head(entry, H, head, a), for every argument.  kWaveHash (NS >= 4, so
+// D >= 256: lpt = 64, a wavefront is ONE target, and C >= 32, so the two heads that share a hash sit in the same step of
+// every lane): entry and head & ~1 are the same in all lanes, so the hash's argument is taken from the first lane and
+// the 64-bit mix runs once per wavefront on the scalar unit; only the choice of the hash's half stays per lane.  Left
+// on the vector unit, four hashes in flight cost <*, 4, 1> two waves per SIMD.
+// What kWaveHash relies on, all of it given by NS >= 4 and the entries' shape checks (check_heads, check_channels):
+//   lpt == 64, so the 64 lanes of a wavefront are ONE group, one target, one entry k at a time, and they leave the
+//     kernel together (t >= T): the first active lane's entry is every lane's;
+//   C >= 32 (H <= 8 and D >= 256), so head & ~1 = ((lane + 64 * hl * SPH) >> c_log2) & ~1 does not depend on the lane:
+//     C = 32: head = 2 hl + (lane >> 5); C = 64: head = hl; C >= 128: SPH = C / 64 and head = hl;
+//   H == 1 or H even (check_heads: 1, 2, 4, 8): the line that forms i2 says where.  An odd H > 1 would need
+//     (entry * H + head) >> 1 with the lane's own head, which is not uniform.
+template <bool kWaveHash>
+__device__ __forceinline__ bool bwd_keep(uint64_t entry, int H, int head, const ActArgs& a) {
+  if constexpr (!kWaveHash) {
+    return attn_keep_head(entry, H, head, a);
+  } else {
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)entry);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(entry >> 32));
+    const uint32_t he = __builtin_amdgcn_readfirstlane((uint32_t)head & ~1u);
+    // i = entry * H + head.  H even: entry * H is even, so i >> 1 = (entry * H + (head & ~1)) >> 1; H = 1: head = 0 and
+    // i >> 1 = entry >> 1.  Holds for H in {1, even} ONLY (check_heads admits 1, 2, 4, 8)
+    const uint64_t i2 = ((((uint64_t)hi << 32) | lo) * (uint64_t)H + he) >> 1;
+    const uint64_t r = mix64(a.seed + i2 * 0x9E3779B97F4A7C15ull);
+    const bool odd = (((uint32_t)entry * (uint32_t)H + (uint32_t)head) & 1u) != 0;
+    return (uint32_t)(odd ? r >> 32 : r) < a.keep_thr;
   }
 }
 
@@ -77,7 +122,13 @@ __global__ __launch_bounds__(kTfNT) void k_transformer_fwd(const int64_t* __rest
 // written once, zeros for a row without entries (whose row_sum = 0 is never divided by).  The logit is the forward's,
 // bit for bit (the tree at the top of the file; contraction off, so that the product by scale is rounded before
 // row_max is subtracted, as it is there).
-template <typename Tin, int NS, int SPH>
+// kDrop (the forward's (p, seed)): go is taken on the saved DROPPED out, so sum_j d alpha gh = go and
+// ge = alpha (d gh - go) is the softmax gradient again -- a dropped entry (d = 0) still sends -alpha go to its logit --
+// and grad_v[j] takes d alpha g_i.  d = keep ? 1 / (1 - p) : 0 per (entry, head), the forward's draws: the lane's head
+// hl is global head (lane + lpt * hl * SPH) >> c_log2.  The draw is bwd_keep above: for NS < 4 every lane hashes for
+// the heads it holds (attn_keep_head); from NS = 4 on the hash runs once per wavefront on the first lane's argument and
+// a lane only picks its half of it.
+template <typename Tin, int NS, int SPH, bool kDrop>
 __global__ __launch_bounds__(kTfNT) void k_transformer_bwd(const int64_t* __restrict__ rowptr,
                                                            const int64_t* __restrict__ col, int64_t T, const Tin* qm,
                                                            int64_t q_stride, const Tin* km, int64_t k_stride,
@@ -87,7 +138,8 @@ __global__ __launch_bounds__(kTfNT) void k_transformer_bwd(const int64_t* __rest
                                                            const float* __restrict__ row_max,
                                                            const float* __restrict__ row_sum,
                                                            const float* __restrict__ g, float* __restrict__ grad_q,
-                                                           float* grad_k, float* grad_v) {
+                                                           float* grad_k, float* grad_v,
+                                                           [[maybe_unused]] ActArgs drop) {
 #pragma clang fp contract(off)
   constexpr int HL = NS / SPH;
   const int lpt = 1 << lpt_log2;
@@ -97,9 +149,11 @@ __global__ __launch_bounds__(kTfNT) void k_transformer_bwd(const int64_t* __rest
   if (t >= T) return;  // whole groups leave together
   const int64_t b = rowptr[t], e = rowptr[t + 1];
   float gv[NS], qv[NS], gq[NS], go[HL], m[HL], inv_s[HL];
+  [[maybe_unused]] int heads[HL];
 #pragma unroll
   for (int hl = 0; hl < HL; ++hl) {
     const int head = (lane + lpt * hl * SPH) >> c_log2;
+    if constexpr (kDrop) heads[hl] = head;
     const float s = row_sum[t * H + head];
     m[hl] = row_max[t * H + head];
     inv_s[hl] = s > 0.f ? 1.f / s : 0.f;
@@ -125,6 +179,11 @@ __global__ __launch_bounds__(kTfNT) void k_transformer_bwd(const int64_t* __rest
     for (int i = 0; i < NS; ++i) {
       kx[i] = load1(km + j * k_stride + lane + lpt * i);
       vx[i] = load1(vm + j * v_stride + lane + lpt * i);
+    }
+    [[maybe_unused]] float dq[HL];  // kDrop: d = keep / (1 - p)
+    if constexpr (kDrop) {
+#pragma unroll
+      for (int hl = 0; hl < HL; ++hl) dq[hl] = bwd_keep<(NS >= 4)>((uint64_t)k, H, heads[hl], drop) ? drop.scale : 0.f;
     }
 #pragma unroll
     for (int hl = 0; hl < HL; ++hl) gh[hl] = 0.f;
@@ -158,7 +217,12 @@ __global__ __launch_bounds__(kTfNT) void k_transformer_bwd(const int64_t* __rest
 #pragma unroll
     for (int hl = 0; hl < HL; ++hl) {
       a[hl] = expf(pe[hl] * scale - m[hl]) * inv_s[hl];
-      ges[hl] = a[hl] * (gh[hl] - go[hl]) * scale;  // ge * scale
+      if constexpr (kDrop) {
+        ges[hl] = a[hl] * (dq[hl] * gh[hl] - go[hl]) * scale;  // ge * scale
+        a[hl] *= dq[hl];  // from here on a is the message's weight d alpha
+      } else {
+        ges[hl] = a[hl] * (gh[hl] - go[hl]) * scale;  // ge * scale
+      }
     }
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
@@ -206,32 +270,56 @@ static spp_status tf_check_rows(const spp_transformer_desc* d, const char* who, 
   return SPP_OK;
 }
 
-extern "C" spp_status spp_transformer_forward(const spp_transformer_desc* d, void* stream) {
-  const char* who = "spp_transformer_forward";
+// Attention dropout of the spp_transformer_*_drop entries (spp.h f4a); the entries without it pass TfDrop{}.  p is
+// checked right after the shape, before the T == 0 return and the rows, in eval mode too; training = 0 or p = 0 runs
+// the kDrop = false kernels.
+struct TfDrop {
+  bool given = false;
+  float p = 0.f;
+  int32_t training = 0;
+  uint64_t seed = 0;
+  bool on() const { return given && training && p > 0.f; }
+  ActArgs args() const { return act_args(on() ? p : 0.f, training, seed); }
+};
+static spp_status tf_check_drop(const TfDrop& dr, const char* who) {
+  SPP_REQUIRE(!dr.given || (dr.p >= 0.f && dr.p < 1.f), "%s: attention dropout needs 0 <= p < 1", who);
+  return SPP_OK;
+}
+// fn(std::bool_constant<kDrop>{})
+template <class Fn>
+static void with_drop(bool on, Fn&& fn) {
+  if (on) fn(std::true_type{}); else fn(std::false_type{});
+}
+
+static spp_status tf_forward(const spp_transformer_desc* d, void* stream, const char* who, const TfDrop& dr) {
   SPP_TRY(tf_check_shape(d, who));
+  SPP_TRY(tf_check_drop(dr, who));
   if (d->num_targets == 0) return SPP_OK;
   SPP_TRY(tf_check_rows(d, who, false));
   const int64_t T = d->num_targets;
   const Shape sh = shape_of(d->heads, d->C);
   const int lpr_log2 = sh.lpr_log2, seg_log2 = sh.seg_log2, g_log2 = sh.g_log2, nq = sh.nq, cph = sh.cph;
   const unsigned grid = (unsigned)ceil_div(T << lpr_log2, kTfNT);
+  const ActArgs da = dr.args();
   with_elem(d->x_elem, [&](auto tin) {
     with_fwd_shape(nq, cph, [&](auto q, auto c) {
-      using Tin = typename decltype(tin)::type;
-      hipLaunchKernelGGL((k_transformer_fwd<Tin, decltype(q)::value, decltype(c)::value>), dim3(grid), dim3(kTfNT), 0,
-                         as_stream(stream), d->rowptr_dev, d->col_dev, T, static_cast<const Tin*>(d->q_dev),
-                         d->q_stride_elems, static_cast<const Tin*>(d->k_dev), d->k_stride_elems,
-                         static_cast<const Tin*>(d->v_dev), d->v_stride_elems, d->scale, lpr_log2, seg_log2, g_log2,
-                         (int)d->heads, d->out_dev, d->row_max_dev, d->row_sum_dev);
+      with_drop(dr.on(), [&](auto drop) {
+        using Tin = typename decltype(tin)::type;
+        hipLaunchKernelGGL((k_transformer_fwd<Tin, decltype(q)::value, decltype(c)::value, decltype(drop)::value>),
+                           dim3(grid), dim3(kTfNT), 0, as_stream(stream), d->rowptr_dev, d->col_dev, T,
+                           static_cast<const Tin*>(d->q_dev), d->q_stride_elems, static_cast<const Tin*>(d->k_dev),
+                           d->k_stride_elems, static_cast<const Tin*>(d->v_dev), d->v_stride_elems, d->scale, lpr_log2,
+                           seg_log2, g_log2, (int)d->heads, d->out_dev, d->row_max_dev, d->row_sum_dev, da);
+      });
     });
   });
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
 }
 
-extern "C" spp_status spp_transformer_backward(const spp_transformer_desc* d, void* stream) {
-  const char* who = "spp_transformer_backward";
+static spp_status tf_backward(const spp_transformer_desc* d, void* stream, const char* who, const TfDrop& dr) {
   SPP_TRY(tf_check_shape(d, who));
+  SPP_TRY(tf_check_drop(dr, who));
   if (d->num_targets == 0) return SPP_OK;  // nothing is touched: grad_k / grad_v stay as the caller zeroed them
   SPP_TRY(tf_check_rows(d, who, true));
   const int64_t T = d->num_targets, D = d->heads * d->C;
@@ -239,17 +327,36 @@ extern "C" spp_status spp_transformer_backward(const spp_transformer_desc* d, vo
   const int ns = (int)(D / lpt), sph = (int)std::max<int64_t>(1, d->C / kWave);
   const int seg_log2 = log2_of(std::min<int64_t>(d->C, lpt)), c_log2 = log2_of(d->C);
   const unsigned grid = (unsigned)ceil_div(T << lpt_log2, kTfNT);
+  const ActArgs da = dr.args();
   with_elem(d->x_elem, [&](auto tin) {
     with_bwd_shape(ns, sph, [&](auto n, auto s) {
-      using Tin = typename decltype(tin)::type;
-      hipLaunchKernelGGL((k_transformer_bwd<Tin, decltype(n)::value, decltype(s)::value>), dim3(grid), dim3(kTfNT), 0,
-                         as_stream(stream), d->rowptr_dev, d->col_dev, T, static_cast<const Tin*>(d->q_dev),
-                         d->q_stride_elems, static_cast<const Tin*>(d->k_dev), d->k_stride_elems,
-                         static_cast<const Tin*>(d->v_dev), d->v_stride_elems, d->scale, lpt_log2, seg_log2, c_log2,
-                         (int)d->heads, d->out_dev, d->row_max_dev, d->row_sum_dev, d->grad_out_dev, d->grad_q_dev,
-                         d->grad_k_dev, d->grad_v_dev);
+      with_drop(dr.on(), [&](auto drop) {
+        using Tin = typename decltype(tin)::type;
+        hipLaunchKernelGGL((k_transformer_bwd<Tin, decltype(n)::value, decltype(s)::value, decltype(drop)::value>),
+                           dim3(grid), dim3(kTfNT), 0, as_stream(stream), d->rowptr_dev, d->col_dev, T,
+                           static_cast<const Tin*>(d->q_dev), d->q_stride_elems, static_cast<const Tin*>(d->k_dev),
+                           d->k_stride_elems, static_cast<const Tin*>(d->v_dev), d->v_stride_elems, d->scale, lpt_log2,
+                           seg_log2, c_log2, (int)d->heads, d->out_dev, d->row_max_dev, d->row_sum_dev, d->grad_out_dev,
+                           d->grad_q_dev, d->grad_k_dev, d->grad_v_dev, da);
+      });
     });
   });
   SPP_HIP_TRY(hipGetLastError());
   return SPP_OK;
+}
+
+extern "C" spp_status spp_transformer_forward(const spp_transformer_desc* d, void* stream) {
+  return tf_forward(d, stream, "spp_transformer_forward", TfDrop{});
+}
+extern "C" spp_status spp_transformer_backward(const spp_transformer_desc* d, void* stream) {
+  return tf_backward(d, stream, "spp_transformer_backward", TfDrop{});
+}
+// with attention dropout (spp.h f4a): (p, training, seed) after `stream`
+extern "C" spp_status spp_transformer_forward_drop(const spp_transformer_desc* d, void* stream, float p,
+                                                   int32_t training, uint64_t seed) {
+  return tf_forward(d, stream, "spp_transformer_forward_drop", TfDrop{true, p, training, seed});
+}
+extern "C" spp_status spp_transformer_backward_drop(const spp_transformer_desc* d, void* stream, float p,
+                                                    int32_t training, uint64_t seed) {
+  return tf_backward(d, stream, "spp_transformer_backward_drop", TfDrop{true, p, training, seed});
 }

@@ -48,11 +48,15 @@ constexpr int tf_nb() { return NQ <= 2 ? 4 : 2; }
 // logit is the butterfly's sum times scale (one product, the same bits in every lane of the head's segment);
 // State::take does the online softmax on the v pieces.  x_rows >= 0: an entry outside [0, x_rows) is node 0;
 // x_rows < 0: the ids are taken as they are (an MFG hop's).  b and e are the same for all lanes of the group.
-template <int NB, typename Tin, int NQ, int CPH>
+// kDrop (attention dropout of the training pair, spp.h f4a): CSR entry k is softmax entry k of the keep rule
+// (its absolute position in col); every lane draws for its own heads, dr->head, and the draws are issued right after
+// the rows' loads, ahead of the butterfly.  The softmax (mm, ss) takes every entry; only acc skips a dropped one.
+template <int NB, bool kDrop = false, typename Tin, int NQ, int CPH>
 __device__ __forceinline__ void walk(State<NQ, CPH>& st, const f4 (&qv)[NQ], const int64_t (&c0)[NQ], const Tin* km,
                                      int64_t k_stride, const Tin* vm, int64_t v_stride,
                                      const int64_t* __restrict__ col, int64_t b, int64_t e, int64_t x_rows,
-                                     float scale, int seg_log2) {
+                                     float scale, int seg_log2,
+                                     [[maybe_unused]] const Drop<NQ / CPH>* dr = nullptr) {
 #pragma clang fp contract(off)
   constexpr int HL = NQ / CPH;
   for (int64_t k0 = b; k0 < e; k0 += NB) {
@@ -70,6 +74,14 @@ __device__ __forceinline__ void walk(State<NQ, CPH>& st, const f4 (&qv)[NQ], con
         kv[u][q] = load4(km + j[u] * k_stride + c0[q]);
         vv[u][q] = load4(vm + j[u] * v_stride + c0[q]);
       }
+    [[maybe_unused]] bool keep[NB * HL];
+    if constexpr (kDrop) {
+#pragma unroll
+      for (int u = 0; u < NB; ++u)
+#pragma unroll
+        for (int hl = 0; hl < HL; ++hl)
+          keep[u * HL + hl] = attn_keep_head((uint64_t)(k0 + u), dr->H, dr->head[hl], dr->a);
+    }
     float pd[NB * HL];
 #pragma unroll
     for (int u = 0; u < NB; ++u)
@@ -89,7 +101,10 @@ __device__ __forceinline__ void walk(State<NQ, CPH>& st, const f4 (&qv)[NQ], con
     for (int u = 0; u < NB; ++u) {
       if (k0 + u >= e) continue;
 #pragma unroll
-      for (int hl = 0; hl < HL; ++hl) st.take(hl, pd[u * HL + hl] * scale, vv[u]);
+      for (int hl = 0; hl < HL; ++hl) {
+        if constexpr (kDrop) st.template take<true>(hl, pd[u * HL + hl] * scale, vv[u], keep[u * HL + hl]);
+        else st.take(hl, pd[u * HL + hl] * scale, vv[u]);
+      }
     }
   }
 }

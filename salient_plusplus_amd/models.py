@@ -1390,8 +1390,9 @@ def _transformer_reference(q, k, v, rowptr, col, scale, p=0.0):
     e_ij^h = scale * q[i,h] . k[j,h], alpha = softmax_j(e), out[i,h] = sum_j alpha_ij^h v[j,h] over ALL CSR entries of
     row i -- no self loop, diagonal entries kept, a repeated entry counted as often as it appears -- and zeros for a
     row without entries.  The path for everything the kernels do not read: CPU tensors, head counts outside
-    {1, 2, 4, 8}, C with C / 4 not a power of two, H * C > 1024; and for p > 0 in training, where F.dropout on alpha
-    draws torch's own mask (attention dropout inside the kernels is not built for this layer)."""
+    {1, 2, 4, 8}, C with C / 4 not a power of two, H * C > 1024.  p > 0 (training): F.dropout on alpha -- torch's own
+    mask, from the generator of alpha's device, NOT the kernels' counter-based one (_attn_keep_reference), which the
+    rows the kernels read get (spp.h f4a)."""
     T, H = q.size(0), q.size(1)
     dt = torch.float64 if q.dtype == torch.float64 else torch.float32
     q, k, v = q.to(dt), k.to(dt), v.to(dt)
@@ -1432,10 +1433,20 @@ class _TransformerLayer(torch.autograd.Function):
     [T, H, C] fp32, spp_transformer_forward / spp_transformer_backward.  The rows are fp32, fp16 or bf16 (under bf16
     autocast the projections outside the node give bf16 rows, which the kernels read as such); k and v may be views
     of one [S, 2 D] matrix.  The node runs with autocast off, returns fp32 and casts grad_q / grad_k / grad_v back to
-    the rows' dtype; a gradient nobody needs is not computed (NULL in the descriptor)."""
+    the rows' dtype; a gradient nobody needs is not computed (NULL in the descriptor).  p > 0: attention dropout
+    inside the kernels (spp.h f4a) -- the forward draws a seed from torch's CPU generator (_attn_seed), and both
+    directions call the _drop entries with (p, training = 1, seed), so the backward applies the forward's mask; p = 0
+    calls the entries without dropout."""
 
     @staticmethod
-    def forward(ctx, q, k, v, rowptr, col, heads, scale):
+    def _call(L, name, d, drop):
+        if drop:
+            nat.check(getattr(L, name + "_drop")(C.byref(d), _stream(), drop[0], 1, drop[1]))
+        else:
+            nat.check(getattr(L, name)(C.byref(d), _stream()))
+
+    @staticmethod
+    def forward(ctx, q, k, v, rowptr, col, heads, scale, p=0.0):
         with _no_autocast():
             L = nat.load()
             nat.require_device()
@@ -1443,8 +1454,9 @@ class _TransformerLayer(torch.autograd.Function):
             f32 = dict(dtype=torch.float32, device=q.device)
             out = torch.empty((T, heads, D // heads), **f32)
             rmax, rsum = torch.empty((T, heads), **f32), torch.empty((T, heads), **f32)
-            nat.check(L.spp_transformer_forward(
-                C.byref(_transformer_desc(q, k, v, heads, rowptr, col, scale, out, rmax, rsum)), _stream()))
+            ctx.drop = (float(p), _attn_seed()) if p > 0.0 else None
+            _TransformerLayer._call(L, "spp_transformer_forward",
+                                    _transformer_desc(q, k, v, heads, rowptr, col, scale, out, rmax, rsum), ctx.drop)
             ctx.save_for_backward(q, k, v, rowptr, col, out, rmax, rsum)
             ctx.heads, ctx.scale = int(heads), float(scale)
             return out
@@ -1461,9 +1473,9 @@ class _TransformerLayer(torch.autograd.Function):
             g_v = torch.zeros((S, D), **f32) if ctx.needs_input_grad[2] else None
             d = _transformer_desc(q, k, v, ctx.heads, rowptr, col, ctx.scale, out, rmax, rsum, grad_out_dev=g,
                                   grad_q_dev=g_q, grad_k_dev=g_k, grad_v_dev=g_v)
-            nat.check(nat.load().spp_transformer_backward(C.byref(d), _stream()))
+            _TransformerLayer._call(nat.load(), "spp_transformer_backward", d, ctx.drop)
             return (g_q.to(q.dtype) if ctx.needs_input_grad[0] else None, g_k.to(k.dtype) if g_k is not None else None,
-                    g_v.to(v.dtype) if g_v is not None else None, None, None, None, None)
+                    g_v.to(v.dtype) if g_v is not None else None, None, None, None, None, None)
 
 
 class TransformerConv(torch.nn.Module):
@@ -1485,10 +1497,13 @@ class TransformerConv(torch.nn.Module):
     C / 4 a power of two and H * C <= 1024, and _transformer_reference, the same function in plain torch ops, for
     everything else.
 
-    ``dropout`` = p in [0, 1): F.dropout(alpha, p, training) on the attention coefficients.  p = 0 and eval mode run
-    exactly the paths above; training with p > 0 takes _transformer_reference with torch's own mask (attention dropout
-    inside the kernels is not built for this layer).  ``edge_dim`` other than None (edge features) is not built:
-    NotImplementedError."""
+    ``dropout`` = p in [0, 1): F.dropout(alpha, p, training) on the attention coefficients of every (entry, head); the
+    softmax itself runs over all entries.  p = 0 and eval mode run exactly the paths above.  In training with p > 0 the
+    rows the kernels read take _TransformerLayer with the mask generated inside its kernels from a seed drawn from
+    torch's CPU generator (spp.h f4a; GATConv's rule without self loops, _attn_keep_reference(E, 0, H, p, seed) restates
+    it: torch.manual_seed makes a run repeatable); everything else takes _transformer_reference with F.dropout on its
+    alpha: torch's own mask there, not the kernels'.  No parameter or buffer: the state dict does not change.
+    ``edge_dim`` other than None (edge features) is not built: NotImplementedError."""
 
     def __init__(self, in_channels, out_channels, heads=1, concat=True, beta=False, dropout=0.0, edge_dim=None,
                  bias=True, root_weight=True):
@@ -1525,8 +1540,8 @@ class TransformerConv(torch.nn.Module):
         q, k, v = self.lin_query(x_target), self.lin_key(x), self.lin_value(x)
         scale = 1.0 / float(Cc) ** 0.5
         p = self.dropout if self.training else 0.0
-        if p == 0.0 and _transformer_kernels_read(q, k, v, H, Cc):
-            out = _TransformerLayer.apply(q, k, v, rowptr, col, H, scale)
+        if _transformer_kernels_read(q, k, v, H, Cc) and (p == 0.0 or q.is_cuda):
+            out = _TransformerLayer.apply(q, k, v, rowptr, col, H, scale, *((p,) if p > 0.0 else ()))
         else:
             out = _transformer_reference(q.view(T, H, Cc), k.view(S, H, Cc), v.view(S, H, Cc), rowptr, col, scale, p)
         out = out.reshape(T, H * Cc) if self.concat else out.mean(1)
@@ -1545,7 +1560,8 @@ class GraphTransformer(torch.nn.Module):
     TransformerConv, ReLU + dropout 0.5 between layers, log_softmax.  Every hidden layer is ``heads`` heads of
     ``hidden_channels // heads`` channels, concatenated (the hidden width stays ``hidden_channels``, which must be a
     multiple of ``heads``); the last layer is the mean of its heads.  ``beta`` and ``attn_dropout`` are every conv's
-    ``beta`` and ``dropout``.
+    ``beta`` and ``dropout``; with ``attn_dropout`` > 0 a training step stays on the HIP kernels (the mask is drawn
+    inside them, spp.h f4a), and eval mode and the layer-wise scoring below apply no dropout.
 
     There is no ``inference`` method.  Exact layer-wise scoring over the resident graph is
     ``inference.layerwise_inference(model, ...)`` (``inference.evaluate`` for predictions and loss;

@@ -10,8 +10,9 @@ attn=P: GAT(..., attn_dropout=P): PyG's dropout on the attention coefficients, i
 --heads H: GAT(..., heads=H) (default 1: the reference model): hidden layers of H heads of 256 // H, the last one averaged.
 gatv2: models.GATv2 (csrc/gatv2.hip), with --heads and attn= as GAT.
 transformer: models.GraphTransformer (csrc/transformer_conv.hip), with --heads and attn= as GAT (attn > 0 trains on the
-torch reference path: spp.h f3y).  reference: the same model with every layer sent to models._transformer_reference, the
-plain-torch path, for the comparison of DESIGN section 7 f3y."""
+kernels with the mask drawn inside them: spp.h f4a).  reference: the same model with every layer sent to
+models._transformer_reference, the plain-torch path (attn > 0: torch's own mask there), for the comparison of DESIGN
+section 7 f3y."""
 import contextlib
 import os
 import sys
