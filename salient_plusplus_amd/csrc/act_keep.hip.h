@@ -87,4 +87,26 @@ static inline ActArgs act_args(float p, int32_t training, uint64_t seed) {
   return a;
 }
 
+// The attention dropout arguments of a _drop entry (spp.h f3t, f3x, f4a: (p, training, seed) after `stream`), host side;
+// the entries without dropout pass AttnDrop{}.  training = 0 or p = 0 runs the kDrop = false kernels, which never read
+// the block (it then carries p = 0).
+struct AttnDrop {
+  bool given = false;
+  float p = 0.f;
+  int32_t training = 0;
+  uint64_t seed = 0;
+  bool on() const { return given && training && p > 0.f; }
+  ActArgs args() const { return act_args(on() ? p : 0.f, training, seed); }
+};
+// every entry runs this right after its shape checks, before its sizes and buffers, in eval mode too
+static inline spp_status attn_drop_check(const AttnDrop& dr, const char* who) {
+  SPP_REQUIRE(!dr.given || (dr.p >= 0.f && dr.p < 1.f), "%s: attention dropout needs 0 <= p < 1", who);
+  return SPP_OK;
+}
+// fn(std::bool_constant<kDrop>{})
+template <class Fn>
+static void with_drop(bool on, Fn&& fn) {
+  if (on) fn(std::true_type{}); else fn(std::false_type{});
+}
+
 }  // namespace spp

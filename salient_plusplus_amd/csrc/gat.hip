@@ -660,25 +660,6 @@ static void with_heads(int32_t heads, Fn&& fn) {
   }
 }
 static bool al16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-// Attention dropout of the spp_gat_mh_*_drop entries (spp.h f3t); the entries without it pass GatDrop{}.  p is checked
-// right after gat_check, before the sizes; training = 0 or p = 0 runs the kDrop = false kernels.
-struct GatDrop {
-  bool given = false;
-  float p = 0.f;
-  int32_t training = 0;
-  uint64_t seed = 0;
-  bool on() const { return given && training && p > 0.f; }
-  ActArgs args() const { return act_args(p, training, seed); }
-};
-static spp_status gat_drop_check(const GatDrop& dr, const char* who) {
-  SPP_REQUIRE(!dr.given || (dr.p >= 0.f && dr.p < 1.f), "%s: attention dropout needs 0 <= p < 1", who);
-  return SPP_OK;
-}
-// fn(std::bool_constant<kDrop>{})
-template <class Fn>
-static void with_drop(bool on, Fn&& fn) {
-  if (on) fn(std::true_type{}); else fn(std::false_type{});
-}
 // the per-head arrays are read and written H floats at a time (load_heads): 4, 8 and 16-byte accesses at H = 1, 2, >= 4
 static bool al_heads(const void* p, int32_t heads) {
   return reinterpret_cast<uintptr_t>(p) % (4 * std::min<int32_t>(heads, 4)) == 0;
@@ -708,7 +689,7 @@ struct GatHop {
   void* workspace;
   int64_t workspace_bytes;
   void* stream;
-  GatDrop drop;
+  AttnDrop drop;  // spp_gat_mh_*_drop (spp.h f3t): checked right after gat_check, before the sizes
 };
 static float* out(const float* p) { return const_cast<float*>(p); }
 
@@ -776,7 +757,7 @@ static spp_status gat_logits_backward(const GatHop& h) {
 
 static spp_status gat_aggregate_forward(const GatHop& h) {
   SPP_TRY(gat_check(h));
-  SPP_TRY(gat_drop_check(h.drop, h.who));
+  SPP_TRY(attn_drop_check(h.drop, h.who));
   SPP_REQUIRE(h.T >= 0, "%s: negative size", h.who);
   if (h.T == 0) return SPP_OK;
   SPP_REQUIRE(h.rowptr && h.x && h.a_src && h.a_dst && h.z && h.row_max && h.row_sum && al16(h.z) &&
@@ -785,7 +766,7 @@ static spp_status gat_aggregate_forward(const GatHop& h) {
               "%s: NULL or unaligned buffer", h.who);
   const int lpr_log2 = lanes_log2(h.K / 4);
   const unsigned grid = (unsigned)ceil_div(h.T << lpr_log2, kAggNT);
-  const ActArgs da = h.drop.on() ? h.drop.args() : ActArgs{};
+  const ActArgs da = h.drop.args();
   with_elem(h.x_elem, [&](auto tin) {
     with_heads(h.heads, [&](auto hh) {
       with_drop(h.drop.on(), [&](auto drop) {
@@ -805,7 +786,7 @@ static spp_status gat_aggregate_forward(const GatHop& h) {
 // alpha_self: the gather form's attention weights in its workspace, else NULL
 static spp_status gat_backward_launch(const GatHop& h, float* grad_x, float* alpha_e, float* alpha_self) {
   const bool vec = grad_x == nullptr;
-  const ActArgs da = h.drop.on() ? h.drop.args() : ActArgs{};
+  const ActArgs da = h.drop.args();
   const int lpt_log2 = lanes_log2(vec ? h.K / 4 : h.K);
   const unsigned grid = (unsigned)ceil_div(h.T << lpt_log2, kAggNT);
   with_elem_vec(h.x_elem, vec, [&](auto tin, auto v) {
@@ -833,7 +814,7 @@ static bool gat_backward_bufs_ok(const GatHop& h) {
 
 static spp_status gat_aggregate_backward(const GatHop& h) {
   SPP_TRY(gat_check(h));
-  SPP_TRY(gat_drop_check(h.drop, h.who));
+  SPP_TRY(attn_drop_check(h.drop, h.who));
   SPP_REQUIRE(h.T >= 0, "%s: negative size", h.who);
   if (h.T == 0) return SPP_OK;
   SPP_REQUIRE(gat_backward_bufs_ok(h), "%s: NULL or unaligned buffer", h.who);
@@ -853,7 +834,7 @@ extern "C" int64_t spp_gat_mh_aggregate_backward_gather_workspace_bytes(int64_t 
 // that the atomic form leaves to the caller.  grad_a_src [S, H] is zeroed by the caller as before.
 static spp_status gat_aggregate_backward_gather(const GatHop& h) {
   SPP_TRY(gat_check(h));
-  SPP_TRY(gat_drop_check(h.drop, h.who));
+  SPP_TRY(attn_drop_check(h.drop, h.who));
   SPP_REQUIRE(h.T >= 0 && h.S >= h.T && h.E >= 0, "%s: bad sizes", h.who);
   if (h.S == 0) return SPP_OK;
   SPP_REQUIRE(h.S < (1ll << 31) && h.E < (1ll << 31), "%s: 32-bit indices", h.who);

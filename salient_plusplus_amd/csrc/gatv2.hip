@@ -230,29 +230,11 @@ static spp_status gatv2_check_rows(const spp_gatv2_desc* d, const char* who) {
   return SPP_OK;
 }
 
-// Attention dropout of the spp_gatv2_*_drop entries (spp.h f3x); the entries without it pass V2Drop{}.  p is checked
-// right after the shape, before the T == 0 return and the rows; training = 0 or p = 0 runs the kDrop = false kernels.
-struct V2Drop {
-  bool given = false;
-  float p = 0.f;
-  int32_t training = 0;
-  uint64_t seed = 0;
-  bool on() const { return given && training && p > 0.f; }
-  ActArgs args() const { return act_args(on() ? p : 0.f, training, seed); }
-};
-static spp_status gatv2_check_drop(const V2Drop& dr, const char* who) {
-  SPP_REQUIRE(!dr.given || (dr.p >= 0.f && dr.p < 1.f), "%s: attention dropout needs 0 <= p < 1", who);
-  return SPP_OK;
-}
-// fn(std::bool_constant<kDrop>{})
-template <class Fn>
-static void with_drop(bool on, Fn&& fn) {
-  if (on) fn(std::true_type{}); else fn(std::false_type{});
-}
-
-static spp_status gatv2_forward(const spp_gatv2_desc* d, void* stream, const char* who, const V2Drop& dr) {
+// Attention dropout of the spp_gatv2_*_drop entries (spp.h f3x): AttnDrop (act_keep.hip.h), checked right after the
+// shape, before the T == 0 return and the rows.
+static spp_status gatv2_forward(const spp_gatv2_desc* d, void* stream, const char* who, const AttnDrop& dr) {
   SPP_TRY(gatv2_check_shape(d, who));
-  SPP_TRY(gatv2_check_drop(dr, who));
+  SPP_TRY(attn_drop_check(dr, who));
   if (d->num_targets == 0) return SPP_OK;
   SPP_TRY(gatv2_check_rows(d, who));
   const int64_t T = d->num_targets;
@@ -276,9 +258,9 @@ static spp_status gatv2_forward(const spp_gatv2_desc* d, void* stream, const cha
   return SPP_OK;
 }
 
-static spp_status gatv2_backward(const spp_gatv2_desc* d, void* stream, const char* who, const V2Drop& dr) {
+static spp_status gatv2_backward(const spp_gatv2_desc* d, void* stream, const char* who, const AttnDrop& dr) {
   SPP_TRY(gatv2_check_shape(d, who));
-  SPP_TRY(gatv2_check_drop(dr, who));
+  SPP_TRY(attn_drop_check(dr, who));
   const int64_t T = d->num_targets, D = d->heads * d->C;
   SPP_REQUIRE(d->grad_att_dev && aligned_to(d->grad_att_dev, 16), "%s: NULL or misaligned grad_att", who);
   if (T > 0) {
@@ -316,17 +298,17 @@ static spp_status gatv2_backward(const spp_gatv2_desc* d, void* stream, const ch
 }
 
 extern "C" spp_status spp_gatv2_forward(const spp_gatv2_desc* d, void* stream) {
-  return gatv2_forward(d, stream, "spp_gatv2_forward", V2Drop{});
+  return gatv2_forward(d, stream, "spp_gatv2_forward", AttnDrop{});
 }
 extern "C" spp_status spp_gatv2_backward(const spp_gatv2_desc* d, void* stream) {
-  return gatv2_backward(d, stream, "spp_gatv2_backward", V2Drop{});
+  return gatv2_backward(d, stream, "spp_gatv2_backward", AttnDrop{});
 }
 // with attention dropout (spp.h f3x): (p, training, seed) after `stream`
 extern "C" spp_status spp_gatv2_forward_drop(const spp_gatv2_desc* d, void* stream, float p, int32_t training,
                                              uint64_t seed) {
-  return gatv2_forward(d, stream, "spp_gatv2_forward_drop", V2Drop{true, p, training, seed});
+  return gatv2_forward(d, stream, "spp_gatv2_forward_drop", AttnDrop{true, p, training, seed});
 }
 extern "C" spp_status spp_gatv2_backward_drop(const spp_gatv2_desc* d, void* stream, float p, int32_t training,
                                               uint64_t seed) {
-  return gatv2_backward(d, stream, "spp_gatv2_backward_drop", V2Drop{true, p, training, seed});
+  return gatv2_backward(d, stream, "spp_gatv2_backward_drop", AttnDrop{true, p, training, seed});
 }

@@ -270,30 +270,11 @@ static spp_status tf_check_rows(const spp_transformer_desc* d, const char* who, 
   return SPP_OK;
 }
 
-// Attention dropout of the spp_transformer_*_drop entries (spp.h f4a); the entries without it pass TfDrop{}.  p is
-// checked right after the shape, before the T == 0 return and the rows, in eval mode too; training = 0 or p = 0 runs
-// the kDrop = false kernels.
-struct TfDrop {
-  bool given = false;
-  float p = 0.f;
-  int32_t training = 0;
-  uint64_t seed = 0;
-  bool on() const { return given && training && p > 0.f; }
-  ActArgs args() const { return act_args(on() ? p : 0.f, training, seed); }
-};
-static spp_status tf_check_drop(const TfDrop& dr, const char* who) {
-  SPP_REQUIRE(!dr.given || (dr.p >= 0.f && dr.p < 1.f), "%s: attention dropout needs 0 <= p < 1", who);
-  return SPP_OK;
-}
-// fn(std::bool_constant<kDrop>{})
-template <class Fn>
-static void with_drop(bool on, Fn&& fn) {
-  if (on) fn(std::true_type{}); else fn(std::false_type{});
-}
-
-static spp_status tf_forward(const spp_transformer_desc* d, void* stream, const char* who, const TfDrop& dr) {
+// Attention dropout of the spp_transformer_*_drop entries (spp.h f4a): AttnDrop (act_keep.hip.h), checked right after
+// the shape, before the T == 0 return and the rows, in eval mode too.
+static spp_status tf_forward(const spp_transformer_desc* d, void* stream, const char* who, const AttnDrop& dr) {
   SPP_TRY(tf_check_shape(d, who));
-  SPP_TRY(tf_check_drop(dr, who));
+  SPP_TRY(attn_drop_check(dr, who));
   if (d->num_targets == 0) return SPP_OK;
   SPP_TRY(tf_check_rows(d, who, false));
   const int64_t T = d->num_targets;
@@ -317,9 +298,9 @@ static spp_status tf_forward(const spp_transformer_desc* d, void* stream, const 
   return SPP_OK;
 }
 
-static spp_status tf_backward(const spp_transformer_desc* d, void* stream, const char* who, const TfDrop& dr) {
+static spp_status tf_backward(const spp_transformer_desc* d, void* stream, const char* who, const AttnDrop& dr) {
   SPP_TRY(tf_check_shape(d, who));
-  SPP_TRY(tf_check_drop(dr, who));
+  SPP_TRY(attn_drop_check(dr, who));
   if (d->num_targets == 0) return SPP_OK;  // nothing is touched: grad_k / grad_v stay as the caller zeroed them
   SPP_TRY(tf_check_rows(d, who, true));
   const int64_t T = d->num_targets, D = d->heads * d->C;
@@ -346,17 +327,17 @@ static spp_status tf_backward(const spp_transformer_desc* d, void* stream, const
 }
 
 extern "C" spp_status spp_transformer_forward(const spp_transformer_desc* d, void* stream) {
-  return tf_forward(d, stream, "spp_transformer_forward", TfDrop{});
+  return tf_forward(d, stream, "spp_transformer_forward", AttnDrop{});
 }
 extern "C" spp_status spp_transformer_backward(const spp_transformer_desc* d, void* stream) {
-  return tf_backward(d, stream, "spp_transformer_backward", TfDrop{});
+  return tf_backward(d, stream, "spp_transformer_backward", AttnDrop{});
 }
 // with attention dropout (spp.h f4a): (p, training, seed) after `stream`
 extern "C" spp_status spp_transformer_forward_drop(const spp_transformer_desc* d, void* stream, float p,
                                                    int32_t training, uint64_t seed) {
-  return tf_forward(d, stream, "spp_transformer_forward_drop", TfDrop{true, p, training, seed});
+  return tf_forward(d, stream, "spp_transformer_forward_drop", AttnDrop{true, p, training, seed});
 }
 extern "C" spp_status spp_transformer_backward_drop(const spp_transformer_desc* d, void* stream, float p,
                                                     int32_t training, uint64_t seed) {
-  return tf_backward(d, stream, "spp_transformer_backward_drop", TfDrop{true, p, training, seed});
+  return tf_backward(d, stream, "spp_transformer_backward_drop", AttnDrop{true, p, training, seed});
 }

@@ -46,6 +46,34 @@ def _no_autocast():
     return torch.autocast("cuda", enabled=False) if torch.is_autocast_enabled("cuda") else contextlib.nullcontext()
 
 
+def _draw_seed():
+    """a 64-bit seed for the kernels' counter-based dropout from torch's CPU generator (one draw): torch.manual_seed
+    makes a run repeatable.  Called only where a mask is needed (training, p > 0)."""
+    return int(torch.empty((), dtype=torch.int64).random_().item()) & 0xFFFFFFFFFFFFFFFF
+
+
+_attn_seed = _draw_seed            # the name the attention layers draw through: their tests replace it to plant a seed
+
+
+def _call_drop(L, name, args, drop):
+    """the entry `name`, or with attention dropout (drop = (p, seed)) its _drop spelling, which takes (p, training = 1,
+    seed) after the same arguments: the one place that picks between the two"""
+    if drop:
+        nat.check(getattr(L, name + "_drop")(*args, drop[0], 1, drop[1]))
+    else:
+        nat.check(getattr(L, name)(*args))
+
+
+def _is_prefix(x, x_target):
+    """x_target starts where x starts with x's strides (x[:T], the MFG contract); a call site that needs the widths
+    to agree or T <= S says so itself"""
+    return x_target.data_ptr() == x.data_ptr() and x_target.stride() == x.stride()
+
+
+_GATHER_MIN_WORK = 1 << 22         # E x F from which an aggregation's input gradient is gathered over the transposed hop
+_ATTN_HEADS = (1, 2, 4, 8)         # the head counts the GAT, GATv2 and Transformer kernels are built for
+
+
 class _Refs:
     """RowRefs on their way through _SageStack.apply (a non-tensor argument)"""
     __slots__ = ("r",)
@@ -171,7 +199,7 @@ class _MeanAggregate(torch.autograd.Function):
         vec = Fdim % 4 == 0 and (T <= 1 or g.stride(0) % 4 == 0) and g.data_ptr() % (4 * g.element_size()) == 0
         if ctx.concat and vec:
             grad_x = _agg_backward(nat.SPP_AGG_OPERAND, rowptr, col, T, S, g, Fdim, odt,
-                                   gather=col.numel() * Fdim >= (1 << 22))
+                                   gather=col.numel() * Fdim >= _GATHER_MIN_WORK)
         else:
             grad_x = _agg_backward(nat.SPP_AGG_MEAN, rowptr, col, T, S, g if not ctx.concat else g[:, :Fdim], Fdim, odt,
                                    gather=False)
@@ -190,7 +218,7 @@ class _ReluDropout(torch.autograd.Function):
         xc = x.contiguous()
         y = torch.empty_like(xc)
         # the seed comes from torch's CPU generator, so torch.manual_seed makes a run repeatable
-        seed = int(torch.empty((), dtype=torch.int64).random_().item()) & 0xFFFFFFFFFFFFFFFF if training else 0
+        seed = _draw_seed() if training else 0
         nat.check(L.spp_relu_dropout_forward(_p(xc), xc.numel(), float(p), int(bool(training)), seed, _p(y), _stream()))
         ctx.save_for_backward(y)
         ctx.scale = 1.0 / (1.0 - float(p)) if training else 1.0
@@ -339,7 +367,7 @@ class _BatchNormAct(torch.autograd.Function):
             if n < 2:       # torch's message, before any buffer is touched
                 raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(z.shape)}")
             # the seed comes from torch's CPU generator, so torch.manual_seed makes a run repeatable
-            seed = int(torch.empty((), dtype=torch.int64).random_().item()) & 0xFFFFFFFFFFFFFFFF if p > 0 else 0
+            seed = _draw_seed() if p > 0 else 0
             bn.num_batches_tracked.add_(1)
         else:
             seed = 0
@@ -507,7 +535,7 @@ class SAGEConv(torch.nn.Module):
             return out if self.lin_l.bias is None else out + self.lin_l.bias
         # [mean_j x_j | x_target] @ [W_l | W_r]^T: one GEMM instead of two plus an add
         T = x_target.size(0)
-        if x_target.data_ptr() == x.data_ptr() and x_target.size(1) == x.size(1) and x_target.stride() == x.stride():
+        if _is_prefix(x, x_target) and x_target.size(1) == x.size(1):
             fused = aggregate.apply(x, rowptr, col, T, True)                # x_target = x[:T] (the MFG contract)
         else:                                                               # a foreign target matrix
             mean = aggregate.apply(x, rowptr, col, T, False)                # (bf16 under bf16 autocast)
@@ -516,7 +544,33 @@ class SAGEConv(torch.nn.Module):
         return out if self.lin_l.bias is None else out + self.lin_l.bias
 
 
-class SAGE(torch.nn.Module):
+class _ConvModel(torch.nn.Module):
+    """What every model here shares: ``convs``, reset as the reference resets them"""
+
+    def reset_parameters(self):
+        for conv in self.convs:
+            conv.reset_parameters()
+            conv.apply(init_weights)
+
+
+class _LayerwiseInference:
+    """``model.inference`` of the models that have one (GraphTransformer does not: see its docstring)"""
+
+    @torch.no_grad()
+    def inference(self, x_all, rowptr, col, **kw):
+        """Exact log-probabilities of every node (or of ``nodes=``) from the whole graph, layer by layer: see
+        ``inference.layerwise_inference`` (keywords ``nodes``, ``rows_per_slab``, ``act_dtype``).  The reference's
+        ``inference(x_all, device, make_subgraph_iter)`` walks sampled full-neighbour subgraphs; here nothing is sampled:
+        the graph and x_all are resident, so the arguments are the matrix and the graph's CSR.
+
+        GAT and GATv2: the long-row softmax behind ``_attn_layers`` (``_gat_layer`` / ``_gatv2_layer``).  GIN: BatchNorm
+        on its running statistics.  GCN: keyword ``edge_weight``, what ``adj_t`` carries in training.  SAGEResInception:
+        the head as a running accumulator (``_resinc_layers``)."""
+        from .inference import layerwise_inference
+        return layerwise_inference(self, x_all, rowptr, col, **kw)
+
+
+class SAGE(_LayerwiseInference, _ConvModel):
     """``aggr="max"`` (keyword only) replaces every layer's mean by the element-wise maximum over the neighbours
     (PyG's SAGEConv(aggr="max")); parameters and state-dict keys are those of the default."""
 
@@ -531,11 +585,6 @@ class SAGE(torch.nn.Module):
             self.convs.append(SAGEConv(hidden_channels, hidden_channels, bias=False, aggr=aggr))
         self.convs.append(SAGEConv(hidden_channels, out_channels, bias=False, aggr=aggr))
         self.reset_parameters()
-
-    def reset_parameters(self):
-        for conv in self.convs:
-            conv.reset_parameters()
-            conv.apply(init_weights)
 
     def forward(self, x, adjs):
         # the reference converts the whole feature matrix to fp32 first (models.py:43); the first
@@ -573,15 +622,6 @@ class SAGE(torch.nn.Module):
             if i != self.num_layers - 1:
                 x = relu_dropout(x, 0.5, self.training)
         return torch.log_softmax(x, dim=-1)
-
-    @torch.no_grad()
-    def inference(self, x_all, rowptr, col, **kw):
-        """Exact log-probabilities of every node (or of ``nodes=``) from the whole graph, layer by layer: see
-        ``inference.layerwise_inference`` (keywords ``nodes``, ``rows_per_slab``, ``act_dtype``).  The reference's
-        ``inference(x_all, device, make_subgraph_iter)`` walks sampled full-neighbour subgraphs; here nothing is sampled:
-        the graph and x_all are resident, so the arguments are the matrix and the graph's CSR."""
-        from .inference import layerwise_inference
-        return layerwise_inference(self, x_all, rowptr, col, **kw)
 
 
 def _wgrad(g, a):
@@ -685,7 +725,7 @@ class _SageStack(torch.autograd.Function):
                 operands.append(A)
                 wcats.append(W)
                 if i != n_layers - 1:
-                    seeds.append(int(torch.empty((), dtype=torch.int64).random_().item()) if training else 0)
+                    seeds.append(_draw_seed() if training else 0)
                     acts.append(Z)                                              # the pre-activation
             out = torch.log_softmax(Z, dim=-1, dtype=torch.float32)
         # tensors through save_for_backward (saved-tensor hooks, in-place version checks, a second backward with
@@ -725,7 +765,7 @@ class _SageStack(torch.autograd.Function):
                 # the input gradient with the ReLU + dropout backward applied before the row is stored: by gather over
                 # the transposed hop, or (small hops) k_grad_init, the scatter and k_relu_dropout_bwd_pre
                 gZ = _agg_backward(nat.SPP_AGG_OPERAND_ACT, rowptr, col, T, ctx.src_rows[i], gA, K, dt,
-                                   gather=col.numel() * K >= (1 << 22), z=acts[i - 1],
+                                   gather=col.numel() * K >= _GATHER_MIN_WORK, z=acts[i - 1],
                                    act=(p_, training_, seeds[i - 1]), st=st)
         return (None, None, None, None, *grads)
 
@@ -766,6 +806,24 @@ class _GatAggregate(torch.autograd.Function):
         return grad_h, grad_as, grad_ad, None, None, None
 
 
+def _check_heads(heads, bool_ok=True):
+    """a conv's or a model's ``heads``; only TransformerConv and GraphTransformer refuse a bool"""
+    if (isinstance(heads, bool) and not bool_ok) or not isinstance(heads, int) or heads < 1:
+        raise ValueError(f"heads must be a positive int, got {heads!r}")
+
+
+def _check_attn_dropout(dropout):
+    if isinstance(dropout, bool) or not isinstance(dropout, (int, float)) or not 0.0 <= dropout < 1.0:
+        raise ValueError(f"dropout must be a number in [0, 1), got {dropout!r}")
+
+
+def _gat_kernels_read(x, x_target):
+    """the rows _GatLayer / _GatLayerMH read in place, with the targets the prefix of x"""
+    K = x.size(1)
+    return (x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and x.dtype in _ELEM and K % 4 == 0 and K <= 1024 and
+            _is_prefix(x, x_target))
+
+
 class GATConv(torch.nn.Module):
     """torch_geometric.nn.GATConv(in, out, heads=1, concat=True, negative_slope=0.2, dropout=0, add_self_loops=True,
     bias=...) on a bipartite ((x, x_target), adj_t): one shared linear map for sources and targets
@@ -785,10 +843,8 @@ class GATConv(torch.nn.Module):
 
     def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, bias=True):
         super().__init__()
-        if not isinstance(heads, int) or heads < 1:
-            raise ValueError(f"heads must be a positive int, got {heads!r}")
-        if isinstance(dropout, bool) or not isinstance(dropout, (int, float)) or not 0.0 <= dropout < 1.0:
-            raise ValueError(f"dropout must be a number in [0, 1), got {dropout!r}")
+        _check_heads(heads)
+        _check_attn_dropout(dropout)
         self.heads, self.out_channels, self.concat = heads, out_channels, bool(concat)
         self.negative_slope = negative_slope
         self.dropout = float(dropout)
@@ -814,9 +870,8 @@ class GATConv(torch.nn.Module):
             return self._forward_heads(x_pair, adj_t)
         x, x_target = x_pair
         rowptr, col, _ = adj_t.csr()
-        T, K = x_target.size(0), x.size(1)
-        if (x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and x.dtype in _ELEM and
-                K % 4 == 0 and K <= 1024 and x_target.data_ptr() == x.data_ptr() and x_target.stride() == x.stride()):
+        T = x_target.size(0)
+        if _gat_kernels_read(x, x_target):
             # aggregate the raw rows with the attention weights, project only the T targets (_GatLayer)
             out = _GatLayer.apply(x, self.lin_src.weight, self.att_src.view(-1), self.att_dst.view(-1), rowptr, col, T,
                                   self.negative_slope)
@@ -831,20 +886,16 @@ class GATConv(torch.nn.Module):
     def _forward_heads(self, x_pair, adj_t):
         x, x_target = x_pair
         rowptr, col, _ = adj_t.csr()
-        T, K, H = x_target.size(0), x.size(1), self.heads
+        T, H = x_target.size(0), self.heads
         att_src, att_dst = self.att_src.view(H, -1), self.att_dst.view(H, -1)
         p = self.dropout if self.training else 0.0
-        if (H in _GAT_MH_HEADS and x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and x.dtype in _ELEM and
-                K % 4 == 0 and K <= 1024 and x_target.data_ptr() == x.data_ptr() and x_target.stride() == x.stride()):
+        if H in _ATTN_HEADS and _gat_kernels_read(x, x_target):
             out = _GatLayerMH.apply(x, self.lin_src.weight, att_src, att_dst, rowptr, col, T, self.negative_slope,
                                     self.concat, p)
         else:
             out = _gat_mh_reference(x, x_target, self.lin_src.weight, att_src, att_dst, rowptr, col,
                                     self.negative_slope, self.concat, p)
         return out if self.bias is None else out + self.bias
-
-
-_GAT_MH_HEADS = (1, 2, 4, 8)       # the head counts the multi-head kernels are built for
 
 
 def _attn_keep_reference(E, T, H, p, seed):
@@ -864,9 +915,28 @@ def _attn_keep_reference(E, T, H, p, seed):
     return (draw < thr).astype(np.uint8).reshape(E + T, H)
 
 
-def _attn_seed():
-    """a 64-bit seed from torch's CPU generator, as _ReluDropout takes its: torch.manual_seed makes a run repeatable"""
-    return int(torch.empty((), dtype=torch.int64).random_().item()) & 0xFFFFFFFFFFFFFFFF
+def _with_self_loops(rowptr, col, T):
+    """GATConv's and GATv2Conv's edge list (src, dst) of a hop: set_diag -- the diagonal entries dropped, then one self
+    loop (i, i) per target, after the E' kept entries"""
+    dst = torch.repeat_interleave(torch.arange(T, device=col.device), rowptr[1:] - rowptr[:-1])
+    keep = col != dst
+    loops = torch.arange(T, device=col.device)
+    return torch.cat([col[keep], loops]), torch.cat([dst[keep], loops])
+
+
+def _softmax_aggregate(e, src, dst, rows, T, p):
+    """The tail of the three plain-torch references: alpha = the softmax of the logits e [E', H] over every target's
+    entries, F.dropout on it when p > 0, out[t] = sum alpha * rows[src] -- [T, H, C], all in e's dtype"""
+    dt, H = e.dtype, e.size(1)
+    emax = torch.full((T, H), float("-inf"), dtype=dt, device=e.device)
+    emax = emax.scatter_reduce(0, dst[:, None].expand(-1, H), e, "amax")
+    w = torch.exp(e - emax[dst])
+    den = torch.zeros((T, H), dtype=dt, device=e.device).index_add_(0, dst, w)
+    alpha = w / den[dst]
+    if p > 0.0:
+        alpha = F.dropout(alpha, p, training=True)
+    out = torch.zeros((T,) + tuple(rows.shape[1:]), dtype=dt, device=e.device)
+    return out.index_add_(0, dst, alpha[:, :, None] * rows[src].to(dt))
 
 
 def _gat_mh_reference(x, x_target, W, att_src, att_dst, rowptr, col, slope, concat, p=0.0):
@@ -878,32 +948,13 @@ def _gat_mh_reference(x, x_target, W, att_src, att_dst, rowptr, col, slope, conc
     H, Cc = att_src.shape
     S, T = x.size(0), x_target.size(0)
     h = F.linear(x.to(W.dtype), W).view(S, H, Cc)
-    h_t = h[:T] if x_target.data_ptr() == x.data_ptr() and x_target.stride() == x.stride() else \
-        F.linear(x_target.to(W.dtype), W).view(T, H, Cc)
+    h_t = h[:T] if _is_prefix(x, x_target) else F.linear(x_target.to(W.dtype), W).view(T, H, Cc)
     a_src = (h * att_src).sum(-1)                                           # [S, H]
     a_dst = (h_t * att_dst).sum(-1)                                         # [T, H]
-    dst = torch.repeat_interleave(torch.arange(T, device=col.device), rowptr[1:] - rowptr[:-1])
-    keep = col != dst
-    loops = torch.arange(T, device=col.device)
-    src, dst = torch.cat([col[keep], loops]), torch.cat([dst[keep], loops])
-    e = F.leaky_relu(a_src[src].float() + a_dst[dst].float(), slope)        # [E', H]
-    emax = torch.full((T, H), float("-inf"), device=e.device).scatter_reduce(0, dst[:, None].expand(-1, H), e, "amax")
-    w = torch.exp(e - emax[dst])
-    den = torch.zeros((T, H), device=e.device).index_add_(0, dst, w)
-    alpha = w / den[dst]
-    if p > 0.0:
-        alpha = F.dropout(alpha, p, training=True)
-    out = torch.zeros((T, H, Cc), device=e.device).index_add_(0, dst, alpha[:, :, None] * h[src].float())
+    src, dst = _with_self_loops(rowptr, col, T)
+    e = F.leaky_relu(a_src[src].float() + a_dst[dst].float(), slope)        # [E', H], fp32 from here on
+    out = _softmax_aggregate(e, src, dst, h, T, p)
     return out.reshape(T, H * Cc) if concat else out.mean(1)
-
-
-def _gat_aggregate_call(L, name, args, drop):
-    """the aggregate entry `name`, or with attention dropout (drop = (p, seed)) its _drop spelling, which takes
-    (p, training = 1, seed) after the same arguments: the one place that picks between the two"""
-    if drop:
-        nat.check(getattr(L, name + "_drop")(*args, drop[0], 1, drop[1]))
-    else:
-        nat.check(getattr(L, name)(*args))
 
 
 def _gat_kernels_forward(x, V_src, V_dst, rowptr, col, T, H, slope, p=0.0):
@@ -923,7 +974,7 @@ def _gat_kernels_forward(x, V_src, V_dst, rowptr, col, T, H, slope, p=0.0):
     z = torch.empty((T, H, K), **f32)
     rmax, rsum = torch.empty((T, H), **f32), torch.empty((T, H), **f32)
     drop = (p, _attn_seed()) if p > 0.0 else None
-    _gat_aggregate_call(L, "spp_gat_mh_aggregate_forward",
+    _call_drop(L, "spp_gat_mh_aggregate_forward",
                         (_p(rowptr), _p(col), T, _p(x), elem, xs, K, H, _p(a_src), _p(a_dst), float(slope), _p(z),
                          _p(rmax), _p(rsum), st), drop)
     return a_src, a_dst, z, rmax, rsum, drop
@@ -942,20 +993,20 @@ def _gat_kernels_backward(x, rowptr, col, a_src, a_dst, z, rmax, rsum, g_z, V, s
     elem = _ELEM[x.dtype]
     xs = x.stride(0) if S > 1 else K
     E = col.numel()
-    gather = want_gx and E * K >= (1 << 22)
+    gather = want_gx and E * K >= _GATHER_MIN_WORK
     f32 = dict(dtype=torch.float32, device=x.device)
     g_as, g_ad = torch.zeros((S, H), **f32), torch.empty((T, H), **f32)
     if gather:      # no E x K fp32 atomics, no zero fill, and the logits' rank-1 terms are added in the same pass
         g_x = torch.empty((S, K), **f32)
         nbytes = int(L.spp_gat_mh_aggregate_backward_gather_workspace_bytes(T, S, E, H))
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        _gat_aggregate_call(L, "spp_gat_mh_aggregate_backward_gather",
+        _call_drop(L, "spp_gat_mh_aggregate_backward_gather",
                             (_p(rowptr), _p(col), T, S, E, _p(x), elem, xs, K, H, _p(a_src), _p(a_dst), slope, _p(z),
                              _p(rmax), _p(rsum), _p(g_z), _p(V[0]), _p(V[1]), _p(g_x), _p(g_as), _p(g_ad), _p(ws),
                              nbytes, st), drop)
     else:
         g_x = torch.zeros((S, K), **f32) if want_gx else None
-        _gat_aggregate_call(L, "spp_gat_mh_aggregate_backward",
+        _call_drop(L, "spp_gat_mh_aggregate_backward",
                             (_p(rowptr), _p(col), T, _p(x), elem, xs, K, H, _p(a_src), _p(a_dst), slope, _p(z),
                              _p(rmax), _p(rsum), _p(g_z), _p(g_x), _p(g_as), _p(g_ad), st), drop)
     g_V = torch.empty((2, H, K), **f32)
@@ -1096,7 +1147,41 @@ class _GatLayer(torch.autograd.Function):
         return g_x, gW, g_att[0].to(att_src.dtype), g_att[1].to(att_dst.dtype), None, None, None, None
 
 
-class GAT(torch.nn.Module):
+class _AttentionModel(_ConvModel):
+    """The shape GAT, GATv2 and GraphTransformer share: ``num_layers`` convs of the class ``conv`` (keywords ``kw``),
+    ReLU + dropout 0.5 between layers, log_softmax.  Every hidden layer is ``heads`` heads of ``hidden_channels // heads``
+    channels, concatenated; the last layer is the mean of its heads (``last_concat``: their concatenation)."""
+
+    def __init__(self, conv, in_channels, hidden_channels, out_channels, num_layers, heads, last_concat=False, **kw):
+        super().__init__()
+        _check_heads(heads)
+        if hidden_channels % heads != 0:
+            raise ValueError(f"hidden_channels ({hidden_channels}) must be a multiple of heads ({heads})")
+        self.num_layers = num_layers
+        self.hidden_channels = hidden_channels
+        self.heads = heads
+        c = hidden_channels // heads
+        self.convs = torch.nn.ModuleList()
+        self.convs.append(conv(in_channels, c, heads=heads, concat=True, **kw))
+        for _ in range(num_layers - 2):
+            self.convs.append(conv(hidden_channels, c, heads=heads, concat=True, **kw))
+        self.convs.append(conv(hidden_channels, out_channels, heads=heads, concat=last_concat, **kw))
+        self.reset_parameters()
+
+    def forward(self, x, adjs):
+        if isinstance(x, (TableRows, RowRefs)):          # (the fused first layer exists for SAGE; see DESIGN section 5)
+            x = x.materialize()
+        # the reference converts the features to fp32 first (models.py:221); the convs here read the fp16 rows directly
+        # (exact: every fp16 value is an fp32 value)
+        for i, (adj_t, _e_id, size) in enumerate(adjs):
+            x_target = x[:size[1]]
+            x = self.convs[i]((x, x_target), adj_t)
+            if i != self.num_layers - 1:
+                x = relu_dropout(x, 0.5, self.training)
+        return torch.log_softmax(x, dim=-1)
+
+
+class GAT(_LayerwiseInference, _AttentionModel):
     """The reference's GAT (driver/models.py:195-231): ``num_layers`` GATConv(bias=False), ReLU + dropout 0.5 between
     layers, log_softmax.
 
@@ -1111,59 +1196,15 @@ class GAT(torch.nn.Module):
     as the same model with 0."""
 
     def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, heads=1, attn_dropout=0.0):
-        super().__init__()
-        if not isinstance(heads, int) or heads < 1:
-            raise ValueError(f"heads must be a positive int, got {heads!r}")
-        if hidden_channels % heads != 0:
-            raise ValueError(f"hidden_channels ({hidden_channels}) must be a multiple of heads ({heads})")
-        self.num_layers = num_layers
-        self.hidden_channels = hidden_channels
-        self.heads = heads
-        self.convs = torch.nn.ModuleList()
-        p = attn_dropout
-        if heads == 1:
-            self.convs.append(GATConv(in_channels, hidden_channels, bias=False, heads=1, dropout=p))
-            for _ in range(num_layers - 2):
-                self.convs.append(GATConv(hidden_channels, hidden_channels, bias=False, heads=1, dropout=p))
-            self.convs.append(GATConv(hidden_channels, out_channels, bias=False, heads=1, dropout=p))
-        else:
-            c = hidden_channels // heads
-            self.convs.append(GATConv(in_channels, c, heads=heads, concat=True, bias=False, dropout=p))
-            for _ in range(num_layers - 2):
-                self.convs.append(GATConv(hidden_channels, c, heads=heads, concat=True, bias=False, dropout=p))
-            self.convs.append(GATConv(hidden_channels, out_channels, heads=heads, concat=False, bias=False, dropout=p))
-        self.reset_parameters()
-
-    def reset_parameters(self):
-        for conv in self.convs:
-            conv.reset_parameters()
-            conv.apply(init_weights)
-
-    def forward(self, x, adjs):
-        if isinstance(x, (TableRows, RowRefs)):                     # (the fused first layer exists for SAGE; see DESIGN section 5)
-            x = x.materialize()
-        # the reference converts the features to fp32 first (models.py:221); GATConv here reads the fp16
-        # rows directly (exact: every fp16 value is an fp32 value)
-        for i, (adj_t, _e_id, size) in enumerate(adjs):
-            x_target = x[:size[1]]
-            x = self.convs[i]((x, x_target), adj_t)
-            if i != self.num_layers - 1:
-                x = relu_dropout(x, 0.5, self.training)
-        return torch.log_softmax(x, dim=-1)
-
-    @torch.no_grad()
-    def inference(self, x_all, rowptr, col, **kw):
-        """as ``SAGE.inference``: ``inference.layerwise_inference`` (the long-row softmax behind ``_attn_layers`` / ``_gat_layer``)"""
-        from .inference import layerwise_inference
-        return layerwise_inference(self, x_all, rowptr, col, **kw)
+        # heads=1, the reference model: the last layer keeps GATConv's default concat=True too (one head: the same
+        # function, and with attn_dropout the GEMM spelling _GatLayerMH has always run for it)
+        super().__init__(GATConv, in_channels, hidden_channels, out_channels, num_layers, heads, last_concat=heads == 1,
+                         bias=False, dropout=attn_dropout)
 
 
 # --------------------------------------------------------------------------------------------
 # GATv2  (PyG's GATv2Conv, "dynamic attention": csrc/gatv2.hip, spp.h f3v)
 # --------------------------------------------------------------------------------------------
-_GATV2_HEADS = (1, 2, 4, 8)        # the head counts spp_gatv2_forward / _backward are built for
-
-
 def _gatv2_reference(x_l, x_r, att, rowptr, col, slope, p=0.0):
     """GATv2Conv's message passing in PyG's order, in plain torch ops, on the projected rows: x_l [S, H, C] = lin_l(x),
     x_r [T, H, C] = lin_r(x_target), att [H, C] -> out [T, H, C] (fp32; float64 for float64 rows).  The path for
@@ -1172,22 +1213,12 @@ def _gatv2_reference(x_l, x_r, att, rowptr, col, slope, p=0.0):
     set_diag: diagonal entries dropped, one self loop (i, i) per target, whose message is source row i.
     p > 0 (training): F.dropout on alpha -- torch's own mask, from the generator of alpha's device, NOT the kernels'
     counter-based one (_attn_keep_reference), which the rows the kernels read get (spp.h f3x)."""
-    T, H = x_r.size(0), att.size(0)
+    T = x_r.size(0)
     dt = torch.float64 if x_l.dtype == torch.float64 else torch.float32
     x_l, x_r, att = x_l.to(dt), x_r.to(dt), att.to(dt)
-    dst = torch.repeat_interleave(torch.arange(T, device=col.device), rowptr[1:] - rowptr[:-1])
-    keep = col != dst
-    loops = torch.arange(T, device=col.device)
-    src, dst = torch.cat([col[keep], loops]), torch.cat([dst[keep], loops])
+    src, dst = _with_self_loops(rowptr, col, T)
     e = (F.leaky_relu(x_l[src] + x_r[dst], slope) * att).sum(-1)            # [E', H]
-    emax = torch.full((T, H), float("-inf"), dtype=dt, device=e.device)
-    emax = emax.scatter_reduce(0, dst[:, None].expand(-1, H), e, "amax")
-    w = torch.exp(e - emax[dst])
-    den = torch.zeros((T, H), dtype=dt, device=e.device).index_add_(0, dst, w)
-    alpha = w / den[dst]
-    if p > 0.0:
-        alpha = F.dropout(alpha, p, training=True)
-    return torch.zeros((T,) + tuple(x_l.shape[1:]), dtype=dt, device=e.device).index_add_(0, dst, alpha[:, :, None] * x_l[src])
+    return _softmax_aggregate(e, src, dst, x_l, T, p)
 
 
 def _gatv2_desc(x_l, x_r, att, rowptr, col, slope, out, rmax, rsum, **grads):
@@ -1201,13 +1232,39 @@ def _gatv2_desc(x_l, x_r, att, rowptr, col, slope, out, rmax, rsum, **grads):
                          row_max_dev=_p(rmax), row_sum_dev=_p(rsum), **{k: _p(v) for k, v in grads.items()})
 
 
-def _gatv2_kernels_read(x_l, x_r, H, Cc):
-    """the rows and widths spp_gatv2_forward accepts (spp.h f3v)"""
+def _attn_kernels_read(H, Cc, *rows):
+    """the rows and widths the GATv2 / Transformer kernel pair accepts (spp.h f3v, f3y): CUDA matrices of one fp32 / fp16
+    / bf16 dtype with unit column stride and rows aligned to 4 elements, H in {1, 2, 4, 8}, C % 4 == 0 with C / 4 a power
+    of two, H * C <= 1024"""
     g = Cc // 4
-    return (x_l.is_cuda and H in _GATV2_HEADS and Cc > 0 and Cc % 4 == 0 and g & (g - 1) == 0 and H * Cc <= 1024 and
-            x_l.dtype in _ELEM and x_r.dtype == x_l.dtype and x_l.dim() == 2 and x_r.dim() == 2 and
-            all(t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % (4 * t.element_size()) == 0
-                for t in (x_l, x_r)))
+    x = rows[0]
+    return (x.is_cuda and H in _ATTN_HEADS and Cc > 0 and Cc % 4 == 0 and g & (g - 1) == 0 and H * Cc <= 1024 and
+            x.dtype in _ELEM and
+            all(t.dtype == x.dtype and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 4 == 0 and
+                t.data_ptr() % (4 * t.element_size()) == 0 for t in rows))
+
+
+def _gatv2_kernels_read(x_l, x_r, H, Cc):
+    return _attn_kernels_read(H, Cc, x_l, x_r)
+
+
+def _attn_forward(ctx, name, desc, T, H, Cc, p, device):
+    """What the forwards of _GATv2Layer and _TransformerLayer share: the new out [T, H, C] and softmax statistics rmax,
+    rsum [T, H] (fp32), ctx.drop = (p, seed) with the seed drawn here (_attn_seed), or None for p = 0, and the one call
+    of the entry `name` (_call_drop) on desc(out, rmax, rsum)."""
+    L = nat.load()
+    nat.require_device()
+    f32 = dict(dtype=torch.float32, device=device)
+    out = torch.empty((T, H, Cc), **f32)
+    rmax, rsum = torch.empty((T, H), **f32), torch.empty((T, H), **f32)
+    ctx.drop = (float(p), _attn_seed()) if p > 0.0 else None
+    _call_drop(L, name, (C.byref(desc(out, rmax, rsum)), _stream()), ctx.drop)
+    return out, rmax, rsum
+
+
+def _grad_back(g, row, wanted=True):
+    """a kernel's fp32 gradient in its row matrix's dtype; None if it was not computed or nobody wants it"""
+    return g.to(row.dtype) if wanted and g is not None else None
 
 
 class _GATv2Layer(torch.autograd.Function):
@@ -1216,30 +1273,17 @@ class _GATv2Layer(torch.autograd.Function):
     projections outside the node give bf16 rows, which the kernels read as such); x_r may be a view of x_l
     (share_weights).  The node runs with autocast off, returns fp32 and casts grad_xl / grad_xr back to the rows' dtype;
     att and its gradient are fp32.  p > 0: attention dropout inside the kernels (spp.h f3x) -- the forward draws a seed
-    from torch's CPU generator (_attn_seed), and both directions call the _drop entries with (p, training = 1, seed),
+    from torch's CPU generator (_attn_forward), and both directions call the _drop entries with (p, training = 1, seed),
     so the backward applies the forward's mask; p = 0 calls the entries without dropout."""
-
-    @staticmethod
-    def _call(L, name, d, drop):
-        if drop:
-            nat.check(getattr(L, name + "_drop")(C.byref(d), _stream(), drop[0], 1, drop[1]))
-        else:
-            nat.check(getattr(L, name)(C.byref(d), _stream()))
 
     @staticmethod
     def forward(ctx, x_l, x_r, att, rowptr, col, slope, p=0.0):
         with _no_autocast():
-            L = nat.load()
-            nat.require_device()
             H, Cc = att.shape
-            T = x_r.size(0)
             att32 = att.detach().to(torch.float32).contiguous()
-            f32 = dict(dtype=torch.float32, device=x_l.device)
-            out = torch.empty((T, H, Cc), **f32)
-            rmax, rsum = torch.empty((T, H), **f32), torch.empty((T, H), **f32)
-            d = _gatv2_desc(x_l, x_r, att32, rowptr, col, slope, out, rmax, rsum)
-            ctx.drop = (float(p), _attn_seed()) if p > 0.0 else None
-            _GATv2Layer._call(L, "spp_gatv2_forward", d, ctx.drop)
+            out, rmax, rsum = _attn_forward(
+                ctx, "spp_gatv2_forward", lambda *o: _gatv2_desc(x_l, x_r, att32, rowptr, col, slope, *o),
+                x_r.size(0), H, Cc, p, x_l.device)
             ctx.save_for_backward(x_l, x_r, att32, rowptr, col, out, rmax, rsum)
             ctx.slope, ctx.att_dtype = float(slope), att.dtype
             return out
@@ -1256,10 +1300,9 @@ class _GATv2Layer(torch.autograd.Function):
             g_xr, g_att = torch.empty((T, D), **f32), torch.empty((H, Cc), **f32)
             d = _gatv2_desc(x_l, x_r, att32, rowptr, col, ctx.slope, out, rmax, rsum, grad_out_dev=g, grad_x_l_dev=g_xl,
                             grad_x_r_dev=g_xr, grad_att_dev=g_att)
-            _GATv2Layer._call(nat.load(), "spp_gatv2_backward", d, ctx.drop)
-            return (g_xl.to(x_l.dtype) if g_xl is not None else None,
-                    g_xr.to(x_r.dtype) if ctx.needs_input_grad[1] else None, g_att.to(ctx.att_dtype), None, None, None,
-                    None)
+            _call_drop(nat.load(), "spp_gatv2_backward", (C.byref(d), _stream()), ctx.drop)
+            return (_grad_back(g_xl, x_l), _grad_back(g_xr, x_r, ctx.needs_input_grad[1]), g_att.to(ctx.att_dtype),
+                    None, None, None, None)
 
 
 class GATv2Conv(torch.nn.Module):
@@ -1288,10 +1331,8 @@ class GATv2Conv(torch.nn.Module):
     def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, bias=True,
                  share_weights=False):
         super().__init__()
-        if not isinstance(heads, int) or heads < 1:
-            raise ValueError(f"heads must be a positive int, got {heads!r}")
-        if isinstance(dropout, bool) or not isinstance(dropout, (int, float)) or not 0.0 <= dropout < 1.0:
-            raise ValueError(f"dropout must be a number in [0, 1), got {dropout!r}")
+        _check_heads(heads)
+        _check_attn_dropout(dropout)
         self.heads, self.out_channels, self.concat = heads, out_channels, bool(concat)
         self.negative_slope = negative_slope
         self.dropout = float(dropout)
@@ -1316,7 +1357,7 @@ class GATv2Conv(torch.nn.Module):
         x, x_target = x_pair
         rowptr, col, _ = adj_t.csr()
         S, T, H, Cc = x.size(0), x_target.size(0), self.heads, self.out_channels
-        prefix = x_target.data_ptr() == x.data_ptr() and x_target.stride() == x.stride() and T <= S
+        prefix = _is_prefix(x, x_target) and T <= S
         if not torch.is_autocast_enabled(x.device.type):        # (autocast casts the GEMM's operands itself)
             x, x_target = x.to(self.lin_l.weight.dtype), x_target.to(self.lin_r.weight.dtype)
         x_l = self.lin_l(x)
@@ -1331,7 +1372,7 @@ class GATv2Conv(torch.nn.Module):
         return out if self.bias is None else out + self.bias
 
 
-class GATv2(torch.nn.Module):
+class GATv2(_LayerwiseInference, _AttentionModel):
     """GAT's shape with GATv2Conv layers: ``num_layers`` GATv2Conv(bias=False), ReLU + dropout 0.5 between layers,
     log_softmax.  Every hidden layer is ``heads`` heads of ``hidden_channels // heads`` channels, concatenated (the hidden
     width stays ``hidden_channels``, which must be a multiple of ``heads``); the last layer is the mean of its heads.
@@ -1339,51 +1380,13 @@ class GATv2(torch.nn.Module):
 
     def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, heads=1, share_weights=False,
                  attn_dropout=0.0):
-        super().__init__()
-        if not isinstance(heads, int) or heads < 1:
-            raise ValueError(f"heads must be a positive int, got {heads!r}")
-        if hidden_channels % heads != 0:
-            raise ValueError(f"hidden_channels ({hidden_channels}) must be a multiple of heads ({heads})")
-        self.num_layers = num_layers
-        self.hidden_channels = hidden_channels
-        self.heads = heads
-        kw = dict(heads=heads, bias=False, share_weights=share_weights, dropout=attn_dropout)
-        c = hidden_channels // heads
-        self.convs = torch.nn.ModuleList()
-        self.convs.append(GATv2Conv(in_channels, c, concat=True, **kw))
-        for _ in range(num_layers - 2):
-            self.convs.append(GATv2Conv(hidden_channels, c, concat=True, **kw))
-        self.convs.append(GATv2Conv(hidden_channels, out_channels, concat=False, **kw))
-        self.reset_parameters()
-
-    def reset_parameters(self):
-        for conv in self.convs:
-            conv.reset_parameters()
-            conv.apply(init_weights)
-
-    def forward(self, x, adjs):
-        if isinstance(x, (TableRows, RowRefs)):
-            x = x.materialize()
-        for i, (adj_t, _e_id, size) in enumerate(adjs):
-            x_target = x[:size[1]]
-            x = self.convs[i]((x, x_target), adj_t)
-            if i != self.num_layers - 1:
-                x = relu_dropout(x, 0.5, self.training)
-        return torch.log_softmax(x, dim=-1)
-
-    @torch.no_grad()
-    def inference(self, x_all, rowptr, col, **kw):
-        """as ``SAGE.inference``: ``inference.layerwise_inference`` (``_attn_layers`` / ``_gatv2_layer``)"""
-        from .inference import layerwise_inference
-        return layerwise_inference(self, x_all, rowptr, col, **kw)
+        super().__init__(GATv2Conv, in_channels, hidden_channels, out_channels, num_layers, heads, bias=False,
+                         share_weights=share_weights, dropout=attn_dropout)
 
 
 # --------------------------------------------------------------------------------------------
 # GraphTransformer  (PyG's TransformerConv, scaled dot-product attention: csrc/transformer_conv.hip, spp.h f3y)
 # --------------------------------------------------------------------------------------------
-_TRANSFORMER_HEADS = (1, 2, 4, 8)   # the head counts spp_transformer_forward / _backward are built for
-
-
 def _transformer_reference(q, k, v, rowptr, col, scale, p=0.0):
     """TransformerConv's message passing in plain torch ops, on the projected rows: q [T, H, C] = lin_query(x_target),
     k [S, H, C] = lin_key(x), v [S, H, C] = lin_value(x) -> out [T, H, C] (fp32; float64 for float64 rows):
@@ -1393,19 +1396,12 @@ def _transformer_reference(q, k, v, rowptr, col, scale, p=0.0):
     {1, 2, 4, 8}, C with C / 4 not a power of two, H * C > 1024.  p > 0 (training): F.dropout on alpha -- torch's own
     mask, from the generator of alpha's device, NOT the kernels' counter-based one (_attn_keep_reference), which the
     rows the kernels read get (spp.h f4a)."""
-    T, H = q.size(0), q.size(1)
+    T = q.size(0)
     dt = torch.float64 if q.dtype == torch.float64 else torch.float32
     q, k, v = q.to(dt), k.to(dt), v.to(dt)
     dst = torch.repeat_interleave(torch.arange(T, device=col.device), rowptr[1:] - rowptr[:-1])
     e = (q[dst] * k[col]).sum(-1) * scale                                   # [E, H]
-    emax = torch.full((T, H), float("-inf"), dtype=dt, device=e.device)
-    emax = emax.scatter_reduce(0, dst[:, None].expand(-1, H), e, "amax")
-    w = torch.exp(e - emax[dst])
-    den = torch.zeros((T, H), dtype=dt, device=e.device).index_add_(0, dst, w)
-    alpha = w / den[dst]
-    if p > 0.0:
-        alpha = F.dropout(alpha, p, training=True)
-    return torch.zeros((T,) + tuple(v.shape[1:]), dtype=dt, device=e.device).index_add_(0, dst, alpha[:, :, None] * v[col])
+    return _softmax_aggregate(e, col, dst, v, T, p)
 
 
 def _transformer_desc(q, k, v, H, rowptr, col, scale, out, rmax, rsum, **grads):
@@ -1420,12 +1416,7 @@ def _transformer_desc(q, k, v, H, rowptr, col, scale, out, rmax, rsum, **grads):
 
 
 def _transformer_kernels_read(q, k, v, H, Cc):
-    """the rows and widths spp_transformer_forward accepts (spp.h f3y)"""
-    g = Cc // 4
-    return (q.is_cuda and H in _TRANSFORMER_HEADS and Cc > 0 and Cc % 4 == 0 and g & (g - 1) == 0 and H * Cc <= 1024 and
-            q.dtype in _ELEM and k.dtype == q.dtype and v.dtype == q.dtype and
-            all(t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 4 == 0 and
-                t.data_ptr() % (4 * t.element_size()) == 0 for t in (q, k, v)))
+    return _attn_kernels_read(H, Cc, q, k, v)
 
 
 class _TransformerLayer(torch.autograd.Function):
@@ -1434,29 +1425,16 @@ class _TransformerLayer(torch.autograd.Function):
     autocast the projections outside the node give bf16 rows, which the kernels read as such); k and v may be views
     of one [S, 2 D] matrix.  The node runs with autocast off, returns fp32 and casts grad_q / grad_k / grad_v back to
     the rows' dtype; a gradient nobody needs is not computed (NULL in the descriptor).  p > 0: attention dropout
-    inside the kernels (spp.h f4a) -- the forward draws a seed from torch's CPU generator (_attn_seed), and both
-    directions call the _drop entries with (p, training = 1, seed), so the backward applies the forward's mask; p = 0
-    calls the entries without dropout."""
-
-    @staticmethod
-    def _call(L, name, d, drop):
-        if drop:
-            nat.check(getattr(L, name + "_drop")(C.byref(d), _stream(), drop[0], 1, drop[1]))
-        else:
-            nat.check(getattr(L, name)(C.byref(d), _stream()))
+    inside the kernels (spp.h f4a), as _GATv2Layer's: seed and call in _attn_forward, the same (p, seed) in the
+    backward."""
 
     @staticmethod
     def forward(ctx, q, k, v, rowptr, col, heads, scale, p=0.0):
         with _no_autocast():
-            L = nat.load()
-            nat.require_device()
             T, D = q.shape
-            f32 = dict(dtype=torch.float32, device=q.device)
-            out = torch.empty((T, heads, D // heads), **f32)
-            rmax, rsum = torch.empty((T, heads), **f32), torch.empty((T, heads), **f32)
-            ctx.drop = (float(p), _attn_seed()) if p > 0.0 else None
-            _TransformerLayer._call(L, "spp_transformer_forward",
-                                    _transformer_desc(q, k, v, heads, rowptr, col, scale, out, rmax, rsum), ctx.drop)
+            out, rmax, rsum = _attn_forward(
+                ctx, "spp_transformer_forward", lambda *o: _transformer_desc(q, k, v, heads, rowptr, col, scale, *o),
+                T, heads, D // heads, p, q.device)
             ctx.save_for_backward(q, k, v, rowptr, col, out, rmax, rsum)
             ctx.heads, ctx.scale = int(heads), float(scale)
             return out
@@ -1473,9 +1451,9 @@ class _TransformerLayer(torch.autograd.Function):
             g_v = torch.zeros((S, D), **f32) if ctx.needs_input_grad[2] else None
             d = _transformer_desc(q, k, v, ctx.heads, rowptr, col, ctx.scale, out, rmax, rsum, grad_out_dev=g,
                                   grad_q_dev=g_q, grad_k_dev=g_k, grad_v_dev=g_v)
-            _TransformerLayer._call(nat.load(), "spp_transformer_backward", d, ctx.drop)
-            return (g_q.to(q.dtype) if ctx.needs_input_grad[0] else None, g_k.to(k.dtype) if g_k is not None else None,
-                    g_v.to(v.dtype) if g_v is not None else None, None, None, None, None, None)
+            _call_drop(nat.load(), "spp_transformer_backward", (C.byref(d), _stream()), ctx.drop)
+            return (_grad_back(g_q, q, ctx.needs_input_grad[0]), _grad_back(g_k, k), _grad_back(g_v, v), None, None,
+                    None, None, None)
 
 
 class TransformerConv(torch.nn.Module):
@@ -1510,10 +1488,8 @@ class TransformerConv(torch.nn.Module):
         super().__init__()
         if edge_dim is not None:
             raise NotImplementedError("TransformerConv: edge features (edge_dim) are not built; use edge_dim=None")
-        if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
-            raise ValueError(f"heads must be a positive int, got {heads!r}")
-        if isinstance(dropout, bool) or not isinstance(dropout, (int, float)) or not 0.0 <= dropout < 1.0:
-            raise ValueError(f"dropout must be a number in [0, 1), got {dropout!r}")
+        _check_heads(heads, bool_ok=False)
+        _check_attn_dropout(dropout)
         self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
         self.concat, self.root_weight = bool(concat), bool(root_weight)
         self.beta = bool(beta) and self.root_weight
@@ -1555,7 +1531,7 @@ class TransformerConv(torch.nn.Module):
         return out
 
 
-class GraphTransformer(torch.nn.Module):
+class GraphTransformer(_AttentionModel):
     """GAT's shape with TransformerConv layers (the UniMP model without label propagation): ``num_layers``
     TransformerConv, ReLU + dropout 0.5 between layers, log_softmax.  Every hidden layer is ``heads`` heads of
     ``hidden_channels // heads`` channels, concatenated (the hidden width stays ``hidden_channels``, which must be a
@@ -1570,43 +1546,15 @@ class GraphTransformer(torch.nn.Module):
     models."""
 
     def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, heads=1, beta=False, attn_dropout=0.0):
-        super().__init__()
-        if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
-            raise ValueError(f"heads must be a positive int, got {heads!r}")
-        if hidden_channels % heads != 0:
-            raise ValueError(f"hidden_channels ({hidden_channels}) must be a multiple of heads ({heads})")
-        self.num_layers = num_layers
-        self.hidden_channels = hidden_channels
-        self.heads = heads
-        kw = dict(heads=heads, beta=beta, dropout=attn_dropout)
-        c = hidden_channels // heads
-        self.convs = torch.nn.ModuleList()
-        self.convs.append(TransformerConv(in_channels, c, concat=True, **kw))
-        for _ in range(num_layers - 2):
-            self.convs.append(TransformerConv(hidden_channels, c, concat=True, **kw))
-        self.convs.append(TransformerConv(hidden_channels, out_channels, concat=False, **kw))
-        self.reset_parameters()
-
-    def reset_parameters(self):
-        for conv in self.convs:
-            conv.reset_parameters()
-            conv.apply(init_weights)
-
-    def forward(self, x, adjs):
-        if isinstance(x, (TableRows, RowRefs)):
-            x = x.materialize()
-        for i, (adj_t, _e_id, size) in enumerate(adjs):
-            x_target = x[:size[1]]
-            x = self.convs[i]((x, x_target), adj_t)
-            if i != self.num_layers - 1:
-                x = relu_dropout(x, 0.5, self.training)
-        return torch.log_softmax(x, dim=-1)
+        _check_heads(heads, bool_ok=False)
+        super().__init__(TransformerConv, in_channels, hidden_channels, out_channels, num_layers, heads, beta=beta,
+                         dropout=attn_dropout)
 
 
 # --------------------------------------------------------------------------------------------
 # GIN  (driver/models.py:234-283: GINConv(Sequential(Linear, BatchNorm1d, ReLU, Linear, ReLU)), eps = 0)
 # --------------------------------------------------------------------------------------------
-_SUM_GATHER_MIN_WORK = 1 << 22      # E x F from which the input gradient is gathered, as in the mean's backward
+_SUM_GATHER_MIN_WORK = _GATHER_MIN_WORK     # (the name the sum's tests know it by)
 
 
 class _SumAggregate(torch.autograd.Function):
@@ -1695,8 +1643,8 @@ class GINConv(torch.nn.Module):
             x = (x.materialize() if isinstance(x, (TableRows, RowRefs)) else x).to(torch.float32).contiguous()
             if x_target is not None:
                 x_target = x[:T]
-        prefix = x_target is None or (isinstance(x, torch.Tensor) and x_target.data_ptr() == x.data_ptr() and
-                                      x_target.stride() == x.stride() and x_target.size(1) == x.size(1))
+        prefix = x_target is None or (isinstance(x, torch.Tensor) and _is_prefix(x, x_target) and
+                                      x_target.size(1) == x.size(1))
         if prefix:                                                          # x_target = x[:T] (the MFG contract)
             h = _SumAggregate.apply(x, rowptr, col, T, self._scale())
         else:                                                               # a foreign target matrix
@@ -1713,7 +1661,7 @@ def _gin_mlp(d_in, d_hidden):
                                torch.nn.Linear(d_hidden, d_hidden), torch.nn.ReLU())
 
 
-class GIN(torch.nn.Module):
+class GIN(_LayerwiseInference, _ConvModel):
     """``num_layers`` GINConv (in -> hidden, then hidden -> hidden, the last one included), then lin1, ReLU, dropout,
     lin2, log_softmax.  The first layer reads a TableRows / RowRefs input in place.  ``fused_norm=True`` runs every
     conv's BatchNorm1d + ReLU as ``batch_norm_act`` (same modules, same state dict)."""
@@ -1733,9 +1681,7 @@ class GIN(torch.nn.Module):
         self.reset_parameters()
 
     def reset_parameters(self):
-        for conv in self.convs:
-            conv.reset_parameters()
-            conv.apply(init_weights)
+        super().reset_parameters()
         self.lin1.reset_parameters()
         self.lin2.reset_parameters()
 
@@ -1749,13 +1695,6 @@ class GIN(torch.nn.Module):
         x = F.relu(self.lin1(x))
         x = F.dropout(x, p=self.dropout, training=self.training)
         return torch.log_softmax(self.lin2(x), dim=-1)
-
-    @torch.no_grad()
-    def inference(self, x_all, rowptr, col, **kw):
-        """Exact log-probabilities of every node (or of ``nodes=``) from the whole graph, layer by layer, BatchNorm on
-        its running statistics: see ``inference.layerwise_inference``"""
-        from .inference import layerwise_inference
-        return layerwise_inference(self, x_all, rowptr, col, **kw)
 
 
 # --------------------------------------------------------------------------------------------
@@ -1988,8 +1927,8 @@ class GCNConv(torch.nn.Module):
             T = int(size[1]) if size is not None else int(adj_t.sparse_sizes()[0])
         if isinstance(x, torch.Tensor) and x.dtype not in _ELEM:
             x = x.to(torch.float32)
-        prefix = x_target is None or (isinstance(x, torch.Tensor) and x_target.data_ptr() == x.data_ptr() and
-                                      x_target.stride() == x.stride() and x_target.size(1) == x.size(1))
+        prefix = x_target is None or (isinstance(x, torch.Tensor) and _is_prefix(x, x_target) and
+                                      x_target.size(1) == x.size(1))
         w = value.to(torch.float32) if value is not None else None
         self_w = None
         if self.normalize:
@@ -2007,7 +1946,7 @@ class GCNConv(torch.nn.Module):
         return out if self.bias is None else out + self.bias
 
 
-class GCN(torch.nn.Module):
+class GCN(_LayerwiseInference, _ConvModel):
     """The reference's GCN (driver/models.py:343-381): ``num_layers`` GCNConv(bias=False, improved=False), each but the
     last followed by BatchNorm1d, ReLU and dropout 0.5, then log_softmax; ``bns`` holds ``num_layers`` BatchNorm1d(hidden)
     of which the last is unused, as in the reference.  ``normalize`` (keyword only; the reference: False) is handed to
@@ -2032,11 +1971,6 @@ class GCN(torch.nn.Module):
         self.bns.append(torch.nn.BatchNorm1d(hidden_channels))
         self.reset_parameters()
 
-    def reset_parameters(self):
-        for conv in self.convs:
-            conv.reset_parameters()
-            conv.apply(init_weights)
-
     def forward(self, x, adjs):
         # the reference converts the features to fp32 first (models.py:372); the sum reads fp16 rows directly (exact)
         for i, (adj_t, _e_id, size) in enumerate(adjs):
@@ -2047,12 +1981,6 @@ class GCN(torch.nn.Module):
                 else:
                     x = F.dropout(F.relu(self.bns[i](x)), p=0.5, training=self.training)
         return torch.log_softmax(x, dim=-1)
-
-    @torch.no_grad()
-    def inference(self, x_all, rowptr, col, **kw):
-        """as ``SAGE.inference``: ``inference.layerwise_inference`` (keyword ``edge_weight``: what ``adj_t`` carries in training)"""
-        from .inference import layerwise_inference
-        return layerwise_inference(self, x_all, rowptr, col, **kw)
 
 
 # --------------------------------------------------------------------------------------------
@@ -2090,7 +2018,7 @@ def _dropout(x, p, training):
     return F.dropout(x, p=p, training=True) if (training and p > 0) else x
 
 
-class SAGEResInception(torch.nn.Module):
+class SAGEResInception(_LayerwiseInference, _ConvModel):
     """SAGEConv layers (in -> hidden, then hidden -> hidden: the last one outputs hidden too), each followed by
     BatchNorm1d, leaky_relu and dropout, with a residual (Linear for the first layer, identity after); the input
     and every layer's rows of the final targets are concatenated into a two-Linear MLP head.  ``fused_norm=True`` runs
@@ -2116,9 +2044,7 @@ class SAGEResInception(torch.nn.Module):
         self.reset_parameters()
 
     def reset_parameters(self):
-        for conv in self.convs:
-            conv.reset_parameters()
-            conv.apply(init_weights)
+        super().reset_parameters()
         for m in self.res_linears:
             if isinstance(m, torch.nn.Linear):
                 m.reset_parameters()
@@ -2145,12 +2071,6 @@ class SAGEResInception(torch.nn.Module):
                 x = h + self.res_linears[i](x_target)
             collect.append(x[:end_size])
         return torch.log_softmax(self.mlp(torch.cat(collect, -1)), dim=-1)
-
-    @torch.no_grad()
-    def inference(self, x_all, rowptr, col, **kw):
-        """as ``SAGE.inference``: ``inference.layerwise_inference`` (the head as a running accumulator: ``_resinc_layers``)"""
-        from .inference import layerwise_inference
-        return layerwise_inference(self, x_all, rowptr, col, **kw)
 
 
 _UNSUPPORTED_MODELS = {"sageclassic": "not used in the paper", "jknet": "not used in the paper",
