@@ -19,6 +19,7 @@ There is no CPU fallback: without the HIP extension and a GPU every entry point 
 import collections
 import ctypes as C
 import datetime
+import itertools
 import math
 import os
 import threading
@@ -287,7 +288,40 @@ def fp8_scales_tag(scale_log2: torch.Tensor) -> int:
     return _fnv1a64(scale_log2.cpu().contiguous().view(torch.uint8).numpy().tobytes()) or 1
 
 
-class TableRows:
+class _RowsLike:
+    """What iterators and records ask of a feature matrix, for a stand-in that holds none: sizes / device / dtype read like
+    the tensor's and ``to`` another device materialises.  A subclass names ``_rows`` (the tensor with one entry per row),
+    ``_width`` and ``dtype``, and brings its own ``record_stream`` and ``materialize``."""
+    __slots__ = ()
+
+    @property
+    def is_cuda(self):
+        return self._rows.is_cuda
+
+    @property
+    def device(self):
+        return self._rows.device
+
+    @property
+    def shape(self):
+        return torch.Size((self._rows.numel(), self._width))
+
+    def size(self, dim=None):
+        return self.shape if dim is None else self.shape[dim]
+
+    def dim(self):
+        return 2
+
+    def numel(self):
+        return self._rows.numel() * self._width
+
+    def to(self, device=None, non_blocking=False, **_kw):
+        if device is None or torch.device(device) == self._rows.device:
+            return self
+        return self.materialize().to(device=device, non_blocking=non_blocking)
+
+
+class TableRows(_RowsLike):
     """``x = table[n_id]`` without the copy: what a Session with ``table_features`` puts in the place of the batch's
     feature matrix (fast_sampler.cpp:1004-1016 ``serial_index(x_cpu, n_id)``).  ``models.SAGE`` aggregates its first
     layer straight from ``table`` (spp_agg_forward, source SPP_AGG_TABLE: same rows, same summation order, bit-identical
@@ -300,40 +334,21 @@ class TableRows:
     def __init__(self, table, n_id: torch.Tensor):
         self.table, self.n_id = table, n_id
 
-    # -- what iterators and records ask of a feature matrix --
     @property
-    def is_cuda(self):
-        return self.n_id.is_cuda
+    def _rows(self):
+        return self.n_id
 
     @property
-    def device(self):
-        return self.n_id.device
+    def _width(self):
+        return self.table.size(1)
 
     @property
     def dtype(self):
         return self.table.dtype
 
-    @property
-    def shape(self):
-        return torch.Size((self.n_id.numel(), self.table.size(1)))
-
-    def size(self, dim=None):
-        return self.shape if dim is None else self.shape[dim]
-
-    def dim(self):
-        return 2
-
-    def numel(self):
-        return self.n_id.numel() * self.table.size(1)
-
     def record_stream(self, stream):
         if self.n_id.is_cuda:
             self.n_id.record_stream(stream)              # (the table lives as long as the graph does)
-
-    def to(self, device=None, non_blocking=False, **_kw):
-        if device is None or torch.device(device) == self.n_id.device:
-            return self
-        return self.materialize().to(device=device, non_blocking=non_blocking)
 
     def materialize(self) -> torch.Tensor:
         """The feature matrix itself: the HIP row gather on the caller's current stream (a5, serial_index)."""
@@ -348,7 +363,7 @@ class TableRows:
         return out
 
 
-class RowRefs:
+class RowRefs(_RowsLike):
     """``x = cat(features_gather + [cached])[perm]`` (transferers.py:472-486) without the copy: what a PARTITIONED Session
     with ``row_refs`` puts in the place of the batch's feature matrix.  ``addr[j]`` is the device address of the feature
     row of MFG node j -- in this rank's resident partition, in the VIP cache, in a peer's partition (P2P transport) or in
@@ -362,39 +377,21 @@ class RowRefs:
         self.addr, self.n_id, self.width, self._dtype, self.x_remote, self.keep = addr, n_id, int(width), dtype, x_remote, keep
 
     @property
-    def is_cuda(self):
-        return self.addr.is_cuda
+    def _rows(self):
+        return self.addr
 
     @property
-    def device(self):
-        return self.addr.device
+    def _width(self):
+        return self.width
 
     @property
     def dtype(self):
         return self._dtype
 
-    @property
-    def shape(self):
-        return torch.Size((self.addr.numel(), self.width))
-
-    def size(self, dim=None):
-        return self.shape if dim is None else self.shape[dim]
-
-    def dim(self):
-        return 2
-
-    def numel(self):
-        return self.addr.numel() * self.width
-
     def record_stream(self, stream):
         for t in (self.addr, self.n_id, self.x_remote):
             if t is not None and t.is_cuda:
                 t.record_stream(stream)                  # (the resident tables live as long as the Sessions' graph does)
-
-    def to(self, device=None, non_blocking=False, **_kw):
-        if device is None or torch.device(device) == self.addr.device:
-            return self
-        return self.materialize().to(device=device, non_blocking=non_blocking)
 
     def materialize(self) -> torch.Tensor:
         """The feature matrix itself (on the caller's current stream)."""
@@ -825,6 +822,140 @@ def _host_ranges(n, batch_size, skip_nonfull, force_exact, exact_k):
 
 
 # --------------------------------------------------------------------------------------------
+# the output arenas of a delivery: one allocation per output kind for all the batches it covers
+# --------------------------------------------------------------------------------------------
+class _Arena:
+    """One allocation cut into consecutive segments (elements of a 1-D arena, rows of a 2-D one).  The segments are booked
+    first -- ``add`` returns the segment's index -- and the tensor is allocated and split ONCE; what the consumer gets
+    (``views[k]``) and what the native side gets (``ptrs[k]``, None for an empty segment) are both read from entry k of that
+    one book, so the two cannot drift apart."""
+    __slots__ = ("lens", "t", "views", "ptrs", "_offs", "_step")
+
+    def __init__(self):
+        self.lens = []
+
+    def add(self, n: int) -> int:
+        self.lens.append(n)
+        return len(self.lens) - 1
+
+    def alloc(self, dtype, device, width=None, coarse=True):
+        """`coarse`: the size is rounded up to a coarse grid (<= 3 %): the totals of a group differ by fractions of a
+        percent from group to group, and the caching allocator would otherwise keep meeting sizes no cached block fits"""
+        lens = self.lens
+        total = sum(lens)
+        rows = _coarse(total) if coarse else total
+        t = self.t = torch.empty(rows if width is None else (rows, width), dtype=dtype, device=device)
+        self.views = t.split(lens + [rows - total])
+        self._step = step = t.element_size() * (1 if width is None else width)
+        self._offs = offs = list(itertools.accumulate(lens, initial=0))
+        base = t.data_ptr()
+        self.ptrs = [base + step * o if n else None for o, n in zip(offs, lens)]
+        return t
+
+    def span(self, k0: int, k1: int):
+        """(view, pointer) of the segments k0 .. k1-1 as one"""
+        a, b = self._offs[k0], self._offs[k1]
+        return self.t[a:b], (self.t.data_ptr() + self._step * a if b > a else None)
+
+
+_BatchViews = collections.namedtuple(
+    "_BatchViews", "x y adjs idx_range n_id row_addr x_remote nids flat cached perm pc U")
+
+
+def _layout(descs, n, *, device, e_id, want_n_id=False, refs=False, want_parts=False, P=0, rank=0, p2p=False, want_x=False,
+            want_x8=False, want_y=False, F=0, x_dtype=None, y_width=0, y_dtype=None, coarse=True):
+    """Where a delivery writes the `n` batches `descs[0..n)` describe (spp_batch_desc: the host counts of every batch), and
+    what the consumer reads them through.  -> (GroupOut[n] for the native side, [_BatchViews] for the records, arenas).
+
+    int64 arena, batch after batch: n_id (`want_n_id`), one address per row (`refs`), rowptr and col of every hop, then --
+    `want_parts` -- the P ownership buckets (`flat` spans them), the cached ids and the perm.  x arena (`want_x`: written by
+    the delivery; `want_x8`: fp16 rows written by the dequantising gather behind it) and the arena of the rows received
+    over RCCL (`refs`, none with `p2p`): F elements of `x_dtype` per row, every batch starting on a 16-byte boundary
+    (rows of 16k + 8 bytes: on an even row), so that the delivery may store 16-byte pieces whatever the batches before it
+    hold (gather_body.hip.h, kVecSpan).  y arena: exactly the seeds' rows.  An empty segment's pointer is None.  `coarse`
+    rounds the int64, x and received-rows arenas (_Arena.alloc).  Touches nothing but its arguments."""
+    H = int(descs[0].counts.num_hops)
+    ids, xs, xrs, ys = _Arena(), _Arena(), _Arena(), _Arena()
+    have_x = want_x or want_x8
+    align = 16 // math.gcd(F * x_dtype.itemsize, 16) if (have_x or refs) else 1
+    plan = []
+    for i in range(n):
+        d = descs[i]
+        c = d.counts
+        U = int(c.num_nodes)
+        k_first = len(ids.lens)
+        if want_n_id:
+            ids.add(U)
+        if refs:
+            ids.add(U)
+        TS = []
+        for h in range(H):
+            T = int(c.T[h])
+            ids.add(T + 1)
+            ids.add(int(c.E[h]))
+            TS.append((T, int(c.S[h])))
+        pc = None
+        if want_parts:
+            pc = [int(c.part_counts[m]) for m in range(P + 1)]
+            for m in range(P + 1):
+                ids.add(pc[m])
+            ids.add(U)
+        k_x = k_xr = k_y = -1
+        if have_x:
+            k_x = xs.add(U)
+            xs.add((-U) % align)
+        if refs:                                       # rows received over RCCL for this batch (P2P: none are copied)
+            r = 0 if p2p else U - int(c.part_counts[rank]) - int(c.part_counts[P])
+            k_xr = xrs.add(r)
+            xrs.add((-r) % align)
+        start, stop = int(d.start), int(d.stop)
+        if want_y:
+            k_y = ys.add(stop - start)
+        plan.append((k_first, U, TS, pc, k_x, k_xr, k_y, (start, stop)))
+    arenas = [ids.alloc(torch.int64, device, coarse=coarse)]
+    if have_x:
+        arenas.append(xs.alloc(x_dtype, device, F, coarse))
+    if want_y:
+        arenas.append(ys.alloc(y_dtype, device, y_width, False))
+    if refs and sum(xrs.lens):
+        arenas.append(xrs.alloc(x_dtype, device, F, coarse))
+    outs = (nat.GroupOut * n)()
+    views, ptrs = ids.views, ids.ptrs
+    records = []
+    for i in range(n):
+        k, U, TS, pc, k_x, k_xr, k_y, rng = plan[i]
+        o = outs[i]
+        mfg = o.mfg
+        n_id = addr = xr = x = y = nids = flat = cached = perm = None
+        if want_n_id:
+            n_id, mfg.n_id = views[k], ptrs[k]
+            k += 1
+        if refs:
+            addr, mfg.row_addr = views[k], ptrs[k]
+            k += 1
+            if xrs.lens[k_xr]:                         # (a batch that received rows: the arena was allocated)
+                xr, mfg.x_remote = xrs.views[k_xr], xrs.ptrs[k_xr]
+        adjs = []
+        for h in range(H):
+            mfg.rowptr[h], mfg.col[h] = ptrs[k], ptrs[k + 1]
+            adjs.append((views[k], views[k + 1], e_id, TS[h]))         # e_id: always empty (sample_cpu.hpp:120)
+            k += 2
+        if want_parts:
+            nids = list(views[k:k + P])
+            flat, mfg.parts = ids.span(k, k + P)
+            cached, mfg.cached = views[k + P], ptrs[k + P]
+            perm, mfg.perm = views[k + P + 1], ptrs[k + P + 1]
+        if have_x:
+            x = xs.views[k_x]
+            if want_x:
+                o.x_out = xs.ptrs[k_x]
+        if want_y:
+            y, o.y_out = ys.views[k_y], ys.ptrs[k_y]
+        records.append(_BatchViews(x, y, adjs, rng, n_id, addr, xr, nids, flat, cached, perm, pc, U))
+    return outs, records, arenas
+
+
+# --------------------------------------------------------------------------------------------
 # Session   (fast_sampler.cpp:533-936 + worker :963-1274)
 # --------------------------------------------------------------------------------------------
 def resident_graph(config):
@@ -860,16 +991,9 @@ def resident_partition(config):
     rank = int(pb.rank)
     if not 0 <= rank < offs.numel() - 1:
         raise RuntimeError(f"resident_partition: rank {rank} outside the book's {offs.numel() - 1} partitions")
-    parts = [t for t in (xg, xc) if t is not None and t.dim() == 2 and t.size(0) > 0]
-    if len(parts) == 2:
-        x = _resident_concat(xg, xc)
-    elif len(parts) == 1:
-        x = _resident.get_rows(parts[0])
-    else:
-        wide = [t for t in (xg, xc) if t is not None and t.dim() == 2 and t.size(1) > 0]
-        if not wide:
-            raise RuntimeError("resident_partition: the configuration carries no feature table (x_gpu / x_cpu)")
-        x = torch.empty((0, wide[0].size(1)), dtype=wide[0].dtype, device=_device())
+    x = _resident_local_rows(xg, xc)
+    if x is None:
+        raise RuntimeError("resident_partition: the configuration carries no feature table (x_gpu / x_cpu)")
     n_local = int(offs[rank + 1] - offs[rank])
     if x.size(0) != n_local:
         raise RuntimeError(f"resident_partition: the partition holds {x.size(0)} rows, the book gives rank {rank} {n_local}")
@@ -900,8 +1024,38 @@ class Session:
         self._col = _resident.get(config.col, torch.int64)
         self._idx = config.idx.to(self._dev, torch.int64).contiguous()
         self._distributed = bool(config.distributed)
+        self._init_resident(fp8, pfp8)
+        slots = self._init_sampler(max_items_in_queue)
+        cfg = self._session_cfg(slots)
+        self.native_exchange = False
+        # Native exchange and the batch record.  A consumer built on the REFERENCE's façade wraps every
+        # batch in its own 7-field NamedTuple (fast_trainer/samplers.py:32-88), which reads
+        # partition_nids / cached_nids / perm_partition_to_mfg and has no room for `x`: by default the
+        # record therefore carries the ownership buckets as well, and the assembled features stay
+        # retrievable from the Session (take_native_features).  This repository's own façade sets
+        # compact_native_records and gets only what its iterator reads (x, y, MFG).
+        self.compact_native_records = False
+        self._native_feats = {}
+        self._cache_feats = None
+        self.p2p = False
+        self._peers = None
+        if self._distributed:
+            self._init_p2p_peers()
+            self._init_exchange(cfg, fp8_comm, pfp8)
+        h = C.c_void_p()
+        try:
+            nat.check(L.spp_session_create(C.byref(cfg), C.byref(h)))
+        except Exception:
+            _SamplerPool.release(self._pool_entry)
+            self._pool_entry = None
+            raise
+        self._h = h
+        self._init_delivery()
 
-        # features / labels resident in HBM
+    # ---- the steps of __init__, in the order they run ----
+    def _init_resident(self, fp8, pfp8):
+        """features / labels resident in HBM: self._x (None without a table), self._fp8 / self._pfp8, self._y"""
+        config = self.config
         self._fp8 = None
         self._pfp8 = None
         if fp8:
@@ -916,16 +1070,7 @@ class Session:
             self._pfp8 = Fp8Features._wrap(_resident.get(pfp8.q), _resident.get(pfp8.scale_log2))
             self._x = self._pfp8.q.view(torch.uint8)
         elif self._distributed:
-            xg, xc = config.x_gpu, config.x_cpu
-            parts = [t for t in (xg, xc) if t is not None and t.dim() == 2 and t.size(0) > 0]
-            if len(parts) == 2:
-                self._x = _resident_concat(xg, xc)
-            elif len(parts) == 1:
-                self._x = _resident.get_rows(parts[0])
-            else:
-                # a rank that owns no rows still takes part in the exchange: keep the width and dtype
-                wide = [t for t in (xg, xc) if t is not None and t.dim() == 2 and t.size(1) > 0]
-                self._x = torch.empty((0, wide[0].size(1)), dtype=wide[0].dtype, device=self._dev) if wide else None
+            self._x = _resident_local_rows(config.x_gpu, config.x_cpu)
         else:
             self._x = _resident.get_rows(config.x_cpu) \
                 if config.x_cpu is not None and config.x_cpu.dim() == 2 and config.x_cpu.numel() > 0 else None
@@ -936,6 +1081,10 @@ class Session:
         if self._y is not None and self._y.dim() == 1:
             self._y = self._y.unsqueeze(-1)
 
+    def _init_sampler(self, max_items_in_queue) -> int:
+        """ranges and slots: the pooled sampler that fits this session's batches (with the ownership bucketing of a
+        distributed one fused in); -> the slots in flight"""
+        config = self.config
         n = self._idx.numel()
         force_exact = bool(config.force_exact_num_batches)
         if force_exact and (config.exact_num_batches <= 0 or n // max(1, config.exact_num_batches) < 1):
@@ -946,7 +1095,12 @@ class Session:
         self._part = self._partition_cfg() if self._distributed else None
         self._pool_entry = _SamplerPool.acquire(self._rowptr, self._col, self._sizes, max_batch, slots,
                                                 self._dev.index, part=self._part)
+        return slots
 
+    def _session_cfg(self, slots):
+        """the spp_session_cfg of this session (its exchange is added by _init_exchange)"""
+        config = self.config
+        n = self._idx.numel()
         cfg = nat.SessionCfg()
         cfg.rowptr_dev, cfg.col_dev = self._rowptr.data_ptr(), self._col.data_ptr()
         cfg.num_nodes, cfg.nnz = self._rowptr.numel() - 1, self._col.numel()
@@ -956,7 +1110,7 @@ class Session:
         for i, s in enumerate(self._sizes):
             cfg.sizes[i] = s
         cfg.skip_nonfull_batch = int(bool(config.skip_nonfull_batch))
-        cfg.force_exact_num_batches = int(force_exact)
+        cfg.force_exact_num_batches = int(bool(config.force_exact_num_batches))
         cfg.exact_num_batches = int(config.exact_num_batches)
         cfg.max_items_in_queue = slots
         cfg.group_size = int(os.environ.get("SPP_GROUP_SIZE", "0"))   # 0 = auto
@@ -969,82 +1123,76 @@ class Session:
         cfg.sampler = self._pool_entry[0]
         if self._part is not None:
             cfg.part = C.pointer(self._part[0])
-        self.native_exchange = False
-        # Native exchange and the batch record.  A consumer built on the REFERENCE's façade wraps every
-        # batch in its own 7-field NamedTuple (fast_trainer/samplers.py:32-88), which reads
-        # partition_nids / cached_nids / perm_partition_to_mfg and has no room for `x`: by default the
-        # record therefore carries the ownership buckets as well, and the assembled features stay
-        # retrievable from the Session (take_native_features).  This repository's own façade sets
-        # compact_native_records and gets only what its iterator reads (x, y, MFG).
-        self.compact_native_records = False
-        self._native_feats = {}
-        self._cache_feats = None
-        self.p2p = False
-        self._peers = None
-        if self._distributed:
-            pb = config.partition_book
-            # P2P transport (opt-in, SPP_DIST_TRANSPORT=p2p): remote rows are read in their owners' partitions, no exchange
-            p2p = os.environ.get("SPP_DIST_TRANSPORT", "rccl").lower() == "p2p" and self._x is not None
-            if p2p:
-                peers = getattr(_p2p_tls, "peers", None)
-                if peers is None:
-                    key = (self._x.data_ptr(), int(pb.world_size), int(pb.rank))
-                    peers = _p2p_auto.get(key)
-                    if peers is None:
-                        peers = _p2p_auto[key] = p2p_open_peers(self._x)      # collective, once per resident table
-                if len(peers.ptrs) != int(pb.world_size):
-                    raise RuntimeError(f"P2P transport: {len(peers.ptrs)} peer tables for {int(pb.world_size)} partitions")
-                self._peers = peers
-            comm = fp8_comm if fp8_comm is not None else (None if p2p else native_comm())
-            if self._x is not None and (p2p or (comm is not None and
-                                                (comm.world, comm.rank) == (int(pb.world_size), int(pb.rank)))):
-                xc = nat.ExchangeCfg()
-                xc.comm = None if p2p else comm.handle
-                if p2p:
-                    self._peer_arr = (C.c_void_p * len(peers.ptrs))(*[v or None for v in peers.ptrs])
-                    xc.peer_x_dev = C.cast(self._peer_arr, C.POINTER(C.c_void_p))
-                    xc.peer_x_stride_bytes = peers.stride
-                    self.p2p = True
-                xc.x_local_dev, xc.x_local_rows = self._x.data_ptr(), self._x.size(0)
-                xc.row_bytes = self._x.size(1) * self._x.element_size()
-                xc.x_local_stride_bytes = _stride_bytes(self._x)
-                # who issues the exchanges: a session thread (most overlap) or the consumer inside
-                # blocking_get_batch_distributed, at the same program point on every rank (safe next
-                # to the caller's own collectives, e.g. DDP all-reduces) -- the default
-                xc.issue_on_consumer = int(os.environ.get("SPP_EXCHANGE_ISSUE", "consumer").lower() != "thread")
-                if self._pfp8 is not None:
-                    xc.x_elem = nat.SPP_ELEM_FP8_E4M3
-                    xc.scale_log2_dev = self._pfp8.scale_log2.data_ptr()
-                    xc.scales_tag = fp8_scales_tag(pfp8.scale_log2)
-                if bool(config.use_cache):
-                    self._cache_feats = config.cache.device_features()
-                    if isinstance(self._cache_feats, Fp8Features):
-                        if self._pfp8 is None:
-                            raise RuntimeError("cached_features: an fp8 cache needs an fp8 partition (x_gpu=Fp8Features)")
-                        self._cache_fp8 = self._cache_feats              # (keeps the resident pair alive)
-                        self._cache_feats = self._cache_feats.q.view(torch.uint8)
-                    if self._cache_feats.numel():
-                        if self._cache_feats.dtype != self._x.dtype or self._cache_feats.size(1) != self._x.size(1):
-                            raise RuntimeError("cached_features must match the feature rows in dtype and width")
-                        xc.cache_feats_dev, xc.cache_rows = self._cache_feats.data_ptr(), self._cache_feats.size(0)
-                        xc.cache_stride_bytes = _stride_bytes(self._cache_feats)
-                self._xc = xc
-                cfg.exchange = C.pointer(xc)
-                self.native_exchange = True
-                global _trimmed_for_exchange
-                if not _trimmed_for_exchange:
-                    # the exchange buffers are hipMalloc'ed by the library as the first groups size them:
-                    # hand back what torch's caching allocator hoards from set-up, once per process
-                    torch.cuda.empty_cache()
-                    _trimmed_for_exchange = True
-        h = C.c_void_p()
-        try:
-            nat.check(L.spp_session_create(C.byref(cfg), C.byref(h)))
-        except Exception:
-            _SamplerPool.release(self._pool_entry)
-            self._pool_entry = None
-            raise
-        self._h = h
+        return cfg
+
+    def _init_p2p_peers(self):
+        """P2P transport (opt-in, SPP_DIST_TRANSPORT=p2p): remote rows are read in their owners' partitions, no exchange.
+        Sets self._peers (None: another transport)."""
+        if os.environ.get("SPP_DIST_TRANSPORT", "rccl").lower() != "p2p" or self._x is None:
+            return
+        pb = self.config.partition_book
+        peers = getattr(_p2p_tls, "peers", None)
+        if peers is None:
+            key = (self._x.data_ptr(), int(pb.world_size), int(pb.rank))
+            peers = _p2p_auto.get(key)
+            if peers is None:
+                peers = _p2p_auto[key] = p2p_open_peers(self._x)      # collective, once per resident table
+        if len(peers.ptrs) != int(pb.world_size):
+            raise RuntimeError(f"P2P transport: {len(peers.ptrs)} peer tables for {int(pb.world_size)} partitions")
+        self._peers = peers
+
+    def _init_exchange(self, cfg, fp8_comm, pfp8):
+        """The native exchange of a partitioned session (cfg.exchange), when it has rows and a transport: the P2P peers, or
+        a native communicator that matches the partition book.  Sets native_exchange / p2p / _cache_feats."""
+        config, peers = self.config, self._peers
+        pb = config.partition_book
+        p2p = peers is not None
+        comm = fp8_comm if fp8_comm is not None else (None if p2p else native_comm())
+        if self._x is None or not (p2p or (comm is not None and
+                                           (comm.world, comm.rank) == (int(pb.world_size), int(pb.rank)))):
+            return
+        xc = nat.ExchangeCfg()
+        xc.comm = None if p2p else comm.handle
+        if p2p:
+            self._peer_arr = (C.c_void_p * len(peers.ptrs))(*[v or None for v in peers.ptrs])
+            xc.peer_x_dev = C.cast(self._peer_arr, C.POINTER(C.c_void_p))
+            xc.peer_x_stride_bytes = peers.stride
+            self.p2p = True
+        xc.x_local_dev, xc.x_local_rows = self._x.data_ptr(), self._x.size(0)
+        xc.row_bytes = self._x.size(1) * self._x.element_size()
+        xc.x_local_stride_bytes = _stride_bytes(self._x)
+        # who issues the exchanges: a session thread (most overlap) or the consumer inside
+        # blocking_get_batch_distributed, at the same program point on every rank (safe next
+        # to the caller's own collectives, e.g. DDP all-reduces) -- the default
+        xc.issue_on_consumer = int(os.environ.get("SPP_EXCHANGE_ISSUE", "consumer").lower() != "thread")
+        if self._pfp8 is not None:
+            xc.x_elem = nat.SPP_ELEM_FP8_E4M3
+            xc.scale_log2_dev = self._pfp8.scale_log2.data_ptr()
+            xc.scales_tag = fp8_scales_tag(pfp8.scale_log2)
+        if bool(config.use_cache):
+            self._cache_feats = config.cache.device_features()
+            if isinstance(self._cache_feats, Fp8Features):
+                if self._pfp8 is None:
+                    raise RuntimeError("cached_features: an fp8 cache needs an fp8 partition (x_gpu=Fp8Features)")
+                self._cache_fp8 = self._cache_feats              # (keeps the resident pair alive)
+                self._cache_feats = self._cache_feats.q.view(torch.uint8)
+            if self._cache_feats.numel():
+                if self._cache_feats.dtype != self._x.dtype or self._cache_feats.size(1) != self._x.size(1):
+                    raise RuntimeError("cached_features must match the feature rows in dtype and width")
+                xc.cache_feats_dev, xc.cache_rows = self._cache_feats.data_ptr(), self._cache_feats.size(0)
+                xc.cache_stride_bytes = _stride_bytes(self._cache_feats)
+        self._xc = xc
+        cfg.exchange = C.pointer(xc)
+        self.native_exchange = True
+        global _trimmed_for_exchange
+        if not _trimmed_for_exchange:
+            # the exchange buffers are hipMalloc'ed by the library as the first groups size them:
+            # hand back what torch's caching allocator hoards from set-up, once per process
+            torch.cuda.empty_cache()
+            _trimmed_for_exchange = True
+
+    def _init_delivery(self):
+        """delivery-mode flags and the per-batch state of the consumer side"""
         self._desc = nat.BatchDesc()
         # group-at-a-time delivery (include/spp.h spp_session_next_group / spp_session_export_group): the batches
         # of a sampling group are written by ONE launch into three arenas and handed out one by one
@@ -1055,7 +1203,8 @@ class Session:
         # The default: the group is FETCHED as a whole (spp_session_next_group: one blocking call, three allocations and
         # the views for all its batches) and delivered one launch per batch as the consumer asks (spp_session_export on
         # the group's members) -- the host side of group delivery with the launches of batch-at-a-time delivery.
-        # SPP_GROUP_FETCH=0: spp_session_next / spp_session_export per batch, nine allocations each.
+        # SPP_GROUP_FETCH=0: spp_session_next / spp_session_export per batch, each laid out as a group of one (three
+        # allocations of exactly its size per batch).
         self._member_mode = not self._group_mode and os.environ.get("SPP_GROUP_FETCH", "1") != "0"
         self._open = None                          # [next member, fetched group] while a group is partly handed out
         # opt-in (single-GPU sessions): the records carry TableRows(resident table, n_id) in the place of x and the
@@ -1225,58 +1374,65 @@ class Session:
             self._finish()
         return rc == 1          # 0: end of data, 2: not ready yet (non-blocking form only)
 
-    def _alloc_mfg(self, counts, want_n_id=True, num_parts=0):
-        """One int64 arena per batch for n_id and every hop's rowptr/col (a single allocator call
-        instead of 2*hops+1), handed out as views; `e_id` is the shared empty tensor.  With
-        num_parts = P > 0 the arena also holds the ownership buckets; then returns
-        (out, n_id, adjs, (partition_nids, cached_nids, perm))."""
-        H = counts.num_hops
-        U = int(counts.num_nodes) if want_n_id else 0
-        Ts = [int(counts.T[k]) for k in range(H)]
-        Es = [int(counts.E[k]) for k in range(H)]
-        P = num_parts
-        pc = [int(counts.part_counts[m]) for m in range(P + 1)] if P else []
-        owned = sum(pc[:P]) if P else 0
-        n_part = (owned + pc[P] + int(counts.num_nodes)) if P else 0
-        n_mfg = U + sum(Ts) + H + sum(Es)
-        arena = torch.empty(n_mfg + n_part, dtype=torch.int64, device=self._dev)
-        base = arena.data_ptr()
-        out = nat.MfgOut()
-        buckets = None
-        if P:
-            o = n_mfg
-            bounds = [o]
-            for m in range(P):
-                bounds.append(bounds[-1] + pc[m])
-            nids = [arena[bounds[m]:bounds[m + 1]] for m in range(P)]
-            flat = arena[bounds[0]:bounds[P]]
-            out.parts = (base + 8 * o) if owned else None
-            o += owned
-            cached = arena[o:o + pc[P]]
-            out.cached = (base + 8 * o) if pc[P] else None
-            o += pc[P]
-            perm = arena[o:o + int(counts.num_nodes)]
-            out.perm = (base + 8 * o) if int(counts.num_nodes) else None
-            buckets = (nids, cached, perm, flat)
-        n_id = None
-        off = 0
-        if want_n_id:
-            n_id = arena[:U]
-            out.n_id = base if U else None
-            off = U
-        adjs = []
-        e_id = self._e_id                                              # sample_cpu.hpp:120: always empty
-        for k in range(H):
-            rp = arena[off:off + Ts[k] + 1]
-            out.rowptr[k] = base + 8 * off
-            off += Ts[k] + 1
-            cl = arena[off:off + Es[k]]
-            out.col[k] = (base + 8 * off) if Es[k] else None
-            off += Es[k]
-            adjs.append((rp, cl, e_id, (Ts[k], int(counts.S[k]))))
-        if P:
-            return out, n_id, adjs, buckets
-        return out, n_id, adjs
+    def _open_one(self, block: bool):
+        """SPP_GROUP_FETCH=0: spp_session_next / spp_session_try_next, the batch laid out as a group of one (in arenas of
+        exactly its size).  None: not ready yet (block=False) or no batch left."""
+        return self._lay_out((self._desc,), 1, False) if self._next_desc(block) else None
+
+    def _open_group(self, block: bool):
+        """spp_session_next_group + the group's output arenas and views.  None: not ready yet (block=False) or no group
+        left; else what _lay_out returns."""
+        if self._h is None or self._ended:
+            return None
+        n_c = C.c_int32(0)
+        rc = self._L.spp_session_next_group(self._h, 1 if block else 0, self._gdescs, C.byref(n_c))
+        nat.check(rc)
+        if rc == 2:
+            return None
+        if rc == 0:                                   # end of data: the sampler goes back to the pool once the queue is handed out
+            self._ended = True
+            if not self._ready:
+                self._finish()
+            return None
+        global _groups_opened
+        _groups_opened += 1
+        return self._lay_out(self._gdescs, n_c.value, True)
+
+    def _lay_out(self, descs, n, coarse):
+        """What a delivery of this session writes and what its records carry, and the layout that gives the n batches
+        `descs` describe: (n, outs, records, x source args, y source args, flags for _make_record, arenas)."""
+        cfg = self.config
+        distributed = self._distributed
+        native = self.native_exchange
+        P = rank = 0
+        count_remote = False
+        if distributed:
+            P, rank = int(cfg.partition_book.world_size), int(cfg.partition_book.rank)
+            count_remote = bool(cfg.count_remote_frequency) and not bool(cfg.use_cache)
+        want_parts = distributed and (not native or count_remote or not self.compact_native_records)
+        table = self._table_mode()
+        refs = self._refs_mode()
+        fp8, x, y = self._fp8, self._x, self._y
+        want_x = x is not None and (native or not distributed) and not table and not refs
+        want_x8 = fp8 is not None and not table     # fp16 rows written by the dequantising gather, not by the delivery
+        want_y = y is not None
+        outs, records, arenas = _layout(
+            descs, n, device=self._dev, e_id=self._e_id, want_n_id=distributed or table or fp8 is not None, refs=refs,
+            want_parts=want_parts, P=P, rank=rank, p2p=self.p2p, want_x=want_x, want_x8=want_x8, want_y=want_y,
+            F=fp8.size(1) if want_x8 else (x.size(1) if x is not None else 0), x_dtype=self._out_dtype,
+            y_width=y.size(1) if want_y else 0, y_dtype=y.dtype if want_y else None, coarse=coarse)
+        xa = self._x_args if (want_x and not native) else (None, 0, 0, 0)      # (the native exchange assembles x itself)
+        ya = self._y_args if want_y else (None, 0, 0)
+        return n, outs, records, xa, ya, (distributed, native, count_remote, rank, table, refs), arenas
+
+    def _export(self, o, xa, ya):
+        """THE spp_session_export call: one batch (its GroupOut) on the stream the consumer named once
+        (set_export_stream), else on its current one.  -> that stream's raw handle"""
+        # (the raw handle of the caller's current stream: torch.cuda.current_stream() builds a Stream object, 2-3 us)
+        raw = self._export_raw if self._export_raw is not None else torch._C._cuda_getCurrentRawStream(self._dev.index)
+        nat.check(self._L.spp_session_export(self._h, C.byref(o.mfg), xa[0], xa[1], xa[2], xa[3], o.x_out,
+                                             ya[0], ya[1], ya[2], o.y_out, C.c_void_p(raw)))
+        return raw
 
     # ---- group-at-a-time delivery ----
     def _fetch_group(self, block: bool) -> bool:
@@ -1287,9 +1443,7 @@ class Session:
         if grp is None:
             return False
         n, outs, records, xa, ya, flags, _arenas = grp
-        dev = self._dev
-        distributed, native, count_remote, rank = flags
-        stream = torch.cuda.current_stream(dev)
+        stream = torch.cuda.current_stream(self._dev)
         nat.check(self._L.spp_session_export_group(self._h, n, outs, xa[0], xa[1], xa[2], xa[3], ya[0], ya[1], ya[2],
                                                    C.c_void_p(stream.cuda_stream)))
         if self._fp8 is not None:
@@ -1303,18 +1457,41 @@ class Session:
 
     def _fp8_deliver(self, r, raw_stream):
         """x = fp16(dequantised table[n_id]) of one batch record, behind its delivery on the same stream"""
-        x, n_id = r[0], r[4]
-        if isinstance(x, torch.Tensor) and n_id is not None:
-            fp8_gather_rows(self._fp8, n_id, x, raw_stream)
+        if r.x is not None and r.n_id is not None:
+            fp8_gather_rows(self._fp8, r.n_id, r.x, raw_stream)
 
     def _make_record(self, r, flags):
-        (x, y, adjs, rng, n_id, nids, flat, cached, perm, pc, U) = r
-        distributed, native, count_remote, rank = flags
+        """The record a consumer gets for one laid-out batch (_BatchViews): the 4-tuple of the single-GPU branch or the
+        ProtoDistributedBatch of the distributed one -- for every delivery mode."""
+        distributed, native, count_remote, rank, table, refs = flags
+        x = r.x
+        if table:
+            x = TableRows(self._x if self._fp8 is None else self._fp8, r.n_id)
+        elif refs:
+            x = RowRefs(r.row_addr, r.n_id, self._x.size(1), self._x.dtype, r.x_remote,
+                        (self._x, self._cache_feats, self._peers))
         if not distributed:
             if x is None:
-                x = torch.empty((U, 0), device=self._dev)
-            return (x, y, adjs, rng)
-        return self._proto_record(x, y, adjs, rng, n_id, nids, flat, cached, perm, pc, native, count_remote, rank)
+                x = torch.empty((r.U, 0), device=self._dev)
+            return (x, r.y, r.adjs, r.idx_range)
+        b = ProtoDistributedBatch()
+        b.x = x if native else None
+        if r.nids is None:                             # compact native record: only what this repository's iterator reads
+            b.partition_nids, b.partition_nids_flat = [], None
+            b.cached_nids = b.perm_partition_to_mfg = torch.empty(0, dtype=torch.int64, device=self._dev)
+        else:
+            b.partition_nids, b.partition_nids_flat = r.nids, r.flat
+            b.cached_nids, b.perm_partition_to_mfg = r.cached, r.perm
+            b.partition_counts = r.pc
+        b.sliced_cpu_features = torch.empty((0, self._x.size(1) if self._x is not None else 0),
+                                            dtype=self._out_dtype)             # all local rows are in HBM
+        b.sliced_cpu_labels = r.y if r.y is not None else torch.zeros(0)
+        b.adjs = r.adjs
+        b.idx_range = r.idx_range
+        b.n_id = r.n_id
+        if count_remote:
+            self._count_remote(b.partition_nids, rank)
+        return b
 
     def _table_mode(self) -> bool:
         if not self.table_features:
@@ -1343,26 +1520,23 @@ class Session:
         return True
 
     def _next_member(self, block: bool):
-        """The default delivery: the sampling group is FETCHED as a whole (one blocking call, one allocation per output
-        kind for all its batches, the views cut once) and its batches are then delivered one launch each, when asked
-        for -- the host work of a batch is one export call and the record, the GPU sees the same per-batch launches as
-        with batch-at-a-time calls."""
+        """The per-batch delivery.  By default the sampling group is FETCHED as a whole (one blocking call, one allocation
+        per output kind for all its batches, the views cut once) and its batches are then delivered one launch each, when
+        asked for -- the host work of a batch is one export call and the record.  With SPP_GROUP_FETCH=0 every batch is
+        fetched by a call of its own, as a group of one: the GPU sees the same per-batch launches either way."""
         if self._open is None:
+            fetch = self._open_group if self._member_mode else self._open_one
             if self.export_stream is not None:     # the group's arenas belong to the stream its batches are delivered on
                 with torch.cuda.stream(self.export_stream):
-                    grp = self._open_group(block)
+                    grp = fetch(block)
             else:
-                grp = self._open_group(block)
+                grp = fetch(block)
             if grp is None:
                 return None
             self._open = [0, grp]
         i, (n, outs, records, xa, ya, flags, arenas) = self._open
         self.last_arenas = arenas
-        o = outs[i]
-        # (the raw handle of the caller's current stream: torch.cuda.current_stream() builds a Stream object, 2-3 us)
-        raw = self._export_raw if self._export_raw is not None else torch._C._cuda_getCurrentRawStream(self._dev.index)
-        nat.check(self._L.spp_session_export(self._h, C.byref(o.mfg), xa[0], xa[1], xa[2], xa[3], o.x_out,
-                                             ya[0], ya[1], ya[2], o.y_out, C.c_void_p(raw)))
+        raw = self._export(outs[i], xa, ya)
         if self._fp8 is not None:
             self._fp8_deliver(records[i], raw)
         rec = self._make_record(records[i], flags)
@@ -1371,205 +1545,6 @@ class Session:
         else:
             self._open[0] = i + 1
         return rec
-
-    def _open_group(self, block: bool):
-        """spp_session_next_group + the group's output arenas and views.  None: not ready yet (block=False) or no group
-        left; else (n, outs, records, x source args, y source args, (distributed, native, count_remote, rank))."""
-        if self._h is None or self._ended:
-            return None
-        n_c = C.c_int32(0)
-        rc = self._L.spp_session_next_group(self._h, 1 if block else 0, self._gdescs, C.byref(n_c))
-        nat.check(rc)
-        if rc == 2:
-            return None
-        if rc == 0:                                   # end of data: the sampler goes back to the pool once the queue is handed out
-            self._ended = True
-            if not self._ready:
-                self._finish()
-            return None
-        n = n_c.value
-        global _groups_opened
-        _groups_opened += 1
-        dev = self._dev
-        cfg = self.config
-        distributed = self._distributed
-        native = self.native_exchange
-        P = int(cfg.partition_book.world_size) if distributed else 0
-        rank = int(cfg.partition_book.rank) if distributed else 0
-        use_cache = bool(cfg.use_cache) if distributed else False
-        count_remote = distributed and bool(cfg.count_remote_frequency) and not use_cache
-        want_parts = distributed and (not native or count_remote or not self.compact_native_records)
-        table = self._table_mode()
-        refs = self._refs_mode()
-        fp8 = self._fp8
-        want_n_id = distributed or table or fp8 is not None
-        want_x = (self._x is not None) and (native or not distributed) and not table and not refs
-        want_x8 = fp8 is not None and not table     # fp16 rows written by the dequantising gather, not by the delivery
-        want_y = self._y is not None
-        H = int(self._gdescs[0].counts.num_hops)
-        # ---- sizes (host counts of every batch) and the arena layout
-        seg = []                                      # lengths of all int64 segments, batch after batch
-        info = []
-        Us, bss, n_rem = [], [], []
-        for i in range(n):
-            d = self._gdescs[i]
-            c = d.counts
-            U = int(c.num_nodes)
-            Ts = [int(c.T[k]) for k in range(H)]
-            Ss = [int(c.S[k]) for k in range(H)]
-            Es = [int(c.E[k]) for k in range(H)]
-            pc = [int(c.part_counts[m]) for m in range(P + 1)] if want_parts else None
-            first = len(seg)
-            if want_n_id:
-                seg.append(U)
-            if refs:
-                seg.append(U)                          # one address per row
-            for k in range(H):
-                seg.append(Ts[k] + 1)
-                seg.append(Es[k])
-            if want_parts:
-                seg.extend(pc[:P])
-                seg.append(pc[P])
-                seg.append(U)
-            info.append((first, U, Ts, Ss, Es, pc, int(d.start), int(d.stop)))
-            Us.append(U)
-            bss.append(int(d.stop) - int(d.start))
-            if refs:                                   # rows received over RCCL for this batch (P2P: none are copied)
-                n_rem.append(0 if self.p2p else U - int(c.part_counts[rank]) - int(c.part_counts[P]))
-        # arena sizes are rounded up to a coarse grid (<= 3 %): group totals differ by fractions of a percent from
-        # group to group, and the caching allocator would otherwise keep meeting sizes no cached block fits
-        n_seg = sum(seg)
-        arena = torch.empty(_coarse(n_seg), dtype=torch.int64, device=dev)
-        if seg:
-            seg.append(arena.numel() - n_seg)
-        views = arena.split(seg) if seg else ()
-        base = arena.data_ptr()
-        x_views = y_views = None
-        row_b = 0
-        if want_x8:
-            F = fp8.size(1)
-            x_arena = torch.empty((_coarse(sum(Us)), F), dtype=torch.float16, device=dev)   # rows of 2F bytes, F % 16 == 0:
-            x_views = x_arena.split(Us + [x_arena.size(0) - sum(Us)])                       # every batch starts 32-byte aligned
-        if want_x:
-            F = self._x.size(1)
-            row_b = F * self._out_dtype.itemsize     # (an fp8 partition delivers fp16: rows of 2F bytes)
-            # every batch starts on a 16-byte boundary of the arena (rows of 16k + 8 bytes: on an even row), so that the
-            # delivery may store 16-byte pieces whatever the batches before it hold (gather_body.hip.h, kVecSpan)
-            x_align = 16 // math.gcd(row_b, 16)
-            x_split = []
-            for U in Us:
-                x_split += [U, (-U) % x_align]
-            n_rows = sum(x_split)
-            x_arena = torch.empty((_coarse(n_rows), F), dtype=self._out_dtype, device=dev)
-            x_views = x_arena.split(x_split + [x_arena.size(0) - n_rows])[0::2]
-            x_base = x_arena.data_ptr()
-        xr_arena = xr_views = None
-        if refs:
-            F = self._x.size(1)
-            row_b = F * self._x.element_size()
-            xr_align = 16 // math.gcd(row_b, 16)        # every batch's received rows start 16-byte aligned
-            xr_split = []
-            for r_ in n_rem:
-                xr_split += [r_, (-r_) % xr_align]
-            if sum(n_rem):
-                xr_arena = torch.empty((_coarse(sum(xr_split)), F), dtype=self._x.dtype, device=dev)
-                xr_views = xr_arena.split(xr_split + [xr_arena.size(0) - sum(xr_split)])[0::2]
-                xr_base = xr_arena.data_ptr()
-        if want_y:
-            y_arena = torch.empty((sum(bss), self._y.size(1)), dtype=self._y.dtype, device=dev)
-            y_views = y_arena.split(bss)
-            y_base, yrow_b = y_arena.data_ptr(), self._y.size(1) * self._y.element_size()
-        outs = (nat.GroupOut * n)()
-        e_id = self._e_id
-        off = 0                                       # running element offset into the int64 arena
-        xo = yo = xro = 0
-        records = []
-        for i in range(n):
-            first, U, Ts, Ss, Es, pc, start, stop = info[i]
-            o = outs[i]
-            k = first
-            n_id = None
-            if want_n_id:
-                n_id = views[k]
-                o.mfg.n_id = (base + 8 * off) if U else None
-                off += U
-                k += 1
-            addr = None
-            if refs:
-                addr = views[k]
-                o.mfg.row_addr = (base + 8 * off) if U else None
-                off += U
-                k += 1
-            adjs = []
-            for h in range(H):
-                o.mfg.rowptr[h] = base + 8 * off
-                off += Ts[h] + 1
-                o.mfg.col[h] = (base + 8 * off) if Es[h] else None
-                off += Es[h]
-                adjs.append((views[k], views[k + 1], e_id, (Ts[h], Ss[h])))
-                k += 2
-            nids = flat = cached = perm = None
-            if want_parts:
-                owned = sum(pc[:P])
-                o.mfg.parts = (base + 8 * off) if owned else None
-                nids = list(views[k:k + P])
-                flat = arena[off:off + owned]
-                off += owned
-                k += P
-                cached = views[k]
-                o.mfg.cached = (base + 8 * off) if pc[P] else None
-                off += pc[P]
-                perm = views[k + 1]
-                o.mfg.perm = (base + 8 * off) if U else None
-                off += U
-            x = y = None
-            if table:
-                x = TableRows(self._x if fp8 is None else fp8, n_id)
-            if want_x8:
-                x = x_views[i]
-            if refs:
-                xr = None
-                if n_rem[i]:
-                    xr = xr_views[i]
-                    o.mfg.x_remote = xr_base + xro * row_b
-                    xro += n_rem[i] + (-n_rem[i]) % xr_align
-                x = RowRefs(addr, n_id, self._x.size(1), self._x.dtype, xr, (self._x, self._cache_feats, self._peers))
-            if want_x:
-                x = x_views[i]
-                o.x_out = (x_base + xo * row_b) if U else None
-                xo += U + (-U) % x_align
-            if want_y:
-                y = y_views[i]
-                o.y_out = (y_base + yo * yrow_b) if bss[i] else None
-                yo += bss[i]
-            records.append((x, y, adjs, (start, stop), n_id, nids, flat, cached, perm, pc, U))
-        xa = self._x_args if (want_x and not native) else (None, 0, 0, 0)
-        ya = self._y_args if want_y else (None, 0, 0)
-        arenas = [t for t in (arena, x_arena if (want_x or want_x8) else None, y_arena if want_y else None, xr_arena) if t is not None]
-        return n, outs, records, xa, ya, (distributed, native, count_remote, rank), arenas
-
-    def _proto_record(self, x, y, adjs, rng, n_id, nids, flat, cached, perm, pc, native, count_remote, rank):
-        b = ProtoDistributedBatch()
-        feat_dim = self._x.size(1) if self._x is not None else 0
-        feat_dtype = self._out_dtype
-        if nids is None:                               # compact native record: only what this repository's iterator reads
-            nids, flat = [], None
-            cached = perm = torch.empty(0, dtype=torch.int64, device=self._dev)
-        b.x = x if native else None
-        b.partition_nids = nids
-        b.partition_nids_flat = flat
-        b.cached_nids = cached
-        b.perm_partition_to_mfg = perm
-        if pc is not None:
-            b.partition_counts = pc
-        b.sliced_cpu_features = torch.empty((0, feat_dim), dtype=feat_dtype)   # all local rows are in HBM
-        b.sliced_cpu_labels = y if y is not None else torch.zeros(0)
-        b.adjs = adjs
-        b.idx_range = rng
-        b.n_id = n_id
-        if count_remote:
-            self._count_remote(b.partition_nids, rank)
-        return b
 
     def _pop_ready(self, block: bool):
         """Hand out the next delivered batch; keeps one group delivered AHEAD of the one being handed out, so that
@@ -1596,134 +1571,27 @@ class Session:
     def blocking_get_batch(self, _block=True):
         """-> None or (x, y-or-None, [(rowptr, col, e_id, (T, S)) ...], (start, stop))
         (worker non-distributed branch, fast_sampler.cpp:1004-1016)."""
-        if self._group_mode:
-            return self._pop_ready(_block)
-        if self._member_mode:
-            return self._next_member(_block)
-        if not self._next_desc(_block):
-            return None
-        d = self._desc
-        c = d.counts
-        table = self._table_mode()
-        fp8 = self._fp8
-        out, n_id, adjs = self._alloc_mfg(c, want_n_id=table or fp8 is not None)          # n_id is not part of the tuple
-        x = y = None
-        if table:
-            x = None
-        elif fp8 is not None:
-            x = torch.empty((c.num_nodes, fp8.size(1)), dtype=torch.float16, device=self._dev)
-        elif self._x is not None:
-            x = torch.empty((c.num_nodes, self._x.size(1)), dtype=self._x.dtype, device=self._dev)
-        else:
-            x = torch.empty((c.num_nodes, 0), device=self._dev)
-        if self._y is not None:
-            y = torch.empty((d.stop - d.start, self._y.size(1)), dtype=self._y.dtype, device=self._dev)
-        self._export(out, x, y)
-        if fp8 is not None and not table:
-            fp8_gather_rows(fp8, n_id, x)
-        return (TableRows(self._x if fp8 is None else fp8, n_id) if table else x, y, adjs, (int(d.start), int(d.stop)))
+        return self._pop_ready(_block) if self._group_mode else self._next_member(_block)
 
     def try_get_batch(self):
         """Non-blocking (fast_sampler.cpp:658-670): None when no batch is ready yet or none is left."""
         return self.blocking_get_batch(_block=False)
 
-    def _export(self, out, x, y):
-        xa = self._x_args if x is not None and self._x is not None else (None, 0, 0, 0)
-        ya = self._y_args if y is not None and self._y is not None else (None, 0, 0)
-        nat.check(self._L.spp_session_export(
-            self._h, C.byref(out),
-            xa[0], xa[1], xa[2], xa[3], C.c_void_p(x.data_ptr()) if xa[0] is not None and x.numel() else None,
-            ya[0], ya[1], ya[2], C.c_void_p(y.data_ptr()) if ya[0] is not None and y.numel() else None,
-            C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)))
-
     def blocking_get_batch_distributed(self, _block=True):
-        """-> None or ProtoDistributedBatch (worker distributed branch, fast_sampler.cpp:1017-1272)."""
-        if self._group_mode or self._member_mode:
-            b = self._pop_ready(_block) if self._group_mode else self._next_member(_block)
-            if b is not None and self.native_exchange and not self.compact_native_records:
-                # at most the two newest batches (double buffering); a consumer that never asks loses nothing
-                while len(self._native_feats) >= 2:
-                    self._native_feats.pop(next(iter(self._native_feats)))
-                self._native_feats[b.idx_range] = (b.x, b.n_id)
-            return b
-        if not self._next_desc(_block):
-            return None
-        d = self._desc
-        c = d.counts
-        cfg = self.config
-        pb = cfg.partition_book
-        P, rank = int(pb.world_size), int(pb.rank)
-        use_cache = bool(cfg.use_cache)
-        if self.native_exchange:
-            return self._native_distributed_batch(d, c, P, rank, use_cache)
-        # the ownership buckets were built by the sampling chain; their sizes came with the counts
-        out, n_id, adjs, (nids, cached, perm, flat) = self._alloc_mfg(c, num_parts=P)
-        y = None
-        if self._y is not None:
-            y = torch.empty((d.stop - d.start, self._y.size(1)), dtype=self._y.dtype, device=self._dev)
-        self._export(out, None, y)
-        b = ProtoDistributedBatch()
-        b.partition_nids = nids
-        b.partition_nids_flat = flat
-        b.cached_nids = cached
-        b.perm_partition_to_mfg = perm
-        b.partition_counts = [int(c.part_counts[m]) for m in range(P + 1)]
-        feat_dim = self._x.size(1) if self._x is not None else 0
-        feat_dtype = self._x.dtype if self._x is not None else torch.float16
-        b.sliced_cpu_features = torch.empty((0, feat_dim), dtype=feat_dtype)   # all local rows are in HBM
-        b.sliced_cpu_labels = y if y is not None else torch.zeros(0)
-        b.adjs = adjs
-        b.idx_range = (int(d.start), int(d.stop))
-        b.n_id = n_id
-        if cfg.count_remote_frequency and not use_cache:
-            self._count_remote(b.partition_nids, rank)
+        """-> None or ProtoDistributedBatch (worker distributed branch, fast_sampler.cpp:1017-1272).  With the native
+        exchange one launch has delivered the MFG, the labels and x assembled from {local partition, rows received over
+        RCCL, VIP cache}; otherwise the record carries the ownership buckets the sampling chain built."""
+        b = self._pop_ready(_block) if self._group_mode else self._next_member(_block)
+        if b is not None and self.native_exchange and not self.compact_native_records:
+            # at most the two newest batches (double buffering); a consumer that never asks loses nothing
+            while len(self._native_feats) >= 2:
+                self._native_feats.pop(next(iter(self._native_feats)))
+            self._native_feats[b.idx_range] = (b.x, b.n_id)
         return b
 
     def try_get_batch_distributed(self):
         """Non-blocking (fast_sampler.cpp:672-711): None when the next batch (index order) is not ready."""
         return self.blocking_get_batch_distributed(_block=False)
-
-    def _native_distributed_batch(self, d, c, P, rank, use_cache):
-        """The exchange already ran natively (session.hip): one launch delivers the MFG, the labels
-        and x assembled from {local partition, rows received over RCCL, VIP cache}."""
-        cfg = self.config
-        count_remote = bool(cfg.count_remote_frequency) and not use_cache
-        want_parts = count_remote or not self.compact_native_records
-        if want_parts:
-            out, n_id, adjs, (nids, cached, perm, flat) = self._alloc_mfg(c, num_parts=P)
-        else:
-            out, n_id, adjs = self._alloc_mfg(c)
-            nids, flat = [], None
-            cached = perm = torch.empty(0, dtype=torch.int64, device=self._dev)
-        x = torch.empty((c.num_nodes, self._x.size(1)), dtype=self._out_dtype, device=self._dev)
-        y = None
-        if self._y is not None:
-            y = torch.empty((d.stop - d.start, self._y.size(1)), dtype=self._y.dtype, device=self._dev)
-        ya = self._y_args if y is not None else (None, 0, 0)
-        nat.check(self._L.spp_session_export(
-            self._h, C.byref(out), None, 0, 0, 0, C.c_void_p(x.data_ptr()) if x.numel() else None,
-            ya[0], ya[1], ya[2], C.c_void_p(y.data_ptr()) if ya[0] is not None and y.numel() else None,
-            C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)))
-        b = ProtoDistributedBatch()
-        b.x = x
-        b.partition_nids = nids
-        b.partition_nids_flat = flat
-        b.cached_nids = cached
-        b.perm_partition_to_mfg = perm
-        b.partition_counts = [int(c.part_counts[m]) for m in range(P + 1)]
-        b.sliced_cpu_features = torch.empty((0, self._x.size(1)), dtype=self._out_dtype)
-        b.sliced_cpu_labels = y if y is not None else torch.zeros(0)
-        b.adjs = adjs
-        b.idx_range = (int(d.start), int(d.stop))
-        b.n_id = n_id
-        if count_remote:
-            self._count_remote(b.partition_nids, rank)
-        if not self.compact_native_records:
-            # at most the two newest batches (double buffering); a consumer that never asks loses nothing
-            while len(self._native_feats) >= 2:
-                self._native_feats.pop(next(iter(self._native_feats)))
-            self._native_feats[b.idx_range] = (x, n_id)
-        return b
 
     def take_native_features(self, idx_range):
         """(x, n_id) of the batch covering seeds idx_range = (start, stop) or slice(start, stop), when the
@@ -1795,6 +1663,18 @@ class Session:
     def get_n_most_freq_remote_vertices(self, n: int) -> torch.Tensor:
         self.reduce_multithreaded_frequency_counts()
         return self.remote_vertices_ordered_by_freq[:n].clone()
+
+
+def _resident_local_rows(xg, xc) -> Optional[torch.Tensor]:
+    """A rank's partition of the feature table, resident in HBM: ``x_gpu`` then ``x_cpu``.  A rank that owns no rows
+    still takes part in the exchange: it keeps the width and dtype.  None: the configuration carries no table."""
+    parts = [t for t in (xg, xc) if t is not None and t.dim() == 2 and t.size(0) > 0]
+    if len(parts) == 2:
+        return _resident_concat(xg, xc)
+    if len(parts) == 1:
+        return _resident.get_rows(parts[0])
+    wide = [t for t in (xg, xc) if t is not None and t.dim() == 2 and t.size(1) > 0]
+    return torch.empty((0, wide[0].size(1)), dtype=wide[0].dtype, device=_device()) if wide else None
 
 
 def _resident_concat(x_gpu: torch.Tensor, x_cpu: torch.Tensor) -> torch.Tensor:

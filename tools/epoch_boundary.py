@@ -42,7 +42,8 @@ def _timed(cls, name):
     setattr(cls, name, wrap)
 
 
-for _n in ("_next_desc", "_alloc_mfg", "_export", "close"):
+# (fetching a group or -- SPP_GROUP_FETCH=0 -- one batch, laying its outputs out, the per-batch delivery call)
+for _n in ("_open_group", "_next_desc", "_lay_out", "_export", "close"):
     _timed(fs.Session, _n)
 from salient_plusplus_amd.fast_trainer import samplers as _smp  # noqa: E402
 _timed(_smp.PreparedBatch, "record_stream")
