@@ -4,6 +4,7 @@
 // backward is transpose_hop.hip.h's, the keep rule of the attention dropout act_keep.hip.h's.
 #include "act_keep.hip.h"
 #include "elem_io.hip.h"
+#include "gatv2_core.hip.h"  // check_heads: the head counts of every attention entry, one rule and one message
 #include "transpose_hop.hip.h"
 
 #include <algorithm>
@@ -696,8 +697,7 @@ static float* out(const float* p) { return const_cast<float*>(p); }
 // The head count, and x: x_elem is the element code of its rows (0 fp32, 1 fp16, 2 bf16); the softmax statistics, z and
 // all gradients stay fp32.  Every entry runs these checks before anything else.
 static spp_status gat_check(const GatHop& h) {
-  SPP_REQUIRE(h.heads == 1 || h.heads == 2 || h.heads == 4 || h.heads == 8, "%s: heads must be 1, 2, 4 or 8 (got %d)",
-              h.who, (int)h.heads);
+  SPP_TRY(gatv2::check_heads(h.who, h.heads));
   SPP_REQUIRE(elem_ok(h.x_elem), "%s: unknown element code %d", h.who, (int)h.x_elem);
   const int64_t esz = elem_bytes(h.x_elem);
   SPP_REQUIRE(h.K > 0 && h.K % 4 == 0 && h.K / 4 <= spp::kAggNT && h.x_stride >= h.K &&
@@ -1037,8 +1037,7 @@ extern "C" spp_status spp_gat_mh_attn_keep(int64_t num_edges, int64_t num_target
                                            uint8_t* keep_dev, void* stream) {
   const char* who = "spp_gat_mh_attn_keep";
   SPP_REQUIRE(num_edges >= 0 && num_targets >= 0, "%s: negative size", who);
-  SPP_REQUIRE(heads == 1 || heads == 2 || heads == 4 || heads == 8, "%s: heads must be 1, 2, 4 or 8 (got %d)", who,
-              (int)heads);
+  SPP_TRY(gatv2::check_heads(who, heads));
   SPP_REQUIRE(p >= 0.f && p < 1.f, "%s: attention dropout needs 0 <= p < 1", who);
   const int64_t n = num_edges + num_targets;
   SPP_REQUIRE(n < (1ll << 31) * (int64_t)kAggNT, "%s: size out of range", who);

@@ -11,13 +11,11 @@
 // wave-wide segments for grad_xl; element I/O and the entry checks of elem_io.hip.h.
 // Built for C / 4 a power of two (the per-head reduction is an xor butterfly over aligned lane segments); with H in
 // {1, 2, 4, 8} D = H * C is then a power of two as well, 4 <= D <= 1024.
-#include "gatv2_core.hip.h"
+#include "attn_train.hip.h"
 
 namespace spp {
 
 using namespace gatv2;
-
-constexpr int kV2NT = 256;
 
 // Forward.  The lane mapping, the logit, the online softmax and the walk over a row are gatv2_core.hip.h's (shared with
 // the long-row kernels of graph_gatv2.hip): lpr lanes per target, 4 columns per lane and chunk, NB neighbours in flight,
@@ -28,26 +26,21 @@ constexpr int kV2NT = 256;
 // loop's x_l[t] included.  The lane's head hl is global head ((hl * CPH) * lpr + lane) >> g_log2; every lane hashes for
 // the heads it holds (the lanes of a head's segment draw the same bits).
 template <typename Tin, int NQ, int CPH, bool kDrop>
-__global__ __launch_bounds__(kV2NT) void k_gatv2_fwd(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,
-                                                     int64_t T, const Tin* xl, int64_t xl_stride, const Tin* xr,
-                                                     int64_t xr_stride, const float* __restrict__ att, float slope,
-                                                     int lpr_log2, int seg_log2, int g_log2, int H,
-                                                     float* __restrict__ out, float* __restrict__ row_max,
-                                                     float* __restrict__ row_sum, ActArgs drop) {
+__global__ __launch_bounds__(kAttnNT) void k_gatv2_fwd(
+    const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col, int64_t T, const Tin* xl, int64_t xl_stride,
+    const Tin* xr, int64_t xr_stride, const float* __restrict__ att, float slope, int lpr_log2, int seg_log2,
+    int g_log2, int H, float* __restrict__ out, float* __restrict__ row_max, float* __restrict__ row_sum, ActArgs drop) {
   constexpr int HL = NQ / CPH;
   Lane<NQ, CPH> L;
   L.slope = slope, L.lpr = 1 << lpr_log2, L.lane = threadIdx.x & (L.lpr - 1), L.seg_log2 = seg_log2;
-  const int64_t t = ((int64_t)blockIdx.x * kV2NT + threadIdx.x) >> lpr_log2;
+  const int64_t t = ((int64_t)blockIdx.x * kAttnNT + threadIdx.x) >> lpr_log2;
   if (t >= T) return;  // whole groups leave together (the shuffles below stay inside a group)
-  const int64_t D = (int64_t)NQ * L.lpr * 4;
   L.load(att, xr + t * xr_stride);
   State<NQ, CPH> st;
   self_state(st, L, xl + t * xl_stride);  // the self loop's message: source row t
   if constexpr (kDrop) {
     Drop<HL> dr;
-    dr.a = drop, dr.H = H;
-#pragma unroll
-    for (int hl = 0; hl < HL; ++hl) dr.head[hl] = ((hl * CPH) * L.lpr + L.lane) >> g_log2;
+    fwd_drop_heads<CPH>(dr, drop, H, L.lpr, L.lane, g_log2);
     const uint64_t self = (uint64_t)(rowptr[T] + t);  // the self loops' draws come after the E = rowptr[T] entries'
 #pragma unroll
     for (int hl = 0; hl < HL; ++hl) {
@@ -59,17 +52,7 @@ __global__ __launch_bounds__(kV2NT) void k_gatv2_fwd(const int64_t* __restrict__
   } else {
     walk(st, L, xl, xl_stride, col, rowptr[t], rowptr[t + 1], t, (int64_t)-1);
   }
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) {
-    const int hl = q / CPH;
-    const int p = q * L.lpr + L.lane;
-    const f4 r = st.template result<kDrop>(q, drop.scale);
-    *reinterpret_cast<float4*>(out + t * D + (int64_t)p * 4) = make_float4(r.x, r.y, r.z, r.w);
-    if ((p & ((1 << g_log2) - 1)) == 0) {  // the head's first piece
-      row_max[t * H + (p >> g_log2)] = st.mm[hl];
-      row_sum[t * H + (p >> g_log2)] = st.ss[hl];
-    }
-  }
+  fwd_store<kDrop, false>(st, t, L.lpr, L.lane, g_log2, H, drop.scale, out, row_max, row_sum);
 }
 
 // Backward.  ONE column per lane and step, c = lane + lpt * i, i < NS, lpt = min(64, D) lanes per target: a group's
@@ -87,21 +70,18 @@ __global__ __launch_bounds__(kV2NT) void k_gatv2_fwd(const int64_t* __restrict__
 // and grad_xl[j] takes q alpha g_i + ge att d.  q = keep ? 1 / (1 - p) : 0 per (entry, head), the forward's draws: the
 // lane's head hl is global head (lane + lpt * hl * SPH) >> c_log2, and every lane hashes for the heads it holds.
 template <typename Tin, int NS, int SPH, bool kDrop>
-__global__ __launch_bounds__(kV2NT) void k_gatv2_bwd(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,
-                                                     int64_t T, const Tin* xl, int64_t xl_stride, const Tin* xr,
-                                                     int64_t xr_stride, const float* __restrict__ att, float slope,
-                                                     int lpt_log2, int seg_log2, int c_log2, int H,
-                                                     const float* __restrict__ out, const float* __restrict__ row_max,
-                                                     const float* __restrict__ row_sum, const float* __restrict__ g,
-                                                     int64_t tpg, float* __restrict__ grad_xl,
-                                                     float* __restrict__ grad_xr, float* __restrict__ grad_att,
-                                                     ActArgs drop) {
+__global__ __launch_bounds__(kAttnNT) void k_gatv2_bwd(
+    const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col, int64_t T, const Tin* xl, int64_t xl_stride,
+    const Tin* xr, int64_t xr_stride, const float* __restrict__ att, float slope, int lpt_log2, int seg_log2,
+    int c_log2, int H, const float* __restrict__ out, const float* __restrict__ row_max,
+    const float* __restrict__ row_sum, const float* __restrict__ g, int64_t tpg, float* __restrict__ grad_xl,
+    float* __restrict__ grad_xr, float* __restrict__ grad_att, ActArgs drop) {
   constexpr int HL = NS / SPH;
-  __shared__ float red[kV2NT / kWave][NS][kWave];
+  __shared__ float red[kAttnNT / kWave][NS][kWave];
   const int lpt = 1 << lpt_log2;
   const int lane = threadIdx.x & (lpt - 1);
   const int64_t D = (int64_t)NS * lpt;
-  const int64_t gid = ((int64_t)blockIdx.x * kV2NT + threadIdx.x) >> lpt_log2;
+  const int64_t gid = ((int64_t)blockIdx.x * kAttnNT + threadIdx.x) >> lpt_log2;
   const int64_t t0 = gid * tpg < T ? gid * tpg : T;
   const int64_t t1 = t0 + tpg < T ? t0 + tpg : T;
   float av[NS], ga[NS];
@@ -178,8 +158,7 @@ __global__ __launch_bounds__(kV2NT) void k_gatv2_bwd(const int64_t* __restrict__
         if (grad_xl) unsafeAtomicAdd(grad_xl + j * D + lane + lpt * i, a[i / SPH] * gv[i] + tt);
       }
     }
-#pragma unroll
-    for (int i = 0; i < NS; ++i) grad_xr[t * D + lane + lpt * i] = gr[i];
+    bwd_store_row(grad_xr, t, lane, lpt, gr);
   }
   // grad_att: the groups of a wavefront hold the same columns (lpt < 64), then the wavefronts of the workgroup
   const int wl = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
@@ -195,7 +174,7 @@ __global__ __launch_bounds__(kV2NT) void k_gatv2_bwd(const int64_t* __restrict__
     for (int i = 0; i < NS; ++i) {
       float s = 0.f;
 #pragma unroll
-      for (int w = 0; w < kV2NT / kWave; ++w) s += red[w][i][threadIdx.x];
+      for (int w = 0; w < kAttnNT / kWave; ++w) s += red[w][i][threadIdx.x];
       unsafeAtomicAdd(grad_att + threadIdx.x + lpt * i, s);
     }
   }
@@ -206,16 +185,8 @@ __global__ __launch_bounds__(kV2NT) void k_gatv2_bwd(const int64_t* __restrict__
 using namespace spp;
 using namespace spp::gatv2;
 
-// The checks of both entries, in the order include/spp.h documents: descriptor, head count, element code, C, D, sizes
-// (T == 0 is decided by the caller right after), strides, NULL buffers, alignment.  Nothing here touches the device.
-static spp_status gatv2_check_shape(const spp_gatv2_desc* d, const char* who) {
-  SPP_REQUIRE(d != nullptr, "%s: NULL descriptor", who);
-  SPP_TRY(check_heads(who, d->heads));
-  SPP_REQUIRE(elem_ok(d->x_elem), "%s: unknown element code %d", who, (int)d->x_elem);
-  SPP_TRY(check_channels(who, d->heads, d->C));
-  SPP_REQUIRE(d->num_targets >= 0 && d->num_sources >= d->num_targets, "%s: needs 0 <= T <= S", who);
-  return SPP_OK;
-}
+// The row checks of both entries, after attn_train.hip.h's shape check and the T == 0 decision, in the order include/spp.h
+// documents: strides, NULL buffers, alignment.  Nothing here touches the device.
 static spp_status gatv2_check_rows(const spp_gatv2_desc* d, const char* who) {
   const int64_t D = d->heads * d->C, esz = elem_bytes(d->x_elem);
   SPP_REQUIRE(d->x_l_stride_elems >= D && d->x_r_stride_elems >= D && d->x_l_stride_elems % 4 == 0 &&
@@ -230,85 +201,56 @@ static spp_status gatv2_check_rows(const spp_gatv2_desc* d, const char* who) {
   return SPP_OK;
 }
 
-// Attention dropout of the spp_gatv2_*_drop entries (spp.h f3x): AttnDrop (act_keep.hip.h), checked right after the
-// shape, before the T == 0 return and the rows.
+// attn_entry checks the _drop entries' AttnDrop (spp.h f3x) right after the shape, before the T == 0 return and the rows
 static spp_status gatv2_forward(const spp_gatv2_desc* d, void* stream, const char* who, const AttnDrop& dr) {
-  SPP_TRY(gatv2_check_shape(d, who));
-  SPP_TRY(attn_drop_check(dr, who));
-  if (d->num_targets == 0) return SPP_OK;
-  SPP_TRY(gatv2_check_rows(d, who));
-  const int64_t T = d->num_targets;
-  const Shape sh = shape_of(d->heads, d->C);
-  const int lpr_log2 = sh.lpr_log2, seg_log2 = sh.seg_log2, g_log2 = sh.g_log2, nq = sh.nq, cph = sh.cph;
-  const unsigned grid = (unsigned)ceil_div(T << lpr_log2, kV2NT);
-  const ActArgs da = dr.args();
-  with_elem(d->x_elem, [&](auto tin) {
-    with_fwd_shape(nq, cph, [&](auto q, auto c) {
-      with_drop(dr.on(), [&](auto drop) {
-        using Tin = typename decltype(tin)::type;
-        hipLaunchKernelGGL((k_gatv2_fwd<Tin, decltype(q)::value, decltype(c)::value, decltype(drop)::value>),
-                           dim3(grid), dim3(kV2NT), 0, as_stream(stream), d->rowptr_dev, d->col_dev, T,
-                           static_cast<const Tin*>(d->x_l_dev), d->x_l_stride_elems,
-                           static_cast<const Tin*>(d->x_r_dev), d->x_r_stride_elems, d->att_dev, d->negative_slope,
-                           lpr_log2, seg_log2, g_log2, (int)d->heads, d->out_dev, d->row_max_dev, d->row_sum_dev, da);
-      });
+  return attn_entry(d, who, dr, [&] { return gatv2_check_rows(d, who); }, [&] {
+    dispatch_fwd(d->x_elem, d->heads, d->C, dr.on(), [&](auto tin, auto q, auto c, auto drop, const Shape& sh) {
+      using Tin = typename decltype(tin)::type;
+      hipLaunchKernelGGL((k_gatv2_fwd<Tin, decltype(q)::value, decltype(c)::value, decltype(drop)::value>),
+                         dim3(grid_of(d->num_targets, sh.lpr_log2)), dim3(kAttnNT), 0, as_stream(stream), d->rowptr_dev,
+                         d->col_dev, d->num_targets, static_cast<const Tin*>(d->x_l_dev), d->x_l_stride_elems,
+                         static_cast<const Tin*>(d->x_r_dev), d->x_r_stride_elems, d->att_dev, d->negative_slope,
+                         sh.lpr_log2, sh.seg_log2, sh.g_log2, (int)d->heads, d->out_dev, d->row_max_dev, d->row_sum_dev,
+                         dr.args());
     });
   });
-  SPP_HIP_TRY(hipGetLastError());
-  return SPP_OK;
 }
 
+// grad_att is checked first and zeroed whatever T is: with T == 0 it is the whole answer
 static spp_status gatv2_backward(const spp_gatv2_desc* d, void* stream, const char* who, const AttnDrop& dr) {
-  SPP_TRY(gatv2_check_shape(d, who));
-  SPP_TRY(attn_drop_check(dr, who));
-  const int64_t T = d->num_targets, D = d->heads * d->C;
-  SPP_REQUIRE(d->grad_att_dev && aligned_to(d->grad_att_dev, 16), "%s: NULL or misaligned grad_att", who);
-  if (T > 0) {
+  hipStream_t st = as_stream(stream);
+  auto rows = [&]() -> spp_status {
     SPP_TRY(gatv2_check_rows(d, who));
     SPP_REQUIRE(d->grad_out_dev && d->grad_x_r_dev, "%s: NULL buffer", who);
     SPP_REQUIRE(aligned_to(d->grad_out_dev, 16) && aligned_to(d->grad_x_r_dev, 16) && aligned_to(d->grad_x_l_dev, 16),
                 "%s: misaligned buffer (grad_out, grad_x_l, grad_x_r: 16 bytes)", who);
-  }
-  hipStream_t st = as_stream(stream);
-  SPP_HIP_TRY(hipMemsetAsync(d->grad_att_dev, 0, sizeof(float) * (size_t)D, st));
-  if (T == 0) return SPP_OK;
-  const int lpt_log2 = log2_of(std::min<int64_t>(D, kWave)), lpt = 1 << lpt_log2;
-  const int ns = (int)(D / lpt), sph = (int)std::max<int64_t>(1, d->C / kWave);
-  const int seg_log2 = log2_of(std::min<int64_t>(d->C, lpt)), c_log2 = log2_of(d->C);
-  // every workgroup ends in D atomics onto the same addresses: about 1024 workgroups, whatever T is
-  const int64_t gpb = kV2NT / lpt;
-  const int64_t tpg = std::max<int64_t>(1, ceil_div(T, 1024 * gpb));
-  const unsigned grid = (unsigned)ceil_div(ceil_div(T, tpg), gpb);
-  const ActArgs da = dr.args();
-  with_elem(d->x_elem, [&](auto tin) {
-    with_bwd_shape(ns, sph, [&](auto n, auto s) {
-      with_drop(dr.on(), [&](auto drop) {
-        using Tin = typename decltype(tin)::type;
-        hipLaunchKernelGGL((k_gatv2_bwd<Tin, decltype(n)::value, decltype(s)::value, decltype(drop)::value>),
-                           dim3(grid), dim3(kV2NT), 0, st, d->rowptr_dev, d->col_dev, T,
-                           static_cast<const Tin*>(d->x_l_dev), d->x_l_stride_elems,
-                           static_cast<const Tin*>(d->x_r_dev), d->x_r_stride_elems, d->att_dev, d->negative_slope,
-                           lpt_log2, seg_log2, c_log2, (int)d->heads, d->out_dev, d->row_max_dev, d->row_sum_dev,
-                           d->grad_out_dev, tpg, d->grad_x_l_dev, d->grad_x_r_dev, d->grad_att_dev, da);
-      });
+    return SPP_OK;
+  };
+  auto launch = [&] {
+    dispatch_bwd(d->x_elem, d->heads, d->C, dr.on(), [&](auto tin, auto n, auto s, auto drop, const BwdShape& sh) {
+      using Tin = typename decltype(tin)::type;
+      // every workgroup ends in D atomics onto the same addresses: about 1024 workgroups, whatever T is
+      const int64_t T = d->num_targets, gpb = kAttnNT >> sh.lpt_log2;
+      const int64_t tpg = std::max<int64_t>(1, ceil_div(T, 1024 * gpb));
+      hipLaunchKernelGGL((k_gatv2_bwd<Tin, decltype(n)::value, decltype(s)::value, decltype(drop)::value>),
+                         dim3((unsigned)ceil_div(ceil_div(T, tpg), gpb)), dim3(kAttnNT), 0, st, d->rowptr_dev,
+                         d->col_dev, T, static_cast<const Tin*>(d->x_l_dev), d->x_l_stride_elems,
+                         static_cast<const Tin*>(d->x_r_dev), d->x_r_stride_elems, d->att_dev, d->negative_slope,
+                         sh.lpt_log2, sh.seg_log2, sh.c_log2, (int)d->heads, d->out_dev, d->row_max_dev, d->row_sum_dev,
+                         d->grad_out_dev, tpg, d->grad_x_l_dev, d->grad_x_r_dev, d->grad_att_dev, dr.args());
     });
-  });
-  SPP_HIP_TRY(hipGetLastError());
-  return SPP_OK;
+  };
+  return attn_entry(
+      d, who, dr, rows, launch,
+      [&]() -> spp_status {
+        SPP_REQUIRE(d->grad_att_dev && aligned_to(d->grad_att_dev, 16), "%s: NULL or misaligned grad_att", who);
+        return SPP_OK;
+      },
+      [&]() -> spp_status {
+        SPP_HIP_TRY(hipMemsetAsync(d->grad_att_dev, 0, sizeof(float) * (size_t)(d->heads * d->C), st));
+        return SPP_OK;
+      });
 }
 
-extern "C" spp_status spp_gatv2_forward(const spp_gatv2_desc* d, void* stream) {
-  return gatv2_forward(d, stream, "spp_gatv2_forward", AttnDrop{});
-}
-extern "C" spp_status spp_gatv2_backward(const spp_gatv2_desc* d, void* stream) {
-  return gatv2_backward(d, stream, "spp_gatv2_backward", AttnDrop{});
-}
-// with attention dropout (spp.h f3x): (p, training, seed) after `stream`
-extern "C" spp_status spp_gatv2_forward_drop(const spp_gatv2_desc* d, void* stream, float p, int32_t training,
-                                             uint64_t seed) {
-  return gatv2_forward(d, stream, "spp_gatv2_forward_drop", AttnDrop{true, p, training, seed});
-}
-extern "C" spp_status spp_gatv2_backward_drop(const spp_gatv2_desc* d, void* stream, float p, int32_t training,
-                                              uint64_t seed) {
-  return gatv2_backward(d, stream, "spp_gatv2_backward_drop", AttnDrop{true, p, training, seed});
-}
+SPP_ATTN_ENTRIES(spp_gatv2_forward, spp_gatv2_forward_drop, spp_gatv2_desc, gatv2_forward)
+SPP_ATTN_ENTRIES(spp_gatv2_backward, spp_gatv2_backward_drop, spp_gatv2_desc, gatv2_backward)

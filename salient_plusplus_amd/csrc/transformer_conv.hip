@@ -13,6 +13,7 @@
 // instantiation of the same two kernels: the keep rule of f3t without self-loop draws, the mask never in the softmax.
 // Not here: edge features.  The kernels over the resident graph are graph_transformer.hip's; the forward's per-entry
 // body is shared with them (transformer_core.hip.h).
+#include "attn_train.hip.h"
 #include "transformer_core.hip.h"
 
 #include <cmath>
@@ -21,8 +22,6 @@ namespace spp {
 
 using namespace gatv2;
 using namespace transformer;
-
-constexpr int kTfNT = 256;
 
 // THE LOGIT'S SUMMATION TREE (transformer_core.hip.h states it, with piece4 and the forward's walk) is walked bit for bit
 // by both kernels: the backward recomputes alpha = expf(e - row_max) / row_sum from the forward's e.
@@ -34,22 +33,18 @@ constexpr int kTfNT = 256;
 // No atomics: the same bits in every run.
 // kDrop: out[i,h,:] = sum_j d_ij^h alpha_ij^h v[j,h,:], d = keep / (1 - p) per (entry, head) by the keep rule of f3t
 // (entry k for CSR entry k, no self loop).  The softmax runs over ALL entries -- row_max and row_sum are the
-// kDrop = false bits -- and only acc skips a dropped entry.  The lane's head hl is global head
-// ((hl * CPH) * lpr + lane) >> g_log2, the expression that finds row_max's head below.
+// kDrop = false bits -- and only acc skips a dropped entry.  fwd_drop_heads finds the global head of the lane's head hl.
 template <typename Tin, int NQ, int CPH, bool kDrop>
-__global__ __launch_bounds__(kTfNT) void k_transformer_fwd(const int64_t* __restrict__ rowptr,
-                                                           const int64_t* __restrict__ col, int64_t T, const Tin* qm,
-                                                           int64_t q_stride, const Tin* km, int64_t k_stride,
-                                                           const Tin* vm, int64_t v_stride, float scale, int lpr_log2,
-                                                           int seg_log2, int g_log2, int H, float* __restrict__ out,
-                                                           float* __restrict__ row_max, float* __restrict__ row_sum,
-                                                           [[maybe_unused]] ActArgs drop) {
+__global__ __launch_bounds__(kAttnNT) void k_transformer_fwd(
+    const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col, int64_t T, const Tin* qm, int64_t q_stride,
+    const Tin* km, int64_t k_stride, const Tin* vm, int64_t v_stride, float scale, int lpr_log2, int seg_log2,
+    int g_log2, int H, float* __restrict__ out, float* __restrict__ row_max, float* __restrict__ row_sum,
+    [[maybe_unused]] ActArgs drop) {
 #pragma clang fp contract(off)
   constexpr int NB = tf_nb<NQ>();
   const int lpr = 1 << lpr_log2, lane = threadIdx.x & (lpr - 1);
-  const int64_t t = ((int64_t)blockIdx.x * kTfNT + threadIdx.x) >> lpr_log2;
+  const int64_t t = ((int64_t)blockIdx.x * kAttnNT + threadIdx.x) >> lpr_log2;
   if (t >= T) return;  // whole groups leave together (the shuffles below stay inside a group)
-  const int64_t D = (int64_t)NQ * lpr * 4;
   int64_t c0[NQ];
   f4 qv[NQ];
 #pragma unroll
@@ -61,57 +56,13 @@ __global__ __launch_bounds__(kTfNT) void k_transformer_fwd(const int64_t* __rest
   st.clear();
   const int64_t b = rowptr[t], e = rowptr[t + 1];
   if constexpr (kDrop) {
-    constexpr int HL = NQ / CPH;
-    Drop<HL> dr;
-    dr.a = drop, dr.H = H;
-#pragma unroll
-    for (int hl = 0; hl < HL; ++hl) dr.head[hl] = ((hl * CPH) * lpr + lane) >> g_log2;
+    Drop<NQ / CPH> dr;
+    fwd_drop_heads<CPH>(dr, drop, H, lpr, lane, g_log2);
     walk<NB, true>(st, qv, c0, km, k_stride, vm, v_stride, col, b, e, (int64_t)-1, scale, seg_log2, &dr);
   } else {
     walk<NB>(st, qv, c0, km, k_stride, vm, v_stride, col, b, e, (int64_t)-1, scale, seg_log2);  // (an MFG hop: ids as they are)
   }
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) {
-    const int hl = q / CPH;
-    const int p = q * lpr + lane;
-    const bool empty = st.ss[hl] == 0.f;  // a row without entries: out, row_max and row_sum are 0, nothing is divided
-    f4 r = {0.f, 0.f, 0.f, 0.f};
-    if (!empty) r = st.template result<kDrop>(q, drop.scale);  // kDrop: acc * (drop_scale / ss)
-    *reinterpret_cast<float4*>(out + t * D + (int64_t)p * 4) = make_float4(r.x, r.y, r.z, r.w);
-    if ((p & ((1 << g_log2) - 1)) == 0) {  // the head's first piece
-      row_max[t * H + (p >> g_log2)] = empty ? 0.f : st.mm[hl];
-      row_sum[t * H + (p >> g_log2)] = st.ss[hl];
-    }
-  }
-}
-
-// The backward's draw of (entry, head): attn_keep_head(entry, H, head, a), for every argument.  kWaveHash (NS >= 4, so
-// D >= 256: lpt = 64, a wavefront is ONE target, and C >= 32, so the two heads that share a hash sit in the same step of
-// every lane): entry and head & ~1 are the same in all lanes, so the hash's argument is taken from the first lane and
-// the 64-bit mix runs once per wavefront on the scalar unit; only the choice of the hash's half stays per lane.  Left
-// on the vector unit, four hashes in flight cost <*, 4, 1> two waves per SIMD.
-// What kWaveHash relies on, all of it given by NS >= 4 and the entries' shape checks (check_heads, check_channels):
-//   lpt == 64, so the 64 lanes of a wavefront are ONE group, one target, one entry k at a time, and they leave the
-//     kernel together (t >= T): the first active lane's entry is every lane's;
-//   C >= 32 (H <= 8 and D >= 256), so head & ~1 = ((lane + 64 * hl * SPH) >> c_log2) & ~1 does not depend on the lane:
-//     C = 32: head = 2 hl + (lane >> 5); C = 64: head = hl; C >= 128: SPH = C / 64 and head = hl;
-//   H == 1 or H even (check_heads: 1, 2, 4, 8): the line that forms i2 says where.  An odd H > 1 would need
-//     (entry * H + head) >> 1 with the lane's own head, which is not uniform.
-template <bool kWaveHash>
-__device__ __forceinline__ bool bwd_keep(uint64_t entry, int H, int head, const ActArgs& a) {
-  if constexpr (!kWaveHash) {
-    return attn_keep_head(entry, H, head, a);
-  } else {
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)entry);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(entry >> 32));
-    const uint32_t he = __builtin_amdgcn_readfirstlane((uint32_t)head & ~1u);
-    // i = entry * H + head.  H even: entry * H is even, so i >> 1 = (entry * H + (head & ~1)) >> 1; H = 1: head = 0 and
-    // i >> 1 = entry >> 1.  Holds for H in {1, even} ONLY (check_heads admits 1, 2, 4, 8)
-    const uint64_t i2 = ((((uint64_t)hi << 32) | lo) * (uint64_t)H + he) >> 1;
-    const uint64_t r = mix64(a.seed + i2 * 0x9E3779B97F4A7C15ull);
-    const bool odd = (((uint32_t)entry * (uint32_t)H + (uint32_t)head) & 1u) != 0;
-    return (uint32_t)(odd ? r >> 32 : r) < a.keep_thr;
-  }
+  fwd_store<kDrop, true>(st, t, lpr, lane, g_log2, H, drop.scale, out, row_max, row_sum);
 }
 
 // Backward.  ONE column per lane and step, c = lane + lpt * i, i < NS, lpt = min(64, D) lanes per target, as k_gatv2_bwd:
@@ -125,27 +76,22 @@ __device__ __forceinline__ bool bwd_keep(uint64_t entry, int H, int head, const 
 // kDrop (the forward's (p, seed)): go is taken on the saved DROPPED out, so sum_j d alpha gh = go and
 // ge = alpha (d gh - go) is the softmax gradient again -- a dropped entry (d = 0) still sends -alpha go to its logit --
 // and grad_v[j] takes d alpha g_i.  d = keep ? 1 / (1 - p) : 0 per (entry, head), the forward's draws: the lane's head
-// hl is global head (lane + lpt * hl * SPH) >> c_log2.  The draw is bwd_keep above: for NS < 4 every lane hashes for
-// the heads it holds (attn_keep_head); from NS = 4 on the hash runs once per wavefront on the first lane's argument and
-// a lane only picks its half of it.
+// hl is global head (lane + lpt * hl * SPH) >> c_log2.  The draw is attn_train.hip.h's bwd_keep: for NS < 4 every lane
+// hashes for the heads it holds (attn_keep_head); from NS = 4 on the hash runs once per wavefront on the first lane's
+// argument and a lane only picks its half of it.
 template <typename Tin, int NS, int SPH, bool kDrop>
-__global__ __launch_bounds__(kTfNT) void k_transformer_bwd(const int64_t* __restrict__ rowptr,
-                                                           const int64_t* __restrict__ col, int64_t T, const Tin* qm,
-                                                           int64_t q_stride, const Tin* km, int64_t k_stride,
-                                                           const Tin* vm, int64_t v_stride, float scale, int lpt_log2,
-                                                           int seg_log2, int c_log2, int H,
-                                                           const float* __restrict__ out,
-                                                           const float* __restrict__ row_max,
-                                                           const float* __restrict__ row_sum,
-                                                           const float* __restrict__ g, float* __restrict__ grad_q,
-                                                           float* grad_k, float* grad_v,
-                                                           [[maybe_unused]] ActArgs drop) {
+__global__ __launch_bounds__(kAttnNT) void k_transformer_bwd(
+    const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col, int64_t T, const Tin* qm, int64_t q_stride,
+    const Tin* km, int64_t k_stride, const Tin* vm, int64_t v_stride, float scale, int lpt_log2, int seg_log2,
+    int c_log2, int H, const float* __restrict__ out, const float* __restrict__ row_max,
+    const float* __restrict__ row_sum, const float* __restrict__ g, float* __restrict__ grad_q, float* grad_k,
+    float* grad_v, [[maybe_unused]] ActArgs drop) {
 #pragma clang fp contract(off)
   constexpr int HL = NS / SPH;
   const int lpt = 1 << lpt_log2;
   const int lane = threadIdx.x & (lpt - 1);
   const int64_t D = (int64_t)NS * lpt;
-  const int64_t t = ((int64_t)blockIdx.x * kTfNT + threadIdx.x) >> lpt_log2;
+  const int64_t t = ((int64_t)blockIdx.x * kAttnNT + threadIdx.x) >> lpt_log2;
   if (t >= T) return;  // whole groups leave together
   const int64_t b = rowptr[t], e = rowptr[t + 1];
   float gv[NS], qv[NS], gq[NS], go[HL], m[HL], inv_s[HL];
@@ -231,8 +177,7 @@ __global__ __launch_bounds__(kTfNT) void k_transformer_bwd(const int64_t* __rest
       if (grad_v) unsafeAtomicAdd(grad_v + j * D + lane + lpt * i, a[i / SPH] * gv[i]);
     }
   }
-#pragma unroll
-  for (int i = 0; i < NS; ++i) grad_q[t * D + lane + lpt * i] = gq[i];
+  bwd_store_row(grad_q, t, lane, lpt, gq);
 }
 
 }  // namespace spp
@@ -240,17 +185,8 @@ __global__ __launch_bounds__(kTfNT) void k_transformer_bwd(const int64_t* __rest
 using namespace spp;
 using namespace spp::gatv2;
 
-// The checks of both entries, in the order include/spp.h documents: descriptor, head count, element code, C, power of
-// two, D, sizes (T == 0 is decided by the caller right after), strides, NULL buffers, alignment, scale.  Nothing here
-// touches the device.
-static spp_status tf_check_shape(const spp_transformer_desc* d, const char* who) {
-  SPP_REQUIRE(d != nullptr, "%s: NULL descriptor", who);
-  SPP_TRY(check_heads(who, d->heads));
-  SPP_REQUIRE(elem_ok(d->x_elem), "%s: unknown element code %d", who, (int)d->x_elem);
-  SPP_TRY(check_channels(who, d->heads, d->C));
-  SPP_REQUIRE(d->num_targets >= 0 && d->num_sources >= d->num_targets, "%s: needs 0 <= T <= S", who);
-  return SPP_OK;
-}
+// The row checks of both entries, after attn_train.hip.h's shape check and the T == 0 decision, in the order include/spp.h
+// documents: strides, NULL buffers, alignment, scale.  Nothing here touches the device.
 static spp_status tf_check_rows(const spp_transformer_desc* d, const char* who, bool backward) {
   const int64_t D = d->heads * d->C, esz = elem_bytes(d->x_elem);
   SPP_REQUIRE(d->q_stride_elems >= D && d->k_stride_elems >= D && d->v_stride_elems >= D &&
@@ -270,74 +206,36 @@ static spp_status tf_check_rows(const spp_transformer_desc* d, const char* who, 
   return SPP_OK;
 }
 
-// Attention dropout of the spp_transformer_*_drop entries (spp.h f4a): AttnDrop (act_keep.hip.h), checked right after
-// the shape, before the T == 0 return and the rows, in eval mode too.
+// attn_entry checks the _drop entries' AttnDrop (spp.h f4a) right after the shape, before T == 0, in eval mode too
 static spp_status tf_forward(const spp_transformer_desc* d, void* stream, const char* who, const AttnDrop& dr) {
-  SPP_TRY(tf_check_shape(d, who));
-  SPP_TRY(attn_drop_check(dr, who));
-  if (d->num_targets == 0) return SPP_OK;
-  SPP_TRY(tf_check_rows(d, who, false));
-  const int64_t T = d->num_targets;
-  const Shape sh = shape_of(d->heads, d->C);
-  const int lpr_log2 = sh.lpr_log2, seg_log2 = sh.seg_log2, g_log2 = sh.g_log2, nq = sh.nq, cph = sh.cph;
-  const unsigned grid = (unsigned)ceil_div(T << lpr_log2, kTfNT);
-  const ActArgs da = dr.args();
-  with_elem(d->x_elem, [&](auto tin) {
-    with_fwd_shape(nq, cph, [&](auto q, auto c) {
-      with_drop(dr.on(), [&](auto drop) {
-        using Tin = typename decltype(tin)::type;
-        hipLaunchKernelGGL((k_transformer_fwd<Tin, decltype(q)::value, decltype(c)::value, decltype(drop)::value>),
-                           dim3(grid), dim3(kTfNT), 0, as_stream(stream), d->rowptr_dev, d->col_dev, T,
-                           static_cast<const Tin*>(d->q_dev), d->q_stride_elems, static_cast<const Tin*>(d->k_dev),
-                           d->k_stride_elems, static_cast<const Tin*>(d->v_dev), d->v_stride_elems, d->scale, lpr_log2,
-                           seg_log2, g_log2, (int)d->heads, d->out_dev, d->row_max_dev, d->row_sum_dev, da);
-      });
+  return attn_entry(d, who, dr, [&] { return tf_check_rows(d, who, false); }, [&] {
+    dispatch_fwd(d->x_elem, d->heads, d->C, dr.on(), [&](auto tin, auto q, auto c, auto drop, const Shape& sh) {
+      using Tin = typename decltype(tin)::type;
+      hipLaunchKernelGGL((k_transformer_fwd<Tin, decltype(q)::value, decltype(c)::value, decltype(drop)::value>),
+                         dim3(grid_of(d->num_targets, sh.lpr_log2)), dim3(kAttnNT), 0, as_stream(stream), d->rowptr_dev,
+                         d->col_dev, d->num_targets, static_cast<const Tin*>(d->q_dev), d->q_stride_elems,
+                         static_cast<const Tin*>(d->k_dev), d->k_stride_elems, static_cast<const Tin*>(d->v_dev),
+                         d->v_stride_elems, d->scale, sh.lpr_log2, sh.seg_log2, sh.g_log2, (int)d->heads, d->out_dev,
+                         d->row_max_dev, d->row_sum_dev, dr.args());
     });
   });
-  SPP_HIP_TRY(hipGetLastError());
-  return SPP_OK;
 }
 
+// T == 0: nothing is touched, grad_k / grad_v stay as the caller zeroed them
 static spp_status tf_backward(const spp_transformer_desc* d, void* stream, const char* who, const AttnDrop& dr) {
-  SPP_TRY(tf_check_shape(d, who));
-  SPP_TRY(attn_drop_check(dr, who));
-  if (d->num_targets == 0) return SPP_OK;  // nothing is touched: grad_k / grad_v stay as the caller zeroed them
-  SPP_TRY(tf_check_rows(d, who, true));
-  const int64_t T = d->num_targets, D = d->heads * d->C;
-  const int lpt_log2 = log2_of(std::min<int64_t>(D, kWave)), lpt = 1 << lpt_log2;
-  const int ns = (int)(D / lpt), sph = (int)std::max<int64_t>(1, d->C / kWave);
-  const int seg_log2 = log2_of(std::min<int64_t>(d->C, lpt)), c_log2 = log2_of(d->C);
-  const unsigned grid = (unsigned)ceil_div(T << lpt_log2, kTfNT);
-  const ActArgs da = dr.args();
-  with_elem(d->x_elem, [&](auto tin) {
-    with_bwd_shape(ns, sph, [&](auto n, auto s) {
-      with_drop(dr.on(), [&](auto drop) {
-        using Tin = typename decltype(tin)::type;
-        hipLaunchKernelGGL((k_transformer_bwd<Tin, decltype(n)::value, decltype(s)::value, decltype(drop)::value>),
-                           dim3(grid), dim3(kTfNT), 0, as_stream(stream), d->rowptr_dev, d->col_dev, T,
-                           static_cast<const Tin*>(d->q_dev), d->q_stride_elems, static_cast<const Tin*>(d->k_dev),
-                           d->k_stride_elems, static_cast<const Tin*>(d->v_dev), d->v_stride_elems, d->scale, lpt_log2,
-                           seg_log2, c_log2, (int)d->heads, d->out_dev, d->row_max_dev, d->row_sum_dev, d->grad_out_dev,
-                           d->grad_q_dev, d->grad_k_dev, d->grad_v_dev, da);
-      });
+  return attn_entry(d, who, dr, [&] { return tf_check_rows(d, who, true); }, [&] {
+    dispatch_bwd(d->x_elem, d->heads, d->C, dr.on(), [&](auto tin, auto n, auto s, auto drop, const BwdShape& sh) {
+      using Tin = typename decltype(tin)::type;
+      hipLaunchKernelGGL((k_transformer_bwd<Tin, decltype(n)::value, decltype(s)::value, decltype(drop)::value>),
+                         dim3(grid_of(d->num_targets, sh.lpt_log2)), dim3(kAttnNT), 0, as_stream(stream), d->rowptr_dev,
+                         d->col_dev, d->num_targets, static_cast<const Tin*>(d->q_dev), d->q_stride_elems,
+                         static_cast<const Tin*>(d->k_dev), d->k_stride_elems, static_cast<const Tin*>(d->v_dev),
+                         d->v_stride_elems, d->scale, sh.lpt_log2, sh.seg_log2, sh.c_log2, (int)d->heads, d->out_dev,
+                         d->row_max_dev, d->row_sum_dev, d->grad_out_dev, d->grad_q_dev, d->grad_k_dev, d->grad_v_dev,
+                         dr.args());
     });
   });
-  SPP_HIP_TRY(hipGetLastError());
-  return SPP_OK;
 }
 
-extern "C" spp_status spp_transformer_forward(const spp_transformer_desc* d, void* stream) {
-  return tf_forward(d, stream, "spp_transformer_forward", AttnDrop{});
-}
-extern "C" spp_status spp_transformer_backward(const spp_transformer_desc* d, void* stream) {
-  return tf_backward(d, stream, "spp_transformer_backward", AttnDrop{});
-}
-// with attention dropout (spp.h f4a): (p, training, seed) after `stream`
-extern "C" spp_status spp_transformer_forward_drop(const spp_transformer_desc* d, void* stream, float p,
-                                                   int32_t training, uint64_t seed) {
-  return tf_forward(d, stream, "spp_transformer_forward_drop", AttnDrop{true, p, training, seed});
-}
-extern "C" spp_status spp_transformer_backward_drop(const spp_transformer_desc* d, void* stream, float p,
-                                                    int32_t training, uint64_t seed) {
-  return tf_backward(d, stream, "spp_transformer_backward_drop", AttnDrop{true, p, training, seed});
-}
+SPP_ATTN_ENTRIES(spp_transformer_forward, spp_transformer_forward_drop, spp_transformer_desc, tf_forward)
+SPP_ATTN_ENTRIES(spp_transformer_backward, spp_transformer_backward_drop, spp_transformer_desc, tf_backward)
