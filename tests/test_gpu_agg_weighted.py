@@ -224,7 +224,7 @@ def test_backward(F, dtype):
                     assert gs.dtype == torch.float32
                     within(gs, want_gs, b_gs)
                 gx2, gw2, gs2 = _grads(xs, T, S, self_w, g.cuda())
-                assert same(gw, gw2) and (not self_w or same(gs, gs2))                  # run to run
+                assert same(gx, gx2) and same(gw, gw2) and (not self_w or same(gs, gs2))   # run to run
 
 
 def test_backward_under_bf16_autocast_and_only_the_gradients_asked_for():
