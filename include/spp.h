@@ -2130,6 +2130,73 @@ spp_status spp_transformer_forward_drop(const spp_transformer_desc* desc, void* 
 spp_status spp_transformer_backward_drop(const spp_transformer_desc* desc, void* stream, float p, int32_t training,
                                          uint64_t seed);
 
+/* ------------------------------------------------------------------------- *
+ * f4b  MEAN / MIN / MAX / STD of an MFG hop's neighbour rows in ONE pass, times degree scalers: the message passing of
+ *      PNAConv (Principal Neighbourhood Aggregation), forward and backward, on one descriptor.  Nothing older changes.
+ *
+ *   spp_agg_stats_forward, for target t < T with the d = rowptr[t+1] - rowptr[t] entries k of its row, v_k = x[col[k]]
+ *   (x dense [S, F] fp32 / fp16 / bf16, unit column stride, read exactly), per column c, all in fp32, entries in CSR order:
+ *        K      = v of the row's FIRST entry                    s1 = sum_k (v_k - K)      s2 = sum_k (v_k - K)^2
+ *        mean_b = K + s1 / d                var = max(s2 / d - (s1 / d)^2, 0)             std = sqrt(var + eps)
+ *        min, max: the comparison rule of spp_agg_max_forward and its mirror image (a later entry wins only if strictly
+ *                  better or a NaN; a NaN held stays), kmin / kmax = the CSR POSITION k of the entry that won (int32) --
+ *                  not the source id: a row may list a source twice and the backward credits exactly one entry
+ *      The sums are SHIFTED by K: E[x^2] - E[x]^2 on the raw values loses every digit of a column like 1000 + noise.
+ *      Epilogue: with add_dev (fp32 [T, F] dense) the mean, min and max get add[t,c] added, the std does not; then for
+ *      every scaler enabled in the mask `scalers`, in the order identity (1: 1), amplification (2: log(d+1) / delta),
+ *      attenuation (4: delta / log(d+1)), the four blocks are multiplied by it:
+ *        out [T, n_scalers * 4 * F], row layout [scaler][mean | min | max | std][F]   (the column order of PyG's cat)
+ *      out_elem fp32 / bf16, one rounding per stored element.  An empty row writes zeros everywhere (add or not).
+ *      stats_dev (fp32 [T, 2F]: mean_b | std) and pos_dev (int32 [T, 2F]: kmin | kmax) are written when given -- both or
+ *      neither -- for the backward; an empty row gives 0 and -1.  One order of operations: two runs give the same bits.
+ *
+ *   spp_agg_stats_backward, target-major: with G_a[t,c] = sum_s scale_s(t) g[t, s, a, c] for a in {mean, min, max, std},
+ *      every entry k of row t sends ONE fp32 atomic per column to grad_x[col[k], c]:
+ *        G_mean / d + G_std (v_k - mean_b) / (d std) + [k == kmin] G_min + [k == kmax] G_max
+ *      grad_x is fp32 [S, F] dense and ZEROED BY THE CALLER (an entry naming a source outside [0, S) is skipped).
+ *      grad_add_dev (fp32 [T, F] dense, or NULL) = G_mean + G_min + G_max, a plain store; 0 for an empty row, which sends
+ *      nothing.  grad_elem fp32 / bf16; x, stats, pos, add's presence, scalers, delta, eps as in the forward.
+ *
+ *   The vector form is the only form: F % 4 == 0 and rows, out, add, grad_out, grad_x, grad_add, stats and pos aligned
+ *   to 4 elements.  No scalar form, no TABLE / ROWS / fp8 source: PNAConv aggregates projected rows, which are dense.
+ *   Refused with SPP_ERR_INVALID before anything is enqueued, in a message that names the entry, in this order: a NULL
+ *   descriptor; an unknown element code; a scaler mask outside [1, 7]; delta <= 0, eps < 0 or either not finite;
+ *   a negative size; E beyond 2^31 (positions are int32); F % 4 != 0; T * F or S * F out of range; a stride smaller
+ *   than its row.  T == 0 or F == 0: SPP_OK without a launch and without a look at the pointers.  Then: a NULL required
+ *   pointer (rowptr, out / grad_out; col and x unless E == 0; stats and pos backward, grad_x unless E == 0); stats
+ *   without pos; a row stride below F; a stride or pointer not aligned to 4 elements.
+ * ------------------------------------------------------------------------- */
+enum { SPP_SCALER_IDENTITY = 1, SPP_SCALER_AMPLIFICATION = 2, SPP_SCALER_ATTENUATION = 4 };
+
+typedef struct spp_agg_stats_desc {
+  int32_t x_elem;           /* spp_elem of x's rows: fp32 / fp16 / bf16 */
+  int32_t out_elem;         /* forward: SPP_ELEM_F32 / SPP_ELEM_BF16 */
+  int32_t grad_elem;        /* backward: grad_out, SPP_ELEM_F32 / SPP_ELEM_BF16 */
+  int32_t scalers;          /* mask of SPP_SCALER_* */
+  float delta;              /* > 0 */
+  float eps;                /* >= 0 */
+  const int64_t* rowptr_dev;
+  const int64_t* col_dev;
+  int64_t num_targets;
+  int64_t num_sources;
+  int64_t num_edges;
+  const void* x_dev;        /* [S, F] */
+  int64_t x_stride_elems;
+  int64_t F;
+  const float* add_dev;     /* fp32 [T, F] dense, or NULL */
+  void* out_dev;            /* forward: [T, n_scalers * 4 * F] */
+  int64_t out_stride_elems; /* 0 = dense */
+  float* stats_dev;         /* fp32 [T, 2F] dense: mean_b | std (forward: written if given; backward: read) */
+  int32_t* pos_dev;         /* int32 [T, 2F] dense: kmin | kmax */
+  const void* grad_out_dev; /* backward: [T, n_scalers * 4 * F] */
+  int64_t grad_out_stride_elems; /* 0 = dense */
+  float* grad_x_dev;        /* backward: fp32 [S, F] dense, zeroed by the caller */
+  float* grad_add_dev;      /* backward: fp32 [T, F] dense, or NULL */
+} spp_agg_stats_desc;
+
+spp_status spp_agg_stats_forward(const spp_agg_stats_desc* desc, void* stream);
+spp_status spp_agg_stats_backward(const spp_agg_stats_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

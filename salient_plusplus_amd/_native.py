@@ -97,6 +97,18 @@ class AggMaxBwdDesc(C.Structure):
                 ("F", i64), ("grad_x_dev", p), ("workspace_dev", p), ("workspace_bytes", i64)]
 
 
+SPP_SCALER_IDENTITY, SPP_SCALER_AMPLIFICATION, SPP_SCALER_ATTENUATION = 1, 2, 4
+
+
+class AggStatsDesc(C.Structure):
+    """spp_agg_stats_desc: mean / min / max / std of a hop's rows in one pass, times degree scalers (spp.h f4b)"""
+    _fields_ = [("x_elem", i32), ("out_elem", i32), ("grad_elem", i32), ("scalers", i32), ("delta", C.c_float),
+                ("eps", C.c_float), ("rowptr_dev", p), ("col_dev", p), ("num_targets", i64), ("num_sources", i64),
+                ("num_edges", i64), ("x_dev", p), ("x_stride_elems", i64), ("F", i64), ("add_dev", p), ("out_dev", p),
+                ("out_stride_elems", i64), ("stats_dev", p), ("pos_dev", p), ("grad_out_dev", p),
+                ("grad_out_stride_elems", i64), ("grad_x_dev", p), ("grad_add_dev", p)]
+
+
 class AggWeightedFwdDesc(C.Structure):
     """spp_agg_weighted_fwd_desc: out[t] = sum_k w[k] * x[col[k]] (+ self_w[t] * x[t], last), one fmaf per entry"""
     _fields_ = [("source", i32), ("x_elem", i32), ("out_elem", i32), ("reserved", i32), ("rowptr_dev", p),
@@ -432,6 +444,9 @@ SIGNATURES = {
     "spp_graph_transformer_chunk": (i64, []),
     "spp_graph_transformer_workspace_bytes": (i64, [i64]),
     "spp_graph_transformer_forward": (C.c_int, [C.POINTER(GraphTransformerDesc), p, i64, p]),
+    # mean / min / max / std in one pass (spp.h f4b)
+    "spp_agg_stats_forward": (C.c_int, [C.POINTER(AggStatsDesc), p]),
+    "spp_agg_stats_backward": (C.c_int, [C.POINTER(AggStatsDesc), p]),
 }
 SPP_COMM_ID_BYTES = 128
 SPP_IPC_HANDLE_BYTES = 64

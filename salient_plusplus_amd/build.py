@@ -9,11 +9,13 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libspp_hip.so")
-SOURCES = ["api.hip", "mt19937.hip", "gather.hip", "gather_fp8.hip", "sampler.hip", "partition.hip", "session.hip", "exchange.hip", "vip.hip", "aggregate.hip", "aggregate_max.hip", "aggregate_weighted.hip", "gat.hip", "gatv2.hip", "transformer_conv.hip",
+SOURCES = ["api.hip", "mt19937.hip", "gather.hip", "gather_fp8.hip", "sampler.hip", "partition.hip", "session.hip", "exchange.hip", "vip.hip", "aggregate.hip", "aggregate_max.hip", "aggregate_stats.hip", "aggregate_weighted.hip", "gat.hip", "gatv2.hip", "transformer_conv.hip",
            "graph_aggregate.hip", "graph_agg_weighted.hip", "graph_gat.hip", "graph_gatv2.hip", "graph_transformer.hip", "resinc_epilogue.hip", "classify.hip", "field.hip", "bn_act.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
          "-I" + CSRC, "-Wall", "-Wno-unused-function"] + os.environ.get("SPP_EXTRA_FLAGS", "").split()
+# per-source additions: aggregate_stats.hip is built without the packed fp32 instructions (v_pk_*_f32)
+SOURCE_FLAGS = {"aggregate_stats.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _stale(target, deps):
@@ -38,7 +40,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         s = os.path.join(CSRC, src)
         o = os.path.join(OBJ, src.replace(".hip", ".o"))
         if force or _stale(o, [s] + headers):
-            jobs.append([HIPCC] + FLAGS + ["-c", s, "-o", o])
+            jobs.append([HIPCC] + FLAGS + SOURCE_FLAGS.get(src, []) + ["-c", s, "-o", o])
 
     def run(cmd):
         if verbose:

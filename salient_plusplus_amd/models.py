@@ -1984,6 +1984,247 @@ class GCN(_LayerwiseInference, _ConvModel):
 
 
 # --------------------------------------------------------------------------------------------
+# mean / min / max / std in one pass, PNAConv and PNA  (csrc/aggregate_stats.hip, spp.h f4b; the reference has no PNA)
+# --------------------------------------------------------------------------------------------
+_SCALERS = {"identity": nat.SPP_SCALER_IDENTITY, "amplification": nat.SPP_SCALER_AMPLIFICATION,
+            "attenuation": nat.SPP_SCALER_ATTENUATION}
+_PNA_AGGREGATORS = ("mean", "min", "max", "std")
+
+
+def _scaler_mask(what, scalers):
+    """the kernels' bitmask; the blocks come in the fixed order identity, amplification, attenuation, so the names do too"""
+    names = tuple(scalers) if isinstance(scalers, (tuple, list)) else None
+    order = [s for s in _SCALERS if names and s in names]
+    if not names or list(names) != order:
+        raise ValueError(f"{what}: scalers must be a non-empty selection of {tuple(_SCALERS)} in that order, got {scalers!r}")
+    return sum(_SCALERS[s] for s in names)
+
+
+def _first_hit(xs, best, row, T, E):
+    """the CSR position [T, F] of the FIRST entry of every row whose value is `best` -- the first NaN where the column
+    holds one (spp_agg_max_forward's rule); E for an empty row"""
+    nan = xs.isnan()
+    any_nan = torch.zeros((T, xs.size(1)), dtype=torch.int32, device=xs.device).index_add(0, row, nan.int()) > 0
+    hit = torch.where(any_nan[row], nan, xs == best[row])
+    k = torch.arange(E, dtype=torch.float64, device=xs.device).unsqueeze(1).expand_as(xs)     # (exact: E < 2^53)
+    first = torch.full((T, xs.size(1)), float(E), dtype=torch.float64, device=xs.device)
+    return first.scatter_reduce(0, row.unsqueeze(1).expand_as(xs), torch.where(hit, k, float(E)), "amin").long()
+
+
+def _stats_reference(x, rowptr, col, T, *, add=None, scalers=("identity",), delta=1.0, eps=1e-5, with_pos=False):
+    """Plain torch restatement of spp_agg_stats_forward on a dense x, on x's device: [T, n_s * 4F], row layout
+    [scaler][mean + add | min + add | max + add | std][F] with std = sqrt(max(var, 0) + eps); an empty row gives zeros.
+    fp32 -- float64 when x is float64 -- with the mean and the variance in two passes; differentiable in x and add: the
+    minimum and the maximum send their gradient to the FIRST entry that attains them, by CSR position, so one of two
+    entries that name the same source.  with_pos: also (kmin, kmax) int64 [T, F], -1 for an empty row."""
+    mask = _scaler_mask("stats_aggregate", scalers)
+    dt = torch.float64 if x.dtype == torch.float64 else torch.float32
+    x = x.to(dt)
+    Fdim = x.size(1)
+    row, E = _entry_rows(rowptr, col, T)
+    deg = (rowptr[1:T + 1] - rowptr[:T]).to(dt).unsqueeze(1)
+    has = deg > 0
+    cnt = deg.clamp(min=1)
+    xs = x[col[:E]]                                                      # [E, F]: the gradient returns through here
+    zero = torch.zeros((T, Fdim), dtype=dt, device=x.device)
+    mean = zero.index_add(0, row, xs) / cnt
+    dev = xs - mean[row]
+    std = torch.sqrt((zero.index_add(0, row, dev * dev) / cnt).clamp(min=0) + eps)
+    with torch.no_grad():
+        rows = row.unsqueeze(1).expand(E, Fdim)
+        kmin = _first_hit(xs, zero.scatter_reduce(0, rows, xs, "amin", include_self=False), row, T, E)
+        kmax = _first_hit(xs, zero.scatter_reduce(0, rows, xs, "amax", include_self=False), row, T, E)
+    if E > 0:
+        mn, mx = xs.gather(0, kmin.clamp(max=E - 1)), xs.gather(0, kmax.clamp(max=E - 1))
+    else:
+        mn = mx = zero
+    if add is not None:
+        add = add.to(dt)
+        mean, mn, mx = mean + add, mn + add, mx + add
+    block = torch.where(has, torch.cat([mean, mn, mx, std], 1), torch.zeros((), dtype=dt, device=x.device))
+    logd = torch.log(cnt + 1)
+    scale = {nat.SPP_SCALER_IDENTITY: torch.ones_like(logd), nat.SPP_SCALER_AMPLIFICATION: logd / delta,
+             nat.SPP_SCALER_ATTENUATION: delta / logd}
+    out = torch.cat([block * s for bit, s in scale.items() if mask & bit], 1)
+    if with_pos:
+        none = torch.full_like(kmin, -1)
+        return out, torch.where(has, kmin, none), torch.where(has, kmax, none)
+    return out
+
+
+def _agg_stats_call(name, x, rowptr, col, T, mask, delta, eps, **fields):
+    d = nat.AggStatsDesc(x_elem=_ELEM[x.dtype], scalers=mask, delta=delta, eps=eps, rowptr_dev=_p(rowptr), col_dev=_p(col),
+                         num_targets=T, num_sources=x.size(0), num_edges=col.numel(), x_dev=_p(x),
+                         x_stride_elems=x.stride(0) if x.size(0) > 1 else x.size(1), F=x.size(1),
+                         **{k: (_p(v) if isinstance(v, torch.Tensor) or v is None else v) for k, v in fields.items()})
+    nat.check(getattr(nat.load(), name)(C.byref(d), _stream()))
+
+
+class _StatsAggregate(torch.autograd.Function):
+    """stats_aggregate as ONE node on csrc/aggregate_stats.hip: the forward reads every neighbour row once and keeps the
+    mean_b | std and kmin | kmax of each (target, column) for the backward, which walks the rows again and sends one fp32
+    atomic per (entry, column).  fp32 out (bf16 under bf16 autocast); grad_x comes back in x's dtype, grad_add in add's."""
+
+    @staticmethod
+    def forward(ctx, x, add, rowptr, col, T, mask, delta, eps, out_dtype):
+        nat.require_device()
+        Fdim = x.size(1)
+        width = 4 * Fdim * bin(mask).count("1")
+        out = torch.empty((T, width), dtype=out_dtype, device=x.device)
+        stats = pos = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            stats = torch.empty((T, 2 * Fdim), dtype=torch.float32, device=x.device)
+            pos = torch.empty((T, 2 * Fdim), dtype=torch.int32, device=x.device)
+        _agg_stats_call("spp_agg_stats_forward", x, rowptr, col, T, mask, delta, eps, out_elem=_ELEM[out.dtype],
+                        add_dev=add, out_dev=out, out_stride_elems=0, stats_dev=stats, pos_dev=pos)
+        ctx.save_for_backward(x, rowptr, col, stats, pos)
+        ctx.cfg = (T, mask, delta, eps, add.dtype if add is not None else None)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, rowptr, col, stats, pos = ctx.saved_tensors
+        T, mask, delta, eps, add_dtype = ctx.cfg
+        g = _grad_in(grad_out).contiguous()
+        grad_x = torch.zeros(x.shape, dtype=torch.float32, device=x.device)
+        want_add = add_dtype is not None and ctx.needs_input_grad[1]
+        grad_add = torch.empty((T, x.size(1)), dtype=torch.float32, device=x.device) if want_add else None
+        # add_dev only says whether the forward had one (the backward never reads it)
+        _agg_stats_call("spp_agg_stats_backward", x, rowptr, col, T, mask, delta, eps, grad_elem=_ELEM[g.dtype],
+                        stats_dev=stats, pos_dev=pos, grad_out_dev=g, grad_out_stride_elems=0, grad_x_dev=grad_x,
+                        grad_add_dev=grad_add)
+        return (_grad_back(grad_x, x, ctx.needs_input_grad[0]),
+                grad_add.to(add_dtype) if want_add else None, None, None, None, None, None, None, None)
+
+
+def _stats_kernels_read(x, add):
+    """what spp_agg_stats_forward accepts: dense fp32 / fp16 / bf16 rows on the GPU, F % 4 == 0, rows aligned to 4
+    elements (add is made fp32 and contiguous by the caller)"""
+    return (x.is_cuda and x.dtype in _ELEM and x.size(1) % 4 == 0 and x.size(1) > 0 and x.stride(1) == 1
+            and (x.size(0) <= 1 or x.stride(0) % 4 == 0) and x.data_ptr() % (4 * x.element_size()) == 0
+            and (add is None or add.dtype != torch.float64))
+
+
+def stats_aggregate(x, rowptr, col, num_targets, *, add=None, scalers=("identity",), delta=1.0, eps=1e-5):
+    """Mean, minimum, maximum and standard deviation of every target's neighbour rows, each times the chosen degree
+    scalers: ``[num_targets, n_s * 4F]`` laid out ``[scaler][mean | min | max | std][F]`` (PNAConv's aggregation, the
+    column order of PyG's ``DegreeScalerAggregation``).  ``std = sqrt(max(var, 0) + eps)``; ``scalers`` is a selection of
+    ("identity", "amplification", "attenuation") in that order: 1, ``log(d + 1) / delta``, ``delta / log(d + 1)`` with d
+    the row's length.  ``add`` [num_targets, F] is added to the mean, the minimum and the maximum (a per-target shift of
+    every message moves those three and leaves the spread alone).  An empty row gives zeros and receives no gradient.
+
+    Differentiable in ``x`` and ``add``; the minimum and the maximum credit the first entry that attains them.  Dense
+    fp32 / fp16 / bf16 rows on the GPU with ``F % 4 == 0`` take the HIP kernels (one autograd node; fp32 out, bf16 under
+    bf16 autocast); CPU tensors, float64, other widths and misaligned rows take the plain torch restatement."""
+    what = "stats_aggregate"
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or not x.is_floating_point():
+        raise ValueError(f"{what}: x must be a 2-D floating-point matrix")
+    _check_hop(what, rowptr, col, num_targets)
+    mask = _scaler_mask(what, scalers)
+    if not (isinstance(delta, (int, float)) and 0 < delta < float("inf")):
+        raise ValueError(f"{what}: delta must be a positive finite number, got {delta!r}")
+    if not (isinstance(eps, (int, float)) and 0 <= eps < float("inf")):
+        raise ValueError(f"{what}: eps must be a non-negative finite number, got {eps!r}")
+    if add is not None and (not isinstance(add, torch.Tensor) or tuple(add.shape) != (num_targets, x.size(1))
+                            or not add.is_floating_point() or add.device != x.device):
+        raise ValueError(f"{what}: add must be a floating-point [{num_targets}, {x.size(1)}] matrix on x's device")
+    if not _stats_kernels_read(x, add):
+        return _stats_reference(x, rowptr, col, num_targets, add=add, scalers=scalers, delta=delta, eps=eps)
+    out_dtype = torch.bfloat16 if amp_bf16() else torch.float32
+    with _no_autocast():
+        add32 = add.float().contiguous() if add is not None else None
+        return _StatsAggregate.apply(x, add32, rowptr, col, num_targets, mask, float(delta), float(eps), out_dtype)
+
+
+def pna_delta(rowptr):
+    """PNA's ``delta``: the mean of log(d + 1) over the rows of a hop or a graph (PyG: avg_deg["log"])"""
+    deg = (rowptr[1:] - rowptr[:-1]).double()
+    return float(torch.log(deg + 1).mean()) if deg.numel() else 1.0
+
+
+class PNAConv(torch.nn.Module):
+    """torch_geometric.nn.PNAConv(in, out, aggregators, scalers, deg, towers=1, pre_layers=1, post_layers=1,
+    divide_input=False) without ``edge_dim``, on an MFG hop: the message ``pre_nns.0([x_i | x_j])``, its mean, min, max
+    and std over each target's entries times the degree scalers, ``post_nns.0([x_i | aggregated])``, then ``lin``.
+    Parameters under PyG's names: ``pre_nns.0.0`` (2 in -> in), ``post_nns.0.0`` ((4 n_s + 1) in -> out), ``lin``.
+    ``delta`` (keyword, required) is what PyG derives from ``deg``: the mean of log(d + 1), see ``pna_delta``.
+
+    The pre-linear is linear in [x_i | x_j], so it is computed per NODE, not per edge: a = x_target W_i^T per target,
+    b = x W_j^T + bias per source, message = a_i + b_j.  The mean, min and max of the messages are a_i + those of b and
+    the std is that of b: ``stats_aggregate(b, add=a)``, one pass over the rows of b.  The four aggregators are fixed."""
+
+    def __init__(self, in_channels, out_channels, aggregators=_PNA_AGGREGATORS, scalers=tuple(_SCALERS), *, delta):
+        super().__init__()
+        if tuple(aggregators) != _PNA_AGGREGATORS:
+            raise ValueError(f"PNAConv: aggregators must be {_PNA_AGGREGATORS}, got {aggregators!r}")
+        _scaler_mask("PNAConv", scalers)
+        if not (isinstance(delta, (int, float)) and 0 < delta < float("inf")):
+            raise ValueError(f"PNAConv: delta must be a positive finite number, got {delta!r}")
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.scalers, self.delta = tuple(scalers), float(delta)
+        Lin, Seq = torch.nn.Linear, torch.nn.Sequential
+        self.pre_nns = torch.nn.ModuleList([Seq(Lin(2 * in_channels, in_channels))])
+        self.post_nns = torch.nn.ModuleList([Seq(Lin((4 * len(self.scalers) + 1) * in_channels, out_channels))])
+        self.lin = Lin(out_channels, out_channels)
+
+    def reset_parameters(self):
+        for m in (self.pre_nns[0][0], self.post_nns[0][0], self.lin):
+            m.reset_parameters()
+
+    def forward(self, x, adj_t, size=None):
+        rowptr, col, _ = adj_t.csr()
+        x_target = None
+        if isinstance(x, tuple):
+            x, x_target = x
+        if isinstance(x, (TableRows, RowRefs)):
+            x = x.materialize()
+        pre = self.pre_nns[0][0]
+        if x.dtype != pre.weight.dtype:                                  # (fp16 features: the Linears take the parameters' type)
+            x = x.to(pre.weight.dtype)
+        if x_target is None:
+            x_target = x[:int(size[1]) if size is not None else int(adj_t.sparse_sizes()[0])]
+        x_target = x_target.to(x.dtype)
+        Fin = self.in_channels
+        a = F.linear(x_target, pre.weight[:, :Fin])                      # [T, in]: the target's half of every message
+        b = F.linear(x, pre.weight[:, Fin:], pre.bias)                   # [S, in]: the source's half
+        agg = stats_aggregate(b, rowptr, col, x_target.size(0), add=a, scalers=self.scalers, delta=self.delta)
+        return self.lin(self.post_nns[0][0](torch.cat([x_target.to(agg.dtype), agg], dim=1)))
+
+
+class PNA(_ConvModel):
+    """``num_layers`` PNAConv (all four aggregators, all three scalers), each but the last followed by BatchNorm1d, ReLU
+    and dropout 0.5, then log_softmax: GCN's scaffold.  ``delta`` (keyword, required): ``pna_delta`` of the training
+    graph's rowptr.  No layer-wise ``inference`` in this model: the resident-graph entries have no mean / min / max / std
+    kernel; score with sampled or full-neighbour batches through ``forward``."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, delta):
+        super().__init__()
+        self.num_layers = num_layers
+        self.hidden_channels = hidden_channels
+        self.convs = torch.nn.ModuleList()
+        self.bns = torch.nn.ModuleList()
+        for i in range(num_layers):
+            self.convs.append(PNAConv(in_channels if i == 0 else hidden_channels,
+                                      out_channels if i == num_layers - 1 else hidden_channels, delta=delta))
+            if i != num_layers - 1:
+                self.bns.append(torch.nn.BatchNorm1d(hidden_channels))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        super().reset_parameters()
+        for bn in self.bns:
+            bn.reset_parameters()
+
+    def forward(self, x, adjs):
+        for i, (adj_t, _e_id, size) in enumerate(adjs):
+            x = self.convs[i](x, adj_t, size)
+            if i != self.num_layers - 1:
+                x = relu_dropout(self.bns[i](x), 0.5, self.training)
+        return torch.log_softmax(x, dim=-1)
+
+
+# --------------------------------------------------------------------------------------------
 # SAGEResInception  (driver/models.py:95-192)
 # --------------------------------------------------------------------------------------------
 class MLP(torch.nn.Module):
@@ -2079,11 +2320,11 @@ _UNSUPPORTED_MODELS = {"sageclassic": "not used in the paper", "jknet": "not use
 
 def get_model_type(model_name):
     """driver/main.py:74-95 for the four models the reference marks as working (names case-insensitive), "gcn" (GCN,
-    which the reference leaves unused), "gatv2" (GATv2) and "transformer" (GraphTransformer), which the reference does
-    not have"""
+    which the reference leaves unused), "gatv2" (GATv2), "transformer" (GraphTransformer) and "pna" (PNA), which the
+    reference does not have"""
     name = model_name.lower()
     models = {"sage": SAGE, "gat": GAT, "gin": GIN, "sageresinception": SAGEResInception, "gcn": GCN, "gatv2": GATv2,
-              "transformer": GraphTransformer}
+              "transformer": GraphTransformer, "pna": PNA}
     if name in models:
         return models[name]
     if name in _UNSUPPORTED_MODELS:

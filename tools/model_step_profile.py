@@ -1,7 +1,7 @@
 """One resident batch of the bench workload, N optimisation steps of one of the models (models.get_model_type: SAGE, GAT,
 GIN, SAGEResInception; and models.GCN) on it (fwd + bwd + Adam), timed; run under `rocprofv3 --kernel-trace --stats` for the per-kernel
 table.
-usage: model_step_profile.py [sage|gat|gatv2|transformer|gin|sageresinception|gcn] [steps=30] [workload=S-papers] [fused] [max] [norm] [reference] [--amp bf16] [--heads H] [attn=P]
+usage: model_step_profile.py [sage|gat|gatv2|transformer|gin|sageresinception|gcn|pna] [steps=30] [workload=S-papers] [fused] [max] [norm] [reference] [--amp bf16] [--heads H] [attn=P]
 norm: GCN built with normalize=True (gcn_norm's coefficients and the self term; the reference model's setting is False).
 max: SAGE built with aggr="max" (csrc/aggregate_max.hip, layer by layer) instead of the mean's fused stack.
 fused: GIN / SAGEResInception / GCN built with fused_norm=True (the BatchNorm tail on csrc/bn_act.hip).
@@ -12,7 +12,9 @@ gatv2: models.GATv2 (csrc/gatv2.hip), with --heads and attn= as GAT.
 transformer: models.GraphTransformer (csrc/transformer_conv.hip), with --heads and attn= as GAT (attn > 0 trains on the
 kernels with the mask drawn inside them: spp.h f4a).  reference: the same model with every layer sent to
 models._transformer_reference, the plain-torch path (attn > 0: torch's own mask there), for the comparison of DESIGN
-section 7 f3y."""
+section 7 f3y.
+pna: models.PNA (csrc/aggregate_stats.hip), delta = pna_delta of the workload's graph; with reference every layer's
+aggregation is sent to models._stats_reference (plain torch), for the comparison of DESIGN section 7 f4b."""
 import contextlib
 import os
 import sys
@@ -67,10 +69,10 @@ if heads != 1 and arch not in ATTN:
     sys.exit("--heads: GAT, GATv2 and GraphTransformer only")
 if attn and arch not in ATTN:
     sys.exit("attn=: GAT, GATv2 and GraphTransformer only")
-if reference and arch != "transformer":
-    sys.exit("reference: GraphTransformer only")
+if reference and arch not in ("transformer", "pna"):
+    sys.exit("reference: GraphTransformer and PNA only")
 if reference:
-    models._transformer_kernels_read = lambda *a: False
+    models._transformer_kernels_read = models._stats_kernels_read = lambda *a: False
 if fused and arch not in ("gin", "sageresinception", "gcn"):
     sys.exit("fused: GIN, SAGEResInception and GCN only")
 if norm and arch != "gcn":
@@ -86,6 +88,8 @@ if fused:
     kw["fused_norm"] = True
 if norm:
     kw["normalize"] = True
+if arch == "pna":
+    kw["delta"] = models.pna_delta(wl.rowptr)
 model = (GCN if arch == "gcn" else get_model_type(arch))(wl.x.size(1), 256, 47, 3, **kw).to(dev)
 if arch in ATTN:
     assert [c.heads for c in model.convs] == [heads] * 3, "the model was not built with --heads"
