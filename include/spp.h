@@ -2197,6 +2197,62 @@ typedef struct spp_agg_stats_desc {
 spp_status spp_agg_stats_forward(const spp_agg_stats_desc* desc, void* stream);
 spp_status spp_agg_stats_backward(const spp_agg_stats_desc* desc, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * f4e  MEAN / MIN / MAX / STD over rows of the RESIDENT graph in one pass, times degree scalers: the member of the f3g
+ *      family for f4b's four statistics, the message passing of exact, layer-wise PNA inference.  Forward only.  The
+ *      graph, x, the targets (a slab or a list) and the output stride are spp_graph_agg_desc's, unchanged in meaning;
+ *      scalers, delta, eps, add and the row layout [scaler][mean | min | max | std][F] are spp_agg_stats_desc's.
+ *
+ *   Contract, C = spp_graph_agg_chunk() (f3g's constant).  For output row i with target t, the entries k in [b, e) of
+ *   t's CSR row, d = e - b and v_k = x[col[k]], per column, all in fp32:
+ *     shift       K = v_b, the row's FIRST entry -- for every chunk of a long row too;
+ *     d <= C      s1 = sum (v_k - K), s2 = sum (v_k - K)^2 (one fmaf an entry), the min and the max by f4b's comparison
+ *                 rule from the first entry on, in CSR order one entry at a time: the arithmetic of
+ *                 spp_agg_stats_forward, whose min and max blocks these are bit for bit;
+ *     d > C       consecutive chunks of C entries (the last may be shorter): each chunk's s1 and s2 from zero against the
+ *                 ROW's K, added in chunk order in fp32; a chunk's min and max start from the chunk's first entry and
+ *                 are combined in chunk order by the same rule (a later value wins only if strictly better or a NaN;
+ *                 a NaN held stays).  With one shift for the whole row the chunk sums are sums of the same addends
+ *                 and need no correction term; the price is one more row load (col[b]) per lane group and column round;
+ *     epilogue    f4b's: m1 = s1 / d, mean = K + m1, std = sqrt(max(s2 / d - m1^2, 0) + eps); add_dev (fp32
+ *                 [num_targets, F] dense, indexed by OUTPUT row i, or NULL) is added to the mean, min and max; then the
+ *                 enabled scalers in the order identity, log(d+1) / delta, delta / log(d+1).  An output row is
+ *                 n_scalers * 4 * F wide; out_stride_elems lets it be columns of a wider row;
+ *     empty       a row without entries, or a target id outside [0, x_rows), writes zeros everywhere and ignores add;
+ *     a row's result depends on nothing else: not the grid, the slab, target_ids against target_row0, nor the other
+ *     rows of the call.  A bf16 output rounds each stored element once.  No CSR position is kept; every offset is 64-bit.
+ *
+ *   Load balance and workspace (spp_graph_agg_workspace_bytes(num_targets), 16-byte aligned) as spp_graph_agg_forward:
+ *   a 16-byte memset and two launches, no wait.  The vector form is the only form.  Refused with SPP_ERR_INVALID before
+ *   anything is enqueued: a NULL descriptor; a scaler mask outside [1, 7]; delta <= 0, eps < 0 or either not finite;
+ *   F % 4 != 0; num_targets * F out of range; everything spp_graph_agg_forward refuses (fp8 rows, both or neither
+ *   target form, a slab outside the graph, a short stride or workspace); then x_stride_elems % 4 != 0 or x_dev / add_dev
+ *   not aligned to 4 elements.  num_targets == 0 or F == 0: SPP_OK without a launch.
+ *   Not built: a row-partitioned x, fp8 tables, the receptive-field entries, a scalar form, a backward.
+ * ------------------------------------------------------------------------- */
+typedef struct spp_graph_agg_stats_desc {
+  int32_t x_elem;           /* SPP_ELEM_F32 / _F16 / _BF16 */
+  int32_t out_elem;         /* SPP_ELEM_F32 / SPP_ELEM_BF16 */
+  int32_t scalers;          /* mask of SPP_SCALER_* */
+  float delta;              /* > 0 */
+  float eps;                /* >= 0 */
+  const int64_t* rowptr_dev;
+  const int64_t* col_dev;
+  const void* x_dev;
+  int64_t x_stride_elems;
+  int64_t x_rows;           /* the graph's nodes = the rows of x */
+  int64_t F;
+  int64_t target_row0;      /* slab: the first target; < 0 with a list */
+  const int64_t* target_ids_dev; /* list: the targets; NULL with a slab */
+  int64_t num_targets;
+  const float* add_dev;     /* fp32 [num_targets, F] dense by output row, or NULL */
+  void* out_dev;            /* [num_targets, n_scalers * 4 * F] */
+  int64_t out_stride_elems; /* 0 = dense */
+} spp_graph_agg_stats_desc;
+
+spp_status spp_graph_agg_stats_forward(const spp_graph_agg_stats_desc* desc, void* workspace_dev, int64_t workspace_bytes,
+                                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -172,6 +172,15 @@ class GraphAggWeightedDesc(C.Structure):
                 ("dinv_dev", p), ("self_w_dev", p)]
 
 
+class GraphAggStatsDesc(C.Structure):
+    """spp_graph_agg_stats_desc: GraphAggDesc's graph, x, targets and output; AggStatsDesc's scalers, delta, eps and add
+    (by output row).  Forward only (spp.h f4e)"""
+    _fields_ = [("x_elem", i32), ("out_elem", i32), ("scalers", i32), ("delta", C.c_float), ("eps", C.c_float),
+                ("rowptr_dev", p), ("col_dev", p), ("x_dev", p), ("x_stride_elems", i64), ("x_rows", i64), ("F", i64),
+                ("target_row0", i64), ("target_ids_dev", p), ("num_targets", i64), ("add_dev", p), ("out_dev", p),
+                ("out_stride_elems", i64)]
+
+
 class GraphAggDesc(C.Structure):
     """spp_graph_agg_desc: targets as a slab (target_row0 >= 0) or a list (target_ids_dev, target_row0 < 0)"""
     _fields_ = [("epilogue", i32), ("x_elem", i32), ("out_elem", i32), ("reserved", i32), ("rowptr_dev", p),
@@ -447,6 +456,8 @@ SIGNATURES = {
     # mean / min / max / std in one pass (spp.h f4b)
     "spp_agg_stats_forward": (C.c_int, [C.POINTER(AggStatsDesc), p]),
     "spp_agg_stats_backward": (C.c_int, [C.POINTER(AggStatsDesc), p]),
+    # the same four statistics over rows of the resident graph (spp.h f4e)
+    "spp_graph_agg_stats_forward": (C.c_int, [C.POINTER(GraphAggStatsDesc), p, i64, p]),
 }
 SPP_COMM_ID_BYTES = 128
 SPP_IPC_HANDLE_BYTES = 64

@@ -9,6 +9,8 @@ pair of csrc/graph_gatv2.hip behind ``graph_gatv2_aggregate`` (``spp_graph_gatv2
 ``_gatv2_layer`` of the attention driver; resident entries only.  GraphTransformer (f3z): the long-row pair of
 csrc/graph_transformer.hip behind ``graph_transformer_aggregate`` (``spp_graph_transformer_forward``) and the recipe
 ``_transformer_layer`` of the same driver, with lin_skip and the ReLU in the kernel's epilogue; resident entries only.
+PNA (f4e): the long-row mean / min / max / std pair of csrc/graph_agg_stats.hip behind ``graph_stats_aggregate``
+(``spp_graph_agg_stats_forward``) and the driver ``_pna_layers``; resident entries only.
 
 The kernels' wrappers: ``graph_aggregate`` (``spp_graph_agg_forward``) and ``graph_gat_aggregate``
 (``spp_graph_gat_forward``) read one resident matrix, ``graph_aggregate_parts`` (``spp_graph_agg_parts_forward``) and
@@ -43,7 +45,8 @@ from . import _native as nat
 from .fast_sampler import P2PPeers, RowRefs, TableRows, _common_stride, _row_stride_elems, _table_stride_bytes, \
     p2p_open_peers
 from .fp8 import Fp8Features
-from .models import GAT, GATv2, GCN, GIN, SAGE, GraphTransformer, SAGEResInception, _ELEM, _gcn_fill, _p, _stream
+from .models import GAT, GATv2, GCN, GIN, PNA, SAGE, GraphTransformer, SAGEResInception, _ELEM, _gcn_fill, _p, \
+    _scaler_mask, _stream
 
 _EPILOGUES = {"mean": nat.SPP_AGG_MEAN, "operand": nat.SPP_AGG_OPERAND, "sum": nat.SPP_AGG_SUM,
               "max": nat.SPP_AGG_MAX, "max_operand": nat.SPP_AGG_MAX_OPERAND}
@@ -408,6 +411,16 @@ def _agg_weighted_launch(x, rowptr, col, weight, dinv, fill, self_weight, row0, 
     return _launch(nat.load().spp_graph_agg_weighted_forward, d, workspace, out)
 
 
+def _agg_stats_launch(x, rowptr, col, add, mask, delta, eps, row0, target_ids, T, out, workspace):
+    """spp_graph_agg_stats_forward: x [N, F] is one matrix, ``add`` fp32 [T, F] by output row or None, ``mask`` the
+    scalers' bits; ``out`` [T, n_s * 4F] may be columns of a wider matrix"""
+    N, Fdim = x.shape
+    d = nat.GraphAggStatsDesc(x_elem=_ELEM[x.dtype], scalers=mask, delta=float(delta), eps=float(eps), x_dev=_p(x),
+                              x_stride_elems=x.stride(0) if N > 1 else Fdim, x_rows=N, F=Fdim, add_dev=_p(add),
+                              **_request(rowptr, col, row0, target_ids, T, out))
+    return _launch(nat.load().spp_graph_agg_stats_forward, d, workspace, out)
+
+
 def _agg_parts_launch(src, off, rowptr, col, epilogue, self_scale, row0, target_ids, T, out, workspace, scale_log2=None):
     """spp_graph_agg_parts_forward: ``src`` is ``_parts_source``'s (base addresses, row stride, dtype, F); with
     ``scale_log2`` spp_graph_agg_parts_forward_fp8 over e4m3 parts"""
@@ -587,6 +600,53 @@ def gcn_dinv(rowptr, edge_weight=None, *, add_self_loops=True, improved=False):
     with torch.cuda.device(rowptr.device):
         nat.check(nat.load().spp_gcn_dinv(C.byref(d), _stream()))
     return dinv
+
+
+_STATS_NOT_BUILT = ("the mean / min / max / std aggregation reads one resident fp16 / fp32 / bf16 matrix: a row-partitioned "
+                    "x, fp8 tables and the receptive-field entries are not built for it")
+
+
+def graph_stats_aggregate(x, rowptr, col, *, add=None, scalers=("identity",), delta=1.0, eps=1e-5, row0=None,
+                          num_targets=None, target_ids=None, out=None, out_dtype=torch.float32, workspace=None):
+    """Mean, minimum, maximum and standard deviation over whole rows of the resident graph, each times the chosen degree
+    scalers (``spp_graph_agg_stats_forward``, include/spp.h f4e): [T, n_s * 4F] fp32 or bf16, laid out
+    ``[scaler][mean | min | max | std][F]`` as ``models.stats_aggregate`` -- PNAConv's aggregation for any row length.
+
+    ``x``, ``rowptr`` / ``col``, the targets (``row0`` and ``num_targets``, or ``target_ids``), ``out_dtype`` and
+    ``workspace`` as ``graph_aggregate``; ``out``: an fp32 / bf16 [T, n_s * 4F] matrix to write into (columns of a wider
+    one allowed, at a multiple of 4 elements).  ``add``: contiguous fp32 [T, F] without gradient, by OUTPUT row, added to
+    the mean, the minimum and the maximum.  ``scalers``, ``delta``, ``eps`` as ``models.stats_aggregate``.  F % 4 == 0 and
+    rows of x aligned to 4 elements: the kernels have the vector form only.
+
+    Every sum is shifted by the row's first entry.  A row of at most ``graph_agg_chunk()`` entries runs in CSR order like
+    the training kernel (its min and max blocks bit for bit); a longer row is chunks of that many entries, all shifted by
+    the ROW's first entry, whose sums are added and whose minima and maxima are combined in chunk order.  An empty row
+    gives zeros.  An ``Fp8Table``, fp8 features and a row-partitioned ``x`` are refused.  Forward only; nothing here waits
+    for the device."""
+    what = "graph_stats_aggregate"
+    if isinstance(x, (list, tuple, P2PPeers)):
+        raise NotImplementedError(f"{what}: x is row-partitioned ({type(x).__name__}); {_STATS_NOT_BUILT}")
+    _check_matrix(x, what, fp8_reason=_STATS_NOT_BUILT)
+    N, Fdim = x.shape
+    if Fdim % 4 != 0:
+        raise ValueError(f"{what}: F % 4 != 0 (F = {Fdim}): the kernels move four columns per lane and have no scalar form")
+    _check_graph(what, N, rowptr, col)
+    mask = _scaler_mask(what, scalers)
+    if isinstance(delta, bool) or not (isinstance(delta, (int, float)) and 0 < delta < float("inf")):
+        raise ValueError(f"{what}: delta must be a positive finite number, got {delta!r}")
+    if isinstance(eps, bool) or not (isinstance(eps, (int, float)) and 0 <= eps < float("inf")):
+        raise ValueError(f"{what}: eps must be a non-negative finite number, got {eps!r}")
+    _check_out_dtype(what, out_dtype)
+    row0, target_ids, T = _check_targets(what, N, row0, num_targets, target_ids)
+    if add is not None:
+        _check_fp32(what, "add", add, (T, Fdim), "one row per target, added to the mean, min and max")
+    width = 4 * Fdim * bin(mask).count("1")
+    _check_out(what, out, out_dtype, T, width)
+    workspace = _on_device(what, "x, rowptr, col, add, target_ids, workspace and out", x.device,
+                           [x, rowptr, col, add, target_ids, out], workspace, graph_agg_workspace_bytes, T)
+    if out is None:
+        out = torch.empty((T, width), dtype=out_dtype, device=x.device)
+    return _agg_stats_launch(x, rowptr, col, add, mask, delta, eps, row0, target_ids, T, out, workspace)
 
 
 def graph_aggregate_parts(parts, part_offsets, rowptr, col, *, row0=None, num_targets=None, target_ids=None,
@@ -1613,6 +1673,69 @@ def _attn_layers(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None)
     return sink.result()
 
 
+def _pna_layers(model, place, nodes, rows_per_slab, act_dtype, sink):
+    """PNA over one resident matrix (f4e), project-first like the attention driver because ``PNAConv``'s pre-linear is
+    per NODE (message = a_i + b_j, ``PNAConv``'s docstring).  Layer i, with ``in`` its input width and n_s = 3 scalers:
+
+      project    b = cur @ W_j^T + bias for all rows over ``_row_tiles(cur)``, ONE [n, in] matrix of ``act_dtype``
+      per slab   a = cur[targets] @ W_i^T over the fixed row tiles, made fp32 [T, in]; A [T, (4 n_s + 1) in] of
+                 ``act_dtype`` with A[:, :in] = cur[targets] and ``spp_graph_agg_stats_forward`` (``_agg_stats_launch``,
+                 add = a) writing A[:, in:] in place through its output stride -- PyG's cat without the copy
+      tail       over the fixed row tiles of A: lin(post_nns[0][0](tile)); every layer but the last then relu(bn(.)) on
+                 the running statistics, under bf16 autocast when ``act_dtype`` is bf16 (as ``_gcn_layer``); dropout is
+                 the identity.  The last layer's logits go to the sink.
+
+    Memory, as arithmetic: ``cur``, ``b`` and ``nxt`` are live at once -- THREE [N, .] matrices of ``act_dtype`` (57 GB
+    each in bf16 at N = 111 M and width 256: 3 * 57 + 26 of graph + 28 of features = 225 GB of one 288 GB MI355X) -- and
+    a slab's A is rows_per_slab * 13 * in elements next to its fp32 a (2^20 rows at in = 256 in bf16: 7 GB + 1 GB).  In
+    the last layer ``nxt`` is the sink's: for ``layerwise_inference`` the [N, classes] fp32 result (76 GB at 172 classes:
+    26 + 28 + 2 * 57 + 76 = 244 GB plus the slab; 262 GB was the measured peak), for ``evaluate`` two vectors.
+    ONE name holds each matrix and no view is left behind (``_attn_layers``)."""
+    amp = act_dtype == torch.bfloat16
+    n_layers, dev = len(model.convs), place.dev
+    plan = _whole_graph_plan(place, nodes, n_layers)
+    ws = torch.empty(graph_agg_workspace_bytes(min(rows_per_slab, max([place.n_local] + [st.rows for st in plan]))),
+                     dtype=torch.uint8, device=dev)
+    cur = place.x
+    for i, step in enumerate(plan):
+        last = i == n_layers - 1
+        conv = model.convs[i]
+        pre, post, lin, Fin = conv.pre_nns[0][0], conv.post_nns[0][0], conv.lin, conv.in_channels
+        mask = _scaler_mask("PNAConv", conv.scalers)
+        Wi, Wj = pre.weight[:, :Fin].to(act_dtype).t(), pre.weight[:, Fin:].to(act_dtype).t()
+        bj = pre.bias.to(act_dtype)
+        Wp, bp, Wl, bl = post.weight.to(act_dtype).t(), post.bias.to(act_dtype), lin.weight.to(act_dtype).t(), \
+            lin.bias.to(act_dtype)
+        b = torch.empty((cur.size(0), Fin), dtype=act_dtype, device=dev)
+        for r, n, tile in _row_tiles(cur):
+            b[r:r + n] = torch.addmm(bj, tile.to(act_dtype), Wj)[:n]
+        place.boundary()                                 # the projected rows are complete before anyone aggregates
+        rows, names = step.rows, step.names
+        nxt = None if last else torch.empty((rows, conv.out_channels), dtype=act_dtype, device=dev)
+        if last:
+            sink.open(place, rows, conv.out_channels)
+        for s, T, tids in _slabs(rows, step.ids, rows_per_slab):
+            A = torch.empty((T, (4 * len(conv.scalers) + 1) * Fin), dtype=act_dtype, device=dev)
+            A[:, :Fin] = cur[tids] if tids is not None else cur[s:s + T]
+            a = torch.empty((T, Fin), dtype=torch.float32, device=dev)
+            for r, n, tile in _tiles_contiguous(A[:, :Fin]):
+                a[r:r + n] = (tile @ Wi)[:n]
+            _agg_stats_launch(b, place.rowptr, place.col, a, mask, conv.delta, 1e-5, -1 if tids is not None else s, tids,
+                              T, A[:, Fin:], ws)
+            for r, n, tile in _row_tiles(A):
+                h = torch.addmm(bl, torch.addmm(bp, tile, Wp), Wl)
+                if last:
+                    sink.put(s + r, n, h, names[s + r:s + r + n] if names is not None else None)
+                    continue
+                with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+                    nxt[s + r:s + r + n] = torch.relu(model.bns[i](h))[:n]     # (eval mode: the running statistics)
+            A = a = None
+        cur, nxt = nxt, None                             # ONE name holds the matrix (drops layer i-1's)
+        del b
+        place.boundary()
+    return sink.result()
+
+
 def _resinc_head(model):
     """the two bare Linears of SAGEResInception's MLP head (``end_up_with_fc=True``: no BatchNorm, no activation)"""
     mods = list(model.mlp.module_list)
@@ -1758,9 +1881,24 @@ def _check_transformer(model, what):
                                       f"two), above the kernels' {_GATV2_MAX_D} (heads = {H} is not the limit that was hit)")
 
 
+_PNA_RESIDENT = ("a PNA model is scored over one resident fp16 / fp32 / bf16 matrix by inference.layerwise_inference and "
+                 "inference.evaluate; an Fp8Table input, edge weights, the field entries and the partitioned entries are "
+                 "not built for PNA")
+
+
+def _check_pna(model, what):
+    """the layers' widths as the kernels of ``_pna_layers`` take them: four columns per lane, no scalar form"""
+    for i, c in enumerate(model.convs):
+        if c.in_channels % 4 != 0:
+            raise NotImplementedError(f"{what}: PNA layer {i} has {c.in_channels} input channels; the mean / min / max / "
+                                      "std kernels over the resident graph take widths that are a multiple of 4 only")
+
+
 def _check_model(model, what, admits):
     """one of the model classes the entry admits, with what the GAT, GATv2 and SAGEResInception drivers need of its
     layers (SAGE, GIN and GCN: nothing)"""
+    if isinstance(model, PNA) and admits is _RESIDENT_MODELS:     # admitted next to the tuple, like GraphTransformer; the
+        return _check_pna(model, what)                           # other entries refuse it in their own tuples' wording
     if isinstance(model, GraphTransformer):              # admitted next to _RESIDENT_MODELS, whose refusal keeps its wording
         if admits is not _RESIDENT_MODELS:
             raise NotImplementedError(f"{what}: not built for GraphTransformer: {_TRANSFORMER_RESIDENT}")
@@ -1795,7 +1933,7 @@ def _score(model, place, nodes, rows_per_slab, act_dtype, sink, plan=None):
     """the frame of every driver: eval mode (restored), no gradient, autocast off, the table's device current; a rank
     that fails aborts the placement, so that its peers raise instead of waiting, and every mapping is closed"""
     layers = _attn_layers if isinstance(model, (GAT, GATv2, GraphTransformer)) else \
-        _resinc_layers if isinstance(model, SAGEResInception) else _conv_layers
+        _resinc_layers if isinstance(model, SAGEResInception) else _pna_layers if isinstance(model, PNA) else _conv_layers
     was_training = model.training
     model.eval()
     try:
@@ -1819,7 +1957,9 @@ def layerwise_inference(model, x, rowptr, col, *, nodes=None, rows_per_slab=1 <<
     over the whole graph; every model's ``.inference`` is this call.  The seventh model, ``GraphTransformer``, has no
     ``.inference`` method and is scored by this call directly (``_attn_layers`` with ``_transformer_layer``: heads in
     {1, 2, 4, 8}, heads * padded channels <= 1024, one resident matrix, no ``Fp8Table``, no ``edge_weight``; its five
-    live matrices are that recipe's arithmetic).  Each driver's docstring has its order of operations
+    live matrices are that recipe's arithmetic).  ``PNA`` (f4e) likewise has no ``.inference`` and is scored by this call
+    and by ``evaluate`` (``_pna_layers`` on ``spp_graph_agg_stats_forward``: every layer's input width a multiple of 4,
+    one resident matrix, no ``Fp8Table``, no ``edge_weight``; three live matrices).  Each driver's docstring has its order of operations
     and its memory: ``_conv_layers`` (SAGE, GIN and, through ``_gcn_layer``, GCN), ``_attn_layers`` with ``_gat_layer``
     (GAT at any ``heads``) and ``_gatv2_layer`` (GATv2: heads in {1, 2, 4, 8}, heads * padded channels <= 1024, one
     resident matrix and no ``Fp8Table``) and ``_resinc_layers`` (SAGEResInception).  What follows describes SAGE and
@@ -1877,6 +2017,10 @@ def _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, y, s
             raise NotImplementedError(f"{what}: GraphTransformer over a row-partitioned x ({type(x).__name__}); "
                                       f"{_TRANSFORMER_RESIDENT}")
         _check_matrix(x, what, fp8_reason=f"GraphTransformer: {_TRANSFORMER_RESIDENT}")
+    elif isinstance(model, PNA):
+        if isinstance(x, (list, tuple, P2PPeers)):
+            raise NotImplementedError(f"{what}: PNA over a row-partitioned x ({type(x).__name__}); {_PNA_RESIDENT}")
+        _check_matrix(x, what, fp8_reason=f"PNA: {_PNA_RESIDENT}")
     else:
         _check_table(x, what)
     N = x.size(0)
@@ -1934,7 +2078,7 @@ def evaluate(model, x, rowptr, col, y=None, *, nodes=None, splits=None, rows_per
     ``pred`` and ``nll`` are the same bits whatever ``rows_per_slab`` is and whether ``nodes`` selected it; ``pred[i]`` is
     the argmax of the logits, so ``layerwise_inference``'s row attains its maximum there.  The counts are reduced on the
     device and read back once, at the end.  ``edge_weight``: GCN's entry weights, as ``layerwise_inference`` takes them.
-    The seven models of ``layerwise_inference`` (``GraphTransformer`` included), each through the driver named there."""
+    The models of ``layerwise_inference`` (``GraphTransformer`` and ``PNA`` included), each through the driver named there."""
     what = "evaluate"
     nodes, segments = _check_splits(what, splits, nodes)
     sink = _resident(what, model, x, rowptr, col, nodes, rows_per_slab, act_dtype, y, _Classify(y), edge_weight)

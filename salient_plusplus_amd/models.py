@@ -2195,8 +2195,9 @@ class PNAConv(torch.nn.Module):
 class PNA(_ConvModel):
     """``num_layers`` PNAConv (all four aggregators, all three scalers), each but the last followed by BatchNorm1d, ReLU
     and dropout 0.5, then log_softmax: GCN's scaffold.  ``delta`` (keyword, required): ``pna_delta`` of the training
-    graph's rowptr.  No layer-wise ``inference`` in this model: the resident-graph entries have no mean / min / max / std
-    kernel; score with sampled or full-neighbour batches through ``forward``."""
+    graph's rowptr.  The model has no ``inference`` method; ``inference.layerwise_inference(model, x, rowptr, col)`` and
+    ``inference.evaluate`` score it exactly over the whole resident graph (``_pna_layers`` on
+    ``spp_graph_agg_stats_forward``, DESIGN section 7 f4e: widths a multiple of 4, one resident matrix)."""
 
     def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, delta):
         super().__init__()

@@ -7,6 +7,7 @@ with bf16 activations, timed per layer, and layer 1's slabs once more through th
     python tools/inference_profile.py --model gatv2 [--heads 4] [--share-weights] [--repeats 3] ...
     python tools/inference_profile.py --model sageresinception [--nodes 1500000] [--torch-epilogue] [--repeats 3] ...
     python tools/inference_profile.py --model gcn [--repeats 3] ...      (``gcn_leg``: the weighted kernels against the sum)
+    python tools/inference_profile.py --model pna [--forward-sample 1024] [--repeats 3] ...   (``pna_leg``)
     python tools/inference_profile.py --evaluate [--repeats 3] ...
     python tools/inference_profile.py --parts 8 --workload S-products [--repeats 5] ...
     python tools/inference_profile.py --parts 8 --model gat --workload S-products [--heads 1] [--repeats 9] ...
@@ -75,7 +76,9 @@ def main():
     ap.add_argument("--hidden", type=int, default=256)
     ap.add_argument("--classes", type=int, default=172)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--model", choices=("sage", "gat", "gatv2", "transformer", "sageresinception", "gcn"), default="sage")
+    ap.add_argument("--model", choices=("sage", "gat", "gatv2", "transformer", "sageresinception", "gcn", "pna"), default="sage")
+    ap.add_argument("--forward-sample", type=int, default=0,
+                    help="pna: instead of layerwise_inference, the model's forward over full-neighbour hops of this many nodes")
     ap.add_argument("--beta", action="store_true", help="transformer: every conv's beta gate (torch ops per slab)")
     ap.add_argument("--share-weights", action="store_true", help="gatv2: lin_r is lin_l (one projection, x_r = x_l)")
     ap.add_argument("--heads", type=int, default=1)
@@ -117,6 +120,8 @@ def main():
         return resinc_leg(a, wl, res)
     if a.model == "gcn":
         return gcn_leg(a, wl, res)
+    if a.model == "pna":
+        return pna_leg(a, wl, res)
     if a.evaluate:
         return evaluate_leg(a, wl, res)
 
@@ -168,6 +173,61 @@ def main():
     res["layer1_hop_kernel_s"] = round(hop_s, 4)
     res["layer1_hop_kernel_worst_slab"] = {"row0": worst[1], "s": round(worst[0], 4)}
     print(json.dumps({k: res[k] for k in ("total_s", "layer1_hop_kernel_s", "layer1_hop_kernel_worst_slab")}), flush=True)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+def _full_hops(rowptr, col, seeds, n_layers):
+    """(n_id, hops outermost first) of ``seeds`` with EVERY neighbour kept: (rowptr, local col, targets, sources) a hop,
+    the targets first among the sources -- what a sampler with unlimited fanout would deliver"""
+    hops, targets, dev = [], seeds, seeds.device
+    for _ in range(n_layers):
+        deg = rowptr[targets + 1] - rowptr[targets]
+        rp = torch.zeros(targets.numel() + 1, dtype=torch.int64, device=dev)
+        rp[1:] = torch.cumsum(deg, 0)
+        src = col[torch.arange(int(rp[-1]), device=dev) + torch.repeat_interleave(rowptr[targets] - rp[:-1], deg)]
+        new = torch.unique(src)
+        n_id = torch.cat([targets, new[~torch.isin(new, targets)]])
+        order = torch.argsort(n_id)
+        hops.append((rp, order[torch.searchsorted(n_id[order], src)], targets.numel(), n_id.numel()))
+        targets = n_id
+    return targets, hops[::-1]
+
+
+def pna_leg(a, wl, res):
+    """``--model pna``: ``--repeats`` whole ``layerwise_inference`` passes of PNA 3 x hidden (bf16 activations) in one
+    process, every pass reported (the first warms up).  With ``--forward-sample K``: the same model's ``forward`` under
+    bf16 autocast over three full-neighbour hops of K random nodes instead -- what scoring PNA cost before f4e.  Run the
+    two in fresh processes, alternated."""
+    from salient_plusplus_amd import inference as inf
+    from salient_plusplus_amd.fast_trainer.monkeypatch import SparseTensor
+    from salient_plusplus_amd.models import PNA, pna_delta
+    x, rowptr, col, dev = wl.x, wl.rowptr, wl.col, wl.x.device
+    torch.manual_seed(0)
+    model = PNA(x.size(1), a.hidden, a.classes, 3, delta=pna_delta(rowptr)).to(dev).eval()
+    res.update(model="pna", passes_s=[])
+    if a.forward_sample:
+        seeds = torch.unique(torch.randint(0, wl.num_nodes, (a.forward_sample,), device=dev))
+        n_id, hops = _full_hops(rowptr, col, seeds, 3)
+        res.update(forward_sample=seeds.numel(), hop_sources=[h[3] for h in hops], hop_entries=[int(h[0][-1]) for h in hops])
+        adjs = [(SparseTensor(rowptr=rp, col=cl, sparse_sizes=(T, S)), None, (S, T)) for rp, cl, T, S in hops]
+        xs = x[n_id]
+    for _ in range(a.repeats):
+        torch.cuda.synchronize()
+        t0 = time.time()
+        if a.forward_sample:
+            with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+                out = model(xs, adjs)
+        else:
+            out = inf.layerwise_inference(model, x, rowptr, col, rows_per_slab=a.rows_per_slab, act_dtype=torch.bfloat16)
+        torch.cuda.synchronize()
+        res["passes_s"].append(round(time.time() - t0, 4))
+        assert out.size(1) == a.classes and bool(torch.isfinite(out[:: max(1, out.size(0) // 4096)]).all())
+        del out
+    res["max_memory_GB"] = round(torch.cuda.max_memory_allocated() / 1e9, 1)
+    print(json.dumps({k: v for k, v in res.items() if k != "layers"}), flush=True)
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:
