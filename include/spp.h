@@ -2253,6 +2253,86 @@ typedef struct spp_graph_agg_stats_desc {
 spp_status spp_graph_agg_stats_forward(const spp_graph_agg_stats_desc* desc, void* workspace_dev, int64_t workspace_bytes,
                                        void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * f4f  The LayerNorm tail between the layers of the attention models (GAT, GATv2, GraphTransformer, norm="layer"):
+ *      y = dropout(act(LayerNorm(z))) [+ r], forward and backward; the per-ROW relative of f3p.
+ *
+ *   z, r, y, g, dz are [n, C], row-major and dense, fp32 or bf16 each on its own (dz has z's type); gamma, beta, dgamma,
+ *   dbeta are fp32 [C]; mean, rstd are fp32 [n].  C % 4 == 0 and 4 <= C <= 1024: a lane holds up to four pieces of four
+ *   columns and there is no scalar form.  A bf16 value is read as its fp32 value, all arithmetic is fp32 and a bf16
+ *   output is rounded once, to nearest even.
+ *
+ *   spp_ln_act_forward, for every row i (n == 1 is valid):
+ *        mean[i]  = the mean, var the BIASED variance of row i over its C columns (torch.nn.LayerNorm's), computed
+ *                   from the row's residuals about a first mean -- a two-pass variance: a row of mean 1e4 and spread 1
+ *                   keeps its variance -- while z is read once
+ *        rstd[i]  = 1 / sqrt(var + eps)
+ *        u        = gamma[c] * (z[i,c] - mean[i]) * rstd[i] + beta[c]    of the fp32 operands, rounded once (f3p's rule)
+ *        a        = u (SPP_LN_ACT_NONE) | u > 0 ? u : 0 (SPP_LN_ACT_RELU) | u > 0 ? u : negative_slope * u (_LEAKY_RELU)
+ *        y[i,c]   = round_once((keep(i*C + c) ? a * (1 / (1 - p)) : 0) + r[i,c])          (no dropout: a itself; no r: no add)
+ *      keep(e) is the generator of spp_relu_dropout_forward over a dense array of n*C elements at the same (seed, p),
+ *      exactly as f3p indexes it.  Dropout is applied when training != 0 and p > 0; otherwise the kernels read neither p
+ *      nor seed.  The statistics are the same in training and in eval.  mean and rstd are written (backward reads them).
+ *      A row's y, mean and rstd depend on the row, gamma, beta and C alone (with dropout: on its index i too), not on n.
+ *
+ *   spp_ln_act_backward reads g (the gradient of y), z, mean, rstd, gamma, beta and the seed -- neither y nor a mask:
+ *   the sign of u and keep(e) are recomputed, by the forward's own expressions.
+ *        xh        = (z[i,c] - mean[i]) * rstd[i]
+ *        g_a       = g[i,c] * (keep ? 1 / (1 - p) : 0) * act'(u)          act'(u) = 1 for u > 0, else 0 / negative_slope
+ *        gh        = g_a * gamma[c]
+ *        dz[i,c]   = round_once(rstd[i] * (gh - mean_c(gh) - xh * mean_c(gh * xh)))       means over the row's C columns
+ *        dbeta[c]  = sum_i g_a        dgamma[c] = sum_i g_a * xh
+ *      The column sums: the rows are cut into slabs of SPP_LN_ACT_SLAB_ROWS, one workgroup per slab leaves a [2, C] fp32
+ *      record in the workspace (the sums of g_a, then of g_a * xh), and a second kernel adds the records in a fixed order
+ *      in fp64.  No atomics: the same bits from call to call on the same input.  The gradient of r is g itself: no
+ *      kernel runs for it.
+ *
+ *   Workspace (backward only): spp_ln_act_workspace_bytes(n, C) bytes, 16-byte aligned, the caller's; its contents mean
+ *   nothing between calls.  The entries enqueue their launches on `stream` and never wait for the device.
+ *   Refused with SPP_ERR_INVALID before anything is enqueued, in a message that names the entry: a NULL descriptor;
+ *   negative n; an unknown element code (fp16, fp8) or act; C outside [4, 1024] or C % 4 != 0; a matrix base not aligned
+ *   to 4 of its elements, gamma or beta not aligned to 16 bytes; a NULL required pointer (z, gamma, beta, mean, rstd; y
+ *   forward; g, dz, dgamma, dbeta backward); p outside [0, 1) (a NaN included); backward: a missing, misaligned or too
+ *   small workspace.  n == 0: SPP_OK once the element codes, act and C are accepted; no pointer is looked at (an empty
+ *   tensor has none), nothing is enqueued, nothing written.
+ * ------------------------------------------------------------------------- */
+#define SPP_LN_ACT_SLAB_ROWS 64
+enum { SPP_LN_ACT_NONE = 0, SPP_LN_ACT_RELU = 1, SPP_LN_ACT_LEAKY_RELU = 2 };
+
+typedef struct spp_ln_act_desc {
+  int32_t z_elem;            /* SPP_ELEM_F32 / SPP_ELEM_BF16; dz has the same */
+  int32_t r_elem;            /* forward, with r_dev */
+  int32_t y_elem;            /* forward; independent of z_elem */
+  int32_t g_elem;            /* backward */
+  int32_t act;               /* SPP_LN_ACT_* */
+  int32_t training;          /* != 0 with p > 0: dropout */
+  float negative_slope;
+  float p;                   /* dropout probability, [0, 1) */
+  float eps;
+  int32_t reserved;
+  uint64_t seed;
+  int64_t n;
+  int64_t C;
+  const void* z_dev;
+  const float* gamma_dev;
+  const float* beta_dev;
+  const void* r_dev;         /* forward: the residual, NULL = none */
+  void* y_dev;               /* forward: out */
+  float* mean_dev;           /* [n]; forward: out; backward: in */
+  float* rstd_dev;           /* [n]; forward: out; backward: in */
+  const void* g_dev;         /* backward: the gradient of y */
+  void* dz_dev;              /* backward: out */
+  float* dgamma_dev;         /* backward: out */
+  float* dbeta_dev;          /* backward: out */
+  void* workspace_dev;       /* backward */
+  int64_t workspace_bytes;
+} spp_ln_act_desc;
+
+int64_t spp_ln_act_slab_rows(void);
+int64_t spp_ln_act_workspace_bytes(int64_t n, int64_t C);
+spp_status spp_ln_act_forward(const spp_ln_act_desc* desc, void* stream);
+spp_status spp_ln_act_backward(const spp_ln_act_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

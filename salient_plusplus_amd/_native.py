@@ -60,6 +60,7 @@ class MfgOut(C.Structure):
 # spp_elem and the aggregation descriptor's codes (include/spp.h)
 SPP_ELEM_F32, SPP_ELEM_F16, SPP_ELEM_BF16 = 0, 1, 2
 SPP_BN_ACT_NONE, SPP_BN_ACT_RELU, SPP_BN_ACT_LEAKY_RELU = 0, 1, 2
+SPP_LN_ACT_NONE, SPP_LN_ACT_RELU, SPP_LN_ACT_LEAKY_RELU = 0, 1, 2
 SPP_ELEM_FP8_E4M3 = 3            # spp_agg_forward_fp8, spp_graph_agg_*_forward_fp8, spp_exchange_cfg.x_elem
 SPP_AGG_DENSE, SPP_AGG_TABLE, SPP_AGG_ROWS = 0, 1, 2
 SPP_AGG_MEAN, SPP_AGG_OPERAND, SPP_AGG_OPERAND_ACT, SPP_AGG_SUM = 0, 1, 2, 3
@@ -257,6 +258,15 @@ class BnActDesc(C.Structure):
                 ("dgamma_dev", p), ("dbeta_dev", p), ("workspace_dev", p), ("workspace_bytes", i64)]
 
 
+class LnActDesc(C.Structure):
+    """spp_ln_act_desc: y = dropout(act(LayerNorm(z))) [+ r] on per-row statistics, and its backward"""
+    _fields_ = [("z_elem", i32), ("r_elem", i32), ("y_elem", i32), ("g_elem", i32), ("act", i32), ("training", i32),
+                ("negative_slope", C.c_float), ("p", C.c_float), ("eps", C.c_float), ("reserved", i32),
+                ("seed", C.c_uint64), ("n", i64), ("C", i64), ("z_dev", p), ("gamma_dev", p), ("beta_dev", p),
+                ("r_dev", p), ("y_dev", p), ("mean_dev", p), ("rstd_dev", p), ("g_dev", p), ("dz_dev", p),
+                ("dgamma_dev", p), ("dbeta_dev", p), ("workspace_dev", p), ("workspace_bytes", i64)]
+
+
 class ClassifyDesc(C.Structure):
     """spp_classify_desc: pred = argmax z, nll = logsumexp(z) - z[y]; labels as a slab (y_row0 >= 0) or a list"""
     _fields_ = [("z_elem", i32), ("reserved", i32), ("z_dev", p), ("z_stride_elems", i64), ("n", i64), ("C", i64),
@@ -425,6 +435,11 @@ SIGNATURES = {
     "spp_bn_act_workspace_bytes": (i64, [i64, i64]),
     "spp_bn_act_forward": (C.c_int, [C.POINTER(BnActDesc), p]),
     "spp_bn_act_backward": (C.c_int, [C.POINTER(BnActDesc), p]),
+    # the LayerNorm tail (spp.h f4f)
+    "spp_ln_act_slab_rows": (i64, []),
+    "spp_ln_act_workspace_bytes": (i64, [i64, i64]),
+    "spp_ln_act_forward": (C.c_int, [C.POINTER(LnActDesc), p]),
+    "spp_ln_act_backward": (C.c_int, [C.POINTER(LnActDesc), p]),
     "spp_agg_max_forward": (C.c_int, [C.POINTER(AggMaxFwdDesc), p]),
     "spp_agg_max_backward": (C.c_int, [C.POINTER(AggMaxBwdDesc), p]),
     "spp_agg_weighted_forward": (C.c_int, [C.POINTER(AggWeightedFwdDesc), p]),

@@ -10,14 +10,16 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libspp_hip.so")
 SOURCES = ["api.hip", "mt19937.hip", "gather.hip", "gather_fp8.hip", "sampler.hip", "partition.hip", "session.hip", "exchange.hip", "vip.hip", "aggregate.hip", "aggregate_max.hip", "aggregate_stats.hip", "aggregate_weighted.hip", "gat.hip", "gatv2.hip", "transformer_conv.hip",
-           "graph_aggregate.hip", "graph_agg_weighted.hip", "graph_agg_stats.hip", "graph_gat.hip", "graph_gatv2.hip", "graph_transformer.hip", "resinc_epilogue.hip", "classify.hip", "field.hip", "bn_act.hip"]
+           "graph_aggregate.hip", "graph_agg_weighted.hip", "graph_agg_stats.hip", "graph_gat.hip", "graph_gatv2.hip", "graph_transformer.hip", "resinc_epilogue.hip", "classify.hip", "field.hip", "bn_act.hip", "ln_act.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
          "-I" + CSRC, "-Wall", "-Wno-unused-function"] + os.environ.get("SPP_EXTRA_FLAGS", "").split()
 # per-source additions: aggregate_stats.hip and graph_agg_stats.hip (the same per-column arithmetic, compiled alike) are
-# built without the packed fp32 instructions (v_pk_*_f32)
+# built without the packed fp32 instructions (v_pk_*_f32).  ln_act.hip too: its error-free sequences (pre_act, the Newton
+# residual of rstd) and its fixed summation orders are written one fp32 operation at a time, and this keeps the compiler
+# from pairing them into v_pk_add / v_pk_mul / v_pk_fma forms; the register counts of DESIGN 7 f4f are for this setting
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-SOURCE_FLAGS = {"aggregate_stats.hip": _NO_PACKED_FP32, "graph_agg_stats.hip": _NO_PACKED_FP32}
+SOURCE_FLAGS = {"aggregate_stats.hip": _NO_PACKED_FP32, "graph_agg_stats.hip": _NO_PACKED_FP32, "ln_act.hip": _NO_PACKED_FP32}
 
 
 def _stale(target, deps):

@@ -1897,6 +1897,9 @@ def _check_pna(model, what):
 def _check_model(model, what, admits):
     """one of the model classes the entry admits, with what the GAT, GATv2 and SAGEResInception drivers need of its
     layers (SAGE, GIN and GCN: nothing)"""
+    if getattr(model, "norm", None) is not None:         # GAT, GATv2, GraphTransformer built with norm="layer" (f4f)
+        raise ValueError(f"{what}: the model was built with norm={model.norm!r}; the layer-wise kernels apply no LayerNorm "
+                         "yet, so its scores would be wrong.  Score it batch-wise through its forward in eval mode")
     if isinstance(model, PNA) and admits is _RESIDENT_MODELS:     # admitted next to the tuple, like GraphTransformer; the
         return _check_pna(model, what)                           # other entries refuse it in their own tuples' wording
     if isinstance(model, GraphTransformer):              # admitted next to _RESIDENT_MODELS, whose refusal keeps its wording

@@ -459,6 +459,113 @@ def batch_norm_act(z, bn, *, act="none", negative_slope=0.01, p=0.0, training=No
     return _BatchNormAct.apply(z, bn.weight, bn.bias, residual, bn, act, negative_slope, p, training)
 
 
+# ---- the tail between attention layers: dropout(act(LayerNorm(z))) [+ residual]  (csrc/ln_act.hip, spp.h f4f) ----
+_LN_ACTS = {"none": nat.SPP_LN_ACT_NONE, "relu": nat.SPP_LN_ACT_RELU, "leaky_relu": nat.SPP_LN_ACT_LEAKY_RELU}
+
+
+class _LayerNormAct(torch.autograd.Function):
+    """One node for LayerNorm over the last dimension, the activation, dropout and the residual add.  Saves z, mean,
+    rstd, gamma and beta and keeps the seed: neither the output nor a mask; the backward recomputes the sign of the
+    pre-activation and the keep pattern (spp_ln_act_backward)."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, residual, eps, act, slope, p, training, y_dtype):
+        L = nat.load()
+        n, Cdim = z.shape
+        # the seed comes from torch's CPU generator, so torch.manual_seed makes a run repeatable
+        seed = _draw_seed() if training and p > 0 else 0
+        y = torch.empty((n, Cdim), dtype=y_dtype, device=z.device)
+        mean = torch.empty(n, dtype=torch.float32, device=z.device)
+        rstd = torch.empty_like(mean)
+        d = nat.LnActDesc(z_elem=_ELEM[z.dtype], r_elem=_ELEM[residual.dtype] if residual is not None else 0,
+                          y_elem=_ELEM[y_dtype], act=_LN_ACTS[act], training=int(training), negative_slope=float(slope),
+                          p=float(p), eps=float(eps), seed=seed, n=n, C=Cdim, z_dev=_p(z), gamma_dev=_p(gamma),
+                          beta_dev=_p(beta), r_dev=_p(residual), y_dev=_p(y), mean_dev=_p(mean), rstd_dev=_p(rstd))
+        nat.check(L.spp_ln_act_forward(C.byref(d), _stream()))
+        ctx.save_for_backward(z, gamma, beta, mean, rstd)
+        ctx.cfg = (_LN_ACTS[act], float(slope), float(p), int(training), seed, float(eps))
+        ctx.res_dtype = residual.dtype if residual is not None else None
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        L = nat.load()
+        z, gamma, beta, mean, rstd = ctx.saved_tensors
+        act, slope, p, training, seed, eps = ctx.cfg
+        n, Cdim = z.shape
+        gc = g.contiguous()
+        if gc.dtype not in (torch.float32, torch.bfloat16):
+            gc = gc.to(torch.float32)
+        if gc.data_ptr() % (4 * gc.element_size()):          # a contiguous view at an odd element offset
+            gc = gc.clone()
+        g_res = g.to(ctx.res_dtype) if ctx.needs_input_grad[3] else None
+        dz = torch.empty_like(z)
+        dgamma = torch.empty(Cdim, dtype=torch.float32, device=z.device)
+        dbeta = torch.empty_like(dgamma)
+        if n > 0:
+            ws = torch.empty(L.spp_ln_act_workspace_bytes(n, Cdim), dtype=torch.uint8, device=z.device)
+            d = nat.LnActDesc(z_elem=_ELEM[z.dtype], g_elem=_ELEM[gc.dtype], act=act, training=training,
+                              negative_slope=slope, p=p, eps=eps, seed=seed, n=n, C=Cdim, z_dev=_p(z), gamma_dev=_p(gamma),
+                              beta_dev=_p(beta), mean_dev=_p(mean), rstd_dev=_p(rstd), g_dev=_p(gc), dz_dev=_p(dz),
+                              dgamma_dev=_p(dgamma), dbeta_dev=_p(dbeta), workspace_dev=_p(ws), workspace_bytes=ws.numel())
+            nat.check(L.spp_ln_act_backward(C.byref(d), _stream()))
+        else:
+            dgamma.zero_(), dbeta.zero_()
+        return dz, dgamma, dbeta, g_res, None, None, None, None, None, None
+
+
+def _ln_act_torch(z, ln, act, negative_slope, p, training, residual):
+    """The plain torch composition: F.dropout(act(ln(z)), p, training) + residual"""
+    h = ln(z)
+    if act == "relu":
+        h = F.relu(h)
+    elif act == "leaky_relu":
+        h = F.leaky_relu(h, negative_slope)
+    h = F.dropout(h, p=p, training=training)
+    return h if residual is None else h + residual
+
+
+def _ln_kernels_read(z, ln, p, residual):
+    """what csrc/ln_act.hip takes: contiguous fp32 / bf16 CUDA matrices of a width C % 4 == 0 in [4, 1024], bases aligned
+    to 4 elements, and a LayerNorm over exactly that width with fp32 weight and bias on the same device"""
+    ok = lambda t: (t.is_cuda and t.dim() == 2 and t.is_contiguous() and t.dtype in (torch.float32, torch.bfloat16)
+                    and t.data_ptr() % (4 * t.element_size()) == 0)
+    par = lambda w: (w is not None and w.dtype == torch.float32 and w.device == z.device and w.is_contiguous()
+                     and w.data_ptr() % 16 == 0)
+    return (isinstance(ln, torch.nn.LayerNorm) and ok(z) and tuple(ln.normalized_shape) == (z.size(1),)
+            and z.size(1) % 4 == 0 and 4 <= z.size(1) <= 1024 and 0.0 <= p < 1.0 and par(ln.weight) and par(ln.bias)
+            and (residual is None or (ok(residual) and residual.shape == z.shape and residual.device == z.device)))
+
+
+def layer_norm_act(z, ln, *, act="none", negative_slope=0.01, p=0.0, training=True, residual=None):
+    """``F.dropout(act(ln(z)), p, training) + residual`` as one autograd node on HIP kernels (csrc/ln_act.hip).
+
+    ``ln`` is a ``torch.nn.LayerNorm`` with ``normalized_shape == (C,)`` for z of shape [n, C]: its ``eps``, ``weight``
+    and ``bias`` are used.  ``act`` is "none", "relu" or "leaky_relu" (``negative_slope``); ``residual`` has z's shape.
+    Dropout draws its seed from torch's CPU generator (``torch.manual_seed`` makes a run repeatable); its keep pattern
+    is this library's counter-based generator, not torch's.  The output is fp32 under CUDA autocast (torch's policy for
+    ``layer_norm``), otherwise z's dtype promoted with the residual's.
+
+    Contiguous fp32 / bf16 CUDA matrices with C % 4 == 0 and 4 <= C <= 1024 and fp32 affine parameters on the same
+    device take the kernels.  Everything else -- CPU tensors, other dtypes, widths or strides, ``elementwise_affine=False``
+    or ``bias=False`` modules -- runs the plain torch composition.  Double backward through the kernel path is not
+    supported."""
+    if act not in _LN_ACTS:
+        raise ValueError(f"layer_norm_act: act must be one of {sorted(_LN_ACTS)}, got {act!r}")
+    training = bool(training)
+    if not _ln_kernels_read(z, ln, p, residual):
+        return _ln_act_torch(z, ln, act, negative_slope, p, training, residual)
+    if torch.is_autocast_enabled("cuda"):
+        y_dtype = torch.float32
+    else:
+        y_dtype = torch.promote_types(z.dtype, residual.dtype) if residual is not None else z.dtype
+    return _LayerNormAct.apply(z, ln.weight, ln.bias, residual, ln.eps, act, negative_slope, p, training, y_dtype)
+
+
+_ATTN_NORMS = (None, "layer")
+
+
 class _TallLinear(torch.autograd.Function):
     """y = a @ w.T for a very tall ``a`` ([T, K], T ~ 1e5) and a small ``w`` ([N, K]).
 
@@ -1150,11 +1257,21 @@ class _GatLayer(torch.autograd.Function):
 class _AttentionModel(_ConvModel):
     """The shape GAT, GATv2 and GraphTransformer share: ``num_layers`` convs of the class ``conv`` (keywords ``kw``),
     ReLU + dropout 0.5 between layers, log_softmax.  Every hidden layer is ``heads`` heads of ``hidden_channels // heads``
-    channels, concatenated; the last layer is the mean of its heads (``last_concat``: their concatenation)."""
+    channels, concatenated; the last layer is the mean of its heads (``last_concat``: their concatenation).
 
-    def __init__(self, conv, in_channels, hidden_channels, out_channels, num_layers, heads, last_concat=False, **kw):
+    ``norm="layer"`` (the models' keyword-only ``norm``; default None) puts a ``LayerNorm(hidden_channels)`` in front of
+    every ReLU: ``self.norms``, ``num_layers - 1`` modules (state dict keys ``norms.{i}.weight`` / ``norms.{i}.bias``), and
+    the tail between layers becomes ``layer_norm_act(x, norms[i], act="relu", p=0.5)``, one node on csrc/ln_act.hip
+    (spp.h f4f).  With None there is no such attribute and nothing else changes.  The layer-wise inference entries apply
+    no LayerNorm yet and refuse a model built with it; the forward in eval mode scores it batch-wise."""
+
+    def __init__(self, conv, in_channels, hidden_channels, out_channels, num_layers, heads, last_concat=False, norm=None,
+                 **kw):
         super().__init__()
         _check_heads(heads)
+        if norm not in _ATTN_NORMS:
+            raise ValueError(f"{type(self).__name__}: norm must be None or 'layer', got {norm!r}")
+        self.norm = norm
         if hidden_channels % heads != 0:
             raise ValueError(f"hidden_channels ({hidden_channels}) must be a multiple of heads ({heads})")
         self.num_layers = num_layers
@@ -1166,7 +1283,15 @@ class _AttentionModel(_ConvModel):
         for _ in range(num_layers - 2):
             self.convs.append(conv(hidden_channels, c, heads=heads, concat=True, **kw))
         self.convs.append(conv(hidden_channels, out_channels, heads=heads, concat=last_concat, **kw))
+        if norm == "layer":
+            self.norms = torch.nn.ModuleList(torch.nn.LayerNorm(hidden_channels) for _ in range(num_layers - 1))
         self.reset_parameters()
+
+    def reset_parameters(self):
+        super().reset_parameters()
+        if self.norm == "layer":
+            for ln in self.norms:
+                ln.reset_parameters()
 
     def forward(self, x, adjs):
         if isinstance(x, (TableRows, RowRefs)):          # (the fused first layer exists for SAGE)
@@ -1177,7 +1302,10 @@ class _AttentionModel(_ConvModel):
             x_target = x[:size[1]]
             x = self.convs[i]((x, x_target), adj_t)
             if i != self.num_layers - 1:
-                x = relu_dropout(x, 0.5, self.training)
+                if self.norm == "layer":
+                    x = layer_norm_act(x, self.norms[i], act="relu", p=0.5, training=self.training)
+                else:
+                    x = relu_dropout(x, 0.5, self.training)
         return torch.log_softmax(x, dim=-1)
 
 
@@ -1193,13 +1321,15 @@ class GAT(_LayerwiseInference, _AttentionModel):
 
     ``attn_dropout`` (keyword only, default 0): GATConv's ``dropout`` of every conv, PyG's dropout on the attention
     coefficients (p = 0.6 in the GAT paper).  Training only: eval mode and the inference drivers score the model exactly
-    as the same model with 0."""
+    as the same model with 0.
 
-    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, heads=1, attn_dropout=0.0):
+    ``norm`` (keyword only, default None): "layer" normalises every hidden layer with LayerNorm (``_AttentionModel``)."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, heads=1, attn_dropout=0.0, norm=None):
         # heads=1, the reference model: the last layer keeps GATConv's default concat=True too (one head: the same
         # function, and with attn_dropout the GEMM spelling _GatLayerMH has always run for it)
         super().__init__(GATConv, in_channels, hidden_channels, out_channels, num_layers, heads, last_concat=heads == 1,
-                         bias=False, dropout=attn_dropout)
+                         norm=norm, bias=False, dropout=attn_dropout)
 
 
 # --------------------------------------------------------------------------------------------
@@ -1376,11 +1506,12 @@ class GATv2(_LayerwiseInference, _AttentionModel):
     """GAT's shape with GATv2Conv layers: ``num_layers`` GATv2Conv(bias=False), ReLU + dropout 0.5 between layers,
     log_softmax.  Every hidden layer is ``heads`` heads of ``hidden_channels // heads`` channels, concatenated (the hidden
     width stays ``hidden_channels``, which must be a multiple of ``heads``); the last layer is the mean of its heads.
-    ``share_weights`` and ``attn_dropout`` are every conv's ``share_weights`` and ``dropout``."""
+    ``share_weights`` and ``attn_dropout`` are every conv's ``share_weights`` and ``dropout``; ``norm="layer"``
+    normalises every hidden layer with LayerNorm (``_AttentionModel``)."""
 
     def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, heads=1, share_weights=False,
-                 attn_dropout=0.0):
-        super().__init__(GATv2Conv, in_channels, hidden_channels, out_channels, num_layers, heads, bias=False,
+                 attn_dropout=0.0, norm=None):
+        super().__init__(GATv2Conv, in_channels, hidden_channels, out_channels, num_layers, heads, norm=norm, bias=False,
                          share_weights=share_weights, dropout=attn_dropout)
 
 
@@ -1537,7 +1668,8 @@ class GraphTransformer(_AttentionModel):
     ``hidden_channels // heads`` channels, concatenated (the hidden width stays ``hidden_channels``, which must be a
     multiple of ``heads``); the last layer is the mean of its heads.  ``beta`` and ``attn_dropout`` are every conv's
     ``beta`` and ``dropout``; with ``attn_dropout`` > 0 a training step stays on the HIP kernels (the mask is drawn
-    inside them, spp.h f4a), and eval mode and the layer-wise scoring below apply no dropout.
+    inside them, spp.h f4a), and eval mode and the layer-wise scoring below apply no dropout.  ``norm="layer"``
+    normalises every hidden layer with LayerNorm, as UniMP does (``_AttentionModel``).
 
     There is no ``inference`` method.  Exact layer-wise scoring over the resident graph is
     ``inference.layerwise_inference(model, ...)`` (``inference.evaluate`` for predictions and loss;
@@ -1545,10 +1677,11 @@ class GraphTransformer(_AttentionModel):
     evaluated batch-wise, through this forward on sampled batches in eval mode, as the reference evaluates its
     models."""
 
-    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, heads=1, beta=False, attn_dropout=0.0):
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, heads=1, beta=False, attn_dropout=0.0,
+                 norm=None):
         _check_heads(heads, bool_ok=False)
-        super().__init__(TransformerConv, in_channels, hidden_channels, out_channels, num_layers, heads, beta=beta,
-                         dropout=attn_dropout)
+        super().__init__(TransformerConv, in_channels, hidden_channels, out_channels, num_layers, heads, norm=norm,
+                         beta=beta, dropout=attn_dropout)
 
 
 # --------------------------------------------------------------------------------------------

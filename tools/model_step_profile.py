@@ -1,7 +1,7 @@
 """One resident batch of the bench workload, N optimisation steps of one of the models (models.get_model_type: SAGE, GAT,
 GIN, SAGEResInception; and models.GCN) on it (fwd + bwd + Adam), timed; run under `rocprofv3 --kernel-trace --stats` for the per-kernel
 table.
-usage: model_step_profile.py [sage|gat|gatv2|transformer|gin|sageresinception|gcn|pna] [steps=30] [workload=S-papers] [fused] [max] [norm] [reference] [--amp bf16] [--heads H] [attn=P]
+usage: model_step_profile.py [sage|gat|gatv2|transformer|gin|sageresinception|gcn|pna] [steps=30] [workload=S-papers] [fused] [max] [norm] [ln] [reference] [--amp bf16] [--heads H] [attn=P]
 norm: GCN built with normalize=True (gcn_norm's coefficients and the self term; the reference model's setting is False).
 max: SAGE built with aggr="max" (csrc/aggregate_max.hip, layer by layer) instead of the mean's fused stack.
 fused: GIN / SAGEResInception / GCN built with fused_norm=True (the BatchNorm tail on csrc/bn_act.hip).
@@ -14,7 +14,10 @@ kernels with the mask drawn inside them: spp.h f4a).  reference: the same model 
 models._transformer_reference, the plain-torch path (attn > 0: torch's own mask there), for the comparison of DESIGN
 section 7 f3y.
 pna: models.PNA (csrc/aggregate_stats.hip), delta = pna_delta of the workload's graph; with reference every layer's
-aggregation is sent to models._stats_reference (plain torch), for the comparison of DESIGN section 7 f4b."""
+aggregation is sent to models._stats_reference (plain torch), for the comparison of DESIGN section 7 f4b.
+ln: GAT / GATv2 / GraphTransformer built with norm="layer" (the LayerNorm tail on csrc/ln_act.hip).  ln reference: the same
+model with only that tail sent to the plain torch composition (LayerNorm, ReLU, dropout); the convs stay on their kernels,
+for the comparison of DESIGN section 7 f4f."""
 import contextlib
 import os
 import sys
@@ -51,7 +54,8 @@ fused = "fused" in argv
 use_max = "max" in argv
 norm = "norm" in argv
 reference = "reference" in argv
-argv = [a for a in argv if a not in ("fused", "max", "norm", "reference")]
+ln = "ln" in argv
+argv = [a for a in argv if a not in ("fused", "max", "norm", "reference", "ln")]
 arch = argv[0] if len(argv) > 0 else "sage"
 steps = int(argv[1]) if len(argv) > 1 else 30
 wl = make_workload(argv[2] if len(argv) > 2 else "S-papers", seed=1234, device=torch.device("cuda", 0))
@@ -69,9 +73,13 @@ if heads != 1 and arch not in ATTN:
     sys.exit("--heads: GAT, GATv2 and GraphTransformer only")
 if attn and arch not in ATTN:
     sys.exit("attn=: GAT, GATv2 and GraphTransformer only")
-if reference and arch not in ("transformer", "pna"):
-    sys.exit("reference: GraphTransformer and PNA only")
-if reference:
+if ln and arch not in ATTN:
+    sys.exit("ln: GAT, GATv2 and GraphTransformer only")
+if reference and not ln and arch not in ("transformer", "pna"):
+    sys.exit("reference: GraphTransformer and PNA only, or with ln")
+if reference and ln:
+    models._ln_kernels_read = lambda *a: False
+elif reference:
     models._transformer_kernels_read = models._stats_kernels_read = lambda *a: False
 if fused and arch not in ("gin", "sageresinception", "gcn"):
     sys.exit("fused: GIN, SAGEResInception and GCN only")
@@ -88,6 +96,8 @@ if fused:
     kw["fused_norm"] = True
 if norm:
     kw["normalize"] = True
+if ln:
+    kw["norm"] = "layer"
 if arch == "pna":
     kw["delta"] = models.pna_delta(wl.rowptr)
 model = (GCN if arch == "gcn" else get_model_type(arch))(wl.x.size(1), 256, 47, 3, **kw).to(dev)
@@ -117,5 +127,5 @@ for _ in range(steps):
     loss = step()
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / steps
-print(f"MODEL_STEP {arch}{' aggr=max' if use_max else ''}{' normalize' if norm else ''}{f' heads={heads}' if heads != 1 else ''}{f' attn={attn:g}' if attn else ''}{' fused_norm' if fused else ''}{' reference-path' if reference else ''}{' amp=' + amp if amp else ''} {dt * 1e3:.3f} ms/step on a resident batch: {batch.x.size(0)} nodes, "
+print(f"MODEL_STEP {arch}{' aggr=max' if use_max else ''}{' normalize' if norm else ''}{f' heads={heads}' if heads != 1 else ''}{f' attn={attn:g}' if attn else ''}{' fused_norm' if fused else ''}{' norm=layer' if ln else ''}{' reference-path' if reference else ''}{' amp=' + amp if amp else ''} {dt * 1e3:.3f} ms/step on a resident batch: {batch.x.size(0)} nodes, "
       f"{[int(a.adj_t.nnz()) for a in batch.adjs]} edges, (S, T) {[tuple(int(v) for v in a.size) for a in batch.adjs]}, loss {float(loss):.4f}", flush=True)
