@@ -2333,6 +2333,74 @@ int64_t spp_ln_act_workspace_bytes(int64_t n, int64_t C);
 spp_status spp_ln_act_forward(const spp_ln_act_desc* desc, void* stream);
 spp_status spp_ln_act_backward(const spp_ln_act_desc* desc, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * f4g  The residual gated graph convolution (Bresson & Laurent, "Residual Gated Graph ConvNets"; PyG's
+ *      ResGatedGraphConv; the GatedGCN of the benchmarking papers) over an MFG hop, on rows the caller has projected:
+ *        k [T, D] = lin_key(x_target)     q [S, D] = lin_query(x)     v [S, D] = lin_value(x)
+ *        s_ij[c]  = sigmoid(k[i,c] + q[j,c]) = 1 / (1 + expf(-(k[i,c] + q[j,c])))         a gate per entry AND column
+ *        out[i,c] = sum_{j in row i} s_ij[c] * v[j,c]
+ *      Row i runs over ALL its CSR entries, in CSR order: no self loop is added, diagonal entries are kept, a repeated
+ *      entry counts as often as it appears (PyG's layer).  A target without entries gets zeros.  There is no softmax and
+ *      no head: every column stands alone, so any width D % 4 == 0, 4 <= D <= 1024, is served.
+ *
+ *   Layouts: k, q and v are rows of x_elem (SPP_ELEM_F32 / _F16 / _BF16, one code for the three) with unit column
+ *   stride, each with its own base pointer and row stride in elements: q and v may be the two halves of one [S, 2 D]
+ *   matrix (v = q + D, both strides 2 D) or separate matrices.  Rows are aligned to 4 elements (base and stride).  out,
+ *   grad_out, grad_k [T, D] and grad_q, grad_v [S, D] are fp32, dense, row-major, 16-byte aligned; rowptr and col int64.
+ *   A 16-bit value is read as its fp32 value; all arithmetic is fp32.
+ *
+ *   spp_resgated_forward writes out.  One lane group per target keeps k_i in registers and walks the row; the fp32
+ *   gate and v enter an fp64 accumulator (acc = fma(s, v, acc) from 0, in CSR order) that is rounded to fp32 once: a
+ *   target's bits depend on its row alone, neither on T nor on the launch.  The backward's sums are formed alike.
+ *   spp_resgated_backward reads grad_out (g) and recomputes every gate by the forward's own expression; no [E, D]
+ *   array exists in either direction, and there is no atomic:
+ *        grad_k[i,c] = sum_{j in row i}  (g[i,c] * v[j,c]) * (s (1 - s))      CSR order; written for every target
+ *        grad_v[j,c] = sum_{i names j}   g[i,c] * s                           over source j's entries in ascending CSR
+ *        grad_q[j,c] = sum_{i names j}   (g[i,c] * v[j,c]) * (s (1 - s))      position; written for EVERY source, zeros
+ *                                                                             for one no row names: the caller zeroes
+ *                                                                             nothing
+ *      The source side gathers over the transposed hop, built in the caller's workspace of
+ *      spp_resgated_workspace_bytes(T, S, E) bytes (16-byte aligned; its contents mean nothing between calls; -1 for
+ *      sizes the entries refuse).  grad_q and grad_v NULL TOGETHER: not wanted, the transposed hop is not built and no
+ *      workspace is needed.  Every sum has one order: two calls on the same input give the same bits.
+ *   The entries enqueue their launches on `stream` and never wait for the device.
+ *
+ *   Refused with SPP_ERR_INVALID before anything is enqueued, checked in this order, in a message that names the entry:
+ *   a NULL descriptor; an unknown x_elem (fp8 included); D outside [4, 1024] or D % 4 != 0; T < 0, S < T or E < 0; S or
+ *   E >= 2^31;  -- T == 0 returns SPP_OK here: no pointer is looked at, nothing is enqueued or written --  a row stride
+ *   below D or not a multiple of 4; a NULL rowptr, k, q or v, or col with E > 0; forward: a NULL out; backward: a NULL
+ *   grad_out or grad_k, exactly one of grad_q / grad_v NULL, a NULL workspace when they are wanted; then a misaligned
+ *   buffer, and a workspace that is misaligned or too small.  E == 0 with T > 0 writes zeros.  SPP_ABI_VERSION stays 6.
+ *   Not built: edge features (PyG's edge_dim), an activation other than the sigmoid, rows of the resident graph.
+ * ------------------------------------------------------------------------- */
+typedef struct spp_resgated_desc {
+  int32_t x_elem;             /* k, q and v: SPP_ELEM_F32 / _F16 / _BF16 */
+  int32_t reserved;
+  const int64_t* rowptr_dev;
+  const int64_t* col_dev;
+  int64_t num_targets;        /* T */
+  int64_t num_sources;        /* S >= T */
+  int64_t num_edges;          /* E = rowptr[T] */
+  int64_t D;                  /* columns */
+  const void* k_dev;          /* [T, D] */
+  int64_t k_stride_elems;
+  const void* q_dev;          /* [S, D] */
+  int64_t q_stride_elems;
+  const void* v_dev;          /* [S, D]; may be q_dev + D of one [S, 2 D] matrix */
+  int64_t v_stride_elems;
+  float* out_dev;             /* forward: fp32 [T, D] */
+  const float* grad_out_dev;  /* backward: fp32 [T, D] */
+  float* grad_k_dev;          /* backward: fp32 [T, D] */
+  float* grad_q_dev;          /* backward: fp32 [S, D]; NULL together with grad_v_dev: not wanted */
+  float* grad_v_dev;          /* backward: fp32 [S, D] */
+  void* workspace_dev;        /* backward, when grad_q / grad_v are wanted */
+  int64_t workspace_bytes;
+} spp_resgated_desc;
+
+int64_t spp_resgated_workspace_bytes(int64_t num_targets, int64_t num_sources, int64_t num_edges);
+spp_status spp_resgated_forward(const spp_resgated_desc* desc, void* stream);
+spp_status spp_resgated_backward(const spp_resgated_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,14 @@ class TransformerDesc(C.Structure):
                 ("grad_k_dev", p), ("grad_v_dev", p)]
 
 
+class ResGatedDesc(C.Structure):
+    """spp_resgated_desc: ResGatedGraphConv over a hop on projected rows k [T, D], q and v [S, D]; forward and backward"""
+    _fields_ = [("x_elem", i32), ("reserved", i32), ("rowptr_dev", p), ("col_dev", p), ("num_targets", i64),
+                ("num_sources", i64), ("num_edges", i64), ("D", i64), ("k_dev", p), ("k_stride_elems", i64), ("q_dev", p),
+                ("q_stride_elems", i64), ("v_dev", p), ("v_stride_elems", i64), ("out_dev", p), ("grad_out_dev", p),
+                ("grad_k_dev", p), ("grad_q_dev", p), ("grad_v_dev", p), ("workspace_dev", p), ("workspace_bytes", i64)]
+
+
 class GcnDinvDesc(C.Structure):
     """spp_gcn_dinv_desc: gcn_norm's first pass alone, dinv [num_nodes] over a whole graph"""
     _fields_ = [("fill", i32), ("reserved", i32), ("rowptr_dev", p), ("num_nodes", i64), ("w_dev", p), ("dinv_dev", p)]
@@ -473,6 +481,10 @@ SIGNATURES = {
     "spp_agg_stats_backward": (C.c_int, [C.POINTER(AggStatsDesc), p]),
     # the same four statistics over rows of the resident graph (spp.h f4e)
     "spp_graph_agg_stats_forward": (C.c_int, [C.POINTER(GraphAggStatsDesc), p, i64, p]),
+    # ResGatedGraphConv over a hop (spp.h f4g)
+    "spp_resgated_workspace_bytes": (i64, [i64, i64, i64]),
+    "spp_resgated_forward": (C.c_int, [C.POINTER(ResGatedDesc), p]),
+    "spp_resgated_backward": (C.c_int, [C.POINTER(ResGatedDesc), p]),
 }
 SPP_COMM_ID_BYTES = 128
 SPP_IPC_HANDLE_BYTES = 64

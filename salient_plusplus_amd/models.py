@@ -1685,6 +1685,178 @@ class GraphTransformer(_AttentionModel):
 
 
 # --------------------------------------------------------------------------------------------
+# ResGated  (PyG's ResGatedGraphConv, a sigmoid gate per entry and column: csrc/resgated.hip, spp.h f4g)
+# --------------------------------------------------------------------------------------------
+def _resgated_reference(k, q, v, rowptr, col):
+    """ResGatedGraphConv's message passing in plain torch ops, on the projected rows: k [T, D] = lin_key(x_target),
+    q [S, D] = lin_query(x), v [S, D] = lin_value(x) -> out [T, D] (fp32; float64 for float64 rows):
+    out[i] = sum_j sigmoid(k[i] + q[j]) * v[j] over ALL CSR entries of row i -- no self loop, diagonal entries kept, a
+    repeated entry counted as often as it appears -- and zeros for a row without entries.  The path for everything the
+    kernels do not read: CPU tensors, other dtypes, D % 4 != 0, D > 1024, misaligned or strided rows."""
+    T = k.size(0)
+    dt = torch.float64 if k.dtype == torch.float64 else torch.float32
+    k, q, v = k.to(dt), q.to(dt), v.to(dt)
+    dst = torch.repeat_interleave(torch.arange(T, device=col.device), rowptr[1:] - rowptr[:-1])
+    msg = torch.sigmoid(k[dst] + q[col]) * v[col]                           # [E, D]
+    return torch.zeros((T, k.size(1)), dtype=dt, device=k.device).index_add_(0, dst, msg)
+
+
+def _resgated_kernels_read(k, q, v):
+    """the rows the ResGated kernel pair accepts (spp.h f4g): CUDA matrices of one fp32 / fp16 / bf16 dtype with unit
+    column stride and rows aligned to 4 elements, D % 4 == 0 and 4 <= D <= 1024"""
+    D = k.size(1) if k.dim() == 2 else 0
+    return (k.is_cuda and k.dtype in _ELEM and D % 4 == 0 and 4 <= D <= 1024 and
+            all(t.dtype == k.dtype and t.dim() == 2 and t.size(1) == D and t.stride(1) == 1 and t.stride(0) % 4 == 0 and
+                t.data_ptr() % (4 * t.element_size()) == 0 for t in (k, q, v)))
+
+
+def _resgated_desc(k, q, v, rowptr, col, **bufs):
+    """spp_resgated_desc for projected rows k [T, D], q and v [S, D] (unit column stride, one dtype)"""
+    (T, D), S = k.shape, q.size(0)
+    return nat.ResGatedDesc(x_elem=_ELEM[k.dtype], rowptr_dev=_p(rowptr), col_dev=_p(col), num_targets=T, num_sources=S,
+                            num_edges=col.numel(), D=D, k_dev=_p(k), k_stride_elems=k.stride(0) if T > 1 else D,
+                            q_dev=_p(q), q_stride_elems=q.stride(0) if S > 1 else D, v_dev=_p(v),
+                            v_stride_elems=v.stride(0) if S > 1 else D,
+                            **{n: _p(t) for n, t in bufs.items() if t is not None})
+
+
+class _ResGatedLayer(torch.autograd.Function):
+    """ResGatedGraphConv's message passing as ONE node on the projected rows: (k [T, D], q [S, D], v [S, D]) -> out
+    [T, D] fp32, spp_resgated_forward / spp_resgated_backward.  The rows are fp32, fp16 or bf16 (under bf16 autocast the
+    projections outside the node give bf16 rows, which the kernels read as such); q and v may be views of one [S, 2 D]
+    matrix.  The node runs with autocast off, returns fp32 and casts the gradients back to the rows' dtype.  The backward
+    holds no atomic: grad_q and grad_v are gathered over the transposed hop (only if q or v needs a gradient), so a
+    training step gives the same bits twice."""
+
+    @staticmethod
+    def forward(ctx, k, q, v, rowptr, col):
+        with _no_autocast():
+            nat.require_device()
+            out = torch.empty(k.shape, dtype=torch.float32, device=k.device)
+            d = _resgated_desc(k, q, v, rowptr, col, out_dev=out)
+            nat.check(nat.load().spp_resgated_forward(C.byref(d), _stream()))
+            ctx.save_for_backward(k, q, v, rowptr, col)
+            return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        with _no_autocast():
+            k, q, v, rowptr, col = ctx.saved_tensors
+            (T, D), S, E = k.shape, q.size(0), col.numel()
+            L = nat.load()
+            g = g.to(torch.float32).contiguous()
+            f32 = dict(dtype=torch.float32, device=k.device)
+            sources = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+            g_k = torch.empty((T, D), **f32)
+            # (T == 0: the entry touches nothing, and no row names a source)
+            new = torch.empty if T else torch.zeros
+            g_q, g_v = (new((S, D), **f32), new((S, D), **f32)) if sources else (None, None)
+            nbytes = int(L.spp_resgated_workspace_bytes(T, S, E)) if sources else 0
+            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=k.device) if sources else None
+            d = _resgated_desc(k, q, v, rowptr, col, grad_out_dev=g, grad_k_dev=g_k, grad_q_dev=g_q, grad_v_dev=g_v,
+                               workspace_dev=ws)
+            d.workspace_bytes = nbytes
+            nat.check(L.spp_resgated_backward(C.byref(d), _stream()))
+            return (_grad_back(g_k, k, ctx.needs_input_grad[0]), _grad_back(g_q, q, ctx.needs_input_grad[1]),
+                    _grad_back(g_v, v, ctx.needs_input_grad[2]), None, None)
+
+
+class ResGatedGraphConv(torch.nn.Module):
+    """torch_geometric.nn.ResGatedGraphConv(in, out, act=Sigmoid(), edge_dim=None, root_weight=True, bias=True) (Bresson &
+    Laurent, "Residual Gated Graph ConvNets") on a bipartite ((x, x_target), adj_t), with PyG's parameter names (a PyG
+    state dict loads): lin_key, lin_query, lin_value, each [out, in] with a bias; with ``root_weight`` lin_skip [out, in]
+    without one; ``bias`` [out].
+
+        k = lin_key(x_target) [T, D],  q = lin_query(x) [S, D],  v = lin_value(x) [S, D]
+        out[i] = sum_j sigmoid(k[i] + q[j]) * v[j]  (+ lin_skip(x_target) + bias)
+
+    over ALL entries of row i as adj_t has them: no self loop is added, diagonal entries stay, a repeated entry counts as
+    often as it appears, and a target without entries gets zeros.  q and v come from ONE GEMM over the concatenated
+    weights (two views of its [S, 2 D] result); the projections and the skip are plain torch; the message passing is
+    _ResGatedLayer (csrc/resgated.hip) for CUDA rows of a width D % 4 == 0, 4 <= D <= 1024, and _resgated_reference, the
+    same function in plain torch ops, for everything else.  ``act`` is None (the sigmoid) only; ``edge_dim`` other than
+    None (edge features) is not built: NotImplementedError."""
+
+    def __init__(self, in_channels, out_channels, act=None, edge_dim=None, root_weight=True, bias=True):
+        super().__init__()
+        if edge_dim is not None:
+            raise NotImplementedError("ResGatedGraphConv: edge features (edge_dim) are not built; use edge_dim=None")
+        if act is not None:
+            raise NotImplementedError(f"ResGatedGraphConv: the gate is the sigmoid (act=None); act={act!r} is not built")
+        self.in_channels, self.out_channels, self.root_weight = in_channels, out_channels, bool(root_weight)
+        self.lin_key = torch.nn.Linear(in_channels, out_channels)
+        self.lin_query = torch.nn.Linear(in_channels, out_channels)
+        self.lin_value = torch.nn.Linear(in_channels, out_channels)
+        self.lin_skip = torch.nn.Linear(in_channels, out_channels, bias=False) if self.root_weight else None
+        self.bias = torch.nn.Parameter(torch.zeros(out_channels)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for lin in (self.lin_key, self.lin_query, self.lin_value, self.lin_skip):      # PyG: each Linear's own
+            if lin is not None:
+                lin.reset_parameters()
+        if self.bias is not None:
+            torch.nn.init.zeros_(self.bias)
+
+    def forward(self, x_pair, adj_t):
+        x, x_target = x_pair
+        rowptr, col, _ = adj_t.csr()
+        D = self.out_channels
+        if not torch.is_autocast_enabled(x.device.type):        # (autocast casts the GEMM's operands itself)
+            x, x_target = x.to(self.lin_query.weight.dtype), x_target.to(self.lin_key.weight.dtype)
+        k = self.lin_key(x_target)
+        qv = F.linear(x, torch.cat([self.lin_query.weight, self.lin_value.weight]),
+                      torch.cat([self.lin_query.bias, self.lin_value.bias]))
+        q, v = qv[:, :D], qv[:, D:]
+        layer = _ResGatedLayer.apply if _resgated_kernels_read(k, q, v) else _resgated_reference
+        out = layer(k, q, v, rowptr, col)
+        if self.root_weight:
+            out = out + self.lin_skip(x_target)
+        return out if self.bias is None else out + self.bias
+
+
+class ResGated(_ConvModel):
+    """``num_layers`` ResGatedGraphConv, each but the last followed by BatchNorm1d, ReLU and dropout (0.5), then
+    log_softmax: GCN's scaffold.  ``fused_norm=True`` runs each tail as ``batch_norm_act(act="relu", p=dropout)`` (same
+    modules, same state dict).  The model has no ``inference`` method, and the layer-wise entries of ``inference`` refuse
+    it by name (the kernel over rows of the resident graph is not built); evaluate it batch-wise, through this forward
+    on sampled batches in eval mode, as the reference evaluates its models."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, *, dropout=0.5, fused_norm=False):
+        super().__init__()
+        self.num_layers = num_layers
+        self.hidden_channels = hidden_channels
+        self.dropout = dropout
+        self.fused_norm = fused_norm
+        self.convs = torch.nn.ModuleList()
+        self.bns = torch.nn.ModuleList()
+        for i in range(num_layers):
+            self.convs.append(ResGatedGraphConv(in_channels if i == 0 else hidden_channels,
+                                                out_channels if i == num_layers - 1 else hidden_channels))
+            if i != num_layers - 1:
+                self.bns.append(torch.nn.BatchNorm1d(hidden_channels))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        super().reset_parameters()
+        for bn in self.bns:
+            bn.reset_parameters()
+
+    def forward(self, x, adjs):
+        if isinstance(x, (TableRows, RowRefs)):          # the rows are projected first: nothing reads the table in place
+            x = x.materialize()
+        for i, (adj_t, _e_id, size) in enumerate(adjs):
+            x = self.convs[i]((x, x[:size[1]]), adj_t)
+            if i != self.num_layers - 1:
+                if self.fused_norm:
+                    x = batch_norm_act(x, self.bns[i], act="relu", p=self.dropout)
+                else:
+                    x = F.dropout(F.relu(self.bns[i](x)), p=self.dropout, training=self.training)
+        return torch.log_softmax(x, dim=-1)
+
+
+# --------------------------------------------------------------------------------------------
 # GIN  (driver/models.py:234-283: GINConv(Sequential(Linear, BatchNorm1d, ReLU, Linear, ReLU)), eps = 0)
 # --------------------------------------------------------------------------------------------
 _SUM_GATHER_MIN_WORK = _GATHER_MIN_WORK     # (the name the sum's tests know it by)
@@ -2454,11 +2626,11 @@ _UNSUPPORTED_MODELS = {"sageclassic": "not used in the paper", "jknet": "not use
 
 def get_model_type(model_name):
     """driver/main.py:74-95 for the four models the reference marks as working (names case-insensitive), "gcn" (GCN,
-    which the reference leaves unused), "gatv2" (GATv2), "transformer" (GraphTransformer) and "pna" (PNA), which the
-    reference does not have"""
+    which the reference leaves unused), "gatv2" (GATv2), "transformer" (GraphTransformer), "pna" (PNA) and "resgated" (ResGated),
+    which the reference does not have"""
     name = model_name.lower()
     models = {"sage": SAGE, "gat": GAT, "gin": GIN, "sageresinception": SAGEResInception, "gcn": GCN, "gatv2": GATv2,
-              "transformer": GraphTransformer, "pna": PNA}
+              "transformer": GraphTransformer, "pna": PNA, "resgated": ResGated}
     if name in models:
         return models[name]
     if name in _UNSUPPORTED_MODELS:

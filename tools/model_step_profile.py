@@ -1,7 +1,7 @@
 """One resident batch of the bench workload, N optimisation steps of one of the models (models.get_model_type: SAGE, GAT,
 GIN, SAGEResInception; and models.GCN) on it (fwd + bwd + Adam), timed; run under `rocprofv3 --kernel-trace --stats` for the per-kernel
 table.
-usage: model_step_profile.py [sage|gat|gatv2|transformer|gin|sageresinception|gcn|pna] [steps=30] [workload=S-papers] [fused] [max] [norm] [ln] [reference] [--amp bf16] [--heads H] [attn=P]
+usage: model_step_profile.py [sage|gat|gatv2|transformer|gin|sageresinception|gcn|pna|resgated] [steps=30] [workload=S-papers] [fused] [max] [norm] [ln] [reference] [--amp bf16] [--heads H] [attn=P]
 norm: GCN built with normalize=True (gcn_norm's coefficients and the self term; the reference model's setting is False).
 max: SAGE built with aggr="max" (csrc/aggregate_max.hip, layer by layer) instead of the mean's fused stack.
 fused: GIN / SAGEResInception / GCN built with fused_norm=True (the BatchNorm tail on csrc/bn_act.hip).
@@ -15,6 +15,8 @@ models._transformer_reference, the plain-torch path (attn > 0: torch's own mask 
 section 7 f3y.
 pna: models.PNA (csrc/aggregate_stats.hip), delta = pna_delta of the workload's graph; with reference every layer's
 aggregation is sent to models._stats_reference (plain torch), for the comparison of DESIGN section 7 f4b.
+resgated: models.ResGated (csrc/resgated.hip), with fused as GCN; with reference every layer's message passing is sent to
+models._resgated_reference (plain torch: three [E, D] arrays per direction), for the comparison of DESIGN section 7 f4g.
 ln: GAT / GATv2 / GraphTransformer built with norm="layer" (the LayerNorm tail on csrc/ln_act.hip).  ln reference: the same
 model with only that tail sent to the plain torch composition (LayerNorm, ReLU, dropout); the convs stay on their kernels,
 for the comparison of DESIGN section 7 f4f."""
@@ -75,14 +77,14 @@ if attn and arch not in ATTN:
     sys.exit("attn=: GAT, GATv2 and GraphTransformer only")
 if ln and arch not in ATTN:
     sys.exit("ln: GAT, GATv2 and GraphTransformer only")
-if reference and not ln and arch not in ("transformer", "pna"):
-    sys.exit("reference: GraphTransformer and PNA only, or with ln")
+if reference and not ln and arch not in ("transformer", "pna", "resgated"):
+    sys.exit("reference: GraphTransformer, PNA and ResGated only, or with ln")
 if reference and ln:
     models._ln_kernels_read = lambda *a: False
 elif reference:
-    models._transformer_kernels_read = models._stats_kernels_read = lambda *a: False
-if fused and arch not in ("gin", "sageresinception", "gcn"):
-    sys.exit("fused: GIN, SAGEResInception and GCN only")
+    models._transformer_kernels_read = models._stats_kernels_read = models._resgated_kernels_read = lambda *a: False
+if fused and arch not in ("gin", "sageresinception", "gcn", "resgated"):
+    sys.exit("fused: GIN, SAGEResInception, GCN and ResGated only")
 if norm and arch != "gcn":
     sys.exit("norm: GCN only")
 if use_max and arch != "sage":
